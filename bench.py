@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- hash-join build+probe throughput on MI355X (the BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 30] [--dist uniform]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 30] [--dist uniform] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes of itself
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per GPU) BEFORE it touches the GPU in any way, waits for them and
@@ -20,9 +20,19 @@ by key radix with one all-to-all per relation over RCCL and joined locally
 (htm_hashjoin_amd/sharded.py).
 
 Rank 0 prints ONE JSON line. `value` = (|R|+|S|) summed over all ranks / max-over-ranks
-time, in Mtuples/s. Extra objects: `roofline` (dominant kernel, HIP-event timed on the
-launch stream), `cpu_baseline` (the oracle's threaded port on a bounded sample, rank 0,
-N=1 only), `other_workloads` (local_shuffle and PRJ measured in the same process).
+time, in Mtuples/s; `ms_per_step` = that time / K. A plain run does only what `value` needs:
+set up, W untimed steps, K timed steps, the line. `--full` adds everything else, measured after
+the timed steps: `result` (counters and checks), `roofline` (dominant kernel, HIP-event timed
+on the launch stream over a few extra steps), `cpu_baseline` (the oracle's threaded port on a
+bounded sample, rank 0, N=1 only), `other_workloads` (local_shuffle and PRJ measured in the same
+process); for N > 1 the phase split and the other exchange split.
+
+`--dump-outputs DIR` (N=1): after the K timed steps, what the last one computed, as float64 .npy files --
+  result_counts.npy        [conflicts, totalMatches]
+  result_sums_hi_lo.npy    rows inputSum, tableSumFull, conflictSum, outputSum; columns (value >> 32, value & (2^32-1))
+  table_sample.npy         the table in the reference's format (key, 0 = empty) at table_sample_index.npy, a fixed
+                           seeded sample of at most 2^20 slots (the whole table when it is smaller)
+The inputs are a function of the arguments alone (DataGen's srand(0) stream, S = 1..|S|).
 """
 import argparse
 import json
@@ -34,6 +44,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak, MI355X_MICROARCH.md "Chip-level parameters"
+DUMP_SEED = 20240601     # --dump-outputs: the table sample is drawn by this seed ...
+DUMP_TABLE_SLOTS = 1 << 20   # ... and holds at most this many slots (8 MiB of float64, twice with its index)
 
 
 def parse():
@@ -41,19 +53,24 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (= ranks) of this node; default: WORLD_SIZE if a launcher set it, else 1. N > 1 without "
                          "WORLD_SIZE: bench.py starts the N ranks itself")
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (exactly this many)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (result checks, roofline, CPU "
+                         "baselines, other workloads; N > 1: phase split and other split); off = the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/*.npy (float64; N=1 only)")
     ap.add_argument("--log2n", type=int, default=30, help="per-GPU |R| = |S| = 2^log2n")
     ap.add_argument("--dist", default="uniform")
     ap.add_argument("--shuffle-range", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other_workloads legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the other_workloads legs")
     ap.add_argument("--cpu-sample-log2n", type=int, default=27)
     ap.add_argument("--build-variant", type=int, default=0,
                     help="0 auto, 1 global atomics, 2 workgroup LDS window, 3 wavefront LDS rings")
     ap.add_argument("--strong", action="store_true", help="N>1: split the N=1 total instead of 2^log2n per GPU")
     ap.add_argument("--no-other-split", action="store_true",
-                    help="N>1: skip the few extra steps with the split that was NOT chosen (reported as other_split)")
+                    help="N>1 --full: skip the few extra steps with the split that was NOT chosen (reported as other_split)")
     ap.add_argument("--split", default="low", choices=["auto", "low", "high"],
                     help="N>1: destination = low key bits (default: BASELINE config 4's all-to-all, (G-1)/G of the tuples "
                          "cross xGMI), high key bits (range split), or auto = high when >= 3/4 of every rank's tuples stay "
@@ -69,6 +86,10 @@ def parse():
         a.gpus = int(env_world) if env_world else 1
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and (a.gpus > 1 or os.environ.get("HJ_BENCH_FORCE_SHARDED") == "1"):
+        ap.error("--dump-outputs is implemented for the single-GPU path (--gpus 1)")
     return a
 
 
@@ -127,9 +148,31 @@ def time_steps(torch, dist_mod, world, fn, steps, warmup):
     return dt
 
 
-def oa_leg(torch, hj, ctx, n, dist, window, steps, warmup, S_dev=None, variant=0, keep=None):
+def dump_oa_outputs(ctx, out_dir):
+    """--dump-outputs: what the last build+probe left in `ctx` (counters, table sums, a seeded sample of the table), as
+    float64 .npy files (module docstring). Untimed; the table sums are the library's own reductions (hj_checksums_dev)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ctx.checksums()
+    r = ctx.fetch()
+    np.save(os.path.join(out_dir, "result_counts.npy"), np.array([r["conflicts"], r["totalMatches"]], dtype=np.float64))
+    sums = [r[k] for k in ("inputSum", "tableSumFull", "conflictSum", "outputSum")]
+    np.save(os.path.join(out_dir, "result_sums_hi_lo.npy"),
+            np.array([[v >> 32, v & 0xFFFFFFFF] for v in sums], dtype=np.float64))
+    table = ctx.export_table(r["tableSize"])
+    if table.size <= DUMP_TABLE_SLOTS:
+        idx = np.arange(table.size, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, table.size, DUMP_TABLE_SLOTS, dtype=np.int64))
+    np.save(os.path.join(out_dir, "table_sample.npy"), table[idx].astype(np.float64))     # keys < 2^32: exact
+    np.save(os.path.join(out_dir, "table_sample_index.npy"), idx.astype(np.float64))
+    del table
+
+
+def oa_leg(torch, hj, ctx, n, dist, window, steps, warmup, S_dev=None, variant=0, keep=None, full=True, dump_dir=None):
     """Open-addressing build+probe on one GPU. Returns (result dict, S_dev). keep: a list that receives the host R
-    (the CPU baseline joins the same relation afterwards)."""
+    (the CPU baseline joins the same relation afterwards). full: also per-kernel times and the counters and checks, from
+    steps after the timed ones; dump_dir: --dump-outputs of the last timed step."""
     R = hj.generate_data(dist, n, n, window)
     R_dev = to_device(R, torch, "cuda")
     if keep is not None:
@@ -145,6 +188,13 @@ def oa_leg(torch, hj, ctx, n, dist, window, steps, warmup, S_dev=None, variant=0
         ctx.probe(S_dev.data_ptr(), n)
 
     dt = time_steps(torch, None, 1, step, steps, warmup)
+    if dump_dir is not None:
+        dump_oa_outputs(ctx, dump_dir)
+    out = {"dist": dist, "shuffleRange": window, "rSize": n, "sSize": n,
+           "ms_per_step": dt / steps * 1e3, "mtuples_per_s": 2 * n / (dt / steps) / 1e6}
+    if not full:
+        del R_dev
+        return out, S_dev
     # per-kernel device times of the same launches, from HIP events on the launch stream
     for _ in range(min(steps, 5)):
         step()
@@ -154,10 +204,7 @@ def oa_leg(torch, hj, ctx, n, dist, window, steps, warmup, S_dev=None, variant=0
     ctx.checksums()
     res = ctx.fetch()
     avg = {k: sum(v) / len(v) for k, v in kernel_us.items()}
-    out = {
-        "dist": dist, "shuffleRange": window, "rSize": n, "sSize": n,
-        "ms_per_step": dt / steps * 1e3,
-        "mtuples_per_s": 2 * n / (dt / steps) / 1e6,
+    out.update({
         "kernel_us": avg,
         "conflicts": res["conflicts"], "totalMatches": res["totalMatches"], "inputSum": res["inputSum"],
         "buildVariant": res["buildVariant"], "buildDeferred": res["buildDeferred"], "compactFallback": res["compactFallback"],
@@ -165,7 +212,7 @@ def oa_leg(torch, hj, ctx, n, dist, window, steps, warmup, S_dev=None, variant=0
             "matches_plus_conflicts_eq_rSize": res["totalMatches"] + res["conflicts"] == n,
             "tableSum_plus_conflictSum_eq_inputSum": res["tableSumFull"] + res["conflictSum"] == res["inputSum"],
         },
-    }
+    })
     del R_dev
     return out, S_dev
 
@@ -369,6 +416,45 @@ def launch_ranks(n_ranks, argv):
     return rc
 
 
+def oa_roofline(main_leg, n, a):
+    # roofline of the dominant kernel (the build): algorithmic bytes = 16 B per R tuple
+    # (8 read + 8 slot write, SURVEY.md 8d), duration = HIP-event time of that launch
+    ku = main_leg["kernel_us"]
+    v2 = main_leg["buildVariant"] >= 2          # an LDS build (2: workgroup window, 3: wavefront rings, 4: rings + compact table): its kernel timed alone
+    # Dominant kernel = the build. Variant 2: k_build_own (phase A) timed alone by its own HIP events
+    # (hj_result.buildPhaseA_us); build_us additionally covers k_clear_unowned + k_build_deferred.
+    # Algorithmic bytes per launch (SURVEY.md 8d): build = R read 8 + slot write 8 = 16 B per R tuple;
+    # probe = S read 8 + home-slot read 8 = 16 B per S tuple; table clear = 16 B per R tuple (2|R| slots).
+    dom_name = {4: "k_build_wave<compact>", 3: "k_build_wave", 2: "k_build_own"}.get(main_leg["buildVariant"], "k_build_atomic_min")
+    dom_us = ku["buildPhaseA_us"] if v2 else ku["build_us"]
+    alg = 16.0 * n
+    achieved = alg / (dom_us * 1e-6) / 1e9
+    # HBM bytes per launch from rocprofv3 PMC passes of this very command -- only while the kernel sources are the ones
+    # the passes were taken on
+    traffic, traffic_note = committed_traffic(dom_name, a.log2n == 30 and a.dist == "uniform" and a.shuffle_range == 16)
+    # what the kernel moves by design: R read once (8 B) + every reachable slot written once -- 8 B per slot, or 4 B with
+    # the compact table (the index words that order the inserts stay in LDS); SURVEY.md 8d's algorithmic 16 B per tuple is
+    # what `achieved` is computed from either way
+    moved_model = (12.0 if main_leg["buildVariant"] == 4 else 16.0) * n
+    # Whole step in SURVEY.md 8d's accounting: 16 B per R tuple (read 8 + slot written 8) + 16 B per S tuple (read 8 +
+    # home slot 8) = 32 B per tuple pair. The table clear is NOT a separate 16 B: the LDS builds write every reachable
+    # slot exactly once, empties included (PMC round 1: build group 17.3 GB at 2^30, not 34 GB).
+    step_bytes = 32.0 * n
+    roofline = {"bound": "hbm", "kernel": dom_name,
+                "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                "traffic": traffic, "traffic_note": traffic_note,
+                "algorithmic_bytes_per_launch": alg, "bytes_moved_by_design_per_launch": moved_model, "launch_us": dom_us,
+                "other_kernels": {
+                    "build_group_us (seam/bounds pre-pass + LDS build kernel + edge/unowned clear + deferred phase)" if v2 else "k_fill_empty_us":
+                        ku["build_us"] if v2 else ku["clear_us"],
+                    "k_probe_us": ku["probe_us"], "k_probe_GBps": 16.0 * n / (ku["probe_us"] * 1e-6) / 1e9,
+                    "k_sample_locality_us (the pre-round decides on the device: no host read-back)": ku["clear_us"] if v2 else None},
+                "whole_step": {"algorithmic_bytes": step_bytes, "bytes_per_tuple_pair": 32,
+                               "GBps": step_bytes / (main_leg["ms_per_step"] * 1e-3) / 1e9,
+                               "frac": step_bytes / (main_leg["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}}
+    return roofline
+
+
 def main():
     a = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -429,44 +515,24 @@ def main():
 
     stream = torch.cuda.current_stream().cuda_stream
     ctx = hj.HashJoinContext(local_rank, stream=stream)
-    host_R = [] if not a.no_cpu_baseline else None
-    main_leg, S_dev = oa_leg(torch, hj, ctx, n, a.dist, a.shuffle_range, a.steps, a.warmup, variant=a.build_variant, keep=host_R)
-
-    # roofline of the dominant kernel (the build): algorithmic bytes = 16 B per R tuple
-    # (8 read + 8 slot write, SURVEY.md 8d), duration = HIP-event time of that launch
-    ku = main_leg["kernel_us"]
-    v2 = main_leg["buildVariant"] >= 2          # an LDS build (2: workgroup window, 3: wavefront rings, 4: rings + compact table): its kernel timed alone
-    # Dominant kernel = the build. Variant 2: k_build_own (phase A) timed alone by its own HIP events
-    # (hj_result.buildPhaseA_us); build_us additionally covers k_clear_unowned + k_build_deferred.
-    # Algorithmic bytes per launch (SURVEY.md 8d): build = R read 8 + slot write 8 = 16 B per R tuple;
-    # probe = S read 8 + home-slot read 8 = 16 B per S tuple; table clear = 16 B per R tuple (2|R| slots).
-    dom_name = {4: "k_build_wave<compact>", 3: "k_build_wave", 2: "k_build_own"}.get(main_leg["buildVariant"], "k_build_atomic_min")
-    dom_us = ku["buildPhaseA_us"] if v2 else ku["build_us"]
-    alg = 16.0 * n
-    achieved = alg / (dom_us * 1e-6) / 1e9
-    # HBM bytes per launch from rocprofv3 PMC passes of this very command -- only while the kernel sources are the ones
-    # the passes were taken on
-    traffic, traffic_note = committed_traffic(dom_name, a.log2n == 30 and a.dist == "uniform" and a.shuffle_range == 16)
-    # what the kernel moves by design: R read once (8 B) + every reachable slot written once -- 8 B per slot, or 4 B with
-    # the compact table (the index words that order the inserts stay in LDS); SURVEY.md 8d's algorithmic 16 B per tuple is
-    # what `achieved` is computed from either way
-    moved_model = (12.0 if main_leg["buildVariant"] == 4 else 16.0) * n
-    # Whole step in SURVEY.md 8d's accounting: 16 B per R tuple (read 8 + slot written 8) + 16 B per S tuple (read 8 +
-    # home slot 8) = 32 B per tuple pair. The table clear is NOT a separate 16 B: the LDS builds write every reachable
-    # slot exactly once, empties included (PMC round 1: build group 17.3 GB at 2^30, not 34 GB).
-    step_bytes = 32.0 * n
-    roofline = {"bound": "hbm", "kernel": dom_name,
-                "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                "traffic": traffic, "traffic_note": traffic_note,
-                "algorithmic_bytes_per_launch": alg, "bytes_moved_by_design_per_launch": moved_model, "launch_us": dom_us,
-                "other_kernels": {
-                    "build_group_us (seam/bounds pre-pass + LDS build kernel + edge/unowned clear + deferred phase)" if v2 else "k_fill_empty_us":
-                        ku["build_us"] if v2 else ku["clear_us"],
-                    "k_probe_us": ku["probe_us"], "k_probe_GBps": 16.0 * n / (ku["probe_us"] * 1e-6) / 1e9,
-                    "k_sample_locality_us (the pre-round decides on the device: no host read-back)": ku["clear_us"] if v2 else None},
-                "whole_step": {"algorithmic_bytes": step_bytes, "bytes_per_tuple_pair": 32,
-                               "GBps": step_bytes / (main_leg["ms_per_step"] * 1e-3) / 1e9,
-                               "frac": step_bytes / (main_leg["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}}
+    host_R = [] if a.full and not a.no_cpu_baseline else None
+    main_leg, S_dev = oa_leg(torch, hj, ctx, n, a.dist, a.shuffle_range, a.steps, a.warmup, variant=a.build_variant,
+                             keep=host_R, full=a.full, dump_dir=a.dump_outputs)
+    line = {
+        "metric": "Mtuples/sec build+probe, |R|=|S|=1B uint32, uniform vs local_shuffle",
+        "value": main_leg["mtuples_per_s"], "unit": "Mtuples/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": main_leg["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u64 tuples (u32 key), integer", "data": "synthetic (DataGen restatement, srand(0) glibc stream)",
+        "config": {"workload": f"open-addressing build+probe (atomic), |R|=|S|=2^{a.log2n}, dataDistr={a.dist} "
+                               f"W={a.shuffle_range}, S=sorted, probeLength=4, tableSize=2|R|; "
+                               "step = build (locality pre-round; every reachable slot written once, empties included: "
+                               "no separate table clear) + probe, inputs resident in HBM",
+                   "algo": "atomic", "rSize": n, "sSize": n, "dataDistr": a.dist, "shuffleRange": a.shuffle_range},
+    }
+    if not a.full:
+        ctx.close()
+        print(json.dumps(line), flush=True)
+        return
 
     extra = {}
     if not a.no_extra:
@@ -494,20 +560,11 @@ def main():
         del host_R
         cpu_prj = cpu_baseline_prj(min(a.cpu_sample_log2n, a.log2n))
 
-    line = {
-        "metric": "Mtuples/sec build+probe, |R|=|S|=1B uint32, uniform vs local_shuffle",
-        "value": main_leg["mtuples_per_s"], "unit": "Mtuples/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": main_leg["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u64 tuples (u32 key), integer", "data": "synthetic (DataGen restatement, srand(0) glibc stream)",
-        "config": {"workload": f"open-addressing build+probe (atomic), |R|=|S|=2^{a.log2n}, dataDistr={a.dist} "
-                               f"W={a.shuffle_range}, S=sorted, probeLength=4, tableSize=2|R|; "
-                               "step = build (locality pre-round; every reachable slot written once, empties included: "
-                               "no separate table clear) + probe, inputs resident in HBM",
-                   "algo": "atomic", "rSize": n, "sSize": n, "dataDistr": a.dist, "shuffleRange": a.shuffle_range},
+    line.update({
         "result": {k: main_leg[k] for k in ("conflicts", "totalMatches", "inputSum", "buildVariant",
                                             "buildDeferred", "compactFallback", "checks")},
-        "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_prj": cpu_prj, "other_workloads": extra,
-    }
+        "roofline": oa_roofline(main_leg, n, a), "cpu_baseline": cpu, "cpu_baseline_prj": cpu_prj, "other_workloads": extra,
+    })
     print(json.dumps(line), flush=True)
 
 

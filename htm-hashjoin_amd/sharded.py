@@ -491,7 +491,7 @@ def bench_sharded(args, torch, dist, hj, rank, world, local_rank, engine=None, d
     joining in place, is timed for a few steps beside it and reported as `other_split` -- it says what exploiting the
     data's locality in the exchange is worth, it is not the config-4 number. `phase_ms` / `exchange_ms` / `local_ms`
     come from extra steps whose phases run one after the other (step_phases): exchange and local time separately, as
-    SURVEY.md 8e asks.
+    SURVEY.md 8e asks. Both come after the timed steps and only with --full (null otherwise).
 
     Globally the relation is the near-sorted one the reference generates, cut into contiguous pieces: rank g's
     piece = DataGen over its own key range, drawn piecewise (a rank cannot afford the serial rand() stream of its
@@ -558,8 +558,9 @@ def bench_sharded(args, torch, dist, hj, rank, world, local_rank, engine=None, d
     res = job.result()
     total = 2 * n * world
     # exchange and local time separately: a few steps with the phases run one after the other, maximum over ranks
+    full = getattr(args, "full", False)
     phase_ms = None
-    if world > 1 and "in place" not in res["exchange"]["split"]:
+    if full and world > 1 and "in place" not in res["exchange"]["split"]:
         pj = new_job(args.split)
         runs = [pj.step_phases(r_local, s_local, table_size) for _ in range(3)][1:]      # the first one warms up
         names = list(runs[0])
@@ -568,7 +569,7 @@ def bench_sharded(args, torch, dist, hj, rank, world, local_rank, engine=None, d
         phase_ms = dict(zip(names, (float(x) for x in t.tolist())))
     # the same join with the other split, a few steps, for the record (never part of `value`)
     alt = None
-    if world > 1 and not getattr(args, "no_other_split", False):
+    if full and world > 1 and not getattr(args, "no_other_split", False):
         other = "auto" if job.mode == 0 else "low"
         k = max(1, min(3, args.steps))
         ajob, adt = timed(other, k, 1)

@@ -3,7 +3,9 @@
 # DataGen under -fsanitize=address,undefined, exercised through small C/C++ drivers.
 set -e
 cd "$(dirname "$0")/.."
-cat > /tmp/san_oracle.c <<'C'
+T=$(mktemp -d)
+trap 'rm -rf "$T"' EXIT
+cat > $T/san_oracle.c <<'C'
 #include "hj_oracle.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,9 +31,9 @@ int main(void) {
     return 0;
 }
 C
-gcc -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Ioracle /tmp/san_oracle.c oracle/hj_oracle.c -o /tmp/san_oracle -lpthread -lm
-/tmp/san_oracle
-cat > /tmp/san_datagen.cpp <<'C'
+gcc -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Ioracle $T/san_oracle.c oracle/hj_oracle.c -o $T/san_oracle -lpthread -lm
+$T/san_oracle
+cat > $T/san_datagen.cpp <<'C'
 #include "include/htm_hashjoin.h"
 #include <cstdio>
 #include <vector>
@@ -47,5 +49,5 @@ int main() {
     return 0;
 }
 C
-g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I. /tmp/san_datagen.cpp htm-hashjoin_amd/csrc/hj_datagen.cpp -o /tmp/san_datagen -lpthread
-/tmp/san_datagen
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I. $T/san_datagen.cpp htm-hashjoin_amd/csrc/hj_datagen.cpp -o $T/san_datagen -lpthread
+$T/san_datagen

@@ -19,8 +19,16 @@ def test_bench_refuses_to_run_without_a_gpu():
 
 def test_bench_accepts_the_driver_flags():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps is the number of timed steps and ms_per_step is divided by it: 0 is an error, not a line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0",
+                        "--log2n", "10"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and r.stdout.strip() == ""
+    assert "--steps must be >= 1" in r.stderr
 
 
 def test_sharded_helpers():

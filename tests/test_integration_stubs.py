@@ -1,7 +1,7 @@
 """INTEGRATION.md's reference-side stubs go through a compiler: `HipHashBuild.hpp` (with ENABLE_PROBE 0 and 1, as the
 reference's config.h switches it) is compiled AND linked against libhtmjoin_hip.so, and `HIP_PRO` is compiled against
-the reference's own mc/src/types.h + prj_params.h where they lie (skipped where the reference checkout is absent,
-e.g. on the GPU box). No GPU needed: nothing is run beyond a call that fails with HJ_ERR_NO_DEVICE here."""
+the reference's own mc/src/types.h + prj_params.h, as build() left them in oracle/_ref/include (oracle/Makefile; skipped
+where build() had no reference checkout to take them from, e.g. on the GPU box). No GPU needed: nothing is run beyond a call that fails with HJ_ERR_NO_DEVICE here."""
 import os
 import re
 import subprocess
@@ -11,7 +11,7 @@ import pytest
 from htm_hashjoin_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF_INCLUDE = os.path.join(ROOT, "oracle", "_ref", "include")    # build products, never committed
 
 
 def _blocks(lang):
@@ -41,12 +41,13 @@ def test_main_cpp_dispatch_line_names_the_stub():
     assert any('cmdParams.algo == "hip"' in b and "HipHashBuild(" in b for b in _blocks("cpp"))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "mc", "src")), reason="reference checkout not present")
+@pytest.mark.skipif(not os.path.isfile(os.path.join(REF_INCLUDE, "types.h")),
+                    reason="oracle/_ref/include not built (build() had no reference checkout)")
 def test_hip_pro_stub_compiles_against_the_references_types(tmp_path):
     stub = next(b for b in _blocks("c") if "HIP_PRO" in b)
-    # relation_t / tuple_t come from the reference's own headers, read where they lie (nothing is copied)
+    # relation_t / tuple_t come from the reference's own headers (oracle/_ref/include: build products, never committed)
     (tmp_path / "hip_pro.c").write_text('#include <stdint.h>\n#include "types.h"\n#include "prj_params.h"\n' + stub)
-    cmd = ["gcc", "-std=gnu99", "-Wall", "-Werror", "-fsyntax-only", "-DHAVE_CONFIG_H", "-I", os.path.join(REF, "mc"),
-           "-I", os.path.join(REF, "mc", "src"), "-I", os.path.join(ROOT, "include"), str(tmp_path / "hip_pro.c")]
+    cmd = ["gcc", "-std=gnu99", "-Wall", "-Werror", "-fsyntax-only", "-DHAVE_CONFIG_H", "-I", REF_INCLUDE,
+           "-I", os.path.join(ROOT, "include"), str(tmp_path / "hip_pro.c")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

@@ -222,8 +222,8 @@ def test_single_rank_is_the_plain_operator():
 
 
 def _bench_worker(rank, world, port, out):
-    """bench.py's own N > 1 leg (sharded.bench_sharded) with bench.py's own default flags, under gloo, the compute
-    engine swapped for the checker-backed one."""
+    """bench.py's own N > 1 leg (sharded.bench_sharded) with bench.py's own default flags and --full (the phase split
+    and the other split), under gloo, the compute engine swapped for the checker-backed one."""
     import sys
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -231,7 +231,7 @@ def _bench_worker(rank, world, port, out):
     from htm_hashjoin_amd import sharded
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
-    sys.argv = ["bench.py", "--gpus", str(world), "--log2n", "12", "--steps", "2", "--warmup", "1"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--log2n", "12", "--steps", "2", "--warmup", "1", "--full"]
     import bench
     line = sharded.bench_sharded(bench.parse(), torch, dist, hj, rank, world, 0, engine=OracleShardEngine(), device="cpu")
     if rank == 0:

@@ -1,4 +1,4 @@
-# Round profile (tools/prof_round.sh rNN): kernel-trace stats of the bench's main leg (`bench.py --no-extra
+# Round profile (tools/prof_round.sh rNN): kernel-trace stats of the bench's main leg (`bench.py --full --no-extra
 # --no-cpu-baseline`: only the metric's workload, so that the per-kernel averages can be held against the HIP-event
 # times of the JSON line) + separate FETCH_SIZE / WRITE_SIZE passes of the same leg (never combined with tracing).
 set -e
@@ -7,11 +7,11 @@ R=$GRAFT_REPO_ROOT
 P=$R/gpurun_out/prof_$TAG
 mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 $R/bench.py --no-extra --no-cpu-baseline > $P/bench_under_rocprof.json 2> $P/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 $R/bench.py --full --no-extra --no-cpu-baseline > $P/bench_under_rocprof.json 2> $P/bench_under_rocprof.err
 echo "stats done" ; tail -c 300 $P/bench_under_rocprof.json
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/fetch -- python3 $R/bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline > $P/fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/fetch -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-extra --no-cpu-baseline > $P/fetch.log 2>&1
 echo "fetch done"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $P/write -- python3 $R/bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline > $P/write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $P/write -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-extra --no-cpu-baseline > $P/write.log 2>&1
 echo "write done"
 cd $R
 python3 tools/summarize_prof.py stats $P/stats $P/kernel_stats.csv
