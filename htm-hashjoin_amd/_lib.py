@@ -86,6 +86,9 @@ def _declare(lib):
         "hj_build_dev": ([vp, vp, u64, u64], i32),
         "hj_probe_dev": ([vp, vp, u64], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
+        "hj_prj_build_dev": ([vp, vp, u64], i32),
+        "hj_prj_probe_dev": ([vp, vp, u64], i32),
+        "hj_prj_resident_info": ([vp, P(u64)], i32),
         "hj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_checksums_dev": ([vp], i32),
         "hj_fetch_result": ([vp, P(hj_result)], i32),

@@ -17,7 +17,7 @@
 using namespace hj;
 
 namespace {
-enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_COUNT };
+enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_COUNT };
 }
 
 struct hj_ctx {
@@ -74,6 +74,14 @@ struct hj_ctx {
     size_t capWork = 0;
     bool prjRan = false;
     bool prjOptimistic = false;   // the last radix join enqueued the histogram-free passes
+    // PRJ with a resident R (hj_prj_build_dev / hj_prj_probe_dev): R's final offsets / fragment counts and the work-item
+    // list live in prjRes (prj_resident_carve), R's keys in partR
+    void* prjRes = nullptr; size_t capPrjRes = 0;
+    uint64_t prjMaxSlice = 0;                   // sSize of the last PRJ / AUTO hj_reserve: the largest slice a probe takes
+    bool resident = false;                      // R is partitioned and nothing has replaced it since
+    PrjPlan resPlan{};                          // the plan R was partitioned with (radix bits, R's layout)
+    uint64_t resR = 0;
+    bool resProbed = false, resProbeOpt = false;   // a probe ran since the build; its slice enqueued the histogram-free passes
     // staging for hj_run
     uint64_t *stageR = nullptr, *stageS = nullptr;
     uint64_t capStageR = 0, capStageS = 0;
@@ -229,7 +237,7 @@ void hj_destroy(hj_ctx* c)
     if (c->stream || !c->ownStream) hipStreamSynchronize(c->stream);
     zipf_release(c);
     if (c->stream || !c->ownStream) hipStreamSynchronize(c->stream);
-    void* frees[] = {c->table, c->dCtr, c->tmpA, c->partR, c->partS, c->work, c->stageR, c->stageS,
+    void* frees[] = {c->table, c->dCtr, c->tmpA, c->partR, c->partS, c->work, c->prjRes, c->stageR, c->stageS,
                      c->ownerBuf, c->queueBuf, c->queueCount, c->fitCount, c->boundsBuf, c->htmConflicts, c->htmOwnCounts, c->htmOvfCount,
                      c->htmOvfBase, c->htmScan, c->htmOverflow, c->shard[0].work, c->shard[1].work,
                      c->shard[2].work, c->shard[3].work};
@@ -285,6 +293,7 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         c->plan = prj_plan(rSize, sSize, bits, params->prjMode);
         const uint64_t nmax = rSize > sSize ? rSize : sSize;
         int rc;
+        const uint64_t caps0[4] = {c->capTmp, c->capPartR, c->capPartS, c->capWork};
         // +2 tuples: the 16-byte sweeps may touch one tuple past an odd end
         if ((rc = grow(c, c->tmpA, c->capTmp, nmax + 2))) return rc;
         if ((rc = grow(c, c->partR, c->capPartR, rSize + 2))) return rc;
@@ -294,6 +303,16 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
             HJ_HIP(c, hipMalloc(&c->work, c->plan.workspaceBytes));
             c->capWork = c->plan.workspaceBytes;
         }
+        // resident R (hj_prj_build_dev): its offsets and the probes' work items, for slices up to sSize
+        const size_t rb = prj_resident_bytes(bits, sSize);
+        if (rb > c->capPrjRes) {
+            c->resident = false;
+            if (c->prjRes) { HJ_HIP(c, hipFree(c->prjRes)); c->prjRes = nullptr; c->capPrjRes = 0; }
+            HJ_HIP(c, hipMalloc(&c->prjRes, rb));
+            c->capPrjRes = rb;
+        }
+        if (caps0[0] != c->capTmp || caps0[1] != c->capPartR || caps0[2] != c->capPartS || caps0[3] != c->capWork) c->resident = false;
+        c->prjMaxSlice = sSize;
         if (params->algo == HJ_ALGO_PRJ) return HJ_OK;      // AUTO also needs the open-addressing buffers below
         // ... when the table join can take this R at all (it wants a power-of-two size, as the reference does);
         // otherwise AUTO simply is the radix join, which has no such restriction
@@ -387,7 +406,7 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     HJ_HIP(c, hipSetDevice(c->device));
     c->rSize = n; c->sSize = 0; c->tableSize = tableSize; c->hshift = hshift;
     for (bool& b : c->evSet) b = false;
-    c->prjRan = false; c->htmBuilt = false;
+    c->prjRan = false; c->htmBuilt = false; c->resident = false;
     HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
     int rc;
     if ((rc = record(c, EV_CLEAR0))) return rc;
@@ -514,7 +533,7 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     if (idxBase + rSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_dev: index range exceeds 2^32 - 1");
     c->rSize = rSize; c->sSize = 0; c->tableSize = slots; c->hshift = 0; c->htmBuckets = nb;
     for (bool& b : c->evSet) b = false;
-    c->prjRan = false; c->built = false; c->htmBuilt = false;
+    c->prjRan = false; c->built = false; c->htmBuilt = false; c->resident = false;
     if (!c->htmGenericChains) c->htmChainsFellBack = false;
     HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
     int rc;
@@ -685,7 +704,7 @@ int hj_prj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_
     const PrjPlan pl = prj_plan(rSize, dS ? sSize : 0, c->plan.radixBits, c->params.prjMode);
     if (pl.workspaceBytes > c->capWork) return fail(c, HJ_ERR_STATE, "hj_prj_join_dev: workspace too small");
     for (bool& b : c->evSet) b = false;
-    c->built = false;
+    c->built = false; c->resident = false;
     c->rSize = rSize; c->sSize = dS ? sSize : 0; c->tableSize = 0;
     HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
     int rc;
@@ -699,6 +718,96 @@ int hj_prj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_
     c->prjRan = true;
     c->prjOptimistic = pl.optimistic;
     c->algoUsed = HJ_ALGO_PRJ;
+    return HJ_OK;
+}
+
+// the scratch workspace of the passes holds nothing resident: a slice whose plan needs more than hj_reserve's (the chunk
+// count is not monotone in the size, see prj_plan) gets a larger one
+static int ensure_work(hj_ctx* c, size_t bytes)
+{
+    if (bytes <= c->capWork) return HJ_OK;
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->work) { HJ_HIP(c, hipFree(c->work)); c->work = nullptr; c->capWork = 0; }
+    HJ_HIP(c, hipMalloc(&c->work, bytes));
+    c->capWork = bytes;
+    return HJ_OK;
+}
+
+int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
+{
+    if (c) c->streamAtBuildEnd = false;
+    if (!c || !dR || rSize == 0) return HJ_ERR_INVALID;
+    if (c->params.algo != HJ_ALGO_PRJ && c->params.algo != HJ_ALGO_AUTO)
+        return fail(c, HJ_ERR_STATE, "hj_prj_build_dev: context not reserved for PRJ");
+    if (rSize + 2 > c->capTmp || rSize + 2 > c->capPartR || !c->prjRes ||
+        prj_resident_bytes(c->plan.radixBits, 0) > c->capPrjRes)
+        return fail(c, HJ_ERR_STATE, "hj_prj_build_dev: hj_reserve() not called for this rSize");
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PrjPlan pl = prj_plan(rSize, 0, c->plan.radixBits, c->params.prjMode);    // R's side alone
+    int rc;
+    if ((rc = ensure_work(c, pl.workspaceBytes))) return rc;
+    for (bool& b : c->evSet) b = false;
+    c->built = false; c->htmBuilt = false; c->resident = false;
+    c->rSize = rSize; c->sSize = 0; c->tableSize = 0;
+    HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
+    if ((rc = record(c, EV_PRJ0))) return rc;
+    PrjBuffers buf{c->tmpA, c->partR, c->partS, c->work};
+    HJ_HIP(c, launch_prj_build(pl, buf, prj_resident_carve(c->prjRes, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr,
+                               c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0], c->ev[EV_PRJ_S1], c->stream));
+    c->evSet[EV_PRJ_PART] = c->evSet[EV_PRJ_S0] = c->evSet[EV_PRJ_S1] = true;
+    if ((rc = record(c, EV_PRJ1))) return rc;
+    c->prjRan = true;
+    c->prjOptimistic = pl.optimistic;
+    c->algoUsed = HJ_ALGO_PRJ;
+    c->resident = true; c->resPlan = pl; c->resR = rSize;
+    c->resProbed = false; c->resProbeOpt = false;
+    return HJ_OK;
+}
+
+int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
+{
+    if (c) c->streamAtBuildEnd = false;
+    if (!c || (!dS && sSize)) return HJ_ERR_INVALID;
+    if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: no resident R (call hj_prj_build_dev first)");
+    if (sSize > c->prjMaxSlice || sSize + 2 > c->capPartS || sSize + 2 > c->capTmp ||
+        prj_resident_bytes(c->resPlan.radixBits, sSize) > c->capPrjRes)
+        return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: slice larger than the sSize given to hj_reserve()");
+    if (sSize == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, c->params.prjMode);   // fragS: the slice's own geometry
+    int rc;
+    if ((rc = ensure_work(c, pl.workspaceBytes))) return rc;
+    if ((rc = record(c, EV_RP0))) return rc;
+    PrjBuffers buf{c->tmpA, c->partR, c->partS, c->work};
+    HJ_HIP(c, launch_prj_probe(c->resPlan, c->resR, pl, buf, prj_resident_carve(c->prjRes, c->resPlan.radixBits, sSize), dS, sSize,
+                               c->nCU, c->dCtr, c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
+    c->evSet[EV_RP_PART] = c->evSet[EV_RP_JOIN0] = true;
+    if ((rc = record(c, EV_RP1))) return rc;
+    c->sSize += sSize;
+    c->resProbed = true; c->resProbeOpt = pl.optimistic;
+    return HJ_OK;
+}
+
+int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
+{
+    if (c) c->streamAtBuildEnd = false;
+    if (!c || !out) return HJ_ERR_INVALID;
+    if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_resident_info: no resident R");
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PrjResident res = prj_resident_carve(c->prjRes, c->resPlan.radixBits, 0);
+    unsigned long long st[4];
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(st, res.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    const PrjPlan& pl = c->resPlan;
+    const bool fragR = pl.optimistic && c->hCtr->prjFallbackR == 0;
+    const uint64_t P = 1ull << pl.radixBits;
+    out[0] = !pl.optimistic ? 0u : (c->hCtr->prjFallbackR ? 2u : 1u);
+    out[1] = (!c->resProbed || !c->resProbeOpt) ? 0u : (c->hCtr->prjFallback ? 2u : 1u);
+    out[2] = st[1]; out[3] = st[2]; out[4] = st[3];
+    // R's keys (the fragments with their slack, or one dense run) + its offsets and fragment counts
+    out[5] = 4 * (fragR ? P * pl.fragR.C2 * pl.fragR.cap2 : c->resR) + 4 * (P + 1) + 4 * P * 16;
+    out[6] = out[7] = 0;
     return HJ_OK;
 }
 
@@ -781,6 +890,15 @@ int hj_fetch_result(hj_ctx* c, hj_result* out)
         out->total_us = elapsed_us(c, EV_PRJ0, EV_PRJ1);
         out->prjScatterPass1R_us = elapsed_us(c, EV_PRJ_S0, EV_PRJ_S1);
         out->prjPath = !c->prjOptimistic ? 0u : (k.prjFallback ? 2u : 1u);
+        if (c->resident) {
+            // resident R: the build's passes (partition_us, build_us = passes + R's checksum), the last probe (probe_us = S's
+            // passes + work items + join, join_us = the join kernel alone); prjPath = R's path
+            out->build_us = elapsed_us(c, EV_PRJ0, EV_PRJ1);
+            out->probe_us = elapsed_us(c, EV_RP0, EV_RP1);
+            out->join_us = elapsed_us(c, EV_RP_JOIN0, EV_RP1);
+            out->total_us = out->build_us + out->probe_us;
+            out->prjPath = !c->prjOptimistic ? 0u : (k.prjFallbackR ? 2u : 1u);
+        }
     } else {
         out->conflicts = k.conflicts;
         out->conflictSum = k.conflictSum;

@@ -98,6 +98,9 @@ struct Counters {
     // PRJ, histogram-free partitioning (hj_prj.hip): set to 1 by the scatter kernel that finds a fragment too small;
     // the rest of that path then returns at once and the exact (histogram) path, gated on this word, runs instead
     unsigned long long prjFallback;
+    // PRJ with a resident R (hj_prj_build_dev): R's prjFallback, copied here once R's passes are done. prjFallback itself
+    // is reset before every probe's S passes; the join reads both words to pick each relation's layout
+    unsigned long long prjFallbackR;
     // Open-addressing table formats (k_build_wave<COMPACT>, hj_build_wave.hip). tableFormat says what the table buffer
     // holds after a build: kFormatSlots8 = one 8-byte slot (index << 32 | key) per table slot, all ones = empty (every
     // build but the compact one); kFormatKeys4 = one 4-byte KEY per table slot, 0xFFFFFFFF = empty (the index words only
@@ -376,5 +379,29 @@ hipError_t launch_prj(const PrjPlan& plan, const PrjBuffers& buf,
                       Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s);
 // evScatter0/1 (may be null): recorded around the pass-1 scatter of R, PRJ's dominant kernel
 hipError_t prj_set_attributes();          // per device, at hj_create
+
+// ---- PRJ with a resident R (hj_prj_build_dev / hj_prj_probe_dev, defined in hj_prj.hip) ----
+// Everything of R's partitioning that must outlive the scratch workspace (whose layout every slice plan re-carves) and
+// the per-probe work-item list, in one buffer of prj_resident_bytes(radixBits, maxSlice) sized at hj_reserve.
+struct PrjResident {
+    uint32_t* offR;                 // [P + 1] R's partition offsets (exact passes)
+    uint32_t* cnt2R;                // [P * 16] R's pass-2 fragment counts (histogram-free passes)
+    uint32_t* itemCnt;              // [2P + 1] items per partition: split partitions first, then the rest; scanned in place
+    uint32_t* scanSums;             // scan workspace of itemCnt
+    uint2* items;                   // [P + maxSlice / kPrjItemS + 1] (partition, S chunk)
+    unsigned long long* stats;      // [4] next item ticket, items, split partitions, largest S partition
+};
+constexpr uint32_t kPrjItemS = 1u << 16;  // S tuples per join work item at most (hj_prj.hip, k_prj_probe_items)
+size_t prj_resident_bytes(uint32_t radixBits, uint64_t maxSlice);
+PrjResident prj_resident_carve(void* base, uint32_t radixBits, uint64_t maxSlice);
+// R's passes into buf.partR / res (plan = prj_plan(nR, 0, ...)), then R's checksum (k_prj_join without S);
+// Counters::prjFallbackR = R's fallback. evPartDone: between the passes and the checksum.
+hipError_t launch_prj_build(const PrjPlan& plan, const PrjBuffers& buf, const PrjResident& res, const uint64_t* R, uint64_t nR,
+                            int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s);
+// S's passes into buf.partS (planS = prj_plan(nS, nS, ...)), the work-item list, the skew-split join against the resident R
+// (planR = the build's plan). evPartDone: after S's passes; evJoin0: right before the join kernel.
+hipError_t launch_prj_probe(const PrjPlan& planR, uint64_t nR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+                            const uint64_t* S, uint64_t nS, int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evJoin0,
+                            hipStream_t s);
 
 }  // namespace hj

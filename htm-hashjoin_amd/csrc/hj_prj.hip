@@ -1009,6 +1009,278 @@ k_prj_join(const uint32_t* __restrict__ partR, const uint32_t* __restrict__ offR
 }
 
 // ---------------------------------------------------------------------------
+// skew-split join against a resident R (hj_prj_build_dev / hj_prj_probe_dev)
+//   k_prj_join hands out whole partitions by a fixed stride, so one Zipf-hot S partition (Zipf(0.9) over 2^28 keys puts
+//   ~1.7 % of all draws on one key: ~4.5 M S tuples in one partition of a 2^28 slice, against 4096 on average) is walked
+//   by one workgroup while the other CUs idle. Here the unit of work is an ITEM: a partition and at most kPrjItemS of its
+//   S tuples. The list is built on the device from S's partition sizes (k_prj_items_count, one scan, k_prj_items_fill),
+//   the partitions that are split over several items first, and a persistent grid takes items from a ticket counter:
+//   the big partitions are spread over many CUs at the start, the small ones fill in behind them. Every item rebuilds
+//   its R partition's LDS image (the three modes of k_prj_join) and probes its S range.
+//   kPrjItemS = 2^16: 64 keys per thread and item (256 KiB of S), against an R partition of ~4096 keys at 2^28 / 16 bits
+//   that every item rebuilds (~6 % extra LDS work for the items of a split partition); a 4.5 M hot partition becomes ~70
+//   items. A partition of the histogram-free S layout holds at most 65535 keys (frag_geometry), so it is always ONE item
+//   and only the exact layout (a dense run per partition) is ever split.
+//   No prjChecksum here: the build counts it once per R partition (k_prj_join without S), and probes do not change it.
+// ---------------------------------------------------------------------------
+static_assert(kPrjItemS > 65535u, "a partition of the histogram-free layout is one item");
+
+// keys of partition pid in one relation's layout (exact: cnt == nullptr)
+__device__ __forceinline__ uint32_t part_keys(const uint32_t* __restrict__ off, const uint32_t* __restrict__ cnt,
+                                              uint32_t log2C, uint32_t pid)
+{
+    if (cnt == nullptr) return off[pid + 1] - off[pid];
+    uint32_t n = 0;
+    for (uint32_t f = 0; f < (1u << log2C); ++f) n += cnt[(pid << log2C) + f];
+    return n;
+}
+
+// One thread per partition: items of partition p at itemCnt[p] (split over > 1 item) or itemCnt[P + p] (one item), so that
+// one exclusive scan over [0, 2P] numbers the split partitions' items first; itemCnt[2P] = 0 becomes the total.
+// A partition without R tuples or without S tuples has no item. stats[2] / [3]: split partitions, largest S partition.
+__global__ void __launch_bounds__(kBlock)
+k_prj_items_count(const uint32_t* __restrict__ offR, const uint32_t* __restrict__ cntR, uint32_t log2CR,
+                  const uint32_t* __restrict__ offS, const uint32_t* __restrict__ cntS, uint32_t log2CS,
+                  uint32_t nParts, const Counters* __restrict__ ctr, uint32_t* __restrict__ itemCnt,
+                  unsigned long long* __restrict__ stats)
+{
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    const bool rFrag = cntR != nullptr && ctr->prjFallbackR == 0;      // the layout each relation's passes ended in
+    const bool sFrag = cntS != nullptr && ctr->prjFallback == 0;
+    uint32_t nS = 0, split = 0;
+    if (p < nParts) {
+        const uint32_t nR = part_keys(offR, rFrag ? cntR : nullptr, log2CR, p);
+        nS = part_keys(offS, sFrag ? cntS : nullptr, log2CS, p);
+        const uint32_t items = (nR && nS) ? (nS - 1) / kPrjItemS + 1 : 0u;
+        split = items > 1 ? 1u : 0u;
+        itemCnt[p] = split ? items : 0u;
+        itemCnt[nParts + p] = split ? 0u : items;
+    } else if (p == nParts) {
+        itemCnt[2 * nParts] = 0;
+    }
+    // one atomic per wavefront
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_down((int)nS, off, 64);
+        nS = o > nS ? o : nS;
+        split += (uint32_t)__shfl_down((int)split, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (split) atomicAdd(&stats[2], (unsigned long long)split);
+        if (nS) atomicMax(&stats[3], (unsigned long long)nS);
+    }
+}
+
+// One thread per itemCnt entry: its items (partition, S chunk) at the scanned position. stats[1] = items in all.
+__global__ void __launch_bounds__(kBlock)
+k_prj_items_fill(const uint32_t* __restrict__ scanned, uint32_t nParts, uint2* __restrict__ items,
+                 unsigned long long* __restrict__ stats)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) stats[1] = scanned[2 * nParts];
+    if (i >= 2 * nParts) return;
+    const uint32_t b = scanned[i], n = scanned[i + 1] - b;
+    const uint32_t pid = i < nParts ? i : i - nParts;
+    for (uint32_t k = 0; k < n; ++k) items[b + k] = make_uint2(pid, k);
+}
+
+constexpr int kTailPre = 8;   // loads in flight per thread in the loops past the register prefetch
+
+// f(key) for element i of [from, n) of a run starting at slot `base`, kTailPre loads in flight per thread (a one-load loop
+// waits a whole HBM round trip per key: the rest of a 2^16-tuple item is 48 keys per thread)
+template <typename F>
+__device__ __forceinline__ void for_run(const uint32_t* __restrict__ part, uint32_t base, uint32_t from, uint32_t n, F&& f)
+{
+    for (uint32_t i0 = from + threadIdx.x; i0 < n; i0 += kTailPre * kJoinThreads) {
+        uint32_t k[kTailPre];
+#pragma unroll
+        for (int u = 0; u < kTailPre; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
+            k[u] = part[base + (i < n ? i : n - 1)];                  // clamped: i0 < n, so n >= 1
+        }
+#pragma unroll
+        for (int u = 0; u < kTailPre; ++u)
+            if (i0 + (uint32_t)u * kJoinThreads < n) f(k[u]);
+    }
+}
+
+// gR / gS: the histogram-free geometry (cntR / cntS == nullptr: that relation took the exact passes only); which layout a
+// relation ended in is read from Counters::prjFallbackR / prjFallback, each relation on its own. nR / nS: tuples (the
+// exact layout's clamp bound). items[0 .. *nItemsAt), taken through *ticket (zeroed by the host before the launch).
+template <bool DIRECT>
+__global__ void __launch_bounds__(kJoinThreads)
+k_prj_probe_items(const uint32_t* __restrict__ partR, const uint32_t* __restrict__ offR, const uint32_t* __restrict__ cntR, PartGeom gR, uint32_t nR,
+                  const uint32_t* __restrict__ partS, const uint32_t* __restrict__ offS, const uint32_t* __restrict__ cntS, PartGeom gS, uint32_t nS,
+                  const uint2* __restrict__ items, const uint32_t* __restrict__ nItemsAt, unsigned long long* __restrict__ ticket,
+                  uint32_t radixBits, Counters* __restrict__ ctr)
+{
+    extern __shared__ uint32_t tab[];  // kJoinSlots
+    __shared__ uint32_t sNext;
+    const bool rFrag = cntR != nullptr && ctr->prjFallbackR == 0;
+    const bool sFrag = cntS != nullptr && ctr->prjFallback == 0;
+    const PartView R = rFrag ? PartView{partR, nullptr, cntR, gR.log2C, gR.cap, gR.total} : PartView{partR, offR, nullptr, 0u, 0u, nR};
+    const PartView S = sFrag ? PartView{partS, nullptr, cntS, gS.log2C, gS.cap, gS.total} : PartView{partS, offS, nullptr, 0u, 0u, nS};
+    const uint32_t nItems = *nItemsAt;
+    unsigned long long matches = 0;
+
+    // prefetch slots as in k_prj_join: slot j = element ((j & (spf - 1)) * 1024 + thread) of fragment j >> spfShift
+    const uint32_t spfShiftR = 4u - R.log2C, spfShiftS = 4u - S.log2C;
+    // What an item reads. R: the whole partition (fragments of R.cap slots from `base`, or one run). S: the whole partition
+    // in the histogram-free layout, else the run of at most kPrjItemS tuples of chunk it.y (n = its length).
+    struct Run { uint32_t base, n; };
+    auto r_run = [&](uint32_t pid) { return R.cnt ? Run{(pid << R.log2C) * R.cap, 0u} : Run{R.off[pid], R.off[pid + 1] - R.off[pid]}; };
+    auto s_run = [&](uint2 it) {
+        if (S.cnt) return Run{(it.x << S.log2C) * S.cap, 0u};
+        const uint32_t b = S.off[it.x], lo = it.y * kPrjItemS, len = S.off[it.x + 1] - b - lo;
+        return Run{b + lo, len < kPrjItemS ? len : kPrjItemS};
+    };
+    auto r_cnt = [&](uint32_t pid, const Run& r, uint32_t f) { return R.cnt ? R.cnt[(pid << R.log2C) + f] : r.n; };
+    auto s_cnt = [&](uint2 it, const Run& r, uint32_t f) { return S.cnt ? S.cnt[(it.x << S.log2C) + f] : r.n; };
+    auto load = [](const PartView& v, const Run& r, uint32_t spfShift, uint32_t (&buf)[kJoinPre]) {
+#pragma unroll
+        for (int j = 0; j < kJoinPre; ++j) {
+            const uint32_t o = r.base + ((uint32_t)j >> spfShift) * v.cap + ((j & ((1u << spfShift) - 1u)) * kJoinThreads + threadIdx.x);
+            buf[j] = v.part[o < v.total ? o : v.total - 1];
+        }
+    };
+    // read before any LDS work of the item (see k_prj_join: a scalar count load between LDS atomics serialises them)
+    struct Shape { uint32_t n, mask; bool tail; };
+    auto shape_of = [](uint32_t log2C, uint32_t spfShift, auto&& cnt) {
+        Shape sh{0u, 0u, false};
+        const uint32_t spf = 1u << spfShift;
+        for (uint32_t fr = 0; fr < (1u << log2C); ++fr) {
+            const uint32_t n = cnt(fr);
+            sh.n += n;
+            sh.tail |= n > (kJoinThreads << spfShift);
+            uint32_t mine = n > threadIdx.x ? (n - threadIdx.x + kJoinThreads - 1) / kJoinThreads : 0u;
+            mine = mine < spf ? mine : spf;
+            sh.mask |= ((1u << mine) - 1u) << (fr << spfShift);
+        }
+        return sh;
+    };
+    auto for_each = [](const PartView& v, const Run& r, uint32_t spfShift, const Shape& sh, const uint32_t (&buf)[kJoinPre],
+                       auto&& cnt, auto&& f) {
+#pragma unroll
+        for (int j = 0; j < kJoinPre; ++j)
+            if ((sh.mask >> j) & 1u) f(buf[j]);
+        if (sh.tail)
+            for (uint32_t fr = 0; fr < (1u << v.log2C); ++fr) for_run(v.part, r.base + fr * v.cap, kJoinThreads << spfShift, cnt(fr), f);
+    };
+    auto insert_hashed = [&](uint32_t key) {
+        const uint32_t k = key >> radixBits;
+        uint32_t h = join_hash(k);
+        while (atomicCAS(&tab[h], kEmpty32, k) != kEmpty32) h = (h + 1) & (kJoinSlots - 1);
+    };
+    auto probe_hashed = [&](uint32_t key) {
+        const uint32_t k = key >> radixBits;
+        uint32_t h = join_hash(k);
+        for (;;) {
+            const uint32_t v = tab[h];
+            if (v == kEmpty32) break;
+            matches += (v == k);
+            h = (h + 1) & (kJoinSlots - 1);
+        }
+    };
+
+    if (threadIdx.x == 0) sNext = (uint32_t)atomicAdd(ticket, 1ull);
+    __syncthreads();
+    uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
+    if (cur >= nItems) return;                                 // workgroup-uniform
+    uint2 it = items[cur];
+    uint32_t bufR[kJoinPre], bufS[kJoinPre];
+    load(R, r_run(it.x), spfShiftR, bufR);
+
+    for (;;) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // R(it) has landed
+        __builtin_amdgcn_sched_barrier(0);
+        // the next ticket: issued before S's loads, so that waiting for it does not wait for them; published to the
+        // workgroup at the barrier after R's build
+        uint32_t tk = 0;
+        if (threadIdx.x == 0) tk = (uint32_t)atomicAdd(ticket, 1ull);
+        const Run sr = s_run(it);
+        load(S, sr, spfShiftS, bufS);                          // in flight while R is built
+        __builtin_amdgcn_sched_barrier(0);
+        const uint32_t pid = it.x;
+        const Run rr = r_run(pid);
+        auto rc = [&](uint32_t f) { return r_cnt(pid, rr, f); };
+        auto sc = [&](uint32_t f) { return s_cnt(it, sr, f); };
+        const Shape shR = shape_of(R.log2C, spfShiftR, rc);
+        const Shape shS = shape_of(S.log2C, spfShiftS, sc);
+        const uint32_t nRp = shR.n;
+        uint2 nxt = it;
+        uint32_t nxtIdx = nItems;
+        // after the barrier that follows R's build: the next item, and its R partition in flight while S is probed
+        auto next_item = [&]() {
+            nxtIdx = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
+            if (nxtIdx < nItems) nxt = items[nxtIdx];
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(it) has landed; bufR is free
+            __builtin_amdgcn_sched_barrier(0);
+            load(R, r_run(nxt.x), spfShiftR, bufR);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+
+        if (DIRECT && nRp <= 65535u) {
+            // ---- direct-addressed 16-bit counters (k_prj_join) ----
+            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = 0u;
+            __syncthreads();
+            for_each(R, rr, spfShiftR, shR, bufR, rc, [&](uint32_t key) {
+                const uint32_t k = key >> radixBits;
+                atomicAdd(&tab[k >> 1], 1u << (16u * (k & 1u)));
+            });
+            if (threadIdx.x == 0) sNext = tk;
+            __syncthreads();
+            next_item();
+            uint32_t m32 = 0;                                  // <= 65535 per probe, 16 probes per thread
+#pragma unroll
+            for (int j = 0; j < kJoinPre; ++j)
+                if ((shS.mask >> j) & 1u) {
+                    const uint32_t k = bufS[j] >> radixBits;
+                    m32 += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+                }
+            matches += m32;
+            if (shS.tail)
+                for (uint32_t fr = 0; fr < (1u << S.log2C); ++fr)
+                    for_run(S.part, sr.base + fr * S.cap, kJoinThreads << spfShiftS, sc(fr), [&](uint32_t key) {
+                        const uint32_t k = key >> radixBits;
+                        matches += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+                    });
+            __syncthreads();
+        } else if (nRp <= kJoinBlockTuples) {
+            // ---- the whole R partition in one hashed LDS table (also an R partition without tuples: nothing matches) ----
+            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
+            __syncthreads();
+            for_each(R, rr, spfShiftR, shR, bufR, rc, insert_hashed);
+            if (threadIdx.x == 0) sNext = tk;
+            __syncthreads();
+            next_item();
+            for_each(S, sr, spfShiftS, shS, bufS, sc, probe_hashed);
+            __syncthreads();
+        } else {
+            // ---- oversized R partition (skew): several LDS builds, the item's S probed against each. The histogram-free R
+            // layout never gets here (frag_geometry: a partition fits one table), so R is one run
+            __syncthreads();                                   // no barrier yet in this item: the last ticket has been read
+            if (threadIdx.x == 0) sNext = tk;
+            __syncthreads();
+            next_item();
+            for (uint32_t blk = 0; blk < rr.n; blk += kJoinBlockTuples) {
+                const uint32_t bn = rr.n - blk > kJoinBlockTuples ? kJoinBlockTuples : rr.n - blk;
+                for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
+                __syncthreads();
+                for_run(R.part, rr.base + blk, 0u, bn, insert_hashed);
+                __syncthreads();
+                for (uint32_t fr = 0; fr < (1u << S.log2C); ++fr) for_run(S.part, sr.base + fr * S.cap, 0u, sc(fr), probe_hashed);
+                __syncthreads();
+            }
+        }
+        if (nxtIdx >= nItems) break;                           // wave-uniform: every wavefront read the same ticket
+        it = nxt;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the last (unused) R prefetch
+    // one atomic per wavefront
+    for (int off = 32; off > 0; off >>= 1) matches += __shfl_down(matches, off, 64);
+    if ((threadIdx.x & 63) == 0 && matches) atomicAdd(&counter_shard(ctr)->prjMatches, matches);
+}
+
+// ---------------------------------------------------------------------------
 // host-side planning and launch
 // ---------------------------------------------------------------------------
 static uint32_t pick_chunk_len(uint64_t n)
@@ -1263,6 +1535,125 @@ hipError_t launch_prj(const PrjPlan& pl, const PrjBuffers& buf, const uint64_t* 
     const PartView er{partR, w.offR, nullptr, 0u, 0u, (uint32_t)nR};
     const PartView es{partS, w.offS, nullptr, 0u, 0u, (uint32_t)nS};
     join(er, S ? es : none, exact);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// resident R: hj_prj_build_dev / hj_prj_probe_dev
+// ---------------------------------------------------------------------------
+namespace {
+// everything but the item list depends on the radix bits alone: a later, smaller slice bound never moves R's arrays
+struct ResLayout { size_t offR, cnt2R, itemCnt, scanSums, stats, items, end; };
+ResLayout res_layout(uint32_t radixBits, uint64_t maxSlice)
+{
+    const uint64_t P = 1ull << radixBits;
+    ResLayout l;
+    l.offR = 0;
+    l.cnt2R = l.offR + align_up(sizeof(uint32_t) * (P + 1), 256);
+    l.itemCnt = l.cnt2R + align_up(sizeof(uint32_t) * P * 16, 256);          // C2 <= 16 (frag_geometry)
+    l.scanSums = l.itemCnt + align_up(sizeof(uint32_t) * (2 * P + 1), 256);
+    l.stats = l.scanSums + align_up(sizeof(uint32_t) * scan_workspace_words(2 * P + 1), 256);
+    l.items = l.stats + 256;
+    l.end = l.items + align_up(sizeof(uint2) * (P + maxSlice / kPrjItemS + 2), 256);
+    return l;
+}
+
+// R's checksum (k_prj_join without S) over whichever layout R's passes ended in
+void enqueue_checksum_join(const PrjPlan& pl, const PartView& vr, int nCU, Counters* ctr, Gate gate, hipStream_t s)
+{
+    const uint32_t P = 1u << pl.radixBits;
+    const unsigned grid = P < (unsigned)nCU ? P : (unsigned)nCU;
+    const PartGeom none{0u, 0u, 1u};
+    if (pl.radixBits >= 16)
+        hipLaunchKernelGGL(k_prj_join<true>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                           vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total}, nullptr, nullptr, nullptr, none,
+                           pl.radixBits, P, ctr, gate);
+    else
+        hipLaunchKernelGGL(k_prj_join<false>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                           vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total}, nullptr, nullptr, nullptr, none,
+                           pl.radixBits, P, ctr, gate);
+}
+}  // namespace
+
+size_t prj_resident_bytes(uint32_t radixBits, uint64_t maxSlice) { return res_layout(radixBits, maxSlice).end; }
+
+PrjResident prj_resident_carve(void* base, uint32_t radixBits, uint64_t maxSlice)
+{
+    const ResLayout l = res_layout(radixBits, maxSlice);
+    char* p = static_cast<char*>(base);
+    return PrjResident{reinterpret_cast<uint32_t*>(p + l.offR), reinterpret_cast<uint32_t*>(p + l.cnt2R),
+                       reinterpret_cast<uint32_t*>(p + l.itemCnt), reinterpret_cast<uint32_t*>(p + l.scanSums),
+                       reinterpret_cast<uint2*>(p + l.items), reinterpret_cast<unsigned long long*>(p + l.stats)};
+}
+
+hipError_t launch_prj_build(const PrjPlan& pl, const PrjBuffers& buf, const PrjResident& res, const uint64_t* R, uint64_t nR,
+                            int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s)
+{
+    const Work w = carve(pl, buf.work);
+    uint32_t* const tmp = reinterpret_cast<uint32_t*>(buf.tmpA);
+    uint32_t* const partR = reinterpret_cast<uint32_t*>(buf.partR);
+    hipError_t e;
+    // R's side of launch_prj, with the final offsets / fragment counts in the resident buffer instead of the workspace
+    Gate exact = kNoGate;
+    if (pl.optimistic) {
+        if ((e = partition_relation_frag(pl, pl.fragR, w, R, nR, tmp, partR, res.cnt2R, ctr, s, evScatter0, evScatter1)) != hipSuccess) return e;
+        exact = Gate{&ctr->prjFallback, 1ull};
+        evScatter0 = evScatter1 = nullptr;
+    }
+    if ((e = partition_relation(pl, w, R, nR, tmp, partR, res.offR, exact, s, evScatter0, evScatter1)) != hipSuccess) return e;
+    if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
+    // R's decision outlives the probes' S passes, which reuse prjFallback
+    if ((e = hipMemcpyAsync(&ctr->prjFallbackR, &ctr->prjFallback, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    const uint32_t P = 1u << pl.radixBits;
+    if (pl.optimistic)
+        enqueue_checksum_join(pl, PartView{partR, nullptr, res.cnt2R, pl.fragR.log2C2, pl.fragR.cap2, P * pl.fragR.C2 * pl.fragR.cap2},
+                              nCU, ctr, Gate{&ctr->prjFallback, 0ull}, s);
+    enqueue_checksum_join(pl, PartView{partR, res.offR, nullptr, 0u, 0u, (uint32_t)nR}, nCU, ctr, exact, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_prj_probe(const PrjPlan& planR, uint64_t nR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+                            const uint64_t* S, uint64_t nS, int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evJoin0,
+                            hipStream_t s)
+{
+    const Work w = carve(planS, buf.work);
+    uint32_t* const tmp = reinterpret_cast<uint32_t*>(buf.tmpA);
+    uint32_t* const partS = reinterpret_cast<uint32_t*>(buf.partS);
+    hipError_t e;
+    // S's passes: the histogram-free ones when the slice qualifies, the exact ones gated behind them (a Zipf slice falls back)
+    if ((e = hipMemsetAsync(&ctr->prjFallback, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    Gate exact = kNoGate;
+    if (planS.optimistic) {
+        if ((e = partition_relation_frag(planS, planS.fragS, w, S, nS, tmp, partS, w.cnt2S, ctr, s)) != hipSuccess) return e;
+        exact = Gate{&ctr->prjFallback, 1ull};
+    }
+    if ((e = partition_relation(planS, w, S, nS, tmp, partS, w.offS, exact, s)) != hipSuccess) return e;
+    if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
+    // the work items: count per partition, one scan, fill (no host round trip)
+    const uint32_t P = 1u << planR.radixBits;
+    const uint32_t* const cntR = planR.optimistic ? res.cnt2R : nullptr;
+    const uint32_t* const cntS = planS.optimistic ? w.cnt2S : nullptr;
+    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, res.offR, cntR, planR.fragR.log2C2,
+                       w.offS, cntS, planS.fragS.log2C2, P, ctr, res.itemCnt, res.stats);
+    if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
+    if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
+    // one persistent 1024-thread workgroup per CU (the LDS table is 128 KiB of the CU's 160)
+    const PartGeom gR{planR.fragR.log2C2, planR.fragR.cap2, P * planR.fragR.C2 * planR.fragR.cap2};
+    const PartGeom gS{planS.fragS.log2C2, planS.fragS.cap2, P * planS.fragS.C2 * planS.fragS.cap2};
+    const uint32_t* const nItems = res.itemCnt + 2ull * P;
+    if (planR.radixBits >= 16)
+        hipLaunchKernelGGL(k_prj_probe_items<true>, dim3((unsigned)nCU), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                           reinterpret_cast<const uint32_t*>(buf.partR), res.offR, cntR, gR, (uint32_t)nR,
+                           static_cast<const uint32_t*>(partS), w.offS, cntS, gS, (uint32_t)nS,
+                           res.items, nItems, res.stats, planR.radixBits, ctr);
+    else
+        hipLaunchKernelGGL(k_prj_probe_items<false>, dim3((unsigned)nCU), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                           reinterpret_cast<const uint32_t*>(buf.partR), res.offR, cntR, gR, (uint32_t)nR,
+                           static_cast<const uint32_t*>(partS), w.offS, cntS, gS, (uint32_t)nS,
+                           res.items, nItems, res.stats, planR.radixBits, ctr);
     return hipGetLastError();
 }
 
@@ -1543,6 +1934,10 @@ hipError_t prj_set_attributes()
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_join<false>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_join<true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_probe_items<false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_probe_items<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_scatter_stable),
                                hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -132,6 +132,24 @@ class HashJoinContext:
         self._check(lib.hj_prj_join_dev(self._h, C.c_void_p(dR_ptr), rSize,
                                         C.c_void_p(dS_ptr) if dS_ptr else None, sSize))
 
+    # ---- PRJ with a resident R: partition R once, probe S slice by slice ----
+    def prj_build(self, dR_ptr, rSize):
+        """Radix-partitions dR once and keeps the partitions in the context (dR may be freed afterwards); resets the
+        counters, prjChecksum = R's checksum. Sizing: reserve("prj" or "auto", rSize, largest slice)."""
+        self._check(lib.hj_prj_build_dev(self._h, C.c_void_p(dR_ptr), rSize))
+
+    def prj_probe(self, dS_ptr, sSize):
+        """Partitions one S slice and joins it against the resident R; totalMatches and sSize add up over the slices."""
+        self._check(lib.hj_prj_probe_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize))
+
+    def prj_resident_info(self):
+        """hj_prj_resident_info (waits for the stream): R's and the last slice's partitioning path, the last probe's join
+        work items, its partitions split over several items, its largest S partition, bytes held for R."""
+        out = (C.c_uint64 * 8)()
+        self._check(lib.hj_prj_resident_info(self._h, out))
+        return {"rPath": out[0], "sPath": out[1], "items": out[2], "splitPartitions": out[3],
+                "maxSPartition": out[4], "residentBytes": out[5]}
+
     def join(self, dR_ptr, rSize, dS_ptr, sSize):
         """Build + probe by the reserved algo; "auto" samples R for locality and picks atomic or prj."""
         self._check(lib.hj_join_dev(self._h, C.c_void_p(dR_ptr), rSize,

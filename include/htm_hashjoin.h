@@ -195,6 +195,21 @@ int hj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
  * R-side only, checksum only). */
 int hj_prj_join_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize,
                     const uint64_t *dS, uint64_t sSize);
+/* PRJ with a resident build side. Sizing: hj_reserve(params{algo = PRJ or AUTO}, rSize, sliceSize); radixBits is fixed
+ * at the build and used by every probe.
+ * Partition dR once (the passes of hj_prj_join_dev's R side) and keep the partitions resident in ctx.
+ * dR may be freed or overwritten after the call. Resets the counters; prjChecksum = R's PRO checksum. Async. */
+int hj_prj_build_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize);
+/* Radix-partition dS[0..sSize) with the resident R's radix bits and join it against R's partitions. Adds to
+ * totalMatches and sSize, like hj_probe_dev. Any sSize up to the one given to hj_reserve. Async.
+ * HJ_ERR_STATE without a resident R (no hj_prj_build_dev yet, or hj_prj_join_dev / hj_build_dev / hj_join_dev / an
+ * hj_reserve that reallocated since) or for an sSize above the reserved one. sSize 0 is a no-op. */
+int hj_prj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
+/* Host-visible facts about the resident build and the last probe (waits for the stream), out[8]:
+ * [0] R's path (0 exact, 1 histogram-free, 2 fell back), [1] last probe's S path (same coding),
+ * [2] join work items of the last probe, [3] partitions whose S side was split over > 1 item,
+ * [4] largest S partition of the last probe, [5] resident bytes held for R, [6..7] reserved (0). */
+int hj_prj_resident_info(hj_ctx *ctx, uint64_t out[8]);
 /* Build + probe of dR x dS by whatever hj_reserve was given: HJ_ALGO_NOCC/ATOMIC/HTM = hj_build_dev(idxBase 0) then
  * hj_probe_dev; HJ_ALGO_PRJ = hj_prj_join_dev; HJ_ALGO_AUTO = one locality pre-round over dR (k_sample_locality, one
  * small device->host read-back) and then one of the two. Asynchronous apart from that read-back. */
