@@ -56,28 +56,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_umin(
 
 __device__ __forceinline__ uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
 
-#ifndef HJ_OWN_PRIO
-#define HJ_OWN_PRIO 0
-#endif
-#ifndef HJ_OWN_PRIO_SHIFT
-#define HJ_OWN_PRIO_SHIFT 10
-#endif
-#ifndef HJ_OWN_MAX_ROUNDS
-#define HJ_OWN_MAX_ROUNDS 1                      // rounds of workgroups for large relations (see launch_build_own)
-#endif
-#ifndef HJ_OWN_MIN_CHUNK
-#define HJ_OWN_MIN_CHUNK 524288                  // tuples per chunk below which no further round is added
-#endif
-#ifndef HJ_DRAIN_INPLACE
-#define HJ_DRAIN_INPLACE 1
-#endif
-#ifndef HJ_LOOK_FIRST
-#define HJ_LOOK_FIRST 1
-#endif
-#ifndef HJ_DRAIN_AT
-#define HJ_DRAIN_AT 64
-#endif
-constexpr uint32_t kDrainAt = HJ_DRAIN_AT;            // run retry rounds once this many entries wait (<= 64)
+constexpr uint32_t kDrainAt = 64;                // run retry rounds once this many entries wait (<= 64)
 constexpr int kQCap = 128;                        // per-wavefront retry queue entries (LDS)
 
 // owner[blk]: 0 = free, otherwise (workgroup id + 1).
@@ -163,7 +142,7 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
         // look before leaping: read the next 4 slots when they sit in this (owned) block -- otherwise
         // read the block's first 4 slots and ignore them. Slot values only decrease, so a slot seen
         // below `mine` stays below it.
-        const bool inBlk = HJ_LOOK_FIRST && ((pos & (kBlkSlots - 1)) <= kBlkSlots - 4);
+        const bool inBlk = (pos & (kBlkSlots - 1)) <= kBlkSlots - 4;
         const uint32_t rd = work ? (inBlk ? pos : (pos & ~(kBlkSlots - 1))) : 0u;
         const uint64_t* w = &win[rd & (kWinSlots - 1)];
         const uint64_t v0 = w[0], v1 = w[1], v2 = w[2], v3 = w[3];
@@ -230,15 +209,11 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
     // stay in registers until they are done (no queue round trip between the sparse rounds: 852 -> 828 us on
     // `uniform` at 2^27; doing the same inside the dense rounds while >= 40/24/12 lanes stay busy was slower)
     auto drain = [&]() {
-#if HJ_DRAIN_INPLACE
         while (qCount > 64u) retry_round();
         bool act = lane < qCount;
         uint32_t pos = myQPos[lane], mlo = myQLo[lane], mhi = myQHi[lane];
         qCount = 0;
         while (__ballot(act)) act = round_body(pos, mlo, mhi, act);
-#else
-        while (qCount) retry_round();
-#endif
     };
 
     // Tile geometry: 3072 tuples, six per thread (round 3; 4096 before). A shorter tile's home slots span less of the 16-block
@@ -247,10 +222,7 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
     // slides and barriers per tuple; tiles of 2048: +5 % there, little more gained beyond). For the bucketised table, whose
     // keys spread 4/3 as wide (four slots per three keys), it is what makes W = 2^10 fit at all: 4.8 % of the tuples
     // deferred with tiles of 4096, 0.25 % with 3072 (build 1.58 -> 1.03 ms).
-#ifndef HJ_OWN_PER
-#define HJ_OWN_PER 6
-#endif
-    constexpr int PER = HJ_OWN_PER;
+    constexpr int PER = 6;
     constexpr int TILE = kOwnThreads * PER, SPAN = 64 * PER;
     // tile t covers chunk offsets [t*TILE, ...); this thread's tuple j sits at offset
     // t*TILE + wave*SPAN + 64 j + lane
@@ -267,14 +239,6 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
         uint32_t klo[PER], khi[PER];
 #pragma unroll
         for (int j = 0; j < PER; ++j) { klo[j] = (uint32_t)nxt[j]; khi[j] = (uint32_t)(nxt[j] >> 32); }
-#if HJ_OWN_PRIO
-        {   // the CU's two workgroup slots take turns at the higher issue priority (hj_build_wave.hip: oldest-first
-            // arbitration lets the workgroup a CU received first finish well before the second)
-            const uint32_t slot = (blockIdx.x / ((gridDim.x + 1u) / 2u)) & 1u;
-            if ((((uint32_t)(wall_clock64() >> HJ_OWN_PRIO_SHIFT)) + slot) & 1u) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         const bool full = tb + TILE <= clen;                      // wave-uniform
         const bool firstTile = tb == 0, lastTile = tb + TILE >= clen;
         if (!lastTile) {
@@ -781,10 +745,7 @@ static void own_geometry(uint64_t n, int nCU, uint64_t* nChunksOut, uint64_t* ch
 {
     // one chunk per resident workgroup (2 per CU: 76 KiB LDS each): a single wave of workgroups, no tail,
     // and the fewest chunk seams (measured: 512 chunks beat 768/1024/2048/4096 on MI355X)
-    const int resident = 2 * (nCU > 0 ? nCU : 256);
-    uint64_t rounds = n / ((uint64_t)resident * HJ_OWN_MIN_CHUNK);
-    rounds = rounds < 1 ? 1 : rounds > HJ_OWN_MAX_ROUNDS ? HJ_OWN_MAX_ROUNDS : rounds;
-    const uint64_t nChunks = (uint64_t)resident * rounds;
+    const uint64_t nChunks = 2 * (uint64_t)(nCU > 0 ? nCU : 256);
     uint64_t chunkLen = (n + nChunks - 1) / nChunks;
     chunkLen = (chunkLen + kOwnTile - 1) / kOwnTile * kOwnTile;
     if (chunkLen < (uint64_t)kOwnTile * 4) chunkLen = (uint64_t)kOwnTile * 4;

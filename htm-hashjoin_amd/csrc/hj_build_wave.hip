@@ -37,74 +37,28 @@
 
 namespace hj {
 
-#ifndef HJ_WV_THREADS
-#define HJ_WV_THREADS 256
-#endif
-constexpr int kWvThreads = HJ_WV_THREADS;           // 4 wavefronts per workgroup; they never synchronise
+constexpr int kWvThreads = 256;                     // 4 wavefronts per workgroup; they never synchronise
 constexpr int kWvWaves = kWvThreads / 64;
 constexpr uint32_t kGranShift = kWvGranShift;       // retire granule: 128 slots = 1 KiB = 64 lanes x 16 bytes
 constexpr uint32_t kGranSlots = 1u << kGranShift;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
-#ifndef HJ_WV_PER
-#define HJ_WV_PER 8
-#endif
-#ifndef HJ_WV_WINLOG
-#define HJ_WV_WINLOG 10
-#endif
-#ifndef HJ_WV_QCAP
-#define HJ_WV_QCAP 128
-#endif
-#ifndef HJ_WV_PF
-#define HJ_WV_PF 1
-#endif
-#ifndef HJ_WV_WPE
-#define HJ_WV_WPE 4                                 // wavefronts per SIMD the registers must allow (16 per CU: what the rings' LDS allows)
-#endif
-#ifndef HJ_WV_WAVES_PER_CU
-#define HJ_WV_WAVES_PER_CU 16                       // resident wavefronts per CU (what the rings' LDS allows)
-#endif
-#ifndef HJ_WV_MAX_ROUNDS
-#define HJ_WV_MAX_ROUNDS 8                          // chunks = resident wavefronts x rounds (wave_chunk_len below)
-#endif
-#ifndef HJ_WV_PRIO
-#define HJ_WV_PRIO 2                                // 2: issue priorities rotate in time among a CU's workgroup slots (0: off, 1: static, inverse to age)
-#endif
-#ifndef HJ_WV_PRIO_SHIFT
-#define HJ_WV_PRIO_SHIFT 10                         // rotation period = 2^shift ticks of the 100 MHz clock (10.24 us)
-#endif
-#ifndef HJ_WV_SKEW
-#define HJ_WV_SKEW 0                                // extra tiles per chunk: chunk starts off the power-of-two stride
-#endif
-#ifndef HJ_WV_MIN_CHUNK
-#define HJ_WV_MIN_CHUNK 32768                       // tuples: a second round of workgroups only while chunks stay this long
-#endif
-#ifndef HJ_WV_HICMP
-#define HJ_WV_HICMP 1                               // 1: slot values are compared by their index words (32-bit compares, half the look's LDS bytes)
-#endif
-#ifndef HJ_WV_ALLIN
-#define HJ_WV_ALLIN 1                               // 1: tiles wholly inside ring and range skip the per-tuple ring test
-#endif
-#ifndef HJ_WV_REQUEUE_FRONT
-#define HJ_WV_REQUEUE_FRONT 1                       // 1: unfinished retry entries return to the queue's front (0: to its tail)
-#endif
-#ifndef HJ_WV_CARRY
-#define HJ_WV_CARRY 1                               // 1: leave < 64 retry entries queued across tiles
-#endif
-constexpr int kWvPer = HJ_WV_PER;                   // tuples per lane per tile
-constexpr int kWvTile = 64 * kWvPer;
-constexpr int kWvPf = HJ_WV_PF;                     // tiles of R in flight per wavefront (register prefetch depth)
-constexpr uint32_t kWvWinLog = HJ_WV_WINLOG;
-constexpr uint32_t kWvWin = 1u << kWvWinLog;        // ring slots per wavefront
-constexpr uint32_t kWvGran = kWvWin >> kGranShift;  // ring granules
-constexpr uint32_t kWvQCap = HJ_WV_QCAP;            // retry queue entries per wavefront
-#ifndef HJ_WV_ROUNDAT
-#define HJ_WV_ROUNDAT 64
-#endif
-constexpr uint32_t kWvRoundAt = HJ_WV_ROUNDAT;      // a retry round runs once this many entries wait (<= 64)
-#ifndef HJ_WV_EXPERIMENT
-static_assert(kWvGran == kWvRingGran && kWvTile == (int)kWvTileTuples, "hj_device.h describes this geometry to the sampler");
-#endif
+// ring and tile geometry come from hj_device.h, which describes them to the locality sampler
+constexpr int kWvTile = (int)kWvTileTuples;
+constexpr int kWvPer = kWvTile / 64;                // tuples per lane per tile
+constexpr int kWvPf = 1;                            // tiles of R in flight per wavefront (register prefetch depth)
+constexpr uint32_t kWvGran = kWvRingGran;           // ring granules
+constexpr uint32_t kWvWin = kWvGran << kGranShift;  // ring slots per wavefront
+constexpr uint32_t kWvQCap = 128;                   // retry queue entries per wavefront
+constexpr uint32_t kWvRoundAt = 64;                 // a retry round runs once this many entries wait (<= 64)
+// wavefronts per SIMD the registers must allow (16 per CU: what the rings' LDS allows; the compact build fits in 115
+// VGPRs once the chunk state is scalar)
+constexpr int kWvWpe = 4;
+constexpr uint32_t kWvWavesPerCu = 16;              // resident wavefronts per CU (what the rings' LDS allows)
+constexpr uint32_t kWvMaxRounds = 8;                // chunks = resident wavefronts x rounds (wave_chunk_len below)
+constexpr uint32_t kWvMinChunk = 32768;             // tuples: a second round of workgroups only while chunks stay this long
+// issue priorities rotate in time among a CU's workgroup slots; period = 2^shift ticks of the 100 MHz clock (10.24 us)
+constexpr uint32_t kWvPrioShift = 10;
 static_assert(kWvQCap >= 128 && (kWvQCap & (kWvQCap - 1)) == 0, "FIFO ring: a power of two that takes one full step on top of < 64 waiting entries");
 constexpr size_t kWvLdsBytes = (size_t)kWvWaves * (kWvWin * sizeof(uint64_t) + 3 * kWvQCap * sizeof(uint32_t));
 
@@ -124,14 +78,11 @@ __device__ __forceinline__ unsigned long long wv_ballot(bool p) { return __built
 // this every seam cost ~70 deferred tuples on `uniform` (half a granule's worth), each a cascade of global atomics.
 // starts[c] = q (or p if no crossing shows up: many tuples per granule), raw[c] = the granule (kNone: no valid tuple).
 constexpr uint32_t kWvLook = 256;
-#ifndef HJ_WV_OVERLAP
-#define HJ_WV_OVERLAP 64
-#endif
-constexpr uint32_t kWvOverlap = HJ_WV_OVERLAP;
+constexpr uint32_t kWvOverlap = 64;
 // COMPACT build: positions before its seam a wavefront also reads (shadow zone), so that shadow zone + head zone are
 // exactly its first tile; and the crossers one seam may let in before the build gives up on the compact table
-constexpr uint32_t kWvShadow = 64 * HJ_WV_PER - HJ_WV_OVERLAP;
-constexpr uint32_t kWvTail = HJ_WV_OVERLAP;      // the last positions of a chunk whose next-range tuples the NEXT wavefront inserts
+constexpr uint32_t kWvShadow = kWvTile - kWvOverlap;
+constexpr uint32_t kWvTail = kWvOverlap;         // the last positions of a chunk whose next-range tuples the NEXT wavefront inserts
 constexpr uint32_t kWvPredCap = 64;
 template <bool KEY32, bool HTM>
 __global__ void __launch_bounds__(kBlock)
@@ -245,16 +196,6 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
     if (blockIdx.x == 0 && t == 0) bounds[nChunks] = numGran;
 }
 
-#ifdef HJ_WV_CLOCKS
-// Development builds only (tools/mk_variant.sh ... "-DHJ_WV_CLOCKS", tools/wave_clocks.py): when every chunk's wavefront
-// started and ended, in ticks of the 100 MHz wall clock. Not in the product library.
-__device__ uint32_t g_wvClk[2 * 65536];
-extern "C" int hj_debug_wave_clocks(uint32_t* out, uint32_t nChunks)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wvClk), (size_t)nChunks * 2 * sizeof(uint32_t));
-}
-#endif
-
 // ---- the build ------------------------------------------------------------------------------------------------
 // COMPACT (the fast path of the open-addressing table, hj_device.h "table formats"): the ring still holds (index << 32 | key),
 // but what leaves for HBM is the KEY WORD alone -- 4 bytes per slot instead of 8, and the probe reads 4 bytes per slot too.
@@ -273,10 +214,7 @@ extern "C" int hj_debug_wave_clocks(uint32_t* out, uint32_t nChunks)
 //   * anything else (a key far from its neighbours, a walk that wraps around the table end, key 0xFFFFFFFF = the compact
 //     empty pattern) raises the flag.
 template <bool KEY32, bool CHECK, bool HTM, bool COMPACT>
-#ifndef HJ_WV_WPE_COMPACT
-#define HJ_WV_WPE_COMPACT 4                         // COMPACT: wavefronts per SIMD the registers must allow (115 VGPRs once the chunk state is scalar)
-#endif
-__global__ void __launch_bounds__(kWvThreads, COMPACT ? HJ_WV_WPE_COMPACT : HJ_WV_WPE)
+__global__ void __launch_bounds__(kWvThreads, kWvWpe)
 k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_t nChunks, const uint32_t* __restrict__ starts,
              const uint32_t* __restrict__ bounds, uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift,
              uint32_t probeLen, uint64_t idxBase, ShardCheck sc, DeferredEntry* __restrict__ queue,
@@ -297,18 +235,13 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // whatever is written from here on is never looked at (k_wave_decide reads the flag before anything else)
         if (*reinterpret_cast<volatile unsigned long long*>(&ctr->compactFail)) return;
     }
-#ifdef HJ_WV_CLOCKS
-    if (lane == 0 && c < 65536) g_wvClk[2 * c] = (uint32_t)wall_clock64();
-#endif
     uint64_t* const win = lds + wave * kWvWin;                           // ring: slot s lives at win[s & (kWvWin - 1)]
     uint32_t* const myQPos = reinterpret_cast<uint32_t*>(lds + kWvWaves * kWvWin) + wave * 3 * kWvQCap;
     uint32_t* const myQLo = myQPos + kWvQCap;
     uint32_t* const myQHi = myQLo + kWvQCap;
 
-#if HJ_WV_PRIO
     // workgroups per quarter of the first, resident round (residentWG = what this device holds at once, from the launch)
     const uint32_t prioDiv = ((gridDim.x <= residentWG ? gridDim.x : residentWG) + 3u) / 4u;
-#endif
     const bool lastChunk = c + 1 == nChunks;
     const uint64_t cb0 = starts[c];
     const uint32_t clen = starts[c + 1] - starts[c];                     // the chunk proper: its tuples are counted here
@@ -358,9 +291,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     uint32_t winLoG = shadowOn ? loG - 1 : loG;  // ring = granules [winLoG, winLoG + kWvGran), wave-uniform
     uint32_t qCount = 0, qHead = 0;              // retry queue (FIFO ring): entries and position of the oldest, wave-uniform
     uint32_t rounds = 0;                         // retry rounds so far (wave-uniform)
-#ifdef HJ_WV_STATS
-    uint32_t forcedRounds = 0;                   // development builds: rounds forced by the ring's movement; reported through `deferred`
-#endif
     unsigned long long dropSum = 0, inSum = 0;
     uint32_t drops = 0, bad = 0, foreign = 0;
     uint32_t dCount = 0;                         // tuples deferred so far (wave-uniform)
@@ -375,9 +305,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         while (winLoG < target) {
             ulonglong2* src = reinterpret_cast<ulonglong2*>(win + ((winLoG & (kWvGran - 1)) << kGranShift)) + lane;
             const ulonglong2 t = *src;
-#if defined(HJ_WV_ABL_NOSTORE)
-            if (t.x == 0x1234567ull) table[lane] = t.y;        // ablation (development builds): the retire stores never happen
-#else
             if constexpr (COMPACT) {
                 // the key words alone leave: 512 bytes per granule (the empty pattern's low word is the compact empty
                 // pattern); the shadow granule belongs to the previous wavefront and is not written
@@ -393,7 +320,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 v2 vv; vv.x = t.x; vv.y = t.y;
                 __builtin_nontemporal_store(vv, reinterpret_cast<v2*>(table + ((uint64_t)winLoG << kGranShift)) + lane);
             }
-#endif
             *src = make_ulonglong2(kEmpty, kEmpty);
             ++winLoG;
         }
@@ -437,18 +363,12 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // together); slot values only decrease, so a slot seen below `mine` stays below it
         const bool inGran = (pos & (kGranSlots - 1)) <= kGranSlots - 4;
         const uint32_t rd = (work & inGran) ? pos : (winLoG << kGranShift);
-#if HJ_WV_HICMP
         // slot values are (index << 32 | key) with one index per tuple, the empty pattern has the highest index word: order
         // and equality of two values are those of their INDEX words. The look reads those alone (half the LDS bytes,
         // two ds_read2_b32) and every compare is a 32-bit one.
         const uint32_t* w = reinterpret_cast<const uint32_t*>(&win[rd & (kWvWin - 1)]) + 1;
         const uint32_t myIdx = mhi;
         const bool c0 = w[0] < myIdx, c1 = c0 & (w[2] < myIdx), c2 = c1 & (w[4] < myIdx), c3 = c2 & (w[6] < myIdx);
-#else
-        const uint64_t* w = &win[rd & (kWvWin - 1)];
-        const uint64_t v0 = w[0], v1 = w[1], v2 = w[2], v3 = w[3];
-        const bool c0 = v0 < mine, c1 = c0 & (v1 < mine), c2 = c1 & (v2 < mine), c3 = c2 & (v3 < mine);
-#endif
         uint32_t skip = (uint32_t)c0 + (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
         skip = (work & inGran) ? (skip < budget ? skip : budget) : 0u;
         pos = (pos + skip) & mask32; budget -= skip;
@@ -458,14 +378,9 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         unsigned long long old = kEmpty;
         if (doAtomic)
             old = atomicMin(reinterpret_cast<unsigned long long*>(&win[pos & (kWvWin - 1)]), (unsigned long long)mine);
-#if HJ_WV_HICMP
         const uint32_t oldIdx = (uint32_t)(old >> 32);
         const bool fail = doAtomic & (oldIdx != 0xFFFFFFFFu) & (oldIdx != myIdx);
         const bool disp = fail & (oldIdx > myIdx);                         // displaced a later tuple: carry it on
-#else
-        const bool fail = doAtomic & (old != kEmpty) & (old != mine);
-        const bool disp = fail & (old > mine);                             // displaced a later tuple: carry it on
-#endif
         mlo = disp ? (uint32_t)old : mlo; mhi = disp ? (uint32_t)(old >> 32) : mhi;
         bool dropped = drop0 | drop1;
         if constexpr (COMPACT) {
@@ -510,7 +425,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         return recheck | fail;
     };
     // The retry queue is a FIFO ring (oldest entries first): a round takes the up to 64 oldest entries, whatever is
-    // not finished goes back to the tail. With HJ_WV_CARRY the queue is NOT drained at the end of a tile: fewer than
+    // not finished goes back to the front. The queue is NOT drained at the end of a tile: fewer than
     // 64 entries wait for the next tile's failures, so that every round is dense (draining a tile to completion cost
     // ~10 sparse rounds per tile, more instructions than all the dense work together -- PMC, profiles/r02_*).
     auto retry_round = [&]() {
@@ -523,7 +438,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         qCount -= take;
         const bool again = round_body(pos, mlo, mhi, has);
         const unsigned long long am = wv_ballot(again);
-#if HJ_WV_REQUEUE_FRONT
         // what did not finish goes back to the queue's FRONT: an entry then gets its (at most probeLength) rounds one after
         // the other and is done while its slots are still far from the ring's tail, instead of waiting behind a tile's
         // worth of newer entries (COMPACT has no deferred phase: an entry the ring is about to leave behind costs a
@@ -535,13 +449,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             myQPos[at] = pos; myQLo[at] = mlo; myQHi[at] = mhi;
         }
         qCount += back;
-#else
-        if (again) {
-            const uint32_t at = (qHead + qCount + lane_rank(am)) & (kWvQCap - 1);
-            myQPos[at] = pos; myQLo[at] = mlo; myQHi[at] = mhi;
-        }
-        qCount += (uint32_t)__popcll(am);
-#endif
         ++rounds;
     };
     // to completion: dense rounds while more than a wavefront's worth is queued, then the last <= 64 entries stay in
@@ -585,9 +492,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             klo[j] = (uint32_t)nxt[p][j];
             khi[j] = KEY32 ? 0u : (uint32_t)((uint64_t)nxt[p][j] >> 32);
         }
-#if HJ_WV_PRIO
         {   // The CU arbitrates oldest wavefront first, and the four workgroups of a CU are dispatched one after the other:
-            // measured at 2^27 (tools/wave_clocks.py, every wavefront's start and end), the wavefronts of a CU's first
+            // measured at 2^27 (a development build recorded every wavefront's start and end), the wavefronts of a CU's first
             // workgroup took 349 us for their chunk, those of the second 380, the third 421, the fourth 470 -- the kernel
             // lasted 497 us and ran half empty for its last fifth. So every wavefront sets its issue priority per tile
             // from the wall clock: the four workgroup slots of a CU take turns at the top (10 us each). With it: 389 / 398 /
@@ -595,20 +501,12 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             // loss there. An input without retry rounds is memory bound and hardly reacts: the arbitration that is
             // unfair to its younger wavefronts is the memory system's.)
             const uint32_t slot = (blockIdx.x / prioDiv) & 3u;
-#if HJ_WV_PRIO == 1
-            const uint32_t pr = slot;
-            if (tb == 0) {
-#else
-            const uint32_t pr = ((uint32_t)(wall_clock64() >> HJ_WV_PRIO_SHIFT) + slot) & 3u;
-            {
-#endif
-                if (pr == 0) __builtin_amdgcn_s_setprio(0);
-                else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-                else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(3);
-            }
+            const uint32_t pr = ((uint32_t)(wall_clock64() >> kWvPrioShift) + slot) & 3u;
+            if (pr == 0) __builtin_amdgcn_s_setprio(0);
+            else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+            else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+            else __builtin_amdgcn_s_setprio(3);
         }
-#endif
         // wave-uniform: no shadow / head zone, no overlap zone (COMPACT: and no tail zone)
         if constexpr (COMPACT) {
             // somebody has raised the flag: nothing written from here on is ever looked at (every 8th tile: one scalar load)
@@ -696,7 +594,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 live[j] = ok;
                 if constexpr (FULL && COMPACT) {
                     // the bounds of a full tile were taken at its top (forced rounds)
-                } else if constexpr (FULL && HJ_WV_ALLIN) {
+                } else if constexpr (FULL) {
                     // full tiles take the bounds over every tuple, valid or not: an invalid key (the build fails with
                     // HJ_ERR_KEY_RANGE anyway) can only make the ring move less, and every access stays guarded
                     myMin = home[j] < myMin ? home[j] : myMin;
@@ -723,10 +621,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             target = target < gmin ? target : gmin;
             target = target < limG ? target : limG;
             advance(target);
-            if (HJ_WV_ALLIN) {
-                const uint32_t gmax = tmax >> kGranShift;
-                allIn = full & (gmin - winLoG < kWvGran) & (gmax - winLoG < kWvGran) & (gmax < limG);
-            }
+            const uint32_t gmax = tmax >> kGranShift;
+            allIn = full & (gmin - winLoG < kWvGran) & (gmax - winLoG < kWvGran) & (gmax < limG);
         }
 
         // ---- the PER home-slot attempts of the tile, issued together (independent LDS round trips) ----
@@ -751,15 +647,9 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             while (qCount >= kWvRoundAt) retry_round();                // dense rounds; leaves room for one full step
             const bool lv = live[j], ow = own[j];
             uint32_t mlo = klo[j], mhi = idx0 + tb + lane + 64 * j;
-#if HJ_WV_HICMP
             const uint32_t oldIdx = (uint32_t)(oldv[j] >> 32);
             const bool fail = ow & (oldIdx != 0xFFFFFFFFu);            // the slot was taken
             const bool disp = fail & (oldIdx > mhi);                   // ... by a later tuple: it moves on instead
-#else
-            const uint64_t mine = wv_pack(mhi, mlo);
-            const bool fail = ow & (oldv[j] != kEmpty);                // the slot was taken
-            const bool disp = fail & (oldv[j] > mine);                 // ... by a later tuple: it moves on instead
-#endif
             mlo = disp ? (uint32_t)oldv[j] : mlo; mhi = disp ? (uint32_t)(oldv[j] >> 32) : mhi;
             const uint32_t pos = fail ? ((home[j] + 1) & mask32) : home[j];
             const bool again = fail | (lv & !ow);                      // outside ring or range: the retry round defers it
@@ -772,7 +662,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 qCount += (uint32_t)__popcll(am);
             }
         }
-#if HJ_WV_CARRY
         if constexpr (COMPACT) {
             // Forced rounds. A queued entry whose slot the ring is about to leave behind would have to be deferred, and
             // there is no deferred phase: it gets its rounds now, at the end of the tile, where nothing of the tile is
@@ -806,9 +695,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 if (!need && qCount && tslot) {
                     const uint32_t qp = myQPos[(qHead + lane) & (kWvQCap - 1)];
                     need = wv_ballot((lane < qCount) & (qp < tslot)) != 0;
-#ifdef HJ_WV_STATS
-                    forcedRounds += need ? 1u : 0u;
-#endif
                 }
                 if (!need) break;
                 retry_round();
@@ -825,9 +711,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // an entry may wait for company for one tile, not longer (the ring moves on): no round during this tile -> one now
         if (qCount && rounds == roundsAtTileStart) retry_round();
         }
-#else
-        if (qCount) drain();                                           // before the ring may move on
-#endif
       }
     }
     if (qCount) drain();
@@ -848,19 +731,10 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         dCount = 0;                              // crossers are not deferred tuples: the next wavefront has inserted them
     }
 
-#ifdef HJ_WV_CLOCKS
-    if (lane == 0 && c < 65536) g_wvClk[2 * c + 1] = (uint32_t)wall_clock64();
-#endif
-#if HJ_WV_PRIO
     __builtin_amdgcn_s_setprio(0);               // the rotation's priority is not carried into the counter atomics
-#endif
     // counters: one atomic per wavefront
     unsigned long long c0 = drops, c3 = bad | ((unsigned long long)foreign << 32);
-#ifdef HJ_WV_STATS
-    const unsigned long long c4 = (unsigned long long)rounds | ((unsigned long long)forcedRounds << 32);
-#else
     const unsigned long long c4 = dCount;
-#endif
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         c0 += __shfl_down(c0, off, 64);
@@ -1091,7 +965,7 @@ void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s) { hipLaunchKer
 // ---- host side ----------------------------------------------------------------------------------------------------
 size_t wave_lds_bytes() { return kWvLdsBytes; }
 bool wave_supported(uint64_t tableSize) { return tableSize >= (uint64_t)kWvWin; }
-uint32_t wave_max_chunks(int nCU) { return (uint32_t)HJ_WV_WAVES_PER_CU * (uint32_t)HJ_WV_MAX_ROUNDS * (uint32_t)nCU; }
+uint32_t wave_max_chunks(int nCU) { return kWvWavesPerCu * kWvMaxRounds * (uint32_t)nCU; }
 size_t wave_bounds_bytes(int nCU) { return (6 * (size_t)wave_max_chunks(nCU) + 4) * sizeof(uint32_t); }   // raw, bounds (+1), starts (+1), dcounts, ccounts, pcounts
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen)
 {
@@ -1107,15 +981,15 @@ static uint64_t wave_chunk_len(uint64_t n, int nCU)
     // relations are cut into several rounds' worth of chunks and the hardware's workgroup dispatcher does the balancing
     // (a workgroup that finishes makes room for the next four chunks): 2^30 tuples in 4 x 4096 chunks 3.68 -> 3.49 ms,
     // in 8 x 4096 chunks 3.46 ms.
-    // Chunks stay >= HJ_WV_MIN_CHUNK tuples, though: every chunk pays for its ring (fill, final flush) and for two seam
+    // Chunks stay >= kWvMinChunk tuples, though: every chunk pays for its ring (fill, final flush) and for two seam
     // tiles, and at 2^27 two rounds of 16384-tuple chunks were 2 % SLOWER than one round, four rounds 6 % (32768 against
     // 65536 as the minimum: the same at 2^28, -2 % at 2^29, -1..3 % at 2^30; 16 rounds instead of 8: slower).
-    const uint32_t resident = (uint32_t)HJ_WV_WAVES_PER_CU * (uint32_t)nCU;
-    uint64_t rounds = n / ((uint64_t)resident * HJ_WV_MIN_CHUNK);
-    rounds = rounds < 1 ? 1 : rounds > HJ_WV_MAX_ROUNDS ? HJ_WV_MAX_ROUNDS : rounds;
+    const uint32_t resident = kWvWavesPerCu * (uint32_t)nCU;
+    uint64_t rounds = n / ((uint64_t)resident * kWvMinChunk);
+    rounds = rounds < 1 ? 1 : rounds > kWvMaxRounds ? kWvMaxRounds : rounds;
     const uint64_t chunks = (uint64_t)resident * rounds;
     uint64_t chunkLen = (n + chunks - 1) / chunks;
-    chunkLen = (chunkLen + kWvTile - 1) / kWvTile * kWvTile + (uint64_t)kWvTile * HJ_WV_SKEW;
+    chunkLen = (chunkLen + kWvTile - 1) / kWvTile * kWvTile;
     return chunkLen < (uint64_t)kWvTile * 4 ? (uint64_t)kWvTile * 4 : chunkLen;
 }
 static uint64_t wave_slice_len(uint64_t chunkLen) { return chunkLen + kWvLook + kWvOverlap; }
@@ -1158,7 +1032,7 @@ hipError_t launch_build_wave(const void* R, bool key32, uint64_t n, uint32_t hsh
     uint32_t* const pcounts = ccounts + maxChunks;
     const uint32_t numGran = (uint32_t)(tableSize >> kGranShift);
     // workgroups a device of nCU compute units holds at once (the rotation of issue priorities goes by it)
-    const uint32_t residentWG = (uint32_t)HJ_WV_WAVES_PER_CU * (uint32_t)(nCU > 0 ? nCU : 256) / (uint32_t)kWvWaves;
+    const uint32_t residentWG = kWvWavesPerCu * (uint32_t)(nCU > 0 ? nCU : 256) / (uint32_t)kWvWaves;
     hipError_t e;
     const dim3 gRaw((nChunks + 1 + kBlock / 64 - 1) / (kBlock / 64)), gMain((nChunks + kWvWaves - 1) / kWvWaves);
     if (parts & kWavePre) {

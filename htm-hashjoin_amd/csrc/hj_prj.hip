@@ -510,20 +510,10 @@ k_radix_scatter(const void* __restrict__ in, void* __restrict__ outv, PassParams
 //   No atomics, no scan, no second read: 12 B (pass 1) and 8 B (pass 2) per tuple instead of 20 and 12.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kMaxInFrags = 1024;     // pass-1 fragments one pass-2 chunk may span (C1 <= 1024)
-// workgroup geometry of the two passes: threads, elements per thread and tile, waves per SIMD the registers must allow
-#ifndef HJ_FRAG1_NT
-#define HJ_FRAG1_NT 1024
-#define HJ_FRAG1_E 32
-#define HJ_FRAG1_WPE 4
-#endif
-#ifndef HJ_FRAG1_LANECOL
-#define HJ_FRAG1_LANECOL 1                    // pass 1 ranks into per-(bin, lane column) counters (k_radix_scatter_frag)
-#endif
-#ifndef HJ_FRAG2_NT
-#define HJ_FRAG2_NT 512
-#define HJ_FRAG2_E 16
-#define HJ_FRAG2_WPE 4
-#endif
+// workgroup geometry of the two passes: threads, elements per thread and tile, waves per SIMD the registers must allow;
+// pass 1 ranks into per-(bin, lane column) counters (LANECOL, k_radix_scatter_frag)
+constexpr int kFrag1Threads = 1024, kFrag1Elems = 32, kFrag1Wpe = 4;
+constexpr int kFrag2Threads = 512, kFrag2Elems = 16, kFrag2Wpe = 4;
 
 struct FragPass {
     uint32_t C;              // chunks per input segment = fragments per output partition
@@ -1449,7 +1439,7 @@ hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const 
     hipLaunchKernelGGL(k_scan_add, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, gate);
     const uint32_t nOut = nSeg * fan + 1;
     hipLaunchKernelGGL(k_seg_offsets, dim3((nOut + kBlock - 1) / kBlock), dim3(kBlock), 0, s, p, w.hist, (uint32_t)n, segOut);
-    // instance choice measured at 2^30 (tools/prj_variants.sh, profiles/r01_prj_variants.txt): 512 threads x 16
+    // instance choice measured at 2^30 (profiles/r01_prj_variants.txt): 512 threads x 16
     // elements, no register prefetch, <= 128 VGPRs (2 workgroups per CU); more, smaller workgroups and the
     // prefetching instance were slower or equal
     if (evScatter0) (void)hipEventRecord(evScatter0, s);
@@ -1480,10 +1470,10 @@ hipError_t partition_relation_frag(const PrjPlan& pl, const PrjFrag& g, const Wo
     const uint32_t F1 = 1u << pl.bits1, F2 = 1u << pl.bits2;
     const FragPass p1{g.C1, 0u, F1, g.cap1, w.cnt1, (uint32_t)n, g.chunkLen1, 0u, 0u, nullptr};
     if (evS0) (void)hipEventRecord(evS0, s);
-    hipLaunchKernelGGL((k_radix_scatter_frag<false, HJ_FRAG1_NT, HJ_FRAG1_E, HJ_FRAG1_WPE, HJ_FRAG1_LANECOL != 0>), dim3(g.C1), dim3(HJ_FRAG1_NT), 0, s, static_cast<const void*>(in), tmp, p1, ctr);
+    hipLaunchKernelGGL((k_radix_scatter_frag<false, kFrag1Threads, kFrag1Elems, kFrag1Wpe, true>), dim3(g.C1), dim3(kFrag1Threads), 0, s, static_cast<const void*>(in), tmp, p1, ctr);
     if (evS1) (void)hipEventRecord(evS1, s);
     const FragPass p2{g.C2, pl.bits1, F2, g.cap2, cnt2, 0u, 0u, g.C1 / g.C2, g.cap1, w.cnt1};
-    hipLaunchKernelGGL((k_radix_scatter_frag<true, HJ_FRAG2_NT, HJ_FRAG2_E, HJ_FRAG2_WPE>), dim3(F1 * g.C2), dim3(HJ_FRAG2_NT), 0, s, static_cast<const void*>(tmp), out, p2, ctr);
+    hipLaunchKernelGGL((k_radix_scatter_frag<true, kFrag2Threads, kFrag2Elems, kFrag2Wpe>), dim3(F1 * g.C2), dim3(kFrag2Threads), 0, s, static_cast<const void*>(tmp), out, p2, ctr);
     return hipGetLastError();
 }
 }  // namespace
@@ -1510,10 +1500,7 @@ hipError_t launch_prj(const PrjPlan& pl, const PrjBuffers& buf, const uint64_t* 
     if (S && (e = partition_relation(pl, w, S, nS, tmp, partS, w.offS, exact, s)) != hipSuccess) return e;
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
     const uint32_t P = 1u << pl.radixBits;
-#ifndef HJ_JOIN_ROUNDS
-#define HJ_JOIN_ROUNDS 1
-#endif
-    const unsigned want = (unsigned)nCU * HJ_JOIN_ROUNDS;          // one persistent workgroup per CU (x rounds: development flag)
+    const unsigned want = (unsigned)nCU;                           // one persistent workgroup per CU
     const unsigned grid = P < want ? P : want;
     static_assert(kJoinSlots * 2 == 65536, "two 16-bit counters per LDS word cover every 16-bit key remainder");
     const PartView none{nullptr, nullptr, nullptr, 0u, 0u, 1u};
