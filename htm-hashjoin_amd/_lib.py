@@ -24,6 +24,8 @@ ALGO_IDS = {"nocc": HJ_ALGO_NOCC, "atomic": HJ_ALGO_ATOMIC, "htm": HJ_ALGO_HTM, 
             "auto": HJ_ALGO_AUTO}
 ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 
+HJ_FLAG_KEEP_ROW_IDS = 0x1      # hj_params.flags: open addressing never leaves the table in the compact 4-byte format
+
 
 class hj_params(C.Structure):
     _fields_ = [
@@ -35,7 +37,8 @@ class hj_params(C.Structure):
         ("radixBits", C.c_uint32),
         ("buildVariant", C.c_uint32),
         ("prjMode", C.c_uint32),
-        ("reserved", C.c_uint32 * 4),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
     ]
 
 
@@ -76,6 +79,8 @@ def _declare(lib):
         "hj_reserve": ([vp, P(hj_params), u64, u64], i32),
         "hj_build_dev": ([vp, vp, u64, u64], i32),
         "hj_probe_dev": ([vp, vp, u64], i32),
+        "hj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
+        "hj_pairs_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),

@@ -17,7 +17,7 @@
 using namespace hj;
 
 namespace {
-enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_COUNT };
+enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_PAIRS0, EV_PAIRS1, EV_COUNT };
 }
 
 struct hj_ctx {
@@ -61,6 +61,9 @@ struct hj_ctx {
     int* zipfRawHost[2] = {nullptr, nullptr}; int* zipfRawDev[2] = {nullptr, nullptr}; uint64_t zipfRawCap = 0;
     hipEvent_t zipfDone[2] = {nullptr, nullptr}; int zipfFlip = 0;
     uint32_t variantUsed = 1;
+    // materialising probe (hj_probe_pairs_dev): the output cursor on the device, the capacity of the last call
+    unsigned long long* dPairsCursor = nullptr;
+    uint64_t pairsCapacity = 0;
     // counters
     Counters* dCtr = nullptr;
     Counters* hCtr = nullptr;     // pinned
@@ -186,7 +189,9 @@ int create_common(int device, void* stream, bool own, hj_ctx** out)
               hipHostMalloc(reinterpret_cast<void**>(&c->hFit), 8 * sizeof(unsigned int)) == hipSuccess &&
               hipHostMalloc(reinterpret_cast<void**>(&c->hPreferred), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dPreferred), c->hPreferred, 0) == hipSuccess &&
-              hipMalloc(&c->boundsBuf, wave_bounds_bytes(c->nCU)) == hipSuccess;
+              hipMalloc(&c->boundsBuf, wave_bounds_bytes(c->nCU)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void**>(&c->dPairsCursor), sizeof(unsigned long long)) == hipSuccess &&
+              hipMemset(c->dPairsCursor, 0, sizeof(unsigned long long)) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }
     hipMemset(c->dCtr, 0, sizeof(Counters));
@@ -238,7 +243,7 @@ void hj_destroy(hj_ctx* c)
     zipf_release(c);
     if (c->stream || !c->ownStream) hipStreamSynchronize(c->stream);
     void* frees[] = {c->table, c->dCtr, c->tmpA, c->partR, c->partS, c->work, c->prjRes, c->stageR, c->stageS,
-                     c->ownerBuf, c->queueBuf, c->queueCount, c->fitCount, c->boundsBuf, c->htmConflicts, c->htmOwnCounts, c->htmOvfCount,
+                     c->ownerBuf, c->queueBuf, c->queueCount, c->fitCount, c->boundsBuf, c->dPairsCursor, c->htmConflicts, c->htmOwnCounts, c->htmOvfCount,
                      c->htmOvfBase, c->htmScan, c->htmOverflow, c->shard[0].work, c->shard[1].work,
                      c->shard[2].work, c->shard[3].work};
     for (void* p : frees) if (p) hipFree(p);
@@ -418,7 +423,8 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
                         c->capQueue >= own_queue_bytes(n);
     const bool canWave = n && wave_supported(tableSize) && c->capQueue >= wave_queue_bytes(n, c->nCU);
     const uint32_t pl = probe_len(c->params);
-    const bool canCompact = canWave && wave_compact_supported(tableSize, pl);
+    // HJ_FLAG_KEEP_ROW_IDS: the compact table drops the index words hj_probe_pairs_dev reads -- never tried, never picked
+    const bool canCompact = canWave && wave_compact_supported(tableSize, pl) && !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS);
     if (variant == 4 && !canCompact) variant = 3;
     if (variant == 3 && !canWave) variant = canOwn ? 2 : 1;
     if (variant == 2 && !canOwn) variant = 1;
@@ -670,6 +676,52 @@ int hj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
     if ((rc = record(c, EV_PROBE1))) return rc;
     HJ_HIP(c, hipGetLastError());
     c->sSize += sSize;
+    return HJ_OK;
+}
+
+int hj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
+                       uint64_t capacity)
+{
+    if (!c || (!dS && sSize)) return HJ_ERR_INVALID;
+    // decided on the host: whether the table keeps its index words is chosen on the device (Counters::tableFormat), so
+    // the call keys on what hj_reserve was promised
+    if (c->params.algo == HJ_ALGO_PRJ) return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: a PRJ context keeps no row ids");
+    if (!c->built) return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: no table (call hj_build_dev first)");
+    if (!c->htmBuilt && !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS))
+        return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: open-addressing context reserved without HJ_FLAG_KEEP_ROW_IDS");
+    if (capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: output pointer NULL with capacity > 0");
+    if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: S row range exceeds 2^32 - 1");
+    if (!c->htmBuilt && probe_len(c->params) > pairs_max_probe_len())
+        return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: probeLength above 8");
+    if (sSize == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    c->streamAtBuildEnd = false;
+    int rc;
+    HJ_HIP(c, hipMemsetAsync(c->dPairsCursor, 0, sizeof(unsigned long long), c->stream));
+    if ((rc = record(c, EV_PAIRS0))) return rc;
+    const PairsOut out{dOutS, dOutR, capacity, c->dPairsCursor};
+    if (c->htmBuilt) launch_htm_probe_pairs(dS, sSize, sIdxBase, c->table, c->htmBuckets, c->htmOverflow, out, c->nCU, c->dCtr, c->stream);
+    else launch_probe_pairs(dS, sSize, sIdxBase, c->table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr, c->stream);
+    if ((rc = record(c, EV_PAIRS1))) return rc;
+    HJ_HIP(c, hipGetLastError());
+    c->pairsCapacity = capacity;
+    c->sSize += sSize;
+    return HJ_OK;
+}
+
+int hj_pairs_info(hj_ctx* c, uint64_t out[4])
+{
+    if (c) c->streamAtBuildEnd = false;
+    if (!c || !out) return HJ_ERR_INVALID;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned long long found = 0;
+    HJ_HIP(c, hipMemcpy(&found, c->dPairsCursor, sizeof found, hipMemcpyDeviceToHost));
+    out[0] = found;
+    out[1] = found < c->pairsCapacity ? found : c->pairsCapacity;
+    out[2] = (uint64_t)(elapsed_us(c, EV_PAIRS0, EV_PAIRS1) + 0.5);
+    out[3] = 0;
     return HJ_OK;
 }
 

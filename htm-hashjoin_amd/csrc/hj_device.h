@@ -338,6 +338,17 @@ void launch_htm_sums(const uint64_t* table, uint32_t numBuckets, const uint64_t*
 size_t scan_workspace_words(uint64_t n);
 hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s);
 
+// ---- materialising probe (defined in hj_pairs.hip) --------------------------
+// where hj_probe_pairs_dev writes: the two gather-map planes, their length, and the 64-bit cursor the workgroups claim
+// their runs from (zeroed before the launch; its final value = pairs found, written or not)
+struct PairsOut { uint32_t* s; uint32_t* r; uint64_t capacity; unsigned long long* cursor; };
+uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
+// the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot
+void launch_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
+                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
+void launch_htm_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
+                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
+
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):
 // pass 1 cuts the relation into C1 chunks and writes bin b of chunk c to the fragment (b * C1 + c) of cap1 key slots;

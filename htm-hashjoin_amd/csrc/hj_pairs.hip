@@ -1,0 +1,422 @@
+// hj_pairs.hip -- the materialising probe for gfx950 (MI355X): HOT LOOP 2 with its result kept.
+//
+//   k_probe_pairs      the walk of k_probe (NoCCHashBuild.hpp:70-79) over the 8-byte slot table, one (S row, R row) pair
+//                      per match it counts; the R row is the index word the slot carries (index << 32 | key)
+//   k_htm_probe_pairs  the walk of k_htm_probe (HTMHashBuild.hpp:291-305): bucket, then the whole chain
+//
+// Output: two 4-byte planes (gather maps), filled from 0 without holes in no particular order. How a workgroup gets its
+// stretch of them is the whole design ("Materialising probe"): one returning atomic on one word serves about
+// 88 requests per microsecond chip-wide, so output space is claimed per STAGE, not per wavefront iteration. Every
+// workgroup collects its pairs in an LDS stage of kStagePairs pairs; a round (1024 S tuples, or one bucket of every
+// live chain) first agrees on its pair count -- wavefront scan, four totals exchanged through LDS, one barrier -- and
+// when the stage cannot take the round, the workgroup claims [base, base + fill) with ONE 64-bit atomicAdd and the stage
+// leaves LDS as 16-byte nontemporal stores over the aligned body of the run. That is the spill rule as well: a Zipf-hot
+// key whose chain has thousands of buckets just flushes more often; no lane ever buffers more than one bucket.
+// Pairs at or beyond `capacity` are counted (the cursor runs on) and not written: the check is per element.
+//
+// All integer work, bound by HBM and the table gather; no MFMA.
+
+#include "hj_device.h"
+
+namespace hj {
+
+namespace {
+
+constexpr uint32_t kStagePairs = 4096;          // pairs per stage: 2 planes x 16 KiB of LDS, four workgroups per CU
+constexpr uint32_t kWaves = kBlock / kWave;
+// A round must fit an empty stage (asserted where the rounds are shaped): 1024 S tuples x 4 slots at probeLength 4,
+// 512 x kMaxProbeLen at any other length, 1024 buckets x 3 tuples for htm
+constexpr uint32_t kMaxProbeLen = 8;
+
+typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+
+struct Stage {
+    uint32_t* s;                  // LDS: S rows of the staged pairs
+    uint32_t* r;                  // LDS: R rows
+    uint32_t* wtot;               // LDS [2][kWaves]: the wavefronts' pair counts of a round (bit 31: a lane has more to walk)
+    unsigned long long* base;     // LDS: where the run being flushed starts in the output
+    uint32_t fill;                // pairs staged (the same value in every thread)
+    uint32_t round;
+    unsigned long long found;     // pairs of this workgroup so far (the same value in every thread)
+};
+
+// lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity: the elements before the first 16-byte boundary of the
+// destination and after the last one by one lane each, the body as 16-byte stores. Written once, read by nobody here.
+__device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, uint32_t* __restrict__ out, uint64_t base, uint64_t capacity)
+{
+    if (base >= capacity) return;
+    const uint64_t room = capacity - base;
+    const uint32_t lim = room < cnt ? (uint32_t)room : cnt;           // elements of the run that exist in the output
+    uint32_t* const dst = out + base;
+    uint32_t lead = (uint32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
+    if (lead > lim) lead = lim;
+    if (threadIdx.x < lead) __builtin_nontemporal_store(lds[threadIdx.x], dst + threadIdx.x);
+    const uint32_t nv = (lim - lead) >> 2;
+    for (uint32_t v = threadIdx.x; v < nv; v += kBlock) {
+        const uint32_t i = lead + 4u * v;
+        u4 x;
+        x.x = lds[i]; x.y = lds[i + 1]; x.z = lds[i + 2]; x.w = lds[i + 3];
+        __builtin_nontemporal_store(x, reinterpret_cast<u4*>(dst + i));
+    }
+    const uint32_t tail = lead + 4u * nv;
+    if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
+}
+
+// Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
+__device__ __forceinline__ void stage_flush(Stage& st, const PairsOut& out)
+{
+    if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
+    __syncthreads();                                  // the base is there, and so is every pair of the rounds before
+    const uint64_t base = *st.base;
+    flush_plane(st.s, st.fill, out.s, base, out.capacity);
+    flush_plane(st.r, st.fill, out.r, base, out.capacity);
+    __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
+    st.fill = 0;
+}
+
+// One round: every lane brings m pairs (more: it has further buckets to walk). Returns the lane's position in the
+// stage; the lane then writes its m pairs there. anyMore: some lane of the workgroup has more. One barrier, two when the
+// stage is flushed first. The totals are double-buffered by round parity: a wavefront writes round k + 2's only after the
+// barrier of round k + 1, which every wavefront reaches after reading round k's.
+__device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out, uint32_t m, bool more, bool& anyMore)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    uint32_t inc = m;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t below = __shfl_up(inc, off, kWave);
+        if (lane >= (uint32_t)off) inc += below;
+    }
+    const bool waveMore = __ballot(more) != 0ull;
+    uint32_t* const wt = st.wtot + (st.round & 1u) * kWaves;
+    if (lane == kWave - 1) wt[w] = inc | (waveMore ? 0x80000000u : 0u);
+    __syncthreads();
+    uint32_t wbase = 0, tot = 0, any = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kWaves; ++k) {
+        const uint32_t v = wt[k], c = v & 0x7FFFFFFFu;
+        if (k < w) wbase += c;
+        tot += c;
+        any |= v >> 31;
+    }
+    st.round += 1;
+    anyMore = any != 0;
+    if (st.fill + tot > kStagePairs) stage_flush(st, out);            // workgroup-uniform
+    const uint32_t pos = st.fill + wbase + inc - m;
+    st.fill += tot;
+    st.found += tot;
+    return pos;
+}
+
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;  // valid in lane 0
+}
+
+// the end of both kernels: the last stage, then the workgroup's share of the counters (one atomic per workgroup and
+// counter: found is the same in every thread; the foreign counts are per lane)
+__device__ __forceinline__ void stage_finish(Stage& st, const PairsOut& out, uint32_t foreign, Counters* __restrict__ ctr)
+{
+    if (st.fill) stage_flush(st, out);
+    if (threadIdx.x == 0 && st.found) atomicAdd(&counter_shard(ctr)->matches, st.found);
+    foreign = wave_sum32(foreign);
+    if ((threadIdx.x & (kWave - 1)) == 0 && foreign) atomicAdd(&counter_shard(ctr)->foreign, (unsigned long long)foreign);
+}
+
+// ---------------------------------------------------------------------------
+// the S read of both kernels
+// ---------------------------------------------------------------------------
+// As probe_body of hj_kernels.hip: 16-byte nontemporal loads over the aligned body (two tuples each), the element before
+// and after it by one thread of workgroup 0. A round takes V such loads per lane (lane t of the workgroup: vectors
+// v0 + t, v0 + kBlock + t, ...), and the loads of the NEXT round are issued before this round's table lines are waited
+// for: a workgroup meets at a barrier every round, so what is not in flight before the barrier is latency paid per round.
+constexpr uint64_t kNoElement = ~0ull;          // payload bits set: matches nothing anywhere (a lane without an element)
+
+struct SBody { const u4* S4; uint64_t head, nv, tail; };
+
+__device__ __forceinline__ SBody s_body(const uint64_t* S, uint64_t n)
+{
+    SBody b;
+    b.head = ((16 - (reinterpret_cast<uintptr_t>(S) & 15)) & 15) / sizeof(uint64_t);
+    if (b.head > n) b.head = n;
+    b.S4 = reinterpret_cast<const u4*>(S + b.head);
+    b.nv = (n - b.head) >> 1;
+    b.tail = b.head + 2 * b.nv;
+    return b;
+}
+
+template <int V>
+__device__ __forceinline__ void load_vecs(const SBody& b, uint64_t v0, u4 (&t)[V])
+{
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
+        t[k].x = 0u; t[k].y = ~0u; t[k].z = 0u; t[k].w = ~0u;            // two times "no element"
+        if (v < b.nv) t[k] = __builtin_nontemporal_load(b.S4 + v);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// open addressing
+// ---------------------------------------------------------------------------
+// What the walk of one S element matched: bit j = slot home + j holds the key and no slot before it is empty;
+// first = the R row of the lowest such slot (the only one on unique keys; further ones are read again when written)
+struct Hit { uint32_t mask, first; const uint64_t* p; };
+
+// probe_one of hj_kernels.hip, remembering where it counted. sk with payload bits set matches nothing.
+// FOUR (probeLength 4): the window is loaded unconditionally (slack slots past the table end; an element that cannot
+// match reads the window at `dummy`), so that the windows of all of a lane's elements are in flight together.
+template <bool FOUR>
+__device__ __forceinline__ Hit walk(uint64_t sk, const uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift,
+                                    uint32_t probeLen, uint64_t validLo, uint64_t validHiEx, uint64_t dummy)
+{
+    const uint32_t key = (uint32_t)sk;
+    const uint64_t home = home_slot(key, hshift, mask);
+    const bool ok = (sk >> 32) == 0 && home >= validLo && home < validHiEx;
+    Hit h;
+    h.mask = 0; h.first = 0;
+    h.p = table + (ok ? home : dummy);
+    if constexpr (FOUR) {
+        const uint64_t a = h.p[0], b = h.p[1], c = h.p[2], d = h.p[3];
+        const bool ea = a != kEmpty, eb = ea && b != kEmpty, ec = eb && c != kEmpty, ed = ec && d != kEmpty;
+        const uint32_t m = (uint32_t)(ea && (uint32_t)a == key) | ((uint32_t)(eb && (uint32_t)b == key) << 1) |
+                           ((uint32_t)(ec && (uint32_t)c == key) << 2) | ((uint32_t)(ed && (uint32_t)d == key) << 3);
+        h.mask = ok ? m : 0u;
+        const uint64_t f = (m & 1u) ? a : (m & 2u) ? b : (m & 4u) ? c : d;
+        h.first = (uint32_t)(f >> 32);
+    } else if (ok) {
+        for (uint32_t j = 0; j < probeLen; ++j) {
+            const uint64_t v = h.p[j];
+            if (v == kEmpty) break;
+            if ((uint32_t)v == key) {
+                if (h.mask == 0) h.first = (uint32_t)(v >> 32);
+                h.mask |= 1u << j;
+            }
+        }
+    }
+    return h;
+}
+
+__device__ __forceinline__ void emit(Stage& st, uint32_t& pos, uint32_t sRow, const Hit& h)
+{
+    if (h.mask == 0) return;
+    st.s[pos] = sRow; st.r[pos] = h.first; ++pos;
+    for (uint32_t rest = h.mask & (h.mask - 1u); rest; rest &= rest - 1u) {      // duplicate keys in R
+        const uint32_t j = (uint32_t)__builtin_ctz(rest);
+        st.s[pos] = sRow; st.r[pos] = (uint32_t)(h.p[j] >> 32); ++pos;
+    }
+}
+
+struct OaTable { const uint64_t* table; uint64_t mask; uint32_t hshift, probeLen; uint64_t validLo, validHiEx, dummy; };
+
+// E elements per lane: walk them all, agree on the round's pair count, write the pairs into the stage
+template <int E, bool FOUR>
+__device__ __forceinline__ void oa_round(Stage& st, const PairsOut& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E])
+{
+    Hit h[E];
+    uint32_t m = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        h[e] = walk<FOUR>(sk[e], T.table, T.mask, T.hshift, T.probeLen, T.validLo, T.validHiEx, T.dummy);
+        m += (uint32_t)__popc(h[e].mask);
+    }
+    bool any;
+    uint32_t pos = stage_reserve(st, out, m, false, any);
+#pragma unroll
+    for (int e = 0; e < E; ++e) emit(st, pos, (uint32_t)row[e], h[e]);
+}
+
+template <int V, bool FOUR>
+__device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const OaTable& T,
+                                                 const ShardCheck& sc, const PairsOut& out, Counters* __restrict__ ctr)
+{
+    static_assert(2 * V * kBlock * (FOUR ? 4 : kMaxProbeLen) <= kStagePairs, "a round must fit an empty stage");
+    const SBody b = s_body(S, n);
+    uint32_t foreign = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock * V;
+    uint64_t v0 = (uint64_t)blockIdx.x * kBlock * V;
+    u4 cur[V];
+    load_vecs<V>(b, v0, cur);
+    // every thread of the workgroup runs the same number of rounds (they meet at barriers)
+    for (; v0 < b.nv; v0 += stride) {
+        u4 nxt[V];
+        load_vecs<V>(b, v0 + stride, nxt);
+        uint64_t sk[2 * V], row[2 * V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
+            sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
+            row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
+            if (v < b.nv) foreign += (uint32_t)is_foreign(cur[k].x, sc) + (uint32_t)is_foreign(cur[k].z, sc);
+        }
+        oa_round<2 * V, FOUR>(st, out, T, sk, row);
+#pragma unroll
+        for (int k = 0; k < V; ++k) cur[k] = nxt[k];
+    }
+    if (blockIdx.x == 0 && (b.head || b.tail < n)) {
+        uint64_t sk[2] = {kNoElement, kNoElement};
+        const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
+        if (threadIdx.x == 0) {
+            if (b.head) { sk[0] = S[0]; foreign += is_foreign((uint32_t)sk[0], sc); }
+            if (b.tail < n) { sk[1] = S[b.tail]; foreign += is_foreign((uint32_t)sk[1], sc); }
+        }
+        oa_round<2, FOUR>(st, out, T, sk, row);
+    }
+    stage_finish(st, out, foreign, ctr);
+}
+
+}  // namespace
+
+// probeLength 4 (the reference's default): four elements per lane and round, all sixteen window loads in flight;
+// any other length: two elements, the walk with its early exit
+__global__ void __launch_bounds__(kBlock)
+k_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint64_t mask,
+              uint32_t hshift, uint32_t probeLen, ShardCheck sc, PairsOut out, Counters* __restrict__ ctr)
+{
+    __shared__ uint32_t ldsS[kStagePairs], ldsR[kStagePairs], ldsTot[2 * kWaves];
+    __shared__ unsigned long long ldsBase;
+    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull};
+    OaTable T{table, mask, hshift, probeLen, ctr->validLo, ctr->validHiEx, 0};
+    T.dummy = T.validLo < mask ? T.validLo : 0;          // any in-table slot; this one is in cache
+    if (probeLen == 4) probe_pairs_body<2, true>(st, S, n, sIdxBase, T, sc, out, ctr);
+    else probe_pairs_body<1, false>(st, S, n, sIdxBase, T, sc, out, ctr);
+}
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// --algo htm: bucket, then the whole chain, one bucket per element and round
+// ---------------------------------------------------------------------------
+// the bucket a walk stands at (nullptr: done), and what the last bucket read matched
+struct ChainWalk { const ulonglong2* p; uint32_t key, sRow, m, r0, r1, r2; };
+
+__device__ __forceinline__ void chain_step(ChainWalk& c, const uint64_t* __restrict__ overflow)
+{
+    c.m = 0;
+    if (c.p == nullptr) return;
+    const ulonglong2 a = c.p[0], b = c.p[1];
+    const bool h0 = a.x != kEmpty && (uint32_t)a.x == c.key, h1 = a.y != kEmpty && (uint32_t)a.y == c.key,
+               h2 = b.x != kEmpty && (uint32_t)b.x == c.key;
+    const uint32_t v0 = (uint32_t)(a.x >> 32), v1 = (uint32_t)(a.y >> 32), v2 = (uint32_t)(b.x >> 32);
+    // the matching R rows, packed to the front (r0 .. r[m - 1])
+    c.m = (uint32_t)h0 + (uint32_t)h1 + (uint32_t)h2;
+    c.r0 = h0 ? v0 : h1 ? v1 : v2;
+    c.r1 = (h0 && h1) ? v1 : v2;
+    c.r2 = v2;
+    const uint32_t next = b.y == kEmpty ? 0u : (uint32_t)(b.y >> 32);      // slot 3 = next << 32 | count, all ones = no chain
+    c.p = next ? reinterpret_cast<const ulonglong2*>(overflow + ((uint64_t)next << 2)) : nullptr;
+}
+
+__device__ __forceinline__ void chain_emit(Stage& st, uint32_t& pos, const ChainWalk& c)
+{
+    if (c.m > 0) { st.s[pos] = c.sRow; st.r[pos] = c.r0; ++pos; }
+    if (c.m > 1) { st.s[pos] = c.sRow; st.r[pos] = c.r1; ++pos; }
+    if (c.m > 2) { st.s[pos] = c.sRow; st.r[pos] = c.r2; ++pos; }
+}
+
+struct HtmTable { const uint64_t* table; const uint64_t* overflow; uint32_t bucketMask; uint64_t defLo, defHi; };
+
+// E elements per lane: bucket rounds until the longest chain of the workgroup's elements has ended; lanes whose chains
+// have ended idle through them
+template <int E>
+__device__ __forceinline__ void htm_rounds(Stage& st, const PairsOut& out, const HtmTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E])
+{
+    ChainWalk c[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        c[e].key = (uint32_t)sk[e]; c[e].sRow = (uint32_t)row[e]; c[e].m = 0; c[e].r0 = c[e].r1 = c[e].r2 = 0;
+        const uint64_t slot = (uint64_t)((c[e].key / 3u) & T.bucketMask) << 2;
+        const bool ok = (sk[e] >> 32) == 0 && sk[e] != 0 && slot >= T.defLo && slot + 3 < T.defHi;      // else: equals no stored tuple
+        c[e].p = ok ? reinterpret_cast<const ulonglong2*>(T.table + slot) : nullptr;
+    }
+    bool any;
+    do {
+        uint32_t m = 0;
+        bool more = false;
+#pragma unroll
+        for (int e = 0; e < E; ++e) { chain_step(c[e], T.overflow); m += c[e].m; more = more || c[e].p != nullptr; }
+        uint32_t pos = stage_reserve(st, out, m, more, any);
+#pragma unroll
+        for (int e = 0; e < E; ++e) chain_emit(st, pos, c[e]);
+    } while (any);
+}
+
+constexpr int kHtmVecs = 2;       // four elements per lane and round: at most 12 pairs per lane, 3072 per round
+static_assert(2 * kHtmVecs * kBlock * 3 <= kStagePairs, "a round must fit an empty stage");
+
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock)
+k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint32_t bucketMask,
+                  const uint64_t* __restrict__ overflow, PairsOut out, Counters* __restrict__ ctr)
+{
+    constexpr int V = kHtmVecs;
+    __shared__ uint32_t ldsS[kStagePairs], ldsR[kStagePairs], ldsTot[2 * kWaves];
+    __shared__ unsigned long long ldsBase;
+    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull};
+    // buckets outside the slots the build defined were never written and hold no tuple (hj_device.h, Counters)
+    const HtmTable T{table, overflow, bucketMask, ctr->validLo, ctr->validHiEx + 512};
+    const SBody b = s_body(S, n);
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock * V;
+    uint64_t v0 = (uint64_t)blockIdx.x * kBlock * V;
+    u4 cur[V];
+    load_vecs<V>(b, v0, cur);
+    for (; v0 < b.nv; v0 += stride) {
+        u4 nxt[V];
+        load_vecs<V>(b, v0 + stride, nxt);
+        uint64_t sk[2 * V], row[2 * V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
+            sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
+            row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
+        }
+        htm_rounds<2 * V>(st, out, T, sk, row);
+#pragma unroll
+        for (int k = 0; k < V; ++k) cur[k] = nxt[k];
+    }
+    if (blockIdx.x == 0 && (b.head || b.tail < n)) {
+        uint64_t sk[2] = {kNoElement, kNoElement};
+        const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
+        if (threadIdx.x == 0) {
+            if (b.head) sk[0] = S[0];
+            if (b.tail < n) sk[1] = S[b.tail];
+        }
+        htm_rounds<2>(st, out, T, sk, row);
+    }
+    stage_finish(st, out, 0u, ctr);
+}
+
+namespace {
+
+// four workgroups of 32 KiB of LDS per CU, the rest of S by grid stride; vecs = 16-byte loads per lane and round
+unsigned pairs_grid(uint64_t n, int nCU, int vecs)
+{
+    const uint64_t perBlock = 2ull * kBlock * (uint64_t)vecs;
+    uint64_t blocks = (n + perBlock - 1) / perBlock;
+    const uint64_t most = (uint64_t)(nCU > 0 ? nCU : 256) * 4u;
+    if (blocks > most) blocks = most;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+}  // namespace
+
+uint32_t pairs_max_probe_len() { return kMaxProbeLen; }
+
+void launch_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
+                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_probe_pairs, dim3(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1)), dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift,
+                       probeLen, sc, out, ctr);
+}
+
+void launch_htm_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
+                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_htm_probe_pairs, dim3(pairs_grid(n, nCU, kHtmVecs)), dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1,
+                       overflow, out, ctr);
+}
+
+}  // namespace hj

@@ -61,12 +61,13 @@ def generate_relation(kind, num_tuples, maxid=None, local_shuffle_range=0, zipf_
 
 
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
-            buildVariant=0, prjMode=0):
+            buildVariant=0, prjMode=0, keepRowIds=False):
     p = hj_params()
     p.algo = _lib.ALGO_IDS[algo]
     p.scaleOutput, p.numPartitions, p.probeLength = scaleOutput, numPartitions, probeLength
     p.transactionSize, p.radixBits, p.buildVariant = transactionSize, radixBits, buildVariant
     p.prjMode = prjMode
+    p.flags = _lib.HJ_FLAG_KEEP_ROW_IDS if keepRowIds else 0
     return p
 
 
@@ -127,6 +128,22 @@ class HashJoinContext:
 
     def probe(self, dS_ptr, sSize):
         self._check(lib.hj_probe_dev(self._h, C.c_void_p(dS_ptr), sSize))
+
+    def probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0):
+        """hj_probe_pairs_dev: the probe with its result kept. For every match the probe counts, one pair
+        d_out_s[k] = s_idx_base + position in dS, d_out_r[k] = global input index of the matching R tuple (two device
+        uint32 arrays of `capacity` entries; pairs beyond it are counted, not written). Open addressing needs
+        reserve(..., keepRowIds=True). Adds to totalMatches and sSize like probe()."""
+        self._check(lib.hj_probe_pairs_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
+                                           C.c_void_p(d_out_s) if d_out_s else None,
+                                           C.c_void_p(d_out_r) if d_out_r else None, capacity))
+
+    def pairs_info(self):
+        """hj_pairs_info (waits for the stream): (pairs the last probe_pairs found, pairs it wrote, its device time in
+        microseconds, 0)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_pairs_info(self._h, out))
+        return tuple(int(x) for x in out)
 
     def prj_join(self, dR_ptr, rSize, dS_ptr, sSize):
         self._check(lib.hj_prj_join_dev(self._h, C.c_void_p(dR_ptr), rSize,
@@ -282,6 +299,53 @@ def HTMHashBuild(relR, rSize, relS=None, sSize=0, transactionSize=16, scaleOutpu
     out["outputSum"] = r["outputSum"]
     out["detail"] = r
     return out
+
+
+def join_pairs(relR, relS, algo="htm", probeLength=4, device=0):
+    """The join as two gather maps: (s_idx, r_idx), numpy uint32 arrays of equal length, row k of the result being
+    (relS[s_idx[k]], relR[r_idx[k]]). The order of the rows is unspecified. algo = "htm" (the default): the complete
+    equi-join, duplicate keys included, any len(relR). "atomic" / "nocc": the reference's budgeted open-addressing
+    semantics (an R tuple that ran out of probeLength is not in the table, a walk ends at the first empty slot;
+    len(relR) a power of two).
+    Sizing: the outputs start with len(relS) entries each (exact for a foreign-key join); if the probe reports more
+    pairs than that, they are enlarged to the reported count and the probe runs once more."""
+    if algo not in ("htm", "atomic", "nocc"):
+        raise ValueError(f"join_pairs: algo must be htm, atomic or nocc, not {algo!r}")
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    empty = np.empty(0, dtype=np.uint32)
+    if relR.size == 0 or relS.size == 0:
+        return empty, empty.copy()
+    with HashJoinContext(device) as ctx:
+        held = []
+
+        def alloc(nbytes):
+            held.append(ctx.dev_alloc(nbytes))
+            return held[-1]
+
+        try:
+            ctx.reserve(algo, relR.size, relS.size, probeLength=probeLength, keepRowIds=True)
+            dR, dS = alloc(relR.nbytes), alloc(relS.nbytes)
+            ctx.copy_h2d(dR, relR)
+            ctx.copy_h2d(dS, relS)
+            ctx.build(dR, relR.size)
+            capacity = relS.size
+            while True:
+                d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+                ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity)
+                found, written = ctx.pairs_info()[:2]
+                if found <= capacity:
+                    break
+                capacity = found
+            ctx.fetch()             # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
+            s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
+            if written:
+                ctx.copy_d2h(s_idx, d_s)
+                ctx.copy_d2h(r_idx, d_r)
+        finally:
+            for p in held:
+                ctx.dev_free(p)
+    return s_idx, r_idx
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

@@ -94,8 +94,14 @@ typedef struct {
                                  sized for uniform low key bits, checked; the exact passes of
                                  parallel_radix_join.c:586-626 run instead when one overflows);
                                  1 = exact passes only; 2 = as 0 at any size that can be laid out   */
-    uint32_t reserved[4];
+    uint32_t flags;           /* HJ_FLAG_* bits; 0 = none                        */
+    uint32_t reserved[3];
 } hj_params;
+
+/* hj_params.flags. Open addressing: never leave the table in the compact 4-byte format, so that every slot keeps the
+ * input index of its tuple for hj_probe_pairs_dev (buildVariant 4 runs as 3; buildVariant 0 neither enqueues nor picks
+ * 4). No effect on HJ_ALGO_HTM, whose table always keeps the indices, and on HJ_ALGO_PRJ. */
+#define HJ_FLAG_KEEP_ROW_IDS 0x1u
 
 /* Everything the reference prints in its JSON line (NoCCHashBuild.hpp:127-146,
  * AtomicHashBuild.hpp:133-152) plus device timings. */
@@ -190,6 +196,21 @@ int hj_build_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize, uint64_t idxBa
 /* HOT LOOP 2 (NoCCHashBuild.hpp:66-80): probes dS[0..sSize) against the table
  * of the last hj_build_dev and accumulates totalMatches. Asynchronous. */
 int hj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
+/* HOT LOOP 2 with its result kept: probes dS[0..sSize) like hj_probe_dev and, for every match it counts, writes one
+ * pair  dOutS[k] = sIdxBase + (position in dS),  dOutR[k] = global input index of the matching R tuple
+ * (idxBase + position, as given to hj_build_dev). The two arrays are gather maps into S and R: row k of the join is
+ * (S[dOutS[k]], R[dOutR[k]]). Pairs fill dOut*[0 .. written) without holes; every call starts at 0; pairs beyond
+ * `capacity` are counted but not written. The order of the pairs is unspecified; the multiset is exact. What an S
+ * tuple matches is what hj_probe_dev counts for it: open addressing = the reference's walk (at most probeLength slots
+ * from the home slot, stop at the first empty one), HJ_ALGO_HTM = bucket plus whole chain, i.e. the complete
+ * equi-join. Adds to totalMatches and sSize exactly as hj_probe_dev does. Asynchronous.
+ * HJ_ERR_STATE: no table; a PRJ context; an open-addressing context reserved without HJ_FLAG_KEEP_ROW_IDS.
+ * HJ_ERR_INVALID: an output pointer NULL with capacity > 0, or sIdxBase + sSize > 2^32 - 1. sSize 0 is a no-op. */
+int hj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
+                       uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
+/* Waits for the stream. out[0] = pairs the last hj_probe_pairs_dev found, out[1] = pairs it wrote
+ * (= min(out[0], capacity)), out[2] = its device time in microseconds (rounded), out[3] = 0. */
+int hj_pairs_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */

@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Times the materialising probe against the counting probe on the same table and the same S, through the C ABI, no
+torch: development tool.
+
+    python tools/pairs_bench.py [--log2n 27] [--reps 10] [--counting-only]
+
+One context, |R| = |S| = 2^log2n, R = local_shuffle W=16. Per configuration one JSON line with the median HIP-event
+times over `reps` launches after one warm-up launch of
+  (a) hj_probe_dev                                   -> probe_us
+  (b) hj_probe_pairs_dev into two |pairs|-sized maps -> pairs_us, ratio = (b) / (a), out_GBps = 8 B x pairs / (b)
+Configurations: atomic (HJ_FLAG_KEEP_ROW_IDS) x sorted S and htm x sorted S (every S tuple matches once: the
+write-heaviest unique-key case), htm x Zipf(0.9) S.
+claims = output runs claimed from the cursor per launch, from the kernel's geometry: a workgroup claims when its LDS stage
+of 4096 pairs cannot take the next round, and once more at its end (pairs / 4096 + workgroups when every round is full).
+--counting-only runs (a) alone and uses nothing newer than hj_probe_dev (the 8-byte table is then asked for with
+buildVariant 3): the same script times the yardstick on a checkout that has no materialising probe."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+import htm_hashjoin_amd as hj  # noqa: E402
+
+STAGE_PAIRS, WORKGROUPS = 4096, 256 * 4
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2n", type=int, default=27)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--theta", type=float, default=0.9)
+    ap.add_argument("--counting-only", action="store_true")
+    ap.add_argument("--tag", default="")
+    a = ap.parse_args()
+    n = 1 << a.log2n
+    with hj.HashJoinContext(0) as c:
+        dR, dS, dZ = c.dev_alloc(n * 8), c.dev_alloc(n * 8), c.dev_alloc(n * 8)
+        R = hj.generate_data("local_shuffle", n, n, 16)
+        c.copy_h2d(dR, R)
+        del R
+        c.copy_h2d(dS, np.arange(1, n + 1, dtype=np.uint64))
+        c.zipf_open(n, a.theta, 54321)
+        c.zipf_next(n, dZ)
+        c.zipf_close()
+        c.synchronize()
+        configs = [("atomic", "sorted", dS), ("htm", "sorted", dS), ("htm", "zipf", dZ)]
+        if a.counting_only:
+            configs.insert(0, ("atomic-default", "sorted", dS))
+        for algo, sname, dProbe in configs:
+            if algo == "atomic-default":
+                c.reserve("atomic", n, n)                           # the device's pick: the compact 4-byte table here
+            elif algo == "atomic":
+                kw = {"buildVariant": 3} if a.counting_only else {"keepRowIds": True}
+                c.reserve("atomic", n, n, **kw)
+            else:
+                c.reserve("htm", n, n)
+            c.build(dR, n)
+            probe_us = []
+            for _ in range(a.reps + 1):
+                c.probe(dProbe, n)
+                probe_us.append(c.fetch()["probe_us"])
+            res = c.fetch()
+            row = {"tag": a.tag, "algo": algo, "S": sname, "log2n": a.log2n, "buildVariant": res["buildVariant"],
+                   "matches_per_probe": res["totalMatches"] // (a.reps + 1),
+                   "probe_us": round(statistics.median(probe_us[1:]), 1), "probe_us_min": round(min(probe_us[1:]), 1)}
+            if not a.counting_only:
+                pairs = row["matches_per_probe"]
+                dOutS, dOutR = c.dev_alloc(4 * pairs + 16), c.dev_alloc(4 * pairs + 16)
+                pairs_us = []
+                for _ in range(a.reps + 1):
+                    c.probe_pairs(dProbe, n, dOutS, dOutR, pairs)
+                    found, written, us, _ = c.pairs_info()
+                    assert found == written == pairs, (found, written, pairs)
+                    pairs_us.append(us)
+                c.dev_free(dOutS)
+                c.dev_free(dOutR)
+                med = statistics.median(pairs_us[1:])
+                row.update({"pairs": pairs, "pairs_us": med, "pairs_us_min": min(pairs_us[1:]),
+                            "ratio": round(med / row["probe_us"], 3), "out_GBps": round(8.0 * pairs / med / 1e3, 1),
+                            "claims": pairs // STAGE_PAIRS + min(WORKGROUPS, (n // 2 + 256) // 256)})
+            print(json.dumps(row), flush=True)
+        for p in (dR, dS, dZ):
+            c.dev_free(p)
+
+
+if __name__ == "__main__":
+    main()
