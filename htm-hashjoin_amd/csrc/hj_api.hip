@@ -18,6 +18,33 @@ using namespace hj;
 
 namespace {
 enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_PAIRS0, EV_PAIRS1, EV_COUNT };
+// every device buffer the library owns (hj_ctx::buf)
+enum Buf {
+    B_CTR, B_TABLE,
+    B_OWNER, B_QUEUE,           // ownership build (variant 2) / deferred queue of variants 2 and 3
+    B_QUEUE_COUNT,              // kOwnMaxChunks words, deferred tuples per phase-A workgroup of the window build
+    B_FIT,                      // kSampleWords words (launch_sample_locality)
+    B_BOUNDS,                   // variant 3: per-chunk slot ranges (wave_bounds_bytes)
+    B_HTM_CONFLICTS, B_HTM_OWN_COUNTS,          // htm: conflicts listed per chunk; their counts in the window build
+    B_HTM_OVF_COUNT, B_HTM_OVF_BASE, B_HTM_SCAN,
+    B_HTM_OVERFLOW,             // overflow buckets (index 0 unused)
+    B_PAIRS_CURSOR,             // materialising probe (hj_probe_pairs_dev): the output cursor
+    B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
+    B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
+    B_STAGE_R, B_STAGE_S,       // staging for hj_run
+    B_SHARD0, B_SHARD1, B_SHARD2, B_SHARD3,     // work buffer of hj_ctx::shard[i]
+    B_COUNT
+};
+
+// One device buffer; the capacity is in bytes, always.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    // at least `need` bytes. A buffer that is too small is freed and allocated anew: its content is lost, and *replaced
+    // is set (left alone otherwise)
+    int reserve(hj_ctx* c, size_t need, bool* replaced = nullptr);
+};
 }
 
 struct hj_ctx {
@@ -26,9 +53,9 @@ struct hj_ctx {
     hipStream_t stream = nullptr;
     bool ownStream = false;
     hj_params params{};
-    // open-addressing table
-    uint64_t* table = nullptr;
-    uint64_t tableCapSlots = 0;   // allocated slots incl. slack
+    DevBuf buf[B_COUNT];          // hj_destroy frees exactly these
+    Counters* dCtr() const { return buf[B_CTR].as<Counters>(); }     // the counters: allocated at creation, used by every call
+    // open-addressing table (buf[B_TABLE]: the slots incl. slack)
     uint64_t tableSize = 0;       // live table (2*rSize) of the last build
     uint32_t hshift = 0;             // home-slot shift of the current table (hj_device.h); 0 unless it is a radix shard
     ShardCheck sc{0, 0, 0, 0};       // hj_set_shard_check; mask 0 = off
@@ -36,24 +63,14 @@ struct hj_ctx {
     bool built = false;
     bool probeStartsAtBuildEnd = false;         // the probe was enqueued right behind the build on the library's own stream: EV_BUILD1 is its start
     bool streamAtBuildEnd = false;              // nothing has been enqueued since EV_BUILD1 (own stream only)
-    // ownership build (variant 2)
-    void* ownerBuf = nullptr; size_t capOwner = 0;
-    void* queueBuf = nullptr; size_t capQueue = 0;
-    uint32_t* queueCount = nullptr;             // device: kOwnMaxChunks words, deferred tuples per phase-A workgroup of the window build
-    unsigned int* fitCount = nullptr;           // device, kSampleWords words (launch_sample_locality)
     unsigned int* hFit = nullptr;               // pinned
     unsigned long long* hPreferred = nullptr;   // pinned: Counters::preferred of the last device-side pick (0: none yet)
     unsigned long long* dPreferred = nullptr;   // the same word as the device addresses it (the sampler stores into it)
-    void* boundsBuf = nullptr;                  // variant 3: per-chunk slot ranges (wave_bounds_bytes)
-    // bucketised table of --algo htm (hj_htm.hip): the table itself lives in `table` (4 slots per bucket)
+    // bucketised table of --algo htm (hj_htm.hip): the table itself lives in buf[B_TABLE] (4 slots per bucket)
     bool htmBuilt = false;
     bool htmGenericChains = false;              // build_htm's second attempt: no routing, generic chain kernels
     bool htmChainsFellBack = false;             // ... and that it happened (hj_result.compactFallback bit 8)
     uint32_t htmBuckets = 0;                    // numBuckets of the last htm build
-    uint64_t* htmConflicts = nullptr; size_t capHtmConflicts = 0;       // bytes
-    uint32_t* htmOwnCounts = nullptr; size_t capHtmOwnCounts = 0;        // bytes: conflicts listed per chunk of the window build
-    unsigned int* htmOvfCount = nullptr; uint32_t* htmOvfBase = nullptr; uint32_t* htmScan = nullptr; uint64_t capHtmBuckets = 0;
-    uint64_t* htmOverflow = nullptr; uint64_t capHtmOverflow = 0;       // overflow buckets (index 0 unused)
     uint64_t htmOverflowUsed = 0;
     // streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev)
     hjhost::GlibcRand* zipfRng = nullptr;
@@ -61,35 +78,23 @@ struct hj_ctx {
     int* zipfRawHost[2] = {nullptr, nullptr}; int* zipfRawDev[2] = {nullptr, nullptr}; uint64_t zipfRawCap = 0;
     hipEvent_t zipfDone[2] = {nullptr, nullptr}; int zipfFlip = 0;
     uint32_t variantUsed = 1;
-    // materialising probe (hj_probe_pairs_dev): the output cursor on the device, the capacity of the last call
-    unsigned long long* dPairsCursor = nullptr;
-    uint64_t pairsCapacity = 0;
-    // counters
-    Counters* dCtr = nullptr;
-    Counters* hCtr = nullptr;     // pinned
-    // PRJ workspace
+    uint64_t pairsCapacity = 0;                 // materialising probe (hj_probe_pairs_dev): the capacity of the last call
+    Counters* hCtr = nullptr;     // pinned copy of the counters
+    // PRJ
     PrjPlan plan{};
-    uint64_t *tmpA = nullptr, *partR = nullptr, *partS = nullptr;
-    void* work = nullptr;
-    uint64_t capTmp = 0, capPartR = 0, capPartS = 0;
     uint32_t forceVariant = 0;                  // hj_join_dev(AUTO) has already sampled: build with this variant
     uint32_t algoUsed = 0;
-    size_t capWork = 0;
     bool prjRan = false;
     bool prjOptimistic = false;   // the last radix join enqueued the histogram-free passes
     // PRJ with a resident R (hj_prj_build_dev / hj_prj_probe_dev): R's final offsets / fragment counts and the work-item
-    // list live in prjRes (prj_resident_carve), R's keys in partR
-    void* prjRes = nullptr; size_t capPrjRes = 0;
+    // list live in buf[B_PRJ_RES], R's keys in buf[B_PART_R]
     uint64_t prjMaxSlice = 0;                   // sSize of the last PRJ / AUTO hj_reserve: the largest slice a probe takes
     bool resident = false;                      // R is partitioned and nothing has replaced it since
     PrjPlan resPlan{};                          // the plan R was partitioned with (radix bits, R's layout)
     uint64_t resR = 0;
     bool resProbed = false, resProbeOpt = false;   // a probe ran since the build; its slice enqueued the histogram-free passes
-    // staging for hj_run
-    uint64_t *stageR = nullptr, *stageS = nullptr;
-    uint64_t capStageR = 0, capStageS = 0;
-    // shard helper: up to 4 inputs may sit between their histogram and their scatter
-    struct ShardPlan { const uint64_t* in = nullptr; uint64_t n = 0; uint32_t nShards = 0, mode = 0; void* work = nullptr; size_t cap = 0; uint64_t stamp = 0; };
+    // shard helper: up to 4 inputs may sit between their histogram and their scatter (shard[i] works in buf[B_SHARD0 + i])
+    struct ShardPlan { const uint64_t* in = nullptr; uint64_t n = 0; uint32_t nShards = 0, mode = 0; uint64_t stamp = 0; };
     ShardPlan shard[4];
     uint64_t shardStamp = 0;
     // timing
@@ -123,15 +128,19 @@ bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
 
 uint32_t probe_len(const hj_params& p) { return p.probeLength ? p.probeLength : 4; }
 
-template <typename T>
-int grow(hj_ctx* c, T*& ptr, uint64_t& cap, uint64_t need)
+int DevBuf::reserve(hj_ctx* c, size_t need, bool* replaced)
 {
-    if (need <= cap) return HJ_OK;
-    if (ptr) { HJ_HIP(c, hipFree(ptr)); ptr = nullptr; cap = 0; }
-    void* p = nullptr;
-    HJ_HIP(c, hipMalloc(&p, need * sizeof(T)));
-    ptr = static_cast<T*>(p);
-    cap = need;
+    if (need <= bytes) return HJ_OK;
+    if (replaced) *replaced = true;
+    if (p) {
+        // work enqueued earlier may still use the old buffer (hipFree waits for the device anyway: written out so that
+        // no caller has to think about it)
+        HJ_HIP(c, hipStreamSynchronize(c->stream));
+        HJ_HIP(c, hipFree(p));
+        p = nullptr; bytes = 0;
+    }
+    HJ_HIP(c, hipMalloc(&p, need));
+    bytes = need;
     return HJ_OK;
 }
 
@@ -159,6 +168,49 @@ double elapsed_us(hj_ctx* c, Ev a, Ev b)
     return (double)ms * 1000.0;
 }
 
+// The pair of events a launcher records around its dominant kernel, marked as set where it is handed over
+KernelEvents bracket(hj_ctx* c, Ev before)
+{
+    c->evSet[before] = c->evSet[before + 1] = true;
+    return KernelEvents{c->ev[before], c->ev[before + 1]};
+}
+
+// Every entry point that may enqueue work: the stream then no longer ends at EV_BUILD1 -- noted even when the arguments
+// are rejected next. (hj_probe_dev takes the value over first, see there.)
+#define HJ_ENTER(c, argsOk)                                   \
+    do {                                                      \
+        if (c) (c)->streamAtBuildEnd = false;                 \
+        if (!(c) || !(argsOk)) return HJ_ERR_INVALID;         \
+    } while (0)
+
+// A new operation (a build or a whole radix join) starts: nothing of the last one is timed, built or resident any more,
+// and the counters are zeroed on the stream. What the operation builds it flags at its end, once everything is enqueued.
+int begin_operation(hj_ctx* c, uint64_t rSize, uint64_t sSize, uint64_t tableSize)
+{
+    HJ_HIP(c, hipSetDevice(c->device));
+    for (bool& b : c->evSet) b = false;
+    c->built = c->htmBuilt = c->prjRan = c->resident = false;
+    c->rSize = rSize; c->sSize = sSize; c->tableSize = tableSize;
+    HJ_HIP(c, hipMemsetAsync(c->dCtr(), 0, sizeof(Counters), c->stream));
+    return HJ_OK;
+}
+
+// Which LDS builds a table of tableSize slots for n elements can take: 2 (own), 3 (wave) and 4 (compact) need their
+// buffers (hj_reserve) and a table of at least one window / ring.
+// 4 = the compact ring build (4-byte table, hj_build_wave.hip): what "rings" means whenever it can be tried; if it meets
+// something it cannot handle, the classic ring build (3) enqueued behind it, gated on the device, redoes the table.
+struct BuildCaps { bool own, wave, compact; };
+BuildCaps build_caps(const hj_ctx* c, uint64_t n, uint64_t tableSize)
+{
+    BuildCaps k;
+    k.own = n && own_supported(tableSize) && c->buf[B_OWNER].bytes >= own_owner_bytes(tableSize) &&
+            c->buf[B_QUEUE].bytes >= own_queue_bytes(n);
+    k.wave = n && wave_supported(tableSize) && c->buf[B_QUEUE].bytes >= wave_queue_bytes(n, c->nCU);
+    // HJ_FLAG_KEEP_ROW_IDS: the compact table drops the index words hj_probe_pairs_dev reads -- never tried, never picked
+    k.compact = k.wave && wave_compact_supported(tableSize, probe_len(c->params)) && !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS);
+    return k;
+}
+
 int create_common(int device, void* stream, bool own, hj_ctx** out)
 {
     if (!out) return HJ_ERR_INVALID;
@@ -182,19 +234,19 @@ int create_common(int device, void* stream, bool own, hj_ctx** out)
     } else {
         c->stream = static_cast<hipStream_t>(stream);
     }
-    bool ok = hipMalloc(reinterpret_cast<void**>(&c->dCtr), sizeof(Counters)) == hipSuccess &&
+    bool ok = c->buf[B_CTR].reserve(c, sizeof(Counters)) == HJ_OK &&
               hipHostMalloc(reinterpret_cast<void**>(&c->hCtr), sizeof(Counters)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&c->queueCount), kOwnMaxChunks * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&c->fitCount), kSampleWords * sizeof(unsigned int)) == hipSuccess &&
+              c->buf[B_QUEUE_COUNT].reserve(c, kOwnMaxChunks * sizeof(uint32_t)) == HJ_OK &&
+              c->buf[B_FIT].reserve(c, kSampleWords * sizeof(unsigned int)) == HJ_OK &&
               hipHostMalloc(reinterpret_cast<void**>(&c->hFit), 8 * sizeof(unsigned int)) == hipSuccess &&
               hipHostMalloc(reinterpret_cast<void**>(&c->hPreferred), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dPreferred), c->hPreferred, 0) == hipSuccess &&
-              hipMalloc(&c->boundsBuf, wave_bounds_bytes(c->nCU)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&c->dPairsCursor), sizeof(unsigned long long)) == hipSuccess &&
-              hipMemset(c->dPairsCursor, 0, sizeof(unsigned long long)) == hipSuccess;
+              c->buf[B_BOUNDS].reserve(c, wave_bounds_bytes(c->nCU)) == HJ_OK &&
+              c->buf[B_PAIRS_CURSOR].reserve(c, sizeof(unsigned long long)) == HJ_OK &&
+              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, sizeof(unsigned long long)) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }
-    hipMemset(c->dCtr, 0, sizeof(Counters));
+    hipMemset(c->dCtr(), 0, sizeof(Counters));
     memset(c->hCtr, 0, sizeof(Counters));
     *c->hPreferred = 0;
     *out = c;
@@ -242,11 +294,7 @@ void hj_destroy(hj_ctx* c)
     if (c->stream || !c->ownStream) hipStreamSynchronize(c->stream);
     zipf_release(c);
     if (c->stream || !c->ownStream) hipStreamSynchronize(c->stream);
-    void* frees[] = {c->table, c->dCtr, c->tmpA, c->partR, c->partS, c->work, c->prjRes, c->stageR, c->stageS,
-                     c->ownerBuf, c->queueBuf, c->queueCount, c->fitCount, c->boundsBuf, c->dPairsCursor, c->htmConflicts, c->htmOwnCounts, c->htmOvfCount,
-                     c->htmOvfBase, c->htmScan, c->htmOverflow, c->shard[0].work, c->shard[1].work,
-                     c->shard[2].work, c->shard[3].work};
-    for (void* p : frees) if (p) hipFree(p);
+    for (const DevBuf& b : c->buf) if (b.p) hipFree(b.p);
     if (c->hCtr) hipHostFree(c->hCtr);
     if (c->hFit) hipHostFree(c->hFit);
     if (c->hPreferred) hipHostFree(c->hPreferred);
@@ -274,8 +322,7 @@ const char* hj_last_error(const hj_ctx* c) { return c ? c->err.c_str() : "null c
 
 int hj_synchronize(hj_ctx* c)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c) return HJ_ERR_INVALID;
+    HJ_ENTER(c, true);
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     return HJ_OK;
 }
@@ -297,26 +344,16 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         if (params->prjMode > 2) return fail(c, HJ_ERR_INVALID, "hj_reserve: prjMode must be 0, 1 or 2");
         c->plan = prj_plan(rSize, sSize, bits, params->prjMode);
         const uint64_t nmax = rSize > sSize ? rSize : sSize;
-        int rc;
-        const uint64_t caps0[4] = {c->capTmp, c->capPartR, c->capPartS, c->capWork};
         // +2 tuples: the 16-byte sweeps may touch one tuple past an odd end
-        if ((rc = grow(c, c->tmpA, c->capTmp, nmax + 2))) return rc;
-        if ((rc = grow(c, c->partR, c->capPartR, rSize + 2))) return rc;
-        if (sSize && (rc = grow(c, c->partS, c->capPartS, sSize + 2))) return rc;
-        if (c->plan.workspaceBytes > c->capWork) {
-            if (c->work) { HJ_HIP(c, hipFree(c->work)); c->work = nullptr; c->capWork = 0; }
-            HJ_HIP(c, hipMalloc(&c->work, c->plan.workspaceBytes));
-            c->capWork = c->plan.workspaceBytes;
-        }
-        // resident R (hj_prj_build_dev): its offsets and the probes' work items, for slices up to sSize
-        const size_t rb = prj_resident_bytes(bits, sSize);
-        if (rb > c->capPrjRes) {
-            c->resident = false;
-            if (c->prjRes) { HJ_HIP(c, hipFree(c->prjRes)); c->prjRes = nullptr; c->capPrjRes = 0; }
-            HJ_HIP(c, hipMalloc(&c->prjRes, rb));
-            c->capPrjRes = rb;
-        }
-        if (caps0[0] != c->capTmp || caps0[1] != c->capPartR || caps0[2] != c->capPartS || caps0[3] != c->capWork) c->resident = false;
+        // prjRes: the resident R's offsets (hj_prj_build_dev) and the probes' work items, for slices up to sSize
+        bool replaced = false;      // a resident R does not survive the replacement of any of the five
+        int rc = c->buf[B_TMP].reserve(c, (nmax + 2) * sizeof(uint64_t), &replaced);
+        if (!rc) rc = c->buf[B_PART_R].reserve(c, (rSize + 2) * sizeof(uint64_t), &replaced);
+        if (!rc && sSize) rc = c->buf[B_PART_S].reserve(c, (sSize + 2) * sizeof(uint64_t), &replaced);
+        if (!rc) rc = c->buf[B_WORK].reserve(c, c->plan.workspaceBytes, &replaced);
+        if (!rc) rc = c->buf[B_PRJ_RES].reserve(c, prj_resident_bytes(bits, sSize), &replaced);
+        if (replaced) c->resident = false;
+        if (rc) return rc;
         c->prjMaxSlice = sSize;
         if (params->algo == HJ_ALGO_PRJ) return HJ_OK;      // AUTO also needs the open-addressing buffers below
         // ... when the table join can take this R at all (it wants a power-of-two size, as the reference does);
@@ -328,59 +365,33 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         // any rSize (the hash is (key/3) & mask, not tied to rSize being a power of two)
         if (rSize > (1ull << 31)) return fail(c, HJ_ERR_INVALID, "hj_reserve: rSize > 2^31 per device");
         const uint64_t nb = htm_num_buckets(rSize);
-        int rc = grow(c, c->table, c->tableCapSlots, 4 * nb + kTableSlack);
+        int rc = c->buf[B_TABLE].reserve(c, (4 * nb + kTableSlack) * sizeof(uint64_t));
         if (rc) return rc;
         // rings (variant 3), workgroup window (2) or global atomics (1): buffers for the larger need of the first two
         size_t qb = wave_queue_bytes(rSize, c->nCU), cb = wave_conflict_bytes(rSize, c->nCU);
         if (own_supported(4 * nb)) {
             if (own_queue_bytes(rSize) > qb) qb = own_queue_bytes(rSize);
             if (own_conflict_bytes(rSize, c->nCU) > cb) cb = own_conflict_bytes(rSize, c->nCU);
-            const size_t ob = own_owner_bytes(4 * nb), kb = own_conflict_count_bytes(rSize, c->nCU);
-            if (ob > c->capOwner) {
-                if (c->ownerBuf) { HJ_HIP(c, hipFree(c->ownerBuf)); c->ownerBuf = nullptr; c->capOwner = 0; }
-                HJ_HIP(c, hipMalloc(&c->ownerBuf, ob)); c->capOwner = ob;
-            }
-            if (kb > c->capHtmOwnCounts) {
-                if (c->htmOwnCounts) { HJ_HIP(c, hipFree(c->htmOwnCounts)); c->htmOwnCounts = nullptr; c->capHtmOwnCounts = 0; }
-                HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmOwnCounts), kb)); c->capHtmOwnCounts = kb;
-            }
+            if ((rc = c->buf[B_OWNER].reserve(c, own_owner_bytes(4 * nb)))) return rc;
+            if ((rc = c->buf[B_HTM_OWN_COUNTS].reserve(c, own_conflict_count_bytes(rSize, c->nCU)))) return rc;
         }
-        if (qb > c->capQueue) {
-            if (c->queueBuf) { HJ_HIP(c, hipFree(c->queueBuf)); c->queueBuf = nullptr; c->capQueue = 0; }
-            HJ_HIP(c, hipMalloc(&c->queueBuf, qb)); c->capQueue = qb;
-        }
-        if (cb > c->capHtmConflicts) {
-            if (c->htmConflicts) { HJ_HIP(c, hipFree(c->htmConflicts)); c->htmConflicts = nullptr; c->capHtmConflicts = 0; }
-            HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmConflicts), cb)); c->capHtmConflicts = cb;
-        }
-        if (nb > c->capHtmBuckets) {
-            for (void* p : {(void*)c->htmOvfCount, (void*)c->htmOvfBase, (void*)c->htmScan}) if (p) HJ_HIP(c, hipFree(p));
-            c->htmOvfCount = nullptr; c->htmOvfBase = nullptr; c->htmScan = nullptr; c->capHtmBuckets = 0;
-            HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmOvfCount), nb * sizeof(unsigned int)));
-            HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmOvfBase), nb * sizeof(uint32_t)));
-            HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmScan), scan_workspace_words(nb) * sizeof(uint32_t)));
-            c->capHtmBuckets = nb;
-        }
-        return HJ_OK;
+        if ((rc = c->buf[B_QUEUE].reserve(c, qb))) return rc;
+        if ((rc = c->buf[B_HTM_CONFLICTS].reserve(c, cb))) return rc;
+        if ((rc = c->buf[B_HTM_OVF_COUNT].reserve(c, nb * sizeof(unsigned int)))) return rc;
+        if ((rc = c->buf[B_HTM_OVF_BASE].reserve(c, nb * sizeof(uint32_t)))) return rc;
+        return c->buf[B_HTM_SCAN].reserve(c, scan_workspace_words(nb) * sizeof(uint32_t));
     }
     if (!is_pow2(rSize)) return fail(c, HJ_ERR_INVALID, "hj_reserve: rSize must be a power of two (DataGen.hpp:28, NoCCHashBuild.hpp:36)");
     if (rSize > (1ull << 31)) return fail(c, HJ_ERR_INVALID, "hj_reserve: rSize > 2^31 per device");
-    int rc = grow(c, c->table, c->tableCapSlots, 2 * rSize + kTableSlack);
+    int rc = c->buf[B_TABLE].reserve(c, (2 * rSize + kTableSlack) * sizeof(uint64_t));
     if (rc) return rc;
     if (params->buildVariant > 4) return fail(c, HJ_ERR_INVALID, "hj_reserve: buildVariant must be 0, 1, 2, 3 or 4");
     if (params->buildVariant != 1 && (own_supported(2 * rSize) || wave_supported(2 * rSize))) {
         // 1/8 headroom: a radix shard may receive slightly more than its nominal share (hj_build_keys_dev)
-        const size_t ob = own_owner_bytes(2 * rSize);
         size_t qb = own_queue_bytes(rSize + rSize / 8);
         if (wave_queue_bytes(rSize + rSize / 8, c->nCU) > qb) qb = wave_queue_bytes(rSize + rSize / 8, c->nCU);
-        if (own_supported(2 * rSize) && ob > c->capOwner) {
-            if (c->ownerBuf) { HJ_HIP(c, hipFree(c->ownerBuf)); c->ownerBuf = nullptr; c->capOwner = 0; }
-            HJ_HIP(c, hipMalloc(&c->ownerBuf, ob)); c->capOwner = ob;
-        }
-        if (qb > c->capQueue) {
-            if (c->queueBuf) { HJ_HIP(c, hipFree(c->queueBuf)); c->queueBuf = nullptr; c->capQueue = 0; }
-            HJ_HIP(c, hipMalloc(&c->queueBuf, qb)); c->capQueue = qb;
-        }
+        if (own_supported(2 * rSize) && (rc = c->buf[B_OWNER].reserve(c, own_owner_bytes(2 * rSize)))) return rc;
+        if ((rc = c->buf[B_QUEUE].reserve(c, qb))) return rc;
     }
     return HJ_OK;
 }
@@ -394,13 +405,14 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
 //      hj_device.h: what it defers costs about what global atomics cost for every tuple);
 //   1  global atomics otherwise (no locality: hj_join_dev(AUTO) then takes the radix join instead).
 static int sample_variant(hj_ctx* c, const void* d, bool key32, uint64_t n, uint64_t tableSize, uint32_t hshift,
-                          bool canOwn, bool canWave, uint32_t* variant, bool canCompact = false, bool htm = false)
+                          const BuildCaps& can, uint32_t* variant, bool htm = false)
 {
     const uint32_t nSample = 256;
-    HJ_HIP(c, launch_sample_locality(d, key32, n, tableSize, hshift, nSample, c->fitCount, c->stream, htm));
-    HJ_HIP(c, hipMemcpyAsync(c->hFit, c->fitCount, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    unsigned int* const fit = c->buf[B_FIT].as<unsigned int>();
+    HJ_HIP(c, launch_sample_locality(d, key32, n, tableSize, hshift, nSample, fit, c->stream, htm));
+    HJ_HIP(c, hipMemcpyAsync(c->hFit, fit, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
-    *variant = variant_for_sample(c->hFit[0], c->hFit[1], c->hFit[2], canOwn, canWave, canCompact, c->hFit[3], c->hFit[4]);
+    *variant = variant_for_sample(c->hFit[0], c->hFit[1], c->hFit[2], can.own, can.wave, can.compact, c->hFit[3], c->hFit[4]);
     return HJ_OK;
 }
 
@@ -408,32 +420,27 @@ static int sample_variant(hj_ctx* c, const void* d, bool key32, uint64_t n, uint
 static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32_t hshift,
                         uint64_t tableSize, uint64_t idxBase)
 {
-    HJ_HIP(c, hipSetDevice(c->device));
-    c->rSize = n; c->sSize = 0; c->tableSize = tableSize; c->hshift = hshift;
-    for (bool& b : c->evSet) b = false;
-    c->prjRan = false; c->htmBuilt = false; c->resident = false;
-    HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
     int rc;
+    if ((rc = begin_operation(c, n, 0, tableSize))) return rc;
+    c->hshift = hshift;
     if ((rc = record(c, EV_CLEAR0))) return rc;
-    // which build kernel: 2, 3 and 4 need their buffers (hj_reserve) and a table of at least one window / ring.
-    // 4 = the compact ring build (4-byte table, hj_build_wave.hip): what "rings" means whenever it can be tried; if it meets
-    // something it cannot handle, the classic ring build (3) enqueued behind it, gated on the device, redoes the table.
     uint32_t variant = c->forceVariant ? c->forceVariant : c->params.buildVariant;
-    const bool canOwn = n && own_supported(tableSize) && c->capOwner >= own_owner_bytes(tableSize) &&
-                        c->capQueue >= own_queue_bytes(n);
-    const bool canWave = n && wave_supported(tableSize) && c->capQueue >= wave_queue_bytes(n, c->nCU);
-    const uint32_t pl = probe_len(c->params);
-    // HJ_FLAG_KEEP_ROW_IDS: the compact table drops the index words hj_probe_pairs_dev reads -- never tried, never picked
-    const bool canCompact = canWave && wave_compact_supported(tableSize, pl) && !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS);
-    if (variant == 4 && !canCompact) variant = 3;
-    if (variant == 3 && !canWave) variant = canOwn ? 2 : 1;
-    if (variant == 2 && !canOwn) variant = 1;
-    if (variant == 0 && !canOwn && !canWave) variant = 1;
+    const BuildCaps can = build_caps(c, n, tableSize);
+    if (variant == 4 && !can.compact) variant = 3;
+    if (variant == 3 && !can.wave) variant = can.own ? 2 : 1;
+    if (variant == 2 && !can.own) variant = 1;
+    if (variant == 0 && !can.own && !can.wave) variant = 1;
     c->variantUsed = (variant == 4) ? 0 : variant;     // 0: decided on the device (4 may fall back to 3), reported from Counters::variant
     c->algoUsed = c->params.algo == HJ_ALGO_AUTO ? (uint32_t)HJ_ALGO_ATOMIC : c->params.algo;
-    const unsigned long long* word = &c->dCtr->variant;
-    // the dominant kernel of each LDS variant, bracketed by its own pair of events (hj_result.buildPhaseA_us)
-    const KernelEvents kevWave{c->ev[EV_KW0], c->ev[EV_KW1]}, kevCompact{c->ev[EV_KC0], c->ev[EV_KC1]}, kevOwn{c->ev[EV_KO0], c->ev[EV_KO1]};
+    BuildJob job{};
+    job.R = d; job.key32 = key32; job.n = n; job.hshift = hshift;
+    job.table = c->buf[B_TABLE].as<uint64_t>(); job.tableSize = tableSize;
+    job.probeLen = probe_len(c->params); job.idxBase = idxBase; job.sc = c->sc;
+    job.nCU = c->nCU; job.ctr = c->dCtr(); job.s = c->stream;
+    const WaveBufs wave{c->buf[B_BOUNDS].p, c->buf[B_QUEUE].p};
+    const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>()};
+    const unsigned long long* word = &job.ctr->variant;
+    // The dominant kernel of each LDS variant is bracketed by its own pair of events (bracket(); hj_result.buildPhaseA_us).
     if (variant == 0) {
         // The locality pre-round decides ON THE DEVICE (this call stays asynchronous: no read-back). Behind it the kernels
         // of the candidate variants are enqueued, each gated on the word the pre-round writes; the ones not chosen return
@@ -444,80 +451,60 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
         // so a workload that changes its locality class costs one slow step, never a wrong one, and the next step follows
         // it (round-2 VERDICT, launch tail: 23 -> 9 launches in the steady state).
         const uint32_t expect = (uint32_t)*reinterpret_cast<volatile unsigned long long*>(c->hPreferred);
-        const uint32_t all = 2u | (canOwn ? 4u : 0u) | (canWave ? 8u : 0u) | (canCompact ? 16u : 0u);
+        const uint32_t all = 2u | (can.own ? 4u : 0u) | (can.wave ? 8u : 0u) | (can.compact ? 16u : 0u);
         uint32_t allowed = all;
-        if (expect == 4 && canCompact) allowed = 16u | 8u;
-        else if (expect == 3 && canWave) allowed = 8u;
-        else if (expect == 2 && canOwn) allowed = 4u;
+        if (expect == 4 && can.compact) allowed = 16u | 8u;
+        else if (expect == 3 && can.wave) allowed = 8u;
+        else if (expect == 2 && can.own) allowed = 4u;
         else if (expect == 1) allowed = 2u;
         const bool enqCompact = (allowed >> 4) & 1u, enqWave = (allowed >> 3) & 1u, enqOwn = (allowed >> 2) & 1u, enqGlobal = (allowed >> 1) & 1u;
         SamplePick pick;
-        pick.ctr = c->dCtr; pick.hostPreferred = c->dPreferred; pick.allowedMask = allowed;
-        pick.canOwn = canOwn; pick.canWave = canWave; pick.canCompact = canCompact;
-        HJ_HIP(c, launch_sample_locality(d, key32, n, tableSize, hshift, 256, c->dCtr->fit, c->stream, false, pick, true));
+        pick.ctr = job.ctr; pick.hostPreferred = c->dPreferred; pick.allowedMask = allowed;
+        pick.canOwn = can.own; pick.canWave = can.wave; pick.canCompact = can.compact;
+        HJ_HIP(c, launch_sample_locality(d, key32, n, tableSize, hshift, 256, job.ctr->fit, c->stream, false, pick, true));
         if ((rc = record(c, EV_BUILD0))) return rc;
         // phase A of the LDS variants, each dominant kernel inside its own pair of events, then their tails. (An event
         // record costs the stream ~5 us -- step timeline at 2^22, tools/step_timeline.sh --, so nothing is recorded that
         // hj_fetch does not read.)
         if (enqWave) {
-            HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                        c->queueBuf, c->dCtr, Gate{word, 3, 4}, kWavePre, nullptr, c->stream));
+            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3, 4}, kWavePre));
             if (enqCompact)
-                HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                            c->queueBuf, c->dCtr, Gate{word, 4}, kWaveMain, nullptr, c->stream, nullptr, kWaveCompact, 3, &kevCompact));
-            HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                        c->queueBuf, c->dCtr, Gate{word, 3}, kWaveMain, nullptr, c->stream, nullptr, kWaveClassic, 3, &kevWave));
-            c->evSet[EV_KW0] = c->evSet[EV_KW1] = true;
-            c->evSet[EV_KC0] = c->evSet[EV_KC1] = enqCompact;
-        }
-        if (enqOwn) {
-            HJ_HIP(c, launch_build_own(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->ownerBuf,
-                                       c->queueBuf, c->queueCount, c->dCtr, Gate{word, 2}, 1, nullptr, c->stream, &kevOwn));
-            c->evSet[EV_KO0] = c->evSet[EV_KO1] = true;
-        }
-        if (enqWave) {
-            if (enqCompact)
-                HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                            c->queueBuf, c->dCtr, Gate{word, 4}, kWaveTail, nullptr, c->stream, nullptr, kWaveCompact, 3));
-            HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                        c->queueBuf, c->dCtr, Gate{word, 3}, kWaveTail, nullptr, c->stream));
+                HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
+            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, kWaveClassic, bracket(c, EV_KW0)));
         }
         if (enqOwn)
-            HJ_HIP(c, launch_build_own(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->ownerBuf,
-                                       c->queueBuf, c->queueCount, c->dCtr, Gate{word, 2}, 2, nullptr, c->stream));
+            HJ_HIP(c, launch_build_own(job, own, Gate{word, 2}, 1, bracket(c, EV_KO0)));
+        if (enqWave) {
+            if (enqCompact)
+                HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
+            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveTail));
+        }
+        if (enqOwn)
+            HJ_HIP(c, launch_build_own(job, own, Gate{word, 2}, 2));
         if (enqGlobal) {
-            launch_fill_empty(c->table, tableSize + kTableSlack, Gate{word, 1}, c->stream, c->dCtr, tableSize);
-            launch_build_atomic_min(d, key32, n, c->table, tableSize, hshift, pl, idxBase, c->sc, c->dCtr, Gate{word, 1}, c->stream);
+            launch_fill_empty(job.table, tableSize + kTableSlack, Gate{word, 1}, c->stream, job.ctr, tableSize);
+            launch_build_atomic_min(job, Gate{word, 1});
         }
     } else if (variant == 4) {
         // the compact rings, asked for by the caller: the classic rings stay enqueued behind them as the gated fallback
-        launch_set_variant(c->dCtr, 4, c->stream);
+        launch_set_variant(job.ctr, 4, c->stream);
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                    c->queueBuf, c->dCtr, Gate{word, 4}, kWavePre | kWaveMain, nullptr, c->stream, nullptr, kWaveCompact, 3, &kevCompact));
-        HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                    c->queueBuf, c->dCtr, Gate{word, 3}, kWaveMain, nullptr, c->stream, nullptr, kWaveClassic, 3, &kevWave));
-        c->evSet[EV_KW0] = c->evSet[EV_KW1] = c->evSet[EV_KC0] = c->evSet[EV_KC1] = true;
-        HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                    c->queueBuf, c->dCtr, Gate{word, 4}, kWaveTail, nullptr, c->stream, nullptr, kWaveCompact, 3));
-        HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU, c->boundsBuf,
-                                    c->queueBuf, c->dCtr, Gate{word, 3}, kWaveTail, nullptr, c->stream));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWavePre | kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, kWaveClassic, bracket(c, EV_KW0)));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveTail));
     } else if (variant == 3) {
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_wave(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU,
-                                    c->boundsBuf, c->queueBuf, c->dCtr, Gate{nullptr, 0}, kWaveAll, nullptr, c->stream, nullptr, kWaveClassic, 3, &kevWave));
-        c->evSet[EV_KW0] = c->evSet[EV_KW1] = true;
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWaveAll, kWaveClassic, bracket(c, EV_KW0)));
     } else if (variant == 2) {
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_own(d, key32, n, hshift, c->table, tableSize, pl, idxBase, c->sc, c->nCU,
-                                   c->ownerBuf, c->queueBuf, c->queueCount, c->dCtr, Gate{nullptr, 0}, 3, nullptr, c->stream, &kevOwn));
-        c->evSet[EV_KO0] = c->evSet[EV_KO1] = true;
+        HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
     } else {
-        launch_fill_empty(c->table, tableSize + kTableSlack, Gate{nullptr, 0}, c->stream);
-        launch_set_full_range(tableSize, c->dCtr, Gate{nullptr, 0}, c->stream);
+        launch_fill_empty(job.table, tableSize + kTableSlack, Gate{nullptr, 0}, c->stream);
+        launch_set_full_range(tableSize, job.ctr, Gate{nullptr, 0}, c->stream);
         HJ_HIP(c, hipGetLastError());
         if ((rc = record(c, EV_BUILD0))) return rc;
-        if (n) launch_build_atomic_min(d, key32, n, c->table, tableSize, hshift, pl, idxBase, c->sc, c->dCtr, Gate{nullptr, 0}, c->stream);
+        if (n) launch_build_atomic_min(job, Gate{nullptr, 0});
     }
     HJ_HIP(c, hipGetLastError());
     if ((rc = record(c, EV_BUILD1))) return rc;
@@ -526,73 +513,87 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     return HJ_OK;
 }
 
+// room for `need` overflow buckets behind index 0 (unused); a new area gets 1/8 + 64 buckets of headroom
+static int reserve_htm_overflow(hj_ctx* c, uint64_t need)
+{
+    DevBuf& b = c->buf[B_HTM_OVERFLOW];
+    if ((need + 1) * 4 * sizeof(uint64_t) <= b.bytes) return HJ_OK;
+    return b.reserve(c, (need + need / 8 + 64 + 1) * 4 * sizeof(uint64_t));
+}
+
 // --algo htm: the bucketised table (hj_htm.hip). Not asynchronous: the number of conflicts is read back once, to size
 // the overflow area (the reference, too, builds its chains in a serial phase after the parallel build, :231-279).
 static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idxBase)
 {
-    HJ_HIP(c, hipSetDevice(c->device));
     const uint32_t nb = htm_num_buckets(rSize);
     const uint64_t slots = 4ull * nb;
-    if (slots + kTableSlack > c->tableCapSlots || nb > c->capHtmBuckets || c->capQueue < wave_queue_bytes(rSize, c->nCU) ||
-        c->capHtmConflicts < wave_conflict_bytes(rSize, c->nCU))
+    if ((slots + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes || nb * sizeof(unsigned int) > c->buf[B_HTM_OVF_COUNT].bytes ||
+        nb * sizeof(uint32_t) > c->buf[B_HTM_OVF_BASE].bytes || scan_workspace_words(nb) * sizeof(uint32_t) > c->buf[B_HTM_SCAN].bytes ||
+        c->buf[B_QUEUE].bytes < wave_queue_bytes(rSize, c->nCU) || c->buf[B_HTM_CONFLICTS].bytes < wave_conflict_bytes(rSize, c->nCU))
         return fail(c, HJ_ERR_STATE, "hj_build_dev: hj_reserve() not called for this rSize (htm)");
     if (idxBase + rSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_dev: index range exceeds 2^32 - 1");
-    c->rSize = rSize; c->sSize = 0; c->tableSize = slots; c->hshift = 0; c->htmBuckets = nb;
-    for (bool& b : c->evSet) b = false;
-    c->prjRan = false; c->built = false; c->htmBuilt = false; c->resident = false;
-    if (!c->htmGenericChains) c->htmChainsFellBack = false;
-    HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
     int rc;
+    if ((rc = begin_operation(c, rSize, 0, slots))) return rc;
+    c->hshift = 0; c->htmBuckets = nb;
+    if (!c->htmGenericChains) c->htmChainsFellBack = false;
     if ((rc = record(c, EV_CLEAR0))) return rc;
+    uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
+    uint64_t* const htmConflicts = c->buf[B_HTM_CONFLICTS].as<uint64_t>();
+    uint32_t* const ownCounts = c->buf[B_HTM_OWN_COUNTS].as<uint32_t>();
+    unsigned int* const ovfCount = c->buf[B_HTM_OVF_COUNT].as<unsigned int>();
+    uint32_t* const ovfBase = c->buf[B_HTM_OVF_BASE].as<uint32_t>();
+    uint32_t* const scan = c->buf[B_HTM_SCAN].as<uint32_t>();
+    void* const bounds = c->buf[B_BOUNDS].p;
+    Counters* const ctr = c->dCtr();
     // locality pre-round with the bucketised table's own hash (bucket = key / 3 keeps the key order): the rings if they
-    // will do, the workgroup window for looser locality (shuffle windows up to ~2000 positions), else global atomics
-    const bool canWave = wave_supported(slots);
-    const bool canOwn = own_supported(slots) && c->capOwner >= own_owner_bytes(slots) && c->capQueue >= own_queue_bytes(rSize) &&
-                        c->capHtmConflicts >= own_conflict_bytes(rSize, c->nCU) && c->capHtmOwnCounts >= own_conflict_count_bytes(rSize, c->nCU);
+    // will do, the workgroup window for looser locality (shuffle windows up to ~2000 positions), else global atomics.
+    // The window also lists its conflicts: two buffers more than build_caps asks for
+    BuildCaps can = build_caps(c, rSize, slots);
+    can.own = can.own && c->buf[B_HTM_CONFLICTS].bytes >= own_conflict_bytes(rSize, c->nCU) &&
+              c->buf[B_HTM_OWN_COUNTS].bytes >= own_conflict_count_bytes(rSize, c->nCU);
+    can.compact = false;
     uint32_t variant = c->params.buildVariant > 3 ? 3 : c->params.buildVariant;
-    if (variant == 0 && (canWave || canOwn) &&
-        (rc = sample_variant(c, dR, false, rSize, slots, 0, canOwn, canWave, &variant, false, true))) return rc;
+    if (variant == 0 && (can.wave || can.own) && (rc = sample_variant(c, dR, false, rSize, slots, 0, can, &variant, true))) return rc;
     if (variant == 0) variant = 1;
-    if (variant == 3 && !canWave) variant = canOwn ? 2 : 1;
-    if (variant == 2 && !canOwn) variant = 1;
+    if (variant == 3 && !can.wave) variant = can.own ? 2 : 1;
+    if (variant == 2 && !can.own) variant = 1;
     c->variantUsed = variant; c->algoUsed = HJ_ALGO_HTM;
-    const WaveSlices sl = variant == 2 ? own_conflict_layout(rSize, c->nCU, c->htmOwnCounts) : wave_conflict_layout(rSize, c->nCU, c->boundsBuf);
+    const WaveSlices sl = variant == 2 ? own_conflict_layout(rSize, c->nCU, ownCounts) : wave_conflict_layout(rSize, c->nCU, bounds);
     // the rings: chains in LDS (hj_htm.hip) unless an earlier attempt on this relation had to give up
     const uint32_t nParts = sl.nChunks * htm_chain_parts(sl.sliceLen);
     const bool ldsChains = variant == 3 && !c->htmGenericChains && (uint64_t)nParts + 1 <= nb && htm_chain_info_words(sl.nChunks, sl.sliceLen) <= nb;
-    const KernelEvents kevW{c->ev[EV_KW0], c->ev[EV_KW1]};
-    const KernelEvents kevO{c->ev[EV_KO0], c->ev[EV_KO1]};
+    BuildJob job{};
+    job.R = dR; job.key32 = false; job.n = rSize; job.hshift = 0;
+    job.table = table; job.tableSize = slots;
+    job.probeLen = 3; job.idxBase = idxBase; job.sc = ShardCheck{0, 0, 0, 0};
+    job.nCU = c->nCU; job.ctr = ctr; job.s = c->stream;
     if (variant == 2) {
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_own(dR, false, rSize, 0, c->table, slots, 3, idxBase, ShardCheck{0, 0, 0, 0}, c->nCU, c->ownerBuf,
-                                   c->queueBuf, c->queueCount, c->dCtr, Gate{nullptr, 0}, 3, nullptr, c->stream, &kevO,
-                                   c->htmConflicts, c->htmOwnCounts));
-        c->evSet[EV_KO0] = c->evSet[EV_KO1] = true;
+        const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>(), htmConflicts, ownCounts};
+        HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
     } else if (variant == 3) {
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_wave(dR, false, rSize, 0, c->table, slots, 3, idxBase, ShardCheck{0, 0, 0, 0}, c->nCU, c->boundsBuf,
-                                    c->queueBuf, c->dCtr, Gate{nullptr, 0}, kWaveAll, nullptr, c->stream, c->htmConflicts, kWaveClassic, 3, &kevW,
-                                    ldsChains));
-        c->evSet[EV_KW0] = c->evSet[EV_KW1] = true;
+        const WaveBufs wave{bounds, c->buf[B_QUEUE].p, htmConflicts, ldsChains};
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWaveAll, kWaveClassic, bracket(c, EV_KW0)));
         if (ldsChains) {
             // the chain phase in LDS, first half: overflow buckets per part of a slice, scanned (one word more: the total)
-            HJ_HIP(c, hipMemsetAsync(c->htmOvfBase + nParts, 0, sizeof(uint32_t), c->stream));
-            HJ_HIP(c, launch_htm_chain_count(c->htmConflicts, sl.counts, wave_bounds_ptr(c->nCU, c->boundsBuf), sl.nChunks, sl.sliceLen, nb,
-                                             c->htmOvfBase, c->htmOvfCount, c->dCtr, c->stream));
-            HJ_HIP(c, launch_exclusive_scan_u32(c->htmOvfBase, (uint64_t)nParts + 1, c->htmScan, c->stream));
-            HJ_HIP(c, hipMemcpyAsync(c->hFit, c->htmOvfBase + nParts, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HJ_HIP(c, hipMemsetAsync(ovfBase + nParts, 0, sizeof(uint32_t), c->stream));
+            HJ_HIP(c, launch_htm_chain_count(htmConflicts, sl.counts, wave_bounds_ptr(c->nCU, bounds), sl.nChunks, sl.sliceLen, nb,
+                                             ovfBase, ovfCount, ctr, c->stream));
+            HJ_HIP(c, launch_exclusive_scan_u32(ovfBase, (uint64_t)nParts + 1, scan, c->stream));
+            HJ_HIP(c, hipMemcpyAsync(c->hFit, ovfBase + nParts, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
     } else {
-        launch_fill_empty(c->table, slots + kTableSlack, Gate{nullptr, 0}, c->stream);
-        launch_set_full_range(slots, c->dCtr, Gate{nullptr, 0}, c->stream);
+        launch_fill_empty(table, slots + kTableSlack, Gate{nullptr, 0}, c->stream);
+        launch_set_full_range(slots, ctr, Gate{nullptr, 0}, c->stream);
         HJ_HIP(c, hipGetLastError());
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_htm_build_global(dR, rSize, sl.sliceLen, sl.nChunks, c->table, slots, idxBase, c->htmConflicts,
-                                          const_cast<uint32_t*>(sl.counts), c->dCtr, c->stream));
+        HJ_HIP(c, launch_htm_build_global(dR, rSize, sl.sliceLen, sl.nChunks, table, slots, idxBase, htmConflicts,
+                                          const_cast<uint32_t*>(sl.counts), ctr, c->stream));
     }
     // chains -- only if some bucket overflowed (one read-back of the conflict count): count per bucket, reserve overflow
     // buckets by one scan, fill them in index order, link
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     fold_counter_shards(c->hCtr);
     const uint64_t conflicts = c->hCtr->conflicts;              // >= overflow buckets needed
@@ -608,27 +609,16 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     if (ldsChains) {
         const uint64_t groups = c->hFit[0];                     // overflow buckets the parts need, exactly
         if (conflicts) {
-            if (groups + 1 > c->capHtmOverflow) {
-                if (c->htmOverflow) { HJ_HIP(c, hipFree(c->htmOverflow)); c->htmOverflow = nullptr; c->capHtmOverflow = 0; }
-                const uint64_t cap = groups + groups / 8 + 64;
-                HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmOverflow), (cap + 1) * 4 * sizeof(uint64_t)));
-                c->capHtmOverflow = cap + 1;
-            }
-            HJ_HIP(c, launch_htm_chain_fill(c->htmConflicts, sl.nChunks, sl.sliceLen, nb, c->htmOvfBase, c->htmOvfCount, c->table,
-                                            c->htmOverflow, c->dCtr, c->stream));
+            if ((rc = reserve_htm_overflow(c, groups))) return rc;
+            HJ_HIP(c, launch_htm_chain_fill(htmConflicts, sl.nChunks, sl.sliceLen, nb, ovfBase, ovfCount, table,
+                                            c->buf[B_HTM_OVERFLOW].as<uint64_t>(), ctr, c->stream));
         }
     } else if (conflicts) {
-        HJ_HIP(c, launch_htm_count(c->htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, nb, c->htmOvfCount, c->htmOvfBase, c->stream));
-        HJ_HIP(c, launch_exclusive_scan_u32(c->htmOvfBase, nb, c->htmScan, c->stream));
-        if (conflicts + 1 > c->capHtmOverflow) {
-            HJ_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->htmOverflow) { HJ_HIP(c, hipFree(c->htmOverflow)); c->htmOverflow = nullptr; c->capHtmOverflow = 0; }
-            const uint64_t cap = conflicts + conflicts / 8 + 64;
-            HJ_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->htmOverflow), (cap + 1) * 4 * sizeof(uint64_t)));
-            c->capHtmOverflow = cap + 1;
-        }
-        HJ_HIP(c, launch_htm_chains(c->htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, c->table, nb, c->htmOvfCount, c->htmOvfBase,
-                                    c->htmOverflow, conflicts, c->dCtr, c->stream));
+        HJ_HIP(c, launch_htm_count(htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, nb, ovfCount, ovfBase, c->stream));
+        HJ_HIP(c, launch_exclusive_scan_u32(ovfBase, nb, scan, c->stream));
+        if ((rc = reserve_htm_overflow(c, conflicts))) return rc;
+        HJ_HIP(c, launch_htm_chains(htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, table, nb, ovfCount, ovfBase,
+                                    c->buf[B_HTM_OVERFLOW].as<uint64_t>(), conflicts, ctr, c->stream));
     }
     if ((rc = record(c, EV_BUILD1))) return rc;
     c->built = true; c->htmBuilt = true;
@@ -641,7 +631,7 @@ int hj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idxBase
     if (!c || !dR) return HJ_ERR_INVALID;
     if (c->params.algo == HJ_ALGO_PRJ) return fail(c, HJ_ERR_STATE, "hj_build_dev: context is reserved for PRJ");
     if (c->params.algo == HJ_ALGO_HTM) return rSize ? build_htm(c, dR, rSize, idxBase) : HJ_ERR_INVALID;
-    if (!is_pow2(rSize) || 2 * rSize + kTableSlack > c->tableCapSlots)
+    if (!is_pow2(rSize) || (2 * rSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
         return fail(c, HJ_ERR_STATE, "hj_build_dev: hj_reserve() not called for this rSize");
     // indices stay below 2^32 - 1: (index << 32 | key) of index = key = 0xFFFFFFFF would be the empty pattern
     if (idxBase + rSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_dev: index range exceeds 2^32 - 1");
@@ -654,7 +644,7 @@ int hj_build_keys_dev(hj_ctx* c, const uint32_t* dKeys, uint64_t n, uint32_t hom
     if (c->params.algo == HJ_ALGO_PRJ || c->params.algo == HJ_ALGO_HTM)
         return fail(c, HJ_ERR_STATE, "hj_build_keys_dev: context is reserved for PRJ / htm");
     if (homeShift > 6) return fail(c, HJ_ERR_INVALID, "hj_build_keys_dev: homeShift must be in [0,6]");
-    if (!is_pow2(tableSize) || tableSize + kTableSlack > c->tableCapSlots)
+    if (!is_pow2(tableSize) || (tableSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
         return fail(c, HJ_ERR_STATE, "hj_build_keys_dev: hj_reserve() not called for this table size");
     if (n > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_keys_dev: index range exceeds 2^32 - 1");
     return build_common(c, dKeys, true, n, homeShift, tableSize, 0);
@@ -671,8 +661,9 @@ int hj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
     c->probeStartsAtBuildEnd = c->streamAtBuildEnd;
     c->streamAtBuildEnd = false;
     if (!c->probeStartsAtBuildEnd && (rc = record(c, EV_PROBE0))) return rc;
-    if (sSize && c->htmBuilt) launch_htm_probe(dS, sSize, c->table, c->htmBuckets, c->htmOverflow, c->dCtr, c->stream);
-    else if (sSize) launch_probe(dS, false, sSize, c->table, c->tableSize, c->hshift, probe_len(c->params), c->sc, c->dCtr, c->stream);
+    const uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
+    if (sSize && c->htmBuilt) launch_htm_probe(dS, sSize, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), c->dCtr(), c->stream);
+    else if (sSize) launch_probe(dS, false, sSize, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, c->dCtr(), c->stream);
     if ((rc = record(c, EV_PROBE1))) return rc;
     HJ_HIP(c, hipGetLastError());
     c->sSize += sSize;
@@ -698,11 +689,12 @@ int hj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t s
     HJ_HIP(c, hipSetDevice(c->device));
     c->streamAtBuildEnd = false;
     int rc;
-    HJ_HIP(c, hipMemsetAsync(c->dPairsCursor, 0, sizeof(unsigned long long), c->stream));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), c->stream));
     if ((rc = record(c, EV_PAIRS0))) return rc;
-    const PairsOut out{dOutS, dOutR, capacity, c->dPairsCursor};
-    if (c->htmBuilt) launch_htm_probe_pairs(dS, sSize, sIdxBase, c->table, c->htmBuckets, c->htmOverflow, out, c->nCU, c->dCtr, c->stream);
-    else launch_probe_pairs(dS, sSize, sIdxBase, c->table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr, c->stream);
+    const uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
+    if (c->htmBuilt) launch_htm_probe_pairs(dS, sSize, sIdxBase, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), out, c->nCU, c->dCtr(), c->stream);
+    else launch_probe_pairs(dS, sSize, sIdxBase, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr(), c->stream);
     if ((rc = record(c, EV_PAIRS1))) return rc;
     HJ_HIP(c, hipGetLastError());
     c->pairsCapacity = capacity;
@@ -712,12 +704,11 @@ int hj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t s
 
 int hj_pairs_info(hj_ctx* c, uint64_t out[4])
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !out) return HJ_ERR_INVALID;
+    HJ_ENTER(c, out);
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     unsigned long long found = 0;
-    HJ_HIP(c, hipMemcpy(&found, c->dPairsCursor, sizeof found, hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(&found, c->buf[B_PAIRS_CURSOR].p, sizeof found, hipMemcpyDeviceToHost));
     out[0] = found;
     out[1] = found < c->pairsCapacity ? found : c->pairsCapacity;
     out[2] = (uint64_t)(elapsed_us(c, EV_PAIRS0, EV_PAIRS1) + 0.5);
@@ -727,42 +718,42 @@ int hj_pairs_info(hj_ctx* c, uint64_t out[4])
 
 int hj_probe_keys_dev(hj_ctx* c, const uint32_t* dKeys, uint64_t n)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || (!dKeys && n)) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dKeys || !n);
     if (!c->built || c->htmBuilt) return fail(c, HJ_ERR_STATE, "hj_probe_keys_dev: no open-addressing table (build first)");
     HJ_HIP(c, hipSetDevice(c->device));
     int rc;
     c->probeStartsAtBuildEnd = false;
     if ((rc = record(c, EV_PROBE0))) return rc;
-    if (n) launch_probe(dKeys, true, n, c->table, c->tableSize, c->hshift, probe_len(c->params), c->sc, c->dCtr, c->stream);
+    if (n) launch_probe(dKeys, true, n, c->buf[B_TABLE].as<uint64_t>(), c->tableSize, c->hshift, probe_len(c->params), c->sc, c->dCtr(), c->stream);
     if ((rc = record(c, EV_PROBE1))) return rc;
     HJ_HIP(c, hipGetLastError());
     c->sSize += n;
     return HJ_OK;
 }
 
+static PrjBuffers prj_buffers(const hj_ctx* c)
+{
+    return PrjBuffers{c->buf[B_TMP].as<uint64_t>(), c->buf[B_PART_R].as<uint64_t>(), c->buf[B_PART_S].as<uint64_t>(), c->buf[B_WORK].p};
+}
+
 int hj_prj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_t* dS, uint64_t sSize)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !dR || rSize == 0) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dR && rSize);
     if (sSize == 0) dS = nullptr;                    // an empty S is no S (the join kernel clamps its loads to nS - 1)
     if (c->params.algo != HJ_ALGO_PRJ && c->params.algo != HJ_ALGO_AUTO)
         return fail(c, HJ_ERR_STATE, "hj_prj_join_dev: context not reserved for PRJ");
     const uint64_t nmax = rSize > sSize ? rSize : sSize;
-    if (nmax + 2 > c->capTmp || rSize + 2 > c->capPartR || (dS && sSize + 2 > c->capPartS))
+    if ((nmax + 2) * sizeof(uint64_t) > c->buf[B_TMP].bytes || (rSize + 2) * sizeof(uint64_t) > c->buf[B_PART_R].bytes ||
+        (dS && (sSize + 2) * sizeof(uint64_t) > c->buf[B_PART_S].bytes))
         return fail(c, HJ_ERR_STATE, "hj_prj_join_dev: hj_reserve() not called for these sizes");
-    HJ_HIP(c, hipSetDevice(c->device));
     // the plan depends on the sizes (chunking); re-plan with the reserved bit count
     const PrjPlan pl = prj_plan(rSize, dS ? sSize : 0, c->plan.radixBits, c->params.prjMode);
-    if (pl.workspaceBytes > c->capWork) return fail(c, HJ_ERR_STATE, "hj_prj_join_dev: workspace too small");
-    for (bool& b : c->evSet) b = false;
-    c->built = false; c->resident = false;
-    c->rSize = rSize; c->sSize = dS ? sSize : 0; c->tableSize = 0;
-    HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
+    if (pl.workspaceBytes > c->buf[B_WORK].bytes) return fail(c, HJ_ERR_STATE, "hj_prj_join_dev: workspace too small");
     int rc;
+    if ((rc = begin_operation(c, rSize, dS ? sSize : 0, 0))) return rc;
     if ((rc = record(c, EV_PRJ0))) return rc;
-    PrjBuffers buf{c->tmpA, c->partR, c->partS, c->work};
-    HJ_HIP(c, launch_prj(pl, buf, dR, rSize, dS, dS ? sSize : 0, c->nCU, c->dCtr, c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0],
+    const PrjBuffers buf = prj_buffers(c);
+    HJ_HIP(c, launch_prj(pl, buf, dR, rSize, dS, dS ? sSize : 0, c->nCU, c->dCtr(), c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0],
                          c->ev[EV_PRJ_S1], c->stream));
     c->evSet[EV_PRJ_PART] = c->evSet[EV_PRJ_S0] = c->evSet[EV_PRJ_S1] = true;
     if ((rc = record(c, EV_PRJ1))) return rc;
@@ -773,38 +764,24 @@ int hj_prj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_
     return HJ_OK;
 }
 
-// the scratch workspace of the passes holds nothing resident: a slice whose plan needs more than hj_reserve's (the chunk
-// count is not monotone in the size, see prj_plan) gets a larger one
-static int ensure_work(hj_ctx* c, size_t bytes)
-{
-    if (bytes <= c->capWork) return HJ_OK;
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->work) { HJ_HIP(c, hipFree(c->work)); c->work = nullptr; c->capWork = 0; }
-    HJ_HIP(c, hipMalloc(&c->work, bytes));
-    c->capWork = bytes;
-    return HJ_OK;
-}
-
 int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !dR || rSize == 0) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dR && rSize);
     if (c->params.algo != HJ_ALGO_PRJ && c->params.algo != HJ_ALGO_AUTO)
         return fail(c, HJ_ERR_STATE, "hj_prj_build_dev: context not reserved for PRJ");
-    if (rSize + 2 > c->capTmp || rSize + 2 > c->capPartR || !c->prjRes ||
-        prj_resident_bytes(c->plan.radixBits, 0) > c->capPrjRes)
+    if ((rSize + 2) * sizeof(uint64_t) > c->buf[B_TMP].bytes || (rSize + 2) * sizeof(uint64_t) > c->buf[B_PART_R].bytes ||
+        !c->buf[B_PRJ_RES].p || prj_resident_bytes(c->plan.radixBits, 0) > c->buf[B_PRJ_RES].bytes)
         return fail(c, HJ_ERR_STATE, "hj_prj_build_dev: hj_reserve() not called for this rSize");
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjPlan pl = prj_plan(rSize, 0, c->plan.radixBits, c->params.prjMode);    // R's side alone
     int rc;
-    if ((rc = ensure_work(c, pl.workspaceBytes))) return rc;
-    for (bool& b : c->evSet) b = false;
-    c->built = false; c->htmBuilt = false; c->resident = false;
-    c->rSize = rSize; c->sSize = 0; c->tableSize = 0;
-    HJ_HIP(c, hipMemsetAsync(c->dCtr, 0, sizeof(Counters), c->stream));
+    // the scratch workspace of the passes holds nothing resident: a relation (here) or a slice (hj_prj_probe_dev) whose plan
+    // needs more than hj_reserve's (the chunk count is not monotone in the size, see prj_plan) gets a larger one
+    if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;
+    if ((rc = begin_operation(c, rSize, 0, 0))) return rc;
     if ((rc = record(c, EV_PRJ0))) return rc;
-    PrjBuffers buf{c->tmpA, c->partR, c->partS, c->work};
-    HJ_HIP(c, launch_prj_build(pl, buf, prj_resident_carve(c->prjRes, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr,
+    const PrjBuffers buf = prj_buffers(c);
+    HJ_HIP(c, launch_prj_build(pl, buf, prj_resident_carve(c->buf[B_PRJ_RES].p, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr(),
                                c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0], c->ev[EV_PRJ_S1], c->stream));
     c->evSet[EV_PRJ_PART] = c->evSet[EV_PRJ_S0] = c->evSet[EV_PRJ_S1] = true;
     if ((rc = record(c, EV_PRJ1))) return rc;
@@ -818,21 +795,20 @@ int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
 
 int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || (!dS && sSize)) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dS || !sSize);
     if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: no resident R (call hj_prj_build_dev first)");
-    if (sSize > c->prjMaxSlice || sSize + 2 > c->capPartS || sSize + 2 > c->capTmp ||
-        prj_resident_bytes(c->resPlan.radixBits, sSize) > c->capPrjRes)
+    if (sSize > c->prjMaxSlice || (sSize + 2) * sizeof(uint64_t) > c->buf[B_PART_S].bytes || (sSize + 2) * sizeof(uint64_t) > c->buf[B_TMP].bytes ||
+        prj_resident_bytes(c->resPlan.radixBits, sSize) > c->buf[B_PRJ_RES].bytes)
         return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: slice larger than the sSize given to hj_reserve()");
     if (sSize == 0) return HJ_OK;
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, c->params.prjMode);   // fragS: the slice's own geometry
     int rc;
-    if ((rc = ensure_work(c, pl.workspaceBytes))) return rc;
+    if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;      // R stays resident: see hj_prj_build_dev
     if ((rc = record(c, EV_RP0))) return rc;
-    PrjBuffers buf{c->tmpA, c->partR, c->partS, c->work};
-    HJ_HIP(c, launch_prj_probe(c->resPlan, c->resR, pl, buf, prj_resident_carve(c->prjRes, c->resPlan.radixBits, sSize), dS, sSize,
-                               c->nCU, c->dCtr, c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
+    const PrjBuffers buf = prj_buffers(c);
+    HJ_HIP(c, launch_prj_probe(c->resPlan, c->resR, pl, buf, prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize), dS, sSize,
+                               c->nCU, c->dCtr(), c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
     c->evSet[EV_RP_PART] = c->evSet[EV_RP_JOIN0] = true;
     if ((rc = record(c, EV_RP1))) return rc;
     c->sSize += sSize;
@@ -842,13 +818,12 @@ int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
 
 int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !out) return HJ_ERR_INVALID;
+    HJ_ENTER(c, out);
     if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_resident_info: no resident R");
     HJ_HIP(c, hipSetDevice(c->device));
-    const PrjResident res = prj_resident_carve(c->prjRes, c->resPlan.radixBits, 0);
+    const PrjResident res = prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, 0);
     unsigned long long st[4];
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipMemcpyAsync(st, res.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     const PrjPlan& pl = c->resPlan;
@@ -877,15 +852,12 @@ int hj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_t* d
         // and two radix passes are cheaper
         HJ_HIP(c, hipSetDevice(c->device));
         if (!is_pow2(rSize) || rSize > (1ull << 31)) return hj_prj_join_dev(c, dR, rSize, dS, sSize);   // see hj_reserve
-        if (2 * rSize + kTableSlack > c->tableCapSlots)
+        if ((2 * rSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
             return fail(c, HJ_ERR_STATE, "hj_join_dev: hj_reserve() not called for this rSize");
-        const bool canOwn = own_supported(2 * rSize) && c->capOwner >= own_owner_bytes(2 * rSize) &&
-                            c->capQueue >= own_queue_bytes(rSize);
-        const bool canWave = wave_supported(2 * rSize) && c->capQueue >= wave_queue_bytes(rSize, c->nCU);
+        const BuildCaps can = build_caps(c, rSize, 2 * rSize);
         uint32_t v = 1;
-        const bool canCompact = canWave && wave_compact_supported(2 * rSize, probe_len(c->params));
-        if ((canOwn || canWave) && c->params.buildVariant != 1 &&
-            (rc = sample_variant(c, dR, false, rSize, 2 * rSize, 0, canOwn, canWave, &v, canCompact))) return rc;
+        if ((can.own || can.wave) && c->params.buildVariant != 1 &&
+            (rc = sample_variant(c, dR, false, rSize, 2 * rSize, 0, can, &v))) return rc;
         // no locality: both table phases would be random HBM accesses. Loose locality (variant 2) pays for every tuple
         // that leaves its window with global atomics: at 2^27, local_shuffle W=2^11 (3.8 % deferred) the table join
         // takes 1.09 ms against the radix join's 1.81 ms, at W=2^12 (36 % deferred) 2.79 against 1.83 (round 3, deferred
@@ -903,29 +875,27 @@ int hj_join_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, const uint64_t* d
 
 int hj_checksums_dev(hj_ctx* c)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c) return HJ_ERR_INVALID;
+    HJ_ENTER(c, true);
     if (!c->built) return fail(c, HJ_ERR_STATE, "hj_checksums_dev: no table");
     HJ_HIP(c, hipSetDevice(c->device));
     // zero the two sums so the call is idempotent
-    HJ_HIP(c, hipMemsetAsync(&c->dCtr->tableSumHalf, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipMemsetAsync(&c->dCtr()->tableSumHalf, 0, 2 * sizeof(unsigned long long), c->stream));
     if (c->htmBuilt) {
-        HJ_HIP(c, hipMemsetAsync(&c->dCtr->htmOverflowSum, 0, sizeof(unsigned long long), c->stream));
-        launch_htm_sums(c->table, c->htmBuckets, c->htmOverflow, c->dCtr, c->stream);
+        HJ_HIP(c, hipMemsetAsync(&c->dCtr()->htmOverflowSum, 0, sizeof(unsigned long long), c->stream));
+        launch_htm_sums(c->buf[B_TABLE].as<uint64_t>(), c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), c->dCtr(), c->stream);
         HJ_HIP(c, hipGetLastError());
         return HJ_OK;
     }
-    launch_table_sums(c->table, c->tableSize, c->tableSize / 2, c->dCtr, c->stream);
+    launch_table_sums(c->buf[B_TABLE].as<uint64_t>(), c->tableSize, c->tableSize / 2, c->dCtr(), c->stream);
     HJ_HIP(c, hipGetLastError());
     return HJ_OK;
 }
 
 int hj_fetch_result(hj_ctx* c, hj_result* out)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !out) return HJ_ERR_INVALID;
+    HJ_ENTER(c, out);
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     fold_counter_shards(c->hCtr);
     memset(out, 0, sizeof(*out));
@@ -991,27 +961,26 @@ int hj_fetch_result(hj_ctx* c, hj_result* out)
 
 int hj_export_table(hj_ctx* c, uint64_t* host_table, uint64_t tableSize)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !host_table) return HJ_ERR_INVALID;
+    HJ_ENTER(c, host_table);
     if (!c->built || c->htmBuilt || tableSize != c->tableSize) return fail(c, HJ_ERR_STATE, "hj_export_table: no open-addressing table of that size");
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     Counters k;
-    HJ_HIP(c, hipMemcpy(&k, c->dCtr, sizeof(k), hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(&k, c->dCtr(), sizeof(k), hipMemcpyDeviceToHost));
     // only [validLo, validHiEx + 512) holds defined values (hj_device.h); the rest is empty by definition
     const uint64_t lo = k.validLo, hi = k.validHiEx + 512 < tableSize ? k.validHiEx + 512 : tableSize;
     if (k.tableFormat == kFormatKeys4) {
         // compact device format (4-byte keys, 0xFFFFFFFF = empty) -> reference format (key, 0 = empty): the keys land in
         // the upper half of the caller's buffer and are widened from the front (the write position never passes the read one)
         uint32_t* keys = reinterpret_cast<uint32_t*>(host_table) + tableSize;
-        HJ_HIP(c, hipMemcpy(keys, c->table, tableSize * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HJ_HIP(c, hipMemcpy(keys, c->buf[B_TABLE].p, tableSize * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < tableSize; ++i) {
             const uint32_t v = keys[i];
             host_table[i] = (i < lo || i >= hi || v == 0xFFFFFFFFu) ? 0 : v;
         }
         return HJ_OK;
     }
-    HJ_HIP(c, hipMemcpy(host_table, c->table, tableSize * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(host_table, c->buf[B_TABLE].p, tableSize * sizeof(uint64_t), hipMemcpyDeviceToHost));
     // device format (index << 32 | key, all ones = empty) -> reference format (key, 0 = empty)
     for (uint64_t i = 0; i < tableSize; ++i)
         host_table[i] = (i < lo || i >= hi || host_table[i] == kEmpty) ? 0 : (uint32_t)host_table[i];
@@ -1021,11 +990,10 @@ int hj_export_table(hj_ctx* c, uint64_t* host_table, uint64_t tableSize)
 int hj_export_buckets(hj_ctx* c, void* host_buckets, uint64_t numBuckets, void* host_overflows, uint64_t overflowCap,
                       uint64_t* nOverflow)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !host_buckets) return HJ_ERR_INVALID;
+    HJ_ENTER(c, host_buckets);
     if (!c->htmBuilt || numBuckets != c->htmBuckets) return fail(c, HJ_ERR_STATE, "hj_export_buckets: no htm table of that many buckets");
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     fold_counter_shards(c->hCtr);
     const uint64_t used = c->hCtr->htmOverflowBuckets;
@@ -1046,12 +1014,12 @@ int hj_export_buckets(hj_ctx* c, void* host_buckets, uint64_t numBuckets, void* 
     const uint64_t defLo = c->hCtr->validLo >> 2;
     uint64_t defHi = (c->hCtr->validHiEx + 512) >> 2;
     defHi = defHi < numBuckets ? defHi : numBuckets;
-    HJ_HIP(c, hipMemcpy(host_buckets, c->table, numBuckets * 32, hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(host_buckets, c->buf[B_TABLE].p, numBuckets * 32, hipMemcpyDeviceToHost));
     convert(static_cast<uint64_t*>(host_buckets), numBuckets, defLo, defHi);
     if (host_overflows) {
         memset(host_overflows, 0, 32);                           // index 0 is unused (as in the reference)
         if (used) {
-            HJ_HIP(c, hipMemcpy(static_cast<char*>(host_overflows) + 32, c->htmOverflow + 4, used * 32, hipMemcpyDeviceToHost));
+            HJ_HIP(c, hipMemcpy(static_cast<char*>(host_overflows) + 32, c->buf[B_HTM_OVERFLOW].as<uint64_t>() + 4, used * 32, hipMemcpyDeviceToHost));
             convert(static_cast<uint64_t*>(host_overflows) + 4, used, 0, used);
         }
     }
@@ -1065,14 +1033,16 @@ int hj_run(hj_ctx* c, const hj_params* params, const uint64_t* relR, uint64_t rS
     if (!relS) sSize = 0;
     int rc;
     if ((rc = hj_reserve(c, params, rSize, sSize))) return rc;
-    if ((rc = grow(c, c->stageR, c->capStageR, rSize + 2))) return rc;
-    if (sSize && (rc = grow(c, c->stageS, c->capStageS, sSize + 2))) return rc;
+    if ((rc = c->buf[B_STAGE_R].reserve(c, (rSize + 2) * sizeof(uint64_t)))) return rc;
+    if (sSize && (rc = c->buf[B_STAGE_S].reserve(c, (sSize + 2) * sizeof(uint64_t)))) return rc;
+    uint64_t* const stageR = c->buf[B_STAGE_R].as<uint64_t>();
+    uint64_t* const stageS = c->buf[B_STAGE_S].as<uint64_t>();
     const auto t0 = std::chrono::steady_clock::now();
-    HJ_HIP(c, hipMemcpyAsync(c->stageR, relR, rSize * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    if (sSize) HJ_HIP(c, hipMemcpyAsync(c->stageS, relS, sSize * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HJ_HIP(c, hipMemcpyAsync(stageR, relR, rSize * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (sSize) HJ_HIP(c, hipMemcpyAsync(stageS, relS, sSize * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     c->h2d_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    if ((rc = hj_join_dev(c, c->stageR, rSize, sSize ? c->stageS : nullptr, sSize))) return rc;
+    if ((rc = hj_join_dev(c, stageR, rSize, sSize ? stageS : nullptr, sSize))) return rc;
     if (!c->prjRan && (rc = hj_checksums_dev(c))) return rc;
     return hj_fetch_result(c, out);
 }
@@ -1126,8 +1096,7 @@ int hj_zipf_open(hj_ctx* c, uint64_t alphabetSize, double theta, unsigned seed)
 
 int hj_zipf_next_dev(hj_ctx* c, uint64_t n, uint64_t* dOut)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || (!dOut && n)) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dOut || !n);
     if (!c->zipfRng) return fail(c, HJ_ERR_STATE, "hj_zipf_next_dev: hj_zipf_open() first");
     HJ_HIP(c, hipSetDevice(c->device));
     // pieces of at most 2^26 draws through two pinned buffers: the host draws piece k + 1 of the serial rand() stream
@@ -1187,38 +1156,31 @@ static int shard_check(hj_ctx* c, const char* who, uint64_t n, uint32_t nShards,
 int hj_shard_histogram_dev(hj_ctx* c, const uint64_t* dIn, uint64_t n, uint32_t nShards, uint32_t mode,
                            uint64_t* dCounts)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || (!dIn && n) || !dCounts) return HJ_ERR_INVALID;
+    HJ_ENTER(c, (dIn || !n) && dCounts);
     int rc = shard_check(c, "hj_shard_histogram_dev: nShards must be a power of two <= 64", n, nShards, mode);
     if (rc) return rc;
     HJ_HIP(c, hipSetDevice(c->device));
     // reuse the slot of the same input, else the least recently used one
     hj_ctx::ShardPlan* slot = &c->shard[0];
     for (auto& sp : c->shard) if (sp.in == dIn && sp.n == n) { slot = &sp; break; } else if (sp.stamp < slot->stamp) slot = &sp;
-    const size_t need = shard_work_bytes(n, nShards);
-    if (need > slot->cap) {
-        HJ_HIP(c, hipStreamSynchronize(c->stream));
-        if (slot->work) { HJ_HIP(c, hipFree(slot->work)); slot->work = nullptr; slot->cap = 0; }
-        HJ_HIP(c, hipMalloc(&slot->work, need));
-        slot->cap = need;
-    }
+    DevBuf& work = c->buf[B_SHARD0 + (slot - c->shard)];
+    if ((rc = work.reserve(c, shard_work_bytes(n, nShards)))) return rc;
     slot->in = dIn; slot->n = n; slot->nShards = nShards; slot->mode = mode; slot->stamp = ++c->shardStamp;
-    HJ_HIP(c, launch_shard_hist(dIn, n, nShards, mode, slot->work, reinterpret_cast<unsigned long long*>(dCounts), c->stream));
+    HJ_HIP(c, launch_shard_hist(dIn, n, nShards, mode, work.p, reinterpret_cast<unsigned long long*>(dCounts), c->stream));
     return HJ_OK;
 }
 
 int hj_shard_scatter_dev(hj_ctx* c, const uint64_t* dIn, uint64_t n, uint32_t nShards, uint32_t mode,
                          const uint64_t* dCounts, uint32_t* dOutKeys)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || (!dIn && n) || !dCounts || (!dOutKeys && n)) return HJ_ERR_INVALID;
+    HJ_ENTER(c, (dIn || !n) && dCounts && (dOutKeys || !n));
     int rc = shard_check(c, "hj_shard_scatter_dev: nShards must be a power of two <= 64", n, nShards, mode);
     if (rc) return rc;
     hj_ctx::ShardPlan* slot = nullptr;
-    for (auto& sp : c->shard) if (sp.in == dIn && sp.n == n && sp.nShards == nShards && sp.mode == mode && sp.work) slot = &sp;
+    for (auto& sp : c->shard) if (sp.in == dIn && sp.n == n && sp.nShards == nShards && sp.mode == mode && c->buf[B_SHARD0 + (&sp - c->shard)].p) slot = &sp;
     if (!slot) return fail(c, HJ_ERR_STATE, "hj_shard_scatter_dev: call hj_shard_histogram_dev on this input (same nShards and mode) first");
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, launch_shard_scatter_ordered(dIn, n, nShards, mode, slot->work, dOutKeys, c->stream));
+    HJ_HIP(c, launch_shard_scatter_ordered(dIn, n, nShards, mode, c->buf[B_SHARD0 + (slot - c->shard)].p, dOutKeys, c->stream));
     slot->in = nullptr;   // consumed
     return HJ_OK;
 }
@@ -1243,8 +1205,7 @@ int hj_dev_free(hj_ctx* c, void* dptr)
 
 int hj_copy_h2d(hj_ctx* c, void* dst_dev, const void* src_host, uint64_t bytes)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !dst_dev || !src_host) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dst_dev && src_host);
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
@@ -1253,8 +1214,7 @@ int hj_copy_h2d(hj_ctx* c, void* dst_dev, const void* src_host, uint64_t bytes)
 
 int hj_copy_d2h(hj_ctx* c, void* dst_host, const void* src_dev, uint64_t bytes)
 {
-    if (c) c->streamAtBuildEnd = false;
-    if (!c || !dst_host || !src_dev) return HJ_ERR_INVALID;
+    HJ_ENTER(c, dst_host && src_dev);
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipStreamSynchronize(c->stream));

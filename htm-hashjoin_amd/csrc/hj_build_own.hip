@@ -772,50 +772,46 @@ size_t own_conflict_count_bytes(uint64_t n, int nCU)
     return (size_t)(nChunks + 2) * sizeof(uint32_t);
 }
 
-hipError_t launch_build_own(const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t* table,
-                            uint64_t tableSize, uint32_t probeLen, uint64_t idxBase, ShardCheck sc, int nCU, void* ownerBuf,
-                            void* queueBuf, uint32_t* deferCounts, Counters* ctr, Gate gate, int parts,
-                            hipEvent_t evPhaseA, hipStream_t s, const KernelEvents* kev, uint64_t* htmConflicts, uint32_t* htmCounts)
+hipError_t launch_build_own(const BuildJob& j, const OwnBufs& buf, Gate gate, int parts, KernelEvents kev)
 {
-    const bool htm = htmConflicts != nullptr;
-    if (htm && (key32 || probeLen != 3 || sc.mask || hshift)) return hipErrorInvalidValue;
-    const uint32_t numBlocks = (uint32_t)(tableSize >> kBlkShift);
+    const bool htm = buf.htmConflicts != nullptr;
+    if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || j.hshift)) return hipErrorInvalidValue;
+    const uint32_t numBlocks = (uint32_t)(j.tableSize >> kBlkShift);
     uint64_t nChunks, chunkLen;
-    own_geometry(n, nCU, &nChunks, &chunkLen);
+    own_geometry(j.n, j.nCU, &nChunks, &chunkLen);
     hipError_t e;
     if (parts & 1) {
-    if ((e = hipMemsetAsync(ownerBuf, 0, own_owner_bytes(tableSize), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(buf.owner, 0, own_owner_bytes(j.tableSize), j.s)) != hipSuccess) return e;
     if (nChunks > kOwnMaxChunks) return hipErrorInvalidValue;
-    if (htm && (e = hipMemsetAsync(htmCounts, 0, own_conflict_count_bytes(n, nCU), s)) != hipSuccess) return e;
+    if (htm && (e = hipMemsetAsync(buf.htmCounts, 0, own_conflict_count_bytes(j.n, j.nCU), j.s)) != hipSuccess) return e;
     const unsigned grid = (unsigned)nChunks;
-    if (kev && (e = hipEventRecord(kev->before, s)) != hipSuccess) return e;
+    if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
 #define HJ_OWN_LAUNCH(K32, CHK, HTM)                                                                                 \
-    hipLaunchKernelGGL((k_build_own<K32, CHK, HTM>), dim3(grid), dim3(kOwnThreads), kWinSlots * sizeof(uint64_t), s,  \
-                       R, n, chunkLen, table, tableSize - 1, hshift, probeLen, idxBase, sc,                            \
-                       static_cast<unsigned int*>(ownerBuf), static_cast<DeferredEntry*>(queueBuf), deferCounts, ctr, gate, \
-                       htmConflicts, htmCounts, (uint32_t)chunkLen)
+    hipLaunchKernelGGL((k_build_own<K32, CHK, HTM>), dim3(grid), dim3(kOwnThreads), kWinSlots * sizeof(uint64_t), j.s, \
+                       j.R, j.n, chunkLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,     \
+                       static_cast<unsigned int*>(buf.owner), static_cast<DeferredEntry*>(buf.queue), buf.deferCounts, j.ctr, gate, \
+                       buf.htmConflicts, buf.htmCounts, (uint32_t)chunkLen)
     if (htm) HJ_OWN_LAUNCH(false, false, true);
-    else if (sc.mask) { if (key32) HJ_OWN_LAUNCH(true, true, false); else HJ_OWN_LAUNCH(false, true, false); }   // the instances that count foreign tuples
-    else { if (key32) HJ_OWN_LAUNCH(true, false, false); else HJ_OWN_LAUNCH(false, false, false); }
+    else if (j.sc.mask) { if (j.key32) HJ_OWN_LAUNCH(true, true, false); else HJ_OWN_LAUNCH(false, true, false); }   // the instances that count foreign tuples
+    else { if (j.key32) HJ_OWN_LAUNCH(true, false, false); else HJ_OWN_LAUNCH(false, false, false); }
 #undef HJ_OWN_LAUNCH
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (kev && (e = hipEventRecord(kev->after, s)) != hipSuccess) return e;
-    if (evPhaseA && (e = hipEventRecord(evPhaseA, s)) != hipSuccess) return e;
+    if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
     }
     if (!(parts & 2)) return hipSuccess;
-    hipLaunchKernelGGL(k_finalize_range, dim3(1), dim3(64), 0, s, ctr, numBlocks, tableSize, gate);
-    hipLaunchKernelGGL(k_clear_unowned, dim3(2048), dim3(kBlock), 0, s, table,
-                       static_cast<const unsigned int*>(ownerBuf), ctr, numBlocks, tableSize, gate);
+    hipLaunchKernelGGL(k_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, numBlocks, j.tableSize, gate);
+    hipLaunchKernelGGL(k_clear_unowned, dim3(2048), dim3(kBlock), 0, j.s, j.table,
+                       static_cast<const unsigned int*>(buf.owner), j.ctr, numBlocks, j.tableSize, gate);
     // phase B: `parts` workgroups per slice (about 4096 in all: the walks are chains of dependent global atomics)
     const uint32_t defParts = nChunks >= 4096 ? 1u : (uint32_t)(4096 / nChunks);
     const dim3 gDef((unsigned)(nChunks * defParts));
     if (htm)
-        hipLaunchKernelGGL(k_build_deferred<true>, gDef, dim3(kBlock), 0, s, static_cast<const DeferredEntry*>(queueBuf), deferCounts,
-                           (uint32_t)chunkLen, defParts, table, tableSize - 1, hshift, probeLen, ctr, gate, htmConflicts + nChunks * chunkLen,
-                           htmCounts + nChunks);
+        hipLaunchKernelGGL(k_build_deferred<true>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), buf.deferCounts,
+                           (uint32_t)chunkLen, defParts, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, buf.htmConflicts + nChunks * chunkLen,
+                           buf.htmCounts + nChunks);
     else
-        hipLaunchKernelGGL(k_build_deferred<false>, gDef, dim3(kBlock), 0, s, static_cast<const DeferredEntry*>(queueBuf), deferCounts,
-                           (uint32_t)chunkLen, defParts, table, tableSize - 1, hshift, probeLen, ctr, gate, nullptr, nullptr);
+        hipLaunchKernelGGL(k_build_deferred<false>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), buf.deferCounts,
+                           (uint32_t)chunkLen, defParts, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr);
     return hipGetLastError();
 }
 

@@ -1009,76 +1009,72 @@ WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf)
 const uint32_t* wave_bounds_ptr(int nCU, const void* boundsBuf) { return static_cast<const uint32_t*>(boundsBuf) + wave_max_chunks(nCU); }
 size_t wave_conflict_bytes(uint64_t n, int nCU) { return wave_queue_bytes(n, nCU) / sizeof(DeferredEntry) * sizeof(uint64_t); }
 
-hipError_t launch_build_wave(const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t* table, uint64_t tableSize,
-                             uint32_t probeLen, uint64_t idxBase, ShardCheck sc, int nCU, void* boundsBuf, void* queueBuf,
-                             Counters* ctr, Gate gate, int parts, hipEvent_t evPhaseA, hipStream_t s, uint64_t* htmConflicts,
-                             int mode, uint32_t fallbackVariant, const KernelEvents* kev, bool htmRoute)
+hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, int parts, int mode, KernelEvents kev)
 {
-    const bool htm = htmConflicts != nullptr;
+    const bool htm = buf.htmConflicts != nullptr;
     const bool compact = mode == kWaveCompact;
-    if (htm && (key32 || probeLen != 3 || sc.mask || compact)) return hipErrorInvalidValue;
-    if (!key32 && hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
-    const uint32_t maxChunks = wave_max_chunks(nCU);
-    const uint64_t chunkLen = wave_chunk_len(n, nCU);
+    if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact)) return hipErrorInvalidValue;
+    if (!j.key32 && j.hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
+    const uint32_t maxChunks = wave_max_chunks(j.nCU);
+    const uint64_t chunkLen = wave_chunk_len(j.n, j.nCU);
     static_assert(kWvTile * 4 > (int)(kWvLook + kWvOverlap), "a seam may move by less than the shortest chunk");
     static_assert(kWvShadow + kWvOverlap == (uint32_t)kWvTile, "shadow zone + head zone = the first tile of a compact chunk");
     const uint32_t sliceLen = (uint32_t)wave_slice_len(chunkLen);
-    const uint32_t nChunks = (uint32_t)((n + chunkLen - 1) / chunkLen);
-    uint32_t* const raw = static_cast<uint32_t*>(boundsBuf);
+    const uint32_t nChunks = (uint32_t)((j.n + chunkLen - 1) / chunkLen);
+    uint32_t* const raw = static_cast<uint32_t*>(buf.bounds);
     uint32_t* const bounds = raw + maxChunks;                 // nChunks + 1 entries
     uint32_t* const starts = bounds + maxChunks + 1;          // nChunks + 1 entries
     uint32_t* const dcounts = starts + maxChunks + 1;
     uint32_t* const ccounts = dcounts + maxChunks;            // == wave_conflict_layout(...).counts
     uint32_t* const pcounts = ccounts + maxChunks;
-    const uint32_t numGran = (uint32_t)(tableSize >> kGranShift);
+    const uint32_t numGran = (uint32_t)(j.tableSize >> kGranShift);
     // workgroups a device of nCU compute units holds at once (the rotation of issue priorities goes by it)
-    const uint32_t residentWG = kWvWavesPerCu * (uint32_t)(nCU > 0 ? nCU : 256) / (uint32_t)kWvWaves;
+    const uint32_t residentWG = kWvWavesPerCu * (uint32_t)(j.nCU > 0 ? j.nCU : 256) / (uint32_t)kWvWaves;
     hipError_t e;
     const dim3 gRaw((nChunks + 1 + kBlock / 64 - 1) / (kBlock / 64)), gMain((nChunks + kWvWaves - 1) / kWvWaves);
     if (parts & kWavePre) {
-        if (htm) hipLaunchKernelGGL((k_wave_seams<false, true>), gRaw, dim3(kBlock), 0, s, R, n, (uint32_t)chunkLen, nChunks, tableSize - 1, hshift, starts, raw, gate);
-        else if (key32) hipLaunchKernelGGL((k_wave_seams<true, false>), gRaw, dim3(kBlock), 0, s, R, n, (uint32_t)chunkLen, nChunks, tableSize - 1, hshift, starts, raw, gate);
-        else hipLaunchKernelGGL((k_wave_seams<false, false>), gRaw, dim3(kBlock), 0, s, R, n, (uint32_t)chunkLen, nChunks, tableSize - 1, hshift, starts, raw, gate);
-        hipLaunchKernelGGL(k_wave_bounds_scan, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, s, raw, nChunks, numGran, bounds, gate);
+        if (htm) hipLaunchKernelGGL((k_wave_seams<false, true>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
+        else if (j.key32) hipLaunchKernelGGL((k_wave_seams<true, false>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
+        else hipLaunchKernelGGL((k_wave_seams<false, false>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
+        hipLaunchKernelGGL(k_wave_bounds_scan, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, j.s, raw, nChunks, numGran, bounds, gate);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (parts & kWaveMain) {
-        if (kev && (e = hipEventRecord(kev->before, s)) != hipSuccess) return e;
+        if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
 #define HJ_WV_LAUNCH(K32, CHK, HTM, CMP)                                                                             \
-    hipLaunchKernelGGL((k_build_wave<K32, CHK, HTM, CMP>), gMain, dim3(kWvThreads), kWvLdsBytes, s, R, n, sliceLen, \
-                       nChunks, starts, bounds, table, tableSize - 1, hshift, probeLen, idxBase, sc,                         \
-                       static_cast<DeferredEntry*>(queueBuf), dcounts, ctr, gate, htmConflicts, ccounts, residentWG, pcounts)
+    hipLaunchKernelGGL((k_build_wave<K32, CHK, HTM, CMP>), gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, \
+                       nChunks, starts, bounds, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,       \
+                       static_cast<DeferredEntry*>(buf.queue), dcounts, j.ctr, gate, buf.htmConflicts, ccounts, residentWG, pcounts)
         if (htm) HJ_WV_LAUNCH(false, false, true, false);
         else if (compact) {
-            if (sc.mask) { if (key32) HJ_WV_LAUNCH(true, true, false, true); else HJ_WV_LAUNCH(false, true, false, true); }
-            else { if (key32) HJ_WV_LAUNCH(true, false, false, true); else HJ_WV_LAUNCH(false, false, false, true); }
+            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, true); else HJ_WV_LAUNCH(false, true, false, true); }
+            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, true); else HJ_WV_LAUNCH(false, false, false, true); }
         }
-        else if (sc.mask) { if (key32) HJ_WV_LAUNCH(true, true, false, false); else HJ_WV_LAUNCH(false, true, false, false); }
-        else { if (key32) HJ_WV_LAUNCH(true, false, false, false); else HJ_WV_LAUNCH(false, false, false, false); }
+        else if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false); else HJ_WV_LAUNCH(false, true, false, false); }
+        else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false); else HJ_WV_LAUNCH(false, false, false, false); }
 #undef HJ_WV_LAUNCH
-        if (kev && (e = hipEventRecord(kev->after, s)) != hipSuccess) return e;
+        if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
         if (compact) {
-            // the seams check out or the classic build takes over (Counters::variant := fallbackVariant)
-            hipLaunchKernelGGL(k_wave_validate, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                               static_cast<const DeferredEntry*>(queueBuf), dcounts, pcounts, nChunks, sliceLen, ctr, gate);
-            hipLaunchKernelGGL(k_wave_decide, dim3(1), dim3(64), 0, s, ctr, tableSize, fallbackVariant, gate);
+            // the seams check out or the classic build takes over (Counters::variant := 3)
+            hipLaunchKernelGGL(k_wave_validate, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, j.s,
+                               static_cast<const DeferredEntry*>(buf.queue), dcounts, pcounts, nChunks, sliceLen, j.ctr, gate);
+            hipLaunchKernelGGL(k_wave_decide, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, 3u, gate);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (evPhaseA && (e = hipEventRecord(evPhaseA, s)) != hipSuccess) return e;
     }
     if (!(parts & kWaveTail)) return hipSuccess;
     if (compact) {
-        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(512), dim3(kBlock), 0, s, reinterpret_cast<uint32_t*>(table), ctr, tableSize, gate);
+        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(512), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table), j.ctr, j.tableSize, gate);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_wave_finalize_range, dim3(1), dim3(64), 0, s, ctr, tableSize, gate);
-    hipLaunchKernelGGL(k_wave_fill_edges, dim3(2048), dim3(kBlock), 0, s, table, ctr, tableSize, gate);
+    hipLaunchKernelGGL(k_wave_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, gate);
+    hipLaunchKernelGGL(k_wave_fill_edges, dim3(2048), dim3(kBlock), 0, j.s, j.table, j.ctr, j.tableSize, gate);
     const dim3 gDef((nChunks + kBlock / 64 - 1) / (kBlock / 64));   // one wavefront per slice
-    if (htm) hipLaunchKernelGGL(k_wave_deferred<true>, gDef, dim3(kBlock), 0, s, static_cast<const DeferredEntry*>(queueBuf), dcounts,
-                                nChunks, sliceLen, table, tableSize - 1, hshift, probeLen, ctr, gate, htmConflicts, ccounts,
-                                htmRoute ? bounds : nullptr);
-    else hipLaunchKernelGGL(k_wave_deferred<false>, gDef, dim3(kBlock), 0, s, static_cast<const DeferredEntry*>(queueBuf), dcounts,
-                            nChunks, sliceLen, table, tableSize - 1, hshift, probeLen, ctr, gate, nullptr, nullptr, nullptr);
+    if (htm) hipLaunchKernelGGL(k_wave_deferred<true>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), dcounts,
+                                nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, buf.htmConflicts, ccounts,
+                                buf.htmRoute ? bounds : nullptr);
+    else hipLaunchKernelGGL(k_wave_deferred<false>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), dcounts,
+                            nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 

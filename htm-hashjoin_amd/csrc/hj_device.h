@@ -182,15 +182,20 @@ constexpr unsigned long long kFormatSlots8 = 0, kFormatKeys4 = 1;
 struct DeferredEntry { uint64_t pos; uint64_t packed; };
 // HIP events recorded right before and right after ONE kernel launch (the dominant build kernel of a variant): its device
 // time for the roofline, without the pre-pass and the gated-off launches of the other variants around it
-struct KernelEvents { hipEvent_t before, after; };
+struct KernelEvents { hipEvent_t before = nullptr, after = nullptr; };     // null: the launch is not bracketed
 
 // ---- launch wrappers (defined in hj_kernels.hip) ---------------------------
 // Inputs come in two element formats: 8-byte DataGen tuples (key32 = false; value = key, payload bits must be 0)
 // or bare 32-bit keys (key32 = true; what the multi-GPU exchange delivers). Index of element i = idxBase + i.
+// One build as every build launcher sees it: filled once per build (hj_api.hip), handed to each of its launches
+struct BuildJob {
+    const void* R; bool key32; uint64_t n; uint64_t idxBase;                           // the input
+    uint64_t* table; uint64_t tableSize; uint32_t hshift, probeLen; ShardCheck sc;     // the table and how it is addressed
+    int nCU; Counters* ctr; hipStream_t s;                                             // where it runs
+};
 // fullRange != nullptr: also marks the whole table valid (variant 1 clears and may touch all of it): one launch less
 void launch_fill_empty(uint64_t* table, uint64_t nSlots, Gate gate, hipStream_t s, Counters* fullRange = nullptr, uint64_t tableSize = 0);
-void launch_build_atomic_min(const void* R, bool key32, uint64_t n, uint64_t* table, uint64_t tableSize, uint32_t hshift,
-                             uint32_t probeLen, uint64_t idxBase, ShardCheck sc, Counters* ctr, Gate gate, hipStream_t s);
+void launch_build_atomic_min(const BuildJob& job, Gate gate);
 // the probe and the checksums read Counters::tableFormat on the device: either table format, one launch
 void launch_probe(const void* S, bool key32, uint64_t n, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
                   uint32_t probeLen, ShardCheck sc, Counters* ctr, hipStream_t s);
@@ -264,15 +269,11 @@ __host__ __device__ inline uint32_t variant_for_sample(uint64_t outOwn, uint64_t
 hipError_t own_set_attributes();          // per device, at hj_create
 // phase A (LDS window) -> clear of unowned blocks -> phase B (deferred tuples).
 // Writes every table slot exactly once: no separate launch_fill_empty needed.
-hipError_t launch_build_own(const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t* table,
-                            uint64_t tableSize, uint32_t probeLen, uint64_t idxBase, ShardCheck sc, int nCU, void* ownerBuf,
-                            void* queueBuf, uint32_t* deferCounts, Counters* ctr, Gate gate, int parts,
-                            hipEvent_t evPhaseA, hipStream_t s, const KernelEvents* kev = nullptr,
-                            uint64_t* htmConflicts = nullptr, uint32_t* htmCounts = nullptr);   // parts: 1 = phase A (up to evPhaseA), 2 = the rest, 3 = both
+// deferCounts: kOwnMaxChunks words (the deferred queue is sliced by phase-A workgroup; entries per slice)
 // htmConflicts != nullptr: the bucketised table of --algo htm through the workgroup window (tuples only, probeLen 3): the
 // tuples that find their bucket full are listed per chunk, plus one last slice for the deferred phase's (own_conflict_layout)
-
-// deferCounts: kOwnMaxChunks words (the deferred queue is sliced by phase-A workgroup; entries per slice)
+struct OwnBufs { void* owner; void* queue; uint32_t* deferCounts; uint64_t* htmConflicts = nullptr; uint32_t* htmCounts = nullptr; };
+hipError_t launch_build_own(const BuildJob& job, const OwnBufs& buf, Gate gate, int parts, KernelEvents kev = {});   // parts: 1 = phase A (kev brackets its kernel), 2 = the rest, 3 = both
 constexpr uint32_t kOwnMaxChunks = 8192;
 
 // ---- wavefront-private build (defined in hj_build_wave.hip) ------------------
@@ -284,21 +285,18 @@ size_t wave_lds_bytes();
 bool   wave_supported(uint64_t tableSize);
 size_t wave_bounds_bytes(int nCU);
 size_t wave_queue_bytes(uint64_t n, int nCU);   // deferred queue: one slice per chunk
-// bounds pre-pass -> k_build_wave -> valid range + edge fill -> phase B. queueBuf: own_queue_bytes(n), used as one
+// bounds pre-pass -> k_build_wave -> valid range + edge fill -> phase B. queue: wave_queue_bytes(n, nCU), used as one
 // slice per chunk (a wavefront's deferred tuples go to ITS slice: no atomics in the kernel).
-// parts: kWavePre = the seam / bounds pre-pass, kWaveMain = the build kernel (then evPhaseA), kWaveTail = valid range,
+// parts: kWavePre = the seam / bounds pre-pass, kWaveMain = the build kernel (kev brackets it), kWaveTail = valid range,
 // edge fill and the deferred phase. mode kWaveCompact: the compact build (4-byte table, no deferred phase) -- its main
 // part is k_build_wave<COMPACT> + the seam check + k_wave_decide, which on failure resets the counters and sets
-// Counters::variant = fallbackVariant so that the classic build enqueued behind it (gated on that word) redoes the table;
+// Counters::variant = 3 so that the classic build enqueued behind it (gated on that word) redoes the table;
 // its tail is the edge fill alone. The pre-pass is the same for both modes (gate it with alt).
 constexpr int kWavePre = 1, kWaveMain = 2, kWaveTail = 4, kWaveAll = 7;
 constexpr int kWaveClassic = 0, kWaveCompact = 1;
-hipError_t launch_build_wave(const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t* table, uint64_t tableSize,
-                             uint32_t probeLen, uint64_t idxBase, ShardCheck sc, int nCU, void* boundsBuf, void* queueBuf,
-                             Counters* ctr, Gate gate, int parts, hipEvent_t evPhaseA, hipStream_t s,
-                             uint64_t* htmConflicts = nullptr, int mode = kWaveClassic, uint32_t fallbackVariant = 3,
-                             const KernelEvents* kev = nullptr, bool htmRoute = false);
 // htmRoute: the deferred phase files its conflicts under the chunk that owns their bucket (the LDS chain phase needs that)
+struct WaveBufs { void* bounds; void* queue; uint64_t* htmConflicts = nullptr; bool htmRoute = false; };
+hipError_t launch_build_wave(const BuildJob& job, const WaveBufs& buf, Gate gate, int parts, int mode = kWaveClassic, KernelEvents kev = {});
 const uint32_t* wave_bounds_ptr(int nCU, const void* boundsBuf);     // chunk c owns granules [bounds[c], bounds[c + 1])
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen);
 void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s);

@@ -158,15 +158,14 @@ k_build_atomic_min(const void* __restrict__ Rv, uint64_t n, uint64_t* __restrict
     flush_counter(&sh->foreign, bad >> 32);
 }
 
-void launch_build_atomic_min(const void* R, bool key32, uint64_t n, uint64_t* table, uint64_t tableSize, uint32_t hshift,
-                             uint32_t probeLen, uint64_t idxBase, ShardCheck sc, Counters* ctr, Gate gate, hipStream_t s)
+void launch_build_atomic_min(const BuildJob& j, Gate gate)
 {
-    if (key32)
-        hipLaunchKernelGGL(k_build_atomic_min<true>, dim3(grid_for(n + 1, kBlock)), dim3(kBlock), 0, s,
-                           R, n, table, tableSize - 1, hshift, probeLen, idxBase, sc, ctr, gate);
+    if (j.key32)
+        hipLaunchKernelGGL(k_build_atomic_min<true>, dim3(grid_for(j.n + 1, kBlock)), dim3(kBlock), 0, j.s,
+                           j.R, j.n, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc, j.ctr, gate);
     else
-        hipLaunchKernelGGL(k_build_atomic_min<false>, dim3(grid_for(n / 2 + 1, kBlock)), dim3(kBlock), 0, s,
-                           R, n, table, tableSize - 1, hshift, probeLen, idxBase, sc, ctr, gate);
+        hipLaunchKernelGGL(k_build_atomic_min<false>, dim3(grid_for(j.n / 2 + 1, kBlock)), dim3(kBlock), 0, j.s,
+                           j.R, j.n, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc, j.ctr, gate);
 }
 
 // ---------------------------------------------------------------------------
