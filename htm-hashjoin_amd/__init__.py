@@ -9,6 +9,6 @@ from ._lib import (  # noqa: F401
     HJ_ERR_UNKNOWN_ALGO, HJ_ERR_STATE, HJ_FLAG_KEEP_ROW_IDS, LIB_PATH, hj_params, hj_result, lib,
 )
 from .engine import (  # noqa: F401
-    HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs,
+    HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
     generate_data, generate_relation, device_count, SHARD_ONE_BASED, BUCKET_DTYPE,
 )

@@ -24,7 +24,9 @@ ALGO_IDS = {"nocc": HJ_ALGO_NOCC, "atomic": HJ_ALGO_ATOMIC, "htm": HJ_ALGO_HTM, 
             "auto": HJ_ALGO_AUTO}
 ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 
-HJ_FLAG_KEEP_ROW_IDS = 0x1      # hj_params.flags: open addressing never leaves the table in the compact 4-byte format
+# hj_params.flags: open addressing never leaves the table in the compact 4-byte format; the resident radix join keeps R
+# as {key, row} elements (hj_prj_probe_pairs_dev)
+HJ_FLAG_KEEP_ROW_IDS = 0x1
 
 
 class hj_params(C.Structure):
@@ -84,6 +86,7 @@ def _declare(lib):
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),
+        "hj_prj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
         "hj_prj_resident_info": ([vp, P(u64)], i32),
         "hj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_checksums_dev": ([vp], i32),

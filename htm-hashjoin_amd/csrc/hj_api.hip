@@ -92,6 +92,7 @@ struct hj_ctx {
     bool resident = false;                      // R is partitioned and nothing has replaced it since
     PrjPlan resPlan{};                          // the plan R was partitioned with (radix bits, R's layout)
     uint64_t resR = 0;
+    bool resRows = false;                       // the resident R holds {key, row} elements (reserved with HJ_FLAG_KEEP_ROW_IDS)
     bool resProbed = false, resProbeOpt = false;   // a probe ran since the build; its slice enqueued the histogram-free passes
     // shard helper: up to 4 inputs may sit between their histogram and their scatter (shard[i] works in buf[B_SHARD0 + i])
     struct ShardPlan { const uint64_t* in = nullptr; uint64_t n = 0; uint32_t nShards = 0, mode = 0; uint64_t stamp = 0; };
@@ -773,7 +774,9 @@ int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
         !c->buf[B_PRJ_RES].p || prj_resident_bytes(c->plan.radixBits, 0) > c->buf[B_PRJ_RES].bytes)
         return fail(c, HJ_ERR_STATE, "hj_prj_build_dev: hj_reserve() not called for this rSize");
     HJ_HIP(c, hipSetDevice(c->device));
-    const PrjPlan pl = prj_plan(rSize, 0, c->plan.radixBits, c->params.prjMode);    // R's side alone
+    // HJ_FLAG_KEEP_ROW_IDS: R stays resident as {key, row} elements, which only the exact passes carry (mode 1)
+    const bool rows = (c->params.flags & HJ_FLAG_KEEP_ROW_IDS) != 0;
+    const PrjPlan pl = prj_plan(rSize, 0, c->plan.radixBits, rows ? 1u : c->params.prjMode);    // R's side alone
     int rc;
     // the scratch workspace of the passes holds nothing resident: a relation (here) or a slice (hj_prj_probe_dev) whose plan
     // needs more than hj_reserve's (the chunk count is not monotone in the size, see prj_plan) gets a larger one
@@ -781,15 +784,44 @@ int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
     if ((rc = begin_operation(c, rSize, 0, 0))) return rc;
     if ((rc = record(c, EV_PRJ0))) return rc;
     const PrjBuffers buf = prj_buffers(c);
-    HJ_HIP(c, launch_prj_build(pl, buf, prj_resident_carve(c->buf[B_PRJ_RES].p, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr(),
+    if (rows) HJ_HIP(c, launch_prj_build_rows(pl, buf, prj_resident_carve(c->buf[B_PRJ_RES].p, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr(),
+                                              c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0], c->ev[EV_PRJ_S1], c->stream));
+    else HJ_HIP(c, launch_prj_build(pl, buf, prj_resident_carve(c->buf[B_PRJ_RES].p, pl.radixBits, 0), dR, rSize, c->nCU, c->dCtr(),
                                c->ev[EV_PRJ_PART], c->ev[EV_PRJ_S0], c->ev[EV_PRJ_S1], c->stream));
     c->evSet[EV_PRJ_PART] = c->evSet[EV_PRJ_S0] = c->evSet[EV_PRJ_S1] = true;
     if ((rc = record(c, EV_PRJ1))) return rc;
     c->prjRan = true;
     c->prjOptimistic = pl.optimistic;
     c->algoUsed = HJ_ALGO_PRJ;
-    c->resident = true; c->resPlan = pl; c->resR = rSize;
+    c->resident = true; c->resPlan = pl; c->resR = rSize; c->resRows = rows;
     c->resProbed = false; c->resProbeOpt = false;
+    return HJ_OK;
+}
+
+// whether a slice fits what hj_reserve sized for the probes of a resident R
+static bool prj_slice_fits(const hj_ctx* c, uint64_t sSize)
+{
+    return sSize <= c->prjMaxSlice && (sSize + 2) * sizeof(uint64_t) <= c->buf[B_PART_S].bytes && (sSize + 2) * sizeof(uint64_t) <= c->buf[B_TMP].bytes &&
+           prj_resident_bytes(c->resPlan.radixBits, sSize) <= c->buf[B_PRJ_RES].bytes;
+}
+
+// One probe of a resident R of {key, row} elements: the slice's row-id passes and the pairs join, timed as a probe
+// (EV_RP*); pairsCall: also as a pairs call (EV_PAIRS*), the facts hj_pairs_info reports
+static int prj_probe_rows(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, const PairsOut& out, bool pairsCall)
+{
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, 1u);     // exact passes only: they carry the rows
+    int rc;
+    if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;      // R stays resident: see hj_prj_build_dev
+    if ((rc = record(c, EV_RP0))) return rc;
+    if (pairsCall && (rc = record(c, EV_PAIRS0))) return rc;
+    HJ_HIP(c, launch_prj_probe_rows(c->resPlan, pl, prj_buffers(c), prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize),
+                                    dS, sSize, sIdxBase, out, c->nCU, c->dCtr(), c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
+    c->evSet[EV_RP_PART] = c->evSet[EV_RP_JOIN0] = true;
+    if (pairsCall && (rc = record(c, EV_PAIRS1))) return rc;
+    if ((rc = record(c, EV_RP1))) return rc;
+    c->sSize += sSize;
+    c->resProbed = true; c->resProbeOpt = false;
     return HJ_OK;
 }
 
@@ -797,10 +829,14 @@ int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
 {
     HJ_ENTER(c, dS || !sSize);
     if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: no resident R (call hj_prj_build_dev first)");
-    if (sSize > c->prjMaxSlice || (sSize + 2) * sizeof(uint64_t) > c->buf[B_PART_S].bytes || (sSize + 2) * sizeof(uint64_t) > c->buf[B_TMP].bytes ||
-        prj_resident_bytes(c->resPlan.radixBits, sSize) > c->buf[B_PRJ_RES].bytes)
-        return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: slice larger than the sSize given to hj_reserve()");
+    if (!prj_slice_fits(c, sSize)) return fail(c, HJ_ERR_STATE, "hj_prj_probe_dev: slice larger than the sSize given to hj_reserve()");
     if (sSize == 0) return HJ_OK;
+    if (c->resRows) {
+        // R holds {key, row} elements, which the counting kernels cannot read: the pairs join with capacity 0, counting into
+        // a word of its own (stats[4]: past the four the work items use) so that hj_pairs_info keeps the last pairs call
+        const PrjResident res = prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize);
+        return prj_probe_rows(c, dS, sSize, 0, PairsOut{nullptr, nullptr, 0, res.stats + 4}, false);
+    }
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, c->params.prjMode);   // fragS: the slice's own geometry
     int rc;
@@ -814,6 +850,22 @@ int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
     c->sSize += sSize;
     c->resProbed = true; c->resProbeOpt = pl.optimistic;
     return HJ_OK;
+}
+
+int hj_prj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
+                           uint64_t capacity)
+{
+    HJ_ENTER(c, dS || !sSize);
+    if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: no resident R (call hj_prj_build_dev first)");
+    if (!c->resRows) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: R was built without HJ_FLAG_KEEP_ROW_IDS");
+    if (!prj_slice_fits(c, sSize)) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: slice larger than the sSize given to hj_reserve()");
+    if (capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_prj_probe_pairs_dev: output pointer NULL with capacity > 0");
+    if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_prj_probe_pairs_dev: S row range exceeds 2^32 - 1");
+    if (sSize == 0) return HJ_OK;
+    const int rc = prj_probe_rows(c, dS, sSize, sIdxBase, PairsOut{dOutS, dOutR, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()}, true);
+    if (rc == HJ_OK) c->pairsCapacity = capacity;
+    return rc;
 }
 
 int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
@@ -833,7 +885,8 @@ int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
     out[1] = (!c->resProbed || !c->resProbeOpt) ? 0u : (c->hCtr->prjFallback ? 2u : 1u);
     out[2] = st[1]; out[3] = st[2]; out[4] = st[3];
     // R's keys (the fragments with their slack, or one dense run) + its offsets and fragment counts
-    out[5] = 4 * (fragR ? P * pl.fragR.C2 * pl.fragR.cap2 : c->resR) + 4 * (P + 1) + 4 * P * 16;
+    // (reserved with HJ_FLAG_KEEP_ROW_IDS: one dense run of 8-byte {key, row} elements)
+    out[5] = (c->resRows ? 8 * c->resR : 4 * (fragR ? P * pl.fragR.C2 * pl.fragR.cap2 : c->resR)) + 4 * (P + 1) + 4 * P * 16;
     out[6] = out[7] = 0;
     return HJ_OK;
 }

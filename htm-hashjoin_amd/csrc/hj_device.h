@@ -398,7 +398,8 @@ struct PrjResident {
     uint32_t* itemCnt;              // [2P + 1] items per partition: split partitions first, then the rest; scanned in place
     uint32_t* scanSums;             // scan workspace of itemCnt
     uint2* items;                   // [P + maxSlice / kPrjItemS + 1] (partition, S chunk)
-    unsigned long long* stats;      // [4] next item ticket, items, split partitions, largest S partition
+    unsigned long long* stats;      // [4] next item ticket, items, split partitions, largest S partition;
+                                    // [4]: the pair count of a counting probe against a {key, row} R (hj_prj_probe_dev)
 };
 constexpr uint32_t kPrjItemS = 1u << 16;  // S tuples per join work item at most (hj_prj.hip, k_prj_probe_items)
 size_t prj_resident_bytes(uint32_t radixBits, uint64_t maxSlice);
@@ -412,5 +413,16 @@ hipError_t launch_prj_build(const PrjPlan& plan, const PrjBuffers& buf, const Pr
 hipError_t launch_prj_probe(const PrjPlan& planR, uint64_t nR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
                             const uint64_t* S, uint64_t nS, int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evJoin0,
                             hipStream_t s);
+
+// ---- row-id form of the resident radix join (HJ_FLAG_KEEP_ROW_IDS; defined in hj_prj_pairs.hip) ----
+// buf.partR / partS / tmpA hold 8-byte {key, row} elements; exact passes only (plan = prj_plan(.., mode 1)).
+// R's passes (row = position in R) into buf.partR / res.offR, then R's checksum.
+hipError_t launch_prj_build_rows(const PrjPlan& plan, const PrjBuffers& buf, const PrjResident& res, const uint64_t* R, uint64_t nR,
+                                 int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s);
+// S's passes (row = sIdxBase + position in S), the work-item list, the join that emits (S row, R row) pairs to `out`
+// (out.cursor is zeroed on the stream first; out.capacity 0: the pairs are counted only). Adds to Counters::prjMatches.
+hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+                                 const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
+                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s);
 
 }  // namespace hj

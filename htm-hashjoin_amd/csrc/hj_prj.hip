@@ -210,6 +210,40 @@ k_radix_hist(const void* __restrict__ in, PassParams p, uint32_t* __restrict__ h
     if (threadIdx.x < p.fan) hist[hist_index(p, r, threadIdx.x)] = h[threadIdx.x];
 }
 
+// The histogram of the row-id passes' first pass (HJ_FLAG_KEEP_ROW_IDS on a resident radix join, hj_prj_pairs.hip): it
+// reads every tuple anyway, so it also writes the tuple's {key, row} element -- row = rowBase + position, over the
+// input's own upper word -- to `stamped`, which the scatter passes then move whole (k_radix_scatter<false, false>).
+// One segment, the dense relation: chunks start at even positions, so the body goes as aligned 16-byte vectors.
+__global__ void __launch_bounds__(kBlock)
+k_radix_hist_rows(const uint64_t* __restrict__ in, uint64_t* __restrict__ stamped, PassParams p, uint32_t* __restrict__ hist,
+                  uint32_t rowBase)
+{
+    __shared__ unsigned int h[kMaxFan];
+    const uint32_t c = blockIdx.x;
+    if (c >= p.chunkBase[p.nSeg]) return;
+    const ChunkRange r = chunk_range(p, c);
+    if (threadIdx.x < kMaxFan) h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t fmask = p.fan - 1;
+    const uint4* in4 = reinterpret_cast<const uint4*>(in);
+    uint4* out4 = reinterpret_cast<uint4*>(stamped);
+    const uint32_t vEnd = r.end >> 1;                        // r.begin is even (chunkLen is a multiple of kTile)
+    for (uint32_t v = (r.begin >> 1) + threadIdx.x; v < vEnd; v += kBlock) {
+        const uint4 t = in4[v];
+        const uint32_t row = rowBase + 2 * v;
+        out4[v] = uint4{t.x, row, t.z, row + 1};
+        atomicAdd(&h[(t.x >> p.shift) & fmask], 1u);
+        atomicAdd(&h[(t.z >> p.shift) & fmask], 1u);
+    }
+    if ((r.end & 1u) && threadIdx.x == 0) {                  // the relation's odd last tuple
+        const uint32_t key = (uint32_t)in[r.end - 1];
+        stamped[r.end - 1] = ((uint64_t)(rowBase + r.end - 1) << 32) | key;
+        atomicAdd(&h[(key >> p.shift) & fmask], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < p.fan) hist[hist_index(p, r, threadIdx.x)] = h[threadIdx.x];
+}
+
 // ---------------------------------------------------------------------------
 // exclusive scan of a uint32 array (3 kernels: block scan, scan of block sums, add)
 // ---------------------------------------------------------------------------
@@ -1419,11 +1453,16 @@ Work carve(const PrjPlan& pl, void* base)
     return w;
 }
 
+// The row-id form of a pass (HJ_FLAG_KEEP_ROW_IDS): 8-byte {key, row} elements out. stamped != nullptr: the pass that
+// reads the tuples -- its histogram writes their elements, row = rowBase + position, to `stamped`, and the scatter moves
+// those; nullptr: `in` holds elements already.
+struct PassRows { bool on; uint64_t* stamped; uint32_t rowBase; };
+
 // One radix pass: in -> out, segments segIn[nSeg+1] -> segOut[nSeg*fan+1].
-// in32: the input already holds bare keys (pass 2); the output always does.
+// in32: the input already holds bare keys (pass 2); the output always does, unless rows.on.
 hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const uint32_t* segIn, uint32_t nSeg,
                     uint32_t shift, uint32_t bits, uint32_t* segOut, const Work& w, Gate gate, hipStream_t s,
-                    hipEvent_t evScatter0 = nullptr, hipEvent_t evScatter1 = nullptr)
+                    hipEvent_t evScatter0 = nullptr, hipEvent_t evScatter1 = nullptr, PassRows rows = PassRows{false, nullptr, 0u})
 {
     const uint32_t fan = 1u << bits;
     const PassLayout l = pass_layout(n, nSeg, fan);
@@ -1432,7 +1471,11 @@ hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const 
     // entries past the live chunks must be zero for the scan to be a prefix of live data only
     const hipError_t e = hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * l.histEntries, s);
     if (e != hipSuccess) return e;
-    if (in32) hipLaunchKernelGGL(k_radix_hist<true>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, w.hist, gate);
+    if (rows.on && rows.stamped) {
+        hipLaunchKernelGGL(k_radix_hist_rows, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, static_cast<const uint64_t*>(in), rows.stamped,
+                           p, w.hist, rows.rowBase);
+        in = rows.stamped;
+    } else if (in32) hipLaunchKernelGGL(k_radix_hist<true>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, w.hist, gate);
     else hipLaunchKernelGGL(k_radix_hist<false>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, w.hist, gate);
     hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, gate);
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, w.sums, (uint32_t)l.scanBlocks, gate);
@@ -1443,12 +1486,33 @@ hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const 
     // elements, no register prefetch, <= 128 VGPRs (2 workgroups per CU); more, smaller workgroups and the
     // prefetching instance were slower or equal
     if (evScatter0) (void)hipEventRecord(evScatter0, s);
-    if (in32) hipLaunchKernelGGL((k_radix_scatter<true, true, 512, 4, false, 4>), dim3((unsigned)l.maxChunks), dim3(512), 0, s,
+    // row-id passes: tiles of 4096 elements of 8 bytes -- the same 128-byte runs at fan 256 and the same 36 KiB of LDS as
+    // the key passes (tiles of 8192 spill registers at the 128 that two workgroups per CU leave a thread)
+    if (rows.on) hipLaunchKernelGGL((k_radix_scatter<false, false, 512, 4, false, 4>), dim3((unsigned)l.maxChunks), dim3(512), 0, s,
+                                    in, static_cast<void*>(out), p, w.hist, gate);
+    else if (in32) hipLaunchKernelGGL((k_radix_scatter<true, true, 512, 4, false, 4>), dim3((unsigned)l.maxChunks), dim3(512), 0, s,
                                  in, static_cast<void*>(out), p, w.hist, gate);
     else hipLaunchKernelGGL((k_radix_scatter<false, true, 512, 8, false, 4>), dim3((unsigned)l.maxChunks), dim3(512), 0, s,
                             in, static_cast<void*>(out), p, w.hist, gate);
     if (evScatter1) (void)hipEventRecord(evScatter1, s);
     return hipGetLastError();
+}
+
+// The same two passes in the row-id form: tmp and out hold 8-byte {key, row} elements, row = rowBase + position in `in`.
+// The stamped copy of the input goes to the buffer pass 1 does not write: out (two passes) or tmp (one).
+hipError_t partition_relation_rows(const PrjPlan& pl, const Work& w, const uint64_t* in, uint64_t n, uint32_t rowBase,
+                                   uint64_t* tmp, uint64_t* out, uint32_t* finalOff, hipStream_t s,
+                                   hipEvent_t evS0 = nullptr, hipEvent_t evS1 = nullptr)
+{
+    uint32_t* const tmp32 = reinterpret_cast<uint32_t*>(tmp);
+    uint32_t* const out32 = reinterpret_cast<uint32_t*>(out);
+    hipLaunchKernelGGL(k_init_seg, dim3(1), dim3(64), 0, s, w.seg0, (uint32_t)n);
+    if (pl.bits2 == 0)
+        return run_pass(in, false, out32, n, w.seg0, 1, 0, pl.bits1, finalOff, w, kNoGate, s, evS0, evS1, PassRows{true, tmp, rowBase});
+    const hipError_t e = run_pass(in, false, tmp32, n, w.seg0, 1, 0, pl.bits1, w.seg1, w, kNoGate, s, evS0, evS1, PassRows{true, out, rowBase});
+    if (e != hipSuccess) return e;
+    return run_pass(tmp, false, out32, n, w.seg1, 1u << pl.bits1, pl.bits1, pl.bits2, finalOff, w, kNoGate, s, nullptr, nullptr,
+                    PassRows{true, nullptr, 0u});
 }
 
 hipError_t partition_relation(const PrjPlan& pl, const Work& w, const uint64_t* in, uint64_t n,
@@ -1914,6 +1978,8 @@ hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums,
     return hipGetLastError();
 }
 
+static hipError_t prj_pairs_set_attributes();     // hj_prj_pairs.hip
+
 hipError_t prj_set_attributes()
 {
     // per device (hj_create calls this with its device current): the LDS join table and the stable split's staging
@@ -1926,9 +1992,14 @@ hipError_t prj_set_attributes()
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_probe_items<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
+    if ((e = prj_pairs_set_attributes()) != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_scatter_stable),
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                sizeof(uint32_t) * (kStabMaxFan * kStabGroups + kStabTile + (kStabTile >> 5) + 1));
 }
 
 }  // namespace hj
+
+// the materialising form of the resident join: part of this translation unit, because it runs the passes above in their
+// row-id form and walks the work items k_prj_items_count / k_prj_items_fill build
+#include "hj_prj_pairs.hip"

@@ -1,0 +1,291 @@
+// hj_prj_pairs.hip -- the materialising form of the resident radix join for gfx950 (MI355X): hj_prj_build_dev on a
+// context reserved with HJ_FLAG_KEEP_ROW_IDS, hj_prj_probe_pairs_dev.
+//
+// Not a translation unit of its own: hj_prj.hip includes it at its end, because it instantiates that file's pass
+// templates and walks the work-item list its kernels build (k_prj_items_count / k_prj_items_fill, unchanged).
+//
+//   row-id passes      the exact passes of hj_prj.hip over 8-byte {key, row} elements (partition_relation_rows there): the
+//                      first histogram stamps the row -- idxBase + position in the input -- over each tuple's upper word
+//                      (k_radix_hist_rows), the scatters move the elements whole (k_radix_scatter<false, false>).
+//                      No histogram-free form: its fragments hold bare keys.
+//   k_prj_rows_checksum  prjChecksum of a resident R in this format (k_prj_join reads bare keys)
+//   k_prj_join_pairs   k_prj_probe_items with its result kept: per work item the R partition's LDS table holds
+//                      (key >> radixBits, R row) entries, duplicates of a key as separate entries; a probe walks its run to the
+//                      first empty slot and emits one (S row, R row) pair per equal entry
+//
+// Pair output as in hj_pairs.hip: pairs are staged in LDS, a full stage claims its run of the two output planes with ONE
+// 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
+// LDS: table 15360 slots x (4 B key + 4 B row) = 120 KiB, stage 4096 pairs x 8 B = 32 KiB, 152 KiB of the CU's 160.
+
+namespace hj {
+
+constexpr uint32_t kPairSlots = 15360;            // table slots: a key plane and a row plane of 60 KiB each
+constexpr uint32_t kPairBlockTuples = 11520;      // R tuples per LDS build (load <= 0.75)
+constexpr uint32_t kPairStage = 4096;             // pairs per stage, as in hj_pairs.hip
+constexpr int kPairElems = 2;                     // S elements per thread and round: on unique R keys a round fits half a stage
+constexpr uint32_t kPairWaves = kJoinThreads / 64;
+constexpr size_t kPairLdsBytes = sizeof(uint32_t) * (2 * kPairSlots + 2 * kPairStage);
+static_assert(kPairLdsBytes + 1024 <= 160 * 1024, "table, stage and the few static words must fit one CU's LDS");
+static_assert(kPairBlockTuples * 4 <= kPairSlots * 3, "a probe's walk ends at an empty slot: the table is never full");
+static_assert((uint32_t)kPairElems * kJoinThreads <= kPairStage, "a round of single matches fits an empty stage");
+
+// Slot of key-remainder k: the Fibonacci hash of join_hash, scaled to a slot count that is no power of two
+__device__ __forceinline__ uint32_t pair_hash(uint32_t k) { return __umulhi(k * 0x9E3779B1u, kPairSlots); }
+__device__ __forceinline__ uint32_t pair_next(uint32_t h) { return h + 1 == kPairSlots ? 0u : h + 1; }
+
+typedef unsigned int pairs_u4 __attribute__((ext_vector_type(4)));
+
+// flush_plane of hj_pairs.hip for a workgroup of kJoinThreads: lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity
+__device__ __forceinline__ void prj_flush_plane(const uint32_t* lds, uint32_t cnt, uint32_t* __restrict__ out, uint64_t base, uint64_t capacity)
+{
+    if (base >= capacity) return;
+    const uint64_t room = capacity - base;
+    const uint32_t lim = room < cnt ? (uint32_t)room : cnt;
+    uint32_t* const dst = out + base;
+    uint32_t lead = (uint32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
+    if (lead > lim) lead = lim;
+    if (threadIdx.x < lead) __builtin_nontemporal_store(lds[threadIdx.x], dst + threadIdx.x);
+    const uint32_t nv = (lim - lead) >> 2;
+    for (uint32_t v = threadIdx.x; v < nv; v += kJoinThreads) {
+        const uint32_t i = lead + 4u * v;
+        pairs_u4 x;
+        x.x = lds[i]; x.y = lds[i + 1]; x.z = lds[i + 2]; x.w = lds[i + 3];
+        __builtin_nontemporal_store(x, reinterpret_cast<pairs_u4*>(dst + i));
+    }
+    const uint32_t tail = lead + 4u * nv;
+    if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
+}
+
+// prjChecksum of a resident R of {key, row} elements, as k_prj_join sums it: (key >> radixBits) & (nextpow2(|partition|) - 1)
+__global__ void __launch_bounds__(kBlock)
+k_prj_rows_checksum(const uint2* __restrict__ partR, const uint32_t* __restrict__ offR, uint32_t radixBits, uint32_t nParts,
+                    Counters* __restrict__ ctr)
+{
+    unsigned long long checksum = 0;
+    for (uint32_t pid = blockIdx.x; pid < nParts; pid += gridDim.x) {
+        const uint32_t rb = offR[pid], re = offR[pid + 1];
+        if (re == rb) continue;
+        const uint32_t idxMask = next_pow2_u32(re - rb) - 1;
+        for (uint32_t i = rb + threadIdx.x; i < re; i += kBlock) checksum += (partR[i].x >> radixBits) & idxMask;
+    }
+    for (int off = 32; off > 0; off >>= 1) checksum += __shfl_down(checksum, off, 64);
+    if ((threadIdx.x & 63) == 0 && checksum) atomicAdd(&counter_shard(ctr)->prjChecksum, checksum);
+}
+
+// items[0 .. *nItemsAt) taken through *ticket (zeroed by the host), as in k_prj_probe_items; both relations in the exact
+// layout: partition pid = part[off[pid] .. off[pid + 1]), elements {x = key, y = row}. The arrays are separate __restrict__
+// parameters (k_prj_join: members of a struct became vector loads), and what an item reads is looked up before its LDS work.
+__global__ void __launch_bounds__(kJoinThreads)
+k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ offR,
+                 const uint2* __restrict__ partS, const uint32_t* __restrict__ offS,
+                 const uint2* __restrict__ items, const uint32_t* __restrict__ nItemsAt, unsigned long long* __restrict__ ticket,
+                 uint32_t radixBits, uint32_t* __restrict__ outS, uint32_t* __restrict__ outR, uint64_t capacity,
+                 unsigned long long* __restrict__ cursor, Counters* __restrict__ ctr)
+{
+    extern __shared__ uint32_t pairLds[];
+    uint32_t* const tabK = pairLds;                    // key remainders, kEmpty32 = free
+    uint32_t* const tabR = tabK + kPairSlots;          // the R row of the slot's entry
+    uint32_t* const stS = tabR + kPairSlots;           // the stage: S rows, R rows
+    uint32_t* const stR = stS + kPairStage;
+    __shared__ uint32_t wtot[2 * kPairWaves];          // the wavefronts' pair counts of a round, double-buffered by round parity
+    __shared__ unsigned long long sBase;               // where the run being written starts in the output
+    __shared__ uint32_t sNext;
+
+    const uint32_t nItems = *nItemsAt;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t fill = 0, round = 0;                      // the same in every thread
+    unsigned long long found = 0;                      // pairs of this workgroup (the same in every thread)
+
+    // everything staged -> its run of the output. Called by all threads together.
+    auto flush = [&]() {
+        if (threadIdx.x == 0) sBase = atomicAdd(cursor, (unsigned long long)fill);
+        __syncthreads();                               // the base is there, and so is every pair of the rounds before
+        const uint64_t base = sBase;
+        prj_flush_plane(stS, fill, outS, base, capacity);
+        prj_flush_plane(stR, fill, outR, base, capacity);
+        __syncthreads();                               // nobody refills the stage (or claims again) while it is being read
+        fill = 0;
+    };
+    // the matches of one S element: their number, the R row of the first
+    auto walk = [&](uint32_t key, bool ok, uint32_t& first) {
+        uint32_t m = 0;
+        if (ok) {
+            const uint32_t k = key >> radixBits;
+            uint32_t h = pair_hash(k);
+            for (;;) {
+                const uint32_t v = tabK[h];
+                if (v == kEmpty32) break;
+                if (v == k) { if (m == 0) first = tabR[h]; ++m; }
+                h = pair_next(h);
+            }
+        }
+        return m;
+    };
+    // put(S row, R row) for each of the m matches: the first from the register, further ones (duplicate keys in R) by a second walk
+    auto emit = [&](uint2 e, uint32_t m, uint32_t first, auto&& put) {
+        if (m == 0) return;
+        put(e.y, first);
+        if (m == 1) return;
+        const uint32_t k = e.x >> radixBits;
+        uint32_t h = pair_hash(k), seen = 0;
+        for (;;) {
+            const uint32_t v = tabK[h];
+            if (v == kEmpty32) break;
+            if (v == k && seen++) put(e.y, tabR[h]);
+            h = pair_next(h);
+        }
+    };
+
+    for (;;) {
+        if (threadIdx.x == 0) sNext = (uint32_t)atomicAdd(ticket, 1ull);
+        __syncthreads();
+        const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
+        if (cur >= nItems) break;                      // workgroup-uniform
+        // (sNext is written again only behind the barriers of this item: an item has R tuples, hence at least one build)
+        const uint2 it = items[cur];
+        const uint32_t rb = offR[it.x], nRp = offR[it.x + 1] - rb;
+        const uint32_t sb0 = offS[it.x], lo = it.y * kPrjItemS, rest = offS[it.x + 1] - sb0 - lo;
+        const uint32_t sb = sb0 + lo, nSi = rest < kPrjItemS ? rest : kPrjItemS;      // >= 1: k_prj_items_count
+        auto load_s = [&](uint32_t j0, uint2 (&e)[kPairElems]) {       // clamped: every lane loads a valid address
+#pragma unroll
+            for (int u = 0; u < kPairElems; ++u) {
+                const uint32_t j = j0 + (uint32_t)u * kJoinThreads + threadIdx.x;
+                e[u] = partS[sb + (j < nSi ? j : nSi - 1)];
+            }
+        };
+        // an R partition larger than one table: several builds, the item's S probed against each
+        for (uint32_t blk = 0; blk < nRp; blk += kPairBlockTuples) {
+            const uint32_t bn = nRp - blk > kPairBlockTuples ? kPairBlockTuples : nRp - blk;
+            uint2 nxt[kPairElems];
+            load_s(0u, nxt);                                           // in flight while the table is built
+            for (uint32_t i = threadIdx.x; i < kPairSlots; i += kJoinThreads) tabK[i] = kEmpty32;
+            __syncthreads();
+            for (uint32_t i0 = threadIdx.x; i0 < bn; i0 += kTailPre * kJoinThreads) {
+                uint2 e[kTailPre];
+#pragma unroll
+                for (int u = 0; u < kTailPre; ++u) {
+                    const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
+                    e[u] = partR[rb + blk + (i < bn ? i : bn - 1)];
+                }
+#pragma unroll
+                for (int u = 0; u < kTailPre; ++u)
+                    if (i0 + (uint32_t)u * kJoinThreads < bn) {
+                        const uint32_t k = e[u].x >> radixBits;
+                        uint32_t h = pair_hash(k);
+                        while (atomicCAS(&tabK[h], kEmpty32, k) != kEmpty32) h = pair_next(h);    // an equal key is one more entry
+                        tabR[h] = e[u].y;
+                    }
+            }
+            __syncthreads();
+            // rounds of kPairElems S elements per thread; every thread runs the same number of them (they meet at barriers)
+            for (uint32_t j0 = 0; j0 < nSi; j0 += kPairElems * kJoinThreads) {
+                uint2 e[kPairElems];
+#pragma unroll
+                for (int u = 0; u < kPairElems; ++u) e[u] = nxt[u];
+                load_s(j0 + kPairElems * kJoinThreads < nSi ? j0 + kPairElems * kJoinThreads : j0, nxt);
+                uint32_t m[kPairElems], first[kPairElems], mine = 0;
+#pragma unroll
+                for (int u = 0; u < kPairElems; ++u) {
+                    first[u] = 0;
+                    m[u] = walk(e[u].x, j0 + (uint32_t)u * kJoinThreads + threadIdx.x < nSi, first[u]);
+                    mine += m[u];
+                }
+                // the round's pair count: wavefront scan, the totals exchanged through LDS, one barrier
+                uint32_t inc = mine;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t below = __shfl_up(inc, off, 64);
+                    if (lane >= (uint32_t)off) inc += below;
+                }
+                uint32_t* const wt = wtot + (round & 1u) * kPairWaves;
+                if (lane == 63) wt[wave] = inc;
+                __syncthreads();
+                uint32_t wbase = 0, tot = 0;
+#pragma unroll
+                for (uint32_t w = 0; w < kPairWaves; ++w) {
+                    const uint32_t c = wt[w];
+                    if (w < wave) wbase += c;
+                    tot += c;
+                }
+                round += 1;
+                const uint32_t before = wbase + inc - mine;            // pairs of the round in front of this lane's
+                if (tot > kPairStage) {
+                    // Duplicate keys on both sides: more pairs than a stage holds (one S tuple alone can match a whole
+                    // table). The round claims its run itself and every lane writes its pairs straight to the planes.
+                    if (fill) flush();
+                    if (threadIdx.x == 0) sBase = atomicAdd(cursor, (unsigned long long)tot);
+                    __syncthreads();
+                    // (sBase is written again only behind the next round's barrier)
+                    uint64_t g = sBase + before;
+                    auto put = [&](uint32_t s, uint32_t r) {
+                        if (g < capacity) { outS[g] = s; outR[g] = r; }
+                        ++g;
+                    };
+#pragma unroll
+                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], put);
+                } else {
+                    if (fill + tot > kPairStage) flush();              // workgroup-uniform
+                    uint32_t pos = fill + before;
+                    auto put = [&](uint32_t s, uint32_t r) { stS[pos] = s; stR[pos] = r; ++pos; };
+#pragma unroll
+                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], put);
+                    fill += tot;
+                }
+                found += tot;
+            }
+            __syncthreads();                                           // the table is read no more
+        }
+    }
+    if (fill) flush();
+    if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr)->prjMatches, found);
+}
+
+static hipError_t prj_pairs_set_attributes()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_join_pairs), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kPairLdsBytes);
+}
+
+// R's row-id passes into buf.partR / res.offR (plan: exact passes only), then R's checksum
+hipError_t launch_prj_build_rows(const PrjPlan& pl, const PrjBuffers& buf, const PrjResident& res, const uint64_t* R, uint64_t nR,
+                                 int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s)
+{
+    const Work w = carve(pl, buf.work);
+    hipError_t e;
+    if ((e = partition_relation_rows(pl, w, R, nR, 0u, buf.tmpA, buf.partR, res.offR, s, evScatter0, evScatter1)) != hipSuccess) return e;
+    if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    const uint32_t P = 1u << pl.radixBits;
+    const unsigned want = 4u * (unsigned)nCU;
+    hipLaunchKernelGGL(k_prj_rows_checksum, dim3(P < want ? P : want), dim3(kBlock), 0, s,
+                       reinterpret_cast<const uint2*>(buf.partR), res.offR, pl.radixBits, P, ctr);
+    return hipGetLastError();
+}
+
+// S's row-id passes into buf.partS (rows from sIdxBase), the work-item list, k_prj_join_pairs against the resident R.
+// out.cursor is zeroed here; out.capacity 0 counts only.
+hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+                                 const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
+                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s)
+{
+    const Work w = carve(planS, buf.work);
+    hipError_t e;
+    if ((e = hipMemsetAsync(&ctr->prjFallback, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    if ((e = partition_relation_rows(planS, w, S, nS, (uint32_t)sIdxBase, buf.tmpA, buf.partS, w.offS, s)) != hipSuccess) return e;
+    if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
+    // the work items of the counting probe: the exact layout's offsets are the same whatever the element width
+    const uint32_t P = 1u << planR.radixBits;
+    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, res.offR, nullptr, 0u,
+                       w.offS, nullptr, 0u, P, ctr, res.itemCnt, res.stats);
+    if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
+    if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_join_pairs, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
+                       reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
+                       res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor, ctr);
+    return hipGetLastError();
+}
+
+}  // namespace hj

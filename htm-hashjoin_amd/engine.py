@@ -159,6 +159,15 @@ class HashJoinContext:
         """Partitions one S slice and joins it against the resident R; totalMatches and sSize add up over the slices."""
         self._check(lib.hj_prj_probe_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize))
 
+    def prj_probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0):
+        """hj_prj_probe_pairs_dev: prj_probe with its result kept, against an R built after reserve("prj" or "auto", ...,
+        keepRowIds=True). For every match one pair d_out_s[k] = s_idx_base + position in dS, d_out_r[k] = position of
+        the R tuple in the relation given to prj_build (two device uint32 arrays of `capacity` entries; pairs beyond it
+        are counted, not written). The complete equi-join on the key word. pairs_info() reports the call."""
+        self._check(lib.hj_prj_probe_pairs_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
+                                               C.c_void_p(d_out_s) if d_out_s else None,
+                                               C.c_void_p(d_out_r) if d_out_r else None, capacity))
+
     def prj_resident_info(self):
         """hj_prj_resident_info (waits for the stream): R's and the last slice's partitioning path, the last probe's join
         work items, its partitions split over several items, its largest S partition, bytes held for R."""
@@ -346,6 +355,58 @@ def join_pairs(relR, relS, algo="htm", probeLength=4, device=0):
             for p in held:
                 ctx.dev_free(p)
     return s_idx, r_idx
+
+
+def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0):
+    """The complete equi-join on the key word (the low 32 bits of a tuple) through the resident radix join, as two gather
+    maps like join_pairs: (s_idx, r_idx), numpy uint32 arrays, row k of the result being (relS[s_idx[k]], relR[r_idx[k]]),
+    in no particular order. The path for a scattered or skewed relS. R is partitioned once with its row ids; relS is
+    probed in slices of slice_tuples (default: all of it at once).
+    Sizing, per slice, as in join_pairs: the outputs start with one entry per S tuple of the slice; if the probe reports
+    more pairs than that, they are enlarged to the reported count and the slice is probed once more."""
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    empty = np.empty(0, dtype=np.uint32)
+    if relR.size == 0 or relS.size == 0:
+        return empty, empty.copy()
+    step = relS.size if not slice_tuples else min(int(slice_tuples), relS.size)
+    if step < 1:
+        raise ValueError(f"radix_join_pairs: slice_tuples must be positive, not {slice_tuples!r}")
+    parts_s, parts_r = [], []
+    with HashJoinContext(device) as ctx:
+        held = []
+
+        def alloc(nbytes):
+            held.append(ctx.dev_alloc(nbytes))
+            return held[-1]
+
+        try:
+            ctx.reserve("prj", relR.size, step, radixBits=radixBits, keepRowIds=True)
+            dR, dS = alloc(relR.nbytes), alloc(8 * step)
+            ctx.copy_h2d(dR, relR)
+            ctx.prj_build(dR, relR.size)
+            capacity = step
+            d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+            for lo in range(0, relS.size, step):
+                part = relS[lo:lo + step]
+                ctx.copy_h2d(dS, part)
+                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo)
+                found, written = ctx.pairs_info()[:2]
+                if found > capacity:
+                    capacity = found
+                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo)
+                    found, written = ctx.pairs_info()[:2]
+                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
+                if written:
+                    ctx.copy_d2h(s_idx, d_s)
+                    ctx.copy_d2h(r_idx, d_r)
+                parts_s.append(s_idx)
+                parts_r.append(r_idx)
+        finally:
+            for p in held:
+                ctx.dev_free(p)
+    return np.concatenate(parts_s), np.concatenate(parts_r)
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

@@ -100,7 +100,12 @@ typedef struct {
 
 /* hj_params.flags. Open addressing: never leave the table in the compact 4-byte format, so that every slot keeps the
  * input index of its tuple for hj_probe_pairs_dev (buildVariant 4 runs as 3; buildVariant 0 neither enqueues nor picks
- * 4). No effect on HJ_ALGO_HTM, whose table always keeps the indices, and on HJ_ALGO_PRJ. */
+ * 4). No effect on HJ_ALGO_HTM, whose table always keeps the indices.
+ * Resident radix join (hj_reserve with HJ_ALGO_PRJ or HJ_ALGO_AUTO): hj_prj_build_dev keeps R resident as 8-byte
+ * {key, row} elements (row = position in dR; the input's own upper word is dropped) instead of bare 4-byte keys, for
+ * hj_prj_probe_pairs_dev. Row ids travel through the exact passes only: prjPath and the paths of hj_prj_resident_info
+ * report 0, and R costs 8 bytes per tuple of resident memory. hj_prj_probe_dev keeps working and counts the same.
+ * No effect on the one-shot hj_prj_join_dev. */
 #define HJ_FLAG_KEEP_ROW_IDS 0x1u
 
 /* Everything the reference prints in its JSON line (NoCCHashBuild.hpp:127-146,
@@ -208,7 +213,7 @@ int hj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
  * HJ_ERR_INVALID: an output pointer NULL with capacity > 0, or sIdxBase + sSize > 2^32 - 1. sSize 0 is a no-op. */
 int hj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
                        uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
-/* Waits for the stream. out[0] = pairs the last hj_probe_pairs_dev found, out[1] = pairs it wrote
+/* Waits for the stream. out[0] = pairs the last hj_probe_pairs_dev / hj_prj_probe_pairs_dev found, out[1] = pairs it wrote
  * (= min(out[0], capacity)), out[2] = its device time in microseconds (rounded), out[3] = 0. */
 int hj_pairs_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
@@ -226,6 +231,17 @@ int hj_prj_build_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize);
  * HJ_ERR_STATE without a resident R (no hj_prj_build_dev yet, or hj_prj_join_dev / hj_build_dev / hj_join_dev / an
  * hj_reserve that reallocated since) or for an sSize above the reserved one. sSize 0 is a no-op. */
 int hj_prj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
+/* hj_prj_probe_dev with its result kept, against an R built on a context reserved with HJ_FLAG_KEEP_ROW_IDS: partitions
+ * dS[0..sSize) with its row ids and writes one pair  dOutS[k] = sIdxBase + (position in dS),  dOutR[k] = position of the
+ * matching tuple in the dR given to hj_prj_build_dev  per match, under the output contract of hj_probe_pairs_dev: the
+ * planes fill from 0 without holes on every call, pairs beyond `capacity` are counted but not written, the order is
+ * unspecified, the multiset is exact. The join is hj_prj_probe_dev's: the complete equi-join on the key word (the low 32
+ * bits of a tuple; upper bits are ignored and key 0 is an ordinary key), duplicate keys on both sides included. Adds to
+ * totalMatches and sSize exactly as hj_prj_probe_dev does; hj_pairs_info reports the call. Asynchronous.
+ * HJ_ERR_STATE: no resident R; a resident R built without the flag; sSize above the reserved one.
+ * HJ_ERR_INVALID: an output pointer NULL with capacity > 0, or sIdxBase + sSize > 2^32 - 1. sSize 0 is a no-op. */
+int hj_prj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
+                           uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
 /* Host-visible facts about the resident build and the last probe (waits for the stream), out[8]:
  * [0] R's path (0 exact, 1 histogram-free, 2 fell back), [1] last probe's S path (same coding),
  * [2] join work items of the last probe, [3] partitions whose S side was split over > 1 item,
