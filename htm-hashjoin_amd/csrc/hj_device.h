@@ -176,6 +176,7 @@ __device__ inline bool gate_closed(const Gate& g)
     const unsigned long long v = *g.word;
     return v != g.want && v != g.alt;
 }
+constexpr Gate kNoGate{nullptr, 0ull};
 constexpr unsigned long long kFormatSlots8 = 0, kFormatKeys4 = 1;
 
 // A tuple that left its LDS window (variants 2 and 3): the slot it had reached and (index << 32 | key)
@@ -334,12 +335,36 @@ void launch_htm_probe(const uint64_t* S, uint64_t n, const uint64_t* table, uint
 void launch_htm_sums(const uint64_t* table, uint32_t numBuckets, const uint64_t* overflow, Counters* ctr, hipStream_t s);
 // exclusive scan of a uint32 array in place (defined in hj_prj.hip); sums: ceil(n / 4096) + 1 words of workspace
 size_t scan_workspace_words(uint64_t n);
-hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s);
+hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s, Gate gate = kNoGate);
 
 // ---- materialising probe (defined in hj_pairs.hip) --------------------------
 // where hj_probe_pairs_dev writes: the two gather-map planes, their length, and the 64-bit cursor the workgroups claim
 // their runs from (zeroed before the launch; its final value = pairs found, written or not)
 struct PairsOut { uint32_t* s; uint32_t* r; uint64_t capacity; unsigned long long* cursor; };
+typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+// A staged plane leaves LDS, by a workgroup of NT threads: lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity. The
+// elements before the first 16-byte boundary of the destination and after the last one by one lane each, the body as
+// 16-byte stores. Written once, read by nobody here.
+template <int NT>
+__device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, uint32_t* __restrict__ out, uint64_t base, uint64_t capacity)
+{
+    if (base >= capacity) return;
+    const uint64_t room = capacity - base;
+    const uint32_t lim = room < cnt ? (uint32_t)room : cnt;           // elements of the run that exist in the output
+    uint32_t* const dst = out + base;
+    uint32_t lead = (uint32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
+    if (lead > lim) lead = lim;
+    if (threadIdx.x < lead) __builtin_nontemporal_store(lds[threadIdx.x], dst + threadIdx.x);
+    const uint32_t nv = (lim - lead) >> 2;
+    for (uint32_t v = threadIdx.x; v < nv; v += NT) {
+        const uint32_t i = lead + 4u * v;
+        u4 x;
+        x.x = lds[i]; x.y = lds[i + 1]; x.z = lds[i + 2]; x.w = lds[i + 3];
+        __builtin_nontemporal_store(x, reinterpret_cast<u4*>(dst + i));
+    }
+    const uint32_t tail = lead + 4u * nv;
+    if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
+}
 uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
 // the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot
 void launch_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,

@@ -28,8 +28,6 @@ constexpr uint32_t kWaves = kBlock / kWave;
 // 512 x kMaxProbeLen at any other length, 1024 buckets x 3 tuples for htm
 constexpr uint32_t kMaxProbeLen = 8;
 
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
 struct Stage {
     uint32_t* s;                  // LDS: S rows of the staged pairs
     uint32_t* r;                  // LDS: R rows
@@ -40,36 +38,14 @@ struct Stage {
     unsigned long long found;     // pairs of this workgroup so far (the same value in every thread)
 };
 
-// lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity: the elements before the first 16-byte boundary of the
-// destination and after the last one by one lane each, the body as 16-byte stores. Written once, read by nobody here.
-__device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, uint32_t* __restrict__ out, uint64_t base, uint64_t capacity)
-{
-    if (base >= capacity) return;
-    const uint64_t room = capacity - base;
-    const uint32_t lim = room < cnt ? (uint32_t)room : cnt;           // elements of the run that exist in the output
-    uint32_t* const dst = out + base;
-    uint32_t lead = (uint32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
-    if (lead > lim) lead = lim;
-    if (threadIdx.x < lead) __builtin_nontemporal_store(lds[threadIdx.x], dst + threadIdx.x);
-    const uint32_t nv = (lim - lead) >> 2;
-    for (uint32_t v = threadIdx.x; v < nv; v += kBlock) {
-        const uint32_t i = lead + 4u * v;
-        u4 x;
-        x.x = lds[i]; x.y = lds[i + 1]; x.z = lds[i + 2]; x.w = lds[i + 3];
-        __builtin_nontemporal_store(x, reinterpret_cast<u4*>(dst + i));
-    }
-    const uint32_t tail = lead + 4u * nv;
-    if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
-}
-
 // Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
 __device__ __forceinline__ void stage_flush(Stage& st, const PairsOut& out)
 {
     if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
     __syncthreads();                                  // the base is there, and so is every pair of the rounds before
     const uint64_t base = *st.base;
-    flush_plane(st.s, st.fill, out.s, base, out.capacity);
-    flush_plane(st.r, st.fill, out.r, base, out.capacity);
+    flush_plane<kBlock>(st.s, st.fill, out.s, base, out.capacity);
+    flush_plane<kBlock>(st.r, st.fill, out.r, base, out.capacity);
     __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
     st.fill = 0;
 }

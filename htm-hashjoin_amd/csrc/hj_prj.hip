@@ -7,7 +7,8 @@
 //   k_radix_scatter  the scatter loops (:622-626, :433-437), here staged through LDS so
 //                    every partition's tuples leave the CU as contiguous runs
 //   k_prj_join       bucket_chaining_join (:231-283) with the probe loop the fork
-//                    commented out (:259-276) restored; the table lives in LDS
+//                    commented out (:259-276) restored; the table lives in LDS (join_partition, the core it
+//                    shares with k_prj_probe_items)
 //   k_radix_scatter_frag  the same two passes WITHOUT the histogram loops (the default for large
 //                    relations): private fragments per chunk and bin, capacity checked, the exact
 //                    kernels above enqueued behind as a gated fallback (see "histogram-free partitioning")
@@ -39,7 +40,6 @@ constexpr uint32_t kJoinSlots = 32768;            // LDS table slots (uint32) = 
 constexpr uint32_t kJoinBlockTuples = 24576;      // R tuples per LDS build (load <= 0.75)
 constexpr int kJoinThreads = 1024;
 constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
-constexpr Gate kNoGate{nullptr, 0ull};
 
 struct PassParams {
     const uint32_t* segOff;     // [nSeg + 1] tuple offsets of the input segments
@@ -806,30 +806,226 @@ __device__ __forceinline__ uint32_t join_hash(uint32_t k)
 }
 static_assert(kJoinSlots == (1u << 15), "join_hash assumes 2^15 slots");
 
-constexpr int kJoinPre = 16;   // tuples per thread and relation prefetched in registers (16 x 1024 = 16384)
+// ---------------------------------------------------------------------------
+// the partition-join core: one R partition into the LDS table, one run of S keys probed against it. Its two schedulers
+// are k_prj_join (whole partitions by a fixed stride) and k_prj_probe_items (work items by ticket); they decide what is
+// joined next and when its keys are fetched, the core how a partition is joined.
+// ---------------------------------------------------------------------------
+constexpr int kJoinPre = 16;   // keys per thread and relation prefetched in registers (16 x 1024 = 16384)
+constexpr int kTailPre = 8;    // loads in flight per thread in the loops past the register prefetch
+
+// A relation's final partitions as the join sees them. Exact passes (!frag): partition pid = part[off[pid] .. off[pid+1]),
+// one dense run (log2C = 0). Histogram-free passes (frag): 2^log2C fragments of `cap` slots from pid << log2C, fragment f
+// holding cnt[(pid << log2C) + f] keys at its front. total: slots of `part` that may be read (loads are clamped to
+// total - 1). The kernels take the three arrays and the geometry as separate parameters (see k_prj_join), and a view on
+// the device holds those parameters themselves, never a choice between one of them and null: a load through a pointer
+// the compiler cannot trace to ONE read-only parameter is no scalar load any more.
+struct PartGeom { uint32_t log2C, cap, total; };
+struct PartView { const uint32_t* part; const uint32_t* off; const uint32_t* cnt; PartGeom g; bool frag; };
+
+inline PartView exact_view(const uint32_t* part, const uint32_t* off, uint64_t n)
+{
+    return PartView{part, off, nullptr, PartGeom{0u, 0u, (uint32_t)n}, false};
+}
+inline PartView frag_view(const uint32_t* part, const uint32_t* cnt2, const PrjFrag& g, uint32_t P)
+{
+    return PartView{part, nullptr, cnt2, PartGeom{g.log2C2, g.cap2, P * g.C2 * g.cap2}, true};
+}
+
+// slot j of the 16-deep register prefetch covers element ((j & (spf - 1)) * 1024 + thread) of fragment j >> spfShift,
+// spf = 2^spfShift slots per fragment (one dense run: 16 slots of the one fragment; 4 fragments: 4 slots each). A
+// fragment longer than spf * 1024 is finished by a loop over the rest.
+__device__ __forceinline__ uint32_t spf_shift(const PartView& v) { return 4u - v.g.log2C; }
+
+// The prefetch of the partition whose first slot is `base`. Clamped: every lane always loads a valid address (one
+// unconditional load path -- see hj_build_own.hip for why); which slots hold keys is decided at use (Shape).
+__device__ __forceinline__ void prefetch_part(const PartView& v, uint32_t base, uint32_t (&buf)[kJoinPre])
+{
+    const uint32_t spfShift = spf_shift(v);
+#pragma unroll
+    for (int j = 0; j < kJoinPre; ++j) {
+        const uint32_t o = base + ((uint32_t)j >> spfShift) * v.g.cap + ((j & ((1u << spfShift) - 1u)) * kJoinThreads + threadIdx.x);
+        buf[j] = v.part[o < v.g.total ? o : v.g.total - 1];
+    }
+}
+
+// f(element) for element i of [from, n) of a run starting at slot `base`, kTailPre loads in flight per thread (a one-load
+// loop waits a whole HBM round trip per key: the rest of a 2^16-tuple item is 48 keys per thread)
+template <typename T, typename F>
+__device__ __forceinline__ void for_run(const T* __restrict__ part, uint32_t base, uint32_t from, uint32_t n, F&& f)
+{
+    for (uint32_t i0 = from + threadIdx.x; i0 < n; i0 += kTailPre * kJoinThreads) {
+        T k[kTailPre];
+#pragma unroll
+        for (int u = 0; u < kTailPre; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
+            k[u] = part[base + (i < n ? i : n - 1)];                  // clamped: i0 < n, so n >= 1
+        }
+#pragma unroll
+        for (int u = 0; u < kTailPre; ++u)
+            if (i0 + (uint32_t)u * kJoinThreads < n) f(k[u]);
+    }
+}
+
+// What a partition holds: n keys; mask bit j = prefetch slot j holds a key; tail = some fragment is longer than the
+// prefetch covers.
+struct Shape { uint32_t n, mask; bool tail; };
+
+// One relation's side of a partition (or work item): the fragments from slot `base`, fragment f holding cnt(f) keys.
+// Made BEFORE any LDS work of the partition: the counts come through scalar loads, and waiting for one (lgkmcnt) also
+// waits for every LDS atomic in flight -- a count looked up between two atomics serialises them (measured: join
+// 1.6 -> 2.5 ms).
+template <typename Cnt> struct PartKeys { const PartView& v; uint32_t base; Cnt cnt; Shape sh; };
+
+template <typename Cnt>
+__device__ __forceinline__ PartKeys<Cnt> keys_of(const PartView& v, uint32_t base, Cnt cnt)
+{
+    Shape sh{0u, 0u, false};
+    const uint32_t spfShift = spf_shift(v), spf = 1u << spfShift;  // prefetch slots per fragment
+    for (uint32_t fr = 0; fr < (1u << v.g.log2C); ++fr) {          // one scalar load per fragment
+        const uint32_t n = cnt(fr);
+        sh.n += n;
+        sh.tail |= n > (kJoinThreads << spfShift);
+        // this thread's slots of the fragment hold elements thread, thread + 1024, ...: the first `mine` are keys
+        uint32_t mine = n > threadIdx.x ? (n - threadIdx.x + kJoinThreads - 1) / kJoinThreads : 0u;
+        mine = mine < spf ? mine : spf;
+        sh.mask |= ((1u << mine) - 1u) << (fr << spfShift);
+    }
+    return PartKeys<Cnt>{v, base, cnt, sh};
+}
+
+// f(key) for the keys the prefetch holds / for the keys from element `from` of every fragment on, read from memory
+template <typename F>
+__device__ __forceinline__ void for_slots(const Shape& sh, const uint32_t (&buf)[kJoinPre], F&& f)
+{
+#pragma unroll
+    for (int j = 0; j < kJoinPre; ++j)
+        if ((sh.mask >> j) & 1u) f(buf[j]);
+}
+template <typename Cnt, typename F>
+__device__ __forceinline__ void for_rest(const PartKeys<Cnt>& p, uint32_t from, F&& f)
+{
+    for (uint32_t fr = 0; fr < (1u << p.v.g.log2C); ++fr) for_run(p.v.part, p.base + fr * p.v.g.cap, from, p.cnt(fr), f);
+}
+// f(key) for every key of the partition: the prefetched slots out of `buf`, the rest of long fragments from memory
+template <typename Cnt, typename F>
+__device__ __forceinline__ void for_each(const PartKeys<Cnt>& p, const uint32_t (&buf)[kJoinPre], F&& f)
+{
+    for_slots(p.sh, buf, f);
+    if (p.sh.tail) for_rest(p, kJoinThreads << spf_shift(p.v), f);
+}
+
+// The LDS table (kJoinSlots words) in its two forms; a key is told apart inside its partition by k = key >> radixBits.
+__device__ __forceinline__ void fill_table(uint32_t* tab, uint32_t v)
+{
+    for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = v;
+}
+// Direct-addressed counters (radixBits >= 16): k has at most 16 bits, so the 128 KiB hold one 16-bit counter for EVERY
+// possible k -- tab[k >> 1] holds the counts of k = 2i (low half) and 2i + 1 (high half). Build = one increment, probe =
+// one read, no hashing and no probe walks (the hashed table spends 26 VALU instructions per tuple on them, PMC).
+// Counters cannot overflow while |R partition| <= 65535; larger ones take the hashed table.
+struct DirectCounters {
+    uint32_t* tab; uint32_t radixBits;
+    __device__ __forceinline__ void clear() const { fill_table(tab, 0u); }
+    __device__ __forceinline__ void insert(uint32_t key) const
+    {
+        const uint32_t k = key >> radixBits;
+        atomicAdd(&tab[k >> 1], 1u << (16u * (k & 1u)));
+    }
+    __device__ __forceinline__ uint32_t probe(uint32_t key) const      // :268-271, all equal keys at once
+    {
+        const uint32_t k = key >> radixBits;
+        return (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+    }
+};
+// Open addressing over join_hash, linear probing, at most kJoinBlockTuples keys (load <= 0.75): equal keys are separate
+// entries, a probe walks to the first empty slot.
+struct HashedTable {
+    uint32_t* tab; uint32_t radixBits;
+    __device__ __forceinline__ void clear() const { fill_table(tab, kEmpty32); }
+    __device__ __forceinline__ void insert(uint32_t key) const
+    {
+        const uint32_t k = key >> radixBits;
+        uint32_t h = join_hash(k);
+        while (atomicCAS(&tab[h], kEmpty32, k) != kEmpty32) h = (h + 1) & (kJoinSlots - 1);
+    }
+    __device__ __forceinline__ uint32_t probe(uint32_t key) const      // :268-271
+    {
+        const uint32_t k = key >> radixBits;
+        uint32_t h = join_hash(k), m = 0;
+        for (;;) {
+            const uint32_t v = tab[h];
+            if (v == kEmpty32) break;
+            m += (v == k);
+            h = (h + 1) & (kJoinSlots - 1);
+        }
+        return m;
+    }
+};
+
+// Where join_partition calls its scheduler's hook:
+//   Built      R's keys are in the table, the barrier behind the build has not been passed (a ticket is published here)
+//   Between    behind that barrier: R's prefetch registers are free, S is about to be probed -- the scheduler waits for
+//              S's prefetch (vmcnt) and issues the next R prefetch, in flight while S is probed
+//   Oversized  instead of both, before the first of several builds
+enum class At { Built, Between, Oversized };
+
+// Joins R's partition with S's keys in one LDS table: clear, build from R, hook, probe S; `matches` += the matches.
+// insert(table, key) is the scheduler's, so that it can look at R's keys on their way (k_prj_join's checksum).
+template <typename Table, typename CntR, typename CntS, typename Insert, typename Hook>
+__device__ __forceinline__ void join_one_table(const Table& t, const PartKeys<CntR>& R, const uint32_t (&bufR)[kJoinPre],
+                                               const PartKeys<CntS>& S, const uint32_t (&bufS)[kJoinPre], Insert&& insert,
+                                               Hook&& hook, unsigned long long& matches)
+{
+    t.clear();
+    __syncthreads();
+    for_each(R, bufR, [&](uint32_t key) { insert(t, key); });
+    hook(At::Built);
+    __syncthreads();
+    hook(At::Between);
+    uint32_t m32 = 0;                                  // < 2^16 (2^15 hashed) per probe, 16 probes
+    for_slots(S.sh, bufS, [&](uint32_t key) { m32 += t.probe(key); });
+    matches += m32;
+    if (S.sh.tail) for_rest(S, kJoinThreads << spf_shift(S.v), [&](uint32_t key) { matches += t.probe(key); });
+    __syncthreads();
+}
+
+// The mode is picked from R's partition size: counters (DIRECT, <= 65535 keys), one hashed table (<= kJoinBlockTuples),
+// or, for an oversized R partition (skew), several builds of the hashed table with S probed against each. The last one
+// meets the exact layout only -- the histogram-free passes are not planned for partitions that could outgrow one
+// table (frag_geometry) --, so R is one dense run there.
+template <bool DIRECT, typename CntR, typename CntS, typename Insert, typename Hook>
+__device__ __forceinline__ void join_partition(uint32_t* tab, uint32_t radixBits, const PartKeys<CntR>& R,
+                                               const uint32_t (&bufR)[kJoinPre], const PartKeys<CntS>& S,
+                                               const uint32_t (&bufS)[kJoinPre], Insert&& insert, Hook&& hook,
+                                               unsigned long long& matches)
+{
+    const uint32_t nR = R.sh.n;
+    if (DIRECT && nR <= 65535u) {
+        join_one_table(DirectCounters{tab, radixBits}, R, bufR, S, bufS, insert, hook, matches);
+    } else if (nR <= kJoinBlockTuples) {
+        join_one_table(HashedTable{tab, radixBits}, R, bufR, S, bufS, insert, hook, matches);
+    } else {
+        hook(At::Oversized);
+        const HashedTable t{tab, radixBits};
+        for (uint32_t blk = 0; blk < nR; blk += kJoinBlockTuples) {
+            const uint32_t bn = nR - blk > kJoinBlockTuples ? kJoinBlockTuples : nR - blk;
+            t.clear();
+            __syncthreads();
+            for_run(R.v.part, R.base + blk, 0u, bn, [&](uint32_t key) { insert(t, key); });
+            __syncthreads();
+            for_rest(S, 0u, [&](uint32_t key) { matches += t.probe(key); });
+            __syncthreads();
+        }
+    }
+}
 
 // One persistent workgroup per CU walks the partitions pid = blockIdx.x, += gridDim.x. The LDS table takes
 // 128 KiB, so only one workgroup fits a CU and nothing else could hide the HBM latency of a partition's
 // 2 x 128 KiB: while partition p is built and probed out of registers, the first 16384 R and S tuples of
-// the next partition are already in flight into the other register set (explicit vmcnt wait at the top,
-// one unconditional clamped load path -- see hj_build_own.hip for why). Measured at 2^30: 13.4 ms -> see
-// profiles/.
-// DIRECT (radixBits >= 16): the part of a key that tells the keys of a partition apart, k = key >> radixBits, has at
-// most 16 bits, so the 128 KiB of LDS hold one 16-bit counter for EVERY possible k: build = one counter increment,
-// probe = one read, no hashing and no probe walks (the hash-table version spends 26 VALU instructions per tuple on
-// them, PMC). Counters cannot overflow while |R partition| <= 65535; larger ones take the hash-table path.
-// A relation's final partitions as the join sees them. Exact passes: partition pid = part[off[pid] .. off[pid+1]), one
-// dense run (cnt == nullptr, log2C = 0). Histogram-free passes: 2^log2C fragments of `cap` slots from pid << log2C,
-// fragment f holding cnt[(pid << log2C) + f] keys at its front.
-struct PartView {
-    const uint32_t* part;
-    const uint32_t* off;
-    const uint32_t* cnt;
-    uint32_t log2C, cap;
-    uint32_t total;          // slots of `part` that may be read (loads are clamped to total - 1)
-};
-struct PartGeom { uint32_t log2C, cap, total; };
-
+// the next partition are already in flight into the other register set (explicit vmcnt wait at the top).
+// Measured at 2^30: 13.4 ms -> see profiles/.
+// S == nullptr: R's checksum alone (hj_prj_build_dev).
 // The six arrays are separate __restrict__ parameters, not members of the views: only then does the compiler read the
 // offsets and counts (wave-uniform addresses) with scalar loads. As plain struct members they became vector loads
 // whose s_waitcnt vmcnt(0) also waited for the register prefetch of the next partition (join 1.6 -> 2.5 ms).
@@ -841,184 +1037,49 @@ k_prj_join(const uint32_t* __restrict__ partR, const uint32_t* __restrict__ offR
 {
     extern __shared__ uint32_t tab[];  // kJoinSlots
     if (gate_closed(gate)) return;
-    const PartView R{partR, offR, cntR, gR.log2C, gR.cap, gR.total}, S{partS, offS, cntS, gS.log2C, gS.cap, gS.total};
+    const PartView R{partR, offR, cntR, gR, cntR != nullptr}, S{partS, offS, cntS, gS, cntS != nullptr};
     unsigned long long matches = 0, checksum = 0;
     uint32_t overflowParts = 0;
     const bool haveS = S.part != nullptr;
-
-    // slot j of the 16-deep register prefetch covers element ((j & (spf - 1)) * 1024 + thread) of fragment j >> spfShift
-    // (one dense run: 16 slots of the one fragment; 4 fragments: 4 slots each). A fragment longer than spf * 1024
-    // is finished by a loop over the rest.
-    const uint32_t spfShiftR = 4u - R.log2C, spfShiftS = 4u - S.log2C;
-    auto base_of = [](const PartView& v, uint32_t pid) { return v.cnt ? (pid << v.log2C) * v.cap : v.off[pid]; };
+    auto base_of = [](const PartView& v, uint32_t pid) { return v.frag ? (pid << v.g.log2C) * v.g.cap : v.off[pid]; };
     auto cnt_of = [](const PartView& v, uint32_t pid, uint32_t f) {
-        return v.cnt ? v.cnt[(pid << v.log2C) + f] : v.off[pid + 1] - v.off[pid];
+        return v.frag ? v.cnt[(pid << v.g.log2C) + f] : v.off[pid + 1] - v.off[pid];
     };
-    auto slot_elem = [](uint32_t j, uint32_t spfShift) { return (j & ((1u << spfShift) - 1u)) * kJoinThreads + threadIdx.x; };
 
     // Register pipeline: S(p) is loaded while R(p) is built, R(p+1) while S(p) is probed; each buffer is
     // refilled only after its last use, so no copy of in-flight registers is ever needed.
     uint32_t bufR[kJoinPre], bufS[kJoinPre];   // partitions hold bare keys (see element formats above)
-    auto load_R = [&](uint32_t pid) {   // clamped: every lane always loads a valid address; validity decided at use
-        const uint32_t rb0 = base_of(R, pid < nParts ? pid : nParts - 1);
-#pragma unroll
-        for (int j = 0; j < kJoinPre; ++j) {
-            const uint32_t o = rb0 + ((uint32_t)j >> spfShiftR) * R.cap + slot_elem(j, spfShiftR);
-            bufR[j] = R.part[o < R.total ? o : R.total - 1];
-        }
-    };
-    auto load_S = [&](uint32_t pid) {
-        const uint32_t sb0 = base_of(S, pid);
-#pragma unroll
-        for (int j = 0; j < kJoinPre; ++j) {
-            const uint32_t o = sb0 + ((uint32_t)j >> spfShiftS) * S.cap + slot_elem(j, spfShiftS);
-            bufS[j] = S.part[o < S.total ? o : S.total - 1];
-        }
-    };
-    // What a partition holds, read BEFORE any LDS work of the partition: the counts come through scalar loads, and
-    // waiting for one (lgkmcnt) also waits for every LDS atomic in flight -- a count looked up between two atomics
-    // serialises them (measured: join 1.6 -> 2.5 ms). mask bit j = prefetch slot j holds a key; tail = some fragment
-    // is longer than the prefetch covers.
-    struct Shape { uint32_t n, mask; bool tail; };
-    auto shape_of = [&](const PartView& v, uint32_t pid, uint32_t spfShift) {
-        Shape sh{0u, 0u, false};
-        const uint32_t spf = 1u << spfShift;                       // prefetch slots per fragment
-        for (uint32_t fr = 0; fr < (1u << v.log2C); ++fr) {        // one scalar load per fragment
-            const uint32_t n = cnt_of(v, pid, fr);
-            sh.n += n;
-            sh.tail |= n > (kJoinThreads << spfShift);
-            // this thread's slots of the fragment hold elements thread, thread + 1024, ...: the first `mine` are keys
-            uint32_t mine = n > threadIdx.x ? (n - threadIdx.x + kJoinThreads - 1) / kJoinThreads : 0u;
-            mine = mine < spf ? mine : spf;
-            sh.mask |= ((1u << mine) - 1u) << (fr << spfShift);
-        }
-        return sh;
-    };
-    // f(key) for every key of partition pid: the prefetched slots out of `buf`, the rest of long fragments from memory
-    auto for_each = [&](const PartView& v, uint32_t pid, uint32_t spfShift, const Shape& sh, const uint32_t (&buf)[kJoinPre], auto&& f) {
-#pragma unroll
-        for (int j = 0; j < kJoinPre; ++j)
-            if ((sh.mask >> j) & 1u) f(buf[j]);
-        if (sh.tail) {
-            const uint32_t b = base_of(v, pid);
-            for (uint32_t fr = 0; fr < (1u << v.log2C); ++fr) {
-                const uint32_t n = cnt_of(v, pid, fr);
-                for (uint32_t i = (kJoinThreads << spfShift) + threadIdx.x; i < n; i += kJoinThreads) f(v.part[b + fr * v.cap + i]);
-            }
-        }
-    };
+    auto load_R = [&](uint32_t pid) { prefetch_part(R, base_of(R, pid < nParts ? pid : nParts - 1), bufR); };
     load_R(blockIdx.x);
 
     for (uint32_t pid = blockIdx.x; pid < nParts; pid += gridDim.x) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // R(pid) has landed
         __builtin_amdgcn_sched_barrier(0);
-        if (haveS) load_S(pid);                                // in flight while R is built
+        if (haveS) prefetch_part(S, base_of(S, pid), bufS);    // in flight while R is built
         __builtin_amdgcn_sched_barrier(0);
 
-        const Shape shR = shape_of(R, pid, spfShiftR);
-        const Shape shS = haveS ? shape_of(S, pid, spfShiftS) : Shape{0u, 0u, false};
-        const uint32_t nR = shR.n;
+        const auto keysR = keys_of(R, base_of(R, pid), [&](uint32_t f) { return cnt_of(R, pid, f); });
+        const auto keysS = keys_of(S, haveS ? base_of(S, pid) : 0u, [&](uint32_t f) { return haveS ? cnt_of(S, pid, f) : 0u; });
+        const uint32_t nR = keysR.sh.n;
         if (nR == 0) {          // serial_radix_partition :531 queues only non-empty R parts (wave-uniform)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             load_R(pid + gridDim.x);
             continue;
         }
         const uint32_t idxMask = next_pow2_u32(nR) - 1;  // bucket idx mask, :242-245
-
-        if (DIRECT && nR <= 65535u) {
-            // ---- direct-addressed counters: tab[k >> 1] holds the counts of k = 2i (low half) and 2i + 1 (high half) ----
-            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = 0u;
-            __syncthreads();
-            for_each(R, pid, spfShiftR, shR, bufR, [&](uint32_t key) {
-                const uint32_t k = key >> radixBits;
-                checksum += k & idxMask;                          // :249,256
-                atomicAdd(&tab[k >> 1], 1u << (16u * (k & 1u)));
-            });
-            __syncthreads();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(pid) has landed; bufR is free
-            __builtin_amdgcn_sched_barrier(0);
-            load_R(pid + gridDim.x);                           // in flight while S is probed
-            __builtin_amdgcn_sched_barrier(0);
-            if (haveS) {
-                uint32_t m32 = 0;                              // <= 65535 per probe, a few dozen probes per thread
-#pragma unroll
-                for (int j = 0; j < kJoinPre; ++j)
-                    if ((shS.mask >> j) & 1u) {
-                        const uint32_t k = bufS[j] >> radixBits;
-                        m32 += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;      // :268-271, all equal keys at once
-                    }
-                matches += m32;
-                if (shS.tail) {
-                    const uint32_t sb = base_of(S, pid);
-                    for (uint32_t fr = 0; fr < (1u << S.log2C); ++fr) {
-                        const uint32_t n = cnt_of(S, pid, fr);
-                        for (uint32_t i = (kJoinThreads << spfShiftS) + threadIdx.x; i < n; i += kJoinThreads) {
-                            const uint32_t k = S.part[sb + fr * S.cap + i] >> radixBits;
-                            matches += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        } else if (nR <= kJoinBlockTuples) {
-            // ---- the common case: the whole R partition fits one LDS table ----
-            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
-            __syncthreads();
-            for_each(R, pid, spfShiftR, shR, bufR, [&](uint32_t key) {
-                const uint32_t k = key >> radixBits;           // distinguishes keys inside a partition
-                checksum += k & idxMask;                          // :249,256
-                uint32_t h = join_hash(k);
-                while (atomicCAS(&tab[h], kEmpty32, k) != kEmpty32) h = (h + 1) & (kJoinSlots - 1);
-            });
-            __syncthreads();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(pid) has landed; bufR is free
-            __builtin_amdgcn_sched_barrier(0);
-            load_R(pid + gridDim.x);                           // in flight while S is probed
-            __builtin_amdgcn_sched_barrier(0);
-            if (haveS)
-                for_each(S, pid, spfShiftS, shS, bufS, [&](uint32_t key) {
-                    const uint32_t k = key >> radixBits;
-                    uint32_t h = join_hash(k);
-                    for (;;) {
-                        const uint32_t v = tab[h];
-                        if (v == kEmpty32) break;
-                        matches += (v == k);                          // :268-271
-                        h = (h + 1) & (kJoinSlots - 1);
-                    }
-                });
-            __syncthreads();
-        } else {
-            // ---- oversized R partition (skew): several LDS builds, S probed against each. Exact layout only: the
-            // histogram-free passes are not planned for partitions that could outgrow one table (prj_plan)
-            overflowParts += 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            load_R(pid + gridDim.x);
-            const uint32_t rb = R.off[pid], re = R.off[pid + 1];
-            const uint32_t sb = haveS ? S.off[pid] : 0, se = haveS ? S.off[pid + 1] : 0;
-            for (uint32_t blk = rb; blk < re; blk += kJoinBlockTuples) {
-                const uint32_t bend = (re - blk > kJoinBlockTuples) ? blk + kJoinBlockTuples : re;
-                for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
-                __syncthreads();
-                for (uint32_t i = blk + threadIdx.x; i < bend; i += kJoinThreads) {
-                    const uint32_t k = R.part[i] >> radixBits;
-                    checksum += k & idxMask;
-                    uint32_t h = join_hash(k);
-                    while (atomicCAS(&tab[h], kEmpty32, k) != kEmpty32) h = (h + 1) & (kJoinSlots - 1);
-                }
-                __syncthreads();
-                for (uint32_t i = sb + threadIdx.x; i < se; i += kJoinThreads) {
-                    const uint32_t k = S.part[i] >> radixBits;
-                    uint32_t h = join_hash(k);
-                    for (;;) {
-                        const uint32_t v = tab[h];
-                        if (v == kEmpty32) break;
-                        matches += (v == k);
-                        h = (h + 1) & (kJoinSlots - 1);
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        join_partition<DIRECT>(tab, radixBits, keysR, bufR, keysS, bufS,
+            [&](const auto& t, uint32_t key) {
+                checksum += (key >> radixBits) & idxMask;      // :249,256
+                t.insert(key);
+            },
+            [&](At at) {
+                if (at == At::Built) return;
+                if (at == At::Oversized) overflowParts += 1;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(pid) has landed; bufR is free
+                __builtin_amdgcn_sched_barrier(0);
+                load_R(pid + gridDim.x);                           // in flight while S is probed
+                __builtin_amdgcn_sched_barrier(0);
+            }, matches);
     }
     // one atomic per wavefront
     for (int off = 32; off > 0; off >>= 1) {
@@ -1040,7 +1101,7 @@ k_prj_join(const uint32_t* __restrict__ partR, const uint32_t* __restrict__ offR
 //   S tuples. The list is built on the device from S's partition sizes (k_prj_items_count, one scan, k_prj_items_fill),
 //   the partitions that are split over several items first, and a persistent grid takes items from a ticket counter:
 //   the big partitions are spread over many CUs at the start, the small ones fill in behind them. Every item rebuilds
-//   its R partition's LDS image (the three modes of k_prj_join) and probes its S range.
+//   its R partition's LDS image and probes its S range (join_partition, as k_prj_join does for whole partitions).
 //   kPrjItemS = 2^16: 64 keys per thread and item (256 KiB of S), against an R partition of ~4096 keys at 2^28 / 16 bits
 //   that every item rebuilds (~6 % extra LDS work for the items of a split partition); a 4.5 M hot partition becomes ~70
 //   items. A partition of the histogram-free S layout holds at most 65535 keys (frag_geometry), so it is always ONE item
@@ -1107,26 +1168,6 @@ k_prj_items_fill(const uint32_t* __restrict__ scanned, uint32_t nParts, uint2* _
     for (uint32_t k = 0; k < n; ++k) items[b + k] = make_uint2(pid, k);
 }
 
-constexpr int kTailPre = 8;   // loads in flight per thread in the loops past the register prefetch
-
-// f(key) for element i of [from, n) of a run starting at slot `base`, kTailPre loads in flight per thread (a one-load loop
-// waits a whole HBM round trip per key: the rest of a 2^16-tuple item is 48 keys per thread)
-template <typename F>
-__device__ __forceinline__ void for_run(const uint32_t* __restrict__ part, uint32_t base, uint32_t from, uint32_t n, F&& f)
-{
-    for (uint32_t i0 = from + threadIdx.x; i0 < n; i0 += kTailPre * kJoinThreads) {
-        uint32_t k[kTailPre];
-#pragma unroll
-        for (int u = 0; u < kTailPre; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
-            k[u] = part[base + (i < n ? i : n - 1)];                  // clamped: i0 < n, so n >= 1
-        }
-#pragma unroll
-        for (int u = 0; u < kTailPre; ++u)
-            if (i0 + (uint32_t)u * kJoinThreads < n) f(k[u]);
-    }
-}
-
 // gR / gS: the histogram-free geometry (cntR / cntS == nullptr: that relation took the exact passes only); which layout a
 // relation ended in is read from Counters::prjFallbackR / prjFallback, each relation on its own. nR / nS: tuples (the
 // exact layout's clamp bound). items[0 .. *nItemsAt), taken through *ticket (zeroed by the host before the launch).
@@ -1141,68 +1182,19 @@ k_prj_probe_items(const uint32_t* __restrict__ partR, const uint32_t* __restrict
     __shared__ uint32_t sNext;
     const bool rFrag = cntR != nullptr && ctr->prjFallbackR == 0;
     const bool sFrag = cntS != nullptr && ctr->prjFallback == 0;
-    const PartView R = rFrag ? PartView{partR, nullptr, cntR, gR.log2C, gR.cap, gR.total} : PartView{partR, offR, nullptr, 0u, 0u, nR};
-    const PartView S = sFrag ? PartView{partS, nullptr, cntS, gS.log2C, gS.cap, gS.total} : PartView{partS, offS, nullptr, 0u, 0u, nS};
+    const PartView R{partR, offR, cntR, rFrag ? gR : PartGeom{0u, 0u, nR}, rFrag};
+    const PartView S{partS, offS, cntS, sFrag ? gS : PartGeom{0u, 0u, nS}, sFrag};
     const uint32_t nItems = *nItemsAt;
     unsigned long long matches = 0;
 
-    // prefetch slots as in k_prj_join: slot j = element ((j & (spf - 1)) * 1024 + thread) of fragment j >> spfShift
-    const uint32_t spfShiftR = 4u - R.log2C, spfShiftS = 4u - S.log2C;
-    // What an item reads. R: the whole partition (fragments of R.cap slots from `base`, or one run). S: the whole partition
+    // What an item reads. R: the whole partition (fragments of R.g.cap slots from `base`, or one run). S: the whole partition
     // in the histogram-free layout, else the run of at most kPrjItemS tuples of chunk it.y (n = its length).
     struct Run { uint32_t base, n; };
-    auto r_run = [&](uint32_t pid) { return R.cnt ? Run{(pid << R.log2C) * R.cap, 0u} : Run{R.off[pid], R.off[pid + 1] - R.off[pid]}; };
+    auto r_run = [&](uint32_t pid) { return R.frag ? Run{(pid << R.g.log2C) * R.g.cap, 0u} : Run{R.off[pid], R.off[pid + 1] - R.off[pid]}; };
     auto s_run = [&](uint2 it) {
-        if (S.cnt) return Run{(it.x << S.log2C) * S.cap, 0u};
+        if (S.frag) return Run{(it.x << S.g.log2C) * S.g.cap, 0u};
         const uint32_t b = S.off[it.x], lo = it.y * kPrjItemS, len = S.off[it.x + 1] - b - lo;
         return Run{b + lo, len < kPrjItemS ? len : kPrjItemS};
-    };
-    auto r_cnt = [&](uint32_t pid, const Run& r, uint32_t f) { return R.cnt ? R.cnt[(pid << R.log2C) + f] : r.n; };
-    auto s_cnt = [&](uint2 it, const Run& r, uint32_t f) { return S.cnt ? S.cnt[(it.x << S.log2C) + f] : r.n; };
-    auto load = [](const PartView& v, const Run& r, uint32_t spfShift, uint32_t (&buf)[kJoinPre]) {
-#pragma unroll
-        for (int j = 0; j < kJoinPre; ++j) {
-            const uint32_t o = r.base + ((uint32_t)j >> spfShift) * v.cap + ((j & ((1u << spfShift) - 1u)) * kJoinThreads + threadIdx.x);
-            buf[j] = v.part[o < v.total ? o : v.total - 1];
-        }
-    };
-    // read before any LDS work of the item (see k_prj_join: a scalar count load between LDS atomics serialises them)
-    struct Shape { uint32_t n, mask; bool tail; };
-    auto shape_of = [](uint32_t log2C, uint32_t spfShift, auto&& cnt) {
-        Shape sh{0u, 0u, false};
-        const uint32_t spf = 1u << spfShift;
-        for (uint32_t fr = 0; fr < (1u << log2C); ++fr) {
-            const uint32_t n = cnt(fr);
-            sh.n += n;
-            sh.tail |= n > (kJoinThreads << spfShift);
-            uint32_t mine = n > threadIdx.x ? (n - threadIdx.x + kJoinThreads - 1) / kJoinThreads : 0u;
-            mine = mine < spf ? mine : spf;
-            sh.mask |= ((1u << mine) - 1u) << (fr << spfShift);
-        }
-        return sh;
-    };
-    auto for_each = [](const PartView& v, const Run& r, uint32_t spfShift, const Shape& sh, const uint32_t (&buf)[kJoinPre],
-                       auto&& cnt, auto&& f) {
-#pragma unroll
-        for (int j = 0; j < kJoinPre; ++j)
-            if ((sh.mask >> j) & 1u) f(buf[j]);
-        if (sh.tail)
-            for (uint32_t fr = 0; fr < (1u << v.log2C); ++fr) for_run(v.part, r.base + fr * v.cap, kJoinThreads << spfShift, cnt(fr), f);
-    };
-    auto insert_hashed = [&](uint32_t key) {
-        const uint32_t k = key >> radixBits;
-        uint32_t h = join_hash(k);
-        while (atomicCAS(&tab[h], kEmpty32, k) != kEmpty32) h = (h + 1) & (kJoinSlots - 1);
-    };
-    auto probe_hashed = [&](uint32_t key) {
-        const uint32_t k = key >> radixBits;
-        uint32_t h = join_hash(k);
-        for (;;) {
-            const uint32_t v = tab[h];
-            if (v == kEmpty32) break;
-            matches += (v == k);
-            h = (h + 1) & (kJoinSlots - 1);
-        }
     };
 
     if (threadIdx.x == 0) sNext = (uint32_t)atomicAdd(ticket, 1ull);
@@ -1211,7 +1203,7 @@ k_prj_probe_items(const uint32_t* __restrict__ partR, const uint32_t* __restrict
     if (cur >= nItems) return;                                 // workgroup-uniform
     uint2 it = items[cur];
     uint32_t bufR[kJoinPre], bufS[kJoinPre];
-    load(R, r_run(it.x), spfShiftR, bufR);
+    prefetch_part(R, r_run(it.x).base, bufR);
 
     for (;;) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // R(it) has landed
@@ -1221,80 +1213,30 @@ k_prj_probe_items(const uint32_t* __restrict__ partR, const uint32_t* __restrict
         uint32_t tk = 0;
         if (threadIdx.x == 0) tk = (uint32_t)atomicAdd(ticket, 1ull);
         const Run sr = s_run(it);
-        load(S, sr, spfShiftS, bufS);                          // in flight while R is built
+        prefetch_part(S, sr.base, bufS);                       // in flight while R is built
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t pid = it.x;
         const Run rr = r_run(pid);
-        auto rc = [&](uint32_t f) { return r_cnt(pid, rr, f); };
-        auto sc = [&](uint32_t f) { return s_cnt(it, sr, f); };
-        const Shape shR = shape_of(R.log2C, spfShiftR, rc);
-        const Shape shS = shape_of(S.log2C, spfShiftS, sc);
-        const uint32_t nRp = shR.n;
+        const auto keysR = keys_of(R, rr.base, [&](uint32_t f) { return R.frag ? R.cnt[(pid << R.g.log2C) + f] : rr.n; });
+        const auto keysS = keys_of(S, sr.base, [&](uint32_t f) { return S.frag ? S.cnt[(pid << S.g.log2C) + f] : sr.n; });
         uint2 nxt = it;
         uint32_t nxtIdx = nItems;
-        // after the barrier that follows R's build: the next item, and its R partition in flight while S is probed
-        auto next_item = [&]() {
-            nxtIdx = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
-            if (nxtIdx < nItems) nxt = items[nxtIdx];
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(it) has landed; bufR is free
-            __builtin_amdgcn_sched_barrier(0);
-            load(R, r_run(nxt.x), spfShiftR, bufR);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-
-        if (DIRECT && nRp <= 65535u) {
-            // ---- direct-addressed 16-bit counters (k_prj_join) ----
-            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = 0u;
-            __syncthreads();
-            for_each(R, rr, spfShiftR, shR, bufR, rc, [&](uint32_t key) {
-                const uint32_t k = key >> radixBits;
-                atomicAdd(&tab[k >> 1], 1u << (16u * (k & 1u)));
-            });
-            if (threadIdx.x == 0) sNext = tk;
-            __syncthreads();
-            next_item();
-            uint32_t m32 = 0;                                  // <= 65535 per probe, 16 probes per thread
-#pragma unroll
-            for (int j = 0; j < kJoinPre; ++j)
-                if ((shS.mask >> j) & 1u) {
-                    const uint32_t k = bufS[j] >> radixBits;
-                    m32 += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                }
-            matches += m32;
-            if (shS.tail)
-                for (uint32_t fr = 0; fr < (1u << S.log2C); ++fr)
-                    for_run(S.part, sr.base + fr * S.cap, kJoinThreads << spfShiftS, sc(fr), [&](uint32_t key) {
-                        const uint32_t k = key >> radixBits;
-                        matches += (tab[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                    });
-            __syncthreads();
-        } else if (nRp <= kJoinBlockTuples) {
-            // ---- the whole R partition in one hashed LDS table (also an R partition without tuples: nothing matches) ----
-            for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
-            __syncthreads();
-            for_each(R, rr, spfShiftR, shR, bufR, rc, insert_hashed);
-            if (threadIdx.x == 0) sNext = tk;
-            __syncthreads();
-            next_item();
-            for_each(S, sr, spfShiftS, shS, bufS, sc, probe_hashed);
-            __syncthreads();
-        } else {
-            // ---- oversized R partition (skew): several LDS builds, the item's S probed against each. The histogram-free R
-            // layout never gets here (frag_geometry: a partition fits one table), so R is one run
-            __syncthreads();                                   // no barrier yet in this item: the last ticket has been read
-            if (threadIdx.x == 0) sNext = tk;
-            __syncthreads();
-            next_item();
-            for (uint32_t blk = 0; blk < rr.n; blk += kJoinBlockTuples) {
-                const uint32_t bn = rr.n - blk > kJoinBlockTuples ? kJoinBlockTuples : rr.n - blk;
-                for (uint32_t i = threadIdx.x; i < kJoinSlots; i += kJoinThreads) tab[i] = kEmpty32;
-                __syncthreads();
-                for_run(R.part, rr.base + blk, 0u, bn, insert_hashed);
-                __syncthreads();
-                for (uint32_t fr = 0; fr < (1u << S.log2C); ++fr) for_run(S.part, sr.base + fr * S.cap, 0u, sc(fr), probe_hashed);
-                __syncthreads();
-            }
-        }
+        // (an R partition without tuples builds an empty table: nothing matches)
+        join_partition<DIRECT>(tab, radixBits, keysR, bufR, keysS, bufS,
+            [](const auto& t, uint32_t key) { t.insert(key); },
+            [&](At at) {
+                if (at == At::Oversized) __syncthreads();      // no barrier yet in this item: the last ticket has been read
+                if (at != At::Between && threadIdx.x == 0) sNext = tk;
+                if (at == At::Built) return;
+                if (at == At::Oversized) __syncthreads();
+                // behind the barrier that follows the ticket: the next item, and its R partition in flight while S is probed
+                nxtIdx = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
+                if (nxtIdx < nItems) nxt = items[nxtIdx];
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // S(it) has landed; bufR is free
+                __builtin_amdgcn_sched_barrier(0);
+                prefetch_part(R, r_run(nxt.x).base, bufR);
+                __builtin_amdgcn_sched_barrier(0);
+            }, matches);
         if (nxtIdx >= nItems) break;                           // wave-uniform: every wavefront read the same ticket
         it = nxt;
     }
@@ -1458,6 +1400,25 @@ Work carve(const PrjPlan& pl, void* base)
 // those; nullptr: `in` holds elements already.
 struct PassRows { bool on; uint64_t* stamped; uint32_t rowBase; };
 
+// The front half of a pass, behind k_chunk_base: the histogram of every chunk, its scan (the chunks' write cursors) and the
+// offsets of the output segments. rows.stamped: the row-id histogram, which also writes the {key, row} elements.
+hipError_t pass_offsets(const void* in, bool in32, const PassRows& rows, const PassParams& p, const PassLayout& l, uint64_t n,
+                        uint32_t* hist, uint32_t* sums, uint32_t* segOut, Gate gate, hipStream_t s)
+{
+    // entries past the live chunks must be zero for the scan to be a prefix of live data only
+    hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * l.histEntries, s);
+    if (e != hipSuccess) return e;
+    if (rows.on && rows.stamped)
+        hipLaunchKernelGGL(k_radix_hist_rows, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, static_cast<const uint64_t*>(in), rows.stamped,
+                           p, hist, rows.rowBase);
+    else if (in32) hipLaunchKernelGGL(k_radix_hist<true>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, hist, gate);
+    else hipLaunchKernelGGL(k_radix_hist<false>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, hist, gate);
+    if ((e = launch_exclusive_scan_u32(hist, l.histEntries, sums, s, gate)) != hipSuccess) return e;
+    const uint32_t nOut = p.nSeg * p.fan + 1;
+    hipLaunchKernelGGL(k_seg_offsets, dim3((nOut + kBlock - 1) / kBlock), dim3(kBlock), 0, s, p, hist, (uint32_t)n, segOut);
+    return hipGetLastError();
+}
+
 // One radix pass: in -> out, segments segIn[nSeg+1] -> segOut[nSeg*fan+1].
 // in32: the input already holds bare keys (pass 2); the output always does, unless rows.on.
 hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const uint32_t* segIn, uint32_t nSeg,
@@ -1467,21 +1428,10 @@ hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const 
     const uint32_t fan = 1u << bits;
     const PassLayout l = pass_layout(n, nSeg, fan);
     hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(64), 0, s, segIn, nSeg, l.chunkLen, w.chunkBase);
-    PassParams p{segIn, nSeg, l.chunkLen, w.chunkBase, shift, fan, 0u, 0u};
-    // entries past the live chunks must be zero for the scan to be a prefix of live data only
-    const hipError_t e = hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * l.histEntries, s);
+    const PassParams p{segIn, nSeg, l.chunkLen, w.chunkBase, shift, fan, 0u, 0u};
+    const hipError_t e = pass_offsets(in, in32, rows, p, l, n, w.hist, w.sums, segOut, gate, s);
     if (e != hipSuccess) return e;
-    if (rows.on && rows.stamped) {
-        hipLaunchKernelGGL(k_radix_hist_rows, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, static_cast<const uint64_t*>(in), rows.stamped,
-                           p, w.hist, rows.rowBase);
-        in = rows.stamped;
-    } else if (in32) hipLaunchKernelGGL(k_radix_hist<true>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, w.hist, gate);
-    else hipLaunchKernelGGL(k_radix_hist<false>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, in, p, w.hist, gate);
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, gate);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, w.sums, (uint32_t)l.scanBlocks, gate);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, gate);
-    const uint32_t nOut = nSeg * fan + 1;
-    hipLaunchKernelGGL(k_seg_offsets, dim3((nOut + kBlock - 1) / kBlock), dim3(kBlock), 0, s, p, w.hist, (uint32_t)n, segOut);
+    if (rows.on && rows.stamped) in = rows.stamped;
     // instance choice measured at 2^30 (profiles/r01_prj_variants.txt): 512 threads x 16
     // elements, no register prefetch, <= 128 VGPRs (2 workgroups per CU); more, smaller workgroups and the
     // prefetching instance were slower or equal
@@ -1540,6 +1490,62 @@ hipError_t partition_relation_frag(const PrjPlan& pl, const PrjFrag& g, const Wo
     hipLaunchKernelGGL((k_radix_scatter_frag<true, kFrag2Threads, kFrag2Elems, kFrag2Wpe>), dim3(F1 * g.C2), dim3(kFrag2Threads), 0, s, static_cast<const void*>(tmp), out, p2, ctr);
     return hipGetLastError();
 }
+
+// One relation of a join: its tuples, where its partitions go, and where their description goes -- fragment counts (the
+// histogram-free passes, geometry g) and offsets (the exact passes)
+struct RelParts { const PrjFrag& g; const uint64_t* in; uint64_t n; uint32_t* out; uint32_t* cnt2; uint32_t* off; };
+
+// Partitions the relations of one join (tmp: scratch of both passes). An optimistic plan runs the histogram-free passes
+// (Counters::prjFallback is 0: the caller zeroed it) and enqueues the exact passes behind them, gated on the word a
+// fragment that overflows sets: they return at once unless one did. All relations share the word, so the histogram-free
+// passes of all of them come first. *exact = the gate of the join over the exact layout.
+// ev0 / ev1 (may be null): recorded around the first pass-1 scatter of the first relation.
+hipError_t partition_relations(const PrjPlan& pl, const Work& w, const RelParts* rels, int nRels, uint32_t* tmp, Counters* ctr,
+                               hipStream_t s, Gate* exact, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
+{
+    hipError_t e;
+    *exact = kNoGate;
+    if (pl.optimistic) {
+        for (int i = 0; i < nRels; ++i) {
+            const RelParts& r = rels[i];
+            if ((e = partition_relation_frag(pl, r.g, w, r.in, r.n, tmp, r.out, r.cnt2, ctr, s, ev0, ev1)) != hipSuccess) return e;
+            ev0 = ev1 = nullptr;
+        }
+        *exact = Gate{&ctr->prjFallback, 1ull};
+    }
+    for (int i = 0; i < nRels; ++i) {
+        const RelParts& r = rels[i];
+        if ((e = partition_relation(pl, w, r.in, r.n, tmp, r.out, r.off, *exact, s, ev0, ev1)) != hipSuccess) return e;
+        ev0 = ev1 = nullptr;
+    }
+    return hipSuccess;
+}
+
+// k_prj_join over one layout of R and S; vs = kNoPart: R's checksum alone. One persistent workgroup per CU.
+const PartView kNoPart{nullptr, nullptr, nullptr, PartGeom{0u, 0u, 1u}, false};
+void enqueue_prj_join(const PrjPlan& pl, const PartView& vr, const PartView& vs, int nCU, Counters* ctr, Gate gate, hipStream_t s)
+{
+    static_assert(kJoinSlots * 2 == 65536, "two 16-bit counters per LDS word cover every 16-bit key remainder");
+    const uint32_t P = 1u << pl.radixBits;
+    const unsigned grid = P < (unsigned)nCU ? P : (unsigned)nCU;
+    const auto kernel = pl.radixBits >= 16 ? k_prj_join<true> : k_prj_join<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                       vr.part, vr.off, vr.cnt, vr.g, vs.part, vs.off, vs.cnt, vs.g, pl.radixBits, P, ctr, gate);
+}
+
+// The work items of a probe against the resident R (no host round trip): items per partition, one scan, fill.
+// cntR / cntS: the fragment counts of a relation whose plan was optimistic, else nullptr.
+hipError_t enqueue_prj_items(const PrjResident& res, const uint32_t* offR, const uint32_t* cntR, uint32_t log2CR,
+                             const uint32_t* offS, const uint32_t* cntS, uint32_t log2CS, uint32_t P, Counters* ctr, hipStream_t s)
+{
+    hipError_t e;
+    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, offR, cntR, log2CR,
+                       offS, cntS, log2CS, P, ctr, res.itemCnt, res.stats);
+    if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
+    return hipGetLastError();
+}
 }  // namespace
 
 hipError_t launch_prj(const PrjPlan& pl, const PrjBuffers& buf, const uint64_t* R, uint64_t nR,
@@ -1550,42 +1556,16 @@ hipError_t launch_prj(const PrjPlan& pl, const PrjBuffers& buf, const uint64_t* 
     uint32_t* const tmp = reinterpret_cast<uint32_t*>(buf.tmpA);
     uint32_t* const partR = reinterpret_cast<uint32_t*>(buf.partR);
     uint32_t* const partS = reinterpret_cast<uint32_t*>(buf.partS);
+    const RelParts rels[2] = {{pl.fragR, R, nR, partR, w.cnt2R, w.offR}, {pl.fragS, S, nS, partS, w.cnt2S, w.offS}};
     hipError_t e;
-    // Histogram-free passes first (Counters::prjFallback is 0: the caller zeroed the counters); the exact passes are
-    // enqueued behind them and return at once unless a fragment overflowed.
-    Gate exact = kNoGate;
-    if (pl.optimistic) {
-        if ((e = partition_relation_frag(pl, pl.fragR, w, R, nR, tmp, partR, w.cnt2R, ctr, s, evScatter0, evScatter1)) != hipSuccess) return e;
-        if (S && (e = partition_relation_frag(pl, pl.fragS, w, S, nS, tmp, partS, w.cnt2S, ctr, s)) != hipSuccess) return e;
-        exact = Gate{&ctr->prjFallback, 1ull};
-        evScatter0 = evScatter1 = nullptr;
-    }
-    if ((e = partition_relation(pl, w, R, nR, tmp, partR, w.offR, exact, s, evScatter0, evScatter1)) != hipSuccess) return e;
-    if (S && (e = partition_relation(pl, w, S, nS, tmp, partS, w.offS, exact, s)) != hipSuccess) return e;
+    Gate exact;
+    if ((e = partition_relations(pl, w, rels, S ? 2 : 1, tmp, ctr, s, &exact, evScatter0, evScatter1)) != hipSuccess) return e;
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
     const uint32_t P = 1u << pl.radixBits;
-    const unsigned want = (unsigned)nCU;                           // one persistent workgroup per CU
-    const unsigned grid = P < want ? P : want;
-    static_assert(kJoinSlots * 2 == 65536, "two 16-bit counters per LDS word cover every 16-bit key remainder");
-    const PartView none{nullptr, nullptr, nullptr, 0u, 0u, 1u};
-    auto join = [&](const PartView& vr, const PartView& vs, Gate gate) {
-        if (pl.radixBits >= 16)
-            hipLaunchKernelGGL(k_prj_join<true>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                               vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total},
-                               vs.part, vs.off, vs.cnt, PartGeom{vs.log2C, vs.cap, vs.total}, pl.radixBits, P, ctr, gate);
-        else
-            hipLaunchKernelGGL(k_prj_join<false>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                               vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total},
-                               vs.part, vs.off, vs.cnt, PartGeom{vs.log2C, vs.cap, vs.total}, pl.radixBits, P, ctr, gate);
-    };
-    if (pl.optimistic) {
-        const PartView vr{partR, nullptr, w.cnt2R, pl.fragR.log2C2, pl.fragR.cap2, P * pl.fragR.C2 * pl.fragR.cap2};
-        const PartView vs{partS, nullptr, w.cnt2S, pl.fragS.log2C2, pl.fragS.cap2, P * pl.fragS.C2 * pl.fragS.cap2};
-        join(vr, S ? vs : none, Gate{&ctr->prjFallback, 0ull});
-    }
-    const PartView er{partR, w.offR, nullptr, 0u, 0u, (uint32_t)nR};
-    const PartView es{partS, w.offS, nullptr, 0u, 0u, (uint32_t)nS};
-    join(er, S ? es : none, exact);
+    if (pl.optimistic)
+        enqueue_prj_join(pl, frag_view(partR, w.cnt2R, pl.fragR, P), S ? frag_view(partS, w.cnt2S, pl.fragS, P) : kNoPart, nCU, ctr,
+                         Gate{&ctr->prjFallback, 0ull}, s);
+    enqueue_prj_join(pl, exact_view(partR, w.offR, nR), S ? exact_view(partS, w.offS, nS) : kNoPart, nCU, ctr, exact, s);
     return hipGetLastError();
 }
 
@@ -1608,22 +1588,6 @@ ResLayout res_layout(uint32_t radixBits, uint64_t maxSlice)
     l.end = l.items + align_up(sizeof(uint2) * (P + maxSlice / kPrjItemS + 2), 256);
     return l;
 }
-
-// R's checksum (k_prj_join without S) over whichever layout R's passes ended in
-void enqueue_checksum_join(const PrjPlan& pl, const PartView& vr, int nCU, Counters* ctr, Gate gate, hipStream_t s)
-{
-    const uint32_t P = 1u << pl.radixBits;
-    const unsigned grid = P < (unsigned)nCU ? P : (unsigned)nCU;
-    const PartGeom none{0u, 0u, 1u};
-    if (pl.radixBits >= 16)
-        hipLaunchKernelGGL(k_prj_join<true>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                           vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total}, nullptr, nullptr, nullptr, none,
-                           pl.radixBits, P, ctr, gate);
-    else
-        hipLaunchKernelGGL(k_prj_join<false>, dim3(grid), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                           vr.part, vr.off, vr.cnt, PartGeom{vr.log2C, vr.cap, vr.total}, nullptr, nullptr, nullptr, none,
-                           pl.radixBits, P, ctr, gate);
-}
 }  // namespace
 
 size_t prj_resident_bytes(uint32_t radixBits, uint64_t maxSlice) { return res_layout(radixBits, maxSlice).end; }
@@ -1645,22 +1609,16 @@ hipError_t launch_prj_build(const PrjPlan& pl, const PrjBuffers& buf, const PrjR
     uint32_t* const partR = reinterpret_cast<uint32_t*>(buf.partR);
     hipError_t e;
     // R's side of launch_prj, with the final offsets / fragment counts in the resident buffer instead of the workspace
-    Gate exact = kNoGate;
-    if (pl.optimistic) {
-        if ((e = partition_relation_frag(pl, pl.fragR, w, R, nR, tmp, partR, res.cnt2R, ctr, s, evScatter0, evScatter1)) != hipSuccess) return e;
-        exact = Gate{&ctr->prjFallback, 1ull};
-        evScatter0 = evScatter1 = nullptr;
-    }
-    if ((e = partition_relation(pl, w, R, nR, tmp, partR, res.offR, exact, s, evScatter0, evScatter1)) != hipSuccess) return e;
+    Gate exact;
+    const RelParts rel{pl.fragR, R, nR, partR, res.cnt2R, res.offR};
+    if ((e = partition_relations(pl, w, &rel, 1, tmp, ctr, s, &exact, evScatter0, evScatter1)) != hipSuccess) return e;
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
     // R's decision outlives the probes' S passes, which reuse prjFallback
     if ((e = hipMemcpyAsync(&ctr->prjFallbackR, &ctr->prjFallback, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
     const uint32_t P = 1u << pl.radixBits;
-    if (pl.optimistic)
-        enqueue_checksum_join(pl, PartView{partR, nullptr, res.cnt2R, pl.fragR.log2C2, pl.fragR.cap2, P * pl.fragR.C2 * pl.fragR.cap2},
-                              nCU, ctr, Gate{&ctr->prjFallback, 0ull}, s);
-    enqueue_checksum_join(pl, PartView{partR, res.offR, nullptr, 0u, 0u, (uint32_t)nR}, nCU, ctr, exact, s);
+    if (pl.optimistic) enqueue_prj_join(pl, frag_view(partR, res.cnt2R, pl.fragR, P), kNoPart, nCU, ctr, Gate{&ctr->prjFallback, 0ull}, s);
+    enqueue_prj_join(pl, exact_view(partR, res.offR, nR), kNoPart, nCU, ctr, exact, s);
     return hipGetLastError();
 }
 
@@ -1674,37 +1632,22 @@ hipError_t launch_prj_probe(const PrjPlan& planR, uint64_t nR, const PrjPlan& pl
     hipError_t e;
     // S's passes: the histogram-free ones when the slice qualifies, the exact ones gated behind them (a Zipf slice falls back)
     if ((e = hipMemsetAsync(&ctr->prjFallback, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
-    Gate exact = kNoGate;
-    if (planS.optimistic) {
-        if ((e = partition_relation_frag(planS, planS.fragS, w, S, nS, tmp, partS, w.cnt2S, ctr, s)) != hipSuccess) return e;
-        exact = Gate{&ctr->prjFallback, 1ull};
-    }
-    if ((e = partition_relation(planS, w, S, nS, tmp, partS, w.offS, exact, s)) != hipSuccess) return e;
+    const RelParts rel{planS.fragS, S, nS, partS, w.cnt2S, w.offS};
+    Gate exact;                                                // not used: the join reads both layouts' words itself
+    if ((e = partition_relations(planS, w, &rel, 1, tmp, ctr, s, &exact)) != hipSuccess) return e;
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
-    // the work items: count per partition, one scan, fill (no host round trip)
     const uint32_t P = 1u << planR.radixBits;
     const uint32_t* const cntR = planR.optimistic ? res.cnt2R : nullptr;
     const uint32_t* const cntS = planS.optimistic ? w.cnt2S : nullptr;
-    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, res.offR, cntR, planR.fragR.log2C2,
-                       w.offS, cntS, planS.fragS.log2C2, P, ctr, res.itemCnt, res.stats);
-    if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
+    if ((e = enqueue_prj_items(res, res.offR, cntR, planR.fragR.log2C2, w.offS, cntS, planS.fragS.log2C2, P, ctr, s)) != hipSuccess) return e;
     if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
     // one persistent 1024-thread workgroup per CU (the LDS table is 128 KiB of the CU's 160)
-    const PartGeom gR{planR.fragR.log2C2, planR.fragR.cap2, P * planR.fragR.C2 * planR.fragR.cap2};
-    const PartGeom gS{planS.fragS.log2C2, planS.fragS.cap2, P * planS.fragS.C2 * planS.fragS.cap2};
-    const uint32_t* const nItems = res.itemCnt + 2ull * P;
-    if (planR.radixBits >= 16)
-        hipLaunchKernelGGL(k_prj_probe_items<true>, dim3((unsigned)nCU), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                           reinterpret_cast<const uint32_t*>(buf.partR), res.offR, cntR, gR, (uint32_t)nR,
-                           static_cast<const uint32_t*>(partS), w.offS, cntS, gS, (uint32_t)nS,
-                           res.items, nItems, res.stats, planR.radixBits, ctr);
-    else
-        hipLaunchKernelGGL(k_prj_probe_items<false>, dim3((unsigned)nCU), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
-                           reinterpret_cast<const uint32_t*>(buf.partR), res.offR, cntR, gR, (uint32_t)nR,
-                           static_cast<const uint32_t*>(partS), w.offS, cntS, gS, (uint32_t)nS,
-                           res.items, nItems, res.stats, planR.radixBits, ctr);
+    const PartGeom gR = frag_view(nullptr, cntR, planR.fragR, P).g, gS = frag_view(nullptr, cntS, planS.fragS, P).g;
+    const auto kernel = planR.radixBits >= 16 ? k_prj_probe_items<true> : k_prj_probe_items<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kJoinSlots * sizeof(uint32_t), s,
+                       reinterpret_cast<const uint32_t*>(buf.partR), res.offR, cntR, gR, (uint32_t)nR,
+                       static_cast<const uint32_t*>(partS), w.offS, cntS, gS, (uint32_t)nS,
+                       res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, ctr);
     return hipGetLastError();
 }
 
@@ -1937,14 +1880,9 @@ hipError_t launch_shard_hist(const uint64_t* in, uint64_t n, uint32_t nShards, u
     const PassLayout l = pass_layout(n, 1, nShards);
     hipLaunchKernelGGL(k_init_seg, dim3(1), dim3(64), 0, s, w.seg0, (uint32_t)n);
     hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(64), 0, s, w.seg0, 1u, l.chunkLen, w.chunkBase);
-    PassParams p{w.seg0, 1u, l.chunkLen, w.chunkBase, digitShift & 0xFFu, nShards, (digitShift >> 8) & 1u, 1u};
-    const hipError_t e = hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * l.histEntries, s);
+    const PassParams p{w.seg0, 1u, l.chunkLen, w.chunkBase, digitShift & 0xFFu, nShards, (digitShift >> 8) & 1u, 1u};
+    const hipError_t e = pass_offsets(in, false, PassRows{false, nullptr, 0u}, p, l, n, w.hist, w.sums, w.segOut, kNoGate, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_radix_hist<false>, dim3((unsigned)l.maxChunks), dim3(kBlock), 0, s, static_cast<const void*>(in), p, w.hist, kNoGate);
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, kNoGate);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, w.sums, (uint32_t)l.scanBlocks, kNoGate);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)l.scanBlocks), dim3(kBlock), 0, s, w.hist, l.histEntries, w.sums, kNoGate);
-    hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(kBlock), 0, s, p, w.hist, (uint32_t)n, w.segOut);
     hipLaunchKernelGGL(k_shard_counts, dim3(1), dim3(64), 0, s, w.segOut, nShards, counts);
     return hipGetLastError();
 }
@@ -1968,13 +1906,13 @@ hipError_t launch_shard_scatter_ordered(const uint64_t* in, uint64_t n, uint32_t
 
 size_t scan_workspace_words(uint64_t n) { return (size_t)((n + kScanTile - 1) / kScanTile) + 1; }
 
-hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s)
+hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s, Gate gate)
 {
     const uint64_t blocks = (n + kScanTile - 1) / kScanTile;
     if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, kNoGate);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, sums, (uint32_t)blocks, kNoGate);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, kNoGate);
+    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, gate);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, sums, (uint32_t)blocks, gate);
+    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, gate);
     return hipGetLastError();
 }
 

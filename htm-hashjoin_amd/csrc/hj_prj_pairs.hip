@@ -13,7 +13,7 @@
 //                      (key >> radixBits, R row) entries, duplicates of a key as separate entries; a probe walks its run to the
 //                      first empty slot and emits one (S row, R row) pair per equal entry
 //
-// Pair output as in hj_pairs.hip: pairs are staged in LDS, a full stage claims its run of the two output planes with ONE
+// Pair output as in hj_pairs.hip (flush_plane, hj_device.h): pairs are staged in LDS, a full stage claims its run of the two output planes with ONE
 // 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
 // LDS: table 15360 slots x (4 B key + 4 B row) = 120 KiB, stage 4096 pairs x 8 B = 32 KiB, 152 KiB of the CU's 160.
 
@@ -32,29 +32,6 @@ static_assert((uint32_t)kPairElems * kJoinThreads <= kPairStage, "a round of sin
 // Slot of key-remainder k: the Fibonacci hash of join_hash, scaled to a slot count that is no power of two
 __device__ __forceinline__ uint32_t pair_hash(uint32_t k) { return __umulhi(k * 0x9E3779B1u, kPairSlots); }
 __device__ __forceinline__ uint32_t pair_next(uint32_t h) { return h + 1 == kPairSlots ? 0u : h + 1; }
-
-typedef unsigned int pairs_u4 __attribute__((ext_vector_type(4)));
-
-// flush_plane of hj_pairs.hip for a workgroup of kJoinThreads: lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity
-__device__ __forceinline__ void prj_flush_plane(const uint32_t* lds, uint32_t cnt, uint32_t* __restrict__ out, uint64_t base, uint64_t capacity)
-{
-    if (base >= capacity) return;
-    const uint64_t room = capacity - base;
-    const uint32_t lim = room < cnt ? (uint32_t)room : cnt;
-    uint32_t* const dst = out + base;
-    uint32_t lead = (uint32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
-    if (lead > lim) lead = lim;
-    if (threadIdx.x < lead) __builtin_nontemporal_store(lds[threadIdx.x], dst + threadIdx.x);
-    const uint32_t nv = (lim - lead) >> 2;
-    for (uint32_t v = threadIdx.x; v < nv; v += kJoinThreads) {
-        const uint32_t i = lead + 4u * v;
-        pairs_u4 x;
-        x.x = lds[i]; x.y = lds[i + 1]; x.z = lds[i + 2]; x.w = lds[i + 3];
-        __builtin_nontemporal_store(x, reinterpret_cast<pairs_u4*>(dst + i));
-    }
-    const uint32_t tail = lead + 4u * nv;
-    if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
-}
 
 // prjChecksum of a resident R of {key, row} elements, as k_prj_join sums it: (key >> radixBits) & (nextpow2(|partition|) - 1)
 __global__ void __launch_bounds__(kBlock)
@@ -101,8 +78,8 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
         if (threadIdx.x == 0) sBase = atomicAdd(cursor, (unsigned long long)fill);
         __syncthreads();                               // the base is there, and so is every pair of the rounds before
         const uint64_t base = sBase;
-        prj_flush_plane(stS, fill, outS, base, capacity);
-        prj_flush_plane(stR, fill, outR, base, capacity);
+        flush_plane<kJoinThreads>(stS, fill, outS, base, capacity);
+        flush_plane<kJoinThreads>(stR, fill, outR, base, capacity);
         __syncthreads();                               // nobody refills the stage (or claims again) while it is being read
         fill = 0;
     };
@@ -160,22 +137,12 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
             load_s(0u, nxt);                                           // in flight while the table is built
             for (uint32_t i = threadIdx.x; i < kPairSlots; i += kJoinThreads) tabK[i] = kEmpty32;
             __syncthreads();
-            for (uint32_t i0 = threadIdx.x; i0 < bn; i0 += kTailPre * kJoinThreads) {
-                uint2 e[kTailPre];
-#pragma unroll
-                for (int u = 0; u < kTailPre; ++u) {
-                    const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
-                    e[u] = partR[rb + blk + (i < bn ? i : bn - 1)];
-                }
-#pragma unroll
-                for (int u = 0; u < kTailPre; ++u)
-                    if (i0 + (uint32_t)u * kJoinThreads < bn) {
-                        const uint32_t k = e[u].x >> radixBits;
-                        uint32_t h = pair_hash(k);
-                        while (atomicCAS(&tabK[h], kEmpty32, k) != kEmpty32) h = pair_next(h);    // an equal key is one more entry
-                        tabR[h] = e[u].y;
-                    }
-            }
+            for_run(partR, rb + blk, 0u, bn, [&](uint2 e) {
+                const uint32_t k = e.x >> radixBits;
+                uint32_t h = pair_hash(k);
+                while (atomicCAS(&tabK[h], kEmpty32, k) != kEmpty32) h = pair_next(h);    // an equal key is one more entry
+                tabR[h] = e.y;
+            });
             __syncthreads();
             // rounds of kPairElems S elements per thread; every thread runs the same number of them (they meet at barriers)
             for (uint32_t j0 = 0; j0 < nSi; j0 += kPairElems * kJoinThreads) {
@@ -275,12 +242,8 @@ hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, con
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
     // the work items of the counting probe: the exact layout's offsets are the same whatever the element width
     const uint32_t P = 1u << planR.radixBits;
-    if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, res.offR, nullptr, 0u,
-                       w.offS, nullptr, 0u, P, ctr, res.itemCnt, res.stats);
-    if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
+    if ((e = enqueue_prj_items(res, res.offR, nullptr, 0u, w.offS, nullptr, 0u, P, ctr, s)) != hipSuccess) return e;
     if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_prj_join_pairs, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
                        reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,

@@ -438,6 +438,15 @@ def test_prj_ragged_skewed_and_r_only(ctx):
     got = ctx.run("prj", R1, S1, radixBits=8)
     assert got["totalMatches"] == want["matches"] == oracle.true_cardinality(R1, S1)
     assert got["prjChecksum"] == want["checksum"]
+    # the same partition with 16384 < |R| <= 24576: ONE hashed table, R and S both longer than the register prefetch
+    # (a generator of its own: the cases around keep their inputs)
+    rng1 = np.random.default_rng(31)
+    R1 = (rng1.integers(1, 1 << 14, size=20000, dtype=np.uint64) << np.uint64(8)) | np.uint64(5)
+    S1 = (rng1.integers(1, 1 << 14, size=50001, dtype=np.uint64) << np.uint64(8)) | np.uint64(5)
+    want = oracle.prj_join(R1, S1, 8)
+    got = ctx.run("prj", R1, S1, radixBits=8)
+    assert got["totalMatches"] == want["matches"] == oracle.true_cardinality(R1, S1)
+    assert got["prjChecksum"] == want["checksum"]
     # radixBits 16 = the direct-addressed counter join: heavy duplicates inside one partition (counters well above 1),
     # a partition of exactly 65535 R tuples (the counters' limit) and one of 65536 (falls back to the hash table)
     for m in (65535, 65536, 40000):
@@ -448,6 +457,14 @@ def test_prj_ragged_skewed_and_r_only(ctx):
         got = ctx.run("prj", R2, S2, radixBits=16)
         assert got["totalMatches"] == want["matches"] == oracle.true_cardinality(R2, S2), m
         assert got["prjChecksum"] == want["checksum"], m
+    # the counters with a short R partition (inside the register prefetch) and 50001 S tuples: the counter probe's tail loop
+    R2 = (rng1.integers(0, 300, size=10000, dtype=np.uint64) << np.uint64(16)) | np.uint64(0x1234)
+    S2 = (rng1.integers(0, 400, size=50001, dtype=np.uint64) << np.uint64(16)) | np.uint64(0x1234)
+    R2 = np.concatenate([R2, oracle.generate_data("shuffle", 1 << 16)])
+    want = oracle.prj_join(R2, S2, 16)
+    got = ctx.run("prj", R2, S2, radixBits=16)
+    assert got["totalMatches"] == want["matches"] == oracle.true_cardinality(R2, S2)
+    assert got["prjChecksum"] == want["checksum"]
     # R-side only (what the fork's PRO actually runs): checksum, no matches
     got = ctx.run("prj", R, None, radixBits=14)
     assert got["totalMatches"] == 0 and got["prjChecksum"] == oracle.prj_join(R, None, 14)["checksum"]
