@@ -28,6 +28,11 @@ ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 # as {key, row} elements (hj_prj_probe_pairs_dev)
 HJ_FLAG_KEEP_ROW_IDS = 0x1
 
+# hj_join_kind (hj_probe_join_dev / hj_prj_probe_join_dev) and the R row of a left-outer row without a match
+HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI = 0, 1, 2, 3
+JOIN_KINDS = {"inner": HJ_JOIN_INNER, "left": HJ_JOIN_LEFT, "semi": HJ_JOIN_SEMI, "anti": HJ_JOIN_ANTI}
+HJ_NO_ROW = 0xFFFFFFFF
+
 
 class hj_params(C.Structure):
     _fields_ = [
@@ -82,11 +87,13 @@ def _declare(lib):
         "hj_build_dev": ([vp, vp, u64, u64], i32),
         "hj_probe_dev": ([vp, vp, u64], i32),
         "hj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
+        "hj_probe_join_dev": ([vp, u32, vp, u64, u64, vp, vp, u64], i32),
         "hj_pairs_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
+        "hj_prj_probe_join_dev": ([vp, u32, vp, u64, u64, vp, vp, u64], i32),
         "hj_prj_resident_info": ([vp, P(u64)], i32),
         "hj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_checksums_dev": ([vp], i32),

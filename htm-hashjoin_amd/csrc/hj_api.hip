@@ -28,7 +28,7 @@ enum Buf {
     B_HTM_CONFLICTS, B_HTM_OWN_COUNTS,          // htm: conflicts listed per chunk; their counts in the window build
     B_HTM_OVF_COUNT, B_HTM_OVF_BASE, B_HTM_SCAN,
     B_HTM_OVERFLOW,             // overflow buckets (index 0 unused)
-    B_PAIRS_CURSOR,             // materialising probe (hj_probe_pairs_dev): the output cursor
+    B_PAIRS_CURSOR,             // materialising probe (hj_probe_join_dev): the output cursor, then HJ_JOIN_LEFT's unmatched S tuples
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -78,7 +78,9 @@ struct hj_ctx {
     int* zipfRawHost[2] = {nullptr, nullptr}; int* zipfRawDev[2] = {nullptr, nullptr}; uint64_t zipfRawCap = 0;
     hipEvent_t zipfDone[2] = {nullptr, nullptr}; int zipfFlip = 0;
     uint32_t variantUsed = 1;
-    uint64_t pairsCapacity = 0;                 // materialising probe (hj_probe_pairs_dev): the capacity of the last call
+    uint64_t pairsCapacity = 0;                 // materialising probe (hj_probe_join_dev): the capacity of the last call,
+    uint32_t pairsKind = HJ_JOIN_INNER;         // ... its join kind and its sSize (hj_pairs_info)
+    uint64_t pairsS = 0;
     Counters* hCtr = nullptr;     // pinned copy of the counters
     // PRJ
     PrjPlan plan{};
@@ -243,8 +245,8 @@ int create_common(int device, void* stream, bool own, hj_ctx** out)
               hipHostMalloc(reinterpret_cast<void**>(&c->hPreferred), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dPreferred), c->hPreferred, 0) == hipSuccess &&
               c->buf[B_BOUNDS].reserve(c, wave_bounds_bytes(c->nCU)) == HJ_OK &&
-              c->buf[B_PAIRS_CURSOR].reserve(c, sizeof(unsigned long long)) == HJ_OK &&
-              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, sizeof(unsigned long long)) == hipSuccess;
+              c->buf[B_PAIRS_CURSOR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
+              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }
     hipMemset(c->dCtr(), 0, sizeof(Counters));
@@ -671,36 +673,54 @@ int hj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
     return HJ_OK;
 }
 
-int hj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
-                       uint64_t capacity)
+// The one host sequence of the materialising table probe; fn: the entry point's name, for the error texts
+static int probe_join(hj_ctx* c, const char* fn, uint32_t kind, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS,
+                      uint32_t* dOutR, uint64_t capacity)
 {
     if (!c || (!dS && sSize)) return HJ_ERR_INVALID;
+    const std::string f(fn);
+    if (kind > HJ_JOIN_ANTI) return fail(c, HJ_ERR_INVALID, (f + ": kind must be an hj_join_kind").c_str());
+    const bool planeR = kind <= HJ_JOIN_LEFT;            // SEMI and ANTI write S rows only: dOutR is ignored
     // decided on the host: whether the table keeps its index words is chosen on the device (Counters::tableFormat), so
     // the call keys on what hj_reserve was promised
-    if (c->params.algo == HJ_ALGO_PRJ) return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: a PRJ context keeps no row ids");
-    if (!c->built) return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: no table (call hj_build_dev first)");
+    if (c->params.algo == HJ_ALGO_PRJ) return fail(c, HJ_ERR_STATE, (f + ": a PRJ context keeps no row ids").c_str());
+    if (!c->built) return fail(c, HJ_ERR_STATE, (f + ": no table (call hj_build_dev first)").c_str());
     if (!c->htmBuilt && !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS))
-        return fail(c, HJ_ERR_STATE, "hj_probe_pairs_dev: open-addressing context reserved without HJ_FLAG_KEEP_ROW_IDS");
-    if (capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: output pointer NULL with capacity > 0");
+        return fail(c, HJ_ERR_STATE, (f + ": open-addressing context reserved without HJ_FLAG_KEEP_ROW_IDS").c_str());
+    if (capacity && (!dOutS || (planeR && !dOutR))) return fail(c, HJ_ERR_INVALID, (f + ": output pointer NULL with capacity > 0").c_str());
     if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull)
-        return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: S row range exceeds 2^32 - 1");
+        return fail(c, HJ_ERR_INVALID, (f + ": S row range exceeds 2^32 - 1").c_str());
     if (!c->htmBuilt && probe_len(c->params) > pairs_max_probe_len())
-        return fail(c, HJ_ERR_INVALID, "hj_probe_pairs_dev: probeLength above 8");
+        return fail(c, HJ_ERR_INVALID, (f + ": probeLength above 8").c_str());
     if (sSize == 0) return HJ_OK;
     HJ_HIP(c, hipSetDevice(c->device));
     c->streamAtBuildEnd = false;
     int rc;
-    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
-    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), c->stream));
+    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
     if ((rc = record(c, EV_PAIRS0))) return rc;
     const uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
-    if (c->htmBuilt) launch_htm_probe_pairs(dS, sSize, sIdxBase, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), out, c->nCU, c->dCtr(), c->stream);
-    else launch_probe_pairs(dS, sSize, sIdxBase, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr(), c->stream);
+    if (c->htmBuilt) launch_htm_probe_pairs(kind, dS, sSize, sIdxBase, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), out, c->nCU, c->dCtr(), c->stream);
+    else launch_probe_pairs(kind, dS, sSize, sIdxBase, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr(), c->stream);
     if ((rc = record(c, EV_PAIRS1))) return rc;
     HJ_HIP(c, hipGetLastError());
-    c->pairsCapacity = capacity;
+    c->pairsCapacity = capacity; c->pairsKind = kind; c->pairsS = sSize;
     c->sSize += sSize;
     return HJ_OK;
+}
+
+// (No R row is HJ_NO_ROW: hj_build_dev and build_htm refuse idxBase + rSize > 2^32 - 1, hj_build_keys_dev n > 2^32 - 1, so
+// the largest row is 2^32 - 2 and HJ_JOIN_LEFT needs no check of its own.)
+int hj_probe_join_dev(hj_ctx* c, uint32_t kind, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
+                      uint64_t capacity)
+{
+    return probe_join(c, "hj_probe_join_dev", kind, dS, sSize, sIdxBase, dOutS, dOutR, capacity);
+}
+
+int hj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
+                       uint64_t capacity)
+{
+    return probe_join(c, "hj_probe_pairs_dev", HJ_JOIN_INNER, dS, sSize, sIdxBase, dOutS, dOutR, capacity);
 }
 
 int hj_pairs_info(hj_ctx* c, uint64_t out[4])
@@ -708,12 +728,15 @@ int hj_pairs_info(hj_ctx* c, uint64_t out[4])
     HJ_ENTER(c, out);
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned long long found = 0;
-    HJ_HIP(c, hipMemcpy(&found, c->buf[B_PAIRS_CURSOR].p, sizeof found, hipMemcpyDeviceToHost));
+    unsigned long long words[2] = {0, 0};        // the cursor = rows found; LEFT's unmatched S tuples
+    HJ_HIP(c, hipMemcpy(words, c->buf[B_PAIRS_CURSOR].p, sizeof words, hipMemcpyDeviceToHost));
+    const unsigned long long found = words[0];
     out[0] = found;
     out[1] = found < c->pairsCapacity ? found : c->pairsCapacity;
     out[2] = (uint64_t)(elapsed_us(c, EV_PAIRS0, EV_PAIRS1) + 0.5);
-    out[3] = 0;
+    // unmatched S tuples of the call: SEMI wrote one row per matched tuple, ANTI one per unmatched one
+    out[3] = c->pairsKind == HJ_JOIN_LEFT ? words[1] : c->pairsKind == HJ_JOIN_SEMI ? c->pairsS - found
+           : c->pairsKind == HJ_JOIN_ANTI ? found : 0;
     return HJ_OK;
 }
 
@@ -807,7 +830,7 @@ static bool prj_slice_fits(const hj_ctx* c, uint64_t sSize)
 
 // One probe of a resident R of {key, row} elements: the slice's row-id passes and the pairs join, timed as a probe
 // (EV_RP*); pairsCall: also as a pairs call (EV_PAIRS*), the facts hj_pairs_info reports
-static int prj_probe_rows(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, const PairsOut& out, bool pairsCall)
+static int prj_probe_rows(hj_ctx* c, uint32_t kind, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, const PairsOut& out, bool pairsCall)
 {
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, 1u);     // exact passes only: they carry the rows
@@ -815,7 +838,7 @@ static int prj_probe_rows(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_
     if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;      // R stays resident: see hj_prj_build_dev
     if ((rc = record(c, EV_RP0))) return rc;
     if (pairsCall && (rc = record(c, EV_PAIRS0))) return rc;
-    HJ_HIP(c, launch_prj_probe_rows(c->resPlan, pl, prj_buffers(c), prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize),
+    HJ_HIP(c, launch_prj_probe_rows(kind, c->resPlan, pl, prj_buffers(c), prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize),
                                     dS, sSize, sIdxBase, out, c->nCU, c->dCtr(), c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
     c->evSet[EV_RP_PART] = c->evSet[EV_RP_JOIN0] = true;
     if (pairsCall && (rc = record(c, EV_PAIRS1))) return rc;
@@ -835,7 +858,8 @@ int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
         // R holds {key, row} elements, which the counting kernels cannot read: the pairs join with capacity 0, counting into
         // a word of its own (stats[4]: past the four the work items use) so that hj_pairs_info keeps the last pairs call
         const PrjResident res = prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize);
-        return prj_probe_rows(c, dS, sSize, 0, PairsOut{nullptr, nullptr, 0, res.stats + 4}, false);
+        // (and the word behind it, which HJ_JOIN_INNER leaves at zero)
+        return prj_probe_rows(c, HJ_JOIN_INNER, dS, sSize, 0, PairsOut{nullptr, nullptr, 0, res.stats + 4}, false);
     }
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjPlan pl = prj_plan(sSize, sSize, c->resPlan.radixBits, c->params.prjMode);   // fragS: the slice's own geometry
@@ -852,20 +876,39 @@ int hj_prj_probe_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize)
     return HJ_OK;
 }
 
+// The one host sequence of the materialising radix probe; fn: the entry point's name, for the error texts
+static int prj_probe_join(hj_ctx* c, const char* fn, uint32_t kind, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS,
+                          uint32_t* dOutR, uint64_t capacity)
+{
+    HJ_ENTER(c, dS || !sSize);
+    const std::string f(fn);
+    if (kind > HJ_JOIN_ANTI) return fail(c, HJ_ERR_INVALID, (f + ": kind must be an hj_join_kind").c_str());
+    const bool planeR = kind <= HJ_JOIN_LEFT;            // SEMI and ANTI write S rows only: dOutR is ignored
+    if (!c->resident) return fail(c, HJ_ERR_STATE, (f + ": no resident R (call hj_prj_build_dev first)").c_str());
+    if (!c->resRows) return fail(c, HJ_ERR_STATE, (f + ": R was built without HJ_FLAG_KEEP_ROW_IDS").c_str());
+    if (!prj_slice_fits(c, sSize)) return fail(c, HJ_ERR_STATE, (f + ": slice larger than the sSize given to hj_reserve()").c_str());
+    if (capacity && (!dOutS || (planeR && !dOutR))) return fail(c, HJ_ERR_INVALID, (f + ": output pointer NULL with capacity > 0").c_str());
+    if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, (f + ": S row range exceeds 2^32 - 1").c_str());
+    if (sSize == 0) return HJ_OK;
+    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
+    const int rc = prj_probe_rows(c, kind, dS, sSize, sIdxBase, out, true);
+    if (rc == HJ_OK) { c->pairsCapacity = capacity; c->pairsKind = kind; c->pairsS = sSize; }
+    return rc;
+}
+
+// (No R row is HJ_NO_ROW: hj_reserve refuses rSize >= 2^32 - 1 for PRJ and hj_prj_build_dev takes no more than was reserved,
+// so the largest row is 2^32 - 3 and HJ_JOIN_LEFT needs no check of its own.)
+int hj_prj_probe_join_dev(hj_ctx* c, uint32_t kind, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
+                          uint64_t capacity)
+{
+    return prj_probe_join(c, "hj_prj_probe_join_dev", kind, dS, sSize, sIdxBase, dOutS, dOutR, capacity);
+}
+
 int hj_prj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64_t sIdxBase, uint32_t* dOutS, uint32_t* dOutR,
                            uint64_t capacity)
 {
-    HJ_ENTER(c, dS || !sSize);
-    if (!c->resident) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: no resident R (call hj_prj_build_dev first)");
-    if (!c->resRows) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: R was built without HJ_FLAG_KEEP_ROW_IDS");
-    if (!prj_slice_fits(c, sSize)) return fail(c, HJ_ERR_STATE, "hj_prj_probe_pairs_dev: slice larger than the sSize given to hj_reserve()");
-    if (capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_prj_probe_pairs_dev: output pointer NULL with capacity > 0");
-    if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull)
-        return fail(c, HJ_ERR_INVALID, "hj_prj_probe_pairs_dev: S row range exceeds 2^32 - 1");
-    if (sSize == 0) return HJ_OK;
-    const int rc = prj_probe_rows(c, dS, sSize, sIdxBase, PairsOut{dOutS, dOutR, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()}, true);
-    if (rc == HJ_OK) c->pairsCapacity = capacity;
-    return rc;
+    return prj_probe_join(c, "hj_prj_probe_pairs_dev", HJ_JOIN_INNER, dS, sSize, sIdxBase, dOutS, dOutR, capacity);
 }
 
 int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])

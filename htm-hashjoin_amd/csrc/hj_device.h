@@ -340,6 +340,8 @@ hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums,
 // ---- materialising probe (defined in hj_pairs.hip) --------------------------
 // where hj_probe_pairs_dev writes: the two gather-map planes, their length, and the 64-bit cursor the workgroups claim
 // their runs from (zeroed before the launch; its final value = pairs found, written or not)
+// Join kinds (hj_join_kind): `kind` picks the kernels' instantiation. cursor[1] (zeroed with the cursor) collects the S
+// elements without a match under HJ_JOIN_LEFT and is touched by no other kind; HJ_JOIN_SEMI / ANTI never touch plane r.
 struct PairsOut { uint32_t* s; uint32_t* r; uint64_t capacity; unsigned long long* cursor; };
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 // A staged plane leaves LDS, by a workgroup of NT threads: lds[0 .. cnt) -> out[base .. base + cnt), cut at capacity. The
@@ -367,9 +369,9 @@ __device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, u
 }
 uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
 // the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot
-void launch_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
+void launch_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
                         uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
-void launch_htm_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
+void launch_htm_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
                             const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
 
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
@@ -446,7 +448,8 @@ hipError_t launch_prj_build_rows(const PrjPlan& plan, const PrjBuffers& buf, con
                                  int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0, hipEvent_t evScatter1, hipStream_t s);
 // S's passes (row = sIdxBase + position in S), the work-item list, the join that emits (S row, R row) pairs to `out`
 // (out.cursor is zeroed on the stream first; out.capacity 0: the pairs are counted only). Adds to Counters::prjMatches.
-hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+// kind: hj_join_kind. HJ_JOIN_LEFT and HJ_JOIN_ANTI give partitions with S tuples and no R tuple a work item of their own.
+hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
                                  const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
                                  hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s);
 

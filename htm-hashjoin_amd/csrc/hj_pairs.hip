@@ -14,6 +14,14 @@
 // key whose chain has thousands of buckets just flushes more often; no lane ever buffers more than one bucket.
 // Pairs at or beyond `capacity` are counted (the cursor runs on) and not written: the check is per element.
 //
+//
+// Join kinds (hj_probe_join_dev): the kind K is a template parameter of both kernels. A kind is a different ROW count per
+// S element and a different thing written, not another pass: INNER one row per match (the code as it was), LEFT the same
+// plus one (S row, kNoRow) row for an element without a match, SEMI the S row once if it has a match, ANTI the S row if
+// it has none. SEMI and ANTI stage and write the S plane only. Lanes without an element (load_vecs pads, the head/tail
+// round leaves 255 threads idle) carry valid = false and never produce an unmatched row. Counters::matches grows by the
+// INNER matches whatever the kind.
+//
 // All integer work, bound by HBM and the table gather; no MFMA.
 
 #include "hj_device.h"
@@ -27,6 +35,9 @@ constexpr uint32_t kWaves = kBlock / kWave;
 // A round must fit an empty stage (asserted where the rounds are shaped): 1024 S tuples x 4 slots at probeLength 4,
 // 512 x kMaxProbeLen at any other length, 1024 buckets x 3 tuples for htm
 constexpr uint32_t kMaxProbeLen = 8;
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;        // HJ_NO_ROW: the R row of a LEFT row without a match
+// hj_join_kind; kinds above LEFT write S rows only
+constexpr int kInner = 0, kLeft = 1, kSemi = 2, kAnti = 3;
 
 struct Stage {
     uint32_t* s;                  // LDS: S rows of the staged pairs
@@ -36,24 +47,29 @@ struct Stage {
     uint32_t fill;                // pairs staged (the same value in every thread)
     uint32_t round;
     unsigned long long found;     // pairs of this workgroup so far (the same value in every thread)
+    // kinds other than INNER, per lane: the inner matches of its elements, its elements without a match
+    unsigned long long inner;
+    uint32_t unmatched;
 };
 
 // Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
+template <int K>
 __device__ __forceinline__ void stage_flush(Stage& st, const PairsOut& out)
 {
     if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
     __syncthreads();                                  // the base is there, and so is every pair of the rounds before
     const uint64_t base = *st.base;
     flush_plane<kBlock>(st.s, st.fill, out.s, base, out.capacity);
-    flush_plane<kBlock>(st.r, st.fill, out.r, base, out.capacity);
+    if constexpr (K <= kLeft) flush_plane<kBlock>(st.r, st.fill, out.r, base, out.capacity);
     __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
     st.fill = 0;
 }
 
-// One round: every lane brings m pairs (more: it has further buckets to walk). Returns the lane's position in the
+// One round: every lane brings m pairs -- rows of the kind K -- (more: it has further buckets to walk). Returns the lane's position in the
 // stage; the lane then writes its m pairs there. anyMore: some lane of the workgroup has more. One barrier, two when the
 // stage is flushed first. The totals are double-buffered by round parity: a wavefront writes round k + 2's only after the
 // barrier of round k + 1, which every wavefront reaches after reading round k's.
+template <int K>
 __device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out, uint32_t m, bool more, bool& anyMore)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
@@ -77,7 +93,7 @@ __device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out
     }
     st.round += 1;
     anyMore = any != 0;
-    if (st.fill + tot > kStagePairs) stage_flush(st, out);            // workgroup-uniform
+    if (st.fill + tot > kStagePairs) stage_flush<K>(st, out);         // workgroup-uniform
     const uint32_t pos = st.fill + wbase + inc - m;
     st.fill += tot;
     st.found += tot;
@@ -93,10 +109,24 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
 
 // the end of both kernels: the last stage, then the workgroup's share of the counters (one atomic per workgroup and
 // counter: found is the same in every thread; the foreign counts are per lane)
+// Kinds other than INNER: the rows are not the matches, so the lanes' inner matches are summed instead; LEFT also leaves
+// its unmatched elements in the word behind the cursor (hj_pairs_info; SEMI and ANTI derive theirs on the host)
+template <int K>
 __device__ __forceinline__ void stage_finish(Stage& st, const PairsOut& out, uint32_t foreign, Counters* __restrict__ ctr)
 {
-    if (st.fill) stage_flush(st, out);
-    if (threadIdx.x == 0 && st.found) atomicAdd(&counter_shard(ctr)->matches, st.found);
+    if (st.fill) stage_flush<K>(st, out);
+    if constexpr (K == kInner) {
+        if (threadIdx.x == 0 && st.found) atomicAdd(&counter_shard(ctr)->matches, st.found);
+    } else {
+        unsigned long long inner = st.inner;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) inner += __shfl_down(inner, off, kWave);
+        if ((threadIdx.x & (kWave - 1)) == 0 && inner) atomicAdd(&counter_shard(ctr)->matches, inner);
+        if constexpr (K == kLeft) {
+            const uint32_t unmatched = wave_sum32(st.unmatched);
+            if ((threadIdx.x & (kWave - 1)) == 0 && unmatched) atomicAdd(out.cursor + 1, (unsigned long long)unmatched);
+        }
+    }
     foreign = wave_sum32(foreign);
     if ((threadIdx.x & (kWave - 1)) == 0 && foreign) atomicAdd(&counter_shard(ctr)->foreign, (unsigned long long)foreign);
 }
@@ -175,8 +205,13 @@ __device__ __forceinline__ Hit walk(uint64_t sk, const uint64_t* __restrict__ ta
     return h;
 }
 
-__device__ __forceinline__ void emit(Stage& st, uint32_t& pos, uint32_t sRow, const Hit& h)
+// valid: the lane holds an element (only the kinds that write unmatched rows ask)
+template <int K>
+__device__ __forceinline__ void emit(Stage& st, uint32_t& pos, uint32_t sRow, const Hit& h, bool valid)
 {
+    if constexpr (K == kSemi) { if (h.mask != 0) { st.s[pos] = sRow; ++pos; } return; }
+    if constexpr (K == kAnti) { if (valid && h.mask == 0) { st.s[pos] = sRow; ++pos; } return; }
+    if constexpr (K == kLeft) if (valid && h.mask == 0) { st.s[pos] = sRow; st.r[pos] = kNoRow; ++pos; }
     if (h.mask == 0) return;
     st.s[pos] = sRow; st.r[pos] = h.first; ++pos;
     for (uint32_t rest = h.mask & (h.mask - 1u); rest; rest &= rest - 1u) {      // duplicate keys in R
@@ -188,23 +223,35 @@ __device__ __forceinline__ void emit(Stage& st, uint32_t& pos, uint32_t sRow, co
 struct OaTable { const uint64_t* table; uint64_t mask; uint32_t hshift, probeLen; uint64_t validLo, validHiEx, dummy; };
 
 // E elements per lane: walk them all, agree on the round's pair count, write the pairs into the stage
-template <int E, bool FOUR>
-__device__ __forceinline__ void oa_round(Stage& st, const PairsOut& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E])
+// Rows per element: INNER popc(mask); LEFT max(popc(mask), 1), SEMI mask != 0, ANTI mask == 0 -- the latter three for a
+// valid lane only (a lane without an element has mask 0 and is no unmatched row)
+template <int K, int E, bool FOUR>
+__device__ __forceinline__ void oa_round(Stage& st, const PairsOut& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
+                                         const bool (&valid)[E])
 {
     Hit h[E];
     uint32_t m = 0;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         h[e] = walk<FOUR>(sk[e], T.table, T.mask, T.hshift, T.probeLen, T.validLo, T.validHiEx, T.dummy);
-        m += (uint32_t)__popc(h[e].mask);
+        const uint32_t hits = (uint32_t)__popc(h[e].mask);
+        if constexpr (K == kInner) {
+            m += hits;
+        } else {
+            const uint32_t none = (uint32_t)(valid[e] && h[e].mask == 0);
+            st.inner += hits;
+            if constexpr (K == kLeft) { m += hits + none; st.unmatched += none; }
+            if constexpr (K == kSemi) m += (uint32_t)(h[e].mask != 0);
+            if constexpr (K == kAnti) m += none;
+        }
     }
     bool any;
-    uint32_t pos = stage_reserve(st, out, m, false, any);
+    uint32_t pos = stage_reserve<K>(st, out, m, false, any);
 #pragma unroll
-    for (int e = 0; e < E; ++e) emit(st, pos, (uint32_t)row[e], h[e]);
+    for (int e = 0; e < E; ++e) emit<K>(st, pos, (uint32_t)row[e], h[e], valid[e]);
 }
 
-template <int V, bool FOUR>
+template <int K, int V, bool FOUR>
 __device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const OaTable& T,
                                                  const ShardCheck& sc, const PairsOut& out, Counters* __restrict__ ctr)
 {
@@ -220,44 +267,49 @@ __device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __re
         u4 nxt[V];
         load_vecs<V>(b, v0 + stride, nxt);
         uint64_t sk[2 * V], row[2 * V];
+        bool valid[2 * V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
             sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
             row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
+            valid[2 * k] = valid[2 * k + 1] = v < b.nv;
             if (v < b.nv) foreign += (uint32_t)is_foreign(cur[k].x, sc) + (uint32_t)is_foreign(cur[k].z, sc);
         }
-        oa_round<2 * V, FOUR>(st, out, T, sk, row);
+        oa_round<K, 2 * V, FOUR>(st, out, T, sk, row, valid);
 #pragma unroll
         for (int k = 0; k < V; ++k) cur[k] = nxt[k];
     }
     if (blockIdx.x == 0 && (b.head || b.tail < n)) {
         uint64_t sk[2] = {kNoElement, kNoElement};
         const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
+        const bool valid[2] = {threadIdx.x == 0 && b.head != 0, threadIdx.x == 0 && b.tail < n};     // 255 threads bring nothing
         if (threadIdx.x == 0) {
             if (b.head) { sk[0] = S[0]; foreign += is_foreign((uint32_t)sk[0], sc); }
             if (b.tail < n) { sk[1] = S[b.tail]; foreign += is_foreign((uint32_t)sk[1], sc); }
         }
-        oa_round<2, FOUR>(st, out, T, sk, row);
+        oa_round<K, 2, FOUR>(st, out, T, sk, row, valid);
     }
-    stage_finish(st, out, foreign, ctr);
+    stage_finish<K>(st, out, foreign, ctr);
 }
 
 }  // namespace
 
 // probeLength 4 (the reference's default): four elements per lane and round, all sixteen window loads in flight;
 // any other length: two elements, the walk with its early exit
+// K: hj_join_kind. SEMI and ANTI keep no R plane in LDS
+template <int K>
 __global__ void __launch_bounds__(kBlock)
 k_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint64_t mask,
               uint32_t hshift, uint32_t probeLen, ShardCheck sc, PairsOut out, Counters* __restrict__ ctr)
 {
-    __shared__ uint32_t ldsS[kStagePairs], ldsR[kStagePairs], ldsTot[2 * kWaves];
+    __shared__ uint32_t ldsS[kStagePairs], ldsR[K <= kLeft ? kStagePairs : 1], ldsTot[2 * kWaves];
     __shared__ unsigned long long ldsBase;
-    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull};
+    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
     OaTable T{table, mask, hshift, probeLen, ctr->validLo, ctr->validHiEx, 0};
     T.dummy = T.validLo < mask ? T.validLo : 0;          // any in-table slot; this one is in cache
-    if (probeLen == 4) probe_pairs_body<2, true>(st, S, n, sIdxBase, T, sc, out, ctr);
-    else probe_pairs_body<1, false>(st, S, n, sIdxBase, T, sc, out, ctr);
+    if (probeLen == 4) probe_pairs_body<K, 2, true>(st, S, n, sIdxBase, T, sc, out, ctr);
+    else probe_pairs_body<K, 1, false>(st, S, n, sIdxBase, T, sc, out, ctr);
 }
 
 namespace {
@@ -267,6 +319,9 @@ namespace {
 // ---------------------------------------------------------------------------
 // the bucket a walk stands at (nullptr: done), and what the last bucket read matched
 struct ChainWalk { const ulonglong2* p; uint32_t key, sRow, m, r0, r1, r2; };
+// what a walk carries besides for the kinds other than INNER: seen = an earlier bucket of the chain matched; done = the
+// element's last row decision is taken (its chain has ended, or the lane never held an element); rows = what this step writes
+struct ChainKind { bool seen, done; uint32_t rows; };
 
 __device__ __forceinline__ void chain_step(ChainWalk& c, const uint64_t* __restrict__ overflow)
 {
@@ -285,8 +340,27 @@ __device__ __forceinline__ void chain_step(ChainWalk& c, const uint64_t* __restr
     c.p = next ? reinterpret_cast<const ulonglong2*>(overflow + ((uint64_t)next << 2)) : nullptr;
 }
 
-__device__ __forceinline__ void chain_emit(Stage& st, uint32_t& pos, const ChainWalk& c)
+// The step's rows of the kind K. An element is unmatched only once its chain has ended (c.p == nullptr after the step)
+// and no bucket matched: that row, like SEMI's, is written once, never once per bucket. At most 3 rows per step: the
+// unmatched row comes with m == 0.
+template <int K>
+__device__ __forceinline__ void chain_rows(const ChainWalk& c, ChainKind& k, Stage& st)
 {
+    const bool ends = !k.done && c.p == nullptr;
+    const bool none = ends && !k.seen && c.m == 0;
+    st.inner += c.m;
+    if constexpr (K == kLeft) { k.rows = c.m + (uint32_t)none; st.unmatched += (uint32_t)none; }
+    if constexpr (K == kSemi) k.rows = (uint32_t)(c.m != 0 && !k.seen);
+    if constexpr (K == kAnti) k.rows = (uint32_t)none;
+    k.seen = k.seen || c.m != 0;
+    k.done = k.done || ends;
+}
+
+template <int K>
+__device__ __forceinline__ void chain_emit(Stage& st, uint32_t& pos, const ChainWalk& c, const ChainKind& k)
+{
+    if constexpr (K >= kSemi) { if (k.rows) { st.s[pos] = c.sRow; ++pos; } return; }
+    if constexpr (K == kLeft) if (k.rows > c.m) { st.s[pos] = c.sRow; st.r[pos] = kNoRow; ++pos; }
     if (c.m > 0) { st.s[pos] = c.sRow; st.r[pos] = c.r0; ++pos; }
     if (c.m > 1) { st.s[pos] = c.sRow; st.r[pos] = c.r1; ++pos; }
     if (c.m > 2) { st.s[pos] = c.sRow; st.r[pos] = c.r2; ++pos; }
@@ -296,26 +370,34 @@ struct HtmTable { const uint64_t* table; const uint64_t* overflow; uint32_t buck
 
 // E elements per lane: bucket rounds until the longest chain of the workgroup's elements has ended; lanes whose chains
 // have ended idle through them
-template <int E>
-__device__ __forceinline__ void htm_rounds(Stage& st, const PairsOut& out, const HtmTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E])
+template <int K, int E>
+__device__ __forceinline__ void htm_rounds(Stage& st, const PairsOut& out, const HtmTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
+                                           const bool (&valid)[E])
 {
     ChainWalk c[E];
+    ChainKind k[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         c[e].key = (uint32_t)sk[e]; c[e].sRow = (uint32_t)row[e]; c[e].m = 0; c[e].r0 = c[e].r1 = c[e].r2 = 0;
         const uint64_t slot = (uint64_t)((c[e].key / 3u) & T.bucketMask) << 2;
         const bool ok = (sk[e] >> 32) == 0 && sk[e] != 0 && slot >= T.defLo && slot + 3 < T.defHi;      // else: equals no stored tuple
         c[e].p = ok ? reinterpret_cast<const ulonglong2*>(T.table + slot) : nullptr;
+        k[e] = ChainKind{false, !valid[e], 0u};
     }
     bool any;
     do {
         uint32_t m = 0;
         bool more = false;
 #pragma unroll
-        for (int e = 0; e < E; ++e) { chain_step(c[e], T.overflow); m += c[e].m; more = more || c[e].p != nullptr; }
-        uint32_t pos = stage_reserve(st, out, m, more, any);
+        for (int e = 0; e < E; ++e) {
+            chain_step(c[e], T.overflow);
+            if constexpr (K == kInner) m += c[e].m;
+            else { chain_rows<K>(c[e], k[e], st); m += k[e].rows; }
+            more = more || c[e].p != nullptr;
+        }
+        uint32_t pos = stage_reserve<K>(st, out, m, more, any);
 #pragma unroll
-        for (int e = 0; e < E; ++e) chain_emit(st, pos, c[e]);
+        for (int e = 0; e < E; ++e) chain_emit<K>(st, pos, c[e], k[e]);
     } while (any);
 }
 
@@ -324,14 +406,15 @@ static_assert(2 * kHtmVecs * kBlock * 3 <= kStagePairs, "a round must fit an emp
 
 }  // namespace
 
+template <int K>
 __global__ void __launch_bounds__(kBlock)
 k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint32_t bucketMask,
                   const uint64_t* __restrict__ overflow, PairsOut out, Counters* __restrict__ ctr)
 {
     constexpr int V = kHtmVecs;
-    __shared__ uint32_t ldsS[kStagePairs], ldsR[kStagePairs], ldsTot[2 * kWaves];
+    __shared__ uint32_t ldsS[kStagePairs], ldsR[K <= kLeft ? kStagePairs : 1], ldsTot[2 * kWaves];
     __shared__ unsigned long long ldsBase;
-    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull};
+    Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
     // buckets outside the slots the build defined were never written and hold no tuple (hj_device.h, Counters)
     const HtmTable T{table, overflow, bucketMask, ctr->validLo, ctr->validHiEx + 512};
     const SBody b = s_body(S, n);
@@ -343,26 +426,29 @@ k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase,
         u4 nxt[V];
         load_vecs<V>(b, v0 + stride, nxt);
         uint64_t sk[2 * V], row[2 * V];
+        bool valid[2 * V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
             sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
             row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
+            valid[2 * k] = valid[2 * k + 1] = v < b.nv;
         }
-        htm_rounds<2 * V>(st, out, T, sk, row);
+        htm_rounds<K, 2 * V>(st, out, T, sk, row, valid);
 #pragma unroll
         for (int k = 0; k < V; ++k) cur[k] = nxt[k];
     }
     if (blockIdx.x == 0 && (b.head || b.tail < n)) {
         uint64_t sk[2] = {kNoElement, kNoElement};
         const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
+        const bool valid[2] = {threadIdx.x == 0 && b.head != 0, threadIdx.x == 0 && b.tail < n};
         if (threadIdx.x == 0) {
             if (b.head) sk[0] = S[0];
             if (b.tail < n) sk[1] = S[b.tail];
         }
-        htm_rounds<2>(st, out, T, sk, row);
+        htm_rounds<K, 2>(st, out, T, sk, row, valid);
     }
-    stage_finish(st, out, 0u, ctr);
+    stage_finish<K>(st, out, 0u, ctr);
 }
 
 namespace {
@@ -381,17 +467,20 @@ unsigned pairs_grid(uint64_t n, int nCU, int vecs)
 
 uint32_t pairs_max_probe_len() { return kMaxProbeLen; }
 
-void launch_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
+void launch_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
                         uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_probe_pairs, dim3(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1)), dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift,
+    const auto kernel = kind == kLeft ? k_probe_pairs<kLeft> : kind == kSemi ? k_probe_pairs<kSemi> : kind == kAnti ? k_probe_pairs<kAnti> : k_probe_pairs<kInner>;
+    hipLaunchKernelGGL(kernel, dim3(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1)), dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift,
                        probeLen, sc, out, ctr);
 }
 
-void launch_htm_probe_pairs(const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
+void launch_htm_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
                             const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_htm_probe_pairs, dim3(pairs_grid(n, nCU, kHtmVecs)), dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1,
+    const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft> : kind == kSemi ? k_htm_probe_pairs<kSemi> : kind == kAnti ? k_htm_probe_pairs<kAnti>
+                                                                                                                  : k_htm_probe_pairs<kInner>;
+    hipLaunchKernelGGL(kernel, dim3(pairs_grid(n, nCU, kHtmVecs)), dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1,
                        overflow, out, ctr);
 }
 

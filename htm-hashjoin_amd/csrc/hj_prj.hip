@@ -1123,11 +1123,13 @@ __device__ __forceinline__ uint32_t part_keys(const uint32_t* __restrict__ off, 
 // One thread per partition: items of partition p at itemCnt[p] (split over > 1 item) or itemCnt[P + p] (one item), so that
 // one exclusive scan over [0, 2P] numbers the split partitions' items first; itemCnt[2P] = 0 becomes the total.
 // A partition without R tuples or without S tuples has no item. stats[2] / [3]: split partitions, largest S partition.
+// rless (the left-outer and anti joins of hj_prj_pairs.hip): a partition with S tuples has its items also without R tuples,
+// one per kPrjItemS S tuples as ever, so the list stays within P + slice / kPrjItemS items.
 __global__ void __launch_bounds__(kBlock)
 k_prj_items_count(const uint32_t* __restrict__ offR, const uint32_t* __restrict__ cntR, uint32_t log2CR,
                   const uint32_t* __restrict__ offS, const uint32_t* __restrict__ cntS, uint32_t log2CS,
                   uint32_t nParts, const Counters* __restrict__ ctr, uint32_t* __restrict__ itemCnt,
-                  unsigned long long* __restrict__ stats)
+                  unsigned long long* __restrict__ stats, bool rless)
 {
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     const bool rFrag = cntR != nullptr && ctr->prjFallbackR == 0;      // the layout each relation's passes ended in
@@ -1136,7 +1138,7 @@ k_prj_items_count(const uint32_t* __restrict__ offR, const uint32_t* __restrict_
     if (p < nParts) {
         const uint32_t nR = part_keys(offR, rFrag ? cntR : nullptr, log2CR, p);
         nS = part_keys(offS, sFrag ? cntS : nullptr, log2CS, p);
-        const uint32_t items = (nR && nS) ? (nS - 1) / kPrjItemS + 1 : 0u;
+        const uint32_t items = ((nR || rless) && nS) ? (nS - 1) / kPrjItemS + 1 : 0u;
         split = items > 1 ? 1u : 0u;
         itemCnt[p] = split ? items : 0u;
         itemCnt[nParts + p] = split ? 0u : items;
@@ -1536,12 +1538,13 @@ void enqueue_prj_join(const PrjPlan& pl, const PartView& vr, const PartView& vs,
 // The work items of a probe against the resident R (no host round trip): items per partition, one scan, fill.
 // cntR / cntS: the fragment counts of a relation whose plan was optimistic, else nullptr.
 hipError_t enqueue_prj_items(const PrjResident& res, const uint32_t* offR, const uint32_t* cntR, uint32_t log2CR,
-                             const uint32_t* offS, const uint32_t* cntS, uint32_t log2CS, uint32_t P, Counters* ctr, hipStream_t s)
+                             const uint32_t* offS, const uint32_t* cntS, uint32_t log2CS, uint32_t P, Counters* ctr, hipStream_t s,
+                             bool rless = false)
 {
     hipError_t e;
     if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_prj_items_count, dim3((P + kBlock) / kBlock), dim3(kBlock), 0, s, offR, cntR, log2CR,
-                       offS, cntS, log2CS, P, ctr, res.itemCnt, res.stats);
+                       offS, cntS, log2CS, P, ctr, res.itemCnt, res.stats, rless);
     if ((e = launch_exclusive_scan_u32(res.itemCnt, 2ull * P + 1, res.scanSums, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
     return hipGetLastError();

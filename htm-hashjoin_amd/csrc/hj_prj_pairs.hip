@@ -16,6 +16,14 @@
 // Pair output as in hj_pairs.hip (flush_plane, hj_device.h): pairs are staged in LDS, a full stage claims its run of the two output planes with ONE
 // 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
 // LDS: table 15360 slots x (4 B key + 4 B row) = 120 KiB, stage 4096 pairs x 8 B = 32 KiB, 152 KiB of the CU's 160.
+//
+// Join kinds (hj_prj_probe_join_dev): the kind K is a template parameter of k_prj_join_pairs; K = INNER is the kernel as it
+// was. An item's S range is probed once per LDS build of its R partition, so "has matched" must survive the block loop:
+// a thread meets the same <= kPrjItemS / kJoinThreads = 64 S elements in every block, and one 64-bit register holds their
+// flags. LEFT writes the inner pairs per block and the (S row, kNoRow) row in the LAST block for flags still clear; SEMI
+// the S row in the first block that matches it; ANTI the S row in the last block. A padding lane holds a clamped COPY of
+// the item's last element (load_s): j < nSi gates every row of these kinds, not only the walk. LEFT and ANTI also take
+// items of partitions without R tuples (k_prj_items_count, rless): no build, every element unmatched.
 
 namespace hj {
 
@@ -28,6 +36,9 @@ constexpr size_t kPairLdsBytes = sizeof(uint32_t) * (2 * kPairSlots + 2 * kPairS
 static_assert(kPairLdsBytes + 1024 <= 160 * 1024, "table, stage and the few static words must fit one CU's LDS");
 static_assert(kPairBlockTuples * 4 <= kPairSlots * 3, "a probe's walk ends at an empty slot: the table is never full");
 static_assert((uint32_t)kPairElems * kJoinThreads <= kPairStage, "a round of single matches fits an empty stage");
+static_assert(kPrjItemS / kJoinThreads <= 64, "the matched flags of a thread's S elements of one item fit one 64-bit register");
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;          // HJ_NO_ROW
+constexpr int kInner = 0, kLeft = 1, kSemi = 2, kAnti = 3;          // hj_join_kind
 
 // Slot of key-remainder k: the Fibonacci hash of join_hash, scaled to a slot count that is no power of two
 __device__ __forceinline__ uint32_t pair_hash(uint32_t k) { return __umulhi(k * 0x9E3779B1u, kPairSlots); }
@@ -52,6 +63,8 @@ k_prj_rows_checksum(const uint2* __restrict__ partR, const uint32_t* __restrict_
 // items[0 .. *nItemsAt) taken through *ticket (zeroed by the host), as in k_prj_probe_items; both relations in the exact
 // layout: partition pid = part[off[pid] .. off[pid + 1]), elements {x = key, y = row}. The arrays are separate __restrict__
 // parameters (k_prj_join: members of a struct became vector loads), and what an item reads is looked up before its LDS work.
+// K: hj_join_kind. cursor[1]: LEFT's unmatched S elements.
+template <int K>
 __global__ void __launch_bounds__(kJoinThreads)
 k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ offR,
                  const uint2* __restrict__ partS, const uint32_t* __restrict__ offS,
@@ -72,6 +85,9 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t fill = 0, round = 0;                      // the same in every thread
     unsigned long long found = 0;                      // pairs of this workgroup (the same in every thread)
+    constexpr bool kRless = K == kLeft || K == kAnti;  // items of partitions without R tuples are in the list
+    unsigned long long inner = 0;                      // kinds other than INNER, per thread: inner matches of its elements
+    uint32_t unmatched = 0;                            // LEFT, per thread: its elements without a match
 
     // everything staged -> its run of the output. Called by all threads together.
     auto flush = [&]() {
@@ -79,7 +95,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
         __syncthreads();                               // the base is there, and so is every pair of the rounds before
         const uint64_t base = sBase;
         flush_plane<kJoinThreads>(stS, fill, outS, base, capacity);
-        flush_plane<kJoinThreads>(stR, fill, outR, base, capacity);
+        if constexpr (K <= kLeft) flush_plane<kJoinThreads>(stR, fill, outR, base, capacity);
         __syncthreads();                               // nobody refills the stage (or claims again) while it is being read
         fill = 0;
     };
@@ -92,14 +108,20 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
             for (;;) {
                 const uint32_t v = tabK[h];
                 if (v == kEmpty32) break;
-                if (v == k) { if (m == 0) first = tabR[h]; ++m; }
+                if (v == k) {
+                    if constexpr (K <= kLeft) { if (m == 0) first = tabR[h]; }       // SEMI and ANTI never read the row plane
+                    ++m;
+                }
                 h = pair_next(h);
             }
         }
         return m;
     };
     // put(S row, R row) for each of the m matches: the first from the register, further ones (duplicate keys in R) by a second walk
-    auto emit = [&](uint2 e, uint32_t m, uint32_t first, auto&& put) {
+    // rows: the element's rows of the kind in this block (INNER: m); LEFT's unmatched row is rows > m
+    auto emit = [&](uint2 e, uint32_t m, uint32_t first, uint32_t rows, auto&& put) {
+        if constexpr (K >= kSemi) { if (rows) put(e.y, 0u); return; }
+        if constexpr (K == kLeft) if (rows > m) put(e.y, kNoRow);
         if (m == 0) return;
         put(e.y, first);
         if (m == 1) return;
@@ -118,7 +140,8 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
         __syncthreads();
         const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)sNext);
         if (cur >= nItems) break;                      // workgroup-uniform
-        // (sNext is written again only behind the barriers of this item: an item has R tuples, hence at least one build)
+        // (sNext is written again only behind the barriers of this item: every item runs the block loop at least once, and
+        // a pass through it ends at a barrier whether it built a table or, for an item without R tuples, did not)
         const uint2 it = items[cur];
         const uint32_t rb = offR[it.x], nRp = offR[it.x + 1] - rb;
         const uint32_t sb0 = offS[it.x], lo = it.y * kPrjItemS, rest = offS[it.x + 1] - sb0 - lo;
@@ -131,31 +154,50 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
             }
         };
         // an R partition larger than one table: several builds, the item's S probed against each
-        for (uint32_t blk = 0; blk < nRp; blk += kPairBlockTuples) {
+        unsigned long long seen = 0;                   // bit (round * kPairElems + u): that S element matched in some block
+        // (an item without R tuples -- kRless only -- takes one pass without a build: every valid element is unmatched)
+        for (uint32_t blk = 0; blk < nRp || (kRless && blk == 0); blk += kPairBlockTuples) {
             const uint32_t bn = nRp - blk > kPairBlockTuples ? kPairBlockTuples : nRp - blk;
+            const bool last = nRp - blk <= kPairBlockTuples;           // (nRp == 0: the only pass is the last)
+            const bool built = !kRless || nRp != 0;                    // workgroup-uniform
             uint2 nxt[kPairElems];
             load_s(0u, nxt);                                           // in flight while the table is built
-            for (uint32_t i = threadIdx.x; i < kPairSlots; i += kJoinThreads) tabK[i] = kEmpty32;
-            __syncthreads();
-            for_run(partR, rb + blk, 0u, bn, [&](uint2 e) {
-                const uint32_t k = e.x >> radixBits;
-                uint32_t h = pair_hash(k);
-                while (atomicCAS(&tabK[h], kEmpty32, k) != kEmpty32) h = pair_next(h);    // an equal key is one more entry
-                tabR[h] = e.y;
-            });
-            __syncthreads();
+            if (built) {
+                for (uint32_t i = threadIdx.x; i < kPairSlots; i += kJoinThreads) tabK[i] = kEmpty32;
+                __syncthreads();
+                for_run(partR, rb + blk, 0u, bn, [&](uint2 e) {
+                    const uint32_t k = e.x >> radixBits;
+                    uint32_t h = pair_hash(k);
+                    while (atomicCAS(&tabK[h], kEmpty32, k) != kEmpty32) h = pair_next(h);    // an equal key is one more entry
+                    tabR[h] = e.y;
+                });
+                __syncthreads();
+            }
             // rounds of kPairElems S elements per thread; every thread runs the same number of them (they meet at barriers)
             for (uint32_t j0 = 0; j0 < nSi; j0 += kPairElems * kJoinThreads) {
                 uint2 e[kPairElems];
 #pragma unroll
                 for (int u = 0; u < kPairElems; ++u) e[u] = nxt[u];
                 load_s(j0 + kPairElems * kJoinThreads < nSi ? j0 + kPairElems * kJoinThreads : j0, nxt);
-                uint32_t m[kPairElems], first[kPairElems], mine = 0;
+                uint32_t m[kPairElems], first[kPairElems], rows[kPairElems], mine = 0;
 #pragma unroll
                 for (int u = 0; u < kPairElems; ++u) {
                     first[u] = 0;
-                    m[u] = walk(e[u].x, j0 + (uint32_t)u * kJoinThreads + threadIdx.x < nSi, first[u]);
-                    mine += m[u];
+                    const bool valid = j0 + (uint32_t)u * kJoinThreads + threadIdx.x < nSi;
+                    m[u] = walk(e[u].x, valid && built, first[u]);
+                    if constexpr (K == kInner) {
+                        rows[u] = m[u];
+                    } else {
+                        // the element's flag; a padding lane (a clamped copy of the last element) writes no row of any kind
+                        const unsigned long long bit = 1ull << (j0 / kJoinThreads + (uint32_t)u);
+                        const bool none = valid && last && m[u] == 0 && !(seen & bit);
+                        inner += m[u];
+                        if constexpr (K == kLeft) { rows[u] = m[u] + (uint32_t)none; unmatched += (uint32_t)none; }
+                        if constexpr (K == kSemi) rows[u] = (uint32_t)(m[u] != 0 && !(seen & bit));
+                        if constexpr (K == kAnti) rows[u] = (uint32_t)none;
+                        if (m[u]) seen |= bit;
+                    }
+                    mine += rows[u];
                 }
                 // the round's pair count: wavefront scan, the totals exchanged through LDS, one barrier
                 uint32_t inc = mine;
@@ -175,7 +217,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
                     tot += c;
                 }
                 round += 1;
-                const uint32_t before = wbase + inc - mine;            // pairs of the round in front of this lane's
+                const uint32_t before = wbase + inc - mine;            // rows of the round in front of this lane's (the kind's rows)
                 if (tot > kPairStage) {
                     // Duplicate keys on both sides: more pairs than a stage holds (one S tuple alone can match a whole
                     // table). The round claims its run itself and every lane writes its pairs straight to the planes.
@@ -185,17 +227,24 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
                     // (sBase is written again only behind the next round's barrier)
                     uint64_t g = sBase + before;
                     auto put = [&](uint32_t s, uint32_t r) {
-                        if (g < capacity) { outS[g] = s; outR[g] = r; }
+                        if (g < capacity) {
+                            outS[g] = s;
+                            if constexpr (K <= kLeft) outR[g] = r;
+                        }
                         ++g;
                     };
 #pragma unroll
-                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], put);
+                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], rows[u], put);
                 } else {
                     if (fill + tot > kPairStage) flush();              // workgroup-uniform
                     uint32_t pos = fill + before;
-                    auto put = [&](uint32_t s, uint32_t r) { stS[pos] = s; stR[pos] = r; ++pos; };
+                    auto put = [&](uint32_t s, uint32_t r) {
+                        stS[pos] = s;
+                        if constexpr (K <= kLeft) stR[pos] = r;
+                        ++pos;
+                    };
 #pragma unroll
-                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], put);
+                    for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], rows[u], put);
                     fill += tot;
                 }
                 found += tot;
@@ -204,13 +253,30 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
         }
     }
     if (fill) flush();
-    if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr)->prjMatches, found);
+    if constexpr (K == kInner) {
+        if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr)->prjMatches, found);
+    } else {
+        // the rows are not the matches: the counter takes the inner matches, LEFT's unmatched elements go behind the cursor
+        unsigned long long un = unmatched;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            inner += __shfl_down(inner, off, 64);
+            un += __shfl_down(un, off, 64);
+        }
+        if (lane == 0 && inner) atomicAdd(&counter_shard(ctr)->prjMatches, inner);
+        if (K == kLeft && lane == 0 && un) atomicAdd(cursor + 1, un);
+    }
 }
 
 static hipError_t prj_pairs_set_attributes()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_join_pairs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kPairLdsBytes);
+    const void* const kernels[4] = {reinterpret_cast<const void*>(k_prj_join_pairs<kInner>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft>),
+                                    reinterpret_cast<const void*>(k_prj_join_pairs<kSemi>), reinterpret_cast<const void*>(k_prj_join_pairs<kAnti>)};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // R's row-id passes into buf.partR / res.offR (plan: exact passes only), then R's checksum
@@ -230,8 +296,8 @@ hipError_t launch_prj_build_rows(const PrjPlan& pl, const PrjBuffers& buf, const
 }
 
 // S's row-id passes into buf.partS (rows from sIdxBase), the work-item list, k_prj_join_pairs against the resident R.
-// out.cursor is zeroed here; out.capacity 0 counts only.
-hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+// out.cursor and the word behind it are zeroed here; out.capacity 0 counts only. kind: hj_join_kind.
+hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
                                  const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
                                  hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s)
 {
@@ -242,10 +308,14 @@ hipError_t launch_prj_probe_rows(const PrjPlan& planR, const PrjPlan& planS, con
     if (evPartDone && (e = hipEventRecord(evPartDone, s)) != hipSuccess) return e;
     // the work items of the counting probe: the exact layout's offsets are the same whatever the element width
     const uint32_t P = 1u << planR.radixBits;
-    if ((e = hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
-    if ((e = enqueue_prj_items(res, res.offR, nullptr, 0u, w.offS, nullptr, 0u, P, ctr, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+    // LEFT and ANTI: the S tuples of a partition without R tuples are rows too, so such a partition gets its items
+    const bool rless = kind == (uint32_t)kLeft || kind == (uint32_t)kAnti;
+    if ((e = enqueue_prj_items(res, res.offR, nullptr, 0u, w.offS, nullptr, 0u, P, ctr, s, rless)) != hipSuccess) return e;
     if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_prj_join_pairs, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
+    const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft> : kind == (uint32_t)kSemi ? k_prj_join_pairs<kSemi>
+                      : kind == (uint32_t)kAnti ? k_prj_join_pairs<kAnti> : k_prj_join_pairs<kInner>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
                        reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
                        res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor, ctr);
     return hipGetLastError();

@@ -23,6 +23,9 @@ from ._lib import lib, hj_params, hj_result
 # struct Bucket, HTMHashBuild.hpp:41-45 (32 bytes)
 BUCKET_DTYPE = np.dtype([("tuples", np.uint64, 3), ("count", np.uint32), ("nextIndex", np.uint32)])
 
+# HJ_NO_ROW: the R row of a left-outer row whose S tuple has no match
+NO_ROW = _lib.HJ_NO_ROW
+
 
 class HashJoinError(RuntimeError):
     def __init__(self, status, detail=""):
@@ -129,18 +132,21 @@ class HashJoinContext:
     def probe(self, dS_ptr, sSize):
         self._check(lib.hj_probe_dev(self._h, C.c_void_p(dS_ptr), sSize))
 
-    def probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0):
-        """hj_probe_pairs_dev: the probe with its result kept. For every match the probe counts, one pair
+    def probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0, kind=0):
+        """hj_probe_join_dev: the probe with its result kept. For every match the probe counts, one pair
         d_out_s[k] = s_idx_base + position in dS, d_out_r[k] = global input index of the matching R tuple (two device
         uint32 arrays of `capacity` entries; pairs beyond it are counted, not written). Open addressing needs
-        reserve(..., keepRowIds=True). Adds to totalMatches and sSize like probe()."""
-        self._check(lib.hj_probe_pairs_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
-                                           C.c_void_p(d_out_s) if d_out_s else None,
-                                           C.c_void_p(d_out_r) if d_out_r else None, capacity))
+        reserve(..., keepRowIds=True). Adds to totalMatches and sSize like probe().
+        kind (HJ_JOIN_*): 0 inner (the above), 1 left outer (an S tuple without a match gives one row with R row NO_ROW),
+        2 semi / 3 anti (one S row per tuple with / without a match; d_out_r is ignored and may be 0). totalMatches
+        grows by the inner matches whatever the kind."""
+        self._check(lib.hj_probe_join_dev(self._h, kind, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
+                                          C.c_void_p(d_out_s) if d_out_s else None,
+                                          C.c_void_p(d_out_r) if d_out_r else None, capacity))
 
     def pairs_info(self):
-        """hj_pairs_info (waits for the stream): (pairs the last probe_pairs found, pairs it wrote, its device time in
-        microseconds, 0)."""
+        """hj_pairs_info (waits for the stream): (rows the last probe_pairs / prj_probe_pairs found, rows it wrote, its
+        device time in microseconds, its S tuples without a match for a kind other than inner -- 0 after an inner call)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_pairs_info(self._h, out))
         return tuple(int(x) for x in out)
@@ -159,14 +165,15 @@ class HashJoinContext:
         """Partitions one S slice and joins it against the resident R; totalMatches and sSize add up over the slices."""
         self._check(lib.hj_prj_probe_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize))
 
-    def prj_probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0):
-        """hj_prj_probe_pairs_dev: prj_probe with its result kept, against an R built after reserve("prj" or "auto", ...,
+    def prj_probe_pairs(self, dS_ptr, sSize, d_out_s, d_out_r, capacity, s_idx_base=0, kind=0):
+        """hj_prj_probe_join_dev: prj_probe with its result kept, against an R built after reserve("prj" or "auto", ...,
         keepRowIds=True). For every match one pair d_out_s[k] = s_idx_base + position in dS, d_out_r[k] = position of
         the R tuple in the relation given to prj_build (two device uint32 arrays of `capacity` entries; pairs beyond it
-        are counted, not written). The complete equi-join on the key word. pairs_info() reports the call."""
-        self._check(lib.hj_prj_probe_pairs_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
-                                               C.c_void_p(d_out_s) if d_out_s else None,
-                                               C.c_void_p(d_out_r) if d_out_r else None, capacity))
+        are counted, not written). The complete equi-join on the key word. pairs_info() reports the call.
+        kind (HJ_JOIN_*): as in probe_pairs."""
+        self._check(lib.hj_prj_probe_join_dev(self._h, kind, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, s_idx_base,
+                                              C.c_void_p(d_out_s) if d_out_s else None,
+                                              C.c_void_p(d_out_r) if d_out_r else None, capacity))
 
     def prj_resident_info(self):
         """hj_prj_resident_info (waits for the stream): R's and the last slice's partitioning path, the last probe's join
@@ -310,21 +317,41 @@ def HTMHashBuild(relR, rSize, relS=None, sSize=0, transactionSize=16, scaleOutpu
     return out
 
 
-def join_pairs(relR, relS, algo="htm", probeLength=4, device=0):
+def _join_kind(fn, how):
+    if how not in _lib.JOIN_KINDS:
+        raise ValueError(f"{fn}: how must be inner, left, semi or anti, not {how!r}")
+    return _lib.JOIN_KINDS[how]
+
+
+def _join_without_device(kind, n_r, n_s):
+    """the gather maps of a join with an empty side (None: the inputs need the device): no S, no rows; no R, every S row
+    is unmatched"""
+    if n_r and n_s:
+        return None
+    keeps = n_s if kind in (_lib.HJ_JOIN_LEFT, _lib.HJ_JOIN_ANTI) else 0
+    s_idx = np.arange(keeps, dtype=np.uint32)
+    return s_idx, (np.full(keeps, NO_ROW, dtype=np.uint32) if kind <= _lib.HJ_JOIN_LEFT else None)
+
+
+def join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="inner"):
     """The join as two gather maps: (s_idx, r_idx), numpy uint32 arrays of equal length, row k of the result being
     (relS[s_idx[k]], relR[r_idx[k]]). The order of the rows is unspecified. algo = "htm" (the default): the complete
     equi-join, duplicate keys included, any len(relR). "atomic" / "nocc": the reference's budgeted open-addressing
     semantics (an R tuple that ran out of probeLength is not in the table, a walk ends at the first empty slot;
     len(relR) a power of two).
     Sizing: the outputs start with len(relS) entries each (exact for a foreign-key join); if the probe reports more
-    pairs than that, they are enlarged to the reported count and the probe runs once more."""
+    pairs than that, they are enlarged to the reported count and the probe runs once more.
+    how = "inner" | "left" | "semi" | "anti", relS being the preserved side: "left" adds one row (s, NO_ROW) for every S
+    tuple without a match; "semi" / "anti" return the S rows with / without a match, once each, and r_idx is None."""
     if algo not in ("htm", "atomic", "nocc"):
         raise ValueError(f"join_pairs: algo must be htm, atomic or nocc, not {algo!r}")
+    kind = _join_kind("join_pairs", how)
     relR = np.ascontiguousarray(relR, dtype=np.uint64)
     relS = np.ascontiguousarray(relS, dtype=np.uint64)
-    empty = np.empty(0, dtype=np.uint32)
-    if relR.size == 0 or relS.size == 0:
-        return empty, empty.copy()
+    trivial = _join_without_device(kind, relR.size, relS.size)
+    if trivial is not None:
+        return trivial
+    plane_r = kind <= _lib.HJ_JOIN_LEFT
     with HashJoinContext(device) as ctx:
         held = []
 
@@ -340,35 +367,39 @@ def join_pairs(relR, relS, algo="htm", probeLength=4, device=0):
             ctx.build(dR, relR.size)
             capacity = relS.size
             while True:
-                d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
-                ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity)
+                d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
+                ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity, kind=kind)
                 found, written = ctx.pairs_info()[:2]
                 if found <= capacity:
                     break
                 capacity = found
             ctx.fetch()             # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
-            s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
+            s_idx, r_idx = np.empty(written, dtype=np.uint32), (np.empty(written, dtype=np.uint32) if plane_r else None)
             if written:
                 ctx.copy_d2h(s_idx, d_s)
-                ctx.copy_d2h(r_idx, d_r)
+                if plane_r:
+                    ctx.copy_d2h(r_idx, d_r)
         finally:
             for p in held:
                 ctx.dev_free(p)
     return s_idx, r_idx
 
 
-def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0):
+def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="inner"):
     """The complete equi-join on the key word (the low 32 bits of a tuple) through the resident radix join, as two gather
     maps like join_pairs: (s_idx, r_idx), numpy uint32 arrays, row k of the result being (relS[s_idx[k]], relR[r_idx[k]]),
     in no particular order. The path for a scattered or skewed relS. R is partitioned once with its row ids; relS is
     probed in slices of slice_tuples (default: all of it at once).
     Sizing, per slice, as in join_pairs: the outputs start with one entry per S tuple of the slice; if the probe reports
-    more pairs than that, they are enlarged to the reported count and the slice is probed once more."""
+    more pairs than that, they are enlarged to the reported count and the slice is probed once more.
+    how: as in join_pairs (r_idx is None for "semi" and "anti", and carries NO_ROW in the unmatched rows of "left")."""
+    kind = _join_kind("radix_join_pairs", how)
     relR = np.ascontiguousarray(relR, dtype=np.uint64)
     relS = np.ascontiguousarray(relS, dtype=np.uint64)
-    empty = np.empty(0, dtype=np.uint32)
-    if relR.size == 0 or relS.size == 0:
-        return empty, empty.copy()
+    trivial = _join_without_device(kind, relR.size, relS.size)
+    if trivial is not None:
+        return trivial
+    plane_r = kind <= _lib.HJ_JOIN_LEFT
     step = relS.size if not slice_tuples else min(int(slice_tuples), relS.size)
     if step < 1:
         raise ValueError(f"radix_join_pairs: slice_tuples must be positive, not {slice_tuples!r}")
@@ -386,27 +417,28 @@ def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0):
             ctx.copy_h2d(dR, relR)
             ctx.prj_build(dR, relR.size)
             capacity = step
-            d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+            d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
             for lo in range(0, relS.size, step):
                 part = relS[lo:lo + step]
                 ctx.copy_h2d(dS, part)
-                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo)
+                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
                 found, written = ctx.pairs_info()[:2]
                 if found > capacity:
                     capacity = found
-                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
-                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo)
+                    d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
+                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
                     found, written = ctx.pairs_info()[:2]
                 s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
                 if written:
                     ctx.copy_d2h(s_idx, d_s)
-                    ctx.copy_d2h(r_idx, d_r)
+                    if plane_r:
+                        ctx.copy_d2h(r_idx, d_r)
                 parts_s.append(s_idx)
                 parts_r.append(r_idx)
         finally:
             for p in held:
                 ctx.dev_free(p)
-    return np.concatenate(parts_s), np.concatenate(parts_r)
+    return np.concatenate(parts_s), (np.concatenate(parts_r) if plane_r else None)
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

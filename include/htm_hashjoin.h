@@ -213,8 +213,31 @@ int hj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
  * HJ_ERR_INVALID: an output pointer NULL with capacity > 0, or sIdxBase + sSize > 2^32 - 1. sSize 0 is a no-op. */
 int hj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
                        uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
-/* Waits for the stream. out[0] = pairs the last hj_probe_pairs_dev / hj_prj_probe_pairs_dev found, out[1] = pairs it wrote
- * (= min(out[0], capacity)), out[2] = its device time in microseconds (rounded), out[3] = 0. */
+/* The join kinds of the materialising probes. S, the probe side, is the preserved side; a "match" is exactly what the
+ * pairs probe of that path emits (above: the walk, the bucket plus its chain, or, for the radix join, the complete
+ * equi-join on the key word). An S tuple is unmatched when that probe emits no pair for it -- on the table paths this
+ * includes tuples outside the DataGen layout and tuples whose home lies outside the slots the build defined.
+ *   HJ_JOIN_INNER  one row per match                                                   planes S, R
+ *   HJ_JOIN_LEFT   one row per match; for a tuple without one, one row with R row = HJ_NO_ROW   planes S, R
+ *   HJ_JOIN_SEMI   one row for a tuple with at least one match, however many            plane S only
+ *   HJ_JOIN_ANTI   one row for a tuple without a match                                  plane S only
+ * R-preserving kinds (right / full outer) are not offered. */
+typedef enum { HJ_JOIN_INNER = 0, HJ_JOIN_LEFT = 1, HJ_JOIN_SEMI = 2, HJ_JOIN_ANTI = 3 } hj_join_kind;
+/* The R row of an HJ_JOIN_LEFT row whose S tuple has no match. No real row takes the value: S rows stay below it by the
+ * check on sIdxBase + sSize, R rows by the builds' own checks (idxBase + rSize <= 2^32 - 1; PRJ: rSize < 2^32 - 1). */
+#define HJ_NO_ROW 0xFFFFFFFFu
+/* hj_probe_pairs_dev for any join kind (hj_probe_pairs_dev is its HJ_JOIN_INNER case). Same preconditions, same errors,
+ * same output contract with "row" for "pair": the planes fill from 0 without holes on every call, rows at or beyond
+ * `capacity` are counted and not written, the order is unspecified, the multiset is exact. For HJ_JOIN_SEMI / ANTI
+ * dOutR is ignored: it may be NULL with capacity > 0 and is never written. totalMatches and sSize grow exactly as under
+ * hj_probe_dev -- by the INNER matches, whatever the kind -- so a context ends with the same hj_result as one driven
+ * through the counting probe. HJ_ERR_INVALID also for kind > 3. Asynchronous. */
+int hj_probe_join_dev(hj_ctx *ctx, uint32_t kind, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
+                      uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
+/* Waits for the stream. About the last hj_probe_pairs_dev / hj_probe_join_dev / hj_prj_probe_pairs_dev /
+ * hj_prj_probe_join_dev: out[0] = rows it produced, out[1] = rows it wrote (= min(out[0], capacity)), out[2] = its device
+ * time in microseconds (rounded), out[3] = S tuples of the call without a match for a kind other than HJ_JOIN_INNER
+ * (0 after an INNER call). */
 int hj_pairs_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
@@ -242,9 +265,16 @@ int hj_prj_probe_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize);
  * HJ_ERR_INVALID: an output pointer NULL with capacity > 0, or sIdxBase + sSize > 2^32 - 1. sSize 0 is a no-op. */
 int hj_prj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
                            uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
+/* hj_prj_probe_pairs_dev for any hj_join_kind (hj_prj_probe_pairs_dev is its HJ_JOIN_INNER case), as hj_probe_join_dev is
+ * for the table probes: the same rows per S tuple, dOutR ignored and never written for HJ_JOIN_SEMI / ANTI, totalMatches
+ * and sSize growing as under hj_prj_probe_dev whatever the kind, HJ_ERR_INVALID also for kind > 3. Under HJ_JOIN_LEFT and
+ * HJ_JOIN_ANTI the S tuples of a partition that holds no R tuple are rows as well. Asynchronous. */
+int hj_prj_probe_join_dev(hj_ctx *ctx, uint32_t kind, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
+                          uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
 /* Host-visible facts about the resident build and the last probe (waits for the stream), out[8]:
  * [0] R's path (0 exact, 1 histogram-free, 2 fell back), [1] last probe's S path (same coding),
- * [2] join work items of the last probe, [3] partitions whose S side was split over > 1 item,
+ * [2] join work items of the last probe (after an HJ_JOIN_LEFT / HJ_JOIN_ANTI call they include the items of partitions
+ * with S tuples and no R tuple; unchanged for every other call), [3] partitions whose S side was split over > 1 item,
  * [4] largest S partition of the last probe, [5] resident bytes held for R, [6..7] reserved (0). */
 int hj_prj_resident_info(hj_ctx *ctx, uint64_t out[8]);
 /* Build + probe of dR x dS by whatever hj_reserve was given: HJ_ALGO_NOCC/ATOMIC/HTM = hj_build_dev(idxBase 0) then

@@ -2,7 +2,7 @@
 """Times the materialising probe against the counting probe on the same table and the same S, through the C ABI, no
 torch: development tool.
 
-    python tools/pairs_bench.py [--log2n 27] [--reps 10] [--counting-only]
+    python tools/pairs_bench.py [--log2n 27] [--reps 10] [--counting-only] [--how left,semi,anti] [--absent-half]
 
 One context, |R| = |S| = 2^log2n, R = local_shuffle W=16. Per configuration one JSON line with the median HIP-event
 times over `reps` launches after one warm-up launch of
@@ -12,6 +12,10 @@ Configurations: atomic (HJ_FLAG_KEEP_ROW_IDS) x sorted S and htm x sorted S (eve
 write-heaviest unique-key case), htm x Zipf(0.9) S.
 claims = output runs claimed from the cursor per launch, from the kernel's geometry: a workgroup claims when its LDS stage
 of 4096 pairs cannot take the next round, and once more at its end (pairs / 4096 + workgroups when every round is full).
+--how: after (b), the same launches through hj_probe_join_dev for each listed join kind -> <kind>_us, <kind>_rows and
+<kind>_ratio = its median / (b)'s, (b) being the INNER join of the same process and input; (b) itself always goes through
+hj_probe_pairs_dev, the entry point older checkouts have. --absent-half: every second tuple of the sorted S gets a key
+above R's (n + its key), so half of S is unmatched.
 --counting-only runs (a) alone and uses nothing newer than hj_probe_dev (the 8-byte table is then asked for with
 buildVariant 3): the same script times the yardstick on a checkout that has no materialising probe."""
 import argparse
@@ -24,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 import htm_hashjoin_amd as hj  # noqa: E402
+from htm_hashjoin_amd import _lib  # noqa: E402
 
 STAGE_PAIRS, WORKGROUPS = 4096, 256 * 4
 
@@ -35,14 +40,21 @@ def main():
     ap.add_argument("--theta", type=float, default=0.9)
     ap.add_argument("--counting-only", action="store_true")
     ap.add_argument("--tag", default="")
+    ap.add_argument("--how", default="", help="comma list of left, semi, anti")
+    ap.add_argument("--absent-half", action="store_true")
     a = ap.parse_args()
     n = 1 << a.log2n
+    kinds = [k for k in a.how.split(",") if k]
     with hj.HashJoinContext(0) as c:
         dR, dS, dZ = c.dev_alloc(n * 8), c.dev_alloc(n * 8), c.dev_alloc(n * 8)
         R = hj.generate_data("local_shuffle", n, n, 16)
         c.copy_h2d(dR, R)
         del R
-        c.copy_h2d(dS, np.arange(1, n + 1, dtype=np.uint64))
+        S = np.arange(1, n + 1, dtype=np.uint64)
+        if a.absent_half:
+            S[1::2] += np.uint64(n)
+        c.copy_h2d(dS, S)
+        del S
         c.zipf_open(n, a.theta, 54321)
         c.zipf_next(n, dZ)
         c.zipf_close()
@@ -72,13 +84,31 @@ def main():
                 dOutS, dOutR = c.dev_alloc(4 * pairs + 16), c.dev_alloc(4 * pairs + 16)
                 pairs_us = []
                 for _ in range(a.reps + 1):
-                    c.probe_pairs(dProbe, n, dOutS, dOutR, pairs)
+                    c._check(hj.lib.hj_probe_pairs_dev(c._h, dProbe, n, 0, dOutS, dOutR, pairs))
                     found, written, us, _ = c.pairs_info()
                     assert found == written == pairs, (found, written, pairs)
                     pairs_us.append(us)
                 c.dev_free(dOutS)
                 c.dev_free(dOutR)
                 med = statistics.median(pairs_us[1:])
+                for how in kinds:
+                    kind = _lib.JOIN_KINDS[how]
+                    c.probe_pairs(dProbe, n, 0, 0, 0, kind=kind)             # capacity 0: the kind's row count
+                    rows = c.pairs_info()[0]
+                    dOutS = c.dev_alloc(4 * rows + 16)
+                    dOutR = c.dev_alloc(4 * rows + 16) if kind <= _lib.HJ_JOIN_LEFT else 0
+                    kind_us = []
+                    for _ in range(a.reps + 1):
+                        c.probe_pairs(dProbe, n, dOutS, dOutR, rows, kind=kind)
+                        found, written, us, _ = c.pairs_info()
+                        assert found == written == rows, (how, found, written, rows)
+                        kind_us.append(us)
+                    c.dev_free(dOutS)
+                    if dOutR:
+                        c.dev_free(dOutR)
+                    kmed = statistics.median(kind_us[1:])
+                    row.update({how + "_rows": rows, how + "_us": kmed, how + "_us_min": min(kind_us[1:]),
+                                how + "_ratio": round(kmed / med, 3)})
                 row.update({"pairs": pairs, "pairs_us": med, "pairs_us_min": min(pairs_us[1:]),
                             "ratio": round(med / row["probe_us"], 3), "out_GBps": round(8.0 * pairs / med / 1e3, 1),
                             "claims": pairs // STAGE_PAIRS + min(WORKGROUPS, (n // 2 + 256) // 256)})

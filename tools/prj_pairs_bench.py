@@ -3,6 +3,7 @@
 development tool.
 
     python tools/prj_pairs_bench.py [--log2n 27] [--reps 10] [--radix-bits 0] [--s sorted,uniform,zipf] [--yardsticks-only]
+                                    [--how left,semi,anti] [--absent-half]
 
 |R| = |S| = 2^log2n, R = the keys 1..n shuffled (unique), so every S tuple matches once. S = sorted, uniform draws, or
 Zipf(theta) over n keys. Per S one JSON line with the median HIP-event times over `reps` launches after one warm-up of
@@ -10,6 +11,10 @@ Zipf(theta) over n keys. Per S one JSON line with the median HIP-event times ove
   (b) htm build + hj_probe_pairs_dev: the only other way to the same pairs    -> htm_pairs_us
   (c) hj_prj_probe_pairs_dev, R resident as {key, row} (HJ_FLAG_KEEP_ROW_IDS) -> pairs_us (pairs_join_us: its join kernel)
 and ratio_a = (c) / (a), ratio_b = (c) / (b), out_GBps = 8 B x pairs / (c), build_us of both resident forms.
+--how: after (c), the same launches through hj_prj_probe_join_dev for each listed join kind -> <kind>_us, <kind>_rows and
+<kind>_ratio = its median / (c)'s, (c) being the INNER join of the same process and input; (c) itself always goes through
+hj_prj_probe_pairs_dev, the entry point older checkouts have. --absent-half: every second tuple of S gets n added to its
+key, which R does not hold, so half of S is unmatched (and (a)'s and (c)'s pair counts halve).
 --yardsticks-only runs (a) and (b) alone and uses nothing newer than hj_prj_probe_dev / hj_probe_pairs_dev: the same
 script times the yardsticks on a checkout that has no materialising radix join."""
 import argparse
@@ -22,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 import htm_hashjoin_amd as hj  # noqa: E402
+from htm_hashjoin_amd import _lib  # noqa: E402
 
 
 def med(xs):
@@ -38,17 +44,24 @@ def main():
     ap.add_argument("--yardsticks-only", action="store_true")
     ap.add_argument("--no-htm", action="store_true", help="skip yardstick (b)")
     ap.add_argument("--tag", default="")
+    ap.add_argument("--how", default="", help="comma list of left, semi, anti")
+    ap.add_argument("--absent-half", action="store_true")
     a = ap.parse_args()
     n = 1 << a.log2n
+    kinds = [k for k in a.how.split(",") if k]
+    want = n // 2 if a.absent_half else n               # pairs per probe
     with hj.HashJoinContext(0) as c:
         dR, dS = c.dev_alloc(n * 8), c.dev_alloc(n * 8)
         c.copy_h2d(dR, hj.generate_data("shuffle", n, n))
         dOutS, dOutR = c.dev_alloc(4 * n + 16), c.dev_alloc(4 * n + 16)
         for sname in a.s.split(","):
-            if sname == "sorted":
-                c.copy_h2d(dS, np.arange(1, n + 1, dtype=np.uint64))
-            elif sname == "uniform":
-                c.copy_h2d(dS, np.random.default_rng(54321).integers(1, n + 1, size=n, dtype=np.uint64))
+            if sname in ("sorted", "uniform"):
+                S = (np.arange(1, n + 1, dtype=np.uint64) if sname == "sorted"
+                     else np.random.default_rng(54321).integers(1, n + 1, size=n, dtype=np.uint64))
+                if a.absent_half:
+                    S[1::2] += np.uint64(n)
+                c.copy_h2d(dS, S)
+                del S
             else:
                 c.zipf_open(n, a.theta, 54321)
                 c.zipf_next(n, dS)
@@ -69,7 +82,7 @@ def main():
                         "count_us": med(us), "count_us_min": round(min(us[1:]), 1), "count_join_us": med(join_us),
                         "count_paths": [info["rPath"], info["sPath"]], "items": info["items"],
                         "maxSPartition": info["maxSPartition"]})
-            assert row["matches_per_probe"] == n, row
+            assert row["matches_per_probe"] == want or sname == "zipf", row
             # (b) the bucketised table's materialising probe
             if not a.no_htm:
                 c.reserve("htm", n, n)
@@ -79,7 +92,7 @@ def main():
                 for _ in range(a.reps + 1):
                     c.probe_pairs(dS, n, dOutS, dOutR, n)
                     found, written, t, _ = c.pairs_info()
-                    assert found == written == n, (found, written)
+                    assert found == written == row["matches_per_probe"], (found, written)
                     us.append(t)
                 row.update({"htm_pairs_us": med(us), "htm_pairs_us_min": min(us[1:])})
             # (c) the materialising radix join
@@ -89,15 +102,25 @@ def main():
                 row["pairs_build_us"] = round(c.fetch()["build_us"], 1)
                 us, join_us = [], []
                 for _ in range(a.reps + 1):
-                    c.prj_probe_pairs(dS, n, dOutS, dOutR, n)
+                    c._check(hj.lib.hj_prj_probe_pairs_dev(c._h, dS, n, 0, dOutS, dOutR, n))
                     found, written, t, _ = c.pairs_info()
-                    assert found == written == n, (found, written)
+                    assert found == written == row["matches_per_probe"], (found, written)
                     us.append(t); join_us.append(c.fetch()["join_us"])
                 row.update({"pairs_us": med(us), "pairs_us_min": min(us[1:]), "pairs_join_us": med(join_us),
                             "ratio_a": round(med(us) / row["count_us"], 3), "out_GBps": round(8.0 * n / med(us) / 1e3, 1),
                             "residentBytes": c.prj_resident_info()["residentBytes"]})
                 if not a.no_htm:
                     row["ratio_b"] = round(med(us) / row["htm_pairs_us"], 3)
+                for how in kinds:                                   # at most n rows each on these inputs: the planes do
+                    kind = _lib.JOIN_KINDS[how]
+                    kus, kjoin = [], []
+                    for _ in range(a.reps + 1):
+                        c.prj_probe_pairs(dS, n, dOutS, dOutR, n, kind=kind)
+                        found, written, t, _ = c.pairs_info()
+                        assert found == written <= n, (how, found, written)
+                        kus.append(t); kjoin.append(c.fetch()["join_us"])
+                    row.update({how + "_rows": found, how + "_us": med(kus), how + "_us_min": min(kus[1:]),
+                                how + "_join_us": med(kjoin), how + "_ratio": round(med(kus) / row["pairs_us"], 3)})
             print(json.dumps(row), flush=True)
         for p in (dR, dS, dOutS, dOutR):
             c.dev_free(p)
