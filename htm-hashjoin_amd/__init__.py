@@ -11,5 +11,5 @@ from ._lib import (  # noqa: F401
 )
 from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
-    generate_data, generate_relation, device_count, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
+    generate_data, generate_relation, device_count, wave_layout_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )

@@ -111,6 +111,8 @@ def _declare(lib):
         "hj_copy_d2h": ([vp, vp, vp, u64], i32),
         "hj_prj_workspace_info": ([u64, u64, u32, P(u64)], i32),
         "hj_prj_fragment_info": ([u64, u64, u32, u32, P(u64)], i32),
+        "hj_wave_layout_info": ([vp, u32, u64, P(u64)], i32),
+        "hj_wave_seams": ([vp, vp, vp, vp, u64, P(u64)], i32),
         "hj_zipf_open": ([vp, u64, C.c_double, C.c_uint], i32),
         "hj_zipf_next_dev": ([vp, u64, vp], i32),
         "hj_zipf_close": ([vp], i32),

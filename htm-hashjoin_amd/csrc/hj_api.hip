@@ -78,6 +78,10 @@ struct hj_ctx {
     int* zipfRawHost[2] = {nullptr, nullptr}; int* zipfRawDev[2] = {nullptr, nullptr}; uint64_t zipfRawCap = 0;
     hipEvent_t zipfDone[2] = {nullptr, nullptr}; int zipfFlip = 0;
     uint32_t variantUsed = 1;
+    // the ring pre-pass of the last build (hj_wave_seams): tuples it cut into chunks (0: it was not enqueued), and whether
+    // it was gated on the variant the device picked
+    uint64_t wavePreN = 0;
+    bool wavePreGated = false;
     uint64_t pairsCapacity = 0;                 // materialising probe (hj_probe_join_dev): the capacity of the last call,
     uint32_t pairsKind = HJ_JOIN_INNER;         // ... its join kind and its sSize (hj_pairs_info)
     uint64_t pairsS = 0;
@@ -193,6 +197,7 @@ int begin_operation(hj_ctx* c, uint64_t rSize, uint64_t sSize, uint64_t tableSiz
     HJ_HIP(c, hipSetDevice(c->device));
     for (bool& b : c->evSet) b = false;
     c->built = c->htmBuilt = c->prjRan = c->resident = false;
+    c->wavePreN = 0;
     c->rSize = rSize; c->sSize = sSize; c->tableSize = tableSize;
     HJ_HIP(c, hipMemsetAsync(c->dCtr(), 0, sizeof(Counters), c->stream));
     return HJ_OK;
@@ -443,6 +448,7 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     const WaveBufs wave{c->buf[B_BOUNDS].p, c->buf[B_QUEUE].p};
     const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>()};
     const unsigned long long* word = &job.ctr->variant;
+    c->wavePreGated = variant == 0;
     // The dominant kernel of each LDS variant is bracketed by its own pair of events (bracket(); hj_result.buildPhaseA_us).
     if (variant == 0) {
         // The locality pre-round decides ON THE DEVICE (this call stays asynchronous: no read-back). Behind it the kernels
@@ -470,6 +476,7 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
         // record costs the stream ~5 us -- step timeline at 2^22, tools/step_timeline.sh --, so nothing is recorded that
         // hj_fetch does not read.)
         if (enqWave) {
+            c->wavePreN = n;
             HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3, 4}, kWavePre));
             if (enqCompact)
                 HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
@@ -491,12 +498,14 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     } else if (variant == 4) {
         // the compact rings, asked for by the caller: the classic rings stay enqueued behind them as the gated fallback
         launch_set_variant(job.ctr, 4, c->stream);
+        c->wavePreN = n;
         if ((rc = record(c, EV_BUILD0))) return rc;
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWavePre | kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, kWaveClassic, bracket(c, EV_KW0)));
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveTail));
     } else if (variant == 3) {
+        c->wavePreN = n;
         if ((rc = record(c, EV_BUILD0))) return rc;
         HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWaveAll, kWaveClassic, bracket(c, EV_KW0)));
     } else if (variant == 2) {
@@ -575,6 +584,7 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
         const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>(), htmConflicts, ownCounts};
         HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
     } else if (variant == 3) {
+        c->wavePreN = rSize; c->wavePreGated = false;
         if ((rc = record(c, EV_BUILD0))) return rc;
         const WaveBufs wave{bounds, c->buf[B_QUEUE].p, htmConflicts, ldsChains};
         HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWaveAll, kWaveClassic, bracket(c, EV_KW0)));
@@ -1155,6 +1165,37 @@ int hj_prj_fragment_info(uint64_t rSize, uint64_t sSize, uint32_t radixBits, uin
         o[0] = g[k]->C1; o[1] = g[k]->cap1; o[2] = g[k]->chunkLen1; o[3] = g[k]->C2; o[4] = g[k]->cap2;
     }
     out[11] = pl.bits1; out[12] = pl.bits2;
+    return HJ_OK;
+}
+
+int hj_wave_layout_info(const hj_ctx* c, uint32_t computeUnits, uint64_t n, uint64_t out[16])
+{
+    if (!out || (!c && (computeUnits == 0 || computeUnits > 65536)) || n > 0xFFFFFFFFull) return HJ_ERR_INVALID;
+    const int nCU = c ? c->nCU : (int)computeUnits;
+    const WaveLayout w = wave_layout(n, nCU);
+    const uint64_t v[16] = {w.chunkLen, w.nChunks, w.sliceLen, w.tileTuples, w.granSlots, w.ringGran, w.look, w.overlap,
+                            w.shadow, w.tail, w.predCap, w.compactMaxProbe, (uint64_t)nCU, 0, 0, 0};
+    memcpy(out, v, sizeof v);
+    return HJ_OK;
+}
+
+int hj_wave_seams(hj_ctx* c, uint32_t* starts, uint32_t* bounds, uint32_t* pcounts, uint64_t capacity, uint64_t* nChunks)
+{
+    HJ_ENTER(c, starts && bounds && nChunks);
+    if (!c->built || !c->wavePreN) return fail(c, HJ_ERR_STATE, "hj_wave_seams: the last build did not run the ring pre-pass");
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    // buildVariant 0: the pre-pass was enqueued behind the device's pick and ran only if that pick was the rings
+    if (c->wavePreGated && c->hCtr->variant != 3 && c->hCtr->variant != 4)
+        return fail(c, HJ_ERR_STATE, "hj_wave_seams: the last build did not run the ring pre-pass");
+    const uint64_t chunks = wave_layout(c->wavePreN, c->nCU).nChunks;
+    *nChunks = chunks;
+    if (capacity < chunks + 1) return fail(c, HJ_ERR_INVALID, "hj_wave_seams: capacity below the number of chunks + 1");
+    const WaveSeams w = wave_seams(c->nCU, c->buf[B_BOUNDS].p);
+    HJ_HIP(c, hipMemcpy(starts, w.starts, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(bounds, w.bounds, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (pcounts) HJ_HIP(c, hipMemcpy(pcounts, w.pcounts, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return HJ_OK;
 }
 

@@ -967,10 +967,11 @@ size_t wave_lds_bytes() { return kWvLdsBytes; }
 bool wave_supported(uint64_t tableSize) { return tableSize >= (uint64_t)kWvWin; }
 uint32_t wave_max_chunks(int nCU) { return kWvWavesPerCu * kWvMaxRounds * (uint32_t)nCU; }
 size_t wave_bounds_bytes(int nCU) { return (6 * (size_t)wave_max_chunks(nCU) + 4) * sizeof(uint32_t); }   // raw, bounds (+1), starts (+1), dcounts, ccounts, pcounts
+constexpr uint32_t kWvCompactMaxProbe = 32;         // the largest probeLength the compact build takes
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen)
 {
     // the shadow granule must cover every slot a walk across the seam can start from
-    return wave_supported(tableSize) && probeLen >= 1 && probeLen <= 32;
+    return wave_supported(tableSize) && probeLen >= 1 && probeLen <= kWvCompactMaxProbe;
 }
 static uint64_t wave_chunk_len(uint64_t n, int nCU)
 {
@@ -1008,6 +1009,21 @@ WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf)
 }
 const uint32_t* wave_bounds_ptr(int nCU, const void* boundsBuf) { return static_cast<const uint32_t*>(boundsBuf) + wave_max_chunks(nCU); }
 size_t wave_conflict_bytes(uint64_t n, int nCU) { return wave_queue_bytes(n, nCU) / sizeof(DeferredEntry) * sizeof(uint64_t); }
+
+WaveLayout wave_layout(uint64_t n, int nCU)
+{
+    const uint64_t chunkLen = wave_chunk_len(n, nCU);
+    return WaveLayout{chunkLen, (n + chunkLen - 1) / chunkLen, wave_slice_len(chunkLen), kWvTileTuples, kGranSlots, kWvGran,
+                      kWvLook, kWvOverlap, kWvShadow, kWvTail, kWvPredCap, kWvCompactMaxProbe};
+}
+WaveSeams wave_seams(int nCU, const void* boundsBuf)
+{
+    // the carving of launch_build_wave: raw, bounds (+1), starts (+1), dcounts, ccounts, pcounts
+    const size_t maxChunks = wave_max_chunks(nCU);
+    const uint32_t* const bounds = static_cast<const uint32_t*>(boundsBuf) + maxChunks;
+    const uint32_t* const starts = bounds + maxChunks + 1;
+    return WaveSeams{starts, bounds, starts + maxChunks + 1 + 2 * maxChunks};
+}
 
 hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, int parts, int mode, KernelEvents kev)
 {

@@ -310,6 +310,17 @@ size_t own_conflict_bytes(uint64_t n, int nCU);
 size_t own_conflict_count_bytes(uint64_t n, int nCU);
 WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf);
 size_t wave_conflict_bytes(uint64_t n, int nCU);
+// planning facts of the ring builds (hj_wave_layout_info): how n tuples are cut into chunks on nCU compute units, and the
+// constants the seam zones of the compact build are made of, taken from the kernel's own
+struct WaveLayout {
+    uint64_t chunkLen, nChunks, sliceLen;
+    uint32_t tileTuples, granSlots, ringGran, look, overlap, shadow, tail, predCap, compactMaxProbe;
+};
+WaveLayout wave_layout(uint64_t n, int nCU);
+// what the pre-pass (starts, bounds: nChunks + 1 words each) and the compact build (pcounts: nChunks words) left in the
+// bounds buffer (hj_wave_seams)
+struct WaveSeams { const uint32_t *starts, *bounds, *pcounts; };
+WaveSeams wave_seams(int nCU, const void* boundsBuf);
 
 // ---- bucketised table of --algo htm (defined in hj_htm.hip) -----------------
 uint32_t htm_num_buckets(uint64_t rSize);         // nextpow2(rSize / 3 + 1), HTMHashBuild.hpp:61-62

@@ -63,6 +63,25 @@ def generate_relation(kind, num_tuples, maxid=None, local_shuffle_range=0, zipf_
     return out
 
 
+_WAVE_LAYOUT_FIELDS = ("chunkLen", "nChunks", "sliceLen", "tileTuples", "granuleSlots", "ringGranules", "look", "overlap",
+                       "shadow", "tail", "crosserCap", "compactMaxProbeLength", "computeUnits")
+
+
+def _wave_layout(handle, compute_units, n):
+    out = (C.c_uint64 * 16)()
+    rc = lib.hj_wave_layout_info(handle, compute_units, n, out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, f"hj_wave_layout_info(n={n}, computeUnits={compute_units})")
+    return {k: int(out[i]) for i, k in enumerate(_WAVE_LAYOUT_FIELDS)}
+
+
+def wave_layout_info(n, compute_units):
+    """hj_wave_layout_info without a context (host-only arithmetic): how the ring builds cut n tuples into chunks on a
+    device of compute_units compute units, and the constants of the seam zones (look, overlap, shadow, tail, crosserCap,
+    compactMaxProbeLength, tileTuples, granuleSlots, ringGranules), as a dict."""
+    return _wave_layout(None, int(compute_units), n)
+
+
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
             buildVariant=0, prjMode=0, keepRowIds=False):
     p = hj_params()
@@ -195,6 +214,28 @@ class HashJoinContext:
         r = hj_result()
         self._check(lib.hj_fetch_result(self._h, C.byref(r)))
         return r.as_dict()
+
+    def wave_layout_info(self, n):
+        """hj_wave_layout_info for this context's device (see engine.wave_layout_info)."""
+        return _wave_layout(self._h, 0, n)
+
+    def wave_seams(self):
+        """hj_wave_seams (waits for the stream): what the ring pre-pass of the last build decided, as numpy uint32 arrays
+        starts[nChunks + 1], bounds[nChunks + 1] (granules) and pcounts[nChunks] (walks let in across each chunk's lower
+        seam; defined only when the compact build held). HJ_ERR_STATE when that build did not run the rings."""
+        n_chunks = C.c_uint64(0)
+        cap = 1
+        while True:
+            starts, bounds = np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.uint32)
+            pcounts = np.empty(cap, dtype=np.uint32)
+            rc = lib.hj_wave_seams(self._h, starts.ctypes.data, bounds.ctypes.data, pcounts.ctypes.data, cap,
+                                   C.byref(n_chunks))
+            if rc == _lib.HJ_ERR_INVALID and n_chunks.value + 1 > cap:
+                cap = n_chunks.value + 1
+                continue
+            self._check(rc)
+            k = n_chunks.value
+            return starts[:k + 1], bounds[:k + 1], pcounts[:k]
 
     def synchronize(self):
         self._check(lib.hj_synchronize(self._h))

@@ -153,8 +153,10 @@ typedef struct {
     uint64_t compactFallback;     /* open addressing: 0 = the compact ring build (buildVariant 4) held or was not
                                      tried; else why it handed over to the classic build -- bit 0: a tuple outside
                                      ring and range (no locality there), bit 1: more than 64 walks across one seam,
-                                     bit 2: key 0xFFFFFFFF, bit 3: a tuple far below its chunk's range, bit 4: a
-                                     seam's two sides disagree (the shadow granule missed a tuple).
+                                     bit 2: key 0xFFFFFFFF, bit 3: a tuple below its chunk's range in the tile that holds
+                                     the chunk's tail zone (in any other tile past the head zone such a tuple is
+                                     outside the ring: bit 0), bit 4: a seam's two sides disagree (the shadow granule
+                                     missed a tuple, or a walk entered it from below).
                                      HJ_ALGO_HTM: bit 8 = the chain phase could not run in LDS behind the ring build (key
                                      range of a chunk or its conflicts too large for the LDS image) and the generic
                                      chain kernels redid it                                                            */
@@ -353,6 +355,28 @@ int hj_prj_workspace_info(uint64_t rSize, uint64_t sSize, uint32_t radixBits, ui
  * partition (= fragments per final partition), slots per pass-2 fragment; out[6..10] = the same for S; out[11], out[12] =
  * radix bits of pass 1 and pass 2. A relation with out[1] (out[6]) == 0 does not qualify. */
 int hj_prj_fragment_info(uint64_t rSize, uint64_t sSize, uint32_t radixBits, uint32_t prjMode, uint64_t out[13]);
+
+/* Planning facts of the ring builds (buildVariant 3 and 4), the counterpart of hj_prj_fragment_info: how a relation of n
+ * tuples is cut into chunks, one per wavefront, and the constants the zones around every chunk seam are made of, reported
+ * from the kernel's own constants. ctx == NULL: host-only arithmetic for a device of `computeUnits` compute units (no
+ * device needed); otherwise the compute units of the context's device are used and computeUnits is ignored.
+ * out[0] = chunk length in tuples (the nominal seam of chunk c is c * out[0]), out[1] = chunks, out[2] = slice length (a
+ * chunk's share of the deferred queue), out[3] = tuples per tile, out[4] = slots per granule, out[5] = granules per ring,
+ * out[6] = look (positions from the nominal seam among which the pre-pass places the real one), out[7] = overlap (positions
+ * past its end a wavefront reads = head zone of the next), out[8] = shadow (positions before its seam the compact build
+ * reads), out[9] = tail (positions before the nominal seam whose next-range tuples the next wavefront inserts), out[10] =
+ * walks across one seam the compact build lists at most, out[11] = the largest probeLength the compact build takes,
+ * out[12] = compute units used, out[13..15] = 0. HJ_ERR_INVALID: out NULL, n > 2^32 - 1, no context and computeUnits 0. */
+int hj_wave_layout_info(const hj_ctx *ctx, uint32_t computeUnits, uint64_t n, uint64_t out[16]);
+/* What the ring pre-pass of the last build decided (waits for the stream): chunk c holds the positions
+ * [starts[c], starts[c + 1]) of the input and owns the granules [bounds[c], bounds[c + 1]) of the table; both arrays take
+ * *nChunks + 1 entries (starts[*nChunks] = n, bounds[*nChunks] = granules of the table). pcounts (may be NULL) takes
+ * *nChunks entries: the walks chunk c let in across its lower seam -- defined only when the compact build held
+ * (hj_result.buildVariant == 4). capacity = entries each array has room for; *nChunks is set whenever the call gets as far
+ * as knowing it. HJ_ERR_STATE: the last build on this context did not run the ring pre-pass (no build, buildVariant 1 or
+ * 2, or buildVariant 0 picking one of them). HJ_ERR_INVALID: capacity < *nChunks + 1, or a NULL argument. */
+int hj_wave_seams(hj_ctx *ctx, uint32_t *starts, uint32_t *bounds, uint32_t *pcounts, uint64_t capacity,
+                  uint64_t *nChunks);
 
 /* ---- device memory for hosts without a HIP runtime of their own ----------- */
 int hj_dev_alloc(hj_ctx *ctx, uint64_t bytes, void **dptr);
