@@ -449,6 +449,15 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>()};
     const unsigned long long* word = &job.ctr->variant;
     c->wavePreGated = variant == 0;
+    // The classic rings (3) of a context that keeps no row ids retire planar: 4-byte keys for the probe, the index words in a
+    // plane of their own that only the deferred walks read. Behind them the packed classic build stays enqueued, gated on the
+    // word k_wave_fixup sets when the planar build had to give up (Counters::planarFail); not needed, its launches return at once.
+    const int classicMode = (c->params.flags & HJ_FLAG_KEEP_ROW_IDS) ? kWaveClassic : kWavePlanar;
+    auto classic_tail = [&](Gate gate) -> hipError_t {
+        hipError_t e = launch_build_wave(job, wave, gate, kWaveTail, classicMode);
+        if (e != hipSuccess || classicMode == kWaveClassic) return e;
+        return launch_build_wave(job, wave, Gate{&job.ctr->packedRedo, 1}, kWaveMain | kWaveTail, kWaveClassic);
+    };
     // The dominant kernel of each LDS variant is bracketed by its own pair of events (bracket(); hj_result.buildPhaseA_us).
     if (variant == 0) {
         // The locality pre-round decides ON THE DEVICE (this call stays asynchronous: no read-back). Behind it the kernels
@@ -480,14 +489,14 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
             HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3, 4}, kWavePre));
             if (enqCompact)
                 HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
-            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, kWaveClassic, bracket(c, EV_KW0)));
+            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, classicMode, bracket(c, EV_KW0)));
         }
         if (enqOwn)
             HJ_HIP(c, launch_build_own(job, own, Gate{word, 2}, 1, bracket(c, EV_KO0)));
         if (enqWave) {
             if (enqCompact)
                 HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
-            HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveTail));
+            HJ_HIP(c, classic_tail(Gate{word, 3}));
         }
         if (enqOwn)
             HJ_HIP(c, launch_build_own(job, own, Gate{word, 2}, 2));
@@ -501,13 +510,14 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
         c->wavePreN = n;
         if ((rc = record(c, EV_BUILD0))) return rc;
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWavePre | kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
-        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, kWaveClassic, bracket(c, EV_KW0)));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, classicMode, bracket(c, EV_KW0)));
         HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
-        HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveTail));
+        HJ_HIP(c, classic_tail(Gate{word, 3}));
     } else if (variant == 3) {
         c->wavePreN = n;
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWaveAll, kWaveClassic, bracket(c, EV_KW0)));
+        HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWavePre | kWaveMain, classicMode, bracket(c, EV_KW0)));
+        HJ_HIP(c, classic_tail(Gate{nullptr, 0}));
     } else if (variant == 2) {
         if ((rc = record(c, EV_BUILD0))) return rc;
         HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
@@ -1044,15 +1054,20 @@ int hj_fetch_result(hj_ctx* c, hj_result* out)
         out->compactFallback = k.compactFail | ((c->htmBuilt && c->htmChainsFellBack) ? 0x100ull : 0ull);
         out->buildDeferred = k.deferred;
         // the dominant build kernel ALONE: the launch of the LDS build that ran is bracketed by its own pair of events (the
-        // launches of the variants the device did not pick return at once: microseconds; the largest bracket is the kernel)
+        // launches of the variants the device did not pick return at once: microseconds; the largest bracket is the kernel).
+        // After a hand-over more than one build kernel ran. compact -> classic: the sum of their brackets. planar -> packed:
+        // the packed redo has no bracket of its own (two more event records on every step, for a road `uniform` never takes),
+        // so the whole build group stands for it: never flattering.
         out->buildPhaseA_us = 0.0;
         static const Ev kBrackets[3][2] = {{EV_KW0, EV_KW1}, {EV_KC0, EV_KC1}, {EV_KO0, EV_KO1}};
         for (const auto& pr : kBrackets) {
             const double us = elapsed_us(c, pr[0], pr[1]);
-            if (us > out->buildPhaseA_us) out->buildPhaseA_us = us;
+            if (k.compactFail != 0) out->buildPhaseA_us += us;
+            else if (us > out->buildPhaseA_us) out->buildPhaseA_us = us;
         }
         out->clear_us = elapsed_us(c, EV_CLEAR0, EV_BUILD0);
         out->build_us = elapsed_us(c, EV_BUILD0, EV_BUILD1);
+        if (k.planarFail != 0) out->buildPhaseA_us = out->build_us;
         out->probe_us = elapsed_us(c, c->probeStartsAtBuildEnd ? EV_BUILD1 : EV_PROBE0, EV_PROBE1);
         // the reference's timed region is build+probe, table zeroing excluded
         // (NoCCHashBuild.hpp:24-34,83); clear_us is reported beside it
@@ -1196,6 +1211,22 @@ int hj_wave_seams(hj_ctx* c, uint32_t* starts, uint32_t* bounds, uint32_t* pcoun
     HJ_HIP(c, hipMemcpy(starts, w.starts, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HJ_HIP(c, hipMemcpy(bounds, w.bounds, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (pcounts) HJ_HIP(c, hipMemcpy(pcounts, w.pcounts, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HJ_OK;
+}
+
+int hj_wave_planar_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    if (!c->built || c->htmBuilt) return fail(c, HJ_ERR_STATE, "hj_wave_planar_info: no open-addressing table");
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    const Counters& k = *c->hCtr;
+    const uint32_t variant = c->variantUsed ? c->variantUsed : (uint32_t)k.variant;
+    out[0] = (variant == 3 && k.tableFormat == kFormatKeys4) ? 1 : 0;
+    out[1] = k.planarFail;
+    out[2] = k.tableFormat;
+    out[3] = 0;
     return HJ_OK;
 }
 

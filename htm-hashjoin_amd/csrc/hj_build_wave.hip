@@ -213,7 +213,13 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
 //   * retry entries the ring is about to leave behind get their rounds before it moves (forced rounds);
 //   * anything else (a key far from its neighbours, a walk that wraps around the table end, key 0xFFFFFFFF = the compact
 //     empty pattern) raises the flag.
-template <bool KEY32, bool CHECK, bool HTM, bool COMPACT>
+// PLANAR (the classic build of a context that keeps no row ids): everything above stays what it is -- ring, inserts, retry
+// queue, seams, deferral --, only the retire differs: a granule leaves as two 512-byte runs, key words to the key plane (the
+// start of the table buffer: exactly the compact format) and index words to the index plane behind it
+// (planar_index_plane), so that the probe reads 4 bytes per slot. The deferred phase then walks on the index plane alone
+// (k_wave_deferred<PLANAR>, k_wave_fixup). Key 0xFFFFFFFF cannot live in a 4-byte table: Counters::planarFail, and the
+// packed build redoes it.
+template <bool KEY32, bool CHECK, bool HTM, bool COMPACT, bool PLANAR>
 __global__ void __launch_bounds__(kWvThreads, kWvWpe)
 k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_t nChunks, const uint32_t* __restrict__ starts,
              const uint32_t* __restrict__ bounds, uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift,
@@ -222,6 +228,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
              uint32_t* __restrict__ ccounts, uint32_t residentWG, uint32_t* __restrict__ pcounts)
 {
     static_assert(!(COMPACT && HTM), "the bucketised table keeps its own layout");
+    static_assert(!(PLANAR && (COMPACT || HTM)), "the planar retire belongs to the classic open-addressing build");
     if (gate_closed(gate)) return;
     extern __shared__ __align__(16) uint64_t lds[];
     // the wavefront's number inside the workgroup is the same in all its lanes, but the compiler only knows that when told:
@@ -313,6 +320,14 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                     u2 vv; vv.x = (uint32_t)t.x; vv.y = (uint32_t)t.y;
                     __builtin_nontemporal_store(vv, reinterpret_cast<u2*>(reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift)) + lane);
                 }
+            } else if constexpr (PLANAR) {
+                // two 512-byte runs: the key words, the index words (the empty pattern's two words are the planes' empty patterns)
+                typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+                u2 kk, ii;
+                kk.x = (uint32_t)t.x; kk.y = (uint32_t)t.y; ii.x = (uint32_t)(t.x >> 32); ii.y = (uint32_t)(t.y >> 32);
+                uint32_t* const keys = reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift);
+                __builtin_nontemporal_store(kk, reinterpret_cast<u2*>(keys) + lane);
+                __builtin_nontemporal_store(ii, reinterpret_cast<u2*>(keys + (mask + 1 + kPlanarIndexGap)) + lane);
             } else {
                 // written once and not read again by this kernel: nontemporal stores (-1.5 % kernel time at 2^30, and
                 // the probe that follows runs 1 % faster; nontemporal LOADS of R were slower)
@@ -621,6 +636,16 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             target = target < gmin ? target : gmin;
             target = target < limG ? target : limG;
             advance(target);
+            if constexpr (PLANAR) {
+                // key 0xFFFFFFFF, the 4-byte empty pattern: its home slot is the table's last one, so only a tile that reaches
+                // that slot looks for it (one scalar compare per tile otherwise)
+                if (tmax == mask32) {
+                    bool ff = false;
+#pragma unroll
+                    for (int j = 0; j < kWvPer; ++j) ff |= live[j] & (klo[j] == 0xFFFFFFFFu);
+                    if (wv_ballot(ff) && lane == 0) atomicOr(&ctr->planarFail, 2ull);
+                }
+            }
             const uint32_t gmax = tmax >> kGranShift;
             allIn = full & (gmin - winLoG < kWvGran) & (gmax - winLoG < kWvGran) & (gmax < limG);
         }
@@ -766,43 +791,95 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
 // at 2^30 `uniform` take 101-107 us whether a workgroup takes a slice (round 2), a wavefront does (now), or the entries are
 // numbered through and dealt out to all lanes (round 3, binary search in a prefix of the counts: 104 us) -- 1.8 returning
 // 64-bit atomics per entry at the 17 G/s the global-atomic build reaches too.
-template <bool HTM>
+// PLANAR (the table of k_build_wave<PLANAR>): the same walk on the INDEX plane alone, with a 32-bit atomicMin. Order and
+// equality of slot values are those of their index words (round_body's look relies on the same), so the index plane
+// decides every step; the key of a displaced tuple is no longer in the slot and is read from R by its index, R[old -
+// idxBase] (R is resident for the whole build). The walks never write the key plane: two walkers that win the same slot one
+// after the other would race with plain stores. Every successful atomicMin instead appends its slot number to the walker's
+// dirty log -- the unused rest of the slice it walks, 4 slot numbers per free entry; one wavefront per slice, so a ballot
+// rank and a wave-uniform count place it -- and k_wave_fixup, behind the kernel boundary, writes the key of every logged
+// slot from what the index plane holds then. A log that does not fit raises Counters::planarFail (an input that defers
+// nearly everything: the rings forced onto a relation without locality).
+struct PlanarWalk { const void* R; bool key32; uint64_t idxBase; uint32_t* lcounts; };
+// the key of the tuple with index word idx (the index plane holds nothing but indices the build handed out, and empty)
+__device__ __forceinline__ uint32_t planar_key_of(const PlanarWalk& pw, uint32_t idx)
+{
+    const uint32_t at = idx - (uint32_t)pw.idxBase;
+    return pw.key32 ? static_cast<const uint32_t*>(pw.R)[at] : (uint32_t)static_cast<const uint64_t*>(pw.R)[at];
+}
+template <bool HTM, bool PLANAR>
 __global__ void __launch_bounds__(kBlock)
-k_wave_deferred(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ dcounts, uint32_t nChunks,
+k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ dcounts, uint32_t nChunks,
                 uint32_t chunkLen, uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift, uint32_t probeLen,
                 Counters* __restrict__ ctr, Gate gate, uint64_t* __restrict__ htmConflicts, uint32_t* __restrict__ ccounts,
-                const uint32_t* __restrict__ routeBounds)
+                const uint32_t* __restrict__ routeBounds, PlanarWalk pw)
 {
+    static_assert(!(HTM && PLANAR), "the bucketised table keeps its packed slots");
     if (gate_closed(gate)) return;
+    // Key 0xFFFFFFFF seen by k_build_wave: the packed build redoes everything. Other wavefronts of THIS kernel raise bit 0 while
+    // this plain load runs, so some may return here and others walk on: harmless only because k_wave_fixup, behind the kernel
+    // boundary, throws the whole planar table away when any bit is set.
+    if constexpr (PLANAR) { if (ctr->planarFail) return; }
     const uint32_t lane = threadIdx.x & 63;
+    const uint32_t mask32 = (uint32_t)mask;
+    [[maybe_unused]] uint32_t* const idxPlane = PLANAR ? planar_index_plane(table, mask + 1) : nullptr;
     unsigned long long drops = 0, dropSum = 0;
     // a wavefront per slice (~220 entries per slice on `uniform` with one round of chunks, ~29 in each of 32768 slices at 2^30)
     for (uint32_t c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nChunks; c += gridDim.x * (kBlock / 64)) {
         const uint32_t cnt = dcounts[c];
-        const DeferredEntry* q = queue + (uint64_t)c * chunkLen;
+        DeferredEntry* const q = queue + (uint64_t)c * chunkLen;
+        [[maybe_unused]] uint32_t* const log = reinterpret_cast<uint32_t*>(q + cnt);      // PLANAR: the slice's dirty log
+        [[maybe_unused]] const uint32_t logCap =
+            cnt < chunkLen ? (chunkLen - cnt) * (uint32_t)(sizeof(DeferredEntry) / sizeof(uint32_t)) : 0u;
+        [[maybe_unused]] uint32_t logCount = 0;                                           // wave-uniform
         for (uint32_t i0 = 0; i0 < cnt; i0 += 64) {
             const uint32_t i = i0 + lane;
             const bool has = i < cnt;
-            uint64_t mine = has ? q[i].packed : 0ull;
-            uint64_t pos = has ? q[i].pos : 0ull;
-            const uint64_t home0 = home32<HTM>((uint32_t)mine, hshift, (uint32_t)mask);
-            uint32_t budget = probeLen - (uint32_t)((pos - home0) & mask);
+            const uint64_t first = has ? q[i].packed : 0ull;
+            uint32_t key = (uint32_t)first, idx = (uint32_t)(first >> 32);
+            uint32_t pos = has ? (uint32_t)q[i].pos : 0u;
+            uint32_t budget = probeLen - ((pos - home32<HTM>(key, hshift, mask32)) & mask32);
             bool dropped = false;
-            for (; has;) {
-                if (budget == 0) { drops += 1; dropSum += (uint32_t)mine; dropped = true; break; }
-                const unsigned long long old =
-                    atomicMin(reinterpret_cast<unsigned long long*>(table + pos), (unsigned long long)mine);
-                if (old == kEmpty || old == mine) break;
-                if (old > mine) {
-                    mine = old;
-                    const uint64_t home = home32<HTM>((uint32_t)old, hshift, (uint32_t)mask);
-                    budget = probeLen - ((uint32_t)((pos - home) & mask) + 1);
-                } else {
-                    budget -= 1;
+            // one step of every walk per turn, the wavefront together (the log's count stays wave-uniform)
+            for (bool act = has; wv_ballot(act);) {
+                const bool out = act & (budget == 0);
+                if (out) { drops += 1; dropSum += key; dropped = true; }
+                act &= !out;
+                uint32_t oldIdx = idx, oldKey = 0;
+                if (act) {
+                    if constexpr (PLANAR) {
+                        oldIdx = atomicMin(idxPlane + pos, idx);
+                    } else {
+                        const unsigned long long old = atomicMin(reinterpret_cast<unsigned long long*>(table + pos),
+                                                                 (unsigned long long)wv_pack(idx, key));
+                        oldIdx = (uint32_t)(old >> 32); oldKey = (uint32_t)old;
+                    }
                 }
-                pos = (pos + 1) & mask;
+                if constexpr (PLANAR) {
+                    const unsigned long long wm = wv_ballot(oldIdx > idx);         // the slot's index word changed
+                    if (wm) {
+                        const uint32_t at = logCount + lane_rank(wm);
+                        if ((oldIdx > idx) & (at < logCap)) log[at] = pos;
+                        logCount += (uint32_t)__popcll(wm);
+                    }
+                }
+                // empty (the highest index word) or my own: placed
+                act &= (oldIdx != kNone) & (oldIdx != idx);
+                if (act) {
+                    if (oldIdx > idx) {                                            // I stay, the displaced tuple walks on
+                        if constexpr (PLANAR) oldKey = planar_key_of(pw, oldIdx);
+                        key = oldKey; idx = oldIdx;
+                        // (a tuple sits less than probeLen slots from its home; anything else ends the walk)
+                        const uint32_t dist = (pos - home32<HTM>(key, hshift, mask32)) & mask32;
+                        budget = dist < probeLen ? probeLen - (dist + 1) : 0u;
+                    } else {
+                        budget -= 1;
+                    }
+                    pos = (pos + 1) & mask32;
+                }
             }
             if constexpr (HTM) {
+                const uint64_t mine = wv_pack(idx, key);
                 // the slice's conflict list is appended to by four wavefronts now: one atomic per wavefront reserves the places
                 // (ccounts[c] holds what k_build_wave recorded; the list's order is free, the chain phase sorts by index)
                 if (routeBounds) {
@@ -828,6 +905,12 @@ k_wave_deferred(const DeferredEntry* __restrict__ queue, const uint32_t* __restr
                 }
             }
         }
+        if constexpr (PLANAR) {
+            if (lane == 0) {
+                pw.lcounts[c] = logCount < logCap ? logCount : logCap;
+                if (logCount > logCap) atomicOr(&ctr->planarFail, 1ull);
+            }
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -837,6 +920,52 @@ k_wave_deferred(const DeferredEntry* __restrict__ queue, const uint32_t* __restr
     if (lane == 0) {
         if (drops) atomicAdd(&counter_shard(ctr)->conflicts, drops);
         if (dropSum) atomicAdd(&counter_shard(ctr)->conflictSum, dropSum);
+    }
+}
+
+// as if the build so far had never run: every sum and maximum a build kernel adds to (one wavefront, a shard per lane)
+__device__ __forceinline__ void reset_build_counters(Counters* __restrict__ ctr, uint32_t lane)
+{
+    static_assert(Counters::kShards == 64, "one shard per lane");
+    ctr->shard[lane] = Counters::Shard{};
+    if (lane == 0) {
+        ctr->conflicts = 0; ctr->conflictSum = 0; ctr->inputSum = 0; ctr->badKeys = 0; ctr->deferred = 0; ctr->foreign = 0;
+        ctr->usedLoInv = 0; ctr->usedHi1 = 0; ctr->ownLo = 0; ctr->ownHiEx = 0;
+    }
+}
+
+// PLANAR, behind the walks' kernel boundary (the only ordering used): a wavefront per slice writes, for every slot of the
+// slice's dirty log, the key that belongs to what the index plane holds now -- key[s] = index[s] == empty ? empty : low word
+// of R[index[s] - idxBase]. A slot logged twice (by one walker after the other) gets the same value twice. The first
+// wavefront also closes the planar build: no flag raised -> the table is in the 4-byte format; otherwise counters back to
+// zero and Counters::packedRedo = 1, on which the packed classic build behind this kernel is gated (it writes every slot
+// again; nothing of this build is looked at).
+__global__ void __launch_bounds__(kBlock)
+k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ dcounts, uint32_t nChunks, uint32_t sliceLen,
+             uint64_t* __restrict__ table, uint64_t tableSize, Counters* __restrict__ ctr, Gate gate, PlanarWalk pw)
+{
+    if (gate_closed(gate)) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const bool fail = ctr->planarFail != 0;                // final: raised by the kernels before this one only
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        if (fail) {
+            reset_build_counters(ctr, lane);
+            if (lane == 0) { ctr->tableFormat = kFormatSlots8; ctr->packedRedo = 1; }
+        } else if (lane == 0) {
+            ctr->tableFormat = kFormatKeys4;
+        }
+    }
+    if (fail) return;
+    uint32_t* const keys = reinterpret_cast<uint32_t*>(table);
+    const uint32_t* const idxPlane = planar_index_plane(table, tableSize);
+    for (uint32_t c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nChunks; c += gridDim.x * (kBlock / 64)) {
+        const uint32_t* const log = reinterpret_cast<const uint32_t*>(queue + (uint64_t)c * sliceLen + dcounts[c]);
+        const uint32_t cnt = pw.lcounts[c];
+        for (uint32_t i = lane; i < cnt; i += 64) {
+            const uint32_t s = log[i];                     // a walker's pos: masked, always inside the table
+            const uint32_t idx = idxPlane[s];
+            keys[s] = idx == kNone ? kNone : planar_key_of(pw, idx);
+        }
     }
 }
 
@@ -920,13 +1049,10 @@ k_wave_validate(const DeferredEntry* __restrict__ queue, const uint32_t* __restr
 __global__ void k_wave_decide(Counters* __restrict__ ctr, uint64_t tableSize, uint32_t fallbackVariant, Gate gate)
 {
     if (blockIdx.x != 0 || threadIdx.x >= 64 || gate_closed(gate)) return;
-    static_assert(Counters::kShards == 64, "one shard per lane");
     const bool fail = ctr->compactFail != 0;
     if (fail) {
-        ctr->shard[threadIdx.x] = Counters::Shard{};
+        reset_build_counters(ctr, threadIdx.x);
         if (threadIdx.x == 0) {
-            ctr->conflicts = 0; ctr->conflictSum = 0; ctr->inputSum = 0; ctr->badKeys = 0; ctr->deferred = 0; ctr->foreign = 0;
-            ctr->usedLoInv = 0; ctr->usedHi1 = 0; ctr->ownLo = 0; ctr->ownHiEx = 0;
             ctr->tableFormat = kFormatSlots8;
             ctr->variant = fallbackVariant;
         }
@@ -940,8 +1066,10 @@ __global__ void k_wave_decide(Counters* __restrict__ ctr, uint64_t tableSize, ui
 }
 
 // compact counterpart of k_wave_fill_edges: 4-byte empties over [validLo, ownLo) and [ownHiEx, validHiEx + 512) + slack
+// index != nullptr (the planar retire): the same stretches of the index plane read empty too -- that is everywhere a
+// deferred walk can step outside the owned range (the valid range covers the blocks the walks start from + one)
 __global__ void __launch_bounds__(kBlock)
-k_wave_fill_edges_keys(uint32_t* __restrict__ keys, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
+k_wave_fill_edges_keys(uint32_t* __restrict__ keys, uint32_t* __restrict__ index, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
 {
     if (gate_closed(gate)) return;
     const uint4 e = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
@@ -953,6 +1081,11 @@ k_wave_fill_edges_keys(uint32_t* __restrict__ keys, const Counters* __restrict__
     for (uint64_t v = a0 + t0; v < a1; v += stride) t4[v] = e;
     const uint64_t b0 = ctr->ownHiEx >> 2, b1 = hi >> 2;
     for (uint64_t v = b0 + t0; v < b1; v += stride) t4[v] = e;
+    if (index) {
+        uint4* i4 = reinterpret_cast<uint4*>(index);
+        for (uint64_t v = a0 + t0; v < a1; v += stride) i4[v] = e;
+        for (uint64_t v = b0 + t0; v < b1; v += stride) i4[v] = e;
+    }
     if (blockIdx.x == 0 && threadIdx.x < kTableSlack) keys[tableSize + threadIdx.x] = 0xFFFFFFFFu;
 }
 
@@ -1028,8 +1161,8 @@ WaveSeams wave_seams(int nCU, const void* boundsBuf)
 hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, int parts, int mode, KernelEvents kev)
 {
     const bool htm = buf.htmConflicts != nullptr;
-    const bool compact = mode == kWaveCompact;
-    if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact)) return hipErrorInvalidValue;
+    const bool compact = mode == kWaveCompact, planar = mode == kWavePlanar;
+    if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact || planar)) return hipErrorInvalidValue;
     if (!j.key32 && j.hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
     const uint32_t maxChunks = wave_max_chunks(j.nCU);
     const uint64_t chunkLen = wave_chunk_len(j.n, j.nCU);
@@ -1057,17 +1190,21 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     }
     if (parts & kWaveMain) {
         if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
-#define HJ_WV_LAUNCH(K32, CHK, HTM, CMP)                                                                             \
-    hipLaunchKernelGGL((k_build_wave<K32, CHK, HTM, CMP>), gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, \
+#define HJ_WV_LAUNCH(K32, CHK, HTM, CMP, PLN)                                                                        \
+    hipLaunchKernelGGL((k_build_wave<K32, CHK, HTM, CMP, PLN>), gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, \
                        nChunks, starts, bounds, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,       \
                        static_cast<DeferredEntry*>(buf.queue), dcounts, j.ctr, gate, buf.htmConflicts, ccounts, residentWG, pcounts)
-        if (htm) HJ_WV_LAUNCH(false, false, true, false);
+        if (htm) HJ_WV_LAUNCH(false, false, true, false, false);
         else if (compact) {
-            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, true); else HJ_WV_LAUNCH(false, true, false, true); }
-            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, true); else HJ_WV_LAUNCH(false, false, false, true); }
+            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, true, false); else HJ_WV_LAUNCH(false, true, false, true, false); }
+            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, true, false); else HJ_WV_LAUNCH(false, false, false, true, false); }
         }
-        else if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false); else HJ_WV_LAUNCH(false, true, false, false); }
-        else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false); else HJ_WV_LAUNCH(false, false, false, false); }
+        else if (planar) {
+            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false, true); else HJ_WV_LAUNCH(false, true, false, false, true); }
+            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false, true); else HJ_WV_LAUNCH(false, false, false, false, true); }
+        }
+        else if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false, false); else HJ_WV_LAUNCH(false, true, false, false, false); }
+        else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false, false); else HJ_WV_LAUNCH(false, false, false, false, false); }
 #undef HJ_WV_LAUNCH
         if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
         if (compact) {
@@ -1080,17 +1217,29 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     }
     if (!(parts & kWaveTail)) return hipSuccess;
     if (compact) {
-        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(512), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table), j.ctr, j.tableSize, gate);
+        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(512), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table), nullptr, j.ctr, j.tableSize, gate);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_wave_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, gate);
-    hipLaunchKernelGGL(k_wave_fill_edges, dim3(2048), dim3(kBlock), 0, j.s, j.table, j.ctr, j.tableSize, gate);
+    DeferredEntry* const queue = static_cast<DeferredEntry*>(buf.queue);
     const dim3 gDef((nChunks + kBlock / 64 - 1) / (kBlock / 64));   // one wavefront per slice
-    if (htm) hipLaunchKernelGGL(k_wave_deferred<true>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), dcounts,
+    if (planar) {
+        // the log counts take the place of the bucketised table's conflict counts, which an open-addressing build never uses
+        const PlanarWalk pw{j.R, j.key32, j.idxBase, ccounts};
+        // 1024 workgroups: the compact road's 512 for one plane of 4-byte words, doubled for two (4.9 us at 2^30, as the packed fill)
+        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(1024), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table),
+                           planar_index_plane(j.table, j.tableSize), j.ctr, j.tableSize, gate);
+        hipLaunchKernelGGL((k_wave_deferred<false, true>), gDef, dim3(kBlock), 0, j.s, queue, dcounts, nChunks, sliceLen, j.table,
+                           j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr, pw);
+        hipLaunchKernelGGL(k_wave_fixup, gDef, dim3(kBlock), 0, j.s, queue, dcounts, nChunks, sliceLen, j.table, j.tableSize, j.ctr, gate, pw);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_wave_fill_edges, dim3(2048), dim3(kBlock), 0, j.s, j.table, j.ctr, j.tableSize, gate);
+    if (htm) hipLaunchKernelGGL((k_wave_deferred<true, false>), gDef, dim3(kBlock), 0, j.s, queue, dcounts,
                                 nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, buf.htmConflicts, ccounts,
-                                buf.htmRoute ? bounds : nullptr);
-    else hipLaunchKernelGGL(k_wave_deferred<false>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), dcounts,
-                            nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr);
+                                buf.htmRoute ? bounds : nullptr, PlanarWalk{});
+    else hipLaunchKernelGGL((k_wave_deferred<false, false>), gDef, dim3(kBlock), 0, j.s, queue, dcounts,
+                            nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr, PlanarWalk{});
     return hipGetLastError();
 }
 

@@ -108,6 +108,12 @@ struct Counters {
     // k_table_sums and hj_export_table read the word. compactFail: raised by the compact build when it meets something
     // only the classic builds can handle; k_wave_decide then resets the counters and hands over to the classic build.
     unsigned long long tableFormat, compactFail;
+    // Planar retire of the classic ring build (k_build_wave<PLANAR>, hj_build_wave.hip): the table ends as kFormatKeys4 with
+    // the index words in a plane of their own behind the keys (planar_index_plane). planarFail: why that build handed
+    // over -- bit 0: a slice's dirty log did not fit (an input that defers nearly everything), bit 1: key 0xFFFFFFFF, the
+    // 4-byte empty pattern. k_wave_fixup then resets the counters and sets packedRedo = 1, the word the packed classic
+    // build enqueued behind it is gated on. Counters::variant stays 3 on both roads.
+    unsigned long long planarFail, packedRedo;
     // the locality pre-round's sample of hj_build_dev (k_sample_locality: launch_sample_locality's eight words, [7] = its
     // ticket) -- inside this struct so that the one memset at the start of a build clears them too
     unsigned int fit[kSampleWords];
@@ -178,6 +184,16 @@ __device__ inline bool gate_closed(const Gate& g)
 }
 constexpr Gate kNoGate{nullptr, 0ull};
 constexpr unsigned long long kFormatSlots8 = 0, kFormatKeys4 = 1;
+// Planar retire: where the index plane starts in the table buffer of (tableSize + kTableSlack) 8-byte words -- behind the
+// key plane and ITS slack (the probe reads up to probeLength - 1 keys past the table's end and must find them empty), at
+// the next multiple of 128 bytes so that the granules' 512-byte runs stay on whole lines in both planes. One uint32 input
+// index per slot, 0xFFFFFFFF = empty; walks on it wrap, so it needs no slack of its own and ends exactly at the buffer's end.
+constexpr uint64_t kPlanarIndexGap = 2 * kTableSlack;      // uint32 words between the key plane's end and the index plane
+static_assert(kPlanarIndexGap * sizeof(uint32_t) % 128 == 0, "whole lines");
+__host__ __device__ inline uint32_t* planar_index_plane(uint64_t* table, uint64_t tableSize)
+{
+    return reinterpret_cast<uint32_t*>(table) + tableSize + kPlanarIndexGap;
+}
 
 // A tuple that left its LDS window (variants 2 and 3): the slot it had reached and (index << 32 | key)
 struct DeferredEntry { uint64_t pos; uint64_t packed; };
@@ -292,9 +308,13 @@ size_t wave_queue_bytes(uint64_t n, int nCU);   // deferred queue: one slice per
 // edge fill and the deferred phase. mode kWaveCompact: the compact build (4-byte table, no deferred phase) -- its main
 // part is k_build_wave<COMPACT> + the seam check + k_wave_decide, which on failure resets the counters and sets
 // Counters::variant = 3 so that the classic build enqueued behind it (gated on that word) redoes the table;
-// its tail is the edge fill alone. The pre-pass is the same for both modes (gate it with alt).
+// its tail is the edge fill alone. The pre-pass is the same for all modes (gate it with alt).
+// mode kWavePlanar: the classic build with the planar retire (k_build_wave<PLANAR>: keys and indices leave for two planes,
+// the table ends as kFormatKeys4). Its tail is valid range, edge fill of both planes, the deferred walks on the index
+// plane and k_wave_fixup, which on Counters::planarFail sets Counters::packedRedo = 1: the word to gate the packed classic
+// build behind it on. Tuples and bare keys; never the bucketised table.
 constexpr int kWavePre = 1, kWaveMain = 2, kWaveTail = 4, kWaveAll = 7;
-constexpr int kWaveClassic = 0, kWaveCompact = 1;
+constexpr int kWaveClassic = 0, kWaveCompact = 1, kWavePlanar = 2;
 // htmRoute: the deferred phase files its conflicts under the chunk that owns their bucket (the LDS chain phase needs that)
 struct WaveBufs { void* bounds; void* queue; uint64_t* htmConflicts = nullptr; bool htmRoute = false; };
 hipError_t launch_build_wave(const BuildJob& job, const WaveBufs& buf, Gate gate, int parts, int mode = kWaveClassic, KernelEvents kev = {});

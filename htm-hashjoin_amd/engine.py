@@ -237,6 +237,13 @@ class HashJoinContext:
             k = n_chunks.value
             return starts[:k + 1], bounds[:k + 1], pcounts[:k]
 
+    def wave_planar_info(self):
+        """hj_wave_planar_info (waits for the stream): whether the last build left the planar table of the classic rings
+        (4-byte keys + an index plane), and why that build handed over to the packed one (0: it did not)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_wave_planar_info(self._h, out))
+        return {"planar": bool(out[0]), "planarFallback": int(out[1]), "tableFormat": int(out[2])}
+
     def synchronize(self):
         self._check(lib.hj_synchronize(self._h))
 

@@ -100,7 +100,8 @@ typedef struct {
 
 /* hj_params.flags. Open addressing: never leave the table in the compact 4-byte format, so that every slot keeps the
  * input index of its tuple for hj_probe_pairs_dev (buildVariant 4 runs as 3; buildVariant 0 neither enqueues nor picks
- * 4). No effect on HJ_ALGO_HTM, whose table always keeps the indices.
+ * 4; buildVariant 3 writes its packed 8-byte slots instead of a key plane and an index plane, hj_wave_planar_info).
+ * No effect on HJ_ALGO_HTM, whose table always keeps the indices.
  * Resident radix join (hj_reserve with HJ_ALGO_PRJ or HJ_ALGO_AUTO): hj_prj_build_dev keeps R resident as 8-byte
  * {key, row} elements (row = position in dR; the input's own upper word is dropped) instead of bare 4-byte keys, for
  * hj_prj_probe_pairs_dev. Row ids travel through the exact passes only: prjPath and the paths of hj_prj_resident_info
@@ -377,6 +378,15 @@ int hj_wave_layout_info(const hj_ctx *ctx, uint32_t computeUnits, uint64_t n, ui
  * 2, or buildVariant 0 picking one of them). HJ_ERR_INVALID: capacity < *nChunks + 1, or a NULL argument. */
 int hj_wave_seams(hj_ctx *ctx, uint32_t *starts, uint32_t *bounds, uint32_t *pcounts, uint64_t capacity,
                   uint64_t *nChunks);
+/* The planar retire of the classic ring build (waits for the stream). On a context reserved WITHOUT HJ_FLAG_KEEP_ROW_IDS,
+ * buildVariant 3 leaves the table as 4-byte keys (what the probe reads) with the input indices in a plane of their own,
+ * which only its deferred phase reads; an input it cannot take is redone by the packed classic build, decided on the
+ * device, and hj_result.buildVariant says 3 either way. out[0] = 1 if the last build's table is the planar one, out[1] =
+ * why the planar build handed over, 0 = it did not or was not tried (bit 0: a chunk's log of slots the deferred phase
+ * changed did not fit -- an input that defers nearly everything; bit 1: key 0xFFFFFFFF, the 4-byte empty pattern),
+ * out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys), out[3] = 0. hj_result.compactFallback does not speak of this.
+ * HJ_ERR_STATE: no open-addressing table. */
+int hj_wave_planar_info(hj_ctx *ctx, uint64_t out[4]);
 
 /* ---- device memory for hosts without a HIP runtime of their own ----------- */
 int hj_dev_alloc(hj_ctx *ctx, uint64_t bytes, void **dptr);
