@@ -219,6 +219,39 @@ BuildCaps build_caps(const hj_ctx* c, uint64_t n, uint64_t tableSize)
     return k;
 }
 
+// The build kernel a request for `variant` ends up with when the context cannot run it: 4 without the compact rings ->
+// the classic ones, 3 without rings -> the window or global atomics, 2 without the window -> global atomics; 0 (the
+// locality pre-round picks) stays 0 only while there is an LDS build to pick.
+static uint32_t settle_variant(uint32_t variant, const BuildCaps& can)
+{
+    if (variant == 4 && !can.compact) variant = 3;
+    if (variant == 3 && !can.wave) variant = can.own ? 2 : 1;
+    if (variant == 2 && !can.own) variant = 1;
+    if (variant == 0 && !can.own && !can.wave) variant = 1;
+    return variant;
+}
+
+// One build as its launchers see it (hj_device.h): the context's table, counters and stream around the caller's input
+static BuildJob build_job(hj_ctx* c, const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t tableSize, uint32_t probeLen,
+                          uint64_t idxBase, ShardCheck sc)
+{
+    BuildJob job{};
+    job.R = R; job.key32 = key32; job.n = n; job.idxBase = idxBase;
+    job.table = c->buf[B_TABLE].as<uint64_t>(); job.tableSize = tableSize; job.hshift = hshift; job.probeLen = probeLen; job.sc = sc;
+    job.nCU = c->nCU; job.ctr = c->dCtr(); job.s = c->stream;
+    return job;
+}
+
+// The counters as they are once the stream has drained, in c->hCtr; fold: with the shards added into the totals
+// (fold_counter_shards), for the callers that read a sum
+static int read_counters(hj_ctx* c, bool fold)
+{
+    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (fold) fold_counter_shards(c->hCtr);
+    return HJ_OK;
+}
+
 int create_common(int device, void* stream, bool own, hj_ctx** out)
 {
     if (!out) return HJ_ERR_INVALID;
@@ -432,19 +465,11 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     if ((rc = begin_operation(c, n, 0, tableSize))) return rc;
     c->hshift = hshift;
     if ((rc = record(c, EV_CLEAR0))) return rc;
-    uint32_t variant = c->forceVariant ? c->forceVariant : c->params.buildVariant;
     const BuildCaps can = build_caps(c, n, tableSize);
-    if (variant == 4 && !can.compact) variant = 3;
-    if (variant == 3 && !can.wave) variant = can.own ? 2 : 1;
-    if (variant == 2 && !can.own) variant = 1;
-    if (variant == 0 && !can.own && !can.wave) variant = 1;
+    const uint32_t variant = settle_variant(c->forceVariant ? c->forceVariant : c->params.buildVariant, can);
     c->variantUsed = (variant == 4) ? 0 : variant;     // 0: decided on the device (4 may fall back to 3), reported from Counters::variant
     c->algoUsed = c->params.algo == HJ_ALGO_AUTO ? (uint32_t)HJ_ALGO_ATOMIC : c->params.algo;
-    BuildJob job{};
-    job.R = d; job.key32 = key32; job.n = n; job.hshift = hshift;
-    job.table = c->buf[B_TABLE].as<uint64_t>(); job.tableSize = tableSize;
-    job.probeLen = probe_len(c->params); job.idxBase = idxBase; job.sc = c->sc;
-    job.nCU = c->nCU; job.ctr = c->dCtr(); job.s = c->stream;
+    const BuildJob job = build_job(c, d, key32, n, hshift, tableSize, probe_len(c->params), idxBase, c->sc);
     const WaveBufs wave{c->buf[B_BOUNDS].p, c->buf[B_QUEUE].p};
     const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>()};
     const unsigned long long* word = &job.ctr->variant;
@@ -559,14 +584,13 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     c->hshift = 0; c->htmBuckets = nb;
     if (!c->htmGenericChains) c->htmChainsFellBack = false;
     if ((rc = record(c, EV_CLEAR0))) return rc;
-    uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
+    const BuildJob job = build_job(c, dR, false, rSize, 0, slots, 3, idxBase, ShardCheck{0, 0, 0, 0});
     uint64_t* const htmConflicts = c->buf[B_HTM_CONFLICTS].as<uint64_t>();
     uint32_t* const ownCounts = c->buf[B_HTM_OWN_COUNTS].as<uint32_t>();
     unsigned int* const ovfCount = c->buf[B_HTM_OVF_COUNT].as<unsigned int>();
     uint32_t* const ovfBase = c->buf[B_HTM_OVF_BASE].as<uint32_t>();
     uint32_t* const scan = c->buf[B_HTM_SCAN].as<uint32_t>();
     void* const bounds = c->buf[B_BOUNDS].p;
-    Counters* const ctr = c->dCtr();
     // locality pre-round with the bucketised table's own hash (bucket = key / 3 keeps the key order): the rings if they
     // will do, the workgroup window for looser locality (shuffle windows up to ~2000 positions), else global atomics.
     // The window also lists its conflicts: two buffers more than build_caps asks for
@@ -574,21 +598,13 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     can.own = can.own && c->buf[B_HTM_CONFLICTS].bytes >= own_conflict_bytes(rSize, c->nCU) &&
               c->buf[B_HTM_OWN_COUNTS].bytes >= own_conflict_count_bytes(rSize, c->nCU);
     can.compact = false;
-    uint32_t variant = c->params.buildVariant > 3 ? 3 : c->params.buildVariant;
-    if (variant == 0 && (can.wave || can.own) && (rc = sample_variant(c, dR, false, rSize, slots, 0, can, &variant, true))) return rc;
-    if (variant == 0) variant = 1;
-    if (variant == 3 && !can.wave) variant = can.own ? 2 : 1;
-    if (variant == 2 && !can.own) variant = 1;
+    uint32_t variant = settle_variant(c->params.buildVariant, can);      // the compact rings: the classic ones here
+    if (variant == 0 && (rc = sample_variant(c, dR, false, rSize, slots, 0, can, &variant, true))) return rc;   // answers within `can`
     c->variantUsed = variant; c->algoUsed = HJ_ALGO_HTM;
     const WaveSlices sl = variant == 2 ? own_conflict_layout(rSize, c->nCU, ownCounts) : wave_conflict_layout(rSize, c->nCU, bounds);
     // the rings: chains in LDS (hj_htm.hip) unless an earlier attempt on this relation had to give up
     const uint32_t nParts = sl.nChunks * htm_chain_parts(sl.sliceLen);
     const bool ldsChains = variant == 3 && !c->htmGenericChains && (uint64_t)nParts + 1 <= nb && htm_chain_info_words(sl.nChunks, sl.sliceLen) <= nb;
-    BuildJob job{};
-    job.R = dR; job.key32 = false; job.n = rSize; job.hshift = 0;
-    job.table = table; job.tableSize = slots;
-    job.probeLen = 3; job.idxBase = idxBase; job.sc = ShardCheck{0, 0, 0, 0};
-    job.nCU = c->nCU; job.ctr = ctr; job.s = c->stream;
     if (variant == 2) {
         if ((rc = record(c, EV_BUILD0))) return rc;
         const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>(), htmConflicts, ownCounts};
@@ -601,24 +617,22 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
         if (ldsChains) {
             // the chain phase in LDS, first half: overflow buckets per part of a slice, scanned (one word more: the total)
             HJ_HIP(c, hipMemsetAsync(ovfBase + nParts, 0, sizeof(uint32_t), c->stream));
-            HJ_HIP(c, launch_htm_chain_count(htmConflicts, sl.counts, wave_bounds_ptr(c->nCU, bounds), sl.nChunks, sl.sliceLen, nb,
-                                             ovfBase, ovfCount, ctr, c->stream));
+            HJ_HIP(c, launch_htm_chain_count(htmConflicts, sl.counts, WaveScratch(c->nCU, bounds).bounds, sl.nChunks, sl.sliceLen, nb,
+                                             ovfBase, ovfCount, job.ctr, c->stream));
             HJ_HIP(c, launch_exclusive_scan_u32(ovfBase, (uint64_t)nParts + 1, scan, c->stream));
             HJ_HIP(c, hipMemcpyAsync(c->hFit, ovfBase + nParts, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
     } else {
-        launch_fill_empty(table, slots + kTableSlack, Gate{nullptr, 0}, c->stream);
-        launch_set_full_range(slots, ctr, Gate{nullptr, 0}, c->stream);
+        launch_fill_empty(job.table, slots + kTableSlack, Gate{nullptr, 0}, c->stream);
+        launch_set_full_range(slots, job.ctr, Gate{nullptr, 0}, c->stream);
         HJ_HIP(c, hipGetLastError());
         if ((rc = record(c, EV_BUILD0))) return rc;
-        HJ_HIP(c, launch_htm_build_global(dR, rSize, sl.sliceLen, sl.nChunks, table, slots, idxBase, htmConflicts,
-                                          const_cast<uint32_t*>(sl.counts), ctr, c->stream));
+        HJ_HIP(c, launch_htm_build_global(dR, rSize, sl.sliceLen, sl.nChunks, job.table, slots, idxBase, htmConflicts,
+                                          const_cast<uint32_t*>(sl.counts), job.ctr, c->stream));
     }
     // chains -- only if some bucket overflowed (one read-back of the conflict count): count per bucket, reserve overflow
     // buckets by one scan, fill them in index order, link
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
-    fold_counter_shards(c->hCtr);
+    if ((rc = read_counters(c, true))) return rc;
     const uint64_t conflicts = c->hCtr->conflicts;              // >= overflow buckets needed
     c->htmOverflowUsed = conflicts;
     if (ldsChains && c->hCtr->htmChainBail) {
@@ -633,15 +647,15 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
         const uint64_t groups = c->hFit[0];                     // overflow buckets the parts need, exactly
         if (conflicts) {
             if ((rc = reserve_htm_overflow(c, groups))) return rc;
-            HJ_HIP(c, launch_htm_chain_fill(htmConflicts, sl.nChunks, sl.sliceLen, nb, ovfBase, ovfCount, table,
-                                            c->buf[B_HTM_OVERFLOW].as<uint64_t>(), ctr, c->stream));
+            HJ_HIP(c, launch_htm_chain_fill(htmConflicts, sl.nChunks, sl.sliceLen, nb, ovfBase, ovfCount, job.table,
+                                            c->buf[B_HTM_OVERFLOW].as<uint64_t>(), job.ctr, c->stream));
         }
     } else if (conflicts) {
         HJ_HIP(c, launch_htm_count(htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, nb, ovfCount, ovfBase, c->stream));
         HJ_HIP(c, launch_exclusive_scan_u32(ovfBase, nb, scan, c->stream));
         if ((rc = reserve_htm_overflow(c, conflicts))) return rc;
-        HJ_HIP(c, launch_htm_chains(htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, table, nb, ovfCount, ovfBase,
-                                    c->buf[B_HTM_OVERFLOW].as<uint64_t>(), conflicts, ctr, c->stream));
+        HJ_HIP(c, launch_htm_chains(htmConflicts, sl.counts, sl.nChunks, sl.sliceLen, job.table, nb, ovfCount, ovfBase,
+                                    c->buf[B_HTM_OVERFLOW].as<uint64_t>(), conflicts, job.ctr, c->stream));
     }
     if ((rc = record(c, EV_BUILD1))) return rc;
     c->built = true; c->htmBuilt = true;
@@ -938,9 +952,8 @@ int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
     HJ_HIP(c, hipSetDevice(c->device));
     const PrjResident res = prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, 0);
     unsigned long long st[4];
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HJ_HIP(c, hipMemcpyAsync(st, res.stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = read_counters(c, false)) return rc;
     const PrjPlan& pl = c->resPlan;
     const bool fragR = pl.optimistic && c->hCtr->prjFallbackR == 0;
     const uint64_t P = 1ull << pl.radixBits;
@@ -1011,9 +1024,7 @@ int hj_fetch_result(hj_ctx* c, hj_result* out)
 {
     HJ_ENTER(c, out);
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
-    fold_counter_shards(c->hCtr);
+    if (const int rc = read_counters(c, true)) return rc;
     memset(out, 0, sizeof(*out));
     const Counters& k = *c->hCtr;
     out->rSize = c->rSize; out->sSize = c->sSize; out->tableSize = c->tableSize;
@@ -1114,9 +1125,7 @@ int hj_export_buckets(hj_ctx* c, void* host_buckets, uint64_t numBuckets, void* 
     HJ_ENTER(c, host_buckets);
     if (!c->htmBuilt || numBuckets != c->htmBuckets) return fail(c, HJ_ERR_STATE, "hj_export_buckets: no htm table of that many buckets");
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
-    fold_counter_shards(c->hCtr);
+    if (const int rc = read_counters(c, true)) return rc;
     const uint64_t used = c->hCtr->htmOverflowBuckets;
     if (nOverflow) *nOverflow = used;
     if (used && (!host_overflows || overflowCap < used + 1)) return fail(c, HJ_ERR_INVALID, "hj_export_buckets: overflow buffer too small");
@@ -1199,15 +1208,14 @@ int hj_wave_seams(hj_ctx* c, uint32_t* starts, uint32_t* bounds, uint32_t* pcoun
     HJ_ENTER(c, starts && bounds && nChunks);
     if (!c->built || !c->wavePreN) return fail(c, HJ_ERR_STATE, "hj_wave_seams: the last build did not run the ring pre-pass");
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = read_counters(c, false)) return rc;
     // buildVariant 0: the pre-pass was enqueued behind the device's pick and ran only if that pick was the rings
     if (c->wavePreGated && c->hCtr->variant != 3 && c->hCtr->variant != 4)
         return fail(c, HJ_ERR_STATE, "hj_wave_seams: the last build did not run the ring pre-pass");
     const uint64_t chunks = wave_layout(c->wavePreN, c->nCU).nChunks;
     *nChunks = chunks;
     if (capacity < chunks + 1) return fail(c, HJ_ERR_INVALID, "hj_wave_seams: capacity below the number of chunks + 1");
-    const WaveSeams w = wave_seams(c->nCU, c->buf[B_BOUNDS].p);
+    const WaveScratch w(c->nCU, c->buf[B_BOUNDS].p);
     HJ_HIP(c, hipMemcpy(starts, w.starts, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HJ_HIP(c, hipMemcpy(bounds, w.bounds, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (pcounts) HJ_HIP(c, hipMemcpy(pcounts, w.pcounts, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1219,8 +1227,7 @@ int hj_wave_planar_info(hj_ctx* c, uint64_t out[4])
     HJ_ENTER(c, out);
     if (!c->built || c->htmBuilt) return fail(c, HJ_ERR_STATE, "hj_wave_planar_info: no open-addressing table");
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipMemcpyAsync(c->hCtr, c->dCtr(), sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (const int rc = read_counters(c, false)) return rc;
     const Counters& k = *c->hCtr;
     const uint32_t variant = c->variantUsed ? c->variantUsed : (uint32_t)k.variant;
     out[0] = (variant == 3 && k.tableFormat == kFormatKeys4) ? 1 : 0;

@@ -54,7 +54,6 @@ constexpr uint32_t kBackBlocks = 2;              // window keeps this much room 
 
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_umin(v); }      // DPP steps (hj_device.h), not LDS permutes
 
-__device__ __forceinline__ uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
 
 constexpr uint32_t kDrainAt = 64;                // run retry rounds once this many entries wait (<= 64)
 constexpr int kQCap = 128;                        // per-wavefront retry queue entries (LDS)
@@ -439,23 +438,12 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
 __global__ void k_finalize_range(Counters* __restrict__ ctr, uint32_t numBlocks, uint64_t tableSize, Gate gate)
 {
     if (blockIdx.x != 0 || threadIdx.x >= 64 || gate_closed(gate)) return;
-    // the two maxima: what was written directly + the 64 shards (hj_device.h, Counters), one shard per lane
-    static_assert(Counters::kShards == 64, "one shard per lane of the single wavefront this kernel runs as");
-    unsigned long long usedLoInvAll = ctr->shard[threadIdx.x & 63].usedLoInv, usedHi1All = ctr->shard[threadIdx.x & 63].usedHi1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long a = __shfl_xor(usedLoInvAll, off, 64), b = __shfl_xor(usedHi1All, off, 64);
-        usedLoInvAll = a > usedLoInvAll ? a : usedLoInvAll; usedHi1All = b > usedHi1All ? b : usedHi1All;
-    }
-    usedLoInvAll = ctr->usedLoInv > usedLoInvAll ? ctr->usedLoInv : usedLoInvAll;
-    usedHi1All = ctr->usedHi1 > usedHi1All ? ctr->usedHi1 : usedHi1All;
+    const UsedBlocks used = fold_used_blocks(ctr);
     if (threadIdx.x != 0) return;
-    const unsigned long long hi1 = usedHi1All;
-    if (hi1 == 0) { ctr->validLo = 0; ctr->validHiEx = 0; return; }          // nothing inserted anywhere
-    const unsigned long long lo = (unsigned long long)(uint32_t)~(uint32_t)usedLoInvAll;
-    const unsigned long long hiEx = hi1 + 1;                                   // blocks [lo, hi+1] probed
-    if (hiEx + 1 >= numBlocks) { ctr->validLo = 0; ctr->validHiEx = tableSize; }
-    else { ctr->validLo = lo << kBlkShift; ctr->validHiEx = hiEx << kBlkShift; }
+    if (used.hi1 == 0) { ctr->validLo = 0; ctr->validHiEx = 0; return; }     // nothing inserted anywhere
+    const unsigned long long lo = (unsigned long long)(uint32_t)~(uint32_t)used.loInv;
+    static_assert(kBlkShift == 9, "set_valid_range's 512 slots past the range are one block");
+    set_valid_range(ctr, lo << kBlkShift, (used.hi1 + 1) << kBlkShift, tableSize);   // blocks [lo, hi+1] probed; numBlocks * 512 = tableSize
 }
 
 // Blocks of the valid range nobody claimed (and the slack past the table end) get the empty pattern.
@@ -538,11 +526,7 @@ k_build_deferred(const DeferredEntry* __restrict__ queueAll, const uint32_t* __r
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        drops += __shfl_down(drops, off, 64);
-        dropSum += __shfl_down(dropSum, off, 64);
-    }
+    wave_sum_all(drops, dropSum);
     if ((threadIdx.x & 63) == 0) {
         if (drops) atomicAdd(&counter_shard(ctr)->conflicts, drops);
         if (dropSum) atomicAdd(&counter_shard(ctr)->conflictSum, dropSum);
@@ -648,12 +632,7 @@ k_sample_locality(const void* __restrict__ Rv, uint64_t n, uint64_t mask, uint32
                 outsideWave += (((okBits >> q) & 1u) && g - gbase >= kWvRingGran) ? 1u : 0u;
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            outside += __shfl_down(outside, off, 64);
-            outsideWave += __shfl_down(outsideWave, off, 64);
-            dup += __shfl_down(dup, off, 64);
-        }
+        wave_sum_all(outside, outsideWave, dup);
         if (lane == 0 && farRows) atomicAdd(&sFar, farRows);
         if (lane == 0 && outside) atomicAdd(&sOutside, outside);
         if (lane == 0 && outsideWave) atomicAdd(&sOutsideWave, outsideWave);
@@ -683,9 +662,7 @@ k_sample_locality(const void* __restrict__ Rv, uint64_t n, uint64_t mask, uint32
         unsigned int v = 0;
         for (uint32_t bk = threadIdx.x; bk < gridDim.x; bk += kBlock)
             v += __hip_atomic_load(&slots[8 * bk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        f[i] = v;
+        f[i] = wave_sum(v);
     }
     if (threadIdx.x == 0) { sOutside = 0; sOutsideWave = 0; sDup = 0; sFar = 0; sMinBlk = 0; }
     __syncthreads();
@@ -715,15 +692,13 @@ hipError_t launch_sample_locality(const void* R, bool key32, uint64_t n, uint64_
         const hipError_t e = hipMemsetAsync(fitCount, 0, 8 * sizeof(unsigned int), s);
         if (e != hipSuccess) return e;
     }
-    if (htm)        // the bucketised table's own hash ((key / 3) << 2: the keys spread 4/3 as wide as in the open-addressing table)
-        hipLaunchKernelGGL((k_sample_locality<false, true>), dim3(nSample < 256 ? nSample : 256), dim3(kBlock), 0, s,
-                           R, n, tableSize - 1, hshift, nSample, fitCount, pick);
-    else if (key32)
-        hipLaunchKernelGGL(k_sample_locality<true>, dim3(nSample < 256 ? nSample : 256), dim3(kBlock), 0, s,
-                           R, n, tableSize - 1, hshift, nSample, fitCount, pick);
-    else
-        hipLaunchKernelGGL(k_sample_locality<false>, dim3(nSample < 256 ? nSample : 256), dim3(kBlock), 0, s,
-                           R, n, tableSize - 1, hshift, nSample, fitCount, pick);
+    auto launch = [&](auto k32, auto htmTag) {
+        hipLaunchKernelGGL((k_sample_locality<decltype(k32)::value, decltype(htmTag)::value>), dim3(nSample < 256 ? nSample : 256),
+                           dim3(kBlock), 0, s, R, n, tableSize - 1, hshift, nSample, fitCount, pick);
+    };
+    // the bucketised table's own hash ((key / 3) << 2: the keys spread 4/3 as wide as in the open-addressing table) on tuples; else the key format
+    if (htm) launch(std::false_type{}, std::true_type{});
+    else with_flag(key32, [&](auto k32) { launch(k32, std::false_type{}); });
     return hipGetLastError();
 }
 
@@ -740,8 +715,9 @@ hipError_t own_set_attributes()
     return hipSuccess;
 }
 
-// chunk geometry of the workgroup-window build: (chunks, tuples per chunk)
-static void own_geometry(uint64_t n, int nCU, uint64_t* nChunksOut, uint64_t* chunkLenOut)
+// chunk geometry of the workgroup-window build
+struct OwnGeometry { uint64_t nChunks, chunkLen; };
+static OwnGeometry own_geometry(uint64_t n, int nCU)
 {
     // one chunk per resident workgroup (2 per CU: 76 KiB LDS each): a single wave of workgroups, no tail,
     // and the fewest chunk seams (measured: 512 chunks beat 768/1024/2048/4096 on MI355X)
@@ -749,36 +725,28 @@ static void own_geometry(uint64_t n, int nCU, uint64_t* nChunksOut, uint64_t* ch
     uint64_t chunkLen = (n + nChunks - 1) / nChunks;
     chunkLen = (chunkLen + kOwnTile - 1) / kOwnTile * kOwnTile;
     if (chunkLen < (uint64_t)kOwnTile * 4) chunkLen = (uint64_t)kOwnTile * 4;
-    *chunkLenOut = chunkLen;
-    *nChunksOut = (n + chunkLen - 1) / chunkLen;
+    return OwnGeometry{(n + chunkLen - 1) / chunkLen, chunkLen};
 }
 // htm: the conflict list of the window build = one slice per chunk + a last slice for the deferred phase's conflicts
 WaveSlices own_conflict_layout(uint64_t n, int nCU, void* countsBuf)
 {
-    uint64_t nChunks, chunkLen;
-    own_geometry(n, nCU, &nChunks, &chunkLen);
-    return WaveSlices{(uint32_t)nChunks + 1, (uint32_t)chunkLen, static_cast<const uint32_t*>(countsBuf)};
+    const OwnGeometry g = own_geometry(n, nCU);
+    return WaveSlices{(uint32_t)g.nChunks + 1, (uint32_t)g.chunkLen, static_cast<const uint32_t*>(countsBuf)};
 }
 size_t own_conflict_bytes(uint64_t n, int nCU)
 {
-    uint64_t nChunks, chunkLen;
-    own_geometry(n, nCU, &nChunks, &chunkLen);
-    return (size_t)(nChunks * chunkLen + n + 64) * sizeof(uint64_t);
+    const OwnGeometry g = own_geometry(n, nCU);
+    return (size_t)(g.nChunks * g.chunkLen + n + 64) * sizeof(uint64_t);
 }
-size_t own_conflict_count_bytes(uint64_t n, int nCU)
-{
-    uint64_t nChunks, chunkLen;
-    own_geometry(n, nCU, &nChunks, &chunkLen);
-    return (size_t)(nChunks + 2) * sizeof(uint32_t);
-}
+size_t own_conflict_count_bytes(uint64_t n, int nCU) { return (size_t)(own_geometry(n, nCU).nChunks + 2) * sizeof(uint32_t); }
 
 hipError_t launch_build_own(const BuildJob& j, const OwnBufs& buf, Gate gate, int parts, KernelEvents kev)
 {
     const bool htm = buf.htmConflicts != nullptr;
     if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || j.hshift)) return hipErrorInvalidValue;
     const uint32_t numBlocks = (uint32_t)(j.tableSize >> kBlkShift);
-    uint64_t nChunks, chunkLen;
-    own_geometry(j.n, j.nCU, &nChunks, &chunkLen);
+    const OwnGeometry g = own_geometry(j.n, j.nCU);
+    const uint64_t nChunks = g.nChunks, chunkLen = g.chunkLen;
     hipError_t e;
     if (parts & 1) {
     if ((e = hipMemsetAsync(buf.owner, 0, own_owner_bytes(j.tableSize), j.s)) != hipSuccess) return e;
@@ -786,15 +754,15 @@ hipError_t launch_build_own(const BuildJob& j, const OwnBufs& buf, Gate gate, in
     if (htm && (e = hipMemsetAsync(buf.htmCounts, 0, own_conflict_count_bytes(j.n, j.nCU), j.s)) != hipSuccess) return e;
     const unsigned grid = (unsigned)nChunks;
     if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
-#define HJ_OWN_LAUNCH(K32, CHK, HTM)                                                                                 \
-    hipLaunchKernelGGL((k_build_own<K32, CHK, HTM>), dim3(grid), dim3(kOwnThreads), kWinSlots * sizeof(uint64_t), j.s, \
-                       j.R, j.n, chunkLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,     \
-                       static_cast<unsigned int*>(buf.owner), static_cast<DeferredEntry*>(buf.queue), buf.deferCounts, j.ctr, gate, \
-                       buf.htmConflicts, buf.htmCounts, (uint32_t)chunkLen)
-    if (htm) HJ_OWN_LAUNCH(false, false, true);
-    else if (j.sc.mask) { if (j.key32) HJ_OWN_LAUNCH(true, true, false); else HJ_OWN_LAUNCH(false, true, false); }   // the instances that count foreign tuples
-    else { if (j.key32) HJ_OWN_LAUNCH(true, false, false); else HJ_OWN_LAUNCH(false, false, false); }
-#undef HJ_OWN_LAUNCH
+    auto launch = [&](auto k32, auto chk, auto htmTag) {
+        hipLaunchKernelGGL((k_build_own<decltype(k32)::value, decltype(chk)::value, decltype(htmTag)::value>), dim3(grid), dim3(kOwnThreads), kWinSlots * sizeof(uint64_t), j.s,
+                           j.R, j.n, chunkLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,
+                           static_cast<unsigned int*>(buf.owner), static_cast<DeferredEntry*>(buf.queue), buf.deferCounts, j.ctr, gate,
+                           buf.htmConflicts, buf.htmCounts, (uint32_t)chunkLen);
+    };
+    // every instantiation there is: the bucketised table on tuples without a shard check; else key format x "counts foreign tuples"
+    if (htm) launch(std::false_type{}, std::false_type{}, std::true_type{});
+    else with_flag(j.key32, [&](auto k32) { with_flag(j.sc.mask != 0, [&](auto chk) { launch(k32, chk, std::false_type{}); }); });
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
     }

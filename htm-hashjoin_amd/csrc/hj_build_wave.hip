@@ -54,15 +54,14 @@ constexpr uint32_t kWvRoundAt = 64;                 // a retry round runs once t
 // wavefronts per SIMD the registers must allow (16 per CU: what the rings' LDS allows; the compact build fits in 115
 // VGPRs once the chunk state is scalar)
 constexpr int kWvWpe = 4;
-constexpr uint32_t kWvWavesPerCu = 16;              // resident wavefronts per CU (what the rings' LDS allows)
-constexpr uint32_t kWvMaxRounds = 8;                // chunks = resident wavefronts x rounds (wave_chunk_len below)
+// kWvWavesPerCu resident wavefronts per CU, chunks = resident wavefronts x up to kWvMaxRounds rounds (hj_device.h; wave_layout below)
 constexpr uint32_t kWvMinChunk = 32768;             // tuples: a second round of workgroups only while chunks stay this long
+constexpr uint32_t kWvShortestChunk = 4 * kWvTileTuples;   // tuples: no chunk is cut shorter
 // issue priorities rotate in time among a CU's workgroup slots; period = 2^shift ticks of the 100 MHz clock (10.24 us)
 constexpr uint32_t kWvPrioShift = 10;
 static_assert(kWvQCap >= 128 && (kWvQCap & (kWvQCap - 1)) == 0, "FIFO ring: a power of two that takes one full step on top of < 64 waiting entries");
 constexpr size_t kWvLdsBytes = (size_t)kWvWaves * (kWvWin * sizeof(uint64_t) + 3 * kWvQCap * sizeof(uint32_t));
 
-__device__ __forceinline__ uint64_t wv_pack(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
 // The lane mask of a condition. HIP's __ballot(int) compares an INTEGER with zero: a condition that already is a lane mask
 // (every compare produces one) is first turned into 0 / 1 per lane and compared again -- two vector instructions per
 // ballot, ~50 per tile in a kernel whose retry rounds are bound by vector issue. This form takes the mask as it is.
@@ -84,6 +83,35 @@ constexpr uint32_t kWvOverlap = 64;
 constexpr uint32_t kWvShadow = kWvTile - kWvOverlap;
 constexpr uint32_t kWvTail = kWvOverlap;         // the last positions of a chunk whose next-range tuples the NEXT wavefront inserts
 constexpr uint32_t kWvPredCap = 64;
+
+// ---- queue slice: chunk c's sliceLen entries of the deferred queue and their three tenants -----------------------------
+// E = DeferredEntry for the kernels that write, const DeferredEntry for the ones that only read.
+//   * deferred entries, from the front: dcounts[c] of them (a tuple leaves at most once: <= clen + kWvOverlap <= sliceLen);
+//     the compact build lists there, `packed` only, the crossers that leave its range at the upper seam
+template <class E>
+__host__ __device__ inline E* slice_deferred(E* queue, uint32_t c, uint32_t sliceLen) { return queue + (uint64_t)c * sliceLen; }
+//   * compact build: the crossers the chunk let in at its lower seam, pcounts[c] of at most kWvPredCap 8-byte words
+//     (index << 32 | key) at the slice's very end
+template <class E>
+__host__ __device__ inline auto slice_crossers(E* queue, uint32_t c, uint32_t sliceLen)
+{
+    using Word = std::conditional_t<std::is_const_v<E>, const uint64_t, uint64_t>;
+    return reinterpret_cast<Word*>(slice_deferred(queue, c + 1, sliceLen)) - kWvPredCap;
+}
+// k_wave_validate accepts a seam with at most kWvPredCap crossers on either side: even in the shortest slice the ones
+// going out (16-byte entries from the front) and the ones let in (8-byte words at the end) never meet
+static_assert(kWvPredCap * (sizeof(DeferredEntry) + sizeof(uint64_t)) <= (kWvShortestChunk + kWvLook + kWvOverlap) * sizeof(DeferredEntry),
+              "the crosser list fits behind the most crossers a compact slice can hold");
+//   * planar retire: the dirty log of the slice's deferred walks, lcounts[c] slot numbers behind the dcount deferred
+//     entries -- 4 per entry the chunk did not defer
+template <class W> struct DirtyLog { W* slot; uint32_t cap; };
+template <class E>
+__host__ __device__ inline auto slice_dirty_log(E* queue, uint32_t c, uint32_t sliceLen, uint32_t dcount)
+{
+    using Word = std::conditional_t<std::is_const_v<E>, const uint32_t, uint32_t>;
+    return DirtyLog<Word>{reinterpret_cast<Word*>(slice_deferred(queue, c, sliceLen) + dcount),
+                          dcount < sliceLen ? (sliceLen - dcount) * (uint32_t)(sizeof(DeferredEntry) / sizeof(uint32_t)) : 0u};
+}
 template <bool KEY32, bool HTM>
 __global__ void __launch_bounds__(kBlock)
 k_wave_seams(const void* __restrict__ Rv, uint64_t n, uint32_t chunkLen, uint32_t nChunks, uint64_t mask,
@@ -301,28 +329,31 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     unsigned long long dropSum = 0, inSum = 0;
     uint32_t drops = 0, bad = 0, foreign = 0;
     uint32_t dCount = 0;                         // tuples deferred so far (wave-uniform)
-    DeferredEntry* const myDeferred = queue + (uint64_t)c * sliceLen;      // <= clen + kWvOverlap <= sliceLen entries
+    DeferredEntry* const myDeferred = slice_deferred(queue, c, sliceLen);
     uint32_t cCount = 0;                         // HTM: conflicts recorded so far (wave-uniform)
     uint64_t* const myConflicts = HTM ? htmConflicts + (uint64_t)c * sliceLen : nullptr;
     (void)cCount; (void)myConflicts;
     uint32_t usedLo = kNone, usedHi1 = 0;        // 512-slot blocks this lane deferred into (Counters::usedLoInv / usedHi1)
 
+    // this lane's two slots of granule g's place in the ring
+    auto ring_granule = [&](uint32_t g) -> ulonglong2* {
+        return reinterpret_cast<ulonglong2*>(win + ((g & (kWvGran - 1)) << kGranShift)) + lane;
+    };
     // the ring's tail up to granule `target` leaves for HBM (empties included) and its LDS copy is reset
     auto advance = [&](uint32_t target) {
+        typedef unsigned int u2 __attribute__((ext_vector_type(2)));
         while (winLoG < target) {
-            ulonglong2* src = reinterpret_cast<ulonglong2*>(win + ((winLoG & (kWvGran - 1)) << kGranShift)) + lane;
+            ulonglong2* src = ring_granule(winLoG);
             const ulonglong2 t = *src;
             if constexpr (COMPACT) {
                 // the key words alone leave: 512 bytes per granule (the empty pattern's low word is the compact empty
                 // pattern); the shadow granule belongs to the previous wavefront and is not written
                 if (winLoG >= loG) {
-                    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
                     u2 vv; vv.x = (uint32_t)t.x; vv.y = (uint32_t)t.y;
                     __builtin_nontemporal_store(vv, reinterpret_cast<u2*>(reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift)) + lane);
                 }
             } else if constexpr (PLANAR) {
                 // two 512-byte runs: the key words, the index words (the empty pattern's two words are the planes' empty patterns)
-                typedef unsigned int u2 __attribute__((ext_vector_type(2)));
                 u2 kk, ii;
                 kk.x = (uint32_t)t.x; kk.y = (uint32_t)t.y; ii.x = (uint32_t)(t.x >> 32); ii.y = (uint32_t)(t.y >> 32);
                 uint32_t* const keys = reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift);
@@ -360,10 +391,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 const unsigned long long xm = wv_ballot(cross);
                 if (xm) {
                     const uint32_t at = pCount + lane_rank(xm);
-                    // the list lives at the end of this chunk's slice of the deferred queue (which the compact build otherwise
-                    // uses for the handful of crossers that leave the range): kWvPredCap 8-byte entries
-                    uint64_t* const myPred = reinterpret_cast<uint64_t*>(queue + (uint64_t)(c + 1) * sliceLen) - kWvPredCap;
-                    if (cross & (at < kWvPredCap)) myPred[at] = wv_pack(mhi, mlo);
+                    uint64_t* const myPred = slice_crossers(queue, c, sliceLen);
+                    if (cross & (at < kWvPredCap)) myPred[at] = pack64(mhi, mlo);
                     raise(cross & (at >= kWvPredCap), 2ull);
                     pCount += (uint32_t)__popcll(xm);
                 }
@@ -373,7 +402,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         const bool drop0 = has & (budget == 0);
         const bool toDefer = has & !drop0 & !ownOk;
         const bool work = has & !drop0 & ownOk;
-        const uint64_t mine = wv_pack(mhi, mlo);
+        const uint64_t mine = pack64(mhi, mlo);
         // look before leaping: the next 4 slots, when they sit in the same granule (contiguous in the ring and owned
         // together); slot values only decrease, so a slot seen below `mine` stays below it
         const bool inGran = (pos & (kGranSlots - 1)) <= kGranSlots - 4;
@@ -602,7 +631,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                     if (!FULL || tmaxF == mask32) ffSeen |= in & (klo[j] == 0xFFFFFFFFu);
                 }
                 const bool ok = mineHere & okKey;
-                inSum += in ? (unsigned long long)wv_pack(khi[j], klo[j]) : 0ull;
+                inSum += in ? (unsigned long long)pack64(khi[j], klo[j]) : 0ull;
                 if constexpr (FULL) badTile += 64u - (uint32_t)__popcll(wv_ballot(okKey));     // scalar: no per-lane count
                 else bad += (in & !okKey) ? 1u : 0u;
                 if constexpr (CHECK) foreign += (in & is_foreign(klo[j], sc)) ? 1u : 0u;
@@ -662,7 +691,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 oldv[j] = kEmpty;
                 if (own[j])
                     oldv[j] = atomicMin(reinterpret_cast<unsigned long long*>(&win[home[j] & (kWvWin - 1)]),
-                                        (unsigned long long)wv_pack(idx0 + tb + lane + 64 * j, klo[j]));
+                                        (unsigned long long)pack64(idx0 + tb + lane + 64 * j, klo[j]));
             }
         };
         if (allIn) attempts(std::true_type{}); else attempts(std::false_type{});
@@ -727,7 +756,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             if (endShadow) {
                 shadowOn = false;
                 while (winLoG < loG) {
-                    reinterpret_cast<ulonglong2*>(win + ((winLoG & (kWvGran - 1)) << kGranShift))[lane] = make_ulonglong2(kEmpty, kEmpty);
+                    *ring_granule(winLoG) = make_ulonglong2(kEmpty, kEmpty);
                     ++winLoG;
                 }
             }
@@ -827,10 +856,8 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
     // a wavefront per slice (~220 entries per slice on `uniform` with one round of chunks, ~29 in each of 32768 slices at 2^30)
     for (uint32_t c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nChunks; c += gridDim.x * (kBlock / 64)) {
         const uint32_t cnt = dcounts[c];
-        DeferredEntry* const q = queue + (uint64_t)c * chunkLen;
-        [[maybe_unused]] uint32_t* const log = reinterpret_cast<uint32_t*>(q + cnt);      // PLANAR: the slice's dirty log
-        [[maybe_unused]] const uint32_t logCap =
-            cnt < chunkLen ? (chunkLen - cnt) * (uint32_t)(sizeof(DeferredEntry) / sizeof(uint32_t)) : 0u;
+        DeferredEntry* const q = slice_deferred(queue, c, chunkLen);
+        [[maybe_unused]] const auto log = slice_dirty_log(queue, c, chunkLen, cnt);      // PLANAR
         [[maybe_unused]] uint32_t logCount = 0;                                           // wave-uniform
         for (uint32_t i0 = 0; i0 < cnt; i0 += 64) {
             const uint32_t i = i0 + lane;
@@ -851,7 +878,7 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
                         oldIdx = atomicMin(idxPlane + pos, idx);
                     } else {
                         const unsigned long long old = atomicMin(reinterpret_cast<unsigned long long*>(table + pos),
-                                                                 (unsigned long long)wv_pack(idx, key));
+                                                                 (unsigned long long)pack64(idx, key));
                         oldIdx = (uint32_t)(old >> 32); oldKey = (uint32_t)old;
                     }
                 }
@@ -859,7 +886,7 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
                     const unsigned long long wm = wv_ballot(oldIdx > idx);         // the slot's index word changed
                     if (wm) {
                         const uint32_t at = logCount + lane_rank(wm);
-                        if ((oldIdx > idx) & (at < logCap)) log[at] = pos;
+                        if ((oldIdx > idx) & (at < log.cap)) log.slot[at] = pos;
                         logCount += (uint32_t)__popcll(wm);
                     }
                 }
@@ -879,7 +906,7 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
                 }
             }
             if constexpr (HTM) {
-                const uint64_t mine = wv_pack(idx, key);
+                const uint64_t mine = pack64(idx, key);
                 // the slice's conflict list is appended to by four wavefronts now: one atomic per wavefront reserves the places
                 // (ccounts[c] holds what k_build_wave recorded; the list's order is free, the chain phase sorts by index)
                 if (routeBounds) {
@@ -907,8 +934,8 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
         }
         if constexpr (PLANAR) {
             if (lane == 0) {
-                pw.lcounts[c] = logCount < logCap ? logCount : logCap;
-                if (logCount > logCap) atomicOr(&ctr->planarFail, 1ull);
+                pw.lcounts[c] = logCount < log.cap ? logCount : log.cap;
+                if (logCount > log.cap) atomicOr(&ctr->planarFail, 1ull);
             }
         }
     }
@@ -959,7 +986,7 @@ k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict
     uint32_t* const keys = reinterpret_cast<uint32_t*>(table);
     const uint32_t* const idxPlane = planar_index_plane(table, tableSize);
     for (uint32_t c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nChunks; c += gridDim.x * (kBlock / 64)) {
-        const uint32_t* const log = reinterpret_cast<const uint32_t*>(queue + (uint64_t)c * sliceLen + dcounts[c]);
+        const uint32_t* const log = slice_dirty_log(queue, c, sliceLen, dcounts[c]).slot;
         const uint32_t cnt = pw.lcounts[c];
         for (uint32_t i = lane; i < cnt; i += 64) {
             const uint32_t s = log[i];                     // a walker's pos: masked, always inside the table
@@ -971,49 +998,47 @@ k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict
 
 // After k_build_wave: the valid slot range (hj_device.h, Counters) = the owned stretch [ownLo, ownHiEx) joined
 // with the blocks deferred tuples start from (+1: a probe walk spills at most probeLen - 1 slots). If it reaches
-// the table's end (walks wrap there) the whole table is made valid. One wavefront. (Round 3 tried this fold inside
+// the table's end the whole table is made valid (set_valid_range). One wavefront. (Round 3 tried this fold inside
 // k_wave_fill_edges, every workgroup for itself, to save the launch: 4 us at 2^22 -- and 55 us at 2^30, with 128 or
 // with 1024 workgroups, against 4.4 + 4.9 us for the two launches: taken back.)
 __global__ void k_wave_finalize_range(Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
 {
     if (blockIdx.x != 0 || threadIdx.x >= 64 || gate_closed(gate)) return;
-    // the two maxima: what was written directly + the 64 shards (hj_device.h, Counters), one shard per lane
-    static_assert(Counters::kShards == 64, "one shard per lane of the single wavefront this kernel runs as");
-    unsigned long long usedLoInvAll = ctr->shard[threadIdx.x & 63].usedLoInv, usedHi1All = ctr->shard[threadIdx.x & 63].usedHi1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long a = __shfl_xor(usedLoInvAll, off, 64), b = __shfl_xor(usedHi1All, off, 64);
-        usedLoInvAll = a > usedLoInvAll ? a : usedLoInvAll; usedHi1All = b > usedHi1All ? b : usedHi1All;
-    }
-    usedLoInvAll = ctr->usedLoInv > usedLoInvAll ? ctr->usedLoInv : usedLoInvAll;
-    usedHi1All = ctr->usedHi1 > usedHi1All ? ctr->usedHi1 : usedHi1All;
+    const UsedBlocks used = fold_used_blocks(ctr);
     if (threadIdx.x != 0) return;
     unsigned long long lo = ctr->ownLo, hiEx = ctr->ownHiEx;
-    const unsigned long long hi1 = usedHi1All;
-    if (hi1) {
-        const unsigned long long dlo = (unsigned long long)(uint32_t)~(uint32_t)usedLoInvAll << 9, dhi = (hi1 + 1) << 9;
+    if (used.hi1) {
+        const unsigned long long dlo = (unsigned long long)(uint32_t)~(uint32_t)used.loInv << 9, dhi = (used.hi1 + 1) << 9;
         lo = dlo < lo ? dlo : lo; hiEx = dhi > hiEx ? dhi : hiEx;
     }
-    if (hiEx + 512 >= tableSize) { lo = 0; hiEx = tableSize; }
-    ctr->validLo = lo; ctr->validHiEx = hiEx;
+    set_valid_range(ctr, lo, hiEx, tableSize);
 }
 
 // Slots of the valid range (+512 slots of defined contents past it, + the slack past the table) that no wavefront
-// owned: [validLo, ownLo) and [ownHiEx, validHiEx + 512).
+// owned: [validLo, ownLo) and [ownHiEx, validHiEx + 512). W = the table's word: uint64_t packed slots, or uint32_t, the key
+// plane of the 4-byte formats; the empty pattern is all ones in both, written 16 bytes per store.
+// plane2 != nullptr (the planar retire's index plane): the same stretches there read empty too -- that is everywhere a
+// deferred walk can step outside the owned range (the valid range covers the blocks the walks start from + one)
+template <class W>
 __global__ void __launch_bounds__(kBlock)
-k_wave_fill_edges(uint64_t* __restrict__ table, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
+k_wave_fill_edges(W* __restrict__ table, W* __restrict__ plane2, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
 {
     if (gate_closed(gate)) return;
-    const ulonglong2 e = make_ulonglong2(kEmpty, kEmpty);
-    ulonglong2* t2 = reinterpret_cast<ulonglong2*>(table);
+    constexpr uint32_t kPerStore = sizeof(uint4) / sizeof(W);            // all bounds are multiples of 128 (granules) or 512
+    const uint4 e = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     const uint64_t stride = (uint64_t)gridDim.x * kBlock, t0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint64_t hi = ctr->validHiEx + 512;
     hi = hi < tableSize ? hi : tableSize;
-    const uint64_t a0 = ctr->validLo >> 1, a1 = ctr->ownLo >> 1;          // all bounds are even (granules / blocks)
-    for (uint64_t v = a0 + t0; v < a1; v += stride) t2[v] = e;
-    const uint64_t b0 = ctr->ownHiEx >> 1, b1 = hi >> 1;
-    for (uint64_t v = b0 + t0; v < b1; v += stride) t2[v] = e;
-    if (blockIdx.x == 0 && threadIdx.x < kTableSlack) table[tableSize + threadIdx.x] = kEmpty;
+    const uint64_t a0 = ctr->validLo / kPerStore, a1 = ctr->ownLo / kPerStore;
+    const uint64_t b0 = ctr->ownHiEx / kPerStore, b1 = hi / kPerStore;
+    auto fill = [&](W* plane) {
+        uint4* const p4 = reinterpret_cast<uint4*>(plane);
+        for (uint64_t v = a0 + t0; v < a1; v += stride) p4[v] = e;
+        for (uint64_t v = b0 + t0; v < b1; v += stride) p4[v] = e;
+    };
+    fill(table);
+    if constexpr (sizeof(W) == sizeof(uint32_t)) { if (plane2) fill(plane2); }      // only the 4-byte formats have a second plane
+    if (blockIdx.x == 0 && threadIdx.x < kTableSlack) table[tableSize + threadIdx.x] = (W)~(W)0;
 }
 
 
@@ -1031,8 +1056,8 @@ k_wave_validate(const DeferredEntry* __restrict__ queue, const uint32_t* __restr
     const uint32_t nOut = dcounts[c - 1], nIn = pcounts[c];
     bool ok = nOut == nIn && nIn <= kWvPredCap;
     if (ok && nIn) {
-        const DeferredEntry* out = queue + (uint64_t)(c - 1) * sliceLen;
-        const uint64_t* in = reinterpret_cast<const uint64_t*>(queue + (uint64_t)(c + 1) * sliceLen) - kWvPredCap;
+        const DeferredEntry* out = slice_deferred(queue, c - 1, sliceLen);
+        const uint64_t* in = slice_crossers(queue, c, sliceLen);
         for (uint32_t i = 0; i < nOut && ok; ++i) {
             const uint64_t v = out[i].packed;
             bool found = false;
@@ -1059,34 +1084,8 @@ __global__ void k_wave_decide(Counters* __restrict__ ctr, uint64_t tableSize, ui
         return;
     }
     if (threadIdx.x != 0) return;
-    unsigned long long lo = ctr->ownLo, hiEx = ctr->ownHiEx;
-    if (hiEx + 512 >= tableSize) { lo = 0; hiEx = tableSize; }
-    ctr->validLo = lo; ctr->validHiEx = hiEx;
+    set_valid_range(ctr, ctr->ownLo, ctr->ownHiEx, tableSize);
     ctr->tableFormat = kFormatKeys4;
-}
-
-// compact counterpart of k_wave_fill_edges: 4-byte empties over [validLo, ownLo) and [ownHiEx, validHiEx + 512) + slack
-// index != nullptr (the planar retire): the same stretches of the index plane read empty too -- that is everywhere a
-// deferred walk can step outside the owned range (the valid range covers the blocks the walks start from + one)
-__global__ void __launch_bounds__(kBlock)
-k_wave_fill_edges_keys(uint32_t* __restrict__ keys, uint32_t* __restrict__ index, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
-{
-    if (gate_closed(gate)) return;
-    const uint4 e = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    uint4* t4 = reinterpret_cast<uint4*>(keys);
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock, t0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    uint64_t hi = ctr->validHiEx + 512;
-    hi = hi < tableSize ? hi : tableSize;
-    const uint64_t a0 = ctr->validLo >> 2, a1 = ctr->ownLo >> 2;          // all bounds are multiples of 128 (granules) or 512
-    for (uint64_t v = a0 + t0; v < a1; v += stride) t4[v] = e;
-    const uint64_t b0 = ctr->ownHiEx >> 2, b1 = hi >> 2;
-    for (uint64_t v = b0 + t0; v < b1; v += stride) t4[v] = e;
-    if (index) {
-        uint4* i4 = reinterpret_cast<uint4*>(index);
-        for (uint64_t v = a0 + t0; v < a1; v += stride) i4[v] = e;
-        for (uint64_t v = b0 + t0; v < b1; v += stride) i4[v] = e;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < kTableSlack) keys[tableSize + threadIdx.x] = 0xFFFFFFFFu;
 }
 
 __global__ void k_set_variant(Counters* __restrict__ ctr, uint32_t v)
@@ -1098,8 +1097,6 @@ void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s) { hipLaunchKer
 // ---- host side ----------------------------------------------------------------------------------------------------
 size_t wave_lds_bytes() { return kWvLdsBytes; }
 bool wave_supported(uint64_t tableSize) { return tableSize >= (uint64_t)kWvWin; }
-uint32_t wave_max_chunks(int nCU) { return kWvWavesPerCu * kWvMaxRounds * (uint32_t)nCU; }
-size_t wave_bounds_bytes(int nCU) { return (6 * (size_t)wave_max_chunks(nCU) + 4) * sizeof(uint32_t); }   // raw, bounds (+1), starts (+1), dcounts, ccounts, pcounts
 constexpr uint32_t kWvCompactMaxProbe = 32;         // the largest probeLength the compact build takes
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen)
 {
@@ -1124,122 +1121,109 @@ static uint64_t wave_chunk_len(uint64_t n, int nCU)
     const uint64_t chunks = (uint64_t)resident * rounds;
     uint64_t chunkLen = (n + chunks - 1) / chunks;
     chunkLen = (chunkLen + kWvTile - 1) / kWvTile * kWvTile;
-    return chunkLen < (uint64_t)kWvTile * 4 ? (uint64_t)kWvTile * 4 : chunkLen;
+    return chunkLen < kWvShortestChunk ? kWvShortestChunk : chunkLen;
 }
-static uint64_t wave_slice_len(uint64_t chunkLen) { return chunkLen + kWvLook + kWvOverlap; }
-size_t wave_queue_bytes(uint64_t n, int nCU)
-{
-    const uint64_t chunkLen = wave_chunk_len(n, nCU);
-    return (size_t)(((n + chunkLen - 1) / chunkLen) * wave_slice_len(chunkLen) + 64) * sizeof(DeferredEntry);
-}
-
-WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf)
-{
-    const uint32_t maxChunks = wave_max_chunks(nCU);
-    const uint64_t chunkLen = wave_chunk_len(n, nCU);
-    return WaveSlices{(uint32_t)((n + chunkLen - 1) / chunkLen), (uint32_t)wave_slice_len(chunkLen),
-                      static_cast<const uint32_t*>(boundsBuf) + 4 * (size_t)maxChunks + 2};
-}
-const uint32_t* wave_bounds_ptr(int nCU, const void* boundsBuf) { return static_cast<const uint32_t*>(boundsBuf) + wave_max_chunks(nCU); }
-size_t wave_conflict_bytes(uint64_t n, int nCU) { return wave_queue_bytes(n, nCU) / sizeof(DeferredEntry) * sizeof(uint64_t); }
-
+// the geometry of a build: every other function takes it from here. A slice has room for the chunk and for what the seams
+// on either side may add to it (the pre-pass moves a seam forward by less than kWvLook; kWvOverlap positions of the next chunk)
 WaveLayout wave_layout(uint64_t n, int nCU)
 {
+    static_assert(kWvShortestChunk > kWvLook + kWvOverlap, "a seam may move by less than the shortest chunk");
+    static_assert(kWvShadow + kWvOverlap == (uint32_t)kWvTile, "shadow zone + head zone = the first tile of a compact chunk");
     const uint64_t chunkLen = wave_chunk_len(n, nCU);
-    return WaveLayout{chunkLen, (n + chunkLen - 1) / chunkLen, wave_slice_len(chunkLen), kWvTileTuples, kGranSlots, kWvGran,
+    return WaveLayout{chunkLen, (n + chunkLen - 1) / chunkLen, chunkLen + kWvLook + kWvOverlap, kWvTileTuples, kGranSlots, kWvGran,
                       kWvLook, kWvOverlap, kWvShadow, kWvTail, kWvPredCap, kWvCompactMaxProbe};
 }
-WaveSeams wave_seams(int nCU, const void* boundsBuf)
+static size_t wave_queue_entries(const WaveLayout& w) { return (size_t)(w.nChunks * w.sliceLen + 64); }
+size_t wave_queue_bytes(uint64_t n, int nCU) { return wave_queue_entries(wave_layout(n, nCU)) * sizeof(DeferredEntry); }
+// the conflict list of the bucketised table: a slice per chunk like the deferred queue's, of 8-byte entries
+size_t wave_conflict_bytes(uint64_t n, int nCU) { return wave_queue_entries(wave_layout(n, nCU)) * sizeof(uint64_t); }
+WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf)
 {
-    // the carving of launch_build_wave: raw, bounds (+1), starts (+1), dcounts, ccounts, pcounts
-    const size_t maxChunks = wave_max_chunks(nCU);
-    const uint32_t* const bounds = static_cast<const uint32_t*>(boundsBuf) + maxChunks;
-    const uint32_t* const starts = bounds + maxChunks + 1;
-    return WaveSeams{starts, bounds, starts + maxChunks + 1 + 2 * maxChunks};
+    const WaveLayout w = wave_layout(n, nCU);
+    return WaveSlices{(uint32_t)w.nChunks, (uint32_t)w.sliceLen, WaveScratch(nCU, boundsBuf).ccounts};
 }
 
 hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, int parts, int mode, KernelEvents kev)
 {
     const bool htm = buf.htmConflicts != nullptr;
     const bool compact = mode == kWaveCompact, planar = mode == kWavePlanar;
+    // (planar + bucketised is refused here: the dirty-log counts live in the conflict counts' words, WaveScratch::lcounts)
     if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact || planar)) return hipErrorInvalidValue;
     if (!j.key32 && j.hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
-    const uint32_t maxChunks = wave_max_chunks(j.nCU);
-    const uint64_t chunkLen = wave_chunk_len(j.n, j.nCU);
-    static_assert(kWvTile * 4 > (int)(kWvLook + kWvOverlap), "a seam may move by less than the shortest chunk");
-    static_assert(kWvShadow + kWvOverlap == (uint32_t)kWvTile, "shadow zone + head zone = the first tile of a compact chunk");
-    const uint32_t sliceLen = (uint32_t)wave_slice_len(chunkLen);
-    const uint32_t nChunks = (uint32_t)((j.n + chunkLen - 1) / chunkLen);
-    uint32_t* const raw = static_cast<uint32_t*>(buf.bounds);
-    uint32_t* const bounds = raw + maxChunks;                 // nChunks + 1 entries
-    uint32_t* const starts = bounds + maxChunks + 1;          // nChunks + 1 entries
-    uint32_t* const dcounts = starts + maxChunks + 1;
-    uint32_t* const ccounts = dcounts + maxChunks;            // == wave_conflict_layout(...).counts
-    uint32_t* const pcounts = ccounts + maxChunks;
+    const WaveLayout w = wave_layout(j.n, j.nCU);
+    const uint32_t chunkLen = (uint32_t)w.chunkLen, sliceLen = (uint32_t)w.sliceLen, nChunks = (uint32_t)w.nChunks;
+    const WaveScratch ws(j.nCU, buf.bounds);
+    DeferredEntry* const queue = static_cast<DeferredEntry*>(buf.queue);
+    const uint64_t mask = j.tableSize - 1;
     const uint32_t numGran = (uint32_t)(j.tableSize >> kGranShift);
     // workgroups a device of nCU compute units holds at once (the rotation of issue priorities goes by it)
     const uint32_t residentWG = kWvWavesPerCu * (uint32_t)(j.nCU > 0 ? j.nCU : 256) / (uint32_t)kWvWaves;
+    const std::true_type yes{};
+    const std::false_type no{};
     hipError_t e;
     const dim3 gRaw((nChunks + 1 + kBlock / 64 - 1) / (kBlock / 64)), gMain((nChunks + kWvWaves - 1) / kWvWaves);
     if (parts & kWavePre) {
-        if (htm) hipLaunchKernelGGL((k_wave_seams<false, true>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
-        else if (j.key32) hipLaunchKernelGGL((k_wave_seams<true, false>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
-        else hipLaunchKernelGGL((k_wave_seams<false, false>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, (uint32_t)chunkLen, nChunks, j.tableSize - 1, j.hshift, starts, raw, gate);
-        hipLaunchKernelGGL(k_wave_bounds_scan, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, j.s, raw, nChunks, numGran, bounds, gate);
+        auto seams = [&](auto k32, auto htmTag) {
+            hipLaunchKernelGGL((k_wave_seams<decltype(k32)::value, decltype(htmTag)::value>), gRaw, dim3(kBlock), 0, j.s, j.R, j.n, chunkLen,
+                               nChunks, mask, j.hshift, ws.starts, ws.raw, gate);
+        };
+        // every instantiation there is: the bucketised table's hash on tuples; else the key format
+        if (htm) seams(no, yes);
+        else with_flag(j.key32, [&](auto k32) { seams(k32, no); });
+        hipLaunchKernelGGL(k_wave_bounds_scan, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, j.s, ws.raw, nChunks, numGran, ws.bounds, gate);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (parts & kWaveMain) {
         if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
-#define HJ_WV_LAUNCH(K32, CHK, HTM, CMP, PLN)                                                                        \
-    hipLaunchKernelGGL((k_build_wave<K32, CHK, HTM, CMP, PLN>), gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, \
-                       nChunks, starts, bounds, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.idxBase, j.sc,       \
-                       static_cast<DeferredEntry*>(buf.queue), dcounts, j.ctr, gate, buf.htmConflicts, ccounts, residentWG, pcounts)
-        if (htm) HJ_WV_LAUNCH(false, false, true, false, false);
-        else if (compact) {
-            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, true, false); else HJ_WV_LAUNCH(false, true, false, true, false); }
-            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, true, false); else HJ_WV_LAUNCH(false, false, false, true, false); }
-        }
-        else if (planar) {
-            if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false, true); else HJ_WV_LAUNCH(false, true, false, false, true); }
-            else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false, true); else HJ_WV_LAUNCH(false, false, false, false, true); }
-        }
-        else if (j.sc.mask) { if (j.key32) HJ_WV_LAUNCH(true, true, false, false, false); else HJ_WV_LAUNCH(false, true, false, false, false); }
-        else { if (j.key32) HJ_WV_LAUNCH(true, false, false, false, false); else HJ_WV_LAUNCH(false, false, false, false, false); }
-#undef HJ_WV_LAUNCH
+        auto build = [&](auto k32, auto chk, auto htmTag, auto cmp, auto pln) {
+            hipLaunchKernelGGL((k_build_wave<decltype(k32)::value, decltype(chk)::value, decltype(htmTag)::value, decltype(cmp)::value, decltype(pln)::value>),
+                               gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, nChunks, ws.starts, ws.bounds, j.table, mask,
+                               j.hshift, j.probeLen, j.idxBase, j.sc, queue, ws.dcounts, j.ctr, gate, buf.htmConflicts, ws.ccounts,
+                               residentWG, ws.pcounts);
+        };
+        // every instantiation there is: the bucketised table on tuples without a shard check; else key format x "counts
+        // foreign tuples" for each of the three modes
+        if (htm) build(no, no, yes, no, no);
+        else with_flag(j.key32, [&](auto k32) {
+            with_flag(j.sc.mask != 0, [&](auto chk) {
+                if (compact) build(k32, chk, no, yes, no);
+                else if (planar) build(k32, chk, no, no, yes);
+                else build(k32, chk, no, no, no);
+            });
+        });
         if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
         if (compact) {
             // the seams check out or the classic build takes over (Counters::variant := 3)
             hipLaunchKernelGGL(k_wave_validate, dim3((nChunks + kBlock - 1) / kBlock), dim3(kBlock), 0, j.s,
-                               static_cast<const DeferredEntry*>(buf.queue), dcounts, pcounts, nChunks, sliceLen, j.ctr, gate);
+                               static_cast<const DeferredEntry*>(queue), ws.dcounts, ws.pcounts, nChunks, sliceLen, j.ctr, gate);
             hipLaunchKernelGGL(k_wave_decide, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, 3u, gate);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (!(parts & kWaveTail)) return hipSuccess;
+    uint32_t* const keys = reinterpret_cast<uint32_t*>(j.table);
     if (compact) {
-        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(512), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table), nullptr, j.ctr, j.tableSize, gate);
+        hipLaunchKernelGGL(k_wave_fill_edges<uint32_t>, dim3(512), dim3(kBlock), 0, j.s, keys, nullptr, j.ctr, j.tableSize, gate);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_wave_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, gate);
-    DeferredEntry* const queue = static_cast<DeferredEntry*>(buf.queue);
     const dim3 gDef((nChunks + kBlock / 64 - 1) / (kBlock / 64));   // one wavefront per slice
+    auto deferred = [&](auto htmTag, auto pln, uint32_t* ccounts, const uint32_t* route, PlanarWalk pw) {
+        hipLaunchKernelGGL((k_wave_deferred<decltype(htmTag)::value, decltype(pln)::value>), gDef, dim3(kBlock), 0, j.s, queue, ws.dcounts,
+                           nChunks, sliceLen, j.table, mask, j.hshift, j.probeLen, j.ctr, gate, buf.htmConflicts, ccounts, route, pw);
+    };
     if (planar) {
-        // the log counts take the place of the bucketised table's conflict counts, which an open-addressing build never uses
-        const PlanarWalk pw{j.R, j.key32, j.idxBase, ccounts};
+        const PlanarWalk pw{j.R, j.key32, j.idxBase, ws.lcounts};
         // 1024 workgroups: the compact road's 512 for one plane of 4-byte words, doubled for two (4.9 us at 2^30, as the packed fill)
-        hipLaunchKernelGGL(k_wave_fill_edges_keys, dim3(1024), dim3(kBlock), 0, j.s, reinterpret_cast<uint32_t*>(j.table),
-                           planar_index_plane(j.table, j.tableSize), j.ctr, j.tableSize, gate);
-        hipLaunchKernelGGL((k_wave_deferred<false, true>), gDef, dim3(kBlock), 0, j.s, queue, dcounts, nChunks, sliceLen, j.table,
-                           j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr, pw);
-        hipLaunchKernelGGL(k_wave_fixup, gDef, dim3(kBlock), 0, j.s, queue, dcounts, nChunks, sliceLen, j.table, j.tableSize, j.ctr, gate, pw);
+        hipLaunchKernelGGL(k_wave_fill_edges<uint32_t>, dim3(1024), dim3(kBlock), 0, j.s, keys, planar_index_plane(j.table, j.tableSize),
+                           j.ctr, j.tableSize, gate);
+        deferred(no, yes, nullptr, nullptr, pw);
+        hipLaunchKernelGGL(k_wave_fixup, gDef, dim3(kBlock), 0, j.s, queue, ws.dcounts, nChunks, sliceLen, j.table, j.tableSize, j.ctr, gate, pw);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_wave_fill_edges, dim3(2048), dim3(kBlock), 0, j.s, j.table, j.ctr, j.tableSize, gate);
-    if (htm) hipLaunchKernelGGL((k_wave_deferred<true, false>), gDef, dim3(kBlock), 0, j.s, queue, dcounts,
-                                nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, buf.htmConflicts, ccounts,
-                                buf.htmRoute ? bounds : nullptr, PlanarWalk{});
-    else hipLaunchKernelGGL((k_wave_deferred<false, false>), gDef, dim3(kBlock), 0, j.s, queue, dcounts,
-                            nChunks, sliceLen, j.table, j.tableSize - 1, j.hshift, j.probeLen, j.ctr, gate, nullptr, nullptr, nullptr, PlanarWalk{});
+    hipLaunchKernelGGL(k_wave_fill_edges<uint64_t>, dim3(2048), dim3(kBlock), 0, j.s, j.table, nullptr, j.ctr, j.tableSize, gate);
+    if (htm) deferred(yes, no, ws.ccounts, buf.htmRoute ? ws.bounds : nullptr, PlanarWalk{});
+    else deferred(no, no, nullptr, nullptr, PlanarWalk{});
     return hipGetLastError();
 }
 

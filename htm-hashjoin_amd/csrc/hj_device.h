@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace hj {
 
 // A table slot holds (inputIndex << 32 | key32). All-ones is "empty" so that a
@@ -44,6 +46,23 @@ __device__ __forceinline__ uint32_t lane_rank(unsigned long long m)
     (void)m; return 0u;         // host pass of hipcc: parsed, never called
 #endif
 }
+
+// (index << 32 | key): a table slot, a deferred tuple, an entry of a conflict list
+__host__ __device__ __forceinline__ uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
+// sums over the wavefront (32- or 64-bit values), valid in lane 0. Several at once, in place: their shuffles interleave,
+// one step of every sum after the other, instead of one chain of six dependent shuffles per sum.
+template <class... T>
+__device__ __forceinline__ void wave_sum_all(T&... v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ((v += __shfl_down(v, off, 64)), ...);
+}
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) { wave_sum_all(v); return v; }
+// A runtime flag becomes a compile-time one: f(std::true_type{}) or f(std::false_type{}). The launchers nest it to pick a
+// kernel's instantiation -- and list, in ONE place per kernel, the combinations that exist at all.
+template <class F>
+inline void with_flag(bool flag, F&& f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
 
 // Optional shard-membership check riding on build and probe (hj_set_shard_check): a tuple is "foreign" when its
 // destination digit ((key - bias) >> shift) & mask differs from id. mask = 0 (and id = 0) switches it off at no
@@ -156,6 +175,27 @@ __device__ __forceinline__ uint32_t wave_umin(uint32_t v)
 __device__ inline Counters::Shard* counter_shard(Counters* ctr)
 {
     return &ctr->shard[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (Counters::kShards - 1)];
+}
+// The two maxima (usedLoInv / usedHi1: the 512-slot blocks an LDS build claimed or deferred into) as the finalize kernels
+// need them. One wavefront, a shard per lane: what was written directly + the 64 shards; the result in every lane.
+struct UsedBlocks { unsigned long long loInv, hi1; };
+__device__ __forceinline__ UsedBlocks fold_used_blocks(const Counters* __restrict__ ctr)
+{
+    static_assert(Counters::kShards == 64, "one shard per lane of the single wavefront the finalize kernels run as");
+    unsigned long long loInv = ctr->shard[threadIdx.x & 63].usedLoInv, hi1 = ctr->shard[threadIdx.x & 63].usedHi1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long a = __shfl_xor(loInv, off, 64), b = __shfl_xor(hi1, off, 64);
+        loInv = a > loInv ? a : loInv; hi1 = b > hi1 ? b : hi1;
+    }
+    return UsedBlocks{ctr->usedLoInv > loInv ? ctr->usedLoInv : loInv, ctr->usedHi1 > hi1 ? ctr->usedHi1 : hi1};
+}
+// The valid slot range [lo, hiEx) of a build (Counters::validLo / validHiEx). The 512 slots past it are read too, and
+// probe walks wrap at the table's end: a range that reaches it makes the whole table valid.
+__device__ __forceinline__ void set_valid_range(Counters* __restrict__ ctr, unsigned long long lo, unsigned long long hiEx, uint64_t tableSize)
+{
+    if (hiEx + 512 >= tableSize) { lo = 0; hiEx = tableSize; }
+    ctr->validLo = lo; ctr->validHiEx = hiEx;
 }
 // host, on a copy of the counters: totals = what was added directly + the shards
 inline void fold_counter_shards(Counters* h)
@@ -298,10 +338,43 @@ constexpr uint32_t kOwnMaxChunks = 8192;
 constexpr uint32_t kWvGranShift = 7;      // retire granule: 128 slots = 1 KiB
 constexpr uint32_t kWvRingGran = 8;       // ring = 8 granules = 1024 slots = 8 KiB per wavefront
 constexpr uint32_t kWvTileTuples = 512;   // tuples per wavefront tile
+constexpr uint32_t kWvWavesPerCu = 16;    // resident wavefronts per CU (what the rings' LDS allows)
+constexpr uint32_t kWvMaxRounds = 8;      // chunks <= resident wavefronts x rounds (wave_layout)
 size_t wave_lds_bytes();
 bool   wave_supported(uint64_t tableSize);
-size_t wave_bounds_bytes(int nCU);
-size_t wave_queue_bytes(uint64_t n, int nCU);   // deferred queue: one slice per chunk
+// How n tuples are cut into chunks on nCU compute units (wave_layout: the ONLY place that works it out; hj_wave_layout_info
+// reports it) and the constants the seam zones of the compact build are made of, taken from the kernel's own
+struct WaveLayout {
+    uint64_t chunkLen, nChunks, sliceLen;
+    uint32_t tileTuples, granSlots, ringGran, look, overlap, shadow, tail, predCap, compactMaxProbe;
+};
+WaveLayout wave_layout(uint64_t n, int nCU);
+// The bounds buffer (WaveBufs::bounds): six arrays of uint32 words, one entry per chunk, sized for the most chunks a device
+// of nCU compute units is ever cut into. THE description of that buffer: whoever sizes, carves or reads it goes through here.
+struct WaveScratch {
+    uint32_t* raw;       // pre-pass: the granule each chunk's seam sample starts in (kNone: no valid tuple)
+    uint32_t* bounds;    // [nChunks + 1] chunk c owns granules [bounds[c], bounds[c + 1])
+    uint32_t* starts;    // [nChunks + 1] chunk c's tuples are R[starts[c] .. starts[c + 1])
+    uint32_t* dcounts;   // entries at the front of each slice of the deferred queue (compact build: crossers out)
+    uint32_t* ccounts;   // bucketised table: entries in each slice of the conflict list
+    uint32_t* pcounts;   // compact build: crossers each chunk let in (its list: the tail of its queue slice)
+    // planar retire: entries of each slice's dirty log. The SAME words as ccounts: a build is planar or bucketised, never
+    // both (launch_build_wave refuses it; k_build_wave and k_wave_deferred have no such instantiation)
+    uint32_t* lcounts;
+    size_t words;
+    WaveScratch(int nCU, void* buf)
+    {
+        const size_t maxChunks = (size_t)kWvWavesPerCu * kWvMaxRounds * (size_t)nCU;
+        words = 0;
+        auto take = [&](size_t k) { uint32_t* const p = buf ? static_cast<uint32_t*>(buf) + words : nullptr; words += k; return p; };
+        raw = take(maxChunks); bounds = take(maxChunks + 1); starts = take(maxChunks + 1);
+        dcounts = take(maxChunks); ccounts = take(maxChunks); pcounts = take(maxChunks);
+        lcounts = ccounts;
+    }
+    size_t bytes() const { return words * sizeof(uint32_t); }
+};
+inline size_t wave_bounds_bytes(int nCU) { return WaveScratch(nCU, nullptr).bytes(); }
+size_t wave_queue_bytes(uint64_t n, int nCU);   // deferred queue: one slice per chunk (its tenants: hj_build_wave.hip, "queue slice")
 // bounds pre-pass -> k_build_wave -> valid range + edge fill -> phase B. queue: wave_queue_bytes(n, nCU), used as one
 // slice per chunk (a wavefront's deferred tuples go to ITS slice: no atomics in the kernel).
 // parts: kWavePre = the seam / bounds pre-pass, kWaveMain = the build kernel (kev brackets it), kWaveTail = valid range,
@@ -318,29 +391,17 @@ constexpr int kWaveClassic = 0, kWaveCompact = 1, kWavePlanar = 2;
 // htmRoute: the deferred phase files its conflicts under the chunk that owns their bucket (the LDS chain phase needs that)
 struct WaveBufs { void* bounds; void* queue; uint64_t* htmConflicts = nullptr; bool htmRoute = false; };
 hipError_t launch_build_wave(const BuildJob& job, const WaveBufs& buf, Gate gate, int parts, int mode = kWaveClassic, KernelEvents kev = {});
-const uint32_t* wave_bounds_ptr(int nCU, const void* boundsBuf);     // chunk c owns granules [bounds[c], bounds[c + 1])
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen);
 void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s);
 // htmConflicts != nullptr: the bucketised table of --algo htm (home_slot_htm, probeLen must be 3, tuples only); every
 // tuple that runs out of budget is appended as (index << 32 | key) to its chunk's slice of htmConflicts (slices and
-// their counts as wave_conflict_layout describes)
+// their counts as wave_conflict_layout describes: WaveScratch::ccounts)
 struct WaveSlices { uint32_t nChunks, sliceLen; const uint32_t* counts; };
 WaveSlices own_conflict_layout(uint64_t n, int nCU, void* countsBuf);
 size_t own_conflict_bytes(uint64_t n, int nCU);
 size_t own_conflict_count_bytes(uint64_t n, int nCU);
 WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf);
 size_t wave_conflict_bytes(uint64_t n, int nCU);
-// planning facts of the ring builds (hj_wave_layout_info): how n tuples are cut into chunks on nCU compute units, and the
-// constants the seam zones of the compact build are made of, taken from the kernel's own
-struct WaveLayout {
-    uint64_t chunkLen, nChunks, sliceLen;
-    uint32_t tileTuples, granSlots, ringGran, look, overlap, shadow, tail, predCap, compactMaxProbe;
-};
-WaveLayout wave_layout(uint64_t n, int nCU);
-// what the pre-pass (starts, bounds: nChunks + 1 words each) and the compact build (pcounts: nChunks words) left in the
-// bounds buffer (hj_wave_seams)
-struct WaveSeams { const uint32_t *starts, *bounds, *pcounts; };
-WaveSeams wave_seams(int nCU, const void* boundsBuf);
 
 // ---- bucketised table of --algo htm (defined in hj_htm.hip) -----------------
 uint32_t htm_num_buckets(uint64_t rSize);         // nextpow2(rSize / 3 + 1), HTMHashBuild.hpp:61-62

@@ -37,13 +37,6 @@ namespace hj {
 
 constexpr uint32_t kHtmProbeLen = 3;                 // tuples per bucket (Bucket::tuples[3])
 
-__device__ __forceinline__ unsigned long long htm_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // ---- build without locality: global atomics, one contiguous piece of R per workgroup (conflicts go to ITS slice) ----
 __global__ void __launch_bounds__(kBlock)
 k_htm_build_global(const uint64_t* __restrict__ R, uint64_t n, uint32_t sliceLen, uint64_t* __restrict__ table,
@@ -74,7 +67,7 @@ k_htm_build_global(const uint64_t* __restrict__ R, uint64_t n, uint32_t sliceLen
     }
     __syncthreads();
     if (threadIdx.x == 0) ccounts[blockIdx.x] = sCount;
-    drops = htm_wave_sum(drops); dropSum = htm_wave_sum(dropSum); inSum = htm_wave_sum(inSum); bad = htm_wave_sum(bad);
+    drops = wave_sum(drops); dropSum = wave_sum(dropSum); inSum = wave_sum(inSum); bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0) {
         Counters::Shard* const sh = counter_shard(ctr);
         if (drops) atomicAdd(&sh->conflicts, drops);
@@ -149,7 +142,7 @@ k_htm_link(uint64_t* __restrict__ table, uint32_t numBuckets, const unsigned int
             overflow[((uint64_t)(first + j) << 2) + 3] = ((uint64_t)(j ? first + j - 1u : 0u) << 32) | (j + 1 < g ? 3u : oc - 3u * (g - 1u));
         groupsSeen += g;
     }
-    groupsSeen = htm_wave_sum(groupsSeen);
+    groupsSeen = wave_sum(groupsSeen);
     if ((threadIdx.x & 63) == 0 && groupsSeen) atomicAdd(&ctr->htmOverflowBuckets, groupsSeen);
 }
 
@@ -363,7 +356,7 @@ k_htm_probe(const uint64_t* __restrict__ S, uint64_t n, const uint64_t* __restri
             p = reinterpret_cast<const ulonglong2*>(overflow + ((uint64_t)next << 2));
         }
     }
-    matches = htm_wave_sum(matches);
+    matches = wave_sum(matches);
     if ((threadIdx.x & 63) == 0 && matches) atomicAdd(&counter_shard(ctr)->matches, matches);
 }
 
@@ -384,7 +377,7 @@ k_htm_sums(const uint64_t* __restrict__ table, uint32_t numBuckets, const uint64
         for (uint32_t j = 0; j < 3; ++j) sum += p[j] == kEmpty ? 0u : (uint32_t)p[j];
         if (isOvf) ovf += sum; else prim += sum;
     }
-    prim = htm_wave_sum(prim); ovf = htm_wave_sum(ovf);
+    prim = wave_sum(prim); ovf = wave_sum(ovf);
     if ((threadIdx.x & 63) == 0) {
         if (prim) atomicAdd(&ctr->tableSumFull, prim);
         if (ovf) atomicAdd(&ctr->htmOverflowSum, ovf);

@@ -28,13 +28,6 @@
 
 namespace hj {
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;  // valid in lane 0
-}
-
 // Adds each wavefront's partial sums to the global counters, one atomic per
 // wavefront and counter (skipped when the wavefront has nothing to add).
 __device__ __forceinline__ void flush_counter(unsigned long long* dst, unsigned long long v)

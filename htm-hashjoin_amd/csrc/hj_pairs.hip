@@ -100,13 +100,6 @@ __device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out
     return pos;
 }
 
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;  // valid in lane 0
-}
-
 // the end of both kernels: the last stage, then the workgroup's share of the counters (one atomic per workgroup and
 // counter: found is the same in every thread; the foreign counts are per lane)
 // Kinds other than INNER: the rows are not the matches, so the lanes' inner matches are summed instead; LEFT also leaves
@@ -118,16 +111,14 @@ __device__ __forceinline__ void stage_finish(Stage& st, const PairsOut& out, uin
     if constexpr (K == kInner) {
         if (threadIdx.x == 0 && st.found) atomicAdd(&counter_shard(ctr)->matches, st.found);
     } else {
-        unsigned long long inner = st.inner;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) inner += __shfl_down(inner, off, kWave);
+        const unsigned long long inner = wave_sum(st.inner);
         if ((threadIdx.x & (kWave - 1)) == 0 && inner) atomicAdd(&counter_shard(ctr)->matches, inner);
         if constexpr (K == kLeft) {
-            const uint32_t unmatched = wave_sum32(st.unmatched);
+            const uint32_t unmatched = wave_sum(st.unmatched);
             if ((threadIdx.x & (kWave - 1)) == 0 && unmatched) atomicAdd(out.cursor + 1, (unsigned long long)unmatched);
         }
     }
-    foreign = wave_sum32(foreign);
+    foreign = wave_sum(foreign);
     if ((threadIdx.x & (kWave - 1)) == 0 && foreign) atomicAdd(&counter_shard(ctr)->foreign, (unsigned long long)foreign);
 }
 

@@ -956,6 +956,44 @@ def test_shard_check_counts_foreign_tuples(variant):
             c.dev_free(p_)
 
 
+@pytest.mark.parametrize("variant,keep,format_", [(2, False, 0), (3, False, 1), (4, False, 1), (3, True, 0)],
+                         ids=["window", "planar", "compact", "packed"])
+def test_shard_check_on_bare_keys_through_the_lds_builds(variant, keep, format_):
+    """hj_set_shard_check riding on hj_build_keys_dev through the workgroup window (variant 2) and through each retire of the
+    ring build: the planar one (variant 3), the compact one (variant 4) and the packed one (variant 3 on a context that
+    keeps row ids) -- the instances of the two build kernels that read bare keys AND count foreign ones. n = 2^14: eight
+    chunks of 2048 tuples, so the rings have seams. `uniform` with its window of 16 is within reach of the rings and of
+    the compact build's seam zones: no hand-over."""
+    n, G, shard = 1 << 14, 4, 1
+    R = oracle.generate_data("uniform", n, n, 16)
+    S = oracle.relS_for("uniform", R)
+    want = oracle.build_probe_seq_ts(R, S, 2 * n, 0, want_table=True)
+    foreign = lambda A: int(((A & np.uint64(G - 1)) != shard).sum())                      # noqa: E731
+    with hj.HashJoinContext(0) as c:
+        c.reserve("atomic", n, S.size, buildVariant=variant, keepRowIds=keep)
+        dR = c.dev_alloc(n * 4 + 16); dS = c.dev_alloc(S.size * 4 + 16)
+        c.copy_h2d(dR + 4, R.astype(np.uint32)); c.copy_h2d(dS + 12, S.astype(np.uint32))
+        c.set_shard_check(G, 0, shard)
+        c.build_keys(dR + 4, n, 0, 2 * n)
+        c.probe_keys(dS + 12, S.size)
+        c.checksums()
+        got = c.fetch()
+        info = c.wave_planar_info()
+        for k in ("conflicts", "totalMatches", "inputSum", "tableSumFull", "conflictSum"):
+            assert got[k] == want[k], (k, got[k], want[k])
+        assert got["foreignTuples"] == foreign(R) + foreign(S)
+        assert np.array_equal(c.export_table(2 * n), want["table"])
+        assert (got["buildVariant"], got["compactFallback"]) == (variant, 0)
+        assert (info["planarFallback"], info["tableFormat"]) == (0, format_), info
+        c.set_shard_check(0)                                       # off again: the same road's instance without the count
+        c.build_keys(dR + 4, n, 0, 2 * n)
+        again = c.fetch()
+        assert (again["foreignTuples"], again["buildVariant"], again["conflicts"]) == (0, variant, want["conflicts"])
+        assert np.array_equal(c.export_table(2 * n), want["table"])
+        assert c.wave_planar_info()["tableFormat"] == format_
+        c.dev_free(dR); c.dev_free(dS)
+
+
 def test_shard_split_flags_payload_bits(ctx):
     """A tuple with payload bits set cannot be told from a valid one once only keys travel: the split sends it as
     key 0 (to shard 0), where the build reports it like hj_build_dev does (HJ_ERR_KEY_RANGE)."""
