@@ -27,6 +27,11 @@ ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 # hj_params.flags: open addressing never leaves the table in the compact 4-byte format; the resident radix join keeps R
 # as {key, row} elements (hj_prj_probe_pairs_dev)
 HJ_FLAG_KEEP_ROW_IDS = 0x1
+# hj_params.flags: the context keeps one bit per R row, set by every INNER / LEFT materialising probe for the R rows of the
+# rows it produces (hj_r_rows_dev turns the bits into rows); needs HJ_FLAG_KEEP_ROW_IDS except on "htm"
+HJ_FLAG_TRACK_R_MATCHES = 0x2
+# hj_r_rows_dev: which rows
+HJ_R_UNMATCHED, HJ_R_MATCHED = 0, 1
 
 # hj_join_kind (hj_probe_join_dev / hj_prj_probe_join_dev) and the R row of a left-outer row without a match
 HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI = 0, 1, 2, 3
@@ -89,6 +94,9 @@ def _declare(lib):
         "hj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
         "hj_probe_join_dev": ([vp, u32, vp, u64, u64, vp, vp, u64], i32),
         "hj_pairs_info": ([vp, P(u64)], i32),
+        "hj_r_marks_clear": ([vp], i32),
+        "hj_r_rows_dev": ([vp, u32, vp, u64], i32),
+        "hj_r_rows_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),

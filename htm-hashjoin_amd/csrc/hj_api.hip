@@ -17,7 +17,7 @@
 using namespace hj;
 
 namespace {
-enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_PAIRS0, EV_PAIRS1, EV_COUNT };
+enum Ev { EV_CLEAR0, EV_BUILD0, EV_BUILD1, EV_KW0, EV_KW1, EV_KC0, EV_KC1, EV_KO0, EV_KO1, EV_PROBE0, EV_PROBE1, EV_PRJ0, EV_PRJ_PART, EV_PRJ1, EV_PRJ_S0, EV_PRJ_S1, EV_RP0, EV_RP_PART, EV_RP_JOIN0, EV_RP1, EV_PAIRS0, EV_PAIRS1, EV_RROWS0, EV_RROWS1, EV_COUNT };
 // every device buffer the library owns (hj_ctx::buf)
 enum Buf {
     B_CTR, B_TABLE,
@@ -29,6 +29,8 @@ enum Buf {
     B_HTM_OVF_COUNT, B_HTM_OVF_BASE, B_HTM_SCAN,
     B_HTM_OVERFLOW,             // overflow buckets (index 0 unused)
     B_PAIRS_CURSOR,             // materialising probe (hj_probe_join_dev): the output cursor, then HJ_JOIN_LEFT's unmatched S tuples
+    B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_device.h)
+    B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -85,6 +87,12 @@ struct hj_ctx {
     uint64_t pairsCapacity = 0;                 // materialising probe (hj_probe_join_dev): the capacity of the last call,
     uint32_t pairsKind = HJ_JOIN_INNER;         // ... its join kind and its sSize (hj_pairs_info)
     uint64_t pairsS = 0;
+    // R-side match marks (HJ_FLAG_TRACK_R_MATCHES): the plane describes the last build -- hj_build_dev or hj_prj_build_dev on
+    // a context reserved with the flag -- while marksBuilt; rows base .. base + rows - 1 are bits 0 .. rows - 1
+    bool marksBuilt = false;
+    uint64_t marksRows = 0, marksBase = 0;
+    bool rRowsCalled = false;                   // hj_r_rows_dev ran since that build; its capacity (hj_r_rows_info)
+    uint64_t rRowsCapacity = 0;
     Counters* hCtr = nullptr;     // pinned copy of the counters
     // PRJ
     PrjPlan plan{};
@@ -197,6 +205,7 @@ int begin_operation(hj_ctx* c, uint64_t rSize, uint64_t sSize, uint64_t tableSiz
     HJ_HIP(c, hipSetDevice(c->device));
     for (bool& b : c->evSet) b = false;
     c->built = c->htmBuilt = c->prjRan = c->resident = false;
+    c->marksBuilt = c->rRowsCalled = false;
     c->wavePreN = 0;
     c->rSize = rSize; c->sSize = sSize; c->tableSize = tableSize;
     HJ_HIP(c, hipMemsetAsync(c->dCtr(), 0, sizeof(Counters), c->stream));
@@ -373,10 +382,22 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
     if (!c || !params) return HJ_ERR_INVALID;
     if (params->algo > HJ_ALGO_AUTO) return fail(c, HJ_ERR_UNKNOWN_ALGO, "hj_reserve: algo");
     if (rSize == 0) return fail(c, HJ_ERR_INVALID, "hj_reserve: rSize == 0");
+    // the marks are indexed by R row: only HJ_ALGO_HTM keeps the rows whatever the flags
+    const bool track = (params->flags & HJ_FLAG_TRACK_R_MATCHES) != 0;
+    if (track && params->algo != HJ_ALGO_HTM && !(params->flags & HJ_FLAG_KEEP_ROW_IDS))
+        return fail(c, HJ_ERR_INVALID, "hj_reserve: HJ_FLAG_TRACK_R_MATCHES needs HJ_FLAG_KEEP_ROW_IDS on open addressing and PRJ / AUTO");
     HJ_HIP(c, hipSetDevice(c->device));
     c->params = *params;
     HJ_HIP(c, hipStreamSynchronize(c->stream));          // buffers may be replaced below; and a new workload starts without an expectation
     *c->hPreferred = 0;
+    if (track) {
+        // one bit per R row in 32-bit words (the sweep reads whole words: rounded up to 16 bytes), and the sweep's workspace
+        bool replaced = false;
+        int rc = c->buf[B_R_MARKS].reserve(c, (((rSize + 31) / 32 + 3) & ~3ull) * sizeof(uint32_t), &replaced);
+        if (!rc) rc = c->buf[B_R_SWEEP].reserve(c, r_sweep_count_words(rSize) * sizeof(uint32_t));
+        if (replaced) c->marksBuilt = c->rRowsCalled = false;       // the plane of the last build is gone
+        if (rc) return rc;
+    }
     if (params->algo == HJ_ALGO_PRJ || params->algo == HJ_ALGO_AUTO) {
         if (rSize >= 0xFFFFFFFFull || sSize >= 0xFFFFFFFFull)
             return fail(c, HJ_ERR_INVALID, "hj_reserve: PRJ sizes must be < 2^32 tuples per device");
@@ -458,6 +479,36 @@ static int sample_variant(hj_ctx* c, const void* d, bool key32, uint64_t n, uint
 }
 
 // Shared by hj_build_dev (DataGen tuples) and hj_build_keys_dev (bare keys of a radix shard).
+// R-side match marks at a build (hj_build_dev / hj_prj_build_dev) of a context reserved with HJ_FLAG_TRACK_R_MATCHES:
+// marks_begin checks that the plane takes rSize rows and zeroes it on the stream, marks_built -- once the build is
+// enqueued -- says what the plane now describes. Neither does anything on a context without the flag.
+static bool tracks(const hj_ctx* c) { return (c->params.flags & HJ_FLAG_TRACK_R_MATCHES) != 0; }
+static size_t marks_bytes(uint64_t rows) { return (size_t)((rows + 31) / 32) * sizeof(uint32_t); }
+static int marks_begin(hj_ctx* c, const char* fn, uint64_t rSize)
+{
+    if (!tracks(c)) return HJ_OK;
+    if (marks_bytes(rSize) > c->buf[B_R_MARKS].bytes || r_sweep_count_words(rSize) * sizeof(uint32_t) > c->buf[B_R_SWEEP].bytes)
+        return fail(c, HJ_ERR_STATE, (std::string(fn) + ": hj_reserve() not called for this rSize (match marks)").c_str());
+    HJ_HIP(c, hipSetDevice(c->device));
+    c->streamAtBuildEnd = false;
+    HJ_HIP(c, hipMemsetAsync(c->buf[B_R_MARKS].p, 0, marks_bytes(rSize), c->stream));
+    return HJ_OK;
+}
+static void marks_built(hj_ctx* c, uint64_t rSize, uint64_t idxBase)
+{
+    if (!tracks(c)) return;
+    c->marksBuilt = true; c->marksRows = rSize; c->marksBase = idxBase;
+    c->rRowsCalled = false;
+}
+// the marks a materialising probe of `kind` sets: none unless the context tracks, the plane describes the table or the
+// resident R being probed, and the kind produces R rows
+static bool marks_for(const hj_ctx* c, uint32_t kind, RMarks* mk)
+{
+    if (!tracks(c) || !c->marksBuilt || kind > HJ_JOIN_LEFT) return false;
+    *mk = RMarks{c->buf[B_R_MARKS].as<uint32_t>(), (uint32_t)c->marksBase, (uint32_t)c->marksRows};
+    return true;
+}
+
 static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32_t hshift,
                         uint64_t tableSize, uint64_t idxBase)
 {
@@ -667,12 +718,20 @@ int hj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idxBase
 {
     if (!c || !dR) return HJ_ERR_INVALID;
     if (c->params.algo == HJ_ALGO_PRJ) return fail(c, HJ_ERR_STATE, "hj_build_dev: context is reserved for PRJ");
-    if (c->params.algo == HJ_ALGO_HTM) return rSize ? build_htm(c, dR, rSize, idxBase) : HJ_ERR_INVALID;
-    if (!is_pow2(rSize) || (2 * rSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
-        return fail(c, HJ_ERR_STATE, "hj_build_dev: hj_reserve() not called for this rSize");
-    // indices stay below 2^32 - 1: (index << 32 | key) of index = key = 0xFFFFFFFF would be the empty pattern
-    if (idxBase + rSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_dev: index range exceeds 2^32 - 1");
-    return build_common(c, dR, false, rSize, 0, 2 * rSize, idxBase);
+    const bool htm = c->params.algo == HJ_ALGO_HTM;
+    if (htm && !rSize) return HJ_ERR_INVALID;
+    if (!htm) {
+        if (!is_pow2(rSize) || (2 * rSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
+            return fail(c, HJ_ERR_STATE, "hj_build_dev: hj_reserve() not called for this rSize");
+        // indices stay below 2^32 - 1: (index << 32 | key) of index = key = 0xFFFFFFFF would be the empty pattern
+        if (idxBase + rSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_build_dev: index range exceeds 2^32 - 1");
+    }
+    // the marks of the build before: cleared in front of the build, outside everything it times
+    int rc;
+    if ((rc = marks_begin(c, "hj_build_dev", rSize))) return rc;
+    rc = htm ? build_htm(c, dR, rSize, idxBase) : build_common(c, dR, false, rSize, 0, 2 * rSize, idxBase);
+    if (rc == HJ_OK) marks_built(c, rSize, idxBase);
+    return rc;
 }
 
 int hj_build_keys_dev(hj_ctx* c, const uint32_t* dKeys, uint64_t n, uint32_t homeShift, uint64_t tableSize)
@@ -680,6 +739,7 @@ int hj_build_keys_dev(hj_ctx* c, const uint32_t* dKeys, uint64_t n, uint32_t hom
     if (!c || (!dKeys && n)) return HJ_ERR_INVALID;
     if (c->params.algo == HJ_ALGO_PRJ || c->params.algo == HJ_ALGO_HTM)
         return fail(c, HJ_ERR_STATE, "hj_build_keys_dev: context is reserved for PRJ / htm");
+    if (tracks(c)) return fail(c, HJ_ERR_STATE, "hj_build_keys_dev: a context reserved with HJ_FLAG_TRACK_R_MATCHES takes no bare keys");
     if (homeShift > 6) return fail(c, HJ_ERR_INVALID, "hj_build_keys_dev: homeShift must be in [0,6]");
     if (!is_pow2(tableSize) || (tableSize + kTableSlack) * sizeof(uint64_t) > c->buf[B_TABLE].bytes)
         return fail(c, HJ_ERR_STATE, "hj_build_keys_dev: hj_reserve() not called for this table size");
@@ -734,8 +794,10 @@ static int probe_join(hj_ctx* c, const char* fn, uint32_t kind, const uint64_t* 
     HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
     if ((rc = record(c, EV_PAIRS0))) return rc;
     const uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();
-    if (c->htmBuilt) launch_htm_probe_pairs(kind, dS, sSize, sIdxBase, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), out, c->nCU, c->dCtr(), c->stream);
-    else launch_probe_pairs(kind, dS, sSize, sIdxBase, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr(), c->stream);
+    RMarks mk;
+    const RMarks* const marks = marks_for(c, kind, &mk) ? &mk : nullptr;
+    if (c->htmBuilt) launch_htm_probe_pairs(kind, dS, sSize, sIdxBase, table, c->htmBuckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), out, c->nCU, c->dCtr(), c->stream, marks);
+    else launch_probe_pairs(kind, dS, sSize, sIdxBase, table, c->tableSize, c->hshift, probe_len(c->params), c->sc, out, c->nCU, c->dCtr(), c->stream, marks);
     if ((rc = record(c, EV_PAIRS1))) return rc;
     HJ_HIP(c, hipGetLastError());
     c->pairsCapacity = capacity; c->pairsKind = kind; c->pairsS = sSize;
@@ -771,6 +833,58 @@ int hj_pairs_info(hj_ctx* c, uint64_t out[4])
     // unmatched S tuples of the call: SEMI wrote one row per matched tuple, ANTI one per unmatched one
     out[3] = c->pairsKind == HJ_JOIN_LEFT ? words[1] : c->pairsKind == HJ_JOIN_SEMI ? c->pairsS - found
            : c->pairsKind == HJ_JOIN_ANTI ? found : 0;
+    return HJ_OK;
+}
+
+// ---- R-side match marks ---------------------------------------------------
+// what the three calls need: a context reserved with the flag whose plane describes its last build
+static int marks_state(hj_ctx* c, const char* fn)
+{
+    const std::string f(fn);
+    if (!tracks(c)) return fail(c, HJ_ERR_STATE, (f + ": context reserved without HJ_FLAG_TRACK_R_MATCHES").c_str());
+    if (!c->marksBuilt) return fail(c, HJ_ERR_STATE, (f + ": the last build was not hj_build_dev / hj_prj_build_dev (or there was none)").c_str());
+    return HJ_OK;
+}
+
+int hj_r_marks_clear(hj_ctx* c)
+{
+    HJ_ENTER(c, true);
+    if (const int rc = marks_state(c, "hj_r_marks_clear")) return rc;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipMemsetAsync(c->buf[B_R_MARKS].p, 0, marks_bytes(c->marksRows), c->stream));
+    return HJ_OK;
+}
+
+int hj_r_rows_dev(hj_ctx* c, uint32_t which, uint32_t* dOutR, uint64_t capacity)
+{
+    HJ_ENTER(c, true);
+    if (const int rc = marks_state(c, "hj_r_rows_dev")) return rc;
+    if (which > HJ_R_MATCHED) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: which must be HJ_R_UNMATCHED or HJ_R_MATCHED");
+    if (capacity && !dOutR) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: output pointer NULL with capacity > 0");
+    HJ_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = record(c, EV_RROWS0))) return rc;
+    const RMarks mk{c->buf[B_R_MARKS].as<uint32_t>(), (uint32_t)c->marksBase, (uint32_t)c->marksRows};
+    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOutR, capacity, c->buf[B_R_SWEEP].as<uint32_t>(), c->stream));
+    if ((rc = record(c, EV_RROWS1))) return rc;
+    c->rRowsCalled = true; c->rRowsCapacity = capacity;
+    return HJ_OK;
+}
+
+int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    if (const int rc = marks_state(c, "hj_r_rows_info")) return rc;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = 0;               // no hj_r_rows_dev since the build
+    out[3] = c->marksRows;
+    if (!c->rRowsCalled) return HJ_OK;
+    uint32_t produced = 0;                      // the word behind the block counts: their total after the scan
+    HJ_HIP(c, hipMemcpy(&produced, c->buf[B_R_SWEEP].as<uint32_t>() + r_sweep_blocks(c->marksRows), sizeof produced, hipMemcpyDeviceToHost));
+    out[0] = produced;
+    out[1] = produced < c->rRowsCapacity ? produced : c->rRowsCapacity;
+    out[2] = (uint64_t)(elapsed_us(c, EV_RROWS0, EV_RROWS1) + 0.5);
     return HJ_OK;
 }
 
@@ -838,6 +952,7 @@ int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
     // the scratch workspace of the passes holds nothing resident: a relation (here) or a slice (hj_prj_probe_dev) whose plan
     // needs more than hj_reserve's (the chunk count is not monotone in the size, see prj_plan) gets a larger one
     if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;
+    if ((rc = marks_begin(c, "hj_prj_build_dev", rSize))) return rc;
     if ((rc = begin_operation(c, rSize, 0, 0))) return rc;
     if ((rc = record(c, EV_PRJ0))) return rc;
     const PrjBuffers buf = prj_buffers(c);
@@ -852,6 +967,7 @@ int hj_prj_build_dev(hj_ctx* c, const uint64_t* dR, uint64_t rSize)
     c->algoUsed = HJ_ALGO_PRJ;
     c->resident = true; c->resPlan = pl; c->resR = rSize; c->resRows = rows;
     c->resProbed = false; c->resProbeOpt = false;
+    marks_built(c, rSize, 0);
     return HJ_OK;
 }
 
@@ -872,8 +988,11 @@ static int prj_probe_rows(hj_ctx* c, uint32_t kind, const uint64_t* dS, uint64_t
     if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;      // R stays resident: see hj_prj_build_dev
     if ((rc = record(c, EV_RP0))) return rc;
     if (pairsCall && (rc = record(c, EV_PAIRS0))) return rc;
+    // only a pairs call marks R rows: the counting probe of a rows context keeps the kernel it ran before there were marks
+    RMarks mk;
+    const RMarks* const marks = pairsCall && marks_for(c, kind, &mk) ? &mk : nullptr;
     HJ_HIP(c, launch_prj_probe_rows(kind, c->resPlan, pl, prj_buffers(c), prj_resident_carve(c->buf[B_PRJ_RES].p, c->resPlan.radixBits, sSize),
-                                    dS, sSize, sIdxBase, out, c->nCU, c->dCtr(), c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream));
+                                    dS, sSize, sIdxBase, out, c->nCU, c->dCtr(), c->ev[EV_RP_PART], c->ev[EV_RP_JOIN0], c->stream, marks));
     c->evSet[EV_RP_PART] = c->evSet[EV_RP_JOIN0] = true;
     if (pairsCall && (rc = record(c, EV_PAIRS1))) return rc;
     if ((rc = record(c, EV_RP1))) return rc;

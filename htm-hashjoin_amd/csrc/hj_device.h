@@ -459,12 +459,50 @@ __device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, u
     const uint32_t tail = lead + 4u * nv;
     if (threadIdx.x < lim - tail) __builtin_nontemporal_store(lds[tail + threadIdx.x], dst + tail + threadIdx.x);
 }
+// R-side match marks (HJ_FLAG_TRACK_R_MATCHES): one bit per R row of the last build, bit (row - base) of words[]; rows =
+// the build's rSize. Set by the MARK instantiations of the three pairs kernels for every R row of a row they produce
+// (written or cut by the capacity alike), read by the sweep of hj_r_marks.hip. Bits only go 0 -> 1 between clears.
+struct RMarks { uint32_t* words; uint32_t base, rows; };
+// what a MARK instantiation takes where the others take PairsOut: the same planes and cursor, and the marks behind them.
+// (A type of its own so that the kernel arguments of the instantiations without marks stay exactly what they were.)
+struct PairsOutMarked : PairsOut { RMarks marks; };
+template <bool MARK> using PairsOutOf = std::conditional_t<MARK, PairsOutMarked, PairsOut>;
+// One produced R row -> its bit. First a relaxed agent-scope LOAD of the word, which L2 serves: a Zipf-hot R row is
+// produced millions of times from every CU, and one word takes a limited number of atomics per microsecond chip-wide.
+// The atomic OR (no value returned) is issued only while the bit reads clear; a stale "clear" costs one redundant OR and
+// is never wrong, because nothing clears a bit while probes run. HJ_NO_ROW (a LEFT row without a match) marks nothing:
+// it is no row of the build, like anything else outside [base, base + rows).
+__device__ __forceinline__ void mark_r_row(const RMarks& mk, uint32_t row)
+{
+    const uint32_t i = row - mk.base;
+    if (i >= mk.rows) return;
+    uint32_t* const w = mk.words + (i >> 5);
+    const uint32_t bit = 1u << (i & 31u);
+    if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) return;
+    __hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the R rows of a stage, as it is read at a flush: neighbouring lanes hold neighbouring pairs
+template <int NT>
+__device__ __forceinline__ void mark_plane(const uint32_t* lds, uint32_t cnt, const RMarks& mk)
+{
+    for (uint32_t i = threadIdx.x; i < cnt; i += NT) mark_r_row(mk, lds[i]);
+}
 uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
 // the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot
+// marks != nullptr (kinds INNER and LEFT only): the MARK instantiation, which also sets the bit of every R row it produces
 void launch_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
-                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
+                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks = nullptr);
 void launch_htm_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
-                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s);
+                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks = nullptr);
+
+// ---- sweep of the R-side match marks (defined in hj_r_marks.hip) ------------
+// The ordered compaction of a mark plane: the rows base + i, i in [0, rows), whose bit equals `set`, ascending, to
+// out[0 ..) without holes; rows at or beyond capacity are counted and not written. counts: r_sweep_count_words(rows) words
+// of workspace -- one count per block and the total behind them (counts[r_sweep_blocks(rows)] after the call), then the
+// scan's own words.
+uint32_t r_sweep_blocks(uint64_t rows);
+size_t r_sweep_count_words(uint64_t rows);
+hipError_t launch_r_sweep(const RMarks& marks, bool set, uint32_t* out, uint64_t capacity, uint32_t* counts, hipStream_t s);
 
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):
@@ -541,8 +579,9 @@ hipError_t launch_prj_build_rows(const PrjPlan& plan, const PrjBuffers& buf, con
 // S's passes (row = sIdxBase + position in S), the work-item list, the join that emits (S row, R row) pairs to `out`
 // (out.cursor is zeroed on the stream first; out.capacity 0: the pairs are counted only). Adds to Counters::prjMatches.
 // kind: hj_join_kind. HJ_JOIN_LEFT and HJ_JOIN_ANTI give partitions with S tuples and no R tuple a work item of their own.
+// marks != nullptr (kinds INNER and LEFT only): the join's MARK instantiation (RMarks above; base 0, the row is the position in R)
 hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
                                  const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
-                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s);
+                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s, const RMarks* marks = nullptr);
 
 }  // namespace hj

@@ -22,6 +22,10 @@
 // round leaves 255 threads idle) carry valid = false and never produce an unmatched row. Counters::matches grows by the
 // INNER matches whatever the kind.
 //
+// R-side match marks (HJ_FLAG_TRACK_R_MATCHES): `bool MARK` next to K on both kernels, instantiated for INNER and LEFT. A MARK
+// instantiation takes PairsOutMarked where the others take PairsOut, and stage_flush also sets the bit of every staged R
+// row (mark_plane, hj_device.h). The instantiations without marks are untouched: same arguments, same code.
+//
 // All integer work, bound by HBM and the table gather; no MFMA.
 
 #include "hj_device.h"
@@ -53,14 +57,18 @@ struct Stage {
 };
 
 // Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
-template <int K>
-__device__ __forceinline__ void stage_flush(Stage& st, const PairsOut& out)
+// Out = PairsOutMarked (the MARK instantiations): every staged R row also sets its mark. Here, because the stage holds every
+// row the workgroup produced since its last flush whether the capacity lets it out or not (flush_plane cuts per element and
+// returns early behind the capacity; the marks must not), and because neighbouring lanes read neighbouring pairs.
+template <int K, class Out>
+__device__ __forceinline__ void stage_flush(Stage& st, const Out& out)
 {
     if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
     __syncthreads();                                  // the base is there, and so is every pair of the rounds before
     const uint64_t base = *st.base;
     flush_plane<kBlock>(st.s, st.fill, out.s, base, out.capacity);
     if constexpr (K <= kLeft) flush_plane<kBlock>(st.r, st.fill, out.r, base, out.capacity);
+    if constexpr (std::is_same_v<Out, PairsOutMarked>) mark_plane<kBlock>(st.r, st.fill, out.marks);
     __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
     st.fill = 0;
 }
@@ -69,8 +77,8 @@ __device__ __forceinline__ void stage_flush(Stage& st, const PairsOut& out)
 // stage; the lane then writes its m pairs there. anyMore: some lane of the workgroup has more. One barrier, two when the
 // stage is flushed first. The totals are double-buffered by round parity: a wavefront writes round k + 2's only after the
 // barrier of round k + 1, which every wavefront reaches after reading round k's.
-template <int K>
-__device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out, uint32_t m, bool more, bool& anyMore)
+template <int K, class Out>
+__device__ __forceinline__ uint32_t stage_reserve(Stage& st, const Out& out, uint32_t m, bool more, bool& anyMore)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
     uint32_t inc = m;
@@ -104,8 +112,8 @@ __device__ __forceinline__ uint32_t stage_reserve(Stage& st, const PairsOut& out
 // counter: found is the same in every thread; the foreign counts are per lane)
 // Kinds other than INNER: the rows are not the matches, so the lanes' inner matches are summed instead; LEFT also leaves
 // its unmatched elements in the word behind the cursor (hj_pairs_info; SEMI and ANTI derive theirs on the host)
-template <int K>
-__device__ __forceinline__ void stage_finish(Stage& st, const PairsOut& out, uint32_t foreign, Counters* __restrict__ ctr)
+template <int K, class Out>
+__device__ __forceinline__ void stage_finish(Stage& st, const Out& out, uint32_t foreign, Counters* __restrict__ ctr)
 {
     if (st.fill) stage_flush<K>(st, out);
     if constexpr (K == kInner) {
@@ -216,8 +224,8 @@ struct OaTable { const uint64_t* table; uint64_t mask; uint32_t hshift, probeLen
 // E elements per lane: walk them all, agree on the round's pair count, write the pairs into the stage
 // Rows per element: INNER popc(mask); LEFT max(popc(mask), 1), SEMI mask != 0, ANTI mask == 0 -- the latter three for a
 // valid lane only (a lane without an element has mask 0 and is no unmatched row)
-template <int K, int E, bool FOUR>
-__device__ __forceinline__ void oa_round(Stage& st, const PairsOut& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
+template <int K, int E, bool FOUR, class Out>
+__device__ __forceinline__ void oa_round(Stage& st, const Out& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
                                          const bool (&valid)[E])
 {
     Hit h[E];
@@ -242,9 +250,9 @@ __device__ __forceinline__ void oa_round(Stage& st, const PairsOut& out, const O
     for (int e = 0; e < E; ++e) emit<K>(st, pos, (uint32_t)row[e], h[e], valid[e]);
 }
 
-template <int K, int V, bool FOUR>
+template <int K, int V, bool FOUR, class Out>
 __device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const OaTable& T,
-                                                 const ShardCheck& sc, const PairsOut& out, Counters* __restrict__ ctr)
+                                                 const ShardCheck& sc, const Out& out, Counters* __restrict__ ctr)
 {
     static_assert(2 * V * kBlock * (FOUR ? 4 : kMaxProbeLen) <= kStagePairs, "a round must fit an empty stage");
     const SBody b = s_body(S, n);
@@ -289,11 +297,13 @@ __device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __re
 // probeLength 4 (the reference's default): four elements per lane and round, all sixteen window loads in flight;
 // any other length: two elements, the walk with its early exit
 // K: hj_join_kind. SEMI and ANTI keep no R plane in LDS
-template <int K>
+// MARK (INNER and LEFT only): `out` also carries the R-side match marks, set at every flush of the stage (stage_flush)
+template <int K, bool MARK>
 __global__ void __launch_bounds__(kBlock)
 k_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint64_t mask,
-              uint32_t hshift, uint32_t probeLen, ShardCheck sc, PairsOut out, Counters* __restrict__ ctr)
+              uint32_t hshift, uint32_t probeLen, ShardCheck sc, PairsOutOf<MARK> out, Counters* __restrict__ ctr)
 {
+    static_assert(!MARK || K <= kLeft, "only the kinds that produce R rows mark them");
     __shared__ uint32_t ldsS[kStagePairs], ldsR[K <= kLeft ? kStagePairs : 1], ldsTot[2 * kWaves];
     __shared__ unsigned long long ldsBase;
     Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
@@ -361,8 +371,8 @@ struct HtmTable { const uint64_t* table; const uint64_t* overflow; uint32_t buck
 
 // E elements per lane: bucket rounds until the longest chain of the workgroup's elements has ended; lanes whose chains
 // have ended idle through them
-template <int K, int E>
-__device__ __forceinline__ void htm_rounds(Stage& st, const PairsOut& out, const HtmTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
+template <int K, int E, class Out>
+__device__ __forceinline__ void htm_rounds(Stage& st, const Out& out, const HtmTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
                                            const bool (&valid)[E])
 {
     ChainWalk c[E];
@@ -397,11 +407,12 @@ static_assert(2 * kHtmVecs * kBlock * 3 <= kStagePairs, "a round must fit an emp
 
 }  // namespace
 
-template <int K>
+template <int K, bool MARK>
 __global__ void __launch_bounds__(kBlock)
 k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, const uint64_t* __restrict__ table, uint32_t bucketMask,
-                  const uint64_t* __restrict__ overflow, PairsOut out, Counters* __restrict__ ctr)
+                  const uint64_t* __restrict__ overflow, PairsOutOf<MARK> out, Counters* __restrict__ ctr)
 {
+    static_assert(!MARK || K <= kLeft, "only the kinds that produce R rows mark them");
     constexpr int V = kHtmVecs;
     __shared__ uint32_t ldsS[kStagePairs], ldsR[K <= kLeft ? kStagePairs : 1], ldsTot[2 * kWaves];
     __shared__ unsigned long long ldsBase;
@@ -459,20 +470,35 @@ unsigned pairs_grid(uint64_t n, int nCU, int vecs)
 uint32_t pairs_max_probe_len() { return kMaxProbeLen; }
 
 void launch_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
-                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
+                        uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks)
 {
-    const auto kernel = kind == kLeft ? k_probe_pairs<kLeft> : kind == kSemi ? k_probe_pairs<kSemi> : kind == kAnti ? k_probe_pairs<kAnti> : k_probe_pairs<kInner>;
-    hipLaunchKernelGGL(kernel, dim3(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1)), dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift,
-                       probeLen, sc, out, ctr);
+    const dim3 grid(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1));
+    if (marks && kind <= (uint32_t)kLeft) {
+        PairsOutMarked om;
+        static_cast<PairsOut&>(om) = out; om.marks = *marks;
+        const auto kernel = kind == kLeft ? k_probe_pairs<kLeft, true> : k_probe_pairs<kInner, true>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift, probeLen, sc, om, ctr);
+        return;
+    }
+    const auto kernel = kind == kLeft ? k_probe_pairs<kLeft, false> : kind == kSemi ? k_probe_pairs<kSemi, false>
+                      : kind == kAnti ? k_probe_pairs<kAnti, false> : k_probe_pairs<kInner, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift, probeLen, sc, out, ctr);
 }
 
 void launch_htm_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
-                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s)
+                            const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks)
 {
-    const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft> : kind == kSemi ? k_htm_probe_pairs<kSemi> : kind == kAnti ? k_htm_probe_pairs<kAnti>
-                                                                                                                  : k_htm_probe_pairs<kInner>;
-    hipLaunchKernelGGL(kernel, dim3(pairs_grid(n, nCU, kHtmVecs)), dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1,
-                       overflow, out, ctr);
+    const dim3 grid(pairs_grid(n, nCU, kHtmVecs));
+    if (marks && kind <= (uint32_t)kLeft) {
+        PairsOutMarked om;
+        static_cast<PairsOut&>(om) = out; om.marks = *marks;
+        const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft, true> : k_htm_probe_pairs<kInner, true>;
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1, overflow, om, ctr);
+        return;
+    }
+    const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft, false> : kind == kSemi ? k_htm_probe_pairs<kSemi, false>
+                      : kind == kAnti ? k_htm_probe_pairs<kAnti, false> : k_htm_probe_pairs<kInner, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1, overflow, out, ctr);
 }
 
 }  // namespace hj

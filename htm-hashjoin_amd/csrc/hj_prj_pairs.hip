@@ -64,14 +64,24 @@ k_prj_rows_checksum(const uint2* __restrict__ partR, const uint32_t* __restrict_
 // layout: partition pid = part[off[pid] .. off[pid + 1]), elements {x = key, y = row}. The arrays are separate __restrict__
 // parameters (k_prj_join: members of a struct became vector loads), and what an item reads is looked up before its LDS work.
 // K: hj_join_kind. cursor[1]: LEFT's unmatched S elements.
-template <int K>
+// MARK (INNER and LEFT only): the last argument also carries the R-side match marks (RMarks, hj_device.h; base 0: an R row
+// is its position in the relation given to the build). Every produced R row sets its bit in one of two places: where the
+// staged R plane is read at a flush (whatever the capacity lets out), and in the `put` of the direct-write round, which
+// bypasses the stage. The last argument of an instantiation without marks is the counters' pointer, as it always was.
+struct CtrMarks { Counters* ctr; RMarks marks; };
+template <bool MARK> using PairsTail = std::conditional_t<MARK, CtrMarks, Counters* __restrict__>;
+__device__ __forceinline__ Counters* ctr_of(Counters* c) { return c; }
+__device__ __forceinline__ Counters* ctr_of(const CtrMarks& t) { return t.ctr; }
+
+template <int K, bool MARK>
 __global__ void __launch_bounds__(kJoinThreads)
 k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ offR,
                  const uint2* __restrict__ partS, const uint32_t* __restrict__ offS,
                  const uint2* __restrict__ items, const uint32_t* __restrict__ nItemsAt, unsigned long long* __restrict__ ticket,
                  uint32_t radixBits, uint32_t* __restrict__ outS, uint32_t* __restrict__ outR, uint64_t capacity,
-                 unsigned long long* __restrict__ cursor, Counters* __restrict__ ctr)
+                 unsigned long long* __restrict__ cursor, PairsTail<MARK> tail)
 {
+    static_assert(!MARK || K <= kLeft, "only the kinds that produce R rows mark them");
     extern __shared__ uint32_t pairLds[];
     uint32_t* const tabK = pairLds;                    // key remainders, kEmpty32 = free
     uint32_t* const tabR = tabK + kPairSlots;          // the R row of the slot's entry
@@ -96,6 +106,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
         const uint64_t base = sBase;
         flush_plane<kJoinThreads>(stS, fill, outS, base, capacity);
         if constexpr (K <= kLeft) flush_plane<kJoinThreads>(stR, fill, outR, base, capacity);
+        if constexpr (MARK) mark_plane<kJoinThreads>(stR, fill, tail.marks);
         __syncthreads();                               // nobody refills the stage (or claims again) while it is being read
         fill = 0;
     };
@@ -231,6 +242,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
                             outS[g] = s;
                             if constexpr (K <= kLeft) outR[g] = r;
                         }
+                        if constexpr (MARK) mark_r_row(tail.marks, r);     // written or not
                         ++g;
                     };
 #pragma unroll
@@ -254,7 +266,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
     }
     if (fill) flush();
     if constexpr (K == kInner) {
-        if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr)->prjMatches, found);
+        if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr_of(tail))->prjMatches, found);
     } else {
         // the rows are not the matches: the counter takes the inner matches, LEFT's unmatched elements go behind the cursor
         unsigned long long un = unmatched;
@@ -263,15 +275,16 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
             inner += __shfl_down(inner, off, 64);
             un += __shfl_down(un, off, 64);
         }
-        if (lane == 0 && inner) atomicAdd(&counter_shard(ctr)->prjMatches, inner);
+        if (lane == 0 && inner) atomicAdd(&counter_shard(ctr_of(tail))->prjMatches, inner);
         if (K == kLeft && lane == 0 && un) atomicAdd(cursor + 1, un);
     }
 }
 
 static hipError_t prj_pairs_set_attributes()
 {
-    const void* const kernels[4] = {reinterpret_cast<const void*>(k_prj_join_pairs<kInner>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft>),
-                                    reinterpret_cast<const void*>(k_prj_join_pairs<kSemi>), reinterpret_cast<const void*>(k_prj_join_pairs<kAnti>)};
+    const void* const kernels[6] = {reinterpret_cast<const void*>(k_prj_join_pairs<kInner, false>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft, false>),
+                                    reinterpret_cast<const void*>(k_prj_join_pairs<kSemi, false>), reinterpret_cast<const void*>(k_prj_join_pairs<kAnti, false>),
+                                    reinterpret_cast<const void*>(k_prj_join_pairs<kInner, true>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft, true>)};
     for (const void* k : kernels) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes);
         if (e != hipSuccess) return e;
@@ -296,10 +309,11 @@ hipError_t launch_prj_build_rows(const PrjPlan& pl, const PrjBuffers& buf, const
 }
 
 // S's row-id passes into buf.partS (rows from sIdxBase), the work-item list, k_prj_join_pairs against the resident R.
-// out.cursor and the word behind it are zeroed here; out.capacity 0 counts only. kind: hj_join_kind.
+// out.cursor and the word behind it are zeroed here; out.capacity 0 counts only. kind: hj_join_kind. marks: the MARK
+// instantiation (INNER and LEFT); nullptr -- every caller that only counts, hj_prj_probe_dev among them -- the kernels as they were.
 hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
                                  const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
-                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s)
+                                 hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s, const RMarks* marks)
 {
     const Work w = carve(planS, buf.work);
     hipError_t e;
@@ -313,8 +327,16 @@ hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjP
     const bool rless = kind == (uint32_t)kLeft || kind == (uint32_t)kAnti;
     if ((e = enqueue_prj_items(res, res.offR, nullptr, 0u, w.offS, nullptr, 0u, P, ctr, s, rless)) != hipSuccess) return e;
     if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
-    const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft> : kind == (uint32_t)kSemi ? k_prj_join_pairs<kSemi>
-                      : kind == (uint32_t)kAnti ? k_prj_join_pairs<kAnti> : k_prj_join_pairs<kInner>;
+    if (marks && kind <= (uint32_t)kLeft) {
+        const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft, true> : k_prj_join_pairs<kInner, true>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
+                           reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
+                           res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor,
+                           CtrMarks{ctr, *marks});
+        return hipGetLastError();
+    }
+    const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft, false> : kind == (uint32_t)kSemi ? k_prj_join_pairs<kSemi, false>
+                      : kind == (uint32_t)kAnti ? k_prj_join_pairs<kAnti, false> : k_prj_join_pairs<kInner, false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
                        reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
                        res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor, ctr);

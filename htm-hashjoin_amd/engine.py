@@ -83,13 +83,13 @@ def wave_layout_info(n, compute_units):
 
 
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
-            buildVariant=0, prjMode=0, keepRowIds=False):
+            buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False):
     p = hj_params()
     p.algo = _lib.ALGO_IDS[algo]
     p.scaleOutput, p.numPartitions, p.probeLength = scaleOutput, numPartitions, probeLength
     p.transactionSize, p.radixBits, p.buildVariant = transactionSize, radixBits, buildVariant
     p.prjMode = prjMode
-    p.flags = _lib.HJ_FLAG_KEEP_ROW_IDS if keepRowIds else 0
+    p.flags = (_lib.HJ_FLAG_KEEP_ROW_IDS if keepRowIds else 0) | (_lib.HJ_FLAG_TRACK_R_MATCHES if trackRMatches else 0)
     return p
 
 
@@ -142,6 +142,9 @@ class HashJoinContext:
 
     # ---- split API, device pointers ---------------------------------------
     def reserve(self, algo, rSize, sSize, **kw):
+        """hj_reserve. Keywords: the fields of hj_params, keepRowIds (HJ_FLAG_KEEP_ROW_IDS) and trackRMatches
+        (HJ_FLAG_TRACK_R_MATCHES: one bit per R row, set by the inner / left probe_pairs and prj_probe_pairs calls for the
+        R rows they produce, read by r_rows; needs keepRowIds except on "htm")."""
         p = _params(algo, **kw)
         self._check(lib.hj_reserve(self._h, C.byref(p), rSize, sSize))
 
@@ -169,6 +172,24 @@ class HashJoinContext:
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_pairs_info(self._h, out))
         return tuple(int(x) for x in out)
+
+    # ---- R-side match marks (reserve(..., trackRMatches=True)) ----------------
+    def r_rows(self, which, d_out_r, capacity):
+        """hj_r_rows_dev: the R rows of the last build that no inner / left probe since has produced (which = 0,
+        HJ_R_UNMATCHED) or that one has (1, HJ_R_MATCHED), ascending, into the device uint32 array d_out_r of `capacity`
+        entries; rows beyond it are counted, not written (capacity 0, d_out_r 0: count only). Changes no mark."""
+        self._check(lib.hj_r_rows_dev(self._h, which, C.c_void_p(d_out_r) if d_out_r else None, capacity))
+
+    def r_rows_info(self):
+        """hj_r_rows_info (waits for the stream): (rows the last r_rows produced, rows it wrote, its device time in
+        microseconds, R rows of the build)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_r_rows_info(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def r_marks_clear(self):
+        """hj_r_marks_clear: every R row unmatched again, without rebuilding."""
+        self._check(lib.hj_r_marks_clear(self._h))
 
     def prj_join(self, dR_ptr, rSize, dS_ptr, sSize):
         self._check(lib.hj_prj_join_dev(self._h, C.c_void_p(dR_ptr), rSize,
@@ -487,6 +508,152 @@ def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="
             for p in held:
                 ctx.dev_free(p)
     return np.concatenate(parts_s), (np.concatenate(parts_r) if plane_r else None)
+
+
+# the R-preserving results: the kind of the probe calls (None: a mark-only pass, capacity 0) and which R rows follow
+_OUTER_KINDS = {"right": (_lib.HJ_JOIN_INNER, _lib.HJ_R_UNMATCHED), "full": (_lib.HJ_JOIN_LEFT, _lib.HJ_R_UNMATCHED),
+                "right_semi": (None, _lib.HJ_R_MATCHED), "right_anti": (None, _lib.HJ_R_UNMATCHED)}
+
+
+def _outer_kind(fn, how):
+    if not isinstance(how, str) or how not in _OUTER_KINDS:
+        raise ValueError(f"{fn}: how must be right, full, right_semi or right_anti, not {how!r}")
+    return _OUTER_KINDS[how]
+
+
+def _outer_result(kind, s_parts, r_parts, r_only):
+    """(s_idx, r_idx) of an R-preserving join: the probe's rows, then one (NO_ROW, r) row per R-only row; the rows alone
+    for right_semi / right_anti"""
+    if kind is None:
+        return None, r_only
+    return (np.concatenate(s_parts + [np.full(r_only.size, NO_ROW, dtype=np.uint32)]),
+            np.concatenate(r_parts + [r_only]))
+
+
+def _outer_without_device(kind, which, n_r, n_s):
+    """an R-preserving join with an empty side (None: the inputs need the device). No S: no R row is matched. No R: the
+    rows of the probe side alone."""
+    if n_r and n_s:
+        return None
+    none = np.empty(0, dtype=np.uint32)
+    s_idx, r_idx = (none, none) if kind is None else _join_without_device(kind, n_r, n_s)
+    r_only = np.arange(n_r, dtype=np.uint32) if which == _lib.HJ_R_UNMATCHED else none
+    return _outer_result(kind, [s_idx], [r_idx], r_only)
+
+
+def _sweep(ctx, alloc, which, n_r):
+    """the rows r_rows(which) gives after the probes, as a numpy array"""
+    d_rows = alloc(4 * n_r)
+    ctx.r_rows(which, d_rows, n_r)
+    written = ctx.r_rows_info()[1]
+    rows = np.empty(written, dtype=np.uint32)
+    if written:
+        ctx.copy_d2h(rows, d_rows)
+    return rows
+
+
+def outer_join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="right"):
+    """The joins that preserve relR, the build side, as gather maps like join_pairs (same algo, same meaning of a match).
+    how = "right": (s_idx, r_idx), the inner rows first, then one row (NO_ROW, r) for every R row no inner row names, r
+    ascending. "full": the same with the left-outer rows in front (an S tuple without a match is (s, NO_ROW)).
+    "right_semi" / "right_anti": (None, r_idx), the R rows some / no inner row names, ascending. With "atomic" / "nocc"
+    an R tuple that ran out of probeLength is not in the table and therefore unmatched."""
+    if algo not in ("htm", "atomic", "nocc"):
+        raise ValueError(f"outer_join_pairs: algo must be htm, atomic or nocc, not {algo!r}")
+    kind, which = _outer_kind("outer_join_pairs", how)
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    trivial = _outer_without_device(kind, which, relR.size, relS.size)
+    if trivial is not None:
+        return trivial
+    with HashJoinContext(device) as ctx:
+        held = []
+
+        def alloc(nbytes):
+            held.append(ctx.dev_alloc(nbytes))
+            return held[-1]
+
+        try:
+            ctx.reserve(algo, relR.size, relS.size, probeLength=probeLength, keepRowIds=True, trackRMatches=True)
+            dR, dS = alloc(relR.nbytes), alloc(relS.nbytes)
+            ctx.copy_h2d(dR, relR)
+            ctx.copy_h2d(dS, relS)
+            ctx.build(dR, relR.size)
+            s_idx = r_idx = None
+            if kind is None:
+                ctx.probe_pairs(dS, relS.size, 0, 0, 0)      # a mark-only pass
+            else:
+                capacity = relS.size
+                while True:
+                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+                    ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity, kind=kind)
+                    found, written = ctx.pairs_info()[:2]
+                    if found <= capacity:
+                        break
+                    capacity = found
+                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
+                if written:
+                    ctx.copy_d2h(s_idx, d_s)
+                    ctx.copy_d2h(r_idx, d_r)
+            ctx.fetch()             # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
+            r_only = _sweep(ctx, alloc, which, relR.size)
+        finally:
+            for p in held:
+                ctx.dev_free(p)
+    return _outer_result(kind, [s_idx], [r_idx], r_only)
+
+
+def radix_outer_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="right"):
+    """outer_join_pairs through the resident radix join (the complete equi-join on the key word, as radix_join_pairs): R is
+    partitioned once with its row ids, relS is probed in slices of slice_tuples, and the marks the slices leave on R's
+    rows become the R-only rows at the end. how and the result as in outer_join_pairs."""
+    kind, which = _outer_kind("radix_outer_join_pairs", how)
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    trivial = _outer_without_device(kind, which, relR.size, relS.size)
+    if trivial is not None:
+        return trivial
+    step = relS.size if not slice_tuples else min(int(slice_tuples), relS.size)
+    if step < 1:
+        raise ValueError(f"radix_outer_join_pairs: slice_tuples must be positive, not {slice_tuples!r}")
+    parts_s, parts_r = [], []
+    with HashJoinContext(device) as ctx:
+        held = []
+
+        def alloc(nbytes):
+            held.append(ctx.dev_alloc(nbytes))
+            return held[-1]
+
+        try:
+            ctx.reserve("prj", relR.size, step, radixBits=radixBits, keepRowIds=True, trackRMatches=True)
+            dR, dS = alloc(relR.nbytes), alloc(8 * step)
+            ctx.copy_h2d(dR, relR)
+            ctx.prj_build(dR, relR.size)
+            capacity = step if kind is not None else 0
+            d_s, d_r = (alloc(4 * capacity), alloc(4 * capacity)) if capacity else (0, 0)
+            for lo in range(0, relS.size, step):
+                part = relS[lo:lo + step]
+                ctx.copy_h2d(dS, part)
+                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
+                if kind is None:
+                    continue
+                found, written = ctx.pairs_info()[:2]
+                if found > capacity:
+                    capacity = found
+                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
+                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
+                    found, written = ctx.pairs_info()[:2]
+                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
+                if written:
+                    ctx.copy_d2h(s_idx, d_s)
+                    ctx.copy_d2h(r_idx, d_r)
+                parts_s.append(s_idx)
+                parts_r.append(r_idx)
+            r_only = _sweep(ctx, alloc, which, relR.size)
+        finally:
+            for p in held:
+                ctx.dev_free(p)
+    return _outer_result(kind, parts_s, parts_r, r_only)
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

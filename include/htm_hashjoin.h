@@ -108,6 +108,14 @@ typedef struct {
  * report 0, and R costs 8 bytes per tuple of resident memory. hj_prj_probe_dev keeps working and counts the same.
  * No effect on the one-shot hj_prj_join_dev. */
 #define HJ_FLAG_KEEP_ROW_IDS 0x1u
+/* hj_params.flags. R-side match marks: the context remembers which R rows have appeared in a row of a materialising probe
+ * since the last build, across probe calls (R is built once, S arrives in slices), and hj_r_rows_dev turns that memory
+ * into rows -- what right outer, full outer, right semi and right anti joins need (see hj_r_rows_dev).
+ * hj_reserve also allocates the mark plane: one bit per R row of the reserved rSize, in 32-bit words. The marks are
+ * indexed by R row, so on open addressing and on HJ_ALGO_PRJ / HJ_ALGO_AUTO the flag is accepted only together with
+ * HJ_FLAG_KEEP_ROW_IDS (hj_reserve: HJ_ERR_INVALID otherwise); HJ_ALGO_HTM, whose table always keeps the rows, takes it
+ * alone. hj_build_keys_dev on such a context returns HJ_ERR_STATE (the sharded path keeps no marks). */
+#define HJ_FLAG_TRACK_R_MATCHES 0x2u
 
 /* Everything the reference prints in its JSON line (NoCCHashBuild.hpp:127-146,
  * AtomicHashBuild.hpp:133-152) plus device timings. */
@@ -224,7 +232,8 @@ int hj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint64_t
  *   HJ_JOIN_LEFT   one row per match; for a tuple without one, one row with R row = HJ_NO_ROW   planes S, R
  *   HJ_JOIN_SEMI   one row for a tuple with at least one match, however many            plane S only
  *   HJ_JOIN_ANTI   one row for a tuple without a match                                  plane S only
- * R-preserving kinds (right / full outer) are not offered. */
+ * R-preserving results (right / full outer, right semi / anti) are no fifth kind: they are the INNER or LEFT calls of a
+ * context reserved with HJ_FLAG_TRACK_R_MATCHES plus hj_r_rows_dev (below). */
 typedef enum { HJ_JOIN_INNER = 0, HJ_JOIN_LEFT = 1, HJ_JOIN_SEMI = 2, HJ_JOIN_ANTI = 3 } hj_join_kind;
 /* The R row of an HJ_JOIN_LEFT row whose S tuple has no match. No real row takes the value: S rows stay below it by the
  * check on sIdxBase + sSize, R rows by the builds' own checks (idxBase + rSize <= 2^32 - 1; PRJ: rSize < 2^32 - 1). */
@@ -242,6 +251,35 @@ int hj_probe_join_dev(hj_ctx *ctx, uint32_t kind, const uint64_t *dS, uint64_t s
  * time in microseconds (rounded), out[3] = S tuples of the call without a match for a kind other than HJ_JOIN_INNER
  * (0 after an INNER call). */
 int hj_pairs_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- R-side match marks (contexts reserved with HJ_FLAG_TRACK_R_MATCHES) ----
+ * One bit per R row of the last build. hj_build_dev and hj_prj_build_dev clear the plane on the stream. Every later
+ * hj_probe_join_dev / hj_prj_probe_join_dev call of kind HJ_JOIN_INNER or HJ_JOIN_LEFT (hj_probe_pairs_dev and
+ * hj_prj_probe_pairs_dev included) sets the bit of every R row that appears in a row it produces -- whether the row is
+ * written or not: rows at or beyond `capacity` mark too, so a call with capacity 0 and NULL planes is a mark-only pass.
+ * HJ_NO_ROW marks nothing. HJ_JOIN_SEMI and HJ_JOIN_ANTI calls, hj_probe_dev and hj_prj_probe_dev never touch the marks
+ * and run the kernels they run without the flag. Bit index: table paths, R row - idxBase of the last build; PRJ, the
+ * position in dR. hj_result and hj_pairs_info are what the same calls give on a context without the flag.
+ * "Matched" is exactly "some produced row named this R row", as an S tuple is unmatched when the probe emits no pair for
+ * it: on open addressing an R tuple the build dropped (a conflict: probeLength exhausted) is unmatched, and so is a
+ * tuple behind the reach of the probe's walk.
+ *   right outer = the rows of the HJ_JOIN_INNER calls, plus (HJ_NO_ROW, r) for every unmatched r
+ *   full outer  = the rows of the HJ_JOIN_LEFT calls, plus the same tail
+ *   right semi  = the matched rows                       right anti = the unmatched rows */
+#define HJ_R_UNMATCHED 0u
+#define HJ_R_MATCHED   1u
+/* Zeroes the marks without rebuilding. Asynchronous. HJ_ERR_STATE as for hj_r_rows_dev. */
+int hj_r_marks_clear(hj_ctx *ctx);
+/* Writes the R rows of the last build whose bit is clear (HJ_R_UNMATCHED) or set (HJ_R_MATCHED), as the pairs report them
+ * (idxBase + position; PRJ: the position in dR), in ASCENDING order from dOutR[0] without holes. Rows at or beyond
+ * `capacity` are counted and not written, so a truncated call yields the first `capacity` rows; capacity 0 (dOutR may be
+ * NULL) only counts. Changes no mark and no counter of hj_result. Asynchronous.
+ * HJ_ERR_STATE: context reserved without HJ_FLAG_TRACK_R_MATCHES; no build yet, or the last build was not hj_build_dev /
+ * hj_prj_build_dev. HJ_ERR_INVALID: which > 1; dOutR NULL with capacity > 0. */
+int hj_r_rows_dev(hj_ctx *ctx, uint32_t which, uint32_t *dOutR, uint64_t capacity);
+/* Waits for the stream. About the last hj_r_rows_dev since the build: out[0] = rows it produced, out[1] = rows it wrote
+ * (= min(out[0], capacity)), out[2] = its device time in microseconds (rounded) -- all 0 when there was none --, out[3] =
+ * R rows of the build. HJ_ERR_STATE as for hj_r_rows_dev. */
+int hj_r_rows_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */

@@ -2,7 +2,7 @@
 """Times the materialising probe against the counting probe on the same table and the same S, through the C ABI, no
 torch: development tool.
 
-    python tools/pairs_bench.py [--log2n 27] [--reps 10] [--counting-only] [--how left,semi,anti] [--absent-half]
+    python tools/pairs_bench.py [--log2n 27] [--reps 10] [--counting-only] [--how left,semi,anti] [--absent-half] [--track-r]
 
 One context, |R| = |S| = 2^log2n, R = local_shuffle W=16. Per configuration one JSON line with the median HIP-event
 times over `reps` launches after one warm-up launch of
@@ -16,6 +16,11 @@ of 4096 pairs cannot take the next round, and once more at its end (pairs / 4096
 <kind>_ratio = its median / (b)'s, (b) being the INNER join of the same process and input; (b) itself always goes through
 hj_probe_pairs_dev, the entry point older checkouts have. --absent-half: every second tuple of the sorted S gets a key
 above R's (n + its key), so half of S is unmatched.
+--track-r: behind the launches above, the same table is built once more on a context reserved with
+HJ_FLAG_TRACK_R_MATCHES and INNER (and LEFT, when --how lists it) is timed again -> track_<kind>_us and track_<kind>_ratio =
+its median / the median of the same kind without the flag, timed just before in this process; track_marked = R rows the
+marks then hold. On the sorted S without --absent-half it also times hj_r_rows_dev (HJ_R_MATCHED) with a quarter, a half
+and all of R's rows marked -> sweep_<rows>_us, sweep_<rows>_GBps = (4 B x rows + 2 x the plane of n / 8 B) / its median.
 --counting-only runs (a) alone and uses nothing newer than hj_probe_dev (the 8-byte table is then asked for with
 buildVariant 3): the same script times the yardstick on a checkout that has no materialising probe."""
 import argparse
@@ -33,6 +38,43 @@ from htm_hashjoin_amd import _lib  # noqa: E402
 STAGE_PAIRS, WORKGROUPS = 4096, 256 * 4
 
 
+def track_r(c, a, row, algo, dR, dProbe, n, kinds, sweep):
+    """--track-r: INNER / LEFT on a tracking context against row's medians of the same kinds, then the sweep"""
+    c.reserve(algo, n, n, keepRowIds=True, trackRMatches=True)
+    c.build(dR, n)
+    for how in ["inner"] + [k for k in kinds if k == "left"]:
+        kind, rows = _lib.JOIN_KINDS[how], row["pairs" if how == "inner" else "left_rows"]
+        dOutS, dOutR = c.dev_alloc(4 * rows + 16), c.dev_alloc(4 * rows + 16)
+        us = []
+        for _ in range(a.reps + 1):
+            c.r_marks_clear()                               # every launch meets clear bits and sets them: the atomics are timed
+            c.probe_pairs(dProbe, n, dOutS, dOutR, rows, kind=kind)
+            found, written, t, _ = c.pairs_info()
+            assert found == written == rows, (how, found, written, rows)
+            us.append(t)
+        c.dev_free(dOutS)
+        c.dev_free(dOutR)
+        med, base = statistics.median(us[1:]), row["pairs_us" if how == "inner" else "left_us"]
+        row.update({"track_" + how + "_us": med, "track_" + how + "_us_min": min(us[1:]), "track_" + how + "_ratio": round(med / base, 3)})
+    c.r_rows(_lib.HJ_R_MATCHED, 0, 0)
+    row["track_marked"] = c.r_rows_info()[0]
+    if not sweep:
+        return
+    dRows = c.dev_alloc(4 * n + 16)
+    for part in (4, 2, 1):                                  # sorted S: its first n / part tuples mark that many rows
+        c.r_marks_clear()
+        c.probe_pairs(dProbe, n // part, 0, 0, 0)           # a mark-only pass
+        us = []
+        for _ in range(a.reps + 1):
+            c.r_rows(_lib.HJ_R_MATCHED, dRows, n)
+            produced, written, t, _ = c.r_rows_info()
+            assert produced == written, (produced, written)
+            us.append(t)
+        med = statistics.median(us[1:])
+        row.update({"sweep_%d_us" % produced: med, "sweep_%d_GBps" % produced: round((4.0 * produced + 2.0 * n / 8) / max(med, 1) / 1e3, 1)})
+    c.dev_free(dRows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=27)
@@ -42,6 +84,7 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--how", default="", help="comma list of left, semi, anti")
     ap.add_argument("--absent-half", action="store_true")
+    ap.add_argument("--track-r", action="store_true", help="also time INNER / LEFT and the sweep with HJ_FLAG_TRACK_R_MATCHES")
     a = ap.parse_args()
     n = 1 << a.log2n
     kinds = [k for k in a.how.split(",") if k]
@@ -112,6 +155,8 @@ def main():
                 row.update({"pairs": pairs, "pairs_us": med, "pairs_us_min": min(pairs_us[1:]),
                             "ratio": round(med / row["probe_us"], 3), "out_GBps": round(8.0 * pairs / med / 1e3, 1),
                             "claims": pairs // STAGE_PAIRS + min(WORKGROUPS, (n // 2 + 256) // 256)})
+                if a.track_r:
+                    track_r(c, a, row, algo, dR, dProbe, n, kinds, sname == "sorted" and not a.absent_half)
             print(json.dumps(row), flush=True)
         for p in (dR, dS, dZ):
             c.dev_free(p)

@@ -3,7 +3,7 @@
 development tool.
 
     python tools/prj_pairs_bench.py [--log2n 27] [--reps 10] [--radix-bits 0] [--s sorted,uniform,zipf] [--yardsticks-only]
-                                    [--how left,semi,anti] [--absent-half]
+                                    [--how left,semi,anti] [--absent-half] [--track-r]
 
 |R| = |S| = 2^log2n, R = the keys 1..n shuffled (unique), so every S tuple matches once. S = sorted, uniform draws, or
 Zipf(theta) over n keys. Per S one JSON line with the median HIP-event times over `reps` launches after one warm-up of
@@ -15,6 +15,12 @@ and ratio_a = (c) / (a), ratio_b = (c) / (b), out_GBps = 8 B x pairs / (c), buil
 <kind>_ratio = its median / (c)'s, (c) being the INNER join of the same process and input; (c) itself always goes through
 hj_prj_probe_pairs_dev, the entry point older checkouts have. --absent-half: every second tuple of S gets n added to its
 key, which R does not hold, so half of S is unmatched (and (a)'s and (c)'s pair counts halve).
+--track-r: behind (c) and the kinds, R is built once more on a context reserved with HJ_FLAG_TRACK_R_MATCHES as well and
+INNER (and LEFT, when --how lists it) is timed again -> track_<kind>_us (track_<kind>_join_us: its join kernel) and
+track_<kind>_ratio = its median / the median of the same kind without the flag, timed just before in this process;
+track_marked = R rows the marks then hold. On the sorted S without --absent-half it also times hj_r_rows_dev (HJ_R_MATCHED)
+with a quarter, a half and all of R's rows marked -> sweep_<rows>_us, sweep_<rows>_GBps = (4 B x rows + 2 x the plane of
+n / 8 B) / its median.
 --yardsticks-only runs (a) and (b) alone and uses nothing newer than hj_prj_probe_dev / hj_probe_pairs_dev: the same
 script times the yardsticks on a checkout that has no materialising radix join."""
 import argparse
@@ -34,6 +40,37 @@ def med(xs):
     return round(statistics.median(xs[1:]), 1)          # [0] is the warm-up launch
 
 
+def track_r(c, a, row, dR, dS, n, dOutS, dOutR, kinds, sweep):
+    """--track-r: INNER / LEFT on a tracking context against row's medians of the same kinds, then the sweep"""
+    c.reserve("prj", n, n, radixBits=a.radix_bits, keepRowIds=True, trackRMatches=True)
+    c.prj_build(dR, n)
+    for how in ["inner"] + [k for k in kinds if k == "left"]:
+        us, join_us = [], []
+        for _ in range(a.reps + 1):
+            c.r_marks_clear()                               # every launch meets clear bits and sets them: the atomics are timed
+            c.prj_probe_pairs(dS, n, dOutS, dOutR, n, kind=_lib.JOIN_KINDS[how])
+            found, written, t, _ = c.pairs_info()
+            assert found == written <= n, (how, found, written)
+            us.append(t); join_us.append(c.fetch()["join_us"])
+        base = row["pairs_us" if how == "inner" else "left_us"]
+        row.update({"track_" + how + "_us": med(us), "track_" + how + "_us_min": min(us[1:]), "track_" + how + "_join_us": med(join_us),
+                    "track_" + how + "_ratio": round(med(us) / base, 3)})
+    c.r_rows(_lib.HJ_R_MATCHED, 0, 0)
+    row["track_marked"] = c.r_rows_info()[0]
+    if not sweep:
+        return
+    for part in (4, 2, 1):                                  # sorted S, unique R: its first n / part tuples mark that many rows
+        c.r_marks_clear()
+        c.prj_probe_pairs(dS, n // part, 0, 0, 0)           # a mark-only pass
+        us = []
+        for _ in range(a.reps + 1):
+            c.r_rows(_lib.HJ_R_MATCHED, dOutR, n)
+            produced, written, t, _ = c.r_rows_info()
+            assert produced == written, (produced, written)
+            us.append(t)
+        row.update({"sweep_%d_us" % produced: med(us), "sweep_%d_GBps" % produced: round((4.0 * produced + 2.0 * n / 8) / max(med(us), 1) / 1e3, 1)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, default=27)
@@ -46,6 +83,7 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--how", default="", help="comma list of left, semi, anti")
     ap.add_argument("--absent-half", action="store_true")
+    ap.add_argument("--track-r", action="store_true", help="also time INNER / LEFT and the sweep with HJ_FLAG_TRACK_R_MATCHES")
     a = ap.parse_args()
     n = 1 << a.log2n
     kinds = [k for k in a.how.split(",") if k]
@@ -121,6 +159,8 @@ def main():
                         kus.append(t); kjoin.append(c.fetch()["join_us"])
                     row.update({how + "_rows": found, how + "_us": med(kus), how + "_us_min": min(kus[1:]),
                                 how + "_join_us": med(kjoin), how + "_ratio": round(med(kus) / row["pairs_us"], 3)})
+                if a.track_r:
+                    track_r(c, a, row, dR, dS, n, dOutS, dOutR, kinds, sname == "sorted" and not a.absent_half)
             print(json.dumps(row), flush=True)
         for p in (dR, dS, dOutS, dOutR):
             c.dev_free(p)
