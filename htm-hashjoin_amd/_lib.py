@@ -37,6 +37,8 @@ HJ_R_UNMATCHED, HJ_R_MATCHED = 0, 1
 HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI = 0, 1, 2, 3
 JOIN_KINDS = {"inner": HJ_JOIN_INNER, "left": HJ_JOIN_LEFT, "semi": HJ_JOIN_SEMI, "anti": HJ_JOIN_ANTI}
 HJ_NO_ROW = 0xFFFFFFFF
+# hj_gather_dev: columns of one call
+HJ_GATHER_MAX_COLS = 8
 
 
 class hj_params(C.Structure):
@@ -75,6 +77,16 @@ class hj_result(C.Structure):
         return d
 
 
+class hj_gather_col(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("width", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("fill", C.c_uint64 * 2),
+    ]
+
+
 def _declare(lib):
     vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
     P = C.POINTER
@@ -97,6 +109,8 @@ def _declare(lib):
         "hj_r_marks_clear": ([vp], i32),
         "hj_r_rows_dev": ([vp, u32, vp, u64], i32),
         "hj_r_rows_info": ([vp, P(u64)], i32),
+        "hj_gather_dev": ([vp, vp, u64, u32, u64, P(hj_gather_col), u32, vp], i32),
+        "hj_gather_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),

@@ -31,6 +31,7 @@ enum Buf {
     B_PAIRS_CURSOR,             // materialising probe (hj_probe_join_dev): the output cursor, then HJ_JOIN_LEFT's unmatched S tuples
     B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_device.h)
     B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
+    B_GATHER_CTR,               // hj_gather_dev: the NULL rows and the out-of-range entries of the last call (two 64-bit words)
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -93,6 +94,10 @@ struct hj_ctx {
     uint64_t marksRows = 0, marksBase = 0;
     bool rRowsCalled = false;                   // hj_r_rows_dev ran since that build; its capacity (hj_r_rows_info)
     uint64_t rRowsCapacity = 0;
+    // hj_gather_dev: it belongs to no build and no operation, so its events are its own (begin_operation forgets ev[])
+    bool gatherCalled = false;                  // ... ran on this context; the rows of the last call (hj_gather_info)
+    uint64_t gatherRows = 0;
+    hipEvent_t evGather[2] = {nullptr, nullptr};
     Counters* hCtr = nullptr;     // pinned copy of the counters
     // PRJ
     PrjPlan plan{};
@@ -293,7 +298,9 @@ int create_common(int device, void* stream, bool own, hj_ctx** out)
               hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dPreferred), c->hPreferred, 0) == hipSuccess &&
               c->buf[B_BOUNDS].reserve(c, wave_bounds_bytes(c->nCU)) == HJ_OK &&
               c->buf[B_PAIRS_CURSOR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
+              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, 2 * sizeof(unsigned long long)) == hipSuccess &&
+              c->buf[B_GATHER_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
+              hipEventCreate(&c->evGather[0]) == hipSuccess && hipEventCreate(&c->evGather[1]) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }
     hipMemset(c->dCtr(), 0, sizeof(Counters));
@@ -349,6 +356,7 @@ void hj_destroy(hj_ctx* c)
     if (c->hFit) hipHostFree(c->hFit);
     if (c->hPreferred) hipHostFree(c->hPreferred);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
+    for (hipEvent_t e : c->evGather) if (e) hipEventDestroy(e);
     if (c->ownStream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -885,6 +893,59 @@ int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
     out[0] = produced;
     out[1] = produced < c->rRowsCapacity ? produced : c->rRowsCapacity;
     out[2] = (uint64_t)(elapsed_us(c, EV_RROWS0, EV_RROWS1) + 0.5);
+    return HJ_OK;
+}
+
+// ---- gather through a row map ----------------------------------------------
+static bool gather_width_ok(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
+
+int hj_gather_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const hj_gather_col* cols,
+                  uint32_t nCols, uint32_t* dValid)
+{
+    HJ_ENTER(c, true);
+    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: more than HJ_GATHER_MAX_COLS columns");
+    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: cols NULL with nCols > 0");
+    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: nRows or srcRows above 2^32 - 1");
+    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: dMap NULL with nRows > 0");
+    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: neither a column nor a validity plane");
+    GatherCols k{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_gather_col& col = cols[i];
+        if (!gather_width_ok(col.width)) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a width that is not 1, 2, 4, 8 or 16");
+        if (col.reserved) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: hj_gather_col.reserved must be 0");
+        const uintptr_t low = col.width - 1;
+        if (!col.dst || (reinterpret_cast<uintptr_t>(col.dst) & low))
+            return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a dst that is NULL or not aligned to its width");
+        if (srcRows && (!col.src || (reinterpret_cast<uintptr_t>(col.src) & low)))      // srcRows 0: src is never read
+            return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a src that is NULL or not aligned to its width");
+        k.col[i] = GatherCol{col.src, col.dst, col.width, 0, {col.fill[0], col.fill[1]}};
+    }
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    unsigned long long* const counts = c->buf[B_GATHER_CTR].as<unsigned long long>();
+    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->evGather[0], c->stream));
+    HJ_HIP(c, launch_gather(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, c->stream));
+    HJ_HIP(c, hipEventRecord(c->evGather[1], c->stream));
+    c->gatherCalled = true; c->gatherRows = nRows;
+    return HJ_OK;
+}
+
+int hj_gather_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = out[3] = 0;      // no hj_gather_dev yet
+    if (!c->gatherCalled) return HJ_OK;
+    unsigned long long words[2] = {0, 0};        // NULL rows, out-of-range entries
+    HJ_HIP(c, hipMemcpy(words, c->buf[B_GATHER_CTR].p, sizeof words, hipMemcpyDeviceToHost));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->evGather[0], c->evGather[1]) != hipSuccess) ms = 0;
+    out[0] = c->gatherRows;
+    out[1] = words[0];
+    out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
+    out[3] = words[1];
     return HJ_OK;
 }
 

@@ -504,6 +504,19 @@ uint32_t r_sweep_blocks(uint64_t rows);
 size_t r_sweep_count_words(uint64_t rows);
 hipError_t launch_r_sweep(const RMarks& marks, bool set, uint32_t* out, uint64_t capacity, uint32_t* counts, hipStream_t s);
 
+// ---- gather through a row map (defined in hj_gather.hip) ---------------------
+// One column of hj_gather_dev as the kernel takes it (hj_gather_col, include/htm_hashjoin.h, field for field), and the
+// columns of a call, passed by value in the kernel arguments.
+constexpr uint32_t kGatherMaxCols = 8;        // HJ_GATHER_MAX_COLS
+struct GatherCol { const void* src; void* dst; uint32_t width, reserved; uint64_t fill[2]; };
+struct GatherCols { GatherCol col[kGatherMaxCols]; };
+// dst_c[k] = src_c[map[k] - rowBase] for k in [0, nRows) and c in [0, nCols); an entry that is HJ_NO_ROW, or that lies at or
+// behind srcRows once the base is off, reads nothing and gives the column's fill. valid (may be null): one bit per row,
+// whole words up to ceil(nRows / 32). counts[0] += the HJ_NO_ROW entries, counts[1] += the out-of-range ones. The caller
+// has checked widths, alignment and nRows, srcRows <= 2^32 - 1.
+hipError_t launch_gather(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols& cols, uint32_t nCols,
+                         uint32_t* valid, unsigned long long* counts, hipStream_t s);
+
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):
 // pass 1 cuts the relation into C1 chunks and writes bin b of chunk c to the fragment (b * C1 + c) of cap1 key slots;

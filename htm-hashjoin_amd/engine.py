@@ -191,6 +191,31 @@ class HashJoinContext:
         """hj_r_marks_clear: every R row unmatched again, without rebuilding."""
         self._check(lib.hj_r_marks_clear(self._h))
 
+    # ---- payload columns through a row map ---------------------------------
+    def gather(self, d_map, n_rows, src_rows, cols, d_valid=0, row_base=0):
+        """hj_gather_dev: for every output row k < n_rows and e = d_map[k] (a device uint32 map as probe_pairs,
+        prj_probe_pairs and r_rows write them), dst[k] = src[e - row_base] in every column; a row whose entry is NO_ROW, or
+        lies at or behind src_rows once the base is off, reads nothing and gets the column's fill. cols: up to
+        HJ_GATHER_MAX_COLS tuples (src_ptr, dst_ptr, width, fill), width 1, 2, 4, 8 or 16 bytes, fill an int or bytes (its
+        low `width` bytes count). d_valid (0: none): device uint32 words, bit k & 31 of word k >> 5 = row k has a source
+        row. Asynchronous; needs no reserve and no table."""
+        cols = list(cols)
+        arr = (_lib.hj_gather_col * max(len(cols), 1))()
+        for c, (src, dst, width, fill) in zip(arr, cols):
+            if isinstance(fill, (bytes, bytearray)):
+                fill = int.from_bytes(bytes(fill[:16]), "little")
+            c.src, c.dst, c.width, c.reserved = src or None, dst or None, width, 0
+            c.fill[0], c.fill[1] = fill & 0xFFFFFFFFFFFFFFFF, (fill >> 64) & 0xFFFFFFFFFFFFFFFF
+        self._check(lib.hj_gather_dev(self._h, C.c_void_p(d_map) if d_map else None, n_rows, row_base, src_rows,
+                                      arr if cols else None, len(cols), C.c_void_p(d_valid) if d_valid else None))
+
+    def gather_info(self):
+        """hj_gather_info (waits for the stream): (rows of the last gather, its NULL rows, its device time in
+        microseconds, its out-of-range entries); all 0 before the first one."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_gather_info(self._h, out))
+        return tuple(int(x) for x in out)
+
     def prj_join(self, dR_ptr, rSize, dS_ptr, sSize):
         self._check(lib.hj_prj_join_dev(self._h, C.c_void_p(dR_ptr), rSize,
                                         C.c_void_p(dS_ptr) if dS_ptr else None, sSize))
@@ -654,6 +679,197 @@ def radix_outer_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0,
             for p in held:
                 ctx.dev_free(p)
     return _outer_result(kind, parts_s, parts_r, r_only)
+
+
+# ---- the joined rows themselves: payload columns through the maps, on the device --------------------------------------
+_TABLE_HOWS = tuple(_lib.JOIN_KINDS) + tuple(_OUTER_KINDS)
+_GATHER_WIDTHS = (1, 2, 4, 8, 16)
+
+
+def _table_columns(fn, side, cols, n):
+    """the payload columns of one side as {name: contiguous 1-D array}; ValueError for what the gather cannot take"""
+    out = {}
+    for name, col in (cols or {}).items():
+        a = np.asarray(col)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"{fn}: {side} column {name!r} must be 1-D with {n} elements, not shape {a.shape}")
+        if a.dtype.itemsize not in _GATHER_WIDTHS:
+            raise ValueError(f"{fn}: {side} column {name!r} has {a.dtype.itemsize}-byte elements; 1, 2, 4, 8 or 16 can be gathered")
+        out[name] = np.ascontiguousarray(a)
+    return out
+
+
+def _take_on_host(cols, idx):
+    """a side of a join that needed no device (an input is empty, so idx is all rows in order or all NO_ROW)"""
+    valid = idx != NO_ROW
+    out = {}
+    for name, col in cols.items():
+        out[name] = np.zeros(idx.size, dtype=col.dtype)
+        out[name][valid] = col[idx[valid]]
+    return out, valid
+
+
+class _Held:
+    """device allocations of one wrapper call: alloc / free as it goes, close frees what is left"""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptrs = ctx, []
+
+    def alloc(self, nbytes):
+        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 4)))
+        return self.ptrs[-1]
+
+    def put(self, a):
+        d = self.alloc(a.nbytes)
+        if a.nbytes:
+            self.ctx.copy_h2d(d, a)
+        return d
+
+    def free(self, *ptrs):
+        for p in ptrs:
+            self.ptrs.remove(p)
+            self.ctx.dev_free(p)
+
+    def close(self):
+        for p in self.ptrs:
+            self.ctx.dev_free(p)
+        self.ptrs = []
+
+
+def _gather_side(ctx, held, d_map, n_rows, row_base, src_rows, d_cols):
+    """One side of n_rows result rows out of the device map d_map: d_cols = [(name, device source, dtype)] -> ({name:
+    array}, valid). One gather call per HJ_GATHER_MAX_COLS columns, the validity plane with the first (alone when the
+    side has no column). The library's own maps have no out-of-range entry: one is an error."""
+    out = {name: np.empty(n_rows, dtype=dt) for name, _, dt in d_cols}
+    words = np.zeros((n_rows + 31) // 32, dtype=np.uint32)
+    if n_rows:
+        d_valid = held.alloc(words.nbytes)
+        dsts = [held.alloc(n_rows * dt.itemsize) for _, _, dt in d_cols]
+        calls = [(d_cols[i:i + _lib.HJ_GATHER_MAX_COLS], dsts[i:i + _lib.HJ_GATHER_MAX_COLS])
+                 for i in range(0, len(d_cols), _lib.HJ_GATHER_MAX_COLS)] or [([], [])]
+        for k, (part, part_dst) in enumerate(calls):
+            ctx.gather(d_map, n_rows, src_rows, [(src, dst, dt.itemsize, 0) for (_, src, dt), dst in zip(part, part_dst)],
+                       d_valid=0 if k else d_valid, row_base=row_base)
+            stray = ctx.gather_info()[3]
+            if stray:
+                raise HashJoinError(_lib.HJ_ERR_STATE, f"{stray} map entries outside the {src_rows} source rows from {row_base}")
+        ctx.copy_d2h(words, d_valid)
+        for (name, _, _), dst in zip(d_cols, dsts):
+            ctx.copy_d2h(out[name], dst)
+        held.free(d_valid, *dsts)
+    valid = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
+    return out, valid
+
+
+def _fetch_map(ctx, d_map, n):
+    idx = np.empty(n, dtype=np.uint32)
+    if n:
+        ctx.copy_d2h(idx, d_map)
+    return idx
+
+
+def _concat_side(parts, cols):
+    """[(columns, valid)] of the calls of one side -> (columns, valid)"""
+    return ({name: np.concatenate([p[0][name] for p in parts]) if parts else np.empty(0, dtype=col.dtype)
+             for name, col in cols.items()},
+            np.concatenate([p[1] for p in parts]) if parts else np.empty(0, dtype=bool))
+
+
+def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", probeLength=4, radixBits=0, slice_tuples=None,
+                device=0):
+    """The joined rows: the key tuples relR / relS as join_pairs takes them, and payload columns of either side (r_cols /
+    s_cols: {name: 1-D numpy array of len(rel) elements of 1, 2, 4, 8 or 16 bytes; structured dtypes welcome}) gathered
+    through the join's maps on the device -- the maps go from the probe, or the sweep of the R marks, straight into
+    HashJoinContext.gather and come to the host only as part of the result.
+    how: inner | left | semi | anti (join_pairs) and right | full | right_semi | right_anti (outer_join_pairs).
+    path: "htm" | "atomic" | "nocc", the table probes with their meaning of a match, or "radix", the resident radix join
+    (radixBits; slice_tuples: relS and its columns are uploaded, probed and gathered in slices of that many tuples).
+    Returns {"s_idx", "r_idx", "s", "r", "s_valid", "r_valid"}: the maps as the pairs wrappers give them, the gathered
+    columns per side as {name: array of the input dtype} and one bool per row and side (False: the row has no tuple of
+    that side, its columns are all-zero bytes). A side the kind has no plane for (R for semi / anti, S for right_semi /
+    right_anti) is None in all three. For right / full the R-only rows follow the probe's rows, R ascending."""
+    fn = "join_tables"
+    if not isinstance(how, str) or how not in _TABLE_HOWS:
+        raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
+    if not isinstance(path, str) or path not in ("htm", "atomic", "nocc", "radix"):
+        raise ValueError(f"{fn}: path must be htm, atomic, nocc or radix, not {path!r}")
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    r_cols = _table_columns(fn, "R", r_cols, relR.size)
+    s_cols = _table_columns(fn, "S", s_cols, relS.size)
+    outer = how in _OUTER_KINDS
+    kind, which = _OUTER_KINDS[how] if outer else (_lib.JOIN_KINDS[how], None)
+    plane_s = kind is not None                              # right_semi / right_anti: R rows alone
+    plane_r = outer or kind <= _lib.HJ_JOIN_LEFT            # semi / anti: S rows alone
+    tail = outer and plane_s                                # right / full: the R-only rows follow the probe's
+    radix = path == "radix"
+    step = relS.size if not (radix and slice_tuples) else min(int(slice_tuples), relS.size)
+    if radix and relS.size and step < 1:
+        raise ValueError(f"{fn}: slice_tuples must be positive, not {slice_tuples!r}")
+
+    def result(s_idx, r_idx, s_side, r_side):
+        return {"s_idx": s_idx, "r_idx": r_idx, "s": s_side[0] if plane_s else None, "r": r_side[0] if plane_r else None,
+                "s_valid": s_side[1] if plane_s else None, "r_valid": r_side[1] if plane_r else None}
+
+    trivial = (_outer_without_device(kind, which, relR.size, relS.size) if outer
+               else _join_without_device(kind, relR.size, relS.size))
+    if trivial is not None:
+        s_idx, r_idx = trivial
+        return result(s_idx, r_idx, _take_on_host(s_cols, s_idx) if plane_s else None,
+                      _take_on_host(r_cols, r_idx) if plane_r else None)
+
+    s_maps, r_maps, s_parts, r_parts = [], [], [], []
+    with HashJoinContext(device) as ctx:
+        held = _Held(ctx)
+        try:
+            ctx.reserve("prj" if radix else path, relR.size, step, probeLength=probeLength, radixBits=radixBits,
+                        keepRowIds=True, trackRMatches=outer)
+            dR = held.put(relR)
+            d_r_cols = [(name, held.put(col), col.dtype) for name, col in r_cols.items()] if plane_r else []
+            if radix:
+                ctx.prj_build(dR, relR.size)
+            else:
+                ctx.build(dR, relR.size)
+            probe = ctx.prj_probe_pairs if radix else ctx.probe_pairs
+            dS = held.alloc(8 * step)
+            d_s_slice = [(name, held.alloc(step * col.dtype.itemsize), col.dtype) for name, col in s_cols.items()] if plane_s else []
+            capacity = step if plane_s else 0               # a mark-only pass needs no planes
+            d_s, d_r = (held.alloc(4 * capacity), held.alloc(4 * capacity) if plane_r else 0) if capacity else (0, 0)
+            for lo in range(0, relS.size, step):
+                part = relS[lo:lo + step]
+                ctx.copy_h2d(dS, part)
+                probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
+                if not plane_s:
+                    continue
+                found, written = ctx.pairs_info()[:2]
+                if found > capacity:                        # sized for a foreign-key join: enlarge to the reported count, once
+                    held.free(*(p for p in (d_s, d_r) if p))
+                    capacity = found
+                    d_s, d_r = held.alloc(4 * capacity), (held.alloc(4 * capacity) if plane_r else 0)
+                    probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
+                    found, written = ctx.pairs_info()[:2]
+                for (name, d_col, _) in d_s_slice:
+                    ctx.copy_h2d(d_col, s_cols[name][lo:lo + step])
+                s_maps.append(_fetch_map(ctx, d_s, written))
+                s_parts.append(_gather_side(ctx, held, d_s, written, lo, part.size, d_s_slice))
+                if plane_r:
+                    r_maps.append(_fetch_map(ctx, d_r, written))
+                    r_parts.append(_gather_side(ctx, held, d_r, written, 0, relR.size, d_r_cols))
+            if not radix:
+                ctx.fetch()         # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
+            if outer:               # the R-only rows: the sweep's map feeds the gather where it lies
+                d_rows = held.alloc(4 * relR.size)
+                ctx.r_rows(which, d_rows, relR.size)
+                n_tail = ctx.r_rows_info()[1]
+                r_maps.append(_fetch_map(ctx, d_rows, n_tail))
+                r_parts.append(_gather_side(ctx, held, d_rows, n_tail, 0, relR.size, d_r_cols))
+                if tail:            # their S side is NULL by construction
+                    s_maps.append(np.full(n_tail, NO_ROW, dtype=np.uint32))
+                    s_parts.append(_take_on_host(s_cols, s_maps[-1]))
+        finally:
+            held.close()
+    return result(np.concatenate(s_maps) if plane_s else None, np.concatenate(r_maps) if plane_r else None,
+                  _concat_side(s_parts, s_cols), _concat_side(r_parts, r_cols))
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

@@ -280,6 +280,38 @@ int hj_r_rows_dev(hj_ctx *ctx, uint32_t which, uint32_t *dOutR, uint64_t capacit
  * (= min(out[0], capacity)), out[2] = its device time in microseconds (rounded) -- all 0 when there was none --, out[3] =
  * R rows of the build. HJ_ERR_STATE as for hj_r_rows_dev. */
 int hj_r_rows_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- payload columns through the row maps ----
+ * The planes of hj_probe_join_dev / hj_prj_probe_join_dev and the rows of hj_r_rows_dev are gather maps; hj_gather_dev is
+ * the step from a map to the joined rows: for output row k and e = dMap[k],
+ *   e == HJ_NO_ROW (the raw entry, whatever rowBase is)     a NULL row: every column gets its fill, validity bit 0
+ *   i = e - rowBase, unsigned, >= srcRows                   out of range: never dereferenced; fill and bit 0 like a NULL
+ *                                                           row, and counted apart (hj_gather_info out[3])
+ *   otherwise                                               dst[k] = src[i] in every column, validity bit 1
+ * rowBase is the idxBase / sIdxBase the map was written with (S slices: the slice's sIdxBase with the slice's columns).
+ * The library's own maps over the relation they were made from have no out-of-range entry. The map is taken as it is:
+ * it is neither sorted nor bucketed, so a random map fetches one cache line per element. */
+#define HJ_GATHER_MAX_COLS 8
+typedef struct {
+    const void *src;     /* device: srcRows elements of `width` bytes (may be NULL when srcRows == 0) */
+    void       *dst;     /* device: nRows elements of `width` bytes                                   */
+    uint32_t    width;   /* 1, 2, 4, 8 or 16; src and dst aligned to it                               */
+    uint32_t    reserved;/* 0                                                                          */
+    uint64_t    fill[2]; /* the low `width` bytes are what a NULL row gets                            */
+} hj_gather_col;         /* 40 bytes */
+/* Gathers nCols (0 .. HJ_GATHER_MAX_COLS) columns through dMap[0..nRows), one pass over the map per element width
+ * among them. `cols` is host memory and is read before the call returns. dValid (may be NULL): the validity plane in the Arrow layout, bit k & 31 of 32-bit
+ * word k >> 5, 1 = valid; words 0 .. ceil(nRows / 32) - 1 are written whole (the bits at or behind nRows are 0), nothing
+ * behind them. nCols 0 with a dValid gives the plane alone. Needs no table, no hj_reserve and no particular state; touches
+ * no counter of hj_result, hj_pairs_info or hj_r_rows_info. Asynchronous on the context's stream. nRows 0 is a no-op.
+ * HJ_ERR_INVALID (nothing is enqueued): nCols > HJ_GATHER_MAX_COLS; a width other than 1, 2, 4, 8, 16; reserved != 0; a
+ * dst, or with srcRows > 0 a src, that is NULL or not aligned to its width; dMap NULL with nRows > 0; cols NULL with
+ * nCols > 0; nRows or srcRows above 2^32 - 1; nCols == 0 and dValid == NULL with nRows > 0. */
+int hj_gather_dev(hj_ctx *ctx, const uint32_t *dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows,
+                  const hj_gather_col *cols, uint32_t nCols, uint32_t *dValid);
+/* Waits for the stream. About the last hj_gather_dev that enqueued work: out[0] = its rows, out[1] = its NULL rows
+ * (HJ_NO_ROW entries), out[2] = its device time in microseconds (rounded), out[3] = its out-of-range entries. All 0 before
+ * the first one. */
+int hj_gather_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
