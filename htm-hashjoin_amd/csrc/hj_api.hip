@@ -1417,6 +1417,21 @@ int hj_wave_planar_info(hj_ctx* c, uint64_t out[4])
     return HJ_OK;
 }
 
+int hj_table_debug(hj_ctx* c, uint64_t out[6])
+{
+    HJ_ENTER(c, out);
+    if (!c->built) return fail(c, HJ_ERR_STATE, "hj_table_debug: no table (call hj_build_dev first)");
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (const int rc = read_counters(c, false)) return rc;
+    const Counters& k = *c->hCtr;
+    out[0] = k.validLo; out[1] = k.validHiEx;
+    out[2] = k.tableFormat;
+    out[3] = c->tableSize;                                   // htm: 4 slots per bucket
+    out[4] = (uint64_t)reinterpret_cast<uintptr_t>(c->buf[B_TABLE].p);
+    out[5] = c->buf[B_TABLE].bytes;
+    return HJ_OK;
+}
+
 int hj_prj_workspace_info(uint64_t rSize, uint64_t sSize, uint32_t radixBits, uint64_t out[4])
 {
     if (!out || radixBits > 16) return HJ_ERR_INVALID;

@@ -96,6 +96,15 @@ struct Counters {
     // and deferred targets; k_finalize_range turns them into the valid SLOT range
     // [validLo, validHiEx): a home slot outside it cannot match anything (k_probe skips it), slots in
     // [validLo, validHiEx + 512) hold defined values.
+    // THE contract, for every build that sets the range and every reader of the table: the test is on the HOME slot --
+    // home in [validLo, validHiEx) is probed, and its walk stays inside the defined slots. Everything outside
+    // [validLo, validHiEx + 512) keeps what an earlier build on the context left, in that build's format, and is never
+    // looked at. validHiEx is at most 1024 slots above the last slot a tuple can land on (window: the last block touched
+    // + 1 is probed; rings: one ring from the granule the window stands on), and validHiEx + 512 >= tableSize makes the
+    // whole table valid (set_valid_range). The bucketised probes (k_htm_probe, HtmTable) state the same per bucket: a
+    // bucket is read when its four slots are defined, slot + 3 < validHiEx + 512; k_htm_sums and hj_export_buckets count
+    // the buckets [validLo / 4, (validHiEx + 512) / 4). Both conventions agree on every bucket a build can fill: buckets
+    // with a home in [validHiEx, validHiEx + 512) are defined and empty.
     unsigned long long usedLoInv, usedHi1;
     unsigned long long validLo, validHiEx;
     unsigned long long foreign;      // tuples of the build / probe inputs that fail the shard check (ShardCheck)

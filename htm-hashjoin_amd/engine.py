@@ -290,6 +290,15 @@ class HashJoinContext:
         self._check(lib.hj_wave_planar_info(self._h, out))
         return {"planar": bool(out[0]), "planarFallback": int(out[1]), "tableFormat": int(out[2])}
 
+    def table_debug(self):
+        """hj_table_debug (waits for the stream; for tests): the valid slot range [validLo, validHiEx) of the last build,
+        its table format (0 = 8-byte slots, 1 = 4-byte keys), the slots of the live table (htm: 4 per bucket), and the
+        table buffer's device address and size in bytes -- with copy_d2h, the raw table words."""
+        out = (C.c_uint64 * 6)()
+        self._check(lib.hj_table_debug(self._h, out))
+        return {"validLo": int(out[0]), "validHiEx": int(out[1]), "tableFormat": int(out[2]), "tableSlots": int(out[3]),
+                "tableAddr": int(out[4]), "tableBytes": int(out[5])}
+
     def synchronize(self):
         self._check(lib.hj_synchronize(self._h))
 

@@ -457,6 +457,15 @@ int hj_wave_seams(hj_ctx *ctx, uint32_t *starts, uint32_t *bounds, uint32_t *pco
  * out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys), out[3] = 0. hj_result.compactFallback does not speak of this.
  * HJ_ERR_STATE: no open-addressing table. */
 int hj_wave_planar_info(hj_ctx *ctx, uint64_t out[4]);
+/* The table of the last hj_build_dev / hj_build_keys_dev as its readers see it (waits for the stream; for tests). An LDS
+ * build (buildVariant 2, 3, 4, also under HJ_ALGO_HTM) writes only the slots some tuple can reach: out[0], out[1] = the
+ * valid slot range [validLo, validHiEx) -- a home slot outside it matches nothing, the slots [validLo, validHiEx + 512)
+ * hold defined contents, and everything else in the buffer is whatever an earlier build on this context left there, in
+ * that build's format. out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys; HJ_ALGO_HTM: always 0), out[3] = slots of
+ * the live table (HJ_ALGO_HTM: 4 per bucket), out[4] = device address of the table buffer, out[5] = its size in bytes
+ * (hj_reserve only grows it). With out[4], hj_copy_d2h reads the raw table words. Changes nothing.
+ * HJ_ERR_STATE: no table (no build yet, or the last operation was a radix join). */
+int hj_table_debug(hj_ctx *ctx, uint64_t out[6]);
 
 /* ---- device memory for hosts without a HIP runtime of their own ----------- */
 int hj_dev_alloc(hj_ctx *ctx, uint64_t bytes, void **dptr);
