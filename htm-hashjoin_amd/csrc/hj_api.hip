@@ -73,6 +73,10 @@ struct hj_ctx {
     bool htmBuilt = false;
     bool htmGenericChains = false;              // build_htm's second attempt: no routing, generic chain kernels
     bool htmChainsFellBack = false;             // ... and that it happened (hj_result.compactFallback bit 8)
+    // the LDS chain phase of the last build_htm (hj_htm_chain_info): 0 not tried, 1 held, 2 handed over; the cause mask of a
+    // hand-over (Counters::htmChainBail of the first attempt: the second one resets the counters); overflow buckets of the parts
+    uint32_t htmChainState = 0;
+    uint64_t htmChainCause = 0, htmChainGroups = 0;
     uint32_t htmBuckets = 0;                    // numBuckets of the last htm build
     uint64_t htmOverflowUsed = 0;
     // streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev)
@@ -641,7 +645,7 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     int rc;
     if ((rc = begin_operation(c, rSize, 0, slots))) return rc;
     c->hshift = 0; c->htmBuckets = nb;
-    if (!c->htmGenericChains) c->htmChainsFellBack = false;
+    if (!c->htmGenericChains) { c->htmChainsFellBack = false; c->htmChainState = 0; c->htmChainCause = 0; c->htmChainGroups = 0; }
     if ((rc = record(c, EV_CLEAR0))) return rc;
     const BuildJob job = build_job(c, dR, false, rSize, 0, slots, 3, idxBase, ShardCheck{0, 0, 0, 0});
     uint64_t* const htmConflicts = c->buf[B_HTM_CONFLICTS].as<uint64_t>();
@@ -663,7 +667,7 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     const WaveSlices sl = variant == 2 ? own_conflict_layout(rSize, c->nCU, ownCounts) : wave_conflict_layout(rSize, c->nCU, bounds);
     // the rings: chains in LDS (hj_htm.hip) unless an earlier attempt on this relation had to give up
     const uint32_t nParts = sl.nChunks * htm_chain_parts(sl.sliceLen);
-    const bool ldsChains = variant == 3 && !c->htmGenericChains && (uint64_t)nParts + 1 <= nb && htm_chain_info_words(sl.nChunks, sl.sliceLen) <= nb;
+    const bool ldsChains = variant == 3 && !c->htmGenericChains && htm_chain_tries(sl.nChunks, sl.sliceLen, nb);
     if (variant == 2) {
         if ((rc = record(c, EV_BUILD0))) return rc;
         const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>(), htmConflicts, ownCounts};
@@ -696,14 +700,17 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     c->htmOverflowUsed = conflicts;
     if (ldsChains && c->hCtr->htmChainBail) {
         // an input the LDS chain phase cannot take (hj_htm.hip): once more, unrouted, with the generic chain kernels
+        c->htmChainCause = c->hCtr->htmChainBail;               // kept here: the second attempt zeroes the counters
         c->htmGenericChains = true;
         rc = build_htm(c, dR, rSize, idxBase);
         c->htmGenericChains = false;
         c->htmChainsFellBack = true;
+        c->htmChainState = 2;
         return rc;
     }
     if (ldsChains) {
         const uint64_t groups = c->hFit[0];                     // overflow buckets the parts need, exactly
+        c->htmChainState = 1; c->htmChainGroups = groups;
         if (conflicts) {
             if ((rc = reserve_htm_overflow(c, groups))) return rc;
             HJ_HIP(c, launch_htm_chain_fill(htmConflicts, sl.nChunks, sl.sliceLen, nb, ovfBase, ovfCount, job.table,
@@ -1317,6 +1324,8 @@ int hj_export_buckets(hj_ctx* c, void* host_buckets, uint64_t numBuckets, void* 
             if (i < lo || i >= hi) { p[0] = p[1] = p[2] = p[3] = 0; continue; }
             uint32_t count = 0;
             for (int j = 0; j < 3; ++j) { count += p[j] != kEmpty; p[j] = (p[j] == kEmpty) ? 0 : (uint32_t)p[j]; }
+            // a bucket with a link word carries its count there: that stored word is what is exported, not a recount
+            if (p[3] != kEmpty) count = (uint32_t)p[3];
             const uint32_t next = p[3] == kEmpty ? 0u : (uint32_t)(p[3] >> 32);
             p[3] = (uint64_t)count | ((uint64_t)next << 32);     // little-endian {uint32 count; uint32 nextIndex}
         }
@@ -1399,6 +1408,31 @@ int hj_wave_seams(hj_ctx* c, uint32_t* starts, uint32_t* bounds, uint32_t* pcoun
     HJ_HIP(c, hipMemcpy(starts, w.starts, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HJ_HIP(c, hipMemcpy(bounds, w.bounds, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (pcounts) HJ_HIP(c, hipMemcpy(pcounts, w.pcounts, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HJ_OK;
+}
+
+int hj_htm_chain_layout_info(const hj_ctx* c, uint32_t computeUnits, uint64_t n, uint64_t out[8])
+{
+    if (!out || (!c && (computeUnits == 0 || computeUnits > 65536)) || n == 0 || n > 0xFFFFFFFFull) return HJ_ERR_INVALID;
+    const int nCU = c ? c->nCU : (int)computeUnits;
+    const WaveLayout w = wave_layout(n, nCU);
+    const uint64_t v[8] = {w.nChunks, w.sliceLen, htm_chain_parts((uint32_t)w.sliceLen), kChainCountCap, kChainCap, kChainMaxParts,
+                           kChainPartTuples,
+                           // build_htm's rule for a request for the rings: they must take the table at all (wave_supported), and
+                           // the phase's scratch must fit (htm_chain_tries -- which every table the rings take satisfies)
+                           (wave_supported(4ull * htm_num_buckets(n)) &&
+                            htm_chain_tries((uint32_t)w.nChunks, (uint32_t)w.sliceLen, htm_num_buckets(n))) ? 1u : 0u};
+    memcpy(out, v, sizeof v);
+    return HJ_OK;
+}
+
+int hj_htm_chain_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    if (!c->built || !c->htmBuilt) return fail(c, HJ_ERR_STATE, "hj_htm_chain_info: no htm table (call hj_build_dev on a context reserved for HJ_ALGO_HTM)");
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = c->htmChainState; out[1] = c->htmChainCause; out[2] = c->htmChainGroups; out[3] = 0;
     return HJ_OK;
 }
 

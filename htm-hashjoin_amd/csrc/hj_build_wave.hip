@@ -919,7 +919,7 @@ k_wave_deferred(DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ 
                         while (b - a > 1) { const uint32_t mid = (a + b) >> 1; if (routeBounds[mid] <= gran) a = mid; else b = mid; }
                         const uint32_t at = atomicAdd(&ccounts[a], 1u);
                         if (at < chunkLen) htmConflicts[(uint64_t)a * chunkLen + at] = mine;
-                        else atomicExch(&ctr->htmChainBail, 1ull);
+                        else atomicOr(&ctr->htmChainBail, kChainBailSliceFull);
                     }
                     continue;
                 }

@@ -121,7 +121,8 @@ struct Counters {
     // --algo htm (hj_htm.hip): overflow buckets linked, sum of the tuples they hold
     unsigned long long htmOverflowBuckets, htmOverflowSum;
     // raised by the LDS chain phase (k_htm_chain_lds) or by the routing of the deferred phase's conflicts when an input
-    // does not fit them: the host then redoes the build without routing and chains with the generic kernels
+    // does not fit them: the host then redoes the build without routing and chains with the generic kernels. A mask of
+    // causes (kChainBail*: the table next to the caps, below in this file)
     unsigned long long htmChainBail;
     // PRJ, histogram-free partitioning (hj_prj.hip): set to 1 by the scatter kernel that finds a fragment too small;
     // the rest of that path then returns at once and the exact (histogram) path, gated on this word, runs instead
@@ -425,7 +426,27 @@ hipError_t launch_htm_chains(const uint64_t* conflicts, const uint32_t* ccounts,
                              uint64_t* overflow, uint64_t overflowCapBuckets, Counters* ctr, hipStream_t s);
 // the chain phase in LDS, after the ring build with routed conflicts (hj_htm.hip): count -> partGroups[nSlices * parts] (overflow
 // buckets per part; scan it, one word more for the total) and info (htm_chain_info_words words); fill builds the chains
+constexpr int kChainThreads = 512;
+constexpr uint32_t kChainCountCap = 12288;           // buckets a slice's conflicts may span (k_htm_chain_count's LDS counters)
+constexpr uint32_t kChainCap = 3072;                 // buckets per part = the fill's LDS counters; tuple slots of its overflow image (36 KiB: 4 workgroups per CU)
+constexpr uint32_t kChainMaxParts = 16;
+constexpr uint32_t kChainPartTuples = 4224;          // htm_chain_parts: a part per this many positions of a slice
+// Counters::htmChainBail is a mask of WHY the LDS chain phase gave up (atomicOr; hj_htm_chain_info reports it):
+//   bit  constant              raised by                      when
+//   0    kChainBailSliceFull   k_htm_chain_count, the router  a slice took more conflicts than sliceLen (m > sliceLen; no place left)
+//   1    kChainBailStray       k_htm_chain_count              a conflict lies outside its slice's bucket range [B0, B1)
+//   2    kChainBailSpan        k_htm_chain_count              span > kChainCountCap
+//   3    kChainBailSub         k_htm_chain_count              sub > kChainCap
+//   4    kChainBailImage       k_htm_chain_count              a part needs more than kChainCap / 3 overflow buckets
+// A slice over its length raises bit 0 alone (nothing else of it is looked at); bits 1 to 3 of a slice are raised together;
+// bit 4 only by a slice that passed them. A workgroup that starts after the mask has become non-zero returns at once, so
+// the mask read back is a NON-EMPTY SUBSET of the causes the input holds, never a cause it does not hold.
+constexpr unsigned long long kChainBailSliceFull = 1, kChainBailStray = 2, kChainBailSpan = 4, kChainBailSub = 8, kChainBailImage = 16;
 uint32_t htm_chain_parts(uint32_t sliceLen);
+// the host's rule: the LDS phase is tried when its scratch (groups per part + total, info words) fits the per-bucket arrays.
+// Only tables of two buckets or fewer fail it, and the rings need 256 (wave_supported): behind buildVariant 3 it always
+// holds -- it guards the scratch arrays, it decides nothing
+bool htm_chain_tries(uint32_t nSlices, uint32_t sliceLen, uint32_t numBuckets);
 size_t htm_chain_info_words(uint32_t nSlices, uint32_t sliceLen);
 hipError_t launch_htm_chain_count(const uint64_t* conflicts, const uint32_t* ccounts, const uint32_t* bounds, uint32_t nSlices,
                                   uint32_t sliceLen, uint32_t numBuckets, uint32_t* partGroups, uint32_t* info, Counters* ctr, hipStream_t s);

@@ -168,11 +168,7 @@ k_htm_link(uint64_t* __restrict__ table, uint32_t numBuckets, const unsigned int
 // Anything that does not fit (a slice spanning more than kChainCountCap buckets: sparse keys; a part of more than kChainCap
 // buckets or image slots: many duplicates; a conflict outside its slice's range) raises Counters::htmChainBail, and the
 // host redoes the build without routing and chains with the generic kernels.
-constexpr int kChainThreads = 512;
-constexpr uint32_t kChainCountCap = 12288;           // buckets a slice's conflicts may span (k_htm_chain_count's LDS counters)
-constexpr uint32_t kChainCap = 3072;                 // buckets per part = the fill's LDS counters; tuple slots of its overflow image (36 KiB: 4 workgroups per CU)
-constexpr uint32_t kChainMaxParts = 16;
-
+// The caps (kChainCountCap, kChainCap, kChainMaxParts) and the table of causes the word is a mask of: hj_device.h.
 __device__ __forceinline__ uint32_t chain_block_exclusive_scan(uint32_t v, uint32_t* wsum /*[kChainThreads / 64]*/, uint32_t& total)
 {
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -212,8 +208,8 @@ k_htm_chain_count(const uint64_t* __restrict__ conflicts, const uint32_t* __rest
     const uint32_t m = ccounts[c];
     uint32_t* const sInfo = info + 2 * (size_t)c;
     uint32_t* const pInfo = info + 2 * (size_t)nSlices + 2 * (size_t)c * parts;
-    auto bail = [&]() { if (threadIdx.x == 0) atomicExch(&ctr->htmChainBail, 1ull); };
-    if (m > sliceLen) { bail(); return; }
+    auto bail = [&](unsigned long long why) { if (threadIdx.x == 0) atomicOr(&ctr->htmChainBail, why); };
+    if (m > sliceLen) { bail(kChainBailSliceFull); return; }
     if (m == 0) {
         if (threadIdx.x == 0) { sInfo[0] = 0; sInfo[1] = 0; }
         if (threadIdx.x < parts) { partGroups[c * parts + threadIdx.x] = 0; pInfo[2 * threadIdx.x] = 0; pInfo[2 * threadIdx.x + 1] = 0; }
@@ -235,7 +231,10 @@ k_htm_chain_count(const uint64_t* __restrict__ conflicts, const uint32_t* __rest
     __syncthreads();
     const uint32_t E0 = sMin, span = ~sMaxInv - E0 + 1u;
     const uint32_t sub = (span + parts - 1) / parts;                           // buckets per part
-    if (sStray || span > kChainCountCap || sub > kChainCap) { bail(); return; }   // (a conflict filed under the wrong chunk: not this path)
+    if (sStray || span > kChainCountCap || sub > kChainCap) {                    // (a conflict filed under the wrong chunk: not this path)
+        bail((sStray ? kChainBailStray : 0ull) | (span > kChainCountCap ? kChainBailSpan : 0ull) | (sub > kChainCap ? kChainBailSub : 0ull));
+        return;
+    }
     for (uint32_t i = threadIdx.x; i < span; i += kChainThreads) cnt[i] = 0;
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < m; i += kChainThreads) {
@@ -264,7 +263,7 @@ k_htm_chain_count(const uint64_t* __restrict__ conflicts, const uint32_t* __rest
     if (threadIdx.x == 0) { sInfo[0] = E0; sInfo[1] = sub; }
     if (threadIdx.x < parts) {
         const uint32_t g = pGroups[threadIdx.x];
-        if (3u * g > kChainCap) atomicExch(&ctr->htmChainBail, 1ull);
+        if (3u * g > kChainCap) atomicOr(&ctr->htmChainBail, kChainBailImage);
         partGroups[c * parts + threadIdx.x] = g;
         pInfo[2 * threadIdx.x] = g ? pFirst[threadIdx.x] : 0u;
         pInfo[2 * threadIdx.x + 1] = g ? ~pLastInv[threadIdx.x] + 1u : 0u;
@@ -428,8 +427,13 @@ hipError_t launch_htm_chains(const uint64_t* conflicts, const uint32_t* ccounts,
 uint32_t htm_chain_parts(uint32_t sliceLen)
 {
     // ~4096 tuples' worth of keys per part: 1.4 k buckets on dense keys, a 1.5 k-slot image on `uniform` (half the LDS arrays)
-    const uint32_t p = (sliceLen + 4223u) / 4224u;
+    const uint32_t p = (sliceLen + kChainPartTuples - 1u) / kChainPartTuples;
     return p < 1 ? 1 : p > kChainMaxParts ? kChainMaxParts : p;
+}
+bool htm_chain_tries(uint32_t nSlices, uint32_t sliceLen, uint32_t numBuckets)
+{
+    // the scan of the parts' groups and the info words live in two per-bucket arrays of the table
+    return (uint64_t)nSlices * htm_chain_parts(sliceLen) + 1 <= numBuckets && htm_chain_info_words(nSlices, sliceLen) <= numBuckets;
 }
 size_t htm_chain_info_words(uint32_t nSlices, uint32_t sliceLen) { return 2 * (size_t)nSlices * (1 + htm_chain_parts(sliceLen)); }
 

@@ -82,6 +82,24 @@ def wave_layout_info(n, compute_units):
     return _wave_layout(None, int(compute_units), n)
 
 
+_HTM_CHAIN_LAYOUT_FIELDS = ("slices", "sliceLen", "parts", "chainCountCap", "chainCap", "chainMaxParts", "partTuples", "tries")
+
+
+def _htm_chain_layout(handle, compute_units, n):
+    out = (C.c_uint64 * 8)()
+    rc = lib.hj_htm_chain_layout_info(handle, compute_units, n, out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, f"hj_htm_chain_layout_info(n={n}, computeUnits={compute_units})")
+    return {k: int(out[i]) for i, k in enumerate(_HTM_CHAIN_LAYOUT_FIELDS)}
+
+
+def htm_chain_layout_info(n, compute_units):
+    """hj_htm_chain_layout_info without a context (host-only arithmetic): the slices and parts the LDS chain phase of the
+    bucketised table cuts n tuples' conflicts into on a device of compute_units compute units, the kernel's caps
+    (chainCountCap, chainCap, chainMaxParts, partTuples) and whether the host tries the phase at this size, as a dict."""
+    return _htm_chain_layout(None, int(compute_units), n)
+
+
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
             buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False):
     p = hj_params()
@@ -298,6 +316,18 @@ class HashJoinContext:
         self._check(lib.hj_table_debug(self._h, out))
         return {"validLo": int(out[0]), "validHiEx": int(out[1]), "tableFormat": int(out[2]), "tableSlots": int(out[3]),
                 "tableAddr": int(out[4]), "tableBytes": int(out[5])}
+
+    def htm_chain_layout_info(self, n):
+        """hj_htm_chain_layout_info for this context's device (see engine.htm_chain_layout_info)."""
+        return _htm_chain_layout(self._h, 0, n)
+
+    def htm_chain_info(self):
+        """hj_htm_chain_info (waits for the stream): state 0 = the last htm build did not try the LDS chain phase, 1 = it
+        held, 2 = it handed over (compactFallback bit 8); cause = the mask of why (a non-empty subset of the causes the
+        input holds); groups = overflow buckets the parts asked for where it held."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_htm_chain_info(self._h, out))
+        return {"state": int(out[0]), "cause": int(out[1]), "groups": int(out[2])}
 
     def synchronize(self):
         self._check(lib.hj_synchronize(self._h))

@@ -369,7 +369,9 @@ int hj_export_table(hj_ctx *ctx, uint64_t *host_table, uint64_t tableSize);
  * entries; pass NULL / 0 to learn *nOverflow first). A chain's head is its newest
  * overflow bucket, as in the reference; the physical overflow indices are this
  * library's (a bucket's overflow buckets are neighbours), not the reference's
- * creation order. */
+ * creation order. `count` of a bucket with a chain, and of every overflow bucket,
+ * is the count word the build stored next to the link; of a bucket without a
+ * chain, its tuple slots in use. */
 int hj_export_buckets(hj_ctx *ctx, void *host_buckets, uint64_t numBuckets,
                       void *host_overflows, uint64_t overflowCap, uint64_t *nOverflow);
 
@@ -466,6 +468,30 @@ int hj_wave_planar_info(hj_ctx *ctx, uint64_t out[4]);
  * (hj_reserve only grows it). With out[4], hj_copy_d2h reads the raw table words. Changes nothing.
  * HJ_ERR_STATE: no table (no build yet, or the last operation was a radix join). */
 int hj_table_debug(hj_ctx *ctx, uint64_t out[6]);
+/* The chain phase of the bucketised table behind the ring build (HJ_ALGO_HTM, buildVariant 3): every overflow chain is
+ * built in LDS, one workgroup per PART of a chunk's slice of the conflict list; an input that does not fit hands over to
+ * the generic chain kernels (hj_result.compactFallback bit 8). hj_htm_chain_layout_info is the counterpart of
+ * hj_wave_layout_info (ctx == NULL: host-only arithmetic for computeUnits compute units; else the context's device, and
+ * computeUnits is ignored), for 0 < n < 2^32 tuples: out[0] = slices (= chunks), out[1] = sliceLen (places per slice),
+ * out[2] = parts per slice, out[3] = kChainCountCap (buckets a slice's conflicts may span), out[4] = kChainCap (buckets
+ * per part; tuple slots of a part's overflow image, i.e. kChainCap / 3 overflow buckets), out[5] = kChainMaxParts,
+ * out[6] = positions of a slice per part (parts = ceil(sliceLen / out[6]), at most out[5]), out[7] = 1 when a build of
+ * n tuples that asks for buildVariant 3 tries the LDS phase, else 0: the ring build must take the table at all (at least
+ * one ring of slots, hj_wave_layout_info's ringGranules x granuleSlots; below that buildVariant 3 becomes 2 or 1 and the
+ * phase is not tried), and the phase's scratch must fit two per-bucket arrays (slices x parts + 1 and
+ * 2 x slices x (1 + parts) words, each at most the number of buckets). Every table the rings take has room for the
+ * scratch, so the first condition alone decides. */
+int hj_htm_chain_layout_info(const hj_ctx *ctx, uint32_t computeUnits, uint64_t n, uint64_t out[8]);
+/* What the chain phase of the last hj_build_dev under HJ_ALGO_HTM did (waits for the stream; changes nothing).
+ * out[0] = 0: the LDS phase was not tried (another build variant, or a relation too small for it), 1: it held, 2: it
+ * handed over to the generic chain kernels -- exactly when hj_result.compactFallback has bit 8. out[1] = why it handed
+ * over, else 0: bit 0 = a slice took more conflicts than sliceLen, bit 1 = a conflict lay outside its slice's bucket
+ * range, bit 2 = a slice's conflicts span more than kChainCountCap buckets, bit 3 = a part covers more than kChainCap
+ * buckets, bit 4 = a part needs more than kChainCap / 3 overflow buckets. Workgroups that start after the first cause was
+ * raised return at once: the mask is a non-empty subset of the causes the input holds. out[2] = overflow buckets the
+ * parts asked for when the phase held (= hj_result.htmOverflowBuckets), else 0. out[3] = 0.
+ * HJ_ERR_STATE: no htm table. */
+int hj_htm_chain_info(hj_ctx *ctx, uint64_t out[4]);
 
 /* ---- device memory for hosts without a HIP runtime of their own ----------- */
 int hj_dev_alloc(hj_ctx *ctx, uint64_t bytes, void **dptr);

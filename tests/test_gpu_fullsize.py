@@ -171,3 +171,25 @@ def test_htm_uniform_2p27_chains_in_lds_against_the_sequential_oracle():
                 want["conflictCount"], want["conflictSum"], want["totalMatches"], want["inputSum"], want["bucketSum"],
                 want["overflowBuckets"], want["overflowSum"], want["outputSum"]), variant
         c.dev_free(dR); c.dev_free(dS)
+
+
+@pytest.mark.parametrize("name", ["span_at_cap", "span_over_cap"])
+def test_htm_chain_span_cap_with_five_parts(name):
+    """The one cap of the LDS chain phase no smaller shape reaches (tests/htm_chain_cases.py): a slice's conflicts may span
+    kChainCountCap buckets, and only with five or more parts per slice is that less than parts x kChainCap, i.e. only
+    then can bit 2 be the cause. The smallest n with five parts (about 6.7e7 tuples on 256 compute units), all constants
+    from hj_htm_chain_layout_info: a slice that spans exactly the cap must hold, one bucket more must hand over with bit 2.
+    State, cause, counters and primary buckets of the whole table as in test_gpu_htm_chains.py; the chains are walked for
+    the 2^21 buckets around the slice (the rest of the relation is dense and unique: no chains there, which the counters
+    and the link flags of all primary buckets pin)."""
+    import htm_chain_cases as cc
+    from htm_chain_device import run_case
+    with hj.HashJoinContext(0) as c:
+        n = cc.smallest_n_with_parts(5, None, below=1 << 28, ctx=c)
+        if n is None:
+            pytest.skip("this device's compute units give no relation below 2^28 tuples whose slices have five parts")
+        case = cc.BY_NAME[name]
+        plan, info, got = run_case(c, case, n, bucket_range=lambda what: (max(0, what["lo"] - (1 << 20)), what["hi"] + (1 << 20)))
+        assert plan.parts == 5 and info["state"] == case.state
+        if name == "span_over_cap":
+            assert info["cause"] == cc.BIT_SPAN

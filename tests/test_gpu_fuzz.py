@@ -10,39 +10,11 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+import htm_chain_cases as cc
+from fuzz_relations import make_relation
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def make_relation(rng, n):
-    """A near-sorted relation of n tuples (value = key, as DataGen's): sorted keys with bursts, then displaced by < W."""
-    table = 2 * n
-    kind = rng.integers(0, 5)
-    if kind == 0:          # dense unique keys
-        keys = np.arange(1, n + 1, dtype=np.uint64)
-    elif kind == 1:        # random multiset over a domain of n * f keys
-        f = rng.choice([0.25, 0.5, 1.0, 1.5, 1.99])
-        keys = np.sort(rng.integers(1, max(2, int(n * f)), size=n, dtype=np.uint64))
-    elif kind == 2:        # bursts: few distinct keys, geometric multiplicities
-        distinct = np.sort(rng.choice(np.arange(1, table, dtype=np.uint64), size=max(1, n // int(rng.integers(2, 9))), replace=False))
-        counts = rng.geometric(0.3, size=distinct.size)
-        keys = np.repeat(distinct, counts)[:n]
-        if keys.size < n:
-            keys = np.concatenate([keys, np.arange(1, n - keys.size + 1, dtype=np.uint64) + keys[-1]])
-        keys = np.sort(keys)
-    elif kind == 3:        # sparse keys over the whole table (walks wrap around its end) and a dense stretch at the very top
-        keys = np.sort(np.concatenate([rng.integers(1, table, size=n - n // 8, dtype=np.uint64),
-                                       np.arange(table - n // 8, table, dtype=np.uint64)]))
-    else:                  # two interleaved dense runs (every key twice, far apart in value order only by 1)
-        keys = np.sort(np.concatenate([np.arange(1, n // 2 + 1, dtype=np.uint64)] * 2))
-    keys = keys[:n].astype(np.uint64)
-    keys = np.sort((keys - np.uint64(1)) % np.uint64(table - 1) + np.uint64(1))        # into [1, table - 1], still sorted
-    w = int(rng.choice([1, 2, 4, 8, 16, 16, 16, 32, 48, 64, 100, 300, 2000]))
-    if w > 1:
-        order = np.argsort(np.arange(n) + rng.uniform(0, w, size=n), kind="stable")
-        keys = keys[order]
-    return np.ascontiguousarray(keys), w
 
 
 @pytest.mark.parametrize("block", range(4))
@@ -72,7 +44,9 @@ def test_ring_builds_on_random_near_sorted_relations(block):
 def test_bucketised_table_on_random_near_sorted_relations(block):
     """The same relations through --algo htm: rings with the chain phase in LDS (or, where that gives up, the generic
     chain kernels: bit 8 of compactFallback), window, global atomics, and the device's pick -- every counter, the primary
-    buckets tuple for tuple, the overflow buckets as a multiset, and (small cases) every chain in walk order."""
+    buckets tuple for tuple, the overflow buckets as a multiset, and (small cases) every chain in walk order. Through the
+    rings the LDS phase must hand over exactly when the plan of htm_chain_cases.py, evaluated on the device's own seams,
+    finds a cause, and for causes of the plan's only: no spurious hand-over, no missing one."""
     cases = int(os.environ.get("HJ_FUZZ_CASES", "36")) // 2
     rng = np.random.default_rng(20261000 + block)
     with hj.HashJoinContext(0) as ctx:
@@ -97,6 +71,18 @@ def test_bucketised_table_on_random_near_sorted_relations(block):
                     a, ao = oracle.htm_chains(buckets, overflows)
                     b, bo = oracle.htm_chains(want["buckets"], want["overflows"])
                     assert np.array_equal(ao, bo) and np.array_equal(a, b), tag
+                if variant == 3:
+                    assert got["buildVariant"] == 3, tag                 # at least 1022 tuples: a table the rings take
+                    info = ctx.htm_chain_info()
+                    chain_lay = ctx.htm_chain_layout_info(R.size)
+                    plan = cc.chain_plan(R, ctx.wave_layout_info(R.size), chain_lay, ctx.wave_seams()[1])
+                    tag += (info, plan.mask)
+                    assert chain_lay["tries"] == 1 and plan.strays == 0, tag
+                    assert info["state"] == (2 if plan.mask else 1), tag
+                    assert (info["cause"] != 0) == (plan.mask != 0) and info["cause"] & ~plan.mask == 0, tag
+                    assert (got["compactFallback"] & 0x100 != 0) == (info["state"] == 2), tag
+                    if info["state"] == 1:
+                        assert info["groups"] == want["overflowBuckets"] == plan.total_groups, tag
 
 
 @pytest.mark.parametrize("block", range(2))

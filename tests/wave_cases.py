@@ -50,10 +50,13 @@ def relation(homes, shift=0):
     return (np.asarray(homes, dtype=I64).astype(U64) << U64(shift)) | U64((1 << shift) - 1)
 
 
-def homes_of(rel, table_size, shift=0):
-    """home slot per tuple (int64) and which tuples are valid (upper word 0, not 0)"""
+def homes_of(rel, table_size, shift=0, htm=False):
+    """home slot per tuple (int64) and which tuples are valid (upper word 0, not 0). htm: the bucketised table's home, the
+    first of the four slots of bucket (key / 3) & (table_size / 4 - 1)"""
     rel = np.asarray(rel, dtype=U64)
     valid = ((rel >> U64(32)) == 0) & (rel != 0)
+    if htm:
+        return ((((rel & U64(0xFFFFFFFF)) // U64(3)) << U64(2)) & U64(table_size - 1)).astype(I64), valid
     return (((rel & U64(0xFFFFFFFF)) >> U64(shift)) & U64(table_size - 1)).astype(I64), valid
 
 
@@ -76,7 +79,7 @@ BASES = {"dense": base_dense, "gapped": base_gapped, "odd": base_odd}
 # ---------------------------------------------------------------------------------------------------------------------
 # the pre-pass, restated
 # ---------------------------------------------------------------------------------------------------------------------
-def expected_seams(rel, lay, table_size, home_shift=0):
+def expected_seams(rel, lay, table_size, home_shift=0, htm=False):
     """(starts[nChunks + 1], bounds[nChunks + 1]) as int64, from the rules of k_wave_seams and k_wave_bounds_scan:
       * nominal seam p = c * chunkLen; m = the lowest valid home slot among the SAMPLE tuples from p;
       * chunk c > 0 starts at the first position in [p, p + look) whose (valid) home slot lies at or beyond the first slot
@@ -86,8 +89,9 @@ def expected_seams(rel, lay, table_size, home_shift=0):
         after the highest valid home slot among those positions;
       * bounds = prefix maximum of those granules over the chunks that had a valid tuple in their sample; a chunk without
         one inherits, chunks before the first one take the first one's (0 if there is none); never above the table's
-        granules; bounds[nChunks] = granules of the table, starts[nChunks] = n."""
-    home, valid = homes_of(rel, table_size, home_shift)
+        granules; bounds[nChunks] = granules of the table, starts[nChunks] = n.
+    htm: the same rules on the bucketised table's home slots (table_size = 4 slots per bucket)."""
+    home, valid = homes_of(rel, table_size, home_shift, htm)
     n = home.size
     gran, look, chunk_len, n_chunks = lay["granuleSlots"], lay["look"], lay["chunkLen"], lay["nChunks"]
     assert n_chunks == -(-n // chunk_len)
