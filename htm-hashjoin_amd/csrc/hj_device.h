@@ -493,10 +493,17 @@ __device__ __forceinline__ void flush_plane(const uint32_t* lds, uint32_t cnt, u
 // the build's rSize. Set by the MARK instantiations of the three pairs kernels for every R row of a row they produce
 // (written or cut by the capacity alike), read by the sweep of hj_r_marks.hip. Bits only go 0 -> 1 between clears.
 struct RMarks { uint32_t* words; uint32_t base, rows; };
-// what a MARK instantiation takes where the others take PairsOut: the same planes and cursor, and the marks behind them.
-// (A type of its own so that the kernel arguments of the instantiations without marks stay exactly what they were.)
+// what a MARK instantiation takes where the others take PairsOut: the same planes and cursor, and the marks behind them
 struct PairsOutMarked : PairsOut { RMarks marks; };
 template <bool MARK> using PairsOutOf = std::conditional_t<MARK, PairsOutMarked, PairsOut>;
+template <bool MARK>
+inline PairsOutOf<MARK> pairs_out_of(const PairsOut& out, const RMarks* marks)
+{
+    PairsOutOf<MARK> o;
+    static_cast<PairsOut&>(o) = out;
+    if constexpr (MARK) o.marks = *marks;
+    return o;
+}
 // One produced R row -> its bit. First a relaxed agent-scope LOAD of the word, which L2 serves: a Zipf-hot R row is
 // produced millions of times from every CU, and one word takes a limited number of atomics per microsecond chip-wide.
 // The atomic OR (no value returned) is issued only while the bit reads clear; a stale "clear" costs one redundant OR and
@@ -516,6 +523,136 @@ template <int NT>
 __device__ __forceinline__ void mark_plane(const uint32_t* lds, uint32_t cnt, const RMarks& mk)
 {
     for (uint32_t i = threadIdx.x; i < cnt; i += NT) mark_r_row(mk, lds[i]);
+}
+
+// ---- the pair stage of the three pairs kernels (k_probe_pairs, k_htm_probe_pairs, k_prj_join_pairs) ----
+// How a workgroup gets its place in the output ("Materialising probe"): it collects its rows in an LDS stage of
+// kStagePairs pairs; a round first agrees on its row count -- wavefront scan, the wavefronts' totals exchanged through
+// LDS, one barrier -- and when the stage cannot take the round, the workgroup claims [base, base + fill) with ONE 64-bit
+// atomicAdd on the cursor and the stage leaves LDS through flush_plane.
+constexpr uint32_t kStagePairs = 4096;          // pairs per stage: 2 planes x 16 KiB of LDS
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;        // HJ_NO_ROW: the R row of a LEFT row without a match, a NULL entry of a gather map
+// hj_join_kind; kinds above LEFT write S rows only
+constexpr int kInner = 0, kLeft = 1, kSemi = 2, kAnti = 3;
+
+// A runtime (kind, marks wanted) becomes f(integral_constant<int, K>, bool_constant<MARK>): the instantiations of the
+// pairs kernels that exist, in this one place. Only the kinds that produce R rows mark them.
+template <class F>
+inline void with_kind(uint32_t kind, bool marks, F&& f)
+{
+    using std::integral_constant;
+    if (marks && kind == (uint32_t)kLeft) f(integral_constant<int, kLeft>{}, std::true_type{});
+    else if (marks && kind == (uint32_t)kInner) f(integral_constant<int, kInner>{}, std::true_type{});
+    else if (kind == (uint32_t)kLeft) f(integral_constant<int, kLeft>{}, std::false_type{});
+    else if (kind == (uint32_t)kSemi) f(integral_constant<int, kSemi>{}, std::false_type{});
+    else if (kind == (uint32_t)kAnti) f(integral_constant<int, kAnti>{}, std::false_type{});
+    else f(integral_constant<int, kInner>{}, std::false_type{});
+}
+
+template <int NT>                 // threads of the workgroup
+struct PairStage {
+    uint32_t* s;                  // LDS [kStagePairs]: S rows of the staged pairs
+    uint32_t* r;                  // LDS [kStagePairs]: R rows (kinds above LEFT: unused)
+    uint32_t* wtot;               // LDS [2][NT / 64]: the wavefronts' row counts of a round (bit 31: a lane has more to walk)
+    unsigned long long* base;     // LDS: where the run being written starts in the output
+    uint32_t fill;                // pairs staged (the same value in every thread)
+    uint32_t round;
+    unsigned long long found;     // rows of this workgroup so far (the same value in every thread)
+    // kinds other than INNER, per lane: the inner matches of its elements, its elements without a match
+    unsigned long long inner;
+    uint32_t unmatched;
+};
+
+// Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
+// Out = PairsOutMarked (the MARK instantiations): every staged R row also sets its mark. Here, because the stage holds every
+// row the workgroup produced since its last flush whether the capacity lets it out or not (flush_plane cuts per element and
+// returns early behind the capacity; the marks must not), and because neighbouring lanes read neighbouring pairs.
+template <int K, int NT, class Out>
+__device__ __forceinline__ void stage_flush(PairStage<NT>& st, const Out& out)
+{
+    if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
+    __syncthreads();                                  // the base is there, and so is every pair of the rounds before
+    const uint64_t base = *st.base;
+    flush_plane<NT>(st.s, st.fill, out.s, base, out.capacity);
+    if constexpr (K <= kLeft) flush_plane<NT>(st.r, st.fill, out.r, base, out.capacity);
+    if constexpr (std::is_same_v<Out, PairsOutMarked>) mark_plane<NT>(st.r, st.fill, out.marks);
+    __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
+    st.fill = 0;
+}
+
+// One round: every lane brings m rows of its kind (more: it has further buckets to walk). Returns the rows of the round in
+// front of the lane's own; tot: the round's rows, anyMore: some lane of the workgroup has more. One barrier. The totals
+// are double-buffered by round parity: a wavefront writes round k + 2's only after the barrier of round k + 1, which
+// every wavefront reaches after reading round k's.
+template <int NT>
+__device__ __forceinline__ uint32_t stage_scan(PairStage<NT>& st, uint32_t m, bool more, bool& anyMore, uint32_t& tot)
+{
+    constexpr uint32_t kWaves = NT / kWave;
+    const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    uint32_t inc = m;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t below = __shfl_up(inc, off, kWave);
+        if (lane >= (uint32_t)off) inc += below;
+    }
+    const bool waveMore = __ballot(more) != 0ull;
+    uint32_t* const wt = st.wtot + (st.round & 1u) * kWaves;
+    if (lane == kWave - 1) wt[w] = inc | (waveMore ? 0x80000000u : 0u);
+    __syncthreads();
+    uint32_t wbase = 0, any = 0;
+    tot = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kWaves; ++k) {
+        const uint32_t v = wt[k], c = v & 0x7FFFFFFFu;
+        if (k < w) wbase += c;
+        tot += c;
+        any |= v >> 31;
+    }
+    st.round += 1;
+    anyMore = any != 0;
+    return wbase + inc - m;
+}
+
+// The stage takes a round of tot <= kStagePairs rows, flushed first when they do not fit (a second barrier). Returns the
+// fill before the round: the lane writes its rows from there + what stage_scan returned.
+template <int K, int NT, class Out>
+__device__ __forceinline__ uint32_t stage_place(PairStage<NT>& st, const Out& out, uint32_t tot)
+{
+    if (st.fill + tot > kStagePairs) stage_flush<K>(st, out);         // workgroup-uniform
+    const uint32_t before = st.fill;
+    st.fill += tot;
+    st.found += tot;
+    return before;
+}
+
+// stage_scan, then stage_place: the lane's position in the stage, for kernels whose rounds always fit an empty stage
+template <int K, int NT, class Out>
+__device__ __forceinline__ uint32_t stage_reserve(PairStage<NT>& st, const Out& out, uint32_t m, bool more, bool& anyMore)
+{
+    uint32_t tot;
+    const uint32_t before = stage_scan(st, m, more, anyMore, tot);
+    return stage_place<K>(st, out, tot) + before;
+}
+
+// The end of a pairs kernel: the last stage, then the workgroup's share of the counters. word: the counter of the INNER
+// matches (matches / prjMatches), which grows by them whatever the kind. INNER: the rows are the matches, found is the same
+// in every thread, one atomic per workgroup. Other kinds: the lanes' inner matches are summed instead, and LEFT also leaves
+// its unmatched elements in the word behind the cursor (hj_pairs_info; SEMI and ANTI derive theirs on the host).
+template <int K, int NT, class Out>
+__device__ __forceinline__ void stage_finish(PairStage<NT>& st, const Out& out, Counters* __restrict__ ctr,
+                                             unsigned long long Counters::Shard::* word)
+{
+    if (st.fill) stage_flush<K>(st, out);
+    if constexpr (K == kInner) {
+        if (threadIdx.x == 0 && st.found) atomicAdd(&(counter_shard(ctr)->*word), st.found);
+    } else {
+        const unsigned long long inner = wave_sum(st.inner);
+        if ((threadIdx.x & (kWave - 1)) == 0 && inner) atomicAdd(&(counter_shard(ctr)->*word), inner);
+        if constexpr (K == kLeft) {
+            const uint32_t unmatched = wave_sum(st.unmatched);
+            if ((threadIdx.x & (kWave - 1)) == 0 && unmatched) atomicAdd(out.cursor + 1, (unsigned long long)unmatched);
+        }
+    }
 }
 uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
 // the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot

@@ -37,7 +37,6 @@ namespace hj {
 
 namespace {
 
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;                              // HJ_NO_ROW
 constexpr uint32_t kGatherStepRows = kWave;                           // rows of one wavefront step: two validity words
 constexpr uint32_t kGatherLaneRows = 4;                               // rows in flight per lane, kGatherStepRows apart
 constexpr uint32_t kGatherWaveRows = kGatherStepRows * kGatherLaneRows;

@@ -24,7 +24,10 @@
 //
 // R-side match marks (HJ_FLAG_TRACK_R_MATCHES): `bool MARK` next to K on both kernels, instantiated for INNER and LEFT. A MARK
 // instantiation takes PairsOutMarked where the others take PairsOut, and stage_flush also sets the bit of every staged R
-// row (mark_plane, hj_device.h). The instantiations without marks are untouched: same arguments, same code.
+// row (mark_plane, hj_device.h).
+//
+// The stage itself (PairStage, stage_reserve, stage_flush, stage_finish), the kinds' constants and the dispatch over
+// (kind, marks) are in hj_device.h: k_prj_join_pairs (hj_prj_pairs.hip) stages its rows through the same code.
 //
 // All integer work, bound by HBM and the table gather; no MFMA.
 
@@ -34,101 +37,11 @@ namespace hj {
 
 namespace {
 
-constexpr uint32_t kStagePairs = 4096;          // pairs per stage: 2 planes x 16 KiB of LDS, four workgroups per CU
 constexpr uint32_t kWaves = kBlock / kWave;
 // A round must fit an empty stage (asserted where the rounds are shaped): 1024 S tuples x 4 slots at probeLength 4,
 // 512 x kMaxProbeLen at any other length, 1024 buckets x 3 tuples for htm
 constexpr uint32_t kMaxProbeLen = 8;
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;        // HJ_NO_ROW: the R row of a LEFT row without a match
-// hj_join_kind; kinds above LEFT write S rows only
-constexpr int kInner = 0, kLeft = 1, kSemi = 2, kAnti = 3;
-
-struct Stage {
-    uint32_t* s;                  // LDS: S rows of the staged pairs
-    uint32_t* r;                  // LDS: R rows
-    uint32_t* wtot;               // LDS [2][kWaves]: the wavefronts' pair counts of a round (bit 31: a lane has more to walk)
-    unsigned long long* base;     // LDS: where the run being flushed starts in the output
-    uint32_t fill;                // pairs staged (the same value in every thread)
-    uint32_t round;
-    unsigned long long found;     // pairs of this workgroup so far (the same value in every thread)
-    // kinds other than INNER, per lane: the inner matches of its elements, its elements without a match
-    unsigned long long inner;
-    uint32_t unmatched;
-};
-
-// Claims the output run of everything staged and writes it. Called by all threads of the workgroup together.
-// Out = PairsOutMarked (the MARK instantiations): every staged R row also sets its mark. Here, because the stage holds every
-// row the workgroup produced since its last flush whether the capacity lets it out or not (flush_plane cuts per element and
-// returns early behind the capacity; the marks must not), and because neighbouring lanes read neighbouring pairs.
-template <int K, class Out>
-__device__ __forceinline__ void stage_flush(Stage& st, const Out& out)
-{
-    if (threadIdx.x == 0) *st.base = atomicAdd(out.cursor, (unsigned long long)st.fill);
-    __syncthreads();                                  // the base is there, and so is every pair of the rounds before
-    const uint64_t base = *st.base;
-    flush_plane<kBlock>(st.s, st.fill, out.s, base, out.capacity);
-    if constexpr (K <= kLeft) flush_plane<kBlock>(st.r, st.fill, out.r, base, out.capacity);
-    if constexpr (std::is_same_v<Out, PairsOutMarked>) mark_plane<kBlock>(st.r, st.fill, out.marks);
-    __syncthreads();                                  // nobody refills the stage (or claims again) while it is being read
-    st.fill = 0;
-}
-
-// One round: every lane brings m pairs -- rows of the kind K -- (more: it has further buckets to walk). Returns the lane's position in the
-// stage; the lane then writes its m pairs there. anyMore: some lane of the workgroup has more. One barrier, two when the
-// stage is flushed first. The totals are double-buffered by round parity: a wavefront writes round k + 2's only after the
-// barrier of round k + 1, which every wavefront reaches after reading round k's.
-template <int K, class Out>
-__device__ __forceinline__ uint32_t stage_reserve(Stage& st, const Out& out, uint32_t m, bool more, bool& anyMore)
-{
-    const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    uint32_t inc = m;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const uint32_t below = __shfl_up(inc, off, kWave);
-        if (lane >= (uint32_t)off) inc += below;
-    }
-    const bool waveMore = __ballot(more) != 0ull;
-    uint32_t* const wt = st.wtot + (st.round & 1u) * kWaves;
-    if (lane == kWave - 1) wt[w] = inc | (waveMore ? 0x80000000u : 0u);
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0, any = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kWaves; ++k) {
-        const uint32_t v = wt[k], c = v & 0x7FFFFFFFu;
-        if (k < w) wbase += c;
-        tot += c;
-        any |= v >> 31;
-    }
-    st.round += 1;
-    anyMore = any != 0;
-    if (st.fill + tot > kStagePairs) stage_flush<K>(st, out);         // workgroup-uniform
-    const uint32_t pos = st.fill + wbase + inc - m;
-    st.fill += tot;
-    st.found += tot;
-    return pos;
-}
-
-// the end of both kernels: the last stage, then the workgroup's share of the counters (one atomic per workgroup and
-// counter: found is the same in every thread; the foreign counts are per lane)
-// Kinds other than INNER: the rows are not the matches, so the lanes' inner matches are summed instead; LEFT also leaves
-// its unmatched elements in the word behind the cursor (hj_pairs_info; SEMI and ANTI derive theirs on the host)
-template <int K, class Out>
-__device__ __forceinline__ void stage_finish(Stage& st, const Out& out, uint32_t foreign, Counters* __restrict__ ctr)
-{
-    if (st.fill) stage_flush<K>(st, out);
-    if constexpr (K == kInner) {
-        if (threadIdx.x == 0 && st.found) atomicAdd(&counter_shard(ctr)->matches, st.found);
-    } else {
-        const unsigned long long inner = wave_sum(st.inner);
-        if ((threadIdx.x & (kWave - 1)) == 0 && inner) atomicAdd(&counter_shard(ctr)->matches, inner);
-        if constexpr (K == kLeft) {
-            const uint32_t unmatched = wave_sum(st.unmatched);
-            if ((threadIdx.x & (kWave - 1)) == 0 && unmatched) atomicAdd(out.cursor + 1, (unsigned long long)unmatched);
-        }
-    }
-    foreign = wave_sum(foreign);
-    if ((threadIdx.x & (kWave - 1)) == 0 && foreign) atomicAdd(&counter_shard(ctr)->foreign, (unsigned long long)foreign);
-}
+using Stage = PairStage<kBlock>;
 
 // ---------------------------------------------------------------------------
 // the S read of both kernels
@@ -160,6 +73,47 @@ __device__ __forceinline__ void load_vecs(const SBody& b, uint64_t v0, u4 (&t)[V
         const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
         t[k].x = 0u; t[k].y = ~0u; t[k].z = 0u; t[k].w = ~0u;            // two times "no element"
         if (v < b.nv) t[k] = __builtin_nontemporal_load(b.S4 + v);
+    }
+}
+
+// The S rounds of a workgroup: V vectors (2 V elements) per lane and round by grid stride, then the element before and
+// after the aligned body in one round of two elements for thread 0 of workgroup 0. round(sk, row, valid) takes a round's
+// elements (E = 2 V or 2, the arrays' length); key(k) sees the key word of every element that exists (the foreign-tuple
+// count of k_probe_pairs). Every thread of the workgroup runs the same number of rounds (they meet at barriers).
+template <int V, class Key, class Round>
+__device__ __forceinline__ void for_s_rounds(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase, Key&& key, Round&& round)
+{
+    const SBody b = s_body(S, n);
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock * V;
+    uint64_t v0 = (uint64_t)blockIdx.x * kBlock * V;
+    u4 cur[V];
+    load_vecs<V>(b, v0, cur);
+    for (; v0 < b.nv; v0 += stride) {
+        u4 nxt[V];
+        load_vecs<V>(b, v0 + stride, nxt);
+        uint64_t sk[2 * V], row[2 * V];
+        bool valid[2 * V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
+            sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
+            row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
+            valid[2 * k] = valid[2 * k + 1] = v < b.nv;
+            if (v < b.nv) { key(cur[k].x); key(cur[k].z); }
+        }
+        round(sk, row, valid);
+#pragma unroll
+        for (int k = 0; k < V; ++k) cur[k] = nxt[k];
+    }
+    if (blockIdx.x == 0 && (b.head || b.tail < n)) {
+        uint64_t sk[2] = {kNoElement, kNoElement};
+        const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
+        const bool valid[2] = {threadIdx.x == 0 && b.head != 0, threadIdx.x == 0 && b.tail < n};     // 255 threads bring nothing
+        if (threadIdx.x == 0) {
+            if (b.head) { sk[0] = S[0]; key((uint32_t)sk[0]); }
+            if (b.tail < n) { sk[1] = S[b.tail]; key((uint32_t)sk[1]); }
+        }
+        round(sk, row, valid);
     }
 }
 
@@ -224,7 +178,7 @@ struct OaTable { const uint64_t* table; uint64_t mask; uint32_t hshift, probeLen
 // E elements per lane: walk them all, agree on the round's pair count, write the pairs into the stage
 // Rows per element: INNER popc(mask); LEFT max(popc(mask), 1), SEMI mask != 0, ANTI mask == 0 -- the latter three for a
 // valid lane only (a lane without an element has mask 0 and is no unmatched row)
-template <int K, int E, bool FOUR, class Out>
+template <int K, bool FOUR, int E, class Out>
 __device__ __forceinline__ void oa_round(Stage& st, const Out& out, const OaTable& T, const uint64_t (&sk)[E], const uint64_t (&row)[E],
                                          const bool (&valid)[E])
 {
@@ -255,41 +209,12 @@ __device__ __forceinline__ void probe_pairs_body(Stage& st, const uint64_t* __re
                                                  const ShardCheck& sc, const Out& out, Counters* __restrict__ ctr)
 {
     static_assert(2 * V * kBlock * (FOUR ? 4 : kMaxProbeLen) <= kStagePairs, "a round must fit an empty stage");
-    const SBody b = s_body(S, n);
     uint32_t foreign = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock * V;
-    uint64_t v0 = (uint64_t)blockIdx.x * kBlock * V;
-    u4 cur[V];
-    load_vecs<V>(b, v0, cur);
-    // every thread of the workgroup runs the same number of rounds (they meet at barriers)
-    for (; v0 < b.nv; v0 += stride) {
-        u4 nxt[V];
-        load_vecs<V>(b, v0 + stride, nxt);
-        uint64_t sk[2 * V], row[2 * V];
-        bool valid[2 * V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
-            sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
-            row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
-            valid[2 * k] = valid[2 * k + 1] = v < b.nv;
-            if (v < b.nv) foreign += (uint32_t)is_foreign(cur[k].x, sc) + (uint32_t)is_foreign(cur[k].z, sc);
-        }
-        oa_round<K, 2 * V, FOUR>(st, out, T, sk, row, valid);
-#pragma unroll
-        for (int k = 0; k < V; ++k) cur[k] = nxt[k];
-    }
-    if (blockIdx.x == 0 && (b.head || b.tail < n)) {
-        uint64_t sk[2] = {kNoElement, kNoElement};
-        const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
-        const bool valid[2] = {threadIdx.x == 0 && b.head != 0, threadIdx.x == 0 && b.tail < n};     // 255 threads bring nothing
-        if (threadIdx.x == 0) {
-            if (b.head) { sk[0] = S[0]; foreign += is_foreign((uint32_t)sk[0], sc); }
-            if (b.tail < n) { sk[1] = S[b.tail]; foreign += is_foreign((uint32_t)sk[1], sc); }
-        }
-        oa_round<K, 2, FOUR>(st, out, T, sk, row, valid);
-    }
-    stage_finish<K>(st, out, foreign, ctr);
+    for_s_rounds<V>(S, n, sIdxBase, [&](uint32_t key) { foreign += (uint32_t)is_foreign(key, sc); },
+                    [&](const auto& sk, const auto& row, const auto& valid) { oa_round<K, FOUR>(st, out, T, sk, row, valid); });
+    stage_finish<K>(st, out, ctr, &Counters::Shard::matches);
+    foreign = wave_sum(foreign);
+    if ((threadIdx.x & (kWave - 1)) == 0 && foreign) atomicAdd(&counter_shard(ctr)->foreign, (unsigned long long)foreign);
 }
 
 }  // namespace
@@ -419,38 +344,9 @@ k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase,
     Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
     // buckets outside the slots the build defined were never written and hold no tuple (hj_device.h, Counters)
     const HtmTable T{table, overflow, bucketMask, ctr->validLo, ctr->validHiEx + 512};
-    const SBody b = s_body(S, n);
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock * V;
-    uint64_t v0 = (uint64_t)blockIdx.x * kBlock * V;
-    u4 cur[V];
-    load_vecs<V>(b, v0, cur);
-    for (; v0 < b.nv; v0 += stride) {
-        u4 nxt[V];
-        load_vecs<V>(b, v0 + stride, nxt);
-        uint64_t sk[2 * V], row[2 * V];
-        bool valid[2 * V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const uint64_t v = v0 + (uint64_t)k * kBlock + threadIdx.x;
-            sk[2 * k] = ((uint64_t)cur[k].y << 32) | cur[k].x; sk[2 * k + 1] = ((uint64_t)cur[k].w << 32) | cur[k].z;
-            row[2 * k] = sIdxBase + b.head + 2 * v; row[2 * k + 1] = row[2 * k] + 1;
-            valid[2 * k] = valid[2 * k + 1] = v < b.nv;
-        }
-        htm_rounds<K, 2 * V>(st, out, T, sk, row, valid);
-#pragma unroll
-        for (int k = 0; k < V; ++k) cur[k] = nxt[k];
-    }
-    if (blockIdx.x == 0 && (b.head || b.tail < n)) {
-        uint64_t sk[2] = {kNoElement, kNoElement};
-        const uint64_t row[2] = {sIdxBase, sIdxBase + b.tail};
-        const bool valid[2] = {threadIdx.x == 0 && b.head != 0, threadIdx.x == 0 && b.tail < n};
-        if (threadIdx.x == 0) {
-            if (b.head) sk[0] = S[0];
-            if (b.tail < n) sk[1] = S[b.tail];
-        }
-        htm_rounds<K, 2>(st, out, T, sk, row, valid);
-    }
-    stage_finish<K>(st, out, 0u, ctr);
+    for_s_rounds<V>(S, n, sIdxBase, [](uint32_t) {},
+                    [&](const auto& sk, const auto& row, const auto& valid) { htm_rounds<K>(st, out, T, sk, row, valid); });
+    stage_finish<K>(st, out, ctr, &Counters::Shard::matches);
 }
 
 namespace {
@@ -473,32 +369,20 @@ void launch_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t s
                         uint32_t probeLen, ShardCheck sc, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks)
 {
     const dim3 grid(pairs_grid(n, nCU, probeLen == 4 ? 2 : 1));
-    if (marks && kind <= (uint32_t)kLeft) {
-        PairsOutMarked om;
-        static_cast<PairsOut&>(om) = out; om.marks = *marks;
-        const auto kernel = kind == kLeft ? k_probe_pairs<kLeft, true> : k_probe_pairs<kInner, true>;
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift, probeLen, sc, om, ctr);
-        return;
-    }
-    const auto kernel = kind == kLeft ? k_probe_pairs<kLeft, false> : kind == kSemi ? k_probe_pairs<kSemi, false>
-                      : kind == kAnti ? k_probe_pairs<kAnti, false> : k_probe_pairs<kInner, false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, tableSize - 1, hshift, probeLen, sc, out, ctr);
+    with_kind(kind, marks != nullptr, [&](auto k, auto mark) {
+        hipLaunchKernelGGL((k_probe_pairs<decltype(k)::value, decltype(mark)::value>), grid, dim3(kBlock), 0, s, S, n, sIdxBase, table,
+                           tableSize - 1, hshift, probeLen, sc, pairs_out_of<decltype(mark)::value>(out, marks), ctr);
+    });
 }
 
 void launch_htm_probe_pairs(uint32_t kind, const uint64_t* S, uint64_t n, uint64_t sIdxBase, const uint64_t* table, uint32_t numBuckets,
                             const uint64_t* overflow, PairsOut out, int nCU, Counters* ctr, hipStream_t s, const RMarks* marks)
 {
     const dim3 grid(pairs_grid(n, nCU, kHtmVecs));
-    if (marks && kind <= (uint32_t)kLeft) {
-        PairsOutMarked om;
-        static_cast<PairsOut&>(om) = out; om.marks = *marks;
-        const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft, true> : k_htm_probe_pairs<kInner, true>;
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1, overflow, om, ctr);
-        return;
-    }
-    const auto kernel = kind == kLeft ? k_htm_probe_pairs<kLeft, false> : kind == kSemi ? k_htm_probe_pairs<kSemi, false>
-                      : kind == kAnti ? k_htm_probe_pairs<kAnti, false> : k_htm_probe_pairs<kInner, false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, S, n, sIdxBase, table, numBuckets - 1, overflow, out, ctr);
+    with_kind(kind, marks != nullptr, [&](auto k, auto mark) {
+        hipLaunchKernelGGL((k_htm_probe_pairs<decltype(k)::value, decltype(mark)::value>), grid, dim3(kBlock), 0, s, S, n, sIdxBase, table,
+                           numBuckets - 1, overflow, pairs_out_of<decltype(mark)::value>(out, marks), ctr);
+    });
 }
 
 }  // namespace hj

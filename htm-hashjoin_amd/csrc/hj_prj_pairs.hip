@@ -13,8 +13,8 @@
 //                      (key >> radixBits, R row) entries, duplicates of a key as separate entries; a probe walks its run to the
 //                      first empty slot and emits one (S row, R row) pair per equal entry
 //
-// Pair output as in hj_pairs.hip (flush_plane, hj_device.h): pairs are staged in LDS, a full stage claims its run of the two output planes with ONE
-// 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
+// Pair output through the stage of hj_pairs.hip (PairStage, hj_device.h): pairs are staged in LDS, a full stage claims its run of the two output
+// planes with ONE 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
 // LDS: table 15360 slots x (4 B key + 4 B row) = 120 KiB, stage 4096 pairs x 8 B = 32 KiB, 152 KiB of the CU's 160.
 //
 // Join kinds (hj_prj_probe_join_dev): the kind K is a template parameter of k_prj_join_pairs; K = INNER is the kernel as it
@@ -29,16 +29,12 @@ namespace hj {
 
 constexpr uint32_t kPairSlots = 15360;            // table slots: a key plane and a row plane of 60 KiB each
 constexpr uint32_t kPairBlockTuples = 11520;      // R tuples per LDS build (load <= 0.75)
-constexpr uint32_t kPairStage = 4096;             // pairs per stage, as in hj_pairs.hip
 constexpr int kPairElems = 2;                     // S elements per thread and round: on unique R keys a round fits half a stage
-constexpr uint32_t kPairWaves = kJoinThreads / 64;
-constexpr size_t kPairLdsBytes = sizeof(uint32_t) * (2 * kPairSlots + 2 * kPairStage);
+constexpr size_t kPairLdsBytes = sizeof(uint32_t) * (2 * kPairSlots + 2 * kStagePairs);
 static_assert(kPairLdsBytes + 1024 <= 160 * 1024, "table, stage and the few static words must fit one CU's LDS");
 static_assert(kPairBlockTuples * 4 <= kPairSlots * 3, "a probe's walk ends at an empty slot: the table is never full");
-static_assert((uint32_t)kPairElems * kJoinThreads <= kPairStage, "a round of single matches fits an empty stage");
+static_assert((uint32_t)kPairElems * kJoinThreads <= kStagePairs, "a round of single matches fits an empty stage");
 static_assert(kPrjItemS / kJoinThreads <= 64, "the matched flags of a thread's S elements of one item fit one 64-bit register");
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;          // HJ_NO_ROW
-constexpr int kInner = 0, kLeft = 1, kSemi = 2, kAnti = 3;          // hj_join_kind
 
 // Slot of key-remainder k: the Fibonacci hash of join_hash, scaled to a slot count that is no power of two
 __device__ __forceinline__ uint32_t pair_hash(uint32_t k) { return __umulhi(k * 0x9E3779B1u, kPairSlots); }
@@ -63,53 +59,30 @@ k_prj_rows_checksum(const uint2* __restrict__ partR, const uint32_t* __restrict_
 // items[0 .. *nItemsAt) taken through *ticket (zeroed by the host), as in k_prj_probe_items; both relations in the exact
 // layout: partition pid = part[off[pid] .. off[pid + 1]), elements {x = key, y = row}. The arrays are separate __restrict__
 // parameters (k_prj_join: members of a struct became vector loads), and what an item reads is looked up before its LDS work.
-// K: hj_join_kind. cursor[1]: LEFT's unmatched S elements.
-// MARK (INNER and LEFT only): the last argument also carries the R-side match marks (RMarks, hj_device.h; base 0: an R row
-// is its position in the relation given to the build). Every produced R row sets its bit in one of two places: where the
-// staged R plane is read at a flush (whatever the capacity lets out), and in the `put` of the direct-write round, which
-// bypasses the stage. The last argument of an instantiation without marks is the counters' pointer, as it always was.
-struct CtrMarks { Counters* ctr; RMarks marks; };
-template <bool MARK> using PairsTail = std::conditional_t<MARK, CtrMarks, Counters* __restrict__>;
-__device__ __forceinline__ Counters* ctr_of(Counters* c) { return c; }
-__device__ __forceinline__ Counters* ctr_of(const CtrMarks& t) { return t.ctr; }
-
+// K: hj_join_kind. out.cursor[1]: LEFT's unmatched S elements.
+// MARK (INNER and LEFT only): `out` also carries the R-side match marks (RMarks, hj_device.h; base 0: an R row is its
+// position in the relation given to the build). Every produced R row sets its bit in one of two places: where the staged
+// R plane is read at a flush (stage_flush, whatever the capacity lets out), and in the `put` of the direct-write round,
+// which bypasses the stage.
 template <int K, bool MARK>
 __global__ void __launch_bounds__(kJoinThreads)
 k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ offR,
                  const uint2* __restrict__ partS, const uint32_t* __restrict__ offS,
                  const uint2* __restrict__ items, const uint32_t* __restrict__ nItemsAt, unsigned long long* __restrict__ ticket,
-                 uint32_t radixBits, uint32_t* __restrict__ outS, uint32_t* __restrict__ outR, uint64_t capacity,
-                 unsigned long long* __restrict__ cursor, PairsTail<MARK> tail)
+                 uint32_t radixBits, PairsOutOf<MARK> out, Counters* __restrict__ ctr)
 {
     static_assert(!MARK || K <= kLeft, "only the kinds that produce R rows mark them");
     extern __shared__ uint32_t pairLds[];
     uint32_t* const tabK = pairLds;                    // key remainders, kEmpty32 = free
     uint32_t* const tabR = tabK + kPairSlots;          // the R row of the slot's entry
-    uint32_t* const stS = tabR + kPairSlots;           // the stage: S rows, R rows
-    uint32_t* const stR = stS + kPairStage;
-    __shared__ uint32_t wtot[2 * kPairWaves];          // the wavefronts' pair counts of a round, double-buffered by round parity
-    __shared__ unsigned long long sBase;               // where the run being written starts in the output
+    __shared__ uint32_t wtot[2 * (kJoinThreads / kWave)];      // the stage's words (PairStage::wtot, base)
+    __shared__ unsigned long long sBase;
     __shared__ uint32_t sNext;
+    // the stage behind the table: S rows, R rows
+    PairStage<kJoinThreads> st{tabR + kPairSlots, tabR + kPairSlots + kStagePairs, wtot, &sBase, 0u, 0u, 0ull, 0ull, 0u};
 
     const uint32_t nItems = *nItemsAt;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t fill = 0, round = 0;                      // the same in every thread
-    unsigned long long found = 0;                      // pairs of this workgroup (the same in every thread)
     constexpr bool kRless = K == kLeft || K == kAnti;  // items of partitions without R tuples are in the list
-    unsigned long long inner = 0;                      // kinds other than INNER, per thread: inner matches of its elements
-    uint32_t unmatched = 0;                            // LEFT, per thread: its elements without a match
-
-    // everything staged -> its run of the output. Called by all threads together.
-    auto flush = [&]() {
-        if (threadIdx.x == 0) sBase = atomicAdd(cursor, (unsigned long long)fill);
-        __syncthreads();                               // the base is there, and so is every pair of the rounds before
-        const uint64_t base = sBase;
-        flush_plane<kJoinThreads>(stS, fill, outS, base, capacity);
-        if constexpr (K <= kLeft) flush_plane<kJoinThreads>(stR, fill, outR, base, capacity);
-        if constexpr (MARK) mark_plane<kJoinThreads>(stR, fill, tail.marks);
-        __syncthreads();                               // nobody refills the stage (or claims again) while it is being read
-        fill = 0;
-    };
     // the matches of one S element: their number, the R row of the first
     auto walk = [&](uint32_t key, bool ok, uint32_t& first) {
         uint32_t m = 0;
@@ -202,94 +175,63 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
                         // the element's flag; a padding lane (a clamped copy of the last element) writes no row of any kind
                         const unsigned long long bit = 1ull << (j0 / kJoinThreads + (uint32_t)u);
                         const bool none = valid && last && m[u] == 0 && !(seen & bit);
-                        inner += m[u];
-                        if constexpr (K == kLeft) { rows[u] = m[u] + (uint32_t)none; unmatched += (uint32_t)none; }
+                        st.inner += m[u];
+                        if constexpr (K == kLeft) { rows[u] = m[u] + (uint32_t)none; st.unmatched += (uint32_t)none; }
                         if constexpr (K == kSemi) rows[u] = (uint32_t)(m[u] != 0 && !(seen & bit));
                         if constexpr (K == kAnti) rows[u] = (uint32_t)none;
                         if (m[u]) seen |= bit;
                     }
                     mine += rows[u];
                 }
-                // the round's pair count: wavefront scan, the totals exchanged through LDS, one barrier
-                uint32_t inc = mine;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t below = __shfl_up(inc, off, 64);
-                    if (lane >= (uint32_t)off) inc += below;
-                }
-                uint32_t* const wt = wtot + (round & 1u) * kPairWaves;
-                if (lane == 63) wt[wave] = inc;
-                __syncthreads();
-                uint32_t wbase = 0, tot = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < kPairWaves; ++w) {
-                    const uint32_t c = wt[w];
-                    if (w < wave) wbase += c;
-                    tot += c;
-                }
-                round += 1;
-                const uint32_t before = wbase + inc - mine;            // rows of the round in front of this lane's (the kind's rows)
-                if (tot > kPairStage) {
+                bool any;
+                uint32_t tot;
+                const uint32_t before = stage_scan(st, mine, false, any, tot);     // rows of the round in front of this lane's
+                if (tot > kStagePairs) {
                     // Duplicate keys on both sides: more pairs than a stage holds (one S tuple alone can match a whole
                     // table). The round claims its run itself and every lane writes its pairs straight to the planes.
-                    if (fill) flush();
-                    if (threadIdx.x == 0) sBase = atomicAdd(cursor, (unsigned long long)tot);
+                    if (st.fill) stage_flush<K>(st, out);
+                    if (threadIdx.x == 0) sBase = atomicAdd(out.cursor, (unsigned long long)tot);
                     __syncthreads();
                     // (sBase is written again only behind the next round's barrier)
                     uint64_t g = sBase + before;
                     auto put = [&](uint32_t s, uint32_t r) {
-                        if (g < capacity) {
-                            outS[g] = s;
-                            if constexpr (K <= kLeft) outR[g] = r;
+                        if (g < out.capacity) {
+                            out.s[g] = s;
+                            if constexpr (K <= kLeft) out.r[g] = r;
                         }
-                        if constexpr (MARK) mark_r_row(tail.marks, r);     // written or not
+                        if constexpr (MARK) mark_r_row(out.marks, r);      // written or not
                         ++g;
                     };
 #pragma unroll
                     for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], rows[u], put);
+                    st.found += tot;
                 } else {
-                    if (fill + tot > kPairStage) flush();              // workgroup-uniform
-                    uint32_t pos = fill + before;
+                    uint32_t pos = stage_place<K>(st, out, tot) + before;
                     auto put = [&](uint32_t s, uint32_t r) {
-                        stS[pos] = s;
-                        if constexpr (K <= kLeft) stR[pos] = r;
+                        st.s[pos] = s;
+                        if constexpr (K <= kLeft) st.r[pos] = r;
                         ++pos;
                     };
 #pragma unroll
                     for (int u = 0; u < kPairElems; ++u) emit(e[u], m[u], first[u], rows[u], put);
-                    fill += tot;
                 }
-                found += tot;
             }
             __syncthreads();                                           // the table is read no more
         }
     }
-    if (fill) flush();
-    if constexpr (K == kInner) {
-        if (threadIdx.x == 0 && found) atomicAdd(&counter_shard(ctr_of(tail))->prjMatches, found);
-    } else {
-        // the rows are not the matches: the counter takes the inner matches, LEFT's unmatched elements go behind the cursor
-        unsigned long long un = unmatched;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            inner += __shfl_down(inner, off, 64);
-            un += __shfl_down(un, off, 64);
-        }
-        if (lane == 0 && inner) atomicAdd(&counter_shard(ctr_of(tail))->prjMatches, inner);
-        if (K == kLeft && lane == 0 && un) atomicAdd(cursor + 1, un);
-    }
+    stage_finish<K>(st, out, ctr, &Counters::Shard::prjMatches);
 }
 
 static hipError_t prj_pairs_set_attributes()
 {
-    const void* const kernels[6] = {reinterpret_cast<const void*>(k_prj_join_pairs<kInner, false>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft, false>),
-                                    reinterpret_cast<const void*>(k_prj_join_pairs<kSemi, false>), reinterpret_cast<const void*>(k_prj_join_pairs<kAnti, false>),
-                                    reinterpret_cast<const void*>(k_prj_join_pairs<kInner, true>), reinterpret_cast<const void*>(k_prj_join_pairs<kLeft, true>)};
-    for (const void* k : kernels) {
-        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    for (uint32_t kind = 0; kind <= (uint32_t)kAnti; ++kind)
+        for (const bool marks : {false, true})          // (a kind that marks nothing comes by twice)
+            with_kind(kind, marks, [&](auto k, auto mark) {
+                const auto kernel = k_prj_join_pairs<decltype(k)::value, decltype(mark)::value>;
+                if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes);
+            });
+    return e;
 }
 
 // R's row-id passes into buf.partR / res.offR (plan: exact passes only), then R's checksum
@@ -327,19 +269,11 @@ hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjP
     const bool rless = kind == (uint32_t)kLeft || kind == (uint32_t)kAnti;
     if ((e = enqueue_prj_items(res, res.offR, nullptr, 0u, w.offS, nullptr, 0u, P, ctr, s, rless)) != hipSuccess) return e;
     if (evJoin0 && (e = hipEventRecord(evJoin0, s)) != hipSuccess) return e;
-    if (marks && kind <= (uint32_t)kLeft) {
-        const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft, true> : k_prj_join_pairs<kInner, true>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
+    with_kind(kind, marks != nullptr, [&](auto k, auto mark) {
+        hipLaunchKernelGGL((k_prj_join_pairs<decltype(k)::value, decltype(mark)::value>), dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
                            reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
-                           res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor,
-                           CtrMarks{ctr, *marks});
-        return hipGetLastError();
-    }
-    const auto kernel = kind == (uint32_t)kLeft ? k_prj_join_pairs<kLeft, false> : kind == (uint32_t)kSemi ? k_prj_join_pairs<kSemi, false>
-                      : kind == (uint32_t)kAnti ? k_prj_join_pairs<kAnti, false> : k_prj_join_pairs<kInner, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nCU), dim3(kJoinThreads), kPairLdsBytes, s,
-                       reinterpret_cast<const uint2*>(buf.partR), res.offR, reinterpret_cast<const uint2*>(buf.partS), w.offS,
-                       res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, out.s, out.r, out.capacity, out.cursor, ctr);
+                           res.items, res.itemCnt + 2ull * P, res.stats, planR.radixBits, pairs_out_of<decltype(mark)::value>(out, marks), ctr);
+    });
     return hipGetLastError();
 }
 

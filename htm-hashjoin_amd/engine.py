@@ -466,6 +466,115 @@ def _join_without_device(kind, n_r, n_s):
     return s_idx, (np.full(keeps, NO_ROW, dtype=np.uint32) if kind <= _lib.HJ_JOIN_LEFT else None)
 
 
+class _Held:
+    """device allocations of one wrapper call: alloc / free as it goes, close frees what is left"""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptrs = ctx, []
+
+    def alloc(self, nbytes):
+        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 4)))
+        return self.ptrs[-1]
+
+    def put(self, a):
+        d = self.alloc(a.nbytes)
+        if a.nbytes:
+            self.ctx.copy_h2d(d, a)
+        return d
+
+    def free(self, *ptrs):
+        for p in ptrs:
+            self.ptrs.remove(p)
+            self.ctx.dev_free(p)
+
+    def close(self):
+        for p in self.ptrs:
+            self.ctx.dev_free(p)
+        self.ptrs = []
+
+
+def _fetch_map(ctx, d_map, n):
+    idx = np.empty(n, dtype=np.uint32)
+    if n:
+        ctx.copy_d2h(idx, d_map)
+    return idx
+
+
+
+def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLength=4, radixBits=0):
+    """The host sequence of every materialising wrapper, once: reserve, upload R, build, then relS in slices of `step`
+    tuples -- upload, probe, hand the slice's maps to on_maps -- then the counters and the sweep of the R marks.
+    path: "htm" | "atomic" | "nocc", the table probes (step = len(relS): all of S in one call from row 0; the fetch at
+    the end raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do), or "radix", the
+    resident radix join on the key word.
+    kind: the hj_join_kind of the probes; None: mark-only passes (INNER, capacity 0, NULL planes).
+    which: HJ_R_UNMATCHED / HJ_R_MATCHED, the R rows swept after the probes (the context tracks R's matches), or None.
+    Sizing: the planes start with `step` entries each (exact for a foreign-key join); a slice whose probe reports more
+    rows gets planes of the reported count and is probed once more.
+    on_maps(ctx, held, lo, n_s, d_s, d_r, rows): the device maps of the `rows` rows of the slice relS[lo:lo + n_s] (d_r
+    is 0 for a kind without an R plane); after the probes once more with lo None and d_s 0, d_r being the sweep's map.
+    The maps are valid until on_maps returns; what it allocates from `held` and does not free lives to the end."""
+    radix = path == "radix"
+    plane_r = kind is not None and kind <= _lib.HJ_JOIN_LEFT
+    with HashJoinContext(device) as ctx:
+        held = _Held(ctx)
+        try:
+            ctx.reserve("prj" if radix else path, relR.size, step, probeLength=probeLength, radixBits=radixBits,
+                        keepRowIds=True, trackRMatches=which is not None)
+            dR = held.put(relR)
+            if radix:
+                ctx.prj_build(dR, relR.size)
+            else:
+                ctx.build(dR, relR.size)
+            probe = ctx.prj_probe_pairs if radix else ctx.probe_pairs
+            dS = held.alloc(8 * step)
+            capacity = step if kind is not None else 0
+            d_s, d_r = (held.alloc(4 * capacity), held.alloc(4 * capacity) if plane_r else 0) if capacity else (0, 0)
+            for lo in range(0, relS.size, step):
+                part = relS[lo:lo + step]
+                ctx.copy_h2d(dS, part)
+                probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
+                if kind is None:
+                    continue
+                found, written = ctx.pairs_info()[:2]
+                if found > capacity:
+                    held.free(*(p for p in (d_s, d_r) if p))
+                    capacity = found
+                    d_s, d_r = held.alloc(4 * capacity), (held.alloc(4 * capacity) if plane_r else 0)
+                    probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
+                    found, written = ctx.pairs_info()[:2]
+                on_maps(ctx, held, lo, part.size, d_s, d_r, written)
+            if not radix:
+                ctx.fetch()
+            if which is not None:
+                d_rows = held.alloc(4 * relR.size)
+                ctx.r_rows(which, d_rows, relR.size)
+                on_maps(ctx, held, None, 0, 0, d_rows, ctx.r_rows_info()[1])
+        finally:
+            held.close()
+
+
+def _join_maps(relR, relS, path, kind, which, step, device, **kw):
+    """_drive_join with every map copied to the host: ([S maps], [R maps]), one per slice, the sweep's map the last of R's"""
+    s_parts, r_parts = [], []
+
+    def to_host(ctx, held, lo, n_s, d_s, d_r, rows):
+        if d_s:
+            s_parts.append(_fetch_map(ctx, d_s, rows))
+        if d_r:
+            r_parts.append(_fetch_map(ctx, d_r, rows))
+
+    _drive_join(relR, relS, path, kind, which, step, to_host, device, **kw)
+    return s_parts, r_parts
+
+
+def _slice_step(fn, n_s, slice_tuples):
+    step = n_s if not slice_tuples else min(int(slice_tuples), n_s)
+    if step < 1:
+        raise ValueError(f"{fn}: slice_tuples must be positive, not {slice_tuples!r}")
+    return step
+
+
 def join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="inner"):
     """The join as two gather maps: (s_idx, r_idx), numpy uint32 arrays of equal length, row k of the result being
     (relS[s_idx[k]], relR[r_idx[k]]). The order of the rows is unspecified. algo = "htm" (the default): the complete
@@ -484,38 +593,8 @@ def join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="inner"):
     trivial = _join_without_device(kind, relR.size, relS.size)
     if trivial is not None:
         return trivial
-    plane_r = kind <= _lib.HJ_JOIN_LEFT
-    with HashJoinContext(device) as ctx:
-        held = []
-
-        def alloc(nbytes):
-            held.append(ctx.dev_alloc(nbytes))
-            return held[-1]
-
-        try:
-            ctx.reserve(algo, relR.size, relS.size, probeLength=probeLength, keepRowIds=True)
-            dR, dS = alloc(relR.nbytes), alloc(relS.nbytes)
-            ctx.copy_h2d(dR, relR)
-            ctx.copy_h2d(dS, relS)
-            ctx.build(dR, relR.size)
-            capacity = relS.size
-            while True:
-                d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
-                ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity, kind=kind)
-                found, written = ctx.pairs_info()[:2]
-                if found <= capacity:
-                    break
-                capacity = found
-            ctx.fetch()             # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
-            s_idx, r_idx = np.empty(written, dtype=np.uint32), (np.empty(written, dtype=np.uint32) if plane_r else None)
-            if written:
-                ctx.copy_d2h(s_idx, d_s)
-                if plane_r:
-                    ctx.copy_d2h(r_idx, d_r)
-        finally:
-            for p in held:
-                ctx.dev_free(p)
-    return s_idx, r_idx
+    s_parts, r_parts = _join_maps(relR, relS, algo, kind, None, relS.size, device, probeLength=probeLength)
+    return np.concatenate(s_parts), (np.concatenate(r_parts) if r_parts else None)
 
 
 def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="inner"):
@@ -532,46 +611,9 @@ def radix_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="
     trivial = _join_without_device(kind, relR.size, relS.size)
     if trivial is not None:
         return trivial
-    plane_r = kind <= _lib.HJ_JOIN_LEFT
-    step = relS.size if not slice_tuples else min(int(slice_tuples), relS.size)
-    if step < 1:
-        raise ValueError(f"radix_join_pairs: slice_tuples must be positive, not {slice_tuples!r}")
-    parts_s, parts_r = [], []
-    with HashJoinContext(device) as ctx:
-        held = []
-
-        def alloc(nbytes):
-            held.append(ctx.dev_alloc(nbytes))
-            return held[-1]
-
-        try:
-            ctx.reserve("prj", relR.size, step, radixBits=radixBits, keepRowIds=True)
-            dR, dS = alloc(relR.nbytes), alloc(8 * step)
-            ctx.copy_h2d(dR, relR)
-            ctx.prj_build(dR, relR.size)
-            capacity = step
-            d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
-            for lo in range(0, relS.size, step):
-                part = relS[lo:lo + step]
-                ctx.copy_h2d(dS, part)
-                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
-                found, written = ctx.pairs_info()[:2]
-                if found > capacity:
-                    capacity = found
-                    d_s, d_r = alloc(4 * capacity), (alloc(4 * capacity) if plane_r else 0)
-                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
-                    found, written = ctx.pairs_info()[:2]
-                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
-                if written:
-                    ctx.copy_d2h(s_idx, d_s)
-                    if plane_r:
-                        ctx.copy_d2h(r_idx, d_r)
-                parts_s.append(s_idx)
-                parts_r.append(r_idx)
-        finally:
-            for p in held:
-                ctx.dev_free(p)
-    return np.concatenate(parts_s), (np.concatenate(parts_r) if plane_r else None)
+    step = _slice_step("radix_join_pairs", relS.size, slice_tuples)
+    s_parts, r_parts = _join_maps(relR, relS, "radix", kind, None, step, device, radixBits=radixBits)
+    return np.concatenate(s_parts), (np.concatenate(r_parts) if r_parts else None)
 
 
 # the R-preserving results: the kind of the probe calls (None: a mark-only pass, capacity 0) and which R rows follow
@@ -605,17 +647,6 @@ def _outer_without_device(kind, which, n_r, n_s):
     return _outer_result(kind, [s_idx], [r_idx], r_only)
 
 
-def _sweep(ctx, alloc, which, n_r):
-    """the rows r_rows(which) gives after the probes, as a numpy array"""
-    d_rows = alloc(4 * n_r)
-    ctx.r_rows(which, d_rows, n_r)
-    written = ctx.r_rows_info()[1]
-    rows = np.empty(written, dtype=np.uint32)
-    if written:
-        ctx.copy_d2h(rows, d_rows)
-    return rows
-
-
 def outer_join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="right"):
     """The joins that preserve relR, the build side, as gather maps like join_pairs (same algo, same meaning of a match).
     how = "right": (s_idx, r_idx), the inner rows first, then one row (NO_ROW, r) for every R row no inner row names, r
@@ -630,41 +661,8 @@ def outer_join_pairs(relR, relS, algo="htm", probeLength=4, device=0, how="right
     trivial = _outer_without_device(kind, which, relR.size, relS.size)
     if trivial is not None:
         return trivial
-    with HashJoinContext(device) as ctx:
-        held = []
-
-        def alloc(nbytes):
-            held.append(ctx.dev_alloc(nbytes))
-            return held[-1]
-
-        try:
-            ctx.reserve(algo, relR.size, relS.size, probeLength=probeLength, keepRowIds=True, trackRMatches=True)
-            dR, dS = alloc(relR.nbytes), alloc(relS.nbytes)
-            ctx.copy_h2d(dR, relR)
-            ctx.copy_h2d(dS, relS)
-            ctx.build(dR, relR.size)
-            s_idx = r_idx = None
-            if kind is None:
-                ctx.probe_pairs(dS, relS.size, 0, 0, 0)      # a mark-only pass
-            else:
-                capacity = relS.size
-                while True:
-                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
-                    ctx.probe_pairs(dS, relS.size, d_s, d_r, capacity, kind=kind)
-                    found, written = ctx.pairs_info()[:2]
-                    if found <= capacity:
-                        break
-                    capacity = found
-                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
-                if written:
-                    ctx.copy_d2h(s_idx, d_s)
-                    ctx.copy_d2h(r_idx, d_r)
-            ctx.fetch()             # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
-            r_only = _sweep(ctx, alloc, which, relR.size)
-        finally:
-            for p in held:
-                ctx.dev_free(p)
-    return _outer_result(kind, [s_idx], [r_idx], r_only)
+    s_parts, r_parts = _join_maps(relR, relS, algo, kind, which, relS.size, device, probeLength=probeLength)
+    return _outer_result(kind, s_parts, r_parts[:-1], r_parts[-1])
 
 
 def radix_outer_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0, how="right"):
@@ -677,47 +675,9 @@ def radix_outer_join_pairs(relR, relS, radixBits=0, slice_tuples=None, device=0,
     trivial = _outer_without_device(kind, which, relR.size, relS.size)
     if trivial is not None:
         return trivial
-    step = relS.size if not slice_tuples else min(int(slice_tuples), relS.size)
-    if step < 1:
-        raise ValueError(f"radix_outer_join_pairs: slice_tuples must be positive, not {slice_tuples!r}")
-    parts_s, parts_r = [], []
-    with HashJoinContext(device) as ctx:
-        held = []
-
-        def alloc(nbytes):
-            held.append(ctx.dev_alloc(nbytes))
-            return held[-1]
-
-        try:
-            ctx.reserve("prj", relR.size, step, radixBits=radixBits, keepRowIds=True, trackRMatches=True)
-            dR, dS = alloc(relR.nbytes), alloc(8 * step)
-            ctx.copy_h2d(dR, relR)
-            ctx.prj_build(dR, relR.size)
-            capacity = step if kind is not None else 0
-            d_s, d_r = (alloc(4 * capacity), alloc(4 * capacity)) if capacity else (0, 0)
-            for lo in range(0, relS.size, step):
-                part = relS[lo:lo + step]
-                ctx.copy_h2d(dS, part)
-                ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
-                if kind is None:
-                    continue
-                found, written = ctx.pairs_info()[:2]
-                if found > capacity:
-                    capacity = found
-                    d_s, d_r = alloc(4 * capacity), alloc(4 * capacity)
-                    ctx.prj_probe_pairs(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
-                    found, written = ctx.pairs_info()[:2]
-                s_idx, r_idx = np.empty(written, dtype=np.uint32), np.empty(written, dtype=np.uint32)
-                if written:
-                    ctx.copy_d2h(s_idx, d_s)
-                    ctx.copy_d2h(r_idx, d_r)
-                parts_s.append(s_idx)
-                parts_r.append(r_idx)
-            r_only = _sweep(ctx, alloc, which, relR.size)
-        finally:
-            for p in held:
-                ctx.dev_free(p)
-    return _outer_result(kind, parts_s, parts_r, r_only)
+    step = _slice_step("radix_outer_join_pairs", relS.size, slice_tuples)
+    s_parts, r_parts = _join_maps(relR, relS, "radix", kind, which, step, device, radixBits=radixBits)
+    return _outer_result(kind, s_parts, r_parts[:-1], r_parts[-1])
 
 
 # ---- the joined rows themselves: payload columns through the maps, on the device --------------------------------------
@@ -748,33 +708,6 @@ def _take_on_host(cols, idx):
     return out, valid
 
 
-class _Held:
-    """device allocations of one wrapper call: alloc / free as it goes, close frees what is left"""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def alloc(self, nbytes):
-        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 4)))
-        return self.ptrs[-1]
-
-    def put(self, a):
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            self.ctx.copy_h2d(d, a)
-        return d
-
-    def free(self, *ptrs):
-        for p in ptrs:
-            self.ptrs.remove(p)
-            self.ctx.dev_free(p)
-
-    def close(self):
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-        self.ptrs = []
-
-
 def _gather_side(ctx, held, d_map, n_rows, row_base, src_rows, d_cols):
     """One side of n_rows result rows out of the device map d_map: d_cols = [(name, device source, dtype)] -> ({name:
     array}, valid). One gather call per HJ_GATHER_MAX_COLS columns, the validity plane with the first (alone when the
@@ -798,13 +731,6 @@ def _gather_side(ctx, held, d_map, n_rows, row_base, src_rows, d_cols):
         held.free(d_valid, *dsts)
     valid = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
     return out, valid
-
-
-def _fetch_map(ctx, d_map, n):
-    idx = np.empty(n, dtype=np.uint32)
-    if n:
-        ctx.copy_d2h(idx, d_map)
-    return idx
 
 
 def _concat_side(parts, cols):
@@ -842,9 +768,7 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     plane_r = outer or kind <= _lib.HJ_JOIN_LEFT            # semi / anti: S rows alone
     tail = outer and plane_s                                # right / full: the R-only rows follow the probe's
     radix = path == "radix"
-    step = relS.size if not (radix and slice_tuples) else min(int(slice_tuples), relS.size)
-    if radix and relS.size and step < 1:
-        raise ValueError(f"{fn}: slice_tuples must be positive, not {slice_tuples!r}")
+    step = _slice_step(fn, relS.size, slice_tuples) if radix and relS.size else relS.size
 
     def result(s_idx, r_idx, s_side, r_side):
         return {"s_idx": s_idx, "r_idx": r_idx, "s": s_side[0] if plane_s else None, "r": r_side[0] if plane_r else None,
@@ -857,56 +781,26 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
         return result(s_idx, r_idx, _take_on_host(s_cols, s_idx) if plane_s else None,
                       _take_on_host(r_cols, r_idx) if plane_r else None)
 
-    s_maps, r_maps, s_parts, r_parts = [], [], [], []
-    with HashJoinContext(device) as ctx:
-        held = _Held(ctx)
-        try:
-            ctx.reserve("prj" if radix else path, relR.size, step, probeLength=probeLength, radixBits=radixBits,
-                        keepRowIds=True, trackRMatches=outer)
-            dR = held.put(relR)
-            d_r_cols = [(name, held.put(col), col.dtype) for name, col in r_cols.items()] if plane_r else []
-            if radix:
-                ctx.prj_build(dR, relR.size)
-            else:
-                ctx.build(dR, relR.size)
-            probe = ctx.prj_probe_pairs if radix else ctx.probe_pairs
-            dS = held.alloc(8 * step)
-            d_s_slice = [(name, held.alloc(step * col.dtype.itemsize), col.dtype) for name, col in s_cols.items()] if plane_s else []
-            capacity = step if plane_s else 0               # a mark-only pass needs no planes
-            d_s, d_r = (held.alloc(4 * capacity), held.alloc(4 * capacity) if plane_r else 0) if capacity else (0, 0)
-            for lo in range(0, relS.size, step):
-                part = relS[lo:lo + step]
-                ctx.copy_h2d(dS, part)
-                probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
-                if not plane_s:
-                    continue
-                found, written = ctx.pairs_info()[:2]
-                if found > capacity:                        # sized for a foreign-key join: enlarge to the reported count, once
-                    held.free(*(p for p in (d_s, d_r) if p))
-                    capacity = found
-                    d_s, d_r = held.alloc(4 * capacity), (held.alloc(4 * capacity) if plane_r else 0)
-                    probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind)
-                    found, written = ctx.pairs_info()[:2]
-                for (name, d_col, _) in d_s_slice:
-                    ctx.copy_h2d(d_col, s_cols[name][lo:lo + step])
-                s_maps.append(_fetch_map(ctx, d_s, written))
-                s_parts.append(_gather_side(ctx, held, d_s, written, lo, part.size, d_s_slice))
-                if plane_r:
-                    r_maps.append(_fetch_map(ctx, d_r, written))
-                    r_parts.append(_gather_side(ctx, held, d_r, written, 0, relR.size, d_r_cols))
-            if not radix:
-                ctx.fetch()         # raises HJ_ERR_KEY_RANGE for R tuples outside the DataGen layout, as the operators do
-            if outer:               # the R-only rows: the sweep's map feeds the gather where it lies
-                d_rows = held.alloc(4 * relR.size)
-                ctx.r_rows(which, d_rows, relR.size)
-                n_tail = ctx.r_rows_info()[1]
-                r_maps.append(_fetch_map(ctx, d_rows, n_tail))
-                r_parts.append(_gather_side(ctx, held, d_rows, n_tail, 0, relR.size, d_r_cols))
-                if tail:            # their S side is NULL by construction
-                    s_maps.append(np.full(n_tail, NO_ROW, dtype=np.uint32))
-                    s_parts.append(_take_on_host(s_cols, s_maps[-1]))
-        finally:
-            held.close()
+    s_maps, r_maps, s_parts, r_parts, dev = [], [], [], [], {}
+
+    def gather(ctx, held, lo, n_s, d_s, d_r, rows):
+        """the maps stay where the probe (or the sweep, lo None) left them and feed the gather there"""
+        if not dev:         # the first call: R's columns whole, room for a slice of S's
+            dev["r"] = [(name, held.put(col), col.dtype) for name, col in r_cols.items()] if plane_r else []
+            dev["s"] = [(name, held.alloc(step * col.dtype.itemsize), col.dtype) for name, col in s_cols.items()] if plane_s else []
+        if d_s:
+            for (name, d_col, _) in dev["s"]:
+                ctx.copy_h2d(d_col, s_cols[name][lo:lo + n_s])
+            s_maps.append(_fetch_map(ctx, d_s, rows))
+            s_parts.append(_gather_side(ctx, held, d_s, rows, lo, n_s, dev["s"]))
+        if d_r:
+            r_maps.append(_fetch_map(ctx, d_r, rows))
+            r_parts.append(_gather_side(ctx, held, d_r, rows, 0, relR.size, dev["r"]))
+        if lo is None and tail:         # the S side of the R-only rows is NULL by construction
+            s_maps.append(np.full(rows, NO_ROW, dtype=np.uint32))
+            s_parts.append(_take_on_host(s_cols, s_maps[-1]))
+
+    _drive_join(relR, relS, path, kind, which, step, gather, device, probeLength=probeLength, radixBits=radixBits)
     return result(np.concatenate(s_maps) if plane_s else None, np.concatenate(r_maps) if plane_r else None,
                   _concat_side(s_parts, s_cols), _concat_side(r_parts, r_cols))
 

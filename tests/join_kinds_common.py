@@ -3,6 +3,9 @@ buffers with guard words, the derivation of every kind from the inner pairs, and
 here, and nothing that asks the library what the rows should be: `inner` always comes from numpy / plain Python."""
 import numpy as np
 
+import htm_hashjoin_amd as hj
+from htm_hashjoin_amd import _lib
+
 SENTINEL = 0xA5A5A5A5
 GUARD = 4096
 U64 = np.uint64
@@ -50,6 +53,19 @@ class Dev:
         if words:
             self.ctx.copy_d2h(out, ptr)
         return out
+
+
+def _status(call, *args, **kw):
+    """the status a call of the library ends with"""
+    try:
+        call(*args, **kw)
+    except hj.HashJoinError as e:
+        return e.status
+    return _lib.HJ_OK
+
+
+def zipf(n, alphabet, theta, seed):
+    return hj.generate_relation("zipf", n, alphabet, 0, theta, seed)
 
 
 def matched_rows(inner):

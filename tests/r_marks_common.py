@@ -4,7 +4,7 @@ library), and Marks, which keeps in numpy what a tracking context must remember 
 Unmatched R = setdiff1d(arange(base, base + n), unique(inner & 0xFFFFFFFF)). No test in here."""
 import numpy as np
 
-from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, Dev, Calls  # noqa: F401
+from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, Dev, Calls, _status, zipf  # noqa: F401
 
 UNMATCHED, MATCHED = 0, 1
 LOW = U64(0xFFFFFFFF)

@@ -18,7 +18,8 @@ from oracle import oracle
 pytestmark = pytest.mark.gpu
 
 from join_kinds_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, KINDS, NAMES, NO_ROW, Dev, Calls, derive,
-                               matched_rows)
+                               matched_rows, _status, zipf)
+from r_marks_common import join_expected, walk_expected, inner_expected
 
 
 @pytest.fixture(scope="module")
@@ -26,65 +27,6 @@ def ctx():
     c = hj.HashJoinContext(0)
     yield c
     c.close()
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# references (as in test_gpu_pairs.py)
-# ---------------------------------------------------------------------------------------------------------------------
-def valid_s(S):
-    return ((S >> U64(32)) == 0) & (S != 0)
-
-
-def join_expected(R, S, r_base=0, s_base=0):
-    """all (i, j) with S[i] == R[j], packed and sorted: sort R, searchsorted S, expand the runs"""
-    order = np.argsort(R, kind="stable")
-    Rs = R[order]
-    lo = np.searchsorted(Rs, S, "left")
-    cnt = np.searchsorted(Rs, S, "right") - lo
-    cnt[~valid_s(S)] = 0
-    total = int(cnt.sum())
-    s_idx = np.repeat(np.arange(S.size, dtype=np.int64), cnt)
-    within = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
-    r_idx = order[np.repeat(lo, cnt) + within]
-    packed = ((s_idx + s_base).astype(U64) << U64(32)) | (r_idx + r_base).astype(U64)
-    return np.sort(packed)
-
-
-def walk_expected(R, S, probe_length, r_base=0, s_base=0):
-    """open addressing, plain Python: sequential insert in input order keeping (index, key) per slot
-    (NoCCHashBuild.hpp:43-59, the walk wraps), then the probe walk (:70-79: at most probeLength slots from the home slot,
-    no wrap, stop at the first empty one)"""
-    n = R.size
-    mask = 2 * n - 1
-    keys, idx = [0] * (2 * n + 16), [0] * (2 * n + 16)
-    for i, k in enumerate(R.tolist()):
-        cur, budget = k & mask, probe_length
-        while budget:
-            if keys[cur] == 0:
-                keys[cur], idx[cur] = k, i
-                break
-            cur = (cur + 1) & mask
-            budget -= 1
-    out = []
-    for i, s in enumerate(S.tolist()):
-        if s == 0 or s >> 32:
-            continue
-        cur = s & mask
-        for _ in range(probe_length):
-            if keys[cur] == 0:
-                break
-            if keys[cur] == s:
-                out.append(((i + s_base) << 32) | (idx[cur] + r_base))
-            cur += 1
-    return np.sort(np.array(out, dtype=U64))
-
-
-def inner_expected(algo, R, S, probe_length=4, s_base=0):
-    return join_expected(R, S, s_base=s_base) if algo == "htm" else walk_expected(R, S, probe_length, s_base=s_base)
-
-
-def zipf(n, alphabet, theta, seed):
-    return hj.generate_relation("zipf", n, alphabet, 0, theta, seed)
 
 
 def run_all_kinds(ctx, algo, R, S, inner, probe_length=4, kinds=KINDS, offset=0, tag=None, **reserve):
@@ -324,14 +266,6 @@ def test_ragged_slices_add_up_to_the_whole(ctx, algo):
 # ---------------------------------------------------------------------------------------------------------------------
 # errors
 # ---------------------------------------------------------------------------------------------------------------------
-def _status(call, *args, **kw):
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
-
-
 def test_errors():
     n = 1 << 12
     R = oracle.generate_data("local_shuffle", n, n, 16)

@@ -11,8 +11,8 @@ from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5A5A5A5
-GUARD = 4096
+from join_kinds_common import SENTINEL, GUARD, Dev, _status, zipf
+from r_marks_common import join_expected, walk_expected
 
 
 @pytest.fixture(scope="module")
@@ -20,41 +20,6 @@ def ctx():
     c = hj.HashJoinContext(0)
     yield c
     c.close()
-
-
-class Dev:
-    """device buffers of one test, freed at the end"""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-
-    def alloc(self, nbytes):
-        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 16)))
-        return self.ptrs[-1]
-
-    def put(self, arr):
-        p = self.alloc(arr.nbytes)
-        if arr.size:
-            self.ctx.copy_h2d(p, arr)
-        return p
-
-    def planes(self, capacity):
-        """two output planes of `capacity` words, GUARD sentinel words directly behind each"""
-        fill = np.full(capacity + GUARD, SENTINEL, dtype=np.uint32)
-        return self.put(fill), self.put(fill)
-
-    def get(self, ptr, words):
-        out = np.empty(words, dtype=np.uint32)
-        if words:
-            self.ctx.copy_d2h(out, ptr)
-        return out
 
 
 def probe_pairs(ctx, dev, dS, n, capacity, s_idx_base=0):
@@ -69,58 +34,6 @@ def probe_pairs(ctx, dev, dS, n, capacity, s_idx_base=0):
         guard_ok = guard_ok and bool((s[written:capacity] == SENTINEL).all() and (r[written:capacity] == SENTINEL).all())
     packed = (s[:written].astype(np.uint64) << np.uint64(32)) | r[:written].astype(np.uint64)
     return found, packed, guard_ok
-
-
-def valid_s(S):
-    return ((S >> np.uint64(32)) == 0) & (S != 0)
-
-
-def join_expected(R, S, r_base=0, s_base=0):
-    """all (i, j) with S[i] == R[j], packed and sorted: sort R, searchsorted S, expand the runs"""
-    order = np.argsort(R, kind="stable")
-    Rs = R[order]
-    lo = np.searchsorted(Rs, S, "left")
-    cnt = np.searchsorted(Rs, S, "right") - lo
-    cnt[~valid_s(S)] = 0
-    total = int(cnt.sum())
-    s_idx = np.repeat(np.arange(S.size, dtype=np.int64), cnt)
-    within = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
-    r_idx = order[np.repeat(lo, cnt) + within]
-    packed = ((s_idx + s_base).astype(np.uint64) << np.uint64(32)) | (r_idx + r_base).astype(np.uint64)
-    return np.sort(packed)
-
-
-def walk_expected(R, S, probe_length, r_base=0, s_base=0):
-    """open addressing, plain Python: sequential insert in input order keeping (index, key) per slot
-    (NoCCHashBuild.hpp:43-59, the walk wraps), then the probe walk (:70-79: at most probeLength slots from the home slot,
-    no wrap, stop at the first empty one)"""
-    n = R.size
-    mask = 2 * n - 1
-    keys, idx = [0] * (2 * n + 16), [0] * (2 * n + 16)
-    for i, k in enumerate(R.tolist()):
-        cur, budget = k & mask, probe_length
-        while budget:
-            if keys[cur] == 0:
-                keys[cur], idx[cur] = k, i
-                break
-            cur = (cur + 1) & mask
-            budget -= 1
-    out = []
-    for i, s in enumerate(S.tolist()):
-        if s == 0 or s >> 32:
-            continue
-        cur = s & mask
-        for _ in range(probe_length):
-            if keys[cur] == 0:
-                break
-            if keys[cur] == s:
-                out.append(((i + s_base) << 32) | (idx[cur] + r_base))
-            cur += 1
-    return np.sort(np.array(out, dtype=np.uint64))
-
-
-def zipf(n, alphabet, theta, seed):
-    return hj.generate_relation("zipf", n, alphabet, 0, theta, seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -271,14 +184,6 @@ def test_truncation_never_writes_past_capacity(ctx, algo):
         # capacity 0 with NULL outputs: counts only
         ctx.probe_pairs(dS, n, 0, 0, 0)
         assert ctx.pairs_info()[:2] == (found, 0)
-
-
-def _status(call, *args, **kw):
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
 
 
 def test_errors_and_noops():

@@ -16,7 +16,7 @@ LOW = U64(0xFFFFFFFF)
 COUNTERS = ("totalMatches", "sSize", "prjChecksum", "radixBits", "prjPartitions")
 COUNT_ONLY_ABOVE = 1 << 25       # a slice with more reference rows may be checked by count only (raised HJ_FUZZ_CASES)
 PAIR_BLOCK_TUPLES = 11520        # kPairBlockTuples: R tuples of one LDS build of the pairs join
-STAGE = 4096                     # kPairStage: rows per stage
+STAGE = 4096                     # kStagePairs: rows per stage
 
 
 class Expected:

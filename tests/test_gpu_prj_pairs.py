@@ -12,52 +12,10 @@ from htm_hashjoin_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5A5A5A5
-GUARD = 4096
-U64 = np.uint64
-LOW = U64(0xFFFFFFFF)
+from join_kinds_common import SENTINEL, GUARD, U64, Dev, _status
+from r_marks_common import LOW
 COUNTERS = ("totalMatches", "sSize", "prjChecksum", "radixBits", "prjPartitions")
 COUNT_ONLY_ABOVE = 1 << 25       # a slice with more reference pairs may be checked by count only (raised HJ_FUZZ_CASES)
-
-
-class Dev:
-    """device buffers of one test, freed at the end"""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-
-    def alloc(self, nbytes):
-        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 16)))
-        return self.ptrs[-1]
-
-    def free(self, *ptrs):
-        for p in ptrs:
-            self.ptrs.remove(p)
-            self.ctx.dev_free(p)
-
-    def put(self, arr):
-        p = self.alloc(arr.nbytes)
-        if arr.size:
-            self.ctx.copy_h2d(p, arr)
-        return p
-
-    def planes(self, capacity):
-        """two output planes of `capacity` words, GUARD sentinel words directly behind each"""
-        fill = np.full(capacity + GUARD, SENTINEL, dtype=np.uint32)
-        return self.put(fill), self.put(fill)
-
-    def get(self, ptr, words):
-        out = np.empty(words, dtype=np.uint32)
-        if words:
-            self.ctx.copy_d2h(out, ptr)
-        return out
 
 
 def probe_pairs(ctx, dev, dS, n, capacity, s_idx_base=0):
@@ -291,14 +249,6 @@ def test_upper_tuple_bits_are_ignored_and_key_zero_is_a_key():
 # ---------------------------------------------------------------------------------------------------------------------
 # errors, no-ops, the counting probe on the same context, rebuilds
 # ---------------------------------------------------------------------------------------------------------------------
-def _status(call, *args, **kw):
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
-
-
 def test_errors_and_noops():
     n = 1 << 14
     R = pc.unique_shuffled(n)

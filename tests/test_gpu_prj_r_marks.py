@@ -11,12 +11,12 @@ from htm_hashjoin_amd import _lib
 import prj_cases as pc
 
 from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, SCAN_TILE, Dev,
-                            Calls, Marks, inner_expected, r_rows_of)
+                            Calls, _status, Marks, inner_expected, r_rows_of)
 
 pytestmark = pytest.mark.gpu
 
 PAIR_BLOCK_TUPLES = 11520        # kPairBlockTuples: R tuples of one LDS build of the pairs join
-STAGE = 4096                     # kPairStage: rows per stage
+STAGE = 4096                     # kStagePairs: rows per stage
 ROUND = 2 * 1024                 # kPairElems * kJoinThreads: S elements of one round of a workgroup
 
 
@@ -37,14 +37,6 @@ def tracked(ctx, dev, R, s_max, bits=0):
     dR = dev.put(R)
     ctx.prj_build(dR, R.size)
     return dR, Calls(ctx, dev, ctx.prj_probe_pairs), Marks(ctx, dev, R.size)
-
-
-def _status(call, *args, **kw):
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
 
 
 @pytest.mark.parametrize("n", [1, 31, 32, 33, 1000])

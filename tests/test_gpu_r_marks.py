@@ -11,7 +11,7 @@ from htm_hashjoin_amd import _lib
 from oracle import oracle
 
 from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, Dev, Calls,
-                            Marks, inner_expected, join_expected, r_rows_of)
+                            Marks, _status, zipf, inner_expected, join_expected, r_rows_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +23,12 @@ def ctx():
     c.close()
 
 
-def zipf(n, alphabet, theta, seed):
-    return hj.generate_relation("zipf", n, alphabet, 0, theta, seed)
-
-
 def tracked(ctx, dev, algo, R, s_max, probe_length=4, idx_base=0):
     """reserve with the flag, build R -> (dR, Calls, Marks)"""
     ctx.reserve(algo, R.size, max(s_max, 1), probeLength=probe_length, keepRowIds=True, trackRMatches=True)
     dR = dev.put(R)
     ctx.build(dR, R.size, idx_base)
     return dR, Calls(ctx, dev), Marks(ctx, dev, R.size, idx_base)
-
-
-def _status(call, *args, **kw):
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
 
 
 # ---------------------------------------------------------------------------------------------------------------------

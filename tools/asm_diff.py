@@ -5,7 +5,8 @@
 
 Compiles every csrc/*.hip of both trees to gfx950 assembly with the Makefile's flags (device side only) and prints, per
 file, the kernels that exist on one side only and, per kernel, `identical` or `differs` with the resources of both sides
-(VGPRs, SGPRs, LDS bytes, scratch bytes, spilled SGPRs / VGPRs). Instruction text is compared with symbol names, local
+(VGPRs, SGPRs, LDS bytes, scratch bytes, spilled SGPRs / VGPRs). Kernels are paired by demangled name without the
+argument list, so a kernel whose signature changed is compared with its former self. Instruction text is compared with symbol names, local
 labels and comments taken out; the compilation-unit id never reaches it.
 """
 import os
@@ -15,7 +16,7 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["hj_kernels", "hj_build_own", "hj_build_wave", "hj_htm", "hj_pairs", "hj_prj", "hj_api"]
+FILES = ["hj_kernels", "hj_build_own", "hj_build_wave", "hj_htm", "hj_pairs", "hj_r_marks", "hj_gather", "hj_prj", "hj_api"]
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-value --cuda-device-only -S".split()
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -83,17 +84,19 @@ def main():
         print("|---|---|---|---|---|")
         for f in FILES:
             a, b = kernels(os.path.join(tp, f + ".s")), kernels(os.path.join(tc, f + ".s"))
+            # paired by demangled name without the argument list: a kernel whose signature changed is still the same kernel
             dm = demangle(sorted(set(a) | set(b)))
-            for k in sorted(set(a) | set(b), key=lambda k: dm[k]):
+            a, b = {dm[k]: v for k, v in a.items()}, {dm[k]: v for k, v in b.items()}
+            for k in sorted(set(a) | set(b)):
                 if k not in a or k not in b:
-                    print("| %s | `%s` | only in %s | %s | %s |" % (f, dm[k], "parent" if k in a else "change",
+                    print("| %s | `%s` | only in %s | %s | %s |" % (f, k, "parent" if k in a else "change",
                                                                    fmt(a[k][1]) if k in a else "", fmt(b[k][1]) if k in b else ""))
                 elif a[k][0] == b[k][0] and a[k][1] == b[k][1]:
                     same += 1
-                    print("| %s | `%s` | identical | | |" % (f, dm[k]))
+                    print("| %s | `%s` | identical | | |" % (f, k))
                 else:
                     differs += 1
-                    print("| %s | `%s` | differs | %s | %s |" % (f, dm[k], fmt(a[k][1]), fmt(b[k][1])))
+                    print("| %s | `%s` | differs | %s | %s |" % (f, k, fmt(a[k][1]), fmt(b[k][1])))
         print("\n%d kernels identical, %d differ" % (same, differs))
 
 
