@@ -39,6 +39,9 @@ JOIN_KINDS = {"inner": HJ_JOIN_INNER, "left": HJ_JOIN_LEFT, "semi": HJ_JOIN_SEMI
 HJ_NO_ROW = 0xFFFFFFFF
 # hj_gather_dev: columns of one call
 HJ_GATHER_MAX_COLS = 8
+# hj_key_hash_dev / hj_pairs_verify_dev: key columns of one call, and which side's pointers the hash reads
+HJ_KEY_MAX_COLS = 4
+HJ_KEY_SIDE_S, HJ_KEY_SIDE_R = 0, 1
 
 
 class hj_params(C.Structure):
@@ -87,6 +90,15 @@ class hj_gather_col(C.Structure):
     ]
 
 
+class hj_key_col(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p),
+        ("r", C.c_void_p),
+        ("width", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 def _declare(lib):
     vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
     P = C.POINTER
@@ -111,6 +123,12 @@ def _declare(lib):
         "hj_r_rows_info": ([vp, P(u64)], i32),
         "hj_gather_dev": ([vp, vp, u64, u32, u64, P(hj_gather_col), u32, vp], i32),
         "hj_gather_info": ([vp, P(u64)], i32),
+        "hj_key_hash_dev": ([vp, P(hj_key_col), u32, u32, u64, u32, vp], i32),
+        "hj_key_hash_host": ([P(hj_key_col), u32, u32, u64, u32, vp], i32),
+        "hj_pairs_verify_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col), u32, vp, vp, u64, vp, vp], i32),
+        "hj_verify_info": ([vp, P(u64)], i32),
+        "hj_mark_rows_dev": ([vp, vp, u64, u32, u32, vp, u64], i32),
+        "hj_mark_rows_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_prj_build_dev": ([vp, vp, u64], i32),
         "hj_prj_probe_dev": ([vp, vp, u64], i32),

@@ -32,6 +32,8 @@ enum Buf {
     B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_device.h)
     B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
     B_GATHER_CTR,               // hj_gather_dev: the NULL rows and the out-of-range entries of the last call (two 64-bit words)
+    B_VERIFY_CTR,               // hj_pairs_verify_dev: the output cursor (= pairs kept), then the candidates dropped (two 64-bit words)
+    B_MARK_SWEEP,               // hj_mark_rows_dev: the sweep's workspace for a caller's plane (r_sweep_count_words(rows))
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -102,6 +104,13 @@ struct hj_ctx {
     bool gatherCalled = false;                  // ... ran on this context; the rows of the last call (hj_gather_info)
     uint64_t gatherRows = 0;
     hipEvent_t evGather[2] = {nullptr, nullptr};
+    // hj_pairs_verify_dev and hj_mark_rows_dev: like the gather, no part of a build or an operation
+    bool verifyCalled = false;                  // ... ran on this context; the capacity of the last call (hj_verify_info)
+    uint64_t verifyCapacity = 0;
+    hipEvent_t evVerify[2] = {nullptr, nullptr};
+    bool markRowsCalled = false;                // the same for hj_mark_rows_dev: its rows and capacity (hj_mark_rows_info)
+    uint64_t markRowsRows = 0, markRowsCapacity = 0;
+    hipEvent_t evMarkRows[2] = {nullptr, nullptr};
     Counters* hCtr = nullptr;     // pinned copy of the counters
     // PRJ
     PrjPlan plan{};
@@ -304,7 +313,10 @@ int create_common(int device, void* stream, bool own, hj_ctx** out)
               c->buf[B_PAIRS_CURSOR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
               hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, 2 * sizeof(unsigned long long)) == hipSuccess &&
               c->buf[B_GATHER_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              hipEventCreate(&c->evGather[0]) == hipSuccess && hipEventCreate(&c->evGather[1]) == hipSuccess;
+              hipEventCreate(&c->evGather[0]) == hipSuccess && hipEventCreate(&c->evGather[1]) == hipSuccess &&
+              c->buf[B_VERIFY_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
+              hipEventCreate(&c->evVerify[0]) == hipSuccess && hipEventCreate(&c->evVerify[1]) == hipSuccess &&
+              hipEventCreate(&c->evMarkRows[0]) == hipSuccess && hipEventCreate(&c->evMarkRows[1]) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }
     hipMemset(c->dCtr(), 0, sizeof(Counters));
@@ -361,6 +373,8 @@ void hj_destroy(hj_ctx* c)
     if (c->hPreferred) hipHostFree(c->hPreferred);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
     for (hipEvent_t e : c->evGather) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->evVerify) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->evMarkRows) if (e) hipEventDestroy(e);
     if (c->ownStream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -953,6 +967,133 @@ int hj_gather_info(hj_ctx* c, uint64_t out[4])
     out[1] = words[0];
     out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
     out[3] = words[1];
+    return HJ_OK;
+}
+
+// ---- joins on real key columns: hash, verify, sweep of a caller's plane -----
+// The columns of a call, checked: nCols, widths, reserved, and the pointers of the sides in use (rows > 0 on that side)
+static const char* key_cols_error(const hj_key_col* cols, uint32_t nCols, bool useS, bool useR)
+{
+    if (nCols == 0 || nCols > HJ_KEY_MAX_COLS) return "nCols must be 1 .. HJ_KEY_MAX_COLS";
+    if (!cols) return "cols NULL";
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_key_col& col = cols[i];
+        if (!gather_width_ok(col.width)) return "a width that is not 1, 2, 4, 8 or 16";
+        if (col.reserved) return "hj_key_col.reserved must be 0";
+        const uintptr_t low = col.width - 1;
+        if (useS && (!col.s || (reinterpret_cast<uintptr_t>(col.s) & low))) return "an S column that is NULL or not aligned to its width";
+        if (useR && (!col.r || (reinterpret_cast<uintptr_t>(col.r) & low))) return "an R column that is NULL or not aligned to its width";
+    }
+    return nullptr;
+}
+
+// hj_key_hash_dev's and hj_key_hash_host's arguments -> the kernel's columns; the message of what is wrong, or nullptr
+static const char* key_hash_args(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols* k)
+{
+    if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
+    if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
+    if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
+    if (nRows && !out) return "output pointer NULL with nRows > 0";
+    for (uint32_t i = 0; i < nCols; ++i) { k->p[i] = side == HJ_KEY_SIDE_S ? cols[i].s : cols[i].r; k->width[i] = cols[i].width; }
+    return nullptr;
+}
+
+int hj_key_hash_dev(hj_ctx* c, const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+{
+    HJ_ENTER(c, true);
+    KeyCols k{};
+    if (const char* what = key_hash_args(cols, nCols, side, nRows, dOutTuples, &k))
+        return fail(c, HJ_ERR_INVALID, (std::string("hj_key_hash_dev: ") + what).c_str());
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, launch_key_hash(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
+    return HJ_OK;
+}
+
+int hj_key_hash_host(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+{
+    KeyCols k{};
+    if (key_hash_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
+    key_hash_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
+    return HJ_OK;
+}
+
+int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                        uint64_t rRows, const hj_key_col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                        uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: nPairs, sRows or rRows above 2^32 - 1");
+    if (const char* what = key_cols_error(cols, nCols, sRows != 0, rRows != 0))
+        return fail(c, HJ_ERR_INVALID, (std::string("hj_pairs_verify_dev: ") + what).c_str());
+    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: a map NULL with nPairs > 0");
+    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: an output pointer NULL with capacity > 0");
+    KeyColsSR k{};
+    for (uint32_t i = 0; i < nCols; ++i) { k.s[i] = cols[i].s; k.r[i] = cols[i].r; k.width[i] = cols[i].width; }
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->evVerify[0], c->stream));
+    HJ_HIP(c, launch_pairs_verify(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
+    HJ_HIP(c, hipEventRecord(c->evVerify[1], c->stream));
+    c->verifyCalled = true; c->verifyCapacity = capacity;
+    return HJ_OK;
+}
+
+int hj_verify_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = out[3] = 0;      // no hj_pairs_verify_dev yet
+    if (!c->verifyCalled) return HJ_OK;
+    unsigned long long words[2] = {0, 0};        // pairs kept, candidates dropped
+    HJ_HIP(c, hipMemcpy(words, c->buf[B_VERIFY_CTR].p, sizeof words, hipMemcpyDeviceToHost));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->evVerify[0], c->evVerify[1]) != hipSuccess) ms = 0;
+    out[0] = words[0];
+    out[1] = words[0] < c->verifyCapacity ? words[0] : c->verifyCapacity;
+    out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
+    out[3] = words[1];
+    return HJ_OK;
+}
+
+int hj_mark_rows_dev(hj_ctx* c, const uint32_t* dMarks, uint64_t rows, uint32_t rowBase, uint32_t which, uint32_t* dOut, uint64_t capacity)
+{
+    HJ_ENTER(c, true);
+    if (which > HJ_R_MATCHED) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: which must be HJ_R_UNMATCHED or HJ_R_MATCHED");
+    if (rows > 0xFFFFFFFFull || (uint64_t)rowBase + rows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: rows or rowBase + rows above 2^32 - 1");
+    if (rows && !dMarks) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: dMarks NULL with rows > 0");
+    if (rows && capacity && !dOut) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: output pointer NULL with capacity > 0");
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (const int rc = c->buf[B_MARK_SWEEP].reserve(c, r_sweep_count_words(rows) * sizeof(uint32_t))) return rc;
+    HJ_HIP(c, hipEventRecord(c->evMarkRows[0], c->stream));
+    // the sweep reads the plane and never writes it
+    const RMarks mk{const_cast<uint32_t*>(dMarks), rowBase, (uint32_t)rows};
+    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOut, capacity, c->buf[B_MARK_SWEEP].as<uint32_t>(), c->stream));
+    HJ_HIP(c, hipEventRecord(c->evMarkRows[1], c->stream));
+    c->markRowsCalled = true; c->markRowsRows = rows; c->markRowsCapacity = capacity;
+    return HJ_OK;
+}
+
+int hj_mark_rows_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = out[3] = 0;      // no hj_mark_rows_dev yet
+    if (!c->markRowsCalled) return HJ_OK;
+    uint32_t produced = 0;                      // the word behind the block counts: their total after the scan (no block: no row)
+    if (c->markRowsRows)
+        HJ_HIP(c, hipMemcpy(&produced, c->buf[B_MARK_SWEEP].as<uint32_t>() + r_sweep_blocks(c->markRowsRows), sizeof produced, hipMemcpyDeviceToHost));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->evMarkRows[0], c->evMarkRows[1]) != hipSuccess) ms = 0;
+    out[0] = produced;
+    out[1] = produced < c->markRowsCapacity ? produced : c->markRowsCapacity;
+    out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
+    out[3] = c->markRowsRows;
     return HJ_OK;
 }
 

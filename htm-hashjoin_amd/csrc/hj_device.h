@@ -684,6 +684,24 @@ struct GatherCols { GatherCol col[kGatherMaxCols]; };
 hipError_t launch_gather(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols& cols, uint32_t nCols,
                          uint32_t* valid, unsigned long long* counts, hipStream_t s);
 
+// ---- joins on real key columns (defined in hj_keys.hip) ----------------------
+// The key columns of a call as the kernels take them, by value in the kernel arguments (hj_key_col, include/htm_hashjoin.h):
+// the hash reads one side (KeyCols), the verify step both (KeyColsSR).
+constexpr uint32_t kKeyMaxCols = 4;           // HJ_KEY_MAX_COLS
+struct KeyCols { const void* p[kKeyMaxCols]; uint32_t width[kKeyMaxCols]; };
+struct KeyColsSR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; uint32_t width[kKeyMaxCols]; };
+// out[i] = the join word of row i (the header's MurmurHash3_x86_32 over the row's key columns, & mask) as an 8-byte tuple.
+// mask is the effective one (never 0). The caller has checked widths, alignment and nRows <= 2^32 - 1.
+hipError_t launch_key_hash(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s);
+void key_hash_host(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out);   // the same body in a host loop
+// Candidate pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose key columns are bytewise equal, to `out` as the pairs
+// kernels write theirs (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the candidates dropped as
+// HJ_NO_ROW or outside sRows / rRows, which are never dereferenced). Every kept pair sets bit s of sMarks and bit r of
+// rMarks (RMarks' layout; either may be null). The caller has checked the columns and nPairs <= 2^32 - 1.
+hipError_t launch_pairs_verify(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                               uint32_t rRows, const KeyColsSR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                               hipStream_t s);
+
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):
 // pass 1 cuts the relation into C1 chunks and writes bin b of chunk c to the fragment (b * C1 + c) of cap1 key slots;

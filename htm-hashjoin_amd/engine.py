@@ -114,6 +114,15 @@ def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSiz
 SHARD_ONE_BASED = 0x100
 
 
+def _key_cols(cols):
+    """[(s_ptr, r_ptr, width)] -> (hj_key_col array, its length)"""
+    cols = list(cols)
+    arr = (_lib.hj_key_col * max(len(cols), 1))()
+    for c, (s, r, width) in zip(arr, cols):
+        c.s, c.r, c.width, c.reserved = s or None, r or None, width, 0
+    return arr, len(cols)
+
+
 class HashJoinContext:
     """One engine context bound to one GPU (hj_ctx). ``stream`` is a raw hipStream_t
     handle (e.g. torch.cuda.current_stream().cuda_stream); None = private stream."""
@@ -232,6 +241,51 @@ class HashJoinContext:
         microseconds, its out-of-range entries); all 0 before the first one."""
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_gather_info(self._h, out))
+        return tuple(int(x) for x in out)
+
+    # ---- joins on real key columns: hash, candidate join, verify ---------------
+    def key_hash(self, cols, side, n_rows, d_out, key_mask=0):
+        """hj_key_hash_dev: d_out[i] = the 32-bit join word of row i < n_rows as an 8-byte tuple (what prj_build and
+        prj_probe_pairs take), hashed from the key columns cols = 1 to HJ_KEY_MAX_COLS tuples (s_ptr, r_ptr, width) of
+        device pointers, width 1, 2, 4, 8 or 16 bytes; side (HJ_KEY_SIDE_S / HJ_KEY_SIDE_R) says which pointers are read,
+        the others may be 0. The hash is MurmurHash3_x86_32 over the row's columns (include/htm_hashjoin.h), & key_mask
+        (0: all 32 bits). Asynchronous; needs no reserve and no table."""
+        arr, n = _key_cols(cols)
+        self._check(lib.hj_key_hash_dev(self._h, arr, n, side, n_rows, key_mask, C.c_void_p(d_out) if d_out else None))
+
+    def pairs_verify(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, cols, d_out_s, d_out_r, capacity,
+                     d_s_marks=0, d_r_marks=0):
+        """hj_pairs_verify_dev: of the n_pairs candidate pairs (d_map_s[k] - s_row_base, d_map_r[k]) -- the planes of a
+        prj_probe_pairs(kind=0) call on hashed keys -- keeps those whose key columns (cols as in key_hash, both pointers
+        of every column in use) are bytewise equal, and writes them to d_out_s / d_out_r as probe_pairs writes its pairs
+        (d_out_s keeps the base; pairs beyond `capacity` are counted, not written; capacity 0 with 0 outputs marks only).
+        Every kept pair sets bit s of d_s_marks and bit r of d_r_marks (device uint32 words, bit i & 31 of word i >> 5;
+        0: no plane), which the caller has cleared. A candidate that is NO_ROW or outside s_rows / r_rows is dropped
+        unread. The outputs must not alias the maps. Asynchronous; needs no reserve and no table."""
+        arr, n = _key_cols(cols)
+        p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
+        self._check(lib.hj_pairs_verify_dev(self._h, p(d_map_s), p(d_map_r), n_pairs, s_row_base, s_rows, r_rows, arr, n,
+                                            p(d_out_s), p(d_out_r), capacity, p(d_s_marks), p(d_r_marks)))
+
+    def verify_info(self):
+        """hj_verify_info (waits for the stream): (pairs the last pairs_verify kept, pairs it wrote, its device time in
+        microseconds, candidates it dropped as NO_ROW or out of range); rejected = n_pairs - kept - dropped."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_verify_info(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def mark_rows(self, d_marks, rows, row_base, which, d_out, capacity):
+        """hj_mark_rows_dev: r_rows on a caller's plane. The rows row_base + i, i < rows, whose bit i of d_marks is clear
+        (which = 0, HJ_R_UNMATCHED) or set (1, HJ_R_MATCHED), ascending, into the device uint32 array d_out of `capacity`
+        entries; rows beyond it are counted, not written (capacity 0, d_out 0: count only). Changes no mark."""
+        self._check(lib.hj_mark_rows_dev(self._h, C.c_void_p(d_marks) if d_marks else None, rows, row_base, which,
+                                         C.c_void_p(d_out) if d_out else None, capacity))
+
+    def mark_rows_info(self):
+        """hj_mark_rows_info (waits for the stream): (rows the last mark_rows produced, rows it wrote, its device time in
+        microseconds, the rows of its plane)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_mark_rows_info(self._h, out))
         return tuple(int(x) for x in out)
 
     def prj_join(self, dR_ptr, rSize, dS_ptr, sSize):
@@ -501,7 +555,7 @@ def _fetch_map(ctx, d_map, n):
 
 
 
-def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLength=4, radixBits=0):
+def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLength=4, radixBits=0, fill=None, after=None):
     """The host sequence of every materialising wrapper, once: reserve, upload R, build, then relS in slices of `step`
     tuples -- upload, probe, hand the slice's maps to on_maps -- then the counters and the sweep of the R marks.
     path: "htm" | "atomic" | "nocc", the table probes (step = len(relS): all of S in one call from row 0; the fetch at
@@ -513,7 +567,10 @@ def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLengt
     rows gets planes of the reported count and is probed once more.
     on_maps(ctx, held, lo, n_s, d_s, d_r, rows): the device maps of the `rows` rows of the slice relS[lo:lo + n_s] (d_r
     is 0 for a kind without an R plane); after the probes once more with lo None and d_s 0, d_r being the sweep's map.
-    The maps are valid until on_maps returns; what it allocates from `held` and does not free lives to the end."""
+    The maps are valid until on_maps returns; what it allocates from `held` and does not free lives to the end.
+    fill(ctx, held, d_tuples, lo, n) (join_on): the tuples are made on the device instead of copied there -- all n of R's
+    with lo None, right after the reserve, then those of the slice relS[lo:lo + n] before its probe; relR and relS are
+    then read for their lengths alone. after(ctx, held): runs behind the last slice, the context still open."""
     radix = path == "radix"
     plane_r = kind is not None and kind <= _lib.HJ_JOIN_LEFT
     with HashJoinContext(device) as ctx:
@@ -521,7 +578,11 @@ def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLengt
         try:
             ctx.reserve("prj" if radix else path, relR.size, step, probeLength=probeLength, radixBits=radixBits,
                         keepRowIds=True, trackRMatches=which is not None)
-            dR = held.put(relR)
+            if fill is None:
+                dR = held.put(relR)
+            else:
+                dR = held.alloc(8 * relR.size)
+                fill(ctx, held, dR, None, relR.size)
             if radix:
                 ctx.prj_build(dR, relR.size)
             else:
@@ -532,7 +593,10 @@ def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLengt
             d_s, d_r = (held.alloc(4 * capacity), held.alloc(4 * capacity) if plane_r else 0) if capacity else (0, 0)
             for lo in range(0, relS.size, step):
                 part = relS[lo:lo + step]
-                ctx.copy_h2d(dS, part)
+                if fill is None:
+                    ctx.copy_h2d(dS, part)
+                else:
+                    fill(ctx, held, dS, lo, part.size)
                 probe(dS, part.size, d_s, d_r, capacity, s_idx_base=lo, kind=kind or 0)
                 if kind is None:
                     continue
@@ -550,6 +614,8 @@ def _drive_join(relR, relS, path, kind, which, step, on_maps, device, probeLengt
                 d_rows = held.alloc(4 * relR.size)
                 ctx.r_rows(which, d_rows, relR.size)
                 on_maps(ctx, held, None, 0, 0, d_rows, ctx.r_rows_info()[1])
+            if after is not None:
+                after(ctx, held)
         finally:
             held.close()
 
@@ -740,6 +806,63 @@ def _concat_side(parts, cols):
             np.concatenate([p[1] for p in parts]) if parts else np.empty(0, dtype=bool))
 
 
+class _TableRows:
+    """The result of join_tables / join_on as it grows: every device map a call of add() is given is copied to the host
+    for the result and feeds the gather of its side's payload columns where it lies."""
+
+    def __init__(self, how, r_cols, s_cols, n_r, step):
+        self.outer = how in _OUTER_KINDS
+        self.kind, self.which = _OUTER_KINDS[how] if self.outer else (_lib.JOIN_KINDS[how], None)
+        self.plane_s = self.kind is not None                                # right_semi / right_anti: R rows alone
+        self.plane_r = self.outer or self.kind <= _lib.HJ_JOIN_LEFT         # semi / anti: S rows alone
+        self.r_cols, self.s_cols, self.n_r, self.step = r_cols, s_cols, n_r, step
+        self.s_maps, self.r_maps, self.s_parts, self.r_parts, self.dev, self.s_lo = [], [], [], [], {}, None
+
+    def result(self, s_idx, r_idx, s_side, r_side):
+        return {"s_idx": s_idx, "r_idx": r_idx, "s": s_side[0] if self.plane_s else None, "r": r_side[0] if self.plane_r else None,
+                "s_valid": s_side[1] if self.plane_s else None, "r_valid": r_side[1] if self.plane_r else None}
+
+    def without_device(self, n_s):
+        """the result of a join with an empty side; None: the inputs need the device"""
+        trivial = (_outer_without_device(self.kind, self.which, self.n_r, n_s) if self.outer
+                   else _join_without_device(self.kind, self.n_r, n_s))
+        if trivial is None:
+            return None
+        s_idx, r_idx = trivial
+        return self.result(s_idx, r_idx, _take_on_host(self.s_cols, s_idx) if self.plane_s else None,
+                           _take_on_host(self.r_cols, r_idx) if self.plane_r else None)
+
+    def add(self, ctx, held, lo, n_s, d_s, d_r, rows):
+        """`rows` result rows: d_s their S rows out of the slice of n_s tuples from lo, d_r their R rows. The maps stay
+        where the probe (or a sweep) left them and feed the gather there. A side the kind has a plane for and the rows
+        have no map of (0) is NULL by construction: the S side of R-only rows, the R side of unmatched S rows."""
+        if not self.dev:    # the first call: R's columns whole, room for a slice of S's
+            self.dev["r"] = [(name, held.put(col), col.dtype) for name, col in self.r_cols.items()] if self.plane_r else []
+            self.dev["s"] = ([(name, held.alloc(self.step * col.dtype.itemsize), col.dtype) for name, col in self.s_cols.items()]
+                             if self.plane_s else [])
+        for side, plane, d_map, maps, parts, cols in (("s", self.plane_s, d_s, self.s_maps, self.s_parts, self.s_cols),
+                                                      ("r", self.plane_r, d_r, self.r_maps, self.r_parts, self.r_cols)):
+            if not plane:
+                continue
+            if not d_map:
+                maps.append(np.full(rows, NO_ROW, dtype=np.uint32))
+                parts.append(_take_on_host(cols, maps[-1]))
+                continue
+            maps.append(_fetch_map(ctx, d_map, rows))
+            if side == "r":
+                parts.append(_gather_side(ctx, held, d_map, rows, 0, self.n_r, self.dev["r"]))
+                continue
+            if self.s_lo != lo:         # the slice's columns go up once, however many calls name rows of it
+                for (name, d_col, _) in self.dev["s"]:
+                    ctx.copy_h2d(d_col, self.s_cols[name][lo:lo + n_s])
+                self.s_lo = lo
+            parts.append(_gather_side(ctx, held, d_map, rows, lo, n_s, self.dev["s"]))
+
+    def joined(self):
+        return self.result(np.concatenate(self.s_maps) if self.plane_s else None, np.concatenate(self.r_maps) if self.plane_r else None,
+                           _concat_side(self.s_parts, self.s_cols), _concat_side(self.r_parts, self.r_cols))
+
+
 def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", probeLength=4, radixBits=0, slice_tuples=None,
                 device=0):
     """The joined rows: the key tuples relR / relS as join_pairs takes them, and payload columns of either side (r_cols /
@@ -752,7 +875,8 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     Returns {"s_idx", "r_idx", "s", "r", "s_valid", "r_valid"}: the maps as the pairs wrappers give them, the gathered
     columns per side as {name: array of the input dtype} and one bool per row and side (False: the row has no tuple of
     that side, its columns are all-zero bytes). A side the kind has no plane for (R for semi / anti, S for right_semi /
-    right_anti) is None in all three. For right / full the R-only rows follow the probe's rows, R ascending."""
+    right_anti) is None in all three. For right / full the R-only rows follow the probe's rows, R ascending.
+    Every path joins on one 32-bit word of a tuple; for a 64-bit key, a key of several columns or a 16-byte key: join_on."""
     fn = "join_tables"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -762,47 +886,136 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     relS = np.ascontiguousarray(relS, dtype=np.uint64)
     r_cols = _table_columns(fn, "R", r_cols, relR.size)
     s_cols = _table_columns(fn, "S", s_cols, relS.size)
-    outer = how in _OUTER_KINDS
-    kind, which = _OUTER_KINDS[how] if outer else (_lib.JOIN_KINDS[how], None)
-    plane_s = kind is not None                              # right_semi / right_anti: R rows alone
-    plane_r = outer or kind <= _lib.HJ_JOIN_LEFT            # semi / anti: S rows alone
-    tail = outer and plane_s                                # right / full: the R-only rows follow the probe's
-    radix = path == "radix"
-    step = _slice_step(fn, relS.size, slice_tuples) if radix and relS.size else relS.size
-
-    def result(s_idx, r_idx, s_side, r_side):
-        return {"s_idx": s_idx, "r_idx": r_idx, "s": s_side[0] if plane_s else None, "r": r_side[0] if plane_r else None,
-                "s_valid": s_side[1] if plane_s else None, "r_valid": r_side[1] if plane_r else None}
-
-    trivial = (_outer_without_device(kind, which, relR.size, relS.size) if outer
-               else _join_without_device(kind, relR.size, relS.size))
+    step = _slice_step(fn, relS.size, slice_tuples) if path == "radix" and relS.size else relS.size
+    rows = _TableRows(how, r_cols, s_cols, relR.size, step)
+    trivial = rows.without_device(relS.size)
     if trivial is not None:
-        s_idx, r_idx = trivial
-        return result(s_idx, r_idx, _take_on_host(s_cols, s_idx) if plane_s else None,
-                      _take_on_host(r_cols, r_idx) if plane_r else None)
+        return trivial
+    _drive_join(relR, relS, path, rows.kind, rows.which, step, rows.add, device, probeLength=probeLength, radixBits=radixBits)
+    return rows.joined()
 
-    s_maps, r_maps, s_parts, r_parts, dev = [], [], [], [], {}
 
-    def gather(ctx, held, lo, n_s, d_s, d_r, rows):
-        """the maps stay where the probe (or the sweep, lo None) left them and feed the gather there"""
-        if not dev:         # the first call: R's columns whole, room for a slice of S's
-            dev["r"] = [(name, held.put(col), col.dtype) for name, col in r_cols.items()] if plane_r else []
-            dev["s"] = [(name, held.alloc(step * col.dtype.itemsize), col.dtype) for name, col in s_cols.items()] if plane_s else []
-        if d_s:
-            for (name, d_col, _) in dev["s"]:
-                ctx.copy_h2d(d_col, s_cols[name][lo:lo + n_s])
-            s_maps.append(_fetch_map(ctx, d_s, rows))
-            s_parts.append(_gather_side(ctx, held, d_s, rows, lo, n_s, dev["s"]))
-        if d_r:
-            r_maps.append(_fetch_map(ctx, d_r, rows))
-            r_parts.append(_gather_side(ctx, held, d_r, rows, 0, relR.size, dev["r"]))
-        if lo is None and tail:         # the S side of the R-only rows is NULL by construction
-            s_maps.append(np.full(rows, NO_ROW, dtype=np.uint32))
-            s_parts.append(_take_on_host(s_cols, s_maps[-1]))
+# ---- joins on real key columns: hash, candidate join, verify -------------------------------------------------------------
+def _key_columns(fn, side, keys):
+    """the key columns of one side as a list of contiguous 1-D arrays; ValueError for what the hash cannot take"""
+    cols = [keys] if isinstance(keys, np.ndarray) else [np.asarray(k) for k in keys]
+    if not 1 <= len(cols) <= _lib.HJ_KEY_MAX_COLS:
+        raise ValueError(f"{fn}: {side} has {len(cols)} key columns; 1 to {_lib.HJ_KEY_MAX_COLS} can be joined on")
+    for a in cols:
+        if a.ndim != 1 or a.shape[0] != cols[0].shape[0]:
+            raise ValueError(f"{fn}: the key columns of {side} must be 1-D and of one length, not shape {a.shape}")
+        if a.dtype.itemsize not in _GATHER_WIDTHS:
+            raise ValueError(f"{fn}: a key column of {side} has {a.dtype.itemsize}-byte elements; 1, 2, 4, 8 or 16 can be joined on")
+    return [np.ascontiguousarray(a) for a in cols]
 
-    _drive_join(relR, relS, path, kind, which, step, gather, device, probeLength=probeLength, radixBits=radixBits)
-    return result(np.concatenate(s_maps) if plane_s else None, np.concatenate(r_maps) if plane_r else None,
-                  _concat_side(s_parts, s_cols), _concat_side(r_parts, r_cols))
+
+def _aligned(a):
+    """a, or a copy of it whose first element lies at a multiple of the itemsize (the C ABI's rule for a column)"""
+    width = a.dtype.itemsize
+    if a.ctypes.data % width == 0:
+        return a
+    raw = np.empty(a.nbytes + width, dtype=np.uint8)
+    off = -raw.ctypes.data % width
+    out = raw[off:off + a.nbytes].view(a.dtype)
+    out[...] = a
+    return out
+
+
+def key_hash_host(cols, key_mask=0):
+    """hj_key_hash_host: the 32-bit join word of every row of the key columns `cols` (one 1-D numpy array, or a sequence of
+    1 to HJ_KEY_MAX_COLS of them, elements of 1, 2, 4, 8 or 16 bytes) as a numpy uint64 array -- the tuples
+    HashJoinContext.key_hash writes for the same columns on the device, computed by the same code on the host. The hash
+    is MurmurHash3_x86_32 with seed 0 over the row's columns in order (include/htm_hashjoin.h), & key_mask (0: all 32
+    bits). Needs no device."""
+    cols = [_aligned(a) for a in _key_columns("key_hash_host", "cols", cols)]
+    out = np.empty(cols[0].size, dtype=np.uint64)
+    arr, n = _key_cols([(a.ctypes.data, 0, a.dtype.itemsize) for a in cols])
+    rc = lib.hj_key_hash_host(arr, n, _lib.HJ_KEY_SIDE_S, out.size, int(key_mask), out.ctypes.data)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_key_hash_host")
+    return out
+
+
+# which rows of the slice's S plane a kind adds to the kept pairs (left, full) or returns (semi, anti)
+_ON_S_SWEEP = {_lib.HJ_JOIN_LEFT: _lib.HJ_R_UNMATCHED, _lib.HJ_JOIN_SEMI: _lib.HJ_R_MATCHED, _lib.HJ_JOIN_ANTI: _lib.HJ_R_UNMATCHED}
+
+
+def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0):
+    """join_tables for keys that are not one 32-bit word: r_keys / s_keys are each one 1-D numpy array or a sequence of 1
+    to HJ_KEY_MAX_COLS of them (all of a side of one length; column c of both sides of the same itemsize out of 1, 2, 4,
+    8, 16 bytes -- 64-bit integers, several columns, 16-byte structured elements), and two rows match when every key
+    column is BYTEWISE equal. For float keys that means -0.0 != 0.0, and a NaN equals the same NaN bit pattern.
+    The method is hash, candidate join, verify, all on the device: the key columns are hashed to a 32-bit join word
+    (HashJoinContext.key_hash), the resident radix join gives the candidate pairs on that word, pairs_verify compares
+    the real key bytes of every candidate and marks the S and R rows of the pairs it keeps, and the kind follows from the
+    kept pairs and the sweeps of those marks (mark_rows). key_mask (0: none) keeps only those bits of the join word: more
+    candidates, the same result -- for tests; the result never depends on the hash's quality.
+    how, r_cols / s_cols, radixBits, slice_tuples and the result -- {"s_idx", "r_idx", "s", "r", "s_valid", "r_valid"} -- as
+    in join_tables(path="radix"). Per slice, left and full give the kept pairs first, then the slice's unmatched S rows
+    ascending; semi and anti give their S rows ascending; for right / full the R-only rows come last, R ascending."""
+    fn = "join_on"
+    if not isinstance(how, str) or how not in _TABLE_HOWS:
+        raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
+    r_keys, s_keys = _key_columns(fn, "R", r_keys), _key_columns(fn, "S", s_keys)
+    widths = [a.dtype.itemsize for a in r_keys]
+    if widths != [a.dtype.itemsize for a in s_keys]:
+        raise ValueError(f"{fn}: the key columns of R have {widths}-byte elements, those of S {[a.dtype.itemsize for a in s_keys]}")
+    if not 0 <= int(key_mask) <= 0xFFFFFFFF:
+        raise ValueError(f"{fn}: key_mask must fit 32 bits, not {key_mask!r}")
+    n_r, n_s = r_keys[0].size, s_keys[0].size
+    if max(n_r, n_s) > 0xFFFFFFFF:
+        raise ValueError(f"{fn}: a relation of more than 2^32 - 1 rows")
+    r_cols = _table_columns(fn, "R", r_cols, n_r)
+    s_cols = _table_columns(fn, "S", s_cols, n_s)
+    step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
+    rows = _TableRows(how, r_cols, s_cols, n_r, step)
+    trivial = rows.without_device(n_s)
+    if trivial is not None:
+        return trivial
+    pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
+    s_sweep = _ON_S_SWEEP.get(rows.kind)
+    dev = {}
+
+    def hash_keys(ctx, held, d_tuples, lo, n):
+        """R's key columns go up whole, a slice's into the room kept for one; either is hashed where it lies"""
+        if lo is None:
+            dev["r"] = [held.put(k) for k in r_keys]
+            dev["s"] = [held.alloc(step * w) for w in widths]
+            dev["r_marks"] = held.put(np.zeros((n_r + 31) // 32, dtype=np.uint32))
+            dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))
+            dev["cols"] = list(zip(dev["s"], dev["r"], widths))
+            ctx.key_hash(dev["cols"], _lib.HJ_KEY_SIDE_R, n, d_tuples, key_mask)
+        else:
+            for d, k in zip(dev["s"], s_keys):
+                ctx.copy_h2d(d, k[lo:lo + n])
+            ctx.key_hash(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, key_mask)
+
+    def verify(ctx, held, lo, n, d_s, d_r, candidates):
+        """the slice's candidates -> its kept pairs and the marks of both sides, then the rows of its kind"""
+        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        capacity = candidates if pairs else 0           # right_semi / right_anti, semi / anti: a mark-only pass
+        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
+        ctx.pairs_verify(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        if pairs:
+            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.verify_info()[1])
+            held.free(d_ks, d_kr)
+        if s_sweep is not None:
+            d_rows = held.alloc(4 * n)
+            ctx.mark_rows(dev["s_marks"], n, lo, s_sweep, d_rows, n)
+            rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
+            held.free(d_rows)
+
+    def r_only(ctx, held):
+        if rows.which is not None:
+            d_rows = held.alloc(4 * n_r)
+            ctx.mark_rows(dev["r_marks"], n_r, 0, rows.which, d_rows, n_r)
+            rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
+
+    # the candidate join is INNER whatever the kind, and the context's own R marks stay out of it: a candidate that the
+    # verify step rejects would have set them
+    _drive_join(r_keys[0], s_keys[0], "radix", _lib.HJ_JOIN_INNER, None, step, verify, device, radixBits=radixBits,
+                fill=hash_keys, after=r_only)
+    return rows.joined()
 
 
 def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):

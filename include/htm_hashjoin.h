@@ -312,6 +312,81 @@ int hj_gather_dev(hj_ctx *ctx, const uint32_t *dMap, uint64_t nRows, uint32_t ro
  * (HJ_NO_ROW entries), out[2] = its device time in microseconds (rounded), out[3] = its out-of-range entries. All 0 before
  * the first one. */
 int hj_gather_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- joins on real key columns: hash, candidate join, verify ----
+ * Every join above matches on one 32-bit word. A key of 64 bits, of several columns or of 16 bytes is joined in three steps:
+ * hj_key_hash_dev hashes the key columns of each row to a 32-bit join word, written as the 8-byte tuple the resident radix
+ * join takes; hj_prj_probe_join_dev(HJ_JOIN_INNER) on those tuples gives CANDIDATE pairs; hj_pairs_verify_dev compares the
+ * real key bytes of every candidate, keeps the equal ones and records which S rows and which R rows took part in a kept
+ * pair in two caller-owned bit planes. hj_mark_rows_dev turns such a plane into rows, and all eight join kinds follow from
+ * the kept pairs and two sweeps. A context's own HJ_FLAG_TRACK_R_MATCHES marks are of no use here: a candidate the
+ * verify step rejects would have set them.
+ * A key column is one element of `width` bytes per row, the S side's and the R side's elements of a column having the
+ * same width; keys are equal when every column is BYTEWISE equal (floats: -0.0 != 0.0, a NaN equals the same bit pattern).
+ *
+ * The hash (a test may restate it): MurmurHash3_x86_32 with seed 0 over the row's key columns in column order. An element
+ * of width 1 or 2 is zero-extended to one 32-bit word; a wider element contributes its little-endian 32-bit words in
+ * order. `len`, the value xored in before the finaliser, is 4 x the number of words. The join word is h & keyMask, keyMask
+ * 0 meaning 0xFFFFFFFF. That is, with h = 0 and for every word k in order:
+ *   k *= 0xcc9e2d51; k = rotl32(k, 15); k *= 0x1b873593; h ^= k; h = rotl32(h, 13); h = h * 5 + 0xe6546b64;
+ * then h ^= len; h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16. (One 4-byte column holding 0
+ * hashes to 0x2362F9DE.) keyMask exists so that tests and users can force collisions: the join's result does not depend
+ * on the hash's quality, only its speed does. */
+#define HJ_KEY_MAX_COLS 4
+typedef struct {
+    const void *s;       /* the S side's column: sRows elements of `width` bytes (NULL where that side is not in use) */
+    const void *r;       /* the R side's column: rRows elements of `width` bytes                                    */
+    uint32_t    width;   /* 1, 2, 4, 8 or 16; the pointer of a side in use aligned to it                             */
+    uint32_t    reserved;/* 0                                                                                         */
+} hj_key_col;            /* 24 bytes */
+#define HJ_KEY_SIDE_S 0u
+#define HJ_KEY_SIDE_R 1u
+/* dOutTuples[i] = (uint64_t)(join word of row i) for i in [0, nRows), from the `side` pointers of cols[0 .. nCols): an
+ * 8-byte tuple as hj_prj_build_dev and hj_prj_probe_join_dev take it. Device pointers; `cols` is host memory and is read
+ * before the call returns. Coalesced loads of every column, one 8-byte store per row, no atomics. Asynchronous on the
+ * context's stream; nRows 0 is a no-op. Needs no hj_reserve, no table and no state; touches no counter and no *_info.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): nCols 0 or above HJ_KEY_MAX_COLS, cols NULL; a width
+ * other than 1, 2, 4, 8, 16; reserved != 0; side > 1; with nRows > 0 a column pointer of the side that is NULL or not
+ * aligned to its width, or dOutTuples NULL; nRows above 2^32 - 1. */
+int hj_key_hash_dev(hj_ctx *ctx, const hj_key_col *cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask,
+                    uint64_t *dOutTuples);
+/* The same function on host pointers: no context, no device (the kernel and this loop share one body). For hosts that
+ * pre-hash, and so that the hash can be tested anywhere. HJ_ERR_INVALID as hj_key_hash_dev. */
+int hj_key_hash_host(const hj_key_col *cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask,
+                     uint64_t *outTuples);
+/* Candidate pairs -> exact pairs. For candidate k in [0, nPairs): s = dMapS[k] - sRowBase, r = dMapR[k] (the planes of an
+ * hj_prj_probe_join_dev(HJ_JOIN_INNER) call with sIdxBase = sRowBase). A candidate whose raw entry is HJ_NO_ROW on either
+ * side, or with s >= sRows or r >= rRows, is never dereferenced: it is dropped and counted apart (hj_verify_info out[3]).
+ * Otherwise the pair is kept iff cols[c].s[s] and cols[c].r[r] are bytewise equal in every column c. Kept pairs go to
+ * dOutS / dOutR under the output contract of hj_probe_pairs_dev: dOutS[j] is the original entry dMapS[k], base included;
+ * the planes fill from 0 without holes; pairs at or beyond `capacity` are counted and not written; the order is
+ * unspecified, the multiset is exact. Every kept pair, written or cut by the capacity, sets bit s of dSMarks and bit r of
+ * dRMarks where those are not NULL: bit i & 31 of 32-bit word i >> 5, words 0 .. ceil(rows / 32) - 1, nothing behind
+ * them. Bits only go 0 -> 1: the caller clears the planes (per S slice, once per R). capacity 0 with NULL outputs is a
+ * mark-only pass. dOutS / dOutR must not alias dMapS / dMapR, each other, or the planes. `cols` is host memory, read
+ * before the call returns. Asynchronous; needs no hj_reserve, no table and no state; touches no counter of hj_result,
+ * hj_pairs_info, hj_r_rows_info or hj_gather_info.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): the column errors of hj_key_hash_dev, for the s pointers
+ * with sRows > 0 and the r pointers with rRows > 0; a map NULL with nPairs > 0; an output NULL with nPairs > 0 and
+ * capacity > 0; nPairs, sRows or rRows above 2^32 - 1. nPairs 0 is a call that kept nothing. */
+int hj_pairs_verify_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMapR, uint64_t nPairs, uint32_t sRowBase,
+                        uint64_t sRows, uint64_t rRows, const hj_key_col *cols, uint32_t nCols, uint32_t *dOutS,
+                        uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
+/* Waits for the stream. About the last hj_pairs_verify_dev: out[0] = pairs kept, out[1] = pairs written (= min(out[0],
+ * capacity)), out[2] = its device time in microseconds (rounded), out[3] = candidates dropped as NULL or out of range.
+ * Rejected candidates = nPairs - out[0] - out[3]. All 0 before the first call. */
+int hj_verify_info(hj_ctx *ctx, uint64_t out[4]);
+/* hj_r_rows_dev on a caller's plane: the rows rowBase + i, i in [0, rows), whose bit i of dMarks is clear (which =
+ * HJ_R_UNMATCHED) or set (HJ_R_MATCHED), ascending, into dOut[0 ..) without holes; rows at or beyond `capacity` are counted
+ * and not written (capacity 0: the count alone). The plane is read, never changed; the sweep's count workspace belongs to
+ * the context and grows with `rows`. Asynchronous; needs no hj_reserve and no state; touches no counter of hj_result,
+ * hj_pairs_info, hj_r_rows_info or hj_gather_info.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): which > 1; dMarks NULL with rows > 0; dOut NULL with
+ * rows > 0 and capacity > 0; rows or rowBase + rows above 2^32 - 1. */
+int hj_mark_rows_dev(hj_ctx *ctx, const uint32_t *dMarks, uint64_t rows, uint32_t rowBase, uint32_t which, uint32_t *dOut,
+                     uint64_t capacity);
+/* Waits for the stream. About the last hj_mark_rows_dev: out[0] = rows produced, out[1] = rows written (= min(out[0],
+ * capacity)), out[2] = its device time in microseconds (rounded), out[3] = its `rows`. All 0 before the first call. */
+int hj_mark_rows_info(hj_ctx *ctx, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
