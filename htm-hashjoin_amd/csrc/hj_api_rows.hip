@@ -1,0 +1,226 @@
+// hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
+// joins on real key columns (hash, verify, sweep of a caller's plane), and the *_info entry point of every call that has
+// a record (hj_host.h: CallRecord). Host-side glue only.
+#include "hj_host.h"
+
+using namespace hjapi;
+
+extern "C" {
+
+// Waits for the stream. The last call of `rec` in the common form of the *_info entry points: out[0] = the first counter word the
+// call left at dWords (`bytes` of them, at most 16: one 32-bit total or two 64-bit words; nullptr: none), out[1] = min(out[0], capacity),
+// out[2] = its device time in microseconds, out[3] = the second word. All 0 for a call that was never made, or forgotten since.
+static int call_info(hj_ctx* c, const CallRecord& rec, const void* dWords, size_t bytes, uint64_t out[4])
+{
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!rec.called) return HJ_OK;
+    unsigned long long words[2] = {0, 0};
+    if (dWords) HJ_HIP(c, hipMemcpy(words, dWords, bytes, hipMemcpyDeviceToHost));
+    float ms = 0;
+    if (!rec.timed || hipEventElapsedTime(&ms, rec.ev[0], rec.ev[1]) != hipSuccess) ms = 0;
+    out[0] = words[0];
+    out[1] = words[0] < rec.capacity ? words[0] : rec.capacity;
+    out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
+    out[3] = words[1];
+    return HJ_OK;
+}
+
+int hj_pairs_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_PAIRS];      // the cursor = rows found; LEFT's unmatched S tuples
+    if (const int rc = call_info(c, r, c->buf[B_PAIRS_CURSOR].p, 16, out)) return rc;
+    // unmatched S tuples of the call: SEMI wrote one row per matched tuple, ANTI one per unmatched one
+    if (r.kind != HJ_JOIN_LEFT) out[3] = r.kind == HJ_JOIN_SEMI ? r.rows - out[0] : r.kind == HJ_JOIN_ANTI ? out[0] : 0;
+    return HJ_OK;
+}
+
+// ---- R-side match marks ---------------------------------------------------
+// what the three calls need: a context reserved with the flag whose plane describes its last build
+static int marks_state(hj_ctx* c, const char* fn)
+{
+    if (!tracks(c)) return fail(c, HJ_ERR_STATE, fn, "context reserved without HJ_FLAG_TRACK_R_MATCHES");
+    if (!c->marks.built) return fail(c, HJ_ERR_STATE, fn, "the last build was not hj_build_dev / hj_prj_build_dev (or there was none)");
+    return HJ_OK;
+}
+
+int hj_r_marks_clear(hj_ctx* c)
+{
+    HJ_ENTER(c, true);
+    if (const int rc = marks_state(c, "hj_r_marks_clear")) return rc;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipMemsetAsync(c->buf[B_R_MARKS].p, 0, marks_bytes(c->marks.rows), c->stream));
+    return HJ_OK;
+}
+
+int hj_r_rows_dev(hj_ctx* c, uint32_t which, uint32_t* dOutR, uint64_t capacity)
+{
+    HJ_ENTER(c, true);
+    if (const int rc = marks_state(c, "hj_r_rows_dev")) return rc;
+    if (which > HJ_R_MATCHED) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: which must be HJ_R_UNMATCHED or HJ_R_MATCHED");
+    if (capacity && !dOutR) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: output pointer NULL with capacity > 0");
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_R_ROWS].ev[0], c->stream));
+    const RMarks mk{c->buf[B_R_MARKS].as<uint32_t>(), (uint32_t)c->marks.base, (uint32_t)c->marks.rows};
+    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOutR, capacity, c->buf[B_R_SWEEP].as<uint32_t>(), c->stream));
+    return call_end(c, CALL_R_ROWS, capacity, c->marks.rows);
+}
+
+int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    if (const int rc = marks_state(c, "hj_r_rows_info")) return rc;
+    // the word behind the block counts: their total after the scan
+    const CallRecord& r = c->call[CALL_R_ROWS];
+    if (const int rc = call_info(c, r, c->buf[B_R_SWEEP].as<uint32_t>() + r_sweep_blocks(c->marks.rows), sizeof(uint32_t), out)) return rc;
+    out[3] = c->marks.rows;                     // also with no hj_r_rows_dev since the build
+    return HJ_OK;
+}
+
+// ---- gather through a row map ----------------------------------------------
+static bool gather_width_ok(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
+// a column's pointer: there, and aligned to the column's width
+static bool col_ptr_ok(const void* p, uint32_t width) { return p && !(reinterpret_cast<uintptr_t>(p) & (width - 1)); }
+
+int hj_gather_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const hj_gather_col* cols,
+                  uint32_t nCols, uint32_t* dValid)
+{
+    HJ_ENTER(c, true);
+    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: more than HJ_GATHER_MAX_COLS columns");
+    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: cols NULL with nCols > 0");
+    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: nRows or srcRows above 2^32 - 1");
+    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: dMap NULL with nRows > 0");
+    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: neither a column nor a validity plane");
+    GatherCols k{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_gather_col& col = cols[i];
+        if (!gather_width_ok(col.width)) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a width that is not 1, 2, 4, 8 or 16");
+        if (col.reserved) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: hj_gather_col.reserved must be 0");
+        if (!col_ptr_ok(col.dst, col.width)) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a dst that is NULL or not aligned to its width");
+        if (srcRows && !col_ptr_ok(col.src, col.width))                               // srcRows 0: src is never read
+            return fail(c, HJ_ERR_INVALID, "hj_gather_dev: a src that is NULL or not aligned to its width");
+        k.col[i] = GatherCol{col.src, col.dst, col.width, 0, {col.fill[0], col.fill[1]}};
+    }
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    unsigned long long* const counts = c->buf[B_GATHER_CTR].as<unsigned long long>();
+    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_GATHER].ev[0], c->stream));
+    HJ_HIP(c, launch_gather(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, c->stream));
+    return call_end(c, CALL_GATHER, 0, nRows);
+}
+
+int hj_gather_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_GATHER];     // NULL rows, out-of-range entries
+    if (const int rc = call_info(c, r, c->buf[B_GATHER_CTR].p, 16, out)) return rc;
+    out[1] = out[0]; out[0] = r.rows;
+    return HJ_OK;
+}
+
+// ---- joins on real key columns: hash, verify, sweep of a caller's plane -----
+// The columns of a call, checked: nCols, widths, reserved, and the pointers of the sides in use (rows > 0 on that side)
+static const char* key_cols_error(const hj_key_col* cols, uint32_t nCols, bool useS, bool useR)
+{
+    if (nCols == 0 || nCols > HJ_KEY_MAX_COLS) return "nCols must be 1 .. HJ_KEY_MAX_COLS";
+    if (!cols) return "cols NULL";
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_key_col& col = cols[i];
+        if (!gather_width_ok(col.width)) return "a width that is not 1, 2, 4, 8 or 16";
+        if (col.reserved) return "hj_key_col.reserved must be 0";
+        if (useS && !col_ptr_ok(col.s, col.width)) return "an S column that is NULL or not aligned to its width";
+        if (useR && !col_ptr_ok(col.r, col.width)) return "an R column that is NULL or not aligned to its width";
+    }
+    return nullptr;
+}
+
+// hj_key_hash_dev's and hj_key_hash_host's arguments -> the kernel's columns; the message of what is wrong, or nullptr
+static const char* key_hash_args(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols* k)
+{
+    if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
+    if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
+    if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
+    if (nRows && !out) return "output pointer NULL with nRows > 0";
+    for (uint32_t i = 0; i < nCols; ++i) { k->p[i] = side == HJ_KEY_SIDE_S ? cols[i].s : cols[i].r; k->width[i] = cols[i].width; }
+    return nullptr;
+}
+
+int hj_key_hash_dev(hj_ctx* c, const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+{
+    HJ_ENTER(c, true);
+    KeyCols k{};
+    if (const char* what = key_hash_args(cols, nCols, side, nRows, dOutTuples, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_key_hash_dev", what);
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, launch_key_hash(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
+    return HJ_OK;
+}
+
+int hj_key_hash_host(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+{
+    KeyCols k{};
+    if (key_hash_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
+    key_hash_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
+    return HJ_OK;
+}
+
+int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                        uint64_t rRows, const hj_key_col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                        uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: nPairs, sRows or rRows above 2^32 - 1");
+    if (const char* what = key_cols_error(cols, nCols, sRows != 0, rRows != 0))
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev", what);
+    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: a map NULL with nPairs > 0");
+    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: an output pointer NULL with capacity > 0");
+    KeyColsSR k{};
+    for (uint32_t i = 0; i < nCols; ++i) { k.s[i] = cols[i].s; k.r[i] = cols[i].r; k.width[i] = cols[i].width; }
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_VERIFY].ev[0], c->stream));
+    HJ_HIP(c, launch_pairs_verify(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
+    return call_end(c, CALL_VERIFY, capacity, nPairs);
+}
+
+int hj_verify_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    return call_info(c, c->call[CALL_VERIFY], c->buf[B_VERIFY_CTR].p, 16, out);     // pairs kept, candidates dropped
+}
+
+int hj_mark_rows_dev(hj_ctx* c, const uint32_t* dMarks, uint64_t rows, uint32_t rowBase, uint32_t which, uint32_t* dOut, uint64_t capacity)
+{
+    HJ_ENTER(c, true);
+    if (which > HJ_R_MATCHED) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: which must be HJ_R_UNMATCHED or HJ_R_MATCHED");
+    if (rows > 0xFFFFFFFFull || (uint64_t)rowBase + rows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: rows or rowBase + rows above 2^32 - 1");
+    if (rows && !dMarks) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: dMarks NULL with rows > 0");
+    if (rows && capacity && !dOut) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: output pointer NULL with capacity > 0");
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (const int rc = c->buf[B_MARK_SWEEP].reserve(c, r_sweep_count_words(rows) * sizeof(uint32_t))) return rc;
+    HJ_HIP(c, hipEventRecord(c->call[CALL_MARK_ROWS].ev[0], c->stream));
+    // the sweep reads the plane and never writes it
+    const RMarks mk{const_cast<uint32_t*>(dMarks), rowBase, (uint32_t)rows};
+    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOut, capacity, c->buf[B_MARK_SWEEP].as<uint32_t>(), c->stream));
+    return call_end(c, CALL_MARK_ROWS, capacity, rows);
+}
+
+int hj_mark_rows_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    // the word behind the block counts: their total after the scan (no block: no row)
+    const CallRecord& r = c->call[CALL_MARK_ROWS];
+    const uint32_t* const total = r.rows ? c->buf[B_MARK_SWEEP].as<uint32_t>() + r_sweep_blocks(r.rows) : nullptr;
+    if (const int rc = call_info(c, r, total, sizeof(uint32_t), out)) return rc;
+    out[3] = r.rows;
+    return HJ_OK;
+}
+
+}  // extern "C"

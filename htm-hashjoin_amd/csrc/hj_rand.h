@@ -1,5 +1,5 @@
 // hj_rand.h -- glibc's rand() stream and the Zipf tables built from it, shared by the host generators
-// (hj_datagen.cpp) and the streaming device generator (hj_api.hip: hj_zipf_open / hj_zipf_next_dev). Host code only.
+// (hj_datagen.cpp) and the streaming device generator (hj_api_tools.hip: hj_zipf_open / hj_zipf_next_dev). Host code only.
 #pragma once
 
 #include <cmath>
