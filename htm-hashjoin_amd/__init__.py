@@ -13,5 +13,5 @@ from ._lib import (  # noqa: F401
 from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
     outer_join_pairs, radix_outer_join_pairs, join_tables, join_on, key_hash_host,
-    generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
+    generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )

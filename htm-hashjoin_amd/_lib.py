@@ -157,6 +157,8 @@ def _declare(lib):
         "hj_table_debug": ([vp, P(u64)], i32),
         "hj_htm_chain_layout_info": ([vp, u32, u64, P(u64)], i32),
         "hj_htm_chain_info": ([vp, P(u64)], i32),
+        "hj_own_layout_info": ([vp, u32, u64, P(u64)], i32),
+        "hj_own_info": ([vp, vp, u64, vp, u64, P(u64)], i32),
         "hj_zipf_open": ([vp, u64, C.c_double, C.c_uint], i32),
         "hj_zipf_next_dev": ([vp, u64, vp], i32),
         "hj_zipf_close": ([vp], i32),

@@ -174,7 +174,11 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         size_t qb = wave_queue_bytes(rSize, c->nCU), cb = wave_conflict_bytes(rSize, c->nCU);
         if (own && own_queue_bytes(rSize) > qb) qb = own_queue_bytes(rSize);
         if (own && own_conflict_bytes(rSize, c->nCU) > cb) cb = own_conflict_bytes(rSize, c->nCU);
-        return reserve_all(c, {{B_TABLE, (4 * nb + kTableSlack) * sizeof(uint64_t)}, {B_OWNER, own ? own_owner_bytes(4 * nb) : 0},
+        bool ownerReplaced = false;                 // hj_own_info: the owner words of the last window build are gone
+        int rc = c->buf[B_OWNER].reserve(c, own ? own_owner_bytes(4 * nb) : 0, &ownerReplaced);
+        if (ownerReplaced) c->op.ownN = 0;
+        if (rc) return rc;
+        return reserve_all(c, {{B_TABLE, (4 * nb + kTableSlack) * sizeof(uint64_t)},
                                {B_HTM_OWN_COUNTS, own ? own_conflict_count_bytes(rSize, c->nCU) : 0}, {B_QUEUE, qb}, {B_HTM_CONFLICTS, cb},
                                {B_HTM_OVF_COUNT, nb * sizeof(unsigned int)}, {B_HTM_OVF_BASE, nb * sizeof(uint32_t)},
                                {B_HTM_SCAN, scan_workspace_words(nb) * sizeof(uint32_t)}});
@@ -188,7 +192,10 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         // 1/8 headroom: a radix shard may receive slightly more than its nominal share (hj_build_keys_dev)
         size_t qb = own_queue_bytes(rSize + rSize / 8);
         if (wave_queue_bytes(rSize + rSize / 8, c->nCU) > qb) qb = wave_queue_bytes(rSize + rSize / 8, c->nCU);
-        if (own_supported(2 * rSize) && (rc = c->buf[B_OWNER].reserve(c, own_owner_bytes(2 * rSize)))) return rc;
+        bool ownerReplaced = false;                 // hj_own_info: the owner words of the last window build are gone
+        if (own_supported(2 * rSize)) rc = c->buf[B_OWNER].reserve(c, own_owner_bytes(2 * rSize), &ownerReplaced);
+        if (ownerReplaced) c->op.ownN = 0;
+        if (rc) return rc;
         if ((rc = c->buf[B_QUEUE].reserve(c, qb))) return rc;
     }
     return HJ_OK;

@@ -97,8 +97,10 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
                 HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveMain, kWaveCompact, bracket(c, EV_KC0)));
             HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 3}, kWaveMain, classicMode, bracket(c, EV_KW0)));
         }
-        if (enqOwn)
+        if (enqOwn) {
+            c->op.ownN = n; c->op.ownGated = true;
             HJ_HIP(c, launch_build_own(job, own, Gate{word, 2}, 1, bracket(c, EV_KO0)));
+        }
         if (enqWave) {
             if (enqCompact)
                 HJ_HIP(c, launch_build_wave(job, wave, Gate{word, 4}, kWaveTail, kWaveCompact));
@@ -125,6 +127,7 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
         HJ_HIP(c, launch_build_wave(job, wave, Gate{nullptr, 0}, kWavePre | kWaveMain, classicMode, bracket(c, EV_KW0)));
         HJ_HIP(c, classic_tail(Gate{nullptr, 0}));
     } else if (variant == 2) {
+        c->op.ownN = n;
         if ((rc = record(c, EV_BUILD0))) return rc;
         HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
     } else {
@@ -187,6 +190,7 @@ static int build_htm(hj_ctx* c, const uint64_t* dR, uint64_t rSize, uint64_t idx
     const uint32_t nParts = sl.nChunks * htm_chain_parts(sl.sliceLen);
     const bool ldsChains = variant == 3 && !genericChains && htm_chain_tries(sl.nChunks, sl.sliceLen, nb);
     if (variant == 2) {
+        c->op.ownN = rSize;
         if ((rc = record(c, EV_BUILD0))) return rc;
         const OwnBufs own{c->buf[B_OWNER].p, c->buf[B_QUEUE].p, c->buf[B_QUEUE_COUNT].as<uint32_t>(), htmConflicts, ownCounts};
         HJ_HIP(c, launch_build_own(job, own, Gate{nullptr, 0}, 3, bracket(c, EV_KO0)));
@@ -465,6 +469,35 @@ int hj_wave_seams(hj_ctx* c, uint32_t* starts, uint32_t* bounds, uint32_t* pcoun
     HJ_HIP(c, hipMemcpy(starts, w.starts, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HJ_HIP(c, hipMemcpy(bounds, w.bounds, (chunks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (pcounts) HJ_HIP(c, hipMemcpy(pcounts, w.pcounts, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HJ_OK;
+}
+
+int hj_own_layout_info(const hj_ctx* c, uint32_t computeUnits, uint64_t n, uint64_t out[16])
+{
+    if (!out || (!c && (computeUnits == 0 || computeUnits > 65536)) || n == 0 || n > 0xFFFFFFFFull) return HJ_ERR_INVALID;
+    const int nCU = c ? c->nCU : (int)computeUnits;
+    const OwnLayout w = own_layout(n, nCU);
+    const uint64_t v[16] = {w.chunkLen, w.nChunks, w.tileTuples, w.blockSlots, w.winBlocks, w.backBlocks, w.seamDivisor, w.minTableSlots,
+                            w.deferredParts, w.maxProbeLen, (uint64_t)nCU, 0, 0, 0, 0, 0};
+    memcpy(out, v, sizeof v);
+    return HJ_OK;
+}
+
+int hj_own_info(hj_ctx* c, uint32_t* owner, uint64_t ownerCapacity, uint32_t* deferCounts, uint64_t countsCapacity, uint64_t out[4])
+{
+    HJ_ENTER(c, owner && deferCounts && out);
+    const char* const notRun = "hj_own_info: the last build did not run the workgroup-window build";
+    if (!c->op.built || !c->op.ownN) return fail(c, HJ_ERR_STATE, notRun);
+    if (const int rc = read_counters(c, false)) return rc;
+    // buildVariant 0: its kernels were enqueued behind the device's pick and ran only if that pick was the window
+    if (c->op.ownGated && c->hCtr->variant != 2) return fail(c, HJ_ERR_STATE, notRun);
+    const OwnLayout w = own_layout(c->op.ownN, c->nCU);
+    const uint64_t blocks = c->op.tableSize / w.blockSlots, chunks = w.nChunks;
+    out[0] = blocks; out[1] = chunks; out[2] = 0; out[3] = 0;
+    if (ownerCapacity < blocks || countsCapacity < chunks) return fail(c, HJ_ERR_INVALID, "hj_own_info: capacity below the number of blocks / chunks");
+    HJ_HIP(c, hipMemcpy(owner, c->buf[B_OWNER].p, blocks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HJ_HIP(c, hipMemcpy(deferCounts, c->buf[B_QUEUE_COUNT].p, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < chunks; ++i) out[2] += deferCounts[i];
     return HJ_OK;
 }
 

@@ -51,6 +51,12 @@ constexpr uint32_t kBlkSlots = 1u << kBlkShift;  // 512 slots = 4 KiB
 constexpr uint32_t kWinBlocks = 16;
 constexpr uint32_t kWinSlots = kBlkSlots * kWinBlocks;   // 8192 slots = 64 KiB
 constexpr uint32_t kBackBlocks = 2;              // window keeps this much room behind a tile's lowest key
+constexpr int kOwnPer = 6;                       // tuples per thread and build tile
+constexpr int kOwnBuildTile = kOwnThreads * kOwnPer;   // tuples per BUILD tile of k_build_own (3072; why not kOwnTile: see there)
+constexpr uint32_t kSeamDiv = 4;                 // seam tiles claim a block only if it holds >= 1/kSeamDiv of the fullest one's tuples
+// The largest probeLength the valid range is right for (reported by hj_own_layout_info, enforced nowhere): a walk (phase B's too) must end at most one block past the block it
+// starts in -- k_finalize_range makes blocks [lo, hi + 1] the stored range and the straddle flag wants ONE next block.
+constexpr uint32_t kOwnMaxProbeLen = kBlkSlots + 1;
 
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_umin(v); }      // DPP steps (hj_device.h), not LDS permutes
 
@@ -221,8 +227,8 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
     // slides and barriers per tuple; tiles of 2048: +5 % there, little more gained beyond). For the bucketised table, whose
     // keys spread 4/3 as wide (four slots per three keys), it is what makes W = 2^10 fit at all: 4.8 % of the tuples
     // deferred with tiles of 4096, 0.25 % with 3072 (build 1.58 -> 1.03 ms).
-    constexpr int PER = 6;
-    constexpr int TILE = kOwnThreads * PER, SPAN = 64 * PER;
+    constexpr int PER = kOwnPer;
+    constexpr int TILE = kOwnBuildTile, SPAN = 64 * PER;
     // tile t covers chunk offsets [t*TILE, ...); this thread's tuple j sits at offset
     // t*TILE + wave*SPAN + 64 j + lane
     const uint32_t tOff = wave * SPAN + lane;
@@ -343,7 +349,7 @@ k_build_own(const void* __restrict__ Rv, uint64_t n, uint64_t chunkLen,
             for (int off = 8; off > 0; off >>= 1) { const uint32_t o = __shfl_xor(mx, off, 64); mx = o > mx ? o : mx; }
             if (t < kWinBlocks) {
                 need[t] = 0;
-                if (c && (c >= 0x10000u || c * 4 >= mx) && owned[t] == 0) {
+                if (c && (c >= 0x10000u || c * kSeamDiv >= mx) && owned[t] == 0) {
                     const uint32_t blk = wb + ((t - wb) & (kWinBlocks - 1));   // ring position -> block in [wb, wb+K)
                     owned[t] = (blk < numBlocks && atomicCAS(&owner[blk], 0u, me) == 0u) ? 1u : 2u;
                     if (owned[t] == 1u) { usedLo = blk < usedLo ? blk : usedLo; usedHi1 = blk + 1 > usedHi1 ? blk + 1 : usedHi1; }
@@ -715,6 +721,8 @@ hipError_t own_set_attributes()
     return hipSuccess;
 }
 
+// phase B: workgroups per slice of the deferred queue (about 4096 in all: the walks are chains of dependent global atomics)
+static uint32_t own_deferred_parts(uint64_t nChunks) { return nChunks >= 4096 ? 1u : (uint32_t)(4096 / nChunks); }
 // chunk geometry of the workgroup-window build
 struct OwnGeometry { uint64_t nChunks, chunkLen; };
 static OwnGeometry own_geometry(uint64_t n, int nCU)
@@ -726,6 +734,13 @@ static OwnGeometry own_geometry(uint64_t n, int nCU)
     chunkLen = (chunkLen + kOwnTile - 1) / kOwnTile * kOwnTile;
     if (chunkLen < (uint64_t)kOwnTile * 4) chunkLen = (uint64_t)kOwnTile * 4;
     return OwnGeometry{(n + chunkLen - 1) / chunkLen, chunkLen};
+}
+// What hj_own_layout_info reports: the chunk geometry and the kernel's own constants
+OwnLayout own_layout(uint64_t n, int nCU)
+{
+    const OwnGeometry g = own_geometry(n, nCU);
+    return OwnLayout{g.chunkLen, g.nChunks, (uint64_t)kOwnBuildTile, kBlkSlots, kWinBlocks, kBackBlocks, kSeamDiv, kWinSlots,
+                     own_deferred_parts(g.nChunks), kOwnMaxProbeLen};
 }
 // htm: the conflict list of the window build = one slice per chunk + a last slice for the deferred phase's conflicts
 WaveSlices own_conflict_layout(uint64_t n, int nCU, void* countsBuf)
@@ -770,8 +785,8 @@ hipError_t launch_build_own(const BuildJob& j, const OwnBufs& buf, Gate gate, in
     hipLaunchKernelGGL(k_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, numBlocks, j.tableSize, gate);
     hipLaunchKernelGGL(k_clear_unowned, dim3(2048), dim3(kBlock), 0, j.s, j.table,
                        static_cast<const unsigned int*>(buf.owner), j.ctr, numBlocks, j.tableSize, gate);
-    // phase B: `parts` workgroups per slice (about 4096 in all: the walks are chains of dependent global atomics)
-    const uint32_t defParts = nChunks >= 4096 ? 1u : (uint32_t)(4096 / nChunks);
+    // phase B: `parts` workgroups per slice
+    const uint32_t defParts = own_deferred_parts(nChunks);
     const dim3 gDef((unsigned)(nChunks * defParts));
     if (htm)
         hipLaunchKernelGGL(k_build_deferred<true>, gDef, dim3(kBlock), 0, j.s, static_cast<const DeferredEntry*>(buf.queue), buf.deferCounts,

@@ -342,6 +342,10 @@ hipError_t own_set_attributes();          // per device, at hj_create
 struct OwnBufs { void* owner; void* queue; uint32_t* deferCounts; uint64_t* htmConflicts = nullptr; uint32_t* htmCounts = nullptr; };
 hipError_t launch_build_own(const BuildJob& job, const OwnBufs& buf, Gate gate, int parts, KernelEvents kev = {});   // parts: 1 = phase A (kev brackets its kernel), 2 = the rest, 3 = both
 constexpr uint32_t kOwnMaxChunks = 8192;
+// The window build's chunk geometry for n tuples on nCU compute units and its kernels' constants (own_layout: what
+// hj_own_layout_info reports; the launcher takes the same geometry and the same phase-B parts)
+struct OwnLayout { uint64_t chunkLen, nChunks, tileTuples, blockSlots, winBlocks, backBlocks, seamDivisor, minTableSlots, deferredParts, maxProbeLen; };
+OwnLayout own_layout(uint64_t n, int nCU);
 
 // ---- wavefront-private build (defined in hj_build_wave.hip) ------------------
 // geometry the locality sampler (k_sample_locality) needs to predict what k_build_wave would defer

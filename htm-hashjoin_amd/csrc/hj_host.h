@@ -92,6 +92,10 @@ struct hj_ctx {
         // it was gated on the variant the device picked
         uint64_t wavePreN = 0;
         bool wavePreGated = false;
+        // the workgroup-window build (hj_own_info): tuples it cut into chunks (0: it was not enqueued, or hj_reserve has
+        // replaced the owner table since), and whether it was gated on the variant the device picked
+        uint64_t ownN = 0;
+        bool ownGated = false;
     } op;
     // ---- the bucketised table of --algo htm (hj_htm.hip; 4 slots per bucket in buf[B_TABLE]). Reset by begin_operation.
     struct Htm {

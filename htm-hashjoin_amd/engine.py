@@ -100,6 +100,25 @@ def htm_chain_layout_info(n, compute_units):
     return _htm_chain_layout(None, int(compute_units), n)
 
 
+_OWN_LAYOUT_FIELDS = ("chunkLen", "nChunks", "tileTuples", "blockSlots", "windowBlocks", "backBlocks", "seamDivisor",
+                      "minTableSlots", "deferredParts", "maxProbeLength", "computeUnits")
+
+
+def _own_layout(handle, compute_units, n):
+    out = (C.c_uint64 * 16)()
+    rc = lib.hj_own_layout_info(handle, compute_units, n, out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, f"hj_own_layout_info(n={n}, computeUnits={compute_units})")
+    return {k: int(out[i]) for i, k in enumerate(_OWN_LAYOUT_FIELDS)}
+
+
+def own_layout_info(n, compute_units):
+    """hj_own_layout_info without a context (host-only arithmetic): how the workgroup-window build (buildVariant 2) cuts n
+    tuples into chunks on a device of compute_units compute units, and its kernels' constants (tileTuples, blockSlots,
+    windowBlocks, backBlocks, seamDivisor, minTableSlots, deferredParts, maxProbeLength), as a dict."""
+    return _own_layout(None, int(compute_units), n)
+
+
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
             buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False):
     p = hj_params()
@@ -382,6 +401,23 @@ class HashJoinContext:
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_htm_chain_info(self._h, out))
         return {"state": int(out[0]), "cause": int(out[1]), "groups": int(out[2])}
+
+    def own_layout_info(self, n):
+        """hj_own_layout_info for this context's device (see engine.own_layout_info)."""
+        return _own_layout(self._h, 0, n)
+
+    def own_info(self):
+        """hj_own_info (waits for the stream): what the last workgroup-window build left, as numpy uint32 arrays
+        owner[table blocks] (0, or chunk + 1) and deferCounts[chunks], and the sum of the counts. HJ_ERR_STATE when that
+        build did not run the window build."""
+        out = (C.c_uint64 * 4)()
+        owner, counts = np.empty(1, dtype=np.uint32), np.empty(1, dtype=np.uint32)
+        rc = lib.hj_own_info(self._h, owner.ctypes.data, owner.size, counts.ctypes.data, counts.size, out)
+        if rc == _lib.HJ_ERR_INVALID and (out[0] > owner.size or out[1] > counts.size):
+            owner, counts = np.empty(int(out[0]), dtype=np.uint32), np.empty(int(out[1]), dtype=np.uint32)
+            rc = lib.hj_own_info(self._h, owner.ctypes.data, owner.size, counts.ctypes.data, counts.size, out)
+        self._check(rc)
+        return owner[:int(out[0])], counts[:int(out[1])], int(out[2])
 
     def synchronize(self):
         self._check(lib.hj_synchronize(self._h))

@@ -567,6 +567,31 @@ int hj_htm_chain_layout_info(const hj_ctx *ctx, uint32_t computeUnits, uint64_t 
  * parts asked for when the phase held (= hj_result.htmOverflowBuckets), else 0. out[3] = 0.
  * HJ_ERR_STATE: no htm table. */
 int hj_htm_chain_info(hj_ctx *ctx, uint64_t out[4]);
+/* Planning facts of the workgroup-window build (buildVariant 2, also under HJ_ALGO_HTM), the counterpart of
+ * hj_wave_layout_info, for 0 < n < 2^32 tuples, reported from the kernel's own constants. ctx == NULL: host-only arithmetic
+ * for a device of `computeUnits` compute units; otherwise the context's device, and computeUnits is ignored.
+ * out[0] = chunk length in tuples (chunk c = positions [c * out[0], (c + 1) * out[0]) of the input, one workgroup each),
+ * out[1] = chunks, out[2] = tuples per build tile, out[3] = slots per table block (the unit of ownership), out[4] = blocks
+ * per LDS window, out[5] = blocks the window keeps behind a tile's lowest home block, out[6] = the seam-tile divisor (in a
+ * chunk's first and last tile a block is claimed only if it holds at least 1/out[6] of what the tile's fullest block
+ * holds), out[7] = slots of the smallest table the build takes (one window; below it buildVariant 2 becomes 1), out[8] =
+ * workgroups per chunk's slice of the deferred queue in the deferred phase, out[9] = the largest probeLength for which
+ * the build's valid slot range is right (not enforced: hj_reserve and the builds take any probeLength) = out[3] + 1: a
+ * walk, the deferred phase's included, must end at most one block past the block it starts in, because the valid slot
+ * range is "the blocks claimed or deferred into, plus one" and a walk that straddles a block end asks for one next block,
+ * out[10] = compute units used, out[11..15] = 0.
+ * HJ_ERR_INVALID: out NULL, n == 0 or n > 2^32 - 1, no context and computeUnits 0. */
+int hj_own_layout_info(const hj_ctx *ctx, uint32_t computeUnits, uint64_t n, uint64_t out[16]);
+/* What the last workgroup-window build left (waits for the stream; changes nothing; for tests): owner[b] = 0 when nobody
+ * claimed table block b, else (chunk + 1) of the workgroup that did, for the out[0] blocks of the table; deferCounts[c] =
+ * tuples chunk c's workgroup handed to the deferred phase, for the out[1] chunks; out[2] = their sum (=
+ * hj_result.buildDeferred), out[3] = 0. ownerCapacity / countsCapacity = entries the arrays have room for; out[0] and
+ * out[1] are set whenever the call gets as far as knowing them. HJ_ERR_STATE: the last build on this context did not run
+ * the window build (no build, a radix join, buildVariant 1, 3, 4, or buildVariant 0 picking one of them), or hj_reserve
+ * has replaced the owner table since -- the only call between two builds that touches what is reported here.
+ * HJ_ERR_INVALID: a NULL argument, or a capacity below out[0] / out[1]. */
+int hj_own_info(hj_ctx *ctx, uint32_t *owner, uint64_t ownerCapacity, uint32_t *deferCounts, uint64_t countsCapacity,
+                uint64_t out[4]);
 
 /* ---- device memory for hosts without a HIP runtime of their own ----------- */
 int hj_dev_alloc(hj_ctx *ctx, uint64_t bytes, void **dptr);
