@@ -240,14 +240,16 @@ __device__ __forceinline__ Window load_window(uint32_t key, const uint64_t* __re
     return w;
 }
 
+// live = false: the element can match nothing whatever its home slot (a tuple with payload bits set)
 struct WindowK { uint32_t a, b, c, d; uint32_t key; bool ok; };
 __device__ __forceinline__ WindowK load_window_keys(uint32_t key, const uint32_t* __restrict__ keys, uint64_t mask,
-                                                    uint32_t hshift, uint64_t validLo, uint64_t validHiEx, uint64_t dummy)
+                                                    uint32_t hshift, uint64_t validLo, uint64_t validHiEx, uint64_t dummy,
+                                                    bool live = true)
 {
     WindowK w;
     w.key = key;
     const uint64_t home = home_slot(key, hshift, mask);
-    w.ok = home >= validLo && home < validHiEx;
+    w.ok = live && home >= validLo && home < validHiEx;
     const uint32_t* p = keys + (w.ok ? home : dummy);
     w.a = p[0]; w.b = p[1]; w.c = p[2]; w.d = p[3];
     return w;
@@ -271,10 +273,12 @@ __device__ __forceinline__ uint32_t count_window(const Window& w)
 }
 
 // 16-byte loads over the aligned body (2 tuples or 4 keys per lane), the few elements before and after
-// it by one thread. Tuples: two windows one after the other -- that version already runs at the chip's
-// read-stream rate (6.1-6.35 TB/s), and batching its loads made it slower. Keys: four windows per lane,
-// which one after the other meant five dependent round trips per iteration (4.2 TB/s); their eight loads are
-// issued together.
+// it by one thread. Keys: four windows per lane, which one after the other meant five dependent round trips per
+// iteration (4.2 TB/s); their eight loads are issued together. Tuples on 4-byte keys: the two windows are issued
+// together as well, the payload test folded into the window's `ok` (2.34 -> 2.23 ms at 2^30; requesting the next S
+// vector before the windows are counted, or four tuples per lane, gained nothing on top: profiles/probe_inflight.md).
+// Tuples on 8-byte slots: two windows one after the other -- twice the bytes per window, already at the chip's
+// read-stream rate (6.4-6.5 TB/s), and batching those loads measured slower again.
 template <bool KEY32, bool COMPACT>
 __device__ __forceinline__ void probe_body(const void* __restrict__ Sv, uint64_t n, const uint64_t* __restrict__ table, uint64_t mask,
                                            uint32_t hshift, uint32_t probeLen, ShardCheck sc, Counters* __restrict__ ctr)
@@ -327,8 +331,14 @@ __device__ __forceinline__ void probe_body(const void* __restrict__ Sv, uint64_t
         } else {
             foreign += (uint32_t)is_foreign(t.x, sc) + (uint32_t)is_foreign(t.z, sc);
             if constexpr (COMPACT) {
-                matches += probe_one_keys(((uint64_t)t.y << 32) | t.x, keys, mask, hshift, probeLen, validLo, validHiEx);
-                matches += probe_one_keys(((uint64_t)t.w << 32) | t.z, keys, mask, hshift, probeLen, validLo, validHiEx);
+                if (probeLen == 4) {
+                    const WindowK w0 = load_window_keys(t.x, keys, mask, hshift, validLo, validHiEx, dummy, t.y == 0);
+                    const WindowK w1 = load_window_keys(t.z, keys, mask, hshift, validLo, validHiEx, dummy, t.w == 0);
+                    matches += count_window_keys(w0) + count_window_keys(w1);
+                } else {
+                    matches += probe_one_keys(((uint64_t)t.y << 32) | t.x, keys, mask, hshift, probeLen, validLo, validHiEx);
+                    matches += probe_one_keys(((uint64_t)t.w << 32) | t.z, keys, mask, hshift, probeLen, validLo, validHiEx);
+                }
             } else {
                 matches += probe_one(((uint64_t)t.y << 32) | t.x, table, mask, hshift, probeLen, validLo, validHiEx);
                 matches += probe_one(((uint64_t)t.w << 32) | t.z, table, mask, hshift, probeLen, validLo, validHiEx);
