@@ -42,6 +42,8 @@ HJ_GATHER_MAX_COLS = 8
 # hj_key_hash_dev / hj_pairs_verify_dev: key columns of one call, and which side's pointers the hash reads
 HJ_KEY_MAX_COLS = 4
 HJ_KEY_SIDE_S, HJ_KEY_SIDE_R = 0, 1
+# hj_key_col2.flags: in this column a NULL equals a NULL
+HJ_KEY_NULLS_EQUAL = 0x1
 
 
 class hj_params(C.Structure):
@@ -99,6 +101,19 @@ class hj_key_col(C.Structure):
     ]
 
 
+class hj_key_col2(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p),
+        ("r", C.c_void_p),
+        ("sOffsets", C.c_void_p),
+        ("rOffsets", C.c_void_p),
+        ("sValid", C.c_void_p),
+        ("rValid", C.c_void_p),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
 def _declare(lib):
     vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
     P = C.POINTER
@@ -127,6 +142,9 @@ def _declare(lib):
         "hj_key_hash_host": ([P(hj_key_col), u32, u32, u64, u32, vp], i32),
         "hj_pairs_verify_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col), u32, vp, vp, u64, vp, vp], i32),
         "hj_verify_info": ([vp, P(u64)], i32),
+        "hj_key_hash2_dev": ([vp, P(hj_key_col2), u32, u32, u64, u32, vp], i32),
+        "hj_key_hash2_host": ([P(hj_key_col2), u32, u32, u64, u32, vp], i32),
+        "hj_pairs_verify2_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col2), u32, vp, vp, u64, vp, vp], i32),
         "hj_mark_rows_dev": ([vp, vp, u64, u32, u32, vp, u64], i32),
         "hj_mark_rows_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),

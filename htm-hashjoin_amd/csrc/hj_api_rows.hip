@@ -189,6 +189,87 @@ int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR,
     return call_end(c, CALL_VERIFY, capacity, nPairs);
 }
 
+// ---- the same on key columns in the Arrow layout (hj_key_col2) --------------
+static bool word_ptr_ok(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 3u); }     // NULL passes: the pointer is optional
+
+// The hj_key_col2 columns of a call, checked like key_cols_error checks hj_key_col's, and what the descriptor adds
+static const char* key_cols2_error(const hj_key_col2* cols, uint32_t nCols, bool useS, bool useR)
+{
+    if (nCols == 0 || nCols > HJ_KEY_MAX_COLS) return "nCols must be 1 .. HJ_KEY_MAX_COLS";
+    if (!cols) return "cols NULL";
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_key_col2& col = cols[i];
+        if (col.width && !gather_width_ok(col.width)) return "a width that is not 0, 1, 2, 4, 8 or 16";
+        if (col.flags & ~HJ_KEY_NULLS_EQUAL) return "hj_key_col2.flags has bits other than HJ_KEY_NULLS_EQUAL";
+        if (col.width && (col.sOffsets || col.rOffsets)) return "offsets on a column whose width is not 0";
+        if (!word_ptr_ok(col.sOffsets) || !word_ptr_ok(col.rOffsets) || !word_ptr_ok(col.sValid) || !word_ptr_ok(col.rValid))
+            return "an offsets or validity pointer that is not 4-byte aligned";
+        const uint32_t align = col.width ? col.width : 1u;            // a bytes buffer may start anywhere
+        if (useS && !col_ptr_ok(col.s, align)) return "an S column that is NULL or not aligned to its width";
+        if (useR && !col_ptr_ok(col.r, align)) return "an R column that is NULL or not aligned to its width";
+        if (!col.width && ((useS && !col.sOffsets) || (useR && !col.rOffsets))) return "width 0 without offsets on a side in use";
+    }
+    return nullptr;
+}
+
+static const char* key_hash2_args(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols2* k)
+{
+    if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
+    if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
+    if (const char* what = key_cols2_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
+    if (nRows && !out) return "output pointer NULL with nRows > 0";
+    const bool S = side == HJ_KEY_SIDE_S;
+    for (uint32_t i = 0; i < nCols; ++i) {
+        k->p[i] = S ? cols[i].s : cols[i].r; k->off[i] = S ? cols[i].sOffsets : cols[i].rOffsets;
+        k->valid[i] = S ? cols[i].sValid : cols[i].rValid; k->width[i] = cols[i].width; k->flags[i] = cols[i].flags;
+    }
+    return nullptr;
+}
+
+int hj_key_hash2_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+{
+    HJ_ENTER(c, true);
+    KeyCols2 k{};
+    if (const char* what = key_hash2_args(cols, nCols, side, nRows, dOutTuples, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_key_hash2_dev", what);
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, launch_key_hash2(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
+    return HJ_OK;
+}
+
+int hj_key_hash2_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+{
+    KeyCols2 k{};
+    if (key_hash2_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
+    key_hash2_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
+    return HJ_OK;
+}
+
+int hj_pairs_verify2_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                         uint64_t rRows, const hj_key_col2* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                         uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: nPairs, sRows or rRows above 2^32 - 1");
+    if (const char* what = key_cols2_error(cols, nCols, sRows != 0, rRows != 0))
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev", what);
+    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: a map NULL with nPairs > 0");
+    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: an output pointer NULL with capacity > 0");
+    KeyCols2SR k{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        k.s[i] = cols[i].s; k.r[i] = cols[i].r; k.sOff[i] = cols[i].sOffsets; k.rOff[i] = cols[i].rOffsets;
+        k.sValid[i] = cols[i].sValid; k.rValid[i] = cols[i].rValid; k.width[i] = cols[i].width; k.flags[i] = cols[i].flags;
+    }
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_VERIFY].ev[0], c->stream));
+    HJ_HIP(c, launch_pairs_verify2(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
+    return call_end(c, CALL_VERIFY, capacity, nPairs);
+}
+
 int hj_verify_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);

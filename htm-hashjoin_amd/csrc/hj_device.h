@@ -705,6 +705,21 @@ void key_hash_host(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t
 hipError_t launch_pairs_verify(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
                                uint32_t rRows, const KeyColsSR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
                                hipStream_t s);
+// The same two steps on key columns in the Arrow layout (hj_key_col2, include/htm_hashjoin.h): per column and side the
+// values (fixed width) or the bytes buffer (width 0), the rows + 1 offsets of a variable-length column (else null) and the
+// validity plane (null: no NULLs); flags: HJ_KEY_NULLS_EQUAL. The hash and the column equality are the header's. nRows is
+// also what bounds the validity words the hash reads: ceil(nRows / 32). The caller has checked what the header says the
+// entry points refuse.
+struct KeyCols2 { const void* p[kKeyMaxCols]; const uint32_t* off[kKeyMaxCols]; const uint32_t* valid[kKeyMaxCols];
+                  uint32_t width[kKeyMaxCols], flags[kKeyMaxCols]; };
+struct KeyCols2SR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; const uint32_t* sOff[kKeyMaxCols]; const uint32_t* rOff[kKeyMaxCols];
+                    const uint32_t* sValid[kKeyMaxCols]; const uint32_t* rValid[kKeyMaxCols]; uint32_t width[kKeyMaxCols], flags[kKeyMaxCols]; };
+constexpr uint32_t kKeyNullsEqual = 1u;       // HJ_KEY_NULLS_EQUAL
+hipError_t launch_key_hash2(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s);
+void key_hash2_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out);   // the same body in a host loop
+hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                                uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                                hipStream_t s);
 
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):

@@ -31,6 +31,10 @@
 // like any other (mark_r_row: a relaxed load first, the OR only while the bit reads clear).
 // What it does NOT do: the candidates are taken in the order the radix join left them, which is by partition; the S side
 // is near-sequential only if that order happens to be, and the R side is a random element read per column.
+//
+// k_key_hash2 / k_pairs_verify2 (hj_key_hash2_dev, hj_pairs_verify2_dev): the same pair on key columns in the Arrow
+// layout -- a validity plane and 32-bit offsets per side, both optional (hj_key_col2). They stand next to the first pair,
+// which stays as it is, share its shapes, its stage and its marks, and are described where they are defined below.
 
 #include "hj_device.h"
 
@@ -144,6 +148,232 @@ __device__ __forceinline__ void verify_col(const void* sCol, const void* rCol, c
     for (uint32_t j = 0; j < kVerifyLanePairs; ++j) live[j] = live[j] && same_bytes<E>(a[j], b[j]);
 }
 
+// ---- key columns in the Arrow layout: validity planes and variable-length elements (k_key_hash2, k_pairs_verify2) -----
+constexpr uint32_t kNullSeed = 0x4E554C4Cu;                           // "NULL": a NULL-keyed row hashes its position, not its columns
+constexpr uint32_t kNullWord = 0xFFFFFFFFu;                           // what a NULL contributes in a HJ_KEY_NULLS_EQUAL column
+
+// Word w of a variable-length element, as the hash mixes it and the verify step compares it: its bytes [4w, 4w + 4),
+// little-endian, zero behind its end. On the host they are read one by one.
+__host__ __device__ __forceinline__ uint32_t var_tail_mask(uint32_t len, uint32_t w)
+{
+    const uint32_t rem = len - 4u * w;                                // > 0: w < ceil(len / 4)
+    return rem < 4u ? (1u << (8u * rem)) - 1u : 0xFFFFFFFFu;
+}
+__host__ __forceinline__ uint32_t var_word_host(const uint8_t* e, uint32_t len, uint32_t w)
+{
+    uint32_t k = 0;
+    for (uint32_t b = 0; b < 4u && 4u * w + b < len; ++b) k |= (uint32_t)e[4u * w + b] << (8u * b);
+    return k;
+}
+__host__ __device__ __forceinline__ uint32_t var_words_of(uint32_t len) { return len / 4u + ((len & 3u) ? 1u : 0u); }
+
+// On the device the words of ONE element are walked in order through the ALIGNED 32-bit words that hold it: the word that
+// holds its first byte up to the one that holds its last, nothing outside them (the header's promise), whatever the
+// alignment of the buffer and of the element in it. Word w of the element is a byte-align of the aligned words w and
+// w + 1, so every aligned word is loaded once and carried: var_fetch is the load of one step, var_word the arithmetic.
+struct VarWords {
+    const uint32_t* a;                                                // the aligned word that holds the first byte
+    uint32_t sh, last, cur;                                           // the first byte's place in it; the aligned word of the last byte; aligned word w
+};
+template <bool NT> __device__ __forceinline__ uint32_t var_load(const uint32_t* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+template <bool NT>
+__device__ __forceinline__ VarWords var_begin(const void* bytes, uint32_t o0, uint32_t len)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(bytes) + o0;
+    VarWords v;
+    v.a = reinterpret_cast<const uint32_t*>(a0 & ~(uintptr_t)3);
+    v.sh = (uint32_t)(a0 & 3u);
+    v.last = len ? (uint32_t)(((uint64_t)v.sh + len - 1u) >> 2) : 0u;
+    v.cur = len ? var_load<NT>(v.a) : 0u;                             // an empty element reads nothing
+    return v;
+}
+// the aligned word behind the one carried, where the element reaches into it (on: the element has a word w at all)
+template <bool NT>
+__device__ __forceinline__ uint32_t var_fetch(const VarWords& v, uint32_t w, bool on) { return on && w + 1u <= v.last ? var_load<NT>(v.a + w + 1u) : 0u; }
+__device__ __forceinline__ uint32_t var_word(VarWords& v, uint32_t nxt, uint32_t len, uint32_t w)
+{
+    const uint32_t k = __builtin_amdgcn_alignbyte(nxt, v.cur, v.sh);  // ({nxt, cur} >> 8 * sh): a misaligned start costs no byte loads
+    v.cur = nxt;
+    return k & var_tail_mask(len, w);
+}
+
+// The validity bits of K rows of one plane. Host: the word of the row, shifted. Device (k_key_hash2's rows: a wavefront
+// owns 256 consecutive ones from a multiple of 256, the lane's K = 4 rows 64 apart): the wavefront's eight words are read
+// ONCE, by its lanes 0 .. 7 in one load, and handed round -- a word per 32 rows, not a load per row. A word at or behind
+// ceil(nRows / 32) is not read and counts as 0: rows behind the end, which store nothing.
+template <int K>
+__host__ __device__ __forceinline__ void key_valid_bits(const uint32_t* plane, const uint64_t (&at)[K], uint64_t nRows, bool (&ok)[K])
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint64_t w0 = (at[0] - lane) >> 5, nWords = (nRows + 31u) >> 5;
+    uint32_t mine = 0;
+    if (lane < 2u * K && w0 + lane < nWords) mine = __builtin_nontemporal_load(plane + w0 + lane);
+#pragma unroll
+    for (int j = 0; j < K; ++j) ok[j] = (__shfl(mine, 2 * j + (int)(lane >> 5)) >> (lane & 31u)) & 1u;
+#else
+    (void)nRows;
+    for (int j = 0; j < K; ++j) ok[j] = (plane[at[j] >> 5] >> (at[j] & 31u)) & 1u;
+#endif
+}
+
+// One variable-length column of K rows into their running hashes: the K (off[i], off[i + 1]) pairs first, straight, then
+// per valid row the length and its words; a NULL row (ok false) mixes nothing here and reads no byte. The device loop
+// runs to the lane's own longest element: each step loads the next aligned word of every row that still has words, all
+// of them before the first mix.
+template <int K>
+__host__ __device__ __forceinline__ void key_mix_varlen(const void* bytes, const uint32_t* off, const uint64_t (&row)[K], const bool (&ok)[K],
+                                                        uint32_t (&h)[K], uint32_t (&words)[K])
+{
+    uint32_t o0[K], o1[K], len[K], nW[K], maxW = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) { o0[j] = __builtin_nontemporal_load(off + row[j]); o1[j] = __builtin_nontemporal_load(off + row[j] + 1); }
+#ifdef __HIP_DEVICE_COMPILE__
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        len[j] = ok[j] ? o1[j] - o0[j] : 0u;
+        nW[j] = var_words_of(len[j]);
+        if (ok[j]) { h[j] = mm3_mix(h[j], len[j]); words[j] += 1u + nW[j]; }
+        maxW = nW[j] > maxW ? nW[j] : maxW;
+    }
+#ifdef __HIP_DEVICE_COMPILE__
+    VarWords v[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) v[j] = var_begin<true>(bytes, o0[j], len[j]);
+    for (uint32_t w = 0; w < maxW; ++w) {
+        uint32_t nxt[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) nxt[j] = var_fetch<true>(v[j], w, w < nW[j]);
+        __builtin_amdgcn_sched_barrier(0);                            // the K loads of a step are in flight together
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (w < nW[j]) h[j] = mm3_mix(h[j], var_word(v[j], nxt[j], len[j], w));
+    }
+#else
+    (void)maxW;
+    for (int j = 0; j < K; ++j)
+        for (uint32_t w = 0; w < nW[j]; ++w) h[j] = mm3_mix(h[j], var_word_host(static_cast<const uint8_t*>(bytes) + o0[j], len[j], w));
+#endif
+}
+
+// key_hash_rows on Arrow columns. row: the rows read (behind the end: the last one); at: their positions in the call,
+// which pick the validity bit and are the word of a NULL-keyed row. A column without a plane and without offsets takes
+// key_hash_rows' own path: the same tuples, and nothing per row that the old kernel does not do. kVar false: no column
+// has offsets (the caller looked), and the word loop with its registers is not compiled in.
+template <int K, bool kVar>
+__host__ __device__ __forceinline__ void key_hash2_rows(const KeyCols2& cols, uint32_t nCols, const uint64_t (&row)[K], const uint64_t (&at)[K],
+                                                        uint64_t nRows, uint32_t mask, uint32_t (&word)[K])
+{
+    uint32_t h[K], words[K];
+    bool nullKey[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { h[j] = 0; words[j] = 0; nullKey[j] = false; }
+#pragma unroll
+    for (uint32_t c = 0; c < kKeyMaxCols; ++c) {
+        if (c >= nCols) continue;
+        bool ok[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) ok[j] = true;
+        if (cols.valid[c]) key_valid_bits<K>(cols.valid[c], at, nRows, ok);
+        if (kVar && cols.off[c]) {
+            key_mix_varlen<K>(cols.p[c], cols.off[c], row, ok, h, words);
+        } else {
+            uint32_t t[K];                                            // a NULL's element is read (it exists) and its mix thrown away
+#pragma unroll
+            for (int j = 0; j < K; ++j) t[j] = h[j];
+            switch (cols.width[c]) {
+                case 1: key_mix_col<1, K>(cols.p[c], row, t); break;
+                case 2: key_mix_col<2, K>(cols.p[c], row, t); break;
+                case 4: key_mix_col<4, K>(cols.p[c], row, t); break;
+                case 8: key_mix_col<8, K>(cols.p[c], row, t); break;
+                default: key_mix_col<16, K>(cols.p[c], row, t); break;
+            }
+            const uint32_t n = cols.width[c] <= 4 ? 1u : cols.width[c] / 4u;
+#pragma unroll
+            for (int j = 0; j < K; ++j) { h[j] = ok[j] ? t[j] : h[j]; words[j] += ok[j] ? n : 0u; }
+        }
+        if (cols.valid[c]) {
+            const bool nullsEqual = (cols.flags[c] & kKeyNullsEqual) != 0u;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (ok[j]) continue;
+                if (nullsEqual) { h[j] = mm3_mix(h[j], kNullWord); words[j] += 1u; }
+                else nullKey[j] = true;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        word[j] = (nullKey[j] ? mm3_final(mm3_mix(kNullSeed, (uint32_t)at[j]), 4u) : mm3_final(h[j], 4u * words[j])) & mask;
+}
+
+// verify_col on an Arrow column of fixed width: the validity words of both sides are loaded beside the eight elements
+// (null plane: all valid), everything before the first compare. Either element NULL: equal iff both are and nullsEqual.
+template <int W>
+__device__ __forceinline__ void verify_col2(const void* sCol, const void* rCol, const uint32_t* sValid, const uint32_t* rValid, bool nullsEqual,
+                                            const uint32_t (&si)[kVerifyLanePairs], const uint32_t (&ri)[kVerifyLanePairs],
+                                            bool (&live)[kVerifyLanePairs])
+{
+    using E = KeyElem<W>;
+    E a[kVerifyLanePairs], b[kVerifyLanePairs];
+    uint32_t vs[kVerifyLanePairs], vr[kVerifyLanePairs];
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) {
+        const bool okS = (vs[j] >> (si[j] & 31u)) & 1u, okR = (vr[j] >> (ri[j] & 31u)) & 1u;
+        live[j] = live[j] && ((okS && okR) ? same_bytes<E>(a[j], b[j]) : (!okS && !okR && nullsEqual));
+    }
+}
+
+// A variable-length column of the lane's candidates. The lengths go first: four offsets and two validity words per
+// candidate, all in flight together; NULLs and a length mismatch are settled from them without touching a byte. Then the
+// words, while the candidate is live and words remain: per step one aligned word per side and live candidate, all loaded
+// before the first compare. A candidate that is dropped, rejected or NULL has no words and reads no byte.
+__device__ __forceinline__ void verify_varlen(const void* sBytes, const void* rBytes, const uint32_t* sOff, const uint32_t* rOff,
+                                              const uint32_t* sValid, const uint32_t* rValid, bool nullsEqual,
+                                              const uint32_t (&si)[kVerifyLanePairs], const uint32_t (&ri)[kVerifyLanePairs],
+                                              bool (&live)[kVerifyLanePairs])
+{
+    uint32_t so0[kVerifyLanePairs], so1[kVerifyLanePairs], ro0[kVerifyLanePairs], ro1[kVerifyLanePairs];
+    uint32_t vs[kVerifyLanePairs], vr[kVerifyLanePairs], len[kVerifyLanePairs], nW[kVerifyLanePairs];
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) {
+        so0[j] = sOff[si[j]]; so1[j] = sOff[si[j] + 1u]; ro0[j] = rOff[ri[j]]; ro1[j] = rOff[ri[j] + 1u];
+        vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    VarWords a[kVerifyLanePairs], b[kVerifyLanePairs];
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) {
+        const bool okS = (vs[j] >> (si[j] & 31u)) & 1u, okR = (vr[j] >> (ri[j] & 31u)) & 1u, both = okS && okR;
+        const uint32_t ls = so1[j] - so0[j], lr = ro1[j] - ro0[j];
+        live[j] = live[j] && (both ? ls == lr : (!okS && !okR && nullsEqual));
+        len[j] = live[j] && both ? ls : 0u;
+        nW[j] = var_words_of(len[j]);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { a[j] = var_begin<false>(sBytes, so0[j], len[j]); b[j] = var_begin<false>(rBytes, ro0[j], len[j]); }
+    for (uint32_t w = 0;; ++w) {
+        bool go[kVerifyLanePairs], any = false;
+#pragma unroll
+        for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { go[j] = live[j] && w < nW[j]; any = any || go[j]; }
+        if (!any) break;
+        uint32_t na[kVerifyLanePairs], nb[kVerifyLanePairs];
+#pragma unroll
+        for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { na[j] = var_fetch<false>(a[j], w, go[j]); nb[j] = var_fetch<false>(b[j], w, go[j]); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (uint32_t j = 0; j < kVerifyLanePairs; ++j)
+            if (go[j]) live[j] = var_word(a[j], na[j], len[j], w) == var_word(b[j], nb[j], len[j], w);
+    }
+}
+
 }  // namespace
 
 __global__ void __launch_bounds__(kBlock)
@@ -234,6 +464,144 @@ k_pairs_verify(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ m
     if (kept == 0) return;                                            // workgroup-uniform
     stage_flush<kInner>(st, out);                                     // the claim, both planes, R's marks
     mark_plane<kBlock>(st.s, kept, sMarks);                           // the stage is still as it was flushed
+}
+
+// k_key_hash on Arrow columns (hj_key_col2): the same shape, the same store. What it adds per column: with a validity
+// plane, one load of the wavefront's eight words and a shuffle; with offsets, the lane's four offset pairs and a word
+// loop over aligned words to the lane's own longest element (key_mix_varlen). No LDS allocation, no atomics.
+// What it does NOT do: the word loop waits for a step's loads before it mixes them (the other wavefronts cover that),
+// and a wavefront runs as long as its longest element. Two instances: the launch picks kVar = false when no column has
+// offsets, so that fixed-width columns do not pay for the word loop's registers.
+template <bool kVar>
+__global__ void __launch_bounds__(kBlock)
+k_key_hash2(KeyCols2 cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* __restrict__ out)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kHashBlockRows + w * (kHashLaneRows * kWave) + lane;     // the lane's first row
+    uint64_t row[kHashLaneRows], at[kHashLaneRows];
+    uint32_t word[kHashLaneRows];
+#pragma unroll
+    for (uint32_t j = 0; j < kHashLaneRows; ++j) {
+        at[j] = i0 + j * kWave;
+        row[j] = at[j] < nRows ? at[j] : nRows - 1;                   // a row behind the end reads the last one and stores nothing
+    }
+    key_hash2_rows<(int)kHashLaneRows, kVar>(cols, nCols, row, at, nRows, mask, word);
+#pragma unroll
+    for (uint32_t j = 0; j < kHashLaneRows; ++j)
+        if (at[j] < nRows) out[at[j]] = (uint64_t)word[j];
+}
+
+// k_pairs_verify on Arrow columns (hj_key_col2): the same shape, the same single stage flush, the same marks; the columns
+// go through verify_col2 / verify_varlen. sValid and sOff are indexed by the S row with the base off, like the column.
+// Three instances, so that a call pays in registers only for what its columns have; the launch looks and picks kForm:
+// 0 = fixed columns without a validity plane (k_pairs_verify's work on the new descriptor), 1 = fixed columns, some with
+// a plane, 2 = some variable-length column (the word loop and its cursors).
+template <int kForm>
+__global__ void __launch_bounds__(kBlock)
+k_pairs_verify2(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                uint32_t rRows, KeyCols2SR cols, uint32_t nCols, PairsOutMarked out, RMarks sMarks)
+{
+    __shared__ uint32_t ldsS[kVerifyBlockPairs], ldsR[kVerifyBlockPairs], ldsTot[2 * kVerifyWaves], ldsDrop[kVerifyWaves];
+    __shared__ unsigned long long ldsBase;
+    PairStage<kBlock> st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
+    const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    const uint64_t k0 = (uint64_t)blockIdx.x * kVerifyBlockPairs + w * kVerifyWavePairs + lane;   // the lane's first candidate
+
+    uint32_t es[kVerifyLanePairs], er[kVerifyLanePairs];
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) {
+        const uint64_t k = k0 + j * kVerifyStepPairs;
+        es[j] = er[j] = kNoRow;
+        if (k < nPairs) { es[j] = __builtin_nontemporal_load(mapS + k); er[j] = __builtin_nontemporal_load(mapR + k); }
+    }
+
+    uint32_t si[kVerifyLanePairs], ri[kVerifyLanePairs];
+    bool live[kVerifyLanePairs];
+    uint32_t nDrop = 0;                                               // of this wavefront (ballots: the same in every lane)
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) {
+        const bool in = k0 + j * kVerifyStepPairs < nPairs;
+        si[j] = es[j] - sRowBase; ri[j] = er[j];
+        live[j] = in && es[j] != kNoRow && er[j] != kNoRow && si[j] < sRows && ri[j] < rRows;     // the raw entries: whatever the base
+        nDrop += (uint32_t)__popcll(__ballot(in && !live[j]));
+    }
+    if (lane == 0) ldsDrop[w] = nDrop;                                // read behind stage_reserve's barrier
+
+    if (sRows && rRows) {
+        // a dropped candidate reads, and ignores, one of the first rows (its offsets and validity too: they exist)
+        const uint32_t spareS = threadIdx.x < sRows ? threadIdx.x : sRows - 1u, spareR = threadIdx.x < rRows ? threadIdx.x : rRows - 1u;
+#pragma unroll
+        for (uint32_t j = 0; j < kVerifyLanePairs; ++j) { si[j] = live[j] ? si[j] : spareS; ri[j] = live[j] ? ri[j] : spareR; }
+#pragma unroll
+        for (uint32_t c = 0; c < kKeyMaxCols; ++c) {
+            if (c >= nCols) continue;                                 // kernel arguments: uniform
+            const bool ne = (cols.flags[c] & kKeyNullsEqual) != 0u;
+            const uint32_t *vs = kForm ? cols.sValid[c] : nullptr, *vr = kForm ? cols.rValid[c] : nullptr;
+            switch (cols.width[c]) {
+                case 0: if constexpr (kForm == 2) verify_varlen(cols.s[c], cols.r[c], cols.sOff[c], cols.rOff[c], vs, vr, ne, si, ri, live); break;
+                case 1: verify_col2<1>(cols.s[c], cols.r[c], vs, vr, ne, si, ri, live); break;
+                case 2: verify_col2<2>(cols.s[c], cols.r[c], vs, vr, ne, si, ri, live); break;
+                case 4: verify_col2<4>(cols.s[c], cols.r[c], vs, vr, ne, si, ri, live); break;
+                case 8: verify_col2<8>(cols.s[c], cols.r[c], vs, vr, ne, si, ri, live); break;
+                default: verify_col2<16>(cols.s[c], cols.r[c], vs, vr, ne, si, ri, live); break;
+            }
+        }
+    }
+
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j) m += (uint32_t)live[j];
+    bool any;
+    uint32_t pos = stage_reserve<kInner>(st, out, m, false, any);     // never flushes: the stage was empty and takes every candidate
+#pragma unroll
+    for (uint32_t j = 0; j < kVerifyLanePairs; ++j)
+        if (live[j]) { st.s[pos] = es[j]; st.r[pos] = er[j]; ++pos; }
+    if (threadIdx.x == 0) {
+        uint32_t d = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kVerifyWaves; ++i) d += ldsDrop[i];
+        if (d) atomicAdd(out.cursor + 1, (unsigned long long)d);
+    }
+    const uint32_t kept = st.fill;                                    // the same in every thread
+    if (kept == 0) return;                                            // workgroup-uniform
+    stage_flush<kInner>(st, out);                                     // the claim, both planes, R's marks
+    mark_plane<kBlock>(st.s, kept, sMarks);                           // the stage is still as it was flushed
+}
+
+hipError_t launch_key_hash2(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s)
+{
+    if (nRows == 0) return hipSuccess;
+    const dim3 grid((uint32_t)((nRows + kHashBlockRows - 1) / kHashBlockRows));               // nRows <= 2^32 - 1: <= 2^22 workgroups
+    bool var = false;
+    for (uint32_t c = 0; c < nCols; ++c) var = var || cols.off[c];
+    if (var) hipLaunchKernelGGL(k_key_hash2<true>, grid, dim3(kBlock), 0, s, cols, nCols, nRows, mask, out);
+    else hipLaunchKernelGGL(k_key_hash2<false>, grid, dim3(kBlock), 0, s, cols, nCols, nRows, mask, out);
+    return hipGetLastError();
+}
+
+void key_hash2_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out)
+{
+    for (uint64_t i = 0; i < nRows; ++i) {
+        const uint64_t row[1] = {i};
+        uint32_t word[1];
+        key_hash2_rows<1, true>(cols, nCols, row, row, nRows, mask, word);
+        out[i] = (uint64_t)word[0];
+    }
+}
+
+hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                                uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                                hipStream_t s)
+{
+    if (nPairs == 0) return hipSuccess;
+    const RMarks mkS{sMarks, sRowBase, sMarks ? sRows : 0u}, mkR{rMarks, 0u, rMarks ? rRows : 0u};
+    const PairsOutMarked o = pairs_out_of<true>(out, &mkR);
+    const dim3 grid((uint32_t)((nPairs + kVerifyBlockPairs - 1) / kVerifyBlockPairs));        // nPairs <= 2^32 - 1: <= 2^22 workgroups
+    int form = 0;
+    for (uint32_t c = 0; c < nCols; ++c) form = cols.width[c] == 0u ? 2 : form ? form : (cols.sValid[c] || cols.rValid[c]) ? 1 : 0;
+    const auto kernel = form == 2 ? k_pairs_verify2<2> : form == 1 ? k_pairs_verify2<1> : k_pairs_verify2<0>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, o, mkS);
+    return hipGetLastError();
 }
 
 hipError_t launch_key_hash(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s)

@@ -142,6 +142,17 @@ def _key_cols(cols):
     return arr, len(cols)
 
 
+def _key_cols2(cols):
+    """[(s_ptr, r_ptr, width, s_offsets, r_offsets, s_valid, r_valid, flags)], whatever follows the width optional (0)
+    -> (hj_key_col2 array, its length)"""
+    cols = [tuple(c) + (0,) * (8 - len(c)) for c in cols]
+    arr = (_lib.hj_key_col2 * max(len(cols), 1))()
+    for c, (s, r, width, s_off, r_off, s_valid, r_valid, flags) in zip(arr, cols):
+        c.s, c.r, c.sOffsets, c.rOffsets, c.sValid, c.rValid = (p or None for p in (s, r, s_off, r_off, s_valid, r_valid))
+        c.width, c.flags = width, flags
+    return arr, len(cols)
+
+
 class HashJoinContext:
     """One engine context bound to one GPU (hj_ctx). ``stream`` is a raw hipStream_t
     handle (e.g. torch.cuda.current_stream().cuda_stream); None = private stream."""
@@ -285,6 +296,28 @@ class HashJoinContext:
         p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
         self._check(lib.hj_pairs_verify_dev(self._h, p(d_map_s), p(d_map_r), n_pairs, s_row_base, s_rows, r_rows, arr, n,
                                             p(d_out_s), p(d_out_r), capacity, p(d_s_marks), p(d_r_marks)))
+
+    def key_hash2(self, cols, side, n_rows, d_out, key_mask=0):
+        """hj_key_hash2_dev: key_hash on key columns in the Arrow layout. cols = 1 to HJ_KEY_MAX_COLS tuples (s_ptr,
+        r_ptr, width, s_offsets, r_offsets, s_valid, r_valid, flags) of device pointers, whatever follows the width
+        optional (0). A fixed column has width 1, 2, 4, 8 or 16 and no offsets; a variable-length one width 0, the bytes
+        buffer as its pointer and n_rows + 1 uint32 offsets into it. s_valid / r_valid: the validity plane of that side
+        (uint32 words, bit i & 31 of word i >> 5, 1 = valid; 0: no NULLs). flags: HJ_KEY_NULLS_EQUAL or 0. The hash and
+        the word of a NULL-keyed row: include/htm_hashjoin.h. Asynchronous; needs no reserve and no table."""
+        arr, n = _key_cols2(cols)
+        self._check(lib.hj_key_hash2_dev(self._h, arr, n, side, n_rows, key_mask, C.c_void_p(d_out) if d_out else None))
+
+    def pairs_verify2(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, cols, d_out_s, d_out_r, capacity,
+                      d_s_marks=0, d_r_marks=0):
+        """hj_pairs_verify2_dev: pairs_verify on key columns in the Arrow layout (cols as in key_hash2, both sides of
+        every column in use; the S side's offsets and validity are indexed by the S row with s_row_base off, like its
+        column). A column is equal when -- either element NULL: both are and the column has HJ_KEY_NULLS_EQUAL;
+        otherwise fixed width: bytewise; otherwise: the same length and the same bytes. Outputs, marks, dropped
+        candidates and aliasing as in pairs_verify; verify_info reports the last call of either."""
+        arr, n = _key_cols2(cols)
+        p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
+        self._check(lib.hj_pairs_verify2_dev(self._h, p(d_map_s), p(d_map_r), n_pairs, s_row_base, s_rows, r_rows, arr, n,
+                                             p(d_out_s), p(d_out_r), capacity, p(d_s_marks), p(d_r_marks)))
 
     def verify_info(self):
         """hj_verify_info (waits for the stream): (pairs the last pairs_verify kept, pairs it wrote, its device time in
@@ -1051,6 +1084,226 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     # verify step rejects would have set them
     _drive_join(r_keys[0], s_keys[0], "radix", _lib.HJ_JOIN_INNER, None, step, verify, device, radixBits=radixBits,
                 fill=hash_keys, after=r_only)
+    return rows.joined()
+
+
+# ---- key columns in the Arrow layout: NULL keys and variable-length (string) keys ------------------------------------------
+class KeyColumn:
+    """One key column of join_on_columns / key_hash2_host in the Arrow layout: the values, an optional validity and, for
+    variable-length elements, 32-bit offsets.
+    KeyColumn(values, valid=None): a fixed-width column, values a 1-D numpy array of 1, 2, 4, 8 or 16-byte elements. A
+    numpy.ma.MaskedArray brings its validity along (its mask inverted).
+    KeyColumn.varlen(offsets, data, valid=None): element i is the bytes data[offsets[i]:offsets[i + 1]] (Arrow Binary /
+    Utf8: len(offsets) = rows + 1, non-decreasing, offsets[0] need not be 0).
+    KeyColumn.from_list(items): a variable-length column out of bytes, str (as UTF-8) and None (NULL).
+    valid: one bool per row, False = NULL -- what join_tables / join_on return as s_valid / r_valid; None: no NULLs. The
+    values under a NULL are never compared. nulls_equal: in this column a NULL equals a NULL (HJ_KEY_NULLS_EQUAL); it is
+    what key_hash2_host goes by. The flag belongs to the column of the JOIN, not to one side of it: join_on_columns sets
+    it for column c when its own nulls_equal argument, R's column c or S's column c asks for it.
+    ValueError for offsets that decrease or end behind the data, data above 2^32 - 1 bytes, and lengths that disagree."""
+
+    def __init__(self, values, valid=None, nulls_equal=False):
+        if isinstance(values, np.ma.MaskedArray):
+            if valid is not None:
+                raise ValueError("KeyColumn: a masked array brings its own validity")
+            values, valid = np.ma.getdata(values), ~np.ma.getmaskarray(values)
+        a = np.asarray(values)
+        if a.ndim != 1:
+            raise ValueError(f"KeyColumn: values must be 1-D, not shape {a.shape}")
+        if a.dtype.hasobject or a.dtype.itemsize not in _GATHER_WIDTHS:
+            raise ValueError(f"KeyColumn: {a.dtype} elements; 1, 2, 4, 8 or 16 bytes can be joined on (strings: KeyColumn.from_list)")
+        self.values, self.offsets, self.width, self.rows = _aligned(np.ascontiguousarray(a)), None, a.dtype.itemsize, a.shape[0]
+        self.valid, self.nulls_equal = self._validity(valid, self.rows), bool(nulls_equal)
+
+    @classmethod
+    def varlen(cls, offsets, data, valid=None, nulls_equal=False):
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError("KeyColumn.varlen: offsets must be a 1-D integer array of rows + 1 entries")
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data)
+        if data.ndim != 1 or data.dtype.itemsize != 1:
+            raise ValueError("KeyColumn.varlen: data must be bytes or a 1-D array of 1-byte elements")
+        if data.size > 0xFFFFFFFF:
+            raise ValueError("KeyColumn.varlen: more than 2^32 - 1 bytes of data")
+        wide = off.astype(np.int64) if off.dtype != np.uint64 else off
+        if (wide[1:] < wide[:-1]).any() or int(wide[0]) < 0:
+            raise ValueError("KeyColumn.varlen: offsets must be non-negative and non-decreasing")
+        if int(wide[-1]) > data.size:
+            raise ValueError(f"KeyColumn.varlen: offsets end at {int(wide[-1])}, behind the {data.size} bytes of data")
+        self = cls.__new__(cls)
+        self.values, self.offsets = np.ascontiguousarray(data).view(np.uint8), np.ascontiguousarray(off, dtype=np.uint32)
+        self.width, self.rows = 0, off.size - 1
+        self.valid, self.nulls_equal = cls._validity(valid, self.rows), bool(nulls_equal)
+        return self
+
+    @classmethod
+    def from_list(cls, items, nulls_equal=False):
+        items = list(items)
+        raw = []
+        for x in items:
+            if not (x is None or isinstance(x, (bytes, str))):
+                raise ValueError(f"KeyColumn.from_list: bytes, str or None, not {type(x).__name__}")
+            raw.append(b"" if x is None else x.encode("utf-8") if isinstance(x, str) else x)
+        off = np.zeros(len(raw) + 1, dtype=np.int64)
+        np.cumsum(np.array([len(b) for b in raw], dtype=np.int64), out=off[1:])
+        valid = np.array([x is not None for x in items], dtype=bool)
+        return cls.varlen(off, b"".join(raw), None if valid.all() else valid, nulls_equal)
+
+    @staticmethod
+    def _validity(valid, rows):
+        if valid is None:
+            return None
+        v = np.asarray(valid)
+        if v.dtype != np.bool_ or v.shape != (rows,):
+            raise ValueError(f"KeyColumn: valid must be {rows} bools, not {v.dtype} of shape {v.shape}")
+        return np.ascontiguousarray(v)
+
+    def __len__(self):
+        return self.rows
+
+    def take(self, lo, n):
+        """rows [lo, lo + n) as the C ABI takes a column: (values or bytes, offsets rebased to those bytes or None, the
+        validity bits repacked from bit 0 as uint32 words or None)"""
+        words = None
+        if self.valid is not None:
+            bits = np.packbits(self.valid[lo:lo + n], bitorder="little")
+            words = np.zeros((n + 31) // 32 or 1, dtype=np.uint32)
+            words.view(np.uint8)[:bits.size] = bits
+        if self.offsets is None:
+            return self.values[lo:lo + n], None, words
+        off = self.offsets[lo:lo + n + 1]
+        return self.values[int(off[0]):int(off[-1])], off - off[0], words
+
+
+def _as_key_columns(fn, side, keys):
+    """the key columns of one side as a list of KeyColumn of one length; ValueError for what cannot be joined on"""
+    cols = [keys] if isinstance(keys, (KeyColumn, np.ndarray)) else list(keys)
+    if not 1 <= len(cols) <= _lib.HJ_KEY_MAX_COLS:
+        raise ValueError(f"{fn}: {side} has {len(cols)} key columns; 1 to {_lib.HJ_KEY_MAX_COLS} can be joined on")
+    cols = [c if isinstance(c, KeyColumn) else KeyColumn(c) for c in cols]
+    if any(c.rows != cols[0].rows for c in cols):
+        raise ValueError(f"{fn}: the key columns of {side} have {[c.rows for c in cols]} rows")
+    return cols
+
+
+def key_hash2_host(cols, key_mask=0):
+    """hj_key_hash2_host: key_hash_host on key columns in the Arrow layout -- cols is one KeyColumn (or plain / masked 1-D
+    numpy array) or a sequence of 1 to HJ_KEY_MAX_COLS of them. Returns the join words as a numpy uint64 array, the tuples
+    HashJoinContext.key_hash2 writes for the same columns on the device. A row with a NULL in a column that is not
+    nulls_equal is NULL-keyed: its word is a hash of its position, not of its columns (include/htm_hashjoin.h). Needs no
+    device."""
+    cols = _as_key_columns("key_hash2_host", "cols", cols)
+    if not 0 <= int(key_mask) <= 0xFFFFFFFF:
+        raise ValueError(f"key_hash2_host: key_mask must fit 32 bits, not {key_mask!r}")
+    n = cols[0].rows
+    out = np.empty(n, dtype=np.uint64)
+    held = [c.take(0, n) for c in cols]
+    ptr = lambda a: a.ctypes.data if a is not None else 0       # noqa: E731
+    arr, k = _key_cols2([(ptr(v), 0, c.width, ptr(off), 0, ptr(words), 0, _lib.HJ_KEY_NULLS_EQUAL if c.nulls_equal else 0)
+                         for c, (v, off, words) in zip(cols, held)])
+    rc = lib.hj_key_hash2_host(arr, k, _lib.HJ_KEY_SIDE_S, n, int(key_mask), out.ctypes.data)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_key_hash2_host")
+    return out
+
+
+def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
+                    device=0, key_mask=0):
+    """join_on for key columns that may hold NULLs and variable-length elements (strings): r_keys / s_keys are each one
+    KeyColumn or a sequence of 1 to HJ_KEY_MAX_COLS of them, all of a side of one length; a plain 1-D numpy array stands
+    for KeyColumn(array), a numpy.ma.MaskedArray brings its mask. Column c of both sides is of one kind: fixed with the
+    same itemsize, or variable-length. Two rows match when every column is equal: fixed elements bytewise (as join_on),
+    variable-length ones in length and bytes.
+    NULLs: a row with a NULL in any key column is NULL-keyed and matches nothing, not even another NULL (SQL's =). A
+    NULL-keyed S row is an unmatched S row: it appears in left, full and anti. A NULL-keyed R row is an unmatched R row:
+    it appears in right, full and right_anti. nulls_equal=True sets HJ_KEY_NULLS_EQUAL on every column: a NULL equals a
+    NULL and nothing else (the pandas reading); a column built with nulls_equal=True has it by itself.
+    The method is join_on's with HashJoinContext.key_hash2 / pairs_verify2 in place of key_hash / pairs_verify; per S
+    slice the validity bits are repacked from the slice's first row and the offsets rebased to the slice's own bytes.
+    how, r_cols / s_cols, radixBits, slice_tuples, key_mask, the result dict and the order of its rows: as in join_on."""
+    fn = "join_on_columns"
+    if not isinstance(how, str) or how not in _TABLE_HOWS:
+        raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
+    r_keys, s_keys = _as_key_columns(fn, "R", r_keys), _as_key_columns(fn, "S", s_keys)
+    widths = [c.width for c in r_keys]
+    if widths != [c.width for c in s_keys]:
+        raise ValueError(f"{fn}: the key columns of R have widths {widths} (0: variable-length), those of S {[c.width for c in s_keys]}")
+    if not 0 <= int(key_mask) <= 0xFFFFFFFF:
+        raise ValueError(f"{fn}: key_mask must fit 32 bits, not {key_mask!r}")
+    n_r, n_s = r_keys[0].rows, s_keys[0].rows
+    if max(n_r, n_s) > 0xFFFFFFFF:
+        raise ValueError(f"{fn}: a relation of more than 2^32 - 1 rows")
+    r_cols = _table_columns(fn, "R", r_cols, n_r)
+    s_cols = _table_columns(fn, "S", s_cols, n_s)
+    step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
+    rows = _TableRows(how, r_cols, s_cols, n_r, step)
+    trivial = rows.without_device(n_s)
+    if trivial is not None:
+        return trivial
+    pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
+    s_sweep = _ON_S_SWEEP.get(rows.kind)
+    flags = [_lib.HJ_KEY_NULLS_EQUAL if nulls_equal or r.nulls_equal or s.nulls_equal else 0 for r, s in zip(r_keys, s_keys)]
+    dev = {}
+
+    def s_bytes(c):
+        """the most bytes a slice of S's column c takes"""
+        if c.offsets is None:
+            return step * c.width
+        los = np.arange(0, n_s, step)
+        return int((c.offsets[np.minimum(los + step, n_s)].astype(np.int64) - c.offsets[los]).max())
+
+    def put(ctx, d, a):
+        if a is not None and a.nbytes:
+            ctx.copy_h2d(d, a)
+
+    def hash_keys(ctx, held, d_tuples, lo, n):
+        """R's key columns go up whole, a slice's into the room kept for one; either is hashed where it lies"""
+        if lo is None:
+            def up(a):      # a bytes buffer goes up in whole 32-bit words: the kernels read the aligned words of an element
+                if a is None:
+                    return 0
+                d = held.alloc(a.nbytes + 3 & ~3)
+                put(ctx, d, np.ascontiguousarray(a))
+                return d
+
+            r_dev = [tuple(up(a) for a in c.take(0, n_r)) for c in r_keys]
+            dev["s"] = [(held.alloc(s_bytes(c) + 3 & ~3), held.alloc(4 * (step + 1)) if c.offsets is not None else 0,
+                         held.alloc(4 * ((step + 31) // 32)) if c.valid is not None else 0) for c in s_keys]
+            dev["r_marks"] = held.put(np.zeros((n_r + 31) // 32, dtype=np.uint32))
+            dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))
+            dev["cols"] = [(s[0], r[0], w, s[1], r[1], s[2], r[2], f) for s, r, w, f in zip(dev["s"], r_dev, widths, flags)]
+            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_R, n, d_tuples, key_mask)
+        else:
+            for d, c in zip(dev["s"], s_keys):
+                for d_part, part in zip(d, c.take(lo, n)):
+                    put(ctx, d_part, part)
+            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, key_mask)
+
+    def verify(ctx, held, lo, n, d_s, d_r, candidates):
+        """the slice's candidates -> its kept pairs and the marks of both sides, then the rows of its kind"""
+        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        capacity = candidates if pairs else 0           # right_semi / right_anti, semi / anti: a mark-only pass
+        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
+        ctx.pairs_verify2(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        if pairs:
+            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.verify_info()[1])
+            held.free(d_ks, d_kr)
+        if s_sweep is not None:
+            d_rows = held.alloc(4 * n)
+            ctx.mark_rows(dev["s_marks"], n, lo, s_sweep, d_rows, n)
+            rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
+            held.free(d_rows)
+
+    def r_only(ctx, held):
+        if rows.which is not None:
+            d_rows = held.alloc(4 * n_r)
+            ctx.mark_rows(dev["r_marks"], n_r, 0, rows.which, d_rows, n_r)
+            rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
+
+    # as in join_on: the candidate join is INNER whatever the kind, on tuples made on the device (the two arrays stand for
+    # the relations' lengths alone)
+    _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step, verify, device,
+                radixBits=radixBits, fill=hash_keys, after=r_only)
     return rows.joined()
 
 

@@ -375,6 +375,70 @@ int hj_pairs_verify_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMap
  * capacity)), out[2] = its device time in microseconds (rounded), out[3] = candidates dropped as NULL or out of range.
  * Rejected candidates = nPairs - out[0] - out[3]. All 0 before the first call. */
 int hj_verify_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- key columns in the Arrow layout: NULL keys and variable-length (string) keys ----
+ * hj_key_hash2_dev / hj_key_hash2_host / hj_pairs_verify2_dev are the three calls above on a second column descriptor: a
+ * values buffer, an optional validity plane and an optional 32-bit offsets buffer per side. The candidate join, the
+ * marks, the sweeps, the gather and the eight kinds are untouched. A column's two sides agree in kind: both fixed with
+ * the same width, or both variable-length. An element is NULL when its side has a validity plane and its bit is 0.
+ *
+ * The hash (a test may restate it): the MurmurHash3_x86_32 above, seed 0, over the row's columns in order. A valid fixed
+ * element contributes what it contributes to hj_key_hash_dev. A valid variable-length element of L bytes contributes one
+ * word L, then its bytes as ceil(L / 4) little-endian words, the last one zero-padded. A NULL element of a column with
+ * HJ_KEY_NULLS_EQUAL contributes the single word 0xFFFFFFFF. `len` is 4 x the words mixed for that row. A row is
+ * NULL-KEYED when some column WITHOUT HJ_KEY_NULLS_EQUAL is NULL in it: it can match nothing, and so that such rows do not
+ * pile up on one join word, its word ignores the columns: mm3_final(mm3_mix(0x4E554C4C, (uint32_t)i), 4) & keyMask, i the
+ * row's position in the call, mm3_mix the block step and mm3_final(h, len) the xor of len and the finaliser above. With
+ * no offsets, no validity and flags 0 the tuples are exactly those of hj_key_hash_dev / hj_key_hash_host.
+ *
+ * The verify: for candidate (s, r), column c is equal when -- either element NULL: both are NULL and the column has
+ * HJ_KEY_NULLS_EQUAL; otherwise, fixed width: bytewise; otherwise: same length and the same bytes. The pair is kept when
+ * every column is equal. The bytes of a NULL element are never compared; its offsets are valid offsets (Arrow's rule)
+ * and may be read.
+ *
+ * What is read: of a fixed column, the elements (those under a NULL too: they exist). Of a variable-length element, the
+ * device code may read the aligned 32-bit words that contain its first and its last byte and those between them, and no
+ * byte outside those words; of an empty element nothing. (So up to three bytes in front of the first element and behind
+ * the last are read where the buffer does not start and end on a 4-byte address: device allocations do, or reach
+ * further.) hj_key_hash2_host reads the element's bytes only. */
+#define HJ_KEY_NULLS_EQUAL 0x1u   /* hj_key_col2.flags: in this column a NULL equals a NULL (IS NOT DISTINCT FROM) */
+typedef struct {
+    const void     *s, *r;               /* fixed width: the elements. Variable length: the bytes buffer            */
+    const uint32_t *sOffsets, *rOffsets; /* NULL: fixed width. Else rows + 1 offsets into the bytes buffer (Arrow
+                                            Binary/Utf8 layout): element i = bytes [off[i], off[i+1]); non-decreasing;
+                                            off[0] need not be 0. Caller's contract, not checked on the device       */
+    const uint32_t *sValid, *rValid;     /* NULL: that side has no NULLs. Else the plane hj_gather_dev writes: bit
+                                            i & 31 of 32-bit word i >> 5, 1 = valid                                   */
+    uint32_t width;                      /* 1, 2, 4, 8, 16; 0 for a variable-length column                           */
+    uint32_t flags;                      /* HJ_KEY_NULLS_EQUAL or 0                                                   */
+} hj_key_col2;                           /* 56 bytes */
+/* hj_key_hash_dev on hj_key_col2 columns, from the `side` pointers (values, offsets, validity) of cols[0 .. nCols): the
+ * hash above. Coalesced loads of every fixed column and of the offsets, a validity word read once per 32 rows, one
+ * 8-byte store per row, no atomics. Asynchronous on the context's stream; nRows 0 is a no-op. Needs no hj_reserve, no
+ * table and no state; touches no counter and no *_info. The validity plane of the side holds ceil(nRows / 32) words.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): what hj_key_hash_dev refuses (a width that is neither 0
+ * nor 1, 2, 4, 8, 16; a values pointer of the side that is NULL or, fixed width, not aligned to its width, ...); width 0
+ * without offsets on a side in use; offsets on either side with width != 0; flag bits other than HJ_KEY_NULLS_EQUAL; an
+ * offsets or validity pointer that is not 4-byte aligned. */
+int hj_key_hash2_dev(hj_ctx *ctx, const hj_key_col2 *cols, uint32_t nCols, uint32_t side, uint64_t nRows,
+                     uint32_t keyMask, uint64_t *dOutTuples);
+/* The same function on host pointers: no context, no device (one body, the host reading bytewise). HJ_ERR_INVALID as
+ * hj_key_hash2_dev; a refused call writes nothing. */
+int hj_key_hash2_host(const hj_key_col2 *cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask,
+                      uint64_t *outTuples);
+/* hj_pairs_verify_dev on hj_key_col2 columns, column equality as stated above. Everything else is hj_pairs_verify_dev's,
+ * word for word: a candidate whose raw entry is HJ_NO_ROW on either side, or with s >= sRows or r >= rRows, is never
+ * dereferenced, dropped and counted apart; kept pairs go to dOutS / dOutR under the output contract of
+ * hj_probe_pairs_dev (dOutS[j] the original entry, base included; no holes; pairs at or beyond `capacity` counted and not
+ * written; order unspecified, multiset exact); every kept pair, written or cut, sets bit s of dSMarks and bit r of
+ * dRMarks where those are not NULL, bits only going 0 -> 1; capacity 0 with NULL outputs is a mark-only pass; dOutS /
+ * dOutR must not alias the maps, each other or the planes. sValid / sOffsets are indexed by s (the base is off), so they
+ * hold ceil(sRows / 32) words and sRows + 1 offsets. hj_verify_info reports the last call of either verify entry.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): the column errors of hj_key_hash2_dev, for the s
+ * pointers with sRows > 0 and the r pointers with rRows > 0; a map NULL with nPairs > 0; an output NULL with nPairs > 0
+ * and capacity > 0; nPairs, sRows or rRows above 2^32 - 1. nPairs 0 is a call that kept nothing. */
+int hj_pairs_verify2_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMapR, uint64_t nPairs, uint32_t sRowBase,
+                         uint64_t sRows, uint64_t rRows, const hj_key_col2 *cols, uint32_t nCols, uint32_t *dOutS,
+                         uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
 /* hj_r_rows_dev on a caller's plane: the rows rowBase + i, i in [0, rows), whose bit i of dMarks is clear (which =
  * HJ_R_UNMATCHED) or set (HJ_R_MATCHED), ascending, into dOut[0 ..) without holes; rows at or beyond `capacity` are counted
  * and not written (capacity 0: the count alone). The plane is read, never changed; the sweep's count workspace belongs to
