@@ -8,7 +8,7 @@ from ._lib import (  # noqa: F401
     HJ_OK, HJ_ERR_INVALID, HJ_ERR_NO_DEVICE, HJ_ERR_HIP, HJ_ERR_OOM, HJ_ERR_KEY_RANGE,
     HJ_ERR_UNKNOWN_ALGO, HJ_ERR_STATE, HJ_FLAG_KEEP_ROW_IDS, HJ_FLAG_TRACK_R_MATCHES, HJ_R_UNMATCHED, HJ_R_MATCHED, LIB_PATH, hj_params, hj_result, lib,
     HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI, HJ_NO_ROW, HJ_GATHER_MAX_COLS, hj_gather_col,
-    HJ_KEY_MAX_COLS, HJ_KEY_SIDE_S, HJ_KEY_SIDE_R, hj_key_col, HJ_KEY_NULLS_EQUAL, hj_key_col2,
+    HJ_KEY_MAX_COLS, HJ_KEY_SIDE_S, HJ_KEY_SIDE_R, hj_key_col, HJ_KEY_NULLS_EQUAL, hj_key_col2, hj_gather_col2,
 )
 from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,

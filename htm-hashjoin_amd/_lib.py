@@ -92,6 +92,21 @@ class hj_gather_col(C.Structure):
     ]
 
 
+class hj_gather_col2(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("srcOffsets", C.c_void_p),
+        ("dstOffsets", C.c_void_p),
+        ("srcValid", C.c_void_p),
+        ("dstValid", C.c_void_p),
+        ("dstCapacity", C.c_uint64),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("fill", C.c_uint64 * 2),
+    ]
+
+
 class hj_key_col(C.Structure):
     _fields_ = [
         ("s", C.c_void_p),
@@ -138,6 +153,8 @@ def _declare(lib):
         "hj_r_rows_info": ([vp, P(u64)], i32),
         "hj_gather_dev": ([vp, vp, u64, u32, u64, P(hj_gather_col), u32, vp], i32),
         "hj_gather_info": ([vp, P(u64)], i32),
+        "hj_gather2_dev": ([vp, vp, u64, u32, u64, P(hj_gather_col2), u32, vp], i32),
+        "hj_gather2_info": ([vp, P(u64)], i32),
         "hj_key_hash_dev": ([vp, P(hj_key_col), u32, u32, u64, u32, vp], i32),
         "hj_key_hash_host": ([P(hj_key_col), u32, u32, u64, u32, vp], i32),
         "hj_pairs_verify_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col), u32, vp, vp, u64, vp, vp], i32),

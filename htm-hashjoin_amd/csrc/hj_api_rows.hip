@@ -81,6 +81,7 @@ int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
 
 // ---- gather through a row map ----------------------------------------------
 static bool gather_width_ok(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
+static bool word_ptr_ok(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 3u); }     // NULL passes: the pointer is optional
 // a column's pointer: there, and aligned to the column's width
 static bool col_ptr_ok(const void* p, uint32_t width) { return p && !(reinterpret_cast<uintptr_t>(p) & (width - 1)); }
 
@@ -118,6 +119,81 @@ int hj_gather_info(hj_ctx* c, uint64_t out[4])
     const CallRecord& r = c->call[CALL_GATHER];     // NULL rows, out-of-range entries
     if (const int rc = call_info(c, r, c->buf[B_GATHER_CTR].p, 16, out)) return rc;
     out[1] = out[0]; out[0] = r.rows;
+    return HJ_OK;
+}
+
+// ---- ... on columns in the Arrow layout (hj_gather_col2) ---------------------
+// what hj_gather2_dev refuses of its columns (the message), or nullptr; *k: the columns as the kernels take them
+static const char* gather_cols2_error(const hj_gather_col2* cols, uint32_t nCols, uint64_t nRows, uint64_t srcRows, const uint32_t* dValid,
+                                      GatherCols2* k)
+{
+    // every output range of the call, for the one aliasing rule: a variable-length dst overlaps no other output
+    struct Range { uintptr_t lo, hi; bool bytes; } out[4 * HJ_GATHER_MAX_COLS + 1];
+    uint32_t nOut = 0;
+    const auto add = [&](const void* p, uint64_t bytes, bool isBytes) {
+        if (p && bytes) out[nOut++] = Range{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes, isBytes};
+    };
+    const uint64_t planeBytes = (nRows + 31) / 32 * sizeof(uint32_t);
+    add(dValid, planeBytes, false);
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_gather_col2& col = cols[i];
+        if (col.width && !gather_width_ok(col.width)) return "a width that is not 0, 1, 2, 4, 8 or 16";
+        if (col.flags) return "hj_gather_col2.flags must be 0";
+        if (col.width && (col.srcOffsets || col.dstOffsets)) return "offsets on a column whose width is not 0";
+        if (!col.width && (!col.srcOffsets || !col.dstOffsets)) return "width 0 without srcOffsets or without dstOffsets";
+        if (!word_ptr_ok(col.srcOffsets) || !word_ptr_ok(col.dstOffsets) || !word_ptr_ok(col.srcValid) || !word_ptr_ok(col.dstValid))
+            return "an offsets or validity pointer that is not 4-byte aligned";
+        const uint32_t align = col.width ? col.width : 1u;            // a bytes buffer may start anywhere
+        if (col.width ? !col_ptr_ok(col.dst, align) : (col.dstCapacity && !col.dst)) return "a dst that is NULL or not aligned to its width";
+        if (col.width && col.dstCapacity) return "dstCapacity on a fixed-width column";
+        if (srcRows && !col_ptr_ok(col.src, align)) return "a src that is NULL or not aligned to its width";   // srcRows 0: src is never read
+        k->col[i] = GatherCol2{col.src, col.dst, col.srcOffsets, col.dstOffsets, col.srcValid, col.dstValid, col.dstCapacity, col.width, 0u,
+                               {col.fill[0], col.fill[1]}};
+        add(col.dst, col.width ? nRows * col.width : col.dstCapacity, !col.width);
+        add(col.dstOffsets, (nRows + 1) * sizeof(uint32_t), false);
+        add(col.dstValid, planeBytes, false);
+    }
+    for (uint32_t a = 0; a < nOut; ++a)
+        for (uint32_t b = 0; out[a].bytes && b < nOut; ++b)
+            if (a != b && out[a].lo < out[b].hi && out[b].lo < out[a].hi) return "a variable-length dst that overlaps another output of the call";
+    return nullptr;
+}
+
+int hj_gather2_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const hj_gather_col2* cols,
+                   uint32_t nCols, uint32_t* dValid)
+{
+    HJ_ENTER(c, true);
+    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: more than HJ_GATHER_MAX_COLS columns");
+    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: cols NULL with nCols > 0");
+    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: nRows or srcRows above 2^32 - 1");
+    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: dMap NULL with nRows > 0");
+    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: neither a column nor a validity plane");
+    GatherCols2 k{};
+    if (const char* what = gather_cols2_error(cols, nCols, nRows, srcRows, dValid, &k)) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev", what);
+    if (nRows == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    bool varlen = false;
+    for (uint32_t i = 0; i < nCols; ++i) varlen = varlen || !k.col[i].width;
+    if (varlen)
+        if (const int rc = c->buf[B_GATHER2_WORK].reserve(c, gather2_work_words(nRows) * sizeof(uint32_t))) return rc;
+    unsigned long long* const counts = c->buf[B_GATHER2_CTR].as<unsigned long long>();
+    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_GATHER2].ev[0], c->stream));
+    HJ_HIP(c, launch_gather2(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, counts + 2, c->buf[B_GATHER2_WORK].as<uint32_t>(), c->stream));
+    return call_end(c, CALL_GATHER2, 0, nRows);
+}
+
+int hj_gather2_info(hj_ctx* c, uint64_t out[4 + HJ_GATHER_MAX_COLS])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_GATHER2];
+    for (uint32_t i = 0; i < HJ_GATHER_MAX_COLS; ++i) out[4 + i] = 0;
+    if (const int rc = call_info(c, r, c->buf[B_GATHER2_CTR].p, 16, out)) return rc;
+    out[1] = out[0]; out[0] = r.rows;
+    if (!r.called) { out[0] = 0; return HJ_OK; }
+    unsigned long long totals[HJ_GATHER_MAX_COLS];
+    HJ_HIP(c, hipMemcpy(totals, c->buf[B_GATHER2_CTR].as<unsigned long long>() + 2, sizeof(totals), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < HJ_GATHER_MAX_COLS; ++i) out[4 + i] = totals[i];
     return HJ_OK;
 }
 
@@ -190,7 +266,6 @@ int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR,
 }
 
 // ---- the same on key columns in the Arrow layout (hj_key_col2) --------------
-static bool word_ptr_ok(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 3u); }     // NULL passes: the pointer is optional
 
 // The hj_key_col2 columns of a call, checked like key_cols_error checks hj_key_col's, and what the descriptor adds
 static const char* key_cols2_error(const hj_key_col2* cols, uint32_t nCols, bool useS, bool useR)

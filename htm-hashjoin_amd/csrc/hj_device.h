@@ -687,6 +687,18 @@ struct GatherCols { GatherCol col[kGatherMaxCols]; };
 // has checked widths, alignment and nRows, srcRows <= 2^32 - 1.
 hipError_t launch_gather(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols& cols, uint32_t nCols,
                          uint32_t* valid, unsigned long long* counts, hipStream_t s);
+// The same on columns in the Arrow layout (hj_gather_col2, include/htm_hashjoin.h, field for field; defined in
+// hj_gather_cols.hip): a source validity plane and 32-bit offsets per column, both optional. Columns that are fixed and
+// have neither plane go through launch_gather as they are. work: the context's workspace for the variable-length columns
+// of a call, which run one behind the other -- gather2_work_words(nRows) 32-bit words: the scan's own words, then one
+// 64-bit partial sum per workgroup. totals: kGatherMaxCols 64-bit words, written here (0 for a fixed column): the bytes
+// the rows of column c take. The caller has checked what the header says hj_gather2_dev refuses.
+struct GatherCol2 { const void* src; void* dst; const uint32_t* srcOff; uint32_t* dstOff; const uint32_t* srcValid; uint32_t* dstValid;
+                    uint64_t capacity; uint32_t width, flags; uint64_t fill[2]; };
+struct GatherCols2 { GatherCol2 col[kGatherMaxCols]; };
+size_t gather2_work_words(uint64_t nRows);
+hipError_t launch_gather2(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols2& cols, uint32_t nCols,
+                          uint32_t* valid, unsigned long long* counts, unsigned long long* totals, uint32_t* work, hipStream_t s);
 
 // ---- joins on real key columns (defined in hj_keys.hip) ----------------------
 // The key columns of a call as the kernels take them, by value in the kernel arguments (hj_key_col, include/htm_hashjoin.h):

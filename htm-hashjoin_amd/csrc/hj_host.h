@@ -27,6 +27,8 @@ enum Buf {
     B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_device.h)
     B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
     B_GATHER_CTR,               // hj_gather_dev: the NULL rows and the out-of-range entries of the last call (two 64-bit words)
+    B_GATHER2_CTR,              // hj_gather2_dev: the same two words of ITS last call, then HJ_GATHER_MAX_COLS 64-bit totals: the bytes of each column
+    B_GATHER2_WORK,             // ... and the workspace of its variable-length columns (gather2_work_words(nRows)), grown by the call
     B_VERIFY_CTR,               // hj_pairs_verify_dev: the output cursor (= pairs kept), then the candidates dropped (two 64-bit words)
     B_MARK_SWEEP,               // hj_mark_rows_dev: the sweep's workspace for a caller's plane (r_sweep_count_words(rows))
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
@@ -48,7 +50,7 @@ struct DevBuf {
 
 // The last call of one kind, as its *_info entry point reports it (call_info, hj_api_rows.hip): what the caller asked for,
 // and the pair of events around the call's work. `called` and `timed` die separately: see hj_ctx::call.
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_VERIFY, CALL_MARK_ROWS, CALL_COUNT };
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_MARK_ROWS, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
@@ -123,7 +125,7 @@ struct hj_ctx {
         bool probeOpt = false;                  // the last probe since the build enqueued the histogram-free passes for its slice
     } res;
     // ---- the last call of each kind (CallRecord). begin_operation forgets the TIME of the pairs call (its facts stay) and
-    // the whole R-rows call, which hj_reserve also forgets with the plane; the gather, the verify step and the sweep of
+    // the whole R-rows call, which hj_reserve also forgets with the plane; the two gathers, the verify step and the sweep of
     // a caller's plane belong to no build and no operation and are never forgotten.
     hjapi::CallRecord call[hjapi::CALL_COUNT];
     // ---- streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev). Reset by zipf_release (open, close, destroy).

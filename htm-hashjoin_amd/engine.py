@@ -273,6 +273,39 @@ class HashJoinContext:
         self._check(lib.hj_gather_info(self._h, out))
         return tuple(int(x) for x in out)
 
+    def gather2(self, d_map, n_rows, src_rows, cols, d_valid=0, row_base=0):
+        """hj_gather2_dev: gather on columns in the Arrow layout. cols: up to HJ_GATHER_MAX_COLS dicts with the fields of
+        hj_gather_col2 as keys, whatever is left out being 0 -- src, dst, width (0: variable length), fill (an int or
+        bytes), src_offsets / dst_offsets (variable length: src_rows + 1 offsets in, n_rows + 1 out), src_valid (the
+        source's validity plane), dst_valid (n_rows bits out: the row has a source row and its element is valid),
+        dst_capacity (variable length: the bytes of dst; 0 is the sizing pass) -- all pointers device pointers. The map,
+        row_base and d_valid (the call-level plane "row has a source row") are gather's. Asynchronous; needs no reserve and
+        no table. gather2_info() gives the bytes each column's rows take."""
+        cols = list(cols)
+        arr = (_lib.hj_gather_col2 * max(len(cols), 1))()
+        for c, d in zip(arr, cols):
+            unknown = set(d) - {"src", "dst", "width", "fill", "src_offsets", "dst_offsets", "src_valid", "dst_valid", "dst_capacity", "flags"}
+            if unknown:
+                raise ValueError(f"gather2: unknown column fields {sorted(unknown)}")
+            fill = d.get("fill", 0)
+            if isinstance(fill, (bytes, bytearray)):
+                fill = int.from_bytes(bytes(fill[:16]), "little")
+            c.src, c.dst, c.srcOffsets, c.dstOffsets, c.srcValid, c.dstValid = (
+                d.get(k) or None for k in ("src", "dst", "src_offsets", "dst_offsets", "src_valid", "dst_valid"))
+            c.dstCapacity, c.width, c.flags = d.get("dst_capacity", 0), d.get("width", 0), d.get("flags", 0)
+            c.fill[0], c.fill[1] = fill & 0xFFFFFFFFFFFFFFFF, (fill >> 64) & 0xFFFFFFFFFFFFFFFF
+        self._check(lib.hj_gather2_dev(self._h, C.c_void_p(d_map) if d_map else None, n_rows, row_base, src_rows,
+                                       arr if cols else None, len(cols), C.c_void_p(d_valid) if d_valid else None))
+
+    def gather2_info(self):
+        """hj_gather2_info (waits for the stream): (rows of the last gather2, its NULL rows, its device time in
+        microseconds, its out-of-range entries, then per column the bytes its rows take -- exact in 64 bits, 0 for a fixed
+        column; above 2^32 - 1 the column was not written); all 0 before the first one. gather_info() reports gather()
+        alone, and the other way round."""
+        out = (C.c_uint64 * (4 + _lib.HJ_GATHER_MAX_COLS))()
+        self._check(lib.hj_gather2_info(self._h, out))
+        return tuple(int(x) for x in out)
+
     # ---- joins on real key columns: hash, candidate join, verify ---------------
     def key_hash(self, cols, side, n_rows, d_out, key_mask=0):
         """hj_key_hash_dev: d_out[i] = the 32-bit join word of row i < n_rows as an 8-byte tuple (what prj_build and
@@ -821,9 +854,14 @@ _GATHER_WIDTHS = (1, 2, 4, 8, 16)
 
 
 def _table_columns(fn, side, cols, n):
-    """the payload columns of one side as {name: contiguous 1-D array}; ValueError for what the gather cannot take"""
+    """the payload columns of one side as {name: contiguous 1-D array, or KeyColumn}; ValueError for what the gather cannot take"""
     out = {}
     for name, col in (cols or {}).items():
+        if isinstance(col, KeyColumn):
+            if col.rows != n:
+                raise ValueError(f"{fn}: {side} column {name!r} must have {n} rows, not {col.rows}")
+            out[name] = col
+            continue
         a = np.asarray(col)
         if a.ndim != 1 or a.shape[0] != n:
             raise ValueError(f"{fn}: {side} column {name!r} must be 1-D with {n} elements, not shape {a.shape}")
@@ -833,20 +871,125 @@ def _table_columns(fn, side, cols, n):
     return out
 
 
+def _slice_bytes(c, n, step):
+    """the most bytes a slice of `step` rows of the KeyColumn c, of n rows, takes"""
+    if c.offsets is None:
+        return step * c.width
+    los = np.arange(0, n, step)
+    return int((c.offsets[np.minimum(los + step, n)].astype(np.int64) - c.offsets[los]).max()) if los.size else 0
+
+
+def _take_key_column(col, idx):
+    """the rows idx of a KeyColumn, on the host: NO_ROW gives a NULL (fixed: all-zero bytes; variable length: empty)"""
+    valid = idx != NO_ROW
+    if col.valid is not None:
+        valid[valid] = col.valid[idx[valid]]
+    src = idx[valid].astype(np.int64)
+    if col.offsets is None:
+        values = np.zeros(idx.size, dtype=col.values.dtype)
+        values[valid] = col.values[src]
+        return KeyColumn(values, None if valid.all() else valid, col.nulls_equal)
+    off = col.offsets.astype(np.int64)
+    lens = np.zeros(idx.size, dtype=np.int64)
+    lens[valid] = off[src + 1] - off[src]
+    data = np.concatenate([col.values[off[i]:off[i + 1]] for i in src]) if src.size else np.empty(0, dtype=np.uint8)
+    return KeyColumn.varlen(np.concatenate([[0], np.cumsum(lens)]), data, None if valid.all() else valid, col.nulls_equal)
+
+
+def _concat_key_columns(parts, like):
+    """the KeyColumns of the calls of one side, one behind the other; `like`: the source column (its kind, for no part at all)"""
+    valid = np.concatenate([np.ones(0, dtype=bool)] + [p.valid if p.valid is not None else np.ones(p.rows, dtype=bool) for p in parts])
+    valid = None if valid.all() else valid
+    if like.offsets is None:
+        return KeyColumn(np.concatenate([np.empty(0, dtype=like.values.dtype)] + [p.values for p in parts]), valid, like.nulls_equal)
+    data, offsets, base = [np.empty(0, dtype=np.uint8)], [np.zeros(1, dtype=np.int64)], 0
+    for p in parts:
+        off = p.offsets.astype(np.int64)
+        data.append(p.values[off[0]:off[-1]])
+        offsets.append(off[1:] - off[0] + base)
+        base += int(off[-1] - off[0])
+    return KeyColumn.varlen(np.concatenate(offsets), np.concatenate(data), valid, like.nulls_equal)
+
+
 def _take_on_host(cols, idx):
     """a side of a join that needed no device (an input is empty, so idx is all rows in order or all NO_ROW)"""
     valid = idx != NO_ROW
     out = {}
     for name, col in cols.items():
+        if isinstance(col, KeyColumn):
+            out[name] = _take_key_column(col, idx)
+            continue
         out[name] = np.zeros(idx.size, dtype=col.dtype)
         out[name][valid] = col[idx[valid]]
     return out, valid
 
 
+def _put_parts(ctx, held, parts, room=None):
+    """what KeyColumn.take gave -- (values or bytes, offsets, validity words) -- to the device: into fresh allocations, or
+    into `room`, three device pointers kept for a slice (0 where the column has no such part). A bytes buffer goes up in
+    whole 32-bit words: the kernels read the aligned words of an element."""
+    if room is None:
+        room = tuple(held.alloc(a.nbytes + 3 & ~3) if a is not None else 0 for a in parts)
+    for d, a in zip(room, parts):
+        if a is not None and a.nbytes:
+            ctx.copy_h2d(d, np.ascontiguousarray(a))
+    return room
+
+
+def _gather_key_columns(ctx, held, d_map, n_rows, row_base, src_rows, k_cols):
+    """The KeyColumn columns of one side through HashJoinContext.gather2: k_cols = [(name, (device values, offsets,
+    validity words), the source KeyColumn)] -> {name: KeyColumn of n_rows rows}. Variable-length columns are gathered as a
+    sizing call (dst_capacity 0) followed by the copy call."""
+    out = {}
+    if not n_rows:
+        return {name: _take_key_column(col, np.empty(0, dtype=np.uint32)) for name, _, col in k_cols}
+    words = (n_rows + 31) // 32
+    for i in range(0, len(k_cols), _lib.HJ_GATHER_MAX_COLS):
+        part, descs = k_cols[i:i + _lib.HJ_GATHER_MAX_COLS], []
+        for name, (d_values, d_offsets, d_valid), col in part:
+            d = {"src": d_values, "width": col.width, "src_valid": d_valid, "dst_valid": held.alloc(4 * words), "dst": 0}
+            if col.width:
+                d["dst"] = held.alloc(n_rows * col.width)
+            else:
+                d["src_offsets"], d["dst_offsets"] = d_offsets, held.alloc(4 * (n_rows + 1))
+            descs.append(d)
+        sized = [d for d in descs if not d["width"]]
+        if sized:
+            ctx.gather2(d_map, n_rows, src_rows, sized, row_base=row_base)
+            for d, total in zip(sized, ctx.gather2_info()[4:]):
+                if total > 0xFFFFFFFF:
+                    raise HashJoinError(_lib.HJ_ERR_INVALID, f"a variable-length column's {n_rows} result rows take {total} bytes, above 2^32 - 1")
+                d["dst_capacity"], d["dst"] = total, held.alloc(total) if total else 0
+        ctx.gather2(d_map, n_rows, src_rows, descs, row_base=row_base)
+        stray = ctx.gather2_info()[3]
+        if stray:
+            raise HashJoinError(_lib.HJ_ERR_STATE, f"{stray} map entries outside the {src_rows} source rows from {row_base}")
+        for (name, _, col), d in zip(part, descs):
+            bits = np.zeros(words, dtype=np.uint32)
+            ctx.copy_d2h(bits, d["dst_valid"])
+            valid = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
+            valid = None if valid.all() else valid
+            if col.width:
+                values = np.empty(n_rows, dtype=col.values.dtype)
+                ctx.copy_d2h(values, d["dst"])
+                out[name] = KeyColumn(values, valid, col.nulls_equal)
+            else:
+                offsets, data = np.empty(n_rows + 1, dtype=np.uint32), np.empty(d["dst_capacity"], dtype=np.uint8)
+                ctx.copy_d2h(offsets, d["dst_offsets"])
+                if data.size:
+                    ctx.copy_d2h(data, d["dst"])
+                out[name] = KeyColumn.varlen(offsets, data, valid, col.nulls_equal)
+            held.free(*(d[k] for k in ("dst", "dst_offsets", "dst_valid") if d.get(k)))
+    return out
+
+
 def _gather_side(ctx, held, d_map, n_rows, row_base, src_rows, d_cols):
     """One side of n_rows result rows out of the device map d_map: d_cols = [(name, device source, dtype)] -> ({name:
     array}, valid). One gather call per HJ_GATHER_MAX_COLS columns, the validity plane with the first (alone when the
-    side has no column). The library's own maps have no out-of-range entry: one is an error."""
+    side has no column). The library's own maps have no out-of-range entry: one is an error. A KeyColumn column -- (name,
+    its three device parts, the KeyColumn) -- goes through _gather_key_columns behind the plain ones."""
+    k_cols = [c for c in d_cols if isinstance(c[2], KeyColumn)]
+    d_cols = [c for c in d_cols if not isinstance(c[2], KeyColumn)]
     out = {name: np.empty(n_rows, dtype=dt) for name, _, dt in d_cols}
     words = np.zeros((n_rows + 31) // 32, dtype=np.uint32)
     if n_rows:
@@ -865,12 +1008,14 @@ def _gather_side(ctx, held, d_map, n_rows, row_base, src_rows, d_cols):
             ctx.copy_d2h(out[name], dst)
         held.free(d_valid, *dsts)
     valid = np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
+    out.update(_gather_key_columns(ctx, held, d_map, n_rows, row_base, src_rows, k_cols))
     return out, valid
 
 
 def _concat_side(parts, cols):
     """[(columns, valid)] of the calls of one side -> (columns, valid)"""
-    return ({name: np.concatenate([p[0][name] for p in parts]) if parts else np.empty(0, dtype=col.dtype)
+    return ({name: _concat_key_columns([p[0][name] for p in parts], col) if isinstance(col, KeyColumn)
+             else np.concatenate([p[0][name] for p in parts]) if parts else np.empty(0, dtype=col.dtype)
              for name, col in cols.items()},
             np.concatenate([p[1] for p in parts]) if parts else np.empty(0, dtype=bool))
 
@@ -879,7 +1024,8 @@ class _TableRows:
     """The result of join_tables / join_on as it grows: every device map a call of add() is given is copied to the host
     for the result and feeds the gather of its side's payload columns where it lies."""
 
-    def __init__(self, how, r_cols, s_cols, n_r, step):
+    def __init__(self, how, r_cols, s_cols, n_r, step, n_s=0):
+        self.n_s = n_s
         self.outer = how in _OUTER_KINDS
         self.kind, self.which = _OUTER_KINDS[how] if self.outer else (_lib.JOIN_KINDS[how], None)
         self.plane_s = self.kind is not None                                # right_semi / right_anti: R rows alone
@@ -906,8 +1052,10 @@ class _TableRows:
         where the probe (or a sweep) left them and feed the gather there. A side the kind has a plane for and the rows
         have no map of (0) is NULL by construction: the S side of R-only rows, the R side of unmatched S rows."""
         if not self.dev:    # the first call: R's columns whole, room for a slice of S's
-            self.dev["r"] = [(name, held.put(col), col.dtype) for name, col in self.r_cols.items()] if self.plane_r else []
-            self.dev["s"] = ([(name, held.alloc(self.step * col.dtype.itemsize), col.dtype) for name, col in self.s_cols.items()]
+            self.dev["r"] = [(name, _put_parts(ctx, held, col.take(0, self.n_r)), col) if isinstance(col, KeyColumn)
+                             else (name, held.put(col), col.dtype) for name, col in self.r_cols.items()] if self.plane_r else []
+            self.dev["s"] = ([(name, self.slice_room(held, col), col) if isinstance(col, KeyColumn)
+                              else (name, held.alloc(self.step * col.dtype.itemsize), col.dtype) for name, col in self.s_cols.items()]
                              if self.plane_s else [])
         for side, plane, d_map, maps, parts, cols in (("s", self.plane_s, d_s, self.s_maps, self.s_parts, self.s_cols),
                                                       ("r", self.plane_r, d_r, self.r_maps, self.r_parts, self.r_cols)):
@@ -922,10 +1070,18 @@ class _TableRows:
                 parts.append(_gather_side(ctx, held, d_map, rows, 0, self.n_r, self.dev["r"]))
                 continue
             if self.s_lo != lo:         # the slice's columns go up once, however many calls name rows of it
-                for (name, d_col, _) in self.dev["s"]:
-                    ctx.copy_h2d(d_col, self.s_cols[name][lo:lo + n_s])
+                for (name, d_col, kind) in self.dev["s"]:
+                    if isinstance(kind, KeyColumn):
+                        _put_parts(ctx, held, kind.take(lo, n_s), d_col)
+                    else:
+                        ctx.copy_h2d(d_col, self.s_cols[name][lo:lo + n_s])
                 self.s_lo = lo
             parts.append(_gather_side(ctx, held, d_map, rows, lo, n_s, self.dev["s"]))
+
+    def slice_room(self, held, col):
+        """device room for the largest slice of the S-side KeyColumn col: (values or bytes, offsets, validity words)"""
+        return (held.alloc(_slice_bytes(col, self.n_s, self.step) + 3 & ~3), held.alloc(4 * (self.step + 1)) if col.offsets is not None else 0,
+                held.alloc(4 * ((self.step + 31) // 32)) if col.valid is not None else 0)
 
     def joined(self):
         return self.result(np.concatenate(self.s_maps) if self.plane_s else None, np.concatenate(self.r_maps) if self.plane_r else None,
@@ -956,7 +1112,7 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     r_cols = _table_columns(fn, "R", r_cols, relR.size)
     s_cols = _table_columns(fn, "S", s_cols, relS.size)
     step = _slice_step(fn, relS.size, slice_tuples) if path == "radix" and relS.size else relS.size
-    rows = _TableRows(how, r_cols, s_cols, relR.size, step)
+    rows = _TableRows(how, r_cols, s_cols, relR.size, step, relS.size)
     trivial = rows.without_device(relS.size)
     if trivial is not None:
         return trivial
@@ -1037,7 +1193,7 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     r_cols = _table_columns(fn, "R", r_cols, n_r)
     s_cols = _table_columns(fn, "S", s_cols, n_s)
     step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
-    rows = _TableRows(how, r_cols, s_cols, n_r, step)
+    rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
     trivial = rows.without_device(n_s)
     if trivial is not None:
         return trivial
@@ -1161,6 +1317,15 @@ class KeyColumn:
     def __len__(self):
         return self.rows
 
+    def to_list(self):
+        """the inverse of from_list: one `bytes | None` per row (None: NULL); a fixed element comes back as its bytes"""
+        ok = self.valid if self.valid is not None else np.ones(self.rows, dtype=bool)
+        if self.offsets is None:
+            raw = np.ascontiguousarray(self.values).view(np.uint8).tobytes()
+            return [raw[i * self.width:(i + 1) * self.width] if v else None for i, v in enumerate(ok)]
+        raw, off = self.values.tobytes(), self.offsets
+        return [raw[int(off[i]):int(off[i + 1])] if v else None for i, v in enumerate(ok)]
+
     def take(self, lo, n):
         """rows [lo, lo + n) as the C ABI takes a column: (values or bytes, offsets rebased to those bytes or None, the
         validity bits repacked from bit 0 as uint32 words or None)"""
@@ -1236,7 +1401,7 @@ def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls
     r_cols = _table_columns(fn, "R", r_cols, n_r)
     s_cols = _table_columns(fn, "S", s_cols, n_s)
     step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
-    rows = _TableRows(how, r_cols, s_cols, n_r, step)
+    rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
     trivial = rows.without_device(n_s)
     if trivial is not None:
         return trivial
@@ -1244,13 +1409,6 @@ def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls
     s_sweep = _ON_S_SWEEP.get(rows.kind)
     flags = [_lib.HJ_KEY_NULLS_EQUAL if nulls_equal or r.nulls_equal or s.nulls_equal else 0 for r, s in zip(r_keys, s_keys)]
     dev = {}
-
-    def s_bytes(c):
-        """the most bytes a slice of S's column c takes"""
-        if c.offsets is None:
-            return step * c.width
-        los = np.arange(0, n_s, step)
-        return int((c.offsets[np.minimum(los + step, n_s)].astype(np.int64) - c.offsets[los]).max())
 
     def put(ctx, d, a):
         if a is not None and a.nbytes:
@@ -1267,7 +1425,7 @@ def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls
                 return d
 
             r_dev = [tuple(up(a) for a in c.take(0, n_r)) for c in r_keys]
-            dev["s"] = [(held.alloc(s_bytes(c) + 3 & ~3), held.alloc(4 * (step + 1)) if c.offsets is not None else 0,
+            dev["s"] = [(held.alloc(_slice_bytes(c, n_s, step) + 3 & ~3), held.alloc(4 * (step + 1)) if c.offsets is not None else 0,
                          held.alloc(4 * ((step + 31) // 32)) if c.valid is not None else 0) for c in s_keys]
             dev["r_marks"] = held.put(np.zeros((n_r + 31) // 32, dtype=np.uint32))
             dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))

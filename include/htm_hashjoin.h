@@ -312,6 +312,67 @@ int hj_gather_dev(hj_ctx *ctx, const uint32_t *dMap, uint64_t nRows, uint32_t ro
  * (HJ_NO_ROW entries), out[2] = its device time in microseconds (rounded), out[3] = its out-of-range entries. All 0 before
  * the first one. */
 int hj_gather_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- payload columns in the Arrow layout: source NULLs and variable-length (string) columns ----
+ * hj_gather2_dev is hj_gather_dev on a second column descriptor, modelled on hj_key_col2 (below): per column an optional
+ * source validity plane and optional 32-bit offsets, both gathered on the device. The map semantics are hj_gather_dev's,
+ * word for word: the raw entry HJ_NO_ROW is a NULL row whatever rowBase is; an entry with e - rowBase >= srcRows is never
+ * dereferenced in ANY buffer of any column (values, offsets, validity), gives what a NULL row gives and is counted apart;
+ * dValid stays the call-level plane "row has a source row". Per column, an ELEMENT is valid when its row has a source row
+ * i and the column has no srcValid or bit i of it is 1:
+ *   fixed width       a row with a valid element gets src[i], every other row the fill; the bytes under a source NULL are
+ *                     never read
+ *   variable length   a row with a valid element gets the bytes [srcOffsets[i], srcOffsets[i + 1]) of src, every other row
+ *                     is empty. dstOffsets[0 .. nRows] is always written in full: dstOffsets[0] = 0, dstOffsets[k + 1] -
+ *                     dstOffsets[k] = the bytes of row k, dstOffsets[nRows] = the bytes the rows take. Output bytes at
+ *                     positions at or behind dstCapacity are counted and not written (the library's contract for rows,
+ *                     applied to bytes); the cut is byte-granular: every byte below min(total, dstCapacity) is exact and
+ *                     no byte at or behind it is touched. dstCapacity 0 (dst may be NULL) is the sizing pass: offsets and
+ *                     totals only
+ *   dstValid          (either kind; may be NULL) bit k = row k has a valid element; ceil(nRows / 32) words written whole,
+ *                     the bits at or behind nRows 0, nothing behind them
+ * The totals are exact in 64 bits (hj_gather2_info). A column whose rows take more than 2^32 - 1 bytes cannot be laid out
+ * with 32-bit offsets: none of its bytes are written, its dstOffsets are unspecified, its total says so; nothing faults.
+ * What is read: the map; of a row with a source row the validity word of its element and, if that is valid, its two
+ * offsets; of a valid non-empty element the aligned 32-bit words that hold one of its bytes (the rule of hj_key_hash2_dev)
+ * and no byte outside them; of an empty or ungathered element nothing. What is written: the ranges named above and nothing
+ * else. A call whose columns are all fixed without srcValid and dstValid runs the kernels of hj_gather_dev and costs what
+ * that call costs. */
+typedef struct {
+    const void     *src;        /* fixed width: srcRows elements. Variable length: the bytes buffer (any alignment). May
+                                   be NULL when srcRows == 0                                                              */
+    void           *dst;        /* fixed: nRows elements. Variable length: dstCapacity bytes (any alignment); may be NULL
+                                   when dstCapacity == 0                                                                  */
+    const uint32_t *srcOffsets; /* NULL: fixed width. Else srcRows + 1 offsets into src (Arrow Binary / Utf8): non-decreasing,
+                                   srcOffsets[0] need not be 0. Caller's contract, not checked on the device             */
+    uint32_t       *dstOffsets; /* variable length: nRows + 1 offsets out                                                */
+    const uint32_t *srcValid;   /* NULL: the source has no NULLs. Else the plane hj_gather_dev writes, bit i = source row i,
+                                   ceil(srcRows / 32) words                                                              */
+    uint32_t       *dstValid;   /* NULL, or ceil(nRows / 32) words out                                                   */
+    uint64_t        dstCapacity;/* variable length: the bytes of dst. Fixed width: 0                                     */
+    uint32_t        width;      /* 1, 2, 4, 8 or 16 (src and dst aligned to it); 0 for a variable-length column          */
+    uint32_t        flags;      /* 0                                                                                     */
+    uint64_t        fill[2];    /* fixed width: the low `width` bytes are what a row without a valid element gets        */
+} hj_gather_col2;               /* 80 bytes */
+/* Gathers nCols (0 .. HJ_GATHER_MAX_COLS) columns through dMap[0..nRows). `cols` is host memory and is read before the
+ * call returns. Asynchronous on the context's stream; needs no table, no hj_reserve and no state; touches no counter of
+ * hj_result and no other *_info, hj_gather_info included. The scan workspace of the variable-length columns belongs to the
+ * context and grows with nRows (as for hj_mark_rows_dev). A variable-length column is three steps -- the rows' lengths
+ * into dstOffsets with a 64-bit partial sum per workgroup, the library's exclusive scan over the nRows + 1 words in place,
+ * the copy -- so its cost is two passes over the map and three over dstOffsets besides the bytes. nRows 0 is a no-op.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): everything hj_gather_dev refuses (for a variable-length
+ * column src and dst need no alignment, and dst may be NULL with dstCapacity 0); width 0 without srcOffsets or without
+ * dstOffsets; srcOffsets or dstOffsets with a width other than 0; any flag bit; an offsets or validity pointer that is not
+ * 4-byte aligned; dstCapacity > 0 with dst NULL; dstCapacity != 0 on a fixed column; a variable-length dst whose
+ * dstCapacity bytes overlap another output of the call (a column's dst over its nRows elements or its dstCapacity bytes,
+ * a dstOffsets, a dstValid, dValid) -- as far as the host can tell from the pointers. */
+int hj_gather2_dev(hj_ctx *ctx, const uint32_t *dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows,
+                   const hj_gather_col2 *cols, uint32_t nCols, uint32_t *dValid);
+/* Waits for the stream. About the last hj_gather2_dev that enqueued work (hj_gather_info keeps reporting hj_gather_dev
+ * alone, and the other way round): out[0 .. 3] as hj_gather_info -- rows, NULL rows, device time in microseconds,
+ * out-of-range entries --, out[4 + c] = the bytes the rows of column c take, exact in 64 bits, 0 for a fixed column and for
+ * c at or behind the call's nCols. A total above 2^32 - 1 is the report that the column was not written. All 0 before the
+ * first call. */
+int hj_gather2_info(hj_ctx *ctx, uint64_t out[4 + HJ_GATHER_MAX_COLS]);
 /* ---- joins on real key columns: hash, candidate join, verify ----
  * Every join above matches on one 32-bit word. A key of 64 bits, of several columns or of 16 bytes is joined in three steps:
  * hj_key_hash_dev hashes the key columns of each row to a 32-bit join word, written as the 8-byte tuple the resident radix
