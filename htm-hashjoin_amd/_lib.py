@@ -44,6 +44,11 @@ HJ_KEY_MAX_COLS = 4
 HJ_KEY_SIDE_S, HJ_KEY_SIDE_R = 0, 1
 # hj_key_col2.flags: in this column a NULL equals a NULL
 HJ_KEY_NULLS_EQUAL = 0x1
+# aggregating joins (hj_agg_op, hj_agg_spec.flags)
+HJ_AGG_MAX_COLS = 4
+HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
+AGG_OPS = {"count": HJ_AGG_COUNT, "sum": HJ_AGG_SUM, "min": HJ_AGG_MIN, "max": HJ_AGG_MAX}
+HJ_AGG_SIGNED = 0x1
 
 
 class hj_params(C.Structure):
@@ -129,6 +134,34 @@ class hj_key_col2(C.Structure):
     ]
 
 
+class hj_agg_spec(C.Structure):
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class hj_agg_src(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("srcValid", C.c_void_p),
+    ]
+
+
+class hj_agg_col(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("srcValid", C.c_void_p),
+        ("acc", C.c_void_p),
+        ("op", C.c_uint32),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 def _declare(lib):
     vp, u64, u32, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
     P = C.POINTER
@@ -170,6 +203,13 @@ def _declare(lib):
         "hj_prj_probe_pairs_dev": ([vp, vp, u64, u64, vp, vp, u64], i32),
         "hj_prj_probe_join_dev": ([vp, u32, vp, u64, u64, vp, vp, u64], i32),
         "hj_prj_resident_info": ([vp, P(u64)], i32),
+        "hj_prj_agg_begin": ([vp, P(hj_agg_spec), u32], i32),
+        "hj_prj_probe_agg_dev": ([vp, vp, u64, P(hj_agg_src), u32], i32),
+        "hj_prj_agg_rows_dev": ([vp, P(vp), vp], i32),
+        "hj_prj_agg_info": ([vp, P(u64)], i32),
+        "hj_prj_agg_layout_info": ([u32, P(u64)], i32),
+        "hj_pairs_agg_dev": ([vp, vp, vp, u64, u32, u64, u32, u64, P(hj_agg_col), u32, vp], i32),
+        "hj_pairs_agg_info": ([vp, P(u64)], i32),
         "hj_join_dev": ([vp, vp, u64, vp, u64], i32),
         "hj_checksums_dev": ([vp], i32),
         "hj_fetch_result": ([vp, P(hj_result)], i32),

@@ -157,7 +157,7 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
         const int rc = reserve_all(c, {{B_TMP, (nmax + 2) * sizeof(uint64_t)}, {B_PART_R, (rSize + 2) * sizeof(uint64_t)},
                                        {B_PART_S, sSize ? (sSize + 2) * sizeof(uint64_t) : 0}, {B_WORK, c->plan.workspaceBytes},
                                        {B_PRJ_RES, prj_resident_bytes(bits, sSize)}}, &replaced);
-        if (replaced) c->res = {};
+        if (replaced) { c->res = {}; c->agg = {}; }
         if (rc) return rc;
         c->prjMaxSlice = sSize;
         if (params->algo == HJ_ALGO_PRJ) return HJ_OK;      // AUTO also needs the open-addressing buffers below

@@ -149,6 +149,125 @@ int hj_prj_probe_pairs_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, uint64
     return prj_probe_join(c, "hj_prj_probe_pairs_dev", HJ_JOIN_INNER, dS, sSize, sIdxBase, dOutS, dOutR, capacity);
 }
 
+// ---- aggregating joins on the resident R (hj_prj_agg.hip) -------------------
+// what the three calls behind the begin need (fn: the entry point's name): an aggregation that no build has ended
+static int agg_state(hj_ctx* c, const char* fn)
+{
+    if (!c->res.on) return fail(c, HJ_ERR_STATE, fn, "no resident R (call hj_prj_build_dev first)");
+    if (!c->agg.on) return fail(c, HJ_ERR_STATE, fn, "no aggregation (call hj_prj_agg_begin first)");
+    return HJ_OK;
+}
+
+int hj_prj_agg_begin(hj_ctx* c, const hj_agg_spec* specs, uint32_t nCols)
+{
+    HJ_ENTER(c, true);
+    const char* const fn = "hj_prj_agg_begin";
+    if (!c->res.on) return fail(c, HJ_ERR_STATE, fn, "no resident R (call hj_prj_build_dev first)");
+    if (!c->res.rows) return fail(c, HJ_ERR_STATE, fn, "R was built without HJ_FLAG_KEEP_ROW_IDS");
+    if (nCols == 0 || nCols > HJ_AGG_MAX_COLS) return fail(c, HJ_ERR_INVALID, fn, "nCols must be 1 .. HJ_AGG_MAX_COLS");
+    if (!specs) return fail(c, HJ_ERR_INVALID, fn, "specs NULL");
+    AggOps ops{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_agg_spec& sp = specs[i];
+        if (sp.op > HJ_AGG_MAX) return fail(c, HJ_ERR_INVALID, fn, "op must be an hj_agg_op");
+        if (sp.op == HJ_AGG_COUNT ? sp.width != 0 : (sp.width != 4 && sp.width != 8))
+            return fail(c, HJ_ERR_INVALID, fn, "a width that is not 4 or 8 (HJ_AGG_COUNT: 0)");
+        if (sp.flags & ~HJ_AGG_SIGNED) return fail(c, HJ_ERR_INVALID, fn, "hj_agg_spec.flags has bits other than HJ_AGG_SIGNED");
+        if (sp.reserved) return fail(c, HJ_ERR_INVALID, fn, "hj_agg_spec.reserved must be 0");
+        ops.op[i] = sp.op; ops.width[i] = sp.width; ops.sgn[i] = sp.flags & HJ_AGG_SIGNED;
+    }
+    HJ_HIP(c, hipSetDevice(c->device));
+    c->agg = {};
+    if (const int rc = c->buf[B_AGG].reserve(c, agg_bytes(c->res.nR, nCols))) return rc;
+    c->agg.nCols = nCols; c->agg.nR = c->res.nR; c->agg.ops = ops;
+    HJ_HIP(c, hipMemsetAsync(c->buf[B_AGG].p, 0, 256, c->stream));
+    HJ_HIP(c, launch_agg_fill(agg_planes(c), ops, nCols, c->agg.nR, c->nCU, c->stream));
+    c->agg.on = true;
+    c->call[CALL_PRJ_AGG].called = false;
+    return HJ_OK;
+}
+
+int hj_prj_probe_agg_dev(hj_ctx* c, const uint64_t* dS, uint64_t sSize, const hj_agg_src* srcs, uint32_t nCols)
+{
+    HJ_ENTER(c, dS || !sSize);
+    const char* const fn = "hj_prj_probe_agg_dev";
+    if (const int rc = agg_state(c, fn)) return rc;
+    if (!prj_slice_fits(c, sSize)) return fail(c, HJ_ERR_STATE, fn, "slice larger than the sSize given to hj_reserve()");
+    if (nCols != c->agg.nCols) return fail(c, HJ_ERR_INVALID, fn, "nCols differs from hj_prj_agg_begin's");
+    if (!srcs) return fail(c, HJ_ERR_INVALID, fn, "srcs NULL");
+    AggSrc src{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const uint32_t width = c->agg.ops.width[i];
+        if (reinterpret_cast<uintptr_t>(srcs[i].srcValid) & 3u) return fail(c, HJ_ERR_INVALID, fn, "a srcValid that is not 4-byte aligned");
+        if (width && (!srcs[i].src || (reinterpret_cast<uintptr_t>(srcs[i].src) & (width - 1))))
+            return fail(c, HJ_ERR_INVALID, fn, "a src that is NULL or not aligned to its width");
+        src.p[i] = srcs[i].src; src.valid[i] = srcs[i].srcValid;
+    }
+    if (sSize == 0) return HJ_OK;
+    HJ_HIP(c, hipSetDevice(c->device));
+    // the probe's own sequence is prj_probe's: the slice's geometry with the exact passes (they carry the rows), timed as a probe
+    const PrjPlan pl = prj_plan(sSize, sSize, c->res.plan.radixBits, 1u);
+    int rc;
+    if ((rc = c->buf[B_WORK].reserve(c, pl.workspaceBytes))) return rc;
+    if ((rc = record(c, EV_RP0))) return rc;
+    HJ_HIP(c, hipEventRecord(c->call[CALL_PRJ_AGG].ev[0], c->stream));
+    const PrjResident res = prj_resident_carve(c->buf[B_PRJ_RES].p, c->res.plan.radixBits, sSize);
+    HJ_HIP(c, launch_prj_probe_agg(c->res.plan, pl, prj_buffers(c), res, dS, sSize, src, c->agg.ops, nCols, agg_planes(c),
+                                   c->buf[B_AGG].as<unsigned long long>(), c->nCU, c->dCtr(), c->time.ev[EV_RP_PART], c->time.ev[EV_RP_JOIN0],
+                                   c->stream));
+    if ((rc = call_end(c, CALL_PRJ_AGG, 0, sSize))) return rc;
+    if ((rc = record(c, EV_RP1))) return rc;
+    c->time.set[EV_RP_PART] = c->time.set[EV_RP_JOIN0] = true;      // the launcher recorded them
+    c->op.sSize += sSize;
+    c->res.probeOpt = false;
+    c->agg.probes += 1;
+    return HJ_OK;
+}
+
+int hj_prj_agg_rows_dev(hj_ctx* c, void* const* dOut, uint64_t* dOutCount)
+{
+    HJ_ENTER(c, true);
+    const char* const fn = "hj_prj_agg_rows_dev";
+    if (const int rc = agg_state(c, fn)) return rc;
+    if (!dOut) return fail(c, HJ_ERR_INVALID, fn, "dOut NULL");
+    AggRowsOut out{};
+    for (uint32_t i = 0; i < c->agg.nCols; ++i) {
+        if (!dOut[i] || (reinterpret_cast<uintptr_t>(dOut[i]) & 7u)) return fail(c, HJ_ERR_INVALID, fn, "an output plane that is NULL or not 8-byte aligned");
+        out.col[i] = static_cast<unsigned long long*>(dOut[i]);
+    }
+    if (reinterpret_cast<uintptr_t>(dOutCount) & 7u) return fail(c, HJ_ERR_INVALID, fn, "dOutCount not 8-byte aligned");
+    out.count = reinterpret_cast<unsigned long long*>(dOutCount);
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, launch_agg_rows(c->buf[B_PART_R].as<uint64_t>(), agg_planes(c), out, c->agg.nCols, c->agg.nR, c->nCU, c->stream));
+    return HJ_OK;
+}
+
+int hj_prj_agg_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    HJ_HIP(c, hipSetDevice(c->device));
+    HJ_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!c->res.on || !c->agg.on) return HJ_OK;
+    const CallRecord& r = c->call[CALL_PRJ_AGG];
+    if (r.called) {
+        unsigned long long last = 0;
+        HJ_HIP(c, hipMemcpy(&last, c->buf[B_AGG].p, sizeof last, hipMemcpyDeviceToHost));
+        float ms = 0;
+        if (!r.timed || hipEventElapsedTime(&ms, r.ev[0], r.ev[1]) != hipSuccess) ms = 0;
+        out[0] = last; out[1] = (uint64_t)((double)ms * 1000.0 + 0.5);
+    }
+    out[2] = c->agg.nCols; out[3] = c->agg.probes; out[4] = c->agg.nR;
+    return HJ_OK;
+}
+
+int hj_prj_agg_layout_info(uint32_t nCols, uint64_t out[4])
+{
+    if (!out || nCols == 0 || nCols > HJ_AGG_MAX_COLS) return HJ_ERR_INVALID;
+    for (uint32_t i = 0; i < 4; ++i) out[i] = agg_layout(nCols, i);
+    return HJ_OK;
+}
+
 int hj_prj_resident_info(hj_ctx* c, uint64_t out[8])
 {
     HJ_ENTER(c, out);

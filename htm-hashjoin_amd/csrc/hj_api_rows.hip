@@ -351,6 +351,53 @@ int hj_verify_info(hj_ctx* c, uint64_t out[4])
     return call_info(c, c->call[CALL_VERIFY], c->buf[B_VERIFY_CTR].p, 16, out);     // pairs kept, candidates dropped
 }
 
+// ---- the reduction over a pair list (hj_agg.hip) ----------------------------
+int hj_pairs_agg_dev(hj_ctx* c, const uint32_t* dMapG, const uint32_t* dMapV, uint64_t nPairs, uint32_t gBase, uint64_t gRows, uint32_t vBase,
+                     uint64_t vRows, const hj_agg_col* cols, uint32_t nCols, uint64_t* dCount)
+{
+    HJ_ENTER(c, true);
+    const char* const fn = "hj_pairs_agg_dev";
+    if (nCols > HJ_AGG_MAX_COLS) return fail(c, HJ_ERR_INVALID, fn, "more than HJ_AGG_MAX_COLS columns");
+    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, fn, "cols NULL with nCols > 0");
+    if (!nCols && !dCount) return fail(c, HJ_ERR_INVALID, fn, "neither a column nor dCount");
+    if (nPairs > 0xFFFFFFFFull || gRows > 0xFFFFFFFFull || vRows > 0xFFFFFFFFull)
+        return fail(c, HJ_ERR_INVALID, fn, "nPairs, gRows or vRows above 2^32 - 1");
+    if (nPairs && !dMapG) return fail(c, HJ_ERR_INVALID, fn, "dMapG NULL with nPairs > 0");
+    if (reinterpret_cast<uintptr_t>(dCount) & 7u) return fail(c, HJ_ERR_INVALID, fn, "dCount not 8-byte aligned");
+    PairAggCols k{};
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_agg_col& col = cols[i];
+        if (col.op > HJ_AGG_MAX) return fail(c, HJ_ERR_INVALID, fn, "op must be an hj_agg_op");
+        if (col.op == HJ_AGG_COUNT ? col.width != 0 : (col.width != 4 && col.width != 8))
+            return fail(c, HJ_ERR_INVALID, fn, "a width that is not 4 or 8 (HJ_AGG_COUNT: 0)");
+        if (col.flags & ~HJ_AGG_SIGNED) return fail(c, HJ_ERR_INVALID, fn, "hj_agg_col.flags has bits other than HJ_AGG_SIGNED");
+        if (col.reserved) return fail(c, HJ_ERR_INVALID, fn, "hj_agg_col.reserved must be 0");
+        if (!col.acc || (reinterpret_cast<uintptr_t>(col.acc) & 7u)) return fail(c, HJ_ERR_INVALID, fn, "an acc that is NULL or not 8-byte aligned");
+        if (!word_ptr_ok(col.srcValid)) return fail(c, HJ_ERR_INVALID, fn, "a srcValid that is not 4-byte aligned");
+        if (col.width && vRows && !col_ptr_ok(col.src, col.width)) return fail(c, HJ_ERR_INVALID, fn, "a src that is NULL or not aligned to its width");
+        if (nPairs && !dMapV && (col.width || col.srcValid)) return fail(c, HJ_ERR_INVALID, fn, "dMapV NULL with a column that reads S values or validity");
+        k.src.p[i] = col.src; k.src.valid[i] = col.srcValid; k.acc[i] = static_cast<unsigned long long*>(col.acc);
+        k.ops.op[i] = col.op; k.ops.width[i] = col.width; k.ops.sgn[i] = col.flags & HJ_AGG_SIGNED;
+    }
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (const int rc = c->buf[B_PAIRS_AGG_CTR].reserve(c, 2 * sizeof(unsigned long long))) return rc;
+    unsigned long long* const counts = c->buf[B_PAIRS_AGG_CTR].as<unsigned long long>();
+    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_PAIRS_AGG].ev[0], c->stream));
+    HJ_HIP(c, launch_pairs_agg(dMapG, dMapV, nPairs, gBase, (uint32_t)gRows, vBase, (uint32_t)vRows, k, nCols,
+                               reinterpret_cast<unsigned long long*>(dCount), counts, c->stream));
+    return call_end(c, CALL_PAIRS_AGG, 0, nPairs);
+}
+
+int hj_pairs_agg_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_PAIRS_AGG];  // pairs applied, pairs skipped
+    if (const int rc = call_info(c, r, c->buf[B_PAIRS_AGG_CTR].p, 16, out)) return rc;
+    out[1] = out[0]; out[0] = r.called ? r.rows : 0;
+    return HJ_OK;
+}
+
 int hj_mark_rows_dev(hj_ctx* c, const uint32_t* dMarks, uint64_t rows, uint32_t rowBase, uint32_t which, uint32_t* dOut, uint64_t capacity)
 {
     HJ_ENTER(c, true);

@@ -813,4 +813,68 @@ hipError_t launch_prj_probe_rows(uint32_t kind, const PrjPlan& planR, const PrjP
                                  const uint64_t* S, uint64_t nS, uint64_t sIdxBase, PairsOut out, int nCU, Counters* ctr,
                                  hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s, const RMarks* marks = nullptr);
 
+// ---- aggregating joins: COUNT / SUM / MIN / MAX per group row (hj_prj_agg.hip, hj_agg.hip) ----
+// The columns of a call as the kernels take them, by value in the kernel arguments: the ops (hj_agg_spec; sgn: HJ_AGG_SIGNED),
+// the sources (hj_agg_src) and the accumulator planes. Every accumulator is 64 bits wide.
+constexpr uint32_t kAggMaxCols = 4;           // HJ_AGG_MAX_COLS
+constexpr uint32_t kAggCount = 0, kAggSum = 1, kAggMin = 2, kAggMax = 3;      // hj_agg_op
+struct AggOps { uint32_t op[kAggMaxCols], width[kAggMaxCols], sgn[kAggMaxCols]; };
+struct AggSrc { const void* p[kAggMaxCols]; const uint32_t* valid[kAggMaxCols]; };
+struct AggPlanes { unsigned long long* count; unsigned long long* acc[kAggMaxCols]; };
+struct AggRowsOut { unsigned long long* col[kAggMaxCols]; unsigned long long* count; };
+// the identity of a column's op: what an accumulator holds before its first value
+__device__ __forceinline__ unsigned long long agg_identity(uint32_t op, uint32_t sgn)
+{
+    if (op == kAggMin) return sgn ? 0x7FFFFFFFFFFFFFFFull : 0xFFFFFFFFFFFFFFFFull;
+    if (op == kAggMax) return sgn ? 0x8000000000000000ull : 0ull;
+    return 0ull;
+}
+// acc op= v, without a returned value; SCOPE: the workgroup for an LDS entry, the agent for a global one
+template <int SCOPE>
+__device__ __forceinline__ void agg_apply(unsigned long long* acc, uint32_t op, uint32_t sgn, unsigned long long v)
+{
+    if (op <= kAggSum) __hip_atomic_fetch_add(acc, v, __ATOMIC_RELAXED, SCOPE);
+    else if (op == kAggMin) {
+        if (sgn) __hip_atomic_fetch_min(reinterpret_cast<long long*>(acc), (long long)v, __ATOMIC_RELAXED, SCOPE);
+        else __hip_atomic_fetch_min(acc, v, __ATOMIC_RELAXED, SCOPE);
+    } else {
+        if (sgn) __hip_atomic_fetch_max(reinterpret_cast<long long*>(acc), (long long)v, __ATOMIC_RELAXED, SCOPE);
+        else __hip_atomic_fetch_max(acc, v, __ATOMIC_RELAXED, SCOPE);
+    }
+}
+// a op b, for the reductions in registers that run in front of an atomic
+__device__ __forceinline__ unsigned long long agg_combine(uint32_t op, uint32_t sgn, unsigned long long a, unsigned long long b)
+{
+    if (op <= kAggSum) return a + b;
+    if (op == kAggMin) return sgn ? ((long long)a < (long long)b ? a : b) : (a < b ? a : b);
+    return sgn ? ((long long)a > (long long)b ? a : b) : (a > b ? a : b);
+}
+// the 64-bit value of element i of a column: COUNT brings 1, a 4-byte element is sign- or zero-extended
+__device__ __forceinline__ unsigned long long agg_value(const void* __restrict__ src, uint32_t op, uint32_t width, uint32_t sgn, uint32_t i)
+{
+    if (op == kAggCount) return 1ull;
+    if (width == 8) return static_cast<const unsigned long long*>(src)[i];
+    const uint32_t w = static_cast<const uint32_t*>(src)[i];
+    return sgn ? (unsigned long long)(long long)(int32_t)w : (unsigned long long)w;
+}
+
+// The resident radix join's planes hold n = rSize entries each, indexed by resident position (the index into partR).
+// what: 0 slots, 1 R tuples per LDS build, 2 S elements per round of a workgroup, 3 kPrjItemS (hj_prj_agg_layout_info)
+uint32_t agg_layout(uint32_t nCols, uint32_t what);
+hipError_t launch_agg_fill(const AggPlanes& pl, const AggOps& ops, uint32_t nCols, uint64_t n, int nCU, hipStream_t s);
+// out.col[c][partR[pos].y] = pl.acc[c][pos], out.count likewise (may be null); plain stores, the planes are only read
+hipError_t launch_agg_rows(const uint64_t* partR, const AggPlanes& pl, const AggRowsOut& out, uint32_t nCols, uint64_t n, int nCU, hipStream_t s);
+// launch_prj_probe_rows with the accumulators in place of the pairs: S's row-id passes (rows from 0: src is indexed by the
+// position in S), the work-item list, k_prj_join_agg. Adds to Counters::prjMatches and to *last, which is zeroed here first.
+hipError_t launch_prj_probe_agg(const PrjPlan& planR, const PrjPlan& planS, const PrjBuffers& buf, const PrjResident& res,
+                                const uint64_t* S, uint64_t nS, const AggSrc& src, const AggOps& ops, uint32_t nCols, const AggPlanes& pl,
+                                unsigned long long* last, int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evJoin0, hipStream_t s);
+// The reduction over a pair list (hj_agg.hip): for pair k with g = mapG[k] - gBase, v = mapV[k] - vBase: acc[c][g] op= src[c][v],
+// count[g] += 1 (count may be null, and mapV when no column reads a value). An entry that is HJ_NO_ROW or out of range on
+// either side is never dereferenced: counts[1] += 1, else counts[0] += 1 (two 64-bit words, zeroed before the launch).
+struct PairAggCols { AggSrc src; AggOps ops; unsigned long long* acc[kAggMaxCols]; };
+hipError_t launch_pairs_agg(const uint32_t* mapG, const uint32_t* mapV, uint64_t nPairs, uint32_t gBase, uint32_t gRows, uint32_t vBase,
+                            uint32_t vRows, const PairAggCols& cols, uint32_t nCols, unsigned long long* count, unsigned long long* counts,
+                            hipStream_t s);
+
 }  // namespace hj

@@ -31,6 +31,9 @@ enum Buf {
     B_GATHER2_WORK,             // ... and the workspace of its variable-length columns (gather2_work_words(nRows)), grown by the call
     B_VERIFY_CTR,               // hj_pairs_verify_dev: the output cursor (= pairs kept), then the candidates dropped (two 64-bit words)
     B_MARK_SWEEP,               // hj_mark_rows_dev: the sweep's workspace for a caller's plane (r_sweep_count_words(rows))
+    B_AGG,                      // hj_prj_agg_begin: 256 bytes of words (the matches of the last hj_prj_probe_agg_dev), then the match-count
+                                // plane and HJ_AGG_MAX_COLS accumulator planes of 8 bytes per R tuple, in resident order (agg_planes)
+    B_PAIRS_AGG_CTR,            // hj_pairs_agg_dev: the pairs applied and the pairs skipped by its last call (two 64-bit words)
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -50,7 +53,7 @@ struct DevBuf {
 
 // The last call of one kind, as its *_info entry point reports it (call_info, hj_api_rows.hip): what the caller asked for,
 // and the pair of events around the call's work. `called` and `timed` die separately: see hj_ctx::call.
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_MARK_ROWS, CALL_COUNT };
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
@@ -124,6 +127,9 @@ struct hj_ctx {
         bool rows = false;                      // R holds {key, row} elements (reserved with HJ_FLAG_KEEP_ROW_IDS)
         bool probeOpt = false;                  // the last probe since the build enqueued the histogram-free passes for its slice
     } res;
+    // ---- the aggregation over the resident R (hj_prj_agg_begin .. hj_prj_agg_rows_dev): its columns, the R tuples its planes
+    // in buf[B_AGG] hold, the probes since the begin. Reset by begin_operation; worth nothing without res.on.
+    struct Agg { bool on = false; uint32_t nCols = 0; uint64_t nR = 0, probes = 0; hj::AggOps ops{}; } agg;
     // ---- the last call of each kind (CallRecord). begin_operation forgets the TIME of the pairs call (its facts stay) and
     // the whole R-rows call, which hj_reserve also forgets with the plane; the two gathers, the verify step and the sweep of
     // a caller's plane belong to no build and no operation and are never forgotten.
@@ -238,9 +244,10 @@ inline int begin_operation(hj_ctx* c, uint64_t rSize, uint64_t sSize, uint64_t t
 {
     HJ_HIP(c, hipSetDevice(c->device));
     for (bool& set : c->time.set) set = false;
-    c->op = {}; c->htm = {}; c->prj = {}; c->res = {};
+    c->op = {}; c->htm = {}; c->prj = {}; c->res = {}; c->agg = {};
     forget_marks(c);
     c->call[CALL_PAIRS].timed = false;          // hj_pairs_info keeps the call's facts and reports no time
+    c->call[CALL_PRJ_AGG].called = false;       // the probes of an aggregation end with it
     c->op.rSize = rSize; c->op.sSize = sSize; c->op.tableSize = tableSize;
     HJ_HIP(c, hipMemsetAsync(c->dCtr(), 0, sizeof(Counters), c->stream));
     return HJ_OK;
@@ -326,6 +333,17 @@ inline int pairs_args(hj_ctx* c, const char* fn, uint32_t kind, const char* stat
     if (capacity && (!dOutS || (*planeR && !dOutR))) return fail(c, HJ_ERR_INVALID, fn, "output pointer NULL with capacity > 0");
     if (sIdxBase > 0xFFFFFFFFull || sIdxBase + sSize > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, fn, "S row range exceeds 2^32 - 1");
     return HJ_OK;
+}
+
+// the planes of an aggregation over nR resident tuples, carved from buf[B_AGG]
+inline size_t agg_bytes(uint64_t nR, uint32_t nCols) { return 256 + (size_t)(1 + nCols) * nR * sizeof(unsigned long long); }
+inline AggPlanes agg_planes(const hj_ctx* c)
+{
+    unsigned long long* const base = reinterpret_cast<unsigned long long*>(c->buf[B_AGG].as<char>() + 256);
+    AggPlanes pl{};
+    pl.count = base;
+    for (uint32_t i = 0; i < c->agg.nCols; ++i) pl.acc[i] = base + (size_t)(1 + i) * c->agg.nR;
+    return pl;
 }
 
 // ---- defined in one part, used by another. hj_api_table.hip: the locality pre-round read back on the host (c->pin->fit),

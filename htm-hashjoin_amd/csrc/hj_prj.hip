@@ -1920,6 +1920,7 @@ hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums,
 }
 
 static hipError_t prj_pairs_set_attributes();     // hj_prj_pairs.hip
+static hipError_t prj_agg_set_attributes();       // hj_prj_agg.hip
 
 hipError_t prj_set_attributes()
 {
@@ -1934,6 +1935,7 @@ hipError_t prj_set_attributes()
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_probe_items<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = prj_pairs_set_attributes()) != hipSuccess) return e;
+    if ((e = prj_agg_set_attributes()) != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_scatter_stable),
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                sizeof(uint32_t) * (kStabMaxFan * kStabGroups + kStabTile + (kStabTile >> 5) + 1));
@@ -1944,3 +1946,5 @@ hipError_t prj_set_attributes()
 // the materialising form of the resident join: part of this translation unit, because it runs the passes above in their
 // row-id form and walks the work items k_prj_items_count / k_prj_items_fill build
 #include "hj_prj_pairs.hip"
+// the aggregating form: the same passes and work items, per-R-row accumulators in place of the pair stage
+#include "hj_prj_agg.hip"

@@ -153,6 +153,25 @@ def _key_cols2(cols):
     return arr, len(cols)
 
 
+def _agg_specs(specs):
+    """[(op, width, flags[, reserved])] -> (hj_agg_spec array, its length)"""
+    specs = [tuple(s) + (0,) * (4 - len(s)) for s in specs]
+    arr = (_lib.hj_agg_spec * max(len(specs), 1))()
+    for a, (op, width, flags, reserved) in zip(arr, specs):
+        a.op, a.width, a.flags, a.reserved = op, width, flags, reserved
+    return arr, len(specs)
+
+
+def prj_agg_layout_info(n_cols):
+    """hj_prj_agg_layout_info: the LDS layout of the aggregating radix join for n_cols columns -- table slots, R tuples per
+    LDS build, S elements per round of a workgroup, S tuples per work item. Host-only; no device."""
+    out = (C.c_uint64 * 4)()
+    rc = lib.hj_prj_agg_layout_info(n_cols, out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_prj_agg_layout_info")
+    return {"slots": int(out[0]), "blockTuples": int(out[1]), "roundS": int(out[2]), "itemS": int(out[3])}
+
+
 class HashJoinContext:
     """One engine context bound to one GPU (hj_ctx). ``stream`` is a raw hipStream_t
     handle (e.g. torch.cuda.current_stream().cuda_stream); None = private stream."""
@@ -404,6 +423,63 @@ class HashJoinContext:
         self._check(lib.hj_prj_resident_info(self._h, out))
         return {"rPath": out[0], "sPath": out[1], "items": out[2], "splitPartitions": out[3],
                 "maxSPartition": out[4], "residentBytes": out[5]}
+
+    # ---- aggregating joins: COUNT / SUM / MIN / MAX per R row, without the pairs ----
+    def prj_agg_begin(self, specs):
+        """hj_prj_agg_begin: starts an aggregation over the resident R (built after reserve(..., keepRowIds=True)).
+        specs: 1 to HJ_AGG_MAX_COLS tuples (op, width, flags[, reserved]) -- op an HJ_AGG_* value, width 4 or 8 (0 for
+        HJ_AGG_COUNT), flags HJ_AGG_SIGNED or 0. Allocates and initialises the context's accumulators: 0 for COUNT and
+        SUM, the largest value of the type for MIN, the smallest for MAX."""
+        arr, n = _agg_specs(specs)
+        self._check(lib.hj_prj_agg_begin(self._h, arr, n))
+
+    def prj_probe_agg(self, dS_ptr, sSize, srcs):
+        """hj_prj_probe_agg_dev: prj_probe with its matches reduced. srcs: one tuple (src_ptr, valid_ptr) per column of
+        the begin -- device pointers, src one element per S tuple of the slice (0 for a COUNT), valid_ptr the validity
+        words of those elements or 0. For every match (s, r): the accumulator of r op= src[s] where s is valid, and r's
+        match count + 1. The accumulators persist across calls; totalMatches and sSize grow as under prj_probe."""
+        srcs = list(srcs)
+        arr = (_lib.hj_agg_src * max(len(srcs), 1))()
+        for a, (src, valid) in zip(arr, srcs):
+            a.src, a.srcValid = src or None, valid or None
+        self._check(lib.hj_prj_probe_agg_dev(self._h, C.c_void_p(dS_ptr) if dS_ptr else None, sSize, arr, len(srcs)))
+
+    def prj_agg_rows(self, d_outs, d_count=0):
+        """hj_prj_agg_rows_dev: the accumulators by R row. d_outs: one device pointer per column of the begin, each a plane
+        of rSize 8-byte entries; d_count (0: none): the same for the match counts. Every R row is written once; the
+        accumulators stay as they are."""
+        d_outs = list(d_outs)
+        arr = (C.c_void_p * max(len(d_outs), 1))(*[C.c_void_p(p) if p else None for p in d_outs])
+        self._check(lib.hj_prj_agg_rows_dev(self._h, arr if d_outs else None, C.c_void_p(d_count) if d_count else None))
+
+    def prj_agg_info(self):
+        """hj_prj_agg_info (waits for the stream): the matches of the last prj_probe_agg, its device time in microseconds,
+        the columns of the aggregation, the probes since prj_agg_begin, the R tuples its planes hold."""
+        out = (C.c_uint64 * 8)()
+        self._check(lib.hj_prj_agg_info(self._h, out))
+        return {"matches": int(out[0]), "us": int(out[1]), "nCols": int(out[2]), "probes": int(out[3]), "rows": int(out[4])}
+
+    def pairs_agg(self, d_map_g, d_map_v, n_pairs, g_base, g_rows, v_base, v_rows, cols, d_count=0):
+        """hj_pairs_agg_dev: the reduction over a pair list. For pair k, g = d_map_g[k] - g_base and v = d_map_v[k] -
+        v_base: acc[g] op= src[v] in every column, d_count[g] += 1. cols: up to HJ_AGG_MAX_COLS tuples (src_ptr, valid_ptr,
+        acc_ptr, op, width, flags[, reserved]); the accumulators (g_rows x 8 bytes each) and d_count are the caller's,
+        initialised by the caller. A pair that is NO_ROW or out of range on either side is skipped unread. d_map_v may be
+        0 when no column reads a value. One memory-side atomic per run of equal g within a wavefront and column."""
+        cols = [tuple(c) + (0,) * (7 - len(c)) for c in cols]
+        arr = (_lib.hj_agg_col * max(len(cols), 1))()
+        for a, (src, valid, acc, op, width, flags, reserved) in zip(arr, cols):
+            a.src, a.srcValid, a.acc = src or None, valid or None, acc or None
+            a.op, a.width, a.flags, a.reserved = op, width, flags, reserved
+        p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
+        self._check(lib.hj_pairs_agg_dev(self._h, p(d_map_g), p(d_map_v), n_pairs, g_base, g_rows, v_base, v_rows,
+                                         arr if cols else None, len(cols), p(d_count)))
+
+    def pairs_agg_info(self):
+        """hj_pairs_agg_info (waits for the stream): (pairs of the last pairs_agg, pairs it applied, its device time in
+        microseconds, pairs it skipped as NO_ROW or out of range)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_pairs_agg_info(self._h, out))
+        return tuple(int(x) for x in out)
 
     def join(self, dR_ptr, rSize, dS_ptr, sSize):
         """Build + probe by the reserved algo; "auto" samples R for locality and picks atomic or prj."""
@@ -1372,7 +1448,60 @@ def key_hash2_host(cols, key_mask=0):
     return out
 
 
-def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
+class _ColumnKeys:
+    """What join_on_columns and aggregate_on share: the key columns of both sides on the device (R's whole, a slice of
+    S's in the room kept for one), the hash of either side as _drive_join's `fill`, and the verify step of a slice's
+    candidates. dev: "cols" (the hj_key_col2 tuples), "s_marks" / "r_marks" (the two mark planes)."""
+
+    def __init__(self, r_keys, s_keys, nulls_equal, key_mask, step):
+        self.r_keys, self.s_keys, self.key_mask, self.step = r_keys, s_keys, key_mask, step
+        self.n_r, self.n_s = r_keys[0].rows, s_keys[0].rows
+        self.widths = [c.width for c in r_keys]
+        self.flags = [_lib.HJ_KEY_NULLS_EQUAL if nulls_equal or r.nulls_equal or s.nulls_equal else 0 for r, s in zip(r_keys, s_keys)]
+        self.dev = {}
+
+    @staticmethod
+    def _put(ctx, d, a):
+        if a is not None and a.nbytes:
+            ctx.copy_h2d(d, a)
+
+    def hash_keys(self, ctx, held, d_tuples, lo, n):
+        """R's key columns go up whole, a slice's into the room kept for one; either is hashed where it lies"""
+        dev, step = self.dev, self.step
+        if lo is None:
+            def up(a):      # a bytes buffer goes up in whole 32-bit words: the kernels read the aligned words of an element
+                if a is None:
+                    return 0
+                d = held.alloc(a.nbytes + 3 & ~3)
+                self._put(ctx, d, np.ascontiguousarray(a))
+                return d
+
+            r_dev = [tuple(up(a) for a in c.take(0, self.n_r)) for c in self.r_keys]
+            dev["s"] = [(held.alloc(_slice_bytes(c, self.n_s, step) + 3 & ~3), held.alloc(4 * (step + 1)) if c.offsets is not None else 0,
+                         held.alloc(4 * ((step + 31) // 32)) if c.valid is not None else 0) for c in self.s_keys]
+            dev["r_marks"] = held.put(np.zeros((self.n_r + 31) // 32, dtype=np.uint32))
+            dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))
+            dev["cols"] = [(s[0], r[0], w, s[1], r[1], s[2], r[2], f) for s, r, w, f in zip(dev["s"], r_dev, self.widths, self.flags)]
+            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_R, n, d_tuples, self.key_mask)
+        else:
+            for d, c in zip(dev["s"], self.s_keys):
+                for d_part, part in zip(d, c.take(lo, n)):
+                    self._put(ctx, d_part, part)
+            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, self.key_mask)
+
+    def verify(self, ctx, held, lo, n, d_s, d_r, candidates, pairs):
+        """the slice's candidates -> (its kept pairs' S plane, R plane, their number) -- the planes allocated from held and
+        the caller's to free; pairs False: a mark-only pass, (0, 0, 0) -- and the marks of both sides"""
+        dev = self.dev
+        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        capacity = candidates if pairs else 0
+        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
+        ctx.pairs_verify2(d_s, d_r, candidates, lo, n, self.n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        return d_ks, d_kr, (ctx.verify_info()[1] if pairs else 0)
+
+
+def join_on_columns(
+r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
                     device=0, key_mask=0):
     """join_on for key columns that may hold NULLs and variable-length elements (strings): r_keys / s_keys are each one
     KeyColumn or a sequence of 1 to HJ_KEY_MAX_COLS of them, all of a side of one length; a plain 1-D numpy array stands
@@ -1407,44 +1536,14 @@ def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls
         return trivial
     pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
     s_sweep = _ON_S_SWEEP.get(rows.kind)
-    flags = [_lib.HJ_KEY_NULLS_EQUAL if nulls_equal or r.nulls_equal or s.nulls_equal else 0 for r, s in zip(r_keys, s_keys)]
-    dev = {}
-
-    def put(ctx, d, a):
-        if a is not None and a.nbytes:
-            ctx.copy_h2d(d, a)
-
-    def hash_keys(ctx, held, d_tuples, lo, n):
-        """R's key columns go up whole, a slice's into the room kept for one; either is hashed where it lies"""
-        if lo is None:
-            def up(a):      # a bytes buffer goes up in whole 32-bit words: the kernels read the aligned words of an element
-                if a is None:
-                    return 0
-                d = held.alloc(a.nbytes + 3 & ~3)
-                put(ctx, d, np.ascontiguousarray(a))
-                return d
-
-            r_dev = [tuple(up(a) for a in c.take(0, n_r)) for c in r_keys]
-            dev["s"] = [(held.alloc(_slice_bytes(c, n_s, step) + 3 & ~3), held.alloc(4 * (step + 1)) if c.offsets is not None else 0,
-                         held.alloc(4 * ((step + 31) // 32)) if c.valid is not None else 0) for c in s_keys]
-            dev["r_marks"] = held.put(np.zeros((n_r + 31) // 32, dtype=np.uint32))
-            dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))
-            dev["cols"] = [(s[0], r[0], w, s[1], r[1], s[2], r[2], f) for s, r, w, f in zip(dev["s"], r_dev, widths, flags)]
-            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_R, n, d_tuples, key_mask)
-        else:
-            for d, c in zip(dev["s"], s_keys):
-                for d_part, part in zip(d, c.take(lo, n)):
-                    put(ctx, d_part, part)
-            ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, key_mask)
+    keys = _ColumnKeys(r_keys, s_keys, nulls_equal, key_mask, step)
+    dev = keys.dev
 
     def verify(ctx, held, lo, n, d_s, d_r, candidates):
         """the slice's candidates -> its kept pairs and the marks of both sides, then the rows of its kind"""
-        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
-        capacity = candidates if pairs else 0           # right_semi / right_anti, semi / anti: a mark-only pass
-        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
-        ctx.pairs_verify2(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        d_ks, d_kr, kept = keys.verify(ctx, held, lo, n, d_s, d_r, candidates, pairs)      # right_semi / right_anti, semi / anti: a mark-only pass
         if pairs:
-            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.verify_info()[1])
+            rows.add(ctx, held, lo, n, d_ks, d_kr, kept)
             held.free(d_ks, d_kr)
         if s_sweep is not None:
             d_rows = held.alloc(4 * n)
@@ -1461,11 +1560,218 @@ def join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls
     # as in join_on: the candidate join is INNER whatever the kind, on tuples made on the device (the two arrays stand for
     # the relations' lengths alone)
     _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step, verify, device,
-                radixBits=radixBits, fill=hash_keys, after=r_only)
+                radixBits=radixBits, fill=keys.hash_keys, after=r_only)
     return rows.joined()
 
 
-def PRO(relR, relS=None, nthreads=0, radixBits=0, device=0):
+# ---- aggregating joins: COUNT / SUM / MIN / MAX of S values per R row -----------------------------------------------------
+_AGG_DTYPES = {np.dtype(np.int32): (4, _lib.HJ_AGG_SIGNED), np.dtype(np.uint32): (4, 0),
+               np.dtype(np.int64): (8, _lib.HJ_AGG_SIGNED), np.dtype(np.uint64): (8, 0)}
+
+
+def _agg_identity(op, signed):
+    if op == _lib.HJ_AGG_MIN:
+        return 0x7FFFFFFFFFFFFFFF if signed else 0xFFFFFFFFFFFFFFFF
+    if op == _lib.HJ_AGG_MAX:
+        return 0x8000000000000000 if signed else 0
+    return 0
+
+
+class _AggPlan:
+    """The aggregates of radix_join_aggregate / aggregate_on, checked: cols -- the device columns, one dict each (op,
+    source name or None, width, flags), the wrapper's own COUNT(col) of every nullable source of a SUM / MIN / MAX behind
+    the caller's -- and how the result dict is put together from their planes. ValueError for what cannot be aggregated."""
+
+    def __init__(self, fn, s_cols, aggs, n_s):
+        self.fn, self.sources, self.cols, self.outputs = fn, {}, [], []
+        for name, col in dict(s_cols or {}).items():
+            c = col if isinstance(col, KeyColumn) else KeyColumn(col)
+            if c.offsets is not None or np.asarray(c.values).dtype not in _AGG_DTYPES:
+                raise ValueError(f"{fn}: column {name!r} is {np.asarray(c.values).dtype if c.offsets is None else 'variable-length'}; "
+                                 "int32, uint32, int64 and uint64 can be aggregated (floating-point sums depend on their order)")
+            if c.rows != n_s:
+                raise ValueError(f"{fn}: column {name!r} has {c.rows} rows, S has {n_s}")
+            self.sources[name] = c
+        if not aggs:
+            raise ValueError(f"{fn}: no aggregates")
+        seen = {}            # nullable source -> the device column of its COUNT(col)
+        for out, spec in dict(aggs).items():
+            if out == "count":
+                raise ValueError(f"{fn}: the output name 'count' is taken by the match counts")
+            if not isinstance(spec, (tuple, list)) or len(spec) != 2:
+                raise ValueError(f"{fn}: aggregate {out!r} must be (op, column name or None), not {spec!r}")
+            op, src = spec
+            if not isinstance(op, str) or op.lower() not in _lib.AGG_OPS:
+                raise ValueError(f"{fn}: aggregate {out!r} has op {op!r}; count, sum, min and max exist")
+            op = _lib.AGG_OPS[op.lower()]
+            if src is None and op != _lib.HJ_AGG_COUNT:
+                raise ValueError(f"{fn}: aggregate {out!r} needs a column")
+            if src is not None and src not in self.sources:
+                raise ValueError(f"{fn}: aggregate {out!r} names column {src!r}, which s_cols does not hold")
+            self.outputs.append((out, op, src, self._col(op, src)))
+        for out, op, src, _ in list(self.outputs):
+            if op != _lib.HJ_AGG_COUNT and self.sources[src].valid is not None and src not in seen:
+                seen[src] = self._col(_lib.HJ_AGG_COUNT, src)
+        self.seen = seen
+
+    def _col(self, op, src):
+        width, flags = (0, 0) if op == _lib.HJ_AGG_COUNT else _AGG_DTYPES[np.asarray(self.sources[src].values).dtype]
+        self.cols.append({"op": op, "src": src, "width": width, "flags": flags})
+        return len(self.cols) - 1
+
+    def rounds(self):
+        """the device columns in runs of at most HJ_AGG_MAX_COLS"""
+        return [list(range(i, min(i + _lib.HJ_AGG_MAX_COLS, len(self.cols)))) for i in range(0, len(self.cols), _lib.HJ_AGG_MAX_COLS)]
+
+    def identity(self, i):
+        return _agg_identity(self.cols[i]["op"], bool(self.cols[i]["flags"]))
+
+    def result(self, count, planes):
+        """count: the match counts (uint64 per R row); planes: one uint64 array per device column -> the result dict"""
+        res = {"count": count}
+        for out, op, src, i in self.outputs:
+            if op == _lib.HJ_AGG_COUNT:
+                res[out] = planes[i]
+                continue
+            valid = (planes[self.seen[src]] if src in self.seen else count) > 0
+            values = np.where(valid, planes[i], np.uint64(0))
+            res[out] = KeyColumn(values.view(np.int64) if self.cols[i]["flags"] else values, valid)
+        return res
+
+    def without_device(self, n_r):
+        zeros = np.zeros(n_r, dtype=np.uint64)
+        return self.result(zeros, [zeros.copy() for _ in self.cols])
+
+
+class _AggSources:
+    """the value columns of one S slice on the device: room for `step` elements and their validity words per source"""
+
+    def __init__(self, held, plan, step):
+        self.plan = plan
+        self.dev = {name: (held.alloc(c.width * step), held.alloc(4 * ((step + 31) // 32)) if c.valid is not None else 0)
+                    for name, c in plan.sources.items() if any(col["src"] == name for col in plan.cols)}
+
+    def put(self, ctx, lo, n, names=None):
+        for name, (d_v, d_valid) in self.dev.items():
+            if names is not None and name not in names:
+                continue
+            values, _, words = self.plan.sources[name].take(lo, n)
+            if values.nbytes:
+                ctx.copy_h2d(d_v, np.ascontiguousarray(values))
+            if d_valid:
+                ctx.copy_h2d(d_valid, words)
+
+    def pointers(self, i):
+        """(src, valid) of device column i; a COUNT reads no value"""
+        col = self.plan.cols[i]
+        if col["src"] is None:
+            return 0, 0
+        d_v, d_valid = self.dev[col["src"]]
+        return (0 if col["op"] == _lib.HJ_AGG_COUNT else d_v), d_valid
+
+
+def _fetch_plane(ctx, d, n):
+    a = np.empty(n, dtype=np.uint64)
+    if n:
+        ctx.copy_d2h(a, d)
+    return a
+
+
+def radix_join_aggregate(relR, relS, s_cols, aggs, radixBits=0, slice_tuples=None, device=0):
+    """GROUP BY <R row> over the equi-join of relR and relS on the key word, without the pairs: the fused group-join of the
+    resident radix join (hj_prj_probe_agg_dev). s_cols: {name: values}, one int32, uint32, int64 or uint64 element per S
+    tuple, as a numpy array or a KeyColumn with a validity (False: NULL). aggs: {output name: (op, column name or None)},
+    op "count" | "sum" | "min" | "max"; ("count", None) is COUNT(*), ("count", name) counts the valid elements.
+    Returns a dict: "count", the matches of every R row (uint64, len(relR)); per COUNT a uint64 array; per SUM / MIN /
+    MAX a KeyColumn of int64 (signed sources) or uint64 whose validity is "the group saw at least one valid value" -- an
+    empty group is NULL, as in SQL -- and whose values under a NULL are 0. SUM wraps modulo 2^64. R is partitioned once;
+    relS goes through in slices of slice_tuples (default: all at once), the accumulators adding up. More than
+    HJ_AGG_MAX_COLS device columns (the wrapper adds a COUNT of its own per nullable source) take several rounds over
+    the same resident R. ValueError for an unknown op, a column that is no 4- or 8-byte integer, a missing column, and
+    lengths that disagree."""
+    fn = "radix_join_aggregate"
+    relR = np.ascontiguousarray(relR, dtype=np.uint64)
+    relS = np.ascontiguousarray(relS, dtype=np.uint64)
+    plan = _AggPlan(fn, s_cols, aggs, relS.size)
+    if relR.size == 0 or relS.size == 0:
+        return plan.without_device(relR.size)
+    step = _slice_step(fn, relS.size, slice_tuples)
+    n_r = relR.size
+    planes = [None] * len(plan.cols)
+    with HashJoinContext(device) as ctx:
+        held = _Held(ctx)
+        try:
+            ctx.reserve("prj", n_r, step, radixBits=radixBits, keepRowIds=True)
+            ctx.prj_build(held.put(relR), n_r)
+            dS = held.alloc(8 * step)
+            sources = _AggSources(held, plan, step)
+            d_count = held.alloc(8 * n_r)
+            d_out = [held.alloc(8 * n_r) for _ in range(min(len(plan.cols), _lib.HJ_AGG_MAX_COLS))]
+            for cols in plan.rounds():
+                ctx.prj_agg_begin([(plan.cols[i]["op"], plan.cols[i]["width"], plan.cols[i]["flags"]) for i in cols])
+                names = {plan.cols[i]["src"] for i in cols}
+                for lo in range(0, relS.size, step):
+                    part = relS[lo:lo + step]
+                    ctx.copy_h2d(dS, part)
+                    sources.put(ctx, lo, part.size, names)
+                    ctx.prj_probe_agg(dS, part.size, [sources.pointers(i) for i in cols])
+                ctx.prj_agg_rows(d_out[:len(cols)], d_count)
+                for i, d in zip(cols, d_out):
+                    planes[i] = _fetch_plane(ctx, d, n_r)
+            count = _fetch_plane(ctx, d_count, n_r)
+        finally:
+            held.close()
+    return plan.result(count, planes)
+
+
+def aggregate_on(r_keys, s_keys, s_cols, aggs, nulls_equal=False, radixBits=0, slice_tuples=None, device=0, key_mask=0):
+    """radix_join_aggregate for joins on real key columns: GROUP BY <R row> over the inner join of join_on_columns(r_keys,
+    s_keys, nulls_equal=...), by its method -- key_hash2, the candidate join on the hashed word, pairs_verify2 -- with
+    hj_pairs_agg_dev over the KEPT pairs of each slice in place of the gather (a reduction over the candidates would
+    count what the verify step rejects). r_keys / s_keys, nulls_equal, radixBits, slice_tuples, key_mask: as in
+    join_on_columns; s_cols, aggs and the result dict: as in radix_join_aggregate, one entry per row of R."""
+    fn = "aggregate_on"
+    r_keys, s_keys = _as_key_columns(fn, "R", r_keys), _as_key_columns(fn, "S", s_keys)
+    widths = [c.width for c in r_keys]
+    if widths != [c.width for c in s_keys]:
+        raise ValueError(f"{fn}: the key columns of R have widths {widths} (0: variable-length), those of S {[c.width for c in s_keys]}")
+    if not 0 <= int(key_mask) <= 0xFFFFFFFF:
+        raise ValueError(f"{fn}: key_mask must fit 32 bits, not {key_mask!r}")
+    n_r, n_s = r_keys[0].rows, s_keys[0].rows
+    if max(n_r, n_s) > 0xFFFFFFFF:
+        raise ValueError(f"{fn}: a relation of more than 2^32 - 1 rows")
+    plan = _AggPlan(fn, s_cols, aggs, n_s)
+    if n_r == 0 or n_s == 0:
+        return plan.without_device(n_r)
+    step = _slice_step(fn, n_s, slice_tuples)
+    keys = _ColumnKeys(r_keys, s_keys, nulls_equal, key_mask, step)
+    dev, out = {}, {}
+
+    def reduce(ctx, held, lo, n, d_s, d_r, candidates):
+        """the slice's candidates -> its kept pairs -> the accumulators, grouped by the R plane"""
+        if not dev:
+            dev["sources"] = _AggSources(held, plan, step)
+            dev["count"] = held.put(np.zeros(n_r, dtype=np.uint64))
+            dev["acc"] = [held.put(np.full(n_r, plan.identity(i), dtype=np.uint64)) for i in range(len(plan.cols))]
+        d_ks, d_kr, kept = keys.verify(ctx, held, lo, n, d_s, d_r, candidates, True)
+        dev["sources"].put(ctx, lo, n)
+        for k, cols in enumerate(plan.rounds()):
+            ctx.pairs_agg(d_kr, d_ks, kept, 0, n_r, lo, n,
+                          [dev["sources"].pointers(i) + (dev["acc"][i], plan.cols[i]["op"], plan.cols[i]["width"], plan.cols[i]["flags"])
+                           for i in cols], dev["count"] if k == 0 else 0)
+        held.free(d_ks, d_kr)
+
+    def fetch(ctx, held):
+        out["count"] = _fetch_plane(ctx, dev["count"], n_r)
+        out["planes"] = [_fetch_plane(ctx, d, n_r) for d in dev["acc"]]
+
+    _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step, reduce, device,
+                radixBits=radixBits, fill=keys.hash_keys, after=fetch)
+    return plan.result(out["count"], out["planes"])
+
+
+def PRO(
+relR, relS=None, nthreads=0, radixBits=0, device=0):
     """mc/src/parallel_radix_join.c:1305 (algos[] entry, mc/src/main.c:292-301).
     Returns the join cardinality and the fork's printed checksum ("Results")."""
     relR = np.asarray(relR, dtype=np.uint64)

@@ -544,6 +544,108 @@ int hj_prj_probe_pairs_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, uint
  * HJ_JOIN_ANTI the S tuples of a partition that holds no R tuple are rows as well. Asynchronous. */
 int hj_prj_probe_join_dev(hj_ctx *ctx, uint32_t kind, const uint64_t *dS, uint64_t sSize, uint64_t sIdxBase,
                           uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity);
+/* ---- aggregating joins: COUNT / SUM / MIN / MAX of S values per R row, without the pairs ----
+ * A join that feeds GROUP BY <R row> needs no pair: the resident radix join has R's partition in an LDS table while the S
+ * tuples of that partition stream past it, so the per-R-row accumulators are updated in LDS and leave for memory once per
+ * work item. hj_prj_agg_begin names the columns and allocates the accumulators, hj_prj_probe_agg_dev adds one S slice to
+ * them (R is built once, S arrives in slices), hj_prj_agg_rows_dev writes them out by R row, at any time.
+ * Integer columns only: every accumulator is 64 bits wide, a 4-byte value is sign-extended (HJ_AGG_SIGNED) or zero-extended
+ * to it, SUM wraps modulo 2^64, and every result is independent of the order of the adds -- exact, like everything else
+ * this library returns. Floating-point columns are out of scope for that reason: an atomic float sum depends on the order
+ * its terms arrive in, and no tolerance is offered instead. Values of 1 or 2 bytes are widened by the caller. */
+#define HJ_AGG_MAX_COLS 4
+typedef enum { HJ_AGG_COUNT = 0, HJ_AGG_SUM = 1, HJ_AGG_MIN = 2, HJ_AGG_MAX = 3 } hj_agg_op;
+#define HJ_AGG_SIGNED 0x1u   /* hj_agg_spec.flags / hj_agg_col.flags: the values are signed (extension of 4-byte values; MIN and MAX) */
+typedef struct {
+    uint32_t op;         /* hj_agg_op                                                        */
+    uint32_t width;      /* bytes of a source element: 4 or 8; 0 for HJ_AGG_COUNT            */
+    uint32_t flags;      /* HJ_AGG_SIGNED or 0                                               */
+    uint32_t reserved;   /* 0                                                                */
+} hj_agg_spec;           /* 16 bytes */
+typedef struct {
+    const void     *src;      /* device: one element of the spec's width per S tuple of the slice, indexed by the position in
+                                 dS; aligned to the width. HJ_AGG_COUNT: ignored, may be NULL                               */
+    const uint32_t *srcValid; /* NULL: no NULLs. Else the plane hj_gather_dev writes: bit i & 31 of word i >> 5, 1 = valid,
+                                 ceil(sSize / 32) words                                                                     */
+} hj_agg_src;                 /* 16 bytes */
+/* Starts an aggregation of nCols (1 .. HJ_AGG_MAX_COLS) columns over the resident R, which must have been built on a
+ * context reserved with HJ_FLAG_KEEP_ROW_IDS. Allocates the context-owned accumulators (a buffer that only grows): one
+ * 64-bit match-count plane and nCols 64-bit accumulator planes of rSize entries each, indexed by RESIDENT POSITION -- the
+ * tuple's place in the partitioned R -- not by R row, so that the entries a work item updates are one contiguous range.
+ * Initialises them on the stream: COUNT and SUM 0; MIN INT64_MAX with HJ_AGG_SIGNED, else UINT64_MAX; MAX INT64_MIN with
+ * HJ_AGG_SIGNED, else 0. A second begin starts over. hj_prj_build_dev, hj_prj_join_dev, hj_build_dev (every call that
+ * starts a new operation) and an hj_reserve that reallocates end the aggregation. `specs` is host memory, read before the
+ * call returns. Asynchronous.
+ * HJ_ERR_STATE: no resident R, or one built without HJ_FLAG_KEEP_ROW_IDS. HJ_ERR_INVALID: nCols 0 or above
+ * HJ_AGG_MAX_COLS; specs NULL; an op above HJ_AGG_MAX; a width other than 4 or 8 (HJ_AGG_COUNT: other than 0); a flag bit
+ * other than HJ_AGG_SIGNED; reserved != 0. */
+int hj_prj_agg_begin(hj_ctx *ctx, const hj_agg_spec *specs, uint32_t nCols);
+/* hj_prj_probe_dev with its matches reduced: the complete equi-join of dS[0..sSize) with the resident R on the key word,
+ * duplicate keys on both sides included, key 0 an ordinary key. For every match (s, r) and column c:
+ * acc[c][r] op= value(src[c][s]), and the match count of r grows by 1. An S element whose srcValid bit is 0 contributes
+ * nothing to that column and its bytes are never read; the bytes of an S element without a match are never read either.
+ * HJ_AGG_COUNT with a srcValid counts the valid elements (COUNT(col)), without one the matches (COUNT(*)). The
+ * accumulators persist across calls. totalMatches and sSize grow exactly as under hj_prj_probe_dev; hj_pairs_info, the R
+ * marks and every other *_info but hj_prj_resident_info (whose work items are those of the last probe of any kind) are
+ * untouched. `srcs` is host memory, read before the call returns. Asynchronous. sSize 0 is a no-op.
+ * Cost: the slice's row-id passes as under hj_prj_probe_pairs_dev; one scattered read per matched valid element and
+ * column; per work item one 64-bit global atomic per R tuple that was hit and column, at contiguous addresses. An R
+ * partition larger than one LDS build (hj_prj_agg_layout_info: fewer tuples the more columns) is probed once per build.
+ * HJ_ERR_STATE: no resident R; no hj_prj_agg_begin since the last build; sSize above the reserved one. HJ_ERR_INVALID:
+ * nCols differs from the begin's; srcs NULL; a src that is NULL (but for HJ_AGG_COUNT) or not aligned to its width; a
+ * srcValid that is not 4-byte aligned. */
+int hj_prj_probe_agg_dev(hj_ctx *ctx, const uint64_t *dS, uint64_t sSize, const hj_agg_src *srcs, uint32_t nCols);
+/* Resident order -> R rows: for every resident position pos, with row = the tuple's position in the dR given to
+ * hj_prj_build_dev, dOut[c][row] = acc[c][pos] for the begin's nCols columns and, unless NULL, dOutCount[row] = the match
+ * count. dOut: host array of nCols device pointers to planes of rSize x 8 bytes. Plain stores; every R row is written
+ * exactly once, nothing behind rSize entries. A row that never matched holds count 0 and the identities of the begin.
+ * Changes no accumulator: a later slice and a later call keep working. Asynchronous.
+ * HJ_ERR_STATE as hj_prj_probe_agg_dev. HJ_ERR_INVALID: dOut NULL; a plane that is NULL or not 8-byte aligned. */
+int hj_prj_agg_rows_dev(hj_ctx *ctx, void *const *dOut, uint64_t *dOutCount);
+/* Waits for the stream. out[0] = matches of the last hj_prj_probe_agg_dev since the begin, out[1] = its device time in
+ * microseconds (rounded), out[2] = nCols, out[3] = probes since the begin, out[4] = R tuples the planes hold, out[5..7] = 0.
+ * All 0 without an aggregation. */
+int hj_prj_agg_info(hj_ctx *ctx, uint64_t out[8]);
+/* Host-only arithmetic, no context: the LDS layout of the aggregating join for nCols columns. out[0] = table slots, out[1] =
+ * R tuples per LDS build (at most 0.75 x slots), out[2] = S elements per round of a workgroup, out[3] = S tuples per work
+ * item at most. Per build the LDS holds out[1] x (4 + 8 nCols) bytes of counts and accumulators and out[0] x 6 bytes of
+ * table (a 4-byte key remainder and a 2-byte position per slot), within 160 KiB. HJ_ERR_INVALID: nCols 0 or above
+ * HJ_AGG_MAX_COLS; out NULL. */
+int hj_prj_agg_layout_info(uint32_t nCols, uint64_t out[4]);
+/* The same reduction over a pair list, for the joins whose pairs must exist first: hj_pairs_verify_dev's kept pairs
+ * (joins on real key columns) and the planes of the table probes. */
+typedef struct {
+    const void     *src;      /* device: vRows elements of `width` bytes, aligned to it. HJ_AGG_COUNT: ignored, may be NULL */
+    const uint32_t *srcValid; /* NULL: no NULLs. Else one bit per element of src, ceil(vRows / 32) words                    */
+    void           *acc;      /* device: gRows accumulators of 8 bytes, owned AND INITIALISED by the caller                 */
+    uint32_t        op;       /* hj_agg_op                                                                                   */
+    uint32_t        width;    /* 4 or 8; 0 for HJ_AGG_COUNT                                                                  */
+    uint32_t        flags;    /* HJ_AGG_SIGNED or 0                                                                          */
+    uint32_t        reserved; /* 0                                                                                           */
+} hj_agg_col;                 /* 40 bytes */
+/* For pair k in [0, nPairs), with g = dMapG[k] - gBase and v = dMapV[k] - vBase: acc[c][g] op= value(src[c][v]) for every
+ * column c whose element v is valid, and dCount[g] += 1 (dCount may be NULL; gRows x 8 bytes, the caller's, initialised by
+ * the caller). Either map may be the S plane or the R plane of a pairs call: grouping by S row while aggregating R values
+ * is the same call with the maps swapped. A pair whose raw entry is HJ_NO_ROW on either side, or with g >= gRows or v >=
+ * vRows, is never dereferenced: it is skipped and counted apart (hj_pairs_agg_info out[3]), as in hj_pairs_verify_dev.
+ * dMapV may be NULL when no column reads a value or a validity (HJ_AGG_COUNT without srcValid, or nCols 0 with a dCount).
+ * Values, ops and exactness as for hj_prj_probe_agg_dev. `cols` is host memory, read before the call returns. Needs no
+ * table, no hj_reserve and no state; touches no counter of hj_result and no other *_info. Asynchronous.
+ * Cost, stated plainly: neighbouring lanes of a wavefront whose pairs name the same g combine their values first (a
+ * segmented reduction over 64 pairs) and the last lane of such a run issues the atomic, so the call costs ONE MEMORY-SIDE
+ * ATOMIC REQUEST PER RUN AND COLUMN, each its own scattered 64-byte request. The radix join emits a hot R row's pairs in
+ * runs; a list without runs pays one request per pair and column, the worst shape this chip has for global atomics.
+ * Where the join is on the key word itself, hj_prj_probe_agg_dev avoids both the pairs and these requests.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): nCols above HJ_AGG_MAX_COLS; cols NULL with nCols > 0;
+ * nCols 0 and dCount NULL; the op, width, flags and reserved errors of hj_prj_agg_begin; an acc that is NULL or not 8-byte
+ * aligned; with vRows > 0 a src that is NULL (but for HJ_AGG_COUNT) or not aligned to its width; a srcValid that is not
+ * 4-byte aligned; dMapG NULL with nPairs > 0; dMapV NULL with nPairs > 0 and a column that has a width or a srcValid;
+ * dCount not 8-byte aligned; nPairs, gRows or vRows above 2^32 - 1. nPairs 0 is a call that applied nothing. */
+int hj_pairs_agg_dev(hj_ctx *ctx, const uint32_t *dMapG, const uint32_t *dMapV, uint64_t nPairs, uint32_t gBase, uint64_t gRows,
+                     uint32_t vBase, uint64_t vRows, const hj_agg_col *cols, uint32_t nCols, uint64_t *dCount);
+/* Waits for the stream. About the last hj_pairs_agg_dev: out[0] = its nPairs, out[1] = pairs applied, out[2] = its device
+ * time in microseconds (rounded), out[3] = pairs skipped as HJ_NO_ROW or out of range. All 0 before the first call. */
+int hj_pairs_agg_info(hj_ctx *ctx, uint64_t out[4]);
 /* Host-visible facts about the resident build and the last probe (waits for the stream), out[8]:
  * [0] R's path (0 exact, 1 histogram-free, 2 fell back), [1] last probe's S path (same coding),
  * [2] join work items of the last probe (after an HJ_JOIN_LEFT / HJ_JOIN_ANTI call they include the items of partitions
