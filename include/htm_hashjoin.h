@@ -207,6 +207,10 @@ int hj_reserve(hj_ctx *ctx, const hj_params *params, uint64_t rSize, uint64_t sS
  * table and inserts dR[0..rSize). Asynchronous on the context's stream, also
  * with buildVariant 0: the locality pre-round's decision is taken and acted on
  * by the device (no read-back), hj_result.buildVariant reports it afterwards.
+ * Not so under HJ_ALGO_HTM: that build waits for the stream once, to read the
+ * conflict count back and size the overflow area (with buildVariant 0 once
+ * more, for the locality sample). INTEGRATION.md, "Stream contract", says for
+ * every entry point whether it waits.
  * idxBase = global index of dR[0] (0 unless R is a shard of a larger input). */
 int hj_build_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize, uint64_t idxBase);
 /* HOT LOOP 2 (NoCCHashBuild.hpp:66-80): probes dS[0..sSize) against the table
@@ -654,7 +658,8 @@ int hj_pairs_agg_info(hj_ctx *ctx, uint64_t out[4]);
 int hj_prj_resident_info(hj_ctx *ctx, uint64_t out[8]);
 /* Build + probe of dR x dS by whatever hj_reserve was given: HJ_ALGO_NOCC/ATOMIC/HTM = hj_build_dev(idxBase 0) then
  * hj_probe_dev; HJ_ALGO_PRJ = hj_prj_join_dev; HJ_ALGO_AUTO = one locality pre-round over dR (k_sample_locality, one
- * small device->host read-back) and then one of the two. Asynchronous apart from that read-back. */
+ * small device->host read-back) and then one of the two. Asynchronous apart from that read-back and, under HJ_ALGO_HTM,
+ * the read-back of hj_build_dev. */
 int hj_join_dev(hj_ctx *ctx, const uint64_t *dR, uint64_t rSize,
                 const uint64_t *dS, uint64_t sSize);
 /* The untimed reductions of NoCCHashBuild.hpp:85-113 (table sums). Async. */
@@ -842,7 +847,10 @@ int hj_generate_data(const char *dist, uint64_t n, uint64_t distinct, int window
  * rand() stream where the last call stopped and writes the next n draws to dOut as 8-byte tuples: the host produces
  * only the serial rand() values, the binary search of genzipf.c:118-151 runs on the GPU. The concatenation of the
  * slices equals hj_generate_relation("zipf", total, alphabet, 0, theta, seed, ...) element for element (seed 0:
- * hj_generate_data("zipf")). Asynchronous on the context's stream apart from the host's own drawing. */
+ * hj_generate_data("zipf")). The work is enqueued on the context's stream, but the call is not asynchronous: the host draws
+ * the rand() values itself into one of two pinned buffers and, before it reuses one, waits for the event behind the call that
+ * used it last -- so a third call in a row blocks until the first has run on the device. hj_zipf_open and hj_zipf_close wait
+ * for the stream. */
 int hj_zipf_open(hj_ctx *ctx, uint64_t alphabetSize, double theta, unsigned seed);
 int hj_zipf_next_dev(hj_ctx *ctx, uint64_t n, uint64_t *dOut);
 int hj_zipf_close(hj_ctx *ctx);
