@@ -44,6 +44,11 @@ HJ_KEY_MAX_COLS = 4
 HJ_KEY_SIDE_S, HJ_KEY_SIDE_R = 0, 1
 # hj_key_col2.flags: in this column a NULL equals a NULL
 HJ_KEY_NULLS_EQUAL = 0x1
+# hj_pairs_where_dev: terms of one call, the comparison of a term (hj_cmp_op) and how its elements are read (hj_val_type)
+HJ_WHERE_MAX_TERMS = 4
+HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE = 0, 1, 2, 3, 4, 5
+CMP_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
+HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT = 0, 1, 2
 # aggregating joins (hj_agg_op, hj_agg_spec.flags)
 HJ_AGG_MAX_COLS = 4
 HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
@@ -134,6 +139,19 @@ class hj_key_col2(C.Structure):
     ]
 
 
+class hj_where_term(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p),
+        ("r", C.c_void_p),
+        ("sValid", C.c_void_p),
+        ("rValid", C.c_void_p),
+        ("width", C.c_uint32),
+        ("type", C.c_uint32),
+        ("op", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class hj_agg_spec(C.Structure):
     _fields_ = [
         ("op", C.c_uint32),
@@ -195,6 +213,9 @@ def _declare(lib):
         "hj_key_hash2_dev": ([vp, P(hj_key_col2), u32, u32, u64, u32, vp], i32),
         "hj_key_hash2_host": ([P(hj_key_col2), u32, u32, u64, u32, vp], i32),
         "hj_pairs_verify2_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col2), u32, vp, vp, u64, vp, vp], i32),
+        "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
+        "hj_where_info": ([vp, P(u64)], i32),
+        "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),
         "hj_mark_rows_dev": ([vp, vp, u64, u32, u32, vp, u64], i32),
         "hj_mark_rows_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),

@@ -1,6 +1,6 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), and the *_info entry point of every call that has
-// a record (hj_host.h: CallRecord). Host-side glue only.
+// joins on real key columns (hash, verify, sweep of a caller's plane), the join conditions beyond equality, and the
+// *_info entry point of every call that has a record (hj_host.h: CallRecord). Host-side glue only.
 #include "hj_host.h"
 
 using namespace hjapi;
@@ -349,6 +349,65 @@ int hj_verify_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
     return call_info(c, c->call[CALL_VERIFY], c->buf[B_VERIFY_CTR].p, 16, out);     // pairs kept, candidates dropped
+}
+
+// ---- join conditions beyond equality (hj_where.hip) --------------------------
+// hj_pairs_where_dev's and hj_pairs_where_host's arguments -> the kernel's terms; the message of what is wrong, or nullptr
+static const char* where_args(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint64_t sRows, uint64_t rRows,
+                              const hj_where_term* terms, uint32_t nTerms, const uint32_t* outS, const uint32_t* outR, uint64_t capacity,
+                              WhereTerms* k)
+{
+    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull) return "nPairs, sRows or rRows above 2^32 - 1";
+    if (nTerms == 0 || nTerms > HJ_WHERE_MAX_TERMS) return "nTerms must be 1 .. HJ_WHERE_MAX_TERMS";
+    if (!terms) return "terms NULL";
+    for (uint32_t i = 0; i < nTerms; ++i) {
+        const hj_where_term& t = terms[i];
+        if (t.type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
+        if (t.op > HJ_CMP_GE) return "op must be an hj_cmp_op";
+        const bool widthOk = t.width == 4 || t.width == 8 || (t.type != HJ_VAL_FLOAT && (t.width == 1 || t.width == 2));
+        if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
+        if (t.reserved) return "hj_where_term.reserved must be 0";
+        if (sRows && !col_ptr_ok(t.s, t.width)) return "an s pointer that is NULL or not aligned to its width";
+        if (rRows && !col_ptr_ok(t.r, t.width)) return "an r pointer that is NULL or not aligned to its width";
+        if (!word_ptr_ok(t.sValid) || !word_ptr_ok(t.rValid)) return "a validity pointer that is not 4-byte aligned";
+        k->s[i] = t.s; k->r[i] = t.r; k->sValid[i] = t.sValid; k->rValid[i] = t.rValid;
+        k->width[i] = t.width; k->type[i] = t.type; k->op[i] = t.op;
+    }
+    if (nPairs && (!mapS || !mapR)) return "a map NULL with nPairs > 0";
+    if (nPairs && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
+    return nullptr;
+}
+
+int hj_pairs_where_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                       uint64_t rRows, const hj_where_term* terms, uint32_t nTerms, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                       uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    WhereTerms k{};
+    if (const char* what = where_args(dMapS, dMapR, nPairs, sRows, rRows, terms, nTerms, dOutS, dOutR, capacity, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_where_dev", what);
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_WHERE_CTR].as<unsigned long long>()};
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, hipEventRecord(c->call[CALL_WHERE].ev[0], c->stream));
+    HJ_HIP(c, launch_pairs_where(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nTerms, out, dSMarks, dRMarks, c->stream));
+    return call_end(c, CALL_WHERE, capacity, nPairs);
+}
+
+int hj_where_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    return call_info(c, c->call[CALL_WHERE], c->buf[B_WHERE_CTR].p, 16, out);       // pairs kept, pairs dropped
+}
+
+int hj_pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows, uint64_t rRows,
+                        const hj_where_term* terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
+                        uint32_t* rMarks, uint64_t info[4])
+{
+    WhereTerms k{};
+    if (where_args(mapS, mapR, nPairs, sRows, rRows, terms, nTerms, outS, outR, capacity, &k)) return HJ_ERR_INVALID;
+    pairs_where_host(mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nTerms, outS, outR, capacity, sMarks, rMarks, info);
+    return HJ_OK;
 }
 
 // ---- the reduction over a pair list (hj_agg.hip) ----------------------------

@@ -733,6 +733,26 @@ hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint
                                 uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
                                 hipStream_t s);
 
+// ---- join conditions beyond equality (defined in hj_where.hip) ----------------
+// The terms of a call as the kernel takes them, by value in the kernel arguments (hj_where_term, include/htm_hashjoin.h):
+// term t holds for the pair (s, r) when s[t][s] op[t] r[t][r], both elements of width[t] bytes read as type[t], and neither
+// is NULL (sValid / rValid: the validity plane of that side, null: no NULLs).
+constexpr uint32_t kWhereMaxTerms = 4;        // HJ_WHERE_MAX_TERMS
+constexpr uint32_t kCmpEq = 0, kCmpNe = 1, kCmpLt = 2, kCmpLe = 3, kCmpGt = 4, kCmpGe = 5;     // hj_cmp_op
+constexpr uint32_t kValUint = 0, kValInt = 1, kValFloat = 2;                                  // hj_val_type
+struct WhereTerms { const void* s[kWhereMaxTerms]; const void* r[kWhereMaxTerms]; const uint32_t* sValid[kWhereMaxTerms];
+                    const uint32_t* rValid[kWhereMaxTerms]; uint32_t width[kWhereMaxTerms], type[kWhereMaxTerms], op[kWhereMaxTerms]; };
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `out` as launch_pairs_verify writes its kept pairs
+// (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the pairs dropped as HJ_NO_ROW or outside sRows /
+// rRows, which are never dereferenced); the marks as there. The caller has checked the terms and nPairs <= 2^32 - 1.
+hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                              uint32_t rRows, const WhereTerms& terms, uint32_t nTerms, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                              hipStream_t s);
+// the same pairs in a host loop over host pointers, the kept ones in input order; info: kept, written, 0, dropped (may be null)
+void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
+                      const WhereTerms& terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
+                      uint32_t* rMarks, uint64_t* info);
+
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):
 // pass 1 cuts the relation into C1 chunks and writes bin b of chunk c to the fragment (b * C1 + c) of cap1 key slots;

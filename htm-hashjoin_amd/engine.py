@@ -13,6 +13,7 @@ same fields as a dict. Every operator runs on the GPU through the C ABI; without
 a gfx950 device they raise HashJoinError(HJ_ERR_NO_DEVICE).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -151,6 +152,16 @@ def _key_cols2(cols):
         c.s, c.r, c.sOffsets, c.rOffsets, c.sValid, c.rValid = (p or None for p in (s, r, s_off, r_off, s_valid, r_valid))
         c.width, c.flags = width, flags
     return arr, len(cols)
+
+
+def _where_terms_arr(terms):
+    """[(s_ptr, r_ptr, width, type, op, s_valid, r_valid)], the two planes optional (0) -> (hj_where_term array, its length)"""
+    terms = [tuple(t) + (0,) * (7 - len(t)) for t in terms]
+    arr = (_lib.hj_where_term * max(len(terms), 1))()
+    for a, (s, r, width, type_, op, s_valid, r_valid) in zip(arr, terms):
+        a.s, a.r, a.sValid, a.rValid = (p or None for p in (s, r, s_valid, r_valid))
+        a.width, a.type, a.op, a.reserved = width, type_, op, 0
+    return arr, len(terms)
 
 
 def _agg_specs(specs):
@@ -376,6 +387,28 @@ class HashJoinContext:
         microseconds, candidates it dropped as NO_ROW or out of range); rejected = n_pairs - kept - dropped."""
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_verify_info(self._h, out))
+        return tuple(int(x) for x in out)
+
+    # ---- join conditions beyond equality ------------------------------------------
+    def pairs_where(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, terms, d_out_s, d_out_r, capacity,
+                    d_s_marks=0, d_r_marks=0):
+        """hj_pairs_where_dev: of the n_pairs pairs (d_map_s[k] - s_row_base, d_map_r[k]) -- the planes of an inner probe, or
+        the kept pairs of pairs_verify -- keeps those for which every term holds. terms = 1 to HJ_WHERE_MAX_TERMS tuples
+        (s_ptr, r_ptr, width, type, op, s_valid, r_valid) of device pointers, the two validity planes optional (0: no
+        NULLs): the term is s[si] op r[ri] with op an hj_cmp_op (CMP_OPS) and the elements of `width` bytes read as type
+        HJ_VAL_UINT / HJ_VAL_INT (1, 2, 4, 8 bytes) or HJ_VAL_FLOAT (4, 8: IEEE-754, -0.0 == 0.0, a NaN is unordered). A
+        term with a NULL on either side does not hold. Outputs, marks, dropped pairs and aliasing as in pairs_verify.
+        Asynchronous; needs no reserve and no table."""
+        arr, n = _where_terms_arr(terms)
+        p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
+        self._check(lib.hj_pairs_where_dev(self._h, p(d_map_s), p(d_map_r), n_pairs, s_row_base, s_rows, r_rows, arr, n,
+                                           p(d_out_s), p(d_out_r), capacity, p(d_s_marks), p(d_r_marks)))
+
+    def where_info(self):
+        """hj_where_info (waits for the stream): (pairs the last pairs_where kept, pairs it wrote, its device time in
+        microseconds, pairs it dropped as NO_ROW or out of range); rejected = n_pairs - kept - dropped."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_where_info(self._h, out))
         return tuple(int(x) for x in out)
 
     def mark_rows(self, d_marks, rows, row_base, which, d_out, capacity):
@@ -1164,6 +1197,18 @@ class _TableRows:
                            _concat_side(self.s_parts, self.s_cols), _concat_side(self.r_parts, self.r_cols))
 
 
+def _where_keyword(impl):
+    """The keyword where= on a join: the decorated function keeps its parameters and, called without where=, runs as it is; a
+    call with where= goes to `impl`, the function of this module that takes the same arguments and the condition."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def join(*args, where=None, **kw):
+            return fn(*args, **kw) if where is None else globals()[impl](*args, where=where, **kw)
+        return join
+    return deco
+
+
+@_where_keyword("_join_tables")
 def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", probeLength=4, radixBits=0, slice_tuples=None,
                 device=0):
     """The joined rows: the key tuples relR / relS as join_pairs takes them, and payload columns of either side (r_cols /
@@ -1177,7 +1222,22 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     columns per side as {name: array of the input dtype} and one bool per row and side (False: the row has no tuple of
     that side, its columns are all-zero bytes). A side the kind has no plane for (R for semi / anti, S for right_semi /
     right_anti) is None in all three. For right / full the R-only rows follow the probe's rows, R ascending.
+    where (keyword only): a condition on the matched pair beside the key's equality -- a sequence of 1 to HJ_WHERE_MAX_TERMS terms
+    (s_values, op, r_values), op out of "==", "!=", "<", "<=", ">", ">=", the values 1-D numpy arrays of len(relS) / len(relR)
+    elements (a numpy.ma.MaskedArray or a fixed-width KeyColumn brings NULLs) of one dtype out of uint8..uint64, int8..int64,
+    float32, float64; there is no implicit cast. A pair is a match iff the keys are equal and every term holds; a term with
+    a NULL on either side does not hold; floats compare as IEEE-754 (-0.0 == 0.0, a NaN is unordered). The condition
+    belongs to the match: an S row whose pairs all fail it is an unmatched row of left / anti, and likewise R. The probe
+    then gives the INNER pairs of the path, HashJoinContext.pairs_where keeps those that pass and marks their rows, and the
+    kind follows from the kept pairs and the sweeps of the marks; the order of the rows is join_on's. None or an empty
+    sequence: no condition.
     Every path joins on one 32-bit word of a tuple; for a 64-bit key, a key of several columns or a 16-byte key: join_on."""
+    return _join_tables(relR, relS, r_cols, s_cols, how, path, probeLength, radixBits, slice_tuples, device)
+
+
+def _join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", probeLength=4, radixBits=0, slice_tuples=None,
+                 device=0, where=None):
+    """join_tables, and join_tables with a condition (_where_keyword)"""
     fn = "join_tables"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1188,10 +1248,18 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     r_cols = _table_columns(fn, "R", r_cols, relR.size)
     s_cols = _table_columns(fn, "S", s_cols, relS.size)
     step = _slice_step(fn, relS.size, slice_tuples) if path == "radix" and relS.size else relS.size
+    terms = _where_terms(fn, where, relS.size, relR.size)
     rows = _TableRows(how, r_cols, s_cols, relR.size, step, relS.size)
     trivial = rows.without_device(relS.size)
     if trivial is not None:
         return trivial
+    if terms is not None:
+        # as in join_on: the probe is INNER whatever the kind, and the context's own R marks stay out of it -- a pair that
+        # the condition rejects would have set them
+        cond = _WhereTerms(terms, rows, relR.size, relS.size, step)
+        _drive_join(relR, relS, path, _lib.HJ_JOIN_INNER, None, step, cond.slice, device, probeLength=probeLength, radixBits=radixBits,
+                    after=cond.r_only)
+        return rows.joined()
     _drive_join(relR, relS, path, rows.kind, rows.which, step, rows.add, device, probeLength=probeLength, radixBits=radixBits)
     return rows.joined()
 
@@ -1241,6 +1309,7 @@ def key_hash_host(cols, key_mask=0):
 _ON_S_SWEEP = {_lib.HJ_JOIN_LEFT: _lib.HJ_R_UNMATCHED, _lib.HJ_JOIN_SEMI: _lib.HJ_R_MATCHED, _lib.HJ_JOIN_ANTI: _lib.HJ_R_UNMATCHED}
 
 
+@_where_keyword("_join_on")
 def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0):
     """join_tables for keys that are not one 32-bit word: r_keys / s_keys are each one 1-D numpy array or a sequence of 1
     to HJ_KEY_MAX_COLS of them (all of a side of one length; column c of both sides of the same itemsize out of 1, 2, 4,
@@ -1253,7 +1322,15 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     candidates, the same result -- for tests; the result never depends on the hash's quality.
     how, r_cols / s_cols, radixBits, slice_tuples and the result -- {"s_idx", "r_idx", "s", "r", "s_valid", "r_valid"} -- as
     in join_tables(path="radix"). Per slice, left and full give the kept pairs first, then the slice's unmatched S rows
-    ascending; semi and anti give their S rows ascending; for right / full the R-only rows come last, R ascending."""
+    ascending; semi and anti give their S rows ascending; for right / full the R-only rows come last, R ascending.
+    where (keyword only): as in join_tables -- a pair is a match iff the keys are equal and every term holds. The verify step then runs
+    without mark planes and with its pairs kept whatever the kind, and HashJoinContext.pairs_where over those pairs sets the
+    marks and keeps the pairs of the result."""
+    return _join_on(r_keys, s_keys, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask)
+
+
+def _join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0, where=None):
+    """join_on, and join_on with a condition (_where_keyword)"""
     fn = "join_on"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1269,12 +1346,14 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     r_cols = _table_columns(fn, "R", r_cols, n_r)
     s_cols = _table_columns(fn, "S", s_cols, n_s)
     step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
+    terms = _where_terms(fn, where, n_s, n_r)
     rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
     trivial = rows.without_device(n_s)
     if trivial is not None:
         return trivial
     pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
     s_sweep = _ON_S_SWEEP.get(rows.kind)
+    cond = _WhereTerms(terms, rows, n_r, n_s, step) if terms is not None else None
     dev = {}
 
     def hash_keys(ctx, held, d_tuples, lo, n):
@@ -1306,6 +1385,13 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
             rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
             held.free(d_rows)
 
+    def verify_where(ctx, held, lo, n, d_s, d_r, candidates):
+        """the slice's candidates -> the pairs with equal keys, no plane marked; the condition step takes it from there"""
+        d_es, d_er = held.alloc(4 * candidates), held.alloc(4 * candidates)
+        ctx.pairs_verify(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_es, d_er, candidates)
+        cond.slice(ctx, held, lo, n, d_es, d_er, ctx.verify_info()[1])
+        held.free(d_es, d_er)
+
     def r_only(ctx, held):
         if rows.which is not None:
             d_rows = held.alloc(4 * n_r)
@@ -1314,8 +1400,8 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
 
     # the candidate join is INNER whatever the kind, and the context's own R marks stay out of it: a candidate that the
     # verify step rejects would have set them
-    _drive_join(r_keys[0], s_keys[0], "radix", _lib.HJ_JOIN_INNER, None, step, verify, device, radixBits=radixBits,
-                fill=hash_keys, after=r_only)
+    _drive_join(r_keys[0], s_keys[0], "radix", _lib.HJ_JOIN_INNER, None, step, verify if cond is None else verify_where, device,
+                radixBits=radixBits, fill=hash_keys, after=r_only if cond is None else cond.r_only)
     return rows.joined()
 
 
@@ -1489,17 +1575,21 @@ class _ColumnKeys:
                     self._put(ctx, d_part, part)
             ctx.key_hash2(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, self.key_mask)
 
-    def verify(self, ctx, held, lo, n, d_s, d_r, candidates, pairs):
+    def verify(self, ctx, held, lo, n, d_s, d_r, candidates, pairs, marks=True):
         """the slice's candidates -> (its kept pairs' S plane, R plane, their number) -- the planes allocated from held and
-        the caller's to free; pairs False: a mark-only pass, (0, 0, 0) -- and the marks of both sides"""
+        the caller's to free; pairs False: a mark-only pass, (0, 0, 0) -- and the marks of both sides (marks False: no
+        plane is touched -- a condition step behind this one sets its own)"""
         dev = self.dev
-        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        if marks:
+            ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
         capacity = candidates if pairs else 0
         d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
-        ctx.pairs_verify2(d_s, d_r, candidates, lo, n, self.n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        ctx.pairs_verify2(d_s, d_r, candidates, lo, n, self.n_r, dev["cols"], d_ks, d_kr, capacity,
+                          dev["s_marks"] if marks else 0, dev["r_marks"] if marks else 0)
         return d_ks, d_kr, (ctx.verify_info()[1] if pairs else 0)
 
 
+@_where_keyword("_join_on_columns")
 def join_on_columns(
 r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
                     device=0, key_mask=0):
@@ -1514,7 +1604,13 @@ r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixB
     NULL and nothing else (the pandas reading); a column built with nulls_equal=True has it by itself.
     The method is join_on's with HashJoinContext.key_hash2 / pairs_verify2 in place of key_hash / pairs_verify; per S
     slice the validity bits are repacked from the slice's first row and the offsets rebased to the slice's own bytes.
-    how, r_cols / s_cols, radixBits, slice_tuples, key_mask, the result dict and the order of its rows: as in join_on."""
+    how, r_cols / s_cols, radixBits, slice_tuples, key_mask, where (keyword only), the result dict and the order of its rows: as in join_on."""
+    return _join_on_columns(r_keys, s_keys, r_cols, s_cols, how, nulls_equal, radixBits, slice_tuples, device, key_mask)
+
+
+def _join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
+                     device=0, key_mask=0, where=None):
+    """join_on_columns, and join_on_columns with a condition (_where_keyword)"""
     fn = "join_on_columns"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1530,6 +1626,7 @@ r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixB
     r_cols = _table_columns(fn, "R", r_cols, n_r)
     s_cols = _table_columns(fn, "S", s_cols, n_s)
     step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
+    terms = _where_terms(fn, where, n_s, n_r)
     rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
     trivial = rows.without_device(n_s)
     if trivial is not None:
@@ -1537,6 +1634,7 @@ r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixB
     pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
     s_sweep = _ON_S_SWEEP.get(rows.kind)
     keys = _ColumnKeys(r_keys, s_keys, nulls_equal, key_mask, step)
+    cond = _WhereTerms(terms, rows, n_r, n_s, step) if terms is not None else None
     dev = keys.dev
 
     def verify(ctx, held, lo, n, d_s, d_r, candidates):
@@ -1557,11 +1655,153 @@ r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixB
             ctx.mark_rows(dev["r_marks"], n_r, 0, rows.which, d_rows, n_r)
             rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
 
+    def verify_where(ctx, held, lo, n, d_s, d_r, candidates):
+        """the slice's candidates -> the pairs with equal keys, no plane marked; the condition step takes it from there"""
+        d_es, d_er, equal = keys.verify(ctx, held, lo, n, d_s, d_r, candidates, True, marks=False)
+        cond.slice(ctx, held, lo, n, d_es, d_er, equal)
+        held.free(d_es, d_er)
+
     # as in join_on: the candidate join is INNER whatever the kind, on tuples made on the device (the two arrays stand for
     # the relations' lengths alone)
-    _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step, verify, device,
-                radixBits=radixBits, fill=keys.hash_keys, after=r_only)
+    _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step,
+                verify if cond is None else verify_where, device, radixBits=radixBits, fill=keys.hash_keys,
+                after=r_only if cond is None else cond.r_only)
     return rows.joined()
+
+
+# ---- join conditions beyond equality: where= ------------------------------------------------------------------------------
+_WHERE_TYPES = {"u": _lib.HJ_VAL_UINT, "i": _lib.HJ_VAL_INT, "f": _lib.HJ_VAL_FLOAT}
+
+
+def _where_side(fn, side, values, n):
+    """one side of a term as a fixed-width KeyColumn of n rows; ValueError for what a term cannot compare"""
+    col = values if isinstance(values, KeyColumn) else None
+    if col is None:
+        a = values if isinstance(values, np.ma.MaskedArray) else np.asarray(values)
+        if a.ndim != 1:
+            raise ValueError(f"{fn}: the {side} values of a where term must be 1-D, not shape {a.shape}")
+        dt = a.dtype
+    elif col.offsets is not None:
+        raise ValueError(f"{fn}: a where term cannot compare a variable-length column ({side})")
+    else:
+        dt = col.values.dtype
+    if dt.kind not in _WHERE_TYPES or dt.itemsize > 8 or (dt.kind == "f" and dt.itemsize < 4):
+        raise ValueError(f"{fn}: a where term compares uint8..uint64, int8..int64, float32 or float64, not {dt} ({side})")
+    col = KeyColumn(values) if col is None else col
+    if n is not None and col.rows != n:
+        raise ValueError(f"{fn}: the {side} values of a where term must have {n} elements, not {col.rows}")
+    return col
+
+
+def _where_terms(fn, where, n_s=None, n_r=None):
+    """where= as a list of (S KeyColumn, hj_cmp_op, R KeyColumn, hj_val_type, width); None for None or an empty sequence"""
+    if where is None:
+        return None
+    where = list(where)
+    if not where:
+        return None
+    if len(where) > _lib.HJ_WHERE_MAX_TERMS:
+        raise ValueError(f"{fn}: where has {len(where)} terms; 1 to {_lib.HJ_WHERE_MAX_TERMS} can be evaluated")
+    out = []
+    for term in where:
+        if not isinstance(term, (tuple, list)) or len(term) != 3:
+            raise ValueError(f"{fn}: a where term is (s_values, op, r_values), not {term!r}")
+        s_values, op, r_values = term
+        if not isinstance(op, str) or op not in _lib.CMP_OPS:
+            raise ValueError(f"{fn}: the op of a where term must be one of {', '.join(_lib.CMP_OPS)}, not {op!r}")
+        s, r = _where_side(fn, "S", s_values, n_s), _where_side(fn, "R", r_values, n_r)
+        if s.values.dtype != r.values.dtype:
+            raise ValueError(f"{fn}: a where term compares {s.values.dtype} (S) with {r.values.dtype} (R); there is no implicit cast")
+        out.append((s, _lib.CMP_OPS[op], r, _WHERE_TYPES[s.values.dtype.kind], s.width))
+    return out
+
+
+def pairs_where_host(map_s, map_r, s_row_base, terms, capacity=None, marks=False):
+    """hj_pairs_where_host: HashJoinContext.pairs_where on numpy arrays, computed by the same code on the host. map_s / map_r:
+    the pairs as two uint32 arrays of one length; terms: 1 to HJ_WHERE_MAX_TERMS tuples (s_values, op, r_values) as the
+    where= of the joins takes them, op out of CMP_OPS; the S side has len(s_values) rows from s_row_base, the R side
+    len(r_values). capacity (None: every pair fits) cuts what is written, not what is counted or marked.
+    Returns {"s_idx", "r_idx"} (the kept pairs written, in input order), "info" (kept, written, 0, dropped) and, with
+    marks=True, "s_marks" / "r_marks": the two planes as uint32 words, zero before the call. Needs no device."""
+    fn = "pairs_where_host"
+    map_s, map_r = np.ascontiguousarray(map_s, dtype=np.uint32), np.ascontiguousarray(map_r, dtype=np.uint32)
+    if map_s.ndim != 1 or map_s.shape != map_r.shape:
+        raise ValueError(f"{fn}: the maps must be 1-D and of one length, not shapes {map_s.shape} and {map_r.shape}")
+    cols = _where_terms(fn, terms)
+    if cols is None:
+        raise ValueError(f"{fn}: 1 to {_lib.HJ_WHERE_MAX_TERMS} terms, not none")
+    n_s, n_r = cols[0][0].rows, cols[0][2].rows
+    if any(s.rows != n_s or r.rows != n_r for s, _, r, _, _ in cols):
+        raise ValueError(f"{fn}: the values of every term must have one length per side")
+    capacity = map_s.size if capacity is None else int(capacity)
+    held = [(s.take(0, n_s), r.take(0, n_r)) for s, _, r, _, _ in cols]
+    ptr = lambda a: a.ctypes.data if a is not None else 0       # noqa: E731
+    arr, k = _where_terms_arr([(ptr(sv), ptr(rv), width, type_, op, ptr(sw), ptr(rw))
+                               for (_, op, _, type_, width), ((sv, _, sw), (rv, _, rw)) in zip(cols, held)])
+    out_s, out_r = np.empty(min(capacity, map_s.size), dtype=np.uint32), np.empty(min(capacity, map_s.size), dtype=np.uint32)
+    s_marks = np.zeros((n_s + 31) // 32, dtype=np.uint32) if marks else None
+    r_marks = np.zeros((n_r + 31) // 32, dtype=np.uint32) if marks else None
+    info = (C.c_uint64 * 4)()
+    rc = lib.hj_pairs_where_host(map_s.ctypes.data, map_r.ctypes.data, map_s.size, int(s_row_base), n_s, n_r, arr, k,
+                                 out_s.ctypes.data, out_r.ctypes.data, out_s.size, ptr(s_marks) or None, ptr(r_marks) or None, info)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_pairs_where_host")
+    info = tuple(int(x) for x in info)
+    out = {"s_idx": out_s[:info[1]], "r_idx": out_r[:info[1]], "info": info}
+    if marks:
+        out["s_marks"], out["r_marks"] = s_marks, r_marks
+    return out
+
+
+class _WhereTerms:
+    """What the joins share once they are given where=: the terms' R columns whole on the device and room for one slice of
+    the S columns (uploaded once per slice), the two mark planes of the condition step, the step itself -- the pairs that
+    agree on the key -> the pairs for which every term holds too, as rows of the result -- and the sweeps behind it. rows:
+    the _TableRows the result grows in. slice() has the signature of _drive_join's on_maps, r_only() of its `after`."""
+
+    def __init__(self, terms, rows, n_r, n_s, step):
+        self.terms, self.rows, self.n_r, self.n_s, self.step = terms, rows, n_r, n_s, step
+        self.pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT      # the kept pairs are rows of the result
+        self.s_sweep = _ON_S_SWEEP.get(rows.kind)
+        self.dev, self.lo = None, None
+
+    def _put(self, ctx, held, lo, n):
+        if self.dev is None:    # the first slice: R's columns whole, room for a slice of S's, the planes
+            up = lambda a: held.put(np.ascontiguousarray(a)) if a is not None else 0       # noqa: E731
+            r_dev = [tuple(up(a) for a in r.take(0, self.n_r)) for _, _, r, _, _ in self.terms]
+            s_dev = [(held.alloc(self.step * s.width), 0, held.alloc(4 * ((self.step + 31) // 32)) if s.valid is not None else 0)
+                     for s, _, _, _, _ in self.terms]
+            self.dev = {"s": s_dev, "r_marks": held.put(np.zeros((self.n_r + 31) // 32, dtype=np.uint32)),
+                        "s_marks": held.alloc(4 * ((self.step + 31) // 32)),
+                        "terms": [(sd[0], rd[0], width, type_, op, sd[2], rd[2])
+                                  for sd, rd, (_, op, _, type_, width) in zip(s_dev, r_dev, self.terms)]}
+        if self.lo != lo:       # the slice's columns go up once
+            for d, (s, _, _, _, _) in zip(self.dev["s"], self.terms):
+                _put_parts(ctx, held, s.take(lo, n), d)
+            self.lo = lo
+
+    def slice(self, ctx, held, lo, n, d_s, d_r, n_pairs):
+        """the n_pairs pairs of the slice [lo, lo + n) that agree on the key -> the rows of its kind"""
+        self._put(ctx, held, lo, n)
+        rows, dev = self.rows, self.dev
+        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        capacity = n_pairs if self.pairs else 0          # right_semi / right_anti, semi / anti: a mark-only pass
+        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if self.pairs else (0, 0)
+        ctx.pairs_where(d_s, d_r, n_pairs, lo, n, self.n_r, dev["terms"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
+        if self.pairs:
+            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.where_info()[1])
+            held.free(d_ks, d_kr)
+        if self.s_sweep is not None:
+            d_rows = held.alloc(4 * n)
+            ctx.mark_rows(dev["s_marks"], n, lo, self.s_sweep, d_rows, n)
+            rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
+            held.free(d_rows)
+
+    def r_only(self, ctx, held):
+        if self.rows.which is not None:
+            d_rows = held.alloc(4 * self.n_r)
+            ctx.mark_rows(self.dev["r_marks"], self.n_r, 0, self.rows.which, d_rows, self.n_r)
+            self.rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
 
 
 # ---- aggregating joins: COUNT / SUM / MIN / MAX of S values per R row -----------------------------------------------------

@@ -516,6 +516,59 @@ int hj_mark_rows_dev(hj_ctx *ctx, const uint32_t *dMarks, uint64_t rows, uint32_
 /* Waits for the stream. About the last hj_mark_rows_dev: out[0] = rows produced, out[1] = rows written (= min(out[0],
  * capacity)), out[2] = its device time in microseconds (rounded), out[3] = its `rows`. All 0 before the first call. */
 int hj_mark_rows_info(hj_ctx *ctx, uint64_t out[4]);
+/* ---- join conditions beyond equality: typed comparisons on the matched pair ----
+ * ... ON S.k = R.k AND S.ts >= R.valid_from AND S.ts < R.valid_to: an equi-join plus a condition on the pair. For the
+ * kinds other than INNER the condition belongs to the match -- an S row whose pairs all fail it is an unmatched row of a
+ * left or anti join, and the same goes for R -- so it cannot be a filter behind the join, and the context's own
+ * HJ_FLAG_TRACK_R_MATCHES marks are of no use: a pair the condition rejects would have set them. hj_pairs_where_dev is one
+ * more step of the flow above: pairs in (an INNER probe's, or hj_pairs_verify_dev's kept ones), the pairs that pass out,
+ * and their rows marked in two caller-owned planes, from which hj_mark_rows_dev gives all eight kinds.
+ * A condition is the AND of 1 to HJ_WHERE_MAX_TERMS terms  s[si] OP r[ri], both sides of a term of one type and width.
+ * A pair is kept iff every term holds. A term with a NULL on either side does not hold (SQL's unknown), HJ_CMP_NE
+ * included; the bytes under a NULL are never compared (they are read: they exist). HJ_VAL_UINT / HJ_VAL_INT compare as
+ * integers of that width and signedness. HJ_VAL_FLOAT compares as IEEE-754 binary32 / binary64, which is NOT the bytewise
+ * equality of the key columns above: -0.0 == +0.0, and with a NaN on either side EQ, LT, LE, GT and GE are false and NE
+ * is true. No constants, no arithmetic, no OR, no ordering of strings, no 16-bit floats. */
+#define HJ_WHERE_MAX_TERMS 4
+typedef enum { HJ_CMP_EQ = 0, HJ_CMP_NE = 1, HJ_CMP_LT = 2, HJ_CMP_LE = 3, HJ_CMP_GT = 4, HJ_CMP_GE = 5 } hj_cmp_op;
+typedef enum { HJ_VAL_UINT = 0, HJ_VAL_INT = 1, HJ_VAL_FLOAT = 2 } hj_val_type;
+typedef struct {
+    const void     *s, *r;            /* sRows / rRows elements of `width` bytes, aligned to it            */
+    const uint32_t *sValid, *rValid;  /* NULL: no NULLs. Else the plane hj_gather_dev writes, 1 = valid    */
+    uint32_t width;                   /* UINT / INT: 1, 2, 4, 8.  FLOAT: 4, 8                              */
+    uint32_t type;                    /* hj_val_type, the same on both sides                               */
+    uint32_t op;                      /* hj_cmp_op: the term is  s[si] OP r[ri]                            */
+    uint32_t reserved;                /* 0                                                                 */
+} hj_where_term;                      /* 48 bytes */
+/* Pairs -> the pairs whose terms all hold. Pairs, output and marks are hj_pairs_verify_dev's, word for word: for pair k in
+ * [0, nPairs): s = dMapS[k] - sRowBase, r = dMapR[k]. A pair whose raw entry is HJ_NO_ROW on either side, or with
+ * s >= sRows or r >= rRows, is never dereferenced: it is dropped and counted apart (hj_where_info out[3]). Kept pairs go to
+ * dOutS / dOutR under the output contract of hj_probe_pairs_dev: dOutS[j] is the original entry dMapS[k], base included;
+ * the planes fill from 0 without holes; pairs at or beyond `capacity` are counted and not written; the order is
+ * unspecified, the multiset is exact. Every kept pair, written or cut by the capacity, sets bit s of dSMarks and bit r of
+ * dRMarks where those are not NULL: bit i & 31 of 32-bit word i >> 5, words 0 .. ceil(rows / 32) - 1, nothing behind
+ * them. Bits only go 0 -> 1: the caller clears the planes. capacity 0 with NULL outputs is a mark-only pass. dOutS / dOutR
+ * must not alias dMapS / dMapR, each other, or the planes. sValid is indexed by s (the base is off): ceil(sRows / 32)
+ * words; rValid holds ceil(rRows / 32). `terms` is host memory, read before the call returns. Asynchronous on the
+ * context's stream; needs no hj_reserve, no table and no state; touches no counter of hj_result and no other *_info.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): nTerms 0 or above HJ_WHERE_MAX_TERMS, terms NULL; a type
+ * above HJ_VAL_FLOAT, an op above HJ_CMP_GE, a width the type does not have; reserved != 0; with sRows > 0 an s pointer that
+ * is NULL or not aligned to its width, likewise r with rRows > 0; a validity pointer that is not 4-byte aligned; a map
+ * NULL with nPairs > 0; an output NULL with nPairs > 0 and capacity > 0; nPairs, sRows or rRows above 2^32 - 1. nPairs 0 is
+ * a call that kept nothing. */
+int hj_pairs_where_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMapR, uint64_t nPairs, uint32_t sRowBase,
+                       uint64_t sRows, uint64_t rRows, const hj_where_term *terms, uint32_t nTerms, uint32_t *dOutS,
+                       uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
+/* Waits for the stream. About the last hj_pairs_where_dev: out[0] = pairs kept, out[1] = pairs written (= min(out[0],
+ * capacity)), out[2] = its device time in microseconds (rounded), out[3] = pairs dropped as HJ_NO_ROW or out of range.
+ * Rejected pairs = nPairs - out[0] - out[3]. All 0 before the first call. */
+int hj_where_info(hj_ctx *ctx, uint64_t out[4]);
+/* The same function on host pointers: no context, no device (the kernel and this loop evaluate a term with one body).
+ * The kept pairs are written in input order; `info` (may be NULL) is filled as hj_where_info fills out, info[2] = 0.
+ * HJ_ERR_INVALID as hj_pairs_where_dev; a refused call writes nothing. */
+int hj_pairs_where_host(const uint32_t *mapS, const uint32_t *mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                        uint64_t rRows, const hj_where_term *terms, uint32_t nTerms, uint32_t *outS, uint32_t *outR,
+                        uint64_t capacity, uint32_t *sMarks, uint32_t *rMarks, uint64_t info[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
