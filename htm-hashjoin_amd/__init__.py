@@ -6,7 +6,7 @@ reference (anilshanbhag/HTM-HashJoin) by name and argument meaning.
 """
 from ._lib import (  # noqa: F401
     HJ_OK, HJ_ERR_INVALID, HJ_ERR_NO_DEVICE, HJ_ERR_HIP, HJ_ERR_OOM, HJ_ERR_KEY_RANGE,
-    HJ_ERR_UNKNOWN_ALGO, HJ_ERR_STATE, HJ_FLAG_KEEP_ROW_IDS, HJ_FLAG_TRACK_R_MATCHES, HJ_R_UNMATCHED, HJ_R_MATCHED, LIB_PATH, hj_params, hj_result, lib,
+    HJ_ERR_UNKNOWN_ALGO, HJ_ERR_STATE, HJ_FLAG_KEEP_ROW_IDS, HJ_FLAG_TRACK_R_MATCHES, HJ_FLAG_SLOT_CODES, HJ_R_UNMATCHED, HJ_R_MATCHED, LIB_PATH, hj_params, hj_result, lib,
     HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI, HJ_NO_ROW, HJ_GATHER_MAX_COLS, hj_gather_col,
     HJ_KEY_MAX_COLS, HJ_KEY_SIDE_S, HJ_KEY_SIDE_R, hj_key_col, HJ_KEY_NULLS_EQUAL, hj_key_col2, hj_gather_col2,
     HJ_WHERE_MAX_TERMS, HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE, CMP_OPS, HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT,
@@ -17,5 +17,5 @@ from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
     outer_join_pairs, radix_outer_join_pairs, join_tables, join_on, key_hash_host,
     KeyColumn, join_on_columns, key_hash2_host, pairs_where_host, radix_join_aggregate, aggregate_on, prj_agg_layout_info,
-    generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
+    generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )

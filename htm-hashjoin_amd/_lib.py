@@ -30,6 +30,9 @@ HJ_FLAG_KEEP_ROW_IDS = 0x1
 # hj_params.flags: the context keeps one bit per R row, set by every INNER / LEFT materialising probe for the R rows of the
 # rows it produces (hj_r_rows_dev turns the bits into rows); needs HJ_FLAG_KEEP_ROW_IDS except on "htm"
 HJ_FLAG_TRACK_R_MATCHES = 0x2
+# hj_params.flags: the classic rings leave one code byte per slot (table format 2) whatever the table's size; without it
+# only where a byte holds any 32-bit key (hj_slot_codes_info). For tests of the format at small sizes
+HJ_FLAG_SLOT_CODES = 0x4
 # hj_r_rows_dev: which rows
 HJ_R_UNMATCHED, HJ_R_MATCHED = 0, 1
 
@@ -250,6 +253,7 @@ def _declare(lib):
         "hj_wave_layout_info": ([vp, u32, u64, P(u64)], i32),
         "hj_wave_seams": ([vp, vp, vp, vp, u64, P(u64)], i32),
         "hj_wave_planar_info": ([vp, P(u64)], i32),
+        "hj_slot_codes_info": ([vp, u64, u32, P(u64)], i32),
         "hj_table_debug": ([vp, P(u64)], i32),
         "hj_htm_chain_layout_info": ([vp, u32, u64, P(u64)], i32),
         "hj_htm_chain_info": ([vp, P(u64)], i32),

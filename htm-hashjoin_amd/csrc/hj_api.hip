@@ -132,6 +132,13 @@ int hj_reserve(hj_ctx* c, const hj_params* params, uint64_t rSize, uint64_t sSiz
     const bool track = (params->flags & HJ_FLAG_TRACK_R_MATCHES) != 0;
     if (track && params->algo != HJ_ALGO_HTM && !(params->flags & HJ_FLAG_KEEP_ROW_IDS))
         return fail(c, HJ_ERR_INVALID, "hj_reserve: HJ_FLAG_TRACK_R_MATCHES needs HJ_FLAG_KEEP_ROW_IDS on open addressing and PRJ / AUTO");
+    if (params->flags & HJ_FLAG_SLOT_CODES) {
+        if (params->flags & HJ_FLAG_KEEP_ROW_IDS)
+            return fail(c, HJ_ERR_INVALID, "hj_reserve: HJ_FLAG_SLOT_CODES excludes HJ_FLAG_KEEP_ROW_IDS (a code byte holds no row)");
+        if (params->algo != HJ_ALGO_NOCC && params->algo != HJ_ALGO_ATOMIC)
+            return fail(c, HJ_ERR_INVALID, "hj_reserve: HJ_FLAG_SLOT_CODES needs an open-addressing algo");
+        if (probe_len(*params) > 128) return fail(c, HJ_ERR_INVALID, "hj_reserve: HJ_FLAG_SLOT_CODES needs probeLength <= 128");
+    }
     HJ_HIP(c, hipSetDevice(c->device));
     c->params = *params;
     HJ_HIP(c, hipStreamSynchronize(c->stream));          // buffers may be replaced below; and a new workload starts without an expectation

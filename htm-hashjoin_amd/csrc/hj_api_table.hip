@@ -58,7 +58,14 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     // The classic rings (3) of a context that keeps no row ids retire planar: 4-byte keys for the probe, the index words in a
     // plane of their own that only the deferred walks read. Behind them the packed classic build stays enqueued, gated on the
     // word k_wave_fixup sets when the planar build had to give up (Counters::planarFail); not needed, its launches return at once.
-    const int classicMode = (c->params.flags & HJ_FLAG_KEEP_ROW_IDS) ? kWaveClassic : kWavePlanar;
+    // Slot codes instead of the key plane (kWaveCodes): tuple builds only, and by itself only where a
+    // code byte holds ANY 32-bit key -- tables of 2^27 slots and more at probeLength 4, where the probe's bytes are what
+    // the step costs. Below that everything stays as it was unless HJ_FLAG_SLOT_CODES forces the road (then a key without a
+    // code hands over to the packed build like the planar build's own causes).
+    const SlotCode code = slot_code(tableSize, job.probeLen);
+    const bool codesCan = !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS) && !key32 && hshift == 0 && code.dbits <= kCodeBits;
+    c->op.codesRoad = !codesCan ? 0u : code.fits_all() ? 1u : (c->params.flags & HJ_FLAG_SLOT_CODES) ? 2u : 0u;
+    const int classicMode = (c->params.flags & HJ_FLAG_KEEP_ROW_IDS) ? kWaveClassic : c->op.codesRoad ? kWaveCodes : kWavePlanar;
     auto classic_tail = [&](Gate gate) -> hipError_t {
         hipError_t e = launch_build_wave(job, wave, gate, kWaveTail, classicMode);
         if (e != hipSuccess || classicMode == kWaveClassic) return e;
@@ -372,7 +379,7 @@ int hj_checksums_dev(hj_ctx* c)
     if (c->htm.built) {
         HJ_HIP(c, hipMemsetAsync(&c->dCtr()->htmOverflowSum, 0, sizeof(unsigned long long), c->stream));
         launch_htm_sums(c->buf[B_TABLE].as<uint64_t>(), c->htm.buckets, c->buf[B_HTM_OVERFLOW].as<uint64_t>(), c->dCtr(), c->stream);
-    } else launch_table_sums(c->buf[B_TABLE].as<uint64_t>(), c->op.tableSize, c->op.tableSize / 2, c->dCtr(), c->stream);
+    } else launch_table_sums(c->buf[B_TABLE].as<uint64_t>(), c->op.tableSize, c->op.tableSize / 2, probe_len(c->params), c->dCtr(), c->stream);
     HJ_HIP(c, hipGetLastError());
     return HJ_OK;
 }
@@ -387,6 +394,18 @@ int hj_export_table(hj_ctx* c, uint64_t* host_table, uint64_t tableSize)
     HJ_HIP(c, hipMemcpy(&k, c->dCtr(), sizeof(k), hipMemcpyDeviceToHost));
     // only [validLo, validHiEx + 512) holds defined values (hj_device.h); the rest is empty by definition
     const uint64_t lo = k.validLo, hi = k.validHiEx + 512 < tableSize ? k.validHiEx + 512 : tableSize;
+    if (k.tableFormat == kFormatCodes1) {
+        // slot codes (one byte per slot, 0xFF = empty) -> reference format: the codes land at the end of the caller's buffer
+        // and are decoded from the front (slot i is written at byte 8 i, its code sits at byte 7 tableSize + i: never behind)
+        const SlotCode code = slot_code(tableSize, probe_len(c->params));
+        const uint8_t* codes = reinterpret_cast<const uint8_t*>(host_table) + 7 * tableSize;
+        HJ_HIP(c, hipMemcpy(const_cast<uint8_t*>(codes), c->buf[B_TABLE].p, tableSize, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < tableSize; ++i) {
+            const uint32_t v = codes[i];
+            host_table[i] = (i < lo || i >= hi || v == kCodeEmpty) ? 0 : code.decode(v, (uint32_t)i, (uint32_t)(tableSize - 1));
+        }
+        return HJ_OK;
+    }
     if (k.tableFormat == kFormatKeys4) {
         // compact device format (4-byte keys, 0xFFFFFFFF = empty) -> reference format (key, 0 = empty): the keys land in
         // the upper half of the caller's buffer and are widened from the front (the write position never passes the read one)
@@ -535,6 +554,28 @@ int hj_wave_planar_info(hj_ctx* c, uint64_t out[4])
     const uint32_t variant = c->op.variantUsed ? c->op.variantUsed : (uint32_t)k.variant;
     out[0] = (variant == 3 && k.tableFormat == kFormatKeys4) ? 1 : 0;
     out[1] = k.planarFail; out[2] = k.tableFormat; out[3] = 0;
+    return HJ_OK;
+}
+
+int hj_slot_codes_info(hj_ctx* c, uint64_t tableSize, uint32_t probeLength, uint64_t out[8])
+{
+    if (!out) return HJ_ERR_INVALID;
+    if (c && tableSize == 0) {
+        // the table of the last build
+        if (!c->op.built || c->htm.built) return fail(c, HJ_ERR_STATE, "hj_slot_codes_info: no open-addressing table");
+        tableSize = c->op.tableSize; probeLength = probe_len(c->params);
+    }
+    if (!is_pow2(tableSize) || tableSize > (1ull << 32) || probeLength == 0) return HJ_ERR_INVALID;
+    const SlotCode code = slot_code(tableSize, probeLength);
+    out[0] = code.fits_all() ? 1 : 0; out[1] = code.dbits; out[2] = code.hiCap; out[3] = code.tbits;
+    out[4] = out[5] = out[6] = out[7] = 0;
+    if (!c || !c->op.built || c->htm.built || tableSize != c->op.tableSize) return HJ_OK;
+    if (const int rc = read_counters(c, false)) return rc;
+    const Counters& k = *c->hCtr;
+    const uint32_t variant = c->op.variantUsed ? c->op.variantUsed : (uint32_t)k.variant;
+    out[4] = (variant == 3 && k.tableFormat == kFormatCodes1) ? 1 : 0;      // the table is in slot codes
+    out[5] = (variant == 3 && c->op.codesRoad) ? k.planarFail : 0;          // why the road handed over (0: it did not, or was not taken)
+    out[6] = c->op.codesRoad; out[7] = k.tableFormat;
     return HJ_OK;
 }
 

@@ -247,16 +247,29 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
 // (planar_index_plane), so that the probe reads 4 bytes per slot. The deferred phase then walks on the index plane alone
 // (k_wave_deferred<PLANAR>, k_wave_fixup). Key 0xFFFFFFFF cannot live in a 4-byte table: Counters::planarFail, and the
 // packed build redoes it.
-template <bool KEY32, bool CHECK, bool HTM, bool COMPACT, bool PLANAR>
+// CODES (PLANAR on 8-byte tuples only, mode kWaveCodes): the key run of a retiring granule is 128 code bytes instead of 512
+// bytes of keys (SlotCode, hj_device.h) -- one 2-byte store per lane, one 128-byte line per instruction; the index run, the
+// deferred walks and the log stay what they are. Any key has a code when the table is large enough (the host's rule);
+// otherwise (forced road) a tile holding a key at or above keyLimit raises Counters::planarFail bit 2. Key 0xFFFFFFFF is a
+// key like any other here: the empty pattern is a code no key produces.
+struct CodeRetire { uint32_t dmask, hiShift, hiMask, keyLimit; };
+inline CodeRetire code_retire(const SlotCode& sc)
+{
+    // code = ((key >> hiShift) & hiMask) | ((slot - key) & dmask): the high part lands on its place in one shift
+    const bool high = sc.tbits < 32;
+    return CodeRetire{sc.dmask(), high ? sc.tbits - sc.dbits : 0u, high ? ((sc.hiCap - 1u) << sc.dbits) : 0u, sc.key_limit()};
+}
+template <bool KEY32, bool CHECK, bool HTM, bool COMPACT, bool PLANAR, bool CODES = false>
 __global__ void __launch_bounds__(kWvThreads, kWvWpe)
 k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_t nChunks, const uint32_t* __restrict__ starts,
              const uint32_t* __restrict__ bounds, uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift,
              uint32_t probeLen, uint64_t idxBase, ShardCheck sc, DeferredEntry* __restrict__ queue,
              uint32_t* __restrict__ dcounts, Counters* __restrict__ ctr, Gate gate, uint64_t* __restrict__ htmConflicts,
-             uint32_t* __restrict__ ccounts, uint32_t residentWG, uint32_t* __restrict__ pcounts)
+             uint32_t* __restrict__ ccounts, uint32_t residentWG, uint32_t* __restrict__ pcounts, CodeRetire cr)
 {
     static_assert(!(COMPACT && HTM), "the bucketised table keeps its own layout");
     static_assert(!(PLANAR && (COMPACT || HTM)), "the planar retire belongs to the classic open-addressing build");
+    static_assert(!CODES || (PLANAR && !KEY32), "slot codes: the planar retire of a tuple build (identity hash)");
     if (gate_closed(gate)) return;
     extern __shared__ __align__(16) uint64_t lds[];
     // the wavefront's number inside the workgroup is the same in all its lanes, but the compiler only knows that when told:
@@ -352,6 +365,20 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                     u2 vv; vv.x = (uint32_t)t.x; vv.y = (uint32_t)t.y;
                     __builtin_nontemporal_store(vv, reinterpret_cast<u2*>(reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift)) + lane);
                 }
+            } else if constexpr (CODES) {
+                // 128 code bytes and the 512-byte index run. This lane's slots are 2 * lane and 2 * lane + 1 of the granule;
+                // the granule's first slot is a multiple of 128, so below the displacement's width it adds nothing that
+                // the lane's own offset does not
+                u2 ii;
+                ii.x = (uint32_t)(t.x >> 32); ii.y = (uint32_t)(t.y >> 32);
+                const uint32_t k0 = (uint32_t)t.x, k1 = (uint32_t)t.y;
+                const uint32_t s0 = (winLoG << kGranShift) + 2u * lane;
+                uint32_t c0 = ((k0 >> cr.hiShift) & cr.hiMask) | ((s0 - k0) & cr.dmask);
+                uint32_t c1 = ((k1 >> cr.hiShift) & cr.hiMask) | ((s0 + 1u - k1) & cr.dmask);
+                c0 = ii.x == kNone ? kCodeEmpty : c0; c1 = ii.y == kNone ? kCodeEmpty : c1;
+                uint8_t* const codes = reinterpret_cast<uint8_t*>(table) + ((uint64_t)winLoG << kGranShift);
+                __builtin_nontemporal_store((unsigned short)(c0 | (c1 << 8)), reinterpret_cast<unsigned short*>(codes) + lane);
+                __builtin_nontemporal_store(ii, reinterpret_cast<u2*>(planar_index_plane(table, mask + 1) + ((uint64_t)winLoG << kGranShift)) + lane);
             } else if constexpr (PLANAR) {
                 // two 512-byte runs: the key words, the index words (the empty pattern's two words are the planes' empty patterns)
                 u2 kk, ii;
@@ -665,7 +692,15 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             target = target < gmin ? target : gmin;
             target = target < limG ? target : limG;
             advance(target);
-            if constexpr (PLANAR) {
+            if constexpr (CODES) {
+                // forced road only (keyLimit = 0: every key has a code): a key whose high part no code holds
+                if (cr.keyLimit) {
+                    bool over = false;
+#pragma unroll
+                    for (int j = 0; j < kWvPer; ++j) over |= live[j] & (klo[j] >= cr.keyLimit);
+                    if (wv_ballot(over) && lane == 0) atomicOr(&ctr->planarFail, 4ull);
+                }
+            } else if constexpr (PLANAR) {
                 // key 0xFFFFFFFF, the 4-byte empty pattern: its home slot is the table's last one, so only a tile that reaches
                 // that slot looks for it (one scalar compare per tile otherwise)
                 if (tmax == mask32) {
@@ -969,7 +1004,8 @@ __device__ __forceinline__ void reset_build_counters(Counters* __restrict__ ctr,
 // again; nothing of this build is looked at).
 __global__ void __launch_bounds__(kBlock)
 k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict__ dcounts, uint32_t nChunks, uint32_t sliceLen,
-             uint64_t* __restrict__ table, uint64_t tableSize, Counters* __restrict__ ctr, Gate gate, PlanarWalk pw)
+             uint64_t* __restrict__ table, uint64_t tableSize, Counters* __restrict__ ctr, Gate gate, PlanarWalk pw,
+             bool codes, SlotCode sc)
 {
     if (gate_closed(gate)) return;
     const uint32_t lane = threadIdx.x & 63;
@@ -979,11 +1015,12 @@ k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict
             reset_build_counters(ctr, lane);
             if (lane == 0) { ctr->tableFormat = kFormatSlots8; ctr->packedRedo = 1; }
         } else if (lane == 0) {
-            ctr->tableFormat = kFormatKeys4;
+            ctr->tableFormat = codes ? kFormatCodes1 : kFormatKeys4;
         }
     }
     if (fail) return;
     uint32_t* const keys = reinterpret_cast<uint32_t*>(table);
+    uint8_t* const codePlane = reinterpret_cast<uint8_t*>(table);
     const uint32_t* const idxPlane = planar_index_plane(table, tableSize);
     for (uint32_t c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); c < nChunks; c += gridDim.x * (kBlock / 64)) {
         const uint32_t* const log = slice_dirty_log(queue, c, sliceLen, dcounts[c]).slot;
@@ -991,7 +1028,10 @@ k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict
         for (uint32_t i = lane; i < cnt; i += 64) {
             const uint32_t s = log[i];                     // a walker's pos: masked, always inside the table
             const uint32_t idx = idxPlane[s];
-            keys[s] = idx == kNone ? kNone : planar_key_of(pw, idx);
+            // codes: a byte store per logged slot -- two logged slots of one 4-byte word each get their own byte, nobody
+            // reads a word to write it back
+            if (codes) codePlane[s] = (uint8_t)(idx == kNone ? kCodeEmpty : sc.encode(planar_key_of(pw, idx), s));
+            else keys[s] = idx == kNone ? kNone : planar_key_of(pw, idx);
         }
     }
 }
@@ -1019,25 +1059,25 @@ __global__ void k_wave_finalize_range(Counters* __restrict__ ctr, uint64_t table
 // plane of the 4-byte formats; the empty pattern is all ones in both, written 16 bytes per store.
 // plane2 != nullptr (the planar retire's index plane): the same stretches there read empty too -- that is everywhere a
 // deferred walk can step outside the owned range (the valid range covers the blocks the walks start from + one)
+// (uint8_t: the code plane of kFormatCodes1, 16 slots per store; its index plane is the same plane of 4-byte words)
 template <class W>
 __global__ void __launch_bounds__(kBlock)
-k_wave_fill_edges(W* __restrict__ table, W* __restrict__ plane2, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
+k_wave_fill_edges(W* __restrict__ table, uint32_t* __restrict__ plane2, const Counters* __restrict__ ctr, uint64_t tableSize, Gate gate)
 {
     if (gate_closed(gate)) return;
-    constexpr uint32_t kPerStore = sizeof(uint4) / sizeof(W);            // all bounds are multiples of 128 (granules) or 512
     const uint4 e = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     const uint64_t stride = (uint64_t)gridDim.x * kBlock, t0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint64_t hi = ctr->validHiEx + 512;
     hi = hi < tableSize ? hi : tableSize;
-    const uint64_t a0 = ctr->validLo / kPerStore, a1 = ctr->ownLo / kPerStore;
-    const uint64_t b0 = ctr->ownHiEx / kPerStore, b1 = hi / kPerStore;
-    auto fill = [&](W* plane) {
-        uint4* const p4 = reinterpret_cast<uint4*>(plane);
+    const uint64_t validLo = ctr->validLo, ownLo = ctr->ownLo, ownHiEx = ctr->ownHiEx;
+    auto fill = [&](void* plane, uint32_t perStore) {                    // all bounds are multiples of 128 (granules) or 512
+        const uint64_t a0 = validLo / perStore, a1 = ownLo / perStore, b0 = ownHiEx / perStore, b1 = hi / perStore;
+        uint4* const p4 = static_cast<uint4*>(plane);
         for (uint64_t v = a0 + t0; v < a1; v += stride) p4[v] = e;
         for (uint64_t v = b0 + t0; v < b1; v += stride) p4[v] = e;
     };
-    fill(table);
-    if constexpr (sizeof(W) == sizeof(uint32_t)) { if (plane2) fill(plane2); }      // only the 4-byte formats have a second plane
+    fill(table, sizeof(uint4) / sizeof(W));
+    if constexpr (sizeof(W) <= sizeof(uint32_t)) { if (plane2) fill(plane2, sizeof(uint4) / sizeof(uint32_t)); }   // only the planar formats have a second plane
     if (blockIdx.x == 0 && threadIdx.x < kTableSlack) table[tableSize + threadIdx.x] = (W)~(W)0;
 }
 
@@ -1146,7 +1186,10 @@ WaveSlices wave_conflict_layout(uint64_t n, int nCU, void* boundsBuf)
 hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, int parts, int mode, KernelEvents kev)
 {
     const bool htm = buf.htmConflicts != nullptr;
-    const bool compact = mode == kWaveCompact, planar = mode == kWavePlanar;
+    const bool codes = mode == kWaveCodes;
+    const bool compact = mode == kWaveCompact, planar = mode == kWavePlanar || codes;
+    const SlotCode code = slot_code(j.tableSize, j.probeLen);
+    if (codes && (j.key32 || j.hshift || code.dbits > kCodeBits)) return hipErrorInvalidValue;   // tuples under the identity hash
     // (planar + bucketised is refused here: the dirty-log counts live in the conflict counts' words, WaveScratch::lcounts)
     if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact || planar)) return hipErrorInvalidValue;
     if (!j.key32 && j.hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
@@ -1175,20 +1218,22 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     }
     if (parts & kWaveMain) {
         if (kev.before && (e = hipEventRecord(kev.before, j.s)) != hipSuccess) return e;
-        auto build = [&](auto k32, auto chk, auto htmTag, auto cmp, auto pln) {
-            hipLaunchKernelGGL((k_build_wave<decltype(k32)::value, decltype(chk)::value, decltype(htmTag)::value, decltype(cmp)::value, decltype(pln)::value>),
+        auto build = [&](auto k32, auto chk, auto htmTag, auto cmp, auto pln, auto cds) {
+            hipLaunchKernelGGL((k_build_wave<decltype(k32)::value, decltype(chk)::value, decltype(htmTag)::value, decltype(cmp)::value, decltype(pln)::value,
+                                             decltype(cds)::value>),
                                gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, nChunks, ws.starts, ws.bounds, j.table, mask,
                                j.hshift, j.probeLen, j.idxBase, j.sc, queue, ws.dcounts, j.ctr, gate, buf.htmConflicts, ws.ccounts,
-                               residentWG, ws.pcounts);
+                               residentWG, ws.pcounts, codes ? code_retire(code) : CodeRetire{});
         };
         // every instantiation there is: the bucketised table on tuples without a shard check; else key format x "counts
-        // foreign tuples" for each of the three modes
-        if (htm) build(no, no, yes, no, no);
+        // foreign tuples" for each of the three modes; the slot codes on tuples alone, with and without the count
+        if (htm) build(no, no, yes, no, no, no);
+        else if (codes) with_flag(j.sc.mask != 0, [&](auto chk) { build(no, chk, no, no, yes, yes); });
         else with_flag(j.key32, [&](auto k32) {
             with_flag(j.sc.mask != 0, [&](auto chk) {
-                if (compact) build(k32, chk, no, yes, no);
-                else if (planar) build(k32, chk, no, no, yes);
-                else build(k32, chk, no, no, no);
+                if (compact) build(k32, chk, no, yes, no, no);
+                else if (planar) build(k32, chk, no, no, yes, no);
+                else build(k32, chk, no, no, no, no);
             });
         });
         if (kev.after && (e = hipEventRecord(kev.after, j.s)) != hipSuccess) return e;
@@ -1203,7 +1248,7 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     if (!(parts & kWaveTail)) return hipSuccess;
     uint32_t* const keys = reinterpret_cast<uint32_t*>(j.table);
     if (compact) {
-        hipLaunchKernelGGL(k_wave_fill_edges<uint32_t>, dim3(512), dim3(kBlock), 0, j.s, keys, nullptr, j.ctr, j.tableSize, gate);
+        hipLaunchKernelGGL(k_wave_fill_edges<uint32_t>, dim3(512), dim3(kBlock), 0, j.s, keys, static_cast<uint32_t*>(nullptr), j.ctr, j.tableSize, gate);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_wave_finalize_range, dim3(1), dim3(64), 0, j.s, j.ctr, j.tableSize, gate);
@@ -1215,13 +1260,18 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     if (planar) {
         const PlanarWalk pw{j.R, j.key32, j.idxBase, ws.lcounts};
         // 1024 workgroups: the compact road's 512 for one plane of 4-byte words, doubled for two (4.9 us at 2^30, as the packed fill)
+        if (codes)
+            hipLaunchKernelGGL(k_wave_fill_edges<uint8_t>, dim3(1024), dim3(kBlock), 0, j.s, reinterpret_cast<uint8_t*>(j.table),
+                               planar_index_plane(j.table, j.tableSize), j.ctr, j.tableSize, gate);
+        else
         hipLaunchKernelGGL(k_wave_fill_edges<uint32_t>, dim3(1024), dim3(kBlock), 0, j.s, keys, planar_index_plane(j.table, j.tableSize),
                            j.ctr, j.tableSize, gate);
         deferred(no, yes, nullptr, nullptr, pw);
-        hipLaunchKernelGGL(k_wave_fixup, gDef, dim3(kBlock), 0, j.s, queue, ws.dcounts, nChunks, sliceLen, j.table, j.tableSize, j.ctr, gate, pw);
+        hipLaunchKernelGGL(k_wave_fixup, gDef, dim3(kBlock), 0, j.s, queue, ws.dcounts, nChunks, sliceLen, j.table, j.tableSize, j.ctr, gate, pw,
+                           codes, code);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_wave_fill_edges<uint64_t>, dim3(2048), dim3(kBlock), 0, j.s, j.table, nullptr, j.ctr, j.tableSize, gate);
+    hipLaunchKernelGGL(k_wave_fill_edges<uint64_t>, dim3(2048), dim3(kBlock), 0, j.s, j.table, static_cast<uint32_t*>(nullptr), j.ctr, j.tableSize, gate);
     if (htm) deferred(yes, no, ws.ccounts, buf.htmRoute ? ws.bounds : nullptr, PlanarWalk{});
     else deferred(no, no, nullptr, nullptr, PlanarWalk{});
     return hipGetLastError();

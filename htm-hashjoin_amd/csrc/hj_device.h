@@ -133,14 +133,16 @@ struct Counters {
     // Open-addressing table formats (k_build_wave<COMPACT>, hj_build_wave.hip). tableFormat says what the table buffer
     // holds after a build: kFormatSlots8 = one 8-byte slot (index << 32 | key) per table slot, all ones = empty (every
     // build but the compact one); kFormatKeys4 = one 4-byte KEY per table slot, 0xFFFFFFFF = empty (the index words only
-    // order the inserts; the compact build settles every order inside its LDS rings and never writes them out). k_probe,
+    // order the inserts; the compact build settles every order inside its LDS rings and never writes them out);
+    // kFormatCodes1 = one code BYTE per table slot, 0xFF = empty (SlotCode below: the planar ring build of large tables). k_probe,
     // k_table_sums and hj_export_table read the word. compactFail: raised by the compact build when it meets something
     // only the classic builds can handle; k_wave_decide then resets the counters and hands over to the classic build.
     unsigned long long tableFormat, compactFail;
     // Planar retire of the classic ring build (k_build_wave<PLANAR>, hj_build_wave.hip): the table ends as kFormatKeys4 with
     // the index words in a plane of their own behind the keys (planar_index_plane). planarFail: why that build handed
     // over -- bit 0: a slice's dirty log did not fit (an input that defers nearly everything), bit 1: key 0xFFFFFFFF, the
-    // 4-byte empty pattern. k_wave_fixup then resets the counters and sets packedRedo = 1, the word the packed classic
+    // 4-byte empty pattern; bit 2 (the slot-code road, kWaveCodes, only): a key whose high part no code byte holds.
+    // k_wave_fixup then resets the counters and sets packedRedo = 1, the word the packed classic
     // build enqueued behind it is gated on. Counters::variant stays 3 on both roads.
     unsigned long long planarFail, packedRedo;
     // the locality pre-round's sample of hj_build_dev (k_sample_locality: launch_sample_locality's eight words, [7] = its
@@ -233,7 +235,38 @@ __device__ inline bool gate_closed(const Gate& g)
     return v != g.want && v != g.alt;
 }
 constexpr Gate kNoGate{nullptr, 0ull};
-constexpr unsigned long long kFormatSlots8 = 0, kFormatKeys4 = 1;
+constexpr unsigned long long kFormatSlots8 = 0, kFormatKeys4 = 1, kFormatCodes1 = 2;
+// Slot codes (kFormatCodes1): with the identity hash a stored key sits d < probeLength slots above its
+// home slot = key & (tableSize - 1), so the slot number, d and the key's bits above the table size say everything: one
+// byte per slot, code = (hi << dbits) | d with dbits = ceil(log2(probeLength)), hi = key >> log2(tableSize). Codes use 7
+// bits, the empty pattern is 0xFF. THE place where a code is made and read: build, fix-up, probe, sums and export call it.
+constexpr uint32_t kCodeEmpty = 0xFFu, kCodeBits = 7;
+struct SlotCode {
+    uint32_t dbits;      // bits of the displacement
+    uint32_t tbits;      // log2(tableSize), 32 for a table of 2^32 slots: no high bits, and nothing shifts by 32
+    uint32_t hiCap;      // high parts a code can hold: 2^(7 - dbits), 0 when dbits > 7 (no code at all)
+    __host__ __device__ uint32_t dmask() const { return (1u << dbits) - 1u; }
+    __host__ __device__ uint32_t hi(uint32_t key) const { return tbits >= 32 ? 0u : key >> tbits; }
+    // every 32-bit key has a code: the road has no failure cause of its own
+    __host__ __device__ bool fits_all() const { return dbits <= kCodeBits && (32 - tbits) + dbits <= kCodeBits; }
+    __host__ __device__ bool overflows(uint32_t key) const { return hi(key) >= hiCap; }
+    // the first key that has no code (0: every key has one)
+    __host__ __device__ uint32_t key_limit() const { return (fits_all() || tbits >= 32) ? 0u : (uint32_t)((uint64_t)hiCap << tbits); }
+    __host__ __device__ uint32_t encode(uint32_t key, uint32_t slot) const { return (hi(key) << dbits) | ((slot - key) & dmask()); }
+    __host__ __device__ uint32_t decode(uint32_t code, uint32_t slot, uint32_t mask32) const
+    {
+        const uint32_t home = (slot - (code & dmask())) & mask32;
+        return tbits >= 32 ? home : home | ((code >> dbits) << tbits);
+    }
+};
+__host__ __device__ inline SlotCode slot_code(uint64_t tableSize, uint32_t probeLen)
+{
+    SlotCode c;
+    c.dbits = probeLen <= 1 ? 0u : 32u - (uint32_t)__builtin_clz(probeLen - 1u);      // ceil(log2(probeLength))
+    c.tbits = (uint32_t)__builtin_popcountll(tableSize - 1);                           // tableSize is a power of two, at most 2^32
+    c.hiCap = c.dbits <= kCodeBits ? 1u << (kCodeBits - c.dbits) : 0u;
+    return c;
+}
 // Planar retire: where the index plane starts in the table buffer of (tableSize + kTableSlack) 8-byte words -- behind the
 // key plane and ITS slack (the probe reads up to probeLength - 1 keys past the table's end and must find them empty), at
 // the next multiple of 128 bytes so that the granules' 512-byte runs stay on whole lines in both planes. One uint32 input
@@ -266,7 +299,7 @@ void launch_build_atomic_min(const BuildJob& job, Gate gate);
 // the probe and the checksums read Counters::tableFormat on the device: either table format, one launch
 void launch_probe(const void* S, bool key32, uint64_t n, const uint64_t* table, uint64_t tableSize, uint32_t hshift,
                   uint32_t probeLen, ShardCheck sc, Counters* ctr, hipStream_t s);
-void launch_table_sums(const uint64_t* table, uint64_t tableSize, uint64_t halfSlots, Counters* ctr, hipStream_t s);
+void launch_table_sums(const uint64_t* table, uint64_t tableSize, uint64_t halfSlots, uint32_t probeLen, Counters* ctr, hipStream_t s);
 void launch_zipf_lookup(const int* raw, uint64_t n, const double* lut, const uint32_t* alphabet, uint32_t alphabetSize,
                         uint64_t* out, hipStream_t s);
 // Marks the whole table valid (variant 1 clears and may touch all of it).
@@ -401,7 +434,9 @@ size_t wave_queue_bytes(uint64_t n, int nCU);   // deferred queue: one slice per
 // plane and k_wave_fixup, which on Counters::planarFail sets Counters::packedRedo = 1: the word to gate the packed classic
 // build behind it on. Tuples and bare keys; never the bucketised table.
 constexpr int kWavePre = 1, kWaveMain = 2, kWaveTail = 4, kWaveAll = 7;
-constexpr int kWaveClassic = 0, kWaveCompact = 1, kWavePlanar = 2;
+constexpr int kWaveClassic = 0, kWaveCompact = 1, kWavePlanar = 2, kWaveCodes = 3;
+// mode kWaveCodes: kWavePlanar with the key plane replaced by one code byte per slot (SlotCode above; tuples only). The
+// table ends as kFormatCodes1; a key without a code raises Counters::planarFail bit 2 and the packed build redoes it.
 // htmRoute: the deferred phase files its conflicts under the chunk that owns their bucket (the LDS chain phase needs that)
 struct WaveBufs { void* bounds; void* queue; uint64_t* htmConflicts = nullptr; bool htmRoute = false; };
 hipError_t launch_build_wave(const BuildJob& job, const WaveBufs& buf, Gate gate, int parts, int mode = kWaveClassic, KernelEvents kev = {});

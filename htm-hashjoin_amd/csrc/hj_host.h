@@ -102,6 +102,8 @@ struct hj_ctx {
         // replaced the owner table since), and whether it was gated on the variant the device picked
         uint64_t ownN = 0;
         bool ownGated = false;
+        // the ring build of this table retires slot codes (kWaveCodes): 0 no, 1 by the size rule, 2 forced by HJ_FLAG_SLOT_CODES
+        uint32_t codesRoad = 0;
     } op;
     // ---- the bucketised table of --algo htm (hj_htm.hip; 4 slots per bucket in buf[B_TABLE]). Reset by begin_operation.
     struct Htm {

@@ -357,14 +357,134 @@ __device__ __forceinline__ void probe_body(const void* __restrict__ Sv, uint64_t
     flush_counter(&counter_shard(ctr)->foreign, foreign);
 }
 
-// One launch for either table format: the build decides the format on the device (Counters::tableFormat), the probe is
+// ---- slot codes (Counters::tableFormat == kFormatCodes1): one byte per slot, SlotCode in hj_device.h ----
+// The walk of probe_one on code bytes: slot home + j holds the key iff its code is (hi << dbits) | j. The identity hash
+// (the road is taken by tuple builds only: hshift 0). A key no code can hold (forced road) matches nothing.
+__device__ __forceinline__ uint32_t probe_one_codes(uint64_t sk, const uint8_t* __restrict__ codes, uint64_t mask, uint32_t probeLen,
+                                                    const SlotCode& code, uint64_t validLo, uint64_t validHiEx)
+{
+    const uint32_t key = (uint32_t)sk;
+    const uint64_t home = (uint64_t)key & mask;
+    if ((sk >> 32) != 0 || home < validLo || home >= validHiEx || code.overflows(key)) return 0;
+    const uint8_t* p = codes + home;
+    const uint32_t want = code.hi(key) << code.dbits;
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < probeLen; ++j) {
+        const uint32_t v = p[j];
+        if (v == kCodeEmpty) break;
+        m += (v == want + j);
+    }
+    return m;
+}
+
+// probeLength 4: the window is four code bytes, ONE load (unaligned; the last slot's window ends inside the slack bytes),
+// and the walk is arithmetic on the four bytes at once. hiShift / hiMask place the key's high part on bits 2..6 of a byte.
+typedef uint32_t u32_any_align __attribute__((aligned(1)));
+struct WindowC { uint32_t w, key; bool ok; };
+__device__ __forceinline__ WindowC load_window_codes(uint32_t key, const uint8_t* __restrict__ codes, uint64_t mask, uint64_t validLo,
+                                                     uint64_t validHiEx, uint64_t dummy, bool live)
+{
+    WindowC w;
+    w.key = key;
+    const uint64_t home = (uint64_t)key & mask;
+    w.ok = live && home >= validLo && home < validHiEx;
+    w.w = *reinterpret_cast<const u32_any_align*>(codes + (w.ok ? home : dummy));
+    return w;
+}
+__device__ __forceinline__ uint32_t count_window_codes(const WindowC& w, uint32_t hiShift, uint32_t hiMask)
+{
+    constexpr uint32_t kLow7 = 0x7F7F7F7Fu, kTop = 0x80808080u;
+    const uint32_t b = (w.key >> hiShift) & hiMask;
+    // byte j of `expected` = (hi << 2) | j; x has a zero byte exactly where the slot holds the key
+    const uint32_t expected = __builtin_amdgcn_perm(b, b, 0u) | 0x03020100u;
+    const uint32_t x = w.w ^ expected;
+    const uint32_t t = ((x & kLow7) + kLow7) | x;         // bit 7 of a byte clear <=> the byte of x is zero (exact: no carries between bytes)
+    const uint32_t e = w.w & kTop;                         // codes keep bit 7 clear: set = empty
+    const uint32_t before = (e - 1u) & kTop;               // bit 7 of the bytes before the first empty one (all, if none is)
+    return w.ok ? (uint32_t)__popc(~t & before) : 0u;
+}
+
+template <bool KEY32>
+__device__ __forceinline__ void probe_body_codes(const void* __restrict__ Sv, uint64_t n, const uint64_t* __restrict__ table, uint64_t mask,
+                                                 uint32_t probeLen, ShardCheck sc, Counters* __restrict__ ctr)
+{
+    using Elem = typename std::conditional<KEY32, uint32_t, uint64_t>::type;
+    const uint8_t* const codes = reinterpret_cast<const uint8_t*>(table);
+    const SlotCode code = slot_code(mask + 1, probeLen);
+    const uint32_t keyLimit = code.key_limit(), keyMax = keyLimit ? keyLimit - 1u : 0xFFFFFFFFu;
+    const uint32_t hiShift = code.tbits < 32 ? code.tbits - code.dbits : 0u, hiMask = code.tbits < 32 ? ((code.hiCap - 1u) << code.dbits) : 0u;
+    constexpr uint64_t EPV = 16 / sizeof(Elem);
+    unsigned long long matches = 0;
+    uint32_t foreign = 0;
+    const uint64_t validLo = ctr->validLo, validHiEx = ctr->validHiEx;
+    const uint64_t dummy = validLo < mask ? validLo : 0;
+    const Elem* S = static_cast<const Elem*>(Sv);
+    uint64_t head = ((16 - (reinterpret_cast<uintptr_t>(S) & 15)) & 15) / sizeof(Elem);
+    if (head > n) head = n;
+    const uint4* S4 = reinterpret_cast<const uint4*>(S + head);
+    const uint64_t nv = (n - head) / EPV;
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    uint64_t v0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (!KEY32 && probeLen == 4) {
+        // A window is 4 bytes here: between an S vector's arrival and its windows' a lane has next to nothing in flight, and
+        // with one vector per round trip the loop ran at the memory's LATENCY (2.51 ms at 2^30, slower than on 4-byte keys,
+        // profiles/slot_codes.md). So the loop is rotated and takes two vectors per turn: the four windows are requested,
+        // then the next two S vectors, and only then are the windows counted -- 2 KiB of S per wavefront on its way at
+        // all times. (On 4-byte keys the same rotation lost: there the windows themselves fill the pipe.)
+        // (a vector past the end is the last one read again, and never looked at: the loads stay unconditional, so the
+        // windows are waited for by their count alone while the S vectors behind them are still on their way)
+        const uint64_t last = nv ? nv - 1 : 0;
+        auto load_s = [&](uint64_t v) -> u4 { return __builtin_nontemporal_load(reinterpret_cast<const u4*>(S4) + (v < last ? v : last)); };
+        u4 a = {0u, 0u, 0u, 0u}, b = a;
+        if (v0 < nv) { a = load_s(v0); b = load_s(v0 + stride); }
+        for (uint64_t v = v0; v < nv; v += 2 * stride) {
+            const bool hasB = v + stride < nv;
+            const WindowC w0 = load_window_codes(a.x, codes, mask, validLo, validHiEx, dummy, (a.y == 0) & (a.x <= keyMax));
+            const WindowC w1 = load_window_codes(a.z, codes, mask, validLo, validHiEx, dummy, (a.w == 0) & (a.z <= keyMax));
+            const WindowC w2 = load_window_codes(b.x, codes, mask, validLo, validHiEx, dummy, hasB & (b.y == 0) & (b.x <= keyMax));
+            const WindowC w3 = load_window_codes(b.z, codes, mask, validLo, validHiEx, dummy, hasB & (b.w == 0) & (b.z <= keyMax));
+            foreign += (uint32_t)is_foreign(a.x, sc) + (uint32_t)is_foreign(a.z, sc);
+            foreign += hasB ? (uint32_t)is_foreign(b.x, sc) + (uint32_t)is_foreign(b.z, sc) : 0u;
+            a = load_s(v + 2 * stride); b = load_s(v + 3 * stride);
+            matches += count_window_codes(w0, hiShift, hiMask) + count_window_codes(w1, hiShift, hiMask) +
+                       count_window_codes(w2, hiShift, hiMask) + count_window_codes(w3, hiShift, hiMask);
+        }
+        v0 = nv;                                           // the body is done; head and tail below
+    }
+    for (uint64_t v = v0; v < nv; v += stride) {
+        const u4 t = __builtin_nontemporal_load(reinterpret_cast<const u4*>(S4) + v);
+        if constexpr (KEY32) {
+            foreign += (uint32_t)is_foreign(t.x, sc) + (uint32_t)is_foreign(t.y, sc) + (uint32_t)is_foreign(t.z, sc) + (uint32_t)is_foreign(t.w, sc);
+            matches += probe_one_codes(t.x, codes, mask, probeLen, code, validLo, validHiEx);
+            matches += probe_one_codes(t.y, codes, mask, probeLen, code, validLo, validHiEx);
+            matches += probe_one_codes(t.z, codes, mask, probeLen, code, validLo, validHiEx);
+            matches += probe_one_codes(t.w, codes, mask, probeLen, code, validLo, validHiEx);
+        } else {
+            foreign += (uint32_t)is_foreign(t.x, sc) + (uint32_t)is_foreign(t.z, sc);
+            // other probe lengths: the generic byte walk, one tuple after the other
+            matches += probe_one_codes(((uint64_t)t.y << 32) | t.x, codes, mask, probeLen, code, validLo, validHiEx);
+            matches += probe_one_codes(((uint64_t)t.w << 32) | t.z, codes, mask, probeLen, code, validLo, validHiEx);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (uint64_t i = 0; i < head; ++i) { matches += probe_one_codes(S[i], codes, mask, probeLen, code, validLo, validHiEx); foreign += is_foreign((uint32_t)S[i], sc); }
+        for (uint64_t i = head + nv * EPV; i < n; ++i) { matches += probe_one_codes(S[i], codes, mask, probeLen, code, validLo, validHiEx); foreign += is_foreign((uint32_t)S[i], sc); }
+    }
+    flush_counter(&counter_shard(ctr)->matches, matches);
+    flush_counter(&counter_shard(ctr)->foreign, foreign);
+}
+
+// One launch for every table format: the build decides the format on the device (Counters::tableFormat), the probe is
 // enqueued behind it without a host round trip and branches once, wave-uniformly.
 template <bool KEY32>
 __global__ void __launch_bounds__(kBlock)
 k_probe(const void* __restrict__ Sv, uint64_t n, const uint64_t* __restrict__ table, uint64_t mask,
         uint32_t hshift, uint32_t probeLen, ShardCheck sc, Counters* __restrict__ ctr)
 {
-    if (ctr->tableFormat == kFormatKeys4) probe_body<KEY32, true>(Sv, n, table, mask, hshift, probeLen, sc, ctr);
+    const unsigned long long format = ctr->tableFormat;
+    if (format == kFormatCodes1) probe_body_codes<KEY32>(Sv, n, table, mask, probeLen, sc, ctr);
+    else if (format == kFormatKeys4) probe_body<KEY32, true>(Sv, n, table, mask, hshift, probeLen, sc, ctr);
     else probe_body<KEY32, false>(Sv, n, table, mask, hshift, probeLen, sc, ctr);
 }
 
@@ -383,7 +503,7 @@ void launch_probe(const void* S, bool key32, uint64_t n, const uint64_t* table, 
 // table checksums
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock)
-k_table_sums(const uint64_t* __restrict__ table, uint64_t tableSize, uint64_t halfSlots, Counters* __restrict__ ctr)
+k_table_sums(const uint64_t* __restrict__ table, uint64_t tableSize, uint64_t halfSlots, uint32_t probeLen, Counters* __restrict__ ctr)
 {
     unsigned long long half = 0, full = 0;
     const ulonglong2* t2 = reinterpret_cast<const ulonglong2*>(table);
@@ -391,7 +511,28 @@ k_table_sums(const uint64_t* __restrict__ table, uint64_t tableSize, uint64_t ha
     const uint64_t lo = ctr->validLo;
     uint64_t hi = ctr->validHiEx + 512;
     if (hi > tableSize) hi = tableSize;
-    if (ctr->tableFormat == kFormatKeys4) {               // compact table: 4-byte keys, two per 8 bytes
+    const unsigned long long format = ctr->tableFormat;
+    if (format == kFormatCodes1) {                        // slot codes: 16 per 16-byte load, each decoded with its slot number
+        const SlotCode code = slot_code(tableSize, probeLen);
+        const uint32_t mask32 = (uint32_t)(tableSize - 1);
+        const uint4* c16 = reinterpret_cast<const uint4*>(table);
+        for (uint64_t v = (lo >> 4) + (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < ((hi + 15) >> 4); v += (uint64_t)gridDim.x * kBlock) {
+            const uint4 t = c16[v];                       // (the slack bytes past the table keep a last partial vector inside the buffer)
+            const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (uint32_t k = 0; k < 16; ++k) {
+                const uint64_t s = 16 * v + k;
+                const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+                const uint64_t key = (c == kCodeEmpty || s < lo || s >= hi) ? 0 : code.decode(c, (uint32_t)s, mask32);
+                full += key;
+                if (s < halfSlots) half += key;
+            }
+        }
+        flush_counter(&ctr->tableSumHalf, half);
+        flush_counter(&ctr->tableSumFull, full);
+        return;
+    }
+    if (format == kFormatKeys4) {                         // compact table: 4-byte keys, two per 8 bytes
         const uint2* k2 = reinterpret_cast<const uint2*>(table);
         for (uint64_t v = (lo >> 1) + (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < (hi >> 1); v += (uint64_t)gridDim.x * kBlock) {
             const uint2 t = k2[v];
@@ -417,10 +558,10 @@ k_table_sums(const uint64_t* __restrict__ table, uint64_t tableSize, uint64_t ha
     flush_counter(&ctr->tableSumFull, full);
 }
 
-void launch_table_sums(const uint64_t* table, uint64_t tableSize, uint64_t halfSlots, Counters* ctr, hipStream_t s)
+void launch_table_sums(const uint64_t* table, uint64_t tableSize, uint64_t halfSlots, uint32_t probeLen, Counters* ctr, hipStream_t s)
 {
     hipLaunchKernelGGL(k_table_sums, dim3(grid_for(tableSize / 2, kBlock * 4)), dim3(kBlock), 0, s,
-                       table, tableSize, halfSlots, ctr);
+                       table, tableSize, halfSlots, probeLen, ctr);
 }
 
 // ---------------------------------------------------------------------------

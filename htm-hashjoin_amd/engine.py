@@ -120,14 +120,35 @@ def own_layout_info(n, compute_units):
     return _own_layout(None, int(compute_units), n)
 
 
+_SLOT_CODES_FIELDS = ("fitsAuto", "dbits", "hiCap", "tableBits", "codes", "cause", "road", "tableFormat")
+
+
+def _slot_codes(handle, table_size, probe_length):
+    out = (C.c_uint64 * 8)()
+    rc = lib.hj_slot_codes_info(handle, table_size, probe_length, out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, f"hj_slot_codes_info(tableSize={table_size}, probeLength={probe_length})")
+    d = {k: int(out[i]) for i, k in enumerate(_SLOT_CODES_FIELDS)}
+    d["fitsAuto"], d["codes"] = bool(d["fitsAuto"]), bool(d["codes"])
+    return d
+
+
+def slot_codes_info(table_size, probe_length=4):
+    """hj_slot_codes_info without a context (host-only arithmetic): whether a ring build of a table of table_size slots
+    at probe_length leaves one code byte per slot by itself (fitsAuto), the displacement's bits (dbits) and the high parts
+    a code holds (hiCap), as a dict; the fields about a build (codes, cause, road, tableFormat) are 0."""
+    return _slot_codes(None, int(table_size), int(probe_length))
+
+
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
-            buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False):
+            buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False, slotCodes=False):
     p = hj_params()
     p.algo = _lib.ALGO_IDS[algo]
     p.scaleOutput, p.numPartitions, p.probeLength = scaleOutput, numPartitions, probeLength
     p.transactionSize, p.radixBits, p.buildVariant = transactionSize, radixBits, buildVariant
     p.prjMode = prjMode
-    p.flags = (_lib.HJ_FLAG_KEEP_ROW_IDS if keepRowIds else 0) | (_lib.HJ_FLAG_TRACK_R_MATCHES if trackRMatches else 0)
+    p.flags = ((_lib.HJ_FLAG_KEEP_ROW_IDS if keepRowIds else 0) | (_lib.HJ_FLAG_TRACK_R_MATCHES if trackRMatches else 0) |
+               (_lib.HJ_FLAG_SLOT_CODES if slotCodes else 0))
     return p
 
 
@@ -229,7 +250,7 @@ class HashJoinContext:
 
     # ---- split API, device pointers ---------------------------------------
     def reserve(self, algo, rSize, sSize, **kw):
-        """hj_reserve. Keywords: the fields of hj_params, keepRowIds (HJ_FLAG_KEEP_ROW_IDS) and trackRMatches
+        """hj_reserve. Keywords: the fields of hj_params, slotCodes (HJ_FLAG_SLOT_CODES), keepRowIds (HJ_FLAG_KEEP_ROW_IDS) and trackRMatches
         (HJ_FLAG_TRACK_R_MATCHES: one bit per R row, set by the inner / left probe_pairs and prj_probe_pairs calls for the
         R rows they produce, read by r_rows; needs keepRowIds except on "htm")."""
         p = _params(algo, **kw)
@@ -555,6 +576,13 @@ class HashJoinContext:
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_wave_planar_info(self._h, out))
         return {"planar": bool(out[0]), "planarFallback": int(out[1]), "tableFormat": int(out[2])}
+
+    def slot_codes_info(self):
+        """hj_slot_codes_info for the table of the last build (waits for the stream): slot_codes_info()'s fields, and codes
+        (the table is one code byte per slot), cause (why the road handed over to the 8-byte build; 0: it did not or was not
+        taken; 4 = a key no code holds), road (0 not taken, 1 by the size rule, 2 forced by reserve(..., slotCodes=True)),
+        tableFormat."""
+        return _slot_codes(self._h, 0, 0)
 
     def table_debug(self):
         """hj_table_debug (waits for the stream; for tests): the valid slot range [validLo, validHiEx) of the last build,

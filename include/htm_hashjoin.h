@@ -116,6 +116,15 @@ typedef struct {
  * HJ_FLAG_KEEP_ROW_IDS (hj_reserve: HJ_ERR_INVALID otherwise); HJ_ALGO_HTM, whose table always keeps the rows, takes it
  * alone. hj_build_keys_dev on such a context returns HJ_ERR_STATE (the sharded path keeps no marks). */
 #define HJ_FLAG_TRACK_R_MATCHES 0x2u
+/* hj_params.flags. Open addressing, hj_build_dev through the classic rings (buildVariant 3, or 0 picking it) on a context
+ * without HJ_FLAG_KEEP_ROW_IDS: leave the table as one CODE BYTE per slot (table format 2, hj_slot_codes_info) whatever the
+ * table's size. Without the flag that format is taken exactly where a byte holds any 32-bit key -- (32 - log2(tableSize))
+ * + ceil(log2(probeLength)) <= 7, i.e. tables of 2^27 slots and more at probeLength 4 -- and smaller tables keep 4-byte
+ * keys. With it, a build that meets a key whose bits above the table size do not fit hands over to the 8-byte build
+ * (cause 4 of hj_slot_codes_info); results are the same on every road. For tests of the format at small sizes.
+ * hj_reserve refuses it (HJ_ERR_INVALID) together with HJ_FLAG_KEEP_ROW_IDS, on an algo other than HJ_ALGO_NOCC /
+ * HJ_ALGO_ATOMIC, and with a probeLength above 128. hj_build_keys_dev ignores it. */
+#define HJ_FLAG_SLOT_CODES 0x4u
 
 /* Everything the reference prints in its JSON line (NoCCHashBuild.hpp:127-146,
  * AtomicHashBuild.hpp:133-152) plus device timings. */
@@ -816,14 +825,28 @@ int hj_wave_seams(hj_ctx *ctx, uint32_t *starts, uint32_t *bounds, uint32_t *pco
  * device, and hj_result.buildVariant says 3 either way. out[0] = 1 if the last build's table is the planar one, out[1] =
  * why the planar build handed over, 0 = it did not or was not tried (bit 0: a chunk's log of slots the deferred phase
  * changed did not fit -- an input that defers nearly everything; bit 1: key 0xFFFFFFFF, the 4-byte empty pattern),
- * out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys), out[3] = 0. hj_result.compactFallback does not speak of this.
+ * out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys, 2 = slot codes: hj_slot_codes_info; out[0] is 0 then and out[1]
+ * may carry that road's cause 4), out[3] = 0. hj_result.compactFallback does not speak of this.
  * HJ_ERR_STATE: no open-addressing table. */
 int hj_wave_planar_info(hj_ctx *ctx, uint64_t out[4]);
+/* Slot codes (table format 2: one byte per slot instead of a 4-byte key; see HJ_FLAG_SLOT_CODES). Slot s holds the code
+ * (hi << dbits) | d of the key with home slot s - d and bits above the table size hi; 0xFF = empty; codes use 7 bits.
+ * Host-only arithmetic for a table of tableSize slots (a power of two up to 2^32) at probeLength -- ctx may be NULL:
+ * out[0] = 1 if a build of this table takes the format by itself (every 32-bit key has a code), out[1] = dbits =
+ * ceil(log2(probeLength)), out[2] = hiCap = 2^(7 - dbits) (0: no code at this probeLength), out[3] = log2(tableSize).
+ * With a context whose last build made a table of that size (tableSize 0: that table, at the context's probeLength; waits
+ * for the stream): out[4] = 1 if that table is in slot codes, out[5] = why the road handed over to the 8-byte build, 0 =
+ * it did not or was not taken (the bits of hj_wave_planar_info's out[1], and bit 2, value 4: a key whose high bits no code
+ * holds), out[6] = road the host chose (0 none, 1 by the size rule, 2 forced by the flag), out[7] = table format. Otherwise
+ * out[4..7] = 0. HJ_ERR_INVALID: out NULL, tableSize no power of two or above 2^32, probeLength 0. HJ_ERR_STATE: tableSize 0
+ * without an open-addressing table. */
+int hj_slot_codes_info(hj_ctx *ctx, uint64_t tableSize, uint32_t probeLength, uint64_t out[8]);
 /* The table of the last hj_build_dev / hj_build_keys_dev as its readers see it (waits for the stream; for tests). An LDS
  * build (buildVariant 2, 3, 4, also under HJ_ALGO_HTM) writes only the slots some tuple can reach: out[0], out[1] = the
  * valid slot range [validLo, validHiEx) -- a home slot outside it matches nothing, the slots [validLo, validHiEx + 512)
  * hold defined contents, and everything else in the buffer is whatever an earlier build on this context left there, in
- * that build's format. out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys; HJ_ALGO_HTM: always 0), out[3] = slots of
+ * that build's format. out[2] = table format (0 = 8-byte slots, 1 = 4-byte keys, 2 = one code byte per slot; HJ_ALGO_HTM:
+ * always 0), out[3] = slots of
  * the live table (HJ_ALGO_HTM: 4 per bucket), out[4] = device address of the table buffer, out[5] = its size in bytes
  * (hj_reserve only grows it). With out[4], hj_copy_d2h reads the raw table words. Changes nothing.
  * HJ_ERR_STATE: no table (no build yet, or the last operation was a radix join). */
