@@ -62,6 +62,11 @@ def test_metric_size_uniform_against_the_sequential_oracle():
             for k in ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum"):
                 assert got[k] == want[k], (variant, k, got[k], want[k])
             assert got["outputSum"] == want["outputSumAtomic"]
+            # what the table was: one code byte per slot by the size rule behind the classic rings (what every bench step
+            # takes), 4-byte keys behind the compact rings, 8-byte slots behind the workgroup window
+            info = c.slot_codes_info()
+            assert info["fitsAuto"] and (variant != 0 or (info["road"], info["cause"]) == (1, 0)), (variant, info)
+            assert (info["codes"], info["tableFormat"]) == {0: (True, 2), 4: (False, 1), 2: (False, 0)}[variant], (variant, info)
         # the bare-key entry points a radix shard runs after the exchange, at the same size: at 2^30 the wavefront build cuts
         # the relation into eight rounds' worth of chunks, and the 32-bit instances of the kernels take that path too
         c.copy_h2d(dR, R32); c.copy_h2d(dS, S32)

@@ -656,6 +656,17 @@ def test_maximum_relation_size_on_the_wavefront_rings():
         r = c.fetch()
         assert (r["conflicts"], r["totalMatches"], r["inputSum"], r["tableSumFull"], r["buildVariant"], r["buildDeferred"]) == (
             0, n, tri, tri, 4, 0)
+        # the classic rings on the same relation: a code plane of 2^32 slots, the only table without a high part (tableBits
+        # 32: nothing shifts by 32, every code is the displacement alone)
+        c.reserve("atomic", n, n, buildVariant=3)
+        c.build(dR, n); c.probe(dR, n)
+        c.checksums()
+        r = c.fetch()
+        info = c.slot_codes_info()
+        assert (info["road"], info["tableBits"], info["tableFormat"], info["codes"], info["cause"]) == (1, 32, 2, True, 0), info
+        assert (r["conflicts"], r["totalMatches"], r["inputSum"], r["tableSumFull"], r["buildVariant"], r["compactFallback"]) == (
+            0, n, tri, tri, 3, 0)
+        assert r["tableSumHalf"] == tri - n        # the nocc rule of test_maximum_relation_size: slots [0, rSize) miss key N, which sits in slot N
     with hj.HashJoinContext(0) as c:
         c.reserve("htm", n, n)
         c.build(dR, n); c.probe(dR, n)
