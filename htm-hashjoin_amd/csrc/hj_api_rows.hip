@@ -85,15 +85,23 @@ static bool word_ptr_ok(const void* p) { return !(reinterpret_cast<uintptr_t>(p)
 // a column's pointer: there, and aligned to the column's width
 static bool col_ptr_ok(const void* p, uint32_t width) { return p && !(reinterpret_cast<uintptr_t>(p) & (width - 1)); }
 
+// what hj_gather_dev and hj_gather2_dev refuse before they look at a column
+static int gather_args(hj_ctx* c, const char* fn, const uint32_t* dMap, uint64_t nRows, uint64_t srcRows, const void* cols, uint32_t nCols,
+                       const uint32_t* dValid)
+{
+    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, fn, "more than HJ_GATHER_MAX_COLS columns");
+    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, fn, "cols NULL with nCols > 0");
+    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, fn, "nRows or srcRows above 2^32 - 1");
+    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, fn, "dMap NULL with nRows > 0");
+    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, fn, "neither a column nor a validity plane");
+    return HJ_OK;
+}
+
 int hj_gather_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const hj_gather_col* cols,
                   uint32_t nCols, uint32_t* dValid)
 {
     HJ_ENTER(c, true);
-    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: more than HJ_GATHER_MAX_COLS columns");
-    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: cols NULL with nCols > 0");
-    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: nRows or srcRows above 2^32 - 1");
-    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: dMap NULL with nRows > 0");
-    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, "hj_gather_dev: neither a column nor a validity plane");
+    if (const int rc = gather_args(c, "hj_gather_dev", dMap, nRows, srcRows, cols, nCols, dValid)) return rc;
     GatherCols k{};
     for (uint32_t i = 0; i < nCols; ++i) {
         const hj_gather_col& col = cols[i];
@@ -163,11 +171,7 @@ int hj_gather2_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t row
                    uint32_t nCols, uint32_t* dValid)
 {
     HJ_ENTER(c, true);
-    if (nCols > HJ_GATHER_MAX_COLS) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: more than HJ_GATHER_MAX_COLS columns");
-    if (nCols && !cols) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: cols NULL with nCols > 0");
-    if (nRows > 0xFFFFFFFFull || srcRows > 0xFFFFFFFFull) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: nRows or srcRows above 2^32 - 1");
-    if (nRows && !dMap) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: dMap NULL with nRows > 0");
-    if (nRows && !nCols && !dValid) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev: neither a column nor a validity plane");
+    if (const int rc = gather_args(c, "hj_gather2_dev", dMap, nRows, srcRows, cols, nCols, dValid)) return rc;
     GatherCols2 k{};
     if (const char* what = gather_cols2_error(cols, nCols, nRows, srcRows, dValid, &k)) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev", what);
     if (nRows == 0) return HJ_OK;
@@ -198,7 +202,10 @@ int hj_gather2_info(hj_ctx* c, uint64_t out[4 + HJ_GATHER_MAX_COLS])
 }
 
 // ---- joins on real key columns: hash, verify, sweep of a caller's plane -----
-// The columns of a call, checked: nCols, widths, reserved, and the pointers of the sides in use (rows > 0 on that side)
+// Two column descriptors, hj_key_col and hj_key_col2 (the Arrow layout), each with its own entry points and its own
+// checks; behind the checks there is one path: an hj_key_col is the hj_key_col2 with null offsets, null planes and flags 0.
+
+// The hj_key_col columns of a call, checked: nCols, widths, reserved, and the pointers of the sides in use (rows > 0 on that side)
 static const char* key_cols_error(const hj_key_col* cols, uint32_t nCols, bool useS, bool useR)
 {
     if (nCols == 0 || nCols > HJ_KEY_MAX_COLS) return "nCols must be 1 .. HJ_KEY_MAX_COLS";
@@ -213,62 +220,8 @@ static const char* key_cols_error(const hj_key_col* cols, uint32_t nCols, bool u
     return nullptr;
 }
 
-// hj_key_hash_dev's and hj_key_hash_host's arguments -> the kernel's columns; the message of what is wrong, or nullptr
-static const char* key_hash_args(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols* k)
-{
-    if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
-    if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
-    if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
-    if (nRows && !out) return "output pointer NULL with nRows > 0";
-    for (uint32_t i = 0; i < nCols; ++i) { k->p[i] = side == HJ_KEY_SIDE_S ? cols[i].s : cols[i].r; k->width[i] = cols[i].width; }
-    return nullptr;
-}
-
-int hj_key_hash_dev(hj_ctx* c, const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
-{
-    HJ_ENTER(c, true);
-    KeyCols k{};
-    if (const char* what = key_hash_args(cols, nCols, side, nRows, dOutTuples, &k))
-        return fail(c, HJ_ERR_INVALID, "hj_key_hash_dev", what);
-    if (nRows == 0) return HJ_OK;
-    HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, launch_key_hash(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
-    return HJ_OK;
-}
-
-int hj_key_hash_host(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
-{
-    KeyCols k{};
-    if (key_hash_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
-    key_hash_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
-    return HJ_OK;
-}
-
-int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
-                        uint64_t rRows, const hj_key_col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
-                        uint32_t* dSMarks, uint32_t* dRMarks)
-{
-    HJ_ENTER(c, true);
-    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: nPairs, sRows or rRows above 2^32 - 1");
-    if (const char* what = key_cols_error(cols, nCols, sRows != 0, rRows != 0))
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev", what);
-    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: a map NULL with nPairs > 0");
-    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify_dev: an output pointer NULL with capacity > 0");
-    KeyColsSR k{};
-    for (uint32_t i = 0; i < nCols; ++i) { k.s[i] = cols[i].s; k.r[i] = cols[i].r; k.width[i] = cols[i].width; }
-    HJ_HIP(c, hipSetDevice(c->device));
-    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
-    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_VERIFY].ev[0], c->stream));
-    HJ_HIP(c, launch_pairs_verify(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
-    return call_end(c, CALL_VERIFY, capacity, nPairs);
-}
-
-// ---- the same on key columns in the Arrow layout (hj_key_col2) --------------
-
-// The hj_key_col2 columns of a call, checked like key_cols_error checks hj_key_col's, and what the descriptor adds
-static const char* key_cols2_error(const hj_key_col2* cols, uint32_t nCols, bool useS, bool useR)
+// The hj_key_col2 columns of a call, checked likewise, and what the descriptor adds
+static const char* key_cols_error(const hj_key_col2* cols, uint32_t nCols, bool useS, bool useR)
 {
     if (nCols == 0 || nCols > HJ_KEY_MAX_COLS) return "nCols must be 1 .. HJ_KEY_MAX_COLS";
     if (!cols) return "cols NULL";
@@ -287,55 +240,68 @@ static const char* key_cols2_error(const hj_key_col2* cols, uint32_t nCols, bool
     return nullptr;
 }
 
-static const char* key_hash2_args(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols2* k)
+extern "C++" {      // templates: one body per descriptor
+
+static hj_key_col2 key_col2_of(const hj_key_col& col) { return hj_key_col2{col.s, col.r, nullptr, nullptr, nullptr, nullptr, col.width, 0u}; }
+static hj_key_col2 key_col2_of(const hj_key_col2& col) { return col; }
+
+// The arguments of a key hash entry point, on the device or on the host -> the kernel's columns; the message of what is
+// wrong, or nullptr
+template <class Col>
+static const char* key_hash_args(const Col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint64_t* out, KeyCols2* k)
 {
     if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
     if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
-    if (const char* what = key_cols2_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
+    if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
     if (nRows && !out) return "output pointer NULL with nRows > 0";
     const bool S = side == HJ_KEY_SIDE_S;
     for (uint32_t i = 0; i < nCols; ++i) {
-        k->p[i] = S ? cols[i].s : cols[i].r; k->off[i] = S ? cols[i].sOffsets : cols[i].rOffsets;
-        k->valid[i] = S ? cols[i].sValid : cols[i].rValid; k->width[i] = cols[i].width; k->flags[i] = cols[i].flags;
+        const hj_key_col2 col = key_col2_of(cols[i]);
+        k->p[i] = S ? col.s : col.r; k->off[i] = S ? col.sOffsets : col.rOffsets;
+        k->valid[i] = S ? col.sValid : col.rValid; k->width[i] = col.width; k->flags[i] = col.flags;
     }
     return nullptr;
 }
 
-int hj_key_hash2_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+// hj_key_hash_dev and hj_key_hash2_dev behind their names
+template <class Col>
+static int key_hash_dev(hj_ctx* c, const char* fn, const Col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask,
+                        uint64_t* dOutTuples)
 {
-    HJ_ENTER(c, true);
     KeyCols2 k{};
-    if (const char* what = key_hash2_args(cols, nCols, side, nRows, dOutTuples, &k))
-        return fail(c, HJ_ERR_INVALID, "hj_key_hash2_dev", what);
+    if (const char* what = key_hash_args(cols, nCols, side, nRows, dOutTuples, &k)) return fail(c, HJ_ERR_INVALID, fn, what);
     if (nRows == 0) return HJ_OK;
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, launch_key_hash2(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
     return HJ_OK;
 }
 
-int hj_key_hash2_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+template <class Col>
+static int key_hash_on_host(const Col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
 {
     KeyCols2 k{};
-    if (key_hash2_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
+    if (key_hash_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
     key_hash2_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
     return HJ_OK;
 }
 
-int hj_pairs_verify2_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
-                         uint64_t rRows, const hj_key_col2* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
-                         uint32_t* dSMarks, uint32_t* dRMarks)
+// hj_pairs_verify_dev and hj_pairs_verify2_dev behind their names: one call record and one cursor (hj_verify_info reports
+// the last call of either)
+template <class Col>
+static int pairs_verify_dev(hj_ctx* c, const char* fn, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase,
+                            uint64_t sRows, uint64_t rRows, const Col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                            uint32_t* dSMarks, uint32_t* dRMarks)
 {
-    HJ_ENTER(c, true);
     if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: nPairs, sRows or rRows above 2^32 - 1");
-    if (const char* what = key_cols2_error(cols, nCols, sRows != 0, rRows != 0))
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev", what);
-    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: a map NULL with nPairs > 0");
-    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, "hj_pairs_verify2_dev: an output pointer NULL with capacity > 0");
+        return fail(c, HJ_ERR_INVALID, fn, "nPairs, sRows or rRows above 2^32 - 1");
+    if (const char* what = key_cols_error(cols, nCols, sRows != 0, rRows != 0)) return fail(c, HJ_ERR_INVALID, fn, what);
+    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, fn, "a map NULL with nPairs > 0");
+    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, fn, "an output pointer NULL with capacity > 0");
     KeyCols2SR k{};
     for (uint32_t i = 0; i < nCols; ++i) {
-        k.s[i] = cols[i].s; k.r[i] = cols[i].r; k.sOff[i] = cols[i].sOffsets; k.rOff[i] = cols[i].rOffsets;
-        k.sValid[i] = cols[i].sValid; k.rValid[i] = cols[i].rValid; k.width[i] = cols[i].width; k.flags[i] = cols[i].flags;
+        const hj_key_col2 col = key_col2_of(cols[i]);
+        k.s[i] = col.s; k.r[i] = col.r; k.sOff[i] = col.sOffsets; k.rOff[i] = col.rOffsets;
+        k.sValid[i] = col.sValid; k.rValid[i] = col.rValid; k.width[i] = col.width; k.flags[i] = col.flags;
     }
     HJ_HIP(c, hipSetDevice(c->device));
     const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
@@ -343,6 +309,48 @@ int hj_pairs_verify2_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR
     HJ_HIP(c, hipEventRecord(c->call[CALL_VERIFY].ev[0], c->stream));
     HJ_HIP(c, launch_pairs_verify2(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
     return call_end(c, CALL_VERIFY, capacity, nPairs);
+}
+
+}  // extern "C++"
+
+int hj_key_hash_dev(hj_ctx* c, const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+{
+    HJ_ENTER(c, true);
+    return key_hash_dev(c, "hj_key_hash_dev", cols, nCols, side, nRows, keyMask, dOutTuples);
+}
+
+int hj_key_hash_host(const hj_key_col* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+{
+    return key_hash_on_host(cols, nCols, side, nRows, keyMask, outTuples);
+}
+
+int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                        uint64_t rRows, const hj_key_col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                        uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    return pairs_verify_dev(c, "hj_pairs_verify_dev", dMapS, dMapR, nPairs, sRowBase, sRows, rRows, cols, nCols, dOutS, dOutR, capacity, dSMarks,
+                            dRMarks);
+}
+
+int hj_key_hash2_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
+{
+    HJ_ENTER(c, true);
+    return key_hash_dev(c, "hj_key_hash2_dev", cols, nCols, side, nRows, keyMask, dOutTuples);
+}
+
+int hj_key_hash2_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* outTuples)
+{
+    return key_hash_on_host(cols, nCols, side, nRows, keyMask, outTuples);
+}
+
+int hj_pairs_verify2_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                         uint64_t rRows, const hj_key_col2* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
+                         uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    return pairs_verify_dev(c, "hj_pairs_verify2_dev", dMapS, dMapR, nPairs, sRowBase, sRows, rRows, cols, nCols, dOutS, dOutR, capacity, dSMarks,
+                            dRMarks);
 }
 
 int hj_verify_info(hj_ctx* c, uint64_t out[4])

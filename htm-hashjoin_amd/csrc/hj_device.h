@@ -693,6 +693,49 @@ __device__ __forceinline__ void stage_finish(PairStage<NT>& st, const Out& out, 
         }
     }
 }
+
+// ---- the pair-filter frame of the kernels that take a pair list and keep part of it (k_pairs_verify2, k_pairs_where) ----
+// What the two kernels have in common around their column / term loop: the shape and its names, the flow below, and the
+// launch. The flow is written out in each kernel, the same text twice, NOT shared as device code: as one function that
+// takes the loop as a callable the compiler copies the kernel's by-value column struct into scalar registers up front
+// (the callable captures it by reference) and the variable-length verify instance spills; as two inlined halves around the
+// kernel's own loop the registers are the same but the code is not, and the calls without mark planes measured 3 to 7 %
+// slower (profiles/join_on_columns.md, (e)). A change to the flow is made in both kernels; tools/asm_diff.py and
+// tests/test_gpu_pair_filter_frame.py hold them together.
+// Shape: one workgroup of kBlock lanes per kFilterBlockPairs = 1024 consecutive pairs, so the stage is flushed exactly
+// once; a wavefront owns 256 consecutive pairs and takes them as kFilterLanePairs = 4 steps of 64, the map reads coalesced
+// and nontemporal, all eight in flight before the first is looked at. A pair with an HJ_NO_ROW entry, or with a row outside
+// its relation, is dropped before anything is dereferenced, and counted (ballots) into cursor[1]. The kernel's own loop
+// settles the lane's four pairs: si / ri are the rows with S's base off, live comes in as "not dropped" and goes out as
+// "kept". Its loads are to be unconditional (a load under a per-lane condition is a branch around it, and the wait
+// counters in front of the next one would then wait for it), so a dropped pair brings a spare row, which exists --
+// neighbouring lanes neighbouring rows, not all one address; with sRows or rRows 0 there is no row to read, every pair is
+// dropped and the loop is not run. The kept count is agreed on by stage_reserve (wavefront scan + LDS totals, one barrier),
+// the kept pairs are staged, the run is claimed with one atomicAdd on the 64-bit cursor and leaves through flush_plane
+// (stage_flush, R's marks with it); S's marks are set from the stage too: neighbouring lanes hold neighbouring pairs, and
+// a pair the capacity cuts marks like any other.
+constexpr uint32_t kFilterStepPairs = kWave;
+constexpr uint32_t kFilterLanePairs = 4;                              // pairs in flight per lane, kFilterStepPairs apart
+constexpr uint32_t kFilterWavePairs = kFilterStepPairs * kFilterLanePairs;
+constexpr uint32_t kFilterWaves = kBlock / kWave;
+constexpr uint32_t kFilterBlockPairs = kFilterWavePairs * kFilterWaves;      // 1024
+static_assert(kFilterBlockPairs <= kStagePairs, "a workgroup's pairs fit one stage: it is flushed exactly once");
+
+// The launch of either kernel: k(mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, out, S's marks).
+// sMarks / rMarks: the two planes in RMarks' layout, either may be null.
+template <class Kernel, class Cols>
+inline hipError_t launch_pair_filter(Kernel kernel, const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                                     uint32_t rRows, const Cols& cols, uint32_t nCols, const PairsOut& out, uint32_t* sMarks, uint32_t* rMarks,
+                                     hipStream_t s)
+{
+    if (nPairs == 0) return hipSuccess;
+    const RMarks mkS{sMarks, sRowBase, sMarks ? sRows : 0u}, mkR{rMarks, 0u, rMarks ? rRows : 0u};
+    const PairsOutMarked o = pairs_out_of<true>(out, &mkR);
+    const dim3 grid((uint32_t)((nPairs + kFilterBlockPairs - 1) / kFilterBlockPairs));        // nPairs <= 2^32 - 1: <= 2^22 workgroups
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, o, mkS);
+    return hipGetLastError();
+}
+
 uint32_t pairs_max_probe_len();          // longest walk a round of k_probe_pairs can stage
 // the table must be in the 8-byte slot format (kFormatSlots8): the R row is the index word of the slot
 // marks != nullptr (kinds INNER and LEFT only): the MARK instantiation, which also sets the bit of every R row it produces
@@ -736,27 +779,19 @@ hipError_t launch_gather2(const uint32_t* map, uint64_t nRows, uint32_t rowBase,
                           uint32_t* valid, unsigned long long* counts, unsigned long long* totals, uint32_t* work, hipStream_t s);
 
 // ---- joins on real key columns (defined in hj_keys.hip) ----------------------
-// The key columns of a call as the kernels take them, by value in the kernel arguments (hj_key_col, include/htm_hashjoin.h):
-// the hash reads one side (KeyCols), the verify step both (KeyColsSR).
-constexpr uint32_t kKeyMaxCols = 4;           // HJ_KEY_MAX_COLS
-struct KeyCols { const void* p[kKeyMaxCols]; uint32_t width[kKeyMaxCols]; };
-struct KeyColsSR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; uint32_t width[kKeyMaxCols]; };
-// out[i] = the join word of row i (the header's MurmurHash3_x86_32 over the row's key columns, & mask) as an 8-byte tuple.
-// mask is the effective one (never 0). The caller has checked widths, alignment and nRows <= 2^32 - 1.
-hipError_t launch_key_hash(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s);
-void key_hash_host(const KeyCols& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out);   // the same body in a host loop
-// Candidate pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose key columns are bytewise equal, to `out` as the pairs
-// kernels write theirs (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the candidates dropped as
-// HJ_NO_ROW or outside sRows / rRows, which are never dereferenced). Every kept pair sets bit s of sMarks and bit r of
-// rMarks (RMarks' layout; either may be null). The caller has checked the columns and nPairs <= 2^32 - 1.
-hipError_t launch_pairs_verify(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                               uint32_t rRows, const KeyColsSR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
-                               hipStream_t s);
-// The same two steps on key columns in the Arrow layout (hj_key_col2, include/htm_hashjoin.h): per column and side the
+// The key columns of a call as the kernels take them, by value in the kernel arguments: the hash reads one side
+// (KeyCols2), the verify step both (KeyCols2SR). They are hj_key_col2's (include/htm_hashjoin.h): per column and side the
 // values (fixed width) or the bytes buffer (width 0), the rows + 1 offsets of a variable-length column (else null) and the
-// validity plane (null: no NULLs); flags: HJ_KEY_NULLS_EQUAL. The hash and the column equality are the header's. nRows is
-// also what bounds the validity words the hash reads: ceil(nRows / 32). The caller has checked what the header says the
-// entry points refuse.
+// validity plane (null: no NULLs); flags: HJ_KEY_NULLS_EQUAL. An hj_key_col is the same column with null offsets, null
+// planes and flags 0: hj_key_hash_dev, hj_key_hash_host and hj_pairs_verify_dev fill the descriptor that way.
+// launch_key_hash2: out[i] = the join word of row i (the header's hash over the row's key columns, & mask) as an 8-byte
+// tuple. mask is the effective one (never 0). nRows is also what bounds the validity words the hash reads: ceil(nRows / 32).
+// launch_pairs_verify2: candidate pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose key columns are equal as the header
+// defines it, to `out` as the pairs kernels write theirs (out.cursor: two 64-bit words, zeroed before the launch: kept
+// pairs, then the candidates dropped as HJ_NO_ROW or outside sRows / rRows, which are never dereferenced). Every kept pair
+// sets bit s of sMarks and bit r of rMarks (RMarks' layout; either may be null).
+// The caller has checked what the header says the entry points refuse, and nRows, nPairs <= 2^32 - 1.
+constexpr uint32_t kKeyMaxCols = 4;           // HJ_KEY_MAX_COLS
 struct KeyCols2 { const void* p[kKeyMaxCols]; const uint32_t* off[kKeyMaxCols]; const uint32_t* valid[kKeyMaxCols];
                   uint32_t width[kKeyMaxCols], flags[kKeyMaxCols]; };
 struct KeyCols2SR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; const uint32_t* sOff[kKeyMaxCols]; const uint32_t* rOff[kKeyMaxCols];
@@ -777,7 +812,7 @@ constexpr uint32_t kCmpEq = 0, kCmpNe = 1, kCmpLt = 2, kCmpLe = 3, kCmpGt = 4, k
 constexpr uint32_t kValUint = 0, kValInt = 1, kValFloat = 2;                                  // hj_val_type
 struct WhereTerms { const void* s[kWhereMaxTerms]; const void* r[kWhereMaxTerms]; const uint32_t* sValid[kWhereMaxTerms];
                     const uint32_t* rValid[kWhereMaxTerms]; uint32_t width[kWhereMaxTerms], type[kWhereMaxTerms], op[kWhereMaxTerms]; };
-// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `out` as launch_pairs_verify writes its kept pairs
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `out` as launch_pairs_verify2 writes its kept pairs
 // (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the pairs dropped as HJ_NO_ROW or outside sRows /
 // rRows, which are never dereferenced); the marks as there. The caller has checked the terms and nPairs <= 2^32 - 1.
 hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,

@@ -5,28 +5,25 @@
 // term  s[si] OP r[ri]  holds and marks their S and R rows in two caller-owned planes, so that all eight kinds follow from
 // the kept pairs and two sweeps -- the flow of hj_pairs_verify_dev (hj_keys.hip) with typed comparisons in place of bytes.
 //
-// k_pairs_where. Shape: k_pairs_verify's, because profiles/join_on.md measured that shape. One workgroup of kBlock lanes
-// per kWhereBlockPairs = 1024 consecutive pairs, so the LDS stage (PairStage, hj_device.h) is flushed exactly once; a
-// wavefront owns 256 consecutive pairs and takes them as kWhereLanePairs = 4 steps of 64, the map reads coalesced and
-// nontemporal. A pair with an HJ_NO_ROW entry, or with a row outside its relation, is dropped before anything is
-// dereferenced. The terms are evaluated one after the other: the S and the R element of the term for all four pairs of the
-// lane -- eight element-granular random loads, and with validity planes the eight words beside them -- are in flight before
-// the first compare; a pair that an earlier term has rejected is read again and a dropped one reads a spare row, instead of
-// branching around their loads (a branch would make every load wait for the one before it).
+// k_pairs_where. Shape and flow: the pair-filter frame (hj_device.h) as k_pairs_verify2 (hj_keys.hip) has it, because
+// profiles/join_on.md measured that shape -- 1024 pairs per workgroup, four per lane, dropped pairs counted and never
+// dereferenced, one LDS stage flushed once, both sides marked from it; the flow is written out in both kernels. What is this
+// kernel's own is the loop in the middle. The terms are evaluated one after the other: the S and the R element of the
+// term for all four pairs of the lane -- eight element-granular random loads, and with validity planes the eight words
+// beside them -- are in flight before the first compare; a pair that an earlier term has rejected is read again and a
+// dropped one reads a spare row, instead of branching around their loads (a branch would make every load wait for the
+// one before it).
 // Width, type and op of a term are kernel arguments, so scalar branches select among them; the 6 x 10 x 4 combinations
 // are not instantiated. The switch on the width holds the loads alone, every element zero-extended to 64 bits. The compare
 // is where_holds, ONE __host__ __device__ body that hj_pairs_where_host runs in a host loop: the two raw words are widened
 // to one of two domains -- a 64-bit integer, sign-extended from the width and its sign bit flipped for HJ_VAL_INT so that
 // one unsigned compare serves both, or a double, to which a float widens exactly --, `lt`, `eq` and `unordered` are derived
 // once, and the op picks from those three bits.
-// The rest is k_pairs_verify's: the kept count is agreed on by stage_reserve, the kept pairs are staged, the run is
-// claimed with one atomicAdd on the 64-bit cursor and leaves through flush_plane (stage_flush), and the marks of both sides
-// are set from the stage (mark_plane), a pair the capacity cuts like any other.
 // Two instances: the launch picks kValid = false when no term has a validity plane, so that plain columns do not carry the
 // eight validity words of a term.
 // What it does NOT do: the pairs are taken in the order the join left them, so both elements of a term are random
 // element-granular reads; a term's loads wait for those of the term before (the wait counters cannot tell the arms of the
-// width switch apart); no constants, no arithmetic, no OR; the terms are not fused into the verify kernels.
+// width switch apart); no constants, no arithmetic, no OR; the terms are not fused into the verify kernel.
 
 #include "hj_device.h"
 
@@ -35,13 +32,6 @@
 namespace hj {
 
 namespace {
-
-constexpr uint32_t kWhereStepPairs = kWave;
-constexpr uint32_t kWhereLanePairs = 4;                               // pairs in flight per lane, kWhereStepPairs apart
-constexpr uint32_t kWhereWavePairs = kWhereStepPairs * kWhereLanePairs;
-constexpr uint32_t kWhereWaves = kBlock / kWave;
-constexpr uint32_t kWhereBlockPairs = kWhereWavePairs * kWhereWaves;  // 1024
-static_assert(kWhereBlockPairs <= kStagePairs, "a workgroup's pairs fit one stage: it is flushed exactly once");
 
 // the raw word of a FLOAT element as a double: binary32 widens exactly
 __host__ __device__ __forceinline__ double where_real(uint64_t raw, uint32_t width)
@@ -75,20 +65,20 @@ __host__ __device__ __forceinline__ bool where_holds(uint32_t type, uint32_t wid
 }
 
 // One term's loads for the lane's pairs: both elements of every pair, and with kValid the validity word of either side
-// (null plane: all valid), all of them before the first compare. The loads are unconditional -- see k_pairs_verify's
-// verify_col for why.
+// (null plane: all valid), all of them before the first compare. The loads are unconditional -- see the pair-filter
+// frame (hj_device.h) for why.
 template <class E, bool kValid>
 __device__ __forceinline__ void where_load(const void* sCol, const void* rCol, const uint32_t* sValid, const uint32_t* rValid,
-                                           const uint32_t (&si)[kWhereLanePairs], const uint32_t (&ri)[kWhereLanePairs],
-                                           uint64_t (&a)[kWhereLanePairs], uint64_t (&b)[kWhereLanePairs],
-                                           uint32_t (&vs)[kWhereLanePairs], uint32_t (&vr)[kWhereLanePairs])
+                                           const uint32_t (&si)[kFilterLanePairs], const uint32_t (&ri)[kFilterLanePairs],
+                                           uint64_t (&a)[kFilterLanePairs], uint64_t (&b)[kFilterLanePairs],
+                                           uint32_t (&vs)[kFilterLanePairs], uint32_t (&vr)[kFilterLanePairs])
 {
     if constexpr (kValid) {
 #pragma unroll
-        for (uint32_t j = 0; j < kWhereLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
+        for (uint32_t j = 0; j < kFilterLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
     }
 #pragma unroll
-    for (uint32_t j = 0; j < kWhereLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
     __builtin_amdgcn_sched_barrier(0);                                // no compare moves up between the loads: it would wait there
 }
 
@@ -102,33 +92,34 @@ inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
 
 }  // namespace
 
-// out, sMarks: as k_pairs_verify takes them (cursor[0]: kept pairs; cursor[1]: dropped pairs)
+// out, sMarks: as k_pairs_verify2 takes them (cursor[0]: kept pairs; cursor[1]: dropped pairs). The pair-filter frame
+// (hj_device.h) around the terms
 template <bool kValid>
 __global__ void __launch_bounds__(kBlock)
 k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
               uint32_t rRows, WhereTerms terms, uint32_t nTerms, PairsOutMarked out, RMarks sMarks)
 {
-    __shared__ uint32_t ldsS[kWhereBlockPairs], ldsR[kWhereBlockPairs], ldsTot[2 * kWhereWaves], ldsDrop[kWhereWaves];
+    __shared__ uint32_t ldsS[kFilterBlockPairs], ldsR[kFilterBlockPairs], ldsTot[2 * kFilterWaves], ldsDrop[kFilterWaves];
     __shared__ unsigned long long ldsBase;
     PairStage<kBlock> st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
     const uint32_t lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const uint64_t k0 = (uint64_t)blockIdx.x * kWhereBlockPairs + w * kWhereWavePairs + lane;     // the lane's first pair
+    const uint64_t k0 = (uint64_t)blockIdx.x * kFilterBlockPairs + w * kFilterWavePairs + lane;     // the lane's first pair
 
     // the map entries of the lane's four pairs, all in flight before the first is looked at
-    uint32_t es[kWhereLanePairs], er[kWhereLanePairs];
+    uint32_t es[kFilterLanePairs], er[kFilterLanePairs];
 #pragma unroll
-    for (uint32_t j = 0; j < kWhereLanePairs; ++j) {
-        const uint64_t k = k0 + j * kWhereStepPairs;
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) {
+        const uint64_t k = k0 + j * kFilterStepPairs;
         es[j] = er[j] = kNoRow;
         if (k < nPairs) { es[j] = __builtin_nontemporal_load(mapS + k); er[j] = __builtin_nontemporal_load(mapR + k); }
     }
 
-    uint32_t si[kWhereLanePairs], ri[kWhereLanePairs];
-    bool live[kWhereLanePairs];
+    uint32_t si[kFilterLanePairs], ri[kFilterLanePairs];
+    bool live[kFilterLanePairs];
     uint32_t nDrop = 0;                                               // of this wavefront (ballots: the same in every lane)
 #pragma unroll
-    for (uint32_t j = 0; j < kWhereLanePairs; ++j) {
-        const bool in = k0 + j * kWhereStepPairs < nPairs;
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) {
+        const bool in = k0 + j * kFilterStepPairs < nPairs;
         si[j] = es[j] - sRowBase; ri[j] = er[j];
         live[j] = in && es[j] != kNoRow && er[j] != kNoRow && si[j] < sRows && ri[j] < rRows;       // the raw entries: whatever the base
         nDrop += (uint32_t)__popcll(__ballot(in && !live[j]));
@@ -140,13 +131,13 @@ k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ ma
         // a dropped pair reads, and ignores, one of the first rows (its validity word too: it exists)
         const uint32_t spareS = threadIdx.x < sRows ? threadIdx.x : sRows - 1u, spareR = threadIdx.x < rRows ? threadIdx.x : rRows - 1u;
 #pragma unroll
-        for (uint32_t j = 0; j < kWhereLanePairs; ++j) { si[j] = live[j] ? si[j] : spareS; ri[j] = live[j] ? ri[j] : spareR; }
+        for (uint32_t j = 0; j < kFilterLanePairs; ++j) { si[j] = live[j] ? si[j] : spareS; ri[j] = live[j] ? ri[j] : spareR; }
 #pragma unroll
         for (uint32_t t = 0; t < kWhereMaxTerms; ++t) {
             if (t >= nTerms) continue;                                // kernel arguments: uniform
             const uint32_t *pvs = kValid ? terms.sValid[t] : nullptr, *pvr = kValid ? terms.rValid[t] : nullptr;
-            uint64_t a[kWhereLanePairs], b[kWhereLanePairs];
-            uint32_t vs[kWhereLanePairs], vr[kWhereLanePairs];
+            uint64_t a[kFilterLanePairs], b[kFilterLanePairs];
+            uint32_t vs[kFilterLanePairs], vr[kFilterLanePairs];
             switch (terms.width[t]) {
                 case 1: where_load<uint8_t, kValid>(terms.s[t], terms.r[t], pvs, pvr, si, ri, a, b, vs, vr); break;
                 case 2: where_load<uint16_t, kValid>(terms.s[t], terms.r[t], pvs, pvr, si, ri, a, b, vs, vr); break;
@@ -154,7 +145,7 @@ k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ ma
                 default: where_load<uint64_t, kValid>(terms.s[t], terms.r[t], pvs, pvr, si, ri, a, b, vs, vr); break;
             }
 #pragma unroll
-            for (uint32_t j = 0; j < kWhereLanePairs; ++j) {
+            for (uint32_t j = 0; j < kFilterLanePairs; ++j) {
                 bool ok = where_holds(terms.type[t], terms.width[t], terms.op[t], a[j], b[j]);
                 if constexpr (kValid) ok = ok && ((vs[j] >> (si[j] & 31u)) & (vr[j] >> (ri[j] & 31u)) & 1u);
                 live[j] = live[j] && ok;
@@ -164,16 +155,16 @@ k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ ma
 
     uint32_t m = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kWhereLanePairs; ++j) m += (uint32_t)live[j];
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) m += (uint32_t)live[j];
     bool any;
     uint32_t pos = stage_reserve<kInner>(st, out, m, false, any);     // never flushes: the stage was empty and takes every pair
 #pragma unroll
-    for (uint32_t j = 0; j < kWhereLanePairs; ++j)
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j)
         if (live[j]) { st.s[pos] = es[j]; st.r[pos] = er[j]; ++pos; }
     if (threadIdx.x == 0) {
         uint32_t d = 0;
 #pragma unroll
-        for (uint32_t i = 0; i < kWhereWaves; ++i) d += ldsDrop[i];
+        for (uint32_t i = 0; i < kFilterWaves; ++i) d += ldsDrop[i];
         if (d) atomicAdd(out.cursor + 1, (unsigned long long)d);
     }
     const uint32_t kept = st.fill;                                    // the same in every thread
@@ -186,15 +177,10 @@ hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64
                               uint32_t rRows, const WhereTerms& terms, uint32_t nTerms, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
                               hipStream_t s)
 {
-    if (nPairs == 0) return hipSuccess;
-    const RMarks mkS{sMarks, sRowBase, sMarks ? sRows : 0u}, mkR{rMarks, 0u, rMarks ? rRows : 0u};
-    const PairsOutMarked o = pairs_out_of<true>(out, &mkR);
-    const dim3 grid((uint32_t)((nPairs + kWhereBlockPairs - 1) / kWhereBlockPairs));          // nPairs <= 2^32 - 1: <= 2^22 workgroups
     bool valid = false;
     for (uint32_t t = 0; t < nTerms; ++t) valid = valid || terms.sValid[t] || terms.rValid[t];
     const auto kernel = valid ? k_pairs_where<true> : k_pairs_where<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows, rRows, terms, nTerms, o, mkS);
-    return hipGetLastError();
+    return launch_pair_filter(kernel, mapS, mapR, nPairs, sRowBase, sRows, rRows, terms, nTerms, out, sMarks, rMarks, s);
 }
 
 void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,

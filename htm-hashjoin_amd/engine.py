@@ -1337,7 +1337,7 @@ def key_hash_host(cols, key_mask=0):
 _ON_S_SWEEP = {_lib.HJ_JOIN_LEFT: _lib.HJ_R_UNMATCHED, _lib.HJ_JOIN_SEMI: _lib.HJ_R_MATCHED, _lib.HJ_JOIN_ANTI: _lib.HJ_R_UNMATCHED}
 
 
-@_where_keyword("_join_on")
+@_where_keyword("_join_on_arrays")
 def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0):
     """join_tables for keys that are not one 32-bit word: r_keys / s_keys are each one 1-D numpy array or a sequence of 1
     to HJ_KEY_MAX_COLS of them (all of a side of one length; column c of both sides of the same itemsize out of 1, 2, 4,
@@ -1354,11 +1354,12 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     where (keyword only): as in join_tables -- a pair is a match iff the keys are equal and every term holds. The verify step then runs
     without mark planes and with its pairs kept whatever the kind, and HashJoinContext.pairs_where over those pairs sets the
     marks and keeps the pairs of the result."""
-    return _join_on(r_keys, s_keys, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask)
+    return _join_on_arrays(r_keys, s_keys, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask)
 
 
-def _join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0, where=None):
-    """join_on, and join_on with a condition (_where_keyword)"""
+def _join_on_arrays(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0, where=None):
+    """join_on, and join_on with a condition (_where_keyword): its own checks, then the driver of join_on_columns on the
+    arrays as plain KeyColumns"""
     fn = "join_on"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1366,71 +1367,8 @@ def _join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0,
     widths = [a.dtype.itemsize for a in r_keys]
     if widths != [a.dtype.itemsize for a in s_keys]:
         raise ValueError(f"{fn}: the key columns of R have {widths}-byte elements, those of S {[a.dtype.itemsize for a in s_keys]}")
-    if not 0 <= int(key_mask) <= 0xFFFFFFFF:
-        raise ValueError(f"{fn}: key_mask must fit 32 bits, not {key_mask!r}")
-    n_r, n_s = r_keys[0].size, s_keys[0].size
-    if max(n_r, n_s) > 0xFFFFFFFF:
-        raise ValueError(f"{fn}: a relation of more than 2^32 - 1 rows")
-    r_cols = _table_columns(fn, "R", r_cols, n_r)
-    s_cols = _table_columns(fn, "S", s_cols, n_s)
-    step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
-    terms = _where_terms(fn, where, n_s, n_r)
-    rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
-    trivial = rows.without_device(n_s)
-    if trivial is not None:
-        return trivial
-    pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
-    s_sweep = _ON_S_SWEEP.get(rows.kind)
-    cond = _WhereTerms(terms, rows, n_r, n_s, step) if terms is not None else None
-    dev = {}
-
-    def hash_keys(ctx, held, d_tuples, lo, n):
-        """R's key columns go up whole, a slice's into the room kept for one; either is hashed where it lies"""
-        if lo is None:
-            dev["r"] = [held.put(k) for k in r_keys]
-            dev["s"] = [held.alloc(step * w) for w in widths]
-            dev["r_marks"] = held.put(np.zeros((n_r + 31) // 32, dtype=np.uint32))
-            dev["s_marks"] = held.alloc(4 * ((step + 31) // 32))
-            dev["cols"] = list(zip(dev["s"], dev["r"], widths))
-            ctx.key_hash(dev["cols"], _lib.HJ_KEY_SIDE_R, n, d_tuples, key_mask)
-        else:
-            for d, k in zip(dev["s"], s_keys):
-                ctx.copy_h2d(d, k[lo:lo + n])
-            ctx.key_hash(dev["cols"], _lib.HJ_KEY_SIDE_S, n, d_tuples, key_mask)
-
-    def verify(ctx, held, lo, n, d_s, d_r, candidates):
-        """the slice's candidates -> its kept pairs and the marks of both sides, then the rows of its kind"""
-        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
-        capacity = candidates if pairs else 0           # right_semi / right_anti, semi / anti: a mark-only pass
-        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if pairs else (0, 0)
-        ctx.pairs_verify(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_ks, d_kr, capacity, dev["s_marks"], dev["r_marks"])
-        if pairs:
-            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.verify_info()[1])
-            held.free(d_ks, d_kr)
-        if s_sweep is not None:
-            d_rows = held.alloc(4 * n)
-            ctx.mark_rows(dev["s_marks"], n, lo, s_sweep, d_rows, n)
-            rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
-            held.free(d_rows)
-
-    def verify_where(ctx, held, lo, n, d_s, d_r, candidates):
-        """the slice's candidates -> the pairs with equal keys, no plane marked; the condition step takes it from there"""
-        d_es, d_er = held.alloc(4 * candidates), held.alloc(4 * candidates)
-        ctx.pairs_verify(d_s, d_r, candidates, lo, n, n_r, dev["cols"], d_es, d_er, candidates)
-        cond.slice(ctx, held, lo, n, d_es, d_er, ctx.verify_info()[1])
-        held.free(d_es, d_er)
-
-    def r_only(ctx, held):
-        if rows.which is not None:
-            d_rows = held.alloc(4 * n_r)
-            ctx.mark_rows(dev["r_marks"], n_r, 0, rows.which, d_rows, n_r)
-            rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
-
-    # the candidate join is INNER whatever the kind, and the context's own R marks stay out of it: a candidate that the
-    # verify step rejects would have set them
-    _drive_join(r_keys[0], s_keys[0], "radix", _lib.HJ_JOIN_INNER, None, step, verify if cond is None else verify_where, device,
-                radixBits=radixBits, fill=hash_keys, after=r_only if cond is None else cond.r_only)
-    return rows.joined()
+    return _join_key_columns(fn, [KeyColumn(a) for a in r_keys], [KeyColumn(a) for a in s_keys], False, r_cols, s_cols, how, radixBits,
+                             slice_tuples, device, key_mask, where)
 
 
 # ---- key columns in the Arrow layout: NULL keys and variable-length (string) keys ------------------------------------------
@@ -1563,7 +1501,7 @@ def key_hash2_host(cols, key_mask=0):
 
 
 class _ColumnKeys:
-    """What join_on_columns and aggregate_on share: the key columns of both sides on the device (R's whole, a slice of
+    """What join_on, join_on_columns and aggregate_on share: the key columns of both sides on the device (R's whole, a slice of
     S's in the room kept for one), the hash of either side as _drive_join's `fill`, and the verify step of a slice's
     candidates. dev: "cols" (the hj_key_col2 tuples), "s_marks" / "r_marks" (the two mark planes)."""
 
@@ -1646,6 +1584,12 @@ def _join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", null
     widths = [c.width for c in r_keys]
     if widths != [c.width for c in s_keys]:
         raise ValueError(f"{fn}: the key columns of R have widths {widths} (0: variable-length), those of S {[c.width for c in s_keys]}")
+    return _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where)
+
+
+def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where):
+    """The driver of join_on (fn "join_on") and join_on_columns: hash, candidate join, verify, the rows of the kind. r_keys /
+    s_keys: lists of KeyColumn, checked by the caller, column c of both sides of one width; `how` is one of _TABLE_HOWS."""
     if not 0 <= int(key_mask) <= 0xFFFFFFFF:
         raise ValueError(f"{fn}: key_mask must fit 32 bits, not {key_mask!r}")
     n_r, n_s = r_keys[0].rows, s_keys[0].rows
@@ -1689,8 +1633,9 @@ def _join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", null
         cond.slice(ctx, held, lo, n, d_es, d_er, equal)
         held.free(d_es, d_er)
 
-    # as in join_on: the candidate join is INNER whatever the kind, on tuples made on the device (the two arrays stand for
-    # the relations' lengths alone)
+    # the candidate join is INNER whatever the kind, and the context's own R marks stay out of it: a candidate that the
+    # verify step rejects would have set them. Its tuples are made on the device (_drive_join's fill): the two arrays stand
+    # for the relations' lengths alone
     _drive_join(np.empty(n_r, dtype=np.uint8), np.empty(n_s, dtype=np.uint8), "radix", _lib.HJ_JOIN_INNER, None, step,
                 verify if cond is None else verify_where, device, radixBits=radixBits, fill=keys.hash_keys,
                 after=r_only if cond is None else cond.r_only)

@@ -8,6 +8,7 @@ import pytest
 import htm_hashjoin_amd as hj
 
 from keys2_common import MASKS, ROWS, ModelCol, hash_matrix, key_column
+from test_keys_abi import key_words, murmur3_words
 
 pytestmark = pytest.mark.gpu
 
@@ -86,7 +87,8 @@ def test_device_hash_equals_host_hash(dev, n):
 
 
 def test_device_hash_of_plain_columns_equals_key_hash(dev):
-    """the compatibility property on the device: no offsets, no validity, flags 0 -> what k_key_hash writes"""
+    """the compatibility property on the device: no offsets, no validity, flags 0 -> what hj_key_hash_dev writes. Both
+    entry points run one kernel, so the property rests on the header's wording, restated in test_keys_abi.py"""
     n = 5000
     rng = np.random.default_rng(8)
     a, b = rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(0, 1 << 16, n).astype(np.uint16)
@@ -96,6 +98,7 @@ def test_device_hash_of_plain_columns_equals_key_hash(dev):
     dev.ctx.synchronize()
     assert np.array_equal(dev.get(d_new, n, U64), dev.get(d_old, n, U64))
     assert np.array_equal(dev.get(d_new, n, U64), hj.key_hash_host([a, b], key_mask=0xFFF))
+    assert np.array_equal(dev.get(d_new, n, U64), murmur3_words(key_words([a, b]), 0xFFF))
     dev.release()
 
 

@@ -2,7 +2,7 @@
 against hj_pairs_where_host on the same buffers. Every output plane and every marks plane has sentinel words around it that
 must survive. Run with -m gpu.
 
-hj_where.hip: a workgroup of k_pairs_where takes kWhereBlockPairs = 1024 consecutive pairs, a wavefront 256 of them as four
+hj_where.hip: a workgroup of k_pairs_where takes kFilterBlockPairs = 1024 consecutive pairs, a wavefront 256 of them as four
 steps of 64 -- the pair counts below are the lane step, the wavefront's share, the workgroup's share and more than four
 workgroups, each with its neighbours."""
 import ctypes as C

@@ -157,11 +157,13 @@ def test_null_keyed_rows_hash_their_position():
 @pytest.mark.parametrize("key_mask", MASKS)
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1025])
 def test_plain_columns_hash_as_hj_key_hash_host(n, key_mask):
-    """the compatibility property: no offsets, no validity, flags 0 -> the tuples of hj_key_hash_host, tuple for tuple"""
+    """the compatibility property: no offsets, no validity, flags 0 -> the tuples of hj_key_hash_host, tuple for tuple.
+    Both entry points run one body, so the tuples are also held to the header's wording, restated in test_keys_abi.py"""
     rng = np.random.default_rng(1000 * n + (key_mask & 0xFF))
     for widths in MIXES:
         cols = [random_column(rng, w, n) for w in widths]
         old = hj.key_hash_host(cols if len(cols) > 1 else cols[0], key_mask=key_mask)
+        assert np.array_equal(old, murmur3_words(key_words(cols), key_mask)), (widths, n, key_mask)
         assert np.array_equal(hj.key_hash2_host(cols if len(cols) > 1 else cols[0], key_mask=key_mask), old), (widths, n, key_mask)
         assert np.array_equal(hj.key_hash2_host([hj.KeyColumn(c) for c in cols], key_mask=key_mask), old)
 

@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
-"""Prices key_hash2 / pairs_verify2 (key columns in the Arrow layout) against key_hash / pairs_verify: development tool.
+"""Prices key_hash2 / pairs_verify2 on key columns in the Arrow layout (validity planes, variable-length elements) against
+the same kernels on plain columns: development tool.
 
     python tools/bench_join_on_columns.py [--log2n 27] [--var-log2n 27] [--reps 5] [--nulls 0.1] [--out FILE]
 
 |R| = |S| = n = 2^log2n, unique uint64 keys 1..n in two different random orders (generate_relation "pk"), everything
 resident on the device before anything is timed; no map visits the host. The candidates are those of the full join word:
-key_hash(R), prj_build, key_hash(S), prj_probe_pairs, once per leg. The yardstick is the old pair of kernels on the same
-commit, in the same process, alternating with the new pair; its own spread over the rounds is the noise.
-  plain      one non-nullable 8-byte column: key_hash2 / pairs_verify2 on the descriptor key_hash / pairs_verify take
-  nullable   the same column with validity planes on both sides, a share --nulls of the bits clear; the old kernels on
-             the same elements (they know no NULL: they keep every candidate) remain the yardstick
+key_hash(R), prj_build, key_hash(S), prj_probe_pairs, once per leg. There is one hash kernel and one verify kernel; the v1
+names (key_hash / pairs_verify on hj_key_col) run their narrow instances (kVar false, kForm 0).
+  plain      one non-nullable 8-byte column through the v1 names: the timing of those names, to be compared across two
+             builds (profiles/join_on_columns.md, (e)), and the yardstick of the next leg. (Up to the commit that removed
+             the first kernel pair this leg timed that pair against the narrow instances in one process: section (a).)
+  nullable   the same column with validity planes on both sides, a share --nulls of the bits clear, through key_hash2 /
+             pairs_verify2 (kForm 1), alternating with the v1 names on the same elements (kForm 0; they know no NULL: they
+             keep every candidate), whose own spread over the rounds is the noise
              (byte model: the plain one plus n / 8 B of plane for the hash and one 4 B validity word per side and
              candidate for the verify step; the pairs written are put at n though fewer are kept: an upper bound)
   varlen     one variable-length column, 2^var-log2n rows: the element of key k is its 8 little-endian bytes repeated to
@@ -17,8 +21,9 @@ commit, in the same process, alternating with the new pair; its own spread over 
              against the byte model -- hash: 8 B of offsets, the bytes and the 8 B tuple per row; verify: 8 B of maps, 16 B
              of offsets and both elements per candidate, 8 B per kept pair
 Per round the S-side hash is timed with the host clock around the synchronised call (the hash has no *_info) and the
-verify step by verify_info's device time. One JSON line per round, one summary line per leg: median (min..max), the ratio
-of the medians, and the yardstick's spread (max - min) / median."""
+verify step by verify_info's device time. One JSON line per round, one summary line per leg: median (min..max) and the
+spread (max - min) / median of every timing, the model bandwidth of the leg's last variant and, with two variants, the
+ratio of the medians."""
 import argparse
 import json
 import os
@@ -88,7 +93,8 @@ def main():
             return (time.perf_counter() - t0) * 1e6
 
         def leg(name, n, hash_s, verify, bytes_hash, bytes_verify, extra):
-            """hash_s / verify: {"old": call, "new": call}, or "new" alone; verify returns (kept, dropped). Alternating rounds."""
+            """hash_s / verify: {variant: call}, "v1" (the yardstick, where there are two) and / or "new"; verify returns
+            (kept, dropped). Alternating rounds."""
             for which in hash_s:
                 hash_s[which](), verify[which]()                       # warm-up of every shape
             rounds = []
@@ -104,13 +110,12 @@ def main():
             for k in (k for k in rounds[0] if k.endswith("_us")):
                 v = [r[k] for r in rounds]
                 summary[k] = [round(statistics.median(v), 1), min(v), max(v)]
+                summary[k[:-3] + "_spread"] = round((max(v) - min(v)) / statistics.median(v), 3)
+            last = list(hash_s)[-1]
             for step, model in (("hash", bytes_hash), ("verify", bytes_verify)):
-                new = summary[f"{step}_new_us"]
-                summary[f"{step}_new_GBps"] = round(model / new[0] / 1e3, 1)
-                if "old" in hash_s:
-                    old = summary[f"{step}_old_us"]
-                    summary[f"{step}_new_over_old"] = round(new[0] / old[0], 3)
-                    summary[f"{step}_old_spread"] = round((old[2] - old[1]) / old[0], 3)
+                summary[f"{step}_{last}_GBps"] = round(model / summary[f"{step}_{last}_us"][0] / 1e3, 1)
+                if len(hash_s) == 2:
+                    summary[f"{step}_new_over_v1"] = round(summary[f"{step}_new_us"][0] / summary[f"{step}_v1_us"][0], 3)
             summary.update({k: rounds[-1][k] for k in rounds[-1] if k.startswith(("kept_", "dropped_"))})
             emit(summary)
 
@@ -142,10 +147,9 @@ def main():
                     return kept, dropped
                 return run
 
-            old_hash = lambda: c.key_hash(plain, hj.HJ_KEY_SIDE_S, n, d_ts)       # noqa: E731
-            old = verifier(c.pairs_verify, plain, cand, n)
-            leg("plain", n, {"old": old_hash, "new": lambda: c.key_hash2(plain, hj.HJ_KEY_SIDE_S, n, d_ts)},
-                {"old": old, "new": verifier(c.pairs_verify2, plain, cand, n)}, n * 16, cand * 24 + n * 8, {"candidates": cand})
+            v1_hash = lambda: c.key_hash(plain, hj.HJ_KEY_SIDE_S, n, d_ts)        # noqa: E731
+            v1 = verifier(c.pairs_verify, plain, cand, n)
+            leg("plain", n, {"v1": v1_hash}, {"v1": v1}, n * 16, cand * 24 + n * 8, {"candidates": cand})
 
             rng = np.random.default_rng(7)
             planes = []
@@ -155,8 +159,8 @@ def main():
                 planes.append(np.resize(bits, 4 * words).view(np.uint32))
             d_vs, d_vr = put(planes[0]), put(planes[1])
             nullable = [(d_s, d_r, 8, 0, 0, d_vs, d_vr, 0)]
-            leg("nullable", n, {"old": old_hash, "new": lambda: c.key_hash2(nullable, hj.HJ_KEY_SIDE_S, n, d_ts)},
-                {"old": old, "new": verifier(c.pairs_verify2, nullable, cand, n)}, n * 16 + n // 8, cand * 32 + n * 8,
+            leg("nullable", n, {"v1": v1_hash, "new": lambda: c.key_hash2(nullable, hj.HJ_KEY_SIDE_S, n, d_ts)},
+                {"v1": v1, "new": verifier(c.pairs_verify2, nullable, cand, n)}, n * 16 + n // 8, cand * 32 + n * 8,
                 {"candidates": cand, "nulls": a.nulls})
             free(d_vs, d_vr, d_ms, d_mr, d_ks, d_kr)
 
