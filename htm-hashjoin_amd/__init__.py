@@ -10,12 +10,12 @@ from ._lib import (  # noqa: F401
     HJ_JOIN_INNER, HJ_JOIN_LEFT, HJ_JOIN_SEMI, HJ_JOIN_ANTI, HJ_NO_ROW, HJ_GATHER_MAX_COLS, hj_gather_col,
     HJ_KEY_MAX_COLS, HJ_KEY_SIDE_S, HJ_KEY_SIDE_R, hj_key_col, HJ_KEY_NULLS_EQUAL, hj_key_col2, hj_gather_col2,
     HJ_WHERE_MAX_TERMS, HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE, CMP_OPS, HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT,
-    hj_where_term,
+    hj_where_term, ASOF_OPS, hj_asof_term,
     HJ_AGG_MAX_COLS, HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX, HJ_AGG_SIGNED, hj_agg_spec, hj_agg_src, hj_agg_col,
 )
 from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
     outer_join_pairs, radix_outer_join_pairs, join_tables, join_on, key_hash_host,
-    KeyColumn, join_on_columns, key_hash2_host, pairs_where_host, radix_join_aggregate, aggregate_on, prj_agg_layout_info,
+    KeyColumn, join_on_columns, key_hash2_host, pairs_where_host, pairs_asof_host, radix_join_aggregate, aggregate_on, prj_agg_layout_info,
     generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )

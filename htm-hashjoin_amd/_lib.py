@@ -52,6 +52,8 @@ HJ_WHERE_MAX_TERMS = 4
 HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE = 0, 1, 2, 3, 4, 5
 CMP_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT = 0, 1, 2
+# hj_pairs_asof_dev: the ops that order (backward: >=, >; forward: <=, <)
+ASOF_OPS = {op: CMP_OPS[op] for op in (">=", ">", "<=", "<")}
 # aggregating joins (hj_agg_op, hj_agg_spec.flags)
 HJ_AGG_MAX_COLS = 4
 HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
@@ -155,6 +157,10 @@ class hj_where_term(C.Structure):
     ]
 
 
+class hj_asof_term(C.Structure):
+    _fields_ = list(hj_where_term._fields_)     # the same layout; op is one of GE, GT, LE, LT
+
+
 class hj_agg_spec(C.Structure):
     _fields_ = [
         ("op", C.c_uint32),
@@ -219,6 +225,9 @@ def _declare(lib):
         "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
         "hj_where_info": ([vp, P(u64)], i32),
         "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),
+        "hj_pairs_asof_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_asof_term), vp, vp, vp, vp, u64, vp, vp], i32),
+        "hj_asof_info": ([vp, P(u64)], i32),
+        "hj_pairs_asof_host": ([vp, vp, u64, u32, u64, u64, P(hj_asof_term), vp, vp, vp, vp, u64, vp, vp, P(u64)], i32),
         "hj_mark_rows_dev": ([vp, vp, u64, u32, u32, vp, u64], i32),
         "hj_mark_rows_info": ([vp, P(u64)], i32),
         "hj_prj_join_dev": ([vp, vp, u64, vp, u64], i32),

@@ -48,7 +48,8 @@ static int create_common(int device, void* stream, bool own, hj_ctx** out)
               c->buf[B_GATHER_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
               c->buf[B_GATHER2_CTR].reserve(c, (2 + kGatherMaxCols) * sizeof(unsigned long long)) == HJ_OK &&
               c->buf[B_VERIFY_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              c->buf[B_WHERE_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK;
+              c->buf[B_WHERE_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
+              c->buf[B_ASOF_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->time.ev[i]) == hipSuccess;
     for (CallRecord& r : c->call) ok = ok && hipEventCreate(&r.ev[0]) == hipSuccess && hipEventCreate(&r.ev[1]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }

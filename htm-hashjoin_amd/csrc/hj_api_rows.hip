@@ -1,5 +1,5 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), the join conditions beyond equality, and the
+// joins on real key columns (hash, verify, sweep of a caller's plane), the join conditions beyond equality, the as-of step, and the
 // *_info entry point of every call that has a record (hj_host.h: CallRecord). Host-side glue only.
 #include "hj_host.h"
 
@@ -415,6 +415,64 @@ int hj_pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPa
     WhereTerms k{};
     if (where_args(mapS, mapR, nPairs, sRows, rRows, terms, nTerms, outS, outR, capacity, &k)) return HJ_ERR_INVALID;
     pairs_where_host(mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nTerms, outS, outR, capacity, sMarks, rMarks, info);
+    return HJ_OK;
+}
+
+// ---- as-of joins (hj_asof.hip) -----------------------------------------------
+// hj_pairs_asof_dev's and hj_pairs_asof_host's arguments -> the kernels' term; the message of what is wrong, or nullptr
+static const char* asof_args(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint64_t sRows, uint64_t rRows, const hj_asof_term* t,
+                             const uint64_t* bestVal, const uint32_t* bestRow, const uint32_t* outS, const uint32_t* outR, uint64_t capacity,
+                             AsofTerm* k)
+{
+    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull) return "nPairs, sRows or rRows above 2^32 - 1";
+    if (!t) return "term NULL";
+    if (t->type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
+    if (t->op != HJ_CMP_GE && t->op != HJ_CMP_GT && t->op != HJ_CMP_LE && t->op != HJ_CMP_LT)
+        return "op must be HJ_CMP_GE, HJ_CMP_GT, HJ_CMP_LE or HJ_CMP_LT";
+    const bool widthOk = t->width == 4 || t->width == 8 || (t->type != HJ_VAL_FLOAT && (t->width == 1 || t->width == 2));
+    if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
+    if (t->reserved) return "hj_asof_term.reserved must be 0";
+    if (sRows && !col_ptr_ok(t->s, t->width)) return "an s pointer that is NULL or not aligned to its width";
+    if (rRows && !col_ptr_ok(t->r, t->width)) return "an r pointer that is NULL or not aligned to its width";
+    if (!word_ptr_ok(t->sValid) || !word_ptr_ok(t->rValid)) return "a validity pointer that is not 4-byte aligned";
+    if (!bestVal || (reinterpret_cast<uintptr_t>(bestVal) & 7u)) return "dBestVal NULL or not 8-byte aligned";
+    if (!bestRow || !word_ptr_ok(bestRow)) return "dBestRow NULL or not 4-byte aligned";
+    if (nPairs && (!mapS || !mapR)) return "a map NULL with nPairs > 0";
+    if (nPairs && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
+    *k = AsofTerm{t->s, t->r, t->sValid, t->rValid, t->width, t->type, t->op};
+    return nullptr;
+}
+
+int hj_pairs_asof_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                      uint64_t rRows, const hj_asof_term* term, uint64_t* dBestVal, uint32_t* dBestRow, uint32_t* dOutS, uint32_t* dOutR,
+                      uint64_t capacity, uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    AsofTerm k{};
+    if (const char* what = asof_args(dMapS, dMapR, nPairs, sRows, rRows, term, dBestVal, dBestRow, dOutS, dOutR, capacity, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_pairs_asof_dev", what);
+    HJ_HIP(c, hipSetDevice(c->device));
+    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_ASOF_CTR].as<unsigned long long>()};
+    HJ_HIP(c, hipEventRecord(c->call[CALL_ASOF].ev[0], c->stream));          // the whole call: the initialisations too
+    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
+    HJ_HIP(c, launch_pairs_asof(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, reinterpret_cast<unsigned long long*>(dBestVal),
+                                dBestRow, out, dSMarks, dRMarks, c->stream));
+    return call_end(c, CALL_ASOF, capacity, nPairs);
+}
+
+int hj_asof_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    return call_info(c, c->call[CALL_ASOF], c->buf[B_ASOF_CTR].p, 16, out);        // pairs kept, pairs dropped
+}
+
+int hj_pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows, uint64_t rRows,
+                       const hj_asof_term* term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
+                       uint32_t* sMarks, uint32_t* rMarks, uint64_t info[4])
+{
+    AsofTerm k{};
+    if (asof_args(mapS, mapR, nPairs, sRows, rRows, term, bestVal, bestRow, outS, outR, capacity, &k)) return HJ_ERR_INVALID;
+    pairs_asof_host(mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, bestVal, bestRow, outS, outR, capacity, sMarks, rMarks, info);
     return HJ_OK;
 }
 

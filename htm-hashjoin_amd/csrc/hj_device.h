@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -694,14 +695,15 @@ __device__ __forceinline__ void stage_finish(PairStage<NT>& st, const Out& out, 
     }
 }
 
-// ---- the pair-filter frame of the kernels that take a pair list and keep part of it (k_pairs_verify2, k_pairs_where) ----
+// ---- the pair-filter frame of the kernels that take a pair list and keep part of it (k_pairs_verify2, k_pairs_where,
+// k_asof_keep of hj_asof.hip, which repeats the text a third time with one plane load as its loop) ----
 // What the two kernels have in common around their column / term loop: the shape and its names, the flow below, and the
 // launch. The flow is written out in each kernel, the same text twice, NOT shared as device code: as one function that
 // takes the loop as a callable the compiler copies the kernel's by-value column struct into scalar registers up front
 // (the callable captures it by reference) and the variable-length verify instance spills; as two inlined halves around the
 // kernel's own loop the registers are the same but the code is not, and the calls without mark planes measured 3 to 7 %
-// slower (profiles/join_on_columns.md, (e)). A change to the flow is made in both kernels; tools/asm_diff.py and
-// tests/test_gpu_pair_filter_frame.py hold them together.
+// slower (profiles/join_on_columns.md, (e)). A change to the flow is made in both kernels and in k_asof_keep; tools/asm_diff.py
+// and tests/test_gpu_pair_filter_frame.py hold the two together, tests/test_gpu_asof.py the third to the same contract.
 // Shape: one workgroup of kBlock lanes per kFilterBlockPairs = 1024 consecutive pairs, so the stage is flushed exactly
 // once; a wavefront owns 256 consecutive pairs and takes them as kFilterLanePairs = 4 steps of 64, the map reads coalesced
 // and nontemporal, all eight in flight before the first is looked at. A pair with an HJ_NO_ROW entry, or with a row outside
@@ -822,6 +824,103 @@ hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64
 void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
                       const WhereTerms& terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
                       uint32_t* rMarks, uint64_t* info);
+
+// What the condition step (hj_where.hip) and the as-of step (hj_asof.hip) share: how two elements compare, how one orders,
+// and a term's loads for the lane's pairs of the pair-filter frame.
+// the raw word of a FLOAT element as a double: binary32 widens exactly
+__host__ __device__ __forceinline__ double where_real(uint64_t raw, uint32_t width)
+{
+    return width == 4u ? (double)__builtin_bit_cast(float, (uint32_t)raw) : __builtin_bit_cast(double, raw);
+}
+
+// Whether  a OP b  holds, a and b the zero-extended raw words of two valid elements of `width` bytes read as `type`.
+// Unordered (a NaN on either side): lt and eq are false, so EQ, LT and LE fail by themselves and NE holds.
+__host__ __device__ __forceinline__ bool where_holds(uint32_t type, uint32_t width, uint32_t op, uint64_t a, uint64_t b)
+{
+    bool lt, eq, un = false;
+    if (type == kValFloat) {
+        const double x = where_real(a, width), y = where_real(b, width);
+        lt = x < y; eq = x == y; un = x != x || y != y;
+    } else {
+        // INT: sign-extended from its width, then the sign bit flipped -- the order of the signed values as unsigned ones
+        const uint32_t sh = type == kValInt ? 64u - 8u * width : 0u;
+        const uint64_t flip = type == kValInt ? 1ull << 63 : 0ull;
+        const uint64_t x = (uint64_t)((int64_t)(a << sh) >> sh) ^ flip, y = (uint64_t)((int64_t)(b << sh) >> sh) ^ flip;
+        lt = x < y; eq = x == y;
+    }
+    switch (op) {
+        case kCmpEq: return eq;
+        case kCmpNe: return !eq;
+        case kCmpLt: return lt;
+        case kCmpLe: return lt || eq;
+        case kCmpGt: return !(lt || eq || un);
+        default: return !(lt || un);                                  // kCmpGe
+    }
+}
+
+// The order key of the as-of step: the zero-extended raw word of a valid element that is no NaN -> an unsigned 64-bit word
+// that orders as the values do and is equal exactly where where_holds calls two values equal. Integers: where_holds's
+// sign-extend and flip. Floats: widened to double, -0.0 taken for +0.0, then the bits folded -- a negative's all
+// complemented, a positive's sign bit set -- so that negatives order below positives. The forward ops (LT, LE: the SMALLEST
+// R value is wanted) complement the key: every kernel takes a maximum.
+__host__ __device__ __forceinline__ uint64_t asof_key(uint32_t type, uint32_t width, uint32_t op, uint64_t raw)
+{
+    uint64_t key;
+    if (type == kValFloat) {
+        double x = where_real(raw, width);
+        if (x == 0.0) x = 0.0;                                        // -0.0 == 0.0: one key for both
+        const uint64_t bits = __builtin_bit_cast(uint64_t, x);
+        key = (bits >> 63) ? ~bits : bits | (1ull << 63);
+    } else {
+        const uint32_t sh = type == kValInt ? 64u - 8u * width : 0u;
+        key = (uint64_t)((int64_t)(raw << sh) >> sh) ^ (type == kValInt ? 1ull << 63 : 0ull);
+    }
+    return (op == kCmpLt || op == kCmpLe) ? ~key : key;
+}
+
+// One term's loads for the lane's pairs: both elements of every pair, and with kValid the validity word of either side
+// (null plane: all valid), all of them before the first compare. The loads are unconditional -- see the pair-filter
+// frame for why.
+template <class E, bool kValid>
+__device__ __forceinline__ void where_load(const void* sCol, const void* rCol, const uint32_t* sValid, const uint32_t* rValid,
+                                           const uint32_t (&si)[kFilterLanePairs], const uint32_t (&ri)[kFilterLanePairs],
+                                           uint64_t (&a)[kFilterLanePairs], uint64_t (&b)[kFilterLanePairs],
+                                           uint32_t (&vs)[kFilterLanePairs], uint32_t (&vr)[kFilterLanePairs])
+{
+    if constexpr (kValid) {
+#pragma unroll
+        for (uint32_t j = 0; j < kFilterLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
+    __builtin_amdgcn_sched_barrier(0);                                // no compare moves up between the loads: it would wait there
+}
+
+// element i of a column of `width` bytes, zero-extended (the host loops)
+inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
+{
+    uint64_t v = 0;
+    memcpy(&v, static_cast<const uint8_t*>(col) + (size_t)i * width, width);      // little-endian: the low bytes
+    return v;
+}
+
+// ---- as-of joins: one best match per S row (defined in hj_asof.hip) -----------
+// The term of a call as the kernels take it (hj_asof_term, include/htm_hashjoin.h): the pair (s, r) is eligible when
+// s[s] op r[r] holds as a term of the condition step does, op one of LT, LE, GT, GE.
+struct AsofTerm { const void *s, *r; const uint32_t *sValid, *rValid; uint32_t width, type, op; };
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> per S row the eligible pair with the largest asof_key of its R element, ties to
+// the lowest R row, to `out` as launch_pairs_where writes its kept pairs (out.cursor: two 64-bit words, zeroed before the
+// launch: kept pairs, pairs dropped); the marks as there, set by the kept pairs alone. bestVal (sRows 64-bit words) and
+// bestRow (sRows words) are initialised here, on s: after the call bestRow[i] is the R row kept for S row i or kNoRow,
+// bestVal[i] its key (0 without one). The caller has checked the term and nPairs, sRows, rRows <= 2^32 - 1.
+hipError_t launch_pairs_asof(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                             uint32_t rRows, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, PairsOut out,
+                             uint32_t* sMarks, uint32_t* rMarks, hipStream_t s);
+// the same in host loops over host pointers (asof_key and where_holds are the kernels' own), the kept pairs in input
+// order; info: kept, written, 0, dropped (may be null)
+void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
+                     const AsofTerm& term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
+                     uint32_t* sMarks, uint32_t* rMarks, uint64_t* info);
 
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):

@@ -31,6 +31,7 @@ enum Buf {
     B_GATHER2_WORK,             // ... and the workspace of its variable-length columns (gather2_work_words(nRows)), grown by the call
     B_VERIFY_CTR,               // hj_pairs_verify_dev: the output cursor (= pairs kept), then the candidates dropped (two 64-bit words)
     B_WHERE_CTR,                // hj_pairs_where_dev: the output cursor (= pairs kept), then the pairs dropped (two 64-bit words)
+    B_ASOF_CTR,                 // hj_pairs_asof_dev: the output cursor (= pairs kept), then the pairs dropped (two 64-bit words)
     B_MARK_SWEEP,               // hj_mark_rows_dev: the sweep's workspace for a caller's plane (r_sweep_count_words(rows))
     B_AGG,                      // hj_prj_agg_begin: 256 bytes of words (the matches of the last hj_prj_probe_agg_dev), then the match-count
                                 // plane and HJ_AGG_MAX_COLS accumulator planes of 8 bytes per R tuple, in resident order (agg_planes)
@@ -54,7 +55,7 @@ struct DevBuf {
 
 // The last call of one kind, as its *_info entry point reports it (call_info, hj_api_rows.hip): what the caller asked for,
 // and the pair of events around the call's work. `called` and `timed` die separately: see hj_ctx::call.
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_COUNT };
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
@@ -135,7 +136,7 @@ struct hj_ctx {
     struct Agg { bool on = false; uint32_t nCols = 0; uint64_t nR = 0, probes = 0; hj::AggOps ops{}; } agg;
     // ---- the last call of each kind (CallRecord). begin_operation forgets the TIME of the pairs call (its facts stay) and
     // the whole R-rows call, which hj_reserve also forgets with the plane; the two gathers, the verify step, the condition step
-    // (hj_pairs_where_dev) and the sweep of a caller's plane belong to no build and no operation and are never forgotten.
+    // (hj_pairs_where_dev), the as-of step (hj_pairs_asof_dev) and the sweep of a caller's plane belong to no build and no operation and are never forgotten.
     hjapi::CallRecord call[hjapi::CALL_COUNT];
     // ---- streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev). Reset by zipf_release (open, close, destroy).
     struct Zipf {

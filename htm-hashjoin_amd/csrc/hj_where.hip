@@ -15,7 +15,7 @@
 // one before it).
 // Width, type and op of a term are kernel arguments, so scalar branches select among them; the 6 x 10 x 4 combinations
 // are not instantiated. The switch on the width holds the loads alone, every element zero-extended to 64 bits. The compare
-// is where_holds, ONE __host__ __device__ body that hj_pairs_where_host runs in a host loop: the two raw words are widened
+// is where_holds (hj_device.h), ONE __host__ __device__ body that hj_pairs_where_host runs in a host loop: the two raw words are widened
 // to one of two domains -- a 64-bit integer, sign-extended from the width and its sign bit flipped for HJ_VAL_INT so that
 // one unsigned compare serves both, or a double, to which a float widens exactly --, `lt`, `eq` and `unordered` are derived
 // once, and the op picks from those three bits.
@@ -27,70 +27,7 @@
 
 #include "hj_device.h"
 
-#include <string.h>
-
 namespace hj {
-
-namespace {
-
-// the raw word of a FLOAT element as a double: binary32 widens exactly
-__host__ __device__ __forceinline__ double where_real(uint64_t raw, uint32_t width)
-{
-    return width == 4u ? (double)__builtin_bit_cast(float, (uint32_t)raw) : __builtin_bit_cast(double, raw);
-}
-
-// Whether  a OP b  holds, a and b the zero-extended raw words of two valid elements of `width` bytes read as `type`.
-// Unordered (a NaN on either side): lt and eq are false, so EQ, LT and LE fail by themselves and NE holds.
-__host__ __device__ __forceinline__ bool where_holds(uint32_t type, uint32_t width, uint32_t op, uint64_t a, uint64_t b)
-{
-    bool lt, eq, un = false;
-    if (type == kValFloat) {
-        const double x = where_real(a, width), y = where_real(b, width);
-        lt = x < y; eq = x == y; un = x != x || y != y;
-    } else {
-        // INT: sign-extended from its width, then the sign bit flipped -- the order of the signed values as unsigned ones
-        const uint32_t sh = type == kValInt ? 64u - 8u * width : 0u;
-        const uint64_t flip = type == kValInt ? 1ull << 63 : 0ull;
-        const uint64_t x = (uint64_t)((int64_t)(a << sh) >> sh) ^ flip, y = (uint64_t)((int64_t)(b << sh) >> sh) ^ flip;
-        lt = x < y; eq = x == y;
-    }
-    switch (op) {
-        case kCmpEq: return eq;
-        case kCmpNe: return !eq;
-        case kCmpLt: return lt;
-        case kCmpLe: return lt || eq;
-        case kCmpGt: return !(lt || eq || un);
-        default: return !(lt || un);                                  // kCmpGe
-    }
-}
-
-// One term's loads for the lane's pairs: both elements of every pair, and with kValid the validity word of either side
-// (null plane: all valid), all of them before the first compare. The loads are unconditional -- see the pair-filter
-// frame (hj_device.h) for why.
-template <class E, bool kValid>
-__device__ __forceinline__ void where_load(const void* sCol, const void* rCol, const uint32_t* sValid, const uint32_t* rValid,
-                                           const uint32_t (&si)[kFilterLanePairs], const uint32_t (&ri)[kFilterLanePairs],
-                                           uint64_t (&a)[kFilterLanePairs], uint64_t (&b)[kFilterLanePairs],
-                                           uint32_t (&vs)[kFilterLanePairs], uint32_t (&vr)[kFilterLanePairs])
-{
-    if constexpr (kValid) {
-#pragma unroll
-        for (uint32_t j = 0; j < kFilterLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kFilterLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
-    __builtin_amdgcn_sched_barrier(0);                                // no compare moves up between the loads: it would wait there
-}
-
-// element i of a column of `width` bytes, zero-extended (the host loop)
-inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
-{
-    uint64_t v = 0;
-    memcpy(&v, static_cast<const uint8_t*>(col) + (size_t)i * width, width);      // little-endian: the low bytes
-    return v;
-}
-
-}  // namespace
 
 // out, sMarks: as k_pairs_verify2 takes them (cursor[0]: kept pairs; cursor[1]: dropped pairs). The pair-filter frame
 // (hj_device.h) around the terms

@@ -185,6 +185,15 @@ def _where_terms_arr(terms):
     return arr, len(terms)
 
 
+def _asof_term_arr(term):
+    """(s_ptr, r_ptr, width, type, op, s_valid, r_valid), the two planes optional (0) -> one hj_asof_term"""
+    s, r, width, type_, op, s_valid, r_valid = tuple(term) + (0,) * (7 - len(term))
+    a = _lib.hj_asof_term()
+    a.s, a.r, a.sValid, a.rValid = (p or None for p in (s, r, s_valid, r_valid))
+    a.width, a.type, a.op, a.reserved = width, type_, op, 0
+    return a
+
+
 def _agg_specs(specs):
     """[(op, width, flags[, reserved])] -> (hj_agg_spec array, its length)"""
     specs = [tuple(s) + (0,) * (4 - len(s)) for s in specs]
@@ -430,6 +439,29 @@ class HashJoinContext:
         microseconds, pairs it dropped as NO_ROW or out of range); rejected = n_pairs - kept - dropped."""
         out = (C.c_uint64 * 4)()
         self._check(lib.hj_where_info(self._h, out))
+        return tuple(int(x) for x in out)
+
+    # ---- as-of joins: one best match per S row ------------------------------------
+    def pairs_asof(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, term, d_best_val, d_best_row, d_out_s, d_out_r,
+                   capacity, d_s_marks=0, d_r_marks=0):
+        """hj_pairs_asof_dev: of the n_pairs pairs (d_map_s[k] - s_row_base, d_map_r[k]) keeps, per S row, the one eligible
+        pair whose R value is nearest on the permitted side. term = (s_ptr, r_ptr, width, type, op, s_valid, r_valid) as a
+        term of pairs_where, op out of ASOF_OPS: a pair is eligible when s[si] op r[ri] holds (a NULL or a NaN on either
+        side: it does not); ">=" / ">" keep the pair with the largest R value, "<=" / "<" the one with the smallest; ties go
+        to the lowest R row. d_best_val (s_rows 64-bit words) and d_best_row (s_rows 32-bit words) are the caller's planes,
+        initialised by the call: d_best_row[i] ends as the R row kept for S row s_row_base + i, or NO_ROW. Outputs, marks
+        (set by the kept pairs alone), dropped pairs and aliasing as in pairs_where. All pairs of an S row must be in one
+        call. Asynchronous; needs no reserve and no table."""
+        p = lambda d: C.c_void_p(d) if d else None       # noqa: E731
+        self._check(lib.hj_pairs_asof_dev(self._h, p(d_map_s), p(d_map_r), n_pairs, s_row_base, s_rows, r_rows,
+                                          C.byref(_asof_term_arr(term)), p(d_best_val), p(d_best_row), p(d_out_s), p(d_out_r),
+                                          capacity, p(d_s_marks), p(d_r_marks)))
+
+    def asof_info(self):
+        """hj_asof_info (waits for the stream): (pairs the last pairs_asof kept, pairs it wrote, the device time of the whole
+        call in microseconds, pairs it dropped as NO_ROW or out of range)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.hj_asof_info(self._h, out))
         return tuple(int(x) for x in out)
 
     def mark_rows(self, d_marks, rows, row_base, which, d_out, capacity):
@@ -1226,12 +1258,12 @@ class _TableRows:
 
 
 def _where_keyword(impl):
-    """The keyword where= on a join: the decorated function keeps its parameters and, called without where=, runs as it is; a
-    call with where= goes to `impl`, the function of this module that takes the same arguments and the condition."""
+    """The keywords where= and asof= on a join: the decorated function keeps its parameters and, called with neither, runs as
+    it is; a call with either goes to `impl`, the function of this module that takes the same arguments and the two."""
     def deco(fn):
         @functools.wraps(fn)
-        def join(*args, where=None, **kw):
-            return fn(*args, **kw) if where is None else globals()[impl](*args, where=where, **kw)
+        def join(*args, where=None, asof=None, **kw):
+            return fn(*args, **kw) if where is None and asof is None else globals()[impl](*args, where=where, asof=asof, **kw)
         return join
     return deco
 
@@ -1259,13 +1291,20 @@ def join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", p
     then gives the INNER pairs of the path, HashJoinContext.pairs_where keeps those that pass and marks their rows, and the
     kind follows from the kept pairs and the sweeps of the marks; the order of the rows is join_on's. None or an empty
     sequence: no condition.
+    asof (keyword only): one term (s_values, op, r_values) with the values of a where term and op out of ">=", ">" (backward:
+    the latest R row at or before / before the S value) and "<=", "<" (forward). A pair is then a match iff the keys are equal,
+    every where term holds, and it is the AS-OF pair of its S row among such pairs: the one whose R value is the largest
+    (backward) or smallest (forward) for which s op r holds -- a NULL or a NaN on either side never holds --, ties on the value
+    going to the lowest R row. Every S row has at most one match; an S row without an eligible pair is an unmatched S row, an
+    R row that wins no S row an unmatched R row, and all eight kinds follow (HashJoinContext.pairs_asof behind the condition
+    step, which then keeps its pairs whatever the kind and marks nothing).
     Every path joins on one 32-bit word of a tuple; for a 64-bit key, a key of several columns or a 16-byte key: join_on."""
     return _join_tables(relR, relS, r_cols, s_cols, how, path, probeLength, radixBits, slice_tuples, device)
 
 
 def _join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", probeLength=4, radixBits=0, slice_tuples=None,
-                 device=0, where=None):
-    """join_tables, and join_tables with a condition (_where_keyword)"""
+                 device=0, where=None, asof=None):
+    """join_tables, and join_tables with a condition or an as-of term (_where_keyword)"""
     fn = "join_tables"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1277,14 +1316,15 @@ def _join_tables(relR, relS, r_cols=None, s_cols=None, how="inner", path="htm", 
     s_cols = _table_columns(fn, "S", s_cols, relS.size)
     step = _slice_step(fn, relS.size, slice_tuples) if path == "radix" and relS.size else relS.size
     terms = _where_terms(fn, where, relS.size, relR.size)
+    best = _asof_term(fn, asof, relS.size, relR.size)
     rows = _TableRows(how, r_cols, s_cols, relR.size, step, relS.size)
     trivial = rows.without_device(relS.size)
     if trivial is not None:
         return trivial
-    if terms is not None:
+    if terms is not None or best is not None:
         # as in join_on: the probe is INNER whatever the kind, and the context's own R marks stay out of it -- a pair that
         # the condition rejects would have set them
-        cond = _WhereTerms(terms, rows, relR.size, relS.size, step)
+        cond = _pair_steps(terms, best, rows, relR.size, relS.size, step)
         _drive_join(relR, relS, path, _lib.HJ_JOIN_INNER, None, step, cond.slice, device, probeLength=probeLength, radixBits=radixBits,
                     after=cond.r_only)
         return rows.joined()
@@ -1353,11 +1393,15 @@ def join_on(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, 
     ascending; semi and anti give their S rows ascending; for right / full the R-only rows come last, R ascending.
     where (keyword only): as in join_tables -- a pair is a match iff the keys are equal and every term holds. The verify step then runs
     without mark planes and with its pairs kept whatever the kind, and HashJoinContext.pairs_where over those pairs sets the
-    marks and keeps the pairs of the result."""
+    marks and keeps the pairs of the result.
+    asof (keyword only): as in join_tables -- per S row the one pair with equal keys, every where term holding, whose R value is
+    nearest on the permitted side. The verify step and the condition step then keep their pairs and mark nothing, and
+    HashJoinContext.pairs_asof sets the marks and keeps the pairs of the result."""
     return _join_on_arrays(r_keys, s_keys, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask)
 
 
-def _join_on_arrays(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0, where=None):
+def _join_on_arrays(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radixBits=0, slice_tuples=None, device=0, key_mask=0, where=None,
+                    asof=None):
     """join_on, and join_on with a condition (_where_keyword): its own checks, then the driver of join_on_columns on the
     arrays as plain KeyColumns"""
     fn = "join_on"
@@ -1368,7 +1412,7 @@ def _join_on_arrays(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", radix
     if widths != [a.dtype.itemsize for a in s_keys]:
         raise ValueError(f"{fn}: the key columns of R have {widths}-byte elements, those of S {[a.dtype.itemsize for a in s_keys]}")
     return _join_key_columns(fn, [KeyColumn(a) for a in r_keys], [KeyColumn(a) for a in s_keys], False, r_cols, s_cols, how, radixBits,
-                             slice_tuples, device, key_mask, where)
+                             slice_tuples, device, key_mask, where, asof)
 
 
 # ---- key columns in the Arrow layout: NULL keys and variable-length (string) keys ------------------------------------------
@@ -1570,13 +1614,13 @@ r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixB
     NULL and nothing else (the pandas reading); a column built with nulls_equal=True has it by itself.
     The method is join_on's with HashJoinContext.key_hash2 / pairs_verify2 in place of key_hash / pairs_verify; per S
     slice the validity bits are repacked from the slice's first row and the offsets rebased to the slice's own bytes.
-    how, r_cols / s_cols, radixBits, slice_tuples, key_mask, where (keyword only), the result dict and the order of its rows: as in join_on."""
+    how, r_cols / s_cols, radixBits, slice_tuples, key_mask, where and asof (keyword only), the result dict and the order of its rows: as in join_on."""
     return _join_on_columns(r_keys, s_keys, r_cols, s_cols, how, nulls_equal, radixBits, slice_tuples, device, key_mask)
 
 
 def _join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", nulls_equal=False, radixBits=0, slice_tuples=None,
-                     device=0, key_mask=0, where=None):
-    """join_on_columns, and join_on_columns with a condition (_where_keyword)"""
+                     device=0, key_mask=0, where=None, asof=None):
+    """join_on_columns, and join_on_columns with a condition or an as-of term (_where_keyword)"""
     fn = "join_on_columns"
     if not isinstance(how, str) or how not in _TABLE_HOWS:
         raise ValueError(f"{fn}: how must be one of {', '.join(_TABLE_HOWS)}, not {how!r}")
@@ -1584,10 +1628,10 @@ def _join_on_columns(r_keys, s_keys, r_cols=None, s_cols=None, how="inner", null
     widths = [c.width for c in r_keys]
     if widths != [c.width for c in s_keys]:
         raise ValueError(f"{fn}: the key columns of R have widths {widths} (0: variable-length), those of S {[c.width for c in s_keys]}")
-    return _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where)
+    return _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where, asof)
 
 
-def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where):
+def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radixBits, slice_tuples, device, key_mask, where, asof=None):
     """The driver of join_on (fn "join_on") and join_on_columns: hash, candidate join, verify, the rows of the kind. r_keys /
     s_keys: lists of KeyColumn, checked by the caller, column c of both sides of one width; `how` is one of _TABLE_HOWS."""
     if not 0 <= int(key_mask) <= 0xFFFFFFFF:
@@ -1599,6 +1643,7 @@ def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radi
     s_cols = _table_columns(fn, "S", s_cols, n_s)
     step = _slice_step(fn, n_s, slice_tuples) if n_s else 0
     terms = _where_terms(fn, where, n_s, n_r)
+    best = _asof_term(fn, asof, n_s, n_r)
     rows = _TableRows(how, r_cols, s_cols, n_r, step, n_s)
     trivial = rows.without_device(n_s)
     if trivial is not None:
@@ -1606,7 +1651,7 @@ def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radi
     pairs = rows.kind is not None and rows.kind <= _lib.HJ_JOIN_LEFT        # the kept pairs are rows of the result
     s_sweep = _ON_S_SWEEP.get(rows.kind)
     keys = _ColumnKeys(r_keys, s_keys, nulls_equal, key_mask, step)
-    cond = _WhereTerms(terms, rows, n_r, n_s, step) if terms is not None else None
+    cond = _pair_steps(terms, best, rows, n_r, n_s, step)
     dev = keys.dev
 
     def verify(ctx, held, lo, n, d_s, d_r, candidates):
@@ -1646,23 +1691,23 @@ def _join_key_columns(fn, r_keys, s_keys, nulls_equal, r_cols, s_cols, how, radi
 _WHERE_TYPES = {"u": _lib.HJ_VAL_UINT, "i": _lib.HJ_VAL_INT, "f": _lib.HJ_VAL_FLOAT}
 
 
-def _where_side(fn, side, values, n):
+def _where_side(fn, side, values, n, what="a where term"):
     """one side of a term as a fixed-width KeyColumn of n rows; ValueError for what a term cannot compare"""
     col = values if isinstance(values, KeyColumn) else None
     if col is None:
         a = values if isinstance(values, np.ma.MaskedArray) else np.asarray(values)
         if a.ndim != 1:
-            raise ValueError(f"{fn}: the {side} values of a where term must be 1-D, not shape {a.shape}")
+            raise ValueError(f"{fn}: the {side} values of {what} must be 1-D, not shape {a.shape}")
         dt = a.dtype
     elif col.offsets is not None:
-        raise ValueError(f"{fn}: a where term cannot compare a variable-length column ({side})")
+        raise ValueError(f"{fn}: {what} cannot compare a variable-length column ({side})")
     else:
         dt = col.values.dtype
     if dt.kind not in _WHERE_TYPES or dt.itemsize > 8 or (dt.kind == "f" and dt.itemsize < 4):
-        raise ValueError(f"{fn}: a where term compares uint8..uint64, int8..int64, float32 or float64, not {dt} ({side})")
+        raise ValueError(f"{fn}: {what} compares uint8..uint64, int8..int64, float32 or float64, not {dt} ({side})")
     col = KeyColumn(values) if col is None else col
     if n is not None and col.rows != n:
-        raise ValueError(f"{fn}: the {side} values of a where term must have {n} elements, not {col.rows}")
+        raise ValueError(f"{fn}: the {side} values of {what} must have {n} elements, not {col.rows}")
     return col
 
 
@@ -1687,6 +1732,22 @@ def _where_terms(fn, where, n_s=None, n_r=None):
             raise ValueError(f"{fn}: a where term compares {s.values.dtype} (S) with {r.values.dtype} (R); there is no implicit cast")
         out.append((s, _lib.CMP_OPS[op], r, _WHERE_TYPES[s.values.dtype.kind], s.width))
     return out
+
+
+def _asof_term(fn, asof, n_s=None, n_r=None):
+    """asof= as (S KeyColumn, hj_cmp_op, R KeyColumn, hj_val_type, width), the shape of a where term; None for None"""
+    if asof is None:
+        return None
+    what = "the asof term"
+    if not isinstance(asof, (tuple, list)) or len(asof) != 3:
+        raise ValueError(f"{fn}: asof is one term (s_values, op, r_values), not {asof!r}")
+    s_values, op, r_values = asof
+    if not isinstance(op, str) or op not in _lib.ASOF_OPS:
+        raise ValueError(f"{fn}: the op of {what} must be one of {', '.join(_lib.ASOF_OPS)}, not {op!r}")
+    s, r = _where_side(fn, "S", s_values, n_s, what), _where_side(fn, "R", r_values, n_r, what)
+    if s.values.dtype != r.values.dtype:
+        raise ValueError(f"{fn}: {what} compares {s.values.dtype} (S) with {r.values.dtype} (R); there is no implicit cast")
+    return (s, _lib.ASOF_OPS[op], r, _WHERE_TYPES[s.values.dtype.kind], s.width)
 
 
 def pairs_where_host(map_s, map_r, s_row_base, terms, capacity=None, marks=False):
@@ -1721,6 +1782,44 @@ def pairs_where_host(map_s, map_r, s_row_base, terms, capacity=None, marks=False
         raise HashJoinError(rc, "hj_pairs_where_host")
     info = tuple(int(x) for x in info)
     out = {"s_idx": out_s[:info[1]], "r_idx": out_r[:info[1]], "info": info}
+    if marks:
+        out["s_marks"], out["r_marks"] = s_marks, r_marks
+    return out
+
+
+def pairs_asof_host(map_s, map_r, s_row_base, term, capacity=None, marks=False):
+    """hj_pairs_asof_host: HashJoinContext.pairs_asof on numpy arrays, computed by the same code on the host. map_s / map_r:
+    the pairs as two uint32 arrays of one length; term: (s_values, op, r_values) as the asof= of the joins takes it; the S
+    side has len(s_values) rows from s_row_base, the R side len(r_values). capacity (None: every pair fits) cuts what is
+    written, not what is counted or marked.
+    Returns {"s_idx", "r_idx"} (the kept pairs written, in input order), "best_row" (per S row the R row kept, or NO_ROW: the
+    left-outer as-of map), "info" (kept, written, 0, dropped) and, with marks=True, "s_marks" / "r_marks": the two planes as
+    uint32 words, zero before the call. Needs no device."""
+    fn = "pairs_asof_host"
+    map_s, map_r = np.ascontiguousarray(map_s, dtype=np.uint32), np.ascontiguousarray(map_r, dtype=np.uint32)
+    if map_s.ndim != 1 or map_s.shape != map_r.shape:
+        raise ValueError(f"{fn}: the maps must be 1-D and of one length, not shapes {map_s.shape} and {map_r.shape}")
+    col = _asof_term(fn, term)
+    if col is None:
+        raise ValueError(f"{fn}: one term (s_values, op, r_values), not None")
+    s, op, r, type_, width = col
+    n_s, n_r = s.rows, r.rows
+    capacity = map_s.size if capacity is None else int(capacity)
+    (sv, _, sw), (rv, _, rw) = s.take(0, n_s), r.take(0, n_r)
+    ptr = lambda a: a.ctypes.data if a is not None else 0       # noqa: E731
+    arr = _asof_term_arr((ptr(sv), ptr(rv), width, type_, op, ptr(sw), ptr(rw)))
+    out_s, out_r = np.empty(min(capacity, map_s.size), dtype=np.uint32), np.empty(min(capacity, map_s.size), dtype=np.uint32)
+    best_val, best_row = np.empty(max(n_s, 1), dtype=np.uint64), np.empty(max(n_s, 1), dtype=np.uint32)
+    s_marks = np.zeros((n_s + 31) // 32, dtype=np.uint32) if marks else None
+    r_marks = np.zeros((n_r + 31) // 32, dtype=np.uint32) if marks else None
+    info = (C.c_uint64 * 4)()
+    rc = lib.hj_pairs_asof_host(map_s.ctypes.data, map_r.ctypes.data, map_s.size, int(s_row_base), n_s, n_r, C.byref(arr),
+                                best_val.ctypes.data, best_row.ctypes.data, out_s.ctypes.data, out_r.ctypes.data, out_s.size,
+                                ptr(s_marks) or None, ptr(r_marks) or None, info)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_pairs_asof_host")
+    info = tuple(int(x) for x in info)
+    out = {"s_idx": out_s[:info[1]], "r_idx": out_r[:info[1]], "best_row": best_row[:n_s], "info": info}
     if marks:
         out["s_marks"], out["r_marks"] = s_marks, r_marks
     return out
@@ -1764,10 +1863,14 @@ class _WhereTerms:
         if self.pairs:
             rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.where_info()[1])
             held.free(d_ks, d_kr)
+        self.s_rows(ctx, held, lo, n)
+
+    def s_rows(self, ctx, held, lo, n):
+        """the rows a kind takes from the sweep of the slice's S plane"""
         if self.s_sweep is not None:
             d_rows = held.alloc(4 * n)
-            ctx.mark_rows(dev["s_marks"], n, lo, self.s_sweep, d_rows, n)
-            rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
+            ctx.mark_rows(self.dev["s_marks"], n, lo, self.s_sweep, d_rows, n)
+            self.rows.add(ctx, held, lo, n, d_rows, 0, ctx.mark_rows_info()[1])
             held.free(d_rows)
 
     def r_only(self, ctx, held):
@@ -1775,6 +1878,46 @@ class _WhereTerms:
             d_rows = held.alloc(4 * self.n_r)
             ctx.mark_rows(self.dev["r_marks"], self.n_r, 0, self.rows.which, d_rows, self.n_r)
             self.rows.add(ctx, held, None, 0, 0, d_rows, ctx.mark_rows_info()[1])
+
+
+class _AsofStep(_WhereTerms):
+    """_WhereTerms for a join that is given asof=, with or without where=: the as-of term's columns travel as one more term
+    behind the condition's. slice() runs the condition step, where there is one, with its pairs kept whatever the kind and
+    no mark plane, then HashJoinContext.pairs_asof over what it kept: that call sets the marks and gives the pairs of the
+    result. The two best planes are sized for one slice; a slice's pair list is complete when it arrives here (_drive_join
+    probes a slice again whose rows exceeded the planes), so every S row has all its pairs in one call."""
+
+    def __init__(self, best, terms, rows, n_r, n_s, step):
+        super().__init__(list(terms or []) + [best], rows, n_r, n_s, step)
+        self.n_where = len(terms or [])
+
+    def slice(self, ctx, held, lo, n, d_s, d_r, n_pairs):
+        self._put(ctx, held, lo, n)
+        rows, dev = self.rows, self.dev
+        if "best_val" not in dev:
+            dev["best_val"], dev["best_row"] = held.alloc(8 * self.step), held.alloc(4 * self.step)
+        ctx.copy_h2d(dev["s_marks"], np.zeros((n + 31) // 32, dtype=np.uint32))
+        mine = []
+        if self.n_where:
+            mine = [held.alloc(4 * n_pairs), held.alloc(4 * n_pairs)]
+            ctx.pairs_where(d_s, d_r, n_pairs, lo, n, self.n_r, dev["terms"][:self.n_where], mine[0], mine[1], n_pairs)
+            d_s, d_r, n_pairs = mine[0], mine[1], ctx.where_info()[1]
+        capacity = min(n_pairs, n) if self.pairs else 0     # one pair per S row at most; semi / anti and R's kinds: a mark-only pass
+        d_ks, d_kr = (held.alloc(4 * capacity), held.alloc(4 * capacity)) if self.pairs else (0, 0)
+        ctx.pairs_asof(d_s, d_r, n_pairs, lo, n, self.n_r, dev["terms"][-1], dev["best_val"], dev["best_row"], d_ks, d_kr, capacity,
+                       dev["s_marks"], dev["r_marks"])
+        if self.pairs:
+            rows.add(ctx, held, lo, n, d_ks, d_kr, ctx.asof_info()[1])
+            held.free(d_ks, d_kr)
+        held.free(*mine)
+        self.s_rows(ctx, held, lo, n)
+
+
+def _pair_steps(terms, best, rows, n_r, n_s, step):
+    """the steps behind the pairs that agree on the key: none (None), the condition step, or the as-of step behind it"""
+    if best is not None:
+        return _AsofStep(best, terms, rows, n_r, n_s, step)
+    return _WhereTerms(terms, rows, n_r, n_s, step) if terms is not None else None
 
 
 # ---- aggregating joins: COUNT / SUM / MIN / MAX of S values per R row -----------------------------------------------------

@@ -578,6 +578,66 @@ int hj_where_info(hj_ctx *ctx, uint64_t out[4]);
 int hj_pairs_where_host(const uint32_t *mapS, const uint32_t *mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
                         uint64_t rRows, const hj_where_term *terms, uint32_t nTerms, uint32_t *outS, uint32_t *outR,
                         uint64_t capacity, uint32_t *sMarks, uint32_t *rMarks, uint64_t info[4]);
+/* ---- as-of joins: one best match per S row ----
+ * ... ON S.k = R.k AND S.ts >= R.ts, and of the R rows that qualify the LATEST one: the price in force, the last quote
+ * before a trade (pandas.merge_asof, DuckDB's ASOF JOIN). R carries one timestamp per version, not an interval, so no
+ * condition on the pair alone expresses it: whether a pair survives depends on the other pairs of its S row. The as-of
+ * step is an arg-max per S row over the matched pairs and sits behind hj_pairs_where_dev as that sits behind the verify
+ * step: pairs in (an INNER probe's, the verify step's or the condition step's kept ones), per S row at most one pair out,
+ * and the rows of the pairs that come out marked in two caller-owned planes, from which hj_mark_rows_dev gives all eight
+ * kinds.
+ * The term  s[si] OP r[ri]  is an hj_where_term's with OP one of HJ_CMP_GE, HJ_CMP_GT, HJ_CMP_LE, HJ_CMP_LT. A pair is
+ * ELIGIBLE when the term holds with hj_pairs_where_dev's meaning: a NULL on either side does not hold, a NaN is unordered
+ * and does not hold, -0.0 == 0.0. Per S row exactly one eligible pair is KEPT (none when it has no eligible pair): for
+ * GE / GT the pair with the largest R value (backward: the latest at or before), for LE / LT the pair with the smallest
+ * (forward). Ties on the R value -- -0.0 and 0.0 are one -- go to the lowest R row: the library's index-priority rule.
+ * The result therefore depends neither on the order of the list nor on scheduling. */
+typedef struct {
+    const void     *s, *r;            /* sRows / rRows elements of `width` bytes, aligned to it            */
+    const uint32_t *sValid, *rValid;  /* NULL: no NULLs. Else the plane hj_gather_dev writes, 1 = valid    */
+    uint32_t width;                   /* UINT / INT: 1, 2, 4, 8.  FLOAT: 4, 8                              */
+    uint32_t type;                    /* hj_val_type, the same on both sides                               */
+    uint32_t op;                      /* HJ_CMP_GE, HJ_CMP_GT (backward), HJ_CMP_LE, HJ_CMP_LT (forward)    */
+    uint32_t reserved;                /* 0                                                                 */
+} hj_asof_term;                       /* 48 bytes */
+/* Pairs -> per S row the as-of pair. Pairs, output and marks are hj_pairs_where_dev's: for pair k in [0, nPairs):
+ * s = dMapS[k] - sRowBase, r = dMapR[k]; a pair whose raw entry is HJ_NO_ROW on either side, or with s >= sRows or
+ * r >= rRows, is never dereferenced: it is dropped and counted apart (hj_asof_info out[3]). Kept pairs go to dOutS / dOutR
+ * under the output contract of hj_probe_pairs_dev (dOutS[j] the original entry, base included; no holes; pairs at or beyond
+ * `capacity` counted and not written; order unspecified, multiset exact). Every kept pair, written or cut by the capacity,
+ * sets bit s of dSMarks and bit r of dRMarks where those are not NULL, bits only going 0 -> 1: the caller clears the
+ * planes. An R row is marked only when it wins some S row: an eligible pair that loses marks nothing. capacity 0 with NULL
+ * outputs is a mark-only pass. dOutS / dOutR must not alias the maps, each other, the mark planes or the best planes.
+ * dBestVal (sRows 64-bit words, 8-byte aligned) and dBestRow (sRows 32-bit words) are caller-owned planes that the call
+ * initialises itself, on the context's stream. dBestRow is an OUTPUT: after the call dBestRow[i] is the R row kept for S row
+ * sRowBase + i, or HJ_NO_ROW -- the left-outer as-of map in S order. dBestVal is workspace (it ends as the order key of the
+ * kept pair's R value, 0 without one).
+ * ALL PAIRS OF AN S ROW MUST BE IN ONE CALL: the planes are reset per call, and the best pair of half a list is not the
+ * best pair of the list. Each (s, r) occurs at most once in a join's pair list, so one pair per matched S row is kept; in
+ * a list that repeats the winning pair each copy is kept and counted.
+ * Three kernels behind the two initialisations, each reading the whole list (profiles/pairs_asof.md). `term` is host
+ * memory, read before the call returns. Asynchronous on the context's stream; needs no hj_reserve, no table and no state;
+ * touches no counter of hj_result and no other *_info.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): term NULL; a type above HJ_VAL_FLOAT; an op that is not
+ * GE, GT, LE or LT (EQ and NE order nothing); a width the type does not have; reserved != 0; with sRows > 0 an s pointer
+ * that is NULL or not aligned to its width, likewise r with rRows > 0; a validity pointer that is not 4-byte aligned;
+ * dBestVal NULL or not 8-byte aligned, dBestRow NULL or not 4-byte aligned; a map NULL with nPairs > 0; an output NULL with
+ * nPairs > 0 and capacity > 0; nPairs, sRows or rRows above 2^32 - 1. nPairs 0 is a call that kept nothing (the planes are
+ * initialised all the same). */
+int hj_pairs_asof_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMapR, uint64_t nPairs, uint32_t sRowBase,
+                      uint64_t sRows, uint64_t rRows, const hj_asof_term *term, uint64_t *dBestVal, uint32_t *dBestRow,
+                      uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
+/* Waits for the stream. About the last hj_pairs_asof_dev: out[0] = pairs kept, out[1] = pairs written (= min(out[0],
+ * capacity)), out[2] = the device time of the whole call -- initialisations and all three kernels -- in microseconds
+ * (rounded), out[3] = pairs dropped as HJ_NO_ROW or out of range. All 0 before the first call. */
+int hj_asof_info(hj_ctx *ctx, uint64_t out[4]);
+/* The same function on host pointers: no context, no device (the kernels and these loops compare and order with one
+ * body). bestVal / bestRow are initialised and left as the device call leaves them. The kept pairs are written in input
+ * order; `info` (may be NULL) is filled as hj_asof_info fills out, info[2] = 0. HJ_ERR_INVALID as hj_pairs_asof_dev; a
+ * refused call writes nothing. */
+int hj_pairs_asof_host(const uint32_t *mapS, const uint32_t *mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
+                       uint64_t rRows, const hj_asof_term *term, uint64_t *bestVal, uint32_t *bestRow, uint32_t *outS,
+                       uint32_t *outR, uint64_t capacity, uint32_t *sMarks, uint32_t *rMarks, uint64_t info[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
