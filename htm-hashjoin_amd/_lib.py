@@ -263,6 +263,7 @@ def _declare(lib):
         "hj_wave_seams": ([vp, vp, vp, vp, u64, P(u64)], i32),
         "hj_wave_planar_info": ([vp, P(u64)], i32),
         "hj_slot_codes_info": ([vp, u64, u32, P(u64)], i32),
+        "hj_ring_word_layout_info": ([u64, u32, u32, u32, u32, P(u64)], i32),
         "hj_table_debug": ([vp, P(u64)], i32),
         "hj_htm_chain_layout_info": ([vp, u32, u64, P(u64)], i32),
         "hj_htm_chain_info": ([vp, P(u64)], i32),

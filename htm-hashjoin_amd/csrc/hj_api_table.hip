@@ -63,7 +63,8 @@ static int build_common(hj_ctx* c, const void* d, bool key32, uint64_t n, uint32
     // the step costs. Below that everything stays as it was unless HJ_FLAG_SLOT_CODES forces the road (then a key without a
     // code hands over to the packed build like the planar build's own causes).
     const SlotCode code = slot_code(tableSize, job.probeLen);
-    const bool codesCan = !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS) && !key32 && hshift == 0 && code.dbits <= kCodeBits;
+    const bool codesCan = !(c->params.flags & HJ_FLAG_KEEP_ROW_IDS) && !key32 && hshift == 0 && code.dbits <= kCodeBits &&
+                          wave_codes_supported(n, job.nCU, tableSize);
     c->op.codesRoad = !codesCan ? 0u : code.fits_all() ? 1u : (c->params.flags & HJ_FLAG_SLOT_CODES) ? 2u : 0u;
     const int classicMode = (c->params.flags & HJ_FLAG_KEEP_ROW_IDS) ? kWaveClassic : c->op.codesRoad ? kWaveCodes : kWavePlanar;
     auto classic_tail = [&](Gate gate) -> hipError_t {
@@ -576,6 +577,23 @@ int hj_slot_codes_info(hj_ctx* c, uint64_t tableSize, uint32_t probeLength, uint
     out[4] = (variant == 3 && k.tableFormat == kFormatCodes1) ? 1 : 0;      // the table is in slot codes
     out[5] = (variant == 3 && c->op.codesRoad) ? k.planarFail : 0;          // why the road handed over (0: it did not, or was not taken)
     out[6] = c->op.codesRoad; out[7] = k.tableFormat;
+    return HJ_OK;
+}
+
+int hj_ring_word_layout_info(uint64_t tableSize, uint32_t probeLength, uint32_t rel, uint32_t key, uint32_t steps, uint64_t out[8])
+{
+    if (!out || !is_pow2(tableSize) || tableSize > (1ull << 32) || probeLength == 0) return HJ_ERR_INVALID;
+    const SlotCode code = slot_code(tableSize, probeLength);
+    out[5] = RingWord::kRelCap; out[6] = RingWord::kEmpty; out[0] = out[1] = out[2] = out[3] = out[4] = out[7] = 0;
+    // what the road never makes: no code at this probeLength, a key without a code, a tuple past the layout rule, a step
+    // past the budget
+    if (code.dbits > kCodeBits || code.overflows(key) || !RingWord::holds((uint64_t)rel + 1) || steps >= probeLength) return HJ_ERR_INVALID;
+    const RingWord rw = ring_word(code);
+    const uint32_t mask32 = (uint32_t)(tableSize - 1);
+    uint32_t word = rw.at_home(rel, key), pos = key & mask32;
+    for (uint32_t k = 0; k < steps; ++k) { word = RingWord::step(word); pos = (pos + 1) & mask32; }
+    out[0] = word; out[1] = rw.key(word, pos, mask32); out[2] = rw.tries_left(word, probeLength);
+    out[3] = RingWord::rel(word); out[4] = RingWord::code(word); out[7] = pos;
     return HJ_OK;
 }
 

@@ -54,6 +54,10 @@ constexpr uint32_t kWvRoundAt = 64;                 // a retry round runs once t
 // wavefronts per SIMD the registers must allow (16 per CU: what the rings' LDS allows; the compact build fits in 115
 // VGPRs once the chunk state is scalar)
 constexpr int kWvWpe = 4;
+// ... and on the slot-code road, whose ring of words leaves LDS for a fifth workgroup per CU (kWvWordLdsBytes below): 5, i.e. at
+// most 96 VGPRs. That fifth wavefront per SIMD is where the road's gain comes from (profiles/ring_words.md section 4), so it is asked
+// for here and not left to what the register allocator happens to need.
+constexpr int kWvWordWpe = 5;
 // kWvWavesPerCu resident wavefronts per CU, chunks = resident wavefronts x up to kWvMaxRounds rounds (hj_device.h; wave_layout below)
 constexpr uint32_t kWvMinChunk = 32768;             // tuples: a second round of workgroups only while chunks stay this long
 constexpr uint32_t kWvShortestChunk = 4 * kWvTileTuples;   // tuples: no chunk is cut shorter
@@ -61,6 +65,12 @@ constexpr uint32_t kWvShortestChunk = 4 * kWvTileTuples;   // tuples: no chunk i
 constexpr uint32_t kWvPrioShift = 10;
 static_assert(kWvQCap >= 128 && (kWvQCap & (kWvQCap - 1)) == 0, "FIFO ring: a power of two that takes one full step on top of < 64 waiting entries");
 constexpr size_t kWvLdsBytes = (size_t)kWvWaves * (kWvWin * sizeof(uint64_t) + 3 * kWvQCap * sizeof(uint32_t));
+// slot-code road: the ring holds 4-byte ring words (RingWord, hj_device.h) and a queue entry is (pos, word)
+// ring granules on that road: 1024 slots in 4 KiB. 16 granules were measured against 8 at 2^30 `uniform` (profiles/ring_words.md
+// section 2): the deferred tail shrinks from 203 to 41 us, the build kernel grows by 320, the step is slower
+constexpr uint32_t kWvWordGran = 8;
+constexpr size_t kWvWordLdsBytes = (size_t)kWvWaves * ((kWvWordGran << kGranShift) * sizeof(uint32_t) + 2 * kWvQCap * sizeof(uint32_t));
+static_assert((kWvWordGran & (kWvWordGran - 1)) == 0 && kWvWordLdsBytes <= kWvLdsBytes, "a ring of words costs no more LDS than the 8-byte ring");
 
 // The lane mask of a condition. HIP's __ballot(int) compares an INTEGER with zero: a condition that already is a lane mask
 // (every compare produces one) is first turned into 0 / 1 per lane and compared again -- two vector instructions per
@@ -252,20 +262,21 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
 // deferred walks and the log stay what they are. Any key has a code when the table is large enough (the host's rule);
 // otherwise (forced road) a tile holding a key at or above keyLimit raises Counters::planarFail bit 2. Key 0xFFFFFFFF is a
 // key like any other here: the empty pattern is a code no key produces.
-struct CodeRetire { uint32_t dmask, hiShift, hiMask, keyLimit; };
-inline CodeRetire code_retire(const SlotCode& sc)
-{
-    // code = ((key >> hiShift) & hiMask) | ((slot - key) & dmask): the high part lands on its place in one shift
-    const bool high = sc.tbits < 32;
-    return CodeRetire{sc.dmask(), high ? sc.tbits - sc.dbits : 0u, high ? ((sc.hiCap - 1u) << sc.dbits) : 0u, sc.key_limit()};
-}
+// On this road the RING holds 4-byte ring words, (offset in the chunk << 7 | code), not (index << 32 | key): the code is made
+// once, at insertion, a step to the next slot is word + 1, every atomic, look, compare and select is a 32-bit one, a queue
+// entry is (pos, word), and a ring of kWvWordGran granules costs half the LDS of as many 8-byte ones. Whether a tuple's budget
+// is spent is decided when its try FAILS, from the word before the step (RingWord::tries_left), so every word in the ring
+// or the queue has a try left. The key comes back out of (pos, word) where it is needed: the sum of the dropped keys
+// and a deferred entry, which is today's (pos, index << 32 | key). Everything around the ring is the one copy below.
+struct WordRing { RingWord rw; uint32_t keyLimit; };
+inline WordRing word_ring(const SlotCode& sc) { return WordRing{ring_word(sc), sc.key_limit()}; }
 template <bool KEY32, bool CHECK, bool HTM, bool COMPACT, bool PLANAR, bool CODES = false>
-__global__ void __launch_bounds__(kWvThreads, kWvWpe)
+__global__ void __launch_bounds__(kWvThreads, CODES ? kWvWordWpe : kWvWpe)
 k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_t nChunks, const uint32_t* __restrict__ starts,
              const uint32_t* __restrict__ bounds, uint64_t* __restrict__ table, uint64_t mask, uint32_t hshift,
              uint32_t probeLen, uint64_t idxBase, ShardCheck sc, DeferredEntry* __restrict__ queue,
              uint32_t* __restrict__ dcounts, Counters* __restrict__ ctr, Gate gate, uint64_t* __restrict__ htmConflicts,
-             uint32_t* __restrict__ ccounts, uint32_t residentWG, uint32_t* __restrict__ pcounts, CodeRetire cr)
+             uint32_t* __restrict__ ccounts, uint32_t residentWG, uint32_t* __restrict__ pcounts, WordRing cr)
 {
     static_assert(!(COMPACT && HTM), "the bucketised table keeps its own layout");
     static_assert(!(PLANAR && (COMPACT || HTM)), "the planar retire belongs to the classic open-addressing build");
@@ -283,10 +294,17 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // whatever is written from here on is never looked at (k_wave_decide reads the flag before anything else)
         if (*reinterpret_cast<volatile unsigned long long*>(&ctr->compactFail)) return;
     }
+    // ring geometry of this instantiation: RGRAN granules of RWIN slots, 8-byte slots or (CODES) 4-byte ring words
+    constexpr uint32_t RGRAN = CODES ? kWvWordGran : kWvGran, RWIN = RGRAN << kGranShift;
+    constexpr uint32_t QWORDS = CODES ? 2u : 3u;                         // words of a queue entry
     uint64_t* const win = lds + wave * kWvWin;                           // ring: slot s lives at win[s & (kWvWin - 1)]
-    uint32_t* const myQPos = reinterpret_cast<uint32_t*>(lds + kWvWaves * kWvWin) + wave * 3 * kWvQCap;
-    uint32_t* const myQLo = myQPos + kWvQCap;
-    uint32_t* const myQHi = myQLo + kWvQCap;
+    uint32_t* const win32 = reinterpret_cast<uint32_t*>(lds) + wave * RWIN;   // CODES: slot s lives at win32[s & (RWIN - 1)]
+    uint32_t* const myQPos = (CODES ? reinterpret_cast<uint32_t*>(lds) + kWvWaves * RWIN : reinterpret_cast<uint32_t*>(lds + kWvWaves * kWvWin))
+                             + wave * QWORDS * kWvQCap;
+    uint32_t* const myQLo = myQPos + kWvQCap;                            // CODES: the ring word
+    uint32_t* const myQHi = myQLo + kWvQCap;                             // CODES: no such word
+    const RingWord& rw = cr.rw;
+    (void)win; (void)win32; (void)myQHi; (void)rw;
 
     // workgroups per quarter of the first, resident round (residentWG = what this device holds at once, from the launch)
     const uint32_t prioDiv = ((gridDim.x <= residentWG ? gridDim.x : residentWG) + 3u) / 4u;
@@ -334,9 +352,14 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     bool ffSeen = false;                         // a key equal to the compact empty pattern
     (void)pCount; (void)ffSeen;
 
-    for (uint32_t i = lane; i < kWvWin / 2; i += 64) reinterpret_cast<ulonglong2*>(win)[i] = make_ulonglong2(kEmpty, kEmpty);
+    if constexpr (CODES) {
+        for (uint32_t i = lane; i < RWIN / 4; i += 64)
+            reinterpret_cast<uint4*>(win32)[i] = make_uint4(RingWord::kEmpty, RingWord::kEmpty, RingWord::kEmpty, RingWord::kEmpty);
+    } else {
+        for (uint32_t i = lane; i < kWvWin / 2; i += 64) reinterpret_cast<ulonglong2*>(win)[i] = make_ulonglong2(kEmpty, kEmpty);
+    }
 
-    uint32_t winLoG = shadowOn ? loG - 1 : loG;  // ring = granules [winLoG, winLoG + kWvGran), wave-uniform
+    uint32_t winLoG = shadowOn ? loG - 1 : loG;  // ring = granules [winLoG, winLoG + RGRAN), wave-uniform
     uint32_t qCount = 0, qHead = 0;              // retry queue (FIFO ring): entries and position of the oldest, wave-uniform
     uint32_t rounds = 0;                         // retry rounds so far (wave-uniform)
     unsigned long long dropSum = 0, inSum = 0;
@@ -356,6 +379,22 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     auto advance = [&](uint32_t target) {
         typedef unsigned int u2 __attribute__((ext_vector_type(2)));
         while (winLoG < target) {
+            if constexpr (CODES) {
+                // 128 code bytes and the 512-byte index run, out of this lane's two ring words: the code is the word's low
+                // bits as they stand, the index is the chunk's first plus the word's rel
+                uint2* const src = reinterpret_cast<uint2*>(win32 + ((winLoG & (RGRAN - 1)) << kGranShift)) + lane;
+                const uint2 t = *src;
+                const bool e0 = t.x == RingWord::kEmpty, e1 = t.y == RingWord::kEmpty;
+                const uint32_t c0 = e0 ? kCodeEmpty : RingWord::code(t.x), c1 = e1 ? kCodeEmpty : RingWord::code(t.y);
+                u2 ii;
+                ii.x = e0 ? kNone : idx0 + RingWord::rel(t.x); ii.y = e1 ? kNone : idx0 + RingWord::rel(t.y);
+                uint8_t* const codes = reinterpret_cast<uint8_t*>(table) + ((uint64_t)winLoG << kGranShift);
+                __builtin_nontemporal_store((unsigned short)(c0 | (c1 << 8)), reinterpret_cast<unsigned short*>(codes) + lane);
+                __builtin_nontemporal_store(ii, reinterpret_cast<u2*>(planar_index_plane(table, mask + 1) + ((uint64_t)winLoG << kGranShift)) + lane);
+                *src = make_uint2(RingWord::kEmpty, RingWord::kEmpty);
+                ++winLoG;
+                continue;
+            }
             ulonglong2* src = ring_granule(winLoG);
             const ulonglong2 t = *src;
             if constexpr (COMPACT) {
@@ -365,20 +404,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                     u2 vv; vv.x = (uint32_t)t.x; vv.y = (uint32_t)t.y;
                     __builtin_nontemporal_store(vv, reinterpret_cast<u2*>(reinterpret_cast<uint32_t*>(table) + ((uint64_t)winLoG << kGranShift)) + lane);
                 }
-            } else if constexpr (CODES) {
-                // 128 code bytes and the 512-byte index run. This lane's slots are 2 * lane and 2 * lane + 1 of the granule;
-                // the granule's first slot is a multiple of 128, so below the displacement's width it adds nothing that
-                // the lane's own offset does not
-                u2 ii;
-                ii.x = (uint32_t)(t.x >> 32); ii.y = (uint32_t)(t.y >> 32);
-                const uint32_t k0 = (uint32_t)t.x, k1 = (uint32_t)t.y;
-                const uint32_t s0 = (winLoG << kGranShift) + 2u * lane;
-                uint32_t c0 = ((k0 >> cr.hiShift) & cr.hiMask) | ((s0 - k0) & cr.dmask);
-                uint32_t c1 = ((k1 >> cr.hiShift) & cr.hiMask) | ((s0 + 1u - k1) & cr.dmask);
-                c0 = ii.x == kNone ? kCodeEmpty : c0; c1 = ii.y == kNone ? kCodeEmpty : c1;
-                uint8_t* const codes = reinterpret_cast<uint8_t*>(table) + ((uint64_t)winLoG << kGranShift);
-                __builtin_nontemporal_store((unsigned short)(c0 | (c1 << 8)), reinterpret_cast<unsigned short*>(codes) + lane);
-                __builtin_nontemporal_store(ii, reinterpret_cast<u2*>(planar_index_plane(table, mask + 1) + ((uint64_t)winLoG << kGranShift)) + lane);
             } else if constexpr (PLANAR) {
                 // two 512-byte runs: the key words, the index words (the empty pattern's two words are the planes' empty patterns)
                 u2 kk, ii;
@@ -400,13 +425,57 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     // may this wavefront touch slot pos right now: inside the ring and inside the owned range
     auto in_ring = [&](uint32_t pos) -> bool {
         const uint32_t g = pos >> kGranShift;
-        return (g - winLoG < kWvGran) & (g < limG);
+        return (g - winLoG < RGRAN) & (g < limG);
+    };
+    // a tuple leaves for this wavefront's OWN slice of the deferred queue, [cb, cb + clen): a tuple leaves at most once, so
+    // the slice cannot overflow, and no atomic is needed to place it (a returning global atomic per round with a
+    // straggler stalled the wavefront for microseconds). dm = the lanes that defer, not empty.
+    auto defer = [&](unsigned long long dm, bool toDefer, uint32_t pos, uint64_t packed) {
+        if (toDefer) {
+            DeferredEntry* q = myDeferred + dCount + lane_rank(dm);
+            q->pos = pos; q->packed = packed;
+            const uint32_t db = pos >> 9;
+            usedLo = db < usedLo ? db : usedLo; usedHi1 = db + 1 > usedHi1 ? db + 1 : usedHi1;
+        }
+        dCount += (uint32_t)__popcll(dm);
+    };
+    // CODES: the round on the entry (pos, word) a lane holds; the same terminal events. The entry has a try left at pos.
+    auto round_words = [&](uint32_t& pos, uint32_t& word, const bool has) -> bool {
+        const bool ownOk = in_ring(pos);
+        const bool toDefer = has & !ownOk, work = has & ownOk;
+        // look before leaping (below): four consecutive ring words, compared whole -- their order is that of their rel
+        const bool inGran = (pos & (kGranSlots - 1)) <= kGranSlots - 4;
+        const uint32_t rd = (work & inGran) ? pos : (winLoG << kGranShift);
+        const uint32_t* w = win32 + (rd & (RWIN - 1));
+        const bool c0 = w[0] < word, c1 = c0 & (w[1] < word), c2 = c1 & (w[2] < word), c3 = c2 & (w[3] < word);
+        uint32_t skip = (uint32_t)c0 + (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
+        skip = (work & inGran) ? skip : 0u;
+        const bool drop1 = work & (skip >= rw.tries_left(word, probeLen));   // every slot it had left holds an earlier tuple
+        const uint32_t fwd = drop1 ? 0u : skip;                               // a dropped tuple's (pos, word) stay as they are
+        pos = (pos + fwd) & mask32; word = RingWord::step(word, fwd);
+        const bool recheck = work & !drop1 & (skip == 4);                     // may have left the granule: next round
+        const bool doAtomic = work & !drop1 & !recheck;
+        uint32_t old = RingWord::kEmpty;
+        if (doAtomic) old = atomicMin(&win32[pos & (RWIN - 1)], word);
+        const bool fail = doAtomic & (old != RingWord::kEmpty) & (old != word);
+        word = (fail & (old > word)) ? old : word;                            // displaced a later tuple: carry it on
+        const bool spent = fail & (rw.tries_left(word, probeLen) <= 1u);      // that was the carried tuple's last slot
+        const bool dropped = drop1 | spent;
+        if (wv_ballot(dropped)) {
+            drops += dropped ? 1u : 0u; dropSum += dropped ? (unsigned long long)rw.key(word, pos, mask32) : 0ull;
+        }
+        const unsigned long long dm = wv_ballot(toDefer);
+        if (dm) defer(dm, toDefer, pos, pack64(idx0 + RingWord::rel(word), rw.key(word, pos, mask32)));
+        const bool on = fail & !spent;
+        pos = on ? ((pos + 1) & mask32) : pos; word = on ? RingWord::step(word) : word;
+        return recheck | on;
     };
 
     // One round on the entry (pos, mlo, mhi) a lane holds (hj_build_own.hip's round, with range + ring standing in
     // for block ownership): terminal events are placed / dropped (budget exhausted, NoCCHashBuild.hpp:57-58) /
     // deferred; returns "not finished" with the entry's next state in place.
     auto round_body = [&](uint32_t& pos, uint32_t& mlo, uint32_t& mhi, const bool has) -> bool {
+        if constexpr (CODES) return round_words(pos, mlo, has);
         const uint32_t key = mlo;
         const uint32_t homeOfKey = home32<HTM>(key, hshift, mask32);
         uint32_t budget = probeLen - ((pos - homeOfKey) & mask32);
@@ -467,9 +536,6 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 cCount += (uint32_t)__popcll(cm);
             }
         }
-        // deferred tuples go to this wavefront's OWN slice of the deferred queue, [cb, cb + clen): a tuple leaves at
-        // most once, so the slice cannot overflow, and no atomic is needed to place it (a returning global atomic
-        // per round with a straggler stalled the wavefront for microseconds)
         const unsigned long long dm = wv_ballot(toDefer);
         if (dm) {
             if constexpr (COMPACT) {
@@ -483,13 +549,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                     dCount += (uint32_t)__popcll(cmk);
                 }
             } else {
-            if (toDefer) {
-                DeferredEntry* q = myDeferred + dCount + lane_rank(dm);
-                q->pos = pos; q->packed = mine;
-                const uint32_t db = pos >> 9;
-                usedLo = db < usedLo ? db : usedLo; usedHi1 = db + 1 > usedHi1 ? db + 1 : usedHi1;
-            }
-            dCount += (uint32_t)__popcll(dm);
+                defer(dm, toDefer, pos, mine);
             }
         }
         pos = fail ? ((pos + 1) & mask32) : pos;
@@ -504,7 +564,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         const bool has = lane < take;
         // lanes >= take read stale-but-in-bounds entries and ignore them
         const uint32_t at0 = (qHead + lane) & (kWvQCap - 1);
-        uint32_t pos = myQPos[at0], mlo = myQLo[at0], mhi = myQHi[at0];
+        uint32_t pos = myQPos[at0], mlo = myQLo[at0], mhi = CODES ? 0u : myQHi[at0];
         qHead = (qHead + take) & (kWvQCap - 1);
         qCount -= take;
         const bool again = round_body(pos, mlo, mhi, has);
@@ -517,7 +577,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         qHead = (qHead - back) & (kWvQCap - 1);
         if (again) {
             const uint32_t at = (qHead + lane_rank(am)) & (kWvQCap - 1);
-            myQPos[at] = pos; myQLo[at] = mlo; myQHi[at] = mhi;
+            myQPos[at] = pos; myQLo[at] = mlo; if constexpr (!CODES) myQHi[at] = mhi;
         }
         qCount += back;
         ++rounds;
@@ -528,7 +588,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         while (qCount > 64u) retry_round();
         bool act = lane < qCount;
         const uint32_t at0 = (qHead + lane) & (kWvQCap - 1);
-        uint32_t pos = myQPos[at0], mlo = myQLo[at0], mhi = myQHi[at0];
+        uint32_t pos = myQPos[at0], mlo = myQLo[at0], mhi = CODES ? 0u : myQHi[at0];
         qCount = 0;
         while (wv_ballot(act)) act = round_body(pos, mlo, mhi, act);
     };
@@ -687,7 +747,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             // keeps as much history as it can: retry entries carried over from the previous tile are still inside.
             // It never moves past the tile's lowest home slot (an outlier key is deferred, not the tile).
             const uint32_t top = (uint32_t)(((uint64_t)tmax + probeLen + 8u) >> kGranShift) + 1u;
-            uint32_t target = top > kWvGran ? top - kWvGran : 0u;
+            uint32_t target = top > RGRAN ? top - RGRAN : 0u;
             const uint32_t gmin = tmin >> kGranShift;
             target = target < gmin ? target : gmin;
             target = target < limG ? target : limG;
@@ -711,11 +771,11 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 }
             }
             const uint32_t gmax = tmax >> kGranShift;
-            allIn = full & (gmin - winLoG < kWvGran) & (gmax - winLoG < kWvGran) & (gmax < limG);
+            allIn = full & (gmin - winLoG < RGRAN) & (gmax - winLoG < RGRAN) & (gmax < limG);
         }
 
         // ---- the PER home-slot attempts of the tile, issued together (independent LDS round trips) ----
-        unsigned long long oldv[kWvPer];
+        std::conditional_t<CODES, uint32_t, unsigned long long> oldv[kWvPer];
         // (when the tile's lowest and highest home slot are inside ring and range -- nearly every full tile -- the
         // per-tuple test is skipped: the retry rounds leave the VALU little to spare, hj DESIGN 4.2)
         auto attempts = [&](auto allTag) {
@@ -723,10 +783,15 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
 #pragma unroll
             for (int j = 0; j < kWvPer; ++j) {
                 own[j] = live[j] & (ALL || in_ring(home[j]));
+                if constexpr (CODES) {
+                    oldv[j] = RingWord::kEmpty;
+                    if (own[j]) oldv[j] = atomicMin(&win32[home[j] & (RWIN - 1)], rw.at_home(tb + lane + 64 * j, klo[j]));
+                } else {
                 oldv[j] = kEmpty;
                 if (own[j])
                     oldv[j] = atomicMin(reinterpret_cast<unsigned long long*>(&win[home[j] & (kWvWin - 1)]),
                                         (unsigned long long)pack64(idx0 + tb + lane + 64 * j, klo[j]));
+                }
             }
         };
         if (allIn) attempts(std::true_type{}); else attempts(std::false_type{});
@@ -735,18 +800,34 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         for (int j = 0; j < kWvPer; ++j) {
             while (qCount >= kWvRoundAt) retry_round();                // dense rounds; leaves room for one full step
             const bool lv = live[j], ow = own[j];
-            uint32_t mlo = klo[j], mhi = idx0 + tb + lane + 64 * j;
+            uint32_t pos, mlo, mhi;
+            bool again;
+            if constexpr (CODES) {
+                mlo = rw.at_home(tb + lane + 64 * j, klo[j]); mhi = 0u;
+                const bool fail = ow & (oldv[j] != RingWord::kEmpty);  // the slot was taken
+                mlo = (fail & (oldv[j] > mlo)) ? oldv[j] : mlo;        // ... by a later tuple: it moves on instead
+                // the home slot was the carried tuple's last try (the displaced one's, or probeLength 1): dropped here
+                const bool spent = fail & (rw.tries_left(mlo, probeLen) <= 1u);
+                if (wv_ballot(spent)) {
+                    drops += spent ? 1u : 0u; dropSum += spent ? (unsigned long long)rw.key(mlo, home[j], mask32) : 0ull;
+                }
+                const bool on = fail & !spent;
+                pos = on ? ((home[j] + 1) & mask32) : home[j]; mlo = on ? RingWord::step(mlo) : mlo;
+                again = on | (lv & !ow);
+            } else {
+            mlo = klo[j]; mhi = idx0 + tb + lane + 64 * j;
             const uint32_t oldIdx = (uint32_t)(oldv[j] >> 32);
             const bool fail = ow & (oldIdx != 0xFFFFFFFFu);            // the slot was taken
             const bool disp = fail & (oldIdx > mhi);                   // ... by a later tuple: it moves on instead
             mlo = disp ? (uint32_t)oldv[j] : mlo; mhi = disp ? (uint32_t)(oldv[j] >> 32) : mhi;
-            const uint32_t pos = fail ? ((home[j] + 1) & mask32) : home[j];
-            const bool again = fail | (lv & !ow);                      // outside ring or range: the retry round defers it
+            pos = fail ? ((home[j] + 1) & mask32) : home[j];
+            again = fail | (lv & !ow);                                 // outside ring or range: the retry round defers it
+            }
             const unsigned long long am = wv_ballot(again);
             if (am) {
                 if (again) {
                     const uint32_t at = (qHead + qCount + lane_rank(am)) & (kWvQCap - 1);
-                    myQPos[at] = pos; myQLo[at] = mlo; myQHi[at] = mhi;
+                    myQPos[at] = pos; myQLo[at] = mlo; if constexpr (!CODES) myQHi[at] = mhi;
                 }
                 qCount += (uint32_t)__popcll(am);
             }
@@ -806,7 +887,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
 
     // ---- the rest of the range: what is left in the ring, then empties up to the next chunk's range ----
     uint32_t endG = limG;
-    if (lastChunk) endG = winLoG + kWvGran < numGran ? winLoG + kWvGran : numGran;
+    if (lastChunk) endG = winLoG + RGRAN < numGran ? winLoG + RGRAN : numGran;
     advance(endG);
     if (lane == 0) {
         if (c == 0) ctr->ownLo = (unsigned long long)loG << kGranShift;
@@ -1137,6 +1218,12 @@ void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s) { hipLaunchKer
 // ---- host side ----------------------------------------------------------------------------------------------------
 size_t wave_lds_bytes() { return kWvLdsBytes; }
 bool wave_supported(uint64_t tableSize) { return tableSize >= (uint64_t)kWvWin; }
+bool wave_codes_supported(uint64_t n, int nCU, uint64_t tableSize)
+{
+    // the table is no smaller than a ring, and every position a wavefront reads has a ring word (RingWord::holds: a slice
+    // is longer than anything a wavefront reads). Otherwise the caller retires 4-byte keys out of the 8-byte ring.
+    return tableSize >= ((uint64_t)kWvWordGran << kGranShift) && RingWord::holds(wave_layout(n, nCU).sliceLen);
+}
 constexpr uint32_t kWvCompactMaxProbe = 32;         // the largest probeLength the compact build takes
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen)
 {
@@ -1190,6 +1277,7 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
     const bool compact = mode == kWaveCompact, planar = mode == kWavePlanar || codes;
     const SlotCode code = slot_code(j.tableSize, j.probeLen);
     if (codes && (j.key32 || j.hshift || code.dbits > kCodeBits)) return hipErrorInvalidValue;   // tuples under the identity hash
+    if (codes && !wave_codes_supported(j.n, j.nCU, j.tableSize)) return hipErrorInvalidValue;    // the ring of words and its rule
     // (planar + bucketised is refused here: the dirty-log counts live in the conflict counts' words, WaveScratch::lcounts)
     if (htm && (j.key32 || j.probeLen != 3 || j.sc.mask || compact || planar)) return hipErrorInvalidValue;
     if (!j.key32 && j.hshift) return hipErrorInvalidValue;         // the kernel's tuple instances assume it
@@ -1221,9 +1309,9 @@ hipError_t launch_build_wave(const BuildJob& j, const WaveBufs& buf, Gate gate, 
         auto build = [&](auto k32, auto chk, auto htmTag, auto cmp, auto pln, auto cds) {
             hipLaunchKernelGGL((k_build_wave<decltype(k32)::value, decltype(chk)::value, decltype(htmTag)::value, decltype(cmp)::value, decltype(pln)::value,
                                              decltype(cds)::value>),
-                               gMain, dim3(kWvThreads), kWvLdsBytes, j.s, j.R, j.n, sliceLen, nChunks, ws.starts, ws.bounds, j.table, mask,
+                               gMain, dim3(kWvThreads), decltype(cds)::value ? kWvWordLdsBytes : kWvLdsBytes, j.s, j.R, j.n, sliceLen, nChunks, ws.starts, ws.bounds, j.table, mask,
                                j.hshift, j.probeLen, j.idxBase, j.sc, queue, ws.dcounts, j.ctr, gate, buf.htmConflicts, ws.ccounts,
-                               residentWG, ws.pcounts, codes ? code_retire(code) : CodeRetire{});
+                               residentWG, ws.pcounts, codes ? word_ring(code) : WordRing{});
         };
         // every instantiation there is: the bucketised table on tuples without a shard check; else key format x "counts
         // foreign tuples" for each of the three modes; the slot codes on tuples alone, with and without the count

@@ -268,6 +268,37 @@ __host__ __device__ inline SlotCode slot_code(uint64_t tableSize, uint32_t probe
     c.hiCap = c.dbits <= kCodeBits ? 1u << (kCodeBits - c.dbits) : 0u;
     return c;
 }
+// Ring words (DESIGN.md 4.2a-bis "Build"): what a slot of a wavefront's LDS ring holds on the slot-code road. Inside a ring
+// only the ORDER of the tuples matters, and a wavefront's tuples are numbered by their offset from the first position it
+// reads; the key is what the slot number and the code say. So word = (rel << 7) | code -- 4 bytes, and the key never sits
+// in LDS. rel is unique per tuple of a ring and monotone in the tuple index: order and equality of two words are those of
+// their rel, and the empty pattern (all ones) is above every word the layout rule lets in. THE place where a ring word is
+// made, stepped and read: the build kernel and hj_ring_word_layout_info call it.
+struct RingWord {
+    static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+    static constexpr uint32_t kRelCap = (1u << (32 - kCodeBits)) - 1u;   // rel < kRelCap: no word equals the empty pattern
+    SlotCode sc;
+    uint32_t hiShift, hiMask;     // the key's high part lands on its place in the code in one shift and one mask
+    // the layout rule: a wavefront reads fewer than `positions` positions (a slice's length bounds them)
+    __host__ __device__ static bool holds(uint64_t positions) { return positions <= kRelCap; }
+    // the word a tuple tries its home slot with (d = 0). A key without a code (forced road, cause 4) keeps its rel whole:
+    // the table is thrown away, the ring stays in order
+    __host__ __device__ uint32_t at_home(uint32_t rel, uint32_t key) const { return (rel << kCodeBits) | ((key >> hiShift) & hiMask); }
+    __host__ __device__ static uint32_t rel(uint32_t word) { return word >> kCodeBits; }
+    __host__ __device__ static uint32_t code(uint32_t word) { return word & ((1u << kCodeBits) - 1u); }
+    // tries the tuple has left, the slot it stands at included: at least 1 for every word in a ring or a queue
+    __host__ __device__ uint32_t tries_left(uint32_t word, uint32_t probeLen) const { return probeLen - (word & sc.dmask()); }
+    // k slots on, k < tries_left: the displacement stays below probeLength and never carries into the high part. Whether
+    // the budget is spent is decided from tries_left BEFORE the step, and a dropped tuple's key is read before it too.
+    __host__ __device__ static uint32_t step(uint32_t word, uint32_t k = 1u) { return word + k; }
+    // the key of the tuple that stands at slot pos with this word (SlotCode::decode: the wrap at the table's end included)
+    __host__ __device__ uint32_t key(uint32_t word, uint32_t pos, uint32_t mask32) const { return sc.decode(code(word), pos, mask32); }
+};
+__host__ __device__ inline RingWord ring_word(const SlotCode& sc)
+{
+    const bool high = sc.tbits < 32 && sc.dbits <= kCodeBits;
+    return RingWord{sc, high ? sc.tbits - sc.dbits : 0u, high ? ((sc.hiCap - 1u) << sc.dbits) : 0u};
+}
 // Planar retire: where the index plane starts in the table buffer of (tableSize + kTableSlack) 8-byte words -- behind the
 // key plane and ITS slack (the probe reads up to probeLength - 1 keys past the table's end and must find them empty), at
 // the next multiple of 128 bytes so that the granules' 512-byte runs stay on whole lines in both planes. One uint32 input
@@ -442,6 +473,8 @@ constexpr int kWaveClassic = 0, kWaveCompact = 1, kWavePlanar = 2, kWaveCodes = 
 struct WaveBufs { void* bounds; void* queue; uint64_t* htmConflicts = nullptr; bool htmRoute = false; };
 hipError_t launch_build_wave(const BuildJob& job, const WaveBufs& buf, Gate gate, int parts, int mode = kWaveClassic, KernelEvents kev = {});
 bool wave_compact_supported(uint64_t tableSize, uint32_t probeLen);
+// mode kWaveCodes takes this build: its ring of 4-byte words (RingWord) fits the table and holds the layout's chunks
+bool wave_codes_supported(uint64_t n, int nCU, uint64_t tableSize);
 void launch_set_variant(Counters* ctr, uint32_t v, hipStream_t s);
 // htmConflicts != nullptr: the bucketised table of --algo htm (home_slot_htm, probeLen must be 3, tuples only); every
 // tuple that runs out of budget is appended as (index << 32 | key) to its chunk's slice of htmConflicts (slices and

@@ -140,6 +140,24 @@ def slot_codes_info(table_size, probe_length=4):
     return _slot_codes(None, int(table_size), int(probe_length))
 
 
+_RING_WORD_FIELDS = ("word", "key", "triesLeft", "rel", "code", "relCap", "empty", "slot")
+
+
+def ring_word_info(table_size, probe_length, rel, key, steps=0):
+    """hj_ring_word_layout_info (host-only arithmetic): the 4-byte ring word of the tuple with offset rel and that key after
+    `steps` steps from its home slot, and what reads back out of it, as a dict (word, key, triesLeft, rel, code, relCap,
+    empty, slot). HashJoinError(HJ_ERR_INVALID) for what the slot-code road never makes; its relCap and empty are then in
+    the error's .partial dict when the table size and probe length were good."""
+    out = (C.c_uint64 * 8)()
+    rc = lib.hj_ring_word_layout_info(int(table_size), int(probe_length), int(rel), int(key), int(steps), out)
+    d = {k: int(out[i]) for i, k in enumerate(_RING_WORD_FIELDS)}
+    if rc != _lib.HJ_OK:
+        err = HashJoinError(rc, f"hj_ring_word_layout_info(tableSize={table_size}, probeLength={probe_length}, rel={rel}, key={key}, steps={steps})")
+        err.partial = d
+        raise err
+    return d
+
+
 def _params(algo, scaleOutput=2, numPartitions=64, probeLength=4, transactionSize=16, radixBits=0,
             buildVariant=0, prjMode=0, keepRowIds=False, trackRMatches=False, slotCodes=False):
     p = hj_params()

@@ -901,6 +901,16 @@ int hj_wave_planar_info(hj_ctx *ctx, uint64_t out[4]);
  * out[4..7] = 0. HJ_ERR_INVALID: out NULL, tableSize no power of two or above 2^32, probeLength 0. HJ_ERR_STATE: tableSize 0
  * without an open-addressing table. */
 int hj_slot_codes_info(hj_ctx *ctx, uint64_t tableSize, uint32_t probeLength, uint64_t out[8]);
+/* Ring words (host-only arithmetic; for tests): what a slot of a wavefront's LDS ring holds while a build on the slot-code
+ * road runs, word = (rel << 7) | code, rel = the tuple's offset from the first position its wavefront reads; all ones =
+ * empty. For the tuple with that rel and key in a table of tableSize slots at probeLength, after `steps` steps from its home
+ * slot: out[0] = the word, out[1] = the key read back out of (slot, word), out[2] = tries the tuple has left, this slot
+ * included (probeLength - steps), out[3] = rel and out[4] = code read back out of the word (the code is the one the slot
+ * ends with: hj_slot_codes_info), out[5] = the layout rule's bound (a rel must be below it), out[6] = the empty pattern,
+ * out[7] = the slot. HJ_ERR_INVALID: what the road never makes -- out NULL, a bad table size or probeLength (as
+ * hj_slot_codes_info), no code at this probeLength, a key without a code, rel at or above the bound, steps >= probeLength
+ * (out[5] and out[6] are set whenever out, tableSize and probeLength are good). */
+int hj_ring_word_layout_info(uint64_t tableSize, uint32_t probeLength, uint32_t rel, uint32_t key, uint32_t steps, uint64_t out[8]);
 /* The table of the last hj_build_dev / hj_build_keys_dev as its readers see it (waits for the stream; for tests). An LDS
  * build (buildVariant 2, 3, 4, also under HJ_ALGO_HTM) writes only the slots some tuple can reach: out[0], out[1] = the
  * valid slot range [validLo, validHiEx) -- a home slot outside it matches nothing, the slots [validLo, validHiEx + 512)
