@@ -17,5 +17,6 @@ from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
     outer_join_pairs, radix_outer_join_pairs, join_tables, join_on, key_hash_host,
     KeyColumn, join_on_columns, key_hash2_host, pairs_where_host, pairs_asof_host, radix_join_aggregate, aggregate_on, prj_agg_layout_info,
+    key_groups, key_groups_host, distinct_on, group_by_columns,
     generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, ring_word_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )

@@ -222,6 +222,9 @@ def _declare(lib):
         "hj_key_hash2_dev": ([vp, P(hj_key_col2), u32, u32, u64, u32, vp], i32),
         "hj_key_hash2_host": ([P(hj_key_col2), u32, u32, u64, u32, vp], i32),
         "hj_pairs_verify2_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_key_col2), u32, vp, vp, u64, vp, vp], i32),
+        "hj_key_groups_dev": ([vp, P(hj_key_col2), u32, u32, u64, u32, vp, vp, vp, u64], i32),
+        "hj_key_groups_info": ([vp, P(u64)], i32),
+        "hj_key_groups_host": ([P(hj_key_col2), u32, u32, u64, u32, vp, vp, vp, u64, P(u64)], i32),
         "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
         "hj_where_info": ([vp, P(u64)], i32),
         "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),

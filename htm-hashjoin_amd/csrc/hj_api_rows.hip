@@ -1,6 +1,7 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), the join conditions beyond equality, the as-of step, and the
-// *_info entry point of every call that has a record (hj_host.h: CallRecord). Host-side glue only.
+// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns, the
+// join conditions beyond equality, the as-of step, and the *_info entry point of every call that has a record (hj_host.h:
+// CallRecord). Host-side glue only.
 #include "hj_host.h"
 
 using namespace hjapi;
@@ -245,6 +246,18 @@ extern "C++" {      // templates: one body per descriptor
 static hj_key_col2 key_col2_of(const hj_key_col& col) { return hj_key_col2{col.s, col.r, nullptr, nullptr, nullptr, nullptr, col.width, 0u}; }
 static hj_key_col2 key_col2_of(const hj_key_col2& col) { return col; }
 
+// the `side` pointers of checked columns as the kernels take them
+template <class Col>
+static void key_side_cols(const Col* cols, uint32_t nCols, uint32_t side, KeyCols2* k)
+{
+    const bool S = side == HJ_KEY_SIDE_S;
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_key_col2 col = key_col2_of(cols[i]);
+        k->p[i] = S ? col.s : col.r; k->off[i] = S ? col.sOffsets : col.rOffsets;
+        k->valid[i] = S ? col.sValid : col.rValid; k->width[i] = col.width; k->flags[i] = col.flags;
+    }
+}
+
 // The arguments of a key hash entry point, on the device or on the host -> the kernel's columns; the message of what is
 // wrong, or nullptr
 template <class Col>
@@ -254,12 +267,7 @@ static const char* key_hash_args(const Col* cols, uint32_t nCols, uint32_t side,
     if (nRows > 0xFFFFFFFFull) return "nRows above 2^32 - 1";
     if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
     if (nRows && !out) return "output pointer NULL with nRows > 0";
-    const bool S = side == HJ_KEY_SIDE_S;
-    for (uint32_t i = 0; i < nCols; ++i) {
-        const hj_key_col2 col = key_col2_of(cols[i]);
-        k->p[i] = S ? col.s : col.r; k->off[i] = S ? col.sOffsets : col.rOffsets;
-        k->valid[i] = S ? col.sValid : col.rValid; k->width[i] = col.width; k->flags[i] = col.flags;
-    }
+    key_side_cols(cols, nCols, side, k);
     return nullptr;
 }
 
@@ -357,6 +365,62 @@ int hj_verify_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
     return call_info(c, c->call[CALL_VERIFY], c->buf[B_VERIFY_CTR].p, 16, out);     // pairs kept, candidates dropped
+}
+
+// ---- rows of one table grouped by their key columns (hj_groups.hip) ----------
+// hj_key_groups_dev's and hj_key_groups_host's arguments -> the kernels' columns; the message of what is wrong, or nullptr
+static const char* key_groups_args(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, const uint32_t* rep,
+                                   const uint32_t* group, const uint32_t* firstRows, uint64_t capacity, KeyCols2* k)
+{
+    if (side > HJ_KEY_SIDE_R) return "side must be HJ_KEY_SIDE_S or HJ_KEY_SIDE_R";
+    if (nRows > 0xFFFFFFFEull) return "nRows above 2^32 - 2";
+    if (const char* what = key_cols_error(cols, nCols, nRows && side == HJ_KEY_SIDE_S, nRows && side == HJ_KEY_SIDE_R)) return what;
+    if (nRows && !rep) return "dRep NULL with nRows > 0";
+    if (nRows && capacity && !firstRows) return "dFirstRows NULL with capacity > 0";
+    if (!word_ptr_ok(rep) || !word_ptr_ok(group) || !word_ptr_ok(firstRows)) return "an output pointer that is not 4-byte aligned";
+    key_side_cols(cols, nCols, side, k);
+    return nullptr;
+}
+
+int hj_key_groups_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint32_t* dRep,
+                      uint32_t* dGroup, uint32_t* dFirstRows, uint64_t capacity)
+{
+    HJ_ENTER(c, true);
+    KeyCols2 k{};
+    if (const char* what = key_groups_args(cols, nCols, side, nRows, dRep, dGroup, dFirstRows, capacity, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_key_groups_dev", what);
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (const int rc = c->buf[B_GROUPS_CTR].reserve(c, 4 * sizeof(unsigned long long))) return rc;
+    if (nRows)
+        if (const int rc = c->buf[B_GROUPS_WORK].reserve(c, key_groups_work_bytes(nRows))) return rc;
+    HJ_HIP(c, hipEventRecord(c->call[CALL_GROUPS].ev[0], c->stream));          // the whole call: the table's fill too
+    HJ_HIP(c, launch_key_groups(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dRep, dGroup, dFirstRows, capacity, c->buf[B_GROUPS_WORK].p,
+                                c->buf[B_GROUPS_CTR].as<unsigned long long>(), c->stream));
+    return call_end(c, CALL_GROUPS, capacity, nRows);
+}
+
+int hj_key_groups_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_GROUPS];
+    for (int i = 4; i < 8; ++i) out[i] = 0;
+    // the word behind the sweep's block counts: the first rows it found (no row: no work was enqueued and there is no word)
+    const uint32_t* const total = r.called && r.rows ? key_groups_total(c->buf[B_GROUPS_WORK].p, r.rows) : nullptr;
+    if (const int rc = call_info(c, r, total, sizeof(uint32_t), out)) return rc;
+    if (!r.called || !r.rows) return HJ_OK;
+    unsigned long long ctr[4];
+    HJ_HIP(c, hipMemcpy(ctr, c->buf[B_GROUPS_CTR].p, sizeof(ctr), hipMemcpyDeviceToHost));
+    out[3] = ctr[2]; out[4] = key_groups_slots(r.rows); out[5] = ctr[0]; out[6] = ctr[1]; out[7] = ctr[3];
+    return HJ_OK;
+}
+
+int hj_key_groups_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint32_t* rep, uint32_t* group,
+                       uint32_t* firstRows, uint64_t capacity, uint64_t out[8])
+{
+    KeyCols2 k{};
+    if (!out || key_groups_args(cols, nCols, side, nRows, rep, group, firstRows, capacity, &k)) return HJ_ERR_INVALID;
+    key_groups_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, rep, group, firstRows, capacity, out);
+    return HJ_OK;
 }
 
 // ---- join conditions beyond equality (hj_where.hip) --------------------------

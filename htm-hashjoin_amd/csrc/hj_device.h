@@ -838,6 +838,23 @@ hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint
                                 uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
                                 hipStream_t s);
 
+// ---- rows of one table grouped by their key columns (defined in hj_groups.hip, a part of hj_keys.hip) ----
+// launch_key_groups: rep[i] = the lowest row with row i's key (kNoRow: NULL-keyed), firstRows = the rows with rep[i] == i,
+// ascending, cut at `capacity` (null with capacity 0), group[i] = the position of rep[i] among them (null: not wanted).
+// work: key_groups_work_bytes(nRows) bytes -- the table of key_groups_slots(nRows) 8-byte slots, filled with EMPTY here on
+// s, the first-row plane, its popcounts and their scan, the sweep's counts; key_groups_total: where the number of groups
+// lies in it after the call (one 32-bit word). ctr: four 64-bit words, zeroed here -- probe steps beyond the home slot, word
+// collisions, NULL-keyed rows, the failure word. mask is the effective one (never 0). The caller has checked what the
+// header says the entry point refuses, and nRows <= 2^32 - 2.
+uint64_t key_groups_slots(uint64_t nRows);
+size_t key_groups_work_bytes(uint64_t nRows);
+const uint32_t* key_groups_total(const void* work, uint64_t nRows);
+hipError_t launch_key_groups(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint32_t* rep, uint32_t* group,
+                             uint32_t* firstRows, uint64_t capacity, void* work, unsigned long long* ctr, hipStream_t s);
+// the same hash and compare bodies around a sequential table; out: hj_key_groups_host's
+void key_groups_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint32_t* rep, uint32_t* group, uint32_t* firstRows,
+                     uint64_t capacity, uint64_t out[8]);
+
 // ---- join conditions beyond equality (defined in hj_where.hip) ----------------
 // The terms of a call as the kernel takes them, by value in the kernel arguments (hj_where_term, include/htm_hashjoin.h):
 // term t holds for the pair (s, r) when s[t][s] op[t] r[t][r], both elements of width[t] bytes read as type[t], and neither

@@ -1,5 +1,6 @@
 // hj_keys.hip -- joins on real key columns for gfx950 (MI355X): hj_key_hash_dev / hj_key_hash2_dev and
-// hj_pairs_verify_dev / hj_pairs_verify2_dev.
+// hj_pairs_verify_dev / hj_pairs_verify2_dev. hj_groups.hip (hj_key_groups_dev) is included at the end: it groups the rows
+// of ONE table with the hash and the element compare of this file.
 //
 // The joins of this library match on one 32-bit word. A key of 64 bits, of several columns, of 16 bytes, with NULLs or of
 // variable length is joined as hash -> candidate join -> verify: k_key_hash2 turns the key columns of a row into a 32-bit
@@ -92,8 +93,8 @@ constexpr uint32_t kHashLaneRows = 4;                                 // rows pe
 constexpr uint32_t kHashBlockRows = kHashLaneRows * kBlock;           // 1024
 
 // ---- the verify step ------------------------------------------------------------------------------------------------
-template <class E> __device__ __forceinline__ bool same_bytes(const E& a, const E& b) { return a == b; }
-template <> __device__ __forceinline__ bool same_bytes<u4>(const u4& a, const u4& b)
+template <class E> __host__ __device__ __forceinline__ bool same_bytes(const E& a, const E& b) { return a == b; }
+template <> __host__ __device__ __forceinline__ bool same_bytes<u4>(const u4& a, const u4& b)
 {
     return (((a.x ^ b.x) | (a.y ^ b.y)) | ((a.z ^ b.z) | (a.w ^ b.w))) == 0u;
 }
@@ -466,3 +467,7 @@ hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint
 }
 
 }  // namespace hj
+
+// rows of one table grouped by their key columns: part of this translation unit, because it hashes with key_hash2_rows and
+// compares elements with same_bytes and the var_* word walk above -- one copy of each
+#include "hj_groups.hip"

@@ -513,6 +513,51 @@ int hj_key_hash2_host(const hj_key_col2 *cols, uint32_t nCols, uint32_t side, ui
 int hj_pairs_verify2_dev(hj_ctx *ctx, const uint32_t *dMapS, const uint32_t *dMapR, uint64_t nPairs, uint32_t sRowBase,
                          uint64_t sRows, uint64_t rRows, const hj_key_col2 *cols, uint32_t nCols, uint32_t *dOutS,
                          uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
+/* ---- the rows of ONE table grouped by their key columns: DISTINCT, GROUP BY key, a dense group id ----
+ * Which rows of a table have the same key? For row i in [0, nRows), from the `side` pointers of cols[0 .. nCols) (as
+ * hj_key_hash2_dev reads them):
+ *   dRep[i]    the LOWEST row whose key equals row i's -- column equality exactly as hj_pairs_verify2_dev defines it: fixed
+ *              width bytewise; variable length the same length and the same bytes; a NULL equals a NULL only in a column
+ *              with HJ_KEY_NULLS_EQUAL.
+ *   dFirstRows the rows with dRep[i] == i, ascending, from 0 without holes: one row per distinct key (DISTINCT ON, in
+ *              order of first occurrence). Rows at or beyond `capacity` are counted and not written; capacity 0 with
+ *              NULL is the count alone.
+ *   dGroup[i]  the position of dRep[i] in the COMPLETE ascending list of first rows, whatever `capacity` is: a dense
+ *              group id in order of first occurrence (pandas.factorize, torch.unique(return_inverse) up to the order).
+ * A NULL-keyed row (some column WITHOUT HJ_KEY_NULLS_EQUAL is NULL in it, as above) belongs to no group: dRep[i] =
+ * dGroup[i] = HJ_NO_ROW, it is counted apart (hj_key_groups_info out[3]) and its key bytes are never compared. With the
+ * flag on every column no row is NULL-keyed and the NULLs form groups (SQL's GROUP BY). dGroup and dFirstRows may be
+ * NULL (not wanted); dRep may not be NULL when nRows > 0. dGroup with HJ_NO_ROW entries is a dMapG that hj_pairs_agg_dev
+ * takes as it stands: those pairs are skipped.
+ * The result is exact and depends neither on keyMask (which only forces collisions, as in hj_key_hash2_dev), nor on the
+ * slot a key lands in, nor on scheduling. Method: a hash table of >= 2 * nRows 8-byte slots (join word << 32 | row),
+ * filled with EMPTY on the stream at the start of every call; an insert with the priority rule "the lowest row of a key
+ * wins" (CAS into an empty slot, the real keys compared where the words agree, a 64-bit atomicMin only while the slot's row is
+ * above i); a second launch that turns slots into rows and marks the first rows; the ordered sweep of hj_mark_rows_dev
+ * for dFirstRows and the library's scan for the ids. No lane waits for another, and the probe loop is bounded by the
+ * slot count: a row that exceeded it would set the failure word (out[7]) and end as HJ_NO_ROW -- the host never waits on it.
+ * What is read of the columns: what hj_key_hash2_dev reads, and the elements again where two rows are compared.
+ * Asynchronous on the context's stream; nRows 0 enqueues no kernel. Needs no hj_reserve, no table and no state; touches
+ * no counter and no other *_info. The workspace (the table, one bit per row, one word per 32 rows, the sweep's counts)
+ * belongs to the context and only grows: a call that needs more waits for the stream once. `cols` is host memory and is
+ * read before the call returns. The outputs must not alias each other or the columns.
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): the column errors of hj_key_hash2_dev; side > 1; nRows
+ * above 2^32 - 2; dRep NULL with nRows > 0; dFirstRows NULL with nRows > 0 and capacity > 0; an output pointer that is not
+ * 4-byte aligned. */
+int hj_key_groups_dev(hj_ctx *ctx, const hj_key_col2 *cols, uint32_t nCols, uint32_t side, uint64_t nRows,
+                      uint32_t keyMask, uint32_t *dRep, uint32_t *dGroup, uint32_t *dFirstRows, uint64_t capacity);
+/* Waits for the stream. About the last hj_key_groups_dev: out[0] = groups (= first rows found), out[1] = first rows
+ * written (= min(out[0], capacity)), out[2] = the device time of the whole call in microseconds (rounded), out[3] =
+ * NULL-keyed rows, out[4] = table slots, out[5] = probe steps beyond the home slot, summed over the rows, out[6] = key
+ * compares that found a different key (word collisions), summed, out[7] = the device-side failure word, 0 on success.
+ * out[5] and out[6] depend on scheduling (they describe the table, not the result). All 0 before the first call and
+ * after a call with nRows 0. */
+int hj_key_groups_info(hj_ctx *ctx, uint64_t out[8]);
+/* The same function on host pointers: no context, no device (the hash and the compare are the kernels' bodies, around a
+ * sequential table). out[0], out[1] and out[3] as above, the rest 0; out may not be NULL. HJ_ERR_INVALID as
+ * hj_key_groups_dev; a refused call writes nothing. */
+int hj_key_groups_host(const hj_key_col2 *cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask,
+                       uint32_t *rep, uint32_t *group, uint32_t *firstRows, uint64_t capacity, uint64_t out[8]);
 /* hj_r_rows_dev on a caller's plane: the rows rowBase + i, i in [0, rows), whose bit i of dMarks is clear (which =
  * HJ_R_UNMATCHED) or set (HJ_R_MATCHED), ascending, into dOut[0 ..) without holes; rows at or beyond `capacity` are counted
  * and not written (capacity 0: the count alone). The plane is read, never changed; the sweep's count workspace belongs to
