@@ -54,10 +54,15 @@ constexpr uint32_t kWvRoundAt = 64;                 // a retry round runs once t
 // wavefronts per SIMD the registers must allow (16 per CU: what the rings' LDS allows; the compact build fits in 115
 // VGPRs once the chunk state is scalar)
 constexpr int kWvWpe = 4;
-// ... and on the slot-code road, whose ring of words leaves LDS for a fifth workgroup per CU (kWvWordLdsBytes below): 5, i.e. at
-// most 96 VGPRs. That fifth wavefront per SIMD is where the road's gain comes from (profiles/ring_words.md section 4), so it is asked
-// for here and not left to what the register allocator happens to need.
-constexpr int kWvWordWpe = 5;
+// ... and on the slot-code road, whose ring of words leaves LDS for up to eight workgroups per CU (kWvWordLdsBytes below): 7, i.e.
+// at most 72 VGPRs. The kernel is a chain of dependent LDS round trips per wavefront and every further resident wavefront hides
+// some of the waiting (profiles/ring_words.md section 4, profiles/ring_occupancy.md), so the occupancy is asked for here and not
+// left to what the register allocator happens to need; the kernel fits without scratch because its attempts and push rows go in
+// batches of kWvWordRows rows and the next tile's loads are issued behind classify() (k_build_wave). Eight (64 VGPRs) needs
+// scratch. Chunk geometry and priority rotation still count kWvWavesPerCu wavefronts per CU: the dispatcher simply keeps the
+// further workgroups resident.
+constexpr int kWvWordWpe = 7;
+constexpr int kWvWordRows = 4;                      // rows of a tile per batch of attempts + push rows on that road
 // kWvWavesPerCu resident wavefronts per CU, chunks = resident wavefronts x up to kWvMaxRounds rounds (hj_device.h; wave_layout below)
 constexpr uint32_t kWvMinChunk = 32768;             // tuples: a second round of workgroups only while chunks stay this long
 constexpr uint32_t kWvShortestChunk = 4 * kWvTileTuples;   // tuples: no chunk is cut shorter
@@ -71,6 +76,7 @@ constexpr size_t kWvLdsBytes = (size_t)kWvWaves * (kWvWin * sizeof(uint64_t) + 3
 constexpr uint32_t kWvWordGran = 8;
 constexpr size_t kWvWordLdsBytes = (size_t)kWvWaves * ((kWvWordGran << kGranShift) * sizeof(uint32_t) + 2 * kWvQCap * sizeof(uint32_t));
 static_assert((kWvWordGran & (kWvWordGran - 1)) == 0 && kWvWordLdsBytes <= kWvLdsBytes, "a ring of words costs no more LDS than the 8-byte ring");
+static_assert((size_t)kWvWordWpe * kWvWordLdsBytes <= 160u * 1024u, "the workgroups the registers allow fit a CU's 160 KiB of LDS");
 
 // The lane mask of a condition. HIP's __ballot(int) compares an INTEGER with zero: a condition that already is a lane mask
 // (every compare produces one) is first turned into 0 / 1 per lane and compared again -- two vector instructions per
@@ -364,6 +370,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
     uint32_t rounds = 0;                         // retry rounds so far (wave-uniform)
     unsigned long long dropSum = 0, inSum = 0;
     uint32_t drops = 0, bad = 0, foreign = 0;
+    // CODES: the three counts are wave-uniform -- the lane count of a ballot, kept by the scalar unit -- and not one vector
+    // register each (kWvWordWpe); lane 0 hands them in at the end
     uint32_t dCount = 0;                         // tuples deferred so far (wave-uniform)
     DeferredEntry* const myDeferred = slice_deferred(queue, c, sliceLen);
     uint32_t cCount = 0;                         // HTM: conflicts recorded so far (wave-uniform)
@@ -462,7 +470,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         const bool spent = fail & (rw.tries_left(word, probeLen) <= 1u);      // that was the carried tuple's last slot
         const bool dropped = drop1 | spent;
         if (wv_ballot(dropped)) {
-            drops += dropped ? 1u : 0u; dropSum += dropped ? (unsigned long long)rw.key(word, pos, mask32) : 0ull;
+            drops += (uint32_t)__popcll(wv_ballot(dropped)); dropSum += dropped ? (unsigned long long)rw.key(word, pos, mask32) : 0ull;
         }
         const unsigned long long dm = wv_ballot(toDefer);
         if (dm) defer(dm, toDefer, pos, pack64(idx0 + RingWord::rel(word), rw.key(word, pos, mask32)));
@@ -644,7 +652,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             if ((tb & (8u * kWvTile - 1u)) == 7u * kWvTile && *reinterpret_cast<volatile unsigned long long*>(&ctr->compactFail)) return;
         }
         const bool full = (tb + kWvTile <= (cend < tailFrom ? cend : tailFrom)) & (tb >= S + kWvOverlap);
-        issue(nxt[p], tb + kWvPf * kWvTile);
+        // the next tile's loads: behind classify() on the slot-code road (below), where they can take the registers of this tile's high words
+        if constexpr (!CODES) issue(nxt[p], tb + kWvPf * kWvTile);
         const uint32_t roundsAtTileStart = rounds;
         (void)roundsAtTileStart;
         uint32_t myMin = kNone, myMaxInv = kNone;                     // max kept as min of the complement
@@ -652,7 +661,22 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // per row: "a tuple this wavefront inserts" / "... and whose home slot it may touch now". Kept as one boolean per
         // row -- a lane mask in a scalar register pair, free to produce and to branch on -- not as bits of a per-lane word
         // (two VALU instructions per tuple to pack, two to unpack, in a kernel whose retry rounds are VALU bound)
-        bool live[kWvPer], own[kWvPer];
+        // (`own` is a batch's: the attempts and push rows below go in batches of ROWS rows)
+        constexpr int ROWS = CODES ? kWvWordRows : kWvPer;
+        static_assert(kWvPer % ROWS == 0, "whole batches");
+        bool live[kWvPer], own[ROWS];
+        // row j's home slot where the attempts and the push rows need it. CODES: made again from the key (identity hash: one
+        // v_and) against a copy of the mask the optimiser cannot see through, so that no row's home slot stays in a register
+        // from classify() to its push row -- eight VGPRs the road's occupancy has no room for
+        auto home_of = [&](int j) -> uint32_t {
+            if constexpr (CODES) {
+                uint32_t m = mask32;
+                asm volatile("" : "+s"(m));
+                return klo[j] & m;
+            } else {
+                return home[j];
+            }
+        };
         // FULL tiles (every position is this chunk's own, no seam zone) skip the zone tests: they are all but the
         // first and the last one or two tiles of a chunk
         uint32_t badTile = 0;                                         // wave-uniform: invalid tuples of a full tile
@@ -720,8 +744,10 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 const bool ok = mineHere & okKey;
                 inSum += in ? (unsigned long long)pack64(khi[j], klo[j]) : 0ull;
                 if constexpr (FULL) badTile += 64u - (uint32_t)__popcll(wv_ballot(okKey));     // scalar: no per-lane count
+                else if constexpr (CODES) bad += (uint32_t)__popcll(wv_ballot(in & !okKey));
                 else bad += (in & !okKey) ? 1u : 0u;
-                if constexpr (CHECK) foreign += (in & is_foreign(klo[j], sc)) ? 1u : 0u;
+                if constexpr (CHECK && CODES) foreign += (uint32_t)__popcll(wv_ballot(in & is_foreign(klo[j], sc)));
+                else if constexpr (CHECK) foreign += (in & is_foreign(klo[j], sc)) ? 1u : 0u;
                 live[j] = ok;
                 if constexpr (FULL && COMPACT) {
                     // the bounds of a full tile were taken at its top (forced rounds)
@@ -737,7 +763,10 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             }
         };
         if (full) classify(std::true_type{}); else classify(std::false_type{});
-        bad += lane == 0 ? badTile : 0u;
+        // CODES: the next tile's loads are issued here and not at the tile's top: khi[] is dead from here on, so the eight 64-bit
+        // loads in flight cost eight registers less where the tile needs the most (kWvWordWpe)
+        if constexpr (CODES) issue(nxt[p], tb + kWvPf * kWvTile);
+        if constexpr (CODES) bad += badTile; else bad += lane == 0 ? badTile : 0u;
         uint32_t tmin, tmax = 0;                                      // tmin == kNone: the tile holds no valid tuple
         if (COMPACT && full) { tmin = tminF; tmax = tmaxF; }          // taken from the keys at the end of the tile before
         else { tmin = wave_umin(myMin); if (tmin != kNone) tmax = ~wave_umin(myMaxInv); }
@@ -774,22 +803,38 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             allIn = full & (gmin - winLoG < RGRAN) & (gmax - winLoG < RGRAN) & (gmax < limG);
         }
 
-        // ---- the PER home-slot attempts of the tile, issued together (independent LDS round trips) ----
-        std::conditional_t<CODES, uint32_t, unsigned long long> oldv[kWvPer];
+        // ---- the home-slot attempts and the push rows, one batch of ROWS rows after the other ----
+        // ROWS = kWvPer (the 8-byte rings): the tile's eight attempts are issued together, then its eight rows are pushed.
+        // ROWS = kWvWordRows (the slot-code road): the same for rows 0-3, then for rows 4-7, so that four returned words and
+        // four `own` masks are live at a time instead of eight -- the registers the road's occupancy hangs on (kWvWordWpe).
+        // The table is the same. The protocol is confluent (index-priority protocol): the slots' final values do
+        // not depend on the order of the atomicMins, and the attempts of rows 4-7 are the same operations, applied after
+        // rows 0-3 were pushed and perhaps had a round. Rows 0-3 hold the tile's first 256 positions, so nothing of rows 4-7
+        // can be displaced by them later; a round between the batches treats what it finds in a slot as any round does.
+        // The queue's invariant is per row (`while (qCount >= kWvRoundAt)` before every push leaves room for one full
+        // step of 64), and the ring moved once, above, before the first batch: allIn and in_ring hold for every batch,
+        // because rounds never move the ring.
+        int b = 0;                                                    // the batch's first row
+#pragma unroll
+        do {
+        std::conditional_t<CODES, uint32_t, unsigned long long> oldv[ROWS];
+        // the PER home-slot attempts of a batch, issued together (independent LDS round trips)
         // (when the tile's lowest and highest home slot are inside ring and range -- nearly every full tile -- the
         // per-tuple test is skipped: the retry rounds leave the VALU little to spare, hj DESIGN 4.2)
         auto attempts = [&](auto allTag) {
             constexpr bool ALL = decltype(allTag)::value;
 #pragma unroll
-            for (int j = 0; j < kWvPer; ++j) {
-                own[j] = live[j] & (ALL || in_ring(home[j]));
+            for (int r = 0; r < ROWS; ++r) {
+                const int j = b + r;
+                const uint32_t hm = home_of(j);
+                own[r] = live[j] & (ALL || in_ring(hm));
                 if constexpr (CODES) {
-                    oldv[j] = RingWord::kEmpty;
-                    if (own[j]) oldv[j] = atomicMin(&win32[home[j] & (RWIN - 1)], rw.at_home(tb + lane + 64 * j, klo[j]));
+                    oldv[r] = RingWord::kEmpty;
+                    if (own[r]) oldv[r] = atomicMin(&win32[hm & (RWIN - 1)], rw.at_home(tb + lane + 64 * j, klo[j]));
                 } else {
-                oldv[j] = kEmpty;
-                if (own[j])
-                    oldv[j] = atomicMin(reinterpret_cast<unsigned long long*>(&win[home[j] & (kWvWin - 1)]),
+                oldv[r] = kEmpty;
+                if (own[r])
+                    oldv[r] = atomicMin(reinterpret_cast<unsigned long long*>(&win[hm & (kWvWin - 1)]),
                                         (unsigned long long)pack64(idx0 + tb + lane + 64 * j, klo[j]));
                 }
             }
@@ -797,30 +842,32 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         if (allIn) attempts(std::true_type{}); else attempts(std::false_type{});
         // ---- whatever did not finish goes to the retry queue, compacted ----
 #pragma unroll
-        for (int j = 0; j < kWvPer; ++j) {
+        for (int r = 0; r < ROWS; ++r) {
+            const int j = b + r;
             while (qCount >= kWvRoundAt) retry_round();                // dense rounds; leaves room for one full step
-            const bool lv = live[j], ow = own[j];
+            const bool lv = live[j], ow = own[r];
+            const uint32_t hm = home_of(j);
             uint32_t pos, mlo, mhi;
             bool again;
             if constexpr (CODES) {
                 mlo = rw.at_home(tb + lane + 64 * j, klo[j]); mhi = 0u;
-                const bool fail = ow & (oldv[j] != RingWord::kEmpty);  // the slot was taken
-                mlo = (fail & (oldv[j] > mlo)) ? oldv[j] : mlo;        // ... by a later tuple: it moves on instead
+                const bool fail = ow & (oldv[r] != RingWord::kEmpty);  // the slot was taken
+                mlo = (fail & (oldv[r] > mlo)) ? oldv[r] : mlo;        // ... by a later tuple: it moves on instead
                 // the home slot was the carried tuple's last try (the displaced one's, or probeLength 1): dropped here
                 const bool spent = fail & (rw.tries_left(mlo, probeLen) <= 1u);
                 if (wv_ballot(spent)) {
-                    drops += spent ? 1u : 0u; dropSum += spent ? (unsigned long long)rw.key(mlo, home[j], mask32) : 0ull;
+                    drops += (uint32_t)__popcll(wv_ballot(spent)); dropSum += spent ? (unsigned long long)rw.key(mlo, hm, mask32) : 0ull;
                 }
                 const bool on = fail & !spent;
-                pos = on ? ((home[j] + 1) & mask32) : home[j]; mlo = on ? RingWord::step(mlo) : mlo;
+                pos = on ? ((hm + 1) & mask32) : hm; mlo = on ? RingWord::step(mlo) : mlo;
                 again = on | (lv & !ow);
             } else {
             mlo = klo[j]; mhi = idx0 + tb + lane + 64 * j;
-            const uint32_t oldIdx = (uint32_t)(oldv[j] >> 32);
+            const uint32_t oldIdx = (uint32_t)(oldv[r] >> 32);
             const bool fail = ow & (oldIdx != 0xFFFFFFFFu);            // the slot was taken
             const bool disp = fail & (oldIdx > mhi);                   // ... by a later tuple: it moves on instead
-            mlo = disp ? (uint32_t)oldv[j] : mlo; mhi = disp ? (uint32_t)(oldv[j] >> 32) : mhi;
-            pos = fail ? ((home[j] + 1) & mask32) : home[j];
+            mlo = disp ? (uint32_t)oldv[r] : mlo; mhi = disp ? (uint32_t)(oldv[r] >> 32) : mhi;
+            pos = fail ? ((hm + 1) & mask32) : hm;
             again = fail | (lv & !ow);                                 // outside ring or range: the retry round defers it
             }
             const unsigned long long am = wv_ballot(again);
@@ -832,6 +879,8 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 qCount += (uint32_t)__popcll(am);
             }
         }
+        b += ROWS;
+        } while (ROWS < kWvPer && b < kWvPer);                        // one batch: no loop at all, whatever the optimiser does
         if constexpr (COMPACT) {
             // Forced rounds. A queued entry whose slot the ring is about to leave behind would have to be deferred, and
             // there is no deferred phase: it gets its rounds now, at the end of the tile, where nothing of the tile is
@@ -903,6 +952,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
 
     __builtin_amdgcn_s_setprio(0);               // the rotation's priority is not carried into the counter atomics
     // counters: one atomic per wavefront
+    if constexpr (CODES) { if (lane != 0) drops = bad = foreign = 0u; }
     unsigned long long c0 = drops, c3 = bad | ((unsigned long long)foreign << 32);
     const unsigned long long c4 = dCount;
 #pragma unroll
