@@ -3,7 +3,9 @@ distributions do not produce -- near-sorted multisets with bursts of equal keys,
 relation (most tuples are dropped) to the whole table (sparse keys, wrap-around at the table's end), disorder from none
 to far beyond what the rings hold, every probe length -- through the device's pick (0), the workgroup window (2), the
 classic rings (3) and the compact rings (4; where they cannot hold they must hand over, and the table must still be the sequential one).
-Counters and the whole table, slot for slot. HJ_FUZZ_CASES (default 36) sets the number of cases; the seed is fixed."""
+Counters and the whole table, slot for slot. The classic rings run again on a context that keeps row ids (the packed
+build), and the slot-code road -- one code byte per slot, 4-byte ring words -- has random relations of its own with key
+bits above the table size: forced onto small tables, and once by the size rule at 2^25 slots. HJ_FUZZ_CASES (default 36) sets the number of cases; the seed is fixed."""
 import os
 
 import numpy as np
@@ -11,7 +13,8 @@ import pytest
 
 import htm_hashjoin_amd as hj
 import htm_chain_cases as cc
-from fuzz_relations import make_relation
+from fuzz_relations import make_relation, slot_code_case
+from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +41,98 @@ def test_ring_builds_on_random_near_sorted_relations(block):
                     assert got["compactFallback"] != 0, tag              # a hand-over always says why
                 if variant == 3:
                     assert got["buildVariant"] == 3 and got["compactFallback"] == 0, tag
+            # the classic rings once more on a context that keeps row ids: the packed build, the table probe_pairs reads
+            got = ctx.run("atomic", R, S, probeLength=plen, buildVariant=3, keepRowIds=True)
+            tag = (block, case, n, w, plen, "keepRowIds", got["buildVariant"], got["compactFallback"])
+            for k in ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum"):
+                assert got[k] == want[k], (k, got[k], want[k], tag)
+            assert np.array_equal(ctx.export_table(2 * n), want["table"]), tag
+            assert got["buildVariant"] == 3 and got["compactFallback"] == 0, tag
+
+
+COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum")
+LOG_OVERFLOW, CODE_OVERFLOW = 1, 4                       # slot_codes_info()["cause"]
+
+
+def build_probe_codes(c, R, S, plen, variant, slot_codes, idx_base=0):
+    """one build + probe + checksums through the split API (test_gpu_slot_codes.build_probe) -> (result, table, info)"""
+    c.reserve("atomic", R.size, S.size, probeLength=plen, buildVariant=variant, slotCodes=slot_codes)
+    with Dev(c) as dev:
+        c.build(dev.put(R), R.size, idx_base)
+        c.probe(dev.put(S), S.size)
+        c.checksums()
+        got = c.fetch()
+        return got, c.export_table(2 * R.size), c.slot_codes_info()
+
+
+def check_road(got, table, info, want, road, uncodable, tag):
+    """the oracle's result whatever the road; on the rings, what slot_codes_info says about the road against what the
+    host knows. -> whether the build stayed on the slot-code road"""
+    for k in COUNTERS:
+        assert got[k] == want[k], (k, got[k], want[k], tag)
+    assert got["outputSum"] == want["outputSumAtomic"], tag
+    assert np.array_equal(table, want["table"]), tag
+    if got["buildVariant"] != 3:
+        return False                                         # the device's pick was another build: nothing about the road
+    assert info["road"] == road, tag
+    assert bool(info["cause"] & CODE_OVERFLOW) == uncodable, tag
+    assert info["cause"] & ~(LOG_OVERFLOW | CODE_OVERFLOW) == 0, tag
+    if info["cause"] == 0:
+        assert (info["codes"], info["tableFormat"]) == (True, 2), tag
+    else:                                                    # a hand-over says so: the 8-byte build redid the table
+        assert (info["codes"], info["tableFormat"]) == (False, 0), tag
+    return info["cause"] == 0
+
+
+@pytest.mark.parametrize("block", range(4))
+def test_slot_code_road_on_random_near_sorted_relations(block):
+    """The road production takes, k_build_wave<PLANAR, CODES>, forced onto small tables (slotCodes=True) through the classic
+    rings (3) and the device's pick (0): 1 to 512 chunks, every probe length with its own displacement bits, keys with
+    high parts above the table (fuzz_relations.make_relation(high=True)) so that codes, ring words and decoded keys carry
+    them, idxBase 0 and near 2^32, S asking for every high-part variant of some home slots. Counters, outputSum and the
+    whole table against the sequential oracle; then the road: cause 4 exactly when R holds a key without a code (the host
+    knows: keyLimit = hiCap << tableBits), a hand-over for the dirty log (cause 1) permitted but reported, and otherwise
+    (codes, road, tableFormat) == (True, 2, 2). At least half of the cases without an uncodable key must have stayed on the
+    road (test_fuzz_tables.py shows from the drawn W that the seeds allow it)."""
+    cases = int(os.environ.get("HJ_FUZZ_CASES", "36"))
+    rng = np.random.default_rng(20265000 + block)
+    stayed = codable = 0
+    with hj.HashJoinContext(0) as ctx:
+        for case in range(block, cases, 4):
+            n, plen, idx_base, R, S, w, hi = slot_code_case(rng)
+            lay = ctx.wave_layout_info(n)
+            uncodable = bool((R >= np.uint64(hi["keyLimit"])).any())
+            assert uncodable == (hi["over"] > 0)
+            want = oracle.build_probe_seq(R, S, plen, want_table=True)
+            for variant in (3, 0):
+                got, table, info = build_probe_codes(ctx, R, S, plen, variant, True, idx_base)
+                tag = (block, case, n, w, plen, idx_base, hi["mode"], hi["over"], lay["nChunks"], lay["chunkLen"], variant,
+                       got["buildVariant"], got["compactFallback"], info)
+                if variant == 3:
+                    assert got["buildVariant"] == 3 and got["compactFallback"] == 0, tag
+                on_road = check_road(got, table, info, want, 2, uncodable, tag)
+                if variant == 3 and not uncodable:
+                    codable += 1
+                    stayed += on_road
+    print(f"slot-code road: block {block}: {stayed} of {codable} codable cases stayed")
+    assert 2 * stayed >= codable, (block, stayed, codable)
+
+
+def test_slot_code_road_by_the_size_rule():
+    """The one large case: 2^25 slots at probeLength 1, where a byte holds any 32-bit key -- no flag, the road by the size
+    rule (road 1) -- on a random relation of 2^24 tuples whose high parts take all 128 values."""
+    n, plen = 1 << 24, 1
+    assert hj.slot_codes_info(2 * n, plen)["fitsAuto"]
+    rng = np.random.default_rng(20266000)
+    R, w, hi = make_relation(rng, n, high=True, plen=plen, hi_mode="uniform")
+    assert hi["hiCap"] == 128 and hi["over"] == 0 and np.unique(R >> np.uint64(25)).size == 128
+    S = np.ascontiguousarray(np.concatenate([rng.permutation(R)[: n // 4], R[:4096] ^ np.uint64(1 << 31)]))
+    want = oracle.build_probe_seq(R, S, plen, want_table=True)
+    with hj.HashJoinContext(0) as ctx:
+        got, table, info = build_probe_codes(ctx, R, S, plen, 3, False)
+        tag = (n, w, plen, got["buildVariant"], got["compactFallback"], info)
+        assert got["buildVariant"] == 3 and got["compactFallback"] == 0 and info["fitsAuto"], tag
+        check_road(got, table, info, want, 1, False, tag)
 
 
 @pytest.mark.parametrize("block", range(2))
