@@ -14,9 +14,12 @@ from ._lib import (  # noqa: F401
     HJ_AGG_MAX_COLS, HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX, HJ_AGG_SIGNED, hj_agg_spec, hj_agg_src, hj_agg_col,
 )
 from .engine import (  # noqa: F401
-    HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, join_pairs, radix_join_pairs,
-    outer_join_pairs, radix_outer_join_pairs, join_tables, join_on, key_hash_host,
-    KeyColumn, join_on_columns, key_hash2_host, pairs_where_host, pairs_asof_host, radix_join_aggregate, aggregate_on, prj_agg_layout_info,
-    key_groups, key_groups_host, distinct_on, group_by_columns,
+    HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, prj_agg_layout_info,
     generate_data, generate_relation, device_count, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, ring_word_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )
+from .columns import KeyColumn, key_hash_host, key_hash2_host  # noqa: F401
+from .conditions import pairs_where_host, pairs_asof_host  # noqa: F401
+from .joins import join_pairs, radix_join_pairs, outer_join_pairs, radix_outer_join_pairs, join_tables  # noqa: F401
+from .key_joins import join_on, join_on_columns  # noqa: F401
+from .aggregates import radix_join_aggregate, aggregate_on  # noqa: F401
+from .groups import key_groups, key_groups_host, distinct_on, group_by_columns  # noqa: F401
