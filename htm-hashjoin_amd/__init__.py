@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     HJ_KEY_MAX_COLS, HJ_KEY_SIDE_S, HJ_KEY_SIDE_R, hj_key_col, HJ_KEY_NULLS_EQUAL, hj_key_col2, hj_gather_col2,
     HJ_WHERE_MAX_TERMS, HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE, CMP_OPS, HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT,
     hj_where_term, ASOF_OPS, hj_asof_term,
+    HJ_SORT_MAX_COLS, HJ_SORT_DESC, HJ_SORT_NULLS_FIRST, hj_sort_col,
     HJ_AGG_MAX_COLS, HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX, HJ_AGG_SIGNED, hj_agg_spec, hj_agg_src, hj_agg_col,
 )
 from .engine import (  # noqa: F401
@@ -23,3 +24,4 @@ from .joins import join_pairs, radix_join_pairs, outer_join_pairs, radix_outer_j
 from .key_joins import join_on, join_on_columns  # noqa: F401
 from .aggregates import radix_join_aggregate, aggregate_on  # noqa: F401
 from .groups import key_groups, key_groups_host, distinct_on, group_by_columns  # noqa: F401
+from .sorting import sort_rows, sort_rows_host, sort_by_columns, sort_pairs  # noqa: F401

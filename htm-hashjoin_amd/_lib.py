@@ -54,6 +54,9 @@ CMP_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT = 0, 1, 2
 # hj_pairs_asof_dev: the ops that order (backward: >=, >; forward: <=, <)
 ASOF_OPS = {op: CMP_OPS[op] for op in (">=", ">", "<=", "<")}
+# hj_sort_rows_dev: columns of one call, and hj_sort_col.flags
+HJ_SORT_MAX_COLS = 4
+HJ_SORT_DESC, HJ_SORT_NULLS_FIRST = 0x1, 0x2
 # aggregating joins (hj_agg_op, hj_agg_spec.flags)
 HJ_AGG_MAX_COLS = 4
 HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
@@ -161,6 +164,17 @@ class hj_asof_term(C.Structure):
     _fields_ = list(hj_where_term._fields_)     # the same layout; op is one of GE, GT, LE, LT
 
 
+class hj_sort_col(C.Structure):
+    _fields_ = [
+        ("values", C.c_void_p),
+        ("valid", C.c_void_p),
+        ("width", C.c_uint32),
+        ("type", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class hj_agg_spec(C.Structure):
     _fields_ = [
         ("op", C.c_uint32),
@@ -225,6 +239,10 @@ def _declare(lib):
         "hj_key_groups_dev": ([vp, P(hj_key_col2), u32, u32, u64, u32, vp, vp, vp, u64], i32),
         "hj_key_groups_info": ([vp, P(u64)], i32),
         "hj_key_groups_host": ([P(hj_key_col2), u32, u32, u64, u32, vp, vp, vp, u64, P(u64)], i32),
+        "hj_sort_rows_dev": ([vp, P(hj_sort_col), u32, u64, vp], i32),
+        "hj_sort_rows_info": ([vp, P(u64)], i32),
+        "hj_sort_rows_host": ([P(hj_sort_col), u32, u64, vp, P(u64)], i32),
+        "hj_sort_layout_info": ([u64, P(u64)], i32),
         "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
         "hj_where_info": ([vp, P(u64)], i32),
         "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),

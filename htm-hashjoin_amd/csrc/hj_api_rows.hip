@@ -1,5 +1,5 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns, the
+// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns and sorted by them, the
 // join conditions beyond equality, the as-of step, and the *_info entry point of every call that has a record (hj_host.h:
 // CallRecord). Host-side glue only.
 #include "hj_host.h"
@@ -420,6 +420,77 @@ int hj_key_groups_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, u
     KeyCols2 k{};
     if (!out || key_groups_args(cols, nCols, side, nRows, rep, group, firstRows, capacity, &k)) return HJ_ERR_INVALID;
     key_groups_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, rep, group, firstRows, capacity, out);
+    return HJ_OK;
+}
+
+// ---- rows in the order of their columns (hj_sort.hip) -------------------------
+// hj_sort_rows_dev's and hj_sort_rows_host's arguments -> the kernels' columns; the message of what is wrong, or nullptr
+static const char* sort_args(const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, const uint32_t* perm, SortCols* k)
+{
+    if (nCols == 0 || nCols > HJ_SORT_MAX_COLS) return "nCols must be 1 .. HJ_SORT_MAX_COLS";
+    if (!cols) return "cols NULL";
+    if (nRows > 0xFFFFFFFEull) return "nRows above 2^32 - 2";
+    for (uint32_t i = 0; i < nCols; ++i) {
+        const hj_sort_col& col = cols[i];
+        if (col.type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
+        const bool widthOk = col.width == 4 || col.width == 8 || (col.type != HJ_VAL_FLOAT && (col.width == 1 || col.width == 2));
+        if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
+        if (col.flags & ~(HJ_SORT_DESC | HJ_SORT_NULLS_FIRST)) return "hj_sort_col.flags has bits other than HJ_SORT_DESC and HJ_SORT_NULLS_FIRST";
+        if (col.reserved) return "hj_sort_col.reserved must be 0";
+        if (nRows && !col_ptr_ok(col.values, col.width)) return "a values pointer that is NULL or not aligned to its width";
+        if (nRows && !word_ptr_ok(col.valid)) return "a validity pointer that is not 4-byte aligned";
+        k->p[i] = col.values; k->valid[i] = col.valid; k->width[i] = col.width; k->type[i] = col.type; k->flags[i] = col.flags;
+    }
+    if (nRows && (!perm || !word_ptr_ok(perm))) return "dPerm NULL or not 4-byte aligned";
+    return nullptr;
+}
+
+int hj_sort_rows_dev(hj_ctx* c, const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, uint32_t* dPerm)
+{
+    HJ_ENTER(c, true);
+    SortCols k{};
+    if (const char* what = sort_args(cols, nCols, nRows, dPerm, &k)) return fail(c, HJ_ERR_INVALID, "hj_sort_rows_dev", what);
+    HJ_HIP(c, hipSetDevice(c->device));
+    const SortLayout l = sort_layout(nRows, sort_key_bytes(k, nCols));
+    if (nRows)
+        if (const int rc = c->buf[B_SORT_WORK].reserve(c, l.bytes)) return rc;
+    HJ_HIP(c, hipEventRecord(c->call[CALL_SORT].ev[0], c->stream));
+    HJ_HIP(c, launch_sort_rows(k, nCols, nRows, dPerm, c->buf[B_SORT_WORK].p, c->stream));
+    c->sort = {};
+    if (nRows) c->sort = {sort_passes(k, nCols), l.chunks, l.chunkRows, l.bytes};
+    return call_end(c, CALL_SORT, 0, nRows);
+}
+
+int hj_sort_rows_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_SORT];
+    for (int i = 4; i < 8; ++i) out[i] = 0;
+    if (const int rc = call_info(c, r, nullptr, 0, out)) return rc;
+    if (!r.called || !r.rows) { out[2] = 0; return HJ_OK; }     // no row: nothing was enqueued between the two events
+    out[0] = r.rows; out[1] = c->sort.passes; out[3] = 0;       // no pass is ever skipped
+    out[4] = c->sort.chunks; out[5] = c->sort.chunkRows; out[6] = c->sort.bytes;
+    return HJ_OK;
+}
+
+int hj_sort_rows_host(const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, uint32_t* perm, uint64_t out[8])
+{
+    SortCols k{};
+    if (sort_args(cols, nCols, nRows, perm, &k)) return HJ_ERR_INVALID;
+    sort_rows_host(k, nCols, nRows, perm);
+    if (!out) return HJ_OK;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!nRows) return HJ_OK;
+    const SortLayout l = sort_layout(nRows, sort_key_bytes(k, nCols));
+    out[0] = nRows; out[1] = sort_passes(k, nCols); out[4] = l.chunks; out[5] = l.chunkRows; out[6] = l.bytes;
+    return HJ_OK;
+}
+
+int hj_sort_layout_info(uint64_t nRows, uint64_t out[4])
+{
+    if (!out || nRows > 0xFFFFFFFEull) return HJ_ERR_INVALID;
+    const SortLayout l = sort_layout(nRows, 8);
+    out[0] = l.tileRows; out[1] = l.chunkRows; out[2] = l.chunks; out[3] = l.bytes;
     return HJ_OK;
 }
 

@@ -74,6 +74,33 @@ __host__ __device__ inline bool is_foreign(uint32_t key, const ShardCheck& sc) {
 constexpr int kBlock = 256;          // 4 wavefronts of 64
 constexpr int kWave = 64;
 
+// exclusive scan over the NT threads of a workgroup: v -> the sum of the threads below; total: the sum of all. wsum: NT / 64
+// words of LDS. Two barriers; every thread of the workgroup calls it.
+template <int NT = kBlock>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wsum /*[NT/64]*/, uint32_t& total)
+{
+    // inclusive scan inside the wavefront
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t n = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += n;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t wbase = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) {
+        const uint32_t s = wsum[k];
+        if (k < w) wbase += s;
+        tot += s;
+    }
+    total = tot;
+    __syncthreads();
+    return wbase + inc - v;
+}
+
 // words launch_sample_locality works on: 8 (five totals, [7] = the ticket) + 8 per workgroup of the sampler (its own counts)
 constexpr int kSampleBlocks = 256;
 constexpr int kSampleWords = 8 + 8 * kSampleBlocks;
@@ -971,6 +998,42 @@ hipError_t launch_pairs_asof(const uint32_t* mapS, const uint32_t* mapR, uint64_
 void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
                      const AsofTerm& term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
                      uint32_t* sMarks, uint32_t* rMarks, uint64_t* info);
+
+// ---- rows in the order of their columns (defined in hj_sort.hip) --------------
+// The order key of the sort: the zero-extended raw word of a valid element of `width` bytes read as `type` -> an unsigned
+// word of 8 * width bits that orders as the header states it, equal exactly where two elements tie. UINT: the word. INT:
+// the sign bit flipped within the width. FLOAT: folded as asof_key folds, in the element's own width -- a negative's bits all
+// complemented, a positive's sign bit set, -0.0 taken for +0.0 -- and every NaN, whatever its sign or payload, all ones:
+// above +inf. HJ_SORT_DESC complements the word within the width, NaN included. A NULL's key is 0: the caller's business.
+constexpr uint32_t kSortMaxCols = 4;          // HJ_SORT_MAX_COLS
+constexpr uint32_t kSortDesc = 1u, kSortNullsFirst = 2u;      // HJ_SORT_DESC, HJ_SORT_NULLS_FIRST
+__host__ __device__ __forceinline__ uint64_t sort_key(uint32_t type, uint32_t width, uint32_t flags, uint64_t raw)
+{
+    const uint32_t bits = 8u * width;
+    const uint64_t top = 1ull << (bits - 1u), mask = top | (top - 1ull);
+    uint64_t key = raw & mask;
+    if (type == kValInt) key ^= top;
+    else if (type == kValFloat) {
+        const uint64_t mag = key & (top - 1ull), inf = width == 4u ? 0x7F800000ull : 0x7FF0000000000000ull;
+        if (mag > inf) key = mask;                                    // a NaN
+        else if (mag == 0ull) key = top;                              // -0.0 == 0.0: one key for both
+        else key = (key & top) ? ~key & mask : key | top;
+    }
+    return (flags & kSortDesc) ? ~key & mask : key;
+}
+// The columns of a call as the kernels take them (hj_sort_col, include/htm_hashjoin.h); cols[0] is the most significant.
+struct SortCols { const void* p[kSortMaxCols]; const uint32_t* valid[kSortMaxCols]; uint32_t width[kSortMaxCols], type[kSortMaxCols], flags[kSortMaxCols]; };
+// How a pass cuts nRows records of keyBytes-byte keys: a workgroup ranks tileRows records at a time and owns chunkRows (a
+// multiple of it) in a pass; the workspace is two key planes and two row planes of nRows, a histogram of 256 words per
+// chunk -- at most 4096 chunks at any nRows: 4 MiB -- and its scan sums. bytes is monotone in nRows.
+struct SortLayout { uint32_t tileRows, chunkRows, chunks; size_t keyPlane, rowPlane, histBytes, bytes; };
+SortLayout sort_layout(uint64_t nRows, uint32_t keyBytes);
+uint32_t sort_key_bytes(const SortCols& cols, uint32_t nCols);       // 8 with an 8-byte column, else 4
+uint32_t sort_passes(const SortCols& cols, uint32_t nCols);          // one per element byte, one more per validity plane
+// perm[0 .. nRows) = the rows in the order of the columns, stable. work: sort_layout(nRows, sort_key_bytes(..)).bytes. The
+// caller has checked what the header says the entry point refuses. nRows 0 enqueues nothing.
+hipError_t launch_sort_rows(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm, void* work, hipStream_t s);
+void sort_rows_host(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm);     // sort_key around std::stable_sort
 
 // ---- PRJ (defined in hj_prj.hip) -------------------------------------------
 // Fragment geometry of the histogram-free partitioning of ONE relation (hj_prj.hip, "histogram-free partitioning"):

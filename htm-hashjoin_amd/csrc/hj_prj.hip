@@ -250,31 +250,6 @@ k_radix_hist_rows(const uint64_t* __restrict__ in, uint64_t* __restrict__ stampe
 constexpr int kScanPerThread = 16;
 constexpr int kScanTile = kBlock * kScanPerThread;  // 4096
 
-template <int NT = kBlock>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wsum /*[NT/64]*/, uint32_t& total)
-{
-    // inclusive scan inside the wavefront
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t n = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += n;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; ++k) {
-        const uint32_t s = wsum[k];
-        if (k < w) wbase += s;
-        tot += s;
-    }
-    total = tot;
-    __syncthreads();
-    return wbase + inc - v;
-}
-
 __global__ void __launch_bounds__(kBlock)
 k_scan_blocks(uint32_t* __restrict__ data, uint64_t n, uint32_t* __restrict__ blockSums, Gate gate)
 {

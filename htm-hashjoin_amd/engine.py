@@ -182,6 +182,16 @@ SHARD_ONE_BASED = 0x100
 
 
 _KEY_GROUPS_INFO = ("groups", "written", "us", "null_rows", "slots", "probe_steps", "collisions", "failure")
+_SORT_ROWS_INFO = ("rows", "passes", "us", "skipped", "chunks", "chunk_rows", "workspace_bytes", "reserved")
+
+
+def _sort_cols(cols):
+    """[(values_ptr, valid_ptr, width, type, flags)] -> (hj_sort_col array, its length)"""
+    cols = list(cols)
+    arr = (_lib.hj_sort_col * max(len(cols), 1))()
+    for c, (values, valid, width, type_, flags) in zip(arr, cols):
+        c.values, c.valid, c.width, c.type, c.flags, c.reserved = values or None, valid or None, width, type_, flags, 0
+    return arr, len(cols)
 
 
 def _key_cols(cols):
@@ -449,6 +459,22 @@ class HashJoinContext:
         of the call in microseconds, NULL-keyed rows, table slots, probe steps beyond the home slot, key compares that found
         a different key (word collisions), the device-side failure word (0 on success)."""
         return dict(zip(_KEY_GROUPS_INFO, self._info(lib.hj_key_groups_info, 8)))
+
+    # ---- rows in the order of their columns ----------------------------------------
+    def sort_rows(self, desc, n, d_perm):
+        """hj_sort_rows_dev: d_perm[0 .. n) = the rows 0 .. n - 1 of ONE table in ascending lexicographic order of its key
+        columns, stable (ORDER BY). desc = 1 to HJ_SORT_MAX_COLS tuples (values_ptr, valid_ptr, width, type, flags) of device
+        pointers, the most significant column first: elements of `width` bytes read as HJ_VAL_UINT / HJ_VAL_INT (1, 2, 4, 8)
+        or HJ_VAL_FLOAT (4, 8: -0.0 == 0.0, every NaN one value above +inf), valid_ptr the validity plane or 0, flags
+        HJ_SORT_DESC | HJ_SORT_NULLS_FIRST (NULLs stand last without it, whatever the direction). Asynchronous; needs no
+        reserve and no table; the workspace belongs to the context and grows with n."""
+        arr, k = _sort_cols(desc)
+        self._check(lib.hj_sort_rows_dev(self._h, arr, k, n, _vp(d_perm)))
+
+    def sort_rows_info(self):
+        """hj_sort_rows_info (waits for the stream), about the last sort_rows: rows, radix passes, the device time of the
+        whole call (us), passes skipped (always 0), chunks, chunk_rows, workspace_bytes"""
+        return dict(zip(_SORT_ROWS_INFO, self._info(lib.hj_sort_rows_info, 8)))
 
     # ---- join conditions beyond equality ------------------------------------------
     def pairs_where(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, terms, d_out_s, d_out_r, capacity,

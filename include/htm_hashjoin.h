@@ -683,6 +683,62 @@ int hj_asof_info(hj_ctx *ctx, uint64_t out[4]);
 int hj_pairs_asof_host(const uint32_t *mapS, const uint32_t *mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
                        uint64_t rRows, const hj_asof_term *term, uint64_t *bestVal, uint32_t *bestRow, uint32_t *outS,
                        uint32_t *outR, uint64_t capacity, uint32_t *sMarks, uint32_t *rMarks, uint64_t info[4]);
+/* ---- the rows of ONE table in the order of their columns: ORDER BY ----
+ * Every call above that returns rows leaves their order unspecified. hj_sort_rows_dev puts the rows of a table in order:
+ * dPerm[0 .. nRows) is the permutation of the rows 0 .. nRows - 1 in ASCENDING LEXICOGRAPHIC order of cols[0 .. nCols),
+ * cols[0] the most significant -- ORDER BY a DESC, b NULLS FIRST, c, d over typed, nullable columns in one call. A gather
+ * through dPerm (hj_gather_dev / hj_gather2_dev) puts any column of the table, strings included, in that order.
+ * Within a column two valid elements compare as a term of hj_pairs_where_dev compares them: HJ_VAL_UINT / HJ_VAL_INT as
+ * integers of the width and signedness; HJ_VAL_FLOAT as IEEE-754 binary32 / binary64 values with -0.0 == 0.0. Where that
+ * comparison has no opinion a sort must have one, and it is numpy's and pandas': every NaN, whatever its sign or payload,
+ * equals every other NaN and is greater than +inf. HJ_SORT_DESC reverses the order of the column's valid elements, NaN
+ * included (the NaNs then come first among them). A NULL equals a NULL, and the NULLs of a column stand BEHIND all its
+ * valid elements, or in FRONT of them with HJ_SORT_NULLS_FIRST -- independently of HJ_SORT_DESC: pandas' na_position, not
+ * PostgreSQL's default (where DESC implies NULLS FIRST). The bytes under a NULL are read (they exist) and never influence
+ * the result. Rows equal in every column keep ascending row order: the sort is stable, the library's index-priority rule.
+ * The result is therefore unique, independent of scheduling, and the same bit for bit on every run.
+ * Method (hj_sort.hip): an LSD radix sort over (key, row) records, 8 bits per pass, the columns processed last
+ * to first; 4-byte keys for elements of 1, 2 and 4 bytes -- a pass per element byte: an int16 column costs 2 passes, a
+ * float32 column is not widened --, 8-byte keys for 8-byte elements, and one 2-bin pass more for a column with a validity
+ * plane. A pass is a per-chunk histogram, the library's scan, and a stable scatter that ranks with ballots, without an
+ * atomic. No workgroup waits for another (no look-back, no flag that is spun on); every loop is bounded by the chunk.
+ * What it does NOT do: strings (as the condition step: no ordering of strings), 16-byte elements, collations, a row map
+ * as input (gather first), top-k without the full sort, more than HJ_SORT_MAX_COLS columns in a call.
+ * Asynchronous on the context's stream; nRows 0 enqueues no kernel. Needs no hj_reserve, no table and no state; touches no
+ * counter and no other *_info. The workspace (two key planes and two row planes of nRows, a histogram of 256 words per
+ * chunk, the scan's sums: hj_sort_layout_info) belongs to the context and only grows: a call that needs more waits for
+ * the stream once. `cols` is host memory and is read before the call returns. dPerm must not alias a column or a plane.
+ * Nothing is written outside dPerm[0 .. nRows).
+ * HJ_ERR_INVALID (nothing is enqueued; also for a NULL context): nCols 0 or above HJ_SORT_MAX_COLS, cols NULL; a type
+ * above HJ_VAL_FLOAT, a width the type does not have; flag bits other than the two defined; reserved != 0; with nRows > 0
+ * a values pointer that is NULL or not aligned to its width, a validity pointer that is not 4-byte aligned, dPerm NULL or
+ * not 4-byte aligned; nRows above 2^32 - 2. */
+#define HJ_SORT_MAX_COLS   4
+#define HJ_SORT_DESC        0x1u   /* this column descending */
+#define HJ_SORT_NULLS_FIRST 0x2u   /* this column's NULLs before its values (default: after) */
+typedef struct {
+    const void     *values;   /* nRows elements of `width` bytes, aligned to it        */
+    const uint32_t *valid;    /* NULL: no NULLs. Else the plane hj_gather_dev writes   */
+    uint32_t width;           /* UINT / INT: 1, 2, 4, 8.  FLOAT: 4, 8                  */
+    uint32_t type;            /* hj_val_type                                           */
+    uint32_t flags;           /* HJ_SORT_DESC | HJ_SORT_NULLS_FIRST                    */
+    uint32_t reserved;        /* 0                                                     */
+} hj_sort_col;                /* 32 bytes */
+int hj_sort_rows_dev(hj_ctx *ctx, const hj_sort_col *cols, uint32_t nCols, uint64_t nRows, uint32_t *dPerm);
+/* Waits for the stream. About the last hj_sort_rows_dev: out[0] = rows, out[1] = radix passes launched (one per element
+ * byte and one per validity plane), out[2] = the device time of the whole call in microseconds (rounded), out[3] = passes
+ * skipped (always 0: no pass is skipped), out[4] = chunks, out[5] = chunk rows, out[6] = workspace bytes the call needed,
+ * out[7] = 0. All 0 before the first call and after a call with nRows 0. */
+int hj_sort_rows_info(hj_ctx *ctx, uint64_t out[8]);
+/* The same function on host pointers: no context, no device (the order key is the kernels' body, around one stable sort
+ * per column). `out` (may be NULL) is filled as hj_sort_rows_info fills it, out[2] = 0. HJ_ERR_INVALID as
+ * hj_sort_rows_dev; a refused call writes nothing. */
+int hj_sort_rows_host(const hj_sort_col *cols, uint32_t nCols, uint64_t nRows, uint32_t *perm, uint64_t out[8]);
+/* How a pass cuts nRows rows; a pure function, no context and no device: out[0] = tile rows (what one workgroup ranks at
+ * a time), out[1] = chunk rows (what one workgroup owns in a pass, a multiple of the tile; grows with nRows), out[2] =
+ * chunks (at most 4096 at any nRows: the histogram of a pass is bounded by 256 x 4096 words = 4 MiB), out[3] = workspace
+ * bytes with 8-byte keys (monotone in nRows). HJ_ERR_INVALID for out NULL or nRows above 2^32 - 2. */
+int hj_sort_layout_info(uint64_t nRows, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */

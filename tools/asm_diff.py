@@ -16,7 +16,7 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["hj_kernels", "hj_build_own", "hj_build_wave", "hj_htm", "hj_pairs", "hj_r_marks", "hj_gather", "hj_keys", "hj_where", "hj_asof", "hj_agg",
+FILES = ["hj_kernels", "hj_build_own", "hj_build_wave", "hj_htm", "hj_pairs", "hj_r_marks", "hj_gather", "hj_keys", "hj_where", "hj_asof", "hj_agg", "hj_sort",
          "hj_prj",      # its translation unit includes hj_prj_pairs.hip and hj_prj_agg.hip: their kernels are listed under it
          "hj_api",
          "hj_api_table", "hj_api_prj", "hj_api_rows", "hj_api_tools"]
