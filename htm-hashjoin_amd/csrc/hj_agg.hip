@@ -10,7 +10,7 @@
 //
 // The cost is one memory-side atomic request per run and column, scattered: a list without runs (a foreign-key join grouped
 // by its unique side) pays one request per pair and column. Exact: integer ops only, so no result depends on the order.
-#include "hj_device.h"
+#include "hj_columns.h"
 
 namespace hj {
 
@@ -44,7 +44,7 @@ k_pairs_agg(const uint32_t* __restrict__ mapG, const uint32_t* __restrict__ mapV
             const uint32_t op = cols.ops.op[c], sgn = cols.ops.sgn[c];
             const unsigned long long id = agg_identity(op, sgn);
             const uint32_t* const valid = cols.src.valid[c];
-            const bool ok = live && (!valid || ((valid[v >> 5] >> (v & 31u)) & 1u));
+            const bool ok = live && (!valid || valid_bit(valid, v));
             unsigned long long x = ok ? agg_value(cols.src.p[c], op, cols.ops.width[c], sgn, v) : id;
 #pragma unroll
             for (uint32_t off = 1; off < (uint32_t)kWave; off <<= 1) {

@@ -6,7 +6,7 @@
 
 using namespace hjapi;
 
-// One build as its launchers see it (hj_device.h): the context's table, counters and stream around the caller's input
+// One build as its launchers see it (hj_table.h): the context's table, counters and stream around the caller's input
 static BuildJob build_job(hj_ctx* c, const void* R, bool key32, uint64_t n, uint32_t hshift, uint64_t tableSize, uint32_t probeLen,
                           uint64_t idxBase, ShardCheck sc)
 {
@@ -23,7 +23,7 @@ static BuildJob build_job(hj_ctx* c, const void* R, bool key32, uint64_t n, uint
 //   3  the wavefront-private rings (hj_build_wave.hip) if at most 1/128 of the sampled tuples would fall outside
 //      their ring (tight locality: the reference's default shuffle window of 16, anything up to ~100 positions);
 //   2  the workgroup window (hj_build_own.hip) if it would have to defer at most 3/4 of the tuples (variant_for_sample,
-//      hj_device.h: what it defers costs about what global atomics cost for every tuple);
+//      hj_table.h: what it defers costs about what global atomics cost for every tuple);
 //   1  global atomics otherwise (no locality: hj_join_dev(AUTO) then takes the radix join instead).
 int hjapi::sample_variant(hj_ctx* c, const void* d, bool key32, uint64_t n, uint64_t tableSize, uint32_t hshift,
                           const BuildCaps& can, uint32_t* variant, bool htm)
@@ -393,7 +393,7 @@ int hj_export_table(hj_ctx* c, uint64_t* host_table, uint64_t tableSize)
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     Counters k;
     HJ_HIP(c, hipMemcpy(&k, c->dCtr(), sizeof(k), hipMemcpyDeviceToHost));
-    // only [validLo, validHiEx + 512) holds defined values (hj_device.h); the rest is empty by definition
+    // only [validLo, validHiEx + 512) holds defined values (hj_table.h); the rest is empty by definition
     const uint64_t lo = k.validLo, hi = k.validHiEx + 512 < tableSize ? k.validHiEx + 512 : tableSize;
     if (k.tableFormat == kFormatCodes1) {
         // slot codes (one byte per slot, 0xFF = empty) -> reference format: the codes land at the end of the caller's buffer

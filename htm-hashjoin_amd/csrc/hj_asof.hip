@@ -6,11 +6,11 @@
 // planes with one entry per S row, which the call initialises itself:
 //
 //   k_asof_best   bestVal[s] = max over the ELIGIBLE pairs (s, r) -- s[s] OP r[r] holds as a term of the condition step
-//                 does -- of asof_key(r[r]) (hj_device.h: an unsigned word that orders as the values do; the forward ops
+//                 does -- of asof_key(r[r]) (hj_columns.h: an unsigned word that orders as the values do; the forward ops
 //                 complement it, so every pass takes a maximum). 64-bit atomic max at agent scope.
 //   k_asof_row    bestRow[s] = min over the eligible pairs whose key EQUALS bestVal[s] of their R row: ties on the value --
 //                 -0.0 and 0.0 among them -- go to the lowest R row, the library's index-priority rule. 32-bit atomic min.
-//   k_asof_keep   the pair-filter frame (hj_device.h) a third time: a live pair is kept iff its R row is bestRow[s]; staged,
+//   k_asof_keep   the pair-filter frame (hj_pairs.h) a third time: a live pair is kept iff its R row is bestRow[s]; staged,
 //                 claimed, flushed and marked on both sides as k_pairs_where does it.
 //
 // Both planes hold a maximum / minimum over a SET of pairs, so the result does not depend on the order of the list or on
@@ -32,7 +32,7 @@
 // What it does NOT do: no packed single pass for narrow values, no "nearest" of both sides, no tolerance window, no as-of
 // without an equality key; all pairs of an S row must be in ONE call (the planes are reset per call).
 
-#include "hj_device.h"
+#include "hj_columns.h"
 
 namespace hj {
 
@@ -141,7 +141,7 @@ k_asof_row(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR,
 }
 
 // pass 3: out, sMarks as k_pairs_where takes them (cursor[0]: kept pairs; cursor[1]: dropped pairs). The pair-filter frame
-// (hj_device.h) around one load of the bestRow plane per pair; nCols is the launch's and unused.
+// (hj_pairs.h) around one load of the bestRow plane per pair; nCols is the launch's and unused.
 __global__ void __launch_bounds__(kBlock)
 k_asof_keep(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
             uint32_t rRows, const uint32_t* __restrict__ bestRow, uint32_t nCols, PairsOutMarked out, RMarks sMarks)
@@ -232,27 +232,23 @@ void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs
                      uint32_t* sMarks, uint32_t* rMarks, uint64_t* info)
 {
     for (uint32_t i = 0; i < sRows; ++i) { bestVal[i] = 0; bestRow[i] = kNoRow; }
-    const auto dropped_pair = [&](uint64_t k) {
-        const uint32_t es = mapS[k], er = mapR[k];
-        return es == kNoRow || er == kNoRow || es - sRowBase >= sRows || er >= rRows;
-    };
     uint64_t kept = 0, dropped = 0;
     for (uint64_t k = 0; k < nPairs; ++k) {
-        if (dropped_pair(k)) { ++dropped; continue; }
+        if (dropped_pair(mapS[k], mapR[k], sRowBase, sRows, rRows)) { ++dropped; continue; }
         const uint32_t si = mapS[k] - sRowBase, ri = mapR[k];
-        const bool okS = !t.sValid || ((t.sValid[si >> 5] >> (si & 31u)) & 1u), okR = !t.rValid || ((t.rValid[ri >> 5] >> (ri & 31u)) & 1u);
+        const bool okS = !t.sValid || valid_bit(t.sValid, si), okR = !t.rValid || valid_bit(t.rValid, ri);
         const uint64_t b = where_elem_host(t.r, t.width, ri);
         if (!okS || !okR || !where_holds(t.type, t.width, t.op, where_elem_host(t.s, t.width, si), b)) continue;
         const uint64_t key = asof_key(t.type, t.width, t.op, b);
         if (bestRow[si] == kNoRow || key > bestVal[si] || (key == bestVal[si] && ri < bestRow[si])) { bestVal[si] = key; bestRow[si] = ri; }
     }
     for (uint64_t k = 0; k < nPairs; ++k) {
-        if (dropped_pair(k)) continue;
+        if (dropped_pair(mapS[k], mapR[k], sRowBase, sRows, rRows)) continue;
         const uint32_t es = mapS[k], er = mapR[k], si = es - sRowBase;
         if (bestRow[si] != er) continue;
         if (kept < capacity) { outS[kept] = es; outR[kept] = er; }
-        if (sMarks) sMarks[si >> 5] |= 1u << (si & 31u);
-        if (rMarks) rMarks[er >> 5] |= 1u << (er & 31u);
+        if (sMarks) set_mark_bit(sMarks, si);
+        if (rMarks) set_mark_bit(rMarks, er);
         ++kept;
     }
     if (info) { info[0] = kept; info[1] = kept < capacity ? kept : capacity; info[2] = 0; info[3] = dropped; }

@@ -38,7 +38,7 @@
 // owned blocks; phase B applies the rest. Which workgroup wins a claim changes
 // only how many tuples are deferred, never the result.
 
-#include "hj_device.h"
+#include "hj_table.h"
 
 #include <type_traits>
 
@@ -58,7 +58,7 @@ constexpr uint32_t kSeamDiv = 4;                 // seam tiles claim a block onl
 // starts in -- k_finalize_range makes blocks [lo, hi + 1] the stored range and the straddle flag wants ONE next block.
 constexpr uint32_t kOwnMaxProbeLen = kBlkSlots + 1;
 
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_umin(v); }      // DPP steps (hj_device.h), not LDS permutes
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_umin(v); }      // DPP steps (hj_common.h), not LDS permutes
 
 
 constexpr uint32_t kDrainAt = 64;                // run retry rounds once this many entries wait (<= 64)
@@ -66,7 +66,7 @@ constexpr int kQCap = 128;                        // per-wavefront retry queue e
 
 // owner[blk]: 0 = free, otherwise (workgroup id + 1).
 // KEY32 = false: R holds DataGen tuples (value = key); KEY32 = true: bare 32-bit keys (what the multi-GPU exchange
-// delivers). Either way index = idxBase + position and home slot = (key >> hshift) & mask (hj_device.h).
+// delivers). Either way index = idxBase + position and home slot = (key >> hshift) & mask (hj_common.h).
 //
 // rocprof showed the first versions VALU-issue bound (120 VALU + 90 SALU instructions per 64
 // tuples on unique keys, 5x that on duplicate-heavy `uniform`, LDS <10 % busy), so the insert is
@@ -79,7 +79,7 @@ constexpr int kQCap = 128;                        // per-wavefront retry queue e
 //               atomicMin) run on 64 queue entries at a time, so every round is dense regardless of
 //               how long individual probe/displacement chains get.
 // All per-tuple arithmetic is 32-bit: key = low word, slot numbers < 2^32, value = {key, index}.
-// HTM = true: the bucketised table of --algo htm (hj_device.h, home_slot_htm: every tuple of a bucket has the bucket's
+// HTM = true: the bucketised table of --algo htm (hj_common.h, home_slot_htm: every tuple of a bucket has the bucket's
 // first slot as its home, probeLen = 3); a tuple that runs out of budget is one of the reference's conflicts
 // (HTMHashBuild.hpp:181-183) and is appended, as (index << 32 | key), to this workgroup's slice of htmConflicts
 // (confSlice entries per workgroup; ccounts[workgroup] = how many) for the chain phase (hj_htm.hip).

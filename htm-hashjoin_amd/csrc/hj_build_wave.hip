@@ -31,7 +31,7 @@
 // All integer work on 8-byte tuples (or bare 32-bit keys); HBM traffic = R read once + every reachable slot
 // written once = the algorithmic 16 bytes per tuple of SURVEY.md 8d. No MFMA.
 
-#include "hj_device.h"
+#include "hj_table.h"
 
 #include <type_traits>
 
@@ -43,7 +43,7 @@ constexpr uint32_t kGranShift = kWvGranShift;       // retire granule: 128 slots
 constexpr uint32_t kGranSlots = 1u << kGranShift;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
-// ring and tile geometry come from hj_device.h, which describes them to the locality sampler
+// ring and tile geometry come from hj_table.h, which describes them to the locality sampler
 constexpr int kWvTile = (int)kWvTileTuples;
 constexpr int kWvPer = kWvTile / 64;                // tuples per lane per tile
 constexpr int kWvPf = 1;                            // tiles of R in flight per wavefront (register prefetch depth)
@@ -63,14 +63,14 @@ constexpr int kWvWpe = 4;
 // further workgroups resident.
 constexpr int kWvWordWpe = 7;
 constexpr int kWvWordRows = 4;                      // rows of a tile per batch of attempts + push rows on that road
-// kWvWavesPerCu resident wavefronts per CU, chunks = resident wavefronts x up to kWvMaxRounds rounds (hj_device.h; wave_layout below)
+// kWvWavesPerCu resident wavefronts per CU, chunks = resident wavefronts x up to kWvMaxRounds rounds (hj_table.h; wave_layout below)
 constexpr uint32_t kWvMinChunk = 32768;             // tuples: a second round of workgroups only while chunks stay this long
 constexpr uint32_t kWvShortestChunk = 4 * kWvTileTuples;   // tuples: no chunk is cut shorter
 // issue priorities rotate in time among a CU's workgroup slots; period = 2^shift ticks of the 100 MHz clock (10.24 us)
 constexpr uint32_t kWvPrioShift = 10;
 static_assert(kWvQCap >= 128 && (kWvQCap & (kWvQCap - 1)) == 0, "FIFO ring: a power of two that takes one full step on top of < 64 waiting entries");
 constexpr size_t kWvLdsBytes = (size_t)kWvWaves * (kWvWin * sizeof(uint64_t) + 3 * kWvQCap * sizeof(uint32_t));
-// slot-code road: the ring holds 4-byte ring words (RingWord, hj_device.h) and a queue entry is (pos, word)
+// slot-code road: the ring holds 4-byte ring words (RingWord, hj_table.h) and a queue entry is (pos, word)
 // ring granules on that road: 1024 slots in 4 KiB. 16 granules were measured against 8 at 2^30 `uniform` (profiles/ring_words.md
 // section 2): the deferred tail shrinks from 203 to 41 us, the build kernel grows by 320, the step is slower
 constexpr uint32_t kWvWordGran = 8;
@@ -241,7 +241,7 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
 }
 
 // ---- the build ------------------------------------------------------------------------------------------------
-// COMPACT (the fast path of the open-addressing table, hj_device.h "table formats"): the ring still holds (index << 32 | key),
+// COMPACT (the fast path of the open-addressing table, hj_table.h "table formats"): the ring still holds (index << 32 | key),
 // but what leaves for HBM is the KEY WORD alone -- 4 bytes per slot instead of 8, and the probe reads 4 bytes per slot too.
 // The index words exist only to order the inserts, and inside a wavefront's ring they have done that by the time a granule
 // retires; nothing after this kernel may therefore need them: there is no deferred phase. Every way a tuple used to get
@@ -264,7 +264,7 @@ k_wave_bounds_scan(const uint32_t* __restrict__ raw, uint32_t nChunks, uint32_t 
 // (k_wave_deferred<PLANAR>, k_wave_fixup). Key 0xFFFFFFFF cannot live in a 4-byte table: Counters::planarFail, and the
 // packed build redoes it.
 // CODES (PLANAR on 8-byte tuples only, mode kWaveCodes): the key run of a retiring granule is 128 code bytes instead of 512
-// bytes of keys (SlotCode, hj_device.h) -- one 2-byte store per lane, one 128-byte line per instruction; the index run, the
+// bytes of keys (SlotCode, hj_table.h) -- one 2-byte store per lane, one 128-byte line per instruction; the index run, the
 // deferred walks and the log stay what they are. Any key has a code when the table is large enough (the host's rule);
 // otherwise (forced road) a tile holding a key at or above keyLimit raises Counters::planarFail bit 2. Key 0xFFFFFFFF is a
 // key like any other here: the empty pattern is a code no key produces.
@@ -1167,7 +1167,7 @@ k_wave_fixup(const DeferredEntry* __restrict__ queue, const uint32_t* __restrict
     }
 }
 
-// After k_build_wave: the valid slot range (hj_device.h, Counters) = the owned stretch [ownLo, ownHiEx) joined
+// After k_build_wave: the valid slot range (hj_common.h, Counters) = the owned stretch [ownLo, ownHiEx) joined
 // with the blocks deferred tuples start from (+1: a probe walk spills at most probeLen - 1 slots). If it reaches
 // the table's end the whole table is made valid (set_valid_range). One wavefront. (Round 3 tried this fold inside
 // k_wave_fill_edges, every workgroup for itself, to save the launch: 4 us at 2^22 -- and 55 us at 2^30, with 128 or

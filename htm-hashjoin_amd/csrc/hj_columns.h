@@ -1,0 +1,303 @@
+// hj_columns.h -- the relational layer's column code: validity and mark bits, gather, key columns, groups, join
+// conditions and as-of (how two elements compare and order), sort keys, and the aggregates over a pair list.
+// Column descriptors as the kernels take them, the element helpers host and device share, and the launchers.
+#pragma once
+
+#include "hj_common.h"
+#include "hj_pairs.h"
+
+namespace hj {
+
+// ---- validity and mark bits: one bit per row, bit (i & 31) of word i >> 5 ----
+// THE test of a bit: of a word that is held already, and of a plane. Every host loop and the kernels of hj_agg, hj_gather,
+// hj_sort and hj_prj_agg go through them. Four device functions keep the expression written out, because through the
+// helpers their kernels compile to other code (registers, block placement; tools/asm_diff.py): verify_col2 / verify_varlen
+// (k_pairs_verify2), the term loops of k_pairs_where and asof_pairs, and key_rows_equal (k_groups_insert); so does the
+// device branch of key_valid_bits, which reads eight words once per wavefront.
+__host__ __device__ __forceinline__ bool word_bit(uint32_t word, uint32_t i) { return (word >> (i & 31u)) & 1u; }
+__host__ __device__ __forceinline__ bool valid_bit(const uint32_t* plane, uint32_t i) { return word_bit(plane[i >> 5], i); }
+// the host loops' mark of row i (the kernels mark with atomics: mark_r_row)
+inline void set_mark_bit(uint32_t* plane, uint32_t i) { plane[i >> 5] |= 1u << (i & 31u); }
+
+// ---- gather through a row map (defined in hj_gather.hip) ---------------------
+// One column of hj_gather_dev as the kernel takes it (hj_gather_col, include/htm_hashjoin.h, field for field), and the
+// columns of a call, passed by value in the kernel arguments.
+constexpr uint32_t kGatherMaxCols = 8;        // HJ_GATHER_MAX_COLS
+struct GatherCol { const void* src; void* dst; uint32_t width, reserved; uint64_t fill[2]; };
+struct GatherCols { GatherCol col[kGatherMaxCols]; };
+// dst_c[k] = src_c[map[k] - rowBase] for k in [0, nRows) and c in [0, nCols); an entry that is HJ_NO_ROW, or that lies at or
+// behind srcRows once the base is off, reads nothing and gives the column's fill. valid (may be null): one bit per row,
+// whole words up to ceil(nRows / 32). counts[0] += the HJ_NO_ROW entries, counts[1] += the out-of-range ones. The caller
+// has checked widths, alignment and nRows, srcRows <= 2^32 - 1.
+hipError_t launch_gather(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols& cols, uint32_t nCols,
+                         uint32_t* valid, unsigned long long* counts, hipStream_t s);
+// The same on columns in the Arrow layout (hj_gather_col2, include/htm_hashjoin.h, field for field; defined in
+// hj_gather_cols.hip): a source validity plane and 32-bit offsets per column, both optional. Columns that are fixed and
+// have neither plane go through launch_gather as they are. work: the context's workspace for the variable-length columns
+// of a call, which run one behind the other -- gather2_work_words(nRows) 32-bit words: the scan's own words, then one
+// 64-bit partial sum per workgroup. totals: kGatherMaxCols 64-bit words, written here (0 for a fixed column): the bytes
+// the rows of column c take. The caller has checked what the header says hj_gather2_dev refuses.
+struct GatherCol2 { const void* src; void* dst; const uint32_t* srcOff; uint32_t* dstOff; const uint32_t* srcValid; uint32_t* dstValid;
+                    uint64_t capacity; uint32_t width, flags; uint64_t fill[2]; };
+struct GatherCols2 { GatherCol2 col[kGatherMaxCols]; };
+size_t gather2_work_words(uint64_t nRows);
+hipError_t launch_gather2(const uint32_t* map, uint64_t nRows, uint32_t rowBase, uint64_t srcRows, const GatherCols2& cols, uint32_t nCols,
+                          uint32_t* valid, unsigned long long* counts, unsigned long long* totals, uint32_t* work, hipStream_t s);
+
+// ---- joins on real key columns (defined in hj_keys.hip) ----------------------
+// The key columns of a call as the kernels take them, by value in the kernel arguments: the hash reads one side
+// (KeyCols2), the verify step both (KeyCols2SR). They are hj_key_col2's (include/htm_hashjoin.h): per column and side the
+// values (fixed width) or the bytes buffer (width 0), the rows + 1 offsets of a variable-length column (else null) and the
+// validity plane (null: no NULLs); flags: HJ_KEY_NULLS_EQUAL. An hj_key_col is the same column with null offsets, null
+// planes and flags 0: hj_key_hash_dev, hj_key_hash_host and hj_pairs_verify_dev fill the descriptor that way.
+// launch_key_hash2: out[i] = the join word of row i (the header's hash over the row's key columns, & mask) as an 8-byte
+// tuple. mask is the effective one (never 0). nRows is also what bounds the validity words the hash reads: ceil(nRows / 32).
+// launch_pairs_verify2: candidate pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose key columns are equal as the header
+// defines it, to `out` as the pairs kernels write theirs (out.cursor: two 64-bit words, zeroed before the launch: kept
+// pairs, then the candidates dropped as HJ_NO_ROW or outside sRows / rRows, which are never dereferenced). Every kept pair
+// sets bit s of sMarks and bit r of rMarks (RMarks' layout; either may be null).
+// The caller has checked what the header says the entry points refuse, and nRows, nPairs <= 2^32 - 1.
+constexpr uint32_t kKeyMaxCols = 4;           // HJ_KEY_MAX_COLS
+struct KeyCols2 { const void* p[kKeyMaxCols]; const uint32_t* off[kKeyMaxCols]; const uint32_t* valid[kKeyMaxCols];
+                  uint32_t width[kKeyMaxCols], flags[kKeyMaxCols]; };
+struct KeyCols2SR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; const uint32_t* sOff[kKeyMaxCols]; const uint32_t* rOff[kKeyMaxCols];
+                    const uint32_t* sValid[kKeyMaxCols]; const uint32_t* rValid[kKeyMaxCols]; uint32_t width[kKeyMaxCols], flags[kKeyMaxCols]; };
+constexpr uint32_t kKeyNullsEqual = 1u;       // HJ_KEY_NULLS_EQUAL
+hipError_t launch_key_hash2(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s);
+void key_hash2_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out);   // the same body in a host loop
+hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                                uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                                hipStream_t s);
+
+// ---- rows of one table grouped by their key columns (defined in hj_groups.hip) ----
+// launch_key_groups: rep[i] = the lowest row with row i's key (kNoRow: NULL-keyed), firstRows = the rows with rep[i] == i,
+// ascending, cut at `capacity` (null with capacity 0), group[i] = the position of rep[i] among them (null: not wanted).
+// work: key_groups_work_bytes(nRows) bytes -- the table of key_groups_slots(nRows) 8-byte slots, filled with EMPTY here on
+// s, the first-row plane, its popcounts and their scan, the sweep's counts; key_groups_total: where the number of groups
+// lies in it after the call (one 32-bit word). ctr: four 64-bit words, zeroed here -- probe steps beyond the home slot, word
+// collisions, NULL-keyed rows, the failure word. mask is the effective one (never 0). The caller has checked what the
+// header says the entry point refuses, and nRows <= 2^32 - 2.
+uint64_t key_groups_slots(uint64_t nRows);
+size_t key_groups_work_bytes(uint64_t nRows);
+const uint32_t* key_groups_total(const void* work, uint64_t nRows);
+hipError_t launch_key_groups(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint32_t* rep, uint32_t* group,
+                             uint32_t* firstRows, uint64_t capacity, void* work, unsigned long long* ctr, hipStream_t s);
+// the same hash and compare bodies around a sequential table; out: hj_key_groups_host's
+void key_groups_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint32_t* rep, uint32_t* group, uint32_t* firstRows,
+                     uint64_t capacity, uint64_t out[8]);
+
+// ---- join conditions beyond equality (defined in hj_where.hip) ----------------
+// The terms of a call as the kernel takes them, by value in the kernel arguments (hj_where_term, include/htm_hashjoin.h):
+// term t holds for the pair (s, r) when s[t][s] op[t] r[t][r], both elements of width[t] bytes read as type[t], and neither
+// is NULL (sValid / rValid: the validity plane of that side, null: no NULLs).
+constexpr uint32_t kWhereMaxTerms = 4;        // HJ_WHERE_MAX_TERMS
+constexpr uint32_t kCmpEq = 0, kCmpNe = 1, kCmpLt = 2, kCmpLe = 3, kCmpGt = 4, kCmpGe = 5;     // hj_cmp_op
+constexpr uint32_t kValUint = 0, kValInt = 1, kValFloat = 2;                                  // hj_val_type
+struct WhereTerms { const void* s[kWhereMaxTerms]; const void* r[kWhereMaxTerms]; const uint32_t* sValid[kWhereMaxTerms];
+                    const uint32_t* rValid[kWhereMaxTerms]; uint32_t width[kWhereMaxTerms], type[kWhereMaxTerms], op[kWhereMaxTerms]; };
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `out` as launch_pairs_verify2 writes its kept pairs
+// (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the pairs dropped as HJ_NO_ROW or outside sRows /
+// rRows, which are never dereferenced); the marks as there. The caller has checked the terms and nPairs <= 2^32 - 1.
+hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                              uint32_t rRows, const WhereTerms& terms, uint32_t nTerms, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
+                              hipStream_t s);
+// the same pairs in a host loop over host pointers, the kept ones in input order; info: kept, written, 0, dropped (may be null)
+void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
+                      const WhereTerms& terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
+                      uint32_t* rMarks, uint64_t* info);
+
+// What the condition step (hj_where.hip) and the as-of step (hj_asof.hip) share: how two elements compare, how one orders,
+// and a term's loads for the lane's pairs of the pair-filter frame.
+// the raw word of a FLOAT element as a double: binary32 widens exactly
+__host__ __device__ __forceinline__ double where_real(uint64_t raw, uint32_t width)
+{
+    return width == 4u ? (double)__builtin_bit_cast(float, (uint32_t)raw) : __builtin_bit_cast(double, raw);
+}
+
+// Whether  a OP b  holds, a and b the zero-extended raw words of two valid elements of `width` bytes read as `type`.
+// Unordered (a NaN on either side): lt and eq are false, so EQ, LT and LE fail by themselves and NE holds.
+__host__ __device__ __forceinline__ bool where_holds(uint32_t type, uint32_t width, uint32_t op, uint64_t a, uint64_t b)
+{
+    bool lt, eq, un = false;
+    if (type == kValFloat) {
+        const double x = where_real(a, width), y = where_real(b, width);
+        lt = x < y; eq = x == y; un = x != x || y != y;
+    } else {
+        // INT: sign-extended from its width, then the sign bit flipped -- the order of the signed values as unsigned ones
+        const uint32_t sh = type == kValInt ? 64u - 8u * width : 0u;
+        const uint64_t flip = type == kValInt ? 1ull << 63 : 0ull;
+        const uint64_t x = (uint64_t)((int64_t)(a << sh) >> sh) ^ flip, y = (uint64_t)((int64_t)(b << sh) >> sh) ^ flip;
+        lt = x < y; eq = x == y;
+    }
+    switch (op) {
+        case kCmpEq: return eq;
+        case kCmpNe: return !eq;
+        case kCmpLt: return lt;
+        case kCmpLe: return lt || eq;
+        case kCmpGt: return !(lt || eq || un);
+        default: return !(lt || un);                                  // kCmpGe
+    }
+}
+
+// The order key of the as-of step: the zero-extended raw word of a valid element that is no NaN -> an unsigned 64-bit word
+// that orders as the values do and is equal exactly where where_holds calls two values equal. Integers: where_holds's
+// sign-extend and flip. Floats: widened to double, -0.0 taken for +0.0, then the bits folded -- a negative's all
+// complemented, a positive's sign bit set -- so that negatives order below positives. The forward ops (LT, LE: the SMALLEST
+// R value is wanted) complement the key: every kernel takes a maximum.
+__host__ __device__ __forceinline__ uint64_t asof_key(uint32_t type, uint32_t width, uint32_t op, uint64_t raw)
+{
+    uint64_t key;
+    if (type == kValFloat) {
+        double x = where_real(raw, width);
+        if (x == 0.0) x = 0.0;                                        // -0.0 == 0.0: one key for both
+        const uint64_t bits = __builtin_bit_cast(uint64_t, x);
+        key = (bits >> 63) ? ~bits : bits | (1ull << 63);
+    } else {
+        const uint32_t sh = type == kValInt ? 64u - 8u * width : 0u;
+        key = (uint64_t)((int64_t)(raw << sh) >> sh) ^ (type == kValInt ? 1ull << 63 : 0ull);
+    }
+    return (op == kCmpLt || op == kCmpLe) ? ~key : key;
+}
+
+// One term's loads for the lane's pairs: both elements of every pair, and with kValid the validity word of either side
+// (null plane: all valid), all of them before the first compare. The loads are unconditional -- see the pair-filter
+// frame for why. The switch on the width around it (1 / 2 / 4 / 8, uniform) is written out in both callers, k_pairs_where and
+// asof_pairs: as one where_load_width<kValid> it left k_pairs_where's code as it was and placed the blocks of both
+// k_asof_best instances differently (tools/asm_diff.py).
+template <class E, bool kValid>
+__device__ __forceinline__ void where_load(const void* sCol, const void* rCol, const uint32_t* sValid, const uint32_t* rValid,
+                                           const uint32_t (&si)[kFilterLanePairs], const uint32_t (&ri)[kFilterLanePairs],
+                                           uint64_t (&a)[kFilterLanePairs], uint64_t (&b)[kFilterLanePairs],
+                                           uint32_t (&vs)[kFilterLanePairs], uint32_t (&vr)[kFilterLanePairs])
+{
+    if constexpr (kValid) {
+#pragma unroll
+        for (uint32_t j = 0; j < kFilterLanePairs; ++j) { vs[j] = sValid ? sValid[si[j] >> 5] : ~0u; vr[j] = rValid ? rValid[ri[j] >> 5] : ~0u; }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kFilterLanePairs; ++j) { a[j] = static_cast<const E*>(sCol)[si[j]]; b[j] = static_cast<const E*>(rCol)[ri[j]]; }
+    __builtin_amdgcn_sched_barrier(0);                                // no compare moves up between the loads: it would wait there
+}
+
+// A pair the host loops drop as the pair-filter frame does: an HJ_NO_ROW entry, or a row outside its relation
+inline bool dropped_pair(uint32_t es, uint32_t er, uint32_t sRowBase, uint32_t sRows, uint32_t rRows)
+{
+    return es == kNoRow || er == kNoRow || es - sRowBase >= sRows || er >= rRows;
+}
+
+// element i of a column of `width` bytes, zero-extended (the host loops)
+inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
+{
+    uint64_t v = 0;
+    memcpy(&v, static_cast<const uint8_t*>(col) + (size_t)i * width, width);      // little-endian: the low bytes
+    return v;
+}
+
+// ---- as-of joins: one best match per S row (defined in hj_asof.hip) -----------
+// The term of a call as the kernels take it (hj_asof_term, include/htm_hashjoin.h): the pair (s, r) is eligible when
+// s[s] op r[r] holds as a term of the condition step does, op one of LT, LE, GT, GE.
+struct AsofTerm { const void *s, *r; const uint32_t *sValid, *rValid; uint32_t width, type, op; };
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> per S row the eligible pair with the largest asof_key of its R element, ties to
+// the lowest R row, to `out` as launch_pairs_where writes its kept pairs (out.cursor: two 64-bit words, zeroed before the
+// launch: kept pairs, pairs dropped); the marks as there, set by the kept pairs alone. bestVal (sRows 64-bit words) and
+// bestRow (sRows words) are initialised here, on s: after the call bestRow[i] is the R row kept for S row i or kNoRow,
+// bestVal[i] its key (0 without one). The caller has checked the term and nPairs, sRows, rRows <= 2^32 - 1.
+hipError_t launch_pairs_asof(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
+                             uint32_t rRows, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, PairsOut out,
+                             uint32_t* sMarks, uint32_t* rMarks, hipStream_t s);
+// the same in host loops over host pointers (asof_key and where_holds are the kernels' own), the kept pairs in input
+// order; info: kept, written, 0, dropped (may be null)
+void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
+                     const AsofTerm& term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
+                     uint32_t* sMarks, uint32_t* rMarks, uint64_t* info);
+
+// ---- rows in the order of their columns (defined in hj_sort.hip) --------------
+// The order key of the sort: the zero-extended raw word of a valid element of `width` bytes read as `type` -> an unsigned
+// word of 8 * width bits that orders as the header states it, equal exactly where two elements tie. UINT: the word. INT:
+// the sign bit flipped within the width. FLOAT: folded as asof_key folds, in the element's own width -- a negative's bits all
+// complemented, a positive's sign bit set, -0.0 taken for +0.0 -- and every NaN, whatever its sign or payload, all ones:
+// above +inf. HJ_SORT_DESC complements the word within the width, NaN included. A NULL's key is 0: the caller's business.
+constexpr uint32_t kSortMaxCols = 4;          // HJ_SORT_MAX_COLS
+constexpr uint32_t kSortDesc = 1u, kSortNullsFirst = 2u;      // HJ_SORT_DESC, HJ_SORT_NULLS_FIRST
+__host__ __device__ __forceinline__ uint64_t sort_key(uint32_t type, uint32_t width, uint32_t flags, uint64_t raw)
+{
+    const uint32_t bits = 8u * width;
+    const uint64_t top = 1ull << (bits - 1u), mask = top | (top - 1ull);
+    uint64_t key = raw & mask;
+    if (type == kValInt) key ^= top;
+    else if (type == kValFloat) {
+        const uint64_t mag = key & (top - 1ull), inf = width == 4u ? 0x7F800000ull : 0x7FF0000000000000ull;
+        if (mag > inf) key = mask;                                    // a NaN
+        else if (mag == 0ull) key = top;                              // -0.0 == 0.0: one key for both
+        else key = (key & top) ? ~key & mask : key | top;
+    }
+    return (flags & kSortDesc) ? ~key & mask : key;
+}
+// The columns of a call as the kernels take them (hj_sort_col, include/htm_hashjoin.h); cols[0] is the most significant.
+struct SortCols { const void* p[kSortMaxCols]; const uint32_t* valid[kSortMaxCols]; uint32_t width[kSortMaxCols], type[kSortMaxCols], flags[kSortMaxCols]; };
+// How a pass cuts nRows records of keyBytes-byte keys: a workgroup ranks tileRows records at a time and owns chunkRows (a
+// multiple of it) in a pass; the workspace is two key planes and two row planes of nRows, a histogram of 256 words per
+// chunk -- at most 4096 chunks at any nRows: 4 MiB -- and its scan sums. bytes is monotone in nRows.
+struct SortLayout { uint32_t tileRows, chunkRows, chunks; size_t keyPlane, rowPlane, histBytes, bytes; };
+SortLayout sort_layout(uint64_t nRows, uint32_t keyBytes);
+uint32_t sort_key_bytes(const SortCols& cols, uint32_t nCols);       // 8 with an 8-byte column, else 4
+uint32_t sort_passes(const SortCols& cols, uint32_t nCols);          // one per element byte, one more per validity plane
+// perm[0 .. nRows) = the rows in the order of the columns, stable. work: sort_layout(nRows, sort_key_bytes(..)).bytes. The
+// caller has checked what the header says the entry point refuses. nRows 0 enqueues nothing.
+hipError_t launch_sort_rows(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm, void* work, hipStream_t s);
+void sort_rows_host(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm);     // sort_key around std::stable_sort
+
+// ---- aggregating joins: COUNT / SUM / MIN / MAX per group row (hj_prj_agg.hip, hj_agg.hip) ----
+// The columns of a call as the kernels take them, by value in the kernel arguments: the ops (hj_agg_spec; sgn: HJ_AGG_SIGNED),
+// the sources (hj_agg_src) and the accumulator planes. Every accumulator is 64 bits wide.
+constexpr uint32_t kAggMaxCols = 4;           // HJ_AGG_MAX_COLS
+constexpr uint32_t kAggCount = 0, kAggSum = 1, kAggMin = 2, kAggMax = 3;      // hj_agg_op
+struct AggOps { uint32_t op[kAggMaxCols], width[kAggMaxCols], sgn[kAggMaxCols]; };
+struct AggSrc { const void* p[kAggMaxCols]; const uint32_t* valid[kAggMaxCols]; };
+struct AggPlanes { unsigned long long* count; unsigned long long* acc[kAggMaxCols]; };
+struct AggRowsOut { unsigned long long* col[kAggMaxCols]; unsigned long long* count; };
+// the identity of a column's op: what an accumulator holds before its first value
+__device__ __forceinline__ unsigned long long agg_identity(uint32_t op, uint32_t sgn)
+{
+    if (op == kAggMin) return sgn ? 0x7FFFFFFFFFFFFFFFull : 0xFFFFFFFFFFFFFFFFull;
+    if (op == kAggMax) return sgn ? 0x8000000000000000ull : 0ull;
+    return 0ull;
+}
+// acc op= v, without a returned value; SCOPE: the workgroup for an LDS entry, the agent for a global one
+template <int SCOPE>
+__device__ __forceinline__ void agg_apply(unsigned long long* acc, uint32_t op, uint32_t sgn, unsigned long long v)
+{
+    if (op <= kAggSum) __hip_atomic_fetch_add(acc, v, __ATOMIC_RELAXED, SCOPE);
+    else if (op == kAggMin) {
+        if (sgn) __hip_atomic_fetch_min(reinterpret_cast<long long*>(acc), (long long)v, __ATOMIC_RELAXED, SCOPE);
+        else __hip_atomic_fetch_min(acc, v, __ATOMIC_RELAXED, SCOPE);
+    } else {
+        if (sgn) __hip_atomic_fetch_max(reinterpret_cast<long long*>(acc), (long long)v, __ATOMIC_RELAXED, SCOPE);
+        else __hip_atomic_fetch_max(acc, v, __ATOMIC_RELAXED, SCOPE);
+    }
+}
+// a op b, for the reductions in registers that run in front of an atomic
+__device__ __forceinline__ unsigned long long agg_combine(uint32_t op, uint32_t sgn, unsigned long long a, unsigned long long b)
+{
+    if (op <= kAggSum) return a + b;
+    if (op == kAggMin) return sgn ? ((long long)a < (long long)b ? a : b) : (a < b ? a : b);
+    return sgn ? ((long long)a > (long long)b ? a : b) : (a > b ? a : b);
+}
+// the 64-bit value of element i of a column: COUNT brings 1, a 4-byte element is sign- or zero-extended
+__device__ __forceinline__ unsigned long long agg_value(const void* __restrict__ src, uint32_t op, uint32_t width, uint32_t sgn, uint32_t i)
+{
+    if (op == kAggCount) return 1ull;
+    if (width == 8) return static_cast<const unsigned long long*>(src)[i];
+    const uint32_t w = static_cast<const uint32_t*>(src)[i];
+    return sgn ? (unsigned long long)(long long)(int32_t)w : (unsigned long long)w;
+}
+
+// The reduction over a pair list (hj_agg.hip): for pair k with g = mapG[k] - gBase, v = mapV[k] - vBase: acc[c][g] op= src[c][v],
+// count[g] += 1 (count may be null, and mapV when no column reads a value). An entry that is HJ_NO_ROW or out of range on
+// either side is never dereferenced: counts[1] += 1, else counts[0] += 1 (two 64-bit words, zeroed before the launch).
+struct PairAggCols { AggSrc src; AggOps ops; unsigned long long* acc[kAggMaxCols]; };
+hipError_t launch_pairs_agg(const uint32_t* mapG, const uint32_t* mapV, uint64_t nPairs, uint32_t gBase, uint32_t gRows, uint32_t vBase,
+                            uint32_t vRows, const PairAggCols& cols, uint32_t nCols, unsigned long long* count, unsigned long long* counts,
+                            hipStream_t s);
+
+}  // namespace hj

@@ -25,11 +25,18 @@
 // or behind ceil(nRows / 32) are not written; no atomics. NULL and out-of-range rows are counted per wavefront with
 // popcounts of the ballots, and a workgroup adds them to the two device counters once.
 //
+// k_gather's map prologue, plane store and count epilogue are a WRITTEN-OUT COPY of take_rows / store_plane_step / add_counts,
+// which its three siblings further down call (a change to one is made in both). Put on the helpers, the twenty k_gather
+// instances compile to other code (mostly three VGPRs fewer; k_gather<16, 8> 137 VGPRs for 136 and two spilled SGPRs; no
+// scratch, no wavefront lost), and measured parent, change, parent, change at 2^27 rows the medians of three of the
+// thirty-six configurations lay above the parent's slowest single launch -- s_sorted, one 16-byte column, in both runs:
+// 832 and 821 us against 819 us (profiles/gather.md, "k_gather on the shared helpers"). So the text stays.
+//
 // What it does NOT do: the map is neither sorted nor bucketed before the gather. A random map (the R side of a join on a
 // shuffled R) therefore fetches one cache line per element -- the amplification the counting probe shows under a
 // scattered S -- and nothing here hides it.
 
-#include "hj_device.h"
+#include "hj_columns.h"
 
 #include <utility>
 
@@ -315,7 +322,7 @@ __device__ __forceinline__ void element_bits(const uint32_t* __restrict__ srcVal
         if (srcValid && ok[j]) word[j] = srcValid[idx[j] >> 5];
     }
 #pragma unroll
-    for (uint32_t j = 0; j < kGatherLaneRows; ++j) el[j] = ok[j] && ((word[j] >> (idx[j] & 31u)) & 1u);
+    for (uint32_t j = 0; j < kGatherLaneRows; ++j) el[j] = ok[j] && word_bit(word[j], idx[j]);
 }
 
 // the wavefronts' NULL and out-of-range rows -> the two device counters, once per workgroup (k_gather's epilogue)

@@ -1,6 +1,6 @@
 // hj_groups.hip -- the rows of ONE table grouped by their key columns for gfx950 (MI355X): hj_key_groups_dev /
-// hj_key_groups_host. Included by hj_keys.hip: the hash is its key_hash2_rows, the element compare its same_bytes and its
-// var_* word walk.
+// hj_key_groups_host. The hash is the join's key_hash2_rows, the element compare its same_bytes and its var_* word walk:
+// hj_keys_impl.h, which this file shares with hj_keys.hip.
 //
 // What comes out: rep[i] = the lowest row whose key equals row i's (column equality as in the verify step), the first rows
 // (rep[i] == i) ascending, and group[i] = the position of rep[i] among them -- a dense id in order of first occurrence.
@@ -50,6 +50,8 @@
 // it sets the failure word (hj_key_groups_info out[7]) and stops with HJ_NO_ROW.
 // What it does NOT do: the table lives for one call (no keys arriving in slices); the rows of a lane are walked one after
 // the other, so a lane's probes overlap only with those of the other wavefronts.
+
+#include "hj_keys_impl.h"
 
 namespace hj {
 

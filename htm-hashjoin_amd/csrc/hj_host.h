@@ -4,7 +4,11 @@
 #pragma once
 
 #include "../../include/htm_hashjoin.h"
-#include "hj_device.h"
+#include "hj_common.h"
+#include "hj_table.h"
+#include "hj_pairs.h"
+#include "hj_columns.h"
+#include "hj_prj.h"
 #include "hj_rand.h"
 
 #include <string>
@@ -24,7 +28,7 @@ enum Buf {
     B_HTM_OVF_COUNT, B_HTM_OVF_BASE, B_HTM_SCAN,
     B_HTM_OVERFLOW,             // overflow buckets (index 0 unused)
     B_PAIRS_CURSOR,             // materialising probe (hj_probe_join_dev): the output cursor, then HJ_JOIN_LEFT's unmatched S tuples
-    B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_device.h)
+    B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_pairs.h)
     B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
     B_GATHER_CTR,               // hj_gather_dev: the NULL rows and the out-of-range entries of the last call (two 64-bit words)
     B_GATHER2_CTR,              // hj_gather2_dev: the same two words of ITS last call, then HJ_GATHER_MAX_COLS 64-bit totals: the bytes of each column
@@ -93,7 +97,7 @@ struct hj_ctx {
     struct Op {
         uint64_t rSize = 0, sSize = 0;
         uint64_t tableSize = 0;                 // live table (2*rSize; htm: 4 slots per bucket) of the last build, in buf[B_TABLE]
-        uint32_t hshift = 0;                    // home-slot shift of that table (hj_device.h); 0 unless it is a radix shard
+        uint32_t hshift = 0;                    // home-slot shift of that table (hj_common.h); 0 unless it is a radix shard
         uint32_t algoUsed = 0, variantUsed = 1;
         bool built = false;
         bool probeStartsAtBuildEnd = false;     // the probe was enqueued right behind the build on the library's own stream: EV_BUILD1 is its start

@@ -11,7 +11,7 @@
 //            (count = tuple slots in use, no chain). Overflow buckets use the same format in a second array (index 0
 //            unused, as in the reference). Buckets outside the slot range the build defined are never written.
 //   build    the three tuple slots are filled with the index-priority protocol of the open-addressing table
-//            (hj_kernels.hip) with a probe budget of 3 and home slot = the bucket's first slot (hj_device.h,
+//            (hj_kernels.hip) with a probe budget of 3 and home slot = the bucket's first slot (hj_common.h,
 //            home_slot_htm): whatever the scheduling, a bucket ends up with its three lowest-indexed tuples in
 //            index order -- what a single thread walking R in input order stores (:177-179) -- and the tuples
 //            that run out of budget are exactly that thread's conflicts. Fast path: k_build_wave<HTM>
@@ -31,7 +31,7 @@
 //
 // All integer work, HBM bound; no MFMA.
 
-#include "hj_device.h"
+#include "hj_table.h"
 
 namespace hj {
 
@@ -168,7 +168,7 @@ k_htm_link(uint64_t* __restrict__ table, uint32_t numBuckets, const unsigned int
 // Anything that does not fit (a slice spanning more than kChainCountCap buckets: sparse keys; a part of more than kChainCap
 // buckets or image slots: many duplicates; a conflict outside its slice's range) raises Counters::htmChainBail, and the
 // host redoes the build without routing and chains with the generic kernels.
-// The caps (kChainCountCap, kChainCap, kChainMaxParts) and the table of causes the word is a mask of: hj_device.h.
+// The caps (kChainCountCap, kChainCap, kChainMaxParts) and the table of causes the word is a mask of: hj_table.h.
 __device__ __forceinline__ uint32_t chain_block_exclusive_scan(uint32_t v, uint32_t* wsum /*[kChainThreads / 64]*/, uint32_t& total)
 {
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -337,7 +337,7 @@ k_htm_probe(const uint64_t* __restrict__ S, uint64_t n, const uint64_t* __restri
             const uint64_t* __restrict__ overflow, Counters* __restrict__ ctr)
 {
     unsigned long long matches = 0;
-    // buckets outside the slots the build defined were never written and hold no tuple (hj_device.h, Counters)
+    // buckets outside the slots the build defined were never written and hold no tuple (hj_common.h, Counters)
     const uint64_t defLo = ctr->validLo, defHi = ctr->validHiEx + 512;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
         const uint64_t s = S[i];

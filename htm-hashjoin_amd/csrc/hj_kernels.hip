@@ -22,7 +22,7 @@
 //
 // All integer work, HBM/atomic bound; no MFMA.
 
-#include "hj_device.h"
+#include "hj_table.h"
 
 #include <type_traits>
 
@@ -70,7 +70,7 @@ void launch_fill_empty(uint64_t* table, uint64_t nSlots, Gate gate, hipStream_t 
 // build
 // ---------------------------------------------------------------------------
 // Inserts `mine` = (index << 32 | key) starting at slot `pos` with `budget` probes left. The home slot
-// of a key is (key >> hshift) & homeMask, homeMask = tableSize - 1 (hj_device.h).
+// of a key is (key >> hshift) & homeMask, homeMask = tableSize - 1 (hj_common.h).
 __device__ __forceinline__ void insert_priority(uint64_t* __restrict__ table, uint64_t homeMask,
                                                 uint32_t hshift, uint32_t probeLen,
                                                 uint64_t mine, uint64_t pos, uint32_t budget,
@@ -170,7 +170,7 @@ __device__ __forceinline__ uint32_t probe_one(uint64_t sk, const uint64_t* __res
                                               uint64_t validLo, uint64_t validHiEx)
 {
     // a tuple with payload bits set can match nothing; outside the valid range no stored tuple can
-    // have this home slot (hj_device.h, Counters)
+    // have this home slot (hj_common.h, Counters)
     const uint32_t key = (uint32_t)sk;
     const uint64_t home = home_slot(key, hshift, mask);
     if ((sk >> 32) != 0 || home < validLo || home >= validHiEx) return 0;
@@ -357,7 +357,7 @@ __device__ __forceinline__ void probe_body(const void* __restrict__ Sv, uint64_t
     flush_counter(&counter_shard(ctr)->foreign, foreign);
 }
 
-// ---- slot codes (Counters::tableFormat == kFormatCodes1): one byte per slot, SlotCode in hj_device.h ----
+// ---- slot codes (Counters::tableFormat == kFormatCodes1): one byte per slot, SlotCode in hj_common.h ----
 // The walk of probe_one on code bytes: slot home + j holds the key iff its code is (hi << dbits) | j. The identity hash
 // (the road is taken by tuple builds only: hshift 0). A key no code can hold (forced road) matches nothing.
 __device__ __forceinline__ uint32_t probe_one_codes(uint64_t sk, const uint8_t* __restrict__ codes, uint64_t mask, uint32_t probeLen,

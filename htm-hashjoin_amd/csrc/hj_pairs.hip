@@ -24,14 +24,15 @@
 //
 // R-side match marks (HJ_FLAG_TRACK_R_MATCHES): `bool MARK` next to K on both kernels, instantiated for INNER and LEFT. A MARK
 // instantiation takes PairsOutMarked where the others take PairsOut, and stage_flush also sets the bit of every staged R
-// row (mark_plane, hj_device.h).
+// row (mark_plane, hj_pairs.h).
 //
 // The stage itself (PairStage, stage_reserve, stage_flush, stage_finish), the kinds' constants and the dispatch over
-// (kind, marks) are in hj_device.h: k_prj_join_pairs (hj_prj_pairs.hip) stages its rows through the same code.
+// (kind, marks) are in hj_pairs.h: k_prj_join_pairs (hj_prj_pairs.hip) stages its rows through the same code.
 //
 // All integer work, bound by HBM and the table gather; no MFMA.
 
-#include "hj_device.h"
+#include "hj_pairs.h"
+#include "hj_table.h"
 
 namespace hj {
 
@@ -342,7 +343,7 @@ k_htm_probe_pairs(const uint64_t* __restrict__ S, uint64_t n, uint64_t sIdxBase,
     __shared__ uint32_t ldsS[kStagePairs], ldsR[K <= kLeft ? kStagePairs : 1], ldsTot[2 * kWaves];
     __shared__ unsigned long long ldsBase;
     Stage st{ldsS, ldsR, ldsTot, &ldsBase, 0u, 0u, 0ull, 0ull, 0u};
-    // buckets outside the slots the build defined were never written and hold no tuple (hj_device.h, Counters)
+    // buckets outside the slots the build defined were never written and hold no tuple (hj_common.h, Counters)
     const HtmTable T{table, overflow, bucketMask, ctr->validLo, ctr->validHiEx + 512};
     for_s_rounds<V>(S, n, sIdxBase, [](uint32_t) {},
                     [&](const auto& sk, const auto& row, const auto& valid) { htm_rounds<K>(st, out, T, sk, row, valid); });

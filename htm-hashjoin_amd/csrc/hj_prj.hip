@@ -3,7 +3,7 @@
 // What this replaces (paths relative to anilshanbhag/HTM-HashJoin, mc/src/):
 //   k_radix_hist     the histogram loops of parallel_radix_partition (:586-589) and
 //                    radix_cluster (:418-421)
-//   k_scan_*         the prefix / cursor computation (:592-617, :423-430)
+//   (scan)           the prefix / cursor computation (:592-617, :423-430): launch_exclusive_scan_u32, hj_scan.hip
 //   k_radix_scatter  the scatter loops (:622-626, :433-437), here staged through LDS so
 //                    every partition's tuples leave the CU as contiguous runs
 //   k_prj_join       bucket_chaining_join (:231-283) with the probe loop the fork
@@ -25,32 +25,18 @@
 // pass-1 partition). Segments are cut into chunks of chunkLen tuples; a workgroup
 // owns one chunk. Histogram entries are stored [segment][bin][chunk] so that one
 // exclusive scan over the whole array yields every chunk's write cursor.
+//
+// This file: the partition passes (exact and histogram-free), the LDS partition join with the resident-R probe and its
+// work items. What the materialising form (hj_prj_pairs.hip), the aggregating form (hj_prj_agg.hip) and the shard split
+// (hj_shard.hip) share with it is in hj_prj_impl.h; the pass runners they call are defined here.
 
-#include "hj_device.h"
+#include "hj_prj_impl.h"
 
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
 namespace hj {
-
-constexpr int kTile = 8192;                       // largest scatter tile (elements); chunk lengths are multiples of it
-constexpr int kMaxFan = 256;                      // <= 8 radix bits per pass
-constexpr uint32_t kJoinSlots = 32768;            // LDS table slots (uint32) = 128 KiB
-constexpr uint32_t kJoinBlockTuples = 24576;      // R tuples per LDS build (load <= 0.75)
-constexpr int kJoinThreads = 1024;
-constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
-
-struct PassParams {
-    const uint32_t* segOff;     // [nSeg + 1] tuple offsets of the input segments
-    uint32_t nSeg;
-    uint32_t chunkLen;          // multiple of kTile
-    const uint32_t* chunkBase;  // [nSeg + 1] exclusive prefix of chunks per segment
-    uint32_t shift, fan;        // bin = ((key - bias) >> shift) & (fan - 1)
-    uint32_t bias;              // 0, or 1 for the range split of 1-based DataGen keys (shard split only)
-    uint32_t zeroBad;           // shard split only: a tuple with payload bits set counts and travels as key 0, which the
-                                // receiving build reports (HJ_ERR_KEY_RANGE); PRJ reads the key word alone, as mc does
-};
 
 // chunkBase[s] = sum_{t<s} ceil(len_t / chunkLen). nSeg <= 256: one thread.
 __global__ void k_chunk_base(const uint32_t* __restrict__ segOff, uint32_t nSeg, uint32_t chunkLen,
@@ -72,36 +58,10 @@ __global__ void k_init_seg(uint32_t* seg, uint32_t n)
     if (threadIdx.x == 0 && blockIdx.x == 0) { seg[0] = 0; seg[1] = n; }
 }
 
-// Finds the segment of chunk c (largest s with chunkBase[s] <= c). Wave-uniform.
-__device__ __forceinline__ uint32_t find_segment(const uint32_t* __restrict__ chunkBase, uint32_t nSeg, uint32_t c)
+void launch_init_seg(uint32_t* seg, uint32_t n, hipStream_t s) { hipLaunchKernelGGL(k_init_seg, dim3(1), dim3(64), 0, s, seg, n); }
+void launch_chunk_base(const uint32_t* segOff, uint32_t nSeg, uint32_t chunkLen, uint32_t* chunkBase, hipStream_t s)
 {
-    uint32_t lo = 0, hi = nSeg;  // invariant: chunkBase[lo] <= c < chunkBase[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (chunkBase[mid] <= c) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct ChunkRange { uint32_t seg, local, nLocal, begin, end; };
-
-__device__ __forceinline__ ChunkRange chunk_range(const PassParams& p, uint32_t c)
-{
-    ChunkRange r;
-    r.seg = find_segment(p.chunkBase, p.nSeg, c);
-    r.local = c - p.chunkBase[r.seg];
-    r.nLocal = p.chunkBase[r.seg + 1] - p.chunkBase[r.seg];
-    const uint32_t sb = p.segOff[r.seg], se = p.segOff[r.seg + 1];
-    r.begin = sb + r.local * p.chunkLen;
-    const uint64_t e = (uint64_t)r.begin + p.chunkLen;
-    r.end = e < se ? (uint32_t)e : se;
-    return r;
-}
-
-// hist index of (segment, bin, local chunk)
-__device__ __forceinline__ uint64_t hist_index(const PassParams& p, const ChunkRange& r, uint32_t bin)
-{
-    return (uint64_t)p.chunkBase[r.seg] * p.fan + (uint64_t)bin * r.nLocal + r.local;
+    hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(64), 0, s, segOff, nSeg, chunkLen, chunkBase);
 }
 
 // ---------------------------------------------------------------------------
@@ -242,93 +202,6 @@ k_radix_hist_rows(const uint64_t* __restrict__ in, uint64_t* __restrict__ stampe
     }
     __syncthreads();
     if (threadIdx.x < p.fan) hist[hist_index(p, r, threadIdx.x)] = h[threadIdx.x];
-}
-
-// ---------------------------------------------------------------------------
-// exclusive scan of a uint32 array (3 kernels: block scan, scan of block sums, add)
-// ---------------------------------------------------------------------------
-constexpr int kScanPerThread = 16;
-constexpr int kScanTile = kBlock * kScanPerThread;  // 4096
-
-__global__ void __launch_bounds__(kBlock)
-k_scan_blocks(uint32_t* __restrict__ data, uint64_t n, uint32_t* __restrict__ blockSums, Gate gate)
-{
-    __shared__ uint32_t wsum[kBlock / 64];
-    if (gate_closed(gate)) return;
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPerThread;
-    uint32_t v[kScanPerThread], local = 0;
-    // a thread's 16 values are 64 contiguous, 64-byte aligned bytes: four 16-byte loads / stores when they all exist
-    // (one dword per instruction made every wave-instruction touch 64 different lines: 0.79 ms for the 2^26 bucket
-    // counts of the bucketised table at 2^27)
-    const bool whole = base + kScanPerThread <= n;                   // (hipMalloc'ed arrays: data is 256-byte aligned)
-    if (whole) {
-        const uint4* p4 = reinterpret_cast<const uint4*>(data + base);
-#pragma unroll
-        for (int q = 0; q < kScanPerThread / 4; ++q) {
-            const uint4 t = p4[q];
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kScanPerThread; ++k) v[k] = (base + k < n) ? data[base + k] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < kScanPerThread; ++k) local += v[k];
-    uint32_t total;
-    uint32_t ex = block_exclusive_scan(local, wsum, total);
-    if (whole) {
-        uint4* p4 = reinterpret_cast<uint4*>(data + base);
-#pragma unroll
-        for (int q = 0; q < kScanPerThread / 4; ++q) {
-            uint4 t;
-            t.x = ex; ex += v[4 * q]; t.y = ex; ex += v[4 * q + 1]; t.z = ex; ex += v[4 * q + 2]; t.w = ex; ex += v[4 * q + 3];
-            p4[q] = t;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kScanPerThread; ++k) {
-            if (base + k < n) data[base + k] = ex;
-            ex += v[k];
-        }
-    }
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kBlock)
-k_scan_sums(uint32_t* __restrict__ sums, uint32_t m, Gate gate)
-{
-    __shared__ uint32_t wsum[kBlock / 64];
-    if (gate_closed(gate)) return;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < m; base += kBlock) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < m ? sums[i] : 0;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, wsum, total);
-        if (i < m) sums[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock)
-k_scan_add(uint32_t* __restrict__ data, uint64_t n, const uint32_t* __restrict__ blockSums, Gate gate)
-{
-    if (gate_closed(gate)) return;
-    const uint32_t add = blockSums[blockIdx.x];
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPerThread;
-    if (base + kScanPerThread <= n) {
-        uint4* p4 = reinterpret_cast<uint4*>(data + base);
-#pragma unroll
-        for (int q = 0; q < kScanPerThread / 4; ++q) {
-            uint4 t = p4[q];
-            t.x += add; t.y += add; t.z += add; t.w += add;
-            p4[q] = t;
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < kScanPerThread; ++k)
-        if (base + k < n) data[base + k] += add;
 }
 
 // New segment offsets after a pass: segOut[s*fan + bin] = start of that bin.
@@ -763,13 +636,6 @@ k_radix_scatter_frag(const void* __restrict__ in, uint32_t* __restrict__ out, Fr
 // ---------------------------------------------------------------------------
 // per-partition join in LDS
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t next_pow2_u32(uint32_t v)
-{
-    // NEXT_POW_2, parallel_radix_join.c:66-76
-    v--; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; v++;
-    return v;
-}
-
 // Slot of key-remainder k in the LDS table. NOT the identity: inside a partition the remainders of
 // dense keys are consecutive integers, which under linear probing form one solid run that every
 // probe would have to walk to its end (measured: 2.4 s instead of milliseconds at 2^30). A
@@ -786,8 +652,6 @@ static_assert(kJoinSlots == (1u << 15), "join_hash assumes 2^15 slots");
 // are k_prj_join (whole partitions by a fixed stride) and k_prj_probe_items (work items by ticket); they decide what is
 // joined next and when its keys are fetched, the core how a partition is joined.
 // ---------------------------------------------------------------------------
-constexpr int kJoinPre = 16;   // keys per thread and relation prefetched in registers (16 x 1024 = 16384)
-constexpr int kTailPre = 8;    // loads in flight per thread in the loops past the register prefetch
 
 // A relation's final partitions as the join sees them. Exact passes (!frag): partition pid = part[off[pid] .. off[pid+1]),
 // one dense run (log2C = 0). Histogram-free passes (frag): 2^log2C fragments of `cap` slots from pid << log2C, fragment f
@@ -824,23 +688,6 @@ __device__ __forceinline__ void prefetch_part(const PartView& v, uint32_t base, 
     }
 }
 
-// f(element) for element i of [from, n) of a run starting at slot `base`, kTailPre loads in flight per thread (a one-load
-// loop waits a whole HBM round trip per key: the rest of a 2^16-tuple item is 48 keys per thread)
-template <typename T, typename F>
-__device__ __forceinline__ void for_run(const T* __restrict__ part, uint32_t base, uint32_t from, uint32_t n, F&& f)
-{
-    for (uint32_t i0 = from + threadIdx.x; i0 < n; i0 += kTailPre * kJoinThreads) {
-        T k[kTailPre];
-#pragma unroll
-        for (int u = 0; u < kTailPre; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kJoinThreads;
-            k[u] = part[base + (i < n ? i : n - 1)];                  // clamped: i0 < n, so n >= 1
-        }
-#pragma unroll
-        for (int u = 0; u < kTailPre; ++u)
-            if (i0 + (uint32_t)u * kJoinThreads < n) f(k[u]);
-    }
-}
 
 // What a partition holds: n keys; mask bit j = prefetch slot j holds a key; tail = some fragment is longer than the
 // prefetch covers.
@@ -1226,30 +1073,6 @@ k_prj_probe_items(const uint32_t* __restrict__ partR, const uint32_t* __restrict
 // ---------------------------------------------------------------------------
 // host-side planning and launch
 // ---------------------------------------------------------------------------
-static uint32_t pick_chunk_len(uint64_t n)
-{
-    // aim for ~4096 chunks (>= 2 per CU-slot), whole tiles, 4Ki..64Ki tuples
-    uint64_t len = n / 4096;
-    len = (len + kTile - 1) / kTile * kTile;
-    if (len < (uint64_t)kTile) len = kTile;
-    if (len > 65536) len = 65536;
-    return (uint32_t)len;
-}
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct PassLayout { uint32_t chunkLen; uint64_t maxChunks; uint64_t histEntries; uint64_t scanBlocks; };
-
-static PassLayout pass_layout(uint64_t n, uint32_t nSeg, uint32_t fan)
-{
-    PassLayout l;
-    l.chunkLen = pick_chunk_len(n);
-    l.maxChunks = n / l.chunkLen + nSeg + 1;
-    l.histEntries = l.maxChunks * fan;
-    l.scanBlocks = (l.histEntries + kScanTile - 1) / kScanTile;
-    return l;
-}
-
 // Slots of a fragment that is to hold a Poisson-distributed number of keys of the given mean: mean + 7 sigma (one
 // fragment in 10^12 is larger; a run has ~10^6 of them) + a little for tiny means, in whole 16-byte vectors.
 static uint32_t frag_cap(double mean)
@@ -1349,36 +1172,6 @@ uint64_t prj_hist_entries_needed(uint64_t n, uint32_t radixBits)
     return a > b ? a : b;
 }
 
-namespace {
-struct Work {
-    uint32_t *seg0, *seg1, *chunkBase, *hist, *sums, *offR, *offS, *cnt1, *cnt2R, *cnt2S;
-};
-Work carve(const PrjPlan& pl, void* base)
-{
-    const uint32_t F1 = 1u << pl.bits1, F2 = 1u << pl.bits2;
-    const uint64_t P = (uint64_t)F1 * F2;
-    char* p = static_cast<char*>(base);
-    Work w;
-    w.seg0 = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * 2, 256);
-    w.seg1 = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (F1 + 1), 256);
-    w.chunkBase = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (F1 + 2), 256);
-    w.hist = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * pl.histEntries, 256);
-    w.sums = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (pl.scanBlocks + 1), 256);
-    w.offR = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (P + 1), 256);
-    w.offS = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (P + 1), 256);
-    w.cnt1 = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * pl.cnt1Entries, 256);
-    w.cnt2R = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * pl.cnt2EntriesR, 256);
-    w.cnt2S = reinterpret_cast<uint32_t*>(p);
-    return w;
-}
-
-// The row-id form of a pass (HJ_FLAG_KEEP_ROW_IDS): 8-byte {key, row} elements out. stamped != nullptr: the pass that
-// reads the tuples -- its histogram writes their elements, row = rowBase + position, to `stamped`, and the scatter moves
-// those; nullptr: `in` holds elements already.
-struct PassRows { bool on; uint64_t* stamped; uint32_t rowBase; };
-
-// The front half of a pass, behind k_chunk_base: the histogram of every chunk, its scan (the chunks' write cursors) and the
-// offsets of the output segments. rows.stamped: the row-id histogram, which also writes the {key, row} elements.
 hipError_t pass_offsets(const void* in, bool in32, const PassRows& rows, const PassParams& p, const PassLayout& l, uint64_t n,
                         uint32_t* hist, uint32_t* sums, uint32_t* segOut, Gate gate, hipStream_t s)
 {
@@ -1398,7 +1191,7 @@ hipError_t pass_offsets(const void* in, bool in32, const PassRows& rows, const P
 
 // One radix pass: in -> out, segments segIn[nSeg+1] -> segOut[nSeg*fan+1].
 // in32: the input already holds bare keys (pass 2); the output always does, unless rows.on.
-hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const uint32_t* segIn, uint32_t nSeg,
+static hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const uint32_t* segIn, uint32_t nSeg,
                     uint32_t shift, uint32_t bits, uint32_t* segOut, const Work& w, Gate gate, hipStream_t s,
                     hipEvent_t evScatter0 = nullptr, hipEvent_t evScatter1 = nullptr, PassRows rows = PassRows{false, nullptr, 0u})
 {
@@ -1428,8 +1221,7 @@ hipError_t run_pass(const void* in, bool in32, uint32_t* out, uint64_t n, const 
 // The same two passes in the row-id form: tmp and out hold 8-byte {key, row} elements, row = rowBase + position in `in`.
 // The stamped copy of the input goes to the buffer pass 1 does not write: out (two passes) or tmp (one).
 hipError_t partition_relation_rows(const PrjPlan& pl, const Work& w, const uint64_t* in, uint64_t n, uint32_t rowBase,
-                                   uint64_t* tmp, uint64_t* out, uint32_t* finalOff, hipStream_t s,
-                                   hipEvent_t evS0 = nullptr, hipEvent_t evS1 = nullptr)
+                                   uint64_t* tmp, uint64_t* out, uint32_t* finalOff, hipStream_t s, hipEvent_t evS0, hipEvent_t evS1)
 {
     uint32_t* const tmp32 = reinterpret_cast<uint32_t*>(tmp);
     uint32_t* const out32 = reinterpret_cast<uint32_t*>(out);
@@ -1442,7 +1234,7 @@ hipError_t partition_relation_rows(const PrjPlan& pl, const Work& w, const uint6
                     PassRows{true, nullptr, 0u});
 }
 
-hipError_t partition_relation(const PrjPlan& pl, const Work& w, const uint64_t* in, uint64_t n,
+static hipError_t partition_relation(const PrjPlan& pl, const Work& w, const uint64_t* in, uint64_t n,
                               uint32_t* tmp, uint32_t* out, uint32_t* finalOff, Gate gate, hipStream_t s,
                               hipEvent_t evS0 = nullptr, hipEvent_t evS1 = nullptr)
 {
@@ -1454,7 +1246,7 @@ hipError_t partition_relation(const PrjPlan& pl, const Work& w, const uint64_t* 
 }
 
 // The two histogram-free passes over one relation: tuples -> fragments of tmp -> fragments of out, counts in cnt2.
-hipError_t partition_relation_frag(const PrjPlan& pl, const PrjFrag& g, const Work& w, const uint64_t* in, uint64_t n,
+static hipError_t partition_relation_frag(const PrjPlan& pl, const PrjFrag& g, const Work& w, const uint64_t* in, uint64_t n,
                                    uint32_t* tmp, uint32_t* out, uint32_t* cnt2, Counters* ctr, hipStream_t s,
                                    hipEvent_t evS0 = nullptr, hipEvent_t evS1 = nullptr)
 {
@@ -1477,7 +1269,7 @@ struct RelParts { const PrjFrag& g; const uint64_t* in; uint64_t n; uint32_t* ou
 // fragment that overflows sets: they return at once unless one did. All relations share the word, so the histogram-free
 // passes of all of them come first. *exact = the gate of the join over the exact layout.
 // ev0 / ev1 (may be null): recorded around the first pass-1 scatter of the first relation.
-hipError_t partition_relations(const PrjPlan& pl, const Work& w, const RelParts* rels, int nRels, uint32_t* tmp, Counters* ctr,
+static hipError_t partition_relations(const PrjPlan& pl, const Work& w, const RelParts* rels, int nRels, uint32_t* tmp, Counters* ctr,
                                hipStream_t s, Gate* exact, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
 {
     hipError_t e;
@@ -1500,7 +1292,7 @@ hipError_t partition_relations(const PrjPlan& pl, const Work& w, const RelParts*
 
 // k_prj_join over one layout of R and S; vs = kNoPart: R's checksum alone. One persistent workgroup per CU.
 const PartView kNoPart{nullptr, nullptr, nullptr, PartGeom{0u, 0u, 1u}, false};
-void enqueue_prj_join(const PrjPlan& pl, const PartView& vr, const PartView& vs, int nCU, Counters* ctr, Gate gate, hipStream_t s)
+static void enqueue_prj_join(const PrjPlan& pl, const PartView& vr, const PartView& vs, int nCU, Counters* ctr, Gate gate, hipStream_t s)
 {
     static_assert(kJoinSlots * 2 == 65536, "two 16-bit counters per LDS word cover every 16-bit key remainder");
     const uint32_t P = 1u << pl.radixBits;
@@ -1510,11 +1302,9 @@ void enqueue_prj_join(const PrjPlan& pl, const PartView& vr, const PartView& vs,
                        vr.part, vr.off, vr.cnt, vr.g, vs.part, vs.off, vs.cnt, vs.g, pl.radixBits, P, ctr, gate);
 }
 
-// The work items of a probe against the resident R (no host round trip): items per partition, one scan, fill.
-// cntR / cntS: the fragment counts of a relation whose plan was optimistic, else nullptr.
 hipError_t enqueue_prj_items(const PrjResident& res, const uint32_t* offR, const uint32_t* cntR, uint32_t log2CR,
                              const uint32_t* offS, const uint32_t* cntS, uint32_t log2CS, uint32_t P, Counters* ctr, hipStream_t s,
-                             bool rless = false)
+                             bool rless)
 {
     hipError_t e;
     if ((e = hipMemsetAsync(res.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
@@ -1524,7 +1314,6 @@ hipError_t enqueue_prj_items(const PrjResident& res, const uint32_t* offR, const
     hipLaunchKernelGGL(k_prj_items_fill, dim3((2 * P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, res.itemCnt, P, res.items, res.stats);
     return hipGetLastError();
 }
-}  // namespace
 
 hipError_t launch_prj(const PrjPlan& pl, const PrjBuffers& buf, const uint64_t* R, uint64_t nR,
                       const uint64_t* S, uint64_t nS, int nCU, Counters* ctr, hipEvent_t evPartDone, hipEvent_t evScatter0,
@@ -1629,277 +1418,9 @@ hipError_t launch_prj_probe(const PrjPlan& planR, uint64_t nR, const PrjPlan& pl
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// multi-GPU destination split (hj_shard_histogram_dev / hj_shard_scatter_dev): one radix pass on
-// the low log2(nShards) key bits, tuples in, bare keys out, and STABLE: inside a destination the keys
-// keep their input order exactly. The join's semantics are "insert in input order"; the receiving rank
-// takes a key's position in its receive buffer as that order, so the scatter may not permute anything
-// (the PRJ scatter above ranks with LDS atomics and is only stable tile by tile -- the radix join does
-// not care). It also keeps a near-sorted input near-sorted, so the receiver's locality pre-round still
-// picks the LDS-window build.
-//
-// Ranking without atomics: lane l of wavefront w holds, for k = 0..7, the tile's element k*1024 + 64 w + l,
-// so (k, w, l) is input order. For one k a wavefront finds, per lane, the lanes with the same
-// destination (log2(fan) ballots) -- its rank among them is a popcount of the lower lanes, their
-// number goes to cnt[bin][k][w]. An exclusive scan of cnt in exactly that order gives every
-// (bin, k, w) group its place in the tile's staged order.
-// ---------------------------------------------------------------------------
-constexpr int kStabThreads = 1024;
-constexpr int kStabPer = 8;                                    // tuples per thread per tile
-constexpr int kStabTile = kStabThreads * kStabPer;             // 8192
-constexpr int kStabGroups = kStabPer * (kStabThreads / 64);    // (k, wavefront) groups per tile = 128
-constexpr int kStabMaxFan = 64;
-
-__global__ void __launch_bounds__(kStabThreads, 8)
-k_shard_scatter_stable(const uint64_t* __restrict__ in, uint32_t* __restrict__ out, PassParams p,
-                       const uint32_t* __restrict__ scanned)
-{
-    extern __shared__ uint32_t stab[];              // cnt[fan][kStabGroups], then stage[kStabTile + kStabTile/32 + 1]
-    uint32_t* const cnt = stab;
-    const uint32_t nCnt = p.fan * kStabGroups;
-    uint32_t* const stage = stab + nCnt;
-    __shared__ unsigned int delta[kStabMaxFan];     // write cursor of the bin - its offset in the staged tile
-    __shared__ unsigned int cursor[kStabMaxFan];
-    __shared__ uint32_t wsum[kStabThreads / 64];
-    constexpr uint32_t kDump = kStabTile + (kStabTile >> 5);
-
-    const uint32_t c = blockIdx.x;
-    if (c >= p.chunkBase[p.nSeg]) return;
-    const ChunkRange r = chunk_range(p, c);
-    const uint32_t fmask = p.fan - 1;
-    const uint32_t len = r.end - r.begin;
-    const uint32_t wave = threadIdx.x >> 6;
-    int bits = 0;
-    while ((1u << bits) < p.fan) ++bits;
-    if (threadIdx.x < p.fan) cursor[threadIdx.x] = scanned[hist_index(p, r, threadIdx.x)];
-    const uint32_t perThread = nCnt / kStabThreads;               // fan * 128 / 1024 = fan / 8 (fan >= 8) ...
-    const uint32_t items = perThread ? perThread : 1;             // ... or 1 with some threads idle (fan < 8)
-    __syncthreads();
-
-    for (uint32_t tb = 0; tb < len; tb += kStabTile) {
-        for (uint32_t i = threadIdx.x; i < nCnt; i += kStabThreads) cnt[i] = 0;
-        uint32_t key[kStabPer], rk4[kStabPer / 4];    // ranks are < 64: four to a register
-        uint32_t okMask = 0;
-#pragma unroll
-        for (int k = 0; k < kStabPer / 4; ++k) rk4[k] = 0;
-#pragma unroll
-        for (int k = 0; k < kStabPer; ++k) {
-            const uint32_t rel = tb + (uint32_t)k * kStabThreads + threadIdx.x;
-            const bool ok = rel < len;
-            const uint64_t t = ok ? in[(uint64_t)r.begin + rel] : 0ull;
-            key[k] = (t >> 32) ? 0u : (uint32_t)t;                 // payload bits set: see PassParams::zeroBad
-            okMask |= ok ? (1u << k) : 0u;
-        }
-        __syncthreads();                                          // cnt is zero
-#pragma unroll
-        for (int k = 0; k < kStabPer; ++k) {
-            const bool ok = (okMask >> k) & 1u;
-            const uint32_t bin = ((key[k] - p.bias) >> p.shift) & fmask;
-            unsigned long long peers = __ballot(ok);
-            for (int b = 0; b < bits; ++b) {
-                const bool bit = (bin >> b) & 1u;
-                const unsigned long long m = __ballot(bit);
-                peers &= bit ? m : ~m;
-            }
-            const uint32_t rk = lane_rank(peers);
-            rk4[k / 4] |= rk << (8 * (k % 4));
-            if (ok && rk == 0) cnt[(bin * kStabPer + k) * (kStabThreads / 64) + wave] = (uint32_t)__popcll(peers);
-        }
-        __syncthreads();
-        {   // exclusive scan of cnt[0..nCnt) in place, `items` consecutive entries per thread
-            const uint32_t base = threadIdx.x * items;
-            uint32_t local = 0;
-            for (uint32_t i = 0; i < items; ++i) local += (base + i < nCnt) ? cnt[base + i] : 0u;
-            uint32_t total;
-            uint32_t ex = block_exclusive_scan<kStabThreads>(local, wsum, total);
-            for (uint32_t i = 0; i < items; ++i) {
-                if (base + i < nCnt) { const uint32_t v = cnt[base + i]; cnt[base + i] = ex; ex += v; }
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < p.fan) {
-            const uint32_t off = cnt[threadIdx.x * kStabGroups];                      // first group of the bin
-            const uint32_t end = threadIdx.x + 1 < p.fan ? cnt[(threadIdx.x + 1) * kStabGroups]
-                                                         : (len - tb < (uint32_t)kStabTile ? len - tb : (uint32_t)kStabTile);
-            const uint32_t cu = cursor[threadIdx.x];
-            delta[threadIdx.x] = cu - off;
-            cursor[threadIdx.x] = cu + (end - off);
-        }
-#pragma unroll
-        for (int k = 0; k < kStabPer; ++k) {
-            const uint32_t bin = ((key[k] - p.bias) >> p.shift) & fmask;
-            const uint32_t at = cnt[(bin * kStabPer + k) * (kStabThreads / 64) + wave] + ((rk4[k / 4] >> (8 * (k % 4))) & 0xFFu);
-            stage[((okMask >> k) & 1u) ? at + (at >> 5) : kDump] = key[k];
-        }
-        __syncthreads();
-        const uint32_t valid = len - tb < (uint32_t)kStabTile ? len - tb : (uint32_t)kStabTile;
-#pragma unroll 4
-        for (int k = 0; k < kStabPer; ++k) {
-            const uint32_t q = (uint32_t)k * kStabThreads + threadIdx.x;
-            if (q < valid) {
-                const uint32_t t = stage[q + (q >> 5)];
-                out[delta[((t - p.bias) >> p.shift) & fmask] + q] = t;
-            }
-        }
-        __syncthreads();                                          // stage, cnt and delta are reused by the next tile
-    }
-}
-
-
-// The same split for fan-outs <= 16 (every multi-GPU node there is), one WAVEFRONT per chunk and no workgroup barrier:
-// the kernel above synchronises its 16 wavefronts seven times per tile (3.0 TB/s of its 12 bytes per tuple). Here a
-// wavefront walks its chunk in tiles of 512 tuples (lane l holds tile elements 64 k + l, k = 0..7: (k, l) is input
-// order), ranks them bin by bin with ballots -- fan x 8 ballots per tile, the running count is the tile offset of the
-// next bin -- stages the tile in its own 2 KiB of LDS grouped by destination and writes the runs out through cursors it
-// keeps in registers (start = the chunk's scanned histogram entries). Same output, element for element.
-constexpr int kSwThreads = 256;
-constexpr int kSwPer = 8;
-constexpr int kSwTile = 64 * kSwPer;             // 512 tuples per wavefront tile
-constexpr int kSwMaxFan = 16;
-
-__global__ void __launch_bounds__(kSwThreads)
-k_shard_scatter_wave(const uint64_t* __restrict__ in, uint32_t* __restrict__ out, PassParams p,
-                     const uint32_t* __restrict__ scanned)
-{
-    __shared__ uint32_t stage[kSwThreads / 64][kSwTile];
-    __shared__ uint32_t delta[kSwThreads / 64][kSwMaxFan];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t c = blockIdx.x * (kSwThreads / 64) + wave;
-    if (c >= p.chunkBase[p.nSeg]) return;                          // whole wavefronts leave; nobody waits for them
-    const ChunkRange r = chunk_range(p, c);
-    const uint32_t fan = p.fan, fmask = fan - 1;
-    const uint32_t len = r.end - r.begin;
-    uint32_t cur[kSwMaxFan];                                       // write cursor per destination (wave-uniform)
-#pragma unroll
-    for (int b = 0; b < kSwMaxFan; ++b)
-        cur[b] = (uint32_t)b < fan ? (uint32_t)__builtin_amdgcn_readfirstlane((int)scanned[hist_index(p, r, (uint32_t)b)]) : 0u;
-    const uint64_t* __restrict__ src = in + r.begin;
-    uint64_t nxt[kSwPer];
-#pragma unroll
-    for (int k = 0; k < kSwPer; ++k) { const uint32_t rel = 64u * k + lane; nxt[k] = rel < len ? src[rel] : 0ull; }
-    for (uint32_t tb = 0; tb < len; tb += kSwTile) {
-        uint32_t key[kSwPer], bin[kSwPer], pos[kSwPer];
-        uint32_t okMask = 0;
-#pragma unroll
-        for (int k = 0; k < kSwPer; ++k) {
-            const uint64_t t = nxt[k];
-            key[k] = (t >> 32) ? 0u : (uint32_t)t;                 // payload bits set: travels as key 0 (PassParams::zeroBad)
-            const bool ok = tb + 64u * k + lane < len;
-            bin[k] = ok ? ((key[k] - p.bias) >> p.shift) & fmask : 0xFFFFFFFFu;   // past the chunk's end: no destination's
-            okMask |= ok ? (1u << k) : 0u;
-            pos[k] = 0;
-        }
-#pragma unroll
-        for (int k = 0; k < kSwPer; ++k) { const uint32_t rel = tb + kSwTile + 64u * k + lane; nxt[k] = rel < len ? src[rel] : 0ull; }
-        uint32_t off = 0;                                          // staged position where the next destination's run starts
-#pragma unroll
-        for (int b = 0; b < kSwMaxFan; ++b) {
-            if ((uint32_t)b < fan) {                               // wave-uniform
-                uint32_t cnt = 0;
-#pragma unroll
-                for (int k = 0; k < kSwPer; ++k) {
-                    const bool mine = bin[k] == (uint32_t)b;
-                    const unsigned long long m = __ballot(mine);
-                    pos[k] = mine ? off + cnt + lane_rank(m) : pos[k];
-                    cnt += (uint32_t)__popcll(m);
-                }
-                if (lane == 0) delta[wave][b] = cur[b] - off;      // output index of staged position q = delta[bin] + q
-                cur[b] += cnt;
-                off += cnt;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kSwPer; ++k)
-            if ((okMask >> k) & 1u) stage[wave][pos[k]] = key[k];
-        // (LDS operations of one wavefront complete in issue order: the reads below see the stores above)
-        const uint32_t valid = len - tb < (uint32_t)kSwTile ? len - tb : (uint32_t)kSwTile;
-#pragma unroll
-        for (int k = 0; k < kSwPer; ++k) {
-            const uint32_t q = 64u * k + lane;
-            if (q < valid) {
-                const uint32_t t = stage[wave][q];
-                out[delta[wave][((t - p.bias) >> p.shift) & fmask] + q] = t;
-            }
-        }
-    }
-}
-
-namespace {
-struct ShardWork { uint32_t *seg0, *segOut, *chunkBase, *hist, *sums; };
-ShardWork shard_carve(void* base, uint64_t n, uint32_t fan)
-{
-    const PassLayout l = pass_layout(n, 1, fan);
-    char* p = static_cast<char*>(base);
-    ShardWork w;
-    w.seg0 = reinterpret_cast<uint32_t*>(p); p += 256;
-    w.segOut = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * (fan + 1), 256);
-    w.chunkBase = reinterpret_cast<uint32_t*>(p); p += 256;
-    w.hist = reinterpret_cast<uint32_t*>(p); p += align_up(sizeof(uint32_t) * l.histEntries, 256);
-    w.sums = reinterpret_cast<uint32_t*>(p);
-    return w;
-}
-__global__ void k_shard_counts(const uint32_t* __restrict__ segOut, uint32_t fan, unsigned long long* __restrict__ counts)
-{
-    if (threadIdx.x < fan) counts[threadIdx.x] = segOut[threadIdx.x + 1] - segOut[threadIdx.x];
-}
-}  // namespace
-
-size_t shard_work_bytes(uint64_t n, uint32_t nShards)
-{
-    const PassLayout l = pass_layout(n, 1, nShards);
-    return 256 + align_up(sizeof(uint32_t) * (nShards + 1), 256) + 256 +
-           align_up(sizeof(uint32_t) * l.histEntries, 256) + align_up(sizeof(uint32_t) * (l.scanBlocks + 1), 256);
-}
-
-hipError_t launch_shard_hist(const uint64_t* in, uint64_t n, uint32_t nShards, uint32_t digitShift, void* work,
-                             unsigned long long* counts, hipStream_t s)
-{
-    const ShardWork w = shard_carve(work, n, nShards);
-    const PassLayout l = pass_layout(n, 1, nShards);
-    hipLaunchKernelGGL(k_init_seg, dim3(1), dim3(64), 0, s, w.seg0, (uint32_t)n);
-    hipLaunchKernelGGL(k_chunk_base, dim3(1), dim3(64), 0, s, w.seg0, 1u, l.chunkLen, w.chunkBase);
-    const PassParams p{w.seg0, 1u, l.chunkLen, w.chunkBase, digitShift & 0xFFu, nShards, (digitShift >> 8) & 1u, 1u};
-    const hipError_t e = pass_offsets(in, false, PassRows{false, nullptr, 0u}, p, l, n, w.hist, w.sums, w.segOut, kNoGate, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_shard_counts, dim3(1), dim3(64), 0, s, w.segOut, nShards, counts);
-    return hipGetLastError();
-}
-
-// tuples in, bare keys out, stable: the exchange moves 4 bytes per tuple and no index
-hipError_t launch_shard_scatter_ordered(const uint64_t* in, uint64_t n, uint32_t nShards, uint32_t digitShift, void* work,
-                                        uint32_t* outKeys, hipStream_t s)
-{
-    const ShardWork w = shard_carve(work, n, nShards);
-    const PassLayout l = pass_layout(n, 1, nShards);
-    PassParams p{w.seg0, 1u, l.chunkLen, w.chunkBase, digitShift & 0xFFu, nShards, (digitShift >> 8) & 1u, 1u};
-    const size_t lds = sizeof(uint32_t) * ((size_t)nShards * kStabGroups + kStabTile + (kStabTile >> 5) + 1);   // <= 65.1 KiB
-    if (nShards <= (uint32_t)kSwMaxFan)
-        hipLaunchKernelGGL(k_shard_scatter_wave, dim3((unsigned)((l.maxChunks + kSwThreads / 64 - 1) / (kSwThreads / 64))),
-                           dim3(kSwThreads), 0, s, in, outKeys, p, w.hist);
-    else
-        hipLaunchKernelGGL(k_shard_scatter_stable, dim3((unsigned)l.maxChunks), dim3(kStabThreads), lds, s,
-                           in, outKeys, p, w.hist);
-    return hipGetLastError();
-}
-
-size_t scan_workspace_words(uint64_t n) { return (size_t)((n + kScanTile - 1) / kScanTile) + 1; }
-
-hipError_t launch_exclusive_scan_u32(uint32_t* data, uint64_t n, uint32_t* sums, hipStream_t s, Gate gate)
-{
-    const uint64_t blocks = (n + kScanTile - 1) / kScanTile;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, gate);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, s, sums, (uint32_t)blocks, gate);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)blocks), dim3(kBlock), 0, s, data, n, sums, gate);
-    return hipGetLastError();
-}
-
-static hipError_t prj_pairs_set_attributes();     // hj_prj_pairs.hip
-static hipError_t prj_agg_set_attributes();       // hj_prj_agg.hip
-
 hipError_t prj_set_attributes()
 {
-    // per device (hj_create calls this with its device current): the LDS join table and the stable split's staging
+    // per device (hj_create calls this with its device current): the LDS join tables, and the stable split's staging through shard_set_attributes
     hipError_t e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_prj_join<false>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
@@ -1911,15 +1432,7 @@ hipError_t prj_set_attributes()
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kJoinSlots * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = prj_pairs_set_attributes()) != hipSuccess) return e;
     if ((e = prj_agg_set_attributes()) != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_shard_scatter_stable),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               sizeof(uint32_t) * (kStabMaxFan * kStabGroups + kStabTile + (kStabTile >> 5) + 1));
+    return shard_set_attributes();
 }
 
 }  // namespace hj
-
-// the materialising form of the resident join: part of this translation unit, because it runs the passes above in their
-// row-id form and walks the work items k_prj_items_count / k_prj_items_fill build
-#include "hj_prj_pairs.hip"
-// the aggregating form: the same passes and work items, per-R-row accumulators in place of the pair stage
-#include "hj_prj_agg.hip"

@@ -1,8 +1,8 @@
 // hj_prj_agg.hip -- the aggregating form of the resident radix join for gfx950 (MI355X): hj_prj_agg_begin,
 // hj_prj_probe_agg_dev, hj_prj_agg_rows_dev. COUNT / SUM / MIN / MAX of S values per R row, without the pairs.
 //
-// Not a translation unit of its own: hj_prj.hip includes it at its end, behind hj_prj_pairs.hip, whose row-id passes
-// (partition_relation_rows) and work-item list (enqueue_prj_items, rless = false) it uses unchanged.
+// It uses the row-id passes (partition_relation_rows) and the work-item list (enqueue_prj_items, rless = false) of
+// hj_prj.hip unchanged, as hj_prj_pairs.hip does; both through hj_prj_impl.h.
 //
 //   accumulators       one 64-bit match-count plane and nCols 64-bit planes of rSize entries in global memory, indexed by
 //                      RESIDENT POSITION -- the index into partR -- so that the entries of one R partition, hence of one
@@ -29,6 +29,8 @@
 // and issue one LDS atomic was measured under Zipf and did not pay (profiles/join_aggregate.md).
 // All integer work, bound by the scattered value reads and the LDS atomics; no MFMA. Exact: every op is associative and
 // commutative on 64-bit integers (SUM wraps), so no result depends on the order of the adds.
+
+#include "hj_prj_impl.h"
 
 namespace hj {
 
@@ -161,7 +163,7 @@ k_prj_join_agg(const uint2* __restrict__ partR, const uint32_t* __restrict__ off
 #pragma unroll
                                 for (int c = 0; c < NC; ++c) {
                                     const uint32_t* const valid = src.valid[c];
-                                    ok[c] = !valid || ((valid[e[u].y >> 5] >> (e[u].y & 31u)) & 1u);
+                                    ok[c] = !valid || valid_bit(valid, e[u].y);
                                     v[c] = ok[c] ? agg_value(src.p[c], ops.op[c], ops.width[c], ops.sgn[c], e[u].y) : 0ull;
                                 }
                             }
@@ -208,7 +210,7 @@ static void with_agg_cols(uint32_t nCols, F&& f)
     else f(integral_constant<int, 4>{});
 }
 
-static hipError_t prj_agg_set_attributes()
+hipError_t prj_agg_set_attributes()
 {
     hipError_t e = hipSuccess;
     for (uint32_t nc = 1; nc <= kAggMaxCols; ++nc)

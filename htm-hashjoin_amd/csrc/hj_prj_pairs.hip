@@ -1,8 +1,8 @@
 // hj_prj_pairs.hip -- the materialising form of the resident radix join for gfx950 (MI355X): hj_prj_build_dev on a
 // context reserved with HJ_FLAG_KEEP_ROW_IDS, hj_prj_probe_pairs_dev.
 //
-// Not a translation unit of its own: hj_prj.hip includes it at its end, because it instantiates that file's pass
-// templates and walks the work-item list its kernels build (k_prj_items_count / k_prj_items_fill, unchanged).
+// It runs the passes of hj_prj.hip in their row-id form (partition_relation_rows) and walks the work-item list its kernels
+// build (enqueue_prj_items: k_prj_items_count / k_prj_items_fill, unchanged); both through hj_prj_impl.h.
 //
 //   row-id passes      the exact passes of hj_prj.hip over 8-byte {key, row} elements (partition_relation_rows there): the
 //                      first histogram stamps the row -- idxBase + position in the input -- over each tuple's upper word
@@ -13,7 +13,7 @@
 //                      (key >> radixBits, R row) entries, duplicates of a key as separate entries; a probe walks its run to the
 //                      first empty slot and emits one (S row, R row) pair per equal entry
 //
-// Pair output through the stage of hj_pairs.hip (PairStage, hj_device.h): pairs are staged in LDS, a full stage claims its run of the two output
+// Pair output through the stage of hj_pairs.hip (PairStage, hj_pairs.h): pairs are staged in LDS, a full stage claims its run of the two output
 // planes with ONE 64-bit atomicAdd on the cursor and leaves as 16-byte stores; pairs at or beyond `capacity` are counted and not written.
 // LDS: table 15360 slots x (4 B key + 4 B row) = 120 KiB, stage 4096 pairs x 8 B = 32 KiB, 152 KiB of the CU's 160.
 //
@@ -24,6 +24,8 @@
 // the S row in the first block that matches it; ANTI the S row in the last block. A padding lane holds a clamped COPY of
 // the item's last element (load_s): j < nSi gates every row of these kinds, not only the walk. LEFT and ANTI also take
 // items of partitions without R tuples (k_prj_items_count, rless): no build, every element unmatched.
+
+#include "hj_prj_impl.h"
 
 namespace hj {
 
@@ -60,7 +62,7 @@ k_prj_rows_checksum(const uint2* __restrict__ partR, const uint32_t* __restrict_
 // layout: partition pid = part[off[pid] .. off[pid + 1]), elements {x = key, y = row}. The arrays are separate __restrict__
 // parameters (k_prj_join: members of a struct became vector loads), and what an item reads is looked up before its LDS work.
 // K: hj_join_kind. out.cursor[1]: LEFT's unmatched S elements.
-// MARK (INNER and LEFT only): `out` also carries the R-side match marks (RMarks, hj_device.h; base 0: an R row is its
+// MARK (INNER and LEFT only): `out` also carries the R-side match marks (RMarks, hj_pairs.h; base 0: an R row is its
 // position in the relation given to the build). Every produced R row sets its bit in one of two places: where the staged
 // R plane is read at a flush (stage_flush, whatever the capacity lets out), and in the `put` of the direct-write round,
 // which bypasses the stage.
@@ -222,7 +224,7 @@ k_prj_join_pairs(const uint2* __restrict__ partR, const uint32_t* __restrict__ o
     stage_finish<K>(st, out, ctr, &Counters::Shard::prjMatches);
 }
 
-static hipError_t prj_pairs_set_attributes()
+hipError_t prj_pairs_set_attributes()
 {
     hipError_t e = hipSuccess;
     for (uint32_t kind = 0; kind <= (uint32_t)kAnti; ++kind)

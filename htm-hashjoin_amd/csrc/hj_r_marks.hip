@@ -1,7 +1,7 @@
 // hj_r_marks.hip -- the sweep of the R-side match marks for gfx950 (MI355X): hj_r_rows_dev.
 //
 // The pairs kernels of a context reserved with HJ_FLAG_TRACK_R_MATCHES leave one bit per R row of the last build (RMarks,
-// hj_device.h). The sweep turns the set bits, or the clear ones, into rows: an ORDERED compaction, so that the R-only tail
+// hj_pairs.h). The sweep turns the set bits, or the clear ones, into rows: an ORDERED compaction, so that the R-only tail
 // of a right or full outer join comes out ascending and a truncated call yields the first `capacity` rows.
 //
 //   k_r_sweep_count   one workgroup per kSweepWords words of the plane: the rows it will write -> counts[block]
@@ -14,7 +14,7 @@
 // sixteenth of the traffic. The complement is taken on the fly, and the last word is masked to the build's rows in both
 // kernels by the same function, so that a clear bit behind the last row is no row.
 
-#include "hj_device.h"
+#include "hj_pairs.h"
 
 namespace hj {
 

@@ -5,7 +5,7 @@
 //
 // Columns are processed LAST TO FIRST; every pass is stable, so the order a later column left decides the ties of an
 // earlier one, and the row number -- the order the first keys kernel starts from -- decides what is left. Per column:
-//   (keys)      k_sort_keys: key[i] = sort_key(col[row[i]]) (hj_device.h; 0 under a NULL). On the first column processed
+//   (keys)      k_sort_keys: key[i] = sort_key(col[row[i]]) (hj_columns.h; 0 under a NULL). On the first column processed
 //               the rows are the identity: a coalesced read, no row load, and the kernel writes the row plane itself.
 //               After that it is a gather through the rows the previous column left.
 //   per byte of the element, lowest first:
@@ -22,7 +22,7 @@
 // No lane waits for another workgroup: there is no decoupled look-back and no flag anybody spins on -- the three launches
 // of a pass order the passes, and every loop is bounded by the chunk. Passes are never skipped: the decision would have to
 // be the device's (no host round trip), and then no launch would know which of the two planes holds the records.
-#include "hj_device.h"
+#include "hj_columns.h"
 
 #include <algorithm>
 #include <vector>
@@ -70,7 +70,7 @@ k_sort_keys(const void* __restrict__ col, const uint32_t* __restrict__ valid, ui
         if (i >= n) break;
         const uint32_t row = rowsIn ? rowsIn[i] : (uint32_t)i;
         const uint64_t raw = sort_elem(col, width, row);                       // read under a NULL too: the bytes exist
-        const bool ok = !valid || ((valid[row >> 5] >> (row & 31u)) & 1u);
+        const bool ok = !valid || valid_bit(valid, row);
         keys[i] = ok ? (K)sort_key(type, width, flags, raw) : (K)0;
         if (!rowsIn) rowsOut[i] = row;
     }
@@ -80,7 +80,7 @@ k_sort_keys(const void* __restrict__ col, const uint32_t* __restrict__ valid, ui
 template <class K, int MODE>
 __device__ __forceinline__ uint32_t sort_bin(K key, uint32_t row, const uint32_t* __restrict__ valid, uint32_t arg)
 {
-    if constexpr (MODE == kValidBit) return ((valid[row >> 5] >> (row & 31u)) & 1u) ^ arg;
+    if constexpr (MODE == kValidBit) return (uint32_t)valid_bit(valid, row) ^ arg;
     else return (uint32_t)(key >> arg) & (kSortBins - 1);
 }
 
@@ -117,7 +117,7 @@ k_sort_hist(const K* __restrict__ keys, const uint32_t* __restrict__ rows, const
 }
 
 // The stable scatter of one pass: one workgroup per chunk, tile by tile, and no atomic anywhere -- the ranking of
-// k_shard_scatter_stable (hj_prj.hip) at fan 256. Lane l of wavefront w holds, for k = 0..7, the tile's record
+// k_shard_scatter_stable (hj_shard.hip) at fan 256. Lane l of wavefront w holds, for k = 0..7, the tile's record
 // k * 256 + 64 w + l, so (k, w, l) is input order. For one k a wavefront finds, per lane, the lanes with the same digit
 // (8 ballots); a record's rank among them is a popcount of the lower lanes, their number goes to cnt[bin][k][w]. One
 // exclusive scan of cnt in exactly that order gives every (bin, k, w) group its place in the staged tile: the records are
@@ -346,7 +346,7 @@ void sort_rows_host(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32
     for (uint32_t c = nCols; c-- > 0;) {
         const uint32_t flip = (cols.flags[c] & kSortNullsFirst) ? 0u : 1u;
         for (uint64_t i = 0; i < nRows; ++i) {
-            const bool ok = !cols.valid[c] || ((cols.valid[c][i >> 5] >> (i & 31u)) & 1u);
+            const bool ok = !cols.valid[c] || valid_bit(cols.valid[c], (uint32_t)i);
             key[i] = ok ? sort_key(cols.type[c], cols.width[c], cols.flags[c], where_elem_host(cols.p[c], cols.width[c], (uint32_t)i)) : 0ull;
             bin[i] = cols.valid[c] ? (uint8_t)((ok ? 1u : 0u) ^ flip) : 0;
         }

@@ -5,7 +5,7 @@
 // term  s[si] OP r[ri]  holds and marks their S and R rows in two caller-owned planes, so that all eight kinds follow from
 // the kept pairs and two sweeps -- the flow of hj_pairs_verify_dev (hj_keys.hip) with typed comparisons in place of bytes.
 //
-// k_pairs_where. Shape and flow: the pair-filter frame (hj_device.h) as k_pairs_verify2 (hj_keys.hip) has it, because
+// k_pairs_where. Shape and flow: the pair-filter frame (hj_pairs.h) as k_pairs_verify2 (hj_keys.hip) has it, because
 // profiles/join_on.md measured that shape -- 1024 pairs per workgroup, four per lane, dropped pairs counted and never
 // dereferenced, one LDS stage flushed once, both sides marked from it; the flow is written out in both kernels. What is this
 // kernel's own is the loop in the middle. The terms are evaluated one after the other: the S and the R element of the
@@ -15,7 +15,7 @@
 // one before it).
 // Width, type and op of a term are kernel arguments, so scalar branches select among them; the 6 x 10 x 4 combinations
 // are not instantiated. The switch on the width holds the loads alone, every element zero-extended to 64 bits. The compare
-// is where_holds (hj_device.h), ONE __host__ __device__ body that hj_pairs_where_host runs in a host loop: the two raw words are widened
+// is where_holds (hj_columns.h), ONE __host__ __device__ body that hj_pairs_where_host runs in a host loop: the two raw words are widened
 // to one of two domains -- a 64-bit integer, sign-extended from the width and its sign bit flipped for HJ_VAL_INT so that
 // one unsigned compare serves both, or a double, to which a float widens exactly --, `lt`, `eq` and `unordered` are derived
 // once, and the op picks from those three bits.
@@ -25,12 +25,12 @@
 // element-granular reads; a term's loads wait for those of the term before (the wait counters cannot tell the arms of the
 // width switch apart); no constants, no arithmetic, no OR; the terms are not fused into the verify kernel.
 
-#include "hj_device.h"
+#include "hj_columns.h"
 
 namespace hj {
 
 // out, sMarks: as k_pairs_verify2 takes them (cursor[0]: kept pairs; cursor[1]: dropped pairs). The pair-filter frame
-// (hj_device.h) around the terms
+// (hj_pairs.h) around the terms
 template <bool kValid>
 __global__ void __launch_bounds__(kBlock)
 k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
@@ -127,18 +127,18 @@ void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPair
     uint64_t kept = 0, dropped = 0;
     for (uint64_t k = 0; k < nPairs; ++k) {
         const uint32_t es = mapS[k], er = mapR[k], si = es - sRowBase, ri = er;
-        if (es == kNoRow || er == kNoRow || si >= sRows || ri >= rRows) { ++dropped; continue; }
+        if (dropped_pair(es, er, sRowBase, sRows, rRows)) { ++dropped; continue; }
         bool live = true;
         for (uint32_t t = 0; live && t < nTerms; ++t) {
-            const bool okS = !terms.sValid[t] || ((terms.sValid[t][si >> 5] >> (si & 31u)) & 1u);
-            const bool okR = !terms.rValid[t] || ((terms.rValid[t][ri >> 5] >> (ri & 31u)) & 1u);
+            const bool okS = !terms.sValid[t] || valid_bit(terms.sValid[t], si);
+            const bool okR = !terms.rValid[t] || valid_bit(terms.rValid[t], ri);
             live = okS && okR && where_holds(terms.type[t], terms.width[t], terms.op[t], where_elem_host(terms.s[t], terms.width[t], si),
                                              where_elem_host(terms.r[t], terms.width[t], ri));
         }
         if (!live) continue;
         if (kept < capacity) { outS[kept] = es; outR[kept] = er; }
-        if (sMarks) sMarks[si >> 5] |= 1u << (si & 31u);
-        if (rMarks) rMarks[ri >> 5] |= 1u << (ri & 31u);
+        if (sMarks) set_mark_bit(sMarks, si);
+        if (rMarks) set_mark_bit(rMarks, ri);
         ++kept;
     }
     if (info) { info[0] = kept; info[1] = kept < capacity ? kept : capacity; info[2] = 0; info[3] = dropped; }

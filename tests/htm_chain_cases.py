@@ -7,7 +7,7 @@ WHETHER the LDS phase must hold or hand over, and for which cause, comes from ch
 the kernels' comments. No cap is written down here: they come from hj_htm_chain_layout_info (the kernel's own constants),
 the chunk geometry from hj_wave_layout_info, the seams from wave_cases.expected_seams (or the device's hj_wave_seams).
 
-The rules restated (hj_htm.hip "chains along the rings", hj_device.h the table of causes):
+The rules restated (hj_htm.hip "chains along the rings", hj_table.h the table of causes):
   * a conflict is a tuple that finds its bucket (key / 3) & (numBuckets - 1) full: all but the three lowest-indexed tuples
     of a bucket;
   * the conflict list has one slice of sliceLen places per chunk; a conflict is filed under the chunk that owns its

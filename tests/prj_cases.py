@@ -15,7 +15,7 @@ import numpy as np
 
 import htm_hashjoin_amd as hj
 
-# the three constants the join's work items depend on (hj_device.h / hj_prj.hip)
+# the three constants the join's work items depend on (hj_prj.h / hj_prj_impl.h)
 ITEM_S = 1 << 16              # kPrjItemS: S tuples per work item at most
 JOIN_BLOCK_TUPLES = 24576     # kJoinBlockTuples: R tuples of one hashed LDS table
 COUNTER_MAX = 65535           # the DIRECT kernel's 16-bit counters (radixBits >= 16): R tuples per partition they can hold

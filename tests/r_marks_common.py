@@ -9,7 +9,7 @@ from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, Dev
 UNMATCHED, MATCHED = 0, 1
 LOW = U64(0xFFFFFFFF)
 # hj_r_marks.hip: a workgroup of the sweep takes kSweepWords = 256 words of the plane = 8192 rows; the scan of the block
-# counts (launch_exclusive_scan_u32, hj_prj.hip) works in tiles of kScanTile = 4096 entries
+# counts (launch_exclusive_scan_u32, hj_scan.hip) works in tiles of kScanTile = 4096 entries
 SWEEP_ROWS = 32 * 256
 SCAN_TILE = 4096
 

@@ -1,5 +1,5 @@
 """hj_pairs_asof_host and the argument checks of hj_pairs_asof_dev / hj_asof_info through ctypes -> C ABI, without a GPU: the
-host form runs the bodies the kernels run (hj_device.h: where_holds for eligibility, asof_key for the order), so which pair
+host form runs the bodies the kernels run (hj_columns.h: where_holds for eligibility, asof_key for the order), so which pair
 an S row keeps -- by type, width and signedness, with NULLs, NaNs, both zeros and ties -- is checked here, against the model
 of asof_common.py. The device form is held against the same model in test_gpu_asof.py."""
 import ctypes as C

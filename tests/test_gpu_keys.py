@@ -3,7 +3,7 @@ on an MI355X. Expected values come from numpy and from hj_key_hash_host (which t
 header's wording without a GPU), never from the device. Every output plane and every marks plane has sentinel words around
 it that must survive. Run with -m gpu.
 
-hj_keys.hip: a workgroup of k_pairs_verify2 takes kFilterBlockPairs = 1024 consecutive candidates (hj_device.h), a
+hj_keys.hip: a workgroup of k_pairs_verify2 takes kFilterBlockPairs = 1024 consecutive candidates (hj_pairs.h), a
 wavefront 256 of them as four steps of 64. hj_r_marks.hip: a workgroup of the sweep takes 256 words of a plane = 8192 rows."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """The pair-filter frame on an MI355X: hj_pairs_verify_dev, hj_pairs_verify2_dev with validity planes and hj_pairs_where_dev
-with one EQ term share one shape (kFilter*, hj_device.h: map loads, drops, spare rows, stage, drop count, flush, marks around
+with one EQ term share one shape (kFilter*, hj_pairs.h: map loads, drops, spare rows, stage, drop count, flush, marks around
 a column or term loop), so one set of maps drives all three through its seams -- a step of 64 pairs, a wavefront's 256, a
 workgroup's 1024, two workgroups plus one pair. Expected values come from numpy (and, for the condition, from
 pairs_where_host as well), never from the device. The same file holds hj_key_hash_dev to the header's wording

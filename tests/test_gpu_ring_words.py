@@ -1,4 +1,4 @@
-"""The ring build on the slot-code road keeps 4-byte ring words in LDS (hj_device.h RingWord; tests/test_ring_words.py has the
+"""The ring build on the slot-code road keeps 4-byte ring words in LDS (hj_table.h RingWord; tests/test_ring_words.py has the
 word's arithmetic): (offset in the chunk << 7 | code) instead of (index << 32 | key). What a wavefront does with them --
 home attempts, looks, displacement, the budget decided before the step, the key read back for a drop and for a deferred
 tuple, the retire -- is checked here on the forced road (tables of 2^15 slots, reserve(..., slotCodes=True)) and once on the

@@ -1,4 +1,4 @@
-"""Slot codes (table format 2, hj_device.h SlotCode): the classic ring build of a context without row ids leaves ONE BYTE per
+"""Slot codes (table format 2, hj_table.h SlotCode): the classic ring build of a context without row ids leaves ONE BYTE per
 slot -- code = (hi << dbits) | d for the key homed d slots below with bits `hi` above the table size, 0xFF = empty -- and the
 probe, the checksums and the export read that byte. The road is taken by itself only from 2^27 slots on (where a byte holds
 any 32-bit key); here it is forced onto small tables with reserve(..., slotCodes=True) and every case asserts through

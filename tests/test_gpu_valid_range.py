@@ -1,4 +1,4 @@
-"""The valid slot range of the LDS builds, seen by every reader of the table (hj_device.h, Counters): a context first builds a
+"""The valid slot range of the LDS builds, seen by every reader of the table (hj_common.h, Counters): a context first builds a
 POISON relation that leaves a key on every slot outside a band, then builds R -- whose home slots are that band -- through
 the path under test, which writes only [validLo, validHiEx + 512). What lies outside is then really stale (asserted on the
 raw table words, hj_table_debug + hj_copy_d2h), the probe side asks for every stale key and for keys homed at the edges of

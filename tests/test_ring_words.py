@@ -1,4 +1,4 @@
-"""Ring words (hj_device.h RingWord, through hj_ring_word_layout_info: host-only arithmetic, no device): the 4-byte word a slot of a
+"""Ring words (hj_table.h RingWord, through hj_ring_word_layout_info: host-only arithmetic, no device): the 4-byte word a slot of a
 wavefront's LDS ring holds on the slot-code road, word = (rel << 7) | code. For probeLength 1, 2, 3, 4, 8 and tables of 2^15,
 2^27, 2^31, 2^32 slots EVERY displacement, EVERY high part a code holds and rel 0 and the largest the layout rule allows:
 read back, stepped, compared. The code is held to hj_slot_codes_info's description of the byte the slot ends with."""

@@ -1,6 +1,6 @@
 """Relations for the valid-slot-range tests (test_valid_range_cases.py on the CPU, test_gpu_valid_range.py on the device).
 
-An LDS build writes only the slots [validLo, validHiEx + 512) of the table (hj_device.h, Counters); everything else keeps
+An LDS build writes only the slots [validLo, validHiEx + 512) of the table (hj_common.h, Counters); everything else keeps
 what an earlier build on the same context left there. The builders here put a relation R on a chosen BAND of home slots,
 a POISON relation on every other slot of the same table, and a probe side that asks for every poison key and for keys homed
 right at the edges of the range the device reported. What R alone joins to -- the sequential oracle's answer -- is then what

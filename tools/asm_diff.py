@@ -3,12 +3,17 @@
 
     tools/asm_diff.py PARENT_TREE CHANGE_TREE
 
-Compiles every csrc/*.hip of both trees to gfx950 assembly with the Makefile's flags (device side only) and prints, per
-file, the kernels that exist on one side only and, per kernel, `identical` or `differs` with the resources of both sides
-(VGPRs, SGPRs, LDS bytes, scratch bytes, spilled SGPRs / VGPRs). Kernels are paired by demangled name without the
-argument list, so a kernel whose signature changed is compared with its former self. Instruction text is compared with symbol names, local
+Compiles the .hip files behind the objects of each tree's csrc/Makefile (its OBJS) to gfx950 assembly with the Makefile's
+flags (device side only) and prints, per kernel, `identical` or `differs` with the resources of both sides (VGPRs, SGPRs,
+LDS bytes, scratch bytes, spilled SGPRs / VGPRs), and the kernels that exist on one side only. Kernels are paired across
+the whole library by demangled name without the argument list: a kernel whose signature changed, or that moved to another
+file, is compared with its former self and listed under its new file with a note of the old one. A template kernel that
+several objects of a tree instantiate is compared copy by copy. Instruction text is compared with symbol names, local
 labels and comments taken out; the compilation-unit id never reaches it.
+
+A tree may also be a folder of assembly made earlier (*.s, one per translation unit).
 """
+import glob
 import os
 import re
 import subprocess
@@ -16,36 +21,40 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["hj_kernels", "hj_build_own", "hj_build_wave", "hj_htm", "hj_pairs", "hj_r_marks", "hj_gather", "hj_keys", "hj_where", "hj_asof", "hj_agg", "hj_sort",
-         "hj_prj",      # its translation unit includes hj_prj_pairs.hip and hj_prj_agg.hip: their kernels are listed under it
-         "hj_api",
-         "hj_api_table", "hj_api_prj", "hj_api_rows", "hj_api_tools"]
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-value --cuda-device-only -S".split()
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
+def makefile_units(src):
+    """the translation units of a tree: the objects of its Makefile's OBJS that have a .hip"""
+    text = open(os.path.join(src, "Makefile")).read().replace("\\\n", " ")
+    objs = re.search(r"^OBJS\s*:?=(.*)$", text, re.M).group(1)
+    names = re.findall(r"(\w+)\.o\b", objs)
+    return [n for n in names if os.path.exists(os.path.join(src, n + ".hip"))]
+
+
 def compile_tree(tree, out):
-    if os.path.exists(os.path.join(tree, FILES[0] + ".s")):        # a folder of assembly made earlier
-        for f in FILES:
-            os.symlink(os.path.abspath(os.path.join(tree, f + ".s")), os.path.join(out, f + ".s"))
-        return
+    """-> [(unit, path of its assembly)]"""
+    made = sorted(glob.glob(os.path.join(tree, "*.s")))
+    if made:                                                        # a folder of assembly made earlier
+        return [(os.path.basename(p)[:-2], p) for p in made]
     src = os.path.join(tree, "htm-hashjoin_amd", "csrc")
+    units = makefile_units(src)
 
     def one(f):
-        if not os.path.exists(os.path.join(src, f + ".hip")):       # a file only the other tree has: no kernels on this side
-            open(os.path.join(out, f + ".s"), "w").close()
-            return
         subprocess.run([HIPCC, *FLAGS, f + ".hip", "-o", os.path.join(out, f + ".s")], cwd=src, check=True,
                        stderr=subprocess.DEVNULL)
-    with ThreadPoolExecutor(len(FILES)) as ex:
-        list(ex.map(one, FILES))
+    with ThreadPoolExecutor(min(len(units), os.cpu_count() or 4)) as ex:
+        list(ex.map(one, units))
+    return [(f, os.path.join(out, f + ".s")) for f in units]
 
 
 def demangle(names):
     if not names:
         return {}
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {n: re.sub(r"\(.*", "", d).replace("void ", "").replace("hj::", "") for n, d in zip(names, out)}
+    return {n: re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void ", "").replace("hj::", "")
+            for n, d in zip(names, out)}
 
 
 def kernels(path):
@@ -76,33 +85,60 @@ def kernels(path):
     return out
 
 
+def library(units):
+    """{kernel name: [(unit, text, resources)]} over a tree's units, in their order"""
+    lib = {}
+    for unit, path in units:
+        ks = kernels(path)
+        dm = demangle(sorted(ks))
+        for sym in sorted(ks, key=lambda s: dm[s]):
+            lib.setdefault(dm[sym], []).append((unit, *ks[sym]))
+    return lib
+
+
 def fmt(r):
     return "%d / %d / %d / %d / %d+%d" % (r["vgpr"], r["sgpr"], r["lds"], r["scratch"], r["sspill"], r["vspill"])
+
+
+def pairs_of(pa, ca):
+    """every copy of one kernel with its counterpart: the copy of the same unit if the other side has one, else its first"""
+    def partner(x, others):
+        return next((o for o in others if o[0] == x[0]), others[0])
+    out = [(partner(c, pa), c) for c in ca]
+    used = {id(p) for p, _ in out}
+    return out + [(p, partner(p, ca)) for p in pa if id(p) not in used]
+
+
+def compare(parent_units, change_units):
+    """-> rows (unit, kernel, verdict, parent resources, change resources), kernels identical, kernels that differ"""
+    a, b = library(parent_units), library(change_units)
+    rows, same, differs = [], 0, 0
+    for k in set(a) | set(b):
+        if k not in a or k not in b:
+            for unit, _, r in a.get(k) or b[k]:
+                rows.append((unit, k, "only in " + ("parent" if k in a else "change"), fmt(r) if k in a else "", fmt(r) if k in b else ""))
+            continue
+        for p, c in pairs_of(a[k], b[k]):
+            note = "" if p[0] == c[0] else " (parent: %s)" % p[0]
+            if p[1] == c[1] and p[2] == c[2]:
+                same += 1
+                rows.append((c[0], k, "identical" + note, "", ""))
+            else:
+                differs += 1
+                rows.append((c[0], k, "differs" + note, fmt(p[2]), fmt(c[2])))
+    order = {u: i for i, (u, _) in enumerate(change_units)}
+    rows.sort(key=lambda r: (order.get(r[0], len(order)), r[0], r[1], r[2]))
+    return rows, same, differs
 
 
 def main():
     parent, change = sys.argv[1], sys.argv[2]
     with tempfile.TemporaryDirectory() as tp, tempfile.TemporaryDirectory() as tc:
-        compile_tree(parent, tp)
-        compile_tree(change, tc)
-        same = differs = 0
+        rows, same, differs = compare(compile_tree(parent, tp), compile_tree(change, tc))
         print("| file | kernel | machine code | parent: VGPR / SGPR / LDS / scratch / spills (s+v) | change |")
         print("|---|---|---|---|---|")
-        for f in FILES:
-            a, b = kernels(os.path.join(tp, f + ".s")), kernels(os.path.join(tc, f + ".s"))
-            # paired by demangled name without the argument list: a kernel whose signature changed is still the same kernel
-            dm = demangle(sorted(set(a) | set(b)))
-            a, b = {dm[k]: v for k, v in a.items()}, {dm[k]: v for k, v in b.items()}
-            for k in sorted(set(a) | set(b)):
-                if k not in a or k not in b:
-                    print("| %s | `%s` | only in %s | %s | %s |" % (f, k, "parent" if k in a else "change",
-                                                                   fmt(a[k][1]) if k in a else "", fmt(b[k][1]) if k in b else ""))
-                elif a[k][0] == b[k][0] and a[k][1] == b[k][1]:
-                    same += 1
-                    print("| %s | `%s` | identical | | |" % (f, k))
-                else:
-                    differs += 1
-                    print("| %s | `%s` | differs | %s | %s |" % (f, k, fmt(a[k][1]), fmt(b[k][1])))
+        for unit, k, verdict, ra, rb in rows:
+            print("| %s | `%s` | %s | %s | %s |" % (unit, k, verdict, ra, rb))
         print("\n%d kernels identical, %d differ" % (same, differs))
 
 
