@@ -57,6 +57,10 @@ ASOF_OPS = {op: CMP_OPS[op] for op in (">=", ">", "<=", "<")}
 # hj_sort_rows_dev: columns of one call, and hj_sort_col.flags
 HJ_SORT_MAX_COLS = 4
 HJ_SORT_DESC, HJ_SORT_NULLS_FIRST = 0x1, 0x2
+# hj_window_rows_dev: functions of one call, and hj_win_op
+HJ_WIN_MAX_FUNCS = 8
+(HJ_WIN_ROW_NUMBER, HJ_WIN_RANK, HJ_WIN_DENSE_RANK, HJ_WIN_PART_ROWS, HJ_WIN_LAG, HJ_WIN_LEAD, HJ_WIN_FIRST_ROW, HJ_WIN_LAST_ROW,
+ HJ_WIN_RUN_COUNT, HJ_WIN_RUN_SUM, HJ_WIN_RUN_MIN, HJ_WIN_RUN_MAX) = range(12)
 # aggregating joins (hj_agg_op, hj_agg_spec.flags)
 HJ_AGG_MAX_COLS = 4
 HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
@@ -175,6 +179,18 @@ class hj_sort_col(C.Structure):
     ]
 
 
+class hj_win_func(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("srcValid", C.c_void_p),
+        ("out", C.c_void_p),
+        ("op", C.c_uint32),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("offset", C.c_uint32),
+    ]
+
+
 class hj_agg_spec(C.Structure):
     _fields_ = [
         ("op", C.c_uint32),
@@ -243,6 +259,10 @@ def _declare(lib):
         "hj_sort_rows_info": ([vp, P(u64)], i32),
         "hj_sort_rows_host": ([P(hj_sort_col), u32, u64, vp, P(u64)], i32),
         "hj_sort_layout_info": ([u64, P(u64)], i32),
+        "hj_window_rows_dev": ([vp, vp, u64, u64, vp, P(hj_sort_col), u32, P(hj_win_func), u32], i32),
+        "hj_window_rows_info": ([vp, P(u64)], i32),
+        "hj_window_rows_host": ([vp, u64, u64, vp, P(hj_sort_col), u32, P(hj_win_func), u32, P(u64)], i32),
+        "hj_window_layout_info": ([u64, P(u64)], i32),
         "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
         "hj_where_info": ([vp, P(u64)], i32),
         "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),

@@ -1,5 +1,5 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns and sorted by them, the
+// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns and sorted by them, the window functions along a permutation, the
 // join conditions beyond equality, the as-of step, and the *_info entry point of every call that has a record (hj_host.h:
 // CallRecord). Host-side glue only.
 #include "hj_host.h"
@@ -425,11 +425,9 @@ int hj_key_groups_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, u
 
 // ---- rows in the order of their columns (hj_sort.hip) -------------------------
 // hj_sort_rows_dev's and hj_sort_rows_host's arguments -> the kernels' columns; the message of what is wrong, or nullptr
-static const char* sort_args(const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, const uint32_t* perm, SortCols* k)
+// the columns themselves: what hj_sort_rows_* and hj_window_rows_* (its order columns) refuse of one
+static const char* sort_cols_error(const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, SortCols* k)
 {
-    if (nCols == 0 || nCols > HJ_SORT_MAX_COLS) return "nCols must be 1 .. HJ_SORT_MAX_COLS";
-    if (!cols) return "cols NULL";
-    if (nRows > 0xFFFFFFFEull) return "nRows above 2^32 - 2";
     for (uint32_t i = 0; i < nCols; ++i) {
         const hj_sort_col& col = cols[i];
         if (col.type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
@@ -441,6 +439,15 @@ static const char* sort_args(const hj_sort_col* cols, uint32_t nCols, uint64_t n
         if (nRows && !word_ptr_ok(col.valid)) return "a validity pointer that is not 4-byte aligned";
         k->p[i] = col.values; k->valid[i] = col.valid; k->width[i] = col.width; k->type[i] = col.type; k->flags[i] = col.flags;
     }
+    return nullptr;
+}
+
+static const char* sort_args(const hj_sort_col* cols, uint32_t nCols, uint64_t nRows, const uint32_t* perm, SortCols* k)
+{
+    if (nCols == 0 || nCols > HJ_SORT_MAX_COLS) return "nCols must be 1 .. HJ_SORT_MAX_COLS";
+    if (!cols) return "cols NULL";
+    if (nRows > 0xFFFFFFFEull) return "nRows above 2^32 - 2";
+    if (const char* what = sort_cols_error(cols, nCols, nRows, k)) return what;
     if (nRows && (!perm || !word_ptr_ok(perm))) return "dPerm NULL or not 4-byte aligned";
     return nullptr;
 }
@@ -491,6 +498,97 @@ int hj_sort_layout_info(uint64_t nRows, uint64_t out[4])
     if (!out || nRows > 0xFFFFFFFEull) return HJ_ERR_INVALID;
     const SortLayout l = sort_layout(nRows, 8);
     out[0] = l.tileRows; out[1] = l.chunkRows; out[2] = l.chunks; out[3] = l.bytes;
+    return HJ_OK;
+}
+
+// ---- window functions over the runs along a permutation (hj_window.hip) --------
+// hj_window_rows_dev's and hj_window_rows_host's arguments -> the kernels' columns and functions; the message of what is wrong, or nullptr
+static const char* window_args(const uint32_t* perm, uint64_t nPos, uint64_t nRows, const uint32_t* part, const hj_sort_col* order, uint32_t nOrder,
+                               const hj_win_func* funcs, uint32_t nFuncs, SortCols* k, WinFuncs* w)
+{
+    if (nFuncs == 0 || nFuncs > HJ_WIN_MAX_FUNCS) return "nFuncs must be 1 .. HJ_WIN_MAX_FUNCS";
+    if (!funcs) return "funcs NULL";
+    if (nPos > 0xFFFFFFFEull || nRows > 0xFFFFFFFEull) return "nPos or nRows above 2^32 - 2";
+    if (nOrder > HJ_SORT_MAX_COLS) return "nOrder above HJ_SORT_MAX_COLS";
+    if (nOrder && !order) return "order NULL with nOrder > 0";
+    if (const char* what = sort_cols_error(order, nOrder, nRows, k)) return what;
+    if (!perm && nPos > nRows) return "dPerm NULL with nPos > nRows";
+    if (!word_ptr_ok(perm) || !word_ptr_ok(part)) return "dPerm or dPart not 4-byte aligned";
+    for (uint32_t i = 0; i < nFuncs; ++i) {
+        const hj_win_func& f = funcs[i];
+        if (f.op > HJ_WIN_RUN_MAX) return "op must be an hj_win_op";
+        const bool run = f.op >= HJ_WIN_RUN_COUNT, reads = f.op > HJ_WIN_RUN_COUNT;
+        const bool widthOk = reads ? (f.width == 4 || f.width == 8) : run ? (f.width == 0 || f.width == 4 || f.width == 8) : f.width == 0;
+        if (!widthOk) return "a width that the op does not have (RUN_SUM / MIN / MAX: 4 or 8; RUN_COUNT: 0, 4 or 8; else 0)";
+        if (f.flags & ~(run ? HJ_AGG_SIGNED : 0u)) return "hj_win_func.flags has bits other than HJ_AGG_SIGNED, or any outside RUN_*";
+        if (f.offset && f.op != HJ_WIN_LAG && f.op != HJ_WIN_LEAD) return "offset != 0 outside LAG / LEAD";
+        if (!col_ptr_ok(f.out, run ? 8 : 4)) return "an out that is NULL or not aligned to its entries";
+        if (reads && nRows && !col_ptr_ok(f.src, f.width)) return "a src that is NULL or not aligned to its width";
+        if (!word_ptr_ok(f.srcValid)) return "a srcValid that is not 4-byte aligned";
+        w->src[i] = f.src; w->valid[i] = run ? f.srcValid : nullptr; w->out[i] = f.out;
+        w->op[i] = f.op; w->width[i] = f.width; w->sgn[i] = f.flags & HJ_AGG_SIGNED; w->offset[i] = f.offset;
+    }
+    return nullptr;
+}
+
+int hj_window_rows_dev(hj_ctx* c, const uint32_t* dPerm, uint64_t nPos, uint64_t nRows, const uint32_t* dPart, const hj_sort_col* order,
+                       uint32_t nOrder, const hj_win_func* funcs, uint32_t nFuncs)
+{
+    HJ_ENTER(c, true);
+    SortCols k{};
+    WinFuncs w{};
+    if (const char* what = window_args(dPerm, nPos, nRows, dPart, order, nOrder, funcs, nFuncs, &k, &w))
+        return fail(c, HJ_ERR_INVALID, "hj_window_rows_dev", what);
+    HJ_HIP(c, hipSetDevice(c->device));
+    const WindowLayout l = window_layout(nPos);
+    if (const int rc = c->buf[B_WINDOW_CTR].reserve(c, 3 * sizeof(unsigned long long))) return rc;
+    if (nPos)
+        if (const int rc = c->buf[B_WINDOW_WORK].reserve(c, l.bytes)) return rc;
+    HJ_HIP(c, hipEventRecord(c->call[CALL_WINDOW].ev[0], c->stream));
+    HJ_HIP(c, launch_window_rows(dPerm, nPos, (uint32_t)nRows, dPart, k, nOrder, w, nFuncs, c->buf[B_WINDOW_WORK].p,
+                                 c->buf[B_WINDOW_CTR].as<unsigned long long>(), c->stream));
+    c->window = {};
+    if (nPos) c->window = {l.chunks, l.bytes};
+    return call_end(c, CALL_WINDOW, 0, nPos);
+}
+
+int hj_window_rows_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_WINDOW];
+    for (int i = 4; i < 8; ++i) out[i] = 0;
+    uint64_t t[4];
+    if (const int rc = call_info(c, r, nullptr, 0, t)) return rc;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!r.called || !r.rows) return HJ_OK;                     // no position: nothing was enqueued between the two events
+    unsigned long long totals[3];
+    HJ_HIP(c, hipMemcpy(totals, c->buf[B_WINDOW_CTR].p, sizeof(totals), hipMemcpyDeviceToHost));
+    out[0] = r.rows; out[1] = totals[0]; out[2] = totals[1]; out[3] = t[2]; out[4] = totals[2];
+    out[5] = c->window.chunks; out[6] = c->window.bytes;
+    return HJ_OK;
+}
+
+int hj_window_rows_host(const uint32_t* perm, uint64_t nPos, uint64_t nRows, const uint32_t* part, const hj_sort_col* order, uint32_t nOrder,
+                        const hj_win_func* funcs, uint32_t nFuncs, uint64_t out[8])
+{
+    SortCols k{};
+    WinFuncs w{};
+    if (window_args(perm, nPos, nRows, part, order, nOrder, funcs, nFuncs, &k, &w)) return HJ_ERR_INVALID;
+    uint64_t totals[3];
+    window_rows_host(perm, nPos, (uint32_t)nRows, part, k, nOrder, w, nFuncs, totals);
+    if (!out) return HJ_OK;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!nPos) return HJ_OK;
+    const WindowLayout l = window_layout(nPos);
+    out[0] = nPos; out[1] = totals[0]; out[2] = totals[1]; out[4] = totals[2]; out[5] = l.chunks; out[6] = l.bytes;
+    return HJ_OK;
+}
+
+int hj_window_layout_info(uint64_t nPos, uint64_t out[4])
+{
+    if (!out || nPos > 0xFFFFFFFEull) return HJ_ERR_INVALID;
+    const WindowLayout l = window_layout(nPos);
+    out[0] = l.tilePos; out[1] = l.chunkPos; out[2] = l.chunks; out[3] = l.bytes;
     return HJ_OK;
 }
 

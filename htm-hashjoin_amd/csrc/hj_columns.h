@@ -1,5 +1,6 @@
 // hj_columns.h -- the relational layer's column code: validity and mark bits, gather, key columns, groups, join
-// conditions and as-of (how two elements compare and order), sort keys, and the aggregates over a pair list.
+// conditions and as-of (how two elements compare and order), sort keys, the aggregates over a pair list, and the window
+// functions along a permutation.
 // Column descriptors as the kernels take them, the element helpers host and device share, and the launchers.
 #pragma once
 
@@ -299,5 +300,96 @@ struct PairAggCols { AggSrc src; AggOps ops; unsigned long long* acc[kAggMaxCols
 hipError_t launch_pairs_agg(const uint32_t* mapG, const uint32_t* mapV, uint64_t nPairs, uint32_t gBase, uint32_t gRows, uint32_t vBase,
                             uint32_t vRows, const PairAggCols& cols, uint32_t nCols, unsigned long long* count, unsigned long long* counts,
                             hipStream_t s);
+
+// ---- window functions over runs along a permutation (defined in hj_window.hip) ----
+// What the kernels and the host loop share: how a position's head bits come about (win_head: partition head, peer head,
+// skipped entry), and the running accumulators (win_identity / win_op / win_value: hj_pairs_agg_dev's values, 64 bits wide).
+constexpr uint32_t kWinMaxFuncs = 8;          // HJ_WIN_MAX_FUNCS
+constexpr uint32_t kWinRowNumber = 0, kWinRank = 1, kWinDenseRank = 2, kWinPartRows = 3, kWinLag = 4, kWinLead = 5, kWinFirstRow = 6,
+                   kWinLastRow = 7, kWinRunCount = 8, kWinRunMax = 11;                        // hj_win_op
+// the head byte of a position: it starts a partition, it starts a peer run (set with every partition head), its entry is
+// HJ_NO_ROW or at / behind nRows (then all three are set: the entry is a run of its own and belongs to no partition)
+constexpr uint32_t kHeadPart = 1u, kHeadPeer = 2u, kHeadSkip = 4u;
+// element i of a column of `width` bytes, zero-extended; the pointer is aligned to the width
+__host__ __device__ __forceinline__ uint64_t win_elem(const void* col, uint32_t width, uint32_t i)
+{
+    switch (width) {
+        case 1: return static_cast<const uint8_t*>(col)[i];
+        case 2: return static_cast<const uint16_t*>(col)[i];
+        case 4: return static_cast<const uint32_t*>(col)[i];
+        default: return static_cast<const unsigned long long*>(col)[i];
+    }
+}
+// rows a and b tie in every order column: both NULL, or both valid with one sort_key (the flags do not change equality)
+__host__ __device__ __forceinline__ bool win_peers(const SortCols& cols, uint32_t nOrder, uint32_t a, uint32_t b)
+{
+    bool same = true;
+#pragma unroll
+    for (uint32_t c = 0; c < kSortMaxCols; ++c) {
+        if (c >= nOrder) break;
+        const bool va = !cols.valid[c] || valid_bit(cols.valid[c], a), vb = !cols.valid[c] || valid_bit(cols.valid[c], b);
+        if (va && vb)
+            same = same && sort_key(cols.type[c], cols.width[c], 0u, win_elem(cols.p[c], cols.width[c], a)) ==
+                               sort_key(cols.type[c], cols.width[c], 0u, win_elem(cols.p[c], cols.width[c], b));
+        else same = same && va == vb;
+    }
+    return same;
+}
+// the head byte of position p. perm null: the identity (the caller has checked nPos <= nRows). part null: one value.
+__host__ __device__ __forceinline__ uint32_t win_head(const uint32_t* perm, uint64_t p, uint32_t nRows, const uint32_t* part,
+                                                      const SortCols& cols, uint32_t nOrder)
+{
+    const uint32_t row = perm ? perm[p] : (uint32_t)p;
+    if (row >= nRows) return kHeadPart | kHeadPeer | kHeadSkip;         // HJ_NO_ROW too: nRows <= 2^32 - 2
+    if (p == 0) return kHeadPart | kHeadPeer;
+    const uint32_t prev = perm ? perm[p - 1] : (uint32_t)(p - 1);
+    if (prev >= nRows || (part && part[row] != part[prev])) return kHeadPart | kHeadPeer;
+    return win_peers(cols, nOrder, row, prev) ? 0u : kHeadPeer;
+}
+// The accumulators: op is an hj_agg_op (kAggCount .. kAggMax), T uint32_t (positions and counts) or 64 bits wide (values)
+template <class T>
+__host__ __device__ __forceinline__ T win_identity(uint32_t op, uint32_t sgn)
+{
+    constexpr T top = (T)1 << (8 * sizeof(T) - 1);
+    if (op == kAggMin) return sgn ? (T)(top - 1) : (T)~(T)0;
+    if (op == kAggMax) return sgn ? top : (T)0;
+    return (T)0;
+}
+template <class T>
+__host__ __device__ __forceinline__ T win_op(uint32_t op, uint32_t sgn, T a, T b)
+{
+    if (op <= kAggSum) return a + b;
+    constexpr T top = (T)1 << (8 * sizeof(T) - 1);
+    const T flip = sgn ? top : (T)0;                                    // the order of the signed values as unsigned ones
+    const bool less = (T)(a ^ flip) < (T)(b ^ flip);
+    return (op == kAggMin) == less ? a : b;
+}
+// what row `row` brings to a running op: COUNT 1, else the element sign- or zero-extended; under a NULL the identity
+__host__ __device__ __forceinline__ unsigned long long win_value(const void* src, const uint32_t* valid, uint32_t op, uint32_t width,
+                                                                 uint32_t sgn, uint32_t row)
+{
+    if (valid && !valid_bit(valid, row)) return win_identity<unsigned long long>(op, sgn);
+    if (op == kAggCount) return 1ull;
+    if (width == 8) return static_cast<const unsigned long long*>(src)[row];
+    const uint32_t w = static_cast<const uint32_t*>(src)[row];
+    return sgn ? (unsigned long long)(long long)(int32_t)w : (unsigned long long)w;
+}
+// The functions of a call as the kernels take them, by value in the kernel arguments (hj_win_func, include/htm_hashjoin.h);
+// op: the hj_win_op, sgn: HJ_AGG_SIGNED.
+struct WinFuncs { const void* src[kWinMaxFuncs]; const uint32_t* valid[kWinMaxFuncs]; void* out[kWinMaxFuncs];
+                  uint32_t op[kWinMaxFuncs], width[kWinMaxFuncs], sgn[kWinMaxFuncs], offset[kWinMaxFuncs]; };
+// How a call cuts nPos positions: a workgroup scans tilePos positions at a time and owns chunkPos (a multiple of it); at
+// most 4096 chunks at any nPos. The workspace: one head byte and one 4-byte end per position, and the chunk summaries
+// (their size does not depend on nPos). bytes is monotone in nPos.
+struct WindowLayout { uint32_t tilePos, chunkPos, chunks; size_t headBytes, endBytes, sumBytes, bytes; };
+WindowLayout window_layout(uint64_t nPos);
+// out[row(p)] of every function for p in [0, nPos): see hj_window_rows_dev. work: window_layout(nPos).bytes. totals: three
+// 64-bit words, written here -- partitions, peer runs, entries skipped. The caller has checked what the header says the
+// entry point refuses. nPos 0 enqueues nothing.
+hipError_t launch_window_rows(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const SortCols& order, uint32_t nOrder,
+                              const WinFuncs& funcs, uint32_t nFuncs, void* work, unsigned long long* totals, hipStream_t s);
+// the same in one sequential loop over host pointers; totals as above
+void window_rows_host(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const SortCols& order, uint32_t nOrder,
+                      const WinFuncs& funcs, uint32_t nFuncs, uint64_t totals[3]);
 
 }  // namespace hj

@@ -43,6 +43,8 @@ enum Buf {
     B_GROUPS_CTR,               // hj_key_groups_dev: probe steps, word collisions, NULL-keyed rows and the failure word of its last call (four 64-bit words)
     B_GROUPS_WORK,              // ... and its workspace (key_groups_work_bytes(nRows): the table, the first-row plane, the ranks, the sweep's counts), grown by the call
     B_SORT_WORK,                // hj_sort_rows_dev: its workspace (sort_layout(nRows, key bytes).bytes: two key planes, two row planes, the histogram, the scan sums), grown by the call
+    B_WINDOW_CTR,               // hj_window_rows_dev: the partitions, peer runs and skipped entries of its last call (three 64-bit words)
+    B_WINDOW_WORK,              // ... and its workspace (window_layout(nPos).bytes: the head bytes, the end plane, the chunk summaries), grown by the call
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -62,7 +64,7 @@ struct DevBuf {
 
 // The last call of one kind, as its *_info entry point reports it (call_info, hj_api_rows.hip): what the caller asked for,
 // and the pair of events around the call's work. `called` and `timed` die separately: see hj_ctx::call.
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_COUNT };
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
@@ -143,10 +145,12 @@ struct hj_ctx {
     struct Agg { bool on = false; uint32_t nCols = 0; uint64_t nR = 0, probes = 0; hj::AggOps ops{}; } agg;
     // ---- the last call of each kind (CallRecord). begin_operation forgets the TIME of the pairs call (its facts stay) and
     // the whole R-rows call, which hj_reserve also forgets with the plane; the two gathers, the verify step, the condition step
-    // (hj_pairs_where_dev), the as-of step (hj_pairs_asof_dev), the grouping of a table's rows (hj_key_groups_dev), the sort of a table's rows (hj_sort_rows_dev) and the sweep of a caller's plane belong to no build and no operation and are never forgotten.
+    // (hj_pairs_where_dev), the as-of step (hj_pairs_asof_dev), the grouping of a table's rows (hj_key_groups_dev), the sort of a table's rows (hj_sort_rows_dev), the window step (hj_window_rows_dev) and the sweep of a caller's plane belong to no build and no operation and are never forgotten.
     hjapi::CallRecord call[hjapi::CALL_COUNT];
     // ---- the last hj_sort_rows_dev beyond its record: the passes it launched and how it cut the rows (hj_sort_rows_info)
     struct Sort { uint64_t passes = 0, chunks = 0, chunkRows = 0, bytes = 0; } sort;
+    // ---- the last hj_window_rows_dev beyond its record: how it cut the positions (hj_window_rows_info)
+    struct Window { uint64_t chunks = 0, bytes = 0; } window;
     // ---- streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev). Reset by zipf_release (open, close, destroy).
     struct Zipf {
         hjhost::GlibcRand* rng = nullptr;

@@ -183,6 +183,7 @@ SHARD_ONE_BASED = 0x100
 
 _KEY_GROUPS_INFO = ("groups", "written", "us", "null_rows", "slots", "probe_steps", "collisions", "failure")
 _SORT_ROWS_INFO = ("rows", "passes", "us", "skipped", "chunks", "chunk_rows", "workspace_bytes", "reserved")
+_WINDOW_ROWS_INFO = ("positions", "partitions", "peer_runs", "us", "skipped", "chunks", "workspace_bytes", "reserved")
 
 
 def _sort_cols(cols):
@@ -192,6 +193,27 @@ def _sort_cols(cols):
     for c, (values, valid, width, type_, flags) in zip(arr, cols):
         c.values, c.valid, c.width, c.type, c.flags, c.reserved = values or None, valid or None, width, type_, flags, 0
     return arr, len(cols)
+
+
+def _win_funcs(funcs):
+    """[(op, out_ptr, src_ptr, valid_ptr, width, flags, offset)], whatever follows the out pointer optional (0) -> (hj_win_func
+    array, its length)"""
+    funcs = [tuple(f) + (0,) * (7 - len(f)) for f in funcs]
+    arr = (_lib.hj_win_func * max(len(funcs), 1))()
+    for a, (op, out, src, valid, width, flags, offset) in zip(arr, funcs):
+        a.src, a.srcValid, a.out = src or None, valid or None, out or None
+        a.op, a.width, a.flags, a.offset = op, width, flags, offset
+    return arr, len(funcs)
+
+
+def window_layout_info(n_pos):
+    """hj_window_layout_info: how hj_window_rows_dev cuts n_pos positions -- tile positions, chunk positions, chunks,
+    workspace bytes. Host-only; no device."""
+    out = (C.c_uint64 * 4)()
+    rc = lib.hj_window_layout_info(int(n_pos), out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_window_layout_info")
+    return {"tile": int(out[0]), "chunk": int(out[1]), "chunks": int(out[2]), "workspace_bytes": int(out[3])}
 
 
 def _key_cols(cols):
@@ -475,6 +497,26 @@ class HashJoinContext:
         """hj_sort_rows_info (waits for the stream), about the last sort_rows: rows, radix passes, the device time of the
         whole call (us), passes skipped (always 0), chunks, chunk_rows, workspace_bytes"""
         return dict(zip(_SORT_ROWS_INFO, self._info(lib.hj_sort_rows_info, 8)))
+
+    # ---- window functions over the runs along a permutation --------------------------
+    def window_rows(self, d_perm, n_pos, n_rows, d_part, order, funcs):
+        """hj_window_rows_dev: f(...) OVER (PARTITION BY .. ORDER BY ..) along d_perm[0 .. n_pos) (0: the identity). A
+        partition is a maximal run of positions whose d_part[row] are equal (0: one value), peers are the rows that tie in
+        every column of `order` (tuples as sort_rows takes them; the flags do not matter). funcs = 1 to HJ_WIN_MAX_FUNCS
+        tuples (op, out_ptr[, src_ptr, valid_ptr, width, flags, offset]): op an hj_win_op, out n_rows entries INDEXED BY
+        ROW -- uint32 for the numbering ops and the row maps (LAG / LEAD by `offset`, first, last: gather maps with NO_ROW
+        holes), 8 bytes for the running COUNT / SUM / MIN / MAX over src (width 4 or 8, flags HJ_AGG_SIGNED, valid_ptr the
+        validity plane). An entry of d_perm that is NO_ROW or >= n_rows writes nothing and ends the run; a row at no
+        position keeps what its out entries held. Asynchronous; needs no reserve and no table; the workspace belongs to
+        the context and grows with n_pos."""
+        o_arr, n_order = _sort_cols(order)
+        f_arr, n_funcs = _win_funcs(funcs)
+        self._check(lib.hj_window_rows_dev(self._h, _vp(d_perm), n_pos, n_rows, _vp(d_part), o_arr, n_order, f_arr, n_funcs))
+
+    def window_rows_info(self):
+        """hj_window_rows_info (waits for the stream), about the last window_rows: positions, partitions, peer_runs, the
+        device time of the whole call (us), skipped entries, chunks, workspace_bytes"""
+        return dict(zip(_WINDOW_ROWS_INFO, self._info(lib.hj_window_rows_info, 8)))
 
     # ---- join conditions beyond equality ------------------------------------------
     def pairs_where(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, terms, d_out_s, d_out_r, capacity,

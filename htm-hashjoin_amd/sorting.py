@@ -85,13 +85,15 @@ def sort_rows_host(keys, descending=False, nulls="last"):
 
 class _SortedRows:
     """What sort_rows and sort_by_columns share: the key columns on the device, one hj_sort_rows_dev over them, and the
-    permutation it left in d_perm. dev: the _DevColumn of every key column, for a gather behind it."""
+    permutation it left in d_perm. dev: the _DevColumn of every key column, for a gather behind it. lead: descriptors of
+    columns that lie on the device already (window_rows' partition ids), more significant than cols; n: the rows, where
+    cols may be empty."""
 
-    def __init__(self, ctx, held, cols):
-        self.n = cols[0][0].rows
+    def __init__(self, ctx, held, cols, lead=(), n=None):
+        self.n = cols[0][0].rows if n is None else n
         self.dev = [_DevColumn.whole(ctx, held, c) for c, _, _ in cols]
         self.d_perm = held.alloc(4 * self.n)
-        ctx.sort_rows([(d.parts[0], d.parts[2], c.width, t, f) for d, (c, t, f) in zip(self.dev, cols)], self.n, self.d_perm)
+        ctx.sort_rows(list(lead) + [(d.parts[0], d.parts[2], c.width, t, f) for d, (c, t, f) in zip(self.dev, cols)], self.n, self.d_perm)
 
 
 def sort_rows(keys, descending=False, nulls="last", device=0):

@@ -739,6 +739,83 @@ int hj_sort_rows_host(const hj_sort_col *cols, uint32_t nCols, uint64_t nRows, u
  * chunks (at most 4096 at any nRows: the histogram of a pass is bounded by 256 x 4096 words = 4 MiB), out[3] = workspace
  * bytes with 8-byte keys (monotone in nRows). HJ_ERR_INVALID for out NULL or nRows above 2^32 - 2. */
 int hj_sort_layout_info(uint64_t nRows, uint64_t out[4]);
+/* ---- window functions over sorted rows: f(...) OVER (PARTITION BY keys ORDER BY cols) ----
+ * The step between the sort and the gather: hj_key_groups_dev gives every row a dense partition id, hj_sort_rows_dev over
+ * (id, order columns) puts every partition in order, and hj_window_rows_dev scans along that permutation: ROW_NUMBER, RANK,
+ * DENSE_RANK, the rows of the partition, LAG / LEAD / first / last row as gather maps (hj_gather_dev / hj_gather2_dev turn
+ * them into values with NULLs, strings included), and running COUNT / SUM / MIN / MAX.
+ * Everything is defined on RUNS along dPerm, not on sortedness: the call is exact for any dPerm, and the host twin is one
+ * sequential loop. For position p in [0, nPos), row(p) = dPerm[p]; dPerm NULL is the identity and needs nPos <= nRows.
+ *   An entry that is HJ_NO_ROW or >= nRows is never dereferenced and writes nothing; it is counted apart (info out[4]). It
+ *     ends the run in front of it, and the next position starts a new one. It is in no partition and no peer run.
+ *   The partition of p, [start(p), end(p)], is the maximal run of in-range positions around p whose dPart[row] are equal.
+ *     The ids are compared for equality only, HJ_NO_ROW is a value like any other; dPart NULL: one value everywhere.
+ *   Two rows are peers when in every one of the nOrder columns both are NULL, or both are valid and their order keys are
+ *     equal -- the sort's own tie: -0.0 == 0.0, every NaN equals every NaN, the bytes under a NULL are never compared. The
+ *     column flags do not change equality. nOrder 0: all rows of a partition are peers. peerStart(p) is the lowest q in
+ *     [start(p), p] such that q .. p are all peers of p.
+ * out[row(p)] of a function:
+ *   HJ_WIN_ROW_NUMBER  p - start + 1                      HJ_WIN_RANK       peerStart - start + 1
+ *   HJ_WIN_DENSE_RANK  the peer runs that start in [start, p]      HJ_WIN_PART_ROWS  end - start + 1
+ *   HJ_WIN_LAG         dPerm[p - offset] if p - offset >= start, else HJ_NO_ROW (no wrap for an offset above p)
+ *   HJ_WIN_LEAD        dPerm[p + offset] if p + offset <= end, else HJ_NO_ROW (no wrap near 2^32)
+ *   HJ_WIN_FIRST_ROW   dPerm[start]                       HJ_WIN_LAST_ROW   dPerm[end]
+ *   HJ_WIN_RUN_*       COUNT / SUM / MIN / MAX over the valid elements src[row(q)], q in [start, p] -- the frame ROWS BETWEEN
+ *     UNBOUNDED PRECEDING AND CURRENT ROW (pandas' cumsum), unique because the order along dPerm is fixed. Values, sign
+ *     extension, wrap-around (SUM modulo 2^64) and the identity where the frame holds no valid element are
+ *     hj_pairs_agg_dev's. RUN_COUNT counts the valid elements, or the positions when srcValid is NULL. There is no output
+ *     validity: whether a SUM / MIN / MAX saw a value is RUN_COUNT of the same column > 0. Integers only.
+ * A row that occurs at no position is not written: `out` keeps what the caller put there. A row that occurs at two
+ * positions keeps one of its two results (unspecified); nothing else is affected.
+ * Method (hj_window.hip): segmented scans over positions in five launches -- head bits, per-chunk summaries, one
+ * workgroup over the at most 4096 summaries, end(p) from the back where a function needs it, and one pass that computes
+ * every function of the call. No workgroup waits for another, no atomic; every loop is bounded by the chunk.
+ * Cost: two scattered rows per position for the head bits; per RUN function two scattered reads of its source (fewer
+ * where partitions are short); per function and position one scattered 4- or 8-byte store. With dPerm NULL all of it is
+ * coalesced.
+ * Asynchronous on the context's stream; nPos 0 enqueues nothing. Needs no hj_reserve, no table and no state; touches no
+ * counter and no other *_info. The workspace (hj_window_layout_info) belongs to the context and only grows: a call that
+ * needs more waits for the stream once. `funcs` and `order` are host memory and are read before the call returns. Outputs
+ * must not alias each other, dPerm, dPart or a column. Nothing is written outside out[0 .. nRows) of each function.
+ * HJ_ERR_INVALID (nothing is enqueued, nothing written; also for a NULL context): nFuncs 0 or above HJ_WIN_MAX_FUNCS, funcs
+ * NULL; an op above HJ_WIN_RUN_MAX; a width the op does not have (RUN_SUM / MIN / MAX: 4 or 8; RUN_COUNT: 0, 4 or 8; else
+ * 0); flags other than HJ_AGG_SIGNED on a RUN_* op, or any on another; offset != 0 outside LAG / LEAD; an out that is NULL
+ * or not aligned to its entries (4 or 8 bytes); with nRows > 0 a src that is NULL or not aligned to its width where the
+ * op reads one (RUN_SUM / MIN / MAX); a srcValid that is not 4-byte aligned; nOrder above HJ_SORT_MAX_COLS, order NULL
+ * with nOrder > 0, or the column errors of hj_sort_rows_dev; dPerm NULL with nPos > nRows; dPerm or dPart not 4-byte
+ * aligned; nPos or nRows above 2^32 - 2. */
+#define HJ_WIN_MAX_FUNCS 8
+typedef enum {
+    HJ_WIN_ROW_NUMBER = 0, HJ_WIN_RANK = 1, HJ_WIN_DENSE_RANK = 2, HJ_WIN_PART_ROWS = 3,   /* out: uint32 per row   */
+    HJ_WIN_LAG = 4, HJ_WIN_LEAD = 5, HJ_WIN_FIRST_ROW = 6, HJ_WIN_LAST_ROW = 7,            /* out: uint32 row map   */
+    HJ_WIN_RUN_COUNT = 8, HJ_WIN_RUN_SUM = 9, HJ_WIN_RUN_MIN = 10, HJ_WIN_RUN_MAX = 11     /* out: 8 bytes per row  */
+} hj_win_op;
+typedef struct {
+    const void     *src;       /* RUN_*: nRows elements of `width` bytes; else ignored (may be NULL)            */
+    const uint32_t *srcValid;  /* RUN_*: NULL = no NULLs, else the plane hj_gather_dev writes                   */
+    void           *out;       /* nRows entries INDEXED BY ROW: 4 bytes (ops 0..7) or 8 bytes (ops 8..11)       */
+    uint32_t        op;        /* hj_win_op                                                                     */
+    uint32_t        width;     /* RUN_SUM/MIN/MAX: 4 or 8; RUN_COUNT: 0, 4 or 8; else 0                         */
+    uint32_t        flags;     /* HJ_AGG_SIGNED or 0 (RUN_* only)                                               */
+    uint32_t        offset;    /* LAG / LEAD: k (0 .. 2^32 - 1); else 0                                         */
+} hj_win_func;                 /* 40 bytes */
+int hj_window_rows_dev(hj_ctx *ctx, const uint32_t *dPerm, uint64_t nPos, uint64_t nRows, const uint32_t *dPart,
+                       const hj_sort_col *order, uint32_t nOrder, const hj_win_func *funcs, uint32_t nFuncs);
+/* Waits for the stream. About the last hj_window_rows_dev: out[0] = positions, out[1] = partitions (runs of in-range
+ * positions; a skipped entry is none), out[2] = peer runs, out[3] = the device time of the whole call in microseconds
+ * (rounded), out[4] = entries skipped as HJ_NO_ROW or out of range, out[5] = chunks, out[6] = workspace bytes the call
+ * needed, out[7] = 0. All 0 before the first call and after a call with nPos 0. */
+int hj_window_rows_info(hj_ctx *ctx, uint64_t out[8]);
+/* The same function on host pointers: no context, no device (the head test and the accumulate bodies are the kernels',
+ * around one sequential loop). `out` (may be NULL) is filled as hj_window_rows_info fills it, out[3] = 0. HJ_ERR_INVALID
+ * as hj_window_rows_dev; a refused call writes nothing. */
+int hj_window_rows_host(const uint32_t *perm, uint64_t nPos, uint64_t nRows, const uint32_t *part,
+                        const hj_sort_col *order, uint32_t nOrder, const hj_win_func *funcs, uint32_t nFuncs, uint64_t out[8]);
+/* How a call cuts nPos positions; a pure function, no context and no device: out[0] = tile positions (what one workgroup
+ * scans at a time), out[1] = chunk positions (what one workgroup owns, a multiple of the tile; grows with nPos), out[2] =
+ * chunks (at most 4096 at any nPos: one workgroup scans their summaries), out[3] = workspace bytes (one head byte and one
+ * 4-byte end per position, and the chunk summaries; monotone in nPos). HJ_ERR_INVALID for out NULL or nPos above 2^32 - 2. */
+int hj_window_layout_info(uint64_t nPos, uint64_t out[4]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
