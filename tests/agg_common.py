@@ -5,6 +5,8 @@ import numpy as np
 
 from htm_hashjoin_amd import _lib
 
+from gpu_harness import plane_words
+
 U64 = np.uint64
 COUNT, SUM, MIN, MAX = _lib.HJ_AGG_COUNT, _lib.HJ_AGG_SUM, _lib.HJ_AGG_MIN, _lib.HJ_AGG_MAX
 SIGNED = _lib.HJ_AGG_SIGNED
@@ -57,10 +59,7 @@ class Col:
         if self.valid is None:
             return None
         part = self.valid[lo:] if n is None else self.valid[lo:lo + n]
-        bits = np.packbits(part, bitorder="little")
-        w = np.zeros((part.size + 31) // 32 or 1, dtype=np.uint32)
-        w.view(np.uint8)[:bits.size] = bits
-        return w
+        return plane_words(part) if part.size else np.zeros(1, dtype=np.uint32)
 
 
 def reduce_at(acc, op, signed, idx, vals):

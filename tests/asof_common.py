@@ -10,6 +10,7 @@ import numpy as np
 from htm_hashjoin_amd import _lib
 
 import where_common as wc
+from gpu_harness import packed, plane_words, row_bits
 
 NO_ROW, U32, U64 = wc.NO_ROW, np.uint32, np.uint64
 ASOF_OPS = (">=", ">", "<=", "<")
@@ -49,8 +50,8 @@ def model_call(map_s, map_r, base, s_rows, r_rows, term, capacity=None):
     keep[ok] = best_row[s[ok]] == r[ok]         # every copy of the winning pair; an entry of NO_ROW equals no live r
     kept = int(keep.sum())
     cap = map_s.size if capacity is None else capacity
-    return {"keep": keep, "kept": wc.packed(map_s[keep], map_r[keep]), "s_marks": wc.mark_words(s[keep], s_rows),
-            "r_marks": wc.mark_words(r[keep], r_rows), "best_row": best_row, "info": (kept, min(kept, cap), 0, int((~ok).sum()))}
+    return {"keep": keep, "kept": packed(map_s[keep], map_r[keep]), "s_marks": plane_words(row_bits(s[keep], s_rows)),
+            "r_marks": plane_words(row_bits(r[keep], r_rows)), "best_row": best_row, "info": (kept, min(kept, cap), 0, int((~ok).sum()))}
 
 
 def model_join_asof(how, r_keys, s_keys, where_terms, asof_term):
@@ -78,7 +79,7 @@ def model_join_asof(how, r_keys, s_keys, where_terms, asof_term):
 
 def c_term(term, ptr=None):
     """a model term -> (hj_asof_term, what must stay alive); ptr(array) gives the address the library is to read (default:
-    the numpy array's own); a validity goes through valid_words first"""
+    the numpy array's own); a validity goes through plane_words first"""
     keep = []
 
     def at(a):
@@ -91,7 +92,7 @@ def c_term(term, ptr=None):
     s, op, r, s_valid, r_valid = term
     t = _lib.hj_asof_term()
     t.s, t.r = at(s), at(r)
-    t.sValid = at(wc.valid_words(s_valid)) if s_valid is not None else None
-    t.rValid = at(wc.valid_words(r_valid)) if r_valid is not None else None
+    t.sValid = at(plane_words(s_valid)) if s_valid is not None else None
+    t.rValid = at(plane_words(r_valid)) if r_valid is not None else None
     t.width, t.type, t.op, t.reserved = s.dtype.itemsize, wc.TYPE_OF[s.dtype.kind], _lib.CMP_OPS[op], 0
     return t, keep

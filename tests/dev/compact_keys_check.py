@@ -2,9 +2,11 @@
 """compact ring build on bare keys with a home shift (what a radix shard runs): why does it hand over?"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(1, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import htm_hashjoin_amd as hj
 from oracle import oracle
+from gpu_harness import alloc
 for n in (1 << 16, 1 << 20):
     R = oracle.generate_data("uniform", n, n, 16)
     for G in (1, 2, 8):
@@ -17,7 +19,7 @@ for n in (1 << 16, 1 << 20):
             table_size = 2 * (n // G)
             with hj.HashJoinContext(0) as c:
                 c.reserve("atomic", max(r, table_size // 2), 0, buildVariant=4)
-                d = c.dev_alloc((m + 8) * 4)
+                d = alloc(c, (m + 8) * 4)
                 c.copy_h2d(d + 4, keys)
                 c.build_keys(d + 4, m, shift, table_size)
                 c.checksums()

@@ -4,6 +4,7 @@ hj_result.compactFallback bit 8 with the plan and the whole table with the seque
 import numpy as np
 
 import htm_chain_cases as cc
+from gpu_harness import alloc
 from oracle import oracle
 
 
@@ -35,7 +36,7 @@ def run_relation(c, R, tag, want=None, variant=3, bucket_range=None):
     S = cc.probe_side(R)
     if want is None:
         want = oracle.htm_build_probe_seq(R, S, want_buckets=True)
-    dR, dS = c.dev_alloc(n * 8), c.dev_alloc(S.size * 8)
+    dR, dS = alloc(c, n * 8), alloc(c, S.size * 8)
     try:
         c.copy_h2d(dR, R); c.copy_h2d(dS, S)
         c.reserve("htm", n, S.size, buildVariant=variant)

@@ -1,12 +1,12 @@
-"""What the join-kind tests of both materialising probes share (test_gpu_join_kinds.py, test_gpu_prj_join_kinds.py): device
-buffers with guard words, the derivation of every kind from the inner pairs, and the full check of one call. No test in
-here, and nothing that asks the library what the rows should be: `inner` always comes from numpy / plain Python."""
+"""What the join-kind tests of both materialising probes share (test_gpu_join_kinds.py, test_gpu_prj_join_kinds.py): the
+derivation of every kind from the inner pairs, and the full check of one call. No test in here, and nothing that asks the
+library what the rows should be: `inner` always comes from numpy / plain Python."""
 import numpy as np
 
 import htm_hashjoin_amd as hj
-from htm_hashjoin_amd import _lib
 
-SENTINEL = 0xA5A5A5A5
+from gpu_harness import SENTINEL, GuardedPlane  # noqa: F401
+
 GUARD = 4096
 U64 = np.uint64
 INNER, LEFT, SEMI, ANTI = 0, 1, 2, 3
@@ -15,53 +15,9 @@ NAMES = {INNER: "inner", LEFT: "left", SEMI: "semi", ANTI: "anti"}
 NO_ROW = U64(0xFFFFFFFF)
 
 
-class Dev:
-    """device buffers of one test, freed at the end"""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-
-    def alloc(self, nbytes):
-        self.ptrs.append(self.ctx.dev_alloc(max(int(nbytes), 16)))
-        return self.ptrs[-1]
-
-    def free(self, *ptrs):
-        for p in ptrs:
-            self.ptrs.remove(p)
-            self.ctx.dev_free(p)
-
-    def put(self, arr):
-        p = self.alloc(arr.nbytes)
-        if arr.size:
-            self.ctx.copy_h2d(p, arr)
-        return p
-
-    def planes(self, capacity):
-        """two output planes of `capacity` words, GUARD sentinel words directly behind each"""
-        fill = np.full(capacity + GUARD, SENTINEL, dtype=np.uint32)
-        return self.put(fill), self.put(fill)
-
-    def get(self, ptr, words):
-        out = np.empty(words, dtype=np.uint32)
-        if words:
-            self.ctx.copy_d2h(out, ptr)
-        return out
-
-
-def _status(call, *args, **kw):
-    """the status a call of the library ends with"""
-    try:
-        call(*args, **kw)
-    except hj.HashJoinError as e:
-        return e.status
-    return _lib.HJ_OK
+def planes(dev, capacity):
+    """two output planes of `capacity` words, GUARD sentinel words directly behind each"""
+    return GuardedPlane(dev, capacity, behind=GUARD), GuardedPlane(dev, capacity, behind=GUARD)
 
 
 def zipf(n, alphabet, theta, seed):
@@ -101,11 +57,10 @@ class Calls:
         tag = (tag, NAMES[kind], n, s_base, capacity)
         want = derive(kind, inner, n, s_base)
         cap = want.size + 64 if capacity is None else capacity
-        ds, dr = self.dev.planes(cap)
-        self.probe(dS, n, ds, dr, cap, s_base, kind=kind)
+        ds = GuardedPlane(self.dev, cap, behind=GUARD, what="a word behind the last S row was written")
+        dr = GuardedPlane(self.dev, cap, behind=GUARD, what="the R plane was written" if kind in (SEMI, ANTI) else "a word behind the last R row was written")
+        self.probe(dS, n, ds.ptr, dr.ptr, cap, s_base, kind=kind)
         found, written, _us, unmatched = self.ctx.pairs_info()
-        s, r = self.dev.get(ds, cap + GUARD), self.dev.get(dr, cap + GUARD)
-        self.dev.free(ds, dr)
         self.matches += inner.size
         self.s += n
         got = self.ctx.fetch()
@@ -113,13 +68,10 @@ class Calls:
         assert found == want.size and written == min(found, cap), (tag, found, written, want.size)
         assert unmatched == (0 if kind == INNER else n - matched_rows(inner).size), (tag, unmatched)
         assert (got["totalMatches"], got["sSize"]) == (self.matches, self.s), (tag, got["totalMatches"], self.matches)
-        assert (s[written:] == SENTINEL).all(), (tag, "a word behind the last S row was written")
-        if kind in (SEMI, ANTI):
-            assert (r == SENTINEL).all(), (tag, "the R plane was written")
-            rows = s[:written].astype(U64)
-        else:
-            assert (r[written:] == SENTINEL).all(), (tag, "a word behind the last R row was written")
-            rows = (s[:written].astype(U64) << U64(32)) | r[:written].astype(U64)
+        s, r = ds.read(written, tag), dr.read(0 if kind in (SEMI, ANTI) else written, tag)
+        rows = s.astype(U64) if kind in (SEMI, ANTI) else (s.astype(U64) << U64(32)) | r.astype(U64)
+        ds.free()
+        dr.free()
         if cap >= want.size:
             assert np.array_equal(np.sort(rows), want), tag
         else:

@@ -6,6 +6,9 @@ from collections import namedtuple
 import numpy as np
 
 import htm_hashjoin_amd as hj
+from htm_hashjoin_amd import _lib
+
+from keys_common import MIXES
 
 M32 = 0xFFFFFFFF
 NULL_SEED = 0x4E554C4C
@@ -99,7 +102,6 @@ def hash_matrix(rng, n):
     """the column lists of n rows the hash is checked on, host and device: the fixed mixes plain, nullable and with
     NULLs that are equal; every length of LENGTHS (cycled over the rows, so they start at changing alignments), alone,
     nullable and next to fixed columns"""
-    from test_keys_abi import MIXES
     lens = [LENGTHS[(i * 7 + 3) % len(LENGTHS)] for i in range(n)]
     out = [[fixed_col(rng, w, n) for w in widths] for widths in MIXES]
     out += [[fixed_col(rng, w, n, nulls=0.3) for w in widths] for widths in MIXES[::3]]
@@ -141,3 +143,33 @@ def expected_rows(how, pairs, n_r, n_s):
             "full": (s + lone_s + [-1] * len(lone_r), r + [-1] * len(lone_s) + lone_r),
             "right_semi": (None, sorted(r_hit)), "right_anti": (None, lone_r)}[how]
     return tuple(None if x is None else np.array(x, dtype=np.int64) for x in rows)
+
+
+# ---- argument errors of the entry points that take hj_key_col2 ----------------------------------------------------------------
+def _bad_columns(n):
+    """(name, keyword changes) of every column the three entry points refuse, on top of a good one"""
+    keys = np.arange(2 * n, dtype=np.uint64)
+    off = np.arange(n + 2, dtype=np.uint32)
+    valid = np.full(n // 32 + 2, M32, dtype=np.uint32)
+    good_fixed = dict(ptr=keys.ctypes.data, width=8, off=0, valid=valid.ctypes.data, flags=1)
+    good_var = dict(ptr=keys.ctypes.data + 1, width=0, off=off.ctypes.data, valid=0, flags=0)
+    bad = [dict(good_fixed, width=w) for w in (3, 5, 12, 32)]
+    bad += [dict(good_fixed, width=w, ptr=keys.ctypes.data + w // 2) for w in (2, 4, 8, 16)]       # misaligned for its width
+    bad += [dict(good_fixed, ptr=0), dict(good_var, ptr=0),
+            dict(good_var, off=0),                                                                  # width 0 without offsets
+            dict(good_fixed, off=off.ctypes.data),                                                  # offsets with a width
+            dict(good_fixed, flags=2), dict(good_var, flags=0x80000001),                            # unknown flag bits
+            dict(good_var, off=off.ctypes.data + 2), dict(good_fixed, valid=valid.ctypes.data + 1),  # not 4-byte aligned
+            dict(good_var, valid=valid.ctypes.data + 2)]
+    return (keys, off, valid), good_fixed, good_var, bad
+
+
+def _col2(n_cols, side_s, side_r, ptr, width, off, valid, flags):
+    cols = (_lib.hj_key_col2 * 5)()
+    for c in cols:
+        c.width, c.flags = width, flags
+        if side_s:
+            c.s, c.sOffsets, c.sValid = ptr or None, off or None, valid or None
+        if side_r:
+            c.r, c.rOffsets, c.rValid = ptr or None, off or None, valid or None
+    return cols

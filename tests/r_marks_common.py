@@ -4,7 +4,8 @@ library), and Marks, which keeps in numpy what a tracking context must remember 
 Unmatched R = setdiff1d(arange(base, base + n), unique(inner & 0xFFFFFFFF)). No test in here."""
 import numpy as np
 
-from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, Dev, Calls, _status, zipf  # noqa: F401
+from gpu_harness import GuardedPlane
+from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, Calls, zipf  # noqa: F401
 
 UNMATCHED, MATCHED = 0, 1
 LOW = U64(0xFFFFFFFF)
@@ -102,23 +103,22 @@ class Marks:
         return np.setdiff1d(np.arange(self.base, self.base + self.n, dtype=U64), self.seen, assume_unique=True)
 
     def sweep(self, which, capacity=None, null_plane=False):
-        """-> (produced, written, the plane with its guard words)"""
+        """-> (produced, written, the rows written); no word behind them was written"""
         cap = self.n + 64 if capacity is None else capacity
-        d = 0 if null_plane else self.dev.put(np.full(cap + GUARD, SENTINEL, dtype=np.uint32))
-        self.ctx.r_rows(which, d, cap)
+        plane = None if null_plane else GuardedPlane(self.dev, cap, behind=GUARD, what="a word behind the last row was written")
+        self.ctx.r_rows(which, plane.ptr if plane else 0, cap)
         produced, written, _us, rows = self.ctx.r_rows_info()
         assert rows == self.n, (rows, self.n)
-        plane = None
-        if not null_plane:
-            plane = self.dev.get(d, cap + GUARD)
-            self.dev.free(d)
-        return produced, written, plane
+        got = None
+        if plane:
+            got = plane.read(written, which)
+            plane.free()
+        return produced, written, got
 
     def check(self, tag=None):
         for which in (UNMATCHED, MATCHED):
             want = self.expected(which)
-            produced, written, plane = self.sweep(which)
+            produced, written, got = self.sweep(which)
             print(tag, "which", which, "produced", produced, "written", written, "want", want.size)
             assert produced == written == want.size, (tag, which, produced, written, want.size)
-            assert (plane[written:] == SENTINEL).all(), (tag, which, "a word behind the last row was written")
-            assert np.array_equal(plane[:written].astype(U64), want), (tag, which)      # ascending, without holes
+            assert np.array_equal(got.astype(U64), want), (tag, which)      # ascending, without holes

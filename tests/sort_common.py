@@ -14,6 +14,8 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
+from gpu_harness import plane_words
+
 U32, U64 = np.uint32, np.uint64
 DTYPES = ("uint8", "uint16", "uint32", "uint64", "int8", "int16", "int32", "int64", "float32", "float64")
 _TYPE = {"u": _lib.HJ_VAL_UINT, "i": _lib.HJ_VAL_INT, "f": _lib.HJ_VAL_FLOAT}
@@ -45,9 +47,7 @@ class Col:
         if self.valid is None:
             return None
         n = self.valid.size
-        bits = np.packbits(self.valid, bitorder="little")
-        words = np.zeros((n + 31) // 32 or 1, dtype=U32)
-        words.view(np.uint8)[:bits.size] = bits
+        words = plane_words(self.valid) if n else np.zeros(1, dtype=U32)
         if garbage is not None and n % 32:
             words[-1] |= U32(int(garbage.integers(0, 1 << 32)) & ~((1 << (n % 32)) - 1) & 0xFFFFFFFF)
         return words

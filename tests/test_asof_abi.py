@@ -16,6 +16,7 @@ from htm_hashjoin_amd._lib import lib
 import asof_common as ac
 import stream_order as so
 import where_common as wc
+from gpu_harness import packed, plane_words, row_bits
 
 U32, U64, NO_ROW = np.uint32, np.uint64, wc.NO_ROW
 SENT = 0xA5A5A5A5
@@ -175,7 +176,7 @@ def test_a_shuffled_list_gives_the_sorted_lists_result():
         assert np.array_equal(a["s_marks"], b["s_marks"]) and np.array_equal(a["r_marks"], b["r_marks"])
         assert 0 < a["info"][0] < n_s and a["info"][0] == (a["best_row"] != NO_ROW).sum()
         # an R row is marked only when it wins some S row
-        assert a["r_marks"].tolist() == wc.mark_words(np.unique(a["best_row"][a["best_row"] != NO_ROW]), n_r).tolist()
+        assert a["r_marks"].tolist() == plane_words(row_bits(np.unique(a["best_row"][a["best_row"] != NO_ROW]), n_r)).tolist()
 
 
 def test_dropped_entries_a_row_base_and_a_repeated_pair():
@@ -214,7 +215,7 @@ def test_capacity_cuts_the_output_not_the_counts_or_the_marks():
     assert rc == OK and info == (kept, 0, 0, 0) and np.array_equal(best_row, full["best_row"])
     assert np.array_equal(s_marks, full["s_marks"]) and np.array_equal(r_marks, full["r_marks"])
     rc, out_s, out_r, s_marks, r_marks, _b, info = host_call(map_s, map_r, 0, n_s, n_r, term, marks=False)       # no planes
-    assert rc == OK and s_marks is None and np.array_equal(wc.packed(out_s[:kept], out_r[:kept]), full["kept"])
+    assert rc == OK and s_marks is None and np.array_equal(packed(out_s[:kept], out_r[:kept]), full["kept"])
     rc, _s, _r, _sm, _rm, best_row, info = host_call(map_s[:0], map_r[:0], 0, n_s, n_r, term)                    # no pairs: the planes are initialised
     assert rc == OK and info == (0, 0, 0, 0) and (best_row == NO_ROW).all()
 
@@ -227,7 +228,7 @@ def test_the_python_form():
     map_s, map_r = (10 + rng.integers(0, n_s + 5, n)).astype(U32), rng.integers(0, n_r, n).astype(U32)
     want = ac.model_call(map_s, map_r, 10, n_s, n_r, wc.term_of(s, ">", r, sv, rv))
     got = hj.pairs_asof_host(map_s, map_r, 10, (np.ma.MaskedArray(s, mask=~sv), ">", hj.KeyColumn(r, rv)), marks=True)
-    assert got["info"] == want["info"] and np.array_equal(wc.packed(got["s_idx"], got["r_idx"]), want["kept"])
+    assert got["info"] == want["info"] and np.array_equal(packed(got["s_idx"], got["r_idx"]), want["kept"])
     assert np.array_equal(got["s_marks"], want["s_marks"]) and np.array_equal(got["r_marks"], want["r_marks"])
     assert np.array_equal(got["best_row"], want["best_row"])
     cut = hj.pairs_asof_host(map_s, map_r, 10, (s, ">", r), capacity=3)

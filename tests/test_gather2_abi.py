@@ -12,7 +12,7 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
 from keys2_common import HOWS, ModelCol, fixed_col, key_column, varlen_col
-from test_keys_abi import _code, _declared_args, _header
+from keys_common import _code, _declared_args, _header
 
 COL2 = "const hj_gather_col2 *"
 S_PLANE = ("inner", "left", "semi", "anti", "right", "full")

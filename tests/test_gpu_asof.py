@@ -17,7 +17,7 @@ from htm_hashjoin_amd._lib import lib
 
 import asof_common as ac
 import where_common as wc
-from join_kinds_common import SENTINEL, Dev, _status
+from gpu_harness import Device, GuardedPlane, check_pair_filter, ctx, plane_words, status  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,76 +28,26 @@ N_S, N_R = 1500, 1100           # rows of the relations: neither a multiple of 3
 INVALID = _lib.HJ_ERR_INVALID
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
-def guarded(body):
-    g = np.full(GUARD, SENTINEL, dtype=U32)
-    return np.concatenate([g, body, g])
-
-
 def run(ctx, map_s, map_r, base, s_rows, r_rows, term, capacity=None, marks=True, offset=0, tag=None):
     """one hj_pairs_asof_dev over numpy inputs, checked in full against the model and the host form -> the model's dict"""
     n = map_s.size
     want = ac.model_call(map_s, map_r, base, s_rows, r_rows, term, capacity)
     cap = n if capacity is None else capacity
-    sw, rw = -(-s_rows // 32), -(-r_rows // 32)
     s, op, r, s_valid, r_valid = term
-    with Dev(ctx) as dev:
-        d_ms, d_mr = dev.put(map_s), dev.put(map_r)
-        d_term = (dev.put(s), dev.put(r), s.dtype.itemsize, wc.TYPE_OF[s.dtype.kind], _lib.CMP_OPS[op],
-                  dev.put(wc.valid_words(s_valid)) if s_valid is not None else 0, dev.put(wc.valid_words(r_valid)) if r_valid is not None else 0)
-        fill = np.full(offset + cap + GUARD, SENTINEL, dtype=U32)
-        d_os, d_or = (dev.put(fill), dev.put(fill)) if cap else (0, 0)
-        plane_s, plane_r = guarded(np.zeros(sw, U32)), guarded(np.zeros(rw, U32))
-        d_ps, d_pr = (dev.put(plane_s), dev.put(plane_r)) if marks else (0, 0)
-        # the best planes hold junk before the call: it initialises them itself. bestVal: 64-bit words behind a guard of 64 words
-        best_val, best_row = guarded(np.full(2 * s_rows, 0x33333333, U32)), guarded(np.full(s_rows, 0, U32))
-        d_bv, d_br = dev.put(best_val), dev.put(best_row)
-        ctx.pairs_asof(d_ms, d_mr, n, base, s_rows, r_rows, d_term, d_bv + 4 * GUARD, d_br + 4 * GUARD,
-                       d_os + 4 * offset if cap else 0, d_or + 4 * offset if cap else 0, cap,
-                       d_ps + 4 * GUARD if marks else 0, d_pr + 4 * GUARD if marks else 0)
-        info = ctx.asof_info()
-        print(tag, "pairs", n, "info", info, "model", want["info"])
-        assert (info[0], info[1], info[3]) == (want["info"][0], want["info"][1], want["info"][3]), (tag, info, want["info"])
-        written = want["info"][1]
-        got_s = got_r = np.empty(0, dtype=U32)
-        if cap:
-            out_s, out_r = dev.get(d_os, fill.size), dev.get(d_or, fill.size)
-            for out in (out_s, out_r):
-                assert (out[:offset] == SENTINEL).all() and (out[offset + written:] == SENTINEL).all(), (tag, "a word outside the run was written")
-            got_s, got_r = out_s[offset:offset + written], out_r[offset:offset + written]
-        if marks:
-            got_ps, got_pr = dev.get(d_ps, plane_s.size), dev.get(d_pr, plane_r.size)
-            for got, words in ((got_ps, sw), (got_pr, rw)):
-                assert (got[:GUARD] == SENTINEL).all() and (got[GUARD + words:] == SENTINEL).all(), (tag, "a word outside the marks plane was written")
-            assert np.array_equal(got_ps[GUARD:GUARD + sw], want["s_marks"]), (tag, "S marks")      # bit for bit, cut pairs included
-            assert np.array_equal(got_pr[GUARD:GUARD + rw], want["r_marks"]), (tag, "R marks")
-        got_bv, got_br = dev.get(d_bv, best_val.size), dev.get(d_br, best_row.size)
-        for got, words in ((got_bv, 2 * s_rows), (got_br, s_rows)):
-            assert (got[:GUARD] == SENTINEL).all() and (got[GUARD + words:] == SENTINEL).all(), (tag, "a word outside a best plane was written")
-        assert np.array_equal(got_br[GUARD:GUARD + s_rows], want["best_row"]), (tag, "bestRow: the left-outer as-of map")
-        assert np.array_equal(dev.get(d_ms, n), map_s) and np.array_equal(dev.get(d_mr, n), map_r), (tag, "a map was written")
-    got = wc.packed(got_s, got_r)
-    if written == want["info"][0]:
-        assert np.array_equal(got, want["kept"]), (tag, "the kept pairs")
-    else:       # cut by the capacity: any `written` of the kept pairs, each at most as often as it was kept
-        pool, counts = np.unique(want["kept"], return_counts=True)
-        mine, mine_counts = np.unique(got, return_counts=True)
-        at = np.searchsorted(pool, mine)
-        assert (at < pool.size).all() and np.array_equal(pool[np.minimum(at, pool.size - 1)], mine) and (mine_counts <= counts[at]).all(), tag
-    # the host form on the same buffers: the same multiset, the same planes, the same words
+    host = None
     if s_rows == s.size and r_rows == r.size:
-        host = hj.pairs_asof_host(map_s, map_r, base, (hj.KeyColumn(s, s_valid), op, hj.KeyColumn(r, r_valid)), capacity=cap, marks=True)
-        assert host["info"] == want["info"], tag
-        if written == want["info"][0]:
-            assert np.array_equal(wc.packed(host["s_idx"], host["r_idx"]), got), (tag, "host and device disagree")
-        assert np.array_equal(host["s_marks"], want["s_marks"]) and np.array_equal(host["r_marks"], want["r_marks"]), tag
-        assert np.array_equal(host["best_row"], got_br[GUARD:GUARD + s_rows]), tag
+        host = lambda: hj.pairs_asof_host(map_s, map_r, base, (hj.KeyColumn(s, s_valid), op, hj.KeyColumn(r, r_valid)), capacity=cap, marks=True)   # noqa: E731
+    with Device(ctx) as dev:
+        d_term = (dev.put(s), dev.put(r), s.dtype.itemsize, wc.TYPE_OF[s.dtype.kind], _lib.CMP_OPS[op],
+                  dev.put(plane_words(s_valid)) if s_valid is not None else 0, dev.put(plane_words(r_valid)) if r_valid is not None else 0)
+        # the best planes hold junk before the call: it initialises them itself. bestVal: 64-bit words behind a guard of 64 words
+        outside = "a word outside a best plane was written"
+        best = [("best_val", GuardedPlane(dev, 2 * s_rows, front=GUARD, behind=GUARD, body=0x33333333, what=outside), None, None),
+                ("best_row", GuardedPlane(dev, s_rows, front=GUARD, behind=GUARD, body=0, what=outside), want["best_row"],
+                 "bestRow: the left-outer as-of map")]
+        call = lambda ms, mr, os, o_r, c, ps, pr, bv, br: ctx.pairs_asof(ms, mr, n, base, s_rows, r_rows, d_term, bv, br, os, o_r, c, ps, pr)   # noqa: E731
+        check_pair_filter(dev, call, ctx.asof_info, map_s, map_r, s_rows, r_rows, want, cap, GUARD, offset=offset, marks=marks, extra=best,
+                          host=host, tag=tag)
     return want
 
 
@@ -247,7 +197,7 @@ def test_a_second_call_resets_planes_and_cursor(ctx):
     # preset mark bits survive a call
     sw, rw = -(-N_S // 32), -(-N_R // 32)
     pre_s, pre_r = rng.integers(0, 1 << 32, sw).astype(U32), rng.integers(0, 1 << 32, rw).astype(U32)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_ps, d_pr = dev.put(pre_s), dev.put(pre_r)
         d_term = (dev.put(s), dev.put(r), 2, _lib.HJ_VAL_UINT, _lib.CMP_OPS[">"], 0, 0)
         ctx.pairs_asof(dev.put(map_s), dev.put(map_r), map_s.size, 0, N_S, N_R, d_term, dev.alloc(8 * N_S), dev.alloc(4 * N_S), 0, 0, 0, d_ps, d_pr)
@@ -256,10 +206,10 @@ def test_a_second_call_resets_planes_and_cursor(ctx):
 
 
 def test_what_the_device_form_refuses(ctx):
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d = dev.alloc(4096)
         good = (d, d, 8, _lib.HJ_VAL_INT, _lib.HJ_CMP_LT, d, d)
-        call = lambda term, n=16, s_rows=8, r_rows=8, ms=d, mr=d, bv=d, br=d, os=d, o_r=d, cap=16: _status(      # noqa: E731
+        call = lambda term, n=16, s_rows=8, r_rows=8, ms=d, mr=d, bv=d, br=d, os=d, o_r=d, cap=16: status(      # noqa: E731
             ctx.pairs_asof, ms, mr, n, 0, s_rows, r_rows, term, bv, br, os, o_r, cap)
         before = ctx.asof_info()
         edit = lambda i, v: good[:i] + (v,) + good[i + 1:]        # noqa: E731

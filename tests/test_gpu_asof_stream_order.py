@@ -13,6 +13,7 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
+from gpu_harness import fl, packed, plane_words  # noqa: F401
 import asof_common as ac
 import stream_order as so
 import where_common as wc
@@ -22,13 +23,6 @@ pytestmark = pytest.mark.gpu
 U32, U64 = np.uint32, np.uint64
 N_S, N_R, N_PAIRS, BASE = 3001, 2003, 9001, 500
 SLACK = 64                       # output words behind the exact count: they keep the HJ_NO_ROW prefill
-
-
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the test below cannot pass vacuously
-    return f
 
 
 def vp(p):
@@ -54,7 +48,7 @@ def test_pairs_asof_behind_a_delay(fl):
         bMR = st.buf(np.full(N_PAIRS, so.NO_ROW, dtype=U32), real=map_r, warm=np.roll(map_r, 2))
         bS = st.buf(np.full(N_S, np.iinfo(np.int32).min, dtype=np.int32), real=s, warm=s[::-1].copy())
         bR = st.buf(np.full(N_R, np.iinfo(np.int32).max, dtype=np.int32), real=r, warm=r[::-1].copy())
-        bV = st.buf(np.zeros(sw, dtype=U32), real=wc.valid_words(s_valid), warm=wc.valid_words(~s_valid))
+        bV = st.buf(np.zeros(sw, dtype=U32), real=plane_words(s_valid), warm=plane_words(~s_valid))
         # the best planes: what arrives behind the delay must be overwritten by the call's own initialisation
         bBV = st.buf(np.full(N_S, 0x1111111111111111, dtype=U64), real=np.full(N_S, ~U64(0), dtype=U64), warm=np.full(N_S, ~U64(0), dtype=U64), fetch=True)
         bBR = st.buf(np.full(N_S, 0x22222222, dtype=U32), real=np.zeros(N_S, dtype=U32), warm=np.zeros(N_S, dtype=U32), fetch=True)
@@ -76,7 +70,7 @@ def test_pairs_asof_behind_a_delay(fl):
     assert (info[0], info[1], info[3]) == (n_kept, n_kept, want["info"][3]), (info, want["info"])
     got_s, got_r = st.result(oS, U32, "kept S"), st.result(oR, U32, "kept R")
     assert (got_s[n_kept:] == so.NO_ROW).all() and (got_r[n_kept:] == so.NO_ROW).all(), "a word behind the last pair was written"
-    assert np.array_equal(wc.packed(got_s[:n_kept], got_r[:n_kept]), want["kept"])
+    assert np.array_equal(packed(got_s[:n_kept], got_r[:n_kept]), want["kept"])
     assert np.array_equal(st.result(pS, U32, "S marks"), want["s_marks"]) and np.array_equal(st.result(pR, U32, "R marks"), want["r_marks"])
     assert np.array_equal(st.result(bBR, U32, "bestRow"), want["best_row"])
     assert (st.result(bBV, U64, "bestVal")[want["best_row"] == wc.NO_ROW] == 0).all()

@@ -17,8 +17,9 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from r_marks_common import U64, LOW, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, Dev, _status, inner_expected, r_rows_of
-from join_kinds_common import derive, matched_rows
+from gpu_harness import Device, plane_bits, status
+from r_marks_common import U64, LOW, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, inner_expected, r_rows_of
+from join_kinds_common import derive, matched_rows, planes
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,7 @@ def relations():
 
 
 def bits_set(words, rows):
-    return int(np.unpackbits(words.view(np.uint8), bitorder="little")[:rows].sum())
+    return int(plane_bits(words, rows).sum())
 
 
 class Scenario:
@@ -63,7 +64,7 @@ class Scenario:
     def pairs(self):
         """an INNER call that only counts (it marks R rows all the same), then the call of `kind` cut by its capacity"""
         self.probe_pairs(INNER, 0, 0, 0)
-        d_s, d_r = self.dev.planes(PAIRS_CAP)
+        d_s, d_r = (p.ptr for p in planes(self.dev, PAIRS_CAP))
         self.probe_pairs(self.kind, d_s, d_r, PAIRS_CAP)
         found = derive(self.kind, self.inner, N_S).size
         assert found > PAIRS_CAP
@@ -95,7 +96,7 @@ class Scenario:
         assert np.array_equal(self.S[s], self.R[r])
         map_s = np.concatenate([s, s, np.full(7, NO_ROW), np.zeros(5, dtype=np.uint32)])
         map_r = np.concatenate([r, (r + 1) % N_R, np.zeros(7, dtype=np.uint32), np.full(5, 5000, dtype=np.uint32)])
-        d_s, d_r = self.dev.planes(VERIFY_CAP)
+        d_s, d_r = (p.ptr for p in planes(self.dev, VERIFY_CAP))
         self.ctx.pairs_verify(self.dev.put(map_s), self.dev.put(map_r), map_s.size, 0, N_S, N_R, [(self.dS, self.dR, 8)], d_s, d_r,
                               VERIFY_CAP)
         assert self.inner.size > VERIFY_CAP
@@ -119,7 +120,7 @@ def words013(info):
 
 
 def lifetimes(algo, kind, counting_probe=False):
-    with hj.HashJoinContext(0) as ctx, Dev(ctx) as dev:
+    with hj.HashJoinContext(0) as ctx, Device(ctx) as dev:
         sc = Scenario(ctx, dev, algo, kind)
         # 1. nothing has been called
         for name in ("gather_info", "verify_info", "mark_rows_info"):
@@ -150,8 +151,8 @@ def lifetimes(algo, kind, counting_probe=False):
         assert words013(second["pairs"]) == want["pairs"] and second["pairs"][2] == 0, second["pairs"]
         # 4. a reserve that replaces the marks plane: the marks describe no build any more
         sc.reserve(N_R_LARGER)
-        assert _status(ctx.r_rows, UNMATCHED, 0, 0) == _lib.HJ_ERR_STATE
-        assert _status(ctx.r_rows_info) == _lib.HJ_ERR_STATE
+        assert status(ctx.r_rows, UNMATCHED, 0, 0) == _lib.HJ_ERR_STATE
+        assert status(ctx.r_rows_info) == _lib.HJ_ERR_STATE
         third = sc.infos()
         for name in ("gather", "verify", "mark_rows"):
             assert words013(third[name]) == want[name] and third[name][2] != 0, (name, third[name])

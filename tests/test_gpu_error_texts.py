@@ -8,7 +8,8 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from join_kinds_common import Dev
+from gpu_harness import Device, ctx  # noqa: F401
+
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +35,9 @@ def probe_join(ctx, name, kind, dS, n, base, d_s, d_r, cap):
 
 
 @pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
 def mem(ctx):
     """R = S = the keys 1 .. 1024 on the device, and two output planes"""
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d = dev.put(np.arange(1, N + 1, dtype=np.uint64))
         yield {"R": d, "S": d, "s": dev.alloc(4 * N), "r": dev.alloc(4 * N), "big": dev.alloc(8 * (BIG + 2))}
 

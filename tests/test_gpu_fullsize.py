@@ -14,6 +14,8 @@ import pytest
 import htm_hashjoin_amd as hj
 from oracle import oracle
 
+from gpu_harness import alloc
+
 pytestmark = pytest.mark.gpu
 
 N = 1 << 30
@@ -49,8 +51,8 @@ def test_metric_size_uniform_against_the_sequential_oracle():
     assert want["totalMatches"] + want["conflicts"] == N
     R32, S32 = R.astype(np.uint32), S.astype(np.uint32)
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(N * 8); c.copy_h2d(dR, R)
-        dS = c.dev_alloc(N * 8); c.copy_h2d(dS, S)
+        dR = alloc(c, N * 8); c.copy_h2d(dR, R)
+        dS = alloc(c, N * 8); c.copy_h2d(dS, S)
         del R, S
         for variant in (0, 4, 2):                  # what the bench runs (auto -> the classic rings: duplicate keys), the compact rings, the workgroup window
             c.reserve("atomic", N, N, buildVariant=variant)
@@ -95,9 +97,9 @@ def test_metric_size_uniform_against_the_sequential_oracle():
 def test_config3_prj_local_shuffle_1024_closed_forms():
     R = hj.generate_data("local_shuffle", N, N, 1024)
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(N * 8); c.copy_h2d(dR, R)
+        dR = alloc(c, N * 8); c.copy_h2d(dR, R)
         del R
-        dS = c.dev_alloc(N * 8); c.copy_h2d(dS, np.arange(1, N + 1, dtype=np.uint64))
+        dS = alloc(c, N * 8); c.copy_h2d(dS, np.arange(1, N + 1, dtype=np.uint64))
         for mode, path in ((0, 1), (1, 0)):         # the histogram-free passes (what the bench times), then the exact ones
             c.reserve("prj", N, N, prjMode=mode)
             c.prj_join(dR, N, dS, N)
@@ -123,9 +125,9 @@ def test_config5_skew_stress_full_size():
     n, slices, per = 1 << 28, 16, 1 << 28
     R = hj.generate_data("local_shuffle", n, n, 1024)
     with hj.HashJoinContext(0) as c, hj.HashJoinContext(0) as h:
-        dR = c.dev_alloc(n * 8); c.copy_h2d(dR, R)
+        dR = alloc(c, n * 8); c.copy_h2d(dR, R)
         del R
-        dS = c.dev_alloc(per * 8)
+        dS = alloc(c, per * 8)
         c.reserve("atomic", n, per)
         c.build(dR, n)
         h.reserve("htm", n, per)
@@ -161,8 +163,8 @@ def test_htm_uniform_2p27_chains_in_lds_against_the_sequential_oracle():
     want = oracle.htm_build_probe_seq(R, S)
     assert (want["conflictCount"], want["overflowBuckets"]) == (30065252, 17330401)       # DESIGN.md 4.6 quotes these
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); c.copy_h2d(dR, R)
-        dS = c.dev_alloc(n * 8); c.copy_h2d(dS, S)
+        dR = alloc(c, n * 8); c.copy_h2d(dR, R)
+        dS = alloc(c, n * 8); c.copy_h2d(dS, S)
         for variant in (0, 2):
             c.reserve("htm", n, n, buildVariant=variant)
             c.build(dR, n)

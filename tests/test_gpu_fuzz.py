@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, alloc
 import htm_chain_cases as cc
 from fuzz_relations import make_relation, slot_code_case
-from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +57,7 @@ LOG_OVERFLOW, CODE_OVERFLOW = 1, 4                       # slot_codes_info()["ca
 def build_probe_codes(c, R, S, plen, variant, slot_codes, idx_base=0):
     """one build + probe + checksums through the split API (test_gpu_slot_codes.build_probe) -> (result, table, info)"""
     c.reserve("atomic", R.size, S.size, probeLength=plen, buildVariant=variant, slotCodes=slot_codes)
-    with Dev(c) as dev:
+    with Device(c) as dev:
         c.build(dev.put(R), R.size, idx_base)
         c.probe(dev.put(S), S.size)
         c.checksums()
@@ -241,7 +241,7 @@ def test_key_builds_of_a_radix_shard_on_random_keys(block):
             with hj.HashJoinContext(0) as c:
                 c.reserve("atomic", n2, S.size, buildVariant=variant, probeLength=plen)
                 ro, so = 4 * int(rng.integers(0, 4)), 4 * int(rng.integers(0, 4))
-                d_r = c.dev_alloc((m + 8) * 4); d_s = c.dev_alloc((S.size + 8) * 4)
+                d_r = alloc(c, (m + 8) * 4); d_s = alloc(c, (S.size + 8) * 4)
                 c.copy_h2d(d_r + ro, keys); c.copy_h2d(d_s + so, S)
                 c.build_keys(d_r + ro, m, shift, table_size)
                 c.probe_keys(d_s + so, S.size)
@@ -265,7 +265,7 @@ def test_a_reused_context_on_a_random_sequence_of_relations(block):
     S = np.arange(1, n + 1, dtype=np.uint64)
     seen = set()
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); dS = c.dev_alloc(n * 8)
+        dR = alloc(c, n * 8); dS = alloc(c, n * 8)
         c.copy_h2d(dS, S)
         c.reserve("atomic", n, n)
         for step in range(steps):

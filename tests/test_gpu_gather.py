@@ -10,64 +10,13 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from r_marks_common import SENTINEL, U64, LEFT, UNMATCHED, Dev, inner_expected, unmatched_r
-from join_kinds_common import unmatched_rows
+from gather_common import (BIG, BLOCK_ROWS, GUARD_BYTES, GUARD_WORDS, NO_ROW, SEAM_ROWS, STEP_ROWS, WIDTHS, _null_patterns, column, expected,
+                           fill_of)
+from gpu_harness import SENTINEL, U64, Device, GuardedPlane, ctx, plane_bits, plane_words  # noqa: F401
+from join_kinds_common import planes, unmatched_rows
+from r_marks_common import LEFT, UNMATCHED, inner_expected, unmatched_r
 
 pytestmark = pytest.mark.gpu
-
-STEP_ROWS = 64
-LANE_ROWS = 4
-WAVE_ROWS = STEP_ROWS * LANE_ROWS
-BLOCK_ROWS = 4 * WAVE_ROWS
-assert BLOCK_ROWS == 1024
-WIDTHS = (1, 2, 4, 8, 16)
-NO_ROW = 0xFFFFFFFF
-GUARD_BYTES = 256
-GUARD_WORDS = 16
-SEAM_ROWS = (1, 31, 32, 33, STEP_ROWS - 1, STEP_ROWS, STEP_ROWS + 1, WAVE_ROWS - 1, WAVE_ROWS, WAVE_ROWS + 1, BLOCK_ROWS - 1,
-             BLOCK_ROWS, BLOCK_ROWS + 1, 4 * BLOCK_ROWS + 1, 3 * BLOCK_ROWS + 77)
-BIG = 3 * BLOCK_ROWS + 77
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
-def column(rng, rows, width):
-    """`rows` random elements of `width` bytes"""
-    return rng.integers(0, 256, rows * width, dtype=np.uint8).view(f"V{width}")
-
-
-def fill_of(width, salt):
-    """a non-zero fill pattern of its own per column: 16 bytes, of which the low `width` count"""
-    return bytes((17 * salt + 3 * i + 1) % 255 + 1 for i in range(16))
-
-
-def expected(m, row_base, src_rows, src, width, fill):
-    """-> (the column, valid, NULL rows, out-of-range entries) as the header defines them"""
-    e = m.astype(np.int64)
-    null = e == NO_ROW
-    i = (e - row_base) % (1 << 32)
-    oor = ~null & (i >= src_rows)
-    ok = ~null & ~oor
-    out = np.empty(m.size, dtype=f"V{width}")
-    out[:] = np.frombuffer(fill[:width], dtype=f"V{width}")[0]
-    if src is not None and ok.any():
-        out[ok] = src[i[ok]]
-    return out, ok, int(null.sum()), int(oor.sum())
-
-
-def valid_words(ok):
-    return np.packbits(np.concatenate([ok, np.zeros(-ok.size % 32, dtype=bool)]), bitorder="little").view(np.uint32)
-
-
-def get_bytes(ctx, ptr, nbytes):
-    out = np.empty(nbytes, dtype=np.uint8)
-    ctx.copy_d2h(out, ptr)
-    return out
 
 
 class Gather:
@@ -82,29 +31,26 @@ class Gather:
         d_map = dev.put(m)
         if d_srcs is None:
             d_srcs = [dev.put(src) if src is not None and src.size else 0 for src, _, _ in columns]
-        d_dsts = [dev.put(np.full(n * w + GUARD_BYTES, 0xA5, dtype=np.uint8)) for _, w, _ in columns]
+        dsts = [GuardedPlane(dev, n * w, np.uint8, 0xA5, behind=GUARD_BYTES, what="a byte behind the column's end was written") for _, w, _ in columns]
         words = (n + 31) // 32
-        d_valid = dev.put(np.full(1 + words + GUARD_WORDS, SENTINEL, dtype=np.uint32)) if with_valid else 0
-        ctx.gather(d_map, n, src_rows, [(s, d, w, f) for s, d, (_, w, f) in zip(d_srcs, d_dsts, columns)],
-                   d_valid=d_valid + 4 * valid_offset if with_valid else 0, row_base=row_base)
+        valid = GuardedPlane(dev, words, front=valid_offset, behind=1 + GUARD_WORDS - valid_offset,
+                             what="a validity word outside ceil(n / 32) was written") if with_valid else None
+        ctx.gather(d_map, n, src_rows, [(s, d.ptr, w, f) for s, d, (_, w, f) in zip(d_srcs, dsts, columns)],
+                   d_valid=valid.ptr if with_valid else 0, row_base=row_base)
         info = ctx.gather_info()
         got = []
         want_ok, n_null, n_oor = expected(m, row_base, src_rows, None, 1, bytes(16))[1:] if not columns else (None, 0, 0)
-        for (src, w, f), d in zip(columns, d_dsts):
+        for (src, w, f), d in zip(columns, dsts):
             want, want_ok, n_null, n_oor = expected(m, row_base, src_rows, src, w, f)
-            raw = get_bytes(ctx, d, n * w + GUARD_BYTES)
-            assert (raw[n * w:] == 0xA5).all(), (tag, w, "a byte behind the column's end was written")
-            assert raw[:n * w].tobytes() == want.tobytes(), (tag, w, n)
-            got.append(raw[:n * w].view(f"V{w}"))
+            raw = d.read(n * w, (tag, w))
+            assert raw.tobytes() == want.tobytes(), (tag, w, n)
+            got.append(raw.view(f"V{w}"))
         print(tag, "rows", n, "info", info)
         assert (info[0], info[1], info[3]) == (n, n_null, n_oor), (tag, info, n, n_null, n_oor)
         if with_valid:
-            plane = dev.get(d_valid, 1 + words + GUARD_WORDS)
-            assert (plane[:valid_offset] == SENTINEL).all() and (plane[valid_offset + words:] == SENTINEL).all(), \
-                (tag, "a validity word outside ceil(n / 32) was written")
             # whole words: the bits at or behind n in the last one are zero
-            assert np.array_equal(plane[valid_offset:valid_offset + words], valid_words(want_ok)), (tag, n)
-        dev.free(d_map, *d_dsts, *([d_valid] if with_valid else []))
+            assert np.array_equal(valid.read(words, tag), plane_words(want_ok)), (tag, n)
+        dev.free(d_map, *[d.base for d in dsts], *([valid.base] if with_valid else []))
         return got
 
 
@@ -116,7 +62,7 @@ def test_seams(ctx, width):
     rng = np.random.default_rng(100 + width)
     src_rows = 777
     src = column(rng, src_rows, width)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         d_src = dev.put(src)
         for n in SEAM_ROWS:
@@ -128,7 +74,7 @@ def test_validity_plane_at_a_4_byte_boundary(ctx):
     """the plane one word into its allocation: its 8-byte stores must not reach the word in front or the words behind"""
     rng = np.random.default_rng(7)
     src = column(rng, 500, 4)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         for n in (33, STEP_ROWS + 1, BLOCK_ROWS + 1, BIG):
             m = rng.integers(0, 500, n).astype(np.uint32)
             m[rng.integers(0, n, n // 3)] = NO_ROW
@@ -138,32 +84,13 @@ def test_validity_plane_at_a_4_byte_boundary(ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # NULL rows, in an 8-byte and a 1-byte column with a fill pattern each
 # ---------------------------------------------------------------------------------------------------------------------
-def _null_patterns(n):
-    every = np.zeros(n, dtype=bool)
-    ends = every.copy()
-    ends[[0, n - 1]] = True
-    yield "first and last", ends
-    for start in (STEP_ROWS, STEP_ROWS + 5):                    # a whole step of a wavefront; the same run across two steps
-        run = every.copy()
-        run[start:start + STEP_ROWS] = True
-        yield f"run of {STEP_ROWS} at {start}", run
-    for start in (BLOCK_ROWS, BLOCK_ROWS + 3 * STEP_ROWS + 9):  # a whole workgroup; the same run across two workgroups
-        run = every.copy()
-        run[start:start + BLOCK_ROWS] = True
-        yield f"run of {BLOCK_ROWS} at {start}", run
-    second = every.copy()
-    second[::2] = True
-    yield "every second", second
-    yield "every row", ~every
-
-
 @pytest.mark.parametrize("n", [BIG, STEP_ROWS + 1])
 def test_null_rows(ctx, n):
     rng = np.random.default_rng(n)
     src_rows = 1000
     src8, src1 = column(rng, src_rows, 8), column(rng, src_rows, 1)
     cols = [(src8, 8, fill_of(8, 3)), (src1, 1, fill_of(1, 4))]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         for name, null in _null_patterns(BIG):
             null = null[:n].copy()
@@ -187,7 +114,7 @@ def test_eight_columns_in_one_call_equal_eight_calls(ctx):
     cols = [(column(rng, src_rows, w), w, fill_of(w, 10 + k)) for k, w in enumerate(widths)]
     m = rng.integers(0, src_rows, n).astype(np.uint32)
     m[rng.integers(0, n, n // 5)] = NO_ROW
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         together = g.run(m, src_rows, cols, tag="eight columns")
         for k, col in enumerate(cols):
@@ -205,7 +132,7 @@ def test_eight_columns_in_one_call_equal_eight_calls(ctx):
 def test_validity_plane_alone_and_no_validity_plane(ctx):
     rng = np.random.default_rng(9)
     src = column(rng, 300, 2)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         for n in (1, STEP_ROWS + 1, BIG):
             m = rng.integers(0, 300, n).astype(np.uint32)
@@ -224,7 +151,7 @@ def test_map_shapes(ctx):
     src = column(rng, 3 * n, 8)
     maps = {"identity": np.arange(n), "reverse": np.arange(n)[::-1], "one source row": np.full(n, 1234),
             "ascending with gaps": np.cumsum(rng.integers(1, 4, n)) - 1}
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         for name, m in maps.items():
             assert m.max() < 3 * n
@@ -237,7 +164,7 @@ def test_row_base(ctx):
     rng = np.random.default_rng(11)
     n, src_rows = 2 * BLOCK_ROWS + 5, 900
     src = column(rng, src_rows, 8)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         for base in (5000, NO_ROW - 10):
             m = (rng.integers(0, min(src_rows, NO_ROW - base), n) + base).astype(np.uint32)
@@ -255,7 +182,7 @@ def test_out_of_range_entries_are_never_read(ctx):
     width, lead, src_rows, n = 8, 4096, 100, 2 * BLOCK_ROWS + 33
     whole = column(rng, 2 * lead, width)
     src = whole[lead:lead + src_rows]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather(ctx, dev)
         d_whole = dev.put(whole)
         d_src = d_whole + lead * width
@@ -281,10 +208,10 @@ def test_refused_calls_write_nothing(ctx):
     n, src_rows = 100, 50
     m = rng.integers(0, src_rows, n).astype(np.uint32)
     src = column(rng, src_rows, 16)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_map, d_src = dev.put(m), dev.put(src)
-        d_dst = dev.put(np.full(n * 16 + GUARD_BYTES, 0xA5, dtype=np.uint8))
-        d_valid = dev.put(np.full(4 + GUARD_WORDS, SENTINEL, dtype=np.uint32))
+        dst, valid = GuardedPlane(dev, n * 16, np.uint8, 0xA5, behind=GUARD_BYTES), GuardedPlane(dev, 4, behind=GUARD_WORDS)
+        d_dst, d_valid = dst.ptr, valid.ptr
         ctx.gather(d_map, n, src_rows, [(d_src, d_dst, 4, 0)])          # a call to remember
         before = ctx.gather_info()
         assert before[0] == n
@@ -324,8 +251,8 @@ def test_refused_calls_write_nothing(ctx):
         assert raw(d_map, 0, 0, src_rows, one, 1, d_valid) == _lib.HJ_OK
         assert raw(0, 0, 0, 0, [], 0, 0) == _lib.HJ_OK
         assert ctx.gather_info() == before
-        assert (get_bytes(ctx, d_dst, n * 16 + GUARD_BYTES) == 0xA5).all()
-        assert (dev.get(d_valid, 4 + GUARD_WORDS) == SENTINEL).all()
+        dst.read(0, "a refused call wrote a byte")
+        valid.read(0, "a refused call wrote a validity word")
         # and the context still gathers
         Gather(ctx, dev).run(m, src_rows, [(src, 16, fill_of(16, 14))], tag="after the refused calls")
 
@@ -333,7 +260,7 @@ def test_refused_calls_write_nothing(ctx):
 def test_info_is_zero_before_the_first_call():
     with hj.HashJoinContext(0) as fresh:
         assert fresh.gather_info() == (0, 0, 0, 0)
-        with Dev(fresh) as dev:
+        with Device(fresh) as dev:
             Gather(fresh, dev).run(np.arange(5, dtype=np.uint32), 5, [(np.arange(5, dtype=np.uint64).view("V8"), 8, bytes(16))],
                                    tag="no reserve, no table")
         assert fresh.gather_info()[0] == 5
@@ -356,11 +283,11 @@ def test_the_librarys_own_maps(ctx, algo):
     r_only = unmatched_r(inner, n, r_base)
     assert inner.size and no_match.size >= n // 2 and r_only.size >= n // 8
     rows = inner.size + no_match.size
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, S.size, keepRowIds=True, trackRMatches=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n, r_base)
-        d_s, d_r = dev.planes(rows)
+        d_s, d_r = (p.ptr for p in planes(dev, rows))
         ctx.probe_pairs(dS, S.size, d_s, d_r, rows, s_idx_base=s_base, kind=LEFT)
         assert ctx.pairs_info()[:2] == (rows, rows)
         d_rows = dev.put(np.full(n, SENTINEL, dtype=np.uint32))
@@ -375,7 +302,7 @@ def test_the_librarys_own_maps(ctx, algo):
             keys, words = np.empty(n_rows, dtype=U64), np.empty((n_rows + 31) // 32, dtype=np.uint32)
             ctx.copy_d2h(keys, d_dst)
             ctx.copy_d2h(words, d_valid)
-            return keys, np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool), info
+            return keys, plane_bits(words, n_rows), info
 
         s_keys, s_valid, s_info = gather(d_s, rows, dS, S.size, s_base)
         r_keys, r_valid, r_info = gather(d_r, rows, dR, n, r_base)

@@ -15,11 +15,11 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from join_kinds_common import SENTINEL, Dev
+from gather_common import (BIG, BLOCK_ROWS, GUARD_WORDS, NO_ROW, SEAM_ROWS, STEP_ROWS, WAVE_ROWS, WIDTHS, _null_patterns, column, fill_of, fixed,
+                           rows_of, strings, want_of)
+from gather_common import expected as plain_expected
+from gpu_harness import SENTINEL, Device, GuardedPlane, ctx, plane_words  # noqa: F401
 from keys2_common import LENGTHS
-from test_gpu_gather import (BIG, BLOCK_ROWS, GUARD_WORDS, NO_ROW, SEAM_ROWS, STEP_ROWS, WAVE_ROWS, WIDTHS, _null_patterns, column,
-                             fill_of, get_bytes, valid_words)
-from test_gpu_gather import expected as plain_expected
 
 pytestmark = pytest.mark.gpu
 
@@ -27,53 +27,6 @@ COPY_BLOCK_BYTES = 16
 COPY_PASS_BYTES = 256 * COPY_BLOCK_BYTES
 GUARD = 256                      # bytes in front of and behind every output (a multiple of 16: the alignment stays)
 SENT = 0xA5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
-# ---- the model -------------------------------------------------------------------------------------------------------------
-def rows_of(m, row_base, src_rows):
-    """-> (source row per output row, NULL rows, out-of-range entries, rows with a source row)"""
-    e = m.astype(np.int64)
-    null = e == NO_ROW
-    i = (e - row_base) % (1 << 32)
-    oor = ~null & (i >= src_rows)
-    return i, null, oor, ~null & ~oor
-
-
-def fixed(src, width, fill, valid=None, dst_valid=False, **kw):
-    return dict(width=width, src=src, fill=fill, valid=valid, dst_valid=dst_valid, **kw)
-
-
-def strings(rng, lengths, lead=0, valid=None, dst_valid=False, **kw):
-    """a variable-length source: `lead` bytes in front of the first element (offsets[0] = lead), three behind the last"""
-    off = lead + np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
-    data = rng.integers(0, 256, int(off[-1]) + 3, dtype=np.uint8)
-    return dict(width=0, offsets=off, data=data, valid=valid, dst_valid=dst_valid, **kw)
-
-
-def want_of(col, i, ok, n):
-    """-> (rows with a valid element, the output bytes, the output offsets or None)"""
-    el = ok.copy()
-    if col["valid"] is not None:
-        el[ok] = col["valid"][i[ok]]
-    if col["width"]:
-        w = col["width"]
-        out = np.empty(n, dtype=f"V{w}")
-        out[:] = np.frombuffer(col["fill"][:w], dtype=f"V{w}")[0]
-        if el.any():
-            out[el] = col["src"][i[el]]
-        return el, out.tobytes(), None
-    off, data = col["offsets"], col["data"]
-    lens = np.zeros(n, dtype=np.int64)
-    lens[el] = off[i[el] + 1] - off[i[el]]
-    raw = b"".join(data[off[j]:off[j + 1]].tobytes() for j in i[el])
-    return el, raw, np.concatenate([[0], np.cumsum(lens)])
 
 
 class Gather2:
@@ -90,8 +43,8 @@ class Gather2:
         i, null, oor, ok = rows_of(m, row_base, src_rows)
         words = (n + 31) // 32
         d_map = dev.put(m)
-        d_valid = dev.put(np.full(1 + words + GUARD_WORDS, SENTINEL, dtype=np.uint32)) if with_valid else 0
-        descs, wants, held = [], [], [d_map] + ([d_valid] if with_valid else [])
+        valid = GuardedPlane(dev, words, front=valid_offset, behind=1 + GUARD_WORDS - valid_offset, what="dValid guard") if with_valid else None
+        descs, wants, held = [], [], [d_map] + ([valid.base] if with_valid else [])
         for col in cols:
             el, raw, off = want_of(col, i, ok, n)
             total = len(raw) if not col["width"] else 0
@@ -103,44 +56,35 @@ class Gather2:
             else:
                 d_values = dev.put(col["src"] if col["width"] else col["data"]) if src_rows else 0
                 d_off = dev.put(col["offsets"].astype(np.uint32)) if not col["width"] else 0
-                d_ok = dev.put(valid_words(col["valid"])) if col["valid"] is not None else 0
+                d_ok = dev.put(plane_words(col["valid"])) if col["valid"] is not None else 0
                 held += [p for p in (d_values, d_off, d_ok) if p]
-            d_dst = dev.put(np.full(2 * GUARD + lead + room, SENT, dtype=np.uint8))
-            d_doff = dev.put(np.full(2 * GUARD_WORDS + n + 1, SENTINEL, dtype=np.uint32)) if not col["width"] else 0
+            dst = GuardedPlane(dev, room, np.uint8, SENT, front=GUARD + lead, behind=GUARD, what="a byte outside the column's output was written")
+            doff = GuardedPlane(dev, n + 1, front=GUARD_WORDS, behind=GUARD_WORDS, what="dstOffsets guard") if not col["width"] else None
             vo = col.get("dst_valid_offset", 0)
-            d_dvalid = dev.put(np.full(1 + words + GUARD_WORDS, SENTINEL, dtype=np.uint32)) if col["dst_valid"] else 0
-            held += [p for p in (d_dst, d_doff, d_dvalid) if p]
+            dvalid = GuardedPlane(dev, words, front=vo, behind=1 + GUARD_WORDS - vo, what="dstValid guard") if col["dst_valid"] else None
+            held += [p.base for p in (dst, doff, dvalid) if p]
             null_dst = not col["width"] and cap == 0 and col.get("null_dst", False)
-            descs.append(dict(src=d_values, dst=0 if null_dst else d_dst + GUARD + lead, width=col["width"], fill=col.get("fill", 0),
-                              src_offsets=d_off, dst_offsets=d_doff + 4 * GUARD_WORDS if d_doff else 0, src_valid=d_ok,
-                              dst_valid=d_dvalid + 4 * vo if d_dvalid else 0, dst_capacity=0 if col["width"] else cap))
-            wants.append((el, raw, off, total, cap, room, lead, d_dst, d_doff, d_dvalid, vo))
-        ctx.gather2(d_map, n, src_rows, descs, d_valid=d_valid + 4 * valid_offset if with_valid else 0, row_base=row_base)
+            descs.append(dict(src=d_values, dst=0 if null_dst else dst.ptr, width=col["width"], fill=col.get("fill", 0),
+                              src_offsets=d_off, dst_offsets=doff.ptr if doff else 0, src_valid=d_ok,
+                              dst_valid=dvalid.ptr if dvalid else 0, dst_capacity=0 if col["width"] else cap))
+            wants.append((el, raw, off, total, cap, room, dst, doff, dvalid))
+        ctx.gather2(d_map, n, src_rows, descs, d_valid=valid.ptr if with_valid else 0, row_base=row_base)
         info = ctx.gather2_info()
         print(tag, "rows", n, "info", info)
         assert info[:2] == (n, int(null.sum())) and info[3] == int(oor.sum()), (tag, info, n, int(null.sum()), int(oor.sum()))
         assert info[4:] == tuple([w[3] for w in wants] + [0] * (8 - len(wants))), (tag, info)
         if with_valid:
-            plane = dev.get(d_valid, 1 + words + GUARD_WORDS)
-            assert (plane[:valid_offset] == SENTINEL).all() and (plane[valid_offset + words:] == SENTINEL).all(), (tag, "dValid guard")
-            assert np.array_equal(plane[valid_offset:valid_offset + words], valid_words(ok)), (tag, "dValid")
+            assert np.array_equal(valid.read(words, tag), plane_words(ok)), (tag, "dValid")
         got = []
-        for col, (el, raw, off, total, cap, room, lead, d_dst, d_doff, d_dvalid, vo) in zip(cols, wants):
-            buf = get_bytes(ctx, d_dst, 2 * GUARD + lead + room)
-            body = buf[GUARD + lead:GUARD + lead + room]
+        for col, (el, raw, off, total, cap, room, dst, doff, dvalid) in zip(cols, wants):
             kept = room if col["width"] else min(total, cap)
-            assert (buf[:GUARD + lead] == SENT).all() and (buf[GUARD + lead + kept:] == SENT).all(), \
-                (tag, col["width"], "a byte outside the column's output was written")
-            assert body[:kept].tobytes() == raw[:kept], (tag, col["width"], n, "bytes")
-            if d_doff:
-                offs = dev.get(d_doff, 2 * GUARD_WORDS + n + 1)
-                assert (offs[:GUARD_WORDS] == SENTINEL).all() and (offs[GUARD_WORDS + n + 1:] == SENTINEL).all(), (tag, "dstOffsets guard")
-                assert np.array_equal(offs[GUARD_WORDS:GUARD_WORDS + n + 1].astype(np.int64), off), (tag, "dstOffsets")
-            if d_dvalid:
-                plane = dev.get(d_dvalid, 1 + words + GUARD_WORDS)
-                assert (plane[:vo] == SENTINEL).all() and (plane[vo + words:] == SENTINEL).all(), (tag, "dstValid guard")
-                assert np.array_equal(plane[vo:vo + words], valid_words(el)), (tag, "dstValid")
-            got.append((body[:kept].tobytes(), None if off is None else off.copy(), el))
+            body = dst.read(kept, (tag, col["width"]))
+            assert body.tobytes() == raw[:kept], (tag, col["width"], n, "bytes")
+            if doff:
+                assert np.array_equal(doff.read(n + 1, tag).astype(np.int64), off), (tag, "dstOffsets")
+            if dvalid:
+                assert np.array_equal(dvalid.read(words, tag), plane_words(el)), (tag, "dstValid")
+            got.append((body.tobytes(), None if off is None else off.copy(), el))
         dev.free(*held)
         return got
 
@@ -158,7 +102,7 @@ def test_row_seams_lengths_and_alignments(ctx, lead):
     src_rows = 150
     col = strings(rng, cycled_lengths(src_rows), lead=lead)
     pairs = set()
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         d_src = (dev.put(col["data"]), dev.put(col["offsets"].astype(np.uint32)), 0)
         for n in SEAM_ROWS:
@@ -182,7 +126,7 @@ def test_map_shapes(ctx):
     maps = {"identity": np.arange(n), "reverse": np.arange(n)[::-1], "ascending with gaps": np.cumsum(rng.integers(1, 4, n)) - 1,
             "one source row": np.full(n, 8)}                 # a 257-byte element: the output is larger than the source
     assert cycled_lengths(3 * n)[8] == 257
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for name, m in maps.items():
             got = g.run(np.ascontiguousarray(m, dtype=np.uint32), 3 * n, [col, num], tag=name)
@@ -196,7 +140,7 @@ def test_null_rows(ctx, n):
     src_rows = 400
     col = strings(rng, cycled_lengths(src_rows, 5), lead=2, dst_valid=True)
     num = fixed(column(rng, src_rows, 4), 4, fill_of(4, 2), dst_valid=True)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for name, null in _null_patterns(BIG):
             null = null[:n].copy()
@@ -210,7 +154,7 @@ def test_row_base(ctx):
     rng = np.random.default_rng(22)
     n, src_rows = 2 * BLOCK_ROWS + 5, 900
     col = strings(rng, cycled_lengths(src_rows), valid=rng.random(src_rows) < 0.8, dst_valid=True)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for base in (5000, NO_ROW - 10):
             m = (rng.integers(0, min(src_rows, NO_ROW - base), n) + base).astype(np.uint32)
@@ -231,9 +175,9 @@ def test_out_of_range_entries_are_never_read(ctx):
     whole_valid[lead_rows:lead_rows + src_rows] = win["valid"]
     num_whole = column(rng, 2 * lead_rows, 8)
     num = fixed(num_whole[lead_rows:lead_rows + src_rows], 8, fill_of(8, 3), valid=win["valid"], dst_valid=True)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
-        d_data, d_off, d_ok, d_num = dev.put(whole["data"]), dev.put(off.astype(np.uint32)), dev.put(valid_words(whole_valid)), dev.put(num_whole)
+        d_data, d_off, d_ok, d_num = dev.put(whole["data"]), dev.put(off.astype(np.uint32)), dev.put(plane_words(whole_valid)), dev.put(num_whole)
         assert lead_rows % 32 == 0
         win["d_src"] = (d_data, d_off + 4 * lead_rows, d_ok + lead_rows // 8)
         num["d_src"] = (d_num + 8 * lead_rows, 0, d_ok + lead_rows // 8)
@@ -255,7 +199,7 @@ def test_out_of_range_entries_are_never_read(ctx):
 def test_empty_elements(ctx):
     rng = np.random.default_rng(24)
     n = BIG
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for start, run in ((STEP_ROWS + 5, STEP_ROWS), (WAVE_ROWS - 9, WAVE_ROWS), (BLOCK_ROWS - 100, BLOCK_ROWS + 300), (0, n)):
             lens = np.array(cycled_lengths(n))
@@ -284,7 +228,7 @@ def test_long_elements(ctx):
     lens[long_row] = COPY_PASS_BYTES + 904                       # longer than a pass of the workgroup
     lens[block_row] = COPY_BLOCK_BYTES + 1                       # just above one lane's block
     col = strings(rng, lens, lead=1)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for n in (BLOCK_ROWS + 200, 300):
             m = rng.integers(0, src_rows, n).astype(np.uint32)
@@ -312,7 +256,7 @@ def test_cuts(ctx):
     cuts = {"sizing": 0, "one byte": 1, "middle of an element": int(off[mid]) + 20, "middle of a 16-byte store": 16 * 50 + 7,
             "a workgroup's first byte": int(off[BLOCK_ROWS]), "total - 1": total - 1, "total": total, "more than the total": total + 100}
     assert 0 < cuts["middle of an element"] < total and 0 < cuts["a workgroup's first byte"] < total
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for name, cap in cuts.items():
             for lead in (0, 5):
@@ -328,7 +272,7 @@ def test_totals_beyond_32_bits(ctx):
     size, n = (4 << 20) + 1, 1100
     assert BLOCK_ROWS * size > 1 << 32
     m = np.zeros(n, dtype=np.uint32)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_data = dev.alloc(size + 3)
         d_off = dev.put(np.array([0, size], dtype=np.uint32))
         d_map = dev.put(m)
@@ -340,11 +284,11 @@ def test_totals_beyond_32_bits(ctx):
             ctx.gather2(d_map, n, 1, [dict(desc, dst=d_dst + GUARD if cap else 0, dst_capacity=cap)])
             info = ctx.gather2_info()
             assert info[:2] == (n, 0) and info[3] == 0 and info[4] == n * size and info[4] > 0xFFFFFFFF, info
-            assert (get_bytes(ctx, d_dst, 2 * GUARD + 64) == SENT).all()
+            assert (dev.get(d_dst, 2 * GUARD + 64, np.uint8) == SENT).all()
             offs = dev.get(d_doff, 2 * GUARD_WORDS + n + 1)      # unspecified inside, untouched outside
             assert (offs[:GUARD_WORDS] == SENTINEL).all() and (offs[GUARD_WORDS + n + 1:] == SENTINEL).all()
             plane = dev.get(d_dvalid, 1 + (n + 31) // 32 + GUARD_WORDS)
-            assert np.array_equal(plane[:(n + 31) // 32], valid_words(np.ones(n, dtype=bool))) and (plane[(n + 31) // 32:] == SENTINEL).all()
+            assert np.array_equal(plane[:(n + 31) // 32], plane_words(np.ones(n, dtype=bool))) and (plane[(n + 31) // 32:] == SENTINEL).all()
         # below the limit the same call is exact again: 1023 rows are 2^32 - 4 MiB + 1023 bytes
         ctx.gather2(d_map, 1023, 1, [dict(desc, dst_capacity=0)])
         assert ctx.gather2_info()[4] == 1023 * size
@@ -364,7 +308,7 @@ def test_source_validity(ctx, width):
             return fixed(column(rng, src_rows, width), width, fill_of(width, 5), valid=valid, **kw)
         return strings(rng, cycled_lengths(src_rows), lead=1, valid=valid, **kw)
 
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         for share in (0.3, 1.0):                                 # 30 % NULLs; every source row NULL
             valid = rng.random(src_rows) >= share
@@ -401,7 +345,7 @@ def test_eight_mixed_columns_in_one_call_equal_eight_calls(ctx):
             strings(rng, cycled_lengths(src_rows, 4), valid=some(), capacity=1000)]
     m = rng.integers(0, src_rows, n).astype(np.uint32)
     m[rng.integers(0, n, n // 5)] = NO_ROW
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         g = Gather2(ctx, dev)
         together = g.run(m, src_rows, cols, tag="eight mixed columns")
         for k, col in enumerate(cols):
@@ -420,7 +364,7 @@ def test_plain_columns_equal_hj_gather_dev(ctx):
     m = rng.integers(0, src_rows + 50, n).astype(np.uint32)     # some out of range
     m[rng.integers(0, n, n // 5)] = NO_ROW
     words = (n + 31) // 32
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_map = dev.put(m)
         d_srcs = [dev.put(s) for s in srcs]
         outs = []
@@ -436,7 +380,7 @@ def test_plain_columns_equal_hj_gather_dev(ctx):
                             d_valid=d_valid)
                 info = ctx.gather2_info()
                 assert info[4:] == (0,) * 8 and ctx.gather_info() == before       # two records
-            outs.append(([get_bytes(ctx, d, n * w + GUARD).tobytes() for d, w in zip(d_dsts, widths)],
+            outs.append(([dev.get(d, n * w + GUARD, np.uint8).tobytes() for d, w in zip(d_dsts, widths)],
                          dev.get(d_valid, words + GUARD_WORDS).tobytes(), (info[0], info[1], info[3])))
         assert outs[0] == outs[1]
         for k, (w, s) in enumerate(zip(widths, srcs)):
@@ -454,9 +398,9 @@ def test_refused_calls_write_nothing(ctx):
     words = (n + 31) // 32
     col = strings(rng, cycled_lengths(src_rows))
     num = column(rng, src_rows, 16)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_map, d_data, d_off, d_num = dev.put(m), dev.put(col["data"]), dev.put(col["offsets"].astype(np.uint32)), dev.put(num)
-        d_ok = dev.put(valid_words(np.ones(src_rows, dtype=bool)))
+        d_ok = dev.put(plane_words(np.ones(src_rows, dtype=bool)))
         room = 16 * n + 4096
         d_dst, d_dst2 = dev.put(np.full(room, SENT, dtype=np.uint8)), dev.put(np.full(room, SENT, dtype=np.uint8))
         d_doff = dev.put(np.full(n + 1 + GUARD_WORDS, SENTINEL, dtype=np.uint32))
@@ -533,7 +477,7 @@ def test_refused_calls_write_nothing(ctx):
         assert raw([var, fix], n_rows=0) == _lib.HJ_OK and raw([], d_map_=0, n_rows=0, rows=0, valid=0) == _lib.HJ_OK
         assert ctx.gather2_info() == before2 and ctx.gather_info() == before
         for d, size in ((d_dst, room), (d_dst2, room)):
-            assert (get_bytes(ctx, d, size) == SENT).all()
+            assert (dev.get(d, size, np.uint8) == SENT).all()
         for d, size in ((d_doff, n + 1 + GUARD_WORDS), (d_dvalid, words + GUARD_WORDS), (d_valid, words + GUARD_WORDS)):
             assert (dev.get(d, size) == SENTINEL).all()
         # and the context still gathers
@@ -543,7 +487,7 @@ def test_refused_calls_write_nothing(ctx):
 def test_info_is_zero_before_the_first_call():
     with hj.HashJoinContext(0) as fresh:
         assert fresh.gather2_info() == (0,) * 12
-        with Dev(fresh) as dev:
+        with Device(fresh) as dev:
             rng = np.random.default_rng(30)
             Gather2(fresh, dev).run(np.arange(5, dtype=np.uint32), 5, [strings(rng, [3, 0, 9, 1, 40])], tag="no reserve, no table")
         assert fresh.gather2_info()[0] == 5 and fresh.gather_info() == (0, 0, 0, 0)

@@ -8,16 +8,11 @@ import pytest
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import ctx  # noqa: F401
 import htm_chain_cases as cc
 from htm_chain_device import run_case, run_relation
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    with hj.HashJoinContext(0) as c:
-        yield c
 
 
 @pytest.mark.parametrize("case", cc.ONE_PART, ids=lambda c: c.name)

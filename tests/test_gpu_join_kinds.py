@@ -17,21 +17,16 @@ from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-from join_kinds_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, KINDS, NAMES, NO_ROW, Dev, Calls, derive,
-                               matched_rows, _status, zipf)
+from gpu_harness import Device, ctx, status  # noqa: F401
+from join_kinds_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, KINDS, NAMES, NO_ROW, Calls, derive, matched_rows,
+                               zipf,
+                               planes)
 from r_marks_common import join_expected, walk_expected, inner_expected
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def run_all_kinds(ctx, algo, R, S, inner, probe_length=4, kinds=KINDS, offset=0, tag=None, **reserve):
     """build R, then every kind over S passed at dS + 8 * offset bytes (S = buf[offset:])"""
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, R.size, max(S.size, 1), probeLength=probe_length, keepRowIds=True, **reserve)
         buf = np.concatenate([np.zeros(offset, dtype=U64), S])
         dR, dS = dev.put(R), dev.put(buf)
@@ -78,7 +73,7 @@ def test_htm_long_chains(ctx):
     S = np.concatenate([np.array([hot], dtype=U64), absent, near, zipf(1 << 12, 1 << 12, 1.0, 12345),
                         np.array([hot], dtype=U64), absent[:1]])
     inner = join_expected(R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("htm", R.size, S.size)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, R.size)
@@ -159,11 +154,11 @@ def test_stage_flushes_mid_run(ctx, algo, kind):
     want_r = np.full(ns, 0xFFFFFFFF, dtype=np.uint32)
     want_r[:nr] = np.arange(nr, dtype=np.uint32)
     rows = ns if kind == LEFT else ns - nr
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, nr, ns, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, nr)
-        ds, dr = dev.planes(rows)
+        ds, dr = (p.ptr for p in planes(dev, rows))
         ctx.probe_pairs(dS, ns, ds, dr, rows, kind=kind)
         found, written, _us, unmatched = ctx.pairs_info()
         s, r = dev.get(ds, rows + GUARD), dev.get(dr, rows + GUARD)
@@ -193,7 +188,7 @@ def test_capacity_cuts_the_output_and_nothing_else(ctx, algo, kind):
     R, S, inner = _capacity_case(algo)
     want = derive(kind, inner, n)
     assert want.size > 2
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, n, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n)
@@ -250,7 +245,7 @@ def test_ragged_slices_add_up_to_the_whole(ctx, algo):
     S = oracle.generate_data("uniform", n, 2 * n, 16)[: n - 5]            # half of the key range is absent from R
     whole = inner_expected(algo, R, S)
     cuts = [0, 1001, 1001 + 20000, 1001 + 20000 + 1, S.size]              # unequal slices; three start at odd rows
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, S.size, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n)
@@ -270,39 +265,39 @@ def test_errors():
     n = 1 << 12
     R = oracle.generate_data("local_shuffle", n, n, 16)
     S = oracle.generate_data("sorted", 2 * n)[n // 2: n // 2 + n]
-    with hj.HashJoinContext(0) as ctx, Dev(ctx) as dev:
+    with hj.HashJoinContext(0) as ctx, Device(ctx) as dev:
         dR, dS = dev.put(R), dev.put(S)
-        ds, dr = dev.planes(n)
+        ds, dr = (p.ptr for p in planes(dev, n))
         for kind in KINDS:
             # a PRJ context, with and without a resident R
             ctx.reserve("prj", n, n, keepRowIds=True)
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
             ctx.prj_build(dR, n)
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
             # open addressing without the flag: refused before and after the build, and nothing is counted
             ctx.reserve("atomic", n, n)
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
             ctx.build(dR, n)
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_STATE
             got = ctx.fetch()
             assert (got["totalMatches"], got["sSize"]) == (0, 0)
         # with the flag
         ctx.reserve("atomic", n, n, keepRowIds=True)
         ctx.build(dR, n)
         for kind in (4, 5, 0xFFFFFFFF):
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_INVALID
-            assert _status(ctx.probe_pairs, dS, n, 0, 0, 0, kind=kind) == _lib.HJ_ERR_INVALID
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, kind=kind) == _lib.HJ_ERR_INVALID
+            assert status(ctx.probe_pairs, dS, n, 0, 0, 0, kind=kind) == _lib.HJ_ERR_INVALID
         for kind in KINDS:
-            assert _status(ctx.probe_pairs, dS, n, 0, dr, n, kind=kind) == _lib.HJ_ERR_INVALID
-            assert _status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n, kind=kind) == _lib.HJ_ERR_INVALID
+            assert status(ctx.probe_pairs, dS, n, 0, dr, n, kind=kind) == _lib.HJ_ERR_INVALID
+            assert status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n, kind=kind) == _lib.HJ_ERR_INVALID
         for kind in (INNER, LEFT):                            # the R plane is needed where it is written ...
-            assert _status(ctx.probe_pairs, dS, n, ds, 0, n, kind=kind) == _lib.HJ_ERR_INVALID
+            assert status(ctx.probe_pairs, dS, n, ds, 0, n, kind=kind) == _lib.HJ_ERR_INVALID
         got = ctx.fetch()
         assert (got["totalMatches"], got["sSize"]) == (0, 0)                 # nothing of the refused calls was counted
         assert (dev.get(ds, n + GUARD) == SENTINEL).all() and (dev.get(dr, n + GUARD) == SENTINEL).all()
         inner = walk_expected(R, S, 4)
         for k, kind in enumerate((SEMI, ANTI)):               # ... and may be NULL where it is not
-            assert _status(ctx.probe_pairs, dS, n, ds, 0, n, kind=kind) == _lib.HJ_OK
+            assert status(ctx.probe_pairs, dS, n, ds, 0, n, kind=kind) == _lib.HJ_OK
             found, written = ctx.pairs_info()[:2]
             want = derive(kind, inner, n)
             assert found == written == want.size
@@ -327,14 +322,14 @@ def test_inner_is_the_pairs_probe(ctx, algo):
     S = oracle.generate_data("uniform", n, 2 * n, 16)[: n - 3]
     want = inner_expected(algo, R, S)
     got = []
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, S.size, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n)
         ctx.probe_pairs(dS, S.size, 0, 0, 0, kind=LEFT)      # a kind call in front: its unmatched count must not stick
         assert ctx.pairs_info()[3] == S.size - matched_rows(want).size
         for entry in ("hj_probe_join_dev", "hj_probe_pairs_dev"):
-            ds, dr = dev.planes(want.size + 64)
+            ds, dr = (p.ptr for p in planes(dev, want.size + 64))
             args = (ds, dr, want.size + 64)
             if entry == "hj_probe_join_dev":
                 rc = hj.lib.hj_probe_join_dev(ctx._h, INNER, dS, S.size, 0, *args)

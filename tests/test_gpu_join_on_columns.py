@@ -7,8 +7,9 @@ import pytest
 
 import htm_hashjoin_amd as hj
 
+from gpu_harness import alloc
+from join_on_common import PAIR, WEAK, check
 from keys2_common import HOWS, ModelCol, inner_pairs, key_column, row_keys
-from test_gpu_join_on import PAIR, WEAK, check
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +126,7 @@ def test_null_rows_do_not_explode_the_candidates():
         ptrs = []
 
         def put(a):
-            ptrs.append(ctx.dev_alloc(max(a.nbytes, 4)))
+            ptrs.append(alloc(ctx, max(a.nbytes, 4)))
             ctx.copy_h2d(ptrs[-1], a)
             return ptrs[-1]
 

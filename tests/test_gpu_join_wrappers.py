@@ -8,7 +8,8 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from join_kinds_common import U64, INNER, LEFT, SEMI, ANTI, _status, derive
+from gpu_harness import status
+from join_kinds_common import U64, INNER, LEFT, SEMI, ANTI, derive
 from r_marks_common import inner_expected, r_rows_of, unmatched_r
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +99,7 @@ def test_key_range_table_paths_refuse(data, wrapper, how, path):
     R, S, _ = data
     R = R.copy()
     R[7] |= U64(1) << U64(40)
-    assert _status(call, wrapper, R, S, how, path, None) == _lib.HJ_ERR_KEY_RANGE
+    assert status(call, wrapper, R, S, how, path, None) == _lib.HJ_ERR_KEY_RANGE
 
 
 @pytest.mark.parametrize("slice_tuples", [None, SLICE])

@@ -12,10 +12,10 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
+from gpu_harness import GuardedPlane, dev, fl  # noqa: F401
 import groups_common as gc
 import keys2_common as k2
 import stream_order as so
-from test_gpu_keys2 import Device
 
 pytestmark = pytest.mark.gpu
 
@@ -25,26 +25,9 @@ GUARD = 64                       # words in front of and behind every output
 SENT = 0xA5A5A5A5
 
 
-@pytest.fixture(scope="module")
-def dev():
-    d = Device()
-    yield d
-    d.close()
-
-
-class Out:
+def out_plane(dev, n):
     """an output plane of n words on the device between two guards"""
-
-    def __init__(self, dev, n):
-        self.dev, self.n = dev, n
-        self.base = dev.put(np.full(n + 2 * GUARD, SENT, dtype=U32))
-        self.ptr = self.base + 4 * GUARD
-
-    def read(self, written, tag):
-        """the first `written` words; everything else still holds the sentinel"""
-        a = self.dev.get(self.base, self.n + 2 * GUARD)
-        assert (a[:GUARD] == SENT).all() and (a[GUARD + written:] == SENT).all(), (tag, "a word outside the output was written")
-        return a[GUARD:GUARD + written]
+    return GuardedPlane(dev, n, sentinel=SENT, front=GUARD, behind=GUARD, what="a word outside the output was written")
 
 
 def groups_on_device(dev, keys, nulls, key_mask=0, capacity=None, tag=None, release=True):
@@ -56,7 +39,7 @@ def groups_on_device(dev, keys, nulls, key_mask=0, capacity=None, tag=None, rele
         v, off, valid = dev.column(c)
         desc.append((v, 0, c.width, off, 0, valid, 0, f))
     cap = n if capacity is None else capacity
-    rep, group, first = Out(dev, n), Out(dev, n), Out(dev, cap)
+    rep, group, first = out_plane(dev, n), out_plane(dev, n), out_plane(dev, cap)
     dev.ctx.key_groups(desc, hj.HJ_KEY_SIDE_S, n, rep.ptr, group.ptr, first.ptr if cap else 0, cap, key_mask)
     info = dev.ctx.key_groups_info()
     assert info["failure"] == 0, (tag, info)
@@ -165,7 +148,7 @@ def test_optional_outputs(dev):
     """no group plane, no first rows: rep alone, and the count of the groups all the same"""
     cols, want = table("thousand")
     a = cols[0]
-    rep = Out(dev, a.size)
+    rep = out_plane(dev, a.size)
     dev.ctx.key_groups([(dev.put(a), 0, 8)], hj.HJ_KEY_SIDE_S, a.size, rep.ptr)
     info = dev.ctx.key_groups_info()
     assert (info["groups"], info["written"], info["failure"]) == (1000, 0, 0)
@@ -277,13 +260,6 @@ def test_everything_dropped():
 
 
 # ---- stream order ----------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the case below cannot pass vacuously
-    return f
-
-
 def test_stream_order(fl):
     """decoy keys (all distinct) before the delay, the real keys (few, repeated) behind it on the caller's stream: a call
     that read early, or a table filled out of order, answers for the decoys"""

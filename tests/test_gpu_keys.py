@@ -11,7 +11,7 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from join_kinds_common import SENTINEL, U64, Dev, _status
+from gpu_harness import SENTINEL, U64, Device, GuardedPlane, check_pair_filter, ctx, packed, plane_words, row_bits, status  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +22,6 @@ CANDIDATES = 3 * 4096 + 17      # several workgroups, a ragged last one
 PAIR = np.dtype([("a", np.uint64), ("b", np.uint64)])
 WIDTH_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64, 16: PAIR}
 INVALID = _lib.HJ_ERR_INVALID
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def random_column(rng, width, n):
@@ -42,29 +35,16 @@ def test_device_hash_equals_host_hash(ctx, widths):
     for n in (1, 63, 64, 65, 1023, 1025, 4097):
         cols = [random_column(rng, w, n) for w in widths]
         for side, mask in ((hj.HJ_KEY_SIDE_S, 0), (hj.HJ_KEY_SIDE_R, 0), (hj.HJ_KEY_SIDE_R, 0x3F), (hj.HJ_KEY_SIDE_S, 0xFFFF0000)):
-            with Dev(ctx) as dev:
+            with Device(ctx) as dev:
                 d_cols = [dev.put(c) for c in cols]
-                d_out = dev.put(np.full(n + GUARD, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64))
+                out = GuardedPlane(dev, n, U64, 0xA5A5A5A5A5A5A5A5, behind=GUARD, what="a tuple behind the last row was written")
                 # only the pointers of the side in use are given
-                ctx.key_hash([(d, 0, w) if side == hj.HJ_KEY_SIDE_S else (0, d, w) for d, w in zip(d_cols, widths)], side, n, d_out, mask)
-                got = np.empty(n + GUARD, dtype=np.uint64)
-                ctx.copy_d2h(got, d_out)
-            assert (got[n:] == 0xA5A5A5A5A5A5A5A5).all(), (widths, n, "a tuple behind the last row was written")
-            assert np.array_equal(got[:n], hj.key_hash_host(cols, key_mask=mask)), (widths, n, side, mask)
+                ctx.key_hash([(d, 0, w) if side == hj.HJ_KEY_SIDE_S else (0, d, w) for d, w in zip(d_cols, widths)], side, n, out.ptr, mask)
+                got = out.read(n, (widths, n))
+            assert np.array_equal(got, hj.key_hash_host(cols, key_mask=mask)), (widths, n, side, mask)
 
 
 # ---- pairs_verify -----------------------------------------------------------------------------------------------------------
-def mark_words(rows, n):
-    """the plane of n rows in which exactly `rows` are set"""
-    bits = np.zeros(-(-n // 32) * 32, dtype=bool)
-    bits[np.asarray(rows, dtype=np.int64)] = True
-    return np.packbits(bits, bitorder="little").view(np.uint32)
-
-
-def packed(s, r):
-    return np.sort((s.astype(U64) << U64(32)) | r.astype(U64))
-
-
 class Verify:
     """one hj_pairs_verify_dev over numpy inputs, checked in full against numpy"""
 
@@ -90,52 +70,19 @@ class Verify:
         keep, dropped = self.expected(map_s, map_r, base)
         kept = int(keep.sum())
         cap = n if capacity is None else capacity
-        sw, rw = -(-self.s_rows // 32), -(-self.r_rows // 32)
-        with Dev(ctx) as dev:
-            d_ms, d_mr = dev.put(map_s), dev.put(map_r)
+        s = (map_s[keep].astype(np.int64) - base) % (1 << 32)
+        want = {"kept": packed(map_s[keep], map_r[keep]), "info": (kept, min(kept, cap), 0, dropped),
+                "s_marks": plane_words(row_bits(s, self.s_rows)), "r_marks": plane_words(row_bits(map_r[keep], self.r_rows))}
+        with Device(ctx) as dev:
             cols = [(dev.put(a), dev.put(b), a.dtype.itemsize) for a, b in zip(self.s_keys, self.r_keys)]
-            fill = np.full(offset + cap + GUARD, SENTINEL, dtype=np.uint32)
-            d_os, d_or = (dev.put(fill), dev.put(fill)) if cap else (0, 0)
-            plane_s = np.concatenate([np.full(GUARD, SENTINEL, np.uint32), np.zeros(sw, np.uint32), np.full(GUARD, SENTINEL, np.uint32)])
-            plane_r = np.concatenate([np.full(GUARD, SENTINEL, np.uint32), np.zeros(rw, np.uint32), np.full(GUARD, SENTINEL, np.uint32)])
-            d_ps, d_pr = (dev.put(plane_s), dev.put(plane_r)) if marks else (0, 0)
-            ctx.pairs_verify(d_ms, d_mr, n, base, self.s_rows, self.r_rows, cols, d_os + 4 * offset if cap else 0,
-                             d_or + 4 * offset if cap else 0, cap, d_ps + 4 * GUARD if marks else 0, d_pr + 4 * GUARD if marks else 0)
-            info = ctx.verify_info()
-            print(tag, "candidates", n, "info", info, "expected kept", kept, "dropped", dropped)
-            assert (info[0], info[1], info[3]) == (kept, min(kept, cap), dropped), (tag, info, kept, cap, dropped)
-            got_s = got_r = np.empty(0, dtype=np.uint32)
-            if cap:
-                out_s, out_r = dev.get(d_os, fill.size), dev.get(d_or, fill.size)
-                written = min(kept, cap)
-                for out in (out_s, out_r):
-                    assert (out[:offset] == SENTINEL).all() and (out[offset + written:] == SENTINEL).all(), (tag, "a word outside the run was written")
-                got_s, got_r = out_s[offset:offset + written], out_r[offset:offset + written]
-            got_ps = got_pr = None
-            if marks:
-                got_ps, got_pr = dev.get(d_ps, plane_s.size), dev.get(d_pr, plane_r.size)
-                for got, words in ((got_ps, sw), (got_pr, rw)):
-                    assert (got[:GUARD] == SENTINEL).all() and (got[GUARD + words:] == SENTINEL).all(), (tag, "a word outside the marks plane was written")
-                s = (map_s[keep].astype(np.int64) - base) % (1 << 32)
-                assert np.array_equal(got_ps[GUARD:GUARD + sw], mark_words(s, self.s_rows)), (tag, "S marks")
-                assert np.array_equal(got_pr[GUARD:GUARD + rw], mark_words(map_r[keep], self.r_rows)), (tag, "R marks")
-            # the relations and the maps are inputs: untouched
+            call = lambda ms, mr, os, o_r, c, ps, pr: ctx.pairs_verify(ms, mr, n, base, self.s_rows, self.r_rows, cols, os, o_r, c, ps, pr)      # noqa: E731
+            got = check_pair_filter(dev, call, ctx.verify_info, map_s, map_r, self.s_rows, self.r_rows, want, cap, GUARD, offset=offset, marks=marks,
+                                    tag=tag)
+            # the relations are inputs as the maps are: untouched
             for (d_a, d_b, w), a, b in zip(cols, self.s_keys, self.r_keys):
-                back_a, back_b = np.empty_like(a), np.empty_like(b)
-                ctx.copy_d2h(back_a, d_a)
-                ctx.copy_d2h(back_b, d_b)
+                back_a, back_b = dev.get(d_a, a.size, a.dtype), dev.get(d_b, b.size, b.dtype)
                 assert back_a.tobytes() == a.tobytes() and back_b.tobytes() == b.tobytes(), (tag, "a key column was written")
-            assert np.array_equal(dev.get(d_ms, n), map_s) and np.array_equal(dev.get(d_mr, n), map_r), (tag, "a map was written")
-        want = packed(map_s[keep], map_r[keep])
-        got = packed(got_s, got_r)
-        if cap >= kept:
-            assert np.array_equal(got, want), (tag, "the kept pairs")
-        else:           # a sub-multiset of the kept pairs
-            uniq, cnt = np.unique(want, return_counts=True)
-            gu, gc = np.unique(got, return_counts=True)
-            pos = np.searchsorted(uniq, gu)
-            assert (pos < uniq.size).all() and np.array_equal(uniq[np.minimum(pos, uniq.size - 1)], gu) and (gc <= cnt[pos]).all(), (tag, "cut")
-        return got_s, got_r, got_ps, got_pr
+        return got
 
 
 @pytest.fixture(scope="module")
@@ -194,7 +141,7 @@ def test_verify_drops_null_and_out_of_range_candidates_unread(ctx):
     # under a base: entries below it wrap to large rows and are out of range too
     v.run(s + np.uint32(500), r, base=777, tag="base 777 over entries from 500")
     # a relation of no rows: everything is dropped, nothing is read (the column pointers may be NULL)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_s, d_r = dev.put(s), dev.put(r)
         ctx.pairs_verify(d_s, d_r, s.size, 0, 0, rows, [(0, dev.put(keys), 8)], 0, 0, 0)
         assert ctx.verify_info()[0::3] == (0, s.size)
@@ -226,24 +173,22 @@ def test_mark_rows(ctx, rows, base):
     bits = rng.random(rows) < 0.4
     words = -(-rows // 32)
     plane = np.full(words + GUARD, 0xFFFFFFFF, dtype=np.uint32)      # the words behind the plane are not rows
-    plane[:words] = mark_words(np.flatnonzero(bits), rows)
+    plane[:words] = plane_words(bits)
     if rows % 32 and base == 0:          # ... nor are those of the last word (base 777: clear bits there are no rows either)
         plane[words - 1] |= np.uint32((0xFFFFFFFF << (rows % 32)) & 0xFFFFFFFF)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_plane = dev.put(plane)
         for which in (0, 1):
             want = (np.flatnonzero(bits == bool(which)) + base).astype(np.uint32)
             for cap in (rows + 5, max(want.size // 2, 1), 0):
-                d_out = dev.put(np.full(cap + GUARD, SENTINEL, dtype=np.uint32)) if cap else 0
-                ctx.mark_rows(d_plane, rows, base, which, d_out, cap)
+                out = GuardedPlane(dev, cap, behind=GUARD) if cap else None
+                ctx.mark_rows(d_plane, rows, base, which, out.ptr if cap else 0, cap)
                 info = ctx.mark_rows_info()
                 print("rows", rows, "base", base, "which", which, "capacity", cap, "info", info)
                 written = min(want.size, cap)
                 assert (info[0], info[1], info[3]) == (want.size, written, rows), (rows, base, which, cap, info)
-                if cap:
-                    out = dev.get(d_out, cap + GUARD)
-                    assert np.array_equal(out[:written], want[:written]), (rows, base, which, cap)     # ascending: the first `capacity` rows
-                    assert (out[written:] == SENTINEL).all(), (rows, base, which, cap)
+                if cap:     # ascending: the first `capacity` rows, and no word behind them
+                    assert np.array_equal(out.read(written, (rows, base, which, cap)), want[:written]), (rows, base, which, cap)
         assert np.array_equal(dev.get(d_plane, plane.size), plane), "the sweep wrote the plane"
 
 
@@ -252,8 +197,8 @@ def test_argument_errors_enqueue_nothing_and_keep_the_infos(ctx, relations):
     s_keys, r_keys = relations
     s, r = candidates(np.random.default_rng(3), "half", 5000)
     Verify(ctx, s_keys, r_keys).run(s, r, tag="the call the infos speak of")
-    with Dev(ctx) as dev:
-        d_plane = dev.put(mark_words(np.arange(0, N, 3), N))
+    with Device(ctx) as dev:
+        d_plane = dev.put(plane_words(row_bits(np.arange(0, N, 3), N)))
         d_rows = dev.put(np.full(N, SENTINEL, dtype=np.uint32))
         ctx.mark_rows(d_plane, N, 0, 1, d_rows, N)
         before = ctx.verify_info(), ctx.mark_rows_info()
@@ -295,7 +240,7 @@ def test_argument_errors_enqueue_nothing_and_keep_the_infos(ctx, relations):
             hj.lib.hj_mark_rows_dev(h, d_plane, N, 0xFFFFFFFF - N + 1, 0, d_rows, N),
             hj.lib.hj_verify_info(h, None), hj.lib.hj_mark_rows_info(h, None)]
         assert bad == [INVALID] * len(bad), bad
-        assert _status(ctx.key_hash, ok * 5, 0, N, d_out) == INVALID and _status(ctx.mark_rows, d_plane, N, 0, 3, d_rows, N) == INVALID
+        assert status(ctx.key_hash, ok * 5, 0, N, d_out) == INVALID and status(ctx.mark_rows, d_plane, N, 0, 3, d_rows, N) == INVALID
         after = ctx.verify_info(), ctx.mark_rows_info()
         assert after == before, (before, after)
         assert after[0][0] > 0 and after[1][0] > 0

@@ -7,57 +7,14 @@ import pytest
 
 import htm_hashjoin_amd as hj
 
+from gpu_harness import dev, plane_bits, row_bits  # noqa: F401
 from keys2_common import MASKS, ROWS, ModelCol, hash_matrix, key_column
-from test_keys_abi import key_words, murmur3_words
+from keys_common import key_words, murmur3_words
 
 pytestmark = pytest.mark.gpu
 
 U64 = np.uint64
 NE = hj.HJ_KEY_NULLS_EQUAL
-
-
-class Device:
-    """a context and what was allocated on it"""
-
-    def __init__(self):
-        self.ctx, self.ptrs = hj.HashJoinContext(0), []
-
-    def alloc(self, nbytes):
-        self.ptrs.append(self.ctx.dev_alloc(max((int(nbytes) + 3) & ~3, 4)))
-        return self.ptrs[-1]
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        d = self.alloc(a.nbytes)
-        if a.nbytes:
-            self.ctx.copy_h2d(d, a)
-        return d
-
-    def get(self, d, n, dtype=np.uint32):
-        out = np.empty(n, dtype=dtype)
-        if n:
-            self.ctx.copy_d2h(out, d)
-        return out
-
-    def column(self, col):
-        """(values, offsets, validity) of a KeyColumn on the device, 0 for what it has none of"""
-        return tuple(self.put(a) if a is not None else 0 for a in col.take(0, col.rows))
-
-    def release(self):
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-        self.ptrs = []
-
-    def close(self):
-        self.release()
-        self.ctx.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    d = Device()
-    yield d
-    d.close()
 
 
 def descriptor(s, r, width, flags):
@@ -88,7 +45,7 @@ def test_device_hash_equals_host_hash(dev, n):
 
 def test_device_hash_of_plain_columns_equals_key_hash(dev):
     """the compatibility property on the device: no offsets, no validity, flags 0 -> what hj_key_hash_dev writes. Both
-    entry points run one kernel, so the property rests on the header's wording, restated in test_keys_abi.py"""
+    entry points run one kernel, so the property rests on the header's wording, restated in keys_common.py"""
     n = 5000
     rng = np.random.default_rng(8)
     a, b = rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(0, 1 << 16, n).astype(np.uint16)
@@ -157,16 +114,6 @@ def verify_case(composite, flags):
     return cols_s, cols_r, base, map_s, map_r, np.array(fate)
 
 
-def plane_of(rows, n):
-    bits = np.zeros(n, dtype=bool)
-    bits[rows] = True
-    return bits
-
-
-def unpack(words, n):
-    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
-
-
 def case_by_the_model(composite, flags):
     """verify_case and what its list must contain, decided by the model alone (needs no device)"""
     cols_s, cols_r, base, map_s, map_r, fate = verify_case(composite, flags)
@@ -174,7 +121,7 @@ def case_by_the_model(composite, flags):
     assert 2048 < n <= 3072, "two full workgroups and a partial one"
     kept = fate == "kept"
     want = np.sort((map_s[kept].astype(U64) << U64(32)) | map_r[kept].astype(U64))
-    want_s, want_r = plane_of(map_s[kept] - base, n_s), plane_of(map_r[kept], n_r)
+    want_s, want_r = row_bits(map_s[kept] - base, n_s), row_bits(map_r[kept], n_r)
     print("candidates", n, "kept", int(kept.sum()), "rejected", int((fate == "rejected").sum()), "dropped", int((fate == "dropped").sum()))
     assert kept.sum() >= 40 and (fate == "rejected").sum() > 100 and (fate == "dropped").sum() >= 100
     # what the list must contain, by the model
@@ -215,7 +162,7 @@ def test_pairs_verify2_against_the_model(dev, composite, flags):
         dev.ctx.pairs_verify2(d_ms, d_mr, n, base, n_s, n_r, desc, d_ks, d_kr, capacity, d_sm, d_rm)
         info = dev.ctx.verify_info()
         got_s, got_r = (dev.get(d, capacity + 8) for d in (d_ks, d_kr)) if outputs else (None, None)
-        return info, got_s, got_r, unpack(dev.get(d_sm, words_s), n_s), unpack(dev.get(d_rm, words_r), n_r)
+        return info, got_s, got_r, plane_bits(dev.get(d_sm, words_s), n_s), plane_bits(dev.get(d_rm, words_r), n_r)
 
     # room for everything
     info, got_s, got_r, marks_s, marks_r = run(n)

@@ -11,6 +11,7 @@ import pytest
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import alloc, ctx  # noqa: F401
 import own_cases as oc
 from htm_chain_device import assert_table_is_the_oracles
 from oracle import oracle
@@ -18,12 +19,6 @@ from oracle import oracle
 pytestmark = pytest.mark.gpu
 
 COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    with hj.HashJoinContext(0) as c:
-        yield c
 
 
 @pytest.fixture(scope="module")
@@ -51,7 +46,7 @@ def device_run(c, case, variant, keys32=None, reserve=True):
     S = oc.probe_side(case.rel)
     n = case.n
     width = 4 if keys32 else 8
-    dR, dS = c.dev_alloc(width * n + 16), c.dev_alloc(width * S.size + 16)
+    dR, dS = alloc(c, width * n + 16), alloc(c, width * S.size + 16)
     try:
         c.copy_h2d(dR, case.rel.astype(np.uint32) if keys32 else case.rel)
         c.copy_h2d(dS, S.astype(np.uint32) if keys32 else S)

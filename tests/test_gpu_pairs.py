@@ -11,20 +11,14 @@ from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-from join_kinds_common import SENTINEL, GUARD, Dev, _status, zipf
+from gpu_harness import Device, ctx, status  # noqa: F401
+from join_kinds_common import SENTINEL, GUARD, zipf, planes
 from r_marks_common import join_expected, walk_expected
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def probe_pairs(ctx, dev, dS, n, capacity, s_idx_base=0):
     """one hj_probe_pairs_dev call -> (found, packed pairs as written (unsorted), guard words intact)"""
-    ds, dr = dev.planes(capacity)
+    ds, dr = (p.ptr for p in planes(dev, capacity))
     ctx.probe_pairs(dS, n, ds, dr, capacity, s_idx_base)
     found, written, _us, zero = ctx.pairs_info()
     assert written == min(found, capacity) and zero == 0
@@ -73,7 +67,7 @@ def test_htm_pairs_are_the_complete_join(ctx, name):
         assert np.bincount(R.astype(np.int64)).max() > 1000
     if name in ("uniform_1000_x_sorted_1500", "random_2p16_x_self_and_sorted"):
         assert not np.isin(S, R).all()
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("htm", R.size, S.size)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, R.size)
@@ -99,7 +93,7 @@ def test_open_addressing_unique_keys(ctx, dist, n, variant):
     pos = np.empty(n + 1, dtype=np.uint64)
     pos[R.astype(np.int64)] = np.arange(n, dtype=np.uint64)
     want = (np.arange(n, dtype=np.uint64) << np.uint64(32)) | pos[S[:n].astype(np.int64)]       # already sorted by S row
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("atomic", n, S.size, buildVariant=variant, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n)
@@ -119,7 +113,7 @@ def test_open_addressing_duplicate_keys(ctx, dist, n, probe_length):
     S = np.concatenate([R[: n // 2 + 1], oracle.generate_data("sorted", n)])
     want = walk_expected(R, S, probe_length)
     for variant in (0, 1, 3, 4):
-        with Dev(ctx) as dev:
+        with Device(ctx) as dev:
             ctx.reserve("atomic", n, S.size, probeLength=probe_length, buildVariant=variant, keepRowIds=True)
             dR, dS = dev.put(R), dev.put(S)
             ctx.build(dR, n)
@@ -141,7 +135,7 @@ def test_bases_and_slices(ctx, algo):
     S = oracle.generate_data("uniform", n, n // 2, 16)[: n - 5]
     base = join_expected(R, S) if algo == "htm" else walk_expected(R, S, 4)
     cuts = [0, 1001, 1001 + 40000, S.size]                   # unequal slices; the second and third start at odd rows
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, S.size, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n, idx_base=1000)
@@ -167,7 +161,7 @@ def test_truncation_never_writes_past_capacity(ctx, algo):
     R = oracle.generate_data("uniform", n, n, 16)
     S = oracle.generate_data("sorted", n)
     want = join_expected(R, S) if algo == "htm" else walk_expected(R, S, 4)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve(algo, n, n, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         ctx.build(dR, n)
@@ -191,21 +185,21 @@ def test_errors_and_noops():
     R = oracle.generate_data("local_shuffle", n, n, 16)
     S = oracle.generate_data("sorted", n)
     want_count = oracle.build_probe_seq(R, S, 4)
-    with hj.HashJoinContext(0) as ctx, Dev(ctx) as dev:
+    with hj.HashJoinContext(0) as ctx, Device(ctx) as dev:
         dR, dS = dev.put(R), dev.put(S)
-        ds, dr = dev.planes(n)
+        ds, dr = (p.ptr for p in planes(dev, n))
         # no build yet
         ctx.reserve("atomic", n, n, keepRowIds=True)
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         # a PRJ context
         ctx.reserve("prj", n, n)
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         ctx.prj_join(dR, n, dS, n)
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         # open addressing without the flag: refused, and the context still counts as before
         ctx.reserve("atomic", n, n)
         ctx.build(dR, n)
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         ctx.probe(dS, n)
         ctx.checksums()
         got = ctx.fetch()
@@ -215,10 +209,10 @@ def test_errors_and_noops():
         # with the flag: argument errors
         ctx.reserve("atomic", n, n, keepRowIds=True)
         ctx.build(dR, n)
-        assert _status(ctx.probe_pairs, dS, n, 0, dr, n) == _lib.HJ_ERR_INVALID
-        assert _status(ctx.probe_pairs, dS, n, ds, 0, n) == _lib.HJ_ERR_INVALID
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n) == _lib.HJ_ERR_INVALID
-        assert _status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - 1 - n) == _lib.HJ_OK
+        assert status(ctx.probe_pairs, dS, n, 0, dr, n) == _lib.HJ_ERR_INVALID
+        assert status(ctx.probe_pairs, dS, n, ds, 0, n) == _lib.HJ_ERR_INVALID
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n) == _lib.HJ_ERR_INVALID
+        assert status(ctx.probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - 1 - n) == _lib.HJ_OK
         s = dev.get(ds, n)
         assert s.min() == (1 << 32) - 1 - n and s.max() == (1 << 32) - 2
         # sSize 0: outputs, counters and the last call's facts stay as they are
@@ -246,7 +240,7 @@ def test_tuples_outside_the_layout_match_nothing(ctx, algo):
         Sx = S[off:]
         want = join_expected(R, Sx)
         assert want.size == n - 4 - off
-        with Dev(ctx) as dev:
+        with Device(ctx) as dev:
             ctx.reserve(algo, n, n, keepRowIds=True)
             dR, dS = dev.put(R), dev.put(S)
             ctx.build(dR, n)
@@ -263,7 +257,7 @@ def test_shard_check_counts_through_the_pairs_probe(ctx):
     def foreign(A):                 # 4 shards on the low key bits, this context is shard 1
         return int(((A & np.uint64(3)) != 1).sum())
 
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         try:
             ctx.set_shard_check(4, 0, 1)
             ctx.reserve("atomic", n, n, keepRowIds=True)

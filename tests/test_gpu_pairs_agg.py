@@ -3,21 +3,15 @@ accumulators are the caller's: every one is prefilled (identity, or a running va
 import numpy as np
 import pytest
 
-import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import Device, ctx, status  # noqa: F401
+from join_kinds_common import planes
 import prj_cases as pc
 from agg_common import COUNT, SUM, MIN, MAX, SIGNED, U64, Col, expected, get64, put64
-from r_marks_common import Dev, _status, inner_expected
+from r_marks_common import inner_expected
 
 pytestmark = pytest.mark.gpu
 NO_ROW = 0xFFFFFFFF
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def vals(dtype, n, seed):
@@ -31,7 +25,7 @@ def run(ctx, map_g, map_v, g_rows, v_rows, cols, g_base=0, v_base=0, tag=None, n
     """one hj_pairs_agg_dev over the two maps (raw entries, bases included) -> checked against numpy over want_pairs
     (default: every pair, bases off)"""
     map_g, n = np.ascontiguousarray(map_g, dtype=np.uint32), len(map_g)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_g = dev.put(map_g)
         d_v = 0 if null_v else dev.put(np.ascontiguousarray(map_v, dtype=np.uint32))
         d_acc = [put64(dev, g_rows, c.identity) for c in cols]
@@ -59,11 +53,11 @@ def test_maps_of_the_radix_join_in_both_directions(ctx):
     n = 1 << 12
     R, S = pc.uniform(n, n // 2, 1), pc.uniform(3 * n, n // 2 + 50, 2)
     inner = inner_expected("prj", R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("prj", n, S.size, keepRowIds=True)
         ctx.prj_build(dev.put(R), n)
         cap = inner.size + 64
-        d_s, d_r = dev.planes(cap)
+        d_s, d_r = (p.ptr for p in planes(dev, cap))
         ctx.prj_probe_pairs(dev.put(S), S.size, d_s, d_r, cap)
         assert ctx.pairs_info()[0] == inner.size
         map_s, map_r = dev.get(d_s, inner.size), dev.get(d_r, inner.size)
@@ -121,7 +115,7 @@ def test_count_only_without_a_value_map(ctx):
 
 def test_argument_errors(ctx):
     INVALID = _lib.HJ_ERR_INVALID
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         d_map, d_src, d_acc = dev.put(np.zeros(64, dtype=np.uint32)), dev.put(np.zeros(64, dtype=np.int64)), put64(dev, 64, U64(0))
         ok = (d_src, 0, d_acc, SUM, 8, SIGNED)
         ctx.pairs_agg(d_map, d_map, 64, 0, 64, 0, 64, [ok])
@@ -131,10 +125,10 @@ def test_argument_errors(ctx):
                     [(d_src, 0, d_acc, SUM, 8, 2)], [(d_src, 0, d_acc, SUM, 8, 0, 1)], [(d_src, 0, 0, SUM, 8, 0)],
                     [(d_src, 0, d_acc + 4, SUM, 8, 0)], [(0, 0, d_acc, SUM, 8, 0)], [(d_src + 4, 0, d_acc, SUM, 8, 0)],
                     [(d_src, d_src + 2, d_acc, SUM, 8, 0)]):
-            assert _status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, bad) == INVALID, bad
-        assert _status(ctx.pairs_agg, 0, d_map, 64, 0, 64, 0, 64, [ok]) == INVALID                 # dMapG NULL
-        assert _status(ctx.pairs_agg, d_map, 0, 64, 0, 64, 0, 64, [ok]) == INVALID                 # dMapV NULL, a column reads values
-        assert _status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, []) == INVALID               # neither a column nor dCount
-        assert _status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, [ok], d_acc + 4) == INVALID
-        assert _status(ctx.pairs_agg, d_map, d_map, 1 << 32, 0, 64, 0, 64, [ok]) == INVALID
-        assert _status(ctx.pairs_agg, d_map, d_map, 64, 0, 1 << 32, 0, 64, [ok]) == INVALID
+            assert status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, bad) == INVALID, bad
+        assert status(ctx.pairs_agg, 0, d_map, 64, 0, 64, 0, 64, [ok]) == INVALID                 # dMapG NULL
+        assert status(ctx.pairs_agg, d_map, 0, 64, 0, 64, 0, 64, [ok]) == INVALID                 # dMapV NULL, a column reads values
+        assert status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, []) == INVALID               # neither a column nor dCount
+        assert status(ctx.pairs_agg, d_map, d_map, 64, 0, 64, 0, 64, [ok], d_acc + 4) == INVALID
+        assert status(ctx.pairs_agg, d_map, d_map, 1 << 32, 0, 64, 0, 64, [ok]) == INVALID
+        assert status(ctx.pairs_agg, d_map, d_map, 64, 0, 1 << 32, 0, 64, [ok]) == INVALID

@@ -14,16 +14,11 @@ except Exception:                        # noqa: BLE001 -- no torch / no GPU: on
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+
+from gpu_harness import alloc, ctx  # noqa: F401
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def check_oa(got, want, algo="atomic"):
@@ -145,7 +140,7 @@ def test_a_context_follows_its_relation_from_step_to_step():
              (("uniform", 16), 2), (("uniform", 16), 3),                     # duplicate-heavy and tight: the window once, then the classic rings
              (("sorted", 16), 3), (("sorted", 16), 4)]
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); dS = c.dev_alloc(n * 8)
+        dR = alloc(c, n * 8); dS = alloc(c, n * 8)
         c.copy_h2d(dS, S)
         c.reserve("atomic", n, n)
         for key, variant in steps:
@@ -184,7 +179,7 @@ def test_algo_auto_switches_between_table_and_radix_join(ctx):
     # split API: hj_reserve("auto") + hj_join_dev on device pointers, R only
     R = oracle.generate_data("shuffle", n)
     with hj.HashJoinContext(0) as c2:
-        dR = c2.dev_alloc(n * 8)
+        dR = alloc(c2, n * 8)
         c2.copy_h2d(dR, R)
         c2.reserve("auto", n, 0)
         c2.join(dR, n, 0, 0)
@@ -202,8 +197,8 @@ def test_unaligned_device_pointers(ctx):
     want = oracle.build_probe_seq(R, S, 4, want_table=True)
     for variant in (1, 2, 3, 4):
         with hj.HashJoinContext(0) as c2:
-            dR = c2.dev_alloc((n + 2) * 8)
-            dS = c2.dev_alloc((n + 2) * 8)
+            dR = alloc(c2, (n + 2) * 8)
+            dS = alloc(c2, (n + 2) * 8)
             c2.copy_h2d(dR + 8, R)
             c2.copy_h2d(dS + 8, S)
             c2.reserve("atomic", n, n, buildVariant=variant)
@@ -337,7 +332,7 @@ def test_htm_heavy_duplicates_odd_sizes_and_split_api(ctx):
         want = oracle.htm_build_probe_seq(R, S, want_buckets=True)
         for variant in (1, 2, 3):
             with hj.HashJoinContext(0) as c:
-                dR = c.dev_alloc(n * 8 + 16); dS = c.dev_alloc(S.size * 8 + 16)
+                dR = alloc(c, n * 8 + 16); dS = alloc(c, S.size * 8 + 16)
                 c.copy_h2d(dR + 8, R); c.copy_h2d(dS + 8, S)
                 c.reserve("htm", n, S.size, buildVariant=variant)
                 c.build(dR + 8, n)
@@ -562,7 +557,7 @@ def test_empty_s_with_a_pointer_and_index_limit(ctx):
     R = oracle.generate_data("shuffle", n)
     want = oracle.prj_join(R, None, 14)
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); dS = c.dev_alloc(64)
+        dR = alloc(c, n * 8); dS = alloc(c, 64)
         c.copy_h2d(dR, R)
         for algo in ("prj", "auto"):
             c.reserve(algo, n, 0, radixBits=14)
@@ -593,7 +588,7 @@ def test_config2_size_properties(ctx):
     assert (got["conflicts"], got["totalMatches"]) == (want["conflicts"], want["totalMatches"])
     # the bare-key entry points (what a radix shard runs after the exchange) on the same input: same table, same counts
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 4 + 16); dS = c.dev_alloc(n * 4 + 16)
+        dR = alloc(c, n * 4 + 16); dS = alloc(c, n * 4 + 16)
         c.copy_h2d(dR + 4, R.astype(np.uint32)); c.copy_h2d(dS + 8, S.astype(np.uint32))
         c.reserve("atomic", n, n)
         c.build_keys(dR + 4, n, 0, 2 * n)
@@ -621,10 +616,10 @@ def test_maximum_relation_size():
     n = 1 << 31
     R = hj.generate_data("local_shuffle", n, n, 1024)
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); c.copy_h2d(dR, R)
+        dR = alloc(c, n * 8); c.copy_h2d(dR, R)
         del R
         S = hj.generate_data("sorted", n)
-        dS = c.dev_alloc(n * 8); c.copy_h2d(dS, S)
+        dS = alloc(c, n * 8); c.copy_h2d(dS, S)
         del S
         c.reserve("atomic", n, n)
         c.build(dR, n); c.probe(dS, n)
@@ -648,7 +643,7 @@ def test_maximum_relation_size_on_the_wavefront_rings():
     R = hj.generate_data("sorted", n)
     tri = n * (n + 1) // 2
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); c.copy_h2d(dR, R)
+        dR = alloc(c, n * 8); c.copy_h2d(dR, R)
         del R
         c.reserve("atomic", n, n)
         c.build(dR, n); c.probe(dR, n)
@@ -698,7 +693,7 @@ def test_sharded_kernels_on_one_gpu(ctx, G, dist, window, variant):
     inbox_r = [[] for _ in range(G)]
     inbox_s = [[] for _ in range(G)]
     with hj.HashJoinContext(0) as c:
-        d_in = c.dev_alloc((n_piece + 1) * 8); d_out = c.dev_alloc((n_piece + 4) * 4); d_cnt = c.dev_alloc(G * 8)
+        d_in = alloc(c, (n_piece + 1) * 8); d_out = alloc(c, (n_piece + 4) * 4); d_cnt = alloc(c, G * 8)
         for src in range(G):
             for rel, inbox in ((R, inbox_r), (S, inbox_s)):
                 piece = rel[src * n_piece:(src + 1) * n_piece]
@@ -728,7 +723,7 @@ def test_sharded_kernels_on_one_gpu(ctx, G, dist, window, variant):
                 r *= 2
             c.reserve("atomic", r, got_s.size, buildVariant=variant)
             # odd offsets: the key buffers of an exchange start wherever the previous peer's keys ended
-            d_r = c.dev_alloc((got_r.size + 8) * 4); d_s = c.dev_alloc((got_s.size + 8) * 4)
+            d_r = alloc(c, (got_r.size + 8) * 4); d_s = alloc(c, (got_s.size + 8) * 4)
             c.copy_h2d(d_r + 4, got_r) if got_r.size else None
             c.copy_h2d(d_s + 12, got_s) if got_s.size else None
             c.build_keys(d_r + 4, got_r.size, shift, table_size)
@@ -753,7 +748,7 @@ def test_shard_split_is_stable_at_size(G, log2n, dist):
     n = (1 << log2n) - 5                                   # ragged: the last tile and the last chunk are partial
     R = hj.generate_data(dist, 1 << log2n, 1 << log2n, 16)[:n]
     with hj.HashJoinContext(0) as c:
-        d_in = c.dev_alloc(n * 8); d_out = c.dev_alloc(n * 4 + 16); d_cnt = c.dev_alloc(G * 8)
+        d_in = alloc(c, n * 8); d_out = alloc(c, n * 4 + 16); d_cnt = alloc(c, G * 8)
         c.copy_h2d(d_in, R)
         c.shard_histogram(d_in, n, G, d_cnt)
         c.shard_scatter(d_in, n, G, d_cnt, d_out)
@@ -783,7 +778,7 @@ def test_range_split_on_one_gpu(dist, window):
     inbox_r = [[] for _ in range(G)]; inbox_s = [[] for _ in range(G)]
     moved = 0
     with hj.HashJoinContext(0) as c:
-        d_in = c.dev_alloc(n_local * 8); d_out = c.dev_alloc(n_local * 4 + 16); d_cnt = c.dev_alloc(G * 8)
+        d_in = alloc(c, n_local * 8); d_out = alloc(c, n_local * 4 + 16); d_cnt = alloc(c, G * 8)
         for src in range(G):
             for rel, inbox in ((R, inbox_r), (S, inbox_s)):
                 piece = rel[src * n_local:(src + 1) * n_local]
@@ -812,7 +807,7 @@ def test_range_split_on_one_gpu(dist, window):
             while r < got_r.size:
                 r *= 2
             c.reserve("atomic", r, got_s.size)
-            d_r = c.dev_alloc(got_r.size * 4 + 16); d_s = c.dev_alloc(got_s.size * 4 + 16)
+            d_r = alloc(c, got_r.size * 4 + 16); d_s = alloc(c, got_s.size * 4 + 16)
             c.copy_h2d(d_r, got_r); c.copy_h2d(d_s, got_s)
             c.build_keys(d_r, got_r.size, 0, 2 * n_local)
             c.probe_keys(d_s, got_s.size)
@@ -918,7 +913,7 @@ def test_randomised_differential_keys_and_tuples():
             c.reserve("atomic", table_size // 2, S.size, buildVariant=variant, probeLength=probe_len)
             offR, offS = int(rng.integers(0, 4)), int(rng.integers(0, 4))
             if key32:
-                dR = c.dev_alloc(n * 4 + 32); dS = c.dev_alloc(S.size * 4 + 32)
+                dR = alloc(c, n * 4 + 32); dS = alloc(c, S.size * 4 + 32)
                 c.copy_h2d(dR + 4 * offR, keys.astype(np.uint32)); c.copy_h2d(dS + 4 * offS, S.astype(np.uint32))
                 c.build_keys(dR + 4 * offR, n, hshift, table_size)
                 c.probe_keys(dS + 4 * offS, S.size)
@@ -927,7 +922,7 @@ def test_randomised_differential_keys_and_tuples():
                     n = table_size // 2
                     keys = np.resize(keys, n); S = S[: max(1, S.size)]
                     want = oracle.build_probe_seq_ts(keys, S, table_size, 0, probe_len, want_table=True)
-                dR = c.dev_alloc(n * 8 + 32); dS = c.dev_alloc(S.size * 8 + 32)
+                dR = alloc(c, n * 8 + 32); dS = alloc(c, S.size * 8 + 32)
                 c.copy_h2d(dR + 8 * (offR & 1), keys); c.copy_h2d(dS + 8 * (offS & 1), S)
                 c.build(dR + 8 * (offR & 1), n)
                 c.probe(dS + 8 * (offS & 1), S.size)
@@ -950,7 +945,7 @@ def test_shard_check_counts_foreign_tuples(variant):
     S = oracle.generate_data("sorted", n)
     dest = lambda k: (((k - np.uint64(1)) >> np.uint64(14)) & np.uint64(G - 1))          # noqa: E731
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); dS = c.dev_alloc(n * 8 + 16); dK = c.dev_alloc(n * 4 + 16)
+        dR = alloc(c, n * 8); dS = alloc(c, n * 8 + 16); dK = alloc(c, n * 4 + 16)
         c.copy_h2d(dR, R); c.copy_h2d(dS + 8, S); c.copy_h2d(dK + 4, S.astype(np.uint32))
         c.reserve("atomic", n, n, buildVariant=variant)
         for shard in (0, 3):
@@ -982,7 +977,7 @@ def test_shard_check_on_bare_keys_through_the_lds_builds(variant, keep, format_)
     foreign = lambda A: int(((A & np.uint64(G - 1)) != shard).sum())                      # noqa: E731
     with hj.HashJoinContext(0) as c:
         c.reserve("atomic", n, S.size, buildVariant=variant, keepRowIds=keep)
-        dR = c.dev_alloc(n * 4 + 16); dS = c.dev_alloc(S.size * 4 + 16)
+        dR = alloc(c, n * 4 + 16); dS = alloc(c, S.size * 4 + 16)
         c.copy_h2d(dR + 4, R.astype(np.uint32)); c.copy_h2d(dS + 12, S.astype(np.uint32))
         c.set_shard_check(G, 0, shard)
         c.build_keys(dR + 4, n, 0, 2 * n)
@@ -1012,7 +1007,7 @@ def test_shard_split_flags_payload_bits(ctx):
     R = oracle.generate_data("sorted", n)
     R[1234] |= np.uint64(1) << np.uint64(40)
     with hj.HashJoinContext(0) as c:
-        d_in = c.dev_alloc(n * 8); d_out = c.dev_alloc(n * 4); d_cnt = c.dev_alloc(G * 8)
+        d_in = alloc(c, n * 8); d_out = alloc(c, n * 4); d_cnt = alloc(c, G * 8)
         c.copy_h2d(d_in, R)
         c.shard_histogram(d_in, n, G, d_cnt)
         c.shard_scatter(d_in, n, G, d_cnt, d_out)
@@ -1052,7 +1047,7 @@ def test_streaming_zipf_equals_the_host_generator():
         want = (hj.generate_data("zipf", total, alphabet, 16, zipf_theta=theta) if seed == 0 else
                 hj.generate_relation("zipf", total, alphabet, 0, theta, seed))
         with hj.HashJoinContext(0) as c:
-            d = c.dev_alloc(total * 8)
+            d = alloc(c, total * 8)
             c.zipf_open(alphabet, theta, seed)
             off = 0
             for m in slices:

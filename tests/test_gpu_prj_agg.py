@@ -6,20 +6,15 @@ import pytest
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import Device, ctx, status  # noqa: F401
+from join_kinds_common import planes
 import prj_cases as pc
 from agg_common import COUNT, SUM, MIN, MAX, SIGNED, U64, Col, PrjAgg, expected_join, get64, put64
-from r_marks_common import Dev, Marks, _status, inner_expected
+from r_marks_common import Marks, inner_expected
 
 pytestmark = pytest.mark.gpu
 
 I32_MIN, I64_MAX, U64_MAX = -(1 << 31), (1 << 63) - 1, (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def resident(ctx, dev, R, s_max, bits=0, track=False):
@@ -51,7 +46,7 @@ def slices_of(S, lens):
 
 def run_case(ctx, R, S, lens, cols, bits=0, tag=None, between=False):
     """build R, one aggregation of `cols`, S in slices of `lens`; the rows against numpy at the end (between: after every slice)"""
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         resident(ctx, dev, R, max(lens), bits)
         agg = PrjAgg(ctx, dev, R.size, cols)
         for lo, part in slices_of(S, lens):
@@ -125,7 +120,7 @@ def test_a_split_s_partition(ctx, bits):
     S = pc.shuffled([hot[rng.integers(0, hot.size, 2 * item + 1)], cold[rng.integers(0, cold.size, 1 << 11)],
                      pc.uniform(1 << 11, 1 << 20, 53)], 54, bits)
     cols = [Col(SUM, values_of(np.int64, S.size, 7)), Col(MIN, values_of(np.int32, S.size, 8)), Col(MAX, values_of(np.uint64, S.size, 9))]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         resident(ctx, dev, R, S.size, bits)
         agg = PrjAgg(ctx, dev, R.size, cols)
         agg.probe(S)
@@ -143,7 +138,7 @@ def test_zipf(ctx):
     inner = inner_expected("prj", R, S)
     want = expected_join(n, inner, cols)
     assert int(want[0].max()) > 3000                 # the hottest row: thousands of adds to one LDS entry
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         resident(ctx, dev, R, S.size)
         agg = PrjAgg(ctx, dev, n, cols)
         agg.probe(S)
@@ -186,7 +181,7 @@ def test_rows_never_probed_and_s_partitions_without_r(ctx):
     cols = [Col(COUNT), Col(SUM, v), Col(MIN, v), Col(MAX, v)]
     inner = inner_expected("prj", R, S)
     assert 0 < inner.size < 64
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         resident(ctx, dev, R, n, bits=11)
         agg = PrjAgg(ctx, dev, R.size, cols)
         count, planes = agg.rows("no probe")                                 # every row written once, at its identity
@@ -205,32 +200,32 @@ def test_state_and_arguments(ctx):
     S = pc.uniform(n, n, 81)
     v = values_of(np.int64, n, 17)
     INVALID, STATE = _lib.HJ_ERR_INVALID, _lib.HJ_ERR_STATE
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         dR, dS, dV = dev.put(R), dev.put(S), dev.put(v)
         d_out, sum64 = put64(dev, n), [(SUM, 8, SIGNED)]
         c.reserve("prj", n, n)                                               # no row ids
-        assert _status(c.prj_agg_begin, sum64) == STATE                      # no resident R
+        assert status(c.prj_agg_begin, sum64) == STATE                      # no resident R
         c.prj_build(dR, n)
-        assert _status(c.prj_agg_begin, sum64) == STATE                      # an R without row ids
+        assert status(c.prj_agg_begin, sum64) == STATE                      # an R without row ids
         c.reserve("prj", n, n, keepRowIds=True, trackRMatches=True)
         c.prj_build(dR, n)
-        assert _status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE           # before begin
-        assert _status(c.prj_agg_rows, [d_out]) == STATE
+        assert status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE           # before begin
+        assert status(c.prj_agg_rows, [d_out]) == STATE
         for bad in ([], [(COUNT, 0, 0)] * 5, [(4, 8, 0)], [(SUM, 2, 0)], [(SUM, 0, 0)], [(COUNT, 8, 0)], [(SUM, 8, 2)], [(SUM, 8, 0, 1)]):
-            assert _status(c.prj_agg_begin, bad) == INVALID, bad
-        assert _status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE           # a refused begin begins nothing
+            assert status(c.prj_agg_begin, bad) == INVALID, bad
+        assert status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE           # a refused begin begins nothing
         c.prj_agg_begin(sum64)
-        assert _status(c.prj_probe_agg, dS, n, [(dV, 0), (dV, 0)]) == INVALID        # nCols mismatch
-        assert _status(c.prj_probe_agg, dS, n, []) == INVALID
-        assert _status(c.prj_probe_agg, dS, n, [(0, 0)]) == INVALID          # NULL src for SUM
-        assert _status(c.prj_probe_agg, dS, n, [(dV + 4, 0)]) == INVALID     # misaligned src
-        assert _status(c.prj_probe_agg, dS, n, [(dV, dV + 2)]) == INVALID    # misaligned srcValid
-        assert _status(c.prj_agg_rows, []) == INVALID                        # NULL dOut
-        assert _status(c.prj_agg_rows, [0]) == INVALID
-        assert _status(c.prj_probe_agg, dS, n + 1, [(dV, 0)]) == STATE       # above the reserved slice
+        assert status(c.prj_probe_agg, dS, n, [(dV, 0), (dV, 0)]) == INVALID        # nCols mismatch
+        assert status(c.prj_probe_agg, dS, n, []) == INVALID
+        assert status(c.prj_probe_agg, dS, n, [(0, 0)]) == INVALID          # NULL src for SUM
+        assert status(c.prj_probe_agg, dS, n, [(dV + 4, 0)]) == INVALID     # misaligned src
+        assert status(c.prj_probe_agg, dS, n, [(dV, dV + 2)]) == INVALID    # misaligned srcValid
+        assert status(c.prj_agg_rows, []) == INVALID                        # NULL dOut
+        assert status(c.prj_agg_rows, [0]) == INVALID
+        assert status(c.prj_probe_agg, dS, n + 1, [(dV, 0)]) == STATE       # above the reserved slice
         # pairs_info and the marks before ...
         cap = 2 * n
-        d_s, d_r = dev.planes(cap)
+        d_s, d_r = (p.ptr for p in planes(dev, cap))
         c.prj_probe_pairs(dS, n // 2, d_s, d_r, cap)
         pairs_before, marks = c.pairs_info(), Marks(c, dev, n)
         marks.add(inner_expected("prj", R, S[:n // 2]))
@@ -256,11 +251,11 @@ def test_state_and_arguments(ctx):
         assert (get64(c, d_out, n) == 0).all()
         # every call that starts a new operation ends the aggregation
         c.prj_build(dR, n)
-        assert _status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE and _status(c.prj_agg_rows, [d_out]) == STATE
+        assert status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE and status(c.prj_agg_rows, [d_out]) == STATE
         c.prj_agg_begin(sum64)
         c.prj_join(dR, n, dS, n)
-        assert _status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE and _status(c.prj_agg_rows, [d_out]) == STATE
-        assert _status(c.prj_agg_begin, sum64) == STATE
+        assert status(c.prj_probe_agg, dS, n, [(dV, 0)]) == STATE and status(c.prj_agg_rows, [d_out]) == STATE
+        assert status(c.prj_agg_begin, sum64) == STATE
         assert c.prj_agg_info()["nCols"] == 0
 
 

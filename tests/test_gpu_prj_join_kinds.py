@@ -8,7 +8,8 @@ import pytest
 
 import htm_hashjoin_amd as hj
 import prj_cases as pc
-from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, KINDS, NAMES, Dev, Calls, derive, matched_rows
+from gpu_harness import Device, alloc
+from join_kinds_common import SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, KINDS, NAMES, Calls, derive, matched_rows, planes
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,7 @@ def all_kinds(R, S, bits, kinds=KINDS, tag=None, inner=None):
     """build R, then every kind over S on one context; -> {kind: work items of its probe}"""
     inner = Expected(R).pairs(S) if inner is None else inner
     items = {}
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         c.reserve("prj", R.size, S.size, radixBits=bits, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         c.prj_build(dR, R.size)
@@ -185,7 +186,7 @@ def test_random_relations_in_ragged_slices(block):
             R, S, lens, bits, shape = pc.random_relations(block, index)
             kind = 1 + index % 3
             exp = Expected(R)
-            with Dev(c) as dev:
+            with Device(c) as dev:
                 c.reserve("prj", R.size, max(lens), radixBits=bits, prjMode=index % 3, keepRowIds=True)
                 dR, dS = dev.put(R), dev.alloc(8 * max(lens))
                 c.prj_build(dR, R.size)
@@ -221,11 +222,11 @@ def test_other_probes_on_the_same_context():
     S = pc.uniform(n, 1 << 14, 1051)
     cuts = [0, 5000, 5001, n]
     exp = Expected(R)
-    with hj.HashJoinContext(0) as c, hj.HashJoinContext(0) as plain, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, hj.HashJoinContext(0) as plain, Device(c) as dev:
         c.reserve("prj", n, n, radixBits=14, keepRowIds=True)
         plain.reserve("prj", n, n, radixBits=14)
         dR, dS = dev.put(R), dev.put(S)
-        pR, pS = plain.dev_alloc(8 * n), plain.dev_alloc(8 * n)
+        pR, pS = alloc(plain, 8 * n), alloc(plain, 8 * n)
         try:
             plain.copy_h2d(pR, R); plain.copy_h2d(pS, S)
             c.prj_build(dR, n); plain.prj_build(pR, n)
@@ -243,7 +244,7 @@ def test_other_probes_on_the_same_context():
                 assert c.pairs_info()[:2] == info[:2] and c.pairs_info()[3] == info[3]
                 items_count = c.prj_resident_info()["items"]
                 # the pairs probe through its old entry point
-                ds, dr = dev.planes(inner.size + 64)
+                ds, dr = (p.ptr for p in planes(dev, inner.size + 64))
                 assert hj.lib.hj_prj_probe_pairs_dev(c._h, dS + 8 * a, b - a, a, ds, dr, inner.size + 64) == 0
                 plain.prj_probe(pS + 8 * a, b - a)
                 calls.matches += inner.size; calls.s += b - a

@@ -7,12 +7,13 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, alloc, status
 import prj_cases as pc
 from htm_hashjoin_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-from join_kinds_common import SENTINEL, GUARD, U64, Dev, _status
+from join_kinds_common import SENTINEL, GUARD, U64, planes
 from r_marks_common import LOW
 COUNTERS = ("totalMatches", "sSize", "prjChecksum", "radixBits", "prjPartitions")
 COUNT_ONLY_ABOVE = 1 << 25       # a slice with more reference pairs may be checked by count only (raised HJ_FUZZ_CASES)
@@ -20,7 +21,7 @@ COUNT_ONLY_ABOVE = 1 << 25       # a slice with more reference pairs may be chec
 
 def probe_pairs(ctx, dev, dS, n, capacity, s_idx_base=0):
     """one hj_prj_probe_pairs_dev call -> (found, packed pairs as written (unsorted), guard words intact)"""
-    ds, dr = dev.planes(capacity)
+    ds, dr = (p.ptr for p in planes(dev, capacity))
     ctx.prj_probe_pairs(dS, n, ds, dr, capacity, s_idx_base)
     found, written, _us, zero = ctx.pairs_info()
     assert written == min(found, capacity) and zero == 0
@@ -74,11 +75,11 @@ def test_case_table_pairs_are_exact_at_every_probe(case):
     steps = case.steps()
     n_r, n_s = pc.reserve_sizes(steps)
     kw = dict(radixBits=case.bits, prjMode=case.mode)
-    with hj.HashJoinContext(0) as c, hj.HashJoinContext(0) as plain, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, hj.HashJoinContext(0) as plain, Device(c) as dev:
         c.reserve("prj", n_r, n_s, keepRowIds=True, **kw)
         plain.reserve("prj", n_r, n_s, **kw)
         dR, dS = dev.alloc(n_r * 8), dev.alloc(n_s * 8)
-        pR, pS = plain.dev_alloc(n_r * 8), plain.dev_alloc(n_s * 8)
+        pR, pS = alloc(plain, n_r * 8), alloc(plain, n_s * 8)
         try:
             R = exp = r_counts = None
             total = 0
@@ -139,7 +140,7 @@ def test_random_relations_in_ragged_slices(block):
             R, S, lens, bits, shape = pc.random_relations(block, index)
             mode = index % 3
             exp = Expected(R)
-            with Dev(c) as dev:
+            with Device(c) as dev:
                 c.reserve("prj", R.size, max(lens), radixBits=bits, prjMode=mode, keepRowIds=True)
                 dR, dS = dev.put(R), dev.alloc(8 * max(lens))
                 c.prj_build(dR, R.size)
@@ -181,7 +182,7 @@ def test_capacity_cuts_the_output_and_nothing_else():
     S = pc.uniform(n // 2 + 7, n // 2 + n // 8, 901)
     exp = Expected(R)
     want = exp.pairs(S)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         c.reserve("prj", R.size, S.size, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         c.prj_build(dR, R.size)
@@ -210,7 +211,7 @@ def test_one_key_a_hundred_thousand_times(bits):
     S = pc.shuffled([pc.uniform(1 << 16, dense, 911, bits), np.full(20, hot, dtype=U64)], 912, bits)
     want = Expected(R).pairs(S)
     assert want.size == 20 * 100000 + (1 << 16)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         c.reserve("prj", R.size, S.size, radixBits=bits, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         c.prj_build(dR, R.size)
@@ -235,7 +236,7 @@ def test_upper_tuple_bits_are_ignored_and_key_zero_is_a_key():
     zero_pairs = int((R == 0).sum()) * int((S == 0).sum())
     assert zero_pairs > 0
     for r_in, s_in in ((R, S), (R, Sup), (Rup, Sup)):
-        with hj.HashJoinContext(0) as c, Dev(c) as dev:
+        with hj.HashJoinContext(0) as c, Device(c) as dev:
             c.reserve("prj", n, S.size, keepRowIds=True)
             dR, dS = dev.put(r_in), dev.put(s_in)
             c.prj_build(dR, n)
@@ -255,32 +256,32 @@ def test_errors_and_noops():
     S = pc.uniform(n, n + n // 4, 930)
     exp = Expected(R)
     want = exp.pairs(S)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         dR, dS = dev.put(R), dev.put(S)
-        ds, dr = dev.planes(n)
+        ds, dr = (p.ptr for p in planes(dev, n))
         # no resident R
         c.reserve("prj", n, n, keepRowIds=True)
-        assert _status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         c.prj_join(dR, n, dS, n)                                     # the one-shot join leaves nothing resident
-        assert _status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         # a resident R built without the flag; the table probe's entry point keeps refusing a PRJ context
         c.reserve("prj", n, n)
         c.prj_build(dR, n)
-        assert _status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
-        assert _status(c.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(c.prj_probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(c.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
         c.prj_probe(dS, n)
         assert c.fetch()["totalMatches"] == want.size
         assert (dev.get(ds, n) == SENTINEL).all()
         # with the flag
         c.reserve("prj", n, n, keepRowIds=True)
         c.prj_build(dR, n)
-        assert _status(c.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
-        assert _status(c.prj_probe_pairs, dS, n + 1, ds, dr, n) == _lib.HJ_ERR_STATE         # above the reserved slice
-        assert _status(c.prj_probe_pairs, dS, n, 0, dr, n) == _lib.HJ_ERR_INVALID
-        assert _status(c.prj_probe_pairs, dS, n, ds, 0, n) == _lib.HJ_ERR_INVALID
-        assert _status(c.prj_probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n) == _lib.HJ_ERR_INVALID
+        assert status(c.probe_pairs, dS, n, ds, dr, n) == _lib.HJ_ERR_STATE
+        assert status(c.prj_probe_pairs, dS, n + 1, ds, dr, n) == _lib.HJ_ERR_STATE         # above the reserved slice
+        assert status(c.prj_probe_pairs, dS, n, 0, dr, n) == _lib.HJ_ERR_INVALID
+        assert status(c.prj_probe_pairs, dS, n, ds, 0, n) == _lib.HJ_ERR_INVALID
+        assert status(c.prj_probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - n) == _lib.HJ_ERR_INVALID
         assert c.fetch()["totalMatches"] == 0                         # nothing of the refused calls was counted
-        assert _status(c.prj_probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - 1 - n) == _lib.HJ_OK
+        assert status(c.prj_probe_pairs, dS, n, ds, dr, n, s_idx_base=(1 << 32) - 1 - n) == _lib.HJ_OK
         found, written = c.pairs_info()[:2]
         assert found == written == want.size
         s = dev.get(ds, n)[:written]
@@ -313,7 +314,7 @@ def test_rebuilds_leave_the_pairs_correct(algo):
     R1 = pc.unique_shuffled(n)
     R2 = pc.uniform(n - 1001, n // 3, 940)                  # another size, duplicate keys
     S = pc.uniform(n // 2, n, 941)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         c.reserve(algo, n, S.size, keepRowIds=True)
         d1, d2, dS = dev.put(R1), dev.put(R2), dev.put(S)
         for R, dR in ((R1, d1), (R1, d1), (R2, d2), (R1, d1)):
@@ -332,11 +333,11 @@ def test_foreign_key_join_of_2p26_tuples():
     n = 1 << 26
     R = pc.unique_shuffled(n)
     S = R[np.random.default_rng(950).integers(0, n, size=n)]          # foreign keys into R
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         c.reserve("prj", n, n, keepRowIds=True)
         dR, dS = dev.put(R), dev.put(S)
         c.prj_build(dR, n)
-        ds, dr = dev.planes(n)
+        ds, dr = (p.ptr for p in planes(dev, n))
         c.prj_probe_pairs(dS, n, ds, dr, n)
         found, written = c.pairs_info()[:2]
         s_idx, r_idx = dev.get(ds, n + GUARD), dev.get(dr, n + GUARD)

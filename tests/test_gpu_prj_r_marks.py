@@ -8,23 +8,17 @@ import pytest
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import Device, ctx, status  # noqa: F401
 import prj_cases as pc
 
-from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, SCAN_TILE, Dev,
-                            Calls, _status, Marks, inner_expected, r_rows_of)
+from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, SCAN_TILE, Calls,
+                            Marks, inner_expected, r_rows_of)
 
 pytestmark = pytest.mark.gpu
 
 PAIR_BLOCK_TUPLES = 11520        # kPairBlockTuples: R tuples of one LDS build of the pairs join
 STAGE = 4096                     # kStagePairs: rows per stage
 ROUND = 2 * 1024                 # kPairElems * kJoinThreads: S elements of one round of a workgroup
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def expected(R, S, s_base=0):
@@ -42,7 +36,7 @@ def tracked(ctx, dev, R, s_max, bits=0):
 @pytest.mark.parametrize("n", [1, 31, 32, 33, 1000])
 def test_last_word_of_the_plane(ctx, n):
     R = np.arange(1, n + 1, dtype=U64)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, 2 * n)
         marks.check((n, "no probe"))
         for S in (np.concatenate([R[::2], R[:1] + U64(5000)]), R):
@@ -59,7 +53,7 @@ def test_marks_accumulate_over_inner_and_left_slices_only(ctx):
     keys = np.arange(1, 2 * n + 1, dtype=U64)
     slices = [keys[0:900], keys[1000:1700], keys[2500:3001]]             # INNER, LEFT, INNER
     other = np.concatenate([keys[3200:3900], keys[n + 5: n + 50]])       # SEMI, ANTI, counting: rows no slice above names
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, 1024)
         d_other, inner_other = dev.put(other), expected(R, other)
         assert inner_other.size > 0
@@ -93,7 +87,7 @@ def test_rows_cut_by_the_capacity_mark_too(ctx):
     S = pc.uniform(n - 7, n // 2, 6)
     inner = expected(R, S)
     assert inner.size > S.size
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         dS = dev.put(S)
         marks.add(inner)
@@ -114,7 +108,7 @@ def test_an_r_partition_of_several_lds_builds(ctx):
     S = np.concatenate([np.arange(1, 2049, dtype=U64)[::2], np.array([hot, 999999], dtype=U64)])
     inner = expected(R, S)
     assert inner.size == 1024 + 30000
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         calls.call(INNER, dev.put(S), S.size, inner, tag="blocks")
         marks.add(inner)
@@ -133,7 +127,7 @@ def test_the_direct_write_round_marks(ctx, full_capacity):
     assert inner.size >= 40 * (1 << 12) and 40 * ROUND > STAGE
     rows = r_rows_of(inner)
     assert 32 * 40 <= rows.size < R.size                                 # 32 of the 64 keys are drawn, and key 8 and 16
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         dS = dev.put(S)
         if full_capacity:
@@ -150,7 +144,7 @@ def test_partitions_with_s_and_no_r_under_left(ctx):
     S = pc.uniform(n, n, 1000, 11)
     inner = expected(R, S)
     assert 0 < inner.size < 64
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size, bits=11)
         calls.call(LEFT, dev.put(S), S.size, inner, tag="r-less")
         marks.add(inner)
@@ -163,7 +157,7 @@ def test_zipf_probe_marks_exactly(ctx):
     S = hj.generate_relation("zipf", 1 << 16, n, 0, 1.0, 54321)
     inner = expected(R, S)
     assert np.bincount((inner & U64(0xFFFFFFFF)).astype(np.int64)).max() > 3000 and r_rows_of(inner).size < n
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         calls.call(INNER, dev.put(S), S.size, inner, tag="zipf")
         marks.add(inner)
@@ -174,7 +168,7 @@ def test_nothing_everything_and_clearing(ctx):
     n = 1 << 12
     R = pc.unique_shuffled(n, 5)
     absent = np.arange(3 * n, 4 * n - 3, dtype=U64)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, n)
         marks.check("no probe at all")
         calls.call(LEFT, dev.put(absent), absent.size, expected(R, absent), tag="nothing")
@@ -203,16 +197,16 @@ def test_sweep_of_several_blocks(ctx):
     R = rng.permutation(np.arange(1, n + 1, dtype=U64))
     S = np.arange(1, n + 1, dtype=U64)[rng.random(n) < 0.25]
     inner = expected(R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         calls.count_only(INNER, dev.put(S), S.size, inner.size, S.size)
         marks.add(inner)
         marks.check("100003")
         want = marks.expected(UNMATCHED)
         capacity = int((want < 3 * SWEEP_ROWS).sum()) + 5                # cut inside the fourth workgroup's run
-        produced, written, plane = marks.sweep(UNMATCHED, capacity)
+        produced, written, got = marks.sweep(UNMATCHED, capacity)          # no word behind the rows written: Marks.sweep
         assert (produced, written) == (want.size, capacity) and produced > written
-        assert np.array_equal(plane[:capacity].astype(U64), want[:capacity]) and (plane[capacity:] == SENTINEL).all()
+        assert np.array_equal(got.astype(U64), want[:capacity])
 
 
 def test_sweep_whose_block_counts_take_the_second_level_of_the_scan(ctx):
@@ -227,42 +221,42 @@ def test_sweep_whose_block_counts_take_the_second_level_of_the_scan(ctx):
     rows = np.unique(np.concatenate([np.arange(0, n, 7919, dtype=U64), np.array([SWEEP_ROWS - 1, n - SWEEP_ROWS - 1, n - 2, n - 1], dtype=U64)]))
     S = rows + U64(1)
     inner = (np.arange(S.size, dtype=U64) << U64(32)) | rows             # S is sorted and unique: S row i names R row rows[i]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, R, S.size)
         calls.call(INNER, dev.put(S), S.size, inner, tag="second level")
         marks.seen = rows
-        produced, written, plane = marks.sweep(MATCHED, rows.size + 64)
+        produced, written, got = marks.sweep(MATCHED, rows.size + 64)
         assert (produced, written) == (rows.size, rows.size)
-        assert np.array_equal(plane[:written].astype(U64), rows) and (plane[written:] == SENTINEL).all()
+        assert np.array_equal(got.astype(U64), rows)
         assert marks.sweep(UNMATCHED, 0, null_plane=True)[:2] == (n - rows.size, 0)
-        produced, written, plane = marks.sweep(UNMATCHED, n)
-        assert (produced, written) == (n - rows.size, n - rows.size) and (plane[written:] == SENTINEL).all()
-        assert np.array_equal(plane[:written], np.delete(np.arange(n, dtype=np.uint32), rows.astype(np.int64)))
+        produced, written, got = marks.sweep(UNMATCHED, n)
+        assert (produced, written) == (n - rows.size, n - rows.size)
+        assert np.array_equal(got, np.delete(np.arange(n, dtype=np.uint32), rows.astype(np.int64)))
 
 
 def test_errors():
     n = 1 << 10
     R = np.arange(1, n + 1, dtype=U64)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         dR = dev.put(R)
         d_rows = dev.put(np.full(n + GUARD, SENTINEL, dtype=np.uint32))
         for algo in ("prj", "auto"):                                    # the flag without the row ids: refused at hj_reserve
-            assert _status(c.reserve, algo, n, n, trackRMatches=True) == _lib.HJ_ERR_INVALID
+            assert status(c.reserve, algo, n, n, trackRMatches=True) == _lib.HJ_ERR_INVALID
         c.reserve("prj", n, n, keepRowIds=True)                         # reserved without the flag
         c.prj_build(dR, n)
-        assert _status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
-        assert _status(c.r_marks_clear) == _lib.HJ_ERR_STATE
+        assert status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
+        assert status(c.r_marks_clear) == _lib.HJ_ERR_STATE
         c.reserve("prj", n, n, keepRowIds=True, trackRMatches=True)
-        assert _status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE      # that R was built without marks
+        assert status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE      # that R was built without marks
         c.prj_build(dR, n)
-        assert _status(c.r_rows, 2, d_rows, n) == _lib.HJ_ERR_INVALID
-        assert _status(c.r_rows, MATCHED, 0, 1) == _lib.HJ_ERR_INVALID
+        assert status(c.r_rows, 2, d_rows, n) == _lib.HJ_ERR_INVALID
+        assert status(c.r_rows, MATCHED, 0, 1) == _lib.HJ_ERR_INVALID
         c.r_rows(MATCHED, d_rows, n)
         assert c.r_rows_info()[:2] == (0, 0) and c.r_rows_info()[3] == n
         assert (dev.get(d_rows, n + GUARD) == SENTINEL).all()
         dS = dev.put(R)
         c.prj_join(dR, n, dS, n)                                        # the one-shot join: the last build is no longer hj_prj_build_dev
-        assert _status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
+        assert status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
 
 
 def test_radix_outer_join_pairs_end_to_end():

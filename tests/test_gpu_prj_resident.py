@@ -10,15 +10,11 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from oracle import oracle
 
+from gpu_harness import alloc, ctx_per_test  # noqa: F401  (every test of this file starts on a context of its own)
+
 pytestmark = pytest.mark.gpu
 
 ITEM_S = 1 << 16          # kPrjItemS: S tuples per join work item at most
-
-
-@pytest.fixture
-def ctx():
-    with hj.HashJoinContext(0) as c:
-        yield c
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +25,7 @@ def zipf_s():
 
 def upload(c, a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
-    d = c.dev_alloc(max(a.size, 1) * 8)
+    d = alloc(c, max(a.size, 1) * 8)
     c.copy_h2d(d, a)
     return d
 
@@ -49,7 +45,7 @@ def build_and_probe(c, dR, nR, S, slices, **kw):
     c.reserve("prj", nR, max(lens), **kw)
     c.prj_build(dR, nR)
     after_build = c.fetch()
-    dS = c.dev_alloc(max(lens) * 8)
+    dS = alloc(c, max(lens) * 8)
     off = 0
     for m in lens:
         c.copy_h2d(dS, S[off:off + m])
@@ -143,7 +139,7 @@ def test_r_stays_resident_after_dr_is_overwritten_and_freed(ctx):
     ctx.copy_h2d(dR, np.full(n, 77, dtype=np.uint64))
     ctx.synchronize()
     ctx.dev_free(dR)
-    dS = ctx.dev_alloc(n * 8)
+    dS = alloc(ctx, n * 8)
     for k in range(2):
         ctx.copy_h2d(dS, S[k * n:(k + 1) * n])
         ctx.prj_probe(dS, n)
@@ -198,7 +194,7 @@ def test_histogram_free_r_survives_a_falling_back_s(ctx, zipf_s):
     ctx.reserve("prj", n, zipf_s.size, radixBits=14, prjMode=2)
     ctx.prj_build(dR, n)
     assert ctx.fetch()["prjPath"] == 1
-    dS = ctx.dev_alloc(zipf_s.size * 8)
+    dS = alloc(ctx, zipf_s.size * 8)
     ctx.copy_h2d(dS, zipf_s)
     ctx.prj_probe(dS, zipf_s.size)                              # Zipf: S's histogram-free passes fall back
     info = ctx.prj_resident_info()
@@ -222,9 +218,9 @@ def test_config5_full_size_resident_prj():
     n, slices, per = 1 << 28, 16, 1 << 28
     R = hj.generate_data("local_shuffle", n, n, 1024)
     with hj.HashJoinContext(0) as c:
-        dR = c.dev_alloc(n * 8); c.copy_h2d(dR, R)
+        dR = alloc(c, n * 8); c.copy_h2d(dR, R)
         del R
-        dS = c.dev_alloc(per * 8)
+        dS = alloc(c, per * 8)
         c.reserve("prj", n, per)
         c.prj_build(dR, n)
         c.synchronize()

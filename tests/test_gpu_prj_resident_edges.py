@@ -21,6 +21,8 @@ import htm_hashjoin_amd as hj
 import prj_cases as pc
 from oracle import oracle
 
+from gpu_harness import alloc
+
 pytestmark = pytest.mark.gpu
 
 
@@ -31,7 +33,7 @@ def run_case(c, case):
     bits = pc.resolved_bits(n_r, case.bits)
     kw = dict(radixBits=case.bits, prjMode=case.mode)
     c.reserve("prj", n_r, n_s, **kw)
-    dR, dS = c.dev_alloc(n_r * 8), c.dev_alloc(n_s * 8)
+    dR, dS = alloc(c, n_r * 8), alloc(c, n_s * 8)
     R = r_counts = checksum = r_path = None
     total = s_sum = b = 0                                       # b: step of the current build
     slices = []

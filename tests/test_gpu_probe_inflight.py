@@ -7,9 +7,8 @@ up over its probes, so each probe is judged by what it added. Run with -m gpu on
 import numpy as np
 import pytest
 
-import htm_hashjoin_amd as hj
+from gpu_harness import Device, ctx  # noqa: F401
 import valid_range_cases as vc
-from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -28,13 +27,6 @@ TABLES = {
     "window": dict(variant=2, keep=False, dist="uniform", fmt=0),
     "atomics": dict(variant=1, keep=False, dist="uniform", fmt=0),
 }
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")
@@ -111,7 +103,7 @@ def test_vector_edges(ctx, relations, table):
     R = relations["uniform"]
     keys, counts = np.unique(R, return_counts=True)
     dup = keys[counts > 1][:1]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         build(ctx, dev, table, R)
         total = 0
         for size in (0, 1, 2, 3, 4, 5, 7, 8, 9):
@@ -134,7 +126,7 @@ def test_grid_stride_with_shard_check(ctx, relations, table):
     windows do."""
     R = relations["uniform"]
     size = 5 * SWEEP // 2 + 3
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.set_shard_check(4)
         try:
             dbg = build(ctx, dev, table, R)
@@ -177,7 +169,7 @@ def test_tuples_that_can_match_nothing(ctx, table):
     band = vc.band_relation(N, T, T // 4, shuffle=16)
     assert vc.classify(band) == "interior"
     P = vc.poison_for(band, "sorted" if t["fmt"] else "perm", htm=False)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("atomic", N, 0, buildVariant=4 if t["fmt"] else 1)
         ctx.build_keys(dev.put(P.astype(np.uint32)), P.size, 0, T)
         dbg = ctx.table_debug()
@@ -216,7 +208,7 @@ def test_windows_at_the_table_end(ctx, relations, table):
                         np.arange(T - 5, T, dtype=U64) | U64(1 << 32)])
     want = want_matches(R, S)
     assert want >= 8
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("atomic", N, N, buildVariant=t["variant"], keepRowIds=t["keep"])
         ctx.build(dev.put(R), N)
         dbg = ctx.table_debug()
@@ -234,7 +226,7 @@ def test_windows_at_the_table_end(ctx, relations, table):
 def test_every_table_the_tuple_path_reads(ctx, relations, table):
     """sorted S (the benchmark's), a mixed S of a few vectors more than one workgroup takes, on each format and build"""
     R = relations[TABLES[table]["dist"]]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dbg = build(ctx, dev, table, R)
         sides = {"sorted": oracle.relS_for("uniform", R)}
         if dbg["validHiEx"] < dbg["tableSlots"]:
@@ -251,7 +243,7 @@ def test_every_table_the_tuple_path_reads(ctx, relations, table):
 def test_other_probe_lengths(ctx, relations, table, probe):
     """probeLength 1, 2 and 8 walk slot by slot inside the same loop, on one table of each format"""
     R = relations["uniform"]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dbg = build(ctx, dev, table, R, probe)
         for name, S in (("sorted", oracle.relS_for("uniform", R)), ("mixed", mixed_side(R, 2 * 256 * 3 + 5, dbg, seed=13))):
             want = want_matches(R, S, probe)

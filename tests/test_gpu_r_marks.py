@@ -10,17 +10,11 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from oracle import oracle
 
-from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, Dev, Calls,
-                            Marks, _status, zipf, inner_expected, join_expected, r_rows_of)
+from gpu_harness import Device, ctx, status  # noqa: F401
+from r_marks_common import (SENTINEL, GUARD, U64, INNER, LEFT, SEMI, ANTI, UNMATCHED, MATCHED, SWEEP_ROWS, Calls, Marks, zipf,
+                            inner_expected, join_expected, r_rows_of)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def tracked(ctx, dev, algo, R, s_max, probe_length=4, idx_base=0):
@@ -40,7 +34,7 @@ def test_last_word_of_the_plane(ctx, algo, n):
     """no probe: every row unmatched, none beyond rSize; every second row probed; every row probed: the complement of a
     full plane must not invent the rows of the last word's unused bits"""
     R = np.arange(1, n + 1, dtype=U64)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, 2 * n)
         marks.check((algo, n, "no probe"))
         for S in (np.concatenate([R[::2], R[:1] + U64(5000)]), R):
@@ -62,7 +56,7 @@ def test_row_base(ctx, algo):
     S = oracle.generate_data("sorted", 2 * n)[5: n + 300]
     inner = inner_expected(algo, R, S, r_base=r_base, s_base=s_base)
     assert r_rows_of(inner).min() >= r_base and 0 < r_rows_of(inner).size < n
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, S.size, idx_base=r_base)
         calls.call(LEFT, dev.put(S), S.size, inner, s_base=s_base, tag=algo)
         marks.add(inner)
@@ -80,7 +74,7 @@ def test_open_addressing_dropped_tuples_are_unmatched(ctx, probe_length):
     inner = inner_expected("atomic", R, S, probe_length)
     conflicts = oracle.build_probe_seq(R, S, probe_length)["conflicts"]
     assert conflicts > 0 or probe_length == 8
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, "atomic", R, S.size, probe_length)
         calls.call(INNER, dev.put(S), S.size, inner, tag=probe_length)
         marks.add(inner)
@@ -96,7 +90,7 @@ def test_htm_1000_x_1500(ctx):
     g = oracle.generate_data
     R, S = g("uniform", 1 << 10, 1 << 10, 16)[:1000], g("sorted", 2048)[:1500]
     inner = join_expected(R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, "htm", R, S.size)
         calls.call(INNER, dev.put(S), S.size, inner)
         marks.add(inner)
@@ -114,7 +108,7 @@ def test_htm_long_chains(ctx):
     inner = join_expected(R, S)
     rows = r_rows_of(inner)
     assert np.array_equal(rows, np.flatnonzero(np.isin(R, S)).astype(U64)) and rows.size < R.size
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, "htm", R, S.size)
         calls.count_only(INNER, dev.put(S), S.size, inner.size, np.unique(inner >> U64(32)).size)
         marks.add(inner)
@@ -131,7 +125,7 @@ def test_marks_accumulate_over_inner_and_left_slices_only(ctx, algo):
     keys = oracle.generate_data("sorted", 2 * n)
     slices = [keys[0:900], keys[1000:1700], keys[2500:3001]]             # INNER, LEFT, INNER
     other = np.concatenate([keys[3200:3900], keys[n + 5: n + 50]])       # SEMI, ANTI, counting: rows no slice above names
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, 1024)
         d_other, inner_other = dev.put(other), inner_expected(algo, R, other)
         assert inner_other.size > 0
@@ -168,7 +162,7 @@ def test_rows_cut_by_the_capacity_mark_too(ctx, algo):
     S = oracle.generate_data("uniform", n, n // 2, 16)[: n - 7]
     inner = inner_expected(algo, R, S)
     assert inner.size > 3000                                             # far more rows than the capacities below
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, S.size)
         dS = dev.put(S)
         marks.add(inner)
@@ -192,7 +186,7 @@ def test_sweep_capacity_and_several_blocks(ctx):
     R = rng.permutation(np.arange(1, n + 1, dtype=U64))
     S = np.arange(1, n + 1, dtype=U64)[rng.random(n) < 0.6]
     inner = join_expected(R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, "htm", R, S.size)
         calls.count_only(INNER, dev.put(S), S.size, inner.size, S.size)
         marks.add(inner)
@@ -201,14 +195,13 @@ def test_sweep_capacity_and_several_blocks(ctx):
             want = marks.expected(which)
             first_run = int((want < SWEEP_ROWS).sum())                    # rows of the first workgroup's run
             for capacity in (want.size - 1, want.size // 2, first_run, 5, 1):
-                produced, written, plane = marks.sweep(which, capacity)
+                produced, written, got = marks.sweep(which, capacity)          # no word behind the rows written: Marks.sweep
                 print(which, capacity, produced, written)
                 assert (produced, written) == (want.size, capacity) and produced > written
-                assert np.array_equal(plane[:capacity].astype(U64), want[:capacity])
-                assert (plane[capacity:] == SENTINEL).all()
+                assert np.array_equal(got.astype(U64), want[:capacity])
             assert marks.sweep(which, 0, null_plane=True)[:2] == (want.size, 0)       # only the count comes back
-            produced, written, plane = marks.sweep(which, 0)
-            assert (produced, written) == (want.size, 0) and (plane == SENTINEL).all()
+            produced, written, got = marks.sweep(which, 0)
+            assert (produced, written) == (want.size, 0) and got.size == 0
         marks.check("after the truncated sweeps")                       # a sweep changes no mark
 
 
@@ -220,7 +213,7 @@ def test_nothing_and_everything(ctx, algo):
     n = 1 << 12
     R = oracle.generate_data("shuffle", n, n, 16)
     absent = oracle.generate_data("sorted", 4 * n)[3 * n: 3 * n + n - 3]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, n)
         marks.check((algo, "no probe at all"))
         none = inner_expected(algo, R, absent)
@@ -245,7 +238,7 @@ def test_zipf_probe_marks_exactly(ctx, algo):
     S = zipf(1 << 16, n, 1.0, 54321)
     inner = inner_expected("htm", R, S)                                  # unique keys 1..n: the walk finds each in its home slot
     assert np.bincount((inner & U64(0xFFFFFFFF)).astype(np.int64)).max() > 3000 and r_rows_of(inner).size < n
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, S.size)
         calls.call(INNER, dev.put(S), S.size, inner, tag="zipf")
         marks.add(inner)
@@ -261,7 +254,7 @@ def test_clearing(ctx, algo):
     R = oracle.generate_data("shuffle", n, n, 16)
     S = oracle.generate_data("sorted", n)[100:1500]
     inner = inner_expected(algo, R, S)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR, calls, marks = tracked(ctx, dev, algo, R, S.size)
         dS = dev.put(S)
         calls.call(INNER, dS, S.size, inner)
@@ -288,32 +281,32 @@ def test_clearing(ctx, algo):
 def test_errors():
     n = 1 << 10
     R = oracle.generate_data("sorted", n)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         dR = dev.put(R)
         d_rows = dev.put(np.full(n + GUARD, SENTINEL, dtype=np.uint32))
         d_keys = dev.put(R.astype(np.uint32))
         # open addressing with the flag but without the row ids: refused at hj_reserve; htm takes the flag alone
         for algo in ("atomic", "nocc"):
-            assert _status(c.reserve, algo, n, n, trackRMatches=True) == _lib.HJ_ERR_INVALID
-        assert _status(c.reserve, "htm", n, n, trackRMatches=True) == _lib.HJ_OK
+            assert status(c.reserve, algo, n, n, trackRMatches=True) == _lib.HJ_ERR_INVALID
+        assert status(c.reserve, "htm", n, n, trackRMatches=True) == _lib.HJ_OK
         # reserved without the flag
         for algo in ("atomic", "htm"):
             c.reserve(algo, n, n, keepRowIds=True)
             c.build(dR, n)
-            assert _status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
-            assert _status(c.r_rows_info) == _lib.HJ_ERR_STATE
-            assert _status(c.r_marks_clear) == _lib.HJ_ERR_STATE
+            assert status(c.r_rows, UNMATCHED, d_rows, n) == _lib.HJ_ERR_STATE
+            assert status(c.r_rows_info) == _lib.HJ_ERR_STATE
+            assert status(c.r_marks_clear) == _lib.HJ_ERR_STATE
         # with the flag: no build yet
         with hj.HashJoinContext(0) as fresh:
             fresh.reserve("atomic", n, n, keepRowIds=True, trackRMatches=True)
-            assert _status(fresh.r_rows, UNMATCHED, 0, 0) == _lib.HJ_ERR_STATE
+            assert status(fresh.r_rows, UNMATCHED, 0, 0) == _lib.HJ_ERR_STATE
         c.reserve("atomic", n, n, keepRowIds=True, trackRMatches=True)
-        assert _status(c.build_keys, d_keys, n, 0, 2 * n) == _lib.HJ_ERR_STATE
+        assert status(c.build_keys, d_keys, n, 0, 2 * n) == _lib.HJ_ERR_STATE
         c.build(dR, n)
-        assert _status(c.r_rows, 2, d_rows, n) == _lib.HJ_ERR_INVALID
-        assert _status(c.r_rows, 0xFFFFFFFF, d_rows, n) == _lib.HJ_ERR_INVALID
-        assert _status(c.r_rows, UNMATCHED, 0, n) == _lib.HJ_ERR_INVALID          # NULL plane with capacity > 0
-        assert _status(c.build_keys, d_keys, n, 0, 2 * n) == _lib.HJ_ERR_STATE
+        assert status(c.r_rows, 2, d_rows, n) == _lib.HJ_ERR_INVALID
+        assert status(c.r_rows, 0xFFFFFFFF, d_rows, n) == _lib.HJ_ERR_INVALID
+        assert status(c.r_rows, UNMATCHED, 0, n) == _lib.HJ_ERR_INVALID          # NULL plane with capacity > 0
+        assert status(c.build_keys, d_keys, n, 0, 2 * n) == _lib.HJ_ERR_STATE
         assert c.r_rows_info() == (0, 0, 0, n)                                    # no sweep ran
         assert (dev.get(d_rows, n + GUARD) == SENTINEL).all()
         c.r_rows(UNMATCHED, d_rows, n)

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, ctx  # noqa: F401
 import wave_cases as wc
-from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -30,19 +30,10 @@ COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFu
 PROBES = (1, 2, 3, 4, 8)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    lay = c.wave_layout_info(N)
-    assert (lay["nChunks"], lay["chunkLen"], lay["tileTuples"], lay["granuleSlots"], lay["overlap"]) == (8, CHUNK, TILE, 128, ROW), lay
-    yield c
-    c.close()
-
-
 def build_probe(c, rel, S, probe, variant=3):
     """one build + probe + checksums through the split API -> (result, exported table, slot_codes_info, starts)"""
     c.reserve("atomic", rel.size, S.size, probeLength=probe, buildVariant=variant, slotCodes=True)
-    with Dev(c) as dev:
+    with Device(c) as dev:
         c.build(dev.put(np.ascontiguousarray(rel, dtype=U64)), rel.size)
         c.probe(dev.put(np.ascontiguousarray(S, dtype=U64)), S.size)
         c.checksums()
@@ -88,7 +79,10 @@ def odd_base_starts():
 
 @pytest.fixture(scope="module")
 def plain(ctx):
-    """the odd base by itself: its seams are where the cases count their tiles from, nothing is deferred or dropped"""
+    """the layout the cases of this file are written for; then the odd base by itself: its seams are where the cases count
+    their tiles from, nothing is deferred or dropped"""
+    lay = ctx.wave_layout_info(N)
+    assert (lay["nChunks"], lay["chunkLen"], lay["tileTuples"], lay["granuleSlots"], lay["overlap"]) == (8, CHUNK, TILE, 128, ROW), lay
     got, want, starts = run_case(ctx, wc.relation(wc.base_odd(N)), 4, "odd base")
     assert np.array_equal(starts, odd_base_starts()), starts
     assert (want["conflicts"], got["buildDeferred"]) == (0, 0)
@@ -312,7 +306,7 @@ def test_the_size_rule_road(ctx):
     want = oracle.build_probe_seq(rel, S, 4, want_table=True)
     assert want["conflicts"] > n // 64 and 0 < want["totalMatches"] < S.size
     ctx.reserve("atomic", rel.size, S.size, probeLength=4, buildVariant=3)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.build(dev.put(rel), rel.size)
         ctx.probe(dev.put(S), S.size)
         ctx.checksums()

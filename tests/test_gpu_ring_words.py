@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, ctx  # noqa: F401
 import wave_cases as wc
-from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -24,17 +24,10 @@ COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFu
 LOG_OVERFLOW, CODE_OVERFLOW = 1, 4           # slot_codes_info()["cause"]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
 def build_probe(c, rel, S, probe=4, variant=3, slot_codes=True):
     """one build + probe + checksums through the split API -> (result, exported table, slot_codes_info)"""
     c.reserve("atomic", rel.size, S.size, probeLength=probe, buildVariant=variant, slotCodes=slot_codes)
-    with Dev(c) as dev:
+    with Device(c) as dev:
         c.build(dev.put(np.ascontiguousarray(rel, dtype=U64)), rel.size)
         c.probe(dev.put(np.ascontiguousarray(S, dtype=U64)), S.size)
         c.checksums()
@@ -321,7 +314,7 @@ def test_the_size_rule_at_its_smallest_table(ctx):
     want = oracle.build_probe_seq(rel, S, 4, want_table=True)
     assert want["conflicts"] > n // 64 and 0 < want["totalMatches"] < S.size
     ctx.reserve("atomic", rel.size, S.size, probeLength=4, buildVariant=3)
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.build(dev.put(rel), rel.size)
         ctx.probe(dev.put(S), S.size)
         ctx.checksums()

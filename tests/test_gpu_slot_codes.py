@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, ctx  # noqa: F401
 import valid_range_cases as vc
 import wave_cases as wc
-from join_kinds_common import Dev
 from oracle import oracle
 
 gpu = pytest.mark.gpu
@@ -23,17 +23,10 @@ COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFu
 LOG_OVERFLOW, EMPTY_PATTERN, CODE_OVERFLOW = 1, 2, 4         # slot_codes_info()["cause"]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
 def build_probe(c, rel, S, probe=4, variant=3, slot_codes=True, idx_base=0):
     """one build + probe + checksums through the split API -> (result, exported table, slot_codes_info)"""
     c.reserve("atomic", rel.size, S.size, probeLength=probe, buildVariant=variant, slotCodes=slot_codes)
-    with Dev(c) as dev:
+    with Device(c) as dev:
         c.build(dev.put(np.ascontiguousarray(rel, dtype=U64)), rel.size, idx_base)
         c.probe(dev.put(np.ascontiguousarray(S, dtype=U64)), S.size)
         c.checksums()
@@ -212,7 +205,7 @@ def test_vector_edges_and_the_table_end(ctx, probe):
     R[-4:] = np.arange(T - 4, T, dtype=U64)
     keys, counts = np.unique(R, return_counts=True)
     dup = keys[counts > 1][:1]
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dbg = build_codes(ctx, dev, R, probe)
         assert dbg["validHiEx"] == T
         total = 0
@@ -242,7 +235,7 @@ def test_tuples_that_can_match_nothing(ctx, probe):
     assert vc.classify(band, probe) == "interior"
     R = band.R
     stale_code = 1 << hj.slot_codes_info(T, probe)["dbits"]                      # hi = 1, d = 0: slot s holds key s + T
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dbg = build_codes(ctx, dev, R, probe)
         ctx.synchronize()
         ctx.copy_h2d(dbg["tableAddr"], np.full(T, stale_code, dtype=np.uint8))

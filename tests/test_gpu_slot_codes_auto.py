@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device, alloc, ctx  # noqa: F401
 import valid_range_cases as vc
-from join_kinds_common import Dev
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -131,7 +131,7 @@ def check_exact(got, table, want, tag):
 def build_probe(c, rel, S, probe, variant=3, export=True):
     """one build + probe + checksums through the split API -> (result, exported table, slot_codes_info)"""
     c.reserve("atomic", rel.size, S.size, probeLength=probe, buildVariant=variant)
-    with Dev(c) as dev:
+    with Device(c) as dev:
         c.build(dev.put(np.ascontiguousarray(rel, dtype=U64)), rel.size)
         c.probe(dev.put(np.ascontiguousarray(S, dtype=U64)), S.size)
         c.checksums()
@@ -162,13 +162,6 @@ def probe_adds(c, dev, S, offset=0, keys32=False):
 
 # ---- fixtures: one relation per size, one oracle table and one device table at 2^27 slots ------------------------------------
 @pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
 def world():
     cache = {}
 
@@ -197,7 +190,7 @@ def built27(oracle27):
     rel = oracle27[0]
     c = hj.HashJoinContext(0)
     c.reserve("atomic", rel.size, rel.size, probeLength=4, buildVariant=3)
-    dR = c.dev_alloc(rel.nbytes)
+    dR = alloc(c, rel.nbytes)
     c.copy_h2d(dR, rel)
     c.build(dR, rel.size)
     info, got = c.slot_codes_info(), c.fetch()
@@ -269,7 +262,7 @@ def test_all_ones_key_in_s_alone_matches_nothing(ctx, world, probe):
     want = oracle.build_probe_seq(rel, S, probe)
     got, _, info = build_probe(ctx, rel, S, probe, export=False)
     check_exact(got, None, want, ("mirror", probe))
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         assert probe_adds(ctx, dev, np.full(37, ALL_ONES, dtype=U64)) == 0
         assert probe_adds(ctx, dev, np.full(37, ALL_ONES, dtype=U64), 8) == 0
     check_road1(got, info, ("mirror", probe), tbits, probe)
@@ -389,7 +382,7 @@ def test_rotated_probe_loop_at_the_real_shift(oracle27, built27, pools27):
     c, table = built27["ctx"], oracle27[2]["table"]
     stride = 2048 * 256
     total = 0
-    with Dev(c) as dev:
+    with Device(c) as dev:
         for size in (0, 1, 2, 3, 4, 5, 7, 8, 9):
             S = mixed_side(pools27, size, 1000 * size)
             want = np_probe(table, S, 4)
@@ -431,7 +424,7 @@ def test_stale_codes_outside_the_valid_range(ctx):
         check_road1(ctx.fetch(), info, "stale")
         return ctx.table_debug()
 
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         dR = dev.put(R)
         dbg = build(dR)
         ctx.synchronize()
@@ -485,7 +478,7 @@ def test_bare_key_probe_on_the_size_rule(oracle27, built27):
     c, (rel, _, want) = built27["ctx"], oracle27
     pool = bare_key_side(rel, 27, [ALL_ONES, ALL_ONES - (1 << 27)])
     total = 0
-    with Dev(c) as dev:
+    with Device(c) as dev:
         for size in KEY_LENGTHS:
             S = pool[11 * size:12 * size] if size < 4099 else pool[:size]
             expect = np_probe(want["table"], S, 4)
@@ -509,7 +502,7 @@ def test_bare_key_probe_on_the_forced_road(ctx, probe):
     over = np.concatenate([rel[:300] + U64(cap * T), rel[300:600] + U64(2 * cap * T), np.array([ALL_ONES, ALL_ONES - T, cap * T + 5], dtype=U64)])
     pool = bare_key_side(rel, tbits, over, nhi=4 * cap)
     assert (pool >> U64(tbits) >= U64(cap)).sum() > 600
-    with Dev(ctx) as dev:
+    with Device(ctx) as dev:
         ctx.reserve("atomic", n, n, probeLength=probe, buildVariant=3, slotCodes=True)
         ctx.build(dev.put(rel), n)
         info = ctx.slot_codes_info()

@@ -11,9 +11,9 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
+from gpu_harness import Device, GuardedPlane, dev, fl  # noqa: F401
 import sort_common as sc
 import stream_order as so
-from test_gpu_keys2 import Device
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +26,6 @@ EDGES = (1, 2, 63, 64, 65, T - 1, T, T + 1, L - 1, L, L + 1, 2 * L + T + 17, 3 *
 assert max(EDGES) <= 1 << 17
 
 
-@pytest.fixture(scope="module")
-def dev():
-    d = Device()
-    yield d
-    d.close()
-
-
-class Out:
-    """dPerm: n words on the device between two guards"""
-
-    def __init__(self, dev, n):
-        self.dev, self.n = dev, n
-        self.base = dev.put(np.full(n + 2 * GUARD, SENT, dtype=U32))
-        self.ptr = self.base + 4 * GUARD
-
-    def read(self, tag):
-        a = self.dev.get(self.base, self.n + 2 * GUARD)
-        assert (a[:GUARD] == SENT).all() and (a[GUARD + self.n:] == SENT).all(), (tag, "a word outside dPerm was written")
-        return a[GUARD:GUARD + self.n]
-
-
 def sort_on_device(dev, cols, tag=None, garbage=None, release=True):
     """one hj_sort_rows_dev over the columns -> (the permutation, the info dict)"""
     n = cols[0].values.size
@@ -54,10 +33,10 @@ def sort_on_device(dev, cols, tag=None, garbage=None, release=True):
     for c in cols:
         plane = c.plane(garbage)
         desc.append((dev.put(c.values), dev.put(plane) if plane is not None else 0, c.width, c.type, c.flags))
-    out = Out(dev, n)
+    out = GuardedPlane(dev, n, sentinel=SENT, front=GUARD, behind=GUARD, what="a word outside dPerm was written")
     dev.ctx.sort_rows(desc, n, out.ptr)
     info = dev.ctx.sort_rows_info()
-    got = out.read(tag)
+    got = out.read(n, tag)
     _, chunk, chunks, _ = sc.layout(n)
     assert (info["rows"], info["passes"], info["skipped"], info["reserved"]) == (n, sum(c.passes() for c in cols), 0, 0), (tag, info)
     assert (info["chunks"], info["chunk_rows"]) == (chunks, chunk) and info["workspace_bytes"] > 0, (tag, info)
@@ -254,13 +233,6 @@ def test_sort_pairs_on_a_full_outer_join():
 
 
 # ---- stream order ------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the case below cannot pass vacuously
-    return f
-
-
 def test_stream_order(fl):
     """decoy keys (ascending: the identity) and an all-NULL decoy plane before the delay, the real ones behind it on the
     caller's stream: a call that read early answers with the identity"""

@@ -31,10 +31,10 @@ from htm_hashjoin_amd._lib import lib
 import agg_common as ac
 import keys2_common as k2
 import stream_order as so
+from gather_common import column, fill_of, fixed, rows_of, strings, want_of
+from gpu_harness import fl, plane_words  # noqa: F401
 from join_kinds_common import ANTI, LEFT, derive
 from r_marks_common import LOW, inner_expected, join_expected, unmatched_r
-from test_gpu_gather import column, fill_of, valid_words
-from test_gpu_gather2 import fixed, rows_of, strings, want_of
 
 pytestmark = pytest.mark.gpu
 
@@ -48,13 +48,6 @@ _CONTRACT = so.contract()
 def all_async(*names):
     """whether every entry point of a sequence is asynchronous in the steady state, by the table of INTEGRATION.md"""
     return all(_CONTRACT[n][0] == "asynchronous" for n in names)
-
-
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the tests below cannot pass vacuously
-    return f
 
 
 def ok(ctx, rc):
@@ -284,7 +277,7 @@ def test_b_table_pairs_marks_gather(fl):
     has = r2 != NO_ROW
     want_r = np.where(has, pay_r[np.where(has, r2, 0)], U64(fill_r))
     assert np.array_equal(st.result(bGr, U64, "gather R"), want_r)
-    assert np.array_equal(st.result(bGv, U32, "gather valid"), valid_words(has)) and not has.all()
+    assert np.array_equal(st.result(bGv, U32, "gather valid"), plane_words(has)) and not has.all()
     assert np.array_equal(st.result(bGs, U32, "gather S"), pay_s[s2 - N1])
     assert (got["totalMatches"], got["sSize"]) == (d.inner1.size + d.inner2.size, N1 + N2)
 
@@ -304,7 +297,7 @@ def stage_strings(st, col, rng):
     bO = st.buf(np.zeros(off.size, dtype=U32), real=off, warm=off)
     bV = None
     if col["valid"] is not None:
-        w = valid_words(col["valid"])
+        w = plane_words(col["valid"])
         bV = st.buf(np.zeros(w.size, dtype=U32), real=w, warm=w)
     return bD, bO, bV
 
@@ -370,7 +363,7 @@ class Resident:
         poison8 = np.full(NR, ac.POISON, dtype=U64)
         self.bPlain = st.buf(poison8, real=d.plain["src"], warm=np.roll(d.plain["src"].view(U64), 1))
         self.bNull = st.buf(np.full(NR, ac.POISON >> 32, dtype=U32), real=d.nullable["src"], warm=np.roll(d.nullable["src"].view(U32), 1))
-        wv = valid_words(d.nullable["valid"])
+        wv = plane_words(d.nullable["valid"])
         self.bNullV = st.buf(np.zeros(wv.size, dtype=U32), real=wv, warm=wv)
         self.sR, self.sS = stage_strings(st, d.str_r, rng), stage_strings(st, d.str_s, rng)
         # R's columns are gathered through the whole R plane, the SLACK words behind the pairs included: they keep the
@@ -423,16 +416,16 @@ class Resident:
         # the gathers, by the models of test_gpu_gather2.py over the map as it was written (its multiset is exact, above)
         g1 = self.g1
         i, null, _oor, has = rows_of(np.concatenate([r, np.full(SLACK, NO_ROW, dtype=U32)]), 0, NR)
-        assert has[:c1].all() and null[c1:].all() and np.array_equal(st.result(self.oRowV, U32, tag), valid_words(has)), (tag, "dValid")
+        assert has[:c1].all() and null[c1:].all() and np.array_equal(st.result(self.oRowV, U32, tag), plane_words(has)), (tag, "dValid")
         el, raw, _ = want_of(d.plain, i, has, g1)
         assert st.result(self.oPlain, np.uint8, tag).tobytes() == raw, (tag, "plain column")
         el, raw, _ = want_of(d.nullable, i, has, g1)
         assert st.result(self.oNull, np.uint8, tag).tobytes() == raw, (tag, "nullable column")
-        assert np.array_equal(st.result(self.oNullV, U32, tag), valid_words(el)), (tag, "nullable column, dstValid")
+        assert np.array_equal(st.result(self.oNullV, U32, tag), plane_words(el)), (tag, "nullable column, dstValid")
         el, raw, off = want_of(d.str_r, i, has, g1)
         assert len(raw) == d.bytes_r and st.result(self.oStrR, np.uint8, tag).tobytes() == raw, (tag, "string column of R")
         assert np.array_equal(st.result(self.oStrROff, U32, tag).astype(np.int64), off), (tag, "string column of R, offsets")
-        assert np.array_equal(st.result(self.oStrRV, U32, tag), valid_words(el)), (tag, "string column of R, dstValid")
+        assert np.array_equal(st.result(self.oStrRV, U32, tag), plane_words(el)), (tag, "string column of R, dstValid")
         i, _null, _oor, has = rows_of(s, 0, M1)
         el, raw, off = want_of(d.str_s, i, has, c1)
         assert len(raw) == d.bytes_s and st.result(self.oStrS, np.uint8, tag).tobytes() == raw, (tag, "string column of S")
@@ -583,7 +576,7 @@ KEY_MASK = 0xFF                  # 256 join words for thousands of rows: the ver
 def arrow(c):
     """a keys2_common.ModelCol as numpy buffers: (values or bytes, uint32 offsets or None, validity words or None)"""
     valid = np.array([e is not None for e in c.items], dtype=bool)
-    words = None if valid.all() else valid_words(valid)
+    words = None if valid.all() else plane_words(valid)
     if c.width:
         raw = b"".join(b"\xA5" * c.width if e is None else e for e in c.items)
         return np.frombuffer(raw, dtype=np.uint8).copy(), None, words
@@ -679,7 +672,7 @@ def test_e_key_columns(fl):
     el, raw, off = want_of(str_s, i, has, n_kept)
     assert len(raw) == total and st.result(oStr, np.uint8, "string key").tobytes() == raw
     assert np.array_equal(st.result(oOff, U32, "string key").astype(np.int64), off)
-    assert np.array_equal(st.result(oValid, U32, "string key"), valid_words(el))
+    assert np.array_equal(st.result(oValid, U32, "string key"), plane_words(el))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

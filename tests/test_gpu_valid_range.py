@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import Device
 import r_marks_common as rm
 import valid_range_cases as vc
-from join_kinds_common import INNER, LEFT, KINDS, NO_ROW, Calls, Dev, derive
+from join_kinds_common import INNER, LEFT, KINDS, NO_ROW, Calls, derive
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -206,7 +207,7 @@ def run_case(path, band, placement, want_class, probe=4, poison=None, idx_base=0
     want_class: "interior" | "whole" | "control" (asserted), or "device" (the sweeps: returned). -> (class, tag)"""
     p = {**PATHS, **CONTROLS}[path]
     poison = poison or ("htm" if band.htm else "packed")
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         P, raw0 = build_poison(c, dev, band, poison, band.n)
         build_r(c, dev, band, path, probe, idx_base)
         dbg = c.table_debug()
@@ -238,7 +239,7 @@ def run_case(path, band, placement, want_class, probe=4, poison=None, idx_base=0
 def test_table_debug_contract():
     n = 1 << 12
     R = np.arange(1, n + 1, dtype=U64)
-    with hj.HashJoinContext(0) as c, Dev(c) as dev:
+    with hj.HashJoinContext(0) as c, Device(c) as dev:
         with pytest.raises(hj.HashJoinError) as e:
             c.table_debug()
         assert e.value.status == -7                           # HJ_ERR_STATE before any build

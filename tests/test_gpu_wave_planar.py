@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import htm_hashjoin_amd as hj
+from gpu_harness import alloc, ctx  # noqa: F401
 import wave_cases as wc
 from oracle import oracle
 
@@ -16,13 +17,6 @@ pytestmark = pytest.mark.gpu
 N = 1 << 16
 COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum")
 LOG_OVERFLOW, EMPTY_PATTERN = 1, 2          # hj_wave_planar_info, out[1]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
 
 
 def probe_side(rel):
@@ -35,7 +29,7 @@ def build_probe(c, rel, S, probe=4, variant=3, shift=0, keys32=False, table_size
     table_size = table_size or 2 * rel.size
     c.reserve("atomic", table_size // 2, S.size, probeLength=probe, buildVariant=variant, keepRowIds=keep)
     width, dtype = (4, np.uint32) if keys32 else (8, np.uint64)
-    d_r, d_s = c.dev_alloc(width * rel.size + 16), c.dev_alloc(width * S.size + 16)
+    d_r, d_s = alloc(c, width * rel.size + 16), alloc(c, width * S.size + 16)
     try:
         c.copy_h2d(d_r, rel.astype(dtype))
         c.copy_h2d(d_s, S.astype(dtype))
@@ -244,7 +238,7 @@ def test_row_ids_keep_the_packed_slots(ctx):
     S = rel[::5].copy()
     cap = S.size + 8
     ctx.reserve("atomic", n, S.size, buildVariant=3, keepRowIds=True)
-    d_r, d_s, d_os, d_or = ctx.dev_alloc(8 * n), ctx.dev_alloc(8 * S.size), ctx.dev_alloc(4 * cap), ctx.dev_alloc(4 * cap)
+    d_r, d_s, d_os, d_or = alloc(ctx, 8 * n), alloc(ctx, 8 * S.size), alloc(ctx, 4 * cap), alloc(ctx, 4 * cap)
     try:
         ctx.copy_h2d(d_r, rel)
         ctx.copy_h2d(d_s, S)

@@ -8,6 +8,7 @@ import pytest
 
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
+from gpu_harness import alloc, ctx  # noqa: F401
 import wave_cases as wc
 from oracle import oracle
 
@@ -17,13 +18,6 @@ N = 1 << 16
 COUNTERS = ("conflicts", "totalMatches", "inputSum", "tableSumHalf", "tableSumFull", "conflictSum")
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = hj.HashJoinContext(0)
-    yield c
-    c.close()
-
-
 def build_probe(ctx, rel, S, probe, variant, shift=0, keys32=False, table_size=None):
     """one build + probe on the device -> (result, exported table, (starts, bounds, pcounts) if the rings ran)"""
     table_size = table_size or 2 * rel.size
@@ -31,7 +25,7 @@ def build_probe(ctx, rel, S, probe, variant, shift=0, keys32=False, table_size=N
         got = ctx.run("atomic", rel, S, probeLength=probe, buildVariant=variant)
     else:
         ctx.reserve("atomic", table_size // 2, S.size, probeLength=probe, buildVariant=variant)
-        d_r, d_s = ctx.dev_alloc(4 * rel.size + 16), ctx.dev_alloc(4 * S.size + 16)
+        d_r, d_s = alloc(ctx, 4 * rel.size + 16), alloc(ctx, 4 * S.size + 16)
         try:
             ctx.copy_h2d(d_r, rel.astype(np.uint32))
             ctx.copy_h2d(d_s, S.astype(np.uint32))
@@ -174,7 +168,7 @@ def test_empty_pattern_key_and_its_holding_twin(ctx, world):
                 continue
             # the bare-key probe against the compact table of the twin
             ctx.reserve("atomic", N, S.size, probeLength=probe, buildVariant=4)
-            d_r, d_s, d_k = ctx.dev_alloc(8 * N), ctx.dev_alloc(8 * S.size), ctx.dev_alloc(4 * S.size)
+            d_r, d_s, d_k = alloc(ctx, 8 * N), alloc(ctx, 8 * S.size), alloc(ctx, 4 * S.size)
             try:
                 ctx.copy_h2d(d_r, rel)
                 ctx.copy_h2d(d_s, S)
@@ -327,7 +321,7 @@ def test_context_reused_across_hold_hand_over_hold(world):
     sm = wc.seam_of(*w["base"]["gapped"]["seams"], lay, lay["nChunks"] // 2)
     with hj.HashJoinContext(0) as c:
         c.reserve("atomic", N, N, buildVariant=4)
-        d_r, d_s = c.dev_alloc(8 * N), c.dev_alloc(8 * N)
+        d_r, d_s = alloc(c, 8 * N), alloc(c, 8 * N)
         try:
             for x, expect4 in ((cap, (4, 0)), (cap + 1, (3, wc.BIT_CROSSERS)), (cap, (4, 0))):
                 rel = wc.relation(wc.crossers(wc.base_gapped(N), sm, x + 1)[0])

@@ -12,6 +12,7 @@ from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
 import stream_order as so
+from gpu_harness import fl, packed, plane_words  # noqa: F401
 import where_common as wc
 
 pytestmark = pytest.mark.gpu
@@ -19,13 +20,6 @@ pytestmark = pytest.mark.gpu
 U32 = np.uint32
 N_S, N_R, N_PAIRS, BASE = 3001, 2003, 9001, 500
 SLACK = 64                       # map words behind the exact count: they keep the HJ_NO_ROW prefill
-
-
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the test below cannot pass vacuously
-    return f
 
 
 def vp(p):
@@ -50,7 +44,7 @@ def test_pairs_where_behind_a_delay(fl):
         bMR = st.buf(np.full(N_PAIRS, so.NO_ROW, dtype=U32), real=map_r, warm=np.roll(map_r, 2))
         bS = st.buf(np.full(N_S, np.iinfo(np.int32).max, dtype=np.int32), real=s, warm=s[::-1].copy())
         bR = st.buf(np.full(N_R, np.iinfo(np.int32).min, dtype=np.int32), real=r, warm=r[::-1].copy())
-        bV = st.buf(np.zeros(sw, dtype=U32), real=wc.valid_words(s_valid), warm=wc.valid_words(~s_valid))
+        bV = st.buf(np.zeros(sw, dtype=U32), real=plane_words(s_valid), warm=plane_words(~s_valid))
         oS, oR = st.out(n_kept + SLACK, U32, so.NO_ROW), st.out(n_kept + SLACK, U32, so.NO_ROW)
         pS, pR = st.out(sw, U32, 0), st.out(rw, U32, 0)              # the planes, cleared by the caller
 
@@ -69,5 +63,5 @@ def test_pairs_where_behind_a_delay(fl):
     assert (info[0], info[1], info[3]) == (n_kept, n_kept, want["info"][3]), (info, want["info"])
     got_s, got_r = st.result(oS, U32, "kept S"), st.result(oR, U32, "kept R")
     assert (got_s[n_kept:] == so.NO_ROW).all() and (got_r[n_kept:] == so.NO_ROW).all(), "a word behind the last pair was written"
-    assert np.array_equal(wc.packed(got_s[:n_kept], got_r[:n_kept]), want["kept"])
+    assert np.array_equal(packed(got_s[:n_kept], got_r[:n_kept]), want["kept"])
     assert np.array_equal(st.result(pS, U32, "S marks"), want["s_marks"]) and np.array_equal(st.result(pR, U32, "R marks"), want["r_marks"])

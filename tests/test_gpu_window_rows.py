@@ -12,11 +12,11 @@ import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
+from gpu_harness import Device, GuardedPlane, dev, fl  # noqa: F401
 import sort_common as sc
 import stream_order as so
 import window_common as wc
-from test_gpu_keys2 import Device
-from test_window_abi import WRAPPER_FUNCS, wrapper_call, wrapper_check, wrapper_table
+from window_common import WRAPPER_FUNCS, wrapper_call, wrapper_check, wrapper_table
 
 pytestmark = pytest.mark.gpu
 
@@ -29,27 +29,6 @@ EDGES = (1, 2, 63, 64, 65, T - 1, T, T + 1, L - 1, L, L + 1, 2 * L + T + 17, 3 *
 assert max(EDGES) <= 1 << 17
 
 
-@pytest.fixture(scope="module")
-def dev():
-    d = Device()
-    yield d
-    d.close()
-
-
-class Out:
-    """one function's output: n_rows entries on the device between two guards, all of it the sentinel"""
-
-    def __init__(self, dev, func, n_rows):
-        self.dev, self.f, self.n = dev, func, n_rows
-        self.base = dev.put(np.full(n_rows + 2 * GUARD, func.sentinel, dtype=func.dtype))
-        self.ptr = self.base + GUARD * np.dtype(func.dtype).itemsize
-
-    def read(self, tag):
-        a = self.dev.get(self.base, self.n + 2 * GUARD, self.f.dtype)
-        assert (a[:GUARD] == self.f.sentinel).all() and (a[GUARD + self.n:] == self.f.sentinel).all(), (tag, "an entry outside out was written")
-        return a[GUARD:GUARD + self.n]
-
-
 def on_device(dev, case, tag=None, garbage=None, funcs=None, release=True):
     """one hj_window_rows_dev -> ([one array per function], the info dict)"""
     funcs = case.funcs if funcs is None else funcs
@@ -59,13 +38,14 @@ def on_device(dev, case, tag=None, garbage=None, funcs=None, release=True):
     for c in case.order:
         plane = c.plane(garbage)
         order.append((dev.put(c.values), dev.put(plane) if plane is not None else 0, c.width, c.type, c.flags))
-    outs, desc = [Out(dev, f, case.n_rows) for f in funcs], []
+    outs, desc = [GuardedPlane(dev, case.n_rows, f.dtype, f.sentinel, front=GUARD, behind=GUARD, what="an entry outside out was written")
+                  for f in funcs], []
     for f, o in zip(funcs, outs):
         plane = f.plane(case.n_rows, garbage)
         desc.append((f.op, o.ptr, dev.put(f.src) if f.src is not None else 0, dev.put(plane) if plane is not None else 0, f.width, f.flags, f.offset))
     dev.ctx.window_rows(d_perm, case.n_pos, case.n_rows, d_part, order, desc)
     info = dev.ctx.window_rows_info()
-    got = [o.read(tag) for o in outs]
+    got = [o.read(case.n_rows, tag) for o in outs]
     if release:
         dev.release()
     return got, info
@@ -268,13 +248,6 @@ def test_window_rows_without_a_sort():
 
 
 # ---- stream order --------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", params=so.FLAVOURS)
-def fl(request):
-    f = so.Flavour(request.param)
-    assert so.witness(f)         # misused on purpose, the harness sees the decoy: the case below cannot pass vacuously
-    return f
-
-
 def test_stream_order(fl):
     """decoy content before the delay -- a dPerm of HJ_NO_ROW (nothing would be written), one partition id, zero values under
     an all-NULL plane -- and the real inputs behind it on the caller's stream"""

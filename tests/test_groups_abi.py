@@ -15,8 +15,8 @@ from htm_hashjoin_amd import _lib
 
 import groups_common as gc
 import keys2_common as k2
-from test_keys_abi import _declared_args, _header
-from test_keys2_abi import _bad_columns, _col2
+from keys_common import _declared_args, _header
+from keys2_common import _bad_columns, _col2
 
 COL2 = "const hj_key_col2 *"
 DEV_ARGS = [COL2, "uint32_t", "uint32_t", "uint64_t", "uint32_t", "uint32_t *", "uint32_t *", "uint32_t *", "uint64_t"]

@@ -13,9 +13,9 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-from keys2_common import (HOWS, LENGTHS, MASKS, M32, ROWS, ModelCol, fixed_col, hash_matrix, key_column, mm3_final, mm3_mix,
-                          model_words, varlen_col)
-from test_keys_abi import MIXES, PAIR, _code, _declared_args, _header, key_words, murmur3_words, random_column
+from keys2_common import (HOWS, LENGTHS, MASKS, M32, ROWS, ModelCol, _bad_columns, _col2, fixed_col, hash_matrix, key_column, mm3_final,
+                          mm3_mix, model_words, varlen_col)
+from keys_common import MIXES, PAIR, _code, _declared_args, _header, key_words, murmur3_words, random_column
 
 COL2 = "const hj_key_col2 *"
 DEVICE_SYMBOLS = {
@@ -82,7 +82,7 @@ def test_abi_version_and_the_structs_around_are_unchanged():
 
 # ---- the hash --------------------------------------------------------------------------------------------------------------
 def test_the_model_is_the_old_restatement_on_plain_columns():
-    """keys2_common's scalar hash against test_keys_abi's numpy one, neither of them the library"""
+    """keys2_common's scalar hash against keys_common's numpy one, neither of them the library"""
     rng = np.random.default_rng(5)
     for widths in MIXES:
         cols = [random_column(rng, w, 40) for w in widths]
@@ -158,7 +158,7 @@ def test_null_keyed_rows_hash_their_position():
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1025])
 def test_plain_columns_hash_as_hj_key_hash_host(n, key_mask):
     """the compatibility property: no offsets, no validity, flags 0 -> the tuples of hj_key_hash_host, tuple for tuple.
-    Both entry points run one body, so the tuples are also held to the header's wording, restated in test_keys_abi.py"""
+    Both entry points run one body, so the tuples are also held to the header's wording, restated in keys_common.py"""
     rng = np.random.default_rng(1000 * n + (key_mask & 0xFF))
     for widths in MIXES:
         cols = [random_column(rng, w, n) for w in widths]
@@ -194,35 +194,6 @@ def test_host_hash_reads_the_side_it_is_given():
 
 
 # ---- argument errors -------------------------------------------------------------------------------------------------------
-def _bad_columns(n):
-    """(name, keyword changes) of every column the three entry points refuse, on top of a good one"""
-    keys = np.arange(2 * n, dtype=np.uint64)
-    off = np.arange(n + 2, dtype=np.uint32)
-    valid = np.full(n // 32 + 2, M32, dtype=np.uint32)
-    good_fixed = dict(ptr=keys.ctypes.data, width=8, off=0, valid=valid.ctypes.data, flags=1)
-    good_var = dict(ptr=keys.ctypes.data + 1, width=0, off=off.ctypes.data, valid=0, flags=0)
-    bad = [dict(good_fixed, width=w) for w in (3, 5, 12, 32)]
-    bad += [dict(good_fixed, width=w, ptr=keys.ctypes.data + w // 2) for w in (2, 4, 8, 16)]       # misaligned for its width
-    bad += [dict(good_fixed, ptr=0), dict(good_var, ptr=0),
-            dict(good_var, off=0),                                                                  # width 0 without offsets
-            dict(good_fixed, off=off.ctypes.data),                                                  # offsets with a width
-            dict(good_fixed, flags=2), dict(good_var, flags=0x80000001),                            # unknown flag bits
-            dict(good_var, off=off.ctypes.data + 2), dict(good_fixed, valid=valid.ctypes.data + 1),  # not 4-byte aligned
-            dict(good_var, valid=valid.ctypes.data + 2)]
-    return (keys, off, valid), good_fixed, good_var, bad
-
-
-def _col2(n_cols, side_s, side_r, ptr, width, off, valid, flags):
-    cols = (_lib.hj_key_col2 * 5)()
-    for c in cols:
-        c.width, c.flags = width, flags
-        if side_s:
-            c.s, c.sOffsets, c.sValid = ptr or None, off or None, valid or None
-        if side_r:
-            c.r, c.rOffsets, c.rValid = ptr or None, off or None, valid or None
-    return cols
-
-
 def test_host_hash_argument_errors():
     n = 32
     held, good_fixed, good_var, bad = _bad_columns(n)

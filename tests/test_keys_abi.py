@@ -1,11 +1,10 @@
 """Joins on real key columns at the ABI boundary: hj_key_hash_dev, hj_key_hash_host, hj_pairs_verify_dev, hj_verify_info,
 hj_mark_rows_dev and hj_mark_rows_info are declared, exported and bound with the argument types of the header, hj_key_col
-is 24 bytes, nothing of the ABI around them moved; hj_key_hash_host computes the header's hash (restated here in numpy)
+is 24 bytes, nothing of the ABI around them moved; hj_key_hash_host computes the header's hash (restated in keys_common.py in numpy)
 and refuses what the header says it refuses; join_on refuses what it cannot take and answers empty inputs without a
 device. No GPU needed."""
 import ctypes
 import inspect
-import os
 import re
 
 import numpy as np
@@ -14,7 +13,8 @@ import pytest
 import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from keys_common import MIXES, PAIR, _code, _declared_args, _header, key_words, murmur3_words, random_column
+
 # symbol -> its arguments behind the context, as the header spells their types
 DEVICE_SYMBOLS = {
     "hj_key_hash_dev": ["const hj_key_col *", "uint32_t", "uint32_t", "uint64_t", "uint32_t", "uint64_t *"],
@@ -27,22 +27,6 @@ HOST_ARGS = ["const hj_key_col *", "uint32_t", "uint32_t", "uint64_t", "uint32_t
 HOWS = ("inner", "left", "semi", "anti", "right", "full", "right_semi", "right_anti")
 S_PLANE = ("inner", "left", "semi", "anti", "right", "full")
 R_PLANE = ("inner", "left", "right", "full", "right_semi", "right_anti")
-PAIR = np.dtype([("a", np.uint64), ("b", np.float64)])         # a 16-byte structured element
-WIDTH_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64, 16: PAIR}
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "htm_hashjoin.h")).read()
-
-
-def _code():
-    return re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-
-
-def _declared_args(symbol):
-    decl = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % symbol, _code())
-    assert decl, f"{symbol} is not declared in include/htm_hashjoin.h"
-    return [a.strip() for a in decl.group(1).split(",")]
 
 
 @pytest.mark.parametrize("symbol", sorted(DEVICE_SYMBOLS))
@@ -128,44 +112,6 @@ def test_null_context_is_invalid():
 
 
 # ---- the hash: the header's wording, restated ----------------------------------------------------------------------------
-def _rotl(x, r):
-    return ((x << np.uint32(r)) | (x >> np.uint32(32 - r))).astype(np.uint32)
-
-
-def murmur3_words(words, key_mask=0):
-    """MurmurHash3_x86_32, seed 0, of every row of words[rows, nWords] (uint32); len = 4 * nWords; & key_mask (0: all)"""
-    words = np.asarray(words, dtype=np.uint32)
-    h = np.zeros(words.shape[0], dtype=np.uint32)
-    with np.errstate(over="ignore"):
-        for j in range(words.shape[1]):
-            k = words[:, j] * np.uint32(0xcc9e2d51)
-            k = _rotl(k, 15) * np.uint32(0x1b873593)
-            h = _rotl(h ^ k, 13) * np.uint32(5) + np.uint32(0xe6546b64)
-        h = h ^ np.uint32(4 * words.shape[1])
-        h = (h ^ (h >> np.uint32(16))) * np.uint32(0x85ebca6b)
-        h = (h ^ (h >> np.uint32(13))) * np.uint32(0xc2b2ae35)
-        h = h ^ (h >> np.uint32(16))
-    return (h & np.uint32(key_mask or 0xFFFFFFFF)).astype(np.uint64)
-
-
-def key_words(cols):
-    """the 32-bit words of every row: width 1 and 2 zero-extended to one word, wider elements their little-endian words"""
-    parts = []
-    for a in cols:
-        a = np.ascontiguousarray(a)
-        w = a.dtype.itemsize
-        raw = a.view(np.uint8).reshape(a.size, w)
-        if w < 4:
-            raw = np.concatenate([raw, np.zeros((a.size, 4 - w), dtype=np.uint8)], axis=1)
-        parts.append(np.ascontiguousarray(raw).view("<u4").reshape(a.size, -1))
-    return np.concatenate(parts, axis=1)
-
-
-def random_column(rng, width, n):
-    raw = rng.integers(0, 256, size=n * width, dtype=np.uint8)
-    return raw.view(WIDTH_DTYPES[width]).reshape(n).copy()
-
-
 def test_the_published_vector():
     """4 zero bytes, seed 0 -> 0x2362F9DE"""
     assert int(murmur3_words(np.zeros((1, 1), dtype=np.uint32))[0]) == 0x2362F9DE
@@ -173,9 +119,6 @@ def test_the_published_vector():
     # a 1- or 2-byte zero is the same one word
     assert int(hj.key_hash_host(np.zeros(1, dtype=np.uint8))[0]) == 0x2362F9DE
     assert int(hj.key_hash_host([np.zeros(1, dtype=np.uint16)])[0]) == 0x2362F9DE
-
-
-MIXES = [(1,), (2,), (4,), (8,), (16,), (8, 4), (1, 16), (2, 8, 1), (4, 4, 4), (16, 2, 8, 1), (1, 2, 4, 8), (16, 16, 16, 16)]
 
 
 @pytest.mark.parametrize("key_mask", [0, 0x3F, 0xFFFF0000])

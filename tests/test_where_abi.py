@@ -13,6 +13,7 @@ from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
 import where_common as wc
+from gpu_harness import packed
 
 U32, NO_ROW = np.uint32, wc.NO_ROW
 SENT = 0xA5A5A5A5
@@ -170,7 +171,7 @@ def test_capacity_and_the_mark_only_pass():
     arr, k, _alive = wc.c_terms(terms)
     out_s, out_r = np.empty(n, dtype=U32), np.empty(n, dtype=U32)
     assert lib.hj_pairs_where_host(vp(map_s), vp(map_r), n, 0, n_s, n_r, arr, k, vp(out_s), vp(out_r), n, None, None, None) == OK
-    assert np.array_equal(wc.packed(out_s[:kept], out_r[:kept]), full["kept"])
+    assert np.array_equal(packed(out_s[:kept], out_r[:kept]), full["kept"])
     # nPairs 0 keeps nothing, maps and outputs NULL
     info = (C.c_uint64 * 4)(9, 9, 9, 9)
     assert lib.hj_pairs_where_host(None, None, 0, 0, n_s, n_r, arr, k, None, None, 5, None, None, info) == OK and tuple(info) == (0, 0, 0, 0)
@@ -198,7 +199,7 @@ def test_the_python_form():
     want = wc.model_call(map_s, map_r, 10, n_s, n_r, terms)
     py_terms = [(np.ma.MaskedArray(s, mask=~sv) if sv is not None else s, op, hj.KeyColumn(r, rv)) for s, op, r, sv, rv in terms]
     got = hj.pairs_where_host(map_s, map_r, 10, py_terms, marks=True)
-    assert got["info"] == want["info"] and np.array_equal(wc.packed(got["s_idx"], got["r_idx"]), want["kept"])
+    assert got["info"] == want["info"] and np.array_equal(packed(got["s_idx"], got["r_idx"]), want["kept"])
     assert np.array_equal(got["s_marks"], want["s_marks"]) and np.array_equal(got["r_marks"], want["r_marks"])
     cut = hj.pairs_where_host(map_s, map_r, 10, py_terms, capacity=3)
     assert cut["info"][:2] == (want["info"][0], 3) and cut["s_idx"].size == 3 and "s_marks" not in cut

@@ -12,6 +12,8 @@ import numpy as np
 
 from htm_hashjoin_amd import _lib
 
+from gpu_harness import packed, plane_words, row_bits
+
 NO_ROW = 0xFFFFFFFF
 U32, U64 = np.uint32, np.uint64
 OPS = {"==": operator.eq, "!=": operator.ne, "<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}
@@ -34,22 +36,6 @@ def ladder(dtype):
     vals = [0, 1, 2, info.min, info.min + 1, info.max, info.max - 1]
     vals += [(1 << (bits - 1)) - 1, 1 << (bits - 1), (1 << (bits - 1)) + 1] if dtype.kind == "u" else [-1, -2, 100, -100]
     return np.array(list(dict.fromkeys(vals)), dtype=dtype)
-
-
-def mark_words(rows, n):
-    """the plane of n rows in which exactly `rows` are set"""
-    bits = np.zeros(-(-n // 32) * 32, dtype=bool)
-    bits[np.asarray(rows, dtype=np.int64)] = True
-    return np.packbits(bits, bitorder="little").view(U32).copy()
-
-
-def valid_words(valid):
-    """a validity as the C ABI takes it: bit i & 31 of word i >> 5, 1 = valid"""
-    return mark_words(np.flatnonzero(valid), valid.size) if valid.size else np.zeros(0, dtype=U32)
-
-
-def packed(s, r):
-    return np.sort((np.asarray(s).astype(U64) << U64(32)) | np.asarray(r).astype(U64))
 
 
 def term_of(s, op, r, s_valid=None, r_valid=None):
@@ -81,8 +67,8 @@ def model_call(map_s, map_r, base, s_rows, r_rows, terms, capacity=None):
         keep[ok] &= holds(term, s[ok], r[ok])
     kept = int(keep.sum())
     cap = map_s.size if capacity is None else capacity
-    return {"keep": keep, "kept": packed(map_s[keep], map_r[keep]), "s_marks": mark_words(s[keep], s_rows),
-            "r_marks": mark_words(r[keep], r_rows), "info": (kept, min(kept, cap), 0, int((~ok).sum()))}
+    return {"keep": keep, "kept": packed(map_s[keep], map_r[keep]), "s_marks": plane_words(row_bits(s[keep], s_rows)),
+            "r_marks": plane_words(row_bits(r[keep], r_rows)), "info": (kept, min(kept, cap), 0, int((~ok).sum()))}
 
 
 def model_join(how, r_keys, s_keys, terms):
@@ -120,7 +106,7 @@ def rows_of(result):
 def c_terms(terms, ptr=None):
     """model terms -> (hj_where_term array, count, what must stay alive). ptr(array) gives the address the library is to
     read (default: the numpy array's own, aligned by numpy's allocator for these sizes); a validity goes through
-    valid_words first"""
+    plane_words first"""
     keep = []
 
     def at(a):
@@ -133,7 +119,7 @@ def c_terms(terms, ptr=None):
     arr = (_lib.hj_where_term * max(len(terms), 1))()
     for c, (s, op, r, s_valid, r_valid) in zip(arr, terms):
         c.s, c.r = at(s), at(r)
-        c.sValid = at(valid_words(s_valid)) if s_valid is not None else None
-        c.rValid = at(valid_words(r_valid)) if r_valid is not None else None
+        c.sValid = at(plane_words(s_valid)) if s_valid is not None else None
+        c.rValid = at(plane_words(r_valid)) if r_valid is not None else None
         c.width, c.type, c.op, c.reserved = s.dtype.itemsize, TYPE_OF[s.dtype.kind], _lib.CMP_OPS[op], 0
     return arr, len(terms), keep

@@ -9,6 +9,7 @@ import ctypes as C
 
 import numpy as np
 
+import htm_hashjoin_amd as hj
 from htm_hashjoin_amd import _lib
 from htm_hashjoin_amd._lib import lib
 
@@ -320,3 +321,106 @@ def build(n_pos, shape="geometric", peers="runs", perm="random", extra_rows=0, h
     elif funcs == "run":
         funcs = run_funcs(n_rows, seed, null_pct)
     return Case(n_pos, n_rows, plane, None if shape == "one" and seed % 2 else part, order, funcs)
+
+
+# ---- the wrapper against a per-partition loop ------------------------------------------------------------------------------------------
+def _loop_reference(keys, order, descending, nulls, null_keys, cols, funcs):
+    """partition rows by their key tuples (None: NULL) in a dict, sort each partition with Python's stable sort over
+    sort_common's ranks, walk it"""
+    n = len(keys)
+    ranks = [sc._ranks(sc.Col(v, valid, d, w)) for (v, valid), d, w in zip(order, descending, nulls)]
+    parts, dropped = {}, []
+    for i, key in enumerate(keys):
+        if null_keys == "drop" and any(k is None for k in key):
+            dropped.append(i)
+            continue
+        parts.setdefault(key, []).append(i)
+    res = {name: [None] * n for name in funcs}
+    for name, spec in funcs.items():
+        if spec in ("row_number", "rank", "dense_rank", "count"):
+            res[name] = [0] * n
+    for rows in parts.values():
+        rows.sort(key=lambda i: tuple(int(r[i]) for r in ranks))
+        tie = [tuple(int(r[i]) for r in ranks) for i in rows]
+        for name, spec in funcs.items():
+            op = spec if isinstance(spec, str) else spec[0]
+            col = cols[spec[1]] if not isinstance(spec, str) and spec[1] is not None else None
+            acc, cnt, rank, dense = None, 0, 0, 0
+            for j, i in enumerate(rows):
+                if j == 0 or tie[j] != tie[j - 1]:
+                    rank, dense = j + 1, dense + 1
+                if op == "row_number":
+                    res[name][i] = j + 1
+                elif op == "rank":
+                    res[name][i] = rank
+                elif op == "dense_rank":
+                    res[name][i] = dense
+                elif op == "count":
+                    res[name][i] = len(rows)
+                elif op in ("lag", "lead"):
+                    q = j - spec[2] if op == "lag" else j + spec[2]
+                    res[name][i] = col[rows[q]] if 0 <= q < len(rows) else None
+                elif op in ("first", "last"):
+                    res[name][i] = col[rows[0 if op == "first" else -1]]
+                else:
+                    v = 1 if col is None else col[i]
+                    if v is not None:
+                        cnt += 1
+                        acc = v if acc is None else acc + v if op == "cumsum" else min(acc, v) if op == "cummin" else max(acc, v)
+                    res[name][i] = cnt if op == "cumcount" else acc
+    for name, spec in funcs.items():
+        if not isinstance(spec, str) and spec[0] == "cumcount":
+            res[name] = [0 if v is None else v for v in res[name]]
+    return res, len(parts), len(dropped)
+
+
+def wrapper_table(n, seed):
+    """a table with a string and an integer partition key (NULLs in both), two order columns and three payload columns"""
+    rng = np.random.default_rng(seed)
+    names = [None if rng.random() < 0.1 else "k%d" % rng.integers(0, 6) for _ in range(n)]
+    num_valid = rng.random(n) < 0.9
+    num = rng.integers(0, 3, n).astype(np.int64)
+    o1_valid = rng.random(n) < 0.8
+    o1 = rng.integers(-4, 4, n).astype(np.int64)
+    o2 = rng.integers(0, 3, n).astype(np.float32)
+    words = [None if rng.random() < 0.15 else "w%d" % i for i in range(n)]
+    v_valid = rng.random(n) < 0.7
+    v = rng.integers(-1000, 1000, n).astype(np.int32)
+    u = rng.integers(0, 1 << 64, n, dtype=np.uint64)
+    return dict(names=names, num=num, num_valid=num_valid, o1=o1, o1_valid=o1_valid, o2=o2, words=words, v=v, v_valid=v_valid, u=u)
+
+
+WRAPPER_FUNCS = {"rn": "row_number", "rk": "rank", "dr": "dense_rank", "c": "count", "prev_w": ("lag", "w", 1), "next_v": ("lead", "v", 2),
+                 "first_w": ("first", "w"), "last_u": ("last", "u"), "seen": ("cumcount", None), "seen_v": ("cumcount", "v"),
+                 "sum_v": ("cumsum", "v"), "min_v": ("cummin", "v"), "max_u": ("cummax", "u"), "sum_u": ("cumsum", "u")}
+
+
+def wrapper_call(fn, t, null_keys, **kw):
+    return fn(WRAPPER_FUNCS, partition_by=[hj.KeyColumn.from_list(t["names"]), hj.KeyColumn(t["num"], t["num_valid"])],
+              order_by=[hj.KeyColumn(t["o1"], t["o1_valid"]), t["o2"]], descending=[True, False], nulls=["first", "last"],
+              cols={"w": hj.KeyColumn.from_list(t["words"]), "v": hj.KeyColumn(t["v"], t["v_valid"]), "u": t["u"]}, null_keys=null_keys, **kw)
+
+
+def wrapper_check(got, t, null_keys):
+    n = len(t["names"])
+    keys = [(t["names"][i], int(t["num"][i]) if t["num_valid"][i] else None) for i in range(n)]
+    cols = {"w": [None if w is None else w.encode() for w in t["words"]], "v": [int(x) if ok else None for x, ok in zip(t["v"], t["v_valid"])],
+            "u": [int(x) for x in t["u"]]}
+    want, n_parts, n_dropped = _loop_reference(keys, [(t["o1"], t["o1_valid"]), (t["o2"], None)], [True, False], ["first", "last"], null_keys, cols,
+                                               WRAPPER_FUNCS)
+    assert (got["n_partitions"], got["null_rows"]) == (n_parts, n_dropped) and got["perm"].size == n - n_dropped
+    for name in ("rn", "rk", "dr", "c"):
+        assert got[name].dtype == U32 and got[name].tolist() == want[name], name
+    for name in ("seen", "seen_v"):
+        assert got[name].dtype == U64 and got[name].tolist() == want[name], name
+    for name in ("prev_w", "first_w"):
+        assert got[name].to_list() == want[name], name
+    for name, dtype in (("next_v", np.int32), ("last_u", U64), ("sum_v", np.int64), ("min_v", np.int64), ("max_u", U64), ("sum_u", U64)):
+        col = got[name]
+        assert isinstance(col, hj.KeyColumn) and col.values.dtype == dtype, (name, col.values.dtype)
+        ok = col.valid if col.valid is not None else np.ones(n, dtype=bool)
+        assert ok.tolist() == [x is not None for x in want[name]], name
+        mod = 1 << (8 * col.values.dtype.itemsize)
+        assert [int(x) % mod for x in col.values[ok]] == [x % mod for x in want[name] if x is not None], name
+    rows = got["perm"].astype(np.int64)
+    assert np.array_equal(np.sort(rows), np.setdiff1d(np.arange(n), np.flatnonzero(got["rn"] == 0)))
