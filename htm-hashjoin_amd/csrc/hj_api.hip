@@ -43,13 +43,8 @@ static int create_common(int device, void* stream, bool own, hj_ctx** out)
               hipHostMalloc(reinterpret_cast<void**>(&c->hPreferred), sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
               hipHostGetDevicePointer(reinterpret_cast<void**>(&c->dPreferred), c->hPreferred, 0) == hipSuccess &&
               c->buf[B_BOUNDS].reserve(c, wave_bounds_bytes(c->nCU)) == HJ_OK &&
-              c->buf[B_PAIRS_CURSOR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              hipMemset(c->buf[B_PAIRS_CURSOR].p, 0, 2 * sizeof(unsigned long long)) == hipSuccess &&
-              c->buf[B_GATHER_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              c->buf[B_GATHER2_CTR].reserve(c, (2 + kGatherMaxCols) * sizeof(unsigned long long)) == HJ_OK &&
-              c->buf[B_VERIFY_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              c->buf[B_WHERE_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK &&
-              c->buf[B_ASOF_CTR].reserve(c, 2 * sizeof(unsigned long long)) == HJ_OK;
+              c->buf[B_CALL_WORDS].reserve(c, CALL_COUNT * kCallWords * sizeof(unsigned long long)) == HJ_OK &&
+              hipMemset(c->buf[B_CALL_WORDS].p, 0, CALL_COUNT * kCallWords * sizeof(unsigned long long)) == hipSuccess;
     for (int i = 0; ok && i < EV_COUNT; ++i) ok = hipEventCreate(&c->time.ev[i]) == hipSuccess;
     for (CallRecord& r : c->call) ok = ok && hipEventCreate(&r.ev[0]) == hipSuccess && hipEventCreate(&r.ev[1]) == hipSuccess;
     if (!ok) { hj_destroy(c); return HJ_ERR_HIP; }

@@ -131,7 +131,7 @@ static int prj_probe_join(hj_ctx* c, const char* fn, uint32_t kind, const uint64
     bool planeR;
     if (const int bad = pairs_args(c, fn, kind, state, sSize, sIdxBase, dOutS, dOutR, capacity, &planeR)) return bad;
     if (sSize == 0) return HJ_OK;
-    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
+    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, call_words(c, CALL_PAIRS)};
     return prj_probe(c, kind, dS, sSize, sIdxBase, &out, true);
 }
 

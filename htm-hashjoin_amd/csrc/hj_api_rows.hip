@@ -1,38 +1,82 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
-// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns and sorted by them, the window functions along a permutation, the
-// join conditions beyond equality, the as-of step, and the *_info entry point of every call that has a record (hj_host.h:
-// CallRecord). Host-side glue only.
+// joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns
+// and sorted by them, the window functions along a permutation, the join conditions beyond equality, the as-of step, the
+// reduction over a pair list, and the *_info entry point of every call that has a record (hj_host.h: CallRecord).
+// Host-side glue only, and the same three parts for every recorded call: its checks, which give the message of the first
+// thing wrong; recorded_call, the one frame around its launch; call_info, the one reader of what it left.
 #include "hj_host.h"
 
 using namespace hjapi;
 
 extern "C" {
 
-// Waits for the stream. The last call of `rec` in the common form of the *_info entry points: out[0] = the first counter word the
-// call left at dWords (`bytes` of them, at most 16: one 32-bit total or two 64-bit words; nullptr: none), out[1] = min(out[0], capacity),
-// out[2] = its device time in microseconds, out[3] = the second word. All 0 for a call that was never made, or forgotten since.
-static int call_info(hj_ctx* c, const CallRecord& rec, const void* dWords, size_t bytes, uint64_t out[4])
+// Waits for the stream. The last call of kind `which` in the common form of the *_info entry points: out[0] = the call's
+// first counter word, out[1] = min(out[0], capacity), out[2] = its device time in microseconds, out[3] = the second word.
+// words (kCallWords of them, or nullptr: the kind counts nothing): the kind's block (call_words) as the call left it,
+// copied to the host once and whole; a caller that reports more than two words reads the rest there. dTotal (or nullptr): the
+// first word is this 32-bit total in a workspace instead, and out[3] is 0. All 0, words too, for a call that was never
+// made, or forgotten since.
+static int call_info(hj_ctx* c, Call which, const uint32_t* dTotal, unsigned long long* words, uint64_t out[4])
 {
+    const CallRecord& rec = c->call[which];
     HJ_HIP(c, hipSetDevice(c->device));
     HJ_HIP(c, hipStreamSynchronize(c->stream));
     out[0] = out[1] = out[2] = out[3] = 0;
+    for (uint32_t i = 0; words && i < kCallWords; ++i) words[i] = 0;
     if (!rec.called) return HJ_OK;
-    unsigned long long words[2] = {0, 0};
-    if (dWords) HJ_HIP(c, hipMemcpy(words, dWords, bytes, hipMemcpyDeviceToHost));
+    uint32_t total = 0;
+    if (dTotal) HJ_HIP(c, hipMemcpy(&total, dTotal, sizeof(total), hipMemcpyDeviceToHost));
+    if (words) HJ_HIP(c, hipMemcpy(words, call_words(c, which), kCallWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     float ms = 0;
     if (!rec.timed || hipEventElapsedTime(&ms, rec.ev[0], rec.ev[1]) != hipSuccess) ms = 0;
-    out[0] = words[0];
-    out[1] = words[0] < rec.capacity ? words[0] : rec.capacity;
+    out[0] = dTotal ? total : words ? words[0] : 0;
+    out[1] = out[0] < rec.capacity ? out[0] : rec.capacity;
     out[2] = (uint64_t)((double)ms * 1000.0 + 0.5);
-    out[3] = words[1];
+    out[3] = !dTotal && words ? words[1] : 0;
     return HJ_OK;
 }
+// the kinds whose block holds the two words and nothing else
+static int call_info(hj_ctx* c, Call which, uint64_t out[4])
+{
+    unsigned long long words[kCallWords];       // copied and not looked at again
+    return call_info(c, which, nullptr, words, out);
+}
+
+// The one frame of a recorded call, in the order every entry point has always made its HIP calls: the device; the call's
+// workspace grown (work.bytes 0: it has none); `zero` words of the kind's block zeroed on the stream (0: the launcher zeroes
+// its own, or the kind counts nothing); ev[0]; launch(the kind's block); ev[1] and what *_info is to report (call_end, extra).
+// init says on which side of the zeroing ev[0] stands. INIT_TIMED, in front of it: the calls whose time is "the whole call" --
+// as-of, whose launcher goes on to initialise the caller's best planes, and groups and window, whose launchers fill their
+// workspace and zero their own words. INIT_UNTIMED, behind it: all the others, whose time is their kernels'. The intervals
+// are what the benchmark write-ups under profiles/ report, so a call keeps its side.
+enum Init { INIT_UNTIMED, INIT_TIMED };
+struct Work { Buf b; size_t bytes; };
+constexpr Work kNoWork{B_COUNT, 0};
+struct Facts { uint64_t capacity, rows, extra[4]; };
+extern "C++" {
+template <class Launch>
+static int recorded_call(hj_ctx* c, Call which, uint32_t zero, Init init, Work work, const Facts& facts, Launch&& launch)
+{
+    CallRecord& r = c->call[which];
+    unsigned long long* const words = call_words(c, which);
+    HJ_HIP(c, hipSetDevice(c->device));
+    if (work.bytes)
+        if (const int rc = c->buf[work.b].reserve(c, work.bytes)) return rc;
+    if (init == INIT_TIMED) HJ_HIP(c, hipEventRecord(r.ev[0], c->stream));
+    if (zero) HJ_HIP(c, hipMemsetAsync(words, 0, zero * sizeof(unsigned long long), c->stream));
+    if (init == INIT_UNTIMED) HJ_HIP(c, hipEventRecord(r.ev[0], c->stream));
+    HJ_HIP(c, launch(words));
+    if (const int rc = call_end(c, which, facts.capacity, facts.rows)) return rc;
+    for (int i = 0; i < 4; ++i) r.extra[i] = facts.extra[i];
+    return HJ_OK;
+}
+}  // extern "C++"
 
 int hj_pairs_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
     const CallRecord& r = c->call[CALL_PAIRS];      // the cursor = rows found; LEFT's unmatched S tuples
-    if (const int rc = call_info(c, r, c->buf[B_PAIRS_CURSOR].p, 16, out)) return rc;
+    if (const int rc = call_info(c, CALL_PAIRS, out)) return rc;
     // unmatched S tuples of the call: SEMI wrote one row per matched tuple, ANTI one per unmatched one
     if (r.kind != HJ_JOIN_LEFT) out[3] = r.kind == HJ_JOIN_SEMI ? r.rows - out[0] : r.kind == HJ_JOIN_ANTI ? out[0] : 0;
     return HJ_OK;
@@ -62,11 +106,10 @@ int hj_r_rows_dev(hj_ctx* c, uint32_t which, uint32_t* dOutR, uint64_t capacity)
     if (const int rc = marks_state(c, "hj_r_rows_dev")) return rc;
     if (which > HJ_R_MATCHED) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: which must be HJ_R_UNMATCHED or HJ_R_MATCHED");
     if (capacity && !dOutR) return fail(c, HJ_ERR_INVALID, "hj_r_rows_dev: output pointer NULL with capacity > 0");
-    HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_R_ROWS].ev[0], c->stream));
     const RMarks mk{c->buf[B_R_MARKS].as<uint32_t>(), (uint32_t)c->marks.base, (uint32_t)c->marks.rows};
-    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOutR, capacity, c->buf[B_R_SWEEP].as<uint32_t>(), c->stream));
-    return call_end(c, CALL_R_ROWS, capacity, c->marks.rows);
+    return recorded_call(c, CALL_R_ROWS, 0, INIT_UNTIMED, kNoWork, Facts{capacity, c->marks.rows}, [&](unsigned long long*) {
+        return launch_r_sweep(mk, which == HJ_R_MATCHED, dOutR, capacity, c->buf[B_R_SWEEP].as<uint32_t>(), c->stream);
+    });
 }
 
 int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
@@ -74,8 +117,7 @@ int hj_r_rows_info(hj_ctx* c, uint64_t out[4])
     HJ_ENTER(c, out);
     if (const int rc = marks_state(c, "hj_r_rows_info")) return rc;
     // the word behind the block counts: their total after the scan
-    const CallRecord& r = c->call[CALL_R_ROWS];
-    if (const int rc = call_info(c, r, c->buf[B_R_SWEEP].as<uint32_t>() + r_sweep_blocks(c->marks.rows), sizeof(uint32_t), out)) return rc;
+    if (const int rc = call_info(c, CALL_R_ROWS, c->buf[B_R_SWEEP].as<uint32_t>() + r_sweep_blocks(c->marks.rows), nullptr, out)) return rc;
     out[3] = c->marks.rows;                     // also with no hj_r_rows_dev since the build
     return HJ_OK;
 }
@@ -114,19 +156,15 @@ int hj_gather_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t rowB
         k.col[i] = GatherCol{col.src, col.dst, col.width, 0, {col.fill[0], col.fill[1]}};
     }
     if (nRows == 0) return HJ_OK;
-    HJ_HIP(c, hipSetDevice(c->device));
-    unsigned long long* const counts = c->buf[B_GATHER_CTR].as<unsigned long long>();
-    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_GATHER].ev[0], c->stream));
-    HJ_HIP(c, launch_gather(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, c->stream));
-    return call_end(c, CALL_GATHER, 0, nRows);
+    return recorded_call(c, CALL_GATHER, 2, INIT_UNTIMED, kNoWork, Facts{0, nRows},
+                         [&](unsigned long long* counts) { return launch_gather(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, c->stream); });
 }
 
 int hj_gather_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
     const CallRecord& r = c->call[CALL_GATHER];     // NULL rows, out-of-range entries
-    if (const int rc = call_info(c, r, c->buf[B_GATHER_CTR].p, 16, out)) return rc;
+    if (const int rc = call_info(c, CALL_GATHER, out)) return rc;
     out[1] = out[0]; out[0] = r.rows;
     return HJ_OK;
 }
@@ -176,29 +214,23 @@ int hj_gather2_dev(hj_ctx* c, const uint32_t* dMap, uint64_t nRows, uint32_t row
     GatherCols2 k{};
     if (const char* what = gather_cols2_error(cols, nCols, nRows, srcRows, dValid, &k)) return fail(c, HJ_ERR_INVALID, "hj_gather2_dev", what);
     if (nRows == 0) return HJ_OK;
-    HJ_HIP(c, hipSetDevice(c->device));
     bool varlen = false;
     for (uint32_t i = 0; i < nCols; ++i) varlen = varlen || !k.col[i].width;
-    if (varlen)
-        if (const int rc = c->buf[B_GATHER2_WORK].reserve(c, gather2_work_words(nRows) * sizeof(uint32_t))) return rc;
-    unsigned long long* const counts = c->buf[B_GATHER2_CTR].as<unsigned long long>();
-    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_GATHER2].ev[0], c->stream));
-    HJ_HIP(c, launch_gather2(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, counts + 2, c->buf[B_GATHER2_WORK].as<uint32_t>(), c->stream));
-    return call_end(c, CALL_GATHER2, 0, nRows);
+    const Work work{B_GATHER2_WORK, varlen ? gather2_work_words(nRows) * sizeof(uint32_t) : 0};
+    return recorded_call(c, CALL_GATHER2, 2, INIT_UNTIMED, work, Facts{0, nRows}, [&](unsigned long long* counts) {
+        return launch_gather2(dMap, nRows, rowBase, srcRows, k, nCols, dValid, counts, counts + 2, c->buf[B_GATHER2_WORK].as<uint32_t>(), c->stream);
+    });
 }
 
 int hj_gather2_info(hj_ctx* c, uint64_t out[4 + HJ_GATHER_MAX_COLS])
 {
     HJ_ENTER(c, out);
     const CallRecord& r = c->call[CALL_GATHER2];
+    unsigned long long words[kCallWords];
     for (uint32_t i = 0; i < HJ_GATHER_MAX_COLS; ++i) out[4 + i] = 0;
-    if (const int rc = call_info(c, r, c->buf[B_GATHER2_CTR].p, 16, out)) return rc;
-    out[1] = out[0]; out[0] = r.rows;
-    if (!r.called) { out[0] = 0; return HJ_OK; }
-    unsigned long long totals[HJ_GATHER_MAX_COLS];
-    HJ_HIP(c, hipMemcpy(totals, c->buf[B_GATHER2_CTR].as<unsigned long long>() + 2, sizeof(totals), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < HJ_GATHER_MAX_COLS; ++i) out[4 + i] = totals[i];
+    if (const int rc = call_info(c, CALL_GATHER2, nullptr, words, out)) return rc;
+    out[1] = out[0]; out[0] = r.called ? r.rows : 0;
+    for (uint32_t i = 0; i < HJ_GATHER_MAX_COLS; ++i) out[4 + i] = words[2 + i];
     return HJ_OK;
 }
 
@@ -241,6 +273,27 @@ static const char* key_cols_error(const hj_key_col2* cols, uint32_t nCols, bool 
     return nullptr;
 }
 
+// The pair list and its sink as hj_pairs_verify*_dev, hj_pairs_where_* and hj_pairs_asof_* take them. Checked in two halves,
+// sizes_error in front of a call's columns or terms and ptrs_error behind them: that is the order in which every one of these
+// entry points refuses, and for any combination of bad arguments the first refusal reported is to stay what it was.
+struct PairArgs {
+    const uint32_t *mapS, *mapR; uint64_t nPairs; uint32_t sRowBase; uint64_t sRows, rRows;
+    uint32_t *outS, *outR; uint64_t capacity; uint32_t *sMarks, *rMarks;
+    const char* sizes_error() const
+    {
+        return nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull ? "nPairs, sRows or rRows above 2^32 - 1" : nullptr;
+    }
+    const char* ptrs_error() const
+    {
+        if (nPairs && (!mapS || !mapR)) return "a map NULL with nPairs > 0";
+        if (nPairs && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
+        return nullptr;
+    }
+    // as the launchers and the host twins take them, once the sizes are checked (the host twins have no cursor)
+    PairList list() const { return PairList{mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows}; }
+    PairSink sink(unsigned long long* cursor = nullptr) const { return PairSink{PairsOut{outS, outR, capacity, cursor}, sMarks, rMarks}; }
+};
+
 extern "C++" {      // templates: one body per descriptor
 
 static hj_key_col2 key_col2_of(const hj_key_col& col) { return hj_key_col2{col.s, col.r, nullptr, nullptr, nullptr, nullptr, col.width, 0u}; }
@@ -280,7 +333,7 @@ static int key_hash_dev(hj_ctx* c, const char* fn, const Col* cols, uint32_t nCo
     if (const char* what = key_hash_args(cols, nCols, side, nRows, dOutTuples, &k)) return fail(c, HJ_ERR_INVALID, fn, what);
     if (nRows == 0) return HJ_OK;
     HJ_HIP(c, hipSetDevice(c->device));
-    HJ_HIP(c, launch_key_hash2(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dOutTuples, c->stream));
+    HJ_HIP(c, launch_key_hash2(k, nCols, nRows, effective_mask(keyMask), dOutTuples, c->stream));
     return HJ_OK;
 }
 
@@ -289,34 +342,26 @@ static int key_hash_on_host(const Col* cols, uint32_t nCols, uint32_t side, uint
 {
     KeyCols2 k{};
     if (key_hash_args(cols, nCols, side, nRows, outTuples, &k)) return HJ_ERR_INVALID;
-    key_hash2_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, outTuples);
+    key_hash2_host(k, nCols, nRows, effective_mask(keyMask), outTuples);
     return HJ_OK;
 }
 
 // hj_pairs_verify_dev and hj_pairs_verify2_dev behind their names: one call record and one cursor (hj_verify_info reports
 // the last call of either)
 template <class Col>
-static int pairs_verify_dev(hj_ctx* c, const char* fn, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase,
-                            uint64_t sRows, uint64_t rRows, const Col* cols, uint32_t nCols, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity,
-                            uint32_t* dSMarks, uint32_t* dRMarks)
+static int pairs_verify_dev(hj_ctx* c, const char* fn, const PairArgs& a, const Col* cols, uint32_t nCols)
 {
-    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull)
-        return fail(c, HJ_ERR_INVALID, fn, "nPairs, sRows or rRows above 2^32 - 1");
-    if (const char* what = key_cols_error(cols, nCols, sRows != 0, rRows != 0)) return fail(c, HJ_ERR_INVALID, fn, what);
-    if (nPairs && (!dMapS || !dMapR)) return fail(c, HJ_ERR_INVALID, fn, "a map NULL with nPairs > 0");
-    if (nPairs && capacity && (!dOutS || !dOutR)) return fail(c, HJ_ERR_INVALID, fn, "an output pointer NULL with capacity > 0");
+    if (const char* what = a.sizes_error()) return fail(c, HJ_ERR_INVALID, fn, what);
+    if (const char* what = key_cols_error(cols, nCols, a.sRows != 0, a.rRows != 0)) return fail(c, HJ_ERR_INVALID, fn, what);
+    if (const char* what = a.ptrs_error()) return fail(c, HJ_ERR_INVALID, fn, what);
     KeyCols2SR k{};
     for (uint32_t i = 0; i < nCols; ++i) {
         const hj_key_col2 col = key_col2_of(cols[i]);
         k.s[i] = col.s; k.r[i] = col.r; k.sOff[i] = col.sOffsets; k.rOff[i] = col.rOffsets;
         k.sValid[i] = col.sValid; k.rValid[i] = col.rValid; k.width[i] = col.width; k.flags[i] = col.flags;
     }
-    HJ_HIP(c, hipSetDevice(c->device));
-    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_VERIFY_CTR].as<unsigned long long>()};
-    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_VERIFY].ev[0], c->stream));
-    HJ_HIP(c, launch_pairs_verify2(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nCols, out, dSMarks, dRMarks, c->stream));
-    return call_end(c, CALL_VERIFY, capacity, nPairs);
+    return recorded_call(c, CALL_VERIFY, 2, INIT_UNTIMED, kNoWork, Facts{a.capacity, a.nPairs},
+                         [&](unsigned long long* cursor) { return launch_pairs_verify2(a.list(), k, nCols, a.sink(cursor), c->stream); });
 }
 
 }  // extern "C++"
@@ -337,8 +382,8 @@ int hj_pairs_verify_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR,
                         uint32_t* dSMarks, uint32_t* dRMarks)
 {
     HJ_ENTER(c, true);
-    return pairs_verify_dev(c, "hj_pairs_verify_dev", dMapS, dMapR, nPairs, sRowBase, sRows, rRows, cols, nCols, dOutS, dOutR, capacity, dSMarks,
-                            dRMarks);
+    const PairArgs a{dMapS, dMapR, nPairs, sRowBase, sRows, rRows, dOutS, dOutR, capacity, dSMarks, dRMarks};
+    return pairs_verify_dev(c, "hj_pairs_verify_dev", a, cols, nCols);
 }
 
 int hj_key_hash2_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32_t side, uint64_t nRows, uint32_t keyMask, uint64_t* dOutTuples)
@@ -357,14 +402,14 @@ int hj_pairs_verify2_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR
                          uint32_t* dSMarks, uint32_t* dRMarks)
 {
     HJ_ENTER(c, true);
-    return pairs_verify_dev(c, "hj_pairs_verify2_dev", dMapS, dMapR, nPairs, sRowBase, sRows, rRows, cols, nCols, dOutS, dOutR, capacity, dSMarks,
-                            dRMarks);
+    const PairArgs a{dMapS, dMapR, nPairs, sRowBase, sRows, rRows, dOutS, dOutR, capacity, dSMarks, dRMarks};
+    return pairs_verify_dev(c, "hj_pairs_verify2_dev", a, cols, nCols);
 }
 
 int hj_verify_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
-    return call_info(c, c->call[CALL_VERIFY], c->buf[B_VERIFY_CTR].p, 16, out);     // pairs kept, candidates dropped
+    return call_info(c, CALL_VERIFY, out);          // pairs kept, candidates dropped
 }
 
 // ---- rows of one table grouped by their key columns (hj_groups.hip) ----------
@@ -389,14 +434,10 @@ int hj_key_groups_dev(hj_ctx* c, const hj_key_col2* cols, uint32_t nCols, uint32
     KeyCols2 k{};
     if (const char* what = key_groups_args(cols, nCols, side, nRows, dRep, dGroup, dFirstRows, capacity, &k))
         return fail(c, HJ_ERR_INVALID, "hj_key_groups_dev", what);
-    HJ_HIP(c, hipSetDevice(c->device));
-    if (const int rc = c->buf[B_GROUPS_CTR].reserve(c, 4 * sizeof(unsigned long long))) return rc;
-    if (nRows)
-        if (const int rc = c->buf[B_GROUPS_WORK].reserve(c, key_groups_work_bytes(nRows))) return rc;
-    HJ_HIP(c, hipEventRecord(c->call[CALL_GROUPS].ev[0], c->stream));          // the whole call: the table's fill too
-    HJ_HIP(c, launch_key_groups(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, dRep, dGroup, dFirstRows, capacity, c->buf[B_GROUPS_WORK].p,
-                                c->buf[B_GROUPS_CTR].as<unsigned long long>(), c->stream));
-    return call_end(c, CALL_GROUPS, capacity, nRows);
+    const Work work{B_GROUPS_WORK, nRows ? key_groups_work_bytes(nRows) : 0};
+    return recorded_call(c, CALL_GROUPS, 0, INIT_TIMED, work, Facts{capacity, nRows}, [&](unsigned long long* ctr) {
+        return launch_key_groups(k, nCols, nRows, effective_mask(keyMask), dRep, dGroup, dFirstRows, capacity, c->buf[B_GROUPS_WORK].p, ctr, c->stream);
+    });
 }
 
 int hj_key_groups_info(hj_ctx* c, uint64_t out[8])
@@ -406,10 +447,9 @@ int hj_key_groups_info(hj_ctx* c, uint64_t out[8])
     for (int i = 4; i < 8; ++i) out[i] = 0;
     // the word behind the sweep's block counts: the first rows it found (no row: no work was enqueued and there is no word)
     const uint32_t* const total = r.called && r.rows ? key_groups_total(c->buf[B_GROUPS_WORK].p, r.rows) : nullptr;
-    if (const int rc = call_info(c, r, total, sizeof(uint32_t), out)) return rc;
-    if (!r.called || !r.rows) return HJ_OK;
-    unsigned long long ctr[4];
-    HJ_HIP(c, hipMemcpy(ctr, c->buf[B_GROUPS_CTR].p, sizeof(ctr), hipMemcpyDeviceToHost));
+    unsigned long long ctr[kCallWords];
+    if (const int rc = call_info(c, CALL_GROUPS, total, total ? ctr : nullptr, out)) return rc;
+    if (!total) return HJ_OK;
     out[3] = ctr[2]; out[4] = key_groups_slots(r.rows); out[5] = ctr[0]; out[6] = ctr[1]; out[7] = ctr[3];
     return HJ_OK;
 }
@@ -419,8 +459,19 @@ int hj_key_groups_host(const hj_key_col2* cols, uint32_t nCols, uint32_t side, u
 {
     KeyCols2 k{};
     if (!out || key_groups_args(cols, nCols, side, nRows, rep, group, firstRows, capacity, &k)) return HJ_ERR_INVALID;
-    key_groups_host(k, nCols, nRows, keyMask ? keyMask : 0xFFFFFFFFu, rep, group, firstRows, capacity, out);
+    key_groups_host(k, nCols, nRows, effective_mask(keyMask), rep, group, firstRows, capacity, out);
     return HJ_OK;
+}
+
+// ---- typed value columns: the sort's, and the terms of where and as-of --------
+// A column of hj_val_type values and the widths the type has. opError: a term's own refusal of its op, which ranks between
+// the two checks; nullptr for a column, and for a term whose op is in order.
+static const char* val_col_error(uint32_t type, uint32_t width, const char* opError = nullptr)
+{
+    if (type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
+    if (opError) return opError;
+    const bool widthOk = width == 4 || width == 8 || (type != HJ_VAL_FLOAT && (width == 1 || width == 2));
+    return widthOk ? nullptr : "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
 }
 
 // ---- rows in the order of their columns (hj_sort.hip) -------------------------
@@ -430,9 +481,7 @@ static const char* sort_cols_error(const hj_sort_col* cols, uint32_t nCols, uint
 {
     for (uint32_t i = 0; i < nCols; ++i) {
         const hj_sort_col& col = cols[i];
-        if (col.type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
-        const bool widthOk = col.width == 4 || col.width == 8 || (col.type != HJ_VAL_FLOAT && (col.width == 1 || col.width == 2));
-        if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
+        if (const char* what = val_col_error(col.type, col.width)) return what;
         if (col.flags & ~(HJ_SORT_DESC | HJ_SORT_NULLS_FIRST)) return "hj_sort_col.flags has bits other than HJ_SORT_DESC and HJ_SORT_NULLS_FIRST";
         if (col.reserved) return "hj_sort_col.reserved must be 0";
         if (nRows && !col_ptr_ok(col.values, col.width)) return "a values pointer that is NULL or not aligned to its width";
@@ -457,15 +506,10 @@ int hj_sort_rows_dev(hj_ctx* c, const hj_sort_col* cols, uint32_t nCols, uint64_
     HJ_ENTER(c, true);
     SortCols k{};
     if (const char* what = sort_args(cols, nCols, nRows, dPerm, &k)) return fail(c, HJ_ERR_INVALID, "hj_sort_rows_dev", what);
-    HJ_HIP(c, hipSetDevice(c->device));
     const SortLayout l = sort_layout(nRows, sort_key_bytes(k, nCols));
-    if (nRows)
-        if (const int rc = c->buf[B_SORT_WORK].reserve(c, l.bytes)) return rc;
-    HJ_HIP(c, hipEventRecord(c->call[CALL_SORT].ev[0], c->stream));
-    HJ_HIP(c, launch_sort_rows(k, nCols, nRows, dPerm, c->buf[B_SORT_WORK].p, c->stream));
-    c->sort = {};
-    if (nRows) c->sort = {sort_passes(k, nCols), l.chunks, l.chunkRows, l.bytes};
-    return call_end(c, CALL_SORT, 0, nRows);
+    const Facts facts = nRows ? Facts{0, nRows, {sort_passes(k, nCols), l.chunks, l.chunkRows, l.bytes}} : Facts{};
+    return recorded_call(c, CALL_SORT, 0, INIT_UNTIMED, Work{B_SORT_WORK, nRows ? l.bytes : 0}, facts,
+                         [&](unsigned long long*) { return launch_sort_rows(k, nCols, nRows, dPerm, c->buf[B_SORT_WORK].p, c->stream); });
 }
 
 int hj_sort_rows_info(hj_ctx* c, uint64_t out[8])
@@ -473,10 +517,10 @@ int hj_sort_rows_info(hj_ctx* c, uint64_t out[8])
     HJ_ENTER(c, out);
     const CallRecord& r = c->call[CALL_SORT];
     for (int i = 4; i < 8; ++i) out[i] = 0;
-    if (const int rc = call_info(c, r, nullptr, 0, out)) return rc;
+    if (const int rc = call_info(c, CALL_SORT, nullptr, nullptr, out)) return rc;
     if (!r.called || !r.rows) { out[2] = 0; return HJ_OK; }     // no row: nothing was enqueued between the two events
-    out[0] = r.rows; out[1] = c->sort.passes; out[3] = 0;       // no pass is ever skipped
-    out[4] = c->sort.chunks; out[5] = c->sort.chunkRows; out[6] = c->sort.bytes;
+    out[0] = r.rows; out[1] = r.extra[0]; out[3] = 0;           // the passes: none is ever skipped
+    out[4] = r.extra[1]; out[5] = r.extra[2]; out[6] = r.extra[3];
     return HJ_OK;
 }
 
@@ -539,17 +583,11 @@ int hj_window_rows_dev(hj_ctx* c, const uint32_t* dPerm, uint64_t nPos, uint64_t
     WinFuncs w{};
     if (const char* what = window_args(dPerm, nPos, nRows, dPart, order, nOrder, funcs, nFuncs, &k, &w))
         return fail(c, HJ_ERR_INVALID, "hj_window_rows_dev", what);
-    HJ_HIP(c, hipSetDevice(c->device));
     const WindowLayout l = window_layout(nPos);
-    if (const int rc = c->buf[B_WINDOW_CTR].reserve(c, 3 * sizeof(unsigned long long))) return rc;
-    if (nPos)
-        if (const int rc = c->buf[B_WINDOW_WORK].reserve(c, l.bytes)) return rc;
-    HJ_HIP(c, hipEventRecord(c->call[CALL_WINDOW].ev[0], c->stream));
-    HJ_HIP(c, launch_window_rows(dPerm, nPos, (uint32_t)nRows, dPart, k, nOrder, w, nFuncs, c->buf[B_WINDOW_WORK].p,
-                                 c->buf[B_WINDOW_CTR].as<unsigned long long>(), c->stream));
-    c->window = {};
-    if (nPos) c->window = {l.chunks, l.bytes};
-    return call_end(c, CALL_WINDOW, 0, nPos);
+    const Facts facts = nPos ? Facts{0, nPos, {l.chunks, l.bytes}} : Facts{};
+    return recorded_call(c, CALL_WINDOW, 0, INIT_TIMED, Work{B_WINDOW_WORK, nPos ? l.bytes : 0}, facts, [&](unsigned long long* totals) {
+        return launch_window_rows(dPerm, nPos, (uint32_t)nRows, dPart, k, nOrder, w, nFuncs, c->buf[B_WINDOW_WORK].p, totals, c->stream);
+    });
 }
 
 int hj_window_rows_info(hj_ctx* c, uint64_t out[8])
@@ -558,13 +596,12 @@ int hj_window_rows_info(hj_ctx* c, uint64_t out[8])
     const CallRecord& r = c->call[CALL_WINDOW];
     for (int i = 4; i < 8; ++i) out[i] = 0;
     uint64_t t[4];
-    if (const int rc = call_info(c, r, nullptr, 0, t)) return rc;
+    unsigned long long totals[kCallWords];
+    if (const int rc = call_info(c, CALL_WINDOW, nullptr, r.rows ? totals : nullptr, t)) return rc;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (!r.called || !r.rows) return HJ_OK;                     // no position: nothing was enqueued between the two events
-    unsigned long long totals[3];
-    HJ_HIP(c, hipMemcpy(totals, c->buf[B_WINDOW_CTR].p, sizeof(totals), hipMemcpyDeviceToHost));
     out[0] = r.rows; out[1] = totals[0]; out[2] = totals[1]; out[3] = t[2]; out[4] = totals[2];
-    out[5] = c->window.chunks; out[6] = c->window.bytes;
+    out[5] = r.extra[0]; out[6] = r.extra[1];
     return HJ_OK;
 }
 
@@ -593,30 +630,34 @@ int hj_window_layout_info(uint64_t nPos, uint64_t out[4])
 }
 
 // ---- join conditions beyond equality (hj_where.hip) --------------------------
-// hj_pairs_where_dev's and hj_pairs_where_host's arguments -> the kernel's terms; the message of what is wrong, or nullptr
-static const char* where_args(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint64_t sRows, uint64_t rRows,
-                              const hj_where_term* terms, uint32_t nTerms, const uint32_t* outS, const uint32_t* outR, uint64_t capacity,
-                              WhereTerms* k)
+// What the condition step and the as-of step refuse of one term: hj_asof_term has hj_where_term's fields. opError: the step's
+// own rule for the op (val_col_error); reservedError: the text with the step's struct name.
+extern "C++" {
+template <class Term>
+static const char* term_error(const Term& t, const char* opError, const char* reservedError, const PairArgs& a)
 {
-    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull) return "nPairs, sRows or rRows above 2^32 - 1";
+    if (const char* what = val_col_error(t.type, t.width, opError)) return what;
+    if (t.reserved) return reservedError;
+    if (a.sRows && !col_ptr_ok(t.s, t.width)) return "an s pointer that is NULL or not aligned to its width";
+    if (a.rRows && !col_ptr_ok(t.r, t.width)) return "an r pointer that is NULL or not aligned to its width";
+    if (!word_ptr_ok(t.sValid) || !word_ptr_ok(t.rValid)) return "a validity pointer that is not 4-byte aligned";
+    return nullptr;
+}
+}  // extern "C++"
+
+// hj_pairs_where_dev's and hj_pairs_where_host's arguments -> the kernel's terms; the message of what is wrong, or nullptr
+static const char* where_args(const PairArgs& a, const hj_where_term* terms, uint32_t nTerms, WhereTerms* k)
+{
+    if (const char* what = a.sizes_error()) return what;
     if (nTerms == 0 || nTerms > HJ_WHERE_MAX_TERMS) return "nTerms must be 1 .. HJ_WHERE_MAX_TERMS";
     if (!terms) return "terms NULL";
     for (uint32_t i = 0; i < nTerms; ++i) {
         const hj_where_term& t = terms[i];
-        if (t.type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
-        if (t.op > HJ_CMP_GE) return "op must be an hj_cmp_op";
-        const bool widthOk = t.width == 4 || t.width == 8 || (t.type != HJ_VAL_FLOAT && (t.width == 1 || t.width == 2));
-        if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
-        if (t.reserved) return "hj_where_term.reserved must be 0";
-        if (sRows && !col_ptr_ok(t.s, t.width)) return "an s pointer that is NULL or not aligned to its width";
-        if (rRows && !col_ptr_ok(t.r, t.width)) return "an r pointer that is NULL or not aligned to its width";
-        if (!word_ptr_ok(t.sValid) || !word_ptr_ok(t.rValid)) return "a validity pointer that is not 4-byte aligned";
+        if (const char* what = term_error(t, t.op > HJ_CMP_GE ? "op must be an hj_cmp_op" : nullptr, "hj_where_term.reserved must be 0", a)) return what;
         k->s[i] = t.s; k->r[i] = t.r; k->sValid[i] = t.sValid; k->rValid[i] = t.rValid;
         k->width[i] = t.width; k->type[i] = t.type; k->op[i] = t.op;
     }
-    if (nPairs && (!mapS || !mapR)) return "a map NULL with nPairs > 0";
-    if (nPairs && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
-    return nullptr;
+    return a.ptrs_error();
 }
 
 int hj_pairs_where_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows,
@@ -624,54 +665,42 @@ int hj_pairs_where_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, 
                        uint32_t* dSMarks, uint32_t* dRMarks)
 {
     HJ_ENTER(c, true);
+    const PairArgs a{dMapS, dMapR, nPairs, sRowBase, sRows, rRows, dOutS, dOutR, capacity, dSMarks, dRMarks};
     WhereTerms k{};
-    if (const char* what = where_args(dMapS, dMapR, nPairs, sRows, rRows, terms, nTerms, dOutS, dOutR, capacity, &k))
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_where_dev", what);
-    HJ_HIP(c, hipSetDevice(c->device));
-    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_WHERE_CTR].as<unsigned long long>()};
-    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_WHERE].ev[0], c->stream));
-    HJ_HIP(c, launch_pairs_where(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nTerms, out, dSMarks, dRMarks, c->stream));
-    return call_end(c, CALL_WHERE, capacity, nPairs);
+    if (const char* what = where_args(a, terms, nTerms, &k)) return fail(c, HJ_ERR_INVALID, "hj_pairs_where_dev", what);
+    return recorded_call(c, CALL_WHERE, 2, INIT_UNTIMED, kNoWork, Facts{capacity, nPairs},
+                         [&](unsigned long long* cursor) { return launch_pairs_where(a.list(), k, nTerms, a.sink(cursor), c->stream); });
 }
 
 int hj_where_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
-    return call_info(c, c->call[CALL_WHERE], c->buf[B_WHERE_CTR].p, 16, out);       // pairs kept, pairs dropped
+    return call_info(c, CALL_WHERE, out);           // pairs kept, pairs dropped
 }
 
 int hj_pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows, uint64_t rRows,
                         const hj_where_term* terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
                         uint32_t* rMarks, uint64_t info[4])
 {
+    const PairArgs a{mapS, mapR, nPairs, sRowBase, sRows, rRows, outS, outR, capacity, sMarks, rMarks};
     WhereTerms k{};
-    if (where_args(mapS, mapR, nPairs, sRows, rRows, terms, nTerms, outS, outR, capacity, &k)) return HJ_ERR_INVALID;
-    pairs_where_host(mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, nTerms, outS, outR, capacity, sMarks, rMarks, info);
+    if (where_args(a, terms, nTerms, &k)) return HJ_ERR_INVALID;
+    pairs_where_host(a.list(), k, nTerms, a.sink(), info);
     return HJ_OK;
 }
 
 // ---- as-of joins (hj_asof.hip) -----------------------------------------------
 // hj_pairs_asof_dev's and hj_pairs_asof_host's arguments -> the kernels' term; the message of what is wrong, or nullptr
-static const char* asof_args(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint64_t sRows, uint64_t rRows, const hj_asof_term* t,
-                             const uint64_t* bestVal, const uint32_t* bestRow, const uint32_t* outS, const uint32_t* outR, uint64_t capacity,
-                             AsofTerm* k)
+static const char* asof_args(const PairArgs& a, const hj_asof_term* t, const uint64_t* bestVal, const uint32_t* bestRow, AsofTerm* k)
 {
-    if (nPairs > 0xFFFFFFFFull || sRows > 0xFFFFFFFFull || rRows > 0xFFFFFFFFull) return "nPairs, sRows or rRows above 2^32 - 1";
+    if (const char* what = a.sizes_error()) return what;
     if (!t) return "term NULL";
-    if (t->type > HJ_VAL_FLOAT) return "type must be an hj_val_type";
-    if (t->op != HJ_CMP_GE && t->op != HJ_CMP_GT && t->op != HJ_CMP_LE && t->op != HJ_CMP_LT)
-        return "op must be HJ_CMP_GE, HJ_CMP_GT, HJ_CMP_LE or HJ_CMP_LT";
-    const bool widthOk = t->width == 4 || t->width == 8 || (t->type != HJ_VAL_FLOAT && (t->width == 1 || t->width == 2));
-    if (!widthOk) return "a width that the type does not have (UINT / INT: 1, 2, 4, 8; FLOAT: 4, 8)";
-    if (t->reserved) return "hj_asof_term.reserved must be 0";
-    if (sRows && !col_ptr_ok(t->s, t->width)) return "an s pointer that is NULL or not aligned to its width";
-    if (rRows && !col_ptr_ok(t->r, t->width)) return "an r pointer that is NULL or not aligned to its width";
-    if (!word_ptr_ok(t->sValid) || !word_ptr_ok(t->rValid)) return "a validity pointer that is not 4-byte aligned";
+    const bool opOk = t->op == HJ_CMP_GE || t->op == HJ_CMP_GT || t->op == HJ_CMP_LE || t->op == HJ_CMP_LT;
+    if (const char* what = term_error(*t, opOk ? nullptr : "op must be HJ_CMP_GE, HJ_CMP_GT, HJ_CMP_LE or HJ_CMP_LT", "hj_asof_term.reserved must be 0", a))
+        return what;
     if (!bestVal || (reinterpret_cast<uintptr_t>(bestVal) & 7u)) return "dBestVal NULL or not 8-byte aligned";
     if (!bestRow || !word_ptr_ok(bestRow)) return "dBestRow NULL or not 4-byte aligned";
-    if (nPairs && (!mapS || !mapR)) return "a map NULL with nPairs > 0";
-    if (nPairs && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
+    if (const char* what = a.ptrs_error()) return what;
     *k = AsofTerm{t->s, t->r, t->sValid, t->rValid, t->width, t->type, t->op};
     return nullptr;
 }
@@ -681,31 +710,28 @@ int hj_pairs_asof_dev(hj_ctx* c, const uint32_t* dMapS, const uint32_t* dMapR, u
                       uint64_t capacity, uint32_t* dSMarks, uint32_t* dRMarks)
 {
     HJ_ENTER(c, true);
+    const PairArgs a{dMapS, dMapR, nPairs, sRowBase, sRows, rRows, dOutS, dOutR, capacity, dSMarks, dRMarks};
     AsofTerm k{};
-    if (const char* what = asof_args(dMapS, dMapR, nPairs, sRows, rRows, term, dBestVal, dBestRow, dOutS, dOutR, capacity, &k))
-        return fail(c, HJ_ERR_INVALID, "hj_pairs_asof_dev", what);
-    HJ_HIP(c, hipSetDevice(c->device));
-    const PairsOut out{dOutS, dOutR, capacity, c->buf[B_ASOF_CTR].as<unsigned long long>()};
-    HJ_HIP(c, hipEventRecord(c->call[CALL_ASOF].ev[0], c->stream));          // the whole call: the initialisations too
-    HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, launch_pairs_asof(dMapS, dMapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, reinterpret_cast<unsigned long long*>(dBestVal),
-                                dBestRow, out, dSMarks, dRMarks, c->stream));
-    return call_end(c, CALL_ASOF, capacity, nPairs);
+    if (const char* what = asof_args(a, term, dBestVal, dBestRow, &k)) return fail(c, HJ_ERR_INVALID, "hj_pairs_asof_dev", what);
+    return recorded_call(c, CALL_ASOF, 2, INIT_TIMED, kNoWork, Facts{capacity, nPairs}, [&](unsigned long long* cursor) {
+        return launch_pairs_asof(a.list(), k, reinterpret_cast<unsigned long long*>(dBestVal), dBestRow, a.sink(cursor), c->stream);
+    });
 }
 
 int hj_asof_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
-    return call_info(c, c->call[CALL_ASOF], c->buf[B_ASOF_CTR].p, 16, out);        // pairs kept, pairs dropped
+    return call_info(c, CALL_ASOF, out);            // pairs kept, pairs dropped
 }
 
 int hj_pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint64_t sRows, uint64_t rRows,
                        const hj_asof_term* term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
                        uint32_t* sMarks, uint32_t* rMarks, uint64_t info[4])
 {
+    const PairArgs a{mapS, mapR, nPairs, sRowBase, sRows, rRows, outS, outR, capacity, sMarks, rMarks};
     AsofTerm k{};
-    if (asof_args(mapS, mapR, nPairs, sRows, rRows, term, bestVal, bestRow, outS, outR, capacity, &k)) return HJ_ERR_INVALID;
-    pairs_asof_host(mapS, mapR, nPairs, sRowBase, (uint32_t)sRows, (uint32_t)rRows, k, bestVal, bestRow, outS, outR, capacity, sMarks, rMarks, info);
+    if (asof_args(a, term, bestVal, bestRow, &k)) return HJ_ERR_INVALID;
+    pairs_asof_host(a.list(), k, bestVal, bestRow, a.sink(), info);
     return HJ_OK;
 }
 
@@ -737,21 +763,17 @@ int hj_pairs_agg_dev(hj_ctx* c, const uint32_t* dMapG, const uint32_t* dMapV, ui
         k.src.p[i] = col.src; k.src.valid[i] = col.srcValid; k.acc[i] = static_cast<unsigned long long*>(col.acc);
         k.ops.op[i] = col.op; k.ops.width[i] = col.width; k.ops.sgn[i] = col.flags & HJ_AGG_SIGNED;
     }
-    HJ_HIP(c, hipSetDevice(c->device));
-    if (const int rc = c->buf[B_PAIRS_AGG_CTR].reserve(c, 2 * sizeof(unsigned long long))) return rc;
-    unsigned long long* const counts = c->buf[B_PAIRS_AGG_CTR].as<unsigned long long>();
-    HJ_HIP(c, hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    HJ_HIP(c, hipEventRecord(c->call[CALL_PAIRS_AGG].ev[0], c->stream));
-    HJ_HIP(c, launch_pairs_agg(dMapG, dMapV, nPairs, gBase, (uint32_t)gRows, vBase, (uint32_t)vRows, k, nCols,
-                               reinterpret_cast<unsigned long long*>(dCount), counts, c->stream));
-    return call_end(c, CALL_PAIRS_AGG, 0, nPairs);
+    return recorded_call(c, CALL_PAIRS_AGG, 2, INIT_UNTIMED, kNoWork, Facts{0, nPairs}, [&](unsigned long long* counts) {
+        return launch_pairs_agg(dMapG, dMapV, nPairs, gBase, (uint32_t)gRows, vBase, (uint32_t)vRows, k, nCols,
+                                reinterpret_cast<unsigned long long*>(dCount), counts, c->stream);
+    });
 }
 
 int hj_pairs_agg_info(hj_ctx* c, uint64_t out[4])
 {
     HJ_ENTER(c, out);
     const CallRecord& r = c->call[CALL_PAIRS_AGG];  // pairs applied, pairs skipped
-    if (const int rc = call_info(c, r, c->buf[B_PAIRS_AGG_CTR].p, 16, out)) return rc;
+    if (const int rc = call_info(c, CALL_PAIRS_AGG, out)) return rc;
     out[1] = out[0]; out[0] = r.called ? r.rows : 0;
     return HJ_OK;
 }
@@ -764,13 +786,12 @@ int hj_mark_rows_dev(hj_ctx* c, const uint32_t* dMarks, uint64_t rows, uint32_t 
         return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: rows or rowBase + rows above 2^32 - 1");
     if (rows && !dMarks) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: dMarks NULL with rows > 0");
     if (rows && capacity && !dOut) return fail(c, HJ_ERR_INVALID, "hj_mark_rows_dev: output pointer NULL with capacity > 0");
-    HJ_HIP(c, hipSetDevice(c->device));
-    if (const int rc = c->buf[B_MARK_SWEEP].reserve(c, r_sweep_count_words(rows) * sizeof(uint32_t))) return rc;
-    HJ_HIP(c, hipEventRecord(c->call[CALL_MARK_ROWS].ev[0], c->stream));
     // the sweep reads the plane and never writes it
     const RMarks mk{const_cast<uint32_t*>(dMarks), rowBase, (uint32_t)rows};
-    HJ_HIP(c, launch_r_sweep(mk, which == HJ_R_MATCHED, dOut, capacity, c->buf[B_MARK_SWEEP].as<uint32_t>(), c->stream));
-    return call_end(c, CALL_MARK_ROWS, capacity, rows);
+    const Work work{B_MARK_SWEEP, r_sweep_count_words(rows) * sizeof(uint32_t)};
+    return recorded_call(c, CALL_MARK_ROWS, 0, INIT_UNTIMED, work, Facts{capacity, rows}, [&](unsigned long long*) {
+        return launch_r_sweep(mk, which == HJ_R_MATCHED, dOut, capacity, c->buf[B_MARK_SWEEP].as<uint32_t>(), c->stream);
+    });
 }
 
 int hj_mark_rows_info(hj_ctx* c, uint64_t out[4])
@@ -779,7 +800,7 @@ int hj_mark_rows_info(hj_ctx* c, uint64_t out[4])
     // the word behind the block counts: their total after the scan (no block: no row)
     const CallRecord& r = c->call[CALL_MARK_ROWS];
     const uint32_t* const total = r.rows ? c->buf[B_MARK_SWEEP].as<uint32_t>() + r_sweep_blocks(r.rows) : nullptr;
-    if (const int rc = call_info(c, r, total, sizeof(uint32_t), out)) return rc;
+    if (const int rc = call_info(c, CALL_MARK_ROWS, total, nullptr, out)) return rc;
     out[3] = r.rows;
     return HJ_OK;
 }

@@ -342,7 +342,7 @@ static int probe_join(hj_ctx* c, const char* fn, uint32_t kind, const uint64_t* 
     HJ_HIP(c, hipSetDevice(c->device));
     c->op.streamAtBuildEnd = false;
     int rc;
-    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, c->buf[B_PAIRS_CURSOR].as<unsigned long long>()};
+    const PairsOut out{dOutS, planeR ? dOutR : nullptr, capacity, call_words(c, CALL_PAIRS)};
     HJ_HIP(c, hipMemsetAsync(out.cursor, 0, 2 * sizeof(unsigned long long), c->stream));
     HJ_HIP(c, hipEventRecord(c->call[CALL_PAIRS].ev[0], c->stream));
     const uint64_t* const table = c->buf[B_TABLE].as<uint64_t>();

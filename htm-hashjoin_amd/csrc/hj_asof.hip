@@ -204,54 +204,40 @@ k_asof_keep(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ mapR
     mark_plane<kBlock>(st.s, kept, sMarks);                           // the stage is still as it was flushed
 }
 
-hipError_t launch_pairs_asof(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                             uint32_t rRows, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, PairsOut out,
-                             uint32_t* sMarks, uint32_t* rMarks, hipStream_t s)
+hipError_t launch_pairs_asof(const PairList& in, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, const PairSink& to,
+                             hipStream_t s)
 {
     hipError_t e;
-    if (sRows) {
-        if ((e = hipMemsetAsync(bestVal, 0, (size_t)sRows * sizeof(unsigned long long), s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(bestRow, 0xFF, (size_t)sRows * sizeof(uint32_t), s)) != hipSuccess) return e;
+    if (in.sRows) {
+        if ((e = hipMemsetAsync(bestVal, 0, (size_t)in.sRows * sizeof(unsigned long long), s)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(bestRow, 0xFF, (size_t)in.sRows * sizeof(uint32_t), s)) != hipSuccess) return e;
     }
-    if (nPairs == 0) return hipSuccess;
-    if (sRows && rRows) {       // else every pair is dropped: pass 3 counts them
-        const dim3 grid((uint32_t)((nPairs + kFilterBlockPairs - 1) / kFilterBlockPairs));
+    if (in.n == 0) return hipSuccess;
+    if (in.sRows && in.rRows) {       // else every pair is dropped: pass 3 counts them
+        const dim3 grid((uint32_t)((in.n + kFilterBlockPairs - 1) / kFilterBlockPairs));
         const bool valid = term.sValid || term.rValid;
-        hipLaunchKernelGGL(valid ? k_asof_best<true> : k_asof_best<false>, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows,
-                           rRows, term, bestVal);
-        hipLaunchKernelGGL(valid ? k_asof_row<true> : k_asof_row<false>, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows,
-                           rRows, term, static_cast<const unsigned long long*>(bestVal), bestRow);
+        hipLaunchKernelGGL(valid ? k_asof_best<true> : k_asof_best<false>, grid, dim3(kBlock), 0, s, in.mapS, in.mapR, in.n, in.sRowBase, in.sRows,
+                           in.rRows, term, bestVal);
+        hipLaunchKernelGGL(valid ? k_asof_row<true> : k_asof_row<false>, grid, dim3(kBlock), 0, s, in.mapS, in.mapR, in.n, in.sRowBase, in.sRows,
+                           in.rRows, term, static_cast<const unsigned long long*>(bestVal), bestRow);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    return launch_pair_filter(k_asof_keep, mapS, mapR, nPairs, sRowBase, sRows, rRows, static_cast<const uint32_t*>(bestRow), 0u, out, sMarks,
-                              rMarks, s);
+    return launch_pair_filter(k_asof_keep, in, static_cast<const uint32_t*>(bestRow), 0u, to, s);
 }
 
-void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
-                     const AsofTerm& t, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
-                     uint32_t* sMarks, uint32_t* rMarks, uint64_t* info)
+void pairs_asof_host(const PairList& in, const AsofTerm& t, uint64_t* bestVal, uint32_t* bestRow, const PairSink& to, uint64_t* info)
 {
-    for (uint32_t i = 0; i < sRows; ++i) { bestVal[i] = 0; bestRow[i] = kNoRow; }
-    uint64_t kept = 0, dropped = 0;
-    for (uint64_t k = 0; k < nPairs; ++k) {
-        if (dropped_pair(mapS[k], mapR[k], sRowBase, sRows, rRows)) { ++dropped; continue; }
-        const uint32_t si = mapS[k] - sRowBase, ri = mapR[k];
+    for (uint32_t i = 0; i < in.sRows; ++i) { bestVal[i] = 0; bestRow[i] = kNoRow; }
+    for (uint64_t k = 0; k < in.n; ++k) {
+        if (dropped_pair(in.mapS[k], in.mapR[k], in.sRowBase, in.sRows, in.rRows)) continue;
+        const uint32_t si = in.mapS[k] - in.sRowBase, ri = in.mapR[k];
         const bool okS = !t.sValid || valid_bit(t.sValid, si), okR = !t.rValid || valid_bit(t.rValid, ri);
-        const uint64_t b = where_elem_host(t.r, t.width, ri);
-        if (!okS || !okR || !where_holds(t.type, t.width, t.op, where_elem_host(t.s, t.width, si), b)) continue;
+        const uint64_t b = col_elem(t.r, t.width, ri);
+        if (!okS || !okR || !where_holds(t.type, t.width, t.op, col_elem(t.s, t.width, si), b)) continue;
         const uint64_t key = asof_key(t.type, t.width, t.op, b);
         if (bestRow[si] == kNoRow || key > bestVal[si] || (key == bestVal[si] && ri < bestRow[si])) { bestVal[si] = key; bestRow[si] = ri; }
     }
-    for (uint64_t k = 0; k < nPairs; ++k) {
-        if (dropped_pair(mapS[k], mapR[k], sRowBase, sRows, rRows)) continue;
-        const uint32_t es = mapS[k], er = mapR[k], si = es - sRowBase;
-        if (bestRow[si] != er) continue;
-        if (kept < capacity) { outS[kept] = es; outR[kept] = er; }
-        if (sMarks) set_mark_bit(sMarks, si);
-        if (rMarks) set_mark_bit(rMarks, er);
-        ++kept;
-    }
-    if (info) { info[0] = kept; info[1] = kept < capacity ? kept : capacity; info[2] = 0; info[3] = dropped; }
+    pairs_keep_host(in, to, info, [&](uint32_t si, uint32_t ri) { return bestRow[si] == ri; });
 }
 
 }  // namespace hj

@@ -54,9 +54,9 @@ hipError_t launch_gather2(const uint32_t* map, uint64_t nRows, uint32_t rowBase,
 // launch_key_hash2: out[i] = the join word of row i (the header's hash over the row's key columns, & mask) as an 8-byte
 // tuple. mask is the effective one (never 0). nRows is also what bounds the validity words the hash reads: ceil(nRows / 32).
 // launch_pairs_verify2: candidate pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose key columns are equal as the header
-// defines it, to `out` as the pairs kernels write theirs (out.cursor: two 64-bit words, zeroed before the launch: kept
+// defines it, to `to.out` as the pairs kernels write theirs (its cursor: two 64-bit words, zeroed before the launch: kept
 // pairs, then the candidates dropped as HJ_NO_ROW or outside sRows / rRows, which are never dereferenced). Every kept pair
-// sets bit s of sMarks and bit r of rMarks (RMarks' layout; either may be null).
+// sets bit s of to.sMarks and bit r of to.rMarks.
 // The caller has checked what the header says the entry points refuse, and nRows, nPairs <= 2^32 - 1.
 constexpr uint32_t kKeyMaxCols = 4;           // HJ_KEY_MAX_COLS
 struct KeyCols2 { const void* p[kKeyMaxCols]; const uint32_t* off[kKeyMaxCols]; const uint32_t* valid[kKeyMaxCols];
@@ -66,9 +66,7 @@ struct KeyCols2SR { const void* s[kKeyMaxCols]; const void* r[kKeyMaxCols]; cons
 constexpr uint32_t kKeyNullsEqual = 1u;       // HJ_KEY_NULLS_EQUAL
 hipError_t launch_key_hash2(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out, hipStream_t s);
 void key_hash2_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32_t mask, uint64_t* out);   // the same body in a host loop
-hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                                uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
-                                hipStream_t s);
+hipError_t launch_pairs_verify2(const PairList& in, const KeyCols2SR& cols, uint32_t nCols, const PairSink& to, hipStream_t s);
 
 // ---- rows of one table grouped by their key columns (defined in hj_groups.hip) ----
 // launch_key_groups: rep[i] = the lowest row with row i's key (kNoRow: NULL-keyed), firstRows = the rows with rep[i] == i,
@@ -96,16 +94,12 @@ constexpr uint32_t kCmpEq = 0, kCmpNe = 1, kCmpLt = 2, kCmpLe = 3, kCmpGt = 4, k
 constexpr uint32_t kValUint = 0, kValInt = 1, kValFloat = 2;                                  // hj_val_type
 struct WhereTerms { const void* s[kWhereMaxTerms]; const void* r[kWhereMaxTerms]; const uint32_t* sValid[kWhereMaxTerms];
                     const uint32_t* rValid[kWhereMaxTerms]; uint32_t width[kWhereMaxTerms], type[kWhereMaxTerms], op[kWhereMaxTerms]; };
-// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `out` as launch_pairs_verify2 writes its kept pairs
-// (out.cursor: two 64-bit words, zeroed before the launch: kept pairs, then the pairs dropped as HJ_NO_ROW or outside sRows /
+// Pairs (mapS[k] - sRowBase, mapR[k]) -> the pairs whose terms all hold, to `to.out` as launch_pairs_verify2 writes its kept pairs
+// (its cursor: two 64-bit words, zeroed before the launch: kept pairs, then the pairs dropped as HJ_NO_ROW or outside sRows /
 // rRows, which are never dereferenced); the marks as there. The caller has checked the terms and nPairs <= 2^32 - 1.
-hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                              uint32_t rRows, const WhereTerms& terms, uint32_t nTerms, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
-                              hipStream_t s);
+hipError_t launch_pairs_where(const PairList& in, const WhereTerms& terms, uint32_t nTerms, const PairSink& to, hipStream_t s);
 // the same pairs in a host loop over host pointers, the kept ones in input order; info: kept, written, 0, dropped (may be null)
-void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
-                      const WhereTerms& terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
-                      uint32_t* rMarks, uint64_t* info);
+void pairs_where_host(const PairList& in, const WhereTerms& terms, uint32_t nTerms, const PairSink& to, uint64_t* info);
 
 // What the condition step (hj_where.hip) and the as-of step (hj_asof.hip) share: how two elements compare, how one orders,
 // and a term's loads for the lane's pairs of the pair-filter frame.
@@ -186,12 +180,34 @@ inline bool dropped_pair(uint32_t es, uint32_t er, uint32_t sRowBase, uint32_t s
     return es == kNoRow || er == kNoRow || es - sRowBase >= sRows || er >= rRows;
 }
 
-// element i of a column of `width` bytes, zero-extended (the host loops)
-inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
+// element i of a column of `width` bytes, zero-extended; the pointer is aligned to the width (the host loops, and win_peers)
+__host__ __device__ __forceinline__ uint64_t col_elem(const void* col, uint32_t width, uint32_t i)
 {
-    uint64_t v = 0;
-    memcpy(&v, static_cast<const uint8_t*>(col) + (size_t)i * width, width);      // little-endian: the low bytes
-    return v;
+    switch (width) {
+        case 1: return static_cast<const uint8_t*>(col)[i];
+        case 2: return static_cast<const uint16_t*>(col)[i];
+        case 4: return static_cast<const uint32_t*>(col)[i];
+        default: return static_cast<const unsigned long long*>(col)[i];
+    }
+}
+
+// The host loops' frame of a call on a pair list: a pair the pair-filter frame drops is counted; one that keep(si, ri) keeps
+// -- the rows with S's base off -- is written while the capacity lasts, in input order, and sets its marks whether written
+// or not. info: kept, written, 0, dropped (may be null).
+template <class Keep>
+inline void pairs_keep_host(const PairList& in, const PairSink& to, uint64_t* info, Keep&& keep)
+{
+    uint64_t kept = 0, dropped = 0;
+    for (uint64_t k = 0; k < in.n; ++k) {
+        const uint32_t es = in.mapS[k], er = in.mapR[k], si = es - in.sRowBase, ri = er;
+        if (dropped_pair(es, er, in.sRowBase, in.sRows, in.rRows)) { ++dropped; continue; }
+        if (!keep(si, ri)) continue;
+        if (kept < to.out.capacity) { to.out.s[kept] = es; to.out.r[kept] = er; }
+        if (to.sMarks) set_mark_bit(to.sMarks, si);
+        if (to.rMarks) set_mark_bit(to.rMarks, ri);
+        ++kept;
+    }
+    if (info) { info[0] = kept; info[1] = kept < to.out.capacity ? kept : to.out.capacity; info[2] = 0; info[3] = dropped; }
 }
 
 // ---- as-of joins: one best match per S row (defined in hj_asof.hip) -----------
@@ -199,18 +215,15 @@ inline uint64_t where_elem_host(const void* col, uint32_t width, uint32_t i)
 // s[s] op r[r] holds as a term of the condition step does, op one of LT, LE, GT, GE.
 struct AsofTerm { const void *s, *r; const uint32_t *sValid, *rValid; uint32_t width, type, op; };
 // Pairs (mapS[k] - sRowBase, mapR[k]) -> per S row the eligible pair with the largest asof_key of its R element, ties to
-// the lowest R row, to `out` as launch_pairs_where writes its kept pairs (out.cursor: two 64-bit words, zeroed before the
+// the lowest R row, to `to.out` as launch_pairs_where writes its kept pairs (its cursor: two 64-bit words, zeroed before the
 // launch: kept pairs, pairs dropped); the marks as there, set by the kept pairs alone. bestVal (sRows 64-bit words) and
 // bestRow (sRows words) are initialised here, on s: after the call bestRow[i] is the R row kept for S row i or kNoRow,
 // bestVal[i] its key (0 without one). The caller has checked the term and nPairs, sRows, rRows <= 2^32 - 1.
-hipError_t launch_pairs_asof(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                             uint32_t rRows, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, PairsOut out,
-                             uint32_t* sMarks, uint32_t* rMarks, hipStream_t s);
+hipError_t launch_pairs_asof(const PairList& in, const AsofTerm& term, unsigned long long* bestVal, uint32_t* bestRow, const PairSink& to,
+                             hipStream_t s);
 // the same in host loops over host pointers (asof_key and where_holds are the kernels' own), the kept pairs in input
 // order; info: kept, written, 0, dropped (may be null)
-void pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
-                     const AsofTerm& term, uint64_t* bestVal, uint32_t* bestRow, uint32_t* outS, uint32_t* outR, uint64_t capacity,
-                     uint32_t* sMarks, uint32_t* rMarks, uint64_t* info);
+void pairs_asof_host(const PairList& in, const AsofTerm& term, uint64_t* bestVal, uint32_t* bestRow, const PairSink& to, uint64_t* info);
 
 // ---- rows in the order of their columns (defined in hj_sort.hip) --------------
 // The order key of the sort: the zero-extended raw word of a valid element of `width` bytes read as `type` -> an unsigned
@@ -257,12 +270,16 @@ struct AggOps { uint32_t op[kAggMaxCols], width[kAggMaxCols], sgn[kAggMaxCols]; 
 struct AggSrc { const void* p[kAggMaxCols]; const uint32_t* valid[kAggMaxCols]; };
 struct AggPlanes { unsigned long long* count; unsigned long long* acc[kAggMaxCols]; };
 struct AggRowsOut { unsigned long long* col[kAggMaxCols]; unsigned long long* count; };
-// the identity of a column's op: what an accumulator holds before its first value
-__device__ __forceinline__ unsigned long long agg_identity(uint32_t op, uint32_t sgn)
+// The accumulators of the aggregates and of the window functions' running ops: op is an hj_agg_op, T 64 bits wide
+// (values) or uint32_t (the window's positions and counts).
+// the identity of an op: what an accumulator holds before its first value
+template <class T = unsigned long long>
+__host__ __device__ __forceinline__ T agg_identity(uint32_t op, uint32_t sgn)
 {
-    if (op == kAggMin) return sgn ? 0x7FFFFFFFFFFFFFFFull : 0xFFFFFFFFFFFFFFFFull;
-    if (op == kAggMax) return sgn ? 0x8000000000000000ull : 0ull;
-    return 0ull;
+    constexpr T top = (T)1 << (8 * sizeof(T) - 1);
+    if (op == kAggMin) return sgn ? (T)(top - 1) : (T)~(T)0;
+    if (op == kAggMax) return sgn ? top : (T)0;
+    return (T)0;
 }
 // acc op= v, without a returned value; SCOPE: the workgroup for an LDS entry, the agent for a global one
 template <int SCOPE>
@@ -277,7 +294,9 @@ __device__ __forceinline__ void agg_apply(unsigned long long* acc, uint32_t op, 
         else __hip_atomic_fetch_max(acc, v, __ATOMIC_RELAXED, SCOPE);
     }
 }
-// a op b, for the reductions in registers that run in front of an atomic
+// a op b, for the reductions in registers that run in front of an atomic. NOT one body with win_op, its twin of the window's
+// scans: with either text for both, the other side's kernels compile to other code (k_pairs_agg; k_win_apply, k_win_carry,
+// k_win_summary; tools/asm_diff.py).
 __device__ __forceinline__ unsigned long long agg_combine(uint32_t op, uint32_t sgn, unsigned long long a, unsigned long long b)
 {
     if (op <= kAggSum) return a + b;
@@ -285,7 +304,7 @@ __device__ __forceinline__ unsigned long long agg_combine(uint32_t op, uint32_t 
     return sgn ? ((long long)a > (long long)b ? a : b) : (a > b ? a : b);
 }
 // the 64-bit value of element i of a column: COUNT brings 1, a 4-byte element is sign- or zero-extended
-__device__ __forceinline__ unsigned long long agg_value(const void* __restrict__ src, uint32_t op, uint32_t width, uint32_t sgn, uint32_t i)
+__host__ __device__ __forceinline__ unsigned long long agg_value(const void* __restrict__ src, uint32_t op, uint32_t width, uint32_t sgn, uint32_t i)
 {
     if (op == kAggCount) return 1ull;
     if (width == 8) return static_cast<const unsigned long long*>(src)[i];
@@ -303,23 +322,13 @@ hipError_t launch_pairs_agg(const uint32_t* mapG, const uint32_t* mapV, uint64_t
 
 // ---- window functions over runs along a permutation (defined in hj_window.hip) ----
 // What the kernels and the host loop share: how a position's head bits come about (win_head: partition head, peer head,
-// skipped entry), and the running accumulators (win_identity / win_op / win_value: hj_pairs_agg_dev's values, 64 bits wide).
+// skipped entry), and what a row brings to a running accumulator (win_value, over the aggregates' agg_identity and agg_value) and how two of them combine (win_op).
 constexpr uint32_t kWinMaxFuncs = 8;          // HJ_WIN_MAX_FUNCS
 constexpr uint32_t kWinRowNumber = 0, kWinRank = 1, kWinDenseRank = 2, kWinPartRows = 3, kWinLag = 4, kWinLead = 5, kWinFirstRow = 6,
                    kWinLastRow = 7, kWinRunCount = 8, kWinRunMax = 11;                        // hj_win_op
 // the head byte of a position: it starts a partition, it starts a peer run (set with every partition head), its entry is
 // HJ_NO_ROW or at / behind nRows (then all three are set: the entry is a run of its own and belongs to no partition)
 constexpr uint32_t kHeadPart = 1u, kHeadPeer = 2u, kHeadSkip = 4u;
-// element i of a column of `width` bytes, zero-extended; the pointer is aligned to the width
-__host__ __device__ __forceinline__ uint64_t win_elem(const void* col, uint32_t width, uint32_t i)
-{
-    switch (width) {
-        case 1: return static_cast<const uint8_t*>(col)[i];
-        case 2: return static_cast<const uint16_t*>(col)[i];
-        case 4: return static_cast<const uint32_t*>(col)[i];
-        default: return static_cast<const unsigned long long*>(col)[i];
-    }
-}
 // rows a and b tie in every order column: both NULL, or both valid with one sort_key (the flags do not change equality)
 __host__ __device__ __forceinline__ bool win_peers(const SortCols& cols, uint32_t nOrder, uint32_t a, uint32_t b)
 {
@@ -329,8 +338,8 @@ __host__ __device__ __forceinline__ bool win_peers(const SortCols& cols, uint32_
         if (c >= nOrder) break;
         const bool va = !cols.valid[c] || valid_bit(cols.valid[c], a), vb = !cols.valid[c] || valid_bit(cols.valid[c], b);
         if (va && vb)
-            same = same && sort_key(cols.type[c], cols.width[c], 0u, win_elem(cols.p[c], cols.width[c], a)) ==
-                               sort_key(cols.type[c], cols.width[c], 0u, win_elem(cols.p[c], cols.width[c], b));
+            same = same && sort_key(cols.type[c], cols.width[c], 0u, col_elem(cols.p[c], cols.width[c], a)) ==
+                               sort_key(cols.type[c], cols.width[c], 0u, col_elem(cols.p[c], cols.width[c], b));
         else same = same && va == vb;
     }
     return same;
@@ -346,15 +355,7 @@ __host__ __device__ __forceinline__ uint32_t win_head(const uint32_t* perm, uint
     if (prev >= nRows || (part && part[row] != part[prev])) return kHeadPart | kHeadPeer;
     return win_peers(cols, nOrder, row, prev) ? 0u : kHeadPeer;
 }
-// The accumulators: op is an hj_agg_op (kAggCount .. kAggMax), T uint32_t (positions and counts) or 64 bits wide (values)
-template <class T>
-__host__ __device__ __forceinline__ T win_identity(uint32_t op, uint32_t sgn)
-{
-    constexpr T top = (T)1 << (8 * sizeof(T) - 1);
-    if (op == kAggMin) return sgn ? (T)(top - 1) : (T)~(T)0;
-    if (op == kAggMax) return sgn ? top : (T)0;
-    return (T)0;
-}
+// a op b in the window's scans, T as agg_identity's (see agg_combine)
 template <class T>
 __host__ __device__ __forceinline__ T win_op(uint32_t op, uint32_t sgn, T a, T b)
 {
@@ -368,11 +369,8 @@ __host__ __device__ __forceinline__ T win_op(uint32_t op, uint32_t sgn, T a, T b
 __host__ __device__ __forceinline__ unsigned long long win_value(const void* src, const uint32_t* valid, uint32_t op, uint32_t width,
                                                                  uint32_t sgn, uint32_t row)
 {
-    if (valid && !valid_bit(valid, row)) return win_identity<unsigned long long>(op, sgn);
-    if (op == kAggCount) return 1ull;
-    if (width == 8) return static_cast<const unsigned long long*>(src)[row];
-    const uint32_t w = static_cast<const uint32_t*>(src)[row];
-    return sgn ? (unsigned long long)(long long)(int32_t)w : (unsigned long long)w;
+    if (valid && !valid_bit(valid, row)) return agg_identity(op, sgn);
+    return agg_value(src, op, width, sgn, row);
 }
 // The functions of a call as the kernels take them, by value in the kernel arguments (hj_win_func, include/htm_hashjoin.h);
 // op: the hj_win_op, sgn: HJ_AGG_SIGNED.

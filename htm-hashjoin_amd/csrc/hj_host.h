@@ -27,24 +27,16 @@ enum Buf {
     B_HTM_CONFLICTS, B_HTM_OWN_COUNTS,          // htm: conflicts listed per chunk; their counts in the window build
     B_HTM_OVF_COUNT, B_HTM_OVF_BASE, B_HTM_SCAN,
     B_HTM_OVERFLOW,             // overflow buckets (index 0 unused)
-    B_PAIRS_CURSOR,             // materialising probe (hj_probe_join_dev): the output cursor, then HJ_JOIN_LEFT's unmatched S tuples
+    B_CALL_WORDS,               // the counter words of the last call of every kind: one block per Call (call_words, below)
     B_R_MARKS,                  // HJ_FLAG_TRACK_R_MATCHES: one bit per R row (RMarks, hj_pairs.h)
     B_R_SWEEP,                  // ... and the sweep's block counts, their total and its scan workspace (r_sweep_count_words)
-    B_GATHER_CTR,               // hj_gather_dev: the NULL rows and the out-of-range entries of the last call (two 64-bit words)
-    B_GATHER2_CTR,              // hj_gather2_dev: the same two words of ITS last call, then HJ_GATHER_MAX_COLS 64-bit totals: the bytes of each column
-    B_GATHER2_WORK,             // ... and the workspace of its variable-length columns (gather2_work_words(nRows)), grown by the call
-    B_VERIFY_CTR,               // hj_pairs_verify_dev: the output cursor (= pairs kept), then the candidates dropped (two 64-bit words)
-    B_WHERE_CTR,                // hj_pairs_where_dev: the output cursor (= pairs kept), then the pairs dropped (two 64-bit words)
-    B_ASOF_CTR,                 // hj_pairs_asof_dev: the output cursor (= pairs kept), then the pairs dropped (two 64-bit words)
+    B_GATHER2_WORK,             // hj_gather2_dev: the workspace of its variable-length columns (gather2_work_words(nRows)), grown by the call
     B_MARK_SWEEP,               // hj_mark_rows_dev: the sweep's workspace for a caller's plane (r_sweep_count_words(rows))
     B_AGG,                      // hj_prj_agg_begin: 256 bytes of words (the matches of the last hj_prj_probe_agg_dev), then the match-count
                                 // plane and HJ_AGG_MAX_COLS accumulator planes of 8 bytes per R tuple, in resident order (agg_planes)
-    B_PAIRS_AGG_CTR,            // hj_pairs_agg_dev: the pairs applied and the pairs skipped by its last call (two 64-bit words)
-    B_GROUPS_CTR,               // hj_key_groups_dev: probe steps, word collisions, NULL-keyed rows and the failure word of its last call (four 64-bit words)
-    B_GROUPS_WORK,              // ... and its workspace (key_groups_work_bytes(nRows): the table, the first-row plane, the ranks, the sweep's counts), grown by the call
+    B_GROUPS_WORK,              // hj_key_groups_dev: its workspace (key_groups_work_bytes(nRows): the table, the first-row plane, the ranks, the sweep's counts), grown by the call
     B_SORT_WORK,                // hj_sort_rows_dev: its workspace (sort_layout(nRows, key bytes).bytes: two key planes, two row planes, the histogram, the scan sums), grown by the call
-    B_WINDOW_CTR,               // hj_window_rows_dev: the partitions, peer runs and skipped entries of its last call (three 64-bit words)
-    B_WINDOW_WORK,              // ... and its workspace (window_layout(nPos).bytes: the head bytes, the end plane, the chunk summaries), grown by the call
+    B_WINDOW_WORK,              // hj_window_rows_dev: its workspace (window_layout(nPos).bytes: the head bytes, the end plane, the chunk summaries), grown by the call
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -63,14 +55,29 @@ struct DevBuf {
 };
 
 // The last call of one kind, as its *_info entry point reports it (call_info, hj_api_rows.hip): what the caller asked for,
-// and the pair of events around the call's work. `called` and `timed` die separately: see hj_ctx::call.
+// the few words the host knows about how the call cut its input (extra), and the pair of events around the call's work.
+// `called` and `timed` die separately: see hj_ctx::call. What the DEVICE counts during the call lies in the kind's block of
+// buf[B_CALL_WORDS] (call_words): kCallWords 64-bit words = 128 bytes, one L2 line, so the atomics of two kinds never meet
+// in one line. The words of a block, from word 0:
+//   CALL_PAIRS                  the output cursor (= rows found), HJ_JOIN_LEFT's unmatched S tuples
+//   CALL_GATHER                 the NULL rows, the out-of-range entries
+//   CALL_GATHER2                the same two, then HJ_GATHER_MAX_COLS totals: the bytes of each column
+//   CALL_VERIFY, _WHERE, _ASOF  the output cursor (= pairs kept), the pairs dropped unread
+//   CALL_PAIRS_AGG              the pairs applied, the pairs skipped
+//   CALL_GROUPS                 probe steps, word collisions, NULL-keyed rows, the failure word
+//   CALL_WINDOW                 partitions, peer runs, skipped entries
+// CALL_R_ROWS, CALL_MARK_ROWS and CALL_GROUPS find their total in their sweep's workspace, CALL_PRJ_AGG its words in front of
+// buf[B_AGG], CALL_SORT counts nothing on the device.
 enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
     uint32_t kind = 0;                          // pairs: the hj_join_kind
+    uint64_t extra[4] = {0, 0, 0, 0};           // sort: passes, chunks, chunkRows, workspace bytes; window: chunks, workspace bytes
     hipEvent_t ev[2] = {nullptr, nullptr};      // the first in front of the call's work, the second (call_end) behind it
 };
+constexpr uint32_t kCallWords = 16;
+static_assert(2 + HJ_GATHER_MAX_COLS <= kCallWords, "the largest user of a block is hj_gather2_dev: two counts and a total per column");
 
 // pinned host words the device copies into: the locality sampler's answer (sample_variant; hj_join_dev reads fit[0..1]
 // after it) and, apart from it, the overflow buckets the LDS chain phase of build_htm asks for
@@ -144,13 +151,10 @@ struct hj_ctx {
     // in buf[B_AGG] hold, the probes since the begin. Reset by begin_operation; worth nothing without res.on.
     struct Agg { bool on = false; uint32_t nCols = 0; uint64_t nR = 0, probes = 0; hj::AggOps ops{}; } agg;
     // ---- the last call of each kind (CallRecord). begin_operation forgets the TIME of the pairs call (its facts stay) and
-    // the whole R-rows call, which hj_reserve also forgets with the plane; the two gathers, the verify step, the condition step
-    // (hj_pairs_where_dev), the as-of step (hj_pairs_asof_dev), the grouping of a table's rows (hj_key_groups_dev), the sort of a table's rows (hj_sort_rows_dev), the window step (hj_window_rows_dev) and the sweep of a caller's plane belong to no build and no operation and are never forgotten.
+    // the whole R-rows call, which hj_reserve also forgets with the plane, and it ends the probes of an aggregation. Every
+    // other kind -- the calls on rows, row maps and pair lists of hj_api_rows.hip -- belongs to no build and no operation and
+    // is never forgotten.
     hjapi::CallRecord call[hjapi::CALL_COUNT];
-    // ---- the last hj_sort_rows_dev beyond its record: the passes it launched and how it cut the rows (hj_sort_rows_info)
-    struct Sort { uint64_t passes = 0, chunks = 0, chunkRows = 0, bytes = 0; } sort;
-    // ---- the last hj_window_rows_dev beyond its record: how it cut the positions (hj_window_rows_info)
-    struct Window { uint64_t chunks = 0, bytes = 0; } window;
     // ---- streaming Zipf generator (hj_zipf_open / hj_zipf_next_dev). Reset by zipf_release (open, close, destroy).
     struct Zipf {
         hjhost::GlibcRand* rng = nullptr;
@@ -191,6 +195,12 @@ inline int fail(hj_ctx* c, int code, const char* fn, const char* what) { return 
         if (c) (c)->op.streamAtBuildEnd = false;              \
         if (!(c) || !(argsOk)) return HJ_ERR_INVALID;         \
     } while (0)
+
+// the counter block of the last call of kind `which` (allocated and zeroed at creation)
+inline unsigned long long* call_words(const hj_ctx* c, Call which) { return c->buf[B_CALL_WORDS].as<unsigned long long>() + (size_t)which * kCallWords; }
+
+// hj_key_hash*_dev, hj_key_groups_dev and their host twins: a keyMask of 0 means every bit
+inline uint32_t effective_mask(uint32_t keyMask) { return keyMask ? keyMask : 0xFFFFFFFFu; }
 
 inline bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
 inline uint32_t probe_len(const hj_params& p) { return p.probeLength ? p.probeLength : 4; }

@@ -237,14 +237,12 @@ void key_hash2_host(const KeyCols2& cols, uint32_t nCols, uint64_t nRows, uint32
     }
 }
 
-hipError_t launch_pairs_verify2(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                                uint32_t rRows, const KeyCols2SR& cols, uint32_t nCols, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
-                                hipStream_t s)
+hipError_t launch_pairs_verify2(const PairList& in, const KeyCols2SR& cols, uint32_t nCols, const PairSink& to, hipStream_t s)
 {
     int form = 0;
     for (uint32_t c = 0; c < nCols; ++c) form = cols.width[c] == 0u ? 2 : form ? form : (cols.sValid[c] || cols.rValid[c]) ? 1 : 0;
     const auto kernel = form == 2 ? k_pairs_verify2<2> : form == 1 ? k_pairs_verify2<1> : k_pairs_verify2<0>;
-    return launch_pair_filter(kernel, mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, out, sMarks, rMarks, s);
+    return launch_pair_filter(kernel, in, cols, nCols, to, s);
 }
 
 }  // namespace hj

@@ -230,18 +230,21 @@ constexpr uint32_t kFilterWaves = kBlock / kWave;
 constexpr uint32_t kFilterBlockPairs = kFilterWavePairs * kFilterWaves;      // 1024
 static_assert(kFilterBlockPairs <= kStagePairs, "a workgroup's pairs fit one stage: it is flushed exactly once");
 
+// What the calls on a pair list take and leave (verify, where, as-of; their host twins too). The list: pair k is
+// (mapS[k] - sRowBase, mapR[k]), sRows / rRows the rows of the two relations. The sink: the planes and the cursor of the
+// kept pairs (the host twins have no cursor: null) and the two mark planes in RMarks' layout, either may be null.
+struct PairList { const uint32_t* mapS; const uint32_t* mapR; uint64_t n; uint32_t sRowBase, sRows, rRows; };
+struct PairSink { PairsOut out; uint32_t* sMarks; uint32_t* rMarks; };
+
 // The launch of either kernel: k(mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, out, S's marks).
-// sMarks / rMarks: the two planes in RMarks' layout, either may be null.
 template <class Kernel, class Cols>
-inline hipError_t launch_pair_filter(Kernel kernel, const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                                     uint32_t rRows, const Cols& cols, uint32_t nCols, const PairsOut& out, uint32_t* sMarks, uint32_t* rMarks,
-                                     hipStream_t s)
+inline hipError_t launch_pair_filter(Kernel kernel, const PairList& in, const Cols& cols, uint32_t nCols, const PairSink& to, hipStream_t s)
 {
-    if (nPairs == 0) return hipSuccess;
-    const RMarks mkS{sMarks, sRowBase, sMarks ? sRows : 0u}, mkR{rMarks, 0u, rMarks ? rRows : 0u};
-    const PairsOutMarked o = pairs_out_of<true>(out, &mkR);
-    const dim3 grid((uint32_t)((nPairs + kFilterBlockPairs - 1) / kFilterBlockPairs));        // nPairs <= 2^32 - 1: <= 2^22 workgroups
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, mapS, mapR, nPairs, sRowBase, sRows, rRows, cols, nCols, o, mkS);
+    if (in.n == 0) return hipSuccess;
+    const RMarks mkS{to.sMarks, in.sRowBase, to.sMarks ? in.sRows : 0u}, mkR{to.rMarks, 0u, to.rMarks ? in.rRows : 0u};
+    const PairsOutMarked o = pairs_out_of<true>(to.out, &mkR);
+    const dim3 grid((uint32_t)((in.n + kFilterBlockPairs - 1) / kFilterBlockPairs));          // n <= 2^32 - 1: <= 2^22 workgroups
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, in.mapS, in.mapR, in.n, in.sRowBase, in.sRows, in.rRows, cols, nCols, o, mkS);
     return hipGetLastError();
 }
 

@@ -347,7 +347,7 @@ void sort_rows_host(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32
         const uint32_t flip = (cols.flags[c] & kSortNullsFirst) ? 0u : 1u;
         for (uint64_t i = 0; i < nRows; ++i) {
             const bool ok = !cols.valid[c] || valid_bit(cols.valid[c], (uint32_t)i);
-            key[i] = ok ? sort_key(cols.type[c], cols.width[c], cols.flags[c], where_elem_host(cols.p[c], cols.width[c], (uint32_t)i)) : 0ull;
+            key[i] = ok ? sort_key(cols.type[c], cols.width[c], cols.flags[c], col_elem(cols.p[c], cols.width[c], (uint32_t)i)) : 0ull;
             bin[i] = cols.valid[c] ? (uint8_t)((ok ? 1u : 0u) ^ flip) : 0;
         }
         std::stable_sort(perm, perm + nRows, [&](uint32_t a, uint32_t b) { return bin[a] != bin[b] ? bin[a] < bin[b] : key[a] < key[b]; });

@@ -110,38 +110,26 @@ k_pairs_where(const uint32_t* __restrict__ mapS, const uint32_t* __restrict__ ma
     mark_plane<kBlock>(st.s, kept, sMarks);                           // the stage is still as it was flushed
 }
 
-hipError_t launch_pairs_where(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows,
-                              uint32_t rRows, const WhereTerms& terms, uint32_t nTerms, PairsOut out, uint32_t* sMarks, uint32_t* rMarks,
-                              hipStream_t s)
+hipError_t launch_pairs_where(const PairList& in, const WhereTerms& terms, uint32_t nTerms, const PairSink& to, hipStream_t s)
 {
     bool valid = false;
     for (uint32_t t = 0; t < nTerms; ++t) valid = valid || terms.sValid[t] || terms.rValid[t];
     const auto kernel = valid ? k_pairs_where<true> : k_pairs_where<false>;
-    return launch_pair_filter(kernel, mapS, mapR, nPairs, sRowBase, sRows, rRows, terms, nTerms, out, sMarks, rMarks, s);
+    return launch_pair_filter(kernel, in, terms, nTerms, to, s);
 }
 
-void pairs_where_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPairs, uint32_t sRowBase, uint32_t sRows, uint32_t rRows,
-                      const WhereTerms& terms, uint32_t nTerms, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks,
-                      uint32_t* rMarks, uint64_t* info)
+void pairs_where_host(const PairList& in, const WhereTerms& terms, uint32_t nTerms, const PairSink& to, uint64_t* info)
 {
-    uint64_t kept = 0, dropped = 0;
-    for (uint64_t k = 0; k < nPairs; ++k) {
-        const uint32_t es = mapS[k], er = mapR[k], si = es - sRowBase, ri = er;
-        if (dropped_pair(es, er, sRowBase, sRows, rRows)) { ++dropped; continue; }
+    pairs_keep_host(in, to, info, [&](uint32_t si, uint32_t ri) {
         bool live = true;
         for (uint32_t t = 0; live && t < nTerms; ++t) {
             const bool okS = !terms.sValid[t] || valid_bit(terms.sValid[t], si);
             const bool okR = !terms.rValid[t] || valid_bit(terms.rValid[t], ri);
-            live = okS && okR && where_holds(terms.type[t], terms.width[t], terms.op[t], where_elem_host(terms.s[t], terms.width[t], si),
-                                             where_elem_host(terms.r[t], terms.width[t], ri));
+            live = okS && okR && where_holds(terms.type[t], terms.width[t], terms.op[t], col_elem(terms.s[t], terms.width[t], si),
+                                             col_elem(terms.r[t], terms.width[t], ri));
         }
-        if (!live) continue;
-        if (kept < capacity) { outS[kept] = es; outR[kept] = er; }
-        if (sMarks) set_mark_bit(sMarks, si);
-        if (rMarks) set_mark_bit(rMarks, ri);
-        ++kept;
-    }
-    if (info) { info[0] = kept; info[1] = kept < capacity ? kept : capacity; info[2] = 0; info[3] = dropped; }
+        return live;
+    });
 }
 
 }  // namespace hj

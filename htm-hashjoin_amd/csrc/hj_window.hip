@@ -174,7 +174,7 @@ k_win_summary(const uint32_t* __restrict__ perm, uint64_t nPos, uint32_t nRows, 
     for (uint32_t f = 0; f < nFuncs; ++f) {
         if (!is_run(fn.op[f])) continue;
         const uint32_t op = fn.op[f] - kWinRunCount, sgn = fn.sgn[f], width = fn.width[f];
-        unsigned long long acc = win_identity<unsigned long long>(op, sgn);
+        unsigned long long acc = agg_identity<unsigned long long>(op, sgn);
         // four positions a turn: their rows first, then their values -- four scattered loads in flight per lane
         for (uint64_t p0 = from + threadIdx.x; p0 < end; p0 += 4 * kWinThreads) {
             uint32_t row[4];
@@ -185,7 +185,7 @@ k_win_summary(const uint32_t* __restrict__ perm, uint64_t nPos, uint32_t nRows, 
                 row[k] = p >= end ? kNoRow : perm ? perm[p] : (uint32_t)p;
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = row[k] < nRows ? win_value(fn.src[f], fn.valid[f], op, width, sgn, row[k]) : win_identity<unsigned long long>(op, sgn);
+            for (int k = 0; k < 4; ++k) v[k] = row[k] < nRows ? win_value(fn.src[f], fn.valid[f], op, width, sgn, row[k]) : agg_identity<unsigned long long>(op, sgn);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc = win_op<unsigned long long>(op, sgn, acc, v[k]);
         }
@@ -203,7 +203,7 @@ __device__ __forceinline__ void carry_scan(T* __restrict__ data, const uint32_t*
 {
     const uint32_t per = (chunks + kWinThreads - 1) / kWinThreads;
     const uint32_t lo = threadIdx.x * per < chunks ? threadIdx.x * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
-    const T id = win_identity<T>(op, sgn);
+    const T id = agg_identity<T>(op, sgn);
     uint32_t f = 0;
     T v = id;
     for (uint32_t i = lo; i < hi; ++i) {
@@ -342,7 +342,7 @@ k_win_apply(const uint32_t* __restrict__ perm, uint64_t nPos, uint32_t nRows, co
 #pragma unroll
                 for (int k = 0; k < kWinPer; ++k) {
                     f[k] = hb[k] & kHeadPart;
-                    v[k] = ok[k] ? win_value(fn.src[i], fn.valid[i], aop, width, sgn, row[k]) : win_identity<unsigned long long>(aop, sgn);
+                    v[k] = ok[k] ? win_value(fn.src[i], fn.valid[i], aop, width, sgn, row[k]) : agg_identity<unsigned long long>(aop, sgn);
                 }
                 unsigned long long carry = runCarry[i];
                 tile_seg_scan<unsigned long long>(aop, sgn, f, v, carry, ldsV, ldsF);
@@ -469,7 +469,7 @@ void window_rows_host(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const
             const uint32_t op = fn.op[i];
             if (op >= kWinRunCount) {
                 const uint32_t aop = op - kWinRunCount;
-                if (hb & kHeadPart) acc[i] = win_identity<unsigned long long>(aop, fn.sgn[i]);
+                if (hb & kHeadPart) acc[i] = agg_identity<unsigned long long>(aop, fn.sgn[i]);
                 if (!ok) continue;
                 acc[i] = win_op<unsigned long long>(aop, fn.sgn[i], acc[i], win_value(fn.src[i], fn.valid[i], aop, fn.width[i], fn.sgn[i], row));
                 static_cast<unsigned long long*>(fn.out[i])[row] = acc[i];
