@@ -396,9 +396,15 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 const uint32_t c0 = e0 ? kCodeEmpty : RingWord::code(t.x), c1 = e1 ? kCodeEmpty : RingWord::code(t.y);
                 u2 ii;
                 ii.x = e0 ? kNone : idx0 + RingWord::rel(t.x); ii.y = e1 ? kNone : idx0 + RingWord::rel(t.y);
-                uint8_t* const codes = reinterpret_cast<uint8_t*>(table) + ((uint64_t)winLoG << kGranShift);
-                __builtin_nontemporal_store((unsigned short)(c0 | (c1 << 8)), reinterpret_cast<unsigned short*>(codes) + lane);
-                __builtin_nontemporal_store(ii, reinterpret_cast<u2*>(planar_index_plane(table, mask + 1) + ((uint64_t)winLoG << kGranShift)) + lane);
+                // the granule's two runs start at wave-uniform addresses, and the optimiser is held to that: left alone it keeps
+                // a 64-bit address per lane and run alive around the tile loop, four registers the road's occupancy has no
+                // room for now that the ring moves from two places (kWvWordWpe)
+                unsigned short* codes = reinterpret_cast<unsigned short*>(reinterpret_cast<uint8_t*>(table) + ((uint64_t)winLoG << kGranShift));
+                u2* idxRun = reinterpret_cast<u2*>(planar_index_plane(table, mask + 1) + ((uint64_t)winLoG << kGranShift));
+                uint32_t ln = lane;                                       // ... nor the lane's two offsets
+                asm volatile("" : "+s"(codes), "+s"(idxRun), "+v"(ln));
+                __builtin_nontemporal_store((unsigned short)(c0 | (c1 << 8)), codes + ln);
+                __builtin_nontemporal_store(ii, idxRun + ln);
                 *src = make_uint2(RingWord::kEmpty, RingWord::kEmpty);
                 ++winLoG;
                 continue;
@@ -771,6 +777,24 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         if (COMPACT && full) { tmin = tminF; tmax = tmaxF; }          // taken from the keys at the end of the tile before
         else { tmin = wave_umin(myMin); if (tmin != kNone) tmax = ~wave_umin(myMaxInv); }
         bool allIn = false;                                           // wave-uniform: every home slot of the tile lies in ring and range
+        // CODES: the ring moves before each batch, only as far as that batch's highest home slot needs (below): rows 0-3 need
+        // no room for rows 4-7, and the granules that stay are the history that queued entries and displacement chains of the
+        // last tile or two still live in -- one move per tile, all the way, left 1.38 M tuples of 2^30 `uniform` behind the
+        // ring, this leaves 0.25 M (tools/sim/ring_moves.c, profiles/ring_moves.md; rounds in front of a move for the entries
+        // below its target take that to 0.05 M and cost the kernel more than the tail gives back: measured, not kept). Rounds
+        // never move the ring, so where it stands for the second batch is known here: its target and its allIn wait in two
+        // scalars.
+        [[maybe_unused]] uint32_t target1 = 0;
+        [[maybe_unused]] bool allIn1 = false;
+        // how far the ring must move for the highest home slot `hi` (+ a probe walk) to fit: no further, so it keeps as much
+        // history as it can, never past the tile's lowest home slot (an outlier key is deferred, not the tile), never out of
+        // the range
+        [[maybe_unused]] auto ring_target = [&](uint32_t hi, uint32_t gmin) -> uint32_t {
+            const uint32_t top = (uint32_t)(((uint64_t)hi + probeLen + 8u) >> kGranShift) + 1u;
+            uint32_t target = top > RGRAN ? top - RGRAN : 0u;
+            target = target < gmin ? target : gmin;
+            return target < limG ? target : limG;
+        };
         if (tmin != kNone) {
             // The ring moves only as far as it must for the tile's highest home slot (+ a probe walk) to fit, so it
             // keeps as much history as it can: retry entries carried over from the previous tile are still inside.
@@ -780,7 +804,7 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
             const uint32_t gmin = tmin >> kGranShift;
             target = target < gmin ? target : gmin;
             target = target < limG ? target : limG;
-            advance(target);
+            if constexpr (!CODES) advance(target);
             if constexpr (CODES) {
                 // forced road only (keyLimit = 0: every key has a code): a key whose high part no code holds
                 if (cr.keyLimit) {
@@ -800,7 +824,26 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
                 }
             }
             const uint32_t gmax = tmax >> kGranShift;
-            allIn = full & (gmin - winLoG < RGRAN) & (gmax - winLoG < RGRAN) & (gmax < limG);
+            if constexpr (!CODES) allIn = full & (gmin - winLoG < RGRAN) & (gmax - winLoG < RGRAN) & (gmax < limG);
+        }
+        if (tmin != kNone) {
+            if constexpr (CODES) {
+                const uint32_t gmin = tmin >> kGranShift, gmax = tmax >> kGranShift;
+                // the highest home slot of the first batch's rows, taken here from the keys: inside classify() it would cost
+                // a register through rows 4-7, where the tile has none to spare (a full tile's bounds go over every tuple)
+                uint32_t myMaxA = 0;
+#pragma unroll
+                for (int j = 0; j < ROWS; ++j) {
+                    const uint32_t h = home_of(j);
+                    myMaxA = ((full | live[j]) & (h > myMaxA)) ? h : myMaxA;
+                }
+                const uint32_t tmaxA = ~wave_umin(~myMaxA), gmaxA = tmaxA >> kGranShift;
+                advance(ring_target(tmaxA, gmin));
+                allIn = full & (gmin - winLoG < RGRAN) & (gmaxA - winLoG < RGRAN) & (gmaxA < limG);
+                target1 = ring_target(tmax, gmin);
+                const uint32_t lo1 = winLoG > target1 ? winLoG : target1;
+                allIn1 = full & (gmin - lo1 < RGRAN) & (gmax - lo1 < RGRAN) & (gmax < limG);
+            }
         }
 
         // ---- the home-slot attempts and the push rows, one batch of ROWS rows after the other ----
@@ -812,11 +855,14 @@ k_build_wave(const void* __restrict__ Rv, uint64_t n, uint32_t sliceLen, uint32_
         // rows 0-3 were pushed and perhaps had a round. Rows 0-3 hold the tile's first 256 positions, so nothing of rows 4-7
         // can be displaced by them later; a round between the batches treats what it finds in a slot as any round does.
         // The queue's invariant is per row (`while (qCount >= kWvRoundAt)` before every push leaves room for one full
-        // step of 64), and the ring moved once, above, before the first batch: allIn and in_ring hold for every batch,
-        // because rounds never move the ring.
+        // step of 64). The 8-byte rings moved once, above; the slot-code road moves its ring before each batch, and each batch
+        // has its own allIn: in_ring holds through a batch because rounds never move the ring.
         int b = 0;                                                    // the batch's first row
 #pragma unroll
         do {
+        if constexpr (CODES) {
+            if (b) { advance(target1); allIn = allIn1; }
+        }
         std::conditional_t<CODES, uint32_t, unsigned long long> oldv[ROWS];
         // the PER home-slot attempts of a batch, issued together (independent LDS round trips)
         // (when the tile's lowest and highest home slot are inside ring and range -- nearly every full tile -- the
