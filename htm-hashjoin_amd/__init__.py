@@ -13,6 +13,7 @@ from ._lib import (  # noqa: F401
     hj_where_term, ASOF_OPS, hj_asof_term,
     HJ_SORT_MAX_COLS, HJ_SORT_DESC, HJ_SORT_NULLS_FIRST, hj_sort_col,
     HJ_WIN_MAX_FUNCS, hj_win_func,
+    HJ_RANGE_LO_OPEN, HJ_RANGE_HI_OPEN, HJ_RANGE_ALL, HJ_RANGE_FIRST, HJ_RANGE_LAST, RANGE_PICKS, hj_range_term,
     HJ_AGG_MAX_COLS, HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX, HJ_AGG_SIGNED, hj_agg_spec, hj_agg_src, hj_agg_col,
 )
 from .engine import (  # noqa: F401
@@ -27,3 +28,4 @@ from .aggregates import radix_join_aggregate, aggregate_on  # noqa: F401
 from .groups import key_groups, key_groups_host, distinct_on, group_by_columns  # noqa: F401
 from .sorting import sort_rows, sort_rows_host, sort_by_columns, sort_pairs  # noqa: F401
 from .windows import window_rows, window_rows_host  # noqa: F401
+from .ranges import range_join, interval_join, range_join_host, range_pairs_host, range_layout_info  # noqa: F401

@@ -57,6 +57,10 @@ ASOF_OPS = {op: CMP_OPS[op] for op in (">=", ">", "<=", "<")}
 # hj_sort_rows_dev: columns of one call, and hj_sort_col.flags
 HJ_SORT_MAX_COLS = 4
 HJ_SORT_DESC, HJ_SORT_NULLS_FIRST = 0x1, 0x2
+# hj_range_pairs_dev: hj_range_term.flags and hj_range_pick
+HJ_RANGE_LO_OPEN, HJ_RANGE_HI_OPEN = 0x1, 0x2
+HJ_RANGE_ALL, HJ_RANGE_FIRST, HJ_RANGE_LAST = 0, 1, 2
+RANGE_PICKS = {"all": HJ_RANGE_ALL, "first": HJ_RANGE_FIRST, "last": HJ_RANGE_LAST}
 # hj_window_rows_dev: functions of one call, and hj_win_op
 HJ_WIN_MAX_FUNCS = 8
 (HJ_WIN_ROW_NUMBER, HJ_WIN_RANK, HJ_WIN_DENSE_RANK, HJ_WIN_PART_ROWS, HJ_WIN_LAG, HJ_WIN_LEAD, HJ_WIN_FIRST_ROW, HJ_WIN_LAST_ROW,
@@ -179,6 +183,19 @@ class hj_sort_col(C.Structure):
     ]
 
 
+class hj_range_term(C.Structure):
+    _fields_ = [
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("loValid", C.c_void_p),
+        ("hiValid", C.c_void_p),
+        ("width", C.c_uint32),
+        ("type", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("pick", C.c_uint32),
+    ]
+
+
 class hj_win_func(C.Structure):
     _fields_ = [
         ("src", C.c_void_p),
@@ -263,6 +280,13 @@ def _declare(lib):
         "hj_window_rows_info": ([vp, P(u64)], i32),
         "hj_window_rows_host": ([vp, u64, u64, vp, P(hj_sort_col), u32, P(hj_win_func), u32, P(u64)], i32),
         "hj_window_layout_info": ([u64, P(u64)], i32),
+        "hj_range_index_dev": ([vp, P(hj_sort_col), u64, vp, vp, vp], i32),
+        "hj_range_index_info": ([vp, P(u64)], i32),
+        "hj_range_index_host": ([P(hj_sort_col), u64, vp, vp, vp], i32),
+        "hj_range_layout_info": ([u64, u64, P(u64)], i32),
+        "hj_range_pairs_dev": ([vp, vp, vp, vp, u64, P(hj_range_term), u64, u32, vp, vp, u64, vp, vp], i32),
+        "hj_range_pairs_info": ([vp, P(u64)], i32),
+        "hj_range_pairs_host": ([vp, vp, vp, u64, P(hj_range_term), u64, u32, vp, vp, u64, vp, vp, P(u64)], i32),
         "hj_pairs_where_dev": ([vp, vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp], i32),
         "hj_where_info": ([vp, P(u64)], i32),
         "hj_pairs_where_host": ([vp, vp, u64, u32, u64, u64, P(hj_where_term), u32, vp, vp, u64, vp, vp, P(u64)], i32),

@@ -1,7 +1,8 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
 // joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns
 // and sorted by them, the window functions along a permutation, the join conditions beyond equality, the as-of step, the
-// reduction over a pair list, and the *_info entry point of every call that has a record (hj_host.h: CallRecord).
+// range joins without an equality key, the reduction over a pair list, and the *_info entry point of every call that has
+// a record (hj_host.h: CallRecord).
 // Host-side glue only, and the same three parts for every recorded call: its checks, which give the message of the first
 // thing wrong; recorded_call, the one frame around its launch; call_info, the one reader of what it left.
 #include "hj_host.h"
@@ -732,6 +733,118 @@ int hj_pairs_asof_host(const uint32_t* mapS, const uint32_t* mapR, uint64_t nPai
     AsofTerm k{};
     if (asof_args(a, term, bestVal, bestRow, &k)) return HJ_ERR_INVALID;
     pairs_asof_host(a.list(), k, bestVal, bestRow, a.sink(), info);
+    return HJ_OK;
+}
+
+// ---- range joins without an equality key (hj_range.hip) ------------------------
+// hj_range_index_dev's and hj_range_index_host's arguments -> the kernels' column; the message of what is wrong, or nullptr
+static const char* range_index_args(const hj_sort_col* col, uint64_t nRows, const uint32_t* perm, const void* keys, const uint32_t* head, SortCols* k)
+{
+    if (!col) return "col NULL";
+    if (nRows > 0xFFFFFFFEull) return "nRows above 2^32 - 2";
+    if (col->flags) return "hj_sort_col.flags must be 0: the index is ascending with its NULLs last";
+    if (const char* what = sort_cols_error(col, 1, nRows, k)) return what;
+    if (nRows && (!perm || !word_ptr_ok(perm))) return "dPerm NULL or not 4-byte aligned";
+    if (nRows && !col_ptr_ok(keys, col->width == 8 ? 8 : 4)) return "dKeys NULL or not aligned to its key bytes";
+    if (!head || !word_ptr_ok(head)) return "dHead NULL or not 4-byte aligned";
+    return nullptr;
+}
+
+int hj_range_index_dev(hj_ctx* c, const hj_sort_col* col, uint64_t nRows, uint32_t* dPerm, void* dKeys, uint32_t* dHead)
+{
+    HJ_ENTER(c, true);
+    SortCols k{};
+    if (const char* what = range_index_args(col, nRows, dPerm, dKeys, dHead, &k)) return fail(c, HJ_ERR_INVALID, "hj_range_index_dev", what);
+    const SortLayout l = sort_layout(nRows, sort_key_bytes(k, 1));
+    const Facts facts{0, nRows, {(uint64_t)reinterpret_cast<uintptr_t>(dHead)}};
+    return recorded_call(c, CALL_RANGE_INDEX, 0, INIT_UNTIMED, Work{B_SORT_WORK, nRows ? l.bytes : 0}, facts, [&](unsigned long long*) {
+        return launch_range_index(k, nRows, dPerm, dKeys, dHead, c->buf[B_SORT_WORK].p, c->stream);
+    });
+}
+
+int hj_range_index_info(hj_ctx* c, uint64_t out[4])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_RANGE_INDEX];
+    if (const int rc = call_info(c, CALL_RANGE_INDEX, nullptr, nullptr, out)) return rc;
+    if (!r.called) return HJ_OK;
+    uint32_t head[4];                                           // the caller's plane, as the call left it
+    HJ_HIP(c, hipMemcpy(head, reinterpret_cast<const void*>((uintptr_t)r.extra[0]), sizeof(head), hipMemcpyDeviceToHost));
+    out[0] = head[0]; out[1] = head[1]; out[3] = head[2];
+    return HJ_OK;
+}
+
+int hj_range_index_host(const hj_sort_col* col, uint64_t nRows, uint32_t* perm, void* keys, uint32_t head[4])
+{
+    SortCols k{};
+    if (range_index_args(col, nRows, perm, keys, head, &k)) return HJ_ERR_INVALID;
+    range_index_host(k, nRows, perm, keys, head);
+    return HJ_OK;
+}
+
+int hj_range_layout_info(uint64_t nRows, uint64_t sRows, uint64_t out[8])
+{
+    if (!out || nRows > 0xFFFFFFFEull || sRows > 0xFFFFFFFEull) return HJ_ERR_INVALID;
+    const RangeLayout l = range_layout(nRows, sRows);
+    out[0] = l.pivots; out[1] = l.stride; out[2] = l.tilePairs; out[3] = l.bytes; out[4] = l.chunkRows; out[5] = l.chunks; out[6] = l.ldsBytes;
+    out[7] = 0;
+    return HJ_OK;
+}
+
+// hj_range_pairs_dev's and hj_range_pairs_host's arguments -> the kernels' term; the message of what is wrong, or nullptr
+static const char* range_args(const void* keys, const uint32_t* perm, const uint32_t* head, uint64_t rRows, const hj_range_term* t, uint64_t sRows,
+                              const uint32_t* outS, const uint32_t* outR, uint64_t capacity, const uint32_t* sMarks, const uint32_t* rMarks, RangeTerm* k)
+{
+    if (sRows > 0xFFFFFFFEull || rRows > 0xFFFFFFFEull) return "sRows or rRows above 2^32 - 2";
+    if (capacity > 0xFFFFFFFFull) return "capacity above 2^32 - 1";
+    if (!t) return "term NULL";
+    if (!t->lo && !t->hi) return "lo and hi both NULL: a range has a bound";
+    if (const char* what = val_col_error(t->type, t->width)) return what;
+    if (t->flags & ~(HJ_RANGE_LO_OPEN | HJ_RANGE_HI_OPEN)) return "hj_range_term.flags has bits other than HJ_RANGE_LO_OPEN and HJ_RANGE_HI_OPEN";
+    if (t->pick > HJ_RANGE_LAST) return "pick must be an hj_range_pick";
+    if ((reinterpret_cast<uintptr_t>(t->lo) | reinterpret_cast<uintptr_t>(t->hi)) & (t->width - 1)) return "a bound pointer that is not aligned to its width";
+    if (!word_ptr_ok(t->loValid) || !word_ptr_ok(t->hiValid)) return "a validity pointer that is not 4-byte aligned";
+    if (rRows && (!perm || !word_ptr_ok(perm))) return "dPerm NULL or not 4-byte aligned";
+    if (rRows && !col_ptr_ok(keys, t->width == 8 ? 8 : 4)) return "dKeys NULL or not aligned to its key bytes";
+    if (rRows && (!head || !word_ptr_ok(head))) return "dHead NULL or not 4-byte aligned";
+    if (!word_ptr_ok(outS) || !word_ptr_ok(outR) || !word_ptr_ok(sMarks) || !word_ptr_ok(rMarks)) return "an output or mark pointer that is not 4-byte aligned";
+    if (sRows && rRows && capacity && (!outS || !outR)) return "an output pointer NULL with capacity > 0";
+    *k = RangeTerm{t->lo, t->hi, t->loValid, t->hiValid, t->width, t->type, t->flags, t->pick};
+    return nullptr;
+}
+
+int hj_range_pairs_dev(hj_ctx* c, const void* dKeys, const uint32_t* dPerm, const uint32_t* dHead, uint64_t rRows, const hj_range_term* term,
+                       uint64_t sRows, uint32_t sRowBase, uint32_t* dOutS, uint32_t* dOutR, uint64_t capacity, uint32_t* dSMarks, uint32_t* dRMarks)
+{
+    HJ_ENTER(c, true);
+    RangeTerm k{};
+    if (const char* what = range_args(dKeys, dPerm, dHead, rRows, term, sRows, dOutS, dOutR, capacity, dSMarks, dRMarks, &k))
+        return fail(c, HJ_ERR_INVALID, "hj_range_pairs_dev", what);
+    const RangeLayout l = range_layout(rRows, sRows);
+    const PairSink to{PairsOut{dOutS, dOutR, capacity, nullptr}, dSMarks, dRMarks};
+    return recorded_call(c, CALL_RANGE, 4, INIT_UNTIMED, Work{B_RANGE_WORK, l.bytes}, Facts{capacity, sRows}, [&](unsigned long long* words) {
+        return launch_range_pairs(dKeys, dPerm, dHead, (uint32_t)rRows, k, (uint32_t)sRows, sRowBase, to, c->buf[B_RANGE_WORK].p, words, c->stream);
+    });
+}
+
+int hj_range_pairs_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    for (int i = 4; i < 8; ++i) out[i] = 0;
+    unsigned long long words[kCallWords];
+    if (const int rc = call_info(c, CALL_RANGE, nullptr, words, out)) return rc;       // pairs, written, time, S rows with a pair
+    out[4] = words[2]; out[5] = words[3];
+    return HJ_OK;
+}
+
+int hj_range_pairs_host(const void* keys, const uint32_t* perm, const uint32_t* head, uint64_t rRows, const hj_range_term* term, uint64_t sRows,
+                        uint32_t sRowBase, uint32_t* outS, uint32_t* outR, uint64_t capacity, uint32_t* sMarks, uint32_t* rMarks, uint64_t info[8])
+{
+    RangeTerm k{};
+    if (range_args(keys, perm, head, rRows, term, sRows, outS, outR, capacity, sMarks, rMarks, &k)) return HJ_ERR_INVALID;
+    if (rRows && head[3] != (k.width == 8 ? 8u : 4u)) return HJ_ERR_INVALID;              // the index is of another key width
+    const PairSink to{PairsOut{outS, outR, capacity, nullptr}, sMarks, rMarks};
+    range_pairs_host(keys, perm, head, (uint32_t)rRows, k, (uint32_t)sRows, sRowBase, to, info);
     return HJ_OK;
 }
 

@@ -1,6 +1,6 @@
 // hj_columns.h -- the relational layer's column code: validity and mark bits, gather, key columns, groups, join
-// conditions and as-of (how two elements compare and order), sort keys, the aggregates over a pair list, and the window
-// functions along a permutation.
+// conditions and as-of (how two elements compare and order), sort keys, range joins, the aggregates over a pair list, and
+// the window functions along a permutation.
 // Column descriptors as the kernels take them, the element helpers host and device share, and the launchers.
 #pragma once
 
@@ -260,6 +260,31 @@ uint32_t sort_passes(const SortCols& cols, uint32_t nCols);          // one per 
 // caller has checked what the header says the entry point refuses. nRows 0 enqueues nothing.
 hipError_t launch_sort_rows(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm, void* work, hipStream_t s);
 void sort_rows_host(const SortCols& cols, uint32_t nCols, uint64_t nRows, uint32_t* perm);     // sort_key around std::stable_sort
+
+// ---- range joins without an equality key (defined in hj_range.hip) -------------
+// The index of one column: perm = launch_sort_rows' ascending permutation of it, keys[q] = sort_key of the element of row
+// perm[q] in a plane of 4-byte words (widths 1, 2, 4) or 8-byte ones, head = rows indexed (the leading positions whose
+// element is valid and no NaN), NULL rows, NaN rows, key bytes. work: the sort's workspace for the one column.
+hipError_t launch_range_index(const SortCols& col, uint64_t nRows, uint32_t* perm, void* keys, uint32_t* head, void* work, hipStream_t s);
+void range_index_host(const SortCols& col, uint64_t nRows, uint32_t* perm, void* keys, uint32_t head[4]);
+// The term of a range call as the kernels take it (hj_range_term, include/htm_hashjoin.h, field for field)
+struct RangeTerm { const void *lo, *hi; const uint32_t *loValid, *hiValid; uint32_t width, type, flags, pick; };
+// How a call cuts its work: the index of nRows rows is searched through `pivots` keys, every stride-th (a power of two),
+// held in ldsBytes of LDS at most; a workgroup takes chunkRows S rows to their bounds, another tilePairs output positions.
+// The workspace: the pivots, the two bound planes, three planes of one 64-bit word per chunk, the difference plane of
+// nRows + 1 words and its scan sums. bytes is monotone in both arguments.
+struct RangeLayout { uint32_t pivots, stride, tilePairs, chunkRows, chunks, ldsBytes; size_t pivotBytes, boundBytes, chunkBytes, diffBytes, bytes; };
+RangeLayout range_layout(uint64_t nRows, uint64_t sRows);
+// S row i -> the pairs (sRowBase + i, perm[q]) for the positions q of the indexed prefix whose key lies in the row's
+// interval, or the one the pick keeps; to `to` as launch_pairs_where writes its kept pairs, without a cursor: the planes fill
+// from 0 in S-row order of the tiles. head is read on the device; an index of the other key width counts as empty. words:
+// four 64-bit words, written here -- pairs, S rows with a pair, S rows with a NULL or NaN bound, rows indexed. work:
+// range_layout(rRows, sRows).bytes. The caller has checked what the header says the entry point refuses.
+hipError_t launch_range_pairs(const void* keys, const uint32_t* perm, const uint32_t* head, uint32_t rRows, const RangeTerm& t, uint32_t sRows,
+                              uint32_t sRowBase, const PairSink& to, void* work, unsigned long long* words, hipStream_t s);
+// the same on host pointers, the pairs in S-row order and ascending positions; info: hj_range_pairs_host's (may be null)
+void range_pairs_host(const void* keys, const uint32_t* perm, const uint32_t* head, uint32_t rRows, const RangeTerm& t, uint32_t sRows,
+                      uint32_t sRowBase, const PairSink& to, uint64_t info[8]);
 
 // ---- aggregating joins: COUNT / SUM / MIN / MAX per group row (hj_prj_agg.hip, hj_agg.hip) ----
 // The columns of a call as the kernels take them, by value in the kernel arguments: the ops (hj_agg_spec; sgn: HJ_AGG_SIGNED),

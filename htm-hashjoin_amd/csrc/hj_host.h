@@ -37,6 +37,7 @@ enum Buf {
     B_GROUPS_WORK,              // hj_key_groups_dev: its workspace (key_groups_work_bytes(nRows): the table, the first-row plane, the ranks, the sweep's counts), grown by the call
     B_SORT_WORK,                // hj_sort_rows_dev: its workspace (sort_layout(nRows, key bytes).bytes: two key planes, two row planes, the histogram, the scan sums), grown by the call
     B_WINDOW_WORK,              // hj_window_rows_dev: its workspace (window_layout(nPos).bytes: the head bytes, the end plane, the chunk summaries), grown by the call
+    B_RANGE_WORK,               // hj_range_pairs_dev: its workspace (range_layout(rRows, sRows).bytes: the pivots, the bound planes, the chunk words, the difference plane), grown by the call
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
     B_STAGE_R, B_STAGE_S,       // staging for hj_run
@@ -66,9 +67,10 @@ struct DevBuf {
 //   CALL_PAIRS_AGG              the pairs applied, the pairs skipped
 //   CALL_GROUPS                 probe steps, word collisions, NULL-keyed rows, the failure word
 //   CALL_WINDOW                 partitions, peer runs, skipped entries
+//   CALL_RANGE                  pairs (64 bits, exact), S rows with a pair, S rows with a NULL or NaN bound, rows indexed
 // CALL_R_ROWS, CALL_MARK_ROWS and CALL_GROUPS find their total in their sweep's workspace, CALL_PRJ_AGG its words in front of
-// buf[B_AGG], CALL_SORT counts nothing on the device.
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_COUNT };
+// buf[B_AGG], CALL_SORT counts nothing on the device, CALL_RANGE_INDEX leaves its counts in the caller's dHead (extra[0]).
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_RANGE_INDEX, CALL_RANGE, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)

@@ -557,6 +557,40 @@ class HashJoinContext:
         call in microseconds, pairs it dropped as NO_ROW or out of range)."""
         return self._info(lib.hj_asof_info)
 
+    # ---- range joins without an equality key -----------------------------------------
+    def range_index(self, col, n, d_perm, d_keys, d_head):
+        """hj_range_index_dev: the index of ONE column for range_pairs. col = (values_ptr, valid_ptr, width, type) of device
+        pointers as a column of sort_rows (no flags: ascending, NULLs last). d_perm: n uint32 (the ascending, stable
+        permutation), d_keys: n order keys of 4 bytes (widths 1, 2, 4) or 8, d_head: 4 uint32 -- rows indexed (valid and no
+        NaN: a prefix of the order), NULL rows, NaN rows, key bytes. The three planes are the caller's, their content the
+        library's. Asynchronous; needs no reserve and no table; the workspace is sort_rows'."""
+        arr, _ = _sort_cols([tuple(col)[:4] + (0,)])
+        self._check(lib.hj_range_index_dev(self._h, arr, n, _vp(d_perm), _vp(d_keys), _vp(d_head)))
+
+    def range_index_info(self):
+        """hj_range_index_info (waits for the stream), about the last range_index, whose d_head must still be allocated:
+        (rows indexed, NULL rows, the device time of the call in microseconds, NaN rows)."""
+        return self._info(lib.hj_range_index_info)
+
+    def range_pairs(self, d_keys, d_perm, d_head, r_rows, term, s_rows, s_row_base, d_out_s, d_out_r, capacity, d_s_marks=0, d_r_marks=0):
+        """hj_range_pairs_dev: for S row i < s_rows the pairs (s_row_base + i, r) of every indexed R row r whose value lies
+        between lo[i] and hi[i]. term = (lo_ptr, hi_ptr, width, type[, flags, pick, lo_valid, hi_valid]) of device pointers:
+        a bound of 0 is no bound on that side (not both), flags HJ_RANGE_LO_OPEN | HJ_RANGE_HI_OPEN, pick HJ_RANGE_ALL /
+        FIRST (the smallest R value in the range) / LAST (the largest; ties to the lowest R row). The index (range_index)
+        is read on the device: no wait in between. A NULL or NaN bound matches nothing. Outputs and marks as pairs_where;
+        capacity 0 with outputs 0 sizes or marks only; the total is exact in 64 bits. Asynchronous; needs no reserve."""
+        t = tuple(term) + (0,) * (8 - len(term))
+        arr = _lib.hj_range_term()
+        arr.lo, arr.hi, arr.width, arr.type, arr.flags, arr.pick = t[0] or None, t[1] or None, t[2], t[3], t[4], t[5]
+        arr.loValid, arr.hiValid = t[6] or None, t[7] or None
+        self._check(lib.hj_range_pairs_dev(self._h, _vp(d_keys), _vp(d_perm), _vp(d_head), r_rows, C.byref(arr), s_rows, s_row_base,
+                                           _vp(d_out_s), _vp(d_out_r), capacity, _vp(d_s_marks), _vp(d_r_marks)))
+
+    def range_pairs_info(self):
+        """hj_range_pairs_info (waits for the stream), about the last range_pairs: (pairs, pairs written, its device time in
+        microseconds, S rows with a pair, S rows with a NULL or NaN bound, rows indexed, 0, 0)."""
+        return self._info(lib.hj_range_pairs_info, 8)
+
     def mark_rows(self, d_marks, rows, row_base, which, d_out, capacity):
         """hj_mark_rows_dev: r_rows on a caller's plane. The rows row_base + i, i < rows, whose bit i of d_marks is clear
         (which = 0, HJ_R_UNMATCHED) or set (1, HJ_R_MATCHED), ascending, into the device uint32 array d_out of `capacity`

@@ -816,6 +816,90 @@ int hj_window_rows_host(const uint32_t *perm, uint64_t nPos, uint64_t nRows, con
  * chunks (at most 4096 at any nPos: one workgroup scans their summaries), out[3] = workspace bytes (one head byte and one
  * 4-byte end per position, and the chunk summaries; monotone in nPos). HJ_ERR_INVALID for out NULL or nPos above 2^32 - 2. */
 int hj_window_layout_info(uint64_t nPos, uint64_t out[4]);
+/* ---- range joins without an equality key: ... ON R.y BETWEEN S.lo AND S.hi ----
+ * Every join above starts from an equality on a join word. These two calls join on an ORDER condition alone: events
+ * against sessions, packets against address blocks, readings against calibration periods, one bound (R.y < S.x), and the
+ * as-of join without a `by` key (hj_range_pick). The same join with the sides swapped (S.x BETWEEN R.lo AND R.hi) is this
+ * one with S's points indexed and R's intervals probing.
+ *
+ * THE INDEX of R's column is the caller's: three device planes, built once by hj_range_index_dev and probed by any number
+ * of hj_range_pairs_dev calls, one per slice of S.
+ *   dPerm[0 .. nRows)  hj_sort_rows_dev's ascending, stable permutation of the one column (NULLs last, every NaN above
+ *                      +inf in front of them); col->flags must be 0: HJ_SORT_DESC and HJ_SORT_NULLS_FIRST are refused
+ *   dKeys[0 .. nRows)  the order key of the element of row dPerm[q], in a plane of 4-byte words (widths 1, 2 and 4) or of
+ *                      8-byte words (width 8)
+ *   dHead[0 .. 4)      rows indexed, NULL rows, NaN rows, key bytes (4 or 8)
+ * The indexed rows are the leading positions whose element is valid and no NaN: a NULL or a NaN lies in no range, and the
+ * ascending order puts them last, so the indexed rows are a prefix and dHead[0] is its length. The CONTENT of the three
+ * planes belongs to the library: a caller that edits them gets undefined pairs (never a write outside the outputs: the
+ * range call takes no more than rRows rows of them whatever dHead says). Asynchronous on the context's stream; the
+ * workspace is hj_sort_rows_dev's; needs no hj_reserve, no table and no state. HJ_ERR_INVALID: what hj_sort_rows_dev
+ * refuses of one column, flags other than 0, nRows above 2^32 - 2, dKeys NULL or not aligned to its key bytes with
+ * nRows > 0, dHead NULL or not 4-byte aligned. nRows 0 writes dHead alone. */
+int hj_range_index_dev(hj_ctx *ctx, const hj_sort_col *col, uint64_t nRows, uint32_t *dPerm, void *dKeys, uint32_t *dHead);
+/* Waits for the stream. About the last hj_range_index_dev, whose dHead must still be allocated: out[0] = rows indexed,
+ * out[1] = NULL rows, out[2] = the device time of the call in microseconds (rounded), out[3] = NaN rows. All 0 before
+ * the first call. */
+int hj_range_index_info(hj_ctx *ctx, uint64_t out[4]);
+/* The same index on host pointers: no context, no device (the order key is the kernels', the order hj_sort_rows_host's).
+ * HJ_ERR_INVALID as hj_range_index_dev; a refused call writes nothing. */
+int hj_range_index_host(const hj_sort_col *col, uint64_t nRows, uint32_t *perm, void *keys, uint32_t head[4]);
+/* How the range call cuts an index of nRows rows probed by sRows S rows; a pure function, no context and no device:
+ * out[0] = pivots (every out[1]-th key of the index, searched in LDS), out[1] = the pivot stride (a power of two, at least
+ * 16: what is left of a search runs over stride - 1 keys in global memory), out[2] = the pair tile (output positions one
+ * workgroup of the expansion owns), out[3] = workspace bytes (monotone in both arguments), out[4] = chunk rows (S rows one
+ * workgroup takes to their bounds), out[5] = chunks, out[6] = the LDS bytes the pivots may take (8 * out[0] at most),
+ * out[7] = 0. HJ_ERR_INVALID for out NULL or a row count above 2^32 - 2. */
+int hj_range_layout_info(uint64_t nRows, uint64_t sRows, uint64_t out[8]);
+/* THE RANGE STEP. For S row i, i in [0, sRows), the pairs are (sRowBase + i, r) for every indexed R row r whose value
+ * lies in [lo[i], hi[i]], the brackets as the flags say. The comparison is hj_pairs_where_dev's: integers by width and
+ * signedness, floats as IEEE-754 values with -0.0 == 0.0. A NULL or a NaN bound makes the row match nothing; such rows are
+ * counted apart. An empty interval (lo > hi, or lo == hi with an open side) matches nothing. An open bound is a search
+ * for the other end of the run of equal keys, never +-1 on the value: x < UINT64_MAX and x > INT64_MIN are right.
+ *   HJ_RANGE_ALL    every pair
+ *   HJ_RANGE_FIRST  per S row the one pair with the smallest R value in the range
+ *   HJ_RANGE_LAST   ... with the largest; with lo NULL this is the backward as-of join without a key
+ * Ties on the value go to the lowest R row, as in hj_pairs_asof_dev.
+ * Output and marks are hj_probe_pairs_dev's and hj_pairs_where_dev's: the planes fill from 0 without holes; pairs at or
+ * beyond `capacity` are counted and not written; the order is unspecified, the multiset exact; dOutS[j] carries the base.
+ * Bit i of dSMarks is set when S row i has at least one pair, bit r of dRMarks when some S row of the call has r in its
+ * range (FIRST / LAST: when r is the picked row), written or cut by the capacity alike. Bits only go 0 -> 1; nothing is
+ * written behind word ceil(rows / 32) - 1; either plane may be NULL. The R marks cost O(sRows + rRows) whatever the pairs.
+ * Capacity 0 with NULL outputs is the sizing or mark-only pass. THE TOTAL IS EXACT IN 64 BITS and can exceed 2^32.
+ * dHead is read ON THE DEVICE: an index and its probes are enqueued back to back with no host wait in between. An index
+ * whose key bytes are not the term's (dHead[3]) counts as empty. Asynchronous on the context's stream; `term` is read
+ * before the call returns; needs no hj_reserve, no table and no state, and touches no other call's counters; the
+ * workspace belongs to the context and grows with rRows and sRows (hj_range_layout_info).
+ * HJ_ERR_INVALID: sRows or rRows above 2^32 - 2; capacity above 2^32 - 1; term NULL; lo and hi both NULL; a type that is
+ * no hj_val_type or a width the type does not have; flags with other bits; pick above HJ_RANGE_LAST; a bound not aligned
+ * to its width; a validity, output or mark pointer not 4-byte aligned; with rRows > 0: dPerm, dKeys or dHead NULL or
+ * misaligned; with rows on both sides and capacity > 0: an output pointer NULL.
+ * OUT OF SCOPE: strings; an equality key in the same step (that is where= behind a key join); conditions on two
+ * different R columns in one step (an interval on R's side is the same call with the sides swapped); general
+ * two-inequality joins; a sorted output order; more than one device. */
+#define HJ_RANGE_LO_OPEN 0x1u     /* lo <  R.y  instead of  lo <= R.y */
+#define HJ_RANGE_HI_OPEN 0x2u     /* R.y <  hi  instead of  R.y <= hi */
+typedef enum { HJ_RANGE_ALL = 0, HJ_RANGE_FIRST = 1, HJ_RANGE_LAST = 2 } hj_range_pick;
+typedef struct {
+    const void     *lo, *hi;            /* sRows elements each; NULL: no bound on that side (not both)     */
+    const uint32_t *loValid, *hiValid;  /* one bit per S row; NULL: no NULLs                               */
+    uint32_t        width, type;        /* the indexed column's                                            */
+    uint32_t        flags, pick;        /* HJ_RANGE_*_OPEN; an hj_range_pick                               */
+} hj_range_term;                        /* 48 bytes */
+int hj_range_pairs_dev(hj_ctx *ctx, const void *dKeys, const uint32_t *dPerm, const uint32_t *dHead, uint64_t rRows,
+                       const hj_range_term *term, uint64_t sRows, uint32_t sRowBase,
+                       uint32_t *dOutS, uint32_t *dOutR, uint64_t capacity, uint32_t *dSMarks, uint32_t *dRMarks);
+/* Waits for the stream. About the last hj_range_pairs_dev: out[0] = pairs (64 bits, exact), out[1] = pairs written
+ * (min(out[0], capacity)), out[2] = the device time of the call in microseconds (rounded), out[3] = S rows with a pair,
+ * out[4] = S rows with a NULL or NaN bound, out[5] = rows indexed, out[6] = out[7] = 0. All 0 before the first call. */
+int hj_range_pairs_info(hj_ctx *ctx, uint64_t out[8]);
+/* The same step on host pointers: no context, no device (the order key is the kernels', around std::lower_bound and
+ * std::upper_bound); the pairs in S-row order, ascending index positions inside a row. `info` (may be NULL) is filled as
+ * hj_range_pairs_info fills it, info[2] = 0. HJ_ERR_INVALID as hj_range_pairs_dev, and for an index whose key bytes
+ * (head[3]) are not the term's; a refused call writes nothing. */
+int hj_range_pairs_host(const void *keys, const uint32_t *perm, const uint32_t *head, uint64_t rRows,
+                        const hj_range_term *term, uint64_t sRows, uint32_t sRowBase,
+                        uint32_t *outS, uint32_t *outR, uint64_t capacity, uint32_t *sMarks, uint32_t *rMarks, uint64_t info[8]);
 /* PRJ (parallel_radix_join.c:808-1122): radix-partitions dR and dS and joins
  * each partition pair in LDS. Asynchronous. dS may be NULL (fork behaviour:
  * R-side only, checksum only). */
