@@ -12,13 +12,13 @@ from ._lib import (  # noqa: F401
     HJ_WHERE_MAX_TERMS, HJ_CMP_EQ, HJ_CMP_NE, HJ_CMP_LT, HJ_CMP_LE, HJ_CMP_GT, HJ_CMP_GE, CMP_OPS, HJ_VAL_UINT, HJ_VAL_INT, HJ_VAL_FLOAT,
     hj_where_term, ASOF_OPS, hj_asof_term,
     HJ_SORT_MAX_COLS, HJ_SORT_DESC, HJ_SORT_NULLS_FIRST, hj_sort_col,
-    HJ_WIN_MAX_FUNCS, hj_win_func,
+    HJ_WIN_MAX_FUNCS, hj_win_func, HJ_FRAME_MAX_FUNCS, HJ_FRAME_UNBOUNDED_LO, HJ_FRAME_UNBOUNDED_HI, hj_frame_func,
     HJ_RANGE_LO_OPEN, HJ_RANGE_HI_OPEN, HJ_RANGE_ALL, HJ_RANGE_FIRST, HJ_RANGE_LAST, RANGE_PICKS, hj_range_term,
     HJ_AGG_MAX_COLS, HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX, HJ_AGG_SIGNED, hj_agg_spec, hj_agg_src, hj_agg_col,
 )
 from .engine import (  # noqa: F401
     HashJoinError, HashJoinContext, NoCCHashBuild, AtomicHashBuild, HTMHashBuild, PRO, prj_agg_layout_info,
-    generate_data, generate_relation, device_count, window_layout_info, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, ring_word_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
+    generate_data, generate_relation, device_count, window_layout_info, frames_layout_info, wave_layout_info, htm_chain_layout_info, own_layout_info, slot_codes_info, ring_word_info, SHARD_ONE_BASED, BUCKET_DTYPE, NO_ROW,
 )
 from .columns import KeyColumn, key_hash_host, key_hash2_host  # noqa: F401
 from .conditions import pairs_where_host, pairs_asof_host  # noqa: F401

@@ -65,6 +65,9 @@ RANGE_PICKS = {"all": HJ_RANGE_ALL, "first": HJ_RANGE_FIRST, "last": HJ_RANGE_LA
 HJ_WIN_MAX_FUNCS = 8
 (HJ_WIN_ROW_NUMBER, HJ_WIN_RANK, HJ_WIN_DENSE_RANK, HJ_WIN_PART_ROWS, HJ_WIN_LAG, HJ_WIN_LEAD, HJ_WIN_FIRST_ROW, HJ_WIN_LAST_ROW,
  HJ_WIN_RUN_COUNT, HJ_WIN_RUN_SUM, HJ_WIN_RUN_MIN, HJ_WIN_RUN_MAX) = range(12)
+# hj_window_frames_dev: functions of one call, and the frame bits of hj_frame_func.flags (beside HJ_AGG_SIGNED)
+HJ_FRAME_MAX_FUNCS = 8
+HJ_FRAME_UNBOUNDED_LO, HJ_FRAME_UNBOUNDED_HI = 0x2, 0x4
 # aggregating joins (hj_agg_op, hj_agg_spec.flags)
 HJ_AGG_MAX_COLS = 4
 HJ_AGG_COUNT, HJ_AGG_SUM, HJ_AGG_MIN, HJ_AGG_MAX = 0, 1, 2, 3
@@ -196,6 +199,20 @@ class hj_range_term(C.Structure):
     ]
 
 
+class hj_frame_func(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("srcValid", C.c_void_p),
+        ("out", C.c_void_p),
+        ("lo", C.c_int64),
+        ("hi", C.c_int64),
+        ("op", C.c_uint32),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class hj_win_func(C.Structure):
     _fields_ = [
         ("src", C.c_void_p),
@@ -280,6 +297,10 @@ def _declare(lib):
         "hj_window_rows_info": ([vp, P(u64)], i32),
         "hj_window_rows_host": ([vp, u64, u64, vp, P(hj_sort_col), u32, P(hj_win_func), u32, P(u64)], i32),
         "hj_window_layout_info": ([u64, P(u64)], i32),
+        "hj_window_frames_dev": ([vp, vp, u64, u64, vp, P(hj_frame_func), u32], i32),
+        "hj_window_frames_info": ([vp, P(u64)], i32),
+        "hj_window_frames_host": ([vp, u64, u64, vp, P(hj_frame_func), u32, P(u64)], i32),
+        "hj_frames_layout_info": ([u64, P(u64)], i32),
         "hj_range_index_dev": ([vp, P(hj_sort_col), u64, vp, vp, vp], i32),
         "hj_range_index_info": ([vp, P(u64)], i32),
         "hj_range_index_host": ([P(hj_sort_col), u64, vp, vp, vp], i32),

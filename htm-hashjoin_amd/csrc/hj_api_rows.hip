@@ -1,8 +1,8 @@
 // hj_api_rows.hip -- the C ABI's calls on rows: the R-side match marks and their sweep, the gather through a row map, the
 // joins on real key columns (hash, verify, sweep of a caller's plane), the rows of one table grouped by their key columns
-// and sorted by them, the window functions along a permutation, the join conditions beyond equality, the as-of step, the
-// range joins without an equality key, the reduction over a pair list, and the *_info entry point of every call that has
-// a record (hj_host.h: CallRecord).
+// and sorted by them, the window functions along a permutation and their sliding frames, the join conditions beyond
+// equality, the as-of step, the range joins without an equality key, the reduction over a pair list, and the *_info entry
+// point of every call that has a record (hj_host.h: CallRecord).
 // Host-side glue only, and the same three parts for every recorded call: its checks, which give the message of the first
 // thing wrong; recorded_call, the one frame around its launch; call_info, the one reader of what it left.
 #include "hj_host.h"
@@ -626,6 +626,87 @@ int hj_window_layout_info(uint64_t nPos, uint64_t out[4])
 {
     if (!out || nPos > 0xFFFFFFFEull) return HJ_ERR_INVALID;
     const WindowLayout l = window_layout(nPos);
+    out[0] = l.tilePos; out[1] = l.chunkPos; out[2] = l.chunks; out[3] = l.bytes;
+    return HJ_OK;
+}
+
+// ---- sliding window frames over the same runs (hj_frames.hip) -------------------
+// hj_window_frames_dev's and hj_window_frames_host's arguments -> the kernels' functions; the message of what is wrong, or nullptr
+static const char* frames_args(const uint32_t* perm, uint64_t nPos, uint64_t nRows, const uint32_t* part, const hj_frame_func* funcs, uint32_t nFuncs,
+                               FrameFunc* w)
+{
+    constexpr int64_t kMaxOffset = 0xFFFFFFFFll;
+    if (nFuncs == 0 || nFuncs > HJ_FRAME_MAX_FUNCS) return "nFuncs must be 1 .. HJ_FRAME_MAX_FUNCS";
+    if (!funcs) return "funcs NULL";
+    if (nPos > 0xFFFFFFFEull || nRows > 0xFFFFFFFEull) return "nPos or nRows above 2^32 - 2";
+    if (!perm && nPos > nRows) return "dPerm NULL with nPos > nRows";
+    if (!word_ptr_ok(perm) || !word_ptr_ok(part)) return "dPerm or dPart not 4-byte aligned";
+    for (uint32_t i = 0; i < nFuncs; ++i) {
+        const hj_frame_func& f = funcs[i];
+        if (f.op > HJ_AGG_MAX) return "op must be an hj_agg_op";
+        const bool reads = f.op != HJ_AGG_COUNT;
+        if (!(f.width == 4 || f.width == 8 || (!reads && f.width == 0))) return "a width that the op does not have (SUM / MIN / MAX: 4 or 8; COUNT: 0, 4 or 8)";
+        if (f.flags & ~(HJ_AGG_SIGNED | HJ_FRAME_UNBOUNDED_LO | HJ_FRAME_UNBOUNDED_HI))
+            return "hj_frame_func.flags has bits other than HJ_AGG_SIGNED, HJ_FRAME_UNBOUNDED_LO and HJ_FRAME_UNBOUNDED_HI";
+        if (f.reserved) return "hj_frame_func.reserved must be 0";
+        const bool unbLo = f.flags & HJ_FRAME_UNBOUNDED_LO, unbHi = f.flags & HJ_FRAME_UNBOUNDED_HI;
+        if (f.lo < -kMaxOffset || f.lo > kMaxOffset || f.hi < -kMaxOffset || f.hi > kMaxOffset) return "lo or hi outside [-(2^32 - 1), 2^32 - 1]";
+        if ((unbLo && f.lo) || (unbHi && f.hi)) return "a non-zero offset beside its HJ_FRAME_UNBOUNDED flag";
+        if (!unbLo && !unbHi && f.lo > f.hi) return "lo > hi";
+        if (!col_ptr_ok(f.out, 8)) return "an out that is NULL or not 8-byte aligned";
+        if (reads && nRows && !col_ptr_ok(f.src, f.width)) return "a src that is NULL or not aligned to its width";
+        if (!word_ptr_ok(f.srcValid)) return "a srcValid that is not 4-byte aligned";
+        w[i] = FrameFunc{f.src, f.srcValid, f.out, f.lo, f.hi, f.op, f.width, f.flags & HJ_AGG_SIGNED, unbLo, unbHi};
+    }
+    return nullptr;
+}
+
+int hj_window_frames_dev(hj_ctx* c, const uint32_t* dPerm, uint64_t nPos, uint64_t nRows, const uint32_t* dPart, const hj_frame_func* funcs, uint32_t nFuncs)
+{
+    HJ_ENTER(c, true);
+    FrameFunc w[kFrameMaxFuncs];
+    if (const char* what = frames_args(dPerm, nPos, nRows, dPart, funcs, nFuncs, w)) return fail(c, HJ_ERR_INVALID, "hj_window_frames_dev", what);
+    const FramesLayout l = frames_layout(nPos);
+    const Facts facts = nPos ? Facts{0, nPos, {l.chunks, l.bytes}} : Facts{};
+    return recorded_call(c, CALL_FRAMES, 0, INIT_TIMED, Work{B_FRAMES_WORK, nPos ? l.bytes : 0}, facts, [&](unsigned long long* totals) {
+        return launch_window_frames(dPerm, nPos, (uint32_t)nRows, dPart, w, nFuncs, c->buf[B_FRAMES_WORK].p, totals, c->stream);
+    });
+}
+
+int hj_window_frames_info(hj_ctx* c, uint64_t out[8])
+{
+    HJ_ENTER(c, out);
+    const CallRecord& r = c->call[CALL_FRAMES];
+    for (int i = 4; i < 8; ++i) out[i] = 0;
+    uint64_t t[4];
+    unsigned long long totals[kCallWords];
+    if (const int rc = call_info(c, CALL_FRAMES, nullptr, r.rows ? totals : nullptr, t)) return rc;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!r.called || !r.rows) return HJ_OK;                     // no position: nothing was enqueued between the two events
+    out[0] = r.rows; out[1] = totals[0]; out[3] = t[2]; out[4] = totals[2];
+    out[5] = r.extra[0]; out[6] = r.extra[1];
+    return HJ_OK;
+}
+
+int hj_window_frames_host(const uint32_t* perm, uint64_t nPos, uint64_t nRows, const uint32_t* part, const hj_frame_func* funcs, uint32_t nFuncs,
+                          uint64_t out[8])
+{
+    FrameFunc w[kFrameMaxFuncs];
+    if (frames_args(perm, nPos, nRows, part, funcs, nFuncs, w)) return HJ_ERR_INVALID;
+    uint64_t totals[3];
+    window_frames_host(perm, nPos, (uint32_t)nRows, part, w, nFuncs, totals);
+    if (!out) return HJ_OK;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!nPos) return HJ_OK;
+    const FramesLayout l = frames_layout(nPos);
+    out[0] = nPos; out[1] = totals[0]; out[4] = totals[2]; out[5] = l.chunks; out[6] = l.bytes;
+    return HJ_OK;
+}
+
+int hj_frames_layout_info(uint64_t nPos, uint64_t out[4])
+{
+    if (!out || nPos > 0xFFFFFFFEull) return HJ_ERR_INVALID;
+    const FramesLayout l = frames_layout(nPos);
     out[0] = l.tilePos; out[1] = l.chunkPos; out[2] = l.chunks; out[3] = l.bytes;
     return HJ_OK;
 }

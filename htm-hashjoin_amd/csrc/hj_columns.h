@@ -414,5 +414,29 @@ hipError_t launch_window_rows(const uint32_t* perm, uint64_t nPos, uint32_t nRow
 // the same in one sequential loop over host pointers; totals as above
 void window_rows_host(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const SortCols& order, uint32_t nOrder,
                       const WinFuncs& funcs, uint32_t nFuncs, uint64_t totals[3]);
+// the head bytes alone (k_win_heads): heads[p] = win_head(p) for p in [0, nPos). What the frames below start from.
+void launch_window_heads(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const SortCols& order, uint32_t nOrder,
+                         uint8_t* heads, hipStream_t s);
+
+// ---- sliding window frames over the same runs (defined in hj_frames.hip) ----
+// One function of a call (hj_frame_func, include/htm_hashjoin.h): op an hj_agg_op, sgn HJ_AGG_SIGNED, unbLo / unbHi the
+// two HJ_FRAME_UNBOUNDED_* flags (their offset is 0 then), lo <= hi in [-(2^32 - 1), 2^32 - 1] otherwise.
+constexpr uint32_t kFrameMaxFuncs = 8;        // HJ_FRAME_MAX_FUNCS
+struct FrameFunc { const void* src; const uint32_t* valid; void* out; long long lo, hi; uint32_t op, width, sgn, unbLo, unbHi; };
+// How a call cuts nPos positions: window_layout's tiles and chunks. The workspace: one head byte and one 4-byte end per
+// position, TWO 8-byte planes per position that the functions of a call share one after another (the values, which the
+// backward scan turns into H in place, and G), and the chunk summaries (their size does not depend on nPos): 21 bytes per
+// position, whatever nFuncs. bytes is monotone in nPos.
+struct FramesLayout { uint32_t tilePos, chunkPos, chunks; size_t headBytes, endBytes, planeBytes, sumBytes, bytes; };
+FramesLayout frames_layout(uint64_t nPos);
+// out[row(p)] of every function for p in [0, nPos): see hj_window_frames_dev. work: frames_layout(nPos).bytes. totals: three
+// 64-bit words, written here -- partitions, 0, entries skipped. The caller has checked what the header says the entry
+// point refuses. nPos 0 enqueues nothing.
+hipError_t launch_window_frames(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const FrameFunc* funcs, uint32_t nFuncs,
+                                void* work, unsigned long long* totals, hipStream_t s);
+// The same on host pointers by ANOTHER algorithm: one sequential loop per function, a running window for COUNT / SUM and a
+// monotonic deque for MIN / MAX; totals as above.
+void window_frames_host(const uint32_t* perm, uint64_t nPos, uint32_t nRows, const uint32_t* part, const FrameFunc* funcs, uint32_t nFuncs,
+                        uint64_t totals[3]);
 
 }  // namespace hj

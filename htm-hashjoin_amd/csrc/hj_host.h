@@ -37,6 +37,7 @@ enum Buf {
     B_GROUPS_WORK,              // hj_key_groups_dev: its workspace (key_groups_work_bytes(nRows): the table, the first-row plane, the ranks, the sweep's counts), grown by the call
     B_SORT_WORK,                // hj_sort_rows_dev: its workspace (sort_layout(nRows, key bytes).bytes: two key planes, two row planes, the histogram, the scan sums), grown by the call
     B_WINDOW_WORK,              // hj_window_rows_dev: its workspace (window_layout(nPos).bytes: the head bytes, the end plane, the chunk summaries), grown by the call
+    B_FRAMES_WORK,              // hj_window_frames_dev: its workspace (frames_layout(nPos).bytes: the head bytes, the end plane, two 8-byte planes, the chunk summaries), grown by the call
     B_RANGE_WORK,               // hj_range_pairs_dev: its workspace (range_layout(rRows, sRows).bytes: the pivots, the bound planes, the chunk words, the difference plane), grown by the call
     B_TMP, B_PART_R, B_PART_S, B_WORK,          // PRJ workspace
     B_PRJ_RES,                  // resident R: its final offsets / fragment counts and the work-item list (prj_resident_carve)
@@ -67,15 +68,16 @@ struct DevBuf {
 //   CALL_PAIRS_AGG              the pairs applied, the pairs skipped
 //   CALL_GROUPS                 probe steps, word collisions, NULL-keyed rows, the failure word
 //   CALL_WINDOW                 partitions, peer runs, skipped entries
+//   CALL_FRAMES                 partitions, 0, skipped entries
 //   CALL_RANGE                  pairs (64 bits, exact), S rows with a pair, S rows with a NULL or NaN bound, rows indexed
 // CALL_R_ROWS, CALL_MARK_ROWS and CALL_GROUPS find their total in their sweep's workspace, CALL_PRJ_AGG its words in front of
 // buf[B_AGG], CALL_SORT counts nothing on the device, CALL_RANGE_INDEX leaves its counts in the caller's dHead (extra[0]).
-enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_RANGE_INDEX, CALL_RANGE, CALL_COUNT };
+enum Call { CALL_PAIRS, CALL_R_ROWS, CALL_GATHER, CALL_GATHER2, CALL_VERIFY, CALL_WHERE, CALL_ASOF, CALL_MARK_ROWS, CALL_PRJ_AGG, CALL_PAIRS_AGG, CALL_GROUPS, CALL_SORT, CALL_WINDOW, CALL_RANGE_INDEX, CALL_RANGE, CALL_FRAMES, CALL_COUNT };
 struct CallRecord {
     bool called = false, timed = false;
     uint64_t capacity = 0, rows = 0;            // rows: the call's S tuples (pairs), map rows (gather), plane rows (mark rows)
     uint32_t kind = 0;                          // pairs: the hj_join_kind
-    uint64_t extra[4] = {0, 0, 0, 0};           // sort: passes, chunks, chunkRows, workspace bytes; window: chunks, workspace bytes
+    uint64_t extra[4] = {0, 0, 0, 0};           // sort: passes, chunks, chunkRows, workspace bytes; window and frames: chunks, workspace bytes
     hipEvent_t ev[2] = {nullptr, nullptr};      // the first in front of the call's work, the second (call_end) behind it
 };
 constexpr uint32_t kCallWords = 16;

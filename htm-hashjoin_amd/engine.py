@@ -216,6 +216,29 @@ def window_layout_info(n_pos):
     return {"tile": int(out[0]), "chunk": int(out[1]), "chunks": int(out[2]), "workspace_bytes": int(out[3])}
 
 
+def _frame_funcs(funcs):
+    """[(op, out_ptr, lo, hi[, src_ptr, valid_ptr, width, flags])], lo / hi integers or None (unbounded: the flag is set and
+    the offset 0), whatever follows hi optional (0) -> (hj_frame_func array, its length)"""
+    funcs = [tuple(f) + (0,) * (8 - len(f)) for f in funcs]
+    arr = (_lib.hj_frame_func * max(len(funcs), 1))()
+    for a, (op, out, lo, hi, src, valid, width, flags) in zip(arr, funcs):
+        a.src, a.srcValid, a.out = src or None, valid or None, out or None
+        a.lo, a.hi = 0 if lo is None else int(lo), 0 if hi is None else int(hi)
+        a.op, a.width, a.reserved = op, width, 0
+        a.flags = flags | (_lib.HJ_FRAME_UNBOUNDED_LO if lo is None else 0) | (_lib.HJ_FRAME_UNBOUNDED_HI if hi is None else 0)
+    return arr, len(funcs)
+
+
+def frames_layout_info(n_pos):
+    """hj_frames_layout_info: how hj_window_frames_dev cuts n_pos positions -- tile positions, chunk positions, chunks,
+    workspace bytes (at most 32 per position plus 1 MiB, whatever the functions). Host-only; no device."""
+    out = (C.c_uint64 * 4)()
+    rc = lib.hj_frames_layout_info(int(n_pos), out)
+    if rc != _lib.HJ_OK:
+        raise HashJoinError(rc, "hj_frames_layout_info")
+    return {"tile": int(out[0]), "chunk": int(out[1]), "chunks": int(out[2]), "workspace_bytes": int(out[3])}
+
+
 def _key_cols(cols):
     """[(s_ptr, r_ptr, width)] -> (hj_key_col array, its length)"""
     cols = list(cols)
@@ -517,6 +540,25 @@ class HashJoinContext:
         """hj_window_rows_info (waits for the stream), about the last window_rows: positions, partitions, peer_runs, the
         device time of the whole call (us), skipped entries, chunks, workspace_bytes"""
         return dict(zip(_WINDOW_ROWS_INFO, self._info(lib.hj_window_rows_info, 8)))
+
+    # ---- sliding window frames over the same runs -------------------------------------
+    def window_frames(self, d_perm, n_pos, n_rows, d_part, funcs):
+        """hj_window_frames_dev: COUNT / SUM / MIN / MAX OVER (PARTITION BY .. ORDER BY .. ROWS BETWEEN lo AND hi) along
+        d_perm[0 .. n_pos) (0: the identity); positions, partitions (runs of equal d_part[row], 0: one value) and skipped
+        entries are window_rows'. funcs = 1 to HJ_FRAME_MAX_FUNCS tuples (op, out_ptr, lo, hi[, src_ptr, valid_ptr, width,
+        flags]): op an hj_agg_op, out n_rows entries of 8 bytes INDEXED BY ROW, lo <= hi the frame's ends relative to the
+        position (negative: preceding; None: unbounded on that side), the frame clamped to the partition; src of width 4
+        or 8 (flags HJ_AGG_SIGNED), valid_ptr the validity plane. An empty frame gives the op's identity and COUNT 0. A row
+        at no position keeps what its out entries held. Asynchronous; needs no reserve and no table; the workspace belongs
+        to the context (apart from window_rows') and grows with n_pos."""
+        f_arr, n_funcs = _frame_funcs(funcs)
+        self._check(lib.hj_window_frames_dev(self._h, _vp(d_perm), n_pos, n_rows, _vp(d_part), f_arr, n_funcs))
+
+    def window_frames_info(self):
+        """hj_window_frames_info (waits for the stream), about the last window_frames, under window_rows_info's names:
+        positions, partitions, peer_runs (always 0), the device time of the whole call (us), skipped entries, chunks,
+        workspace_bytes"""
+        return dict(zip(_WINDOW_ROWS_INFO, self._info(lib.hj_window_frames_info, 8)))
 
     # ---- join conditions beyond equality ------------------------------------------
     def pairs_where(self, d_map_s, d_map_r, n_pairs, s_row_base, s_rows, r_rows, terms, d_out_s, d_out_r, capacity,

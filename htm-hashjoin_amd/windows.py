@@ -1,6 +1,6 @@
 """Window functions over one table: f(...) OVER (PARTITION BY keys ORDER BY cols) (window_rows, window_rows_host) -- the
 groups' dense ids, the sort over (id, order columns), one segmented scan along the permutation, and a gather through the
-row maps it leaves."""
+row maps it leaves; sliding frames (ROWS BETWEEN lo AND hi) go along the same permutation through hj_window_frames_dev."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +9,7 @@ from . import _lib
 from ._lib import lib
 from .aggregates import _AGG_DTYPES
 from .columns import KeyColumn, _DevColumn, _fetch_map, _host_key_cols2, _ptr, _session, _table_columns, _take_key_column
-from .engine import HashJoinError, NO_ROW, _sort_cols, _win_funcs
+from .engine import HashJoinError, NO_ROW, _frame_funcs, _sort_cols, _win_funcs
 from .groups import _GroupedKeys, _group_key_columns
 from .joins import _gather_key_columns
 from .sorting import _SortedRows, _sort_columns
@@ -17,17 +17,21 @@ from .sorting import _SortedRows, _sort_columns
 _NUMBERS = {"row_number": _lib.HJ_WIN_ROW_NUMBER, "rank": _lib.HJ_WIN_RANK, "dense_rank": _lib.HJ_WIN_DENSE_RANK, "count": _lib.HJ_WIN_PART_ROWS}
 _MAPS = {"lag": _lib.HJ_WIN_LAG, "lead": _lib.HJ_WIN_LEAD, "first": _lib.HJ_WIN_FIRST_ROW, "last": _lib.HJ_WIN_LAST_ROW}
 _RUNS = {"cumsum": _lib.HJ_WIN_RUN_SUM, "cummin": _lib.HJ_WIN_RUN_MIN, "cummax": _lib.HJ_WIN_RUN_MAX}
+_FRAMES = {"sum": _lib.HJ_AGG_SUM, "min": _lib.HJ_AGG_MIN, "max": _lib.HJ_AGG_MAX, "mean": _lib.HJ_AGG_SUM}
+_FRAME_FAR = 0xFFFFFFFF
 _TAKEN = ("perm", "n_partitions", "null_rows")
 
 
 class _WindowPlan:
     """The functions of window_rows / window_rows_host, checked. funcs: the device functions, one dict each (op, src: a
-    column's name or None, width, flags, offset, dtype and fill of its plane), the wrapper's own RUN_COUNT of every source of
-    a cumsum / cummin / cummax behind the caller's; outputs: how the result dict is put together from their planes.
+    column's name or None, width, flags, offset, dtype and fill of its plane; frame: None for a function of hj_window_rows_dev,
+    (lo, hi) for one of hj_window_frames_dev, whose op is an hj_agg_op), the wrapper's own RUN_COUNT of every source of a
+    cumsum / cummin / cummax, and COUNT over the same frame of every framed sum / min / max / mean, behind the caller's;
+    outputs: how the result dict is put together from their planes.
     ValueError for what cannot be computed."""
 
     def __init__(self, fn, funcs, cols, n):
-        self.fn, self.n, self.funcs, self.outputs, self.counts = fn, n, [], [], {}
+        self.fn, self.n, self.funcs, self.outputs, self.counts = fn, n, [], [], {}           # counts: (source, frame) -> its count's function
         self.cols = _table_columns(fn, "the table's", cols, n)
         if not funcs:
             raise ValueError(f"{fn}: no functions")
@@ -53,12 +57,21 @@ class _WindowPlan:
                 src = self._column(out, args[0])
                 width, flags = self._agg_type(out, src)
                 self.outputs.append((out, "run", self._func(_RUNS[name], np.uint64, 0, src, width, flags), src))
+            elif name == "count" and len(args) == 3:
+                src = None if args[0] is None else self._column(out, args[0])
+                self.outputs.append((out, "cumcount", self._count(src, self._frame(out, args[1], args[2]))))
+            elif name in _FRAMES and len(args) == 3:
+                src, frame = self._column(out, args[0]), self._frame(out, args[1], args[2])
+                width, flags = self._agg_type(out, src)
+                self.outputs.append((out, "mean" if name == "mean" else "run", self._func(_FRAMES[name], np.uint64, 0, src, width, flags, frame=frame), src, frame))
             else:
                 raise ValueError(f"{fn}: function {out!r} is {spec!r}; 'row_number', 'rank', 'dense_rank', 'count', ('lag' | 'lead', column, k), "
-                                 "('first' | 'last', column), ('cumcount', column or None) and ('cumsum' | 'cummin' | 'cummax', column) exist")
+                                 "('first' | 'last', column), ('cumcount', column or None), ('cumsum' | 'cummin' | 'cummax', column) and, over the "
+                                 "frame of rows lo .. hi around the current one (None: unbounded), ('sum' | 'min' | 'max' | 'mean', column, lo, hi) "
+                                 "and ('count', column or None, lo, hi) exist")
         for _, kind, _, *src in list(self.outputs):
-            if kind == "run":
-                self._count(src[0])             # whether the frame held a value: the column's own running count
+            if kind in ("run", "mean"):
+                self._count(*src)               # whether the frame held a value: the column's own count over the same frame
 
     def _column(self, out, name):
         if not isinstance(name, str) or name not in self.cols:
@@ -73,18 +86,36 @@ class _WindowPlan:
                              "have running sums, minima and maxima (floating-point sums depend on their order)")
         return _AGG_DTYPES[dtype]
 
-    def _func(self, op, dtype, fill, src=None, width=0, flags=0, offset=0):
-        self.funcs.append({"op": op, "dtype": np.dtype(dtype), "fill": fill, "src": src, "width": width, "flags": flags, "offset": offset})
+    def _frame(self, out, lo, hi):
+        for x in (lo, hi):
+            if x is not None and (isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not -_FRAME_FAR <= int(x) <= _FRAME_FAR):
+                raise ValueError(f"{self.fn}: function {out!r}: the ends of a frame are integers in -(2^32 - 1) .. 2^32 - 1 or None, not {x!r}")
+        if lo is not None and hi is not None and int(lo) > int(hi):
+            raise ValueError(f"{self.fn}: function {out!r}: the frame starts at {lo} and ends at {hi}, in front of its start")
+        return (None if lo is None else int(lo), None if hi is None else int(hi))
+
+    def _func(self, op, dtype, fill, src=None, width=0, flags=0, offset=0, frame=None):
+        self.funcs.append({"op": op, "dtype": np.dtype(dtype), "fill": fill, "src": src, "width": width, "flags": flags, "offset": offset, "frame": frame})
         return len(self.funcs) - 1
 
-    def _count(self, src):
-        if src not in self.counts:
-            self.counts[src] = self._func(_lib.HJ_WIN_RUN_COUNT, np.uint64, 0, src)
-        return self.counts[src]
+    def _count(self, src, frame=None):
+        if (src, frame) not in self.counts:
+            self.counts[src, frame] = self._func(_lib.HJ_WIN_RUN_COUNT if frame is None else _lib.HJ_AGG_COUNT, np.uint64, 0, src, frame=frame)
+        return self.counts[src, frame]
+
+    def reads(self, i):
+        """function i reads its source's values, not only its validity"""
+        f = self.funcs[i]
+        return f["op"] in _RUNS.values() if f["frame"] is None else f["op"] != _lib.HJ_AGG_COUNT
 
     def rounds(self):
-        """the device functions in runs of at most HJ_WIN_MAX_FUNCS"""
-        return [list(range(i, min(i + _lib.HJ_WIN_MAX_FUNCS, len(self.funcs)))) for i in range(0, len(self.funcs), _lib.HJ_WIN_MAX_FUNCS)]
+        """the device functions call by call: (framed, their indices) -- those of hj_window_rows_dev in runs of at most
+        HJ_WIN_MAX_FUNCS, then those of hj_window_frames_dev in runs of at most HJ_FRAME_MAX_FUNCS"""
+        res = []
+        for framed, most in ((False, _lib.HJ_WIN_MAX_FUNCS), (True, _lib.HJ_FRAME_MAX_FUNCS)):
+            idx = [i for i, f in enumerate(self.funcs) if (f["frame"] is not None) == framed]
+            res += [(framed, idx[i:i + most]) for i in range(0, len(idx), most)]
+        return res
 
     def result(self, planes, take, perm, n_partitions, null_rows):
         """planes: one array per device function, indexed by row; take(column name, row map) -> the column's rows there"""
@@ -95,9 +126,12 @@ class _WindowPlan:
             elif kind == "map":
                 res[out] = take(src[0], planes[i])
             else:
-                valid = planes[self.counts[src[0]]] > 0
+                valid = planes[self.counts[tuple(src) if len(src) == 2 else (src[0], None)]] > 0
                 values = np.where(valid, planes[i], np.uint64(0))
-                res[out] = KeyColumn(values.view(np.int64) if self.funcs[i]["flags"] else values, valid)
+                values = values.view(np.int64) if self.funcs[i]["flags"] else values
+                if kind == "mean":                # of the sum as it stands in 64 bits, wrapped if it wrapped
+                    values = np.where(valid, values.astype(np.float64) / np.maximum(planes[self.counts[tuple(src)]], 1).astype(np.float64), 0.0)
+                res[out] = KeyColumn(values, valid)
         res.update(perm=perm, n_partitions=int(n_partitions), null_rows=int(null_rows))
         return res
 
@@ -163,17 +197,21 @@ def window_rows_host(funcs, partition_by=None, order_by=None, cols=None, descend
     srcs = {name: (c._whole()[0], c._whole()[2]) if isinstance(c, KeyColumn) else (c, None) for name, c in plan.cols.items()}
     planes = [np.full(n, f["fill"], dtype=f["dtype"]) for f in plan.funcs]
     o_arr, n_order = _sort_cols(o_desc)
-    for part in plan.rounds():
+    for framed, part in plan.rounds():
         desc = []
         for i in part:
             f = plan.funcs[i]
             v, words = srcs[f["src"]] if f["src"] is not None else (None, None)
-            reads = f["op"] in _RUNS.values()
-            desc.append((f["op"], planes[i].ctypes.data, _ptr(v) if reads else 0, _ptr(words), f["width"], f["flags"], f["offset"]))
-        f_arr, n_funcs = _win_funcs(desc)
-        rc = lib.hj_window_rows_host(_ptr(perm), n_pos, n, _ptr(ids), o_arr, n_order, f_arr, n_funcs, out)
+            ptrs = (_ptr(v) if plan.reads(i) else 0, _ptr(words), f["width"], f["flags"])
+            desc.append((f["op"], planes[i].ctypes.data) + (f["frame"] + ptrs if framed else ptrs + (f["offset"],)))
+        if framed:
+            f_arr, n_funcs = _frame_funcs(desc)
+            rc = lib.hj_window_frames_host(_ptr(perm), n_pos, n, _ptr(ids), f_arr, n_funcs, out)
+        else:
+            f_arr, n_funcs = _win_funcs(desc)
+            rc = lib.hj_window_rows_host(_ptr(perm), n_pos, n, _ptr(ids), o_arr, n_order, f_arr, n_funcs, out)
         if rc != _lib.HJ_OK:
-            raise HashJoinError(rc, "hj_window_rows_host")
+            raise HashJoinError(rc, "hj_window_frames_host" if framed else "hj_window_rows_host")
     del o_held, srcs
     rows = perm[:n_pos] if perm is not None else np.arange(n, dtype=np.uint32)
     return plan.result(planes, lambda name, idx: _take_key_column(plan.cols[name], idx), rows, out[1], null_rows)
@@ -196,9 +234,20 @@ def window_rows(funcs, partition_by=None, order_by=None, cols=None, descending=F
       ("cumsum" | "cummin" | "cummax", column)          over int32 / uint32 / int64 / uint64 values so far, the current row
                                                         included: a KeyColumn as group_by_columns returns SUM / MIN / MAX,
                                                         NULL where no valid value came yet; SUM wraps modulo 2^64
+      ("sum" | "min" | "max", column, lo, hi)           over the FRAME of rows lo .. hi around the current one in its partition
+                                                        (ROWS BETWEEN; integers relative to the row, negative: preceding,
+                                                        None: unbounded): ("sum", "v", -6, 0) is pandas' rolling(7,
+                                                        min_periods=1).sum(), ("max", "v", None, None) transform("max"),
+                                                        (-3, -1) leaves the row itself out. A KeyColumn as cumsum returns, NULL
+                                                        where the frame held no valid value
+      ("count", column or None, lo, hi)                 uint64 per row: the valid values in the frame, None: its rows
+      ("mean", column, lo, hi)                          float64 KeyColumn: the frame's sum over its count, NULL where the
+                                                        count is 0. The mean of the WRAPPED sum: a sum that left 64 bits
+                                                        gives the mean of what is left
     On the device: hj_key_groups_dev gives the ids, hj_sort_rows_dev sorts by (id, order columns) -- with neither there is
-    no sort --, one hj_window_rows_dev per HJ_WIN_MAX_FUNCS functions scans along the permutation, hj_gather2_dev goes
-    through the row maps; the ids, the permutation and the maps never leave the device on the way. null_keys="drop": the
+    no sort --, one hj_window_rows_dev per HJ_WIN_MAX_FUNCS functions scans along the permutation, one hj_window_frames_dev
+    per HJ_FRAME_MAX_FUNCS framed functions goes along the same ids and permutation, hj_gather2_dev goes through the row
+    maps; the ids, the permutation and the maps never leave the device on the way. null_keys="drop": the
     rows with a NULL in a partition key stand at no position -- their numbers are 0, everything else is NULL.
     Returns the outputs and "perm" (the rows in partition and order, dropped rows left out), "n_partitions", "null_rows".
     An empty table is answered without a device."""
@@ -226,15 +275,19 @@ def window_rows(funcs, partition_by=None, order_by=None, cols=None, descending=F
 
         d_out = [held.put(np.full(n, f["fill"], dtype=f["dtype"])) if n_pos < n else held.alloc(n * f["dtype"].itemsize) for f in plan.funcs]
         n_partitions = 0
-        for k, part in enumerate(plan.rounds()):
+        for k, (framed, part) in enumerate(plan.rounds()):
             desc = []
             for i in part:
                 f = plan.funcs[i]
                 d_v, _, d_valid = column(f["src"]).parts if f["src"] is not None else (0, 0, 0)
-                desc.append((f["op"], d_out[i], d_v if f["op"] in _RUNS.values() else 0, d_valid, f["width"], f["flags"], f["offset"]))
-            ctx.window_rows(d_perm, n_pos, n, d_ids, order, desc)
+                ptrs = (d_v if plan.reads(i) else 0, d_valid, f["width"], f["flags"])
+                desc.append((f["op"], d_out[i]) + (f["frame"] + ptrs if framed else ptrs + (f["offset"],)))
+            if framed:
+                ctx.window_frames(d_perm, n_pos, n, d_ids, desc)
+            else:
+                ctx.window_rows(d_perm, n_pos, n, d_ids, order, desc)
             if k == 0:
-                n_partitions = ctx.window_rows_info()["partitions"]
+                n_partitions = (ctx.window_frames_info() if framed else ctx.window_rows_info())["partitions"]
         planes = [None] * len(plan.funcs)
         maps = {i for _, kind, i, *_ in plan.outputs if kind == "map"}
         for i, f in enumerate(plan.funcs):

@@ -816,6 +816,76 @@ int hj_window_rows_host(const uint32_t *perm, uint64_t nPos, uint64_t nRows, con
  * chunks (at most 4096 at any nPos: one workgroup scans their summaries), out[3] = workspace bytes (one head byte and one
  * 4-byte end per position, and the chunk summaries; monotone in nPos). HJ_ERR_INVALID for out NULL or nPos above 2^32 - 2. */
 int hj_window_layout_info(uint64_t nPos, uint64_t out[4]);
+/* ---- sliding window frames: f(x) OVER (PARTITION BY keys ORDER BY cols ROWS BETWEEN lo AND hi) ----
+ * hj_window_rows_dev knows one frame, UNBOUNDED PRECEDING to CURRENT ROW. hj_window_frames_dev computes COUNT / SUM / MIN /
+ * MAX over a frame of ROWS around every position: the 7-day moving sum (lo -6, hi 0), the rolling maximum of the last 100
+ * ticks, the centred window, a frame that leaves the current row out (lo -3, hi -1), and with both sides unbounded the
+ * partition's total next to every row (pandas' groupby().rolling(w) and groupby().transform()).
+ * Positions, rows, partitions and skipped entries are EXACTLY hj_window_rows_dev's: for position p in [0, nPos), row(p) =
+ * dPerm[p] (dPerm NULL: the identity, needs nPos <= nRows); the partition of p, [start, end], is the maximal run of in-range
+ * positions around p whose dPart[row] are equal (dPart NULL: one value); an entry that is HJ_NO_ROW or >= nRows is never
+ * dereferenced, writes nothing, is counted (info out[4]) and cuts the run. The call is exact for any dPerm. Peers play no
+ * part: there are no order columns.
+ * THE FRAME of position p is [max(start, p + lo), min(end, p + hi)]: lo and hi are signed offsets relative to p, lo <= hi,
+ * both in [-(2^32 - 1), 2^32 - 1]; (0, 0) is the element itself. HJ_FRAME_UNBOUNDED_LO / _HI put start / end in the place of
+ * that side, and its offset must be 0; both: the whole partition. p + lo and p + hi are formed in 64 bits: nothing wraps.
+ * A frame with L > R is empty.
+ * out[row(p)], 8 bytes per row: the op (an hj_agg_op) over the valid elements src[row(q)], q in the frame. Values, sign
+ * extension of 4-byte elements (HJ_AGG_SIGNED), wrap-around (SUM modulo 2^64) and the identity of an empty frame or of one
+ * without a valid element are hj_pairs_agg_dev's; COUNT counts the valid elements, or the positions when srcValid is NULL,
+ * and is 0 for an empty frame. There is no output validity: whether a SUM / MIN / MAX saw a value is COUNT of the same
+ * column and frame > 0. Integers only. A row that occurs at no position keeps the caller's bytes; a row at two positions
+ * keeps one of its two results.
+ * Method (hj_frames.hip): positions are cut into blocks of W = hi - lo + 1; one forward and one backward
+ * segmented scan whose segments end at the partition's AND the block's borders give G and H, and a frame, which touches
+ * at most two blocks, is op(H[L], G[R]) -- O(1) per position whatever W, for MIN and MAX too. Per function: one scattered
+ * read of src through dPerm into a position-indexed plane, two coalesced scans over it (one with an unbounded side), one
+ * coalesced combine with a scattered 8-byte store. No workgroup waits for another, no atomic, every loop bounded by the chunk.
+ * WORKSPACE (hj_frames_layout_info): one head byte, one 4-byte end and TWO 8-byte planes per position, which the functions
+ * of a call share one after another, plus the chunk summaries (192 KiB): 21 bytes per position, and never more than 32 bytes
+ * per position plus 1 MiB, whatever nFuncs. It belongs to the context, apart from hj_window_rows_dev's, and only grows: a
+ * call that needs more waits for the stream once.
+ * Asynchronous on the context's stream; nPos 0 enqueues nothing. Needs no hj_reserve, no table and no state; touches no
+ * counter and no other *_info. `funcs` is host memory and is read before the call returns. Outputs must not alias each
+ * other, dPerm, dPart or a column. Nothing is written outside out[0 .. nRows) of each function.
+ * HJ_ERR_INVALID (nothing is enqueued, nothing written; also for a NULL context): nFuncs 0 or above HJ_FRAME_MAX_FUNCS, funcs
+ * NULL; an op above HJ_AGG_MAX; a width the op does not have (SUM / MIN / MAX: 4 or 8; COUNT: 0, 4 or 8); flags other than
+ * HJ_AGG_SIGNED and the two HJ_FRAME_UNBOUNDED_*; reserved != 0; an offset outside [-(2^32 - 1), 2^32 - 1]; a non-zero offset
+ * beside its unbounded flag; lo > hi with both sides bounded; an out that is NULL or not 8-byte aligned; with nRows > 0 a
+ * src that is NULL or not aligned to its width where the op reads one (SUM / MIN / MAX); a srcValid that is not 4-byte
+ * aligned; dPerm NULL with nPos > nRows; dPerm or dPart not 4-byte aligned; nPos or nRows above 2^32 - 2. */
+#define HJ_FRAME_MAX_FUNCS 8
+#define HJ_FRAME_UNBOUNDED_LO 0x2u   /* hj_frame_func.flags: the frame starts at the partition's first position; lo must be 0 */
+#define HJ_FRAME_UNBOUNDED_HI 0x4u   /* ... ends at the partition's last position; hi must be 0                              */
+typedef struct {
+    const void     *src;       /* nRows elements of `width` bytes; COUNT: ignored (may be NULL)                 */
+    const uint32_t *srcValid;  /* NULL = no NULLs, else the plane hj_gather_dev writes                          */
+    void           *out;       /* nRows entries of 8 bytes INDEXED BY ROW                                       */
+    int64_t         lo;        /* the frame's first position relative to p (negative: preceding)                */
+    int64_t         hi;        /* the frame's last position relative to p                                       */
+    uint32_t        op;        /* hj_agg_op                                                                     */
+    uint32_t        width;     /* SUM / MIN / MAX: 4 or 8; COUNT: 0, 4 or 8                                     */
+    uint32_t        flags;     /* HJ_AGG_SIGNED | HJ_FRAME_UNBOUNDED_LO | HJ_FRAME_UNBOUNDED_HI                 */
+    uint32_t        reserved;  /* must be 0                                                                     */
+} hj_frame_func;               /* 56 bytes */
+int hj_window_frames_dev(hj_ctx *ctx, const uint32_t *dPerm, uint64_t nPos, uint64_t nRows, const uint32_t *dPart,
+                         const hj_frame_func *funcs, uint32_t nFuncs);
+/* Waits for the stream. About the last hj_window_frames_dev, in hj_window_rows_info's places: out[0] = positions, out[1] =
+ * partitions (runs of in-range positions; a skipped entry is none), out[2] = 0 (no peer runs), out[3] = the device time of
+ * the whole call in microseconds (rounded), out[4] = entries skipped as HJ_NO_ROW or out of range, out[5] = chunks, out[6] =
+ * workspace bytes the call needed, out[7] = 0. All 0 before the first call and after a call with nPos 0. */
+int hj_window_frames_info(hj_ctx *ctx, uint64_t out[8]);
+/* The same function on host pointers: no context, no device, and ANOTHER ALGORITHM on purpose -- one sequential loop per
+ * function, COUNT / SUM by a running window (add the entering element, subtract the leaving one, modulo 2^64), MIN / MAX by
+ * a monotonic deque; no blocks, no scans; O(nPos) per function whatever W. Twin and kernels are two independent computations
+ * of one definition. `out` (may be NULL) is filled as hj_window_frames_info fills it, out[3] = 0. HJ_ERR_INVALID as
+ * hj_window_frames_dev; a refused call writes nothing. */
+int hj_window_frames_host(const uint32_t *perm, uint64_t nPos, uint64_t nRows, const uint32_t *part,
+                          const hj_frame_func *funcs, uint32_t nFuncs, uint64_t out[8]);
+/* How a call cuts nPos positions; a pure function, no context and no device: out[0] = tile positions, out[1] = chunk
+ * positions (both hj_window_layout_info's), out[2] = chunks (at most 4096), out[3] = workspace bytes (monotone in nPos; at
+ * most 32 bytes per position plus 1 MiB). HJ_ERR_INVALID for out NULL or nPos above 2^32 - 2. */
+int hj_frames_layout_info(uint64_t nPos, uint64_t out[4]);
 /* ---- range joins without an equality key: ... ON R.y BETWEEN S.lo AND S.hi ----
  * Every join above starts from an equality on a join word. These two calls join on an ORDER condition alone: events
  * against sessions, packets against address blocks, readings against calibration periods, one bound (R.y < S.x), and the
